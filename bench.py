@@ -1,17 +1,24 @@
 #!/usr/bin/env python3
 """bench.py -- decode tokens/s (+ prefill tok/s) of the Qwen3-VL-8B hot path on MI355X, through the C ABI.
 
-  python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                           (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 A "step" is one greedy decode token (one pass of the decoder stack + lm_head over the paged KV cache) of the
 configuration BASELINE.json's metric is quoted on: Qwen3-VL-"7B" (= 8B) with one 1024x1024
 image + a 512-token prompt.  Weights are synthetic (random init of that architecture, bf16, built directly in HBM);
-inputs are synthetic and resident in HBM when the timed region starts.  Prefill is run once before the timed region
-and reported as prefill_tok_s.  Decode stays single-GPU (BASELINE.json north_star): with N > 1 every rank serves its
-own request (independent replicas, no data-path collective) => "scaling": "weak".
+inputs are synthetic, seeded (the same for every run with the same arguments) and resident in HBM when the timed region
+starts.  Decode stays single-GPU (BASELINE.json north_star): with N > 1 every rank serves its own request (independent
+replicas, no data-path collective) => "scaling": "weak".
 
-Extra objects on the JSON line: roofline (dominant kernel = the batch-1 weight-streaming matvec, HIP-event timed over
-K further steps) and cpu_baseline (the oracle restatement timed on the host cores on a bounded sample).
+A plain run does only what the headline figure needs: one prefill (it fills the cache the steps read), W warmup steps,
+the K timed steps, the JSON line.  --full adds everything else, each with runs of its own: the prefill timed (median of
+3) and reported as prefill_tok_s against the MFMA peak, roofline (dominant kernel = the batch-1 weight-streaming matvec,
+HIP-event timed over K further steps), cpu_baseline (the oracle restatement timed on the host cores on a bounded
+sample), the video patchify kernel, and with N > 1 the sharded cfg 5 prefill.
+
+--dump-outputs DIR writes what the timed steps computed, as rank 0's caller receives it: tokens.npy (the K greedy
+tokens, float64) and logits.npy (the f32 logits of the last timed step, aha_hip_last_logits).
 """
 from __future__ import annotations
 
@@ -490,8 +497,14 @@ def main():
     ap.add_argument("--sharded-order", default="tp,cp",
                     help="order of the sharded cfg 5 legs of a multi-rank run: tp = the tensor-parallel form BASELINE cfg 5 names, cp = context-parallel")
     ap.add_argument("--sharded-prefill", action="store_true",
-                    help="also run BASELINE cfg 5 through the TP + image-parallel path (always done when WORLD_SIZE > 1)")
+                    help="also run BASELINE cfg 5 through the TP + image-parallel path (done by --full when WORLD_SIZE > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure prefill, roofline, cpu_baseline, video patchify and (N > 1) the sharded cfg 5 prefill")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed steps' outputs (tokens.npy, logits.npy of the last step) to DIR")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # --gpus N without a launcher (the driver runs `python bench.py --gpus N ...`): start the N ranks ourselves, one process per
     # GPU, exactly as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` would.
@@ -576,16 +589,17 @@ def main():
         T, VH, VW = wl["video"]
         frames = torch.randint(0, 256, (T, VH, VW, 3), generator=g, dtype=torch.uint8).to(dev)
         pvv, vgrid = vision_host.process_videos([frames], cfg)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(20):
-            ops.video_to_patches(frames, cfg.vision.patch_size, cfg.vision.spatial_merge_size)
-        e1.record()
-        torch.cuda.synchronize()
-        video_patchify = {"us": round(e0.elapsed_time(e1) * 1e3 / 20, 2),
-                          "GBs": round((frames.numel() + pvv.numel() * 2) / (e0.elapsed_time(e1) * 1e-3 / 20) / 1e9, 1),
-                          "algorithmic_bytes": int(frames.numel() + pvv.numel() * 2)}
+        if args.full:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(20):
+                ops.video_to_patches(frames, cfg.vision.patch_size, cfg.vision.spatial_merge_size)
+            e1.record()
+            torch.cuda.synchronize()
+            video_patchify = {"us": round(e0.elapsed_time(e1) * 1e3 / 20, 2),
+                              "GBs": round((frames.numel() + pvv.numel() * 2) / (e0.elapsed_time(e1) * 1e-3 / 20) / 1e9, 1),
+                              "algorithmic_bytes": int(frames.numel() + pvv.numel() * 2)}
         hi = min(tcfg.vocab_size, 151643)
         stamps = [torch.randint(0, hi, (3,), generator=g).tolist() for _ in range(int(vgrid[:, 0].sum()))]
         ids = torch.randint(0, hi, (4,), generator=g).tolist() + vision_host.video_prompt_ids(cfg, vgrid, stamps) + \
@@ -609,59 +623,84 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- prefill (reported, outside the K timed steps) ----
-    model.forward_initial(ids, 0, data, want_logits=False)  # warm
+    # ---- prefill: fills the cache the decode steps read; timed (outside the K timed steps) only with --full ----
+    _, tok = model.forward_initial(ids, 0, data, want_logits=False)  # also the warm-up of the timed prefills
     t_prefills = []
-    for _ in range(3 if len(ids) < 16384 else 1):           # median of 3 (one sample for the 41k-token workloads: seconds each)
+    for _ in range((3 if len(ids) < 16384 else 1) if args.full else 0):   # median of 3 (one sample for the 41k-token workloads: seconds each)
         model.clear_cache()
         barrier()
         t0 = time.perf_counter()
         _, tok = model.forward_initial(ids, 0, data, want_logits=False)
         t_prefills.append(time.perf_counter() - t0)
-    t_prefill = sorted(t_prefills)[len(t_prefills) // 2]
     off = len(ids)
 
     # ---- decode: W warmup steps, then exactly K timed steps ----
     def run_steps(n, tok, off):
+        """n greedy steps from `tok` at cache offset `off` -> the n tokens."""
         if args.host_loop:
-            for _ in range(n):
-                _, tok = model.forward_step(tok, off, want_logits=False)
-                off += 1
-            return tok, off
+            out = []
+            for i in range(n):
+                _, tok = model.forward_step(tok, off + i, want_logits=False)
+                out.append(tok)
+            return out
         out = model.decode_greedy(tok, off, n)
         assert len(out) == n
-        return out[-1], off + n
+        return out
 
-    tok, off = run_steps(args.warmup, tok, off)
+    warm = run_steps(args.warmup, tok, off)
+    tok, off = (warm[-1] if warm else tok), off + args.warmup
     barrier()
     t0 = time.perf_counter()
-    tok, off = run_steps(args.steps, tok, off)
+    timed = run_steps(args.steps, tok, off)
     barrier()
     dt = time.perf_counter() - t0
+    tok, off = timed[-1], off + args.steps
     job_value, dt = parallel.aggregate_throughput(float(args.steps), dt, device=dev)  # sum of tokens / max over ranks
     kv_mid = off - args.steps // 2
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the greedy tokens and, from the last step, the logits (read before anything else runs)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "tokens.npy"), np.asarray(timed, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "logits.npy"), model.last_logits().astype(np.float32))
 
-    # ---- roofline of the dominant kernel (weight-streaming matvec), HIP events on the model's stream ----
-    model.set_profiling(True)
-    tok, off = run_steps(args.steps, tok, off)
-    prof = {k: model.get_profile(k) for k in ("gemv", "attn_decode", "elem", "argmax")}
-    model.set_profiling(False)
-    # dominant kernel class of a decode step: the weight-streaming matvec (all projections + lm_head)
-    gv = prof["gemv"]
-    achieved = gv["bytes"] / (gv["ms"] * 1e-3) / 1e9 if gv["ms"] > 0 else 0.0
-    roof = {"bound": "hbm",
-            "kernel": "gemv_kernel (batch-1 weight streaming, all projections + lm_head)",
-            "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-            "launches": gv["launches"], "avg_us": round(1e3 * gv["ms"] / max(gv["launches"], 1), 2),
-            "algorithmic_bytes_per_launch": round(gv["bytes"] / max(gv["launches"], 1)),
-            "timing": "HIP event pairs on the model's stream around every launch of the class, collected in THIS run (a pair also sees "
-                      "the ~2.5 us of dispatch latency in front of a kernel: the rocprofv3 kernel-only figure, when attached, is the higher one)"}
-    attach_committed_profiles(roof, args.workload)
-    ad = prof["attn_decode"]
-    attn_gbs = ad["bytes"] / (ad["ms"] * 1e-3) / 1e9 if ad["ms"] > 0 else 0.0
+    if args.full:
+        # ---- roofline of the dominant kernel (weight-streaming matvec), HIP events on the model's stream ----
+        model.set_profiling(True)
+        run_steps(args.steps, tok, off)
+        prof = {k: model.get_profile(k) for k in ("gemv", "attn_decode", "elem", "argmax")}
+        model.set_profiling(False)
+        # dominant kernel class of a decode step: the weight-streaming matvec (all projections + lm_head)
+        gv = prof["gemv"]
+        achieved = gv["bytes"] / (gv["ms"] * 1e-3) / 1e9 if gv["ms"] > 0 else 0.0
+        roof = {"bound": "hbm",
+                "kernel": "gemv_kernel (batch-1 weight streaming, all projections + lm_head)",
+                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
+                "launches": gv["launches"], "avg_us": round(1e3 * gv["ms"] / max(gv["launches"], 1), 2),
+                "algorithmic_bytes_per_launch": round(gv["bytes"] / max(gv["launches"], 1)),
+                "timing": "HIP event pairs on the model's stream around every launch of the class, collected in THIS run (a pair also sees "
+                          "the ~2.5 us of dispatch latency in front of a kernel: the rocprofv3 kernel-only figure, when attached, is the higher one)"}
+        attach_committed_profiles(roof, args.workload)
+        ad = prof["attn_decode"]
+        attn_gbs = ad["bytes"] / (ad["ms"] * 1e-3) / 1e9 if ad["ms"] > 0 else 0.0
 
+    line = None
     if rank == 0:
+        line = {
+            "metric": METRICS.get(args.workload, "decode tokens/s (greedy, batch 1) -- " + args.workload),
+            "value": round(job_value, 3), "unit": "tokens/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+            "config": {"workload": args.workload, "prompt_tokens": len(ids), "image": wl["image"],
+                       "kv_len_mid": kv_mid, "replicas": world, "collective_backend": ("gloo (ranks share a GPU)" if shared_device else "rccl") if world > 1 else None,
+                       "loop": "host forward_step" if args.host_loop else "device-resident greedy loop"},
+            "load_s": round(t_load, 1),
+        }
+        if wl.get("video"):
+            line["config"]["video_frames_hw"] = list(wl["video"])
+    if rank == 0 and args.full:
+        t_prefill = sorted(t_prefills)[len(t_prefills) // 2]
         # the other half of BASELINE's metric: the prefill against the dense bf16 MFMA peak (attention counted causally; stated)
         segs = []
         if data is not None and getattr(data, "image_grid_thw", None) is not None:
@@ -677,25 +716,15 @@ def main():
                                     "lm_head for the last position only; element-wise work not counted; whole prefill wall clock (ViT + "
                                     "36 layers + lm_head + host-side position / page bookkeeping) in the denominator"}
         step_bytes = decode_bytes_per_token(cfg, kv_mid)
-        line = {
-            "metric": METRICS.get(args.workload, "decode tokens/s (greedy, batch 1) -- " + args.workload),
-            "value": round(job_value, 3), "unit": "tokens/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": args.workload, "prompt_tokens": len(ids), "image": wl["image"],
-                       "kv_len_mid": kv_mid, "replicas": world, "collective_backend": ("gloo (ranks share a GPU)" if shared_device else "rccl") if world > 1 else None,
-                       "loop": "host forward_step" if args.host_loop else "device-resident greedy loop"},
+        line.update({
             "prefill_tok_s": round(len(ids) / t_prefill, 1), "prefill_ms": round(1e3 * t_prefill, 2),
             "roofline_prefill": roof_prefill,
             "prefill_ms_samples": [round(1e3 * t, 2) for t in t_prefills],
             "decode_step_hbm_frac": round(step_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
             "attn_decode_GBs": round(attn_gbs, 1),
-            "load_s": round(t_load, 1),
             "roofline": roof,
-        }
+        })
         if wl.get("video"):
-            line["config"]["video_frames_hw"] = list(wl["video"])
             line["video_to_patches"] = video_patchify
         if not args.no_cpu_baseline and world == 1:          # rank 0 at N = 1 only (torchrun also pins its ranks to one OMP thread)
             vit_n = sum(segs) if is_vl else 0
@@ -703,9 +732,9 @@ def main():
     model.close()
     torch.cuda.empty_cache()
     # The part of the path that SHARDS (north_star: long-context prefill + ViT over the node's GPUs): measured next to the
-    # replica decode number whenever there is more than one rank, so a scaling run of this command covers both.
+    # replica decode number by --full whenever there is more than one rank, so a full scaling run of this command covers both.
     clean = True
-    if (world > 1 or args.sharded_prefill) and args.workload == "qwen3vl8b" and not shared_device:
+    if (world > 1 and args.full or args.sharded_prefill) and args.workload == "qwen3vl8b" and not shared_device:
         # These legs have never run on more than one GPU (no multi-GPU box in the build loop): the replica decode numbers above must reach
         # the driver whatever happens in them (run_sharded_legs: an exception becomes an "error" entry and the NEXT leg still runs; a hang
         # is ended by a watchdog on every rank).

@@ -4,12 +4,13 @@ FETCH_SIZE is doubled (MI355X_MICROARCH.md, HBM section).  Per launch = sum over
 import csv, glob, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROUND = os.environ.get("ROUND", "r06")
+OUT = os.path.abspath(os.environ.get("OUT", os.path.join(ROOT, "out")))   # = scripts/collect_pmc.sh's
 
 
 def load(counter):
-    files = glob.glob(os.path.join(ROOT, "gpurun_out", f"pmc_{counter}", "**", "*counter_collection.csv"), recursive=True)
+    files = glob.glob(os.path.join(OUT, f"pmc_{counter}", "**", "*counter_collection.csv"), recursive=True)
     if not files:
-        sys.exit(f"no counter_collection.csv under gpurun_out/pmc_{counter}")
+        sys.exit(f"no counter_collection.csv under {OUT}/pmc_{counter}")
     per = {}
     for f in files:
         for r in csv.DictReader(open(f)):

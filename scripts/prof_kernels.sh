@@ -1,9 +1,11 @@
 #!/bin/bash
 # usage: scripts/prof_kernels.sh <name> <python script + args...>   (run on the GPU box through gpurun)
-# rocprofv3 --kernel-trace --stats of the command; prints the top kernels and leaves the csv under gpurun_out/prof_<name>/
+# rocprofv3 --kernel-trace --stats of the command; prints the top kernels and leaves the csv under $OUT/prof_<name>/ (emptied first;
+# OUT defaults to out/ in the repository)
 name=$1; shift
 root=${GRAFT_REPO_ROOT:-$(pwd)}
-out=$root/gpurun_out/prof_$name
+out=$(realpath -m "${OUT:-$root/out}")/prof_$name
+rm -rf $out
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 script=$1; shift; case $script in /*) ;; *) script=$root/$script;; esac

@@ -81,6 +81,14 @@ def test_bench_gpus_2_self_launches_two_ranks_over_gloo():
     assert abs(j["value"] - 2 * 10 / 0.75) < 1e-3 and abs(j["ms_per_step"] - 75.0) < 1e-6   # both ranks' units / the slower rank's 0.75 s
 
 
+def test_bench_refuses_zero_steps():
+    """ms_per_step is the timed seconds over --steps: a run without timed steps has no figure to report."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--workload", "launcher-selftest"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
 def test_bench_rejects_a_world_size_that_contradicts_gpus():
     import subprocess
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
