@@ -657,6 +657,16 @@ int aha_hip_embed(aha_model* m, const uint32_t* input_ids, size_t n_ids, float* 
   return model_embed(m, input_ids, n_ids, out);
   API_GUARD_END
 }
+int aha_hip_embed_batch(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_tokens_per_pass,
+                        float* out) {
+  API_GUARD_BEGIN
+  if (!m) {
+    set_error("null model");
+    return AHA_ERR_INVALID;
+  }
+  return model_embed_batch(m, input_ids, seq_lens, n_seqs, max_tokens_per_pass, out);
+  API_GUARD_END
+}
 int aha_hip_config_parse(const char* model_dir, aha_model_desc* out) {
   API_GUARD_BEGIN
   if (!model_dir || !out) {

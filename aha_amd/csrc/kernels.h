@@ -56,6 +56,9 @@ void launch_topk_candidates(const float* x, int V, int k, float inv_temp, float*
 void launch_embed_gather(const void* table, const uint32_t* ids, void* out, int S, int H, hipStream_t st);
 void launch_rmsnorm_rows(const void* x, const void* w, void* y, int64_t rows, int dim, int64_t ldx, int64_t ldy,
                          float eps, hipStream_t st);
+// Packed multi-sequence embedding (model_embed_batch): for every segment {row0, len, page0} of seg_tab, the last row x[row0 + len - 1]
+// -> final RMSNorm (rmsnorm_rows_kernel's arithmetic, bf16 result) -> f32 -> x / sqrt(sum x^2 + 1e-6) -> out[segment] (dim floats)
+void launch_embed_pool(const void* x, const int32_t* seg_tab, int n_segs, const void* w, float* out, int dim, float eps, hipStream_t st);
 
 struct RopeArgs {
   const void* qkv;      // (S, ld) bf16: [q heads | k heads | v heads] per token
@@ -77,6 +80,11 @@ struct RopeArgs {
   int kv_start_host = -1;   // the same value as *kv_start when the caller knows it on the host (prefill): selects the row-vectorised kernel
   const void* rope_tab = nullptr;  // optional (S, 128) bf16: cos[64] | sin[64] of every token's angles (launch_rope_table), else computed in place
   int skip_q = 0;           // row-vectorised prefill kernel only: the q heads are normed and rotated by the attention kernel's Q load (AttnPrefillArgs::q_norm_w); K and V only here
+  // Packed independent sequences (row-vectorised kernel only; model_embed_batch): row r's K / V go to cache slot row_slot[r] instead of
+  // kv_start_host + r, and page p of 0 .. n_pages-1 takes its V rows from page_rows[2p] .. + page_rows[2p + 1] (its first packed row, row count)
+  const int32_t* row_slot = nullptr;
+  const int32_t* page_rows = nullptr;
+  int n_pages = 0;
 };
 void launch_qknorm_rope(const RopeArgs& a, hipStream_t st);
 // cos / sin of pos[axis(i)] * inv_freq[i], rounded to bf16 as apply_rotary_pos_emb casts them (rope.rs:96-132): computed ONCE per
@@ -152,6 +160,13 @@ struct AttnPrefillArgs {
   const void* q_norm_w = nullptr;
   const void* q_rope_tab = nullptr;
   float q_eps = 0.f;
+  // Packed independent causal sequences (model_embed_batch; the 16-rows-per-wave kernel, 4 waves): seg_tab = (segments, 3) int32
+  // {row0, len, page0} on the device -- segment j is q / o rows row0 .. row0 + len - 1 and its cache positions 0 .. len - 1 live on pages
+  // page0, page0 + 1, ... of kv.page_ptrs; seg_items = (n_items, 2) int32 {segment, 64-row q block}, most expensive first.  One block per
+  // (item, head); S = the packed rows, kv_offset / kv_total / S2 unused.
+  const int32_t* seg_tab = nullptr;
+  const int32_t* seg_items = nullptr;
+  int n_items = 0;
 };
 void launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t st);
 bool attn_prefill_takes_qfuse(const AttnPrefillArgs& a);   // would launch_attn_prefill run a kernel that norms + rotates Q itself for these arguments?

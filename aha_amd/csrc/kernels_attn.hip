@@ -58,8 +58,26 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu((NWV =
   // Two causal segments in one launch (a.S2 > 0: a context-parallel rank's early and late chunk, csrc/model.hip): q / o rows
   // [0, S) see the cache through kv_offset, rows [S, S + S2) through kv_offset2; a block belongs to ONE segment, the late segment's
   // (longer) blocks go first and the early segment's fill the tail of the late one's last round.
-  int head, qblk, seg_rows = a.S, seg_off = a.kv_offset, seg_tot = a.kv_total, seg_row0 = 0;
-  if (a.nqb > 0) {
+  // Packed independent sequences (a.seg_tab: model_embed_batch): the block's (segment, q block) is item `it` of the host-sorted list (most
+  // expensive first) in either order; the segment's rows see only its own pages (page0 on), causally from its first token.
+  int head, qblk, seg_rows = a.S, seg_off = a.kv_offset, seg_tot = a.kv_total, seg_row0 = 0, page0 = 0;
+  if (a.seg_tab != nullptr) {
+    int it;
+    if (a.nqb > 0) {
+      const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+      const int g = a.nh / a.kvh, hpx = a.nh >> 3;
+      const int hq = slot % hpx;
+      head = (xcd + 8 * (hq / g)) * g + hq % g;
+      it = slot / hpx;
+    } else {
+      head = blockIdx.x % a.nh;
+      it = blockIdx.x / a.nh;
+    }
+    const int sg = a.seg_items[2 * it];
+    qblk = a.seg_items[2 * it + 1];
+    seg_row0 = a.seg_tab[3 * sg], seg_rows = a.seg_tab[3 * sg + 1], page0 = a.seg_tab[3 * sg + 2];
+    seg_off = 0, seg_tot = seg_rows;
+  } else if (a.nqb > 0) {
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int g = a.nh / a.kvh, hpx = a.nh >> 3;  // q heads per kv head / q heads per XCD
     const int hq = slot % hpx, qi = slot / hpx;
@@ -212,7 +230,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu((NWV =
   // the page table is read through the constant address space with a wave-uniform index: a scalar load (s_load_dwordx2), no
   // vector-memory request and no VGPRs for the address of the next page
   typedef const __attribute__((address_space(4))) uint64_t* cptr64_t;
-  const cptr64_t ptab = (cptr64_t)(uintptr_t)a.kv.page_ptrs;
+  const cptr64_t ptab = (cptr64_t)(uintptr_t)(a.kv.page_ptrs + page0);
   gload(ptab[0], 0);
   // Everything requested so far (the q fragments above all) is retired here, once: otherwise the waits the compiler places in
   // the loop must assume the q loads may still be the newest requests (on the path that issues no prefetch) and turn into
@@ -574,7 +592,7 @@ static int attn_prefill_form(const AttnPrefillArgs& a, int smx) {
   // unset = automatic: form 65 (f32 chain only) once its 256-row blocks fill the chip.
   static const int form_env = [] { const char* e = getenv("AHA_ATTN_FORM"); return e ? atoi(e) : -1; }();
   const int form = g_attn_form_override >= 0 ? g_attn_form_override : form_env;
-  if (smx != 3 || form == 16) return 0;
+  if (smx != 3 || form == 16 || a.seg_tab) return 0;   // (packed sequences: this file's kernel only)
   const int64_t blocks64 = (a.rows_hint > 0 ? (int64_t)(a.rows_hint + 255) / 256 : (int64_t)((a.S + 255) / 256 + (a.S2 + 255) / 256)) * a.nh;
   // One 4-wave workgroup per CU: a full launch is rounds of 256 workgroups.  Same-box A/B against the 16-row kernel (scripts/attn64_ab.py,
   // 32 heads x head_dim 128, profiles/r06_attn_prefill.md): full attention 2048 / 3072 / 4096 / 8192 rows = 1 / 1.5 / 2 / 4 rounds:
@@ -604,6 +622,7 @@ void launch_attn_prefill(const AttnPrefillArgs& a_in, hipStream_t st) {
   // that, 64-row blocks balance a causal launch better (S = 1542 x 32 heads: 44 vs 48 us; equal at 2048, 8 waves ahead from there)
   int nwv = (a.d != 64 && (int64_t)((a.S + 127) / 128 + (a.S2 + 127) / 128) * a.nh >= 512) ? 8 : 4;
   if (nw_env == 4 || (nw_env == 8 && a.d != 64)) nwv = nw_env;
+  if (a.seg_tab) nwv = 4;   // packed sequences: the host's items are 64-row q blocks
   static const int sched_env = [] {
     const char* e = getenv("AHA_ATTN_SCHED");
     return e ? atoi(e) : 1;
@@ -625,6 +644,10 @@ void launch_attn_prefill(const AttnPrefillArgs& a_in, hipStream_t st) {
   const int nqb = (a.S + 16 * qt * nwv - 1) / (16 * qt * nwv) + (a.S2 + 16 * qt * nwv - 1) / (16 * qt * nwv);
   a.nqb = xcd_order ? nqb : 0;
   dim3 grid = a.nqb ? dim3(nqb * a.nh) : dim3(nqb, a.nh), block(nwv * 64);
+  if (a.seg_tab) {   // one block per (item, head): XCD-aware 1-D order, or heads fastest so that the costly items go out first
+    a.nqb = xcd_order ? a.n_items : 0;
+    grid = dim3(a.n_items * a.nh);
+  }
   // AHA_ATTN_SMX: the score chain.
   //   3 (default since round 5) = the f32 score chain: the scores stay the f32 QK^T accumulators through scale, mask, maximum and
   //       exponential; P is rounded to bf16 once for the P.V MFMA (attn_common.h softmax_scores<3>)

@@ -85,6 +85,76 @@ void launch_rmsnorm_rows(const void* x, const void* w, void* y, int64_t rows, in
 #undef RMS_CASE
 }
 
+// ---- packed-batch embedding pooling (Qwen3Embedding::embed_one per sequence, qwen3_embedding/mod.rs:50-64) -------------------------
+// One wave per sequence: its last packed row -> the final RMSNorm with rmsnorm_rows_kernel's arithmetic (the same bf16 row forward_hidden
+// normalises, qwen3/model.rs:186-188) -> f32 -> l2_normalize (common/modules.rs:1287-1294: x / sqrt(sum x^2 + 1e-6)) -> out row, f32.
+template <int VPL>
+__global__ __launch_bounds__(256) void embed_pool_kernel(const bf16_t* __restrict__ x, const int32_t* __restrict__ seg_tab, int n_segs,
+                                                         const bf16_t* __restrict__ w, float* __restrict__ out, int dim, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int seg = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (seg >= n_segs) return;
+  const bf16_t* xr = x + (int64_t)(seg_tab[3 * seg] + seg_tab[3 * seg + 1] - 1) * dim;
+  float* outr = out + (int64_t)seg * dim;
+  const int nvec = dim / 8;
+  u32x4_t v[VPL];
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const int vi = i * 64 + lane;
+    if (vi < nvec) {
+      v[i] = ld16(xr + vi * 8);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float a = lo_bf(v[i][j]), b = hi_bf(v[i][j]);
+        float t = fmaf(a, a, b * b);
+        asm volatile("" : "+v"(t));   // four scalar adds in order, as in rmsnorm_rows_kernel
+        ss += t;
+      }
+    }
+  }
+  ss = wave_sum(ss);
+  const float rinv = 1.0f / sqrtf(ss / (float)dim + eps);
+  float s2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const int vi = i * 64 + lane;
+    if (vi < nvec) {
+      const u32x4_t wv = ld16(w + vi * 8);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        v[i][j] = pack_bf(lo_bf(v[i][j]) * rinv * lo_bf(wv[j]), hi_bf(v[i][j]) * rinv * hi_bf(wv[j]));   // the normed bf16 row
+        float t = fmaf(lo_bf(v[i][j]), lo_bf(v[i][j]), hi_bf(v[i][j]) * hi_bf(v[i][j]));
+        asm volatile("" : "+v"(t));
+        s2 += t;
+      }
+    }
+  }
+  const float nrm = sqrtf(wave_sum(s2) + 1e-6f);
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const int vi = i * 64 + lane;
+    if (vi < nvec) {
+      float4* dst = reinterpret_cast<float4*>(outr + vi * 8);
+      dst[0] = make_float4(lo_bf(v[i][0]) / nrm, hi_bf(v[i][0]) / nrm, lo_bf(v[i][1]) / nrm, hi_bf(v[i][1]) / nrm);
+      dst[1] = make_float4(lo_bf(v[i][2]) / nrm, hi_bf(v[i][2]) / nrm, lo_bf(v[i][3]) / nrm, hi_bf(v[i][3]) / nrm);
+    }
+  }
+}
+void launch_embed_pool(const void* x, const int32_t* seg_tab, int n_segs, const void* w, float* out, int dim, float eps, hipStream_t st) {
+  if (n_segs <= 0) return;
+  dim3 grid((unsigned)((n_segs + 3) / 4)), block(256);
+  const int vpl = (dim / 8 + 63) / 64;
+#define POOL_CASE(V) hipLaunchKernelGGL(embed_pool_kernel<V>, grid, block, 0, st, (const bf16_t*)x, seg_tab, n_segs, (const bf16_t*)w, out, dim, eps)
+  if (vpl <= 1) POOL_CASE(1);
+  else if (vpl <= 2) POOL_CASE(2);
+  else if (vpl <= 4) POOL_CASE(4);
+  else if (vpl <= 8) POOL_CASE(8);
+  else if (vpl <= 10) POOL_CASE(10);
+  else POOL_CASE(16);
+#undef POOL_CASE
+}
+
 // ---- D4/D5/D6/M1: per-head q/k RMSNorm + rotary embedding + KV append ----------------------------------------
 // QKNormAttention::forward (/root/reference/src/models/common/modules.rs:530-566): q_norm/k_norm over head_dim,
 // apply_rotary_pos_emb (/root/reference/src/position_embed/rope.rs:96-132) with the half-split rotate_half
@@ -227,7 +297,7 @@ __global__ __launch_bounds__(256) void qknorm_rope_rows_kernel(RopeArgs a, int n
     }
     const bf16_t* row = (const bf16_t*)a.qkv + (int64_t)tokc * a.ld + sub * 8;
     const int slot0 = first + chunk * ROPE_ROWS_CHUNK, slot1 = min(nqk, slot0 + ROPE_ROWS_CHUNK);
-    const int ctok = a.kv_start_host + tokc;
+    const int ctok = a.row_slot ? a.row_slot[tokc] : a.kv_start_host + tokc;
     const int page = ctok / KV_PAGE_TOKENS, t = ctok % KV_PAGE_TOKENS;
     char* kbase = reinterpret_cast<char*>(a.kv.page_ptrs[page] + a.kv.layer_off);
     const bool hi_half = sub >= 8;
@@ -283,9 +353,21 @@ __global__ __launch_bounds__(256) void qknorm_rope_rows_kernel(RopeArgs a, int n
   // ---- role B: V rows, 128 lanes per (page of this call, kv head) ----
   const int64_t u = ((int64_t)(bid - n_qk_blocks) * 256 + threadIdx.x);
   const int unit = (int)(u >> 7), lu = (int)(u & 127);
-  const int p0 = a.kv_start_host / KV_PAGE_TOKENS, p1 = (a.kv_start_host + a.S - 1) / KV_PAGE_TOKENS;
-  const int page = p0 + unit / a.kvh, h = unit % a.kvh;
-  if (page > p1) return;
+  // the page's slot t holds packed row rbase + t, valid for rows [rlo, rhi): one sequence from kv_start_host on, or (row_slot) the rows
+  // page_rows names for this page of one of several packed sequences
+  int page, rbase, rlo = 0, rhi = a.S;
+  const int h = unit % a.kvh;
+  if (a.row_slot) {
+    page = unit / a.kvh;
+    if (page >= a.n_pages) return;
+    rbase = rlo = a.page_rows[2 * page];
+    rhi = rlo + a.page_rows[2 * page + 1];
+  } else {
+    const int p0 = a.kv_start_host / KV_PAGE_TOKENS, p1 = (a.kv_start_host + a.S - 1) / KV_PAGE_TOKENS;
+    page = p0 + unit / a.kvh;
+    if (page > p1) return;
+    rbase = page * KV_PAGE_TOKENS - a.kv_start_host;
+  }
   const int kk = lu >> 6, G = (lu >> 4) & 3, dchunk = lu & 15;
   uint32_t in[8][4];
   bool ok[8];
@@ -293,10 +375,10 @@ __global__ __launch_bounds__(256) void qknorm_rope_rows_kernel(RopeArgs a, int n
 #pragma unroll
   for (int e = 0; e < 8; ++e) {   // slot order inside the piece: e = sub1 * 4 + j  <->  token kk*32 + sub1*16 + G*4 + j
     const int tokp = kk * 32 + (e >> 2) * 16 + G * 4 + (e & 3);
-    const int srow = page * KV_PAGE_TOKENS + tokp - a.kv_start_host;
-    ok[e] = srow >= 0 && srow < a.S;
+    const int srow = rbase + tokp;
+    ok[e] = srow >= rlo && srow < rhi;
     all &= ok[e];
-    const u32x4_t v = ld16((const bf16_t*)a.qkv + (int64_t)min(max(srow, 0), a.S - 1) * a.ld + (int64_t)(a.nh + a.kvh + h) * 128 + dchunk * 8);
+    const u32x4_t v = ld16((const bf16_t*)a.qkv + (int64_t)min(max(srow, rlo), rhi - 1) * a.ld + (int64_t)(a.nh + a.kvh + h) * 128 + dchunk * 8);
     in[e][0] = v[0]; in[e][1] = v[1]; in[e][2] = v[2]; in[e][3] = v[3];
   }
   bf16_t* vb = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(a.kv.page_ptrs[page] + a.kv.layer_off)) +
@@ -338,7 +420,7 @@ void launch_rope_table(const int32_t* pos, int64_t pos_ld, const float* inv_freq
 
 void launch_qknorm_rope(const RopeArgs& a, hipStream_t st) {
   static const bool rows_on = [] { const char* e = getenv("AHA_ROPE_ROWS"); return e ? atoi(e) != 0 : true; }();
-  if (rows_on && a.kv_start_host >= 0 && a.kv.page_ptrs != nullptr && a.d == 128 && a.S >= 16) {
+  if (a.row_slot || (rows_on && a.kv_start_host >= 0 && a.kv.page_ptrs != nullptr && a.d == 128 && a.S >= 16)) {   // (row_slot: this kernel only)
     static const int chunk_env = [] { const char* e = getenv("AHA_ROPE_CHUNK"); return e ? atoi(e) : 8; }();
     // K heads only (skip_q): two heads per wave -- eight would leave S / 4 waves walking all kv heads one after the other (cfg 3: 386 waves on
     // 1024 SIMDs, ~3.7 us of dependent vector work each)
@@ -347,7 +429,7 @@ void launch_qknorm_rope(const RopeArgs& a, hipStream_t st) {
     const int nqk = (a.skip_q ? 0 : a.nh) + a.kvh, nchunk = (nqk + chunk - 1) / chunk;
     const int64_t qk_waves = (int64_t)((a.S + 3) / 4) * nchunk;
     const int n_qk_blocks = (int)((qk_waves + 3) / 4);
-    const int npages = (a.kv_start_host + a.S - 1) / KV_PAGE_TOKENS - a.kv_start_host / KV_PAGE_TOKENS + 1;
+    const int npages = a.row_slot ? a.n_pages : (a.kv_start_host + a.S - 1) / KV_PAGE_TOKENS - a.kv_start_host / KV_PAGE_TOKENS + 1;
     const int n_v_blocks = (npages * a.kvh * 128 + 255) / 256;
     const dim3 grid((unsigned)(n_qk_blocks + n_v_blocks));
     if (chunk == 2) hipLaunchKernelGGL(qknorm_rope_rows_kernel<2>, grid, dim3(256), 0, st, a, n_qk_blocks);

@@ -174,6 +174,13 @@ struct aha_model {
   size_t gemm_ws_bytes = 0;
   void* d_sk_ctrs = nullptr;    // SK_MAX_COUNTERS zeroed u32: per-tile arrival counters of the persistent GEMM kernel (kernels_gemm_sk.hip)
   std::vector<void*> pf_owned;
+  // packed-batch embedding (model_embed_batch): the per-pass int32 tables and the (sequences, hidden) f32 output, grown on demand
+  int32_t* p_seg = nullptr;
+  size_t p_seg_cap = 0;
+  float* p_pool = nullptr;
+  size_t p_pool_cap = 0;
+  int32_t* h_embed_stage = nullptr;   // pinned: a pass's ids | positions | tables on their way up
+  size_t h_embed_stage_cap = 0;
   // vision tower (Qwen3-VL)
   aha::VisionModel* vision = nullptr;
   // audio tower (Qwen3-ASR)
@@ -193,6 +200,7 @@ namespace aha {
 int model_create(aha_ctx* ctx, const aha_model_desc* desc, const aha_tensor_view* w, size_t nw, aha_model** out);
 void model_destroy(aha_model* m);
 int model_embed(aha_model* m, const uint32_t* ids, size_t n, float* out);
+int model_embed_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_tokens_per_pass, float* out);
 int model_forward_initial(aha_model* m, const uint32_t* ids, size_t n, size_t offset, const aha_mm_input* mm,
                           float* logits_out, uint32_t* argmax_out);
 int model_forward_step(aha_model* m, uint32_t token, size_t offset, float* logits_out, uint32_t* argmax_out);

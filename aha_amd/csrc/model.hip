@@ -766,6 +766,9 @@ void model_destroy(aha_model* m) {
   tp_destroy(m);
   for (void* p : m->owned) hipFree(p);
   for (void* p : m->pf_owned) hipFree(p);
+  if (m->p_seg) hipFree(m->p_seg);
+  if (m->p_pool) hipFree(m->p_pool);
+  if (m->h_embed_stage) hipHostFree(m->h_embed_stage);
   for (void* p : m->slabs) hipFree(p);
   if (m->d_page_ptrs) hipFree(m->d_page_ptrs);
   if (m->h_state) hipHostFree(m->h_state);
@@ -1863,6 +1866,229 @@ static int forward_initial_impl(aha_model* m, const uint32_t* ids, size_t n, siz
   rc = fetch_outputs(m, logits_out, argmax_out);
   pstamp("outputs fetched (GPU done)");
   return rc;
+}
+
+// ---- packed-batch embedding -----------------------------------------------------------------------------------------------
+// model_embed for many texts at once: the reference embeds one text at a time (qwen3_embedding/mod.rs:38-64), and so does this per
+// sequence -- positions 0 .. len-1, a cache window of its own from a fresh 64-token page, causal attention inside it -- but the texts of
+// a pass run as ONE packed prefill.  Every GEMM, norm and activation is row-wise and needs no change; the q/k-norm + RoPE kernel puts row r's
+// K / V at cache slot row_slot[r], the 16-row attention kernel runs one block per (sequence, q block, head) over the sequence's own pages
+// (AttnPrefillArgs::seg_tab), and embed_pool_kernel normalises every sequence's last row straight into the f32 output.
+// Passes: sequences in order while the pass stays within max_tokens_per_pass rows (0: EMBED_PASS_ROWS) and twice that many cache slots
+// (short texts waste up to a page each); a pass always holds at least one whole sequence.
+constexpr size_t EMBED_PASS_ROWS = 16384;
+
+static int embed_pass(aha_model* m, const uint32_t* ids, const size_t* lens, int n_seg, float* out) {
+  const aha_model_desc& c = m->desc;
+  const int H = c.hidden_size, I = c.intermediate_size, d = c.head_dim, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
+  const int nq = nh * d, nkv = kvh * d;
+  hipStream_t st = m->stream;
+  // host plan: segment table {row0, len, page0}, (segment, q block) items most expensive first, per-row cache slots, per-page rows
+  std::vector<int32_t> seg(3 * (size_t)n_seg);
+  int S = 0, npages = 0;
+  for (int j = 0; j < n_seg; ++j) {
+    const int len = (int)lens[j];
+    seg[3 * j] = S, seg[3 * j + 1] = len, seg[3 * j + 2] = npages;
+    S += len;
+    npages += (len + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
+  }
+  constexpr int QB = 64;   // q rows per attention block (launch_attn_prefill: 4 waves with seg_tab)
+  std::vector<std::pair<int, int>> items;
+  for (int j = 0; j < n_seg; ++j)
+    for (int b = 0; b * QB < seg[3 * j + 1]; ++b) items.emplace_back(j, b);
+  // cost of a block ~ the keys its last row sees
+  auto cost = [&](const std::pair<int, int>& it) { return std::min(seg[3 * it.first + 1], (it.second + 1) * QB); };
+  std::stable_sort(items.begin(), items.end(), [&](const auto& x, const auto& y) { return cost(x) > cost(y); });
+  const int n_items = (int)items.size();
+  const size_t o_seg = 0, o_items = o_seg + seg.size(), o_slot = o_items + 2 * (size_t)n_items, o_prow = o_slot + S,
+               n_tab = o_prow + 2 * (size_t)npages;
+  std::vector<int32_t> tab(n_tab);
+  std::copy(seg.begin(), seg.end(), tab.begin());
+  for (int i = 0; i < n_items; ++i) tab[o_items + 2 * i] = items[i].first, tab[o_items + 2 * i + 1] = items[i].second;
+  std::vector<int32_t> pos(3 * (size_t)S);
+  for (int j = 0; j < n_seg; ++j) {
+    const int r0 = seg[3 * j], len = seg[3 * j + 1], p0 = seg[3 * j + 2];
+    for (int i = 0; i < len; ++i) {
+      tab[o_slot + r0 + i] = p0 * KV_PAGE_TOKENS + i;
+      for (int a = 0; a < 3; ++a) pos[(size_t)a * S + r0 + i] = i;
+    }
+    for (int p = 0; p * KV_PAGE_TOKENS < len; ++p) {
+      tab[o_prow + 2 * (size_t)(p0 + p)] = r0 + p * KV_PAGE_TOKENS;
+      tab[o_prow + 2 * (size_t)(p0 + p) + 1] = std::min(KV_PAGE_TOKENS, len - p * KV_PAGE_TOKENS);
+    }
+  }
+  int rc;
+  if ((rc = ensure_prefill_scratch(m, (size_t)S))) return rc;
+  if ((size_t)S > m->pf_cap) {
+    set_error("embed_batch: prefill scratch of " + std::to_string(m->pf_cap) + " rows for a pass of " + std::to_string(S));
+    return AHA_ERR_STATE;
+  }
+  if ((rc = model_ensure_pages(m, (size_t)npages * KV_PAGE_TOKENS))) return rc;
+  auto grow = [&](auto** buf, size_t* cap, size_t n) -> int {
+    if (n <= *cap) return AHA_OK;
+    AHA_HIP_CHECK(hipStreamSynchronize(st));
+    if (*buf) AHA_HIP_CHECK(hipFree(*buf));
+    *buf = nullptr;
+    *cap = 0;
+    const size_t want = std::max(n, (size_t)4096);
+    hipError_t e = hipMalloc((void**)buf, want * sizeof(**buf));
+    if (e != hipSuccess) {
+      set_error(std::string("embed_batch: hipMalloc failed: ") + hipGetErrorString(e));
+      return e == hipErrorOutOfMemory ? AHA_ERR_OOM : AHA_ERR_HIP;
+    }
+    *cap = want;
+    return AHA_OK;
+  };
+  if ((rc = grow(&m->p_seg, &m->p_seg_cap, n_tab))) return rc;
+  if ((rc = grow(&m->p_pool, &m->p_pool_cap, (size_t)n_seg * H))) return rc;
+  // ids | positions | tables through one pinned staging buffer (the previous pass's copies have landed: it ended in a synchronise)
+  const size_t n_stage = 4 * (size_t)S + n_tab;
+  if (n_stage > m->h_embed_stage_cap) {
+    if (m->h_embed_stage) AHA_HIP_CHECK(hipHostFree(m->h_embed_stage));
+    m->h_embed_stage = nullptr;
+    m->h_embed_stage_cap = 0;
+    AHA_HIP_CHECK(hipHostMalloc((void**)&m->h_embed_stage, n_stage * 4));
+    m->h_embed_stage_cap = n_stage;
+  }
+  int32_t* hs = m->h_embed_stage;
+  memcpy(hs, ids, (size_t)S * 4);
+  memcpy(hs + S, pos.data(), pos.size() * 4);
+  memcpy(hs + 4 * (size_t)S, tab.data(), n_tab * 4);
+  GemmWorkspaceScope ws_scope(m->p_gemm_ws, m->gemm_ws_bytes, m->d_sk_ctrs);
+  AHA_HIP_CHECK(hipMemcpyAsync(m->p_ids, hs, (size_t)S * 4, hipMemcpyHostToDevice, st));
+  AHA_HIP_CHECK(hipMemcpyAsync(m->p_pos, hs + S, pos.size() * 4, hipMemcpyHostToDevice, st));
+  AHA_HIP_CHECK(hipMemcpyAsync(m->p_seg, hs + 4 * (size_t)S, n_tab * 4, hipMemcpyHostToDevice, st));
+  const int32_t* d_seg = m->p_seg + o_seg;
+  {
+    ProfScope ps(m, "elem", (double)S * H * 4, 0);
+    launch_embed_gather(m->embed, m->p_ids, m->p_x, S, H, st);
+  }
+  launch_rope_table(m->p_pos, S, m->d_inv_freq, m->d_axis_map, S, m->p_rope, st);   // the packed rows' cos / sin, once for all layers
+  double attn_flops = 0;
+  for (int j = 0; j < n_seg; ++j) attn_flops += 4.0 * seg[3 * j + 1] * (0.5 * seg[3 * j + 1]) * nq;
+  // the single-GPU layer of forward_initial_impl, with the packed rows' cache slots in the rope kernel and segments in the attention
+  bool in_norm_done = false;
+  for (int li = 0; li < c.num_hidden_layers; ++li) {
+    const LayerWeights& L = m->layers[li];
+    {
+      GemmArgs g{};
+      g.A = m->p_h; g.W = L.wqkv; g.C = m->p_qkv; g.M = S; g.N = nq + 2 * nkv; g.K = H; g.lda = H; g.ldw = H; g.ldc = g.N; g.act = ACT_NONE;
+      if (!in_norm_done && (rc = prefill_norm(m, L.in_norm, S, 0))) return rc;
+      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
+      launch_gemm(g, st);
+    }
+    in_norm_done = false;
+    {   // K and V of every row to its slot; the q heads are normed and rotated in the attention kernel's Q load
+      RopeArgs r{};
+      r.qkv = m->p_qkv; r.ld = nq + 2 * nkv; r.q_norm_w = L.q_norm; r.k_norm_w = L.k_norm;
+      r.pos = m->p_pos; r.pos_ld = S; r.inv_freq = m->d_inv_freq; r.axis_map = m->d_axis_map;
+      r.q_out = m->p_q; r.kv = model_kv_layer(m, li); r.kv_start = &m->d_state->kv_start;
+      r.S = S; r.nh = nh; r.kvh = kvh; r.d = d; r.eps = c.rms_norm_eps;
+      r.kv_start_host = 0; r.rope_tab = m->p_rope; r.skip_q = 1;
+      r.row_slot = m->p_seg + o_slot; r.page_rows = m->p_seg + o_prow; r.n_pages = npages;
+      ProfScope ps(m, "elem", (double)S * 2 * nkv * 4, 0);
+      launch_qknorm_rope(r, st);
+    }
+    {
+      AttnPrefillArgs a{};
+      a.q = m->p_qkv; a.q_ld = nq + 2 * nkv; a.kv = model_kv_layer(m, li); a.o = m->p_attn; a.S = S; a.nh = nh; a.kvh = kvh; a.d = d;
+      a.kv_offset = 0; a.kv_total = S; a.causal = 1; a.scale = m->attn_scale;
+      a.q_norm_w = L.q_norm; a.q_rope_tab = m->p_rope; a.q_eps = c.rms_norm_eps;
+      a.seg_tab = d_seg; a.seg_items = m->p_seg + o_items; a.n_items = n_items;
+      ProfScope ps(m, "attn_prefill", (double)S * nq * 4 + (double)S * nkv * 4, attn_flops);
+      launch_attn_prefill(a, st);
+    }
+    {
+      GemmArgs g{};
+      g.A = m->p_attn; g.W = L.wo; g.C = m->p_x; g.residual = m->p_x; g.M = S; g.N = H; g.K = nq; g.lda = nq; g.ldw = nq; g.ldc = H; g.act = ACT_NONE;
+      g.norm_w = L.post_norm; g.norm_out = m->p_h; g.norm_eps = c.rms_norm_eps;
+      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + 2.0 * g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
+      if ((rc = gemm_row_parallel(m, g, 0))) return rc;
+    }
+    {
+      GemmArgs g{};
+      g.A = m->p_h; g.W = L.wgu; g.C = m->p_act; g.M = S; g.N = 2 * I; g.K = H; g.lda = H; g.ldw = H; g.ldc = I; g.act = ACT_SILU_MUL_PAIRS;
+      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * I) * 2, 2.0 * g.M * g.N * g.K);
+      launch_gemm(g, st);
+    }
+    {
+      GemmArgs g{};
+      g.A = m->p_act; g.W = L.wdown; g.C = m->p_x; g.residual = m->p_x; g.M = S; g.N = H; g.K = I; g.lda = I; g.ldw = I; g.ldc = H; g.act = ACT_NONE;
+      if (li + 1 < c.num_hidden_layers) {
+        g.norm_w = m->layers[li + 1].in_norm; g.norm_out = m->p_h; g.norm_eps = c.rms_norm_eps;
+        in_norm_done = true;
+      }
+      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + 2.0 * g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
+      if ((rc = gemm_row_parallel(m, g, 0))) return rc;
+    }
+  }
+  {
+    ProfScope ps(m, "elem", (double)n_seg * H * 2 + (double)n_seg * H * 4, 0);
+    launch_embed_pool(m->p_x, d_seg, n_seg, m->final_norm, m->p_pool, H, c.rms_norm_eps, st);
+  }
+  AHA_HIP_CHECK(hipGetLastError());
+  AHA_HIP_CHECK(hipMemcpyAsync(out, m->p_pool, (size_t)n_seg * H * 4, hipMemcpyDeviceToHost, st));
+  AHA_HIP_CHECK(hipStreamSynchronize(st));
+  return AHA_OK;
+}
+
+int model_embed_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_tokens_per_pass, float* out) {
+  const aha_model_desc& c = m->desc;
+  if (n_seqs == 0) {
+    set_error("embed_batch: empty batch (n_seqs == 0)");
+    return AHA_ERR_INVALID;
+  }
+  if (!ids || !seq_lens || !out) {
+    set_error("embed_batch: null input_ids / seq_lens / out");
+    return AHA_ERR_INVALID;
+  }
+  if (c.arch != AHA_ARCH_QWEN3) {
+    set_error("embed_batch: only the Qwen3 text stack has an embedding head in the reference (qwen3_embedding/mod.rs)");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  if (m->tp_size > 1 || m->cp_size > 1 || c.head_dim != 128) {
+    set_error("embed_batch: a single-GPU model with head_dim 128 only (no tensor / context parallelism)");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  size_t total = 0;
+  for (size_t j = 0; j < n_seqs; ++j) {
+    if (seq_lens[j] == 0) {
+      set_error("embed_batch: empty input_ids of sequence " + std::to_string(j));
+      return AHA_ERR_INVALID;
+    }
+    if (seq_lens[j] > (size_t)1 << 24) {
+      set_error("embed_batch: sequence " + std::to_string(j) + " is longer than 2^24 tokens");
+      return AHA_ERR_INVALID;
+    }
+    for (size_t i = 0; i < seq_lens[j]; ++i)
+      if (ids[total + i] >= (uint32_t)c.vocab_size) {
+        set_error("token id out of range in sequence " + std::to_string(j) + " at position " + std::to_string(i));
+        return AHA_ERR_INVALID;
+      }
+    total += seq_lens[j];
+  }
+  AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
+  int rc = model_clear_cache(m);
+  if (rc) return rc;
+  struct ClearGuard {   // the cache is empty afterwards, on success and on error alike (qwen3_embedding/mod.rs:58)
+    aha_model* m;
+    ~ClearGuard() { model_clear_cache(m); }
+  } guard{m};
+  const size_t budget = std::min(max_tokens_per_pass ? max_tokens_per_pass : EMBED_PASS_ROWS, (size_t)1 << 24);
+  const size_t H = (size_t)c.hidden_size;
+  size_t j = 0, off = 0;
+  while (j < n_seqs) {
+    size_t rows = 0, slots = 0, k = j;
+    while (k < n_seqs) {
+      const size_t len = seq_lens[k], sl = (len + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS * KV_PAGE_TOKENS;
+      if (k > j && (rows + len > budget || slots + sl > 2 * budget)) break;
+      rows += len, slots += sl, ++k;
+    }
+    if ((rc = embed_pass(m, ids + off, seq_lens + j, (int)(k - j), out + j * H))) return rc;
+    off += rows;
+    j = k;
+  }
+  return AHA_OK;
 }
 
 }  // namespace aha

@@ -323,15 +323,29 @@ class HipInferenceModel:
                                   out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
+    def embed_batch(self, inputs: Sequence[Sequence[int]], max_tokens_per_pass: int = 0) -> np.ndarray:
+        """embed_one of every sequence, run as packed prefills (aha_hip_embed_batch): (len(inputs), hidden) float32.
+        max_tokens_per_pass = 0 takes the library default; a longer sequence still runs whole, alone in its pass."""
+        seqs = [np.asarray(x, dtype=np.uint32).reshape(-1) for x in inputs]
+        ids = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0, np.uint32))
+        lens = np.ascontiguousarray([s.size for s in seqs], dtype=np.uint64)
+        out = np.empty((len(seqs), self.text_cfg.hidden_size), dtype=np.float32)
+        check(lib().aha_hip_embed_batch(self.handle, ids.ctypes.data, lens.ctypes.data, len(seqs), int(max_tokens_per_pass),
+                                        out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
     def embed_multi(self, inputs: Sequence[Sequence[int]]) -> np.ndarray:
         if len(inputs) == 0:
             raise ValueError("embedding input cannot be empty")  # qwen3_embedding/mod.rs:39-41
-        return np.stack([self.embed_one(x) for x in inputs], 0)
+        return self.embed_batch(inputs)
 
     def rerank(self, query_ids: Sequence[int], documents_ids: Sequence[Sequence[int]]) -> np.ndarray:
-        """Qwen3Reranker::rerank (qwen3_reranker/mod.rs:23-31): cosine_similarity_no_l2(query, docs) on normalised vectors."""
-        q = self.embed_one(query_ids)[None, :]
-        return (q @ self.embed_multi(documents_ids).T)[0]
+        """Qwen3Reranker::rerank (qwen3_reranker/mod.rs:23-31): cosine_similarity_no_l2(query, docs) on normalised vectors.
+        The query and the documents go through one embed_batch call."""
+        if len(documents_ids) == 0:
+            raise ValueError("embedding input cannot be empty")  # embed_multi of the documents, qwen3_embedding/mod.rs:39-41
+        e = self.embed_batch([query_ids, *documents_ids])
+        return (e[:1] @ e[1:].T)[0]
 
     def cache_len(self) -> int:
         return int(lib().aha_hip_cache_len(self.handle))

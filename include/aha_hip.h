@@ -161,6 +161,16 @@ int aha_hip_get_rope_index_mm(const aha_model_desc* desc, const uint32_t* input_
  * Qwen3Reranker::rerank (qwen3_reranker/mod.rs:23-31) is the dot product of two such vectors
  * (cosine_similarity_no_l2, modules.rs:1381-1389) -- host arithmetic on the caller's side. */
 int aha_hip_embed(aha_model* m, const uint32_t* input_ids, size_t n_ids, float* out);
+/* Many texts in one call: out[j * hidden_size ..] == aha_hip_embed of sequence j, within the parity bounds (the reference embeds one
+ * text at a time: qwen3_embedding/mod.rs:38-64; pooling + l2_normalize common/modules.rs:1287-1294; Qwen3Reranker::rerank
+ * qwen3_reranker/mod.rs:23-31 and cosine_similarity_no_l2 modules.rs:1381-1389 are dot products of such rows).  input_ids holds the
+ * n_seqs sequences back to back, seq_lens[j] tokens each.  They run as packed prefills without padding -- every sequence with positions
+ * 0 .. len-1 and a cache window of its own, causal attention inside it -- in passes of at most max_tokens_per_pass tokens (0: a library
+ * default of 16384; a longer sequence runs alone as one pass).  The KV cache is cleared before and after.  AHA_ARCH_QWEN3 on one GPU only:
+ * a tensor- or context-parallel model gets AHA_ERR_UNSUPPORTED.  n_seqs == 0 or an empty sequence: AHA_ERR_INVALID ("empty"); an
+ * id >= vocab_size: AHA_ERR_INVALID ("out of range", naming the sequence and position). */
+int aha_hip_embed_batch(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_tokens_per_pass,
+                        float* out);
 
 /* ---- checkpoint directory -> model (XxxGenerateModel::init minus tokenizer / chat template) --------------------------
  * aha_hip_config_parse: <dir>/config.json -> aha_model_desc, the same field mapping serde does into Qwen3Config

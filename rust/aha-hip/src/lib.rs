@@ -198,6 +198,14 @@ pub mod sys {
         ) -> i32;
         pub fn aha_hip_cp_init_rccl(m: *mut AhaModel, unique_id128: *const c_void) -> i32;
         pub fn aha_hip_embed(m: *mut AhaModel, ids: *const u32, n_ids: usize, out: *mut f32) -> i32;
+        pub fn aha_hip_embed_batch(
+            m: *mut AhaModel,
+            ids: *const u32,
+            seq_lens: *const usize,
+            n_seqs: usize,
+            max_tokens_per_pass: usize,
+            out: *mut f32,
+        ) -> i32;
         pub fn aha_hip_cache_len(m: *const AhaModel) -> usize;
         pub fn aha_hip_audio_resample(
             ctx: *mut AhaCtx,
@@ -264,6 +272,7 @@ pub struct Model {
     ctx: *mut sys::AhaCtx,
     model: *mut sys::AhaModel,
     vocab: usize,
+    hidden: usize,
     stop: Vec<u32>,
 }
 unsafe impl Send for Model {}
@@ -294,7 +303,7 @@ impl Model {
         let mut stop = vec![0u32; 8];
         let n = unsafe { sys::aha_hip_stop_token_ids(model, stop.as_mut_ptr(), 8) };
         stop.truncate(n.clamp(0, 8) as usize);
-        Ok(Self { ctx, model, vocab: desc.vocab_size as usize, stop })
+        Ok(Self { ctx, model, vocab: desc.vocab_size as usize, hidden: desc.hidden_size as usize, stop })
     }
 
     /// From tensors the caller already holds (e.g. the mmapped safetensors views `VarBuilder::from_mmaped_safetensors` opens):
@@ -320,7 +329,7 @@ impl Model {
             return Err(e);
         }
         let n = desc.n_stop_tokens.clamp(0, 8) as usize;
-        Ok(Self { ctx, model, vocab: desc.vocab_size as usize, stop: desc.stop_tokens[..n].to_vec() })
+        Ok(Self { ctx, model, vocab: desc.vocab_size as usize, hidden: desc.hidden_size as usize, stop: desc.stop_tokens[..n].to_vec() })
     }
 
     pub fn vocab_size(&self) -> usize {
@@ -402,6 +411,19 @@ impl Model {
 
     pub fn clear_cache(&mut self) {
         unsafe { sys::aha_hip_clear_cache(self.model) };
+    }
+
+    /// `Qwen3Embedding::embed_one` (qwen3_embedding/mod.rs:50-64) of every sequence, computed as packed prefills
+    /// (`aha_hip_embed_batch`): row `j` of the `(seqs.len(), hidden)` result is sequence `j`'s L2-normalised embedding.
+    /// `max_tokens_per_pass = 0` takes the library default.
+    pub fn embed_batch(&mut self, seqs: &[&[u32]], max_tokens_per_pass: usize) -> Result<Vec<f32>, Error> {
+        let ids: Vec<u32> = seqs.iter().flat_map(|s| s.iter().copied()).collect();
+        let lens: Vec<usize> = seqs.iter().map(|s| s.len()).collect();
+        let mut out = vec![0f32; seqs.len() * self.hidden];
+        check(unsafe {
+            sys::aha_hip_embed_batch(self.model, ids.as_ptr(), lens.as_ptr(), lens.len(), max_tokens_per_pass, out.as_mut_ptr())
+        })?;
+        Ok(out)
     }
 
     /// The greedy loop of `generate_generic` / `generate_stream_generic` (common/generate.rs:115-159, 161-368) kept on the
