@@ -486,6 +486,122 @@ int aha_hip_attn_decode(const void* q, const void* k, const void* v, void* o, in
   API_GUARD_END
 }
 
+// ---- batched decode, op level (scratch allocated per call: test / measurement entries) ----
+int aha_hip_gemv_rows(const void* W, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi, const void* residual,
+                      float* logits, uint32_t* argmax_out, void* stream) {
+  API_GUARD_BEGIN
+  if (!W || !x || R < 1 || R > 32 || N < 1 || K < 8 || K % 8 || epi < 0 || epi > 3 || (epi == 1 && (!residual || !y)) ||
+      ((epi == 0 || epi == 2) && !y) || (epi == 2 && N % 32) || (epi == 3 && (!logits || !argmax_out))) {
+    set_error("gemv_rows: bad arguments (1 <= R <= 32, K % 8 == 0, epi 0..3 with its outputs; epi 2 needs N % 32 == 0)");
+    return AHA_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int tiles = gemv_rows_num_tiles(N);
+  float *ws = nullptr, *bm = nullptr;
+  uint32_t* bi = nullptr;
+  AHA_HIP_CHECK(hipMalloc((void**)&ws, gemv_rows_ws_floats(R, N, K) * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&bm, (size_t)R * tiles * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&bi, (size_t)R * tiles * 4));
+  GemvRowsArgs a{};
+  a.W = W; a.x = x; a.ldx = K; a.R = R; a.N = N; a.K = K; a.ws = ws;
+  a.y = y; a.residual = residual; a.ldy = epi == 2 ? N / 2 : N;
+  a.y_f32 = logits; a.ldf = N; a.blk_max = bm; a.blk_idx = bi;
+  const GemvEpi e = epi == 0 ? GEMV_STORE : epi == 1 ? GEMV_RESIDUAL : epi == 2 ? GEMV_SILU_MUL : GEMV_LOGITS;
+  launch_gemv_rows(a, e, st);
+  if (epi == 3) launch_argmax_rows(bm, bi, tiles, R, argmax_out, st);
+  hipError_t err = hipGetLastError();
+  hipStreamSynchronize(st);
+  hipFree(ws);
+  hipFree(bm);
+  hipFree(bi);
+  AHA_HIP_CHECK(err);
+  return AHA_OK;
+  API_GUARD_END
+}
+
+static bool attn_batch_geometry_ok(int32_t nh, int32_t kvh) { return nh > 0 && kvh > 0 && nh % kvh == 0 && nh / kvh <= 16 && kvh <= 64; }
+
+int aha_hip_attn_decode_batch(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
+                              const int32_t* page0, const int32_t* kv_len, int32_t rows, int32_t nh, int32_t kvh, float eps, float scale,
+                              void* o, void* stream) {
+  API_GUARD_BEGIN
+  if (!qkv || !q_norm_w || !k_norm_w || !rope || !page_ptrs || !page0 || !kv_len || !o || rows < 1 || !attn_batch_geometry_ok(nh, kvh)) {
+    set_error("attn_decode_batch: bad arguments (rows >= 1, nh % kvh == 0, group size <= 16)");
+    return AHA_ERR_INVALID;
+  }
+  for (int r = 0; r < rows; ++r)
+    if (kv_len[r] < 1 || page0[r] < 0) {
+      set_error("attn_decode_batch: row " + std::to_string(r) + " needs kv_len >= 1 and page0 >= 0");
+      return AHA_ERR_INVALID;
+    }
+  hipStream_t st = (hipStream_t)stream;
+  const int g = nh / kvh;
+  int max_split = 1;
+  std::vector<int32_t> tab((size_t)rows * GEN_ROW_WORDS, 0);
+  for (int r = 0; r < rows; ++r) {
+    int32_t* t = tab.data() + (size_t)r * GEN_ROW_WORDS;
+    t[GEN_ROW_PAGE0] = page0[r];
+    t[GEN_ROW_KVLEN] = kv_len[r];
+    t[GEN_ROW_NSPLIT] = attn_decode_nsplit(kv_len[r], g, 64);
+    t[GEN_ROW_POS] = kv_len[r] - 1;
+    max_split = std::max(max_split, t[GEN_ROW_NSPLIT]);
+  }
+  int32_t* d_tab = nullptr;
+  float *po = nullptr, *pml = nullptr;
+  unsigned* ctr = nullptr;
+  AHA_HIP_CHECK(hipMalloc((void**)&d_tab, tab.size() * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&po, (size_t)rows * max_split * nh * 128 * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&pml, (size_t)rows * max_split * nh * 2 * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&ctr, (size_t)rows * kvh * 32 * 4));
+  AHA_HIP_CHECK(hipMemsetAsync(ctr, 0, (size_t)rows * kvh * 32 * 4, st));
+  AHA_HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+  AttnDecodeBatchArgs b{};
+  b.qkv = qkv; b.q_norm_w = q_norm_w; b.k_norm_w = k_norm_w; b.rope = rope; b.page_ptrs = page_ptrs; b.layer_off = 0; b.row_tab = d_tab;
+  b.part_o = po; b.part_ml = pml; b.o = o; b.head_ctr = ctr; b.ctr_step = 1; b.nh = nh; b.kvh = kvh; b.max_nsplit = max_split;
+  b.eps = eps; b.scale = scale;
+  launch_attn_decode_batch(b, rows, max_split, st);
+  hipError_t err = hipGetLastError();
+  hipStreamSynchronize(st);
+  hipFree(d_tab);
+  hipFree(po);
+  hipFree(pml);
+  hipFree(ctr);
+  AHA_HIP_CHECK(err);
+  return AHA_OK;
+  API_GUARD_END
+}
+
+int aha_hip_debug_attn_decode_fused(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
+                                    int32_t kv_len, int32_t nh, int32_t kvh, float eps, float scale, void* o, void* stream) {
+  API_GUARD_BEGIN
+  if (!qkv || !q_norm_w || !k_norm_w || !rope || !page_ptrs || !o || kv_len < 1 || !attn_batch_geometry_ok(nh, kvh)) {
+    set_error("debug_attn_decode_fused: bad arguments (kv_len >= 1, nh % kvh == 0, group size <= 16)");
+    return AHA_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int nsplit = attn_decode_nsplit(kv_len, nh / kvh, 64);
+  float *po = nullptr, *pml = nullptr;
+  unsigned* ctr = nullptr;
+  AHA_HIP_CHECK(hipMalloc((void**)&po, (size_t)nsplit * nh * 128 * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&pml, (size_t)nsplit * nh * 2 * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&ctr, (size_t)kvh * 32 * 4));
+  AHA_HIP_CHECK(hipMemsetAsync(ctr, 0, (size_t)kvh * 32 * 4, st));
+  AttnDecodeFusedArgs a{};
+  a.qkv = qkv; a.q_norm_w = q_norm_w; a.k_norm_w = k_norm_w; a.rope = rope;
+  a.kv.page_ptrs = page_ptrs; a.kv.layer_off = 0; a.kv.kvh = kvh; a.kv.d = 128;
+  a.kv_start_v = kv_len - 1; a.kv_len_v = kv_len; a.part_o = po; a.part_ml = pml; a.o = o; a.head_ctr = ctr;
+  a.ctr_target = nsplit > 1 ? (unsigned)nsplit : 0u; a.nh = nh; a.kvh = kvh; a.nsplit = nsplit; a.eps = eps; a.scale = scale;
+  launch_attn_decode_fused(a, st);
+  hipError_t err = hipGetLastError();
+  hipStreamSynchronize(st);
+  hipFree(po);
+  hipFree(pml);
+  hipFree(ctr);
+  AHA_HIP_CHECK(err);
+  return AHA_OK;
+  API_GUARD_END
+}
+
 int aha_hip_attn_prefill(const void* q, const void* k, const void* v, void* o, int32_t S, int32_t L, int32_t nh,
                          int32_t kvh, int32_t d, int32_t kv_offset, int32_t causal, float scale, void* stream) {
   API_GUARD_BEGIN
@@ -665,6 +781,16 @@ int aha_hip_embed_batch(aha_model* m, const uint32_t* input_ids, const size_t* s
     return AHA_ERR_INVALID;
   }
   return model_embed_batch(m, input_ids, seq_lens, n_seqs, max_tokens_per_pass, out);
+  API_GUARD_END
+}
+int aha_hip_generate_batch(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
+                           size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* logits_out) {
+  API_GUARD_BEGIN
+  if (!m) {
+    set_error("null model");
+    return AHA_ERR_INVALID;
+  }
+  return model_generate_batch(m, input_ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, logits_out);
   API_GUARD_END
 }
 int aha_hip_config_parse(const char* model_dir, aha_model_desc* out) {

@@ -248,6 +248,63 @@ void launch_residual_add_f32_cols(void* x, int64_t ldx, const float* sum, int64_
 void launch_row_to_f32(const void* x_bf16_or_null, float* out, int n, hipStream_t st);   // nullptr: zeros
 void launch_f32_to_row(const float* x, void* out_bf16, int n, hipStream_t st);
 
+// ---- multi-sequence decode (kernels_batch.hip; model_generate_batch) ----------------------------------------------------
+// y[R, N] = x[R, K] . W[N, K]^T for 1 <= R <= 32 rows, the weights streamed once.  Two launches: gemv_rows_kernel (f32 partials of the
+// K splits into ws) and the merge (fixed-order sum + epilogue).  Every output element's summation order depends on (N, K) only.
+// Epilogues: GEMV_STORE / GEMV_RESIDUAL (y = bf16(residual + bf16(lin)), residual may alias y) / GEMV_SILU_MUL (W in the 16-row gate / up
+// block layout of ACT_SILU_MUL_PAIRS, N = 2I, y is (R, I)) / GEMV_LOGITS (y_f32 (R, ldf) f32 + per-(row, 256-column tile) (max, index)
+// partials, gemv_rows_num_tiles(N) per row).
+struct GemvRowsArgs {
+  const void* W;
+  const void* x;       // (R, ldx) bf16
+  const void* residual;
+  void* y;             // (R, ldy) bf16
+  float* y_f32;        // GEMV_LOGITS
+  float* blk_max;      // GEMV_LOGITS: (R, gemv_rows_num_tiles(N))
+  uint32_t* blk_idx;
+  float* ws;           // gemv_rows_ws_floats(R, N, K) f32
+  int R, N, K;         // K % 8 == 0
+  int64_t ldx, ldy, ldf;
+  int64_t ldws = 0;    // set by the launcher
+};
+void launch_gemv_rows(const GemvRowsArgs& a, GemvEpi epi, hipStream_t st);
+void gemv_rows_plan(int N, int K, int* chunks_per_wave, int* k_splits);
+int gemv_rows_num_tiles(int N);
+size_t gemv_rows_ws_floats(int R, int N, int K);
+void launch_argmax_rows(const float* blk_max, const uint32_t* blk_idx, int ntiles, int rows, uint32_t* out, hipStream_t st);
+
+// Per-step row table of the batched decode, GEN_ROW_WORDS int32 per active row
+constexpr int GEN_ROW_WORDS = 8;
+constexpr int GEN_ROW_PAGE0 = 0;   // first logical page of the row's sequence (its pages are consecutive)
+constexpr int GEN_ROW_KVLEN = 1;   // cache length after this step's append
+constexpr int GEN_ROW_NSPLIT = 2;  // KV splits (attn_decode_nsplit of the row's own length)
+constexpr int GEN_ROW_CTR = 3;     // the row's split-arrival counters before this step (the layer's target: + ctr_step * nsplit)
+constexpr int GEN_ROW_POS = 4;     // rope position of the step's token
+constexpr int GEN_ROW_SRC = 5;     // row of the previous step's token vector that holds this row's input token
+void launch_gen_embed(const void* table, const uint32_t* tok_in, const int32_t* row_tab, int rows, void* x, int H, const float* inv_freq,
+                      const int32_t* axis_map, float* rope, hipStream_t st);
+
+// Fused decode attention of many sequences in one launch: block (kv head, split, row) runs attn_decode_fused_body with row r's qkv row,
+// rope row, pages (page_ptrs + page0), lengths and split count; bit-identical per row to launch_attn_decode_fused on the same inputs.
+struct AttnDecodeBatchArgs {
+  const void* qkv;            // (rows, (nh + 2kvh) * 128) bf16
+  const void* q_norm_w;
+  const void* k_norm_w;
+  const float* rope;          // (rows, 128) f32, bf16-representable
+  const uint64_t* page_ptrs;  // logical page -> layer-0 byte address
+  uint64_t layer_off;
+  const int32_t* row_tab;     // (rows, GEN_ROW_WORDS) device
+  float* part_o;              // (rows, max_nsplit, nh, 128)
+  float* part_ml;             // (rows, max_nsplit, nh, 2)
+  void* o;                    // (rows, nh * 128) bf16
+  unsigned* head_ctr;         // (rows, kvh, 32) monotonic split-arrival counters
+  int ctr_step;               // target of row r = row_tab[r].ctr + ctr_step * nsplit
+  int nh, kvh, max_nsplit;
+  float eps, scale;
+};
+void launch_attn_decode_batch(const AttnDecodeBatchArgs& a, int rows, int max_nsplit_rows, hipStream_t st);
+int attn_decode_nsplit(int kv_len_after, int g, int max_nsplit);   // enqueue_decode_step's split rule
+
 struct StepState;  // model.h
 // words the fused decode attention synchronises through (zeroed once at model creation, monotonic afterwards)
 constexpr size_t DECODE_SYNC_BYTES = 32768;

@@ -1,0 +1,330 @@
+// Multi-sequence decode (model_generate_batch, model.hip): the kernels one step of R independent sequences runs on top of the
+// row-wise norms.
+//
+//   gemv_rows_kernel         out[R, N] = x[R, K] . W[N, K]^T for R <= 32: every weight element is read from HBM ONCE per launch
+//                            (non-temporal, straight to VGPRs) and multiplied with all R rows by v_mfma_f32_16x16x32_bf16 -- the rows
+//                            are the A operand, padded to 16 (one or two row tiles), 32 weight rows the B operand of two MFMAs.
+//   gemv_rows_merge_kernel   the fixed-order sum of the K-split partials + the epilogue (store / residual / SiLU.mul pairs / logits).
+//   argmax_rows_kernel       per-row pick of the logits epilogue's (max, index) partials -> the device token vector.
+//   gen_embed_kernel         the R token embeddings (tokens read from the device vector the previous step's pick wrote) + every row's
+//                            rope cos / sin table.
+//   attn_decode_batch_kernel q/k-norm + RoPE + KV append + split-KV attention + split merge of ALL rows in one launch: one block per
+//                            (kv head, split, row), each running attn_decode_fused_body on its row's qkv, rope row and pages.
+//
+// Row isolation (tests/test_generate_batch_gpu.py): every output element of gemv_rows is summed in an order that depends only on
+// (N, K) -- within a wave the MFMA chain over its chunks, across the 4 waves of a block ((w0 + w1) + w2) + w3 through LDS, across the
+// K splits slab 0, 1, ... in the merge kernel -- and an MFMA output row depends only on its own A row.  So a row's bits do not depend on
+// R or on the other rows.  The attention of a row is attn_decode_fused_body with that row's arguments and the single-sequence split rule,
+// so it is bit-identical to attn_decode_fused_kernel on the same inputs.
+#include <hip/hip_runtime.h>
+
+#include "attn_decode_body.h"
+#include "common.h"
+#include "gemv_body.h"   // silu_f: the matvec's activation, for the same bits
+#include "kernels.h"
+
+namespace aha {
+
+namespace {
+
+typedef const __attribute__((address_space(1))) char* gcchar_t;
+typedef const __attribute__((address_space(1))) bf16_t* gcbf_t;
+typedef __attribute__((address_space(1))) bf16_t* gbf_t;
+typedef const __attribute__((address_space(1))) float* gcf_t;
+typedef __attribute__((address_space(1))) float* gf_t;
+// generic pointer -> explicitly global one (global loads / stores, never flat: see common.h gptr16_t)
+template <class T>
+__device__ __forceinline__ T gp(const void* p) { return reinterpret_cast<T>((uint64_t)(uintptr_t)p); }
+
+constexpr int GR_CHUNK = 128;   // k per chunk: 4 MFMA k-steps of 32; lane group q = lane / 16 holds k q*32 .. q*32+31 of the chunk
+constexpr int GR_NB = 32;       // weight rows (output columns) per block: two 16-wide MFMA column tiles
+
+// One wave: columns n0 .. n0+31 (two tiles) x chunks c0 .. c0+CW-1 of K, for NRT row tiles of x.  Lane l: column / row c = l & 15 of a
+// tile, k group q = l >> 4.  MFMA step j of chunk c covers k = c*128 + q*32 + j*8 .. +7 in lane group q: a fixed permutation of the k
+// order, the same for W and x.  Requests are issued x(c), W(c) in chunk order, all up front; the MFMAs of chunk c then wait only for
+// what was requested before chunk c+1.
+template <int CW, int NRT>
+__global__ __launch_bounds__(256, 2) void gemv_rows_kernel(GemvRowsArgs a) {
+  __shared__ __attribute__((aligned(16))) float red[4 * 2 * NRT * 256];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c = lane & 15, q = lane >> 4;
+  const int n0 = blockIdx.x * GR_NB, ks = blockIdx.y;
+  const int K = a.K, N = a.N, R = a.R;
+  const int nchunks = (K + GR_CHUNK - 1) / GR_CHUNK;
+  const int cbase = (ks * 4 + wave) * CW;
+  const gcchar_t W = gp<gcchar_t>(a.W);
+  const gcchar_t X = gp<gcchar_t>(a.x);
+  // weight rows of this lane in the two column tiles (rows past N re-read row N-1: finite values whose outputs are never stored)
+  const int64_t wr0 = (int64_t)min(n0 + c, N - 1) * K, wr1 = (int64_t)min(n0 + 16 + c, N - 1) * K;
+  u32x4_t wf[CW][2][4], xf[CW][NRT][4];
+#pragma unroll
+  for (int i = 0; i < CW; ++i) {
+    const int ch = cbase + i;
+    const int chc = min(ch, nchunks - 1);   // waves past the end of K re-read the last chunk; their x is zero
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt) {
+      const int row = rt * 16 + c;
+      const int64_t xr = (int64_t)min(row, R - 1) * a.ldx;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = ch * GR_CHUNK + q * 32 + j * 8;
+        const int kc = min(chc * GR_CHUNK + q * 32 + j * 8, K - 8);
+        u32x4_t v = *reinterpret_cast<gptr16_t>(X + (xr + kc) * 2);
+        if (row >= R || k >= K) v = u32x4_t{0u, 0u, 0u, 0u};
+        xf[i][rt][j] = v;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int kc = min(chc * GR_CHUNK + q * 32 + j * 8, K - 8);
+      wf[i][0][j] = __builtin_nontemporal_load(reinterpret_cast<gptr16_t>(W + (wr0 + kc) * 2));
+      wf[i][1][j] = __builtin_nontemporal_load(reinterpret_cast<gptr16_t>(W + (wr1 + kc) * 2));
+    }
+  }
+  f32x4_t acc[2][NRT];
+#pragma unroll
+  for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt) acc[nt][rt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < CW; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int rt = 0; rt < NRT; ++rt) acc[nt][rt] = mfma16(as_frag(xf[i][rt][j]), as_frag(wf[i][nt][j]), acc[nt][rt]);
+  // lane l holds out[row (l>>4)*4 + e][col l & 15] of each (column tile, row tile)
+#pragma unroll
+  for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) red[((wave * 2 + nt) * NRT + rt) * 256 + (q * 4 + e) * 16 + c] = acc[nt][rt][e];
+  __syncthreads();
+  // ((w0 + w1) + w2) + w3, then the f32 partial of this K split: ws[ks][row][n]
+  gf_t ws = gp<gf_t>(a.ws) + (int64_t)ks * a.R * a.ldws;
+  for (int e = tid; e < 2 * NRT * 256; e += 256) {
+    const int nt = e / (NRT * 256), rt = (e / 256) % NRT, m = (e >> 4) & 15, n = e & 15;
+    float s = red[e];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) s += red[w * 2 * NRT * 256 + e];
+    const int row = rt * 16 + m, col = n0 + nt * 16 + n;
+    if (row < R && col < N) ws[(int64_t)row * a.ldws + col] = s;
+  }
+}
+
+// Sum of the K splits in slab order + the epilogue.  Block (bx, row): 256 output columns of one row.  The Linear output is rounded to
+// bf16 first, as candle_nn::Linear's output tensor is (gemv_body.h: lin = rbf(acc)).
+template <int EPI>
+__global__ __launch_bounds__(256) void gemv_rows_merge_kernel(GemvRowsArgs a, int nks) {
+  const int row = blockIdx.y, tid = threadIdx.x;
+  const int nout = EPI == GEMV_SILU_MUL ? a.N / 2 : a.N;
+  const int j = blockIdx.x * 256 + tid;
+  const gcf_t ws = gp<gcf_t>(a.ws) + (int64_t)row * a.ldws;
+  const int64_t slab = (int64_t)a.R * a.ldws;
+  float best = -INFINITY;
+  uint32_t best_i = 0xffffffffu;
+  if (j < nout) {
+    if (EPI == GEMV_SILU_MUL) {   // output column j: gate row (j/16)*32 + j%16, up row 16 further (ACT_SILU_MUL_PAIRS block layout)
+      const int ng = (j >> 4) * 32 + (j & 15), nu = ng + 16;
+      float g = ws[ng], u = ws[nu];
+      for (int s = 1; s < nks; ++s) g += ws[s * slab + ng], u += ws[s * slab + nu];
+      const float ga = rbf(silu_f(rbf(g)));   // gate_proj -> act_fn   (modules.rs:82)
+      gp<gbf_t>(a.y)[(int64_t)row * a.ldy + j] = f2bf(ga * rbf(u));   // * up_proj (modules.rs:83-84)
+    } else {
+      float s0 = ws[j];
+      for (int s = 1; s < nks; ++s) s0 += ws[s * slab + j];
+      const float lin = rbf(s0);
+      if (EPI == GEMV_STORE) {
+        gp<gbf_t>(a.y)[(int64_t)row * a.ldy + j] = f2bf(lin);
+      } else if (EPI == GEMV_RESIDUAL) {
+        const float r = bf2f(gp<gcbf_t>(a.residual)[(int64_t)row * a.ldy + j]);
+        gp<gbf_t>(a.y)[(int64_t)row * a.ldy + j] = f2bf(r + lin);
+      } else {   // GEMV_LOGITS: the bf16 logits read back as f32 (generate.rs:75)
+        gp<gf_t>(a.y_f32)[(int64_t)row * a.ldf + j] = lin;
+        best = lin;
+        best_i = (uint32_t)j;
+      }
+    }
+  }
+  if (EPI == GEMV_LOGITS) {   // (max, first index) of the block's 256 columns
+    __shared__ float sv[4];
+    __shared__ uint32_t si[4];
+    for (int off = 32; off > 0; off >>= 1) {
+      const float ov = __shfl_xor(best, off);
+      const uint32_t oi = __shfl_xor(best_i, off);
+      if (ov > best || (ov == best && oi < best_i)) best = ov, best_i = oi;
+    }
+    if ((tid & 63) == 0) sv[tid >> 6] = best, si[tid >> 6] = best_i;
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < 4; ++w)
+        if (sv[w] > best || (sv[w] == best && si[w] < best_i)) best = sv[w], best_i = si[w];
+      a.blk_max[(int64_t)row * gridDim.x + blockIdx.x] = best;
+      a.blk_idx[(int64_t)row * gridDim.x + blockIdx.x] = best_i;
+    }
+  }
+}
+
+// one block per row: the first maximal index over the row's tiles (argmax_partials' rule)
+__global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ blk_max, const uint32_t* __restrict__ blk_idx, int ntiles,
+                                                          uint32_t* __restrict__ out) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  float best = -INFINITY;
+  uint32_t best_i = 0xffffffffu;
+  for (int t = tid; t < ntiles; t += 256) {
+    const float v = blk_max[(int64_t)row * ntiles + t];
+    const uint32_t i = blk_idx[(int64_t)row * ntiles + t];
+    if (v > best || (v == best && i < best_i)) best = v, best_i = i;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(best, off);
+    const uint32_t oi = __shfl_xor(best_i, off);
+    if (ov > best || (ov == best && oi < best_i)) best = ov, best_i = oi;
+  }
+  __shared__ float sv[4];
+  __shared__ uint32_t si[4];
+  if ((tid & 63) == 0) sv[tid >> 6] = best, si[tid >> 6] = best_i;
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w)
+      if (sv[w] > best || (sv[w] == best && si[w] < best_i)) best = sv[w], best_i = si[w];
+    out[row] = best_i == 0xffffffffu ? 0u : best_i;   // all-NaN logits: a valid id, never an index past the embedding table
+  }
+}
+
+// Block r: x[r] = embedding of tok_in[row_tab[r].src] (the previous step's pick), and row r's rope table from its position -- the same
+// cos / sin rounding as embed_state_kernel (model.hip).
+__global__ __launch_bounds__(256) void gen_embed_kernel(const bf16_t* __restrict__ table, const uint32_t* __restrict__ tok_in,
+                                                        const int32_t* __restrict__ row_tab, bf16_t* __restrict__ x, int H,
+                                                        const float* __restrict__ inv_freq, const int32_t* __restrict__ axis_map,
+                                                        float* __restrict__ rope) {
+  const int r = blockIdx.x;
+  const int32_t* t = row_tab + (int64_t)r * GEN_ROW_WORDS;
+  const uint32_t tok = tok_in[t[GEN_ROW_SRC]];
+  const u32x4_t* src = reinterpret_cast<const u32x4_t*>(table + (size_t)tok * H);
+  u32x4_t* dst = reinterpret_cast<u32x4_t*>(x + (size_t)r * H);
+  for (int i = threadIdx.x; i < H / 8; i += 256) dst[i] = src[i];
+  if (threadIdx.x < 64) {
+    const int i = threadIdx.x;
+    const float ang = (float)t[GEN_ROW_POS] * inv_freq[i];   // text-only rows: the three M-RoPE positions are equal
+    (void)axis_map;
+    rope[r * 128 + i] = rbf(cosf(ang));
+    rope[r * 128 + 64 + i] = rbf(sinf(ang));
+  }
+}
+
+// Block (kv head, split, row).  Splits past the row's own count return at once.
+__global__ __launch_bounds__(256, 2) void attn_decode_batch_kernel(AttnDecodeBatchArgs b) {
+  __shared__ __attribute__((aligned(16))) char smem[ATTN_DECODE_FUSED_LDS];
+  const int kvhd = blockIdx.x, split = blockIdx.y, r = blockIdx.z;
+  const int32_t* t = b.row_tab + (int64_t)r * GEN_ROW_WORDS;
+  const int nsplit = __builtin_amdgcn_readfirstlane(t[GEN_ROW_NSPLIT]);
+  if (split >= nsplit) return;
+  const int page0 = __builtin_amdgcn_readfirstlane(t[GEN_ROW_PAGE0]);
+  const int kv_len = __builtin_amdgcn_readfirstlane(t[GEN_ROW_KVLEN]);
+  const unsigned ctr0 = (unsigned)__builtin_amdgcn_readfirstlane(t[GEN_ROW_CTR]);
+  AttnDecodeFusedArgs a{};
+  a.qkv = (const bf16_t*)b.qkv + (int64_t)r * (b.nh + 2 * b.kvh) * 128;
+  a.q_norm_w = b.q_norm_w;
+  a.k_norm_w = b.k_norm_w;
+  a.rope = b.rope + (int64_t)r * 128;
+  a.kv.page_ptrs = b.page_ptrs + page0;
+  a.kv.layer_off = b.layer_off;
+  a.kv.kvh = b.kvh;
+  a.kv.d = 128;
+  a.kv_start_v = kv_len - 1;
+  a.kv_len_v = kv_len;
+  a.part_o = b.part_o + (int64_t)r * b.max_nsplit * b.nh * 128;
+  a.part_ml = b.part_ml + (int64_t)r * b.max_nsplit * b.nh * 2;
+  a.o = (bf16_t*)b.o + (int64_t)r * b.nh * 128;
+  a.head_ctr = b.head_ctr + (int64_t)r * b.kvh * 32;
+  a.ctr_target = ctr0 + (unsigned)b.ctr_step * (unsigned)nsplit;
+  a.trace = nullptr;
+  a.nh = b.nh;
+  a.kvh = b.kvh;
+  a.nsplit = nsplit;
+  a.eps = b.eps;
+  a.scale = b.scale;
+  attn_decode_fused_body(a, smem, kvhd, split, nsplit);
+}
+
+}  // namespace
+
+// K-split plan of gemv_rows: a function of (N, K) only (row isolation).  Chunks per wave cw in {1, 2}; splits nks = ceil(chunks / 4cw);
+// cw drops to 1 when the grid would leave CUs idle.
+void gemv_rows_plan(int N, int K, int* cw, int* nks) {
+  const int chunks = (K + GR_CHUNK - 1) / GR_CHUNK, nb = (N + GR_NB - 1) / GR_NB;
+  int c = chunks > 4 ? 2 : 1;
+  int s = (chunks + 4 * c - 1) / (4 * c);
+  if (c == 2 && (int64_t)nb * s < 256) {
+    c = 1;
+    s = (chunks + 3) / 4;
+  }
+  *cw = c;
+  *nks = s;
+}
+
+int gemv_rows_num_tiles(int N) { return (N + 255) / 256; }
+
+size_t gemv_rows_ws_floats(int R, int N, int K) {
+  int cw, nks;
+  gemv_rows_plan(N, K, &cw, &nks);
+  return (size_t)nks * R * N;
+}
+
+void launch_gemv_rows(const GemvRowsArgs& a0, GemvEpi epi, hipStream_t st) {
+  if (a0.R <= 0 || a0.N <= 0 || a0.K <= 0) return;
+  GemvRowsArgs a = a0;
+  a.ldws = a.N;
+  int cw, nks;
+  gemv_rows_plan(a.N, a.K, &cw, &nks);
+  const dim3 grid((unsigned)((a.N + GR_NB - 1) / GR_NB), (unsigned)nks);
+  const bool two = a.R > 16;
+  if (cw == 2) {
+    if (two) hipLaunchKernelGGL((gemv_rows_kernel<2, 2>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((gemv_rows_kernel<2, 1>), grid, dim3(256), 0, st, a);
+  } else {
+    if (two) hipLaunchKernelGGL((gemv_rows_kernel<1, 2>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((gemv_rows_kernel<1, 1>), grid, dim3(256), 0, st, a);
+  }
+  const int nout = epi == GEMV_SILU_MUL ? a.N / 2 : a.N;
+  const dim3 mgrid((unsigned)((nout + 255) / 256), (unsigned)a.R);
+  switch (epi) {
+    case GEMV_STORE: hipLaunchKernelGGL(gemv_rows_merge_kernel<GEMV_STORE>, mgrid, dim3(256), 0, st, a, nks); break;
+    case GEMV_RESIDUAL: hipLaunchKernelGGL(gemv_rows_merge_kernel<GEMV_RESIDUAL>, mgrid, dim3(256), 0, st, a, nks); break;
+    case GEMV_SILU_MUL: hipLaunchKernelGGL(gemv_rows_merge_kernel<GEMV_SILU_MUL>, mgrid, dim3(256), 0, st, a, nks); break;
+    default: hipLaunchKernelGGL(gemv_rows_merge_kernel<GEMV_LOGITS>, mgrid, dim3(256), 0, st, a, nks); break;
+  }
+}
+
+void launch_argmax_rows(const float* blk_max, const uint32_t* blk_idx, int ntiles, int rows, uint32_t* out, hipStream_t st) {
+  if (rows <= 0) return;
+  hipLaunchKernelGGL(argmax_rows_kernel, dim3((unsigned)rows), dim3(256), 0, st, blk_max, blk_idx, ntiles, out);
+}
+
+void launch_gen_embed(const void* table, const uint32_t* tok_in, const int32_t* row_tab, int rows, void* x, int H, const float* inv_freq,
+                      const int32_t* axis_map, float* rope, hipStream_t st) {
+  if (rows <= 0) return;
+  hipLaunchKernelGGL(gen_embed_kernel, dim3((unsigned)rows), dim3(256), 0, st, (const bf16_t*)table, tok_in, row_tab, (bf16_t*)x, H, inv_freq,
+                     axis_map, rope);
+}
+
+int attn_decode_nsplit(int kv_len_after, int g, int max_nsplit) {
+  // enqueue_decode_step's rule (model.hip): one block (4 waves = 4 KV units) per AHA_ATTN_PAGES_PER_BLOCK pages, at most max_nsplit, and
+  // g * nsplit <= 1024 for the merge's LDS tables
+  static const char* e_div = getenv("AHA_ATTN_PAGES_PER_BLOCK");
+  const int div = e_div ? std::max(1, atoi(e_div)) : 4;
+  const int npages = (kv_len_after + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
+  const int nsplit = (npages + div - 1) / div;
+  return std::max(1, std::min(std::min(nsplit, max_nsplit), 1024 / g));
+}
+
+void launch_attn_decode_batch(const AttnDecodeBatchArgs& b, int rows, int max_nsplit_rows, hipStream_t st) {
+  if (rows <= 0) return;
+  hipLaunchKernelGGL(attn_decode_batch_kernel, dim3((unsigned)b.kvh, (unsigned)max_nsplit_rows, (unsigned)rows), dim3(256), 0, st, b);
+}
+
+}  // namespace aha

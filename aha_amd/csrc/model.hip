@@ -1878,10 +1878,81 @@ static int forward_initial_impl(aha_model* m, const uint32_t* ids, size_t n, siz
 // (short texts waste up to a page each); a pass always holds at least one whole sequence.
 constexpr size_t EMBED_PASS_ROWS = 16384;
 
-static int embed_pass(aha_model* m, const uint32_t* ids, const size_t* lens, int n_seg, float* out) {
+// The single-GPU layer stack of a packed prefill pass of independent sequences (embed_pass, generate_prefill_pass): the rows' embeddings in
+// p_x, their positions' rope table in p_rope; K / V of row r go to cache slot d_slot[r] of the pages page_ptrs names, page p of 0 .. npages-1
+// holding the rows d_prow[2p] .. + d_prow[2p + 1]; the attention runs one block per (d_items entry, head) over d_seg's segments.  Leaves the
+// last layer's output rows in p_x.
+static int packed_layers(aha_model* m, int S, const uint64_t* page_ptrs, const int32_t* d_seg, const int32_t* d_items, int n_items,
+                         const int32_t* d_slot, const int32_t* d_prow, int npages, double attn_flops) {
   const aha_model_desc& c = m->desc;
   const int H = c.hidden_size, I = c.intermediate_size, d = c.head_dim, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
   const int nq = nh * d, nkv = kvh * d;
+  hipStream_t st = m->stream;
+  int rc;
+  // the single-GPU layer of forward_initial_impl, with the packed rows' cache slots in the rope kernel and segments in the attention
+  bool in_norm_done = false;
+  for (int li = 0; li < c.num_hidden_layers; ++li) {
+    const LayerWeights& L = m->layers[li];
+    KvLayer kv = model_kv_layer(m, li);
+    kv.page_ptrs = page_ptrs;
+    {
+      GemmArgs g{};
+      g.A = m->p_h; g.W = L.wqkv; g.C = m->p_qkv; g.M = S; g.N = nq + 2 * nkv; g.K = H; g.lda = H; g.ldw = H; g.ldc = g.N; g.act = ACT_NONE;
+      if (!in_norm_done && (rc = prefill_norm(m, L.in_norm, S, 0))) return rc;
+      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
+      launch_gemm(g, st);
+    }
+    in_norm_done = false;
+    {   // K and V of every row to its slot; the q heads are normed and rotated in the attention kernel's Q load
+      RopeArgs r{};
+      r.qkv = m->p_qkv; r.ld = nq + 2 * nkv; r.q_norm_w = L.q_norm; r.k_norm_w = L.k_norm;
+      r.pos = m->p_pos; r.pos_ld = S; r.inv_freq = m->d_inv_freq; r.axis_map = m->d_axis_map;
+      r.q_out = m->p_q; r.kv = kv; r.kv_start = &m->d_state->kv_start;
+      r.S = S; r.nh = nh; r.kvh = kvh; r.d = d; r.eps = c.rms_norm_eps;
+      r.kv_start_host = 0; r.rope_tab = m->p_rope; r.skip_q = 1;
+      r.row_slot = d_slot; r.page_rows = d_prow; r.n_pages = npages;
+      ProfScope ps(m, "elem", (double)S * 2 * nkv * 4, 0);
+      launch_qknorm_rope(r, st);
+    }
+    {
+      AttnPrefillArgs a{};
+      a.q = m->p_qkv; a.q_ld = nq + 2 * nkv; a.kv = kv; a.o = m->p_attn; a.S = S; a.nh = nh; a.kvh = kvh; a.d = d;
+      a.kv_offset = 0; a.kv_total = S; a.causal = 1; a.scale = m->attn_scale;
+      a.q_norm_w = L.q_norm; a.q_rope_tab = m->p_rope; a.q_eps = c.rms_norm_eps;
+      a.seg_tab = d_seg; a.seg_items = d_items; a.n_items = n_items;
+      ProfScope ps(m, "attn_prefill", (double)S * nq * 4 + (double)S * nkv * 4, attn_flops);
+      launch_attn_prefill(a, st);
+    }
+    {
+      GemmArgs g{};
+      g.A = m->p_attn; g.W = L.wo; g.C = m->p_x; g.residual = m->p_x; g.M = S; g.N = H; g.K = nq; g.lda = nq; g.ldw = nq; g.ldc = H; g.act = ACT_NONE;
+      g.norm_w = L.post_norm; g.norm_out = m->p_h; g.norm_eps = c.rms_norm_eps;
+      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + 2.0 * g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
+      if ((rc = gemm_row_parallel(m, g, 0))) return rc;
+    }
+    {
+      GemmArgs g{};
+      g.A = m->p_h; g.W = L.wgu; g.C = m->p_act; g.M = S; g.N = 2 * I; g.K = H; g.lda = H; g.ldw = H; g.ldc = I; g.act = ACT_SILU_MUL_PAIRS;
+      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * I) * 2, 2.0 * g.M * g.N * g.K);
+      launch_gemm(g, st);
+    }
+    {
+      GemmArgs g{};
+      g.A = m->p_act; g.W = L.wdown; g.C = m->p_x; g.residual = m->p_x; g.M = S; g.N = H; g.K = I; g.lda = I; g.ldw = I; g.ldc = H; g.act = ACT_NONE;
+      if (li + 1 < c.num_hidden_layers) {
+        g.norm_w = m->layers[li + 1].in_norm; g.norm_out = m->p_h; g.norm_eps = c.rms_norm_eps;
+        in_norm_done = true;
+      }
+      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + 2.0 * g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
+      if ((rc = gemm_row_parallel(m, g, 0))) return rc;
+    }
+  }
+  return AHA_OK;
+}
+
+static int embed_pass(aha_model* m, const uint32_t* ids, const size_t* lens, int n_seg, float* out) {
+  const aha_model_desc& c = m->desc;
+  const int H = c.hidden_size, nq = c.num_attention_heads * c.head_dim;
   hipStream_t st = m->stream;
   // host plan: segment table {row0, len, page0}, (segment, q block) items most expensive first, per-row cache slots, per-page rows
   std::vector<int32_t> seg(3 * (size_t)n_seg);
@@ -1966,62 +2037,8 @@ static int embed_pass(aha_model* m, const uint32_t* ids, const size_t* lens, int
   launch_rope_table(m->p_pos, S, m->d_inv_freq, m->d_axis_map, S, m->p_rope, st);   // the packed rows' cos / sin, once for all layers
   double attn_flops = 0;
   for (int j = 0; j < n_seg; ++j) attn_flops += 4.0 * seg[3 * j + 1] * (0.5 * seg[3 * j + 1]) * nq;
-  // the single-GPU layer of forward_initial_impl, with the packed rows' cache slots in the rope kernel and segments in the attention
-  bool in_norm_done = false;
-  for (int li = 0; li < c.num_hidden_layers; ++li) {
-    const LayerWeights& L = m->layers[li];
-    {
-      GemmArgs g{};
-      g.A = m->p_h; g.W = L.wqkv; g.C = m->p_qkv; g.M = S; g.N = nq + 2 * nkv; g.K = H; g.lda = H; g.ldw = H; g.ldc = g.N; g.act = ACT_NONE;
-      if (!in_norm_done && (rc = prefill_norm(m, L.in_norm, S, 0))) return rc;
-      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
-      launch_gemm(g, st);
-    }
-    in_norm_done = false;
-    {   // K and V of every row to its slot; the q heads are normed and rotated in the attention kernel's Q load
-      RopeArgs r{};
-      r.qkv = m->p_qkv; r.ld = nq + 2 * nkv; r.q_norm_w = L.q_norm; r.k_norm_w = L.k_norm;
-      r.pos = m->p_pos; r.pos_ld = S; r.inv_freq = m->d_inv_freq; r.axis_map = m->d_axis_map;
-      r.q_out = m->p_q; r.kv = model_kv_layer(m, li); r.kv_start = &m->d_state->kv_start;
-      r.S = S; r.nh = nh; r.kvh = kvh; r.d = d; r.eps = c.rms_norm_eps;
-      r.kv_start_host = 0; r.rope_tab = m->p_rope; r.skip_q = 1;
-      r.row_slot = m->p_seg + o_slot; r.page_rows = m->p_seg + o_prow; r.n_pages = npages;
-      ProfScope ps(m, "elem", (double)S * 2 * nkv * 4, 0);
-      launch_qknorm_rope(r, st);
-    }
-    {
-      AttnPrefillArgs a{};
-      a.q = m->p_qkv; a.q_ld = nq + 2 * nkv; a.kv = model_kv_layer(m, li); a.o = m->p_attn; a.S = S; a.nh = nh; a.kvh = kvh; a.d = d;
-      a.kv_offset = 0; a.kv_total = S; a.causal = 1; a.scale = m->attn_scale;
-      a.q_norm_w = L.q_norm; a.q_rope_tab = m->p_rope; a.q_eps = c.rms_norm_eps;
-      a.seg_tab = d_seg; a.seg_items = m->p_seg + o_items; a.n_items = n_items;
-      ProfScope ps(m, "attn_prefill", (double)S * nq * 4 + (double)S * nkv * 4, attn_flops);
-      launch_attn_prefill(a, st);
-    }
-    {
-      GemmArgs g{};
-      g.A = m->p_attn; g.W = L.wo; g.C = m->p_x; g.residual = m->p_x; g.M = S; g.N = H; g.K = nq; g.lda = nq; g.ldw = nq; g.ldc = H; g.act = ACT_NONE;
-      g.norm_w = L.post_norm; g.norm_out = m->p_h; g.norm_eps = c.rms_norm_eps;
-      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + 2.0 * g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
-      if ((rc = gemm_row_parallel(m, g, 0))) return rc;
-    }
-    {
-      GemmArgs g{};
-      g.A = m->p_h; g.W = L.wgu; g.C = m->p_act; g.M = S; g.N = 2 * I; g.K = H; g.lda = H; g.ldw = H; g.ldc = I; g.act = ACT_SILU_MUL_PAIRS;
-      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * I) * 2, 2.0 * g.M * g.N * g.K);
-      launch_gemm(g, st);
-    }
-    {
-      GemmArgs g{};
-      g.A = m->p_act; g.W = L.wdown; g.C = m->p_x; g.residual = m->p_x; g.M = S; g.N = H; g.K = I; g.lda = I; g.ldw = I; g.ldc = H; g.act = ACT_NONE;
-      if (li + 1 < c.num_hidden_layers) {
-        g.norm_w = m->layers[li + 1].in_norm; g.norm_out = m->p_h; g.norm_eps = c.rms_norm_eps;
-        in_norm_done = true;
-      }
-      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + 2.0 * g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
-      if ((rc = gemm_row_parallel(m, g, 0))) return rc;
-    }
-  }
+  if ((rc = packed_layers(m, S, m->d_page_ptrs, d_seg, m->p_seg + o_items, n_items, m->p_seg + o_slot, m->p_seg + o_prow, npages, attn_flops)))
+    return rc;
   {
     ProfScope ps(m, "elem", (double)n_seg * H * 2 + (double)n_seg * H * 4, 0);
     launch_embed_pool(m->p_x, d_seg, n_seg, m->final_norm, m->p_pool, H, c.rms_norm_eps, st);
@@ -2087,6 +2104,406 @@ int model_embed_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens,
     if ((rc = embed_pass(m, ids + off, seq_lens + j, (int)(k - j), out + j * H))) return rc;
     off += rows;
     j = k;
+  }
+  return AHA_OK;
+}
+
+// ---- batched greedy generation ---------------------------------------------------------------------------------------------------
+// generate_generic (common/generate.rs:115-159) at temperature 0 for many prompts at once.  Prefill: the packed passes of embed_batch
+// (packed_layers), each prompt on its own run of pages, then every prompt's last row through the final RMSNorm and the batched lm_head ->
+// the first token.  Decode: all unfinished sequences advance together, one step = the R rows through every layer with the weights streamed
+// once per group of <= 32 rows (gemv_rows) and ONE attention launch per layer (attn_decode_batch); the next tokens stay on the device (the
+// step's argmax writes the token vector the next step's embedding gather reads), the host reads them once per step to drop finished rows.
+namespace {
+struct DevBufs {   // per-call device / pinned scratch, freed after the stream has drained
+  hipStream_t st;
+  std::vector<void*> dev, host;
+  ~DevBufs() {
+    hipStreamSynchronize(st);
+    for (void* p : dev) hipFree(p);
+    for (void* p : host) hipHostFree(p);
+  }
+  template <class T>
+  int alloc(T** out, size_t n, bool zero = false) {
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T));
+    if (e != hipSuccess) {
+      set_error(std::string("generate_batch: hipMalloc failed: ") + hipGetErrorString(e));
+      return e == hipErrorOutOfMemory ? AHA_ERR_OOM : AHA_ERR_HIP;
+    }
+    dev.push_back(p);
+    if (zero && hipMemsetAsync(p, 0, std::max<size_t>(n, 1) * sizeof(T), st) != hipSuccess) return AHA_ERR_HIP;
+    *out = (T*)p;
+    return AHA_OK;
+  }
+  template <class T>
+  int alloc_host(T** out, size_t n) {
+    void* p = nullptr;
+    if (hipHostMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
+      set_error("generate_batch: pinned host allocation failed");
+      return AHA_ERR_OOM;
+    }
+    host.push_back(p);
+    *out = (T*)p;
+    return AHA_OK;
+  }
+};
+}  // namespace
+
+constexpr int GEN_ROW_GROUP = 32;   // rows of one gemv_rows launch: larger batches stream the weights once per group
+
+// y[rows] = epi(x[rows] . W^T) in groups of GEN_ROW_GROUP rows.  For GEMV_LOGITS, y_f32 / blk partials are (rows, ldf) / (rows, tiles).
+static void gemv_rows_groups(aha_model* m, GemvRowsArgs g, GemvEpi epi, int rows, float* ws) {
+  const int tiles = gemv_rows_num_tiles(g.N);
+  const double wbytes = (double)g.N * g.K * 2;
+  for (int r0 = 0; r0 < rows; r0 += GEN_ROW_GROUP) {
+    GemvRowsArgs a = g;
+    a.R = std::min(GEN_ROW_GROUP, rows - r0);
+    a.x = (const bf16_t*)g.x + (int64_t)r0 * g.ldx;
+    if (g.y) a.y = (bf16_t*)g.y + (int64_t)r0 * g.ldy;
+    if (g.residual) a.residual = (const bf16_t*)g.residual + (int64_t)r0 * g.ldy;
+    if (g.y_f32) a.y_f32 = g.y_f32 + (int64_t)r0 * g.ldf;
+    if (g.blk_max) a.blk_max = g.blk_max + (int64_t)r0 * tiles, a.blk_idx = g.blk_idx + (int64_t)r0 * tiles;
+    a.ws = ws;
+    ProfScope ps(m, "gemv_rows", wbytes + (double)a.R * (g.K + g.N) * 2, 2.0 * a.R * g.N * g.K);
+    launch_gemv_rows(a, epi, m->stream);
+  }
+}
+
+struct GenCall {
+  int n = 0, V = 0, H = 0, max_nsplit = 1;
+  float* ws = nullptr;
+  void *x = nullptr, *h = nullptr, *qkv = nullptr, *attn = nullptr, *act = nullptr;
+  float *rope = nullptr, *logits = nullptr, *blk_max = nullptr, *part_o = nullptr, *part_ml = nullptr;
+  uint32_t *blk_idx = nullptr, *tok[2] = {nullptr, nullptr};
+  int32_t* rowtab = nullptr;
+  unsigned* ctr = nullptr;
+  uint64_t* pass_pages = nullptr;
+};
+
+// final RMSNorm + lm_head + argmax of `rows` rows of gc.x (bf16, pitch H) -> logits rows / token vector entries from `row0` on
+static void gen_head(aha_model* m, GenCall& gc, int row0, int rows, uint32_t* tok_out) {
+  const aha_model_desc& c = m->desc;
+  const int H = c.hidden_size, tiles = gemv_rows_num_tiles(gc.V);
+  {
+    ProfScope ps(m, "elem", (double)rows * H * 4, 0);
+    launch_rmsnorm_rows((const bf16_t*)gc.x + (int64_t)row0 * H, m->final_norm, (bf16_t*)gc.h + (int64_t)row0 * H, rows, H, H, H, c.rms_norm_eps,
+                        m->stream);
+  }
+  GemvRowsArgs g{};
+  g.W = m->lm_head; g.x = (const bf16_t*)gc.h + (int64_t)row0 * H; g.ldx = H; g.N = gc.V; g.K = H;
+  g.y_f32 = gc.logits + (int64_t)row0 * gc.V; g.ldf = gc.V;
+  g.blk_max = gc.blk_max + (int64_t)row0 * tiles; g.blk_idx = gc.blk_idx + (int64_t)row0 * tiles;
+  gemv_rows_groups(m, g, GEMV_LOGITS, rows, gc.ws);
+  ProfScope ps(m, "argmax", 0, 0);
+  launch_argmax_rows(gc.blk_max + (int64_t)row0 * tiles, gc.blk_idx + (int64_t)row0 * tiles, tiles, rows, tok_out + row0, m->stream);
+}
+
+// One packed prefill pass over sequences j0 .. j0+n_seg-1 (ids: theirs, packed); sequence j's cache starts on logical page page0[j].
+static int generate_prefill_pass(aha_model* m, GenCall& gc, const uint32_t* ids, const size_t* lens, int j0, int n_seg,
+                                 const std::vector<int64_t>& page0) {
+  const aha_model_desc& c = m->desc;
+  const int H = c.hidden_size, nq = c.num_attention_heads * c.head_dim;
+  hipStream_t st = m->stream;
+  // plan as in embed_pass, but the pass's pages are a table of their own: pass page p = the sequence's logical page, so its decode pages
+  // (not written here) never appear in the rope kernel's page list
+  std::vector<int32_t> seg(3 * (size_t)n_seg);
+  std::vector<uint64_t> pages;
+  int S = 0;
+  for (int j = 0; j < n_seg; ++j) {
+    const int len = (int)lens[j];
+    seg[3 * j] = S, seg[3 * j + 1] = len, seg[3 * j + 2] = (int32_t)pages.size();
+    for (int p = 0; p * KV_PAGE_TOKENS < len; ++p) pages.push_back(m->h_page_ptrs[(size_t)page0[j0 + j] + p]);
+    S += len;
+  }
+  const int npages = (int)pages.size();
+  constexpr int QB = 64;
+  std::vector<std::pair<int, int>> items;
+  for (int j = 0; j < n_seg; ++j)
+    for (int b = 0; b * QB < seg[3 * j + 1]; ++b) items.emplace_back(j, b);
+  auto cost = [&](const std::pair<int, int>& it) { return std::min(seg[3 * it.first + 1], (it.second + 1) * QB); };
+  std::stable_sort(items.begin(), items.end(), [&](const auto& x, const auto& y) { return cost(x) > cost(y); });
+  const int n_items = (int)items.size();
+  const size_t o_seg = 0, o_items = o_seg + seg.size(), o_slot = o_items + 2 * (size_t)n_items, o_prow = o_slot + S,
+               o_last = o_prow + 2 * (size_t)npages, n_tab = o_last + n_seg;
+  std::vector<int32_t> tab(n_tab);
+  std::copy(seg.begin(), seg.end(), tab.begin());
+  for (int i = 0; i < n_items; ++i) tab[o_items + 2 * i] = items[i].first, tab[o_items + 2 * i + 1] = items[i].second;
+  std::vector<int32_t> pos(3 * (size_t)S);
+  for (int j = 0; j < n_seg; ++j) {
+    const int r0 = seg[3 * j], len = seg[3 * j + 1], p0 = seg[3 * j + 2];
+    for (int i = 0; i < len; ++i) {
+      tab[o_slot + r0 + i] = p0 * KV_PAGE_TOKENS + i;
+      for (int a = 0; a < 3; ++a) pos[(size_t)a * S + r0 + i] = i;
+    }
+    for (int p = 0; p * KV_PAGE_TOKENS < len; ++p) {
+      tab[o_prow + 2 * (size_t)(p0 + p)] = r0 + p * KV_PAGE_TOKENS;
+      tab[o_prow + 2 * (size_t)(p0 + p) + 1] = std::min(KV_PAGE_TOKENS, len - p * KV_PAGE_TOKENS);
+    }
+    tab[o_last + j] = r0 + len - 1;
+  }
+  int rc;
+  if ((rc = ensure_prefill_scratch(m, (size_t)S))) return rc;
+  if (m->p_seg_cap < n_tab) {
+    AHA_HIP_CHECK(hipStreamSynchronize(st));
+    if (m->p_seg) AHA_HIP_CHECK(hipFree(m->p_seg));
+    m->p_seg = nullptr;
+    m->p_seg_cap = 0;
+    const size_t want = std::max(n_tab, (size_t)4096);
+    hipError_t e = hipMalloc((void**)&m->p_seg, want * 4);
+    if (e != hipSuccess) {
+      set_error(std::string("generate_batch: hipMalloc failed: ") + hipGetErrorString(e));
+      return e == hipErrorOutOfMemory ? AHA_ERR_OOM : AHA_ERR_HIP;
+    }
+    m->p_seg_cap = want;
+  }
+  AHA_HIP_CHECK(hipStreamSynchronize(st));   // the previous pass's copies out of the staging buffer have landed
+  const size_t n_stage = 4 * (size_t)S + n_tab;
+  if (n_stage > m->h_embed_stage_cap) {
+    if (m->h_embed_stage) AHA_HIP_CHECK(hipHostFree(m->h_embed_stage));
+    m->h_embed_stage = nullptr;
+    m->h_embed_stage_cap = 0;
+    AHA_HIP_CHECK(hipHostMalloc((void**)&m->h_embed_stage, n_stage * 4));
+    m->h_embed_stage_cap = n_stage;
+  }
+  int32_t* hs = m->h_embed_stage;
+  memcpy(hs, ids, (size_t)S * 4);
+  memcpy(hs + S, pos.data(), pos.size() * 4);
+  memcpy(hs + 4 * (size_t)S, tab.data(), n_tab * 4);
+  GemmWorkspaceScope ws_scope(m->p_gemm_ws, m->gemm_ws_bytes, m->d_sk_ctrs);
+  AHA_HIP_CHECK(hipMemcpyAsync(m->p_ids, hs, (size_t)S * 4, hipMemcpyHostToDevice, st));
+  AHA_HIP_CHECK(hipMemcpyAsync(m->p_pos, hs + S, pos.size() * 4, hipMemcpyHostToDevice, st));
+  AHA_HIP_CHECK(hipMemcpyAsync(m->p_seg, hs + 4 * (size_t)S, n_tab * 4, hipMemcpyHostToDevice, st));
+  AHA_HIP_CHECK(hipMemcpy(gc.pass_pages, pages.data(), pages.size() * 8, hipMemcpyHostToDevice));
+  {
+    ProfScope ps(m, "elem", (double)S * H * 4, 0);
+    launch_embed_gather(m->embed, m->p_ids, m->p_x, S, H, st);
+  }
+  launch_rope_table(m->p_pos, S, m->d_inv_freq, m->d_axis_map, S, m->p_rope, st);
+  double attn_flops = 0;
+  for (int j = 0; j < n_seg; ++j) attn_flops += 4.0 * seg[3 * j + 1] * (0.5 * seg[3 * j + 1]) * nq;
+  if ((rc = packed_layers(m, S, gc.pass_pages, m->p_seg + o_seg, m->p_seg + o_items, n_items, m->p_seg + o_slot, m->p_seg + o_prow, npages,
+                          attn_flops)))
+    return rc;
+  // every sequence's last row -> gc.x row j0 + j, then the head -> first tokens into token vector 0
+  launch_embed_gather(m->p_x, reinterpret_cast<const uint32_t*>(m->p_seg + o_last), (bf16_t*)gc.x + (int64_t)j0 * H, n_seg, H, st);
+  gen_head(m, gc, j0, n_seg, gc.tok[0]);
+  AHA_HIP_CHECK(hipGetLastError());
+  AHA_HIP_CHECK(hipStreamSynchronize(st));   // the pass page table and the staging buffer are reused by the next pass
+  return AHA_OK;
+}
+
+int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new, size_t max_tokens_per_pass,
+                         uint32_t* tokens_out, size_t* n_out, float* logits_out) {
+  const aha_model_desc& c = m->desc;
+  if (!ids || !seq_lens || !tokens_out || !n_out) {
+    set_error("generate_batch: null input_ids / seq_lens / tokens_out / n_out");
+    return AHA_ERR_INVALID;
+  }
+  if (n_seqs == 0) {
+    set_error("generate_batch: empty batch (n_seqs == 0)");
+    return AHA_ERR_INVALID;
+  }
+  if (max_new == 0) {
+    set_error("generate_batch: max_new must be at least 1");
+    return AHA_ERR_INVALID;
+  }
+  if (c.arch != AHA_ARCH_QWEN3 && c.arch != AHA_ARCH_QWEN3VL) {
+    set_error("generate_batch: Qwen3 and text-only Qwen3-VL only");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  if (m->tp_size > 1 || m->cp_size > 1 || c.head_dim != 128) {
+    set_error("generate_batch: a single-GPU model with head_dim 128 only (no tensor / context parallelism)");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  if (n_seqs > ((size_t)1 << 20) || max_new > ((size_t)1 << 20)) {
+    set_error("generate_batch: at most 2^20 sequences and 2^20 new tokens");
+    return AHA_ERR_INVALID;
+  }
+  size_t total = 0;
+  for (size_t j = 0; j < n_seqs; ++j) {
+    if (seq_lens[j] == 0) {
+      set_error("generate_batch: empty input_ids of sequence " + std::to_string(j));
+      return AHA_ERR_INVALID;
+    }
+    if (seq_lens[j] + max_new > (size_t)1 << 24) {
+      set_error("generate_batch: sequence " + std::to_string(j) + " would grow past 2^24 tokens");
+      return AHA_ERR_INVALID;
+    }
+    for (size_t i = 0; i < seq_lens[j]; ++i)
+      if (ids[total + i] >= (uint32_t)c.vocab_size) {
+        set_error("token id out of range in sequence " + std::to_string(j) + " at position " + std::to_string(i));
+        return AHA_ERR_INVALID;
+      }
+    total += seq_lens[j];
+  }
+  AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
+  int rc = model_clear_cache(m);
+  if (rc) return rc;
+  struct ClearGuard {
+    aha_model* m;
+    ~ClearGuard() { model_clear_cache(m); }
+  } guard{m};
+  hipStream_t st = m->stream;
+  const int n = (int)n_seqs, L = c.num_hidden_layers;
+  const int H = c.hidden_size, I = c.intermediate_size, nh = c.num_attention_heads, kvh = c.num_key_value_heads, g = nh / kvh;
+  const int nq = nh * 128, nkv = kvh * 128, V = c.vocab_size;
+  // every sequence's pages, reserved up front: ceil((len + max_new) / 64) consecutive logical pages
+  std::vector<int64_t> page0(n);
+  size_t npages = 0;
+  for (int j = 0; j < n; ++j) {
+    page0[j] = (int64_t)npages;
+    npages += (seq_lens[j] + max_new + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
+  }
+  if ((rc = model_ensure_pages(m, npages * KV_PAGE_TOKENS))) return rc;
+  DevBufs bufs{st, {}, {}};
+  GenCall gc;
+  gc.n = n, gc.V = V, gc.H = H;
+  for (int j = 0; j < n; ++j) gc.max_nsplit = std::max(gc.max_nsplit, attn_decode_nsplit((int)(seq_lens[j] + max_new), g, m->max_nsplit));
+  size_t ws = 0;
+  const int shapes[5][2] = {{nq + 2 * nkv, H}, {H, nq}, {2 * I, H}, {H, I}, {V, H}};
+  for (auto& sh : shapes) ws = std::max(ws, gemv_rows_ws_floats(std::min(n, GEN_ROW_GROUP), sh[0], sh[1]));
+  const int tiles = gemv_rows_num_tiles(V);
+  size_t max_pass_pages = 0;
+  for (int j = 0; j < n; ++j) max_pass_pages += (seq_lens[j] + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
+  int32_t* h_rowtab = nullptr;
+  uint32_t* h_tok = nullptr;
+  if ((rc = bufs.alloc(&gc.ws, ws)) || (rc = bufs.alloc((bf16_t**)&gc.x, (size_t)n * H)) || (rc = bufs.alloc((bf16_t**)&gc.h, (size_t)n * H)) ||
+      (rc = bufs.alloc((bf16_t**)&gc.qkv, (size_t)n * (nq + 2 * nkv))) || (rc = bufs.alloc((bf16_t**)&gc.attn, (size_t)n * nq)) ||
+      (rc = bufs.alloc((bf16_t**)&gc.act, (size_t)n * I)) || (rc = bufs.alloc(&gc.rope, (size_t)n * 128)) ||
+      (rc = bufs.alloc(&gc.logits, (size_t)n * V)) || (rc = bufs.alloc(&gc.blk_max, (size_t)n * tiles)) ||
+      (rc = bufs.alloc(&gc.blk_idx, (size_t)n * tiles)) || (rc = bufs.alloc(&gc.tok[0], (size_t)n)) || (rc = bufs.alloc(&gc.tok[1], (size_t)n)) ||
+      (rc = bufs.alloc(&gc.rowtab, (size_t)n * GEN_ROW_WORDS)) || (rc = bufs.alloc(&gc.ctr, (size_t)n * kvh * 32, true)) ||
+      (rc = bufs.alloc(&gc.part_o, (size_t)n * gc.max_nsplit * nq)) || (rc = bufs.alloc(&gc.part_ml, (size_t)n * gc.max_nsplit * nh * 2)) ||
+      (rc = bufs.alloc(&gc.pass_pages, max_pass_pages)) || (rc = bufs.alloc_host(&h_rowtab, (size_t)n * GEN_ROW_WORDS)) ||
+      (rc = bufs.alloc_host(&h_tok, (size_t)n)))
+    return rc;
+
+  // ---- prefill: packed passes (embed_batch's pass rule) ----
+  const size_t budget = std::min(max_tokens_per_pass ? max_tokens_per_pass : EMBED_PASS_ROWS, (size_t)1 << 24);
+  {
+    size_t j = 0, off = 0;
+    while (j < n_seqs) {
+      size_t rows = 0, slots = 0, k = j;
+      while (k < n_seqs) {
+        const size_t len = seq_lens[k], sl = (len + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS * KV_PAGE_TOKENS;
+        if (k > j && (rows + len > budget || slots + sl > 2 * budget)) break;
+        rows += len, slots += sl, ++k;
+      }
+      if ((rc = generate_prefill_pass(m, gc, ids + off, seq_lens + j, (int)j, (int)(k - j), page0))) return rc;
+      off += rows;
+      j = k;
+    }
+  }
+  AHA_HIP_CHECK(hipMemcpyAsync(h_tok, gc.tok[0], (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  AHA_HIP_CHECK(hipStreamSynchronize(st));
+  auto is_stop = [&](uint32_t t) {
+    for (int e = 0; e < c.n_stop_tokens; ++e)
+      if (t == c.stop_tokens[e]) return true;
+    return false;
+  };
+  auto copy_logits = [&](int row, int j) -> int {
+    if (logits_out) AHA_HIP_CHECK(hipMemcpy(logits_out + (size_t)j * V, gc.logits + (size_t)row * V, (size_t)V * 4, hipMemcpyDeviceToHost));
+    return AHA_OK;
+  };
+  std::vector<int> active, src_row(n);
+  for (int j = 0; j < n; ++j) {
+    tokens_out[(size_t)j * max_new] = h_tok[j];   // the first token never ends a sequence (generate.rs:131-134)
+    n_out[j] = 1;
+    src_row[j] = j;
+    if (max_new == 1) {
+      if ((rc = copy_logits(j, j))) return rc;
+    } else {
+      active.push_back(j);
+    }
+  }
+
+  // ---- decode ----
+  std::vector<unsigned> ctr_acc(n, 0u);
+  int cur = 0;
+  while (!active.empty()) {
+    const int R = (int)active.size();
+    int max_split = 1;
+    for (int r = 0; r < R; ++r) {
+      const int j = active[r];
+      const int kv_len = (int)(seq_lens[j] + n_out[j]);   // the cache after this step's append
+      const int ns = attn_decode_nsplit(kv_len, g, m->max_nsplit);
+      int32_t* t = h_rowtab + (size_t)r * GEN_ROW_WORDS;
+      t[GEN_ROW_PAGE0] = (int32_t)page0[j];
+      t[GEN_ROW_KVLEN] = kv_len;
+      t[GEN_ROW_NSPLIT] = ns;
+      t[GEN_ROW_CTR] = (int32_t)ctr_acc[r];
+      t[GEN_ROW_POS] = kv_len - 1;
+      t[GEN_ROW_SRC] = src_row[j];
+      t[6] = t[7] = 0;
+      if (ns > 1) ctr_acc[r] += (unsigned)L * (unsigned)ns;   // a single split never touches its counter
+      max_split = std::max(max_split, ns);
+    }
+    AHA_HIP_CHECK(hipMemcpyAsync(gc.rowtab, h_rowtab, (size_t)R * GEN_ROW_WORDS * 4, hipMemcpyHostToDevice, st));
+    {
+      ProfScope ps(m, "elem", (double)R * H * 4, 0);
+      launch_gen_embed(m->embed, gc.tok[cur], gc.rowtab, R, gc.x, H, m->d_inv_freq, m->d_axis_map, gc.rope, st);
+    }
+    double kv_tokens = 0;
+    for (int r = 0; r < R; ++r) kv_tokens += h_rowtab[(size_t)r * GEN_ROW_WORDS + GEN_ROW_KVLEN];
+    for (int li = 0; li < L; ++li) {
+      const LayerWeights& Lw = m->layers[li];
+      {   // h = RMSNorm(x); qkv = h Wqkv^T                      (qwen3/model.rs:79, modules.rs:538-552)
+        {
+          ProfScope ps(m, "elem", (double)R * H * 4, 0);
+          launch_rmsnorm_rows(gc.x, Lw.in_norm, gc.h, R, H, H, H, c.rms_norm_eps, st);
+        }
+        GemvRowsArgs a{};
+        a.W = Lw.wqkv; a.x = gc.h; a.ldx = H; a.y = gc.qkv; a.ldy = nq + 2 * nkv; a.N = nq + 2 * nkv; a.K = H;
+        gemv_rows_groups(m, a, GEMV_STORE, R, gc.ws);
+      }
+      {   // q/k norm + rope + KV append + attention of every row over its own pages (modules.rs:544-574, 757-813)
+        AttnDecodeBatchArgs b{};
+        b.qkv = gc.qkv; b.q_norm_w = Lw.q_norm; b.k_norm_w = Lw.k_norm; b.rope = gc.rope; b.page_ptrs = m->d_page_ptrs;
+        b.layer_off = (uint64_t)li * m->layer_stride; b.row_tab = gc.rowtab; b.part_o = gc.part_o; b.part_ml = gc.part_ml; b.o = gc.attn;
+        b.head_ctr = gc.ctr; b.ctr_step = li + 1; b.nh = nh; b.kvh = kvh; b.max_nsplit = gc.max_nsplit; b.eps = c.rms_norm_eps;
+        b.scale = m->attn_scale;
+        ProfScope ps(m, "attn_decode_batch", kv_tokens * 2 * nkv * 2 + (double)R * (nq + 2 * nkv) * 2, 4.0 * kv_tokens * nq);
+        launch_attn_decode_batch(b, R, max_split, st);
+      }
+      {   // x = x + attn Wo^T                                    (modules.rs:577, qwen3/model.rs:81)
+        GemvRowsArgs a{};
+        a.W = Lw.wo; a.x = gc.attn; a.ldx = nq; a.residual = gc.x; a.y = gc.x; a.ldy = H; a.N = H; a.K = nq;
+        gemv_rows_groups(m, a, GEMV_RESIDUAL, R, gc.ws);
+      }
+      {   // act = silu(h Wg^T) * (h Wu^T), h = RMSNorm(x)        (qwen3/model.rs:83, modules.rs:81-84)
+        {
+          ProfScope ps(m, "elem", (double)R * H * 4, 0);
+          launch_rmsnorm_rows(gc.x, Lw.post_norm, gc.h, R, H, H, H, c.rms_norm_eps, st);
+        }
+        GemvRowsArgs a{};
+        a.W = Lw.wgu; a.x = gc.h; a.ldx = H; a.y = gc.act; a.ldy = I; a.N = 2 * I; a.K = H;
+        gemv_rows_groups(m, a, GEMV_SILU_MUL, R, gc.ws);
+      }
+      {   // x = x + act Wd^T                                     (modules.rs:85, qwen3/model.rs:86)
+        GemvRowsArgs a{};
+        a.W = Lw.wdown; a.x = gc.act; a.ldx = I; a.residual = gc.x; a.y = gc.x; a.ldy = H; a.N = H; a.K = I;
+        gemv_rows_groups(m, a, GEMV_RESIDUAL, R, gc.ws);
+      }
+    }
+    gen_head(m, gc, 0, R, gc.tok[cur ^ 1]);
+    AHA_HIP_CHECK(hipGetLastError());
+    AHA_HIP_CHECK(hipMemcpyAsync(h_tok, gc.tok[cur ^ 1], (size_t)R * 4, hipMemcpyDeviceToHost, st));
+    AHA_HIP_CHECK(hipStreamSynchronize(st));
+    std::vector<int> next;
+    for (int r = 0; r < R; ++r) {
+      const int j = active[r];
+      const uint32_t t = h_tok[r];
+      tokens_out[(size_t)j * max_new + n_out[j]++] = t;
+      src_row[j] = r;
+      if (is_stop(t) || n_out[j] == max_new) {
+        if ((rc = copy_logits(r, j))) return rc;
+      } else {
+        next.push_back(j);
+      }
+    }
+    active.swap(next);
+    cur ^= 1;
   }
   return AHA_OK;
 }

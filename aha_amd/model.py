@@ -334,6 +334,21 @@ class HipInferenceModel:
                                         out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
+    def generate_batch(self, prompts: Sequence[Sequence[int]], max_new: int, max_tokens_per_pass: int = 0, want_logits: bool = False):
+        """Greedy generation of every prompt at once (aha_hip_generate_batch): per prompt, the tokens generate_generic(device_loop=True)
+        yields for it alone at temperature 0.  Returns a list of token lists, and with want_logits also the (len(prompts), vocab) float32
+        logits that chose each prompt's last token."""
+        seqs = [np.asarray(x, dtype=np.uint32).reshape(-1) for x in prompts]
+        ids = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0, np.uint32))
+        lens = np.ascontiguousarray([s.size for s in seqs], dtype=np.uint64)
+        toks = np.zeros((len(seqs), max(int(max_new), 1)), dtype=np.uint32)
+        n_out = np.zeros(len(seqs), dtype=np.uint64)
+        logits = np.empty((len(seqs), self.text_cfg.vocab_size), dtype=np.float32) if want_logits else None
+        check(lib().aha_hip_generate_batch(self.handle, ids.ctypes.data, lens.ctypes.data, len(seqs), int(max_new), int(max_tokens_per_pass),
+                                           toks.ctypes.data, n_out.ctypes.data, None if logits is None else logits.ctypes.data))
+        out = [[int(t) for t in toks[j, :int(n_out[j])]] for j in range(len(seqs))]
+        return (out, logits) if want_logits else out
+
     def embed_multi(self, inputs: Sequence[Sequence[int]]) -> np.ndarray:
         if len(inputs) == 0:
             raise ValueError("embedding input cannot be empty")  # qwen3_embedding/mod.rs:39-41
@@ -489,3 +504,13 @@ def generate_generic(model: HipInferenceModel, input_ids: Sequence[int], max_tok
     completion_secs = time.perf_counter() - t0
     model.clear_cache()
     return generated, Usage(len(input_ids), prompt_secs, len(generated), completion_secs)
+
+
+def generate_generic_batch(model: HipInferenceModel, prompts: Sequence[Sequence[int]], max_tokens: int, max_tokens_per_pass: int = 0):
+    """generate_generic at temperature 0 for many text prompts in one call (HipInferenceModel.generate_batch).  Returns (per-prompt
+    generated token ids, Usage over all prompts: prompt / completion token totals; prompt_secs 0 and completion_secs the whole call,
+    as prefill and decode are not timed apart)."""
+    t0 = time.perf_counter()
+    out = model.generate_batch(prompts, max_tokens, max_tokens_per_pass)
+    secs = time.perf_counter() - t0
+    return out, Usage(sum(len(p) for p in prompts), 0.0, sum(len(o) for o in out), secs)

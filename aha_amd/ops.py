@@ -8,6 +8,7 @@ from __future__ import annotations
 import math
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -198,3 +199,47 @@ def logmel(samples: torch.Tensor) -> torch.Tensor:
     out = torch.empty(128, samples.numel() // 160, dtype=torch.float32, device=samples.device)
     check(lib().aha_hip_logmel(_ptr(samples), samples.numel(), _ptr(out), _stream()))
     return out
+
+
+# ---- batched decode (aha_hip_generate_batch's kernels) ----------------------------------------------------------------------
+GEMV_ROWS_STORE, GEMV_ROWS_RESIDUAL, GEMV_ROWS_SILU_MUL, GEMV_ROWS_LOGITS = 0, 1, 2, 3
+
+
+def gemv_rows(W: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, residual: Optional[torch.Tensor] = None):
+    """y[R, N] = x[R, K] . W[N, K]^T for 1 <= R <= 32, weights streamed once.  epi STORE / RESIDUAL -> (R, N) bf16; SILU_MUL (W in the
+    16-row gate / up block layout) -> (R, N/2) bf16; LOGITS -> ((R, N) f32 logits, (R,) int64 argmax)."""
+    _chk(W, x, residual)
+    N, K = W.shape
+    R = x.shape[0]
+    y = logits = am = None
+    if epi == GEMV_ROWS_LOGITS:
+        logits = torch.empty(R, N, dtype=torch.float32, device=x.device)
+        am = torch.empty(R, dtype=torch.int32, device=x.device)
+    else:
+        y = torch.empty(R, N // 2 if epi == GEMV_ROWS_SILU_MUL else N, dtype=torch.bfloat16, device=x.device)
+    check(lib().aha_hip_gemv_rows(_ptr(W), _ptr(x), _ptr(y), R, N, K, epi, _ptr(residual), _ptr(logits), _ptr(am), _stream()))
+    return (logits, am.long()) if epi == GEMV_ROWS_LOGITS else y
+
+
+def attn_decode_batch(qkv: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: torch.Tensor, rope: torch.Tensor, page_ptrs: torch.Tensor,
+                      page0, kv_len, nh: int, kvh: int, eps: float, scale: float) -> torch.Tensor:
+    """Fused decode attention of R sequences in one launch: qkv (R, (nh+2kvh)*128) bf16, rope (R, 128) f32, page_ptrs (P,) int64 device
+    page addresses, page0 / kv_len: per-row first page and cache length after the append (host ints).  -> (R, nh*128) bf16."""
+    _chk(qkv, q_norm_w, k_norm_w, rope, page_ptrs)
+    R = qkv.shape[0]
+    p0 = np.ascontiguousarray(np.asarray(page0, dtype=np.int32))
+    kl = np.ascontiguousarray(np.asarray(kv_len, dtype=np.int32))
+    o = torch.empty(R, nh * 128, dtype=torch.bfloat16, device=qkv.device)
+    check(lib().aha_hip_attn_decode_batch(_ptr(qkv), _ptr(q_norm_w), _ptr(k_norm_w), _ptr(rope), _ptr(page_ptrs), p0.ctypes.data,
+                                          kl.ctypes.data, R, nh, kvh, eps, scale, _ptr(o), _stream()))
+    return o
+
+
+def debug_attn_decode_fused(qkv_row: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: torch.Tensor, rope_row: torch.Tensor,
+                            page_ptrs: torch.Tensor, kv_len: int, nh: int, kvh: int, eps: float, scale: float) -> torch.Tensor:
+    """The single-sequence fused decode attention kernel on one sequence whose pages are page_ptrs[0 ..]: -> (nh*128) bf16."""
+    _chk(qkv_row, q_norm_w, k_norm_w, rope_row, page_ptrs)
+    o = torch.empty(nh * 128, dtype=torch.bfloat16, device=qkv_row.device)
+    check(lib().aha_hip_debug_attn_decode_fused(_ptr(qkv_row), _ptr(q_norm_w), _ptr(k_norm_w), _ptr(rope_row), _ptr(page_ptrs), int(kv_len),
+                                                nh, kvh, eps, scale, _ptr(o), _stream()))
+    return o

@@ -172,6 +172,20 @@ int aha_hip_embed(aha_model* m, const uint32_t* input_ids, size_t n_ids, float* 
 int aha_hip_embed_batch(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_tokens_per_pass,
                         float* out);
 
+/* Batched greedy generation: for each of n_seqs prompts (packed in input_ids, lengths seq_lens), what generate_generic
+ * (/root/reference/src/models/common/generate.rs:115-159, which serves /v1/chat/completions one prompt at a time) yields at temperature 0
+ * for that prompt alone on a cleared model.  The first token is the argmax of the prefill's last-row logits and never ends a sequence;
+ * up to max_new - 1 greedy tokens follow, ending at (and keeping) the first stop token.  Row j of tokens_out (n_seqs x max_new) holds
+ * n_out[j] tokens; logits_out (n_seqs x vocab f32, may be NULL) receives the logits that chose each sequence's last token (the bf16
+ * Linear output read as f32).  Argmax = the first maximal index.
+ * Prefill runs as packed passes of at most max_tokens_per_pass rows (0: the embed_batch default); decode advances every unfinished sequence
+ * in one step per token, the weights streamed once per group of <= 32 rows.  Sequence j owns ceil((len_j + max_new) / 64) pages of the
+ * cache, reserved before any work (AHA_ERR_OOM if they cannot be had); the cache is cleared before and after, on success and on error.
+ * AHA_ARCH_QWEN3 and text-only AHA_ARCH_QWEN3VL on one GPU with head_dim 128, else AHA_ERR_UNSUPPORTED.  AHA_ERR_INVALID: a null
+ * pointer, n_seqs == 0, an empty prompt, max_new == 0, or an id >= vocab_size (naming the sequence and position). */
+int aha_hip_generate_batch(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
+                           size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* logits_out);
+
 /* ---- checkpoint directory -> model (XxxGenerateModel::init minus tokenizer / chat template) --------------------------
  * aha_hip_config_parse: <dir>/config.json -> aha_model_desc, the same field mapping serde does into Qwen3Config
  *   (/root/reference/src/models/qwen3/config.rs:4-27), Qwen3VLConfig (qwen3vl/config.rs:51-133, text_config / vision_config,
@@ -413,6 +427,23 @@ int aha_hip_qknorm_rope(const void* qkv, const void* q_norm_w, const void* k_nor
 /* D6/D7 decode attention over a contiguous (kvh, L, d) K/V (op-level variant): o (nh*d) bf16. */
 int aha_hip_attn_decode(const void* q, const void* k, const void* v, void* o, int32_t nh, int32_t kvh, int32_t d,
                         int32_t L, float scale, void* stream);
+/* Batched decode (aha_hip_generate_batch's kernels), op level.
+ * aha_hip_gemv_rows: y[R, N] = x[R, K] . W[N, K]^T for 1 <= R <= 32, the weights read once (the step's projections of
+ * /root/reference/src/models/qwen3/model.rs:79-86 for R sequences).  x (R, K) bf16, K % 8 == 0.  epi 0: y (R, N) bf16; 1: y = residual +
+ * Linear (both bf16 (R, N), may alias); 2: SiLU(gate) * up with W in the 16-row gate / up block layout (N = 2I), y (R, I) bf16; 3: logits
+ * (R, N) f32 and argmax_out (R) u32 (device), the first maximal index.  Each output row depends only on its own input row. */
+int aha_hip_gemv_rows(const void* W, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi, const void* residual,
+                      float* logits, uint32_t* argmax_out, void* stream);
+/* aha_hip_attn_decode_batch: the fused decode attention block (QKNormAttention::forward, modules.rs:538-577, without o_proj) of `rows`
+ * sequences in one launch.  qkv (rows, (nh + 2kvh) * 128) bf16; q_norm_w / k_norm_w (128) bf16; rope (rows, 128) f32 cos | sin, bf16
+ * values; page_ptrs: device table of page addresses (pages of kvh K blocks then kvh V blocks, 16 KB each); row r's pages are
+ * page_ptrs[page0[r]], ..., its new token goes to slot kv_len[r] - 1 (page0 / kv_len: HOST arrays).  o (rows, nh * 128) bf16. */
+int aha_hip_attn_decode_batch(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
+                              const int32_t* page0, const int32_t* kv_len, int32_t rows, int32_t nh, int32_t kvh, float eps, float scale,
+                              void* o, void* stream);
+/* Debug: the single-sequence fused decode attention kernel (the decode step's) on one sequence whose pages are page_ptrs[0 ..]. */
+int aha_hip_debug_attn_decode_fused(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
+                                    int32_t kv_len, int32_t nh, int32_t kvh, float eps, float scale, void* o, void* stream);
 /* D7 prefill attention, causal with q position i attending to k positions <= kv_offset + i; q (S, nh*d),
  * k/v (L, kvh*d) token-major, L = kv_offset + S.  causal = 0 gives full (ViT / audio encoder) attention.  d = 128, or 64 with
  * nh == kvh (the Qwen3-ASR audio encoder's geometry). */

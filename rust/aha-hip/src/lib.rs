@@ -206,6 +206,17 @@ pub mod sys {
             max_tokens_per_pass: usize,
             out: *mut f32,
         ) -> i32;
+        pub fn aha_hip_generate_batch(
+            m: *mut AhaModel,
+            ids: *const u32,
+            seq_lens: *const usize,
+            n_seqs: usize,
+            max_new: usize,
+            max_tokens_per_pass: usize,
+            tokens_out: *mut u32,
+            n_out: *mut usize,
+            logits_out: *mut f32,
+        ) -> i32;
         pub fn aha_hip_cache_len(m: *const AhaModel) -> usize;
         pub fn aha_hip_audio_resample(
             ctx: *mut AhaCtx,
@@ -424,6 +435,29 @@ impl Model {
             sys::aha_hip_embed_batch(self.model, ids.as_ptr(), lens.as_ptr(), lens.len(), max_tokens_per_pass, out.as_mut_ptr())
         })?;
         Ok(out)
+    }
+
+    /// `generate_generic` at temperature 0 for every prompt at once (aha_hip_generate_batch): per prompt, the greedy tokens it
+    /// yields alone, ending at (and keeping) the first stop token after the first token.  The cache is empty afterwards.
+    pub fn generate_batch(&mut self, prompts: &[&[u32]], max_new: usize, max_tokens_per_pass: usize) -> Result<Vec<Vec<u32>>, Error> {
+        let ids: Vec<u32> = prompts.iter().flat_map(|s| s.iter().copied()).collect();
+        let lens: Vec<usize> = prompts.iter().map(|s| s.len()).collect();
+        let mut toks = vec![0u32; prompts.len() * max_new.max(1)];
+        let mut n_out = vec![0usize; prompts.len()];
+        check(unsafe {
+            sys::aha_hip_generate_batch(
+                self.model,
+                ids.as_ptr(),
+                lens.as_ptr(),
+                lens.len(),
+                max_new,
+                max_tokens_per_pass,
+                toks.as_mut_ptr(),
+                n_out.as_mut_ptr(),
+                std::ptr::null_mut(),
+            )
+        })?;
+        Ok(n_out.iter().enumerate().map(|(j, &n)| toks[j * max_new..j * max_new + n].to_vec()).collect())
     }
 
     /// The greedy loop of `generate_generic` / `generate_stream_generic` (common/generate.rs:115-159, 161-368) kept on the

@@ -1,0 +1,128 @@
+"""Batched greedy generation (aha_hip_generate_batch) against serial decode_greedy, at Qwen3-0.6B and Qwen3-VL-8B text dimensions
+(configs.qwen3_0_6b / qwen3vl_8b_text, seeded random weights generated on the GPU, no stop tokens so every sequence runs to max_new).
+Prompts of --prompt tokens, --max-new new tokens.  Per batch size B:
+  * aggregate tokens/s of one generate_batch call over B prompts (prefill included) and the decode step time, taken as
+    (t(max_new) - t(1)) / (max_new - 1);
+  * serial: forward_initial + decode_greedy on --serial prompts one after the other, decode tokens/s of that loop;
+and, per projection shape, kernel A (gemv_rows) at R = 1, 16, 32 and above 32 rows (two row groups = the weights streamed twice), as
+weight bytes / time and its fraction of the 8 TB/s HBM peak.  One JSON object per line.
+    python scripts/bench_generate_batch.py [--only 0.6b,8b] [--batches 1,4,8,16,32,64] [--prompt 512] [--max-new 128]
+    python scripts/bench_generate_batch.py --once 8b:16     # one generate_batch call and nothing else (rocprofv3 --kernel-trace --stats)"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+HBM_PEAK = 8.0e12
+
+
+def model_for(name):
+    import torch
+    from aha_amd.configs import qwen3_0_6b, qwen3vl_8b_text
+    from aha_amd.model import HipInferenceModel
+    from aha_amd.weights import qwen3_text_weights
+    cfg = qwen3_0_6b() if name == "0.6b" else qwen3vl_8b_text()
+    cfg.eos_token_ids = []
+    w = qwen3_text_weights(cfg, seed=0, device="cuda")
+    m = HipInferenceModel(cfg, w)
+    del w
+    torch.cuda.empty_cache()
+    return cfg, m
+
+
+def prompts(n, L, vocab, seed=0):
+    g = np.random.default_rng(seed)
+    return [g.integers(0, min(vocab, 150000), size=L).astype(np.uint32).tolist() for _ in range(n)]
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    out = fn()
+    return time.perf_counter() - t0, out
+
+
+def bench_kernel_a(cfg, name):
+    import torch
+    from aha_amd import ops
+    H, I, V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
+    q, kv = cfg.num_attention_heads * 128, cfg.num_key_value_heads * 128
+    shapes = {"qkv": (q + 2 * kv, H), "o_proj": (H, q), "gate_up": (2 * I, H), "down": (H, I), "lm_head": (V, H)}
+    for sname, (N, K) in shapes.items():
+        W = torch.randn(N, K, device="cuda", dtype=torch.bfloat16) * 0.02
+        for R in (1, 16, 32, 64):
+            reps = 20
+            x = torch.randn(min(R, 32), K, device="cuda", dtype=torch.bfloat16)
+            epi = ops.GEMV_ROWS_LOGITS if sname == "lm_head" else ops.GEMV_ROWS_STORE
+            groups = (R + 31) // 32   # above 32 rows: one call per group of 32, each streaming the weights again
+            ops.gemv_rows(W, x, epi)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps * groups):
+                ops.gemv_rows(W, x, epi)
+            torch.cuda.synchronize()
+            # the op-level entry allocates its scratch and synchronises per call: an upper bound of the in-model kernel time
+            dt = (time.perf_counter() - t0) / reps
+            print(json.dumps({"kernel": "gemv_rows", "model": name, "shape": sname, "N": N, "K": K, "R": R, "us": round(dt * 1e6, 1),
+                              "weight_GBps": round(N * K * 2 * groups / dt / 1e9, 1), "hbm_frac": round(N * K * 2 * groups / dt / HBM_PEAK, 3)}),
+                  flush=True)
+        del W
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only", default="0.6b,8b")
+    ap.add_argument("--batches", default="1,4,8,16,32,64")
+    ap.add_argument("--prompt", type=int, default=512)
+    ap.add_argument("--max-new", type=int, default=128)
+    ap.add_argument("--serial", type=int, default=4)
+    ap.add_argument("--once", default="")
+    ap.add_argument("--no-kernel", action="store_true")
+    a = ap.parse_args()
+    import torch
+    from aha_amd import build
+    build.build()
+    if a.once:
+        name, B = a.once.split(":")
+        cfg, m = model_for(name)
+        ps = prompts(int(B), a.prompt, cfg.vocab_size)
+        m.generate_batch(ps, a.max_new)
+        torch.cuda.synchronize()
+        m.close()
+        return
+    for name in a.only.split(","):
+        cfg, m = model_for(name)
+        ps_all = prompts(max(int(b) for b in a.batches.split(",")), a.prompt, cfg.vocab_size)
+        # serial decode_greedy over the first --serial prompts
+        dec = 0.0
+        for p in ps_all[:a.serial]:
+            m.clear_cache()
+            _, tok = m.forward_initial(p, 0, want_logits=False)
+            torch.cuda.synchronize()
+            dt, toks = timed(lambda: m.decode_greedy(tok, len(p), a.max_new - 1))
+            dec += dt
+            m.clear_cache()
+        serial_tps = a.serial * (a.max_new - 1) / dec
+        print(json.dumps({"model": name, "serial_decode_tok_s": round(serial_tps, 1), "serial_step_ms": round(dec / (a.serial * (a.max_new - 1)) * 1e3, 3)}),
+              flush=True)
+        m.generate_batch(ps_all[:2], 4)   # warm-up
+        for B in (int(b) for b in a.batches.split(",")):
+            ps = ps_all[:B]
+            t1, _ = timed(lambda: m.generate_batch(ps, 1))
+            tn, out = timed(lambda: m.generate_batch(ps, a.max_new))
+            assert all(len(o) == a.max_new for o in out)
+            step = (tn - t1) / (a.max_new - 1)
+            print(json.dumps({"model": name, "B": B, "prompt": a.prompt, "max_new": a.max_new, "total_s": round(tn, 3),
+                              "aggregate_tok_s": round(B * a.max_new / tn, 1), "step_ms": round(step * 1e3, 3),
+                              "decode_tok_s": round(B / step, 1), "decode_vs_serial": round(B / step / serial_tps, 2)}), flush=True)
+        if not a.no_kernel:
+            bench_kernel_a(cfg, name)
+        m.close()
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
