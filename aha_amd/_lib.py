@@ -15,6 +15,18 @@ AHA_ARCH_QWEN3, AHA_ARCH_QWEN3VL, AHA_ARCH_QWEN3ASR = 0, 1, 2
 ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF, ACT_SILU, ACT_SILU_MUL_PAIRS = 0, 1, 2, 3, 4
 
 
+AHA_SAMPLE_HAS_TOP_P, AHA_SAMPLE_HAS_TOP_K = 1, 2
+AHA_SAMPLE_NEED_LOGITS = 1
+
+
+class SamplingParams(C.Structure):
+    """aha_sampling_params (include/aha_hip.h); the Rust shim's AhaSamplingParams has the same fields in the same order."""
+    _fields_ = [
+        ("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32), ("repeat_penalty", C.c_float),
+        ("repeat_last_n", C.c_int32), ("flags", C.c_uint32), ("seed", C.c_uint64),
+    ]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [
         ("arch", C.c_int32),
@@ -134,6 +146,14 @@ SIGNATURES = {
     "aha_hip_embed": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "aha_hip_embed_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, _P]),
     "aha_hip_generate_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P]),
+    "aha_hip_generate_batch_sampled": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(SamplingParams), C.c_size_t, C.c_size_t, _P, _P, _P]),
+    "aha_hip_sample_rows": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "aha_hip_sampler_create": (C.c_int, [C.POINTER(SamplingParams), _P]),
+    "aha_hip_sampler_destroy": (None, [_P]),
+    "aha_hip_sampler_plan": (C.c_int, [_P, C.c_size_t, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                       C.POINTER(C.c_size_t)]),
+    "aha_hip_sampler_pick": (C.c_int, [_P, _P, _P, C.c_int32, C.c_float, C.c_float, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "aha_hip_sampler_rng_words": (C.c_uint64, [_P]),
     "aha_hip_gemv_rows": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "aha_hip_attn_decode_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "aha_hip_debug_attn_decode_fused": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),

@@ -9,6 +9,7 @@
 
 #include "common.h"
 #include "model.h"
+#include "sampler.h"
 #include "audio.h"
 #include "vision.h"
 
@@ -519,6 +520,73 @@ int aha_hip_gemv_rows(const void* W, const void* x, void* y, int32_t R, int32_t 
   API_GUARD_END
 }
 
+int aha_hip_sample_rows(const float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* k, const float* temperature,
+                        const float* repeat_penalty, const uint32_t* context, const size_t* context_offsets, float* vals_out,
+                        uint32_t* idx_out, float* ms_out, void* stream) {
+  API_GUARD_BEGIN
+  if (!logits || R < 1 || V < 1 || ld < V || !k || !temperature || !repeat_penalty || !context_offsets || !vals_out || !idx_out || !ms_out) {
+    set_error("sample_rows: bad arguments (R >= 1, ld >= V >= 1, per-row k / temperature / repeat_penalty / context_offsets, outputs)");
+    return AHA_ERR_INVALID;
+  }
+  for (int r = 0; r < R; ++r)
+    if (!sample_shape_ok(V, k[r]) || !(repeat_penalty[r] > 0.f) || context_offsets[r + 1] < context_offsets[r] ||
+        (context_offsets[r + 1] > context_offsets[r] && !context)) {
+      set_error("sample_rows: row " + std::to_string(r) + " needs 1 <= k <= 64, repeat_penalty > 0 and ordered context offsets");
+      return AHA_ERR_INVALID;
+    }
+  hipStream_t st = (hipStream_t)stream;
+  // the row table and the deduplicated in-vocabulary context of model.hip's sampled step
+  std::vector<int32_t> tab((size_t)R * SAMPLE_ROW_WORDS, 0);
+  std::vector<uint32_t> ctx;
+  for (int r = 0; r < R; ++r) {
+    int32_t* t = tab.data() + (size_t)r * SAMPLE_ROW_WORDS;
+    const size_t c0 = ctx.size();
+    if (repeat_penalty[r] != 1.0f) {
+      for (size_t i = context_offsets[r]; i < context_offsets[r + 1]; ++i)
+        if (context[i] < (uint32_t)V) ctx.push_back(context[i]);
+      std::sort(ctx.begin() + c0, ctx.end());
+      ctx.erase(std::unique(ctx.begin() + c0, ctx.end()), ctx.end());
+    }
+    const float inv_t = temperature[r] > 0.f ? (float)(1.0 / (double)temperature[r]) : 1.0f;
+    t[SAMPLE_ROW_LROW] = r;
+    t[SAMPLE_ROW_K] = k[r];
+    memcpy(&t[SAMPLE_ROW_INVT], &inv_t, 4);
+    memcpy(&t[SAMPLE_ROW_PEN], &repeat_penalty[r], 4);
+    t[SAMPLE_ROW_CTX0] = (int32_t)c0;
+    t[SAMPLE_ROW_NCTX] = (int32_t)(ctx.size() - c0);
+  }
+  const int nw = sample_stage1_waves(V);
+  const size_t cand = (size_t)R * (nw + 16) * 64;
+  int32_t* d_tab = nullptr;
+  uint32_t *d_ctx = nullptr, *d_cidx = nullptr;
+  float *d_cval = nullptr, *d_part = nullptr, *d_out = nullptr;
+  AHA_HIP_CHECK(hipMalloc((void**)&d_tab, tab.size() * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&d_ctx, std::max<size_t>(ctx.size(), 1) * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&d_cval, cand * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&d_cidx, cand * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&d_part, 2 * (size_t)R * nw * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&d_out, (size_t)R * SAMPLE_OUT_WORDS * 4));
+  AHA_HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+  if (!ctx.empty()) AHA_HIP_CHECK(hipMemcpyAsync(d_ctx, ctx.data(), ctx.size() * 4, hipMemcpyHostToDevice, st));
+  for (int stage = 0; stage < 3; ++stage)
+    launch_topk_rows(logits, ld, V, R, d_tab, d_ctx, d_cval, d_cidx, d_part, d_part + (size_t)R * nw, d_out, stage, st);
+  hipError_t err = hipGetLastError();
+  // {vals[64], max, sumexp, idx[64]} per row -> the three outputs
+  if (err == hipSuccess) err = hipMemcpy2DAsync(vals_out, 64 * 4, d_out, SAMPLE_OUT_WORDS * 4, 64 * 4, R, hipMemcpyDeviceToDevice, st);
+  if (err == hipSuccess) err = hipMemcpy2DAsync(ms_out, 2 * 4, d_out + 64, SAMPLE_OUT_WORDS * 4, 2 * 4, R, hipMemcpyDeviceToDevice, st);
+  if (err == hipSuccess) err = hipMemcpy2DAsync(idx_out, 64 * 4, d_out + 66, SAMPLE_OUT_WORDS * 4, 64 * 4, R, hipMemcpyDeviceToDevice, st);
+  hipStreamSynchronize(st);
+  hipFree(d_tab);
+  hipFree(d_ctx);
+  hipFree(d_cval);
+  hipFree(d_cidx);
+  hipFree(d_part);
+  hipFree(d_out);
+  AHA_HIP_CHECK(err);
+  return AHA_OK;
+  API_GUARD_END
+}
+
 static bool attn_batch_geometry_ok(int32_t nh, int32_t kvh) { return nh > 0 && kvh > 0 && nh % kvh == 0 && nh / kvh <= 16 && kvh <= 64; }
 
 int aha_hip_attn_decode_batch(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
@@ -791,6 +859,28 @@ int aha_hip_generate_batch(aha_model* m, const uint32_t* input_ids, const size_t
     return AHA_ERR_INVALID;
   }
   return model_generate_batch(m, input_ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, logits_out);
+  API_GUARD_END
+}
+int aha_hip_generate_batch_sampled(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs,
+                                   const aha_sampling_params* params, size_t max_new, size_t max_tokens_per_pass,
+                                   uint32_t* tokens_out, size_t* n_out, float* step_logits_out) {
+  API_GUARD_BEGIN
+  if (n_seqs && !params) {   // the parameters first: they are checked before anything touches the model or the device
+    set_error("generate_batch_sampled: null params");
+    return AHA_ERR_INVALID;
+  }
+  for (size_t j = 0; j < n_seqs && j < ((size_t)1 << 20); ++j) {
+    std::string why;
+    if (sampling_params_check(params[j], &why)) {
+      set_error("generate_batch_sampled: params of sequence " + std::to_string(j) + ": " + why);
+      return AHA_ERR_INVALID;
+    }
+  }
+  if (!m) {
+    set_error("null model");
+    return AHA_ERR_INVALID;
+  }
+  return model_generate_batch_sampled(m, input_ids, seq_lens, n_seqs, params, max_new, max_tokens_per_pass, tokens_out, n_out, step_logits_out);
   API_GUARD_END
 }
 int aha_hip_config_parse(const char* model_dir, aha_model_desc* out) {

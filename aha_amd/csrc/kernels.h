@@ -52,6 +52,16 @@ bool sample_shape_ok(int V, int k);
 void launch_repeat_penalty(const float* logits, float* work, const uint32_t* ctx, int n, float penalty, int V, hipStream_t st);
 void launch_topk_candidates(const float* x, int V, int k, float inv_temp, float* cand_val, unsigned* cand_idx, float* part_m,
                             float* part_s, float* out_val, unsigned* out_idx, float* out_ms, hipStream_t st);
+// The same pipeline for `rows` rows of f32 logits (pitch ld) in one launch per stage (stage 0: stage 1, 1: stage 2a, 2: stage 2b; the
+// caller scopes each for the profile), row s of `tab` (device, SAMPLE_ROW_WORDS int32 per row) naming its logits row, k, 1/T, penalty and
+// context slice of `ctx` (distinct ids < V).  Row s: cand_* [s * (sample_stage1_waves(V) + 16) * 64, ...), part_* [s * nw, ...), out
+// [s * SAMPLE_OUT_WORDS, ...) = {vals[64] f32, max, sumexp, idx[64] u32}.  Bit-identical per row to launch_repeat_penalty +
+// launch_topk_candidates on that row; the logits are only read.
+constexpr int SAMPLE_ROW_WORDS = 8;
+constexpr int SAMPLE_ROW_LROW = 0, SAMPLE_ROW_K = 1, SAMPLE_ROW_INVT = 2, SAMPLE_ROW_PEN = 3, SAMPLE_ROW_CTX0 = 4, SAMPLE_ROW_NCTX = 5;
+constexpr int SAMPLE_OUT_WORDS = 64 + 2 + 64;
+void launch_topk_rows(const float* logits, int64_t ld, int V, int rows, const int32_t* tab, const uint32_t* ctx, float* cand_val,
+                      unsigned* cand_idx, float* part_m, float* part_s, float* out, int stage, hipStream_t st);
 
 void launch_embed_gather(const void* table, const uint32_t* ids, void* out, int S, int H, hipStream_t st);
 void launch_rmsnorm_rows(const void* x, const void* w, void* y, int64_t rows, int dim, int64_t ldx, int64_t ldy,

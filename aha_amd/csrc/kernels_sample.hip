@@ -70,26 +70,39 @@ __global__ void repeat_penalty_kernel(const float* logits, float* work, const ui
 constexpr int S1_C = 8;                      // elements per lane in stage 1
 constexpr int S1_WAVE_ELEMS = 64 * S1_C;     // 512 logits per wave
 constexpr int S1_WAVES_PER_BLOCK = 4;
+__host__ __device__ constexpr int sample_stage1_waves_dev(int V) { return (V + S1_WAVE_ELEMS - 1) / S1_WAVE_ELEMS; }
 
-// stage 1: every wave reduces 512 consecutive logits to its k best and its softmax partial (max, sum exp((x - max) * inv_temp))
-__global__ __launch_bounds__(64 * S1_WAVES_PER_BLOCK) void topk_stage1_kernel(const float* x, int V, int k, float inv_temp,
-                                                                              float* cand_val, unsigned* cand_idx,
-                                                                              float* part_m, float* part_s) {
+// stage 1: every wave reduces 512 consecutive logits to its k best and its softmax partial (max, sum exp((x - max) * inv_temp)).
+// PEN: the row's repeat penalty is applied as the logits are loaded -- ctx[0 .. n_ctx) are DISTINCT in-vocabulary ids (the host
+// dedups them: apply_repeat_penalty's HashSet), so each hit is penalised once, from the untouched value, exactly as
+// repeat_penalty_kernel writes work[t].  The logits buffer itself is never written.
+template <bool PEN>
+__device__ __forceinline__ void topk_stage1_body(const float* x, int V, int k, float inv_temp, const uint32_t* ctx, int n_ctx,
+                                                 float penalty, int w, float* cand_val, unsigned* cand_idx, float* part_m, float* part_s) {
   const int lane = threadIdx.x & 63;
-  const int w = blockIdx.x * S1_WAVES_PER_BLOCK + (threadIdx.x >> 6);
   const int base = w * S1_WAVE_ELEMS;
   if (base >= V) return;
   float v[S1_C];
   unsigned id[S1_C];
-  float lm = -INFINITY;
 #pragma unroll
   for (int j = 0; j < S1_C; ++j) {
     const int i = base + j * 64 + lane;
     const bool ok = i < V;
     v[j] = ok ? x[ok ? i : 0] : -INFINITY;
     id[j] = ok ? (unsigned)i : NO_IDX;
-    lm = fmaxf(lm, v[j]);
   }
+  if (PEN) {
+    for (int c = 0; c < n_ctx; ++c) {        // wave-uniform walk; only ids inside this wave's 512 logits touch registers
+      const unsigned t = ctx[c];
+      if (t - (unsigned)base >= (unsigned)S1_WAVE_ELEMS) continue;
+#pragma unroll
+      for (int j = 0; j < S1_C; ++j)
+        if (id[j] == t) v[j] = v[j] >= 0.f ? v[j] / penalty : v[j] * penalty;
+    }
+  }
+  float lm = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < S1_C; ++j) lm = fmaxf(lm, v[j]);
   const float wm = wave_max(lm);
   float s = 0.f;
 #pragma unroll
@@ -108,14 +121,21 @@ __global__ __launch_bounds__(64 * S1_WAVES_PER_BLOCK) void topk_stage1_kernel(co
   });
 }
 
+__global__ __launch_bounds__(64 * S1_WAVES_PER_BLOCK) void topk_stage1_kernel(const float* x, int V, int k, float inv_temp,
+                                                                              float* cand_val, unsigned* cand_idx,
+                                                                              float* part_m, float* part_s) {
+  topk_stage1_body<false>(x, V, k, inv_temp, nullptr, 0, 1.f, blockIdx.x * S1_WAVES_PER_BLOCK + (threadIdx.x >> 6), cand_val, cand_idx,
+                          part_m, part_s);
+}
+
 constexpr int S2_WAVES = 16;
 constexpr int S2_C = 20;  // 16 waves x 64 lanes x 20 >= 297 stage-1 waves x 64 candidates
 
 // stage 2a (16 one-wave blocks, one per CU -- the rounds are VALU-bound, so the waves must not share a SIMD): each wave
 // reduces a contiguous sixteenth of the stage-1 candidates to its k best
-__global__ __launch_bounds__(64) void topk_stage2a_kernel(const float* cand_val, const unsigned* cand_idx, int n_cand, int k,
-                                                          float* mid_val, unsigned* mid_idx) {
-  const int lane = threadIdx.x, wave = blockIdx.x;
+__device__ __forceinline__ void topk_stage2a_body(const float* cand_val, const unsigned* cand_idx, int n_cand, int k, int wave,
+                                                  float* mid_val, unsigned* mid_idx) {
+  const int lane = threadIdx.x;
   const int chunk = (n_cand + S2_WAVES - 1) / S2_WAVES;
   const int c0 = wave * chunk, c1 = min(c0 + chunk, n_cand);
   float v[S2_C];
@@ -136,10 +156,14 @@ __global__ __launch_bounds__(64) void topk_stage2a_kernel(const float* cand_val,
   });
 }
 
+__global__ __launch_bounds__(64) void topk_stage2a_kernel(const float* cand_val, const unsigned* cand_idx, int n_cand, int k,
+                                                          float* mid_val, unsigned* mid_idx) {
+  topk_stage2a_body(cand_val, cand_idx, n_cand, k, blockIdx.x, mid_val, mid_idx);
+}
+
 // stage 2b (one wave): 16 x k -> k in (value desc, index asc) order, and the softmax partials -> (max, sumexp)
-__global__ __launch_bounds__(64) void topk_stage2b_kernel(const float* mid_val, const unsigned* mid_idx, const float* part_m,
-                                                          const float* part_s, int n_part, int k, float inv_temp,
-                                                          float* out_val, unsigned* out_idx, float* out_ms) {
+__device__ __forceinline__ void topk_stage2b_body(const float* mid_val, const unsigned* mid_idx, const float* part_m, const float* part_s,
+                                                  int n_part, int k, float inv_temp, float* out_val, unsigned* out_idx, float* out_ms) {
   const int lane = threadIdx.x;
   {
     float m = -INFINITY;
@@ -171,9 +195,58 @@ __global__ __launch_bounds__(64) void topk_stage2b_kernel(const float* mid_val, 
   });
 }
 
+__global__ __launch_bounds__(64) void topk_stage2b_kernel(const float* mid_val, const unsigned* mid_idx, const float* part_m,
+                                                          const float* part_s, int n_part, int k, float inv_temp,
+                                                          float* out_val, unsigned* out_idx, float* out_ms) {
+  topk_stage2b_body(mid_val, mid_idx, part_m, part_s, n_part, k, inv_temp, out_val, out_idx, out_ms);
+}
+
+// ---- the same three stages for R rows at once (batched sampled generation): blockIdx.y is the row of the sample table ----------
+// Row s of the table (SAMPLE_ROW_WORDS int32): logits row, k, 1/T and penalty (f32 bits), its distinct context ids ctx[c0 .. c0 + n).
+// Row s owns cand_* [s * (nw + 16) * 64, +(nw + 16) * 64) (stage-1 candidates, then the 16 x k intermediates), part_* [s * nw, +nw) and
+// out [s * SAMPLE_OUT_WORDS, +SAMPLE_OUT_WORDS) = {vals[64], max, sumexp, idx[64]}.  Every stage runs the single-row body on the row's
+// own slices, so a row's outputs are those of the single-row pipeline (the penalty copy there, the load-time penalty here, give the
+// same f32 values).
+__global__ __launch_bounds__(64 * S1_WAVES_PER_BLOCK) void topk_rows_stage1_kernel(const float* logits, int64_t ld, int V,
+                                                                                   const int32_t* tab, const uint32_t* ctx,
+                                                                                   float* cand_val, unsigned* cand_idx,
+                                                                                   float* part_m, float* part_s) {
+  const int32_t* t = tab + (size_t)blockIdx.y * SAMPLE_ROW_WORDS;
+  const int nw = sample_stage1_waves_dev(V);
+  const size_t cb = (size_t)blockIdx.y * (nw + S2_WAVES) * 64, pb = (size_t)blockIdx.y * nw;
+  const float* x = logits + (int64_t)t[SAMPLE_ROW_LROW] * ld;
+  const int w = blockIdx.x * S1_WAVES_PER_BLOCK + (threadIdx.x >> 6);
+  const int n_ctx = t[SAMPLE_ROW_NCTX];
+  if (n_ctx > 0)
+    topk_stage1_body<true>(x, V, t[SAMPLE_ROW_K], __int_as_float(t[SAMPLE_ROW_INVT]), ctx + t[SAMPLE_ROW_CTX0], n_ctx,
+                           __int_as_float(t[SAMPLE_ROW_PEN]), w, cand_val + cb, cand_idx + cb, part_m + pb, part_s + pb);
+  else
+    topk_stage1_body<false>(x, V, t[SAMPLE_ROW_K], __int_as_float(t[SAMPLE_ROW_INVT]), nullptr, 0, 1.f, w, cand_val + cb, cand_idx + cb,
+                            part_m + pb, part_s + pb);
+}
+
+__global__ __launch_bounds__(64) void topk_rows_stage2a_kernel(int V, const int32_t* tab, float* cand_val, unsigned* cand_idx) {
+  const int32_t* t = tab + (size_t)blockIdx.y * SAMPLE_ROW_WORDS;
+  const int nw = sample_stage1_waves_dev(V), k = t[SAMPLE_ROW_K];
+  const size_t cb = (size_t)blockIdx.y * (nw + S2_WAVES) * 64;
+  float* cv = cand_val + cb;   // the row's 16 x k intermediates sit behind its stage-1 candidates
+  unsigned* ci = cand_idx + cb;
+  topk_stage2a_body(cv, ci, nw * k, k, blockIdx.x, cv + (size_t)nw * 64, ci + (size_t)nw * 64);
+}
+
+__global__ __launch_bounds__(64) void topk_rows_stage2b_kernel(int V, const int32_t* tab, const float* cand_val, const unsigned* cand_idx,
+                                                               const float* part_m, const float* part_s, float* out) {
+  const int32_t* t = tab + (size_t)blockIdx.y * SAMPLE_ROW_WORDS;
+  const int nw = sample_stage1_waves_dev(V), k = t[SAMPLE_ROW_K];
+  const size_t cb = (size_t)blockIdx.y * (nw + S2_WAVES) * 64 + (size_t)nw * 64, pb = (size_t)blockIdx.y * nw;
+  float* o = out + (size_t)blockIdx.y * SAMPLE_OUT_WORDS;
+  topk_stage2b_body(cand_val + cb, cand_idx + cb, part_m + pb, part_s + pb, nw, k, __int_as_float(t[SAMPLE_ROW_INVT]), o,
+                    reinterpret_cast<unsigned*>(o + 66), o + 64);
+}
+
 }  // namespace
 
-int sample_stage1_waves(int V) { return (V + S1_WAVE_ELEMS - 1) / S1_WAVE_ELEMS; }
+int sample_stage1_waves(int V) { return sample_stage1_waves_dev(V); }
 // k <= 64 and the stage-1 candidates within what stage 2a holds in registers (16 waves x 64 lanes x 20)
 bool sample_shape_ok(int V, int k) { return V > 0 && k >= 1 && k <= 64 && (int64_t)sample_stage1_waves(V) * k <= S2_WAVES * 64 * S2_C; }
 
@@ -193,6 +266,19 @@ void launch_topk_candidates(const float* x, int V, int k, float inv_temp, float*
   hipLaunchKernelGGL(topk_stage2a_kernel, dim3(S2_WAVES), dim3(64), 0, st, cand_val, cand_idx, nw * k, k, mid_val, mid_idx);
   hipLaunchKernelGGL(topk_stage2b_kernel, dim3(1), dim3(64), 0, st, mid_val, mid_idx, part_m, part_s, nw, k, inv_temp, out_val,
                      out_idx, out_ms);
+}
+
+void launch_topk_rows(const float* logits, int64_t ld, int V, int rows, const int32_t* tab, const uint32_t* ctx, float* cand_val,
+                      unsigned* cand_idx, float* part_m, float* part_s, float* out, int stage, hipStream_t st) {
+  if (rows <= 0) return;
+  const int nw = sample_stage1_waves(V);
+  if (stage == 0)
+    hipLaunchKernelGGL(topk_rows_stage1_kernel, dim3((nw + S1_WAVES_PER_BLOCK - 1) / S1_WAVES_PER_BLOCK, rows), dim3(64 * S1_WAVES_PER_BLOCK),
+                       0, st, logits, ld, V, tab, ctx, cand_val, cand_idx, part_m, part_s);
+  else if (stage == 1)
+    hipLaunchKernelGGL(topk_rows_stage2a_kernel, dim3(S2_WAVES, rows), dim3(64), 0, st, V, tab, cand_val, cand_idx);
+  else
+    hipLaunchKernelGGL(topk_rows_stage2b_kernel, dim3(1, rows), dim3(64), 0, st, V, tab, cand_val, cand_idx, part_m, part_s, out);
 }
 
 }  // namespace aha

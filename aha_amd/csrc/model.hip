@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "audio.h"
+#include "sampler.h"
 #include "vision.h"
 
 namespace aha {
@@ -2293,8 +2294,12 @@ static int generate_prefill_pass(aha_model* m, GenCall& gc, const uint32_t* ids,
   return AHA_OK;
 }
 
-int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new, size_t max_tokens_per_pass,
-                         uint32_t* tokens_out, size_t* n_out, float* logits_out) {
+// params == nullptr: greedy (aha_hip_generate_batch: logits_out = each sequence's last logits).  Otherwise one sampler per sequence
+// (aha_hip_generate_batch_sampled: step_logits_out = every step's logits); the step's tokens are then picked on the host after the batched
+// candidate step, and written back into the token vector the next step's embedding gather reads.
+static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
+                               size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* logits_out,
+                               const aha_sampling_params* params, float* step_logits_out) {
   const aha_model_desc& c = m->desc;
   if (!ids || !seq_lens || !tokens_out || !n_out) {
     set_error("generate_batch: null input_ids / seq_lens / tokens_out / n_out");
@@ -2379,6 +2384,129 @@ int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_le
       (rc = bufs.alloc_host(&h_tok, (size_t)n)))
     return rc;
 
+  // ---- sampled generation: per-sequence samplers and the candidate step's buffers ----
+  std::vector<HostSampler> samplers(params ? n : 0);
+  const int nw = sample_stage1_waves(V);
+  int32_t *d_stab = nullptr, *h_stab = nullptr;
+  uint32_t *d_sctx = nullptr, *h_sctx = nullptr, *d_cidx = nullptr;
+  float *d_cval = nullptr, *d_part = nullptr, *d_sout = nullptr, *h_sout = nullptr, *h_fb = nullptr;
+  if (params) {
+    if (!sample_shape_ok(V, 64)) {
+      set_error("generate_batch_sampled: vocabulary too large for the candidate step");
+      return AHA_ERR_UNSUPPORTED;
+    }
+    size_t ctx_cap = 0, n_fb = 0;
+    for (int j = 0; j < n; ++j) {
+      if ((rc = host_sampler_init(samplers[j], params[j]))) return rc;
+      const HostSampler& S = samplers[j];
+      if (S.repeat_penalty != 1.0f) ctx_cap += std::min<size_t>(max_new, (size_t)S.repeat_last_n);
+      // a sequence that may need its full logits row: Sampling::All, oversized k, any TopP (nucleus wider than the candidates)
+      if (S.kind != SAMPLE_ARGMAX && (S.kind == SAMPLE_TOPP || sampler_candidates_needed(S, (size_t)V) == 0)) ++n_fb;
+    }
+    const size_t cand = (size_t)n * (nw + 16) * 64;
+    if ((rc = bufs.alloc(&d_stab, (size_t)n * SAMPLE_ROW_WORDS)) || (rc = bufs.alloc(&d_sctx, ctx_cap)) || (rc = bufs.alloc(&d_cval, cand)) ||
+        (rc = bufs.alloc(&d_cidx, cand)) || (rc = bufs.alloc(&d_part, 2 * (size_t)n * nw)) ||
+        (rc = bufs.alloc(&d_sout, (size_t)n * SAMPLE_OUT_WORDS)) || (rc = bufs.alloc_host(&h_stab, (size_t)n * SAMPLE_ROW_WORDS)) ||
+        (rc = bufs.alloc_host(&h_sctx, ctx_cap)) || (rc = bufs.alloc_host(&h_sout, (size_t)n * SAMPLE_OUT_WORDS)) ||
+        (rc = bufs.alloc_host(&h_fb, n_fb * (size_t)V)))
+      return rc;
+  }
+  // The end of every step (the prefill's first tokens, then each decode step): the tokens of rows r = 0 .. R-1 (row r = sequence seqs[r])
+  // into h_tok, from the device argmax vector `tok_dev` the head wrote.  Greedy: one copy and one sync.  Sampled: before that sync, one
+  // candidate step over every row that samples (its penalty context uploaded with it) and the candidates' copy; after it the host picks,
+  // a second sync only for rows whose candidates cannot decide (their logits rows come down), and the picked tokens go back up into
+  // tok_dev for the next step's embedding gather.
+  std::vector<int> mode, slot, fb_rows;
+  auto finish_step = [&](const std::vector<int>& seqs, uint32_t* tok_dev) -> int {
+    const int R = (int)seqs.size();
+    enum { GREEDY, CAND, FULL };
+    int ns = 0;
+    if (params) {
+      mode.assign(R, GREEDY);
+      slot.assign(R, -1);
+      size_t nc = 0;
+      for (int r = 0; r < R; ++r) {
+        const int j = seqs[r];
+        const HostSampler& S = samplers[j];
+        float pen;
+        size_t n_ctx;
+        sampler_penalty_context(S, n_out[j], &pen, &n_ctx);
+        if (S.kind == SAMPLE_ARGMAX && pen == 1.0f) continue;   // the device argmax is the token
+        const int k = S.kind == SAMPLE_ARGMAX ? 1 : sampler_candidates_needed(S, (size_t)V);
+        if (!k) {
+          mode[r] = FULL;
+          continue;
+        }
+        mode[r] = CAND;
+        slot[r] = ns;
+        int32_t* t = h_stab + (size_t)ns * SAMPLE_ROW_WORDS;
+        // `&logits / temperature`: 1/T computed in f64, applied in f32 (as model_sample_candidates; ArgMax: T treated as 1)
+        const float inv_t = S.kind == SAMPLE_ARGMAX ? 1.0f : (float)(1.0 / (double)(float)S.temperature);
+        const size_t c0 = nc;
+        if (pen != 1.0f) {   // the distinct in-vocabulary ids of the last n_ctx generated (apply_repeat_penalty's HashSet)
+          const uint32_t* g = tokens_out + (size_t)j * max_new + n_out[j] - n_ctx;
+          for (size_t i = 0; i < n_ctx; ++i)
+            if (g[i] < (uint32_t)V) h_sctx[nc++] = g[i];
+          std::sort(h_sctx + c0, h_sctx + nc);
+          nc = (size_t)(std::unique(h_sctx + c0, h_sctx + nc) - h_sctx);
+        }
+        t[SAMPLE_ROW_LROW] = r;
+        t[SAMPLE_ROW_K] = k;
+        memcpy(&t[SAMPLE_ROW_INVT], &inv_t, 4);
+        memcpy(&t[SAMPLE_ROW_PEN], &pen, 4);
+        t[SAMPLE_ROW_CTX0] = (int32_t)c0;
+        t[SAMPLE_ROW_NCTX] = (int32_t)(nc - c0);
+        t[6] = t[7] = 0;
+        ++ns;
+      }
+      if (ns) {
+        AHA_HIP_CHECK(hipMemcpyAsync(d_stab, h_stab, (size_t)ns * SAMPLE_ROW_WORDS * 4, hipMemcpyHostToDevice, st));
+        if (nc) AHA_HIP_CHECK(hipMemcpyAsync(d_sctx, h_sctx, nc * 4, hipMemcpyHostToDevice, st));
+        const char* names[3] = {"sample_rows_stage1", "sample_rows_stage2a", "sample_rows_stage2b"};
+        for (int stage = 0; stage < 3; ++stage) {
+          ProfScope ps(m, names[stage], stage == 0 ? (double)ns * V * 4 : 0, 0);
+          launch_topk_rows(gc.logits, V, V, ns, d_stab, d_sctx, d_cval, d_cidx, d_part, d_part + (size_t)n * nw, d_sout, stage, st);
+        }
+        AHA_HIP_CHECK(hipGetLastError());
+        AHA_HIP_CHECK(hipMemcpyAsync(h_sout, d_sout, (size_t)ns * SAMPLE_OUT_WORDS * 4, hipMemcpyDeviceToHost, st));
+      }
+      if (step_logits_out)
+        for (int r = 0; r < R; ++r)
+          AHA_HIP_CHECK(hipMemcpyAsync(step_logits_out + ((size_t)seqs[r] * max_new + n_out[seqs[r]]) * V, gc.logits + (size_t)r * V,
+                                       (size_t)V * 4, hipMemcpyDeviceToHost, st));
+    }
+    AHA_HIP_CHECK(hipMemcpyAsync(h_tok, tok_dev, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+    AHA_HIP_CHECK(hipStreamSynchronize(st));
+    if (!params) return AHA_OK;
+    fb_rows.clear();
+    for (int r = 0; r < R; ++r) {
+      if (mode[r] == GREEDY) continue;
+      const int j = seqs[r];
+      if (mode[r] == CAND) {
+        const float* o = h_sout + (size_t)slot[r] * SAMPLE_OUT_WORDS;
+        const int k = h_stab[(size_t)slot[r] * SAMPLE_ROW_WORDS + SAMPLE_ROW_K];
+        const int prc = sampler_pick(samplers[j], o, reinterpret_cast<const uint32_t*>(o + 66), k, o[64], o[65], nullptr, (size_t)V,
+                                     tokens_out + (size_t)j * max_new, n_out[j], &h_tok[r]);
+        if (prc < 0) return prc;
+        if (prc == AHA_OK) continue;
+      }
+      fb_rows.push_back(r);
+    }
+    if (!fb_rows.empty()) {   // rows whose candidates cannot decide: their full logits rows, one more sync
+      for (size_t f = 0; f < fb_rows.size(); ++f)
+        AHA_HIP_CHECK(hipMemcpyAsync(h_fb + f * V, gc.logits + (size_t)fb_rows[f] * V, (size_t)V * 4, hipMemcpyDeviceToHost, st));
+      AHA_HIP_CHECK(hipStreamSynchronize(st));
+      for (size_t f = 0; f < fb_rows.size(); ++f) {
+        const int r = fb_rows[f], j = seqs[r];
+        const int prc = sampler_pick(samplers[j], nullptr, nullptr, 0, 0.f, 0.f, h_fb + f * V, (size_t)V, tokens_out + (size_t)j * max_new,
+                                     n_out[j], &h_tok[r]);
+        if (prc != AHA_OK) return prc < 0 ? prc : AHA_ERR_STATE;
+      }
+    }
+    AHA_HIP_CHECK(hipMemcpyAsync(tok_dev, h_tok, (size_t)R * 4, hipMemcpyHostToDevice, st));
+    return AHA_OK;
+  };
+
   // ---- prefill: packed passes (embed_batch's pass rule) ----
   const size_t budget = std::min(max_tokens_per_pass ? max_tokens_per_pass : EMBED_PASS_ROWS, (size_t)1 << 24);
   {
@@ -2395,8 +2523,11 @@ int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_le
       j = k;
     }
   }
-  AHA_HIP_CHECK(hipMemcpyAsync(h_tok, gc.tok[0], (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  AHA_HIP_CHECK(hipStreamSynchronize(st));
+  {
+    std::vector<int> all(n);
+    for (int j = 0; j < n; ++j) all[j] = j, n_out[j] = 0;
+    if ((rc = finish_step(all, gc.tok[0]))) return rc;
+  }
   auto is_stop = [&](uint32_t t) {
     for (int e = 0; e < c.n_stop_tokens; ++e)
       if (t == c.stop_tokens[e]) return true;
@@ -2488,8 +2619,7 @@ int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_le
     }
     gen_head(m, gc, 0, R, gc.tok[cur ^ 1]);
     AHA_HIP_CHECK(hipGetLastError());
-    AHA_HIP_CHECK(hipMemcpyAsync(h_tok, gc.tok[cur ^ 1], (size_t)R * 4, hipMemcpyDeviceToHost, st));
-    AHA_HIP_CHECK(hipStreamSynchronize(st));
+    if ((rc = finish_step(active, gc.tok[cur ^ 1]))) return rc;
     std::vector<int> next;
     for (int r = 0; r < R; ++r) {
       const int j = active[r];
@@ -2506,6 +2636,16 @@ int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_le
     cur ^= 1;
   }
   return AHA_OK;
+}
+
+int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new, size_t max_tokens_per_pass,
+                         uint32_t* tokens_out, size_t* n_out, float* logits_out) {
+  return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, logits_out, nullptr, nullptr);
+}
+
+int model_generate_batch_sampled(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_sampling_params* params,
+                                 size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* step_logits_out) {
+  return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, nullptr, params, step_logits_out);
 }
 
 }  // namespace aha

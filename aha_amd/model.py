@@ -349,6 +349,30 @@ class HipInferenceModel:
         out = [[int(t) for t in toks[j, :int(n_out[j])]] for j in range(len(seqs))]
         return (out, logits) if want_logits else out
 
+    def generate_batch_sampled(self, prompts: Sequence[Sequence[int]], params, max_new: int, max_tokens_per_pass: int = 0,
+                               want_step_logits: bool = False):
+        """Sampled generation of every prompt at once (aha_hip_generate_batch_sampled): per prompt, the tokens generate_generic_sampled
+        yields for it alone with params[j] (a sampling.SamplingParams each, or one for all prompts).  Returns a list of token lists, and
+        with want_step_logits also the (len(prompts), max_new, vocab) float32 logits before the penalty that chose each token (rows past
+        a sequence's length are zero)."""
+        from .sampling import SamplingParams
+        seqs = [np.asarray(x, dtype=np.uint32).reshape(-1) for x in prompts]
+        if isinstance(params, SamplingParams):
+            params = [params] * len(seqs)
+        if len(params) != len(seqs):
+            raise ValueError(f"{len(params)} sampling params for {len(seqs)} prompts")
+        cp = (_lib.SamplingParams * max(len(seqs), 1))(*[p.to_c() for p in params])
+        ids = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0, np.uint32))
+        lens = np.ascontiguousarray([s.size for s in seqs], dtype=np.uint64)
+        toks = np.zeros((len(seqs), max(int(max_new), 1)), dtype=np.uint32)
+        n_out = np.zeros(len(seqs), dtype=np.uint64)
+        step = np.zeros((len(seqs), max(int(max_new), 1), self.text_cfg.vocab_size), dtype=np.float32) if want_step_logits else None
+        check(lib().aha_hip_generate_batch_sampled(self.handle, ids.ctypes.data, lens.ctypes.data, len(seqs), cp, int(max_new),
+                                                   int(max_tokens_per_pass), toks.ctypes.data, n_out.ctypes.data,
+                                                   None if step is None else step.ctypes.data))
+        out = [[int(t) for t in toks[j, :int(n_out[j])]] for j in range(len(seqs))]
+        return (out, step) if want_step_logits else out
+
     def embed_multi(self, inputs: Sequence[Sequence[int]]) -> np.ndarray:
         if len(inputs) == 0:
             raise ValueError("embedding input cannot be empty")  # qwen3_embedding/mod.rs:39-41
@@ -512,5 +536,16 @@ def generate_generic_batch(model: HipInferenceModel, prompts: Sequence[Sequence[
     as prefill and decode are not timed apart)."""
     t0 = time.perf_counter()
     out = model.generate_batch(prompts, max_tokens, max_tokens_per_pass)
+    secs = time.perf_counter() - t0
+    return out, Usage(sum(len(p) for p in prompts), 0.0, sum(len(o) for o in out), secs)
+
+
+def generate_generic_batch_sampled(model: HipInferenceModel, prompts: Sequence[Sequence[int]], params, max_tokens: int,
+                                   max_tokens_per_pass: int = 0):
+    """generate_generic with each prompt's own sampler (sampling.SamplingParams, one per prompt or one for all) in one call
+    (HipInferenceModel.generate_batch_sampled).  Returns (per-prompt generated token ids, Usage over all prompts, timed as in
+    generate_generic_batch)."""
+    t0 = time.perf_counter()
+    out = model.generate_batch_sampled(prompts, params, max_tokens, max_tokens_per_pass)
     secs = time.perf_counter() - t0
     return out, Usage(sum(len(p) for p in prompts), 0.0, sum(len(o) for o in out), secs)

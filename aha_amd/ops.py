@@ -243,3 +243,23 @@ def debug_attn_decode_fused(qkv_row: torch.Tensor, q_norm_w: torch.Tensor, k_nor
     check(lib().aha_hip_debug_attn_decode_fused(_ptr(qkv_row), _ptr(q_norm_w), _ptr(k_norm_w), _ptr(rope_row), _ptr(page_ptrs), int(kv_len),
                                                 nh, kvh, eps, scale, _ptr(o), _stream()))
     return o
+
+
+def sample_rows(logits: torch.Tensor, k, temperature, repeat_penalty, contexts):
+    """aha_hip_sample_candidates for every row of logits (R, V) f32 (row pitch logits.stride(0)) in one launch per stage: row r with
+    k[r] (1..64), temperature[r], repeat_penalty[r] over the ids contexts[r].  The logits are only read.  -> (vals (R, 64) f32,
+    idx (R, 64) int32, ms (R, 2) f32 = {max, sumexp}); the first k[r] entries of row r are its candidates."""
+    _chk(logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    R, V = logits.shape
+    kk = np.ascontiguousarray(np.asarray(k, dtype=np.int32).reshape(R))
+    tt = np.ascontiguousarray(np.asarray(temperature, dtype=np.float32).reshape(R))
+    pp = np.ascontiguousarray(np.asarray(repeat_penalty, dtype=np.float32).reshape(R))
+    off = np.ascontiguousarray(np.cumsum([0] + [len(c) for c in contexts]), dtype=np.uint64)
+    ctx = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.uint32).reshape(-1) for c in contexts] + [np.zeros(1, np.uint32)]))
+    vals = torch.empty(R, 64, dtype=torch.float32, device=logits.device)
+    idx = torch.empty(R, 64, dtype=torch.int32, device=logits.device)
+    ms = torch.empty(R, 2, dtype=torch.float32, device=logits.device)
+    check(lib().aha_hip_sample_rows(_ptr(logits), logits.stride(0), R, V, kk.ctypes.data, tt.ctypes.data, pp.ctypes.data, ctx.ctypes.data,
+                                    off.ctypes.data, _ptr(vals), _ptr(idx), _ptr(ms), _stream()))
+    return vals, idx, ms

@@ -337,3 +337,28 @@ def generate_stream_generic_text(model, decode, input_ids: Sequence[int], ctx: G
                 break
     finally:
         model.clear_cache()
+
+
+@dataclass
+class SamplingParams:
+    """One request's sampler for the batched sampled generation (HipInferenceModel.generate_batch_sampled): the Options of
+    GenerationContext::new (common/generate.rs:21-53).  None = unset; repeat_last_n and seed default to the reference's 64 and
+    299792458 (common/generate.rs:408,452).  The C struct is aha_sampling_params."""
+    temperature: Optional[float] = None
+    top_p: Optional[float] = None
+    top_k: Optional[int] = None
+    repeat_penalty: Optional[float] = None
+    repeat_last_n: int = 64
+    seed: int = 299792458
+
+    def to_c(self):
+        from ._lib import AHA_SAMPLE_HAS_TOP_K, AHA_SAMPLE_HAS_TOP_P, SamplingParams as CParams
+        flags = (AHA_SAMPLE_HAS_TOP_P if self.top_p is not None else 0) | (AHA_SAMPLE_HAS_TOP_K if self.top_k is not None else 0)
+        return CParams(0.0 if self.temperature is None else float(self.temperature), 1.0 if self.top_p is None else float(self.top_p),
+                       0 if self.top_k is None else int(self.top_k), 1.0 if self.repeat_penalty is None else float(self.repeat_penalty),
+                       int(self.repeat_last_n), flags, int(self.seed) & 0xFFFFFFFFFFFFFFFF)
+
+    def context(self, initial_seq_len: int, max_tokens: int) -> GenerationContext:
+        """The single-sequence GenerationContext of the same request (generate_generic_sampled)."""
+        return GenerationContext(self.temperature, self.top_p, self.top_k, self.repeat_penalty, self.repeat_last_n, self.seed,
+                                 initial_seq_len, max_tokens)

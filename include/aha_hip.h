@@ -186,6 +186,62 @@ int aha_hip_embed_batch(aha_model* m, const uint32_t* input_ids, const size_t* s
 int aha_hip_generate_batch(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
                            size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* logits_out);
 
+/* ---- batched sampled generation ----------------------------------------------------------------------------------------
+ * aha_sampling_params: the Options of GenerationContext::new (common/generate.rs:21-53) for one sequence.
+ *   temperature     < 1e-7 (negative included) = no temperature (get_logit_processor, sample.rs:13: ArgMax); NaN = AHA_ERR_INVALID
+ *   top_p           read only if flags & AHA_SAMPLE_HAS_TOP_P
+ *   top_k           read only if flags & AHA_SAMPLE_HAS_TOP_K; must be >= 1
+ *   repeat_penalty  1.0 = off (use_repeat_penalty, sample.rs:41-60); must be > 0
+ *   repeat_last_n   >= 0; 0 = off
+ *   seed            StdRng::seed_from_u64(seed) (the reference's default is 299792458), one stream per sequence */
+#define AHA_SAMPLE_HAS_TOP_P 1u
+#define AHA_SAMPLE_HAS_TOP_K 2u
+typedef struct aha_sampling_params {
+  float temperature;
+  float top_p;
+  int32_t top_k;
+  float repeat_penalty;
+  int32_t repeat_last_n;
+  uint32_t flags;
+  uint64_t seed;
+} aha_sampling_params;
+
+/* Batched generation with per-sequence samplers: row j of tokens_out (n_seqs x max_new) holds the n_out[j] tokens generate_generic
+ * (generate.rs:115-159) yields for prompt j alone with GenerationContext(params[j]), given the logits this call computes.  The first token
+ * is sampled from the prefill's last row with an empty penalty context and never ends a sequence; up to max_new - 1 more follow, ending
+ * at (and keeping) the first stop token.  Each sequence draws from its own RNG stream.  A sequence with no temperature and penalty 1 is
+ * greedy and gives exactly aha_hip_generate_batch's tokens and logits.  step_logits_out (n_seqs x max_new x vocab f32, may be NULL):
+ * entry [j, t] receives the logits before the penalty that chose token t; entries past n_out[j] are left untouched.
+ * Each decode step runs the candidate step of aha_hip_sample_rows once over every row that samples, copies the candidates to the host
+ * and picks there (aha_hip_sampler_pick's arithmetic); only a row whose candidates cannot decide copies its full logits row.
+ * Supported models, errors, page reservation and the cache clearing are those of aha_hip_generate_batch; invalid params (null, NaN
+ * temperature, top_k < 1 with its flag, repeat_last_n < 0, repeat_penalty <= 0) are AHA_ERR_INVALID before any device work. */
+int aha_hip_generate_batch_sampled(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs,
+                                   const aha_sampling_params* params, size_t max_new, size_t max_tokens_per_pass,
+                                   uint32_t* tokens_out, size_t* n_out, float* step_logits_out);
+
+/* Host-only sampler: candle's LogitsProcessor built by get_logit_processor (sample.rs:7-38) plus use_repeat_penalty's slicing, over
+ * the rand 0.9.2 StdRng of aha_hip_rng_*.  The deterministic half restates aha_amd/sampling.py (weights over the device candidates, the
+ * top-p tie rule, the full-vector path); each sampled token consumes one next_u32, an ArgMax pick none.
+ *   aha_hip_sampler_plan: what the device step needs after n_generated tokens: k_out candidates (0: none -- a greedy row the forward's
+ *     argmax decides, or a sampler that needs the full logits vector), the temperature for the candidate step (0 for ArgMax), the
+ *     effective repeat penalty and how many of the last generated ids form the penalty context.
+ *   aha_hip_sampler_pick: the token from a row's candidates (vals / idx ordered by (value desc, index asc), k of them, with the
+ *     full-vocabulary max and sumexp of aha_hip_sample_candidates over the penalised logits), or -- when vals is NULL or the
+ *     candidates cannot decide -- from `logits` (vocab_size f32, BEFORE the penalty; the sampler applies it).  `generated` is every id
+ *     generated so far (the sampler slices the penalty context).  Returns AHA_SAMPLE_NEED_LOGITS, with the RNG untouched, when it
+ *     needs the full vector and logits is NULL.
+ *   aha_hip_sampler_rng_words: how many u32 the sampler's stream has handed out. */
+#define AHA_SAMPLE_NEED_LOGITS 1
+typedef struct aha_sampler aha_sampler;
+int aha_hip_sampler_create(const aha_sampling_params* params, aha_sampler** out);
+void aha_hip_sampler_destroy(aha_sampler* s);
+int aha_hip_sampler_plan(const aha_sampler* s, size_t vocab_size, size_t n_generated, int32_t* k_out, float* temperature_out,
+                         float* repeat_penalty_out, size_t* n_context_out);
+int aha_hip_sampler_pick(aha_sampler* s, const float* vals, const uint32_t* idx, int32_t k, float max, float sumexp, const float* logits,
+                         size_t vocab_size, const uint32_t* generated, size_t n_generated, uint32_t* token_out);
+uint64_t aha_hip_sampler_rng_words(const aha_sampler* s);
+
 /* ---- checkpoint directory -> model (XxxGenerateModel::init minus tokenizer / chat template) --------------------------
  * aha_hip_config_parse: <dir>/config.json -> aha_model_desc, the same field mapping serde does into Qwen3Config
  *   (/root/reference/src/models/qwen3/config.rs:4-27), Qwen3VLConfig (qwen3vl/config.rs:51-133, text_config / vision_config,
@@ -444,6 +500,14 @@ int aha_hip_attn_decode_batch(const void* qkv, const void* q_norm_w, const void*
 /* Debug: the single-sequence fused decode attention kernel (the decode step's) on one sequence whose pages are page_ptrs[0 ..]. */
 int aha_hip_debug_attn_decode_fused(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
                                     int32_t kv_len, int32_t nh, int32_t kvh, float eps, float scale, void* o, void* stream);
+/* aha_hip_sample_rows: aha_hip_sample_candidates for R rows of f32 logits at once (the candidate step of
+ * aha_hip_generate_batch_sampled), bit-identical per row to it.  logits (device, row r at logits + r * ld, V floats) are only read;
+ * k (1..64), temperature, repeat_penalty: HOST arrays of R; context / context_offsets: HOST, row r's penalty context is
+ * context[context_offsets[r] .. context_offsets[r + 1]) (duplicates and ids >= V allowed, as apply_repeat_penalty).  Device outputs:
+ * vals_out / idx_out (R, 64) -- the first k[r] entries of row r in (value desc, index asc) order -- and ms_out (R, 2) = {max, sumexp}. */
+int aha_hip_sample_rows(const float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* k, const float* temperature,
+                        const float* repeat_penalty, const uint32_t* context, const size_t* context_offsets, float* vals_out,
+                        uint32_t* idx_out, float* ms_out, void* stream);
 /* D7 prefill attention, causal with q position i attending to k positions <= kv_offset + i; q (S, nh*d),
  * k/v (L, kvh*d) token-major, L = kv_offset + S.  causal = 0 gives full (ViT / audio encoder) attention.  d = 128, or 64 with
  * nh == kvh (the Qwen3-ASR audio encoder's geometry). */

@@ -25,6 +25,28 @@ pub mod sys {
     pub struct AhaModel {
         _p: [u8; 0],
     }
+    #[repr(C)]
+    pub struct AhaSampler {
+        _p: [u8; 0],
+    }
+
+    pub const AHA_SAMPLE_HAS_TOP_P: u32 = 1;
+    pub const AHA_SAMPLE_HAS_TOP_K: u32 = 2;
+    pub const AHA_SAMPLE_NEED_LOGITS: i32 = 1;
+
+    /// `aha_sampling_params`: the Options of `GenerationContext::new` (common/generate.rs:21-53); same fields, same order as the
+    /// ctypes mirror `aha_amd._lib.SamplingParams`.
+    #[repr(C)]
+    #[derive(Debug, Clone, Copy)]
+    pub struct AhaSamplingParams {
+        pub temperature: f32,
+        pub top_p: f32,
+        pub top_k: i32,
+        pub repeat_penalty: f32,
+        pub repeat_last_n: i32,
+        pub flags: u32,
+        pub seed: u64,
+    }
 
     pub const AHA_BF16: i32 = 0;
     pub const AHA_F16: i32 = 1;
@@ -217,6 +239,58 @@ pub mod sys {
             n_out: *mut usize,
             logits_out: *mut f32,
         ) -> i32;
+        pub fn aha_hip_generate_batch_sampled(
+            m: *mut AhaModel,
+            ids: *const u32,
+            seq_lens: *const usize,
+            n_seqs: usize,
+            params: *const AhaSamplingParams,
+            max_new: usize,
+            max_tokens_per_pass: usize,
+            tokens_out: *mut u32,
+            n_out: *mut usize,
+            step_logits_out: *mut f32,
+        ) -> i32;
+        pub fn aha_hip_sample_rows(
+            logits: *const f32,
+            ld: i64,
+            rows: i32,
+            vocab: i32,
+            k: *const i32,
+            temperature: *const f32,
+            repeat_penalty: *const f32,
+            context: *const u32,
+            context_offsets: *const usize,
+            vals_out: *mut f32,
+            idx_out: *mut u32,
+            ms_out: *mut f32,
+            stream: *mut c_void,
+        ) -> i32;
+        pub fn aha_hip_sampler_create(params: *const AhaSamplingParams, out: *mut *mut AhaSampler) -> i32;
+        pub fn aha_hip_sampler_destroy(s: *mut AhaSampler);
+        pub fn aha_hip_sampler_plan(
+            s: *const AhaSampler,
+            vocab_size: usize,
+            n_generated: usize,
+            k_out: *mut i32,
+            temperature_out: *mut f32,
+            repeat_penalty_out: *mut f32,
+            n_context_out: *mut usize,
+        ) -> i32;
+        pub fn aha_hip_sampler_pick(
+            s: *mut AhaSampler,
+            vals: *const f32,
+            idx: *const u32,
+            k: i32,
+            max: f32,
+            sumexp: f32,
+            logits: *const f32,
+            vocab_size: usize,
+            generated: *const u32,
+            n_generated: usize,
+            token_out: *mut u32,
+        ) -> i32;
+        pub fn aha_hip_sampler_rng_words(s: *const AhaSampler) -> u64;
         pub fn aha_hip_cache_len(m: *const AhaModel) -> usize;
         pub fn aha_hip_audio_resample(
             ctx: *mut AhaCtx,
@@ -460,6 +534,39 @@ impl Model {
         Ok(n_out.iter().enumerate().map(|(j, &n)| toks[j * max_new..j * max_new + n].to_vec()).collect())
     }
 
+    /// `generate_generic` with each prompt's own sampler, every prompt at once (aha_hip_generate_batch_sampled): per prompt, the
+    /// tokens `generate_generic` yields for it alone with `GenerationContext(params[j])`, each on its own RNG stream.
+    pub fn generate_batch_sampled(
+        &mut self,
+        prompts: &[&[u32]],
+        params: &[sys::AhaSamplingParams],
+        max_new: usize,
+        max_tokens_per_pass: usize,
+    ) -> Result<Vec<Vec<u32>>, Error> {
+        if params.len() != prompts.len() {
+            return Err(Error { code: -1, message: format!("{} sampling params for {} prompts", params.len(), prompts.len()) });
+        }
+        let ids: Vec<u32> = prompts.iter().flat_map(|s| s.iter().copied()).collect();
+        let lens: Vec<usize> = prompts.iter().map(|s| s.len()).collect();
+        let mut toks = vec![0u32; prompts.len() * max_new.max(1)];
+        let mut n_out = vec![0usize; prompts.len()];
+        check(unsafe {
+            sys::aha_hip_generate_batch_sampled(
+                self.model,
+                ids.as_ptr(),
+                lens.as_ptr(),
+                lens.len(),
+                params.as_ptr(),
+                max_new,
+                max_tokens_per_pass,
+                toks.as_mut_ptr(),
+                n_out.as_mut_ptr(),
+                std::ptr::null_mut(),
+            )
+        })?;
+        Ok(n_out.iter().enumerate().map(|(j, &n)| toks[j * max_new..j * max_new + n].to_vec()).collect())
+    }
+
     /// The greedy loop of `generate_generic` / `generate_stream_generic` (common/generate.rs:115-159, 161-368) kept on the
     /// device in chunks of `chunk` tokens: `on_token` sees every token in order (what a streaming response forwards) and
     /// returns `false` to stop; an eos id stops after it has been delivered, as in the reference.
@@ -562,6 +669,50 @@ impl StdRng {
 impl Drop for StdRng {
     fn drop(&mut self) {
         unsafe { sys::aha_hip_rng_destroy(self.0) }
+    }
+}
+
+/// The host half of the sampled single-sequence path (`aha_hip_sampler_*`): `LogitsProcessor` as `get_logit_processor` builds it,
+/// `use_repeat_penalty`'s slicing and the RNG stream.  Per token: `plan` says how many candidates to ask `aha_hip_sample_candidates`
+/// for, `pick` turns them (or, on `Ok(None)`, the full logits of `aha_hip_last_logits`) into the token.
+pub struct Sampler(*mut sys::AhaSampler);
+unsafe impl Send for Sampler {}
+impl Sampler {
+    pub fn new(params: &sys::AhaSamplingParams) -> Result<Self, Error> {
+        let mut h = std::ptr::null_mut();
+        check(unsafe { sys::aha_hip_sampler_create(params, &mut h) })?;
+        Ok(Self(h))
+    }
+    /// (k, temperature, effective repeat penalty, context length) after `n_generated` tokens; k == 0: no candidate step.
+    pub fn plan(&self, vocab_size: usize, n_generated: usize) -> Result<(i32, f32, f32, usize), Error> {
+        let (mut k, mut t, mut p, mut n) = (0i32, 0f32, 1f32, 0usize);
+        check(unsafe { sys::aha_hip_sampler_plan(self.0, vocab_size, n_generated, &mut k, &mut t, &mut p, &mut n) })?;
+        Ok((k, t, p, n))
+    }
+    /// The token, or `None` when the candidates cannot decide and `logits` was not given.
+    pub fn pick(
+        &mut self,
+        cands: Option<(&[f32], &[u32], f32, f32)>,
+        logits: Option<&[f32]>,
+        vocab_size: usize,
+        generated: &[u32],
+    ) -> Result<Option<u32>, Error> {
+        let (vals, idx, k, mx, se) = match cands {
+            Some((v, i, mx, se)) => (v.as_ptr(), i.as_ptr(), v.len().min(i.len()) as i32, mx, se),
+            None => (std::ptr::null(), std::ptr::null(), 0, 0.0, 0.0),
+        };
+        let lg = logits.map_or(std::ptr::null(), |l| l.as_ptr());
+        let mut tok = 0u32;
+        let rc = unsafe {
+            sys::aha_hip_sampler_pick(self.0, vals, idx, k, mx, se, lg, vocab_size, generated.as_ptr(), generated.len(), &mut tok)
+        };
+        check(rc)?;
+        Ok(if rc == sys::AHA_SAMPLE_NEED_LOGITS { None } else { Some(tok) })
+    }
+}
+impl Drop for Sampler {
+    fn drop(&mut self) {
+        unsafe { sys::aha_hip_sampler_destroy(self.0) }
     }
 }
 

@@ -6,8 +6,12 @@ Prompts of --prompt tokens, --max-new new tokens.  Per batch size B:
   * serial: forward_initial + decode_greedy on --serial prompts one after the other, decode tokens/s of that loop;
 and, per projection shape, kernel A (gemv_rows) at R = 1, 16, 32 and above 32 rows (two row groups = the weights streamed twice), as
 weight bytes / time and its fraction of the 8 TB/s HBM peak.  One JSON object per line.
-    python scripts/bench_generate_batch.py [--only 0.6b,8b] [--batches 1,4,8,16,32,64] [--prompt 512] [--max-new 128]
-    python scripts/bench_generate_batch.py --once 8b:16     # one generate_batch call and nothing else (rocprofv3 --kernel-trace --stats)"""
+With --sampler (the Qwen3 default request: T 0.6 / top_p 0.95 / top_k 20, repeat penalty 1.1 over the last 64 ids) each batch size is
+also run through generate_batch_sampled (same timing rule; "sampled_vs_greedy" = its step over the greedy step), and the serial leg
+is generate_generic_sampled (one host round trip per token) instead of decode_greedy.
+    python scripts/bench_generate_batch.py [--only 0.6b,8b] [--batches 1,4,8,16,32,64] [--prompt 512] [--max-new 128] [--sampler]
+    python scripts/bench_generate_batch.py --once 8b:16     # one generate_batch call and nothing else (rocprofv3 --kernel-trace --stats)
+    python scripts/bench_generate_batch.py --once 8b:16 --sampler   # the same with generate_batch_sampled"""
 import argparse
 import json
 import os
@@ -72,6 +76,27 @@ def bench_kernel_a(cfg, name):
         del W
 
 
+def sampler_params():
+    from aha_amd.sampling import SamplingParams
+    return SamplingParams(0.6, 0.95, 20, 1.1, 64)
+
+
+def serial_sampled(m, ps, max_new):
+    """generate_generic_sampled on each prompt: decode tokens/s and step time, the prefill token excluded (timed apart)."""
+    import torch
+    from aha_amd import sampling as hs
+    dec = 0.0
+    for j, p in enumerate(ps):
+        sp = sampler_params()
+        sp.seed = j
+        t1, _ = timed(lambda: hs.generate_generic_sampled(m, p, sp.context(len(p), 1)))
+        tn, out = timed(lambda: hs.generate_generic_sampled(m, p, sp.context(len(p), max_new)))
+        assert len(out) == max_new
+        dec += tn - t1
+    torch.cuda.synchronize()
+    return len(ps) * (max_new - 1) / dec, dec / (len(ps) * (max_new - 1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="0.6b,8b")
@@ -81,6 +106,7 @@ def main():
     ap.add_argument("--serial", type=int, default=4)
     ap.add_argument("--once", default="")
     ap.add_argument("--no-kernel", action="store_true")
+    ap.add_argument("--sampler", action="store_true", help="also the batched sampled path; the serial leg samples too")
     a = ap.parse_args()
     import torch
     from aha_amd import build
@@ -89,35 +115,54 @@ def main():
         name, B = a.once.split(":")
         cfg, m = model_for(name)
         ps = prompts(int(B), a.prompt, cfg.vocab_size)
-        m.generate_batch(ps, a.max_new)
+        if a.sampler:
+            m.generate_batch_sampled(ps, sampler_params(), a.max_new)
+        else:
+            m.generate_batch(ps, a.max_new)
         torch.cuda.synchronize()
         m.close()
         return
     for name in a.only.split(","):
         cfg, m = model_for(name)
         ps_all = prompts(max(int(b) for b in a.batches.split(",")), a.prompt, cfg.vocab_size)
-        # serial decode_greedy over the first --serial prompts
-        dec = 0.0
-        for p in ps_all[:a.serial]:
-            m.clear_cache()
-            _, tok = m.forward_initial(p, 0, want_logits=False)
-            torch.cuda.synchronize()
-            dt, toks = timed(lambda: m.decode_greedy(tok, len(p), a.max_new - 1))
-            dec += dt
-            m.clear_cache()
-        serial_tps = a.serial * (a.max_new - 1) / dec
-        print(json.dumps({"model": name, "serial_decode_tok_s": round(serial_tps, 1), "serial_step_ms": round(dec / (a.serial * (a.max_new - 1)) * 1e3, 3)}),
-              flush=True)
+        if a.sampler:   # serial generate_generic_sampled over the first --serial prompts
+            serial_tps, serial_step = serial_sampled(m, ps_all[:a.serial], a.max_new)
+            print(json.dumps({"model": name, "serial_sampled_decode_tok_s": round(serial_tps, 1), "serial_sampled_step_ms": round(serial_step * 1e3, 3)}),
+                  flush=True)
+        else:   # serial decode_greedy over the first --serial prompts
+            dec = 0.0
+            for p in ps_all[:a.serial]:
+                m.clear_cache()
+                _, tok = m.forward_initial(p, 0, want_logits=False)
+                torch.cuda.synchronize()
+                dt, toks = timed(lambda: m.decode_greedy(tok, len(p), a.max_new - 1))
+                dec += dt
+                m.clear_cache()
+            serial_tps = a.serial * (a.max_new - 1) / dec
+            print(json.dumps({"model": name, "serial_decode_tok_s": round(serial_tps, 1), "serial_step_ms": round(dec / (a.serial * (a.max_new - 1)) * 1e3, 3)}),
+                  flush=True)
         m.generate_batch(ps_all[:2], 4)   # warm-up
+        if a.sampler:
+            m.generate_batch_sampled(ps_all[:2], sampler_params(), 4)
         for B in (int(b) for b in a.batches.split(",")):
             ps = ps_all[:B]
             t1, _ = timed(lambda: m.generate_batch(ps, 1))
             tn, out = timed(lambda: m.generate_batch(ps, a.max_new))
             assert all(len(o) == a.max_new for o in out)
             step = (tn - t1) / (a.max_new - 1)
-            print(json.dumps({"model": name, "B": B, "prompt": a.prompt, "max_new": a.max_new, "total_s": round(tn, 3),
-                              "aggregate_tok_s": round(B * a.max_new / tn, 1), "step_ms": round(step * 1e3, 3),
-                              "decode_tok_s": round(B / step, 1), "decode_vs_serial": round(B / step / serial_tps, 2)}), flush=True)
+            rec = {"model": name, "B": B, "prompt": a.prompt, "max_new": a.max_new, "total_s": round(tn, 3),
+                   "aggregate_tok_s": round(B * a.max_new / tn, 1), "step_ms": round(step * 1e3, 3), "decode_tok_s": round(B / step, 1)}
+            if a.sampler:
+                sp = sampler_params()
+                s1, _ = timed(lambda: m.generate_batch_sampled(ps, sp, 1))
+                sn, out = timed(lambda: m.generate_batch_sampled(ps, sp, a.max_new))
+                assert all(len(o) == a.max_new for o in out)
+                sstep = (sn - s1) / (a.max_new - 1)
+                rec.update({"sampled_total_s": round(sn, 3), "sampled_step_ms": round(sstep * 1e3, 3), "sampled_decode_tok_s": round(B / sstep, 1),
+                            "sampled_vs_greedy": round(sstep / step, 3), "sampled_vs_serial_sampled": round(B / sstep / serial_tps, 2)})
+            else:
+                rec["decode_vs_serial"] = round(B / step / serial_tps, 2)
+            print(json.dumps(rec), flush=True)
         if not a.no_kernel:
             bench_kernel_a(cfg, name)
         m.close()
