@@ -147,6 +147,7 @@ SIGNATURES = {
     "aha_hip_embed_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, _P]),
     "aha_hip_generate_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P]),
     "aha_hip_generate_batch_sampled": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(SamplingParams), C.c_size_t, C.c_size_t, _P, _P, _P]),
+    "aha_hip_generate_batch_mm": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.POINTER(SamplingParams), C.c_size_t, C.c_size_t, _P, _P, _P]),
     "aha_hip_sample_rows": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "aha_hip_sampler_create": (C.c_int, [C.POINTER(SamplingParams), _P]),
     "aha_hip_sampler_destroy": (None, [_P]),

@@ -883,6 +883,24 @@ int aha_hip_generate_batch_sampled(aha_model* m, const uint32_t* input_ids, cons
   return model_generate_batch_sampled(m, input_ids, seq_lens, n_seqs, params, max_new, max_tokens_per_pass, tokens_out, n_out, step_logits_out);
   API_GUARD_END
 }
+int aha_hip_generate_batch_mm(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
+                              const aha_sampling_params* params, size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out,
+                              size_t* n_out, float* step_logits_out) {
+  API_GUARD_BEGIN
+  for (size_t j = 0; params && j < n_seqs && j < ((size_t)1 << 20); ++j) {   // params == NULL: every sequence greedy
+    std::string why;
+    if (sampling_params_check(params[j], &why)) {
+      set_error("generate_batch_mm: params of sequence " + std::to_string(j) + ": " + why);
+      return AHA_ERR_INVALID;
+    }
+  }
+  if (!m) {
+    set_error("null model");
+    return AHA_ERR_INVALID;
+  }
+  return model_generate_batch_mm(m, input_ids, seq_lens, n_seqs, mm, params, max_new, max_tokens_per_pass, tokens_out, n_out, step_logits_out);
+  API_GUARD_END
+}
 int aha_hip_config_parse(const char* model_dir, aha_model_desc* out) {
   API_GUARD_BEGIN
   if (!model_dir || !out) {

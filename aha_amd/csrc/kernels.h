@@ -170,16 +170,19 @@ struct AttnPrefillArgs {
   const void* q_norm_w = nullptr;
   const void* q_rope_tab = nullptr;
   float q_eps = 0.f;
-  // Packed independent causal sequences (model_embed_batch; the 16-rows-per-wave kernel, 4 waves): seg_tab = (segments, 3) int32
-  // {row0, len, page0} on the device -- segment j is q / o rows row0 .. row0 + len - 1 and its cache positions 0 .. len - 1 live on pages
-  // page0, page0 + 1, ... of kv.page_ptrs; seg_items = (n_items, 2) int32 {segment, 64-row q block}, most expensive first.  One block per
-  // (item, head); S = the packed rows, kv_offset / kv_total / S2 unused.
+  // Packed independent sequences (the 16-rows-per-wave kernel, 4 waves): seg_tab = (segments, 3) int32 {row0, len, page0} on the device --
+  // segment j is q / o rows row0 .. row0 + len - 1 and its cache positions 0 .. len - 1 live on pages page0, page0 + 1, ... of
+  // kv.page_ptrs; seg_items = (n_items, 2) int32 {segment, 64-row q block}, most expensive first.  One block per (item, head); S = the
+  // packed rows, kv_offset / kv_total / S2 unused.  Causal (model_embed_batch, generate_batch: head_dim 128, raw q heads with q_norm_w), or
+  // non-causal (the ViT's block-diagonal attention, vision_tower.hip: head_dim 72, q rows in the (N, nh, 96) layout, v_ones_row); a row's
+  // bits are those of its segment's own launch on the 16-row kernel.
   const int32_t* seg_tab = nullptr;
   const int32_t* seg_items = nullptr;
   int n_items = 0;
 };
 void launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t st);
-bool attn_prefill_takes_qfuse(const AttnPrefillArgs& a);   // would launch_attn_prefill run a kernel that norms + rotates Q itself for these arguments?
+bool attn_prefill_takes_qfuse(const AttnPrefillArgs& a);
+int attn_prefill_form_of(const AttnPrefillArgs& a);       // the kernel form launch_attn_prefill takes: 0 = the 16-rows-per-wave kernel, 64 / 65   // would launch_attn_prefill run a kernel that norms + rotates Q itself for these arguments?
 // the one-wave-per-SIMD, 64-q-rows-per-wave form (kernels_attn64.hip); false = not a shape of that kernel, nothing launched
 bool launch_attn_prefill64(const AttnPrefillArgs& a, hipStream_t st, int pipe);
 void set_attn_form_override(int form);     // test hook: -1 = automatic, 16 = the 16-rows-per-wave kernel, 64 / 65 = the 64-row kernel (plain / pipelined)

@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256) void gen_embed_kernel(const bf16_t* __restrict
   for (int i = threadIdx.x; i < H / 8; i += 256) dst[i] = src[i];
   if (threadIdx.x < 64) {
     const int i = threadIdx.x;
-    const float ang = (float)t[GEN_ROW_POS] * inv_freq[i];   // text-only rows: the three M-RoPE positions are equal
+    const float ang = (float)t[GEN_ROW_POS] * inv_freq[i];   // a decode step's three M-RoPE positions are equal (offset + rope_delta)
     (void)axis_map;
     rope[r * 128 + i] = rbf(cosf(ang));
     rope[r * 128 + 64 + i] = rbf(sinf(ang));

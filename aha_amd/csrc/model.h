@@ -205,6 +205,9 @@ int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_le
                          uint32_t* tokens_out, size_t* n_out, float* logits_out);
 int model_generate_batch_sampled(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_sampling_params* params,
                                  size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* step_logits_out);
+int model_generate_batch_mm(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
+                            const aha_sampling_params* params, size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out,
+                            float* step_logits_out);
 int model_forward_initial(aha_model* m, const uint32_t* ids, size_t n, size_t offset, const aha_mm_input* mm,
                           float* logits_out, uint32_t* argmax_out);
 int model_forward_step(aha_model* m, uint32_t token, size_t offset, float* logits_out, uint32_t* argmax_out);

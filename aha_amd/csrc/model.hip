@@ -1882,9 +1882,10 @@ constexpr size_t EMBED_PASS_ROWS = 16384;
 // The single-GPU layer stack of a packed prefill pass of independent sequences (embed_pass, generate_prefill_pass): the rows' embeddings in
 // p_x, their positions' rope table in p_rope; K / V of row r go to cache slot d_slot[r] of the pages page_ptrs names, page p of 0 .. npages-1
 // holding the rows d_prow[2p] .. + d_prow[2p + 1]; the attention runs one block per (d_items entry, head) over d_seg's segments.  Leaves the
-// last layer's output rows in p_x.
+// last layer's output rows in p_x.  vis: the pass has visual rows (the tower's last pass scattered them): DeepStack adds after layer k <
+// n_deepstack (qwen3vl/model.rs:806-822), and on those layers the next in_norm does not ride on down_proj (as in forward_initial_impl).
 static int packed_layers(aha_model* m, int S, const uint64_t* page_ptrs, const int32_t* d_seg, const int32_t* d_items, int n_items,
-                         const int32_t* d_slot, const int32_t* d_prow, int npages, double attn_flops) {
+                         const int32_t* d_slot, const int32_t* d_prow, int npages, double attn_flops, bool vis = false) {
   const aha_model_desc& c = m->desc;
   const int H = c.hidden_size, I = c.intermediate_size, d = c.head_dim, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
   const int nq = nh * d, nkv = kvh * d;
@@ -1940,13 +1941,14 @@ static int packed_layers(aha_model* m, int S, const uint64_t* page_ptrs, const i
     {
       GemmArgs g{};
       g.A = m->p_act; g.W = L.wdown; g.C = m->p_x; g.residual = m->p_x; g.M = S; g.N = H; g.K = I; g.lda = I; g.ldw = I; g.ldc = H; g.act = ACT_NONE;
-      if (li + 1 < c.num_hidden_layers) {
+      if (li + 1 < c.num_hidden_layers && !(vis && vision_has_deepstack(m, li))) {
         g.norm_w = m->layers[li + 1].in_norm; g.norm_out = m->p_h; g.norm_eps = c.rms_norm_eps;
         in_norm_done = true;
       }
       ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + 2.0 * g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
       if ((rc = gemm_row_parallel(m, g, 0))) return rc;
     }
+    if (vis && (rc = vision_deepstack_add(m, li, m->p_x))) return rc;
   }
   return AHA_OK;
 }
@@ -2201,8 +2203,11 @@ static void gen_head(aha_model* m, GenCall& gc, int row0, int rows, uint32_t* to
 }
 
 // One packed prefill pass over sequences j0 .. j0+n_seg-1 (ids: theirs, packed); sequence j's cache starts on logical page page0[j].
+// Positions: sequence j's three M-RoPE rows pos3[j] (3 x len, get_rope_index at offset 0) when it has them, else arange; mm[j] (may be
+// null, or all null): its images / videos, encoded for the whole pass in one tower pass and scattered to its placeholder rows.
 static int generate_prefill_pass(aha_model* m, GenCall& gc, const uint32_t* ids, const size_t* lens, int j0, int n_seg,
-                                 const std::vector<int64_t>& page0) {
+                                 const std::vector<int64_t>& page0, const std::vector<std::vector<int32_t>>& pos3,
+                                 const aha_mm_input* const* mm) {
   const aha_model_desc& c = m->desc;
   const int H = c.hidden_size, nq = c.num_attention_heads * c.head_dim;
   hipStream_t st = m->stream;
@@ -2233,15 +2238,21 @@ static int generate_prefill_pass(aha_model* m, GenCall& gc, const uint32_t* ids,
   std::vector<int32_t> pos(3 * (size_t)S);
   for (int j = 0; j < n_seg; ++j) {
     const int r0 = seg[3 * j], len = seg[3 * j + 1], p0 = seg[3 * j + 2];
+    const std::vector<int32_t>& pj = pos3[(size_t)(j0 + j)];
     for (int i = 0; i < len; ++i) {
       tab[o_slot + r0 + i] = p0 * KV_PAGE_TOKENS + i;
-      for (int a = 0; a < 3; ++a) pos[(size_t)a * S + r0 + i] = i;
+      for (int a = 0; a < 3; ++a) pos[(size_t)a * S + r0 + i] = pj.empty() ? i : pj[(size_t)a * len + i];
     }
     for (int p = 0; p * KV_PAGE_TOKENS < len; ++p) {
       tab[o_prow + 2 * (size_t)(p0 + p)] = r0 + p * KV_PAGE_TOKENS;
       tab[o_prow + 2 * (size_t)(p0 + p) + 1] = std::min(KV_PAGE_TOKENS, len - p * KV_PAGE_TOKENS);
     }
     tab[o_last + j] = r0 + len - 1;
+  }
+  std::vector<VisRequest> vreqs;   // the pass's requests with images / videos, at their first packed row
+  for (int j = 0; j < n_seg && mm; ++j) {
+    const aha_mm_input* q = mm[j0 + j];
+    if (q && (q->n_images > 0 || q->n_videos > 0)) vreqs.push_back(VisRequest{q, ids + seg[3 * j], lens[j], seg[3 * j], j0 + j});
   }
   int rc;
   if ((rc = ensure_prefill_scratch(m, (size_t)S))) return rc;
@@ -2280,11 +2291,13 @@ static int generate_prefill_pass(aha_model* m, GenCall& gc, const uint32_t* ids,
     ProfScope ps(m, "elem", (double)S * H * 4, 0);
     launch_embed_gather(m->embed, m->p_ids, m->p_x, S, H, st);
   }
+  // ViT -> masked_scatter of every request's visual rows into its placeholder rows of the pass (qwen3vl/model.rs:1166-1190)
+  if (!vreqs.empty() && (rc = vision_forward_requests(m, vreqs.data(), vreqs.size(), m->p_x))) return rc;
   launch_rope_table(m->p_pos, S, m->d_inv_freq, m->d_axis_map, S, m->p_rope, st);
   double attn_flops = 0;
   for (int j = 0; j < n_seg; ++j) attn_flops += 4.0 * seg[3 * j + 1] * (0.5 * seg[3 * j + 1]) * nq;
   if ((rc = packed_layers(m, S, gc.pass_pages, m->p_seg + o_seg, m->p_seg + o_items, n_items, m->p_seg + o_slot, m->p_seg + o_prow, npages,
-                          attn_flops)))
+                          attn_flops, !vreqs.empty())))
     return rc;
   // every sequence's last row -> gc.x row j0 + j, then the head -> first tokens into token vector 0
   launch_embed_gather(m->p_x, reinterpret_cast<const uint32_t*>(m->p_seg + o_last), (bf16_t*)gc.x + (int64_t)j0 * H, n_seg, H, st);
@@ -2296,10 +2309,13 @@ static int generate_prefill_pass(aha_model* m, GenCall& gc, const uint32_t* ids,
 
 // params == nullptr: greedy (aha_hip_generate_batch: logits_out = each sequence's last logits).  Otherwise one sampler per sequence
 // (aha_hip_generate_batch_sampled: step_logits_out = every step's logits); the step's tokens are then picked on the host after the batched
-// candidate step, and written back into the token vector the next step's embedding gather reads.
+// candidate step, and written back into the token vector the next step's embedding gather reads.  step_logits_out (greedy or sampled):
+// every step's logits.  mm (aha_hip_generate_batch_mm; may be null): per sequence null or its images / videos -- Qwen3-VL positions
+// (get_rope_index of the sequence alone), the tower per prefill pass, DeepStack in the packed layers, and decode positions kv_len - 1 +
+// the sequence's rope_delta (qwen3vl/model.rs:1235-1264); m->rope_delta is neither read nor written.
 static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
                                size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* logits_out,
-                               const aha_sampling_params* params, float* step_logits_out) {
+                               const aha_sampling_params* params, float* step_logits_out, const aha_mm_input* const* mm = nullptr) {
   const aha_model_desc& c = m->desc;
   if (!ids || !seq_lens || !tokens_out || !n_out) {
     set_error("generate_batch: null input_ids / seq_lens / tokens_out / n_out");
@@ -2341,6 +2357,73 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
         return AHA_ERR_INVALID;
       }
     total += seq_lens[j];
+  }
+  // Qwen3-VL requests: every check of the tower and of get_rope_index here, before any device work; positions (3, len) and rope_delta
+  // of each request with images / videos (a text request: arange, delta 0)
+  std::vector<std::vector<int32_t>> pos3(n_seqs);
+  std::vector<int64_t> rope_delta(n_seqs, 0);
+  if (mm) {
+    size_t off = 0;
+    for (size_t j = 0; j < n_seqs; off += seq_lens[j], ++j) {
+      const aha_mm_input* q = mm[j];
+      if (!q) continue;
+      const std::string who = "generate_batch_mm: sequence " + std::to_string(j) + ": ";
+      if ((q->audio_features && q->n_frames > 0) || (q->audio_samples && q->n_samples > 0)) {
+        set_error(who + "audio input is not supported in batches");
+        return AHA_ERR_UNSUPPORTED;
+      }
+      if (q->image_embeds) {
+        set_error(who + "precomputed image_embeds are not supported in batches (pixel values only)");
+        return AHA_ERR_UNSUPPORTED;
+      }
+      const bool has_img = q->n_images > 0, has_vid = q->n_videos > 0;
+      if (!has_img && !has_vid) continue;
+      if (c.arch != AHA_ARCH_QWEN3VL || !m->vision) {
+        set_error(who + "image input given but this model has no vision tower (arch / model.visual.* weights)");
+        return AHA_ERR_UNSUPPORTED;
+      }
+      if ((has_img && (!q->pixel_values || !q->image_grid_thw)) || (has_vid && (!q->pixel_values_video || !q->video_grid_thw))) {
+        set_error(who + "image / video input without pixel values / grid_thw");
+        return AHA_ERR_INVALID;
+      }
+      if (q->pixel_dtype != AHA_BF16 && q->pixel_dtype != AHA_F32) {
+        set_error(who + "pixel_values must be bf16 or f32");
+        return AHA_ERR_UNSUPPORTED;
+      }
+      const int ms = c.vis_spatial_merge_size;
+      int64_t n_img = 0, n_vid = 0;
+      for (int i = 0; i < (has_img ? q->n_images : 0) + (has_vid ? q->n_videos : 0); ++i) {
+        const bool img = has_img && i < q->n_images;
+        const uint32_t* g = img ? q->image_grid_thw + 3 * i : q->video_grid_thw + 3 * (i - (has_img ? q->n_images : 0));
+        if (ms <= 0 || g[1] % ms || g[2] % ms || g[0] == 0) {
+          set_error(who + "grid_thw: h and w must be multiples of spatial_merge_size");
+          return AHA_ERR_SHAPE;
+        }
+        (img ? n_img : n_vid) += (int64_t)g[0] * g[1] * g[2];
+      }
+      if (n_img != (has_img ? q->n_patches : 0) || n_vid != (has_vid ? q->n_patches_video : 0)) {
+        set_error(who + "pixel_values has " + std::to_string(has_img ? q->n_patches : 0) + " / " + std::to_string(has_vid ? q->n_patches_video : 0) +
+                  " image / video rows, the grids describe " + std::to_string(n_img) + " / " + std::to_string(n_vid));
+        return AHA_ERR_SHAPE;
+      }
+      int64_t n_ipad = 0, n_vpad = 0;
+      for (size_t i = 0; i < seq_lens[j]; ++i) {
+        n_ipad += ids[off + i] == (uint32_t)c.image_token_id;
+        n_vpad += ids[off + i] == (uint32_t)c.video_token_id;
+      }
+      if (n_ipad != n_img / (ms * ms) || n_vpad != n_vid / (ms * ms)) {   // model.rs:1158-1164, 1176-1183
+        set_error(who + "n_image_token num: " + std::to_string(n_ipad) + " / " + std::to_string(n_vpad) + " image / video placeholders, image_embed len: " +
+                  std::to_string(n_img / (ms * ms)) + " / " + std::to_string(n_vid / (ms * ms)));
+        return AHA_ERR_SHAPE;
+      }
+      pos3[j].resize(3 * seq_lens[j]);
+      const int prc = rope_index_core(c, ids + off, seq_lens[j], q->image_grid_thw, has_img ? q->n_images : 0, q->video_grid_thw,
+                                      has_vid ? q->n_videos : 0, pos3[j].data(), &rope_delta[j]);
+      if (prc) {
+        set_error(who + last_error_cstr());
+        return prc;
+      }
+    }
   }
   AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
   int rc = model_clear_cache(m);
@@ -2470,11 +2553,11 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
         AHA_HIP_CHECK(hipGetLastError());
         AHA_HIP_CHECK(hipMemcpyAsync(h_sout, d_sout, (size_t)ns * SAMPLE_OUT_WORDS * 4, hipMemcpyDeviceToHost, st));
       }
-      if (step_logits_out)
-        for (int r = 0; r < R; ++r)
-          AHA_HIP_CHECK(hipMemcpyAsync(step_logits_out + ((size_t)seqs[r] * max_new + n_out[seqs[r]]) * V, gc.logits + (size_t)r * V,
-                                       (size_t)V * 4, hipMemcpyDeviceToHost, st));
     }
+    if (step_logits_out)
+      for (int r = 0; r < R; ++r)
+        AHA_HIP_CHECK(hipMemcpyAsync(step_logits_out + ((size_t)seqs[r] * max_new + n_out[seqs[r]]) * V, gc.logits + (size_t)r * V,
+                                     (size_t)V * 4, hipMemcpyDeviceToHost, st));
     AHA_HIP_CHECK(hipMemcpyAsync(h_tok, tok_dev, (size_t)R * 4, hipMemcpyDeviceToHost, st));
     AHA_HIP_CHECK(hipStreamSynchronize(st));
     if (!params) return AHA_OK;
@@ -2518,7 +2601,7 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
         if (k > j && (rows + len > budget || slots + sl > 2 * budget)) break;
         rows += len, slots += sl, ++k;
       }
-      if ((rc = generate_prefill_pass(m, gc, ids + off, seq_lens + j, (int)j, (int)(k - j), page0))) return rc;
+      if ((rc = generate_prefill_pass(m, gc, ids + off, seq_lens + j, (int)j, (int)(k - j), page0, pos3, mm))) return rc;
       off += rows;
       j = k;
     }
@@ -2564,7 +2647,7 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
       t[GEN_ROW_KVLEN] = kv_len;
       t[GEN_ROW_NSPLIT] = ns;
       t[GEN_ROW_CTR] = (int32_t)ctr_acc[r];
-      t[GEN_ROW_POS] = kv_len - 1;
+      t[GEN_ROW_POS] = (int32_t)(kv_len - 1 + rope_delta[j]);   // seqlen_offset + rope_delta (qwen3vl/model.rs:1235-1264)
       t[GEN_ROW_SRC] = src_row[j];
       t[6] = t[7] = 0;
       if (ns > 1) ctr_acc[r] += (unsigned)L * (unsigned)ns;   // a single split never touches its counter
@@ -2646,6 +2729,12 @@ int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_le
 int model_generate_batch_sampled(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_sampling_params* params,
                                  size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* step_logits_out) {
   return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, nullptr, params, step_logits_out);
+}
+
+int model_generate_batch_mm(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
+                            const aha_sampling_params* params, size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out,
+                            float* step_logits_out) {
+  return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, nullptr, params, step_logits_out, mm);
 }
 
 }  // namespace aha

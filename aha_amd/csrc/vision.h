@@ -13,6 +13,17 @@ int rope_index_core(const aha_model_desc& c, const uint32_t* ids, size_t S, cons
                     const uint32_t* video_grid_thw, int n_videos, int32_t* pos, int64_t* rope_delta);
 int vl_rope_index(aha_model* m, const uint32_t* ids, size_t n, size_t offset, const aha_mm_input* mm, int32_t* pos);
 int vision_forward_and_scatter(aha_model* m, const uint32_t* ids, size_t n, const aha_mm_input* mm, void* x);
+// One request of a tower pass: its images / videos, its ids, the row of x its ids start at; seq >= 0 names it in error messages.
+struct VisRequest {
+  const aha_mm_input* mm;
+  const uint32_t* ids;
+  size_t n;
+  int64_t row0;
+  int seq;
+};
+// The tower over every request's images and videos in ONE pass (no image_embeds), the merged rows scattered to each request's
+// placeholder rows of x; vision_deepstack_add then adds to those rows.  vision_forward_and_scatter = one request at row 0.
+int vision_forward_requests(aha_model* m, const VisRequest* reqs, size_t n_reqs, void* x);
 int vision_deepstack_add(aha_model* m, int layer, void* x);
 bool vision_has_deepstack(aha_model* m, int layer);   // vision_deepstack_add(layer) would change rows
 int vision_debug_embeds(aha_model* m, int which, float* out, size_t n);

@@ -48,6 +48,8 @@ struct VisionModel {
   void* page_store = nullptr;
   uint64_t* d_page_ptrs = nullptr;
   uint64_t page_bytes = 0;
+  size_t pcap = 0;                 // pages of page_store (a pass of many small segments needs more than cap / 64)
+  int32_t* d_seg = nullptr;        // the packed attention launch's {row0, len, page0} segments and (segment, q block) items
   void* merged = nullptr;
   std::vector<void*> deep;
   int64_t n_merged = 0;
@@ -151,6 +153,7 @@ static void vision_free_scratch(VisionModel* v) {
   for (void* p : v->owned) hipFree(p);
   v->owned.clear();
   v->cap = 0;
+  v->pcap = 0;
 }
 
 void vision_destroy(aha_model* m) {
@@ -162,10 +165,11 @@ void vision_destroy(aha_model* m) {
 
 static int vision_ensure_scratch(aha_model* m, size_t N, size_t npages) {
   VisionModel* v = m->vision;
-  if (N <= v->cap) return AHA_OK;
+  if (N <= v->cap && npages <= v->pcap) return AHA_OK;
   AHA_HIP_CHECK(hipStreamSynchronize(m->stream));
+  const size_t n_keep = std::max(N, v->cap);
   vision_free_scratch(v);
-  const size_t cap = (N + 255) / 256 * 256, pcap = npages + cap / KV_PAGE_TOKENS + 64;
+  const size_t cap = (n_keep + 255) / 256 * 256, pcap = npages + cap / KV_PAGE_TOKENS + 64;
   auto al = [&](size_t bytes, void** out, bool zero = false) -> int {
     void* p = nullptr;
     hipError_t e = hipMalloc(&p, bytes);
@@ -199,6 +203,7 @@ static int vision_ensure_scratch(aha_model* m, size_t N, size_t npages) {
   if ((rc = al(pcap * 8, (void**)&v->d_page_ptrs))) return rc;
   if ((rc = al(pcap * 4, (void**)&v->d_page_first))) return rc;
   if ((rc = al(pcap * 4, (void**)&v->d_page_cnt))) return rc;
+  if ((rc = al(pcap * 5 * 4, (void**)&v->d_seg))) return rc;   // <= pcap segments x 3 + <= pcap items x 2 (a 64-row item per page)
   {
     std::vector<uint64_t> ptrs(pcap);
     for (size_t i = 0; i < pcap; ++i) ptrs[i] = (uint64_t)(uintptr_t)v->page_store + i * v->page_bytes;
@@ -214,6 +219,7 @@ static int vision_ensure_scratch(aha_model* m, size_t N, size_t npages) {
   v->gemm_ws_bytes = std::min((size_t)8 * cap * D * 4, (size_t)1 << 30);
   if ((rc = al(v->gemm_ws_bytes, &v->gemm_ws))) return rc;
   v->cap = cap;
+  v->pcap = pcap;
   return AHA_OK;
 }
 
@@ -286,58 +292,86 @@ int vision_forward_and_scatter(aha_model* m, const uint32_t* ids, size_t n, cons
     AHA_HIP_CHECK(hipGetLastError());
     return AHA_OK;
   }
-  const bool has_img = mm->n_images > 0, has_vid = mm->n_videos > 0;
-  if ((!has_img && !has_vid) || (has_img && (!mm->pixel_values || !mm->image_grid_thw)) ||
-      (has_vid && (!mm->pixel_values_video || !mm->video_grid_thw))) {
-    set_error("forward_initial: image / video input without pixel values / grid_thw");
-    return AHA_ERR_INVALID;
+  const VisRequest r{mm, ids, n, 0, -1};
+  return vision_forward_requests(m, &r, 1, x_text);
+}
+
+// Every (image | video frame) of a list of requests through ONE tower pass.  Rows: request order, within a request image patches then
+// video patches; merged rows likewise, scattered to each request's placeholder rows (request row0 + its <|image_pad|> positions, then
+// its <|video_pad|> positions) of x_text.  forward_initial: one request at row 0; generate_batch_mm: the requests of a prefill pass.
+int vision_forward_requests(aha_model* m, const VisRequest* reqs, size_t n_reqs, void* x_text) {
+  VisionModel* v = m->vision;
+  const aha_model_desc& c = m->desc;
+  if (!v) {
+    set_error("this model was created without vision tower weights (model.visual.*)");
+    return AHA_ERR_UNSUPPORTED;
   }
-  const bool encode_only = ids == nullptr;
+  const int ms = v->merge;
+  const bool encode_only = n_reqs == 1 && reqs[0].ids == nullptr;
   // ---- host index construction ------------------------------------------------------------------------------
   // The reference encodes the images and the videos in two get_vision_features calls (model.rs:1150-1187); every (grid, frame) is
-  // its own attention segment and every other op of the tower is row-wise, so here both lists go through ONE pass: rows =
-  // image patches, then video patches; merged rows = image tokens, then video tokens.
+  // its own attention segment and every other op of the tower is row-wise, so here both lists -- of every request -- go through ONE
+  // pass: rows = request 0's image patches, then its video patches, then request 1's, ...; merged rows in the same order.
   std::vector<const uint32_t*> grids;
-  for (int i = 0; i < (has_img ? mm->n_images : 0); ++i) grids.push_back(mm->image_grid_thw + 3 * i);
-  for (int i = 0; i < (has_vid ? mm->n_videos : 0); ++i) grids.push_back(mm->video_grid_thw + 3 * i);
-  int64_t N = 0, N_img = 0;
-  for (size_t i = 0; i < grids.size(); ++i) {
-    const uint32_t* g = grids[i];
-    if (g[1] % ms || g[2] % ms || g[0] == 0) {
-      set_error("grid_thw: h and w must be multiples of spatial_merge_size");
+  std::vector<int64_t> req_img(n_reqs), req_vid(n_reqs);   // patch rows of each request's images / videos
+  std::vector<int32_t> vis_rows;
+  int64_t N = 0;
+  for (size_t q = 0; q < n_reqs; ++q) {
+    const aha_mm_input* mm = reqs[q].mm;
+    const std::string who = reqs[q].seq >= 0 ? "sequence " + std::to_string(reqs[q].seq) + ": " : "";
+    const bool has_img = mm->n_images > 0, has_vid = mm->n_videos > 0;
+    if ((!has_img && !has_vid) || (has_img && (!mm->pixel_values || !mm->image_grid_thw)) ||
+        (has_vid && (!mm->pixel_values_video || !mm->video_grid_thw))) {
+      set_error(who + "forward_initial: image / video input without pixel values / grid_thw");
+      return AHA_ERR_INVALID;
+    }
+    int64_t n_img = 0, n_vid = 0;
+    for (int i = 0; i < (has_img ? mm->n_images : 0) + (has_vid ? mm->n_videos : 0); ++i) {
+      const bool img = has_img && i < mm->n_images;
+      const uint32_t* g = img ? mm->image_grid_thw + 3 * i : mm->video_grid_thw + 3 * (i - (has_img ? mm->n_images : 0));
+      if (g[1] % ms || g[2] % ms || g[0] == 0) {
+        set_error(who + "grid_thw: h and w must be multiples of spatial_merge_size");
+        return AHA_ERR_SHAPE;
+      }
+      grids.push_back(g);
+      (img ? n_img : n_vid) += (int64_t)g[0] * g[1] * g[2];
+    }
+    if (n_img != (has_img ? mm->n_patches : 0)) {
+      set_error(who + "pixel_values has " + std::to_string(mm->n_patches) + " rows, image_grid_thw describes " + std::to_string(n_img));
       return AHA_ERR_SHAPE;
     }
-    N += (int64_t)g[0] * g[1] * g[2];
-    if (has_img && (int)i == mm->n_images - 1) N_img = N;
-  }
-  const int64_t N_vid = N - N_img;
-  if (N_img != (has_img ? mm->n_patches : 0)) {
-    set_error("pixel_values has " + std::to_string(mm->n_patches) + " rows, image_grid_thw describes " + std::to_string(N_img));
-    return AHA_ERR_SHAPE;
-  }
-  if (N_vid != (has_vid ? mm->n_patches_video : 0)) {
-    set_error("pixel_values_video has " + std::to_string(mm->n_patches_video) + " rows, video_grid_thw describes " + std::to_string(N_vid));
-    return AHA_ERR_SHAPE;
+    if (n_vid != (has_vid ? mm->n_patches_video : 0)) {
+      set_error(who + "pixel_values_video has " + std::to_string(mm->n_patches_video) + " rows, video_grid_thw describes " + std::to_string(n_vid));
+      return AHA_ERR_SHAPE;
+    }
+    if (mm->pixel_dtype != AHA_BF16 && mm->pixel_dtype != AHA_F32) {
+      set_error(who + "pixel_values must be bf16 or f32");
+      return AHA_ERR_UNSUPPORTED;
+    }
+    req_img[q] = n_img, req_vid[q] = n_vid;
+    N += n_img + n_vid;
+    if (!encode_only) {
+      const uint32_t* ids = reqs[q].ids;
+      const size_t v0 = vis_rows.size();
+      for (size_t i = 0; i < reqs[q].n; ++i)
+        if (ids[i] == (uint32_t)c.image_token_id) vis_rows.push_back((int32_t)(reqs[q].row0 + (int64_t)i));
+      if ((int64_t)(vis_rows.size() - v0) != n_img / (ms * ms)) {  // model.rs:1158-1164
+        set_error(who + "n_image_token num: " + std::to_string(vis_rows.size() - v0) + " not equal to image_embed len: " + std::to_string(n_img / (ms * ms)));
+        return AHA_ERR_SHAPE;
+      }
+      for (size_t i = 0; i < reqs[q].n; ++i)
+        if (ids[i] == (uint32_t)c.video_token_id) vis_rows.push_back((int32_t)(reqs[q].row0 + (int64_t)i));
+      if ((int64_t)(vis_rows.size() - v0) != (n_img + n_vid) / (ms * ms)) {  // model.rs:1176-1183 (the reference reuses the image wording)
+        set_error(who + "n_image_token num: " + std::to_string(vis_rows.size() - v0 - n_img / (ms * ms)) + " not equal to image_embed len: " +
+                  std::to_string(n_vid / (ms * ms)));
+        return AHA_ERR_SHAPE;
+      }
+    }
   }
   const int64_t n4 = N / (ms * ms);
-  std::vector<int32_t> vis_rows;
-  if (!encode_only) {
-    for (size_t i = 0; i < n; ++i)
-      if (ids[i] == (uint32_t)c.image_token_id) vis_rows.push_back((int32_t)i);
-    if ((int64_t)vis_rows.size() != N_img / (ms * ms)) {  // model.rs:1158-1164
-      set_error("n_image_token num: " + std::to_string(vis_rows.size()) + " not equal to image_embed len: " + std::to_string(N_img / (ms * ms)));
-      return AHA_ERR_SHAPE;
-    }
-    for (size_t i = 0; i < n; ++i)
-      if (ids[i] == (uint32_t)c.video_token_id) vis_rows.push_back((int32_t)i);
-    if ((int64_t)vis_rows.size() != n4) {  // model.rs:1176-1183 (the reference reuses the image wording)
-      set_error("n_image_token num: " + std::to_string(vis_rows.size() - N_img / (ms * ms)) + " not equal to image_embed len: " + std::to_string(N_vid / (ms * ms)));
-      return AHA_ERR_SHAPE;
-    }
-  }
   std::vector<int32_t> idx(4 * N), rowcol(2 * N), page_of(N), slot_of(N);
   std::vector<float> wt(4 * N);
-  struct Seg { int64_t start, len, page0; };
+  struct Seg { int64_t start, len, page0; bool small; };
   std::vector<Seg> segs;
   int64_t off = 0, pages = 0;
   const float Gm1 = (float)(v->G - 1);
@@ -359,7 +393,7 @@ int vision_forward_and_scatter(aha_model* m, const uint32_t* ids, size_t n, cons
     lin(h, hv, hf, hc);
     lin(w, wv, wf, wc);
     for (int ti = 0; ti < t; ++ti) {
-      segs.push_back({off + (int64_t)ti * h * w, (int64_t)h * w, pages});
+      segs.push_back({off + (int64_t)ti * h * w, (int64_t)h * w, pages, false});
       for (int bh = 0; bh < h / ms; ++bh)
         for (int bw = 0; bw < w / ms; ++bw)
           for (int ih = 0; ih < ms; ++ih)
@@ -390,22 +424,27 @@ int vision_forward_and_scatter(aha_model* m, const uint32_t* ids, size_t n, cons
   GemmWorkspaceScope ws_scope(v->gemm_ws, v->gemm_ws_bytes, m->d_sk_ctrs);
   hipStream_t st = m->stream;
   // ---- uploads ---------------------------------------------------------------------------------------------------
-  if (mm->pixel_dtype == AHA_BF16) {
-    if (N_img) AHA_HIP_CHECK(hipMemcpyAsync(v->pix, mm->pixel_values, (size_t)N_img * v->patch_dim * 2, hipMemcpyDefault, st));
-    if (N_vid)
-      AHA_HIP_CHECK(hipMemcpyAsync((char*)v->pix + (size_t)N_img * v->patch_dim * 2, mm->pixel_values_video, (size_t)N_vid * v->patch_dim * 2,
-                                   hipMemcpyDefault, st));
-  } else if (mm->pixel_dtype == AHA_F32) {
-    std::vector<uint16_t> tmp((size_t)N * v->patch_dim);
-    const float* f = (const float*)mm->pixel_values;
-    const float* fv = (const float*)mm->pixel_values_video;
-    const size_t n_img_el = (size_t)N_img * v->patch_dim;
-    for (size_t i = 0; i < n_img_el; ++i) tmp[i] = f2bf_host(f[i]);
-    for (size_t i = n_img_el; i < tmp.size(); ++i) tmp[i] = f2bf_host(fv[i - n_img_el]);
-    AHA_HIP_CHECK(hipMemcpy(v->pix, tmp.data(), tmp.size() * 2, hipMemcpyHostToDevice));
-  } else {
-    set_error("pixel_values must be bf16 or f32");
-    return AHA_ERR_UNSUPPORTED;
+  {
+    int64_t row = 0;
+    const size_t pd = (size_t)v->patch_dim;
+    for (size_t q = 0; q < n_reqs; ++q) {
+      const aha_mm_input* mm = reqs[q].mm;
+      const int64_t N_img = req_img[q], N_vid = req_vid[q];
+      char* dst = (char*)v->pix + (size_t)row * pd * 2;
+      if (mm->pixel_dtype == AHA_BF16) {
+        if (N_img) AHA_HIP_CHECK(hipMemcpyAsync(dst, mm->pixel_values, (size_t)N_img * pd * 2, hipMemcpyDefault, st));
+        if (N_vid) AHA_HIP_CHECK(hipMemcpyAsync(dst + (size_t)N_img * pd * 2, mm->pixel_values_video, (size_t)N_vid * pd * 2, hipMemcpyDefault, st));
+      } else {   // AHA_F32 (checked above)
+        std::vector<uint16_t> tmp((size_t)(N_img + N_vid) * pd);
+        const float* f = (const float*)mm->pixel_values;
+        const float* fv = (const float*)mm->pixel_values_video;
+        const size_t n_img_el = (size_t)N_img * pd;
+        for (size_t i = 0; i < n_img_el; ++i) tmp[i] = f2bf_host(f[i]);
+        for (size_t i = n_img_el; i < tmp.size(); ++i) tmp[i] = f2bf_host(fv[i - n_img_el]);
+        AHA_HIP_CHECK(hipMemcpy(dst, tmp.data(), tmp.size() * 2, hipMemcpyHostToDevice));
+      }
+      row += N_img + N_vid;
+    }
   }
   AHA_HIP_CHECK(hipMemcpyAsync(v->d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, st));
   AHA_HIP_CHECK(hipMemcpyAsync(v->d_wt, wt.data(), wt.size() * 4, hipMemcpyHostToDevice, st));
@@ -420,6 +459,52 @@ int vision_forward_and_scatter(aha_model* m, const uint32_t* ids, size_t n, cons
     }
   AHA_HIP_CHECK(hipMemcpyAsync(v->d_page_first, page_first.data(), page_first.size() * 4, hipMemcpyHostToDevice, st));
   AHA_HIP_CHECK(hipMemcpyAsync(v->d_page_cnt, page_cnt.data(), page_cnt.size() * 4, hipMemcpyHostToDevice, st));
+  // One attention launch per (image, frame) segment cannot fill the chip for the small images of chat (448 x 448: 784 patches = 13 q
+  // blocks x 16 heads = 208 workgroups on 256 CUs), so every segment whose own launch would take the 16-rows-per-wave kernel joins ONE
+  // packed launch (AttnPrefillArgs::seg_tab: a block per (segment, 64-row q block, head), each segment over its own pages, the items
+  // longest segment first).  A row's arithmetic does not depend on the launch it rides in nor on the waves per block, so the tower's bits
+  // are those of the per-segment launches.  Segments large enough for the 64-row forms keep their own launches.
+  // AHA_VIT_SEG_ATTN=0: every segment its own launch (A/B).
+  KvLayer kv{};
+  kv.page_ptrs = v->d_page_ptrs;
+  kv.layer_off = 0;
+  kv.kvh = v->nh;
+  kv.d = v->hd;
+  static const bool seg_attn = [] { const char* e = getenv("AHA_VIT_SEG_ATTN"); return e ? atoi(e) != 0 : true; }();
+  auto seg_args = [&](int64_t start, int64_t page0) {
+    AttnPrefillArgs a{};
+    a.q = (const char*)v->q + (size_t)start * v->nh * VIT_DQK * 2;
+    a.kv = kv;
+    a.kv.page_ptrs = v->d_page_ptrs + page0;
+    a.o = (char*)v->attn + (size_t)start * v->D * 2;
+    a.nh = v->nh; a.kvh = v->nh; a.d = v->hd; a.kv_offset = 0; a.causal = 0;
+    a.scale = v->scale;
+    a.v_ones_row = 1;   // launch_vit_rope_pack wrote 1.0 into V^T pad row 72 of every real token
+    return a;
+  };
+  int n_small = 0, n_seg_items = 0;
+  int64_t small_rows = 0;
+  double small_flops = 0;
+  std::vector<int32_t> stab;   // (lives until the synchronise below: pageable)
+  if (seg_attn) {
+    std::vector<std::pair<int, int>> items;   // (segment, 64-row q block)
+    for (Seg& s : segs) {
+      AttnPrefillArgs a = seg_args(s.start, s.page0);
+      a.S = (int)s.len; a.kv_total = (int)s.len;
+      if (attn_prefill_form_of(a) != 0) continue;
+      s.small = true;
+      for (int b = 0; (int64_t)b * 64 < s.len; ++b) items.emplace_back(n_small, b);
+      stab.push_back((int32_t)s.start), stab.push_back((int32_t)s.len), stab.push_back((int32_t)s.page0);
+      ++n_small;
+      small_rows += s.len;
+      small_flops += 4.0 * s.len * s.len * v->D;
+    }
+    // non-causal: a block's cost is its segment's length
+    std::stable_sort(items.begin(), items.end(), [&](const auto& x, const auto& y) { return stab[3 * x.first + 1] > stab[3 * y.first + 1]; });
+    n_seg_items = (int)items.size();
+    for (const auto& it : items) stab.push_back(it.first), stab.push_back(it.second);
+    if (n_small > 0) AHA_HIP_CHECK(hipMemcpyAsync(v->d_seg, stab.data(), stab.size() * 4, hipMemcpyHostToDevice, st));
+  }
   if (!m->cp_row_map.empty())
     for (auto& r : vis_rows) r = m->cp_row_map[r];
   AHA_HIP_CHECK(hipMemcpyAsync(v->d_vis_rows, vis_rows.data(), vis_rows.size() * 4, hipMemcpyHostToDevice, st));
@@ -431,11 +516,6 @@ int vision_forward_and_scatter(aha_model* m, const uint32_t* ids, size_t n, cons
     ProfScope ps(m, "elem", (double)N * v->D * 2 * 6, 0);
     launch_pos_embed_add(v->x, v->pos_table, v->d_idx, v->d_wt, N, v->D, st);
   }
-  KvLayer kv{};
-  kv.page_ptrs = v->d_page_ptrs;
-  kv.layer_off = 0;
-  kv.kvh = v->nh;
-  kv.d = v->hd;
   launch_vit_rope_table(v->d_rowcol, v->d_inv_freq, (int)N, v->hd, v->d_cs_tab, st);
   // Row-wise launches folded into the GEMM calls (round 6; round-5 verdict, weak #5): norm2 rides on proj, norm1 of block i + 1 on block
   // i's fc2 -- inside the split-K reduce pass when the plan has one (kernels_gemm.hip gemm_splitk_reduce_layernorm_kernel), bit-identical
@@ -457,15 +537,18 @@ int vision_forward_and_scatter(aha_model* m, const uint32_t* ids, size_t n, cons
       ProfScope ps(m, "elem", (double)N * v->D * 3 * 4, 0);
       launch_vit_rope_pack(r, st);
     }
-    for (const Seg& s : segs) {  // block-diagonal attention: one launch per (image, frame) segment (model.rs:258-273)
-      AttnPrefillArgs a{};
-      a.q = (const char*)v->q + (size_t)s.start * v->nh * VIT_DQK * 2;
-      a.kv = kv;
-      a.kv.page_ptrs = v->d_page_ptrs + s.page0;
-      a.o = (char*)v->attn + (size_t)s.start * v->D * 2;
-      a.S = (int)s.len; a.nh = v->nh; a.kvh = v->nh; a.d = v->hd; a.kv_offset = 0; a.kv_total = (int)s.len; a.causal = 0;
-      a.scale = v->scale;
-      a.v_ones_row = 1;   // launch_vit_rope_pack above wrote 1.0 into V^T pad row 72 of every real token
+    // block-diagonal attention (model.rs:258-273): the packed launch over the small segments, one launch per large one
+    if (n_small > 0) {
+      AttnPrefillArgs a = seg_args(0, 0);
+      a.S = (int)small_rows; a.kv_total = (int)small_rows;
+      a.seg_tab = v->d_seg; a.seg_items = v->d_seg + 3 * (size_t)n_small; a.n_items = n_seg_items;
+      ProfScope ps(m, "attn_vit", (double)small_rows * v->D * 8, small_flops);
+      launch_attn_prefill(a, st);
+    }
+    for (const Seg& s : segs) {
+      if (s.small) continue;
+      AttnPrefillArgs a = seg_args(s.start, s.page0);
+      a.S = (int)s.len; a.kv_total = (int)s.len;
       ProfScope ps(m, "attn_vit", (double)s.len * v->D * 8, 4.0 * s.len * s.len * v->D);
       launch_attn_prefill(a, st);
     }

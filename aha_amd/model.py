@@ -52,6 +52,61 @@ class MultiModalData:
     image_embeds: Optional[torch.Tensor] = None
 
 
+def _mm_input(data: MultiModalData):
+    """MultiModalData -> aha_mm_input.  Returns (struct, arrays the struct points into: keep them alive for the call)."""
+    mm = MmInput()
+    keep = []
+    if data.pixel_values is not None:
+        pv = data.pixel_values.detach().contiguous()
+        if pv.is_cuda:  # produced on torch's stream; the library copies on its own stream
+            torch.cuda.current_stream(pv.device).synchronize()
+        grid = np.ascontiguousarray(np.asarray(data.image_grid_thw, dtype=np.uint32).reshape(-1, 3))
+        keep += [pv, grid]
+        mm.pixel_values = pv.data_ptr()
+        mm.pixel_dtype = _DT[pv.dtype]
+        mm.n_patches = pv.shape[0]
+        mm.image_grid_thw = grid.ctypes.data_as(C.POINTER(C.c_uint32))
+        mm.n_images = grid.shape[0]
+    if data.pixel_values_video is not None:
+        pvv = data.pixel_values_video.detach().contiguous()
+        if pvv.is_cuda:
+            torch.cuda.current_stream(pvv.device).synchronize()
+        assert data.pixel_values is None or pvv.dtype == data.pixel_values.dtype, "image and video pixel values share a dtype"
+        vgrid = np.ascontiguousarray(np.asarray(data.video_grid_thw, dtype=np.uint32).reshape(-1, 3))
+        keep += [pvv, vgrid]
+        mm.pixel_values_video = pvv.data_ptr()
+        mm.pixel_dtype = _DT[pvv.dtype]
+        mm.n_patches_video = pvv.shape[0]
+        mm.video_grid_thw = vgrid.ctypes.data_as(C.POINTER(C.c_uint32))
+        mm.n_videos = vgrid.shape[0]
+    if data.image_embeds is not None:
+        ie = data.image_embeds.detach().contiguous()
+        assert ie.is_cuda and ie.dtype == torch.bfloat16 and ie.dim() == 3
+        torch.cuda.current_stream(ie.device).synchronize()
+        grid = np.ascontiguousarray(np.asarray(data.image_grid_thw if data.image_grid_thw is not None else [], dtype=np.uint32).reshape(-1, 3))
+        keep += [ie, grid]
+        mm.image_embeds = ie.data_ptr()
+        mm.n_image_tokens = ie.shape[1]
+        mm.image_grid_thw = grid.ctypes.data_as(C.POINTER(C.c_uint32)) if grid.shape[0] else None
+        mm.n_images = grid.shape[0]
+        if data.video_grid_thw is not None and data.pixel_values_video is None:   # (the grids still drive get_rope_index)
+            vgrid = np.ascontiguousarray(np.asarray(data.video_grid_thw, dtype=np.uint32).reshape(-1, 3))
+            keep.append(vgrid)
+            mm.video_grid_thw = vgrid.ctypes.data_as(C.POINTER(C.c_uint32))
+            mm.n_videos = vgrid.shape[0]
+    if data.audio_features is not None:
+        af = np.ascontiguousarray(np.asarray(data.audio_features, dtype=np.float32))
+        keep.append(af)
+        mm.audio_features = af.ctypes.data_as(C.POINTER(C.c_float))
+        mm.n_frames = af.shape[1]
+    if data.audio_samples is not None:
+        au = np.ascontiguousarray(np.asarray(data.audio_samples, dtype=np.float32).reshape(-1))
+        keep.append(au)
+        mm.audio_samples = au.ctypes.data_as(C.POINTER(C.c_float))
+        mm.n_samples = au.size
+    return mm, keep
+
+
 def make_desc(cfg, kv_reserve_tokens: int = 0) -> ModelDesc:
     d = ModelDesc()
     if isinstance(cfg, Qwen3VLConfig):
@@ -219,51 +274,9 @@ class HipInferenceModel:
                         want_logits: bool = True):
         ids = np.ascontiguousarray(np.asarray(input_ids, dtype=np.uint32).reshape(-1))
         am = C.c_uint32()
-        mm_ref = None
+        mm_ref, keep = None, None
         if data is not None:
-            mm = MmInput()
-            if data.pixel_values is not None:
-                pv = data.pixel_values.detach().contiguous()
-                if pv.is_cuda:  # produced on torch's stream; the library copies on its own stream
-                    torch.cuda.current_stream(pv.device).synchronize()
-                grid = np.ascontiguousarray(np.asarray(data.image_grid_thw, dtype=np.uint32).reshape(-1, 3))
-                mm.pixel_values = pv.data_ptr()
-                mm.pixel_dtype = _DT[pv.dtype]
-                mm.n_patches = pv.shape[0]
-                mm.image_grid_thw = grid.ctypes.data_as(C.POINTER(C.c_uint32))
-                mm.n_images = grid.shape[0]
-            if data.pixel_values_video is not None:
-                pvv = data.pixel_values_video.detach().contiguous()
-                if pvv.is_cuda:
-                    torch.cuda.current_stream(pvv.device).synchronize()
-                assert data.pixel_values is None or pvv.dtype == data.pixel_values.dtype, "image and video pixel values share a dtype"
-                vgrid = np.ascontiguousarray(np.asarray(data.video_grid_thw, dtype=np.uint32).reshape(-1, 3))
-                mm.pixel_values_video = pvv.data_ptr()
-                mm.pixel_dtype = _DT[pvv.dtype]
-                mm.n_patches_video = pvv.shape[0]
-                mm.video_grid_thw = vgrid.ctypes.data_as(C.POINTER(C.c_uint32))
-                mm.n_videos = vgrid.shape[0]
-            if data.image_embeds is not None:
-                ie = data.image_embeds.detach().contiguous()
-                assert ie.is_cuda and ie.dtype == torch.bfloat16 and ie.dim() == 3
-                torch.cuda.current_stream(ie.device).synchronize()
-                grid = np.ascontiguousarray(np.asarray(data.image_grid_thw if data.image_grid_thw is not None else [], dtype=np.uint32).reshape(-1, 3))
-                mm.image_embeds = ie.data_ptr()
-                mm.n_image_tokens = ie.shape[1]
-                mm.image_grid_thw = grid.ctypes.data_as(C.POINTER(C.c_uint32)) if grid.shape[0] else None
-                mm.n_images = grid.shape[0]
-                if data.video_grid_thw is not None and data.pixel_values_video is None:   # (the grids still drive get_rope_index)
-                    vgrid = np.ascontiguousarray(np.asarray(data.video_grid_thw, dtype=np.uint32).reshape(-1, 3))
-                    mm.video_grid_thw = vgrid.ctypes.data_as(C.POINTER(C.c_uint32))
-                    mm.n_videos = vgrid.shape[0]
-            if data.audio_features is not None:
-                af = np.ascontiguousarray(np.asarray(data.audio_features, dtype=np.float32))
-                mm.audio_features = af.ctypes.data_as(C.POINTER(C.c_float))
-                mm.n_frames = af.shape[1]
-            if data.audio_samples is not None:
-                au = np.ascontiguousarray(np.asarray(data.audio_samples, dtype=np.float32).reshape(-1))
-                mm.audio_samples = au.ctypes.data_as(C.POINTER(C.c_float))
-                mm.n_samples = au.size
+            mm, keep = _mm_input(data)
             mm_ref = C.byref(mm)
         lp = self._logits.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None
         check(lib().aha_hip_forward_initial(self.handle, ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.size,
@@ -370,6 +383,43 @@ class HipInferenceModel:
         check(lib().aha_hip_generate_batch_sampled(self.handle, ids.ctypes.data, lens.ctypes.data, len(seqs), cp, int(max_new),
                                                    int(max_tokens_per_pass), toks.ctypes.data, n_out.ctypes.data,
                                                    None if step is None else step.ctypes.data))
+        out = [[int(t) for t in toks[j, :int(n_out[j])]] for j in range(len(seqs))]
+        return (out, step) if want_step_logits else out
+
+    def generate_batch_mm(self, prompts: Sequence[Sequence[int]], data, max_new: int, params=None, max_tokens_per_pass: int = 0,
+                          want_step_logits: bool = False):
+        """Generation of every request at once, with its images / videos (aha_hip_generate_batch_mm): data[j] is request j's
+        MultiModalData (pixel values and grids; no image_embeds, no audio) or None for a text request; data itself may be None.
+        params: None = every request greedy, else a sampling.SamplingParams per request (or one for all).  Per request, the tokens
+        generate_generic yields for it alone with its data.  Returns a list of token lists, and with want_step_logits also the
+        (len(prompts), max_new, vocab) float32 logits that chose each token (rows past a sequence's length are zero)."""
+        from .sampling import SamplingParams
+        seqs = [np.asarray(x, dtype=np.uint32).reshape(-1) for x in prompts]
+        if data is not None and len(data) != len(seqs):
+            raise ValueError(f"{len(data)} MultiModalData entries for {len(seqs)} prompts")
+        cp = None
+        if params is not None:
+            if isinstance(params, SamplingParams):
+                params = [params] * len(seqs)
+            if len(params) != len(seqs):
+                raise ValueError(f"{len(params)} sampling params for {len(seqs)} prompts")
+            cp = (_lib.SamplingParams * max(len(seqs), 1))(*[p.to_c() for p in params])
+        keep, mm_arr = [], None
+        if data is not None:
+            mm_arr = (C.c_void_p * max(len(seqs), 1))()
+            for j, d in enumerate(data):
+                if d is not None:
+                    mm, k = _mm_input(d)
+                    keep += [mm, k]
+                    mm_arr[j] = C.addressof(mm)
+        ids = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0, np.uint32))
+        lens = np.ascontiguousarray([s.size for s in seqs], dtype=np.uint64)
+        toks = np.zeros((len(seqs), max(int(max_new), 1)), dtype=np.uint32)
+        n_out = np.zeros(len(seqs), dtype=np.uint64)
+        step = np.zeros((len(seqs), max(int(max_new), 1), self.text_cfg.vocab_size), dtype=np.float32) if want_step_logits else None
+        check(lib().aha_hip_generate_batch_mm(self.handle, ids.ctypes.data, lens.ctypes.data, len(seqs), mm_arr, cp, int(max_new),
+                                              int(max_tokens_per_pass), toks.ctypes.data, n_out.ctypes.data,
+                                              None if step is None else step.ctypes.data))
         out = [[int(t) for t in toks[j, :int(n_out[j])]] for j in range(len(seqs))]
         return (out, step) if want_step_logits else out
 
@@ -547,5 +597,16 @@ def generate_generic_batch_sampled(model: HipInferenceModel, prompts: Sequence[S
     generate_generic_batch)."""
     t0 = time.perf_counter()
     out = model.generate_batch_sampled(prompts, params, max_tokens, max_tokens_per_pass)
+    secs = time.perf_counter() - t0
+    return out, Usage(sum(len(p) for p in prompts), 0.0, sum(len(o) for o in out), secs)
+
+
+def generate_generic_batch_mm(model: HipInferenceModel, prompts: Sequence[Sequence[int]], data, max_tokens: int, params=None,
+                              max_tokens_per_pass: int = 0):
+    """generate_generic for many requests with their images / videos (data: a MultiModalData or None per prompt) in one call
+    (HipInferenceModel.generate_batch_mm); params None = greedy.  Returns (per-prompt generated token ids, Usage over all prompts,
+    timed as in generate_generic_batch)."""
+    t0 = time.perf_counter()
+    out = model.generate_batch_mm(prompts, data, max_tokens, params, max_tokens_per_pass)
     secs = time.perf_counter() - t0
     return out, Usage(sum(len(p) for p in prompts), 0.0, sum(len(o) for o in out), secs)

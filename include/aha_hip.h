@@ -220,6 +220,28 @@ int aha_hip_generate_batch_sampled(aha_model* m, const uint32_t* input_ids, cons
                                    const aha_sampling_params* params, size_t max_new, size_t max_tokens_per_pass,
                                    uint32_t* tokens_out, size_t* n_out, float* step_logits_out);
 
+/* ---- batched generation with images ------------------------------------------------------------------------------------
+ * aha_hip_generate_batch / _sampled for Qwen3-VL requests with images and videos.  mm: n_seqs entries, each NULL (a text request) or
+ * that request's images and / or videos with forward_initial's rules (pixel values in host or device memory, bf16 or f32, grids on
+ * the host); mm == NULL: every request is text.  params: NULL = every sequence greedy, else n_seqs samplers with exactly the semantics
+ * of aha_hip_generate_batch_sampled (one RNG stream per sequence).  step_logits_out: the layout of _sampled (n_seqs x max_new x vocab
+ * f32, may be NULL), for greedy sequences too: entry [j, n_out[j] - 1] of a greedy sequence is aha_hip_generate_batch's logits_out.
+ * Row j of tokens_out holds what generate_generic (generate.rs:115-159) yields for request j alone, on a cleared model, with its
+ * MultiModalData (sampled rows: given the logits this call computes).  Per request, as Qwen3VLModel::forward does it for one:
+ *   positions      get_rope_index of its own ids and grids at offset 0 (qwen3vl/model.rs:901-1133), a text request arange;
+ *   visual rows    the merged tower rows masked_scatter'ed into its <|image_pad|> then <|video_pad|> rows (model.rs:1166-1190);
+ *   DeepStack      feature k added to its visual rows after decoder layer k (model.rs:806-822);
+ *   decode         position seqlen_offset + its own rope_delta on all three rows (model.rs:1235-1264).
+ * The prefill passes follow aha_hip_generate_batch's rule (text rows, placeholders included, up to max_tokens_per_pass; a request is
+ * never split); one tower pass encodes every image and video of a prefill pass.  The model's own rope_delta is neither read nor left
+ * behind.  Errors, all before any device work (the cache stays cleared): AHA_ERR_UNSUPPORTED for an mm entry on a model that is not
+ * Qwen3-VL or has no vision weights, image_embeds, or audio input; AHA_ERR_SHAPE for a placeholder-count, grid or n_patches mismatch
+ * (the message names the sequence); everything else as aha_hip_generate_batch / _sampled.  Text requests give tokens and logits
+ * bit-identical to aha_hip_generate_batch / _sampled. */
+int aha_hip_generate_batch_mm(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs,
+                              const aha_mm_input* const* mm, const aha_sampling_params* params, size_t max_new,
+                              size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* step_logits_out);
+
 /* Host-only sampler: candle's LogitsProcessor built by get_logit_processor (sample.rs:7-38) plus use_repeat_penalty's slicing, over
  * the rand 0.9.2 StdRng of aha_hip_rng_*.  The deterministic half restates aha_amd/sampling.py (weights over the device candidates, the
  * top-p tie rule, the full-vector path); each sampled token consumes one next_u32, an ArgMax pick none.

@@ -251,6 +251,19 @@ pub mod sys {
             n_out: *mut usize,
             step_logits_out: *mut f32,
         ) -> i32;
+        pub fn aha_hip_generate_batch_mm(
+            m: *mut AhaModel,
+            ids: *const u32,
+            seq_lens: *const usize,
+            n_seqs: usize,
+            mm: *const *const AhaMmInput,
+            params: *const AhaSamplingParams,
+            max_new: usize,
+            max_tokens_per_pass: usize,
+            tokens_out: *mut u32,
+            n_out: *mut usize,
+            step_logits_out: *mut f32,
+        ) -> i32;
         pub fn aha_hip_sample_rows(
             logits: *const f32,
             ld: i64,
@@ -557,6 +570,94 @@ impl Model {
                 lens.as_ptr(),
                 lens.len(),
                 params.as_ptr(),
+                max_new,
+                max_tokens_per_pass,
+                toks.as_mut_ptr(),
+                n_out.as_mut_ptr(),
+                std::ptr::null_mut(),
+            )
+        })?;
+        Ok(n_out.iter().enumerate().map(|(j, &n)| toks[j * max_new..j * max_new + n].to_vec()).collect())
+    }
+
+    /// `generate_generic` for many Qwen3-VL requests with their images / videos, every request at once (aha_hip_generate_batch_mm):
+    /// `mm[j]` is request j's payload (`MmInput::None` for a text request; `Image` / `Vision` otherwise), `params` `None` = every
+    /// request greedy, else one sampler per request.  Per request, the tokens `generate_generic` yields for it alone with its data.
+    pub fn generate_batch_mm(
+        &mut self,
+        prompts: &[&[u32]],
+        mm: &[MmInput<'_>],
+        params: Option<&[sys::AhaSamplingParams]>,
+        max_new: usize,
+        max_tokens_per_pass: usize,
+    ) -> Result<Vec<Vec<u32>>, Error> {
+        if mm.len() != prompts.len() {
+            return Err(Error { code: -1, message: format!("{} multi-modal inputs for {} prompts", mm.len(), prompts.len()) });
+        }
+        if let Some(p) = params {
+            if p.len() != prompts.len() {
+                return Err(Error { code: -1, message: format!("{} sampling params for {} prompts", p.len(), prompts.len()) });
+            }
+        }
+        let mut cs: Vec<sys::AhaMmInput> = Vec::with_capacity(mm.len());
+        let mut present: Vec<bool> = Vec::with_capacity(mm.len());
+        for x in mm {
+            let mut c = sys::AhaMmInput::empty();
+            let some = match *x {
+                MmInput::None => false,
+                MmInput::Image { pixel_values, n_patches, grid_thw } => {
+                    c.pixel_values = pixel_values.as_ptr() as *const _;
+                    c.pixel_dtype = sys::AHA_F32;
+                    c.n_patches = n_patches as i64;
+                    c.image_grid_thw = grid_thw.as_ptr();
+                    c.n_images = (grid_thw.len() / 3) as i32;
+                    true
+                }
+                MmInput::Vision { image, video } => {
+                    c.pixel_dtype = sys::AHA_F32;
+                    if let Some((pv, n, grid)) = image {
+                        c.pixel_values = pv.as_ptr() as *const _;
+                        c.n_patches = n as i64;
+                        c.image_grid_thw = grid.as_ptr();
+                        c.n_images = (grid.len() / 3) as i32;
+                    }
+                    if let Some((pv, n, grid)) = video {
+                        c.pixel_values_video = pv.as_ptr() as *const _;
+                        c.n_patches_video = n as i64;
+                        c.video_grid_thw = grid.as_ptr();
+                        c.n_videos = (grid.len() / 3) as i32;
+                    }
+                    true
+                }
+                MmInput::AudioFeatures { features, n_frames } => {
+                    c.audio_features = features.as_ptr();
+                    c.n_frames = n_frames as i64;
+                    true
+                }
+                MmInput::AudioSamples { samples } => {
+                    c.audio_samples = samples.as_ptr();
+                    c.n_samples = samples.len() as i64;
+                    true
+                }
+            };
+            cs.push(c);
+            present.push(some);
+        }
+        // (cs is complete: the pointers below stay valid for the call)
+        let ptrs: Vec<*const sys::AhaMmInput> =
+            cs.iter().zip(present.iter()).map(|(c, &p)| if p { c as *const sys::AhaMmInput } else { std::ptr::null() }).collect();
+        let ids: Vec<u32> = prompts.iter().flat_map(|s| s.iter().copied()).collect();
+        let lens: Vec<usize> = prompts.iter().map(|s| s.len()).collect();
+        let mut toks = vec![0u32; prompts.len() * max_new.max(1)];
+        let mut n_out = vec![0usize; prompts.len()];
+        check(unsafe {
+            sys::aha_hip_generate_batch_mm(
+                self.model,
+                ids.as_ptr(),
+                lens.as_ptr(),
+                lens.len(),
+                ptrs.as_ptr(),
+                params.map_or(std::ptr::null(), |p| p.as_ptr()),
                 max_new,
                 max_tokens_per_pass,
                 toks.as_mut_ptr(),

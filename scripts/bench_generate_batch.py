@@ -11,7 +11,13 @@ also run through generate_batch_sampled (same timing rule; "sampled_vs_greedy" =
 is generate_generic_sampled (one host round trip per token) instead of decode_greedy.
     python scripts/bench_generate_batch.py [--only 0.6b,8b] [--batches 1,4,8,16,32,64] [--prompt 512] [--max-new 128] [--sampler]
     python scripts/bench_generate_batch.py --once 8b:16     # one generate_batch call and nothing else (rocprofv3 --kernel-trace --stats)
-    python scripts/bench_generate_batch.py --once 8b:16 --sampler   # the same with generate_batch_sampled"""
+    python scripts/bench_generate_batch.py --once 8b:16 --sampler   # the same with generate_batch_sampled
+With --vl: Qwen3-VL-8B with its vision tower (configs.qwen3vl_8b, seeded weights), B requests of one --image W x W image and --prompt
+text tokens each, no stop tokens, through generate_batch_mm.  Per B: prefill ms (one call with max_new 1), ViT ms (vision_encode of
+the B images in one call, timed apart: the tower's share of that prefill), decode step ms by the rule above, aggregate tok/s, and the
+speed-up over a serial leg of forward_initial(mm) + decode_greedy on --serial requests (aggregate tok/s over whole requests).
+    python scripts/bench_generate_batch.py --vl [--batches 1,4,8,16] [--image 448] [--prompt 512] [--max-new 64]
+    python scripts/bench_generate_batch.py --vl --once vl8b:16   # one generate_batch_mm call (rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
 import os
@@ -97,6 +103,72 @@ def serial_sampled(m, ps, max_new):
     return len(ps) * (max_new - 1) / dec, dec / (len(ps) * (max_new - 1))
 
 
+def vl_requests(cfg, B, px, L, seed=0):
+    import torch
+    from aha_amd.vision_host import synthetic_image_request
+    g = torch.Generator().manual_seed(seed)
+    return [synthetic_image_request(cfg, px, L, g) for _ in range(B)]
+
+
+def bench_vl(a):
+    """generate_batch_mm on Qwen3-VL-8B with one image per request against serial forward_initial(mm) + decode_greedy."""
+    import torch
+    from aha_amd.configs import qwen3vl_8b
+    from aha_amd.model import HipInferenceModel, MultiModalData
+    from aha_amd.weights import qwen3vl_weights
+    cfg = qwen3vl_8b()
+    cfg.text.eos_token_ids = []
+    w = qwen3vl_weights(cfg, seed=0, device="cuda")
+    m = HipInferenceModel(cfg, w)
+    del w
+    torch.cuda.empty_cache()
+    batches = [int(b) for b in a.batches.split(",")]
+    if a.once:
+        B = int(a.once.split(":")[1])
+        reqs = vl_requests(cfg, B, a.image, a.prompt)
+        m.generate_batch_mm([r[0] for r in reqs], [r[1] for r in reqs], a.max_new)
+        torch.cuda.synchronize()
+        m.close()
+        return
+    reqs_all = vl_requests(cfg, max(batches + [a.serial]), a.image, a.prompt)
+    dec = 0.0
+    for ids, data in reqs_all[:a.serial]:
+        m.clear_cache()
+        _, tok = m.forward_initial(ids, 0, data, want_logits=False)
+        torch.cuda.synchronize()
+        dt, _ = timed(lambda: m.decode_greedy(tok, len(ids), a.max_new - 1))
+        dec += dt
+        m.clear_cache()
+    def serial_request(ids, data):
+        _, tok = m.forward_initial(ids, 0, data, want_logits=False)
+        return m.decode_greedy(tok, len(ids), a.max_new - 1)
+
+    t_ser = 0.0
+    for ids, data in reqs_all[:a.serial]:   # the whole serial request: prefill + decode
+        t, _ = timed(lambda: serial_request(ids, data))
+        m.clear_cache()
+        t_ser += t
+    serial_tps = a.serial * a.max_new / t_ser
+    print(json.dumps({"model": "vl8b", "image": a.image, "prompt": a.prompt, "serial_decode_tok_s": round(a.serial * (a.max_new - 1) / dec, 1),
+                      "serial_aggregate_tok_s": round(serial_tps, 1)}), flush=True)
+    m.generate_batch_mm([reqs_all[0][0]], [reqs_all[0][1]], 2)   # warm-up
+    for B in batches:
+        reqs = reqs_all[:B]
+        ps, ds = [r[0] for r in reqs], [r[1] for r in reqs]
+        pv = torch.cat([d.pixel_values for d in ds], 0)
+        grid = np.concatenate([d.image_grid_thw for d in ds], 0)
+        torch.cuda.synchronize()
+        tv, _ = timed(lambda: (m.vision_encode(MultiModalData(pv, grid)), torch.cuda.synchronize()))
+        t1, _ = timed(lambda: m.generate_batch_mm(ps, ds, 1))
+        tn, out = timed(lambda: m.generate_batch_mm(ps, ds, a.max_new))
+        assert all(len(o) == a.max_new for o in out)
+        step = (tn - t1) / (a.max_new - 1)
+        print(json.dumps({"model": "vl8b", "B": B, "image": a.image, "prompt": a.prompt, "max_new": a.max_new, "prefill_ms": round(t1 * 1e3, 2),
+                          "vit_ms": round(tv * 1e3, 2), "step_ms": round(step * 1e3, 3), "total_s": round(tn, 3),
+                          "aggregate_tok_s": round(B * a.max_new / tn, 1), "vs_serial": round(B * a.max_new / tn / serial_tps, 2)}), flush=True)
+    m.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="0.6b,8b")
@@ -107,10 +179,15 @@ def main():
     ap.add_argument("--once", default="")
     ap.add_argument("--no-kernel", action="store_true")
     ap.add_argument("--sampler", action="store_true", help="also the batched sampled path; the serial leg samples too")
+    ap.add_argument("--vl", action="store_true", help="Qwen3-VL-8B requests with one image each through generate_batch_mm")
+    ap.add_argument("--image", type=int, default=448)
     a = ap.parse_args()
     import torch
     from aha_amd import build
     build.build()
+    if a.vl:
+        bench_vl(a)
+        return
     if a.once:
         name, B = a.once.split(":")
         cfg, m = model_for(name)
