@@ -133,6 +133,7 @@ SIGNATURES = {
                                        C.c_int32, C.c_int32, C.c_float, _P]),
     "aha_hip_argmax": (C.c_int, [_P, C.c_int64, _P, _P]),
     "aha_hip_logmel": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "aha_hip_logmel_batch": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
     "aha_hip_debug_poison_lds": (C.c_int, [C.c_uint32, _P]),
     "aha_hip_debug_gemm_plan": (C.c_int, [C.c_int32, C.c_int32]),
     "aha_hip_debug_attn_variant": (C.c_int, [C.c_int32]),

@@ -26,13 +26,16 @@ struct AudioModel {
   void *lnp_w = nullptr, *lnp_b = nullptr, *p1w = nullptr, *p1b = nullptr, *p2w = nullptr, *p2b = nullptr;
   float *d_window = nullptr, *d_twid = nullptr, *d_melfb = nullptr;
   float scale = 0.f;
-  // scratch
-  size_t cap_frames = 0;
+  // scratch (audio_ensure_scratch): frames, samples, 100-frame chunks, KV pages and clips of the largest tower pass so far
+  size_t cap_frames = 0, cap_samples = 0, cap_chunks = 0, cap_pages = 0, cap_clips = 0;
   std::vector<void*> owned;
   float *d_samples = nullptr, *d_feat = nullptr, *d_fmax = nullptr;
   void *col = nullptr, *act_a = nullptr, *act_b = nullptr, *tok = nullptr, *x = nullptr, *h = nullptr, *qkv = nullptr, *attn = nullptr,
        *mlp = nullptr, *embeds = nullptr;
   int32_t* d_rows = nullptr;
+  int64_t* d_clips = nullptr;                                            // log-mel clip table
+  int32_t *d_chunks = nullptr, *d_seg = nullptr, *d_slot = nullptr;      // conv1 chunk table, attention {row0, len, page0} + items, KV slots
+  uint32_t* d_src = nullptr;                                             // compaction: packed token row -> conv_out row
   void* page_store = nullptr;
   uint64_t* d_page_ptrs = nullptr;
   uint64_t page_bytes = 0;
@@ -233,7 +236,7 @@ int audio_create(aha_model* m, const aha_tensor_view* w, size_t nw) {
 static void audio_free_scratch(AudioModel* a) {
   for (void* p : a->owned) hipFree(p);
   a->owned.clear();
-  a->cap_frames = 0;
+  a->cap_frames = a->cap_samples = a->cap_chunks = a->cap_pages = a->cap_clips = 0;
 }
 void audio_destroy(aha_model* m) {
   if (!m->audio) return;
@@ -242,13 +245,20 @@ void audio_destroy(aha_model* m) {
   m->audio = nullptr;
 }
 
-static int audio_ensure_scratch(aha_model* m, size_t frames, size_t samples) {
+// Scratch of one tower pass: `frames` feature columns, `samples` raw samples, `chunks` 100-frame windows (13 token rows each), `pages` KV
+// pages (every clip starts on a page of its own: sum of ceil(n_tok_j / 64)), `clips` clips.  Grows only; frames round up to 1000.
+static int audio_ensure_scratch(aha_model* m, size_t frames, size_t samples, size_t chunks, size_t pages, size_t clips) {
   AudioModel* a = m->audio;
-  if (frames <= a->cap_frames) return AHA_OK;
+  if (frames <= a->cap_frames && samples <= a->cap_samples && chunks <= a->cap_chunks && pages <= a->cap_pages && clips <= a->cap_clips)
+    return AHA_OK;
   AHA_HIP_CHECK(hipStreamSynchronize(m->stream));
+  const size_t cap = std::max((std::max(frames, a->cap_frames) + 999) / 1000 * 1000, (size_t)1000);
+  const size_t C = std::max(std::max(chunks, a->cap_chunks), (cap + 99) / 100), win = 2 * (size_t)a->nwin;
+  const size_t scap = std::max(std::max(samples, a->cap_samples), cap * 160);
+  const size_t ntok = C * 13;
+  const size_t pcap = std::max(std::max(pages, a->cap_pages), ntok / KV_PAGE_TOKENS + 2);
+  const size_t ccap = std::max(std::max(clips, a->cap_clips), (size_t)16);
   audio_free_scratch(a);
-  const size_t cap = (frames + 999) / 1000 * 1000;
-  const size_t C = (cap + 99) / 100, win = 2 * (size_t)a->nwin;
   auto al = [&](size_t bytes, void** out, bool zero = false) -> int {
     void* p = nullptr;
     hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
@@ -262,9 +272,8 @@ static int audio_ensure_scratch(aha_model* m, size_t frames, size_t samples) {
     return AHA_OK;
   };
   int rc;
-  const size_t H = a->H, r1 = C * 64 * ((win + 1) / 2), r2 = C * 32 * 25, r3 = C * 16 * 13, ntok = C * 13;
-  (void)samples;
-  if ((rc = al((cap * 160 + 1024) * 4, (void**)&a->d_samples))) return rc;
+  const size_t H = a->H, r1 = C * 64 * ((win + 1) / 2), r2 = C * 32 * 25, r3 = C * 16 * 13;
+  if ((rc = al((scap + 1024) * 4, (void**)&a->d_samples))) return rc;
   if ((rc = al((size_t)a->mels * cap * 4, (void**)&a->d_feat))) return rc;
   if ((rc = al(cap * 4, (void**)&a->d_fmax))) return rc;
   if ((rc = al(std::max(r1 * 16, std::max(r2, r3) * 9 * H) * 2, &a->col))) return rc;
@@ -278,13 +287,17 @@ static int audio_ensure_scratch(aha_model* m, size_t frames, size_t samples) {
   if ((rc = al(ntok * a->ffn * 2, &a->mlp))) return rc;
   if ((rc = al(ntok * a->out * 2, &a->embeds))) return rc;
   if ((rc = al(ntok * 4, (void**)&a->d_rows))) return rc;
-  const size_t pcap = ntok / KV_PAGE_TOKENS + 2;
+  if ((rc = al(ccap * LOGMEL_CLIP_WORDS * 8, (void**)&a->d_clips))) return rc;
+  if ((rc = al(C * 3 * 4, (void**)&a->d_chunks))) return rc;
+  if ((rc = al((3 * ccap + 2 * pcap) * 4, (void**)&a->d_seg))) return rc;
+  if ((rc = al(ntok * 4, (void**)&a->d_slot))) return rc;
+  if ((rc = al(ntok * 4, (void**)&a->d_src))) return rc;
   if ((rc = al(pcap * a->page_bytes, &a->page_store, true))) return rc;
   if ((rc = al(pcap * 8, (void**)&a->d_page_ptrs))) return rc;
   std::vector<uint64_t> ptrs(pcap);
   for (size_t i = 0; i < pcap; ++i) ptrs[i] = (uint64_t)(uintptr_t)a->page_store + i * a->page_bytes;
   AHA_HIP_CHECK(hipMemcpy(a->d_page_ptrs, ptrs.data(), pcap * 8, hipMemcpyHostToDevice));
-  a->cap_frames = cap;
+  a->cap_frames = cap, a->cap_samples = scap, a->cap_chunks = C, a->cap_pages = pcap, a->cap_clips = ccap;
   return AHA_OK;
 }
 
@@ -307,60 +320,159 @@ static int get_out_len(int n) {  // get_feat_extract_output_lengths, processor.r
   }
   return (n / 100) * 13;
 }
+int64_t audio_tokens_of_frames(int64_t F) {
+  const int win = 100;
+  int64_t n_tok = 0;
+  for (int64_t i = 0; i * win < F; ++i) n_tok += get_out_len((int)std::min<int64_t>(win, F - i * win));
+  return n_tok;
+}
 
-int audio_logmel_device(aha_model* m, const float* d_samples, int64_t n_samples, float* d_out, float* d_fmax, int F) {
-  AudioModel* a = m->audio;
-  ProfScope ps(m, "logmel", (double)n_samples * 4 + (double)128 * F * 4, 2.0 * F * 201 * 400 * 2);
-  launch_logmel(d_samples, n_samples, a->d_window, a->d_twid, a->d_melfb, d_out, d_fmax, F, m->stream);
+// One clip of a tower pass (host view)
+struct AudClip {
+  const AudRequest* req;
+  bool samples;       // raw samples (log-mel on the device) rather than features
+  int64_t L, F;       // samples (0 for features), frames
+  int C, n_tok;       // 100-frame windows, audio tokens
+};
+
+// every check of a request, before any device work: the clip's frames / tokens and its placeholder count
+static int audio_check_request(aha_model* m, const AudRequest& r, AudClip* out) {
+  const aha_model_desc& c = m->desc;
+  const std::string who = r.seq >= 0 ? "sequence " + std::to_string(r.seq) + ": " : "";
+  const aha_mm_input* mm = r.mm;
+  AudClip k{&r, false, 0, 0, 0, 0};
+  if (mm->audio_samples && mm->n_samples > 0) {   // samples win over features (as forward_initial has always read them)
+    if (mm->n_samples < 401) {
+      set_error(who + "audio too short for the reflect padding (need > 400 samples)");
+      return AHA_ERR_INVALID;
+    }
+    k.samples = true;
+    k.L = mm->n_samples;
+    k.F = mm->n_samples / 160;  // (L + 400 - 400) / 160 + 1 frames, last one dropped
+  } else if (mm->audio_features && mm->n_frames > 0) {
+    k.F = mm->n_frames;
+  } else {
+    set_error(who + "forward_initial: audio input without features or samples");
+    return AHA_ERR_INVALID;
+  }
+  if (k.F > ((int64_t)1 << 26)) {
+    set_error(who + "audio input too long");
+    return AHA_ERR_INVALID;
+  }
+  k.C = (int)((k.F + 2 * m->audio->nwin - 1) / (2 * m->audio->nwin));
+  k.n_tok = (int)audio_tokens_of_frames(k.F);
+  if (r.ids) {
+    int64_t n_pad = 0;
+    for (size_t i = 0; i < r.n; ++i) n_pad += r.ids[i] == (uint32_t)c.audio_token_id;
+    if (n_pad != k.n_tok) {  // qwen3_asr/model.rs:349-355
+      set_error(who + "n_audio_tokens num: " + std::to_string(n_pad) + " not equal to audio_feature len: " + std::to_string(k.n_tok));
+      return AHA_ERR_SHAPE;
+    }
+  }
+  *out = k;
   return AHA_OK;
 }
 
-int audio_forward_and_scatter(aha_model* m, const uint32_t* ids, size_t n, const aha_mm_input* mm, void* x_text) {
-  AudioModel* a = m->audio;
-  const aha_model_desc& c = m->desc;
-  if (!a) {
-    set_error("this model has no audio tower");
+int audio_check_requests(aha_model* m, const AudRequest* reqs, size_t n_reqs) {
+  if (!m->audio) {
+    set_error(std::string(n_reqs && reqs[0].seq >= 0 ? "sequence " + std::to_string(reqs[0].seq) + ": " : "") +
+              "audio input given but this model has no audio tower");
     return AHA_ERR_UNSUPPORTED;
   }
+  AudClip k;
+  for (size_t i = 0; i < n_reqs; ++i) {
+    const int rc = audio_check_request(m, reqs[i], &k);
+    if (rc) return rc;
+  }
+  return AHA_OK;
+}
+
+// One tower sub-pass over clips k[0 .. n).  Layout (round 7):
+//   features  (128, Ftot) f32, clip j in columns fo_j .. fo_j + F_j - 1: the sample clips' log-mel in ONE launch pair, the feature clips
+//             copied into their columns;
+//   conv      every clip's C_j windows in clip order (sum C_j chunks): conv1 .. conv3, the token gather, conv_out and the 13-periodic
+//             position add run once, row order unchanged;
+//   encoder   clip j keeps the first n_tok_j of its C_j * 13 rows (narrow(0, 0, feature_len_after_cnn) per clip), packed by a row gather;
+//             row-wise ops once over the packed rows, K / V to pages with every clip starting on a page of its own, and the attention
+//             block-diagonal: ONE non-causal seg_tab launch per layer ({row0, len, page0} per clip, 64-row items longest clip first);
+//   projector over the packed rows, then clip j's rows scattered to its request's <|audio_pad|> rows.
+// With one clip every step computes the bits of the one-clip code before it: the same features, the same chunks, the same GEMM shapes (so
+// the same plans), no gather (the rows are already packed), identity KV slots, and a one-segment seg_tab launch = the plain launch.
+static int audio_tower_pass(aha_model* m, const AudClip* k, int n, void* x_text) {
+  AudioModel* a = m->audio;
+  const aha_model_desc& c = m->desc;
   hipStream_t st = m->stream;
-  int64_t F;
-  int rc;
-  if (mm->audio_samples && mm->n_samples > 0) {
-    if (mm->n_samples < 401) {
-      set_error("audio too short for the reflect padding (need > 400 samples)");
-      return AHA_ERR_INVALID;
-    }
-    F = mm->n_samples / 160;  // (L + 400 - 400) / 160 + 1 frames, last one dropped
-    if ((rc = audio_ensure_scratch(m, (size_t)F, (size_t)mm->n_samples))) return rc;
-    AHA_HIP_CHECK(hipMemcpyAsync(a->d_samples, mm->audio_samples, (size_t)mm->n_samples * 4, hipMemcpyDefault, st));
-    if ((rc = audio_logmel_device(m, a->d_samples, mm->n_samples, a->d_feat, a->d_fmax, (int)F))) return rc;
-  } else if (mm->audio_features && mm->n_frames > 0) {
-    F = mm->n_frames;
-    if ((rc = audio_ensure_scratch(m, (size_t)F, 0))) return rc;
-    AHA_HIP_CHECK(hipMemcpyAsync(a->d_feat, mm->audio_features, (size_t)a->mels * F * 4, hipMemcpyDefault, st));
-  } else {
-    set_error("forward_initial: audio input without features or samples");
-    return AHA_ERR_INVALID;
-  }
   const int win = 2 * a->nwin;  // 100 frames per chunk
-  const int C = (int)((F + win - 1) / win);
-  int n_tok = 0;
-  for (int i = 0; i < C; ++i) n_tok += get_out_len((int)std::min<int64_t>(win, F - (int64_t)i * win));
-  std::vector<int32_t> rows;
-  for (size_t i = 0; i < n; ++i)
-    if (ids[i] == (uint32_t)c.audio_token_id) rows.push_back((int32_t)i);
-  if ((int)rows.size() != n_tok) {  // qwen3_asr/model.rs:349-355
-    set_error("n_audio_tokens num: " + std::to_string(rows.size()) + " not equal to audio_feature len: " + std::to_string(n_tok));
-    return AHA_ERR_SHAPE;
+  // ---- host tables --------------------------------------------------------------------------------------------------
+  std::vector<int64_t> fo(n), clip_tab;
+  std::vector<int32_t> chunk_tab, rows, slot, seg, src;
+  int64_t Ftot = 0, Ltot = 0, groups = 0;
+  int Ctot = 0, Ntok = 0, pages = 0, n_mel = 0;
+  for (int j = 0; j < n; ++j) {
+    fo[j] = Ftot;
+    if (k[j].samples) {
+      clip_tab.insert(clip_tab.end(), {Ltot, k[j].L, Ftot, k[j].F, groups});
+      Ltot += k[j].L;
+      groups += (k[j].F + 3) / 4;
+      ++n_mel;
+    }
+    for (int i = 0; i < k[j].C; ++i) chunk_tab.insert(chunk_tab.end(), {(int32_t)Ftot, (int32_t)k[j].F, i});
+    seg.insert(seg.end(), {Ntok, k[j].n_tok, pages});
+    for (int i = 0; i < k[j].n_tok; ++i) {
+      src.push_back(Ctot * 13 + i);
+      slot.push_back(pages * KV_PAGE_TOKENS + i);
+    }
+    const AudRequest& r = *k[j].req;
+    if (r.ids)
+      for (size_t i = 0; i < r.n; ++i)
+        if (r.ids[i] == (uint32_t)c.audio_token_id) rows.push_back((int32_t)(r.row0 + (int64_t)i));
+    Ftot += k[j].F;
+    Ctot += k[j].C;
+    Ntok += k[j].n_tok;
+    pages += (k[j].n_tok + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
   }
-  AHA_HIP_CHECK(hipMemcpyAsync(a->d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, st));
-  AHA_HIP_CHECK(hipStreamSynchronize(st));
+  // attention items: (clip, 64-row q block); non-causal, so a block's cost is its clip's length: longest first
+  std::vector<std::pair<int, int>> items;
+  for (int j = 0; j < n; ++j)
+    for (int b = 0; b * 64 < k[j].n_tok; ++b) items.emplace_back(j, b);
+  std::stable_sort(items.begin(), items.end(), [&](const auto& p, const auto& q) { return k[p.first].n_tok > k[q.first].n_tok; });
+  for (const auto& it : items) seg.push_back(it.first), seg.push_back(it.second);
+  const bool packed = n > 1;   // one clip: its rows are already packed, its KV slots the identity
+  int rc;
+  if ((rc = audio_ensure_scratch(m, (size_t)Ftot, (size_t)Ltot, (size_t)Ctot, (size_t)pages, (size_t)n))) return rc;
+  // ---- uploads ------------------------------------------------------------------------------------------------------
+  {
+    int64_t so = 0;
+    for (int j = 0; j < n; ++j) {
+      const aha_mm_input* mm = k[j].req->mm;
+      if (k[j].samples) {
+        AHA_HIP_CHECK(hipMemcpyAsync(a->d_samples + so, mm->audio_samples, (size_t)k[j].L * 4, hipMemcpyDefault, st));
+        so += k[j].L;
+      } else {   // (128, F_j) -> columns fo_j .. of the (128, Ftot) buffer
+        AHA_HIP_CHECK(hipMemcpy2DAsync(a->d_feat + fo[j], (size_t)Ftot * 4, mm->audio_features, (size_t)k[j].F * 4, (size_t)k[j].F * 4,
+                                       (size_t)a->mels, hipMemcpyDefault, st));
+      }
+    }
+  }
+  if (n_mel) AHA_HIP_CHECK(hipMemcpyAsync(a->d_clips, clip_tab.data(), clip_tab.size() * 8, hipMemcpyHostToDevice, st));
+  AHA_HIP_CHECK(hipMemcpyAsync(a->d_chunks, chunk_tab.data(), chunk_tab.size() * 4, hipMemcpyHostToDevice, st));
+  AHA_HIP_CHECK(hipMemcpyAsync(a->d_seg, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, st));
+  if (packed) {
+    AHA_HIP_CHECK(hipMemcpyAsync(a->d_slot, slot.data(), slot.size() * 4, hipMemcpyHostToDevice, st));
+    AHA_HIP_CHECK(hipMemcpyAsync(a->d_src, src.data(), src.size() * 4, hipMemcpyHostToDevice, st));
+  }
+  if (!rows.empty()) AHA_HIP_CHECK(hipMemcpyAsync(a->d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, st));
+  AHA_HIP_CHECK(hipStreamSynchronize(st));   // host vectors are pageable
+  if (n_mel) {
+    ProfScope ps(m, "logmel", (double)Ltot * 4 + (double)128 * Ftot * 4, 2.0 * Ftot * 201 * 400 * 2);
+    launch_logmel(a->d_samples, a->d_clips, n_mel, groups, Ftot, a->d_window, a->d_twid, a->d_melfb, a->d_feat, a->d_fmax, st);
+  }
 
   // conv stack: (C,1,128,100) -> (C,H,64,50) -> (C,H,32,25) -> (C,H,16,13), each conv + bias + tanh-GELU (model.rs:196-204)
-  const int H = a->H;
+  const int H = a->H, C = Ctot;
   {
     ProfScope ps(m, "elem", (double)C * 64 * 50 * 32, 0);
-    launch_audio_im2col1(a->d_feat, a->col, (int)F, C, a->mels, win, st);
+    launch_audio_im2col1(a->d_feat, a->d_chunks, a->col, Ftot, C, a->mels, win, st);
   }
   agemm(m, a->col, a->c1w, a->act_a, C * 64 * 50, H, 16, a->c1b, nullptr, ACT_GELU_TANH);
   {
@@ -377,21 +489,29 @@ int audio_forward_and_scatter(aha_model* m, const uint32_t* ids, size_t n, const
     ProfScope ps(m, "elem", (double)C * 13 * H * a->fq * 4, 0);
     launch_audio_tokens_gather(a->act_a, a->tok, C, a->fq, 13, H, st);
   }
-  agemm(m, a->tok, a->conv_out, a->x, C * 13, a->D, H * a->fq, nullptr, nullptr, ACT_NONE);
+  const int D = a->D;
+  void* xc = packed ? a->h : a->x;   // the conv_out rows: packed into a->x below when there is more than one clip
+  agemm(m, a->tok, a->conv_out, xc, C * 13, D, H * a->fq, nullptr, nullptr, ACT_NONE);
   {
-    ProfScope ps(m, "elem", (double)C * 13 * a->D * 4, 0);
-    launch_sinus_pe_add(a->x, (int64_t)C * 13, a->D, 13, st);
+    ProfScope ps(m, "elem", (double)C * 13 * D * 4, 0);
+    launch_sinus_pe_add(xc, (int64_t)C * 13, D, 13, st);
   }
-  // the first n_tok rows are the audio tokens (narrow(0, 0, feature_len_after_cnn), model.rs:213-215)
+  // clip j's first n_tok_j rows are its audio tokens (narrow(0, 0, feature_len_after_cnn), model.rs:213-215)
+  const int n_tok = Ntok;
+  if (packed) {
+    ProfScope ps(m, "elem", (double)n_tok * D * 4, 0);
+    launch_embed_gather(a->h, a->d_src, a->x, n_tok, D, st);
+  }
   KvLayer kv{};
   kv.page_ptrs = a->d_page_ptrs;
   kv.layer_off = 0;
   kv.kvh = a->nh;
   kv.d = a->hd;
-  const int D = a->D;
   // round 6: the LayerNorm behind fc2 + residual -- norm1 of the next layer, ln_post after the last -- rides on the fc2 call (its plan at the
   // real widths is K slices + a reduce pass: one launch less per layer); AHA_AUD_FUSE_LN=0: every LayerNorm its own launch (same bits)
   static const bool fuse_ln = [] { const char* e = getenv("AHA_AUD_FUSE_LN"); return e ? atoi(e) != 0 : true; }();
+  double attn_flops = 0;
+  for (int j = 0; j < n; ++j) attn_flops += 4.0 * k[j].n_tok * k[j].n_tok * D;
   bool h_ready = false;   // a->h already holds the LayerNorm of a->x
   for (int li = 0; li < a->layers; ++li) {
     const AudLayerW& L = a->L[li];
@@ -402,13 +522,14 @@ int audio_forward_and_scatter(aha_model* m, const uint32_t* ids, size_t n, const
     agemm(m, a->h, L.qkv_w, a->qkv, n_tok, 3 * D, D, L.qkv_b, nullptr, ACT_NONE);
     {
       ProfScope ps(m, "elem", (double)n_tok * D * 8, 0);
-      launch_kv_pack_generic(a->qkv, 3 * D, D, 2 * D, kv, n_tok, a->nh, a->hd, st);
+      launch_kv_pack_generic(a->qkv, 3 * D, D, 2 * D, kv, n_tok, a->nh, a->hd, st, packed ? a->d_slot : nullptr);
     }
-    {  // global (unmasked, unwindowed) attention over all audio tokens (model.rs:218-220)
+    {  // global (unmasked, unwindowed) attention over each clip's own tokens (model.rs:218-220): block-diagonal, one launch
       AttnPrefillArgs q{};
       q.q = a->qkv; q.q_ld = 3 * D; q.kv = kv; q.o = a->attn; q.S = n_tok; q.nh = a->nh; q.kvh = a->nh; q.d = a->hd;
       q.kv_offset = 0; q.kv_total = n_tok; q.causal = 0; q.scale = a->scale;
-      ProfScope ps(m, "attn_audio", (double)n_tok * D * 8, 4.0 * n_tok * n_tok * D);
+      q.seg_tab = a->d_seg; q.seg_items = a->d_seg + 3 * (size_t)n; q.n_items = (int)items.size();
+      ProfScope ps(m, "attn_audio", (double)n_tok * D * 8, attn_flops);
       launch_attn_prefill(q, st);
     }
     agemm(m, a->attn, L.out_w, a->x, n_tok, D, D, L.out_b, a->x, ACT_NONE);
@@ -433,11 +554,28 @@ int audio_forward_and_scatter(aha_model* m, const uint32_t* ids, size_t n, const
   agemm(m, a->h, a->p1w, a->mlp, n_tok, D, D, a->p1b, nullptr, ACT_GELU_ERF);
   agemm(m, a->mlp, a->p2w, a->embeds, n_tok, a->out, D, a->p2b, nullptr, ACT_NONE);
   a->n_tok = n_tok;
-  {
+  if (!rows.empty()) {
     ProfScope ps(m, "elem", (double)n_tok * a->out * 4, 0);
     launch_scatter_rows(x_text, a->embeds, a->d_rows, n_tok, a->out, 0, st);
   }
   AHA_HIP_CHECK(hipGetLastError());
+  return AHA_OK;
+}
+
+int audio_forward_requests(aha_model* m, const AudRequest* reqs, size_t n_reqs, void* x_text) {
+  int rc;
+  if ((rc = audio_check_requests(m, reqs, n_reqs))) return rc;
+  std::vector<AudClip> clips(n_reqs);
+  for (size_t i = 0; i < n_reqs; ++i) audio_check_request(m, reqs[i], &clips[i]);
+  // sub-passes of at most AUD_PASS_FRAMES frames (a clip is never split; one longer clip is a sub-pass of its own)
+  size_t i = 0;
+  while (i < n_reqs) {
+    size_t e = i + 1;
+    int64_t frames = clips[i].F;
+    while (e < n_reqs && frames + clips[e].F <= AUD_PASS_FRAMES) frames += clips[e++].F;
+    if ((rc = audio_tower_pass(m, clips.data() + i, (int)(e - i), x_text))) return rc;
+    i = e;
+  }
   return AHA_OK;
 }
 
@@ -454,57 +592,56 @@ int audio_debug_embeds(aha_model* m, float* out, size_t n) {
   return AHA_OK;
 }
 
-// op-level frontend (aha_hip_logmel): tables built on the fly
-int logmel_standalone(const float* d_samples, int64_t n_samples, float* d_out, hipStream_t st) {
+// op-level frontend (aha_hip_logmel, aha_hip_logmel_batch): tables built on the fly; clip j's n_samples[j] samples follow clip j - 1's in
+// d_samples, its n_samples[j] / 160 frames follow clip j - 1's in the (128, sum F_j) output
+int logmel_standalone(const float* d_samples, const int64_t* n_samples, size_t n_clips, float* d_out, hipStream_t st) {
+  std::vector<int64_t> tab;
+  int64_t so = 0, Ftot = 0, groups = 0;
+  for (size_t j = 0; j < n_clips; ++j) {
+    const int64_t F = n_samples[j] / 160;
+    tab.insert(tab.end(), {so, n_samples[j], Ftot, F, groups});
+    so += n_samples[j], Ftot += F, groups += (F + 3) / 4;
+  }
   aha_model fake;
   aha_ctx ctx;
   fake.ctx = &ctx;
   fake.stream = st;
-  fake.desc = aha_model_desc{};
-  fake.desc.aud_d_model = 128; fake.desc.aud_attention_heads = 2; fake.desc.aud_num_mel_bins = 128;
-  fake.desc.aud_downsample_hidden_size = 8;
-  // only the tables are needed: build them through a minimal AudioModel
-  AudioModel* a = new AudioModel();
-  fake.audio = a;
   int rc = AHA_OK;
-  {
-    std::vector<float> win(400), tw(800), fb((size_t)201 * 128);
-    for (int j = 0; j < 400; ++j) {
-      const double i = (double)(1 - 400 + 2 * j);
-      win[j] = (float)(0.5 + 0.5 * cos(M_PI * i / 399.0));
-      tw[2 * j] = (float)cos(2.0 * M_PI * j / 400.0);
-      tw[2 * j + 1] = (float)(-sin(2.0 * M_PI * j / 400.0));
+  std::vector<float> win(400), tw(800), fb((size_t)201 * 128);
+  for (int j = 0; j < 400; ++j) {
+    const double i = (double)(1 - 400 + 2 * j);
+    win[j] = (float)(0.5 + 0.5 * cos(M_PI * i / 399.0));
+    tw[2 * j] = (float)cos(2.0 * M_PI * j / 400.0);
+    tw[2 * j + 1] = (float)(-sin(2.0 * M_PI * j / 400.0));
+  }
+  const std::vector<float> melpts = linspace_f(hz2mel(0.0f), hz2mel(8000.0f), 130);
+  std::vector<float> filt(130);
+  for (int i = 0; i < 130; ++i) filt[i] = mel2hz(melpts[i]);
+  const std::vector<float> fft = linspace_f(0.0f, 8000.0f, 201);
+  for (int k = 0; k < 201; ++k)
+    for (int j = 0; j < 128; ++j) {
+      const float down = -1.0f * (filt[j] - fft[k]) / (filt[j + 1] - filt[j]);
+      const float up = (filt[j + 2] - fft[k]) / (filt[j + 2] - filt[j + 1]);
+      fb[(size_t)k * 128 + j] = std::max(std::min(down, up), 0.0f) * (2.0f / (filt[j + 2] - filt[j]));
     }
-    const std::vector<float> melpts = linspace_f(hz2mel(0.0f), hz2mel(8000.0f), 130);
-    std::vector<float> filt(130);
-    for (int i = 0; i < 130; ++i) filt[i] = mel2hz(melpts[i]);
-    const std::vector<float> fft = linspace_f(0.0f, 8000.0f, 201);
-    for (int k = 0; k < 201; ++k)
-      for (int j = 0; j < 128; ++j) {
-        const float down = -1.0f * (filt[j] - fft[k]) / (filt[j + 1] - filt[j]);
-        const float up = (filt[j + 2] - fft[k]) / (filt[j + 2] - filt[j + 1]);
-        fb[(size_t)k * 128 + j] = std::max(std::min(down, up), 0.0f) * (2.0f / (filt[j + 2] - filt[j]));
-      }
-    void *pw = nullptr, *pt = nullptr, *pf = nullptr, *pm = nullptr;
-    const int F = (int)(n_samples / 160);
-    if ((rc = dev_alloc(&fake, win.size() * 4, &pw)) || (rc = dev_alloc(&fake, tw.size() * 4, &pt)) ||
-        (rc = dev_alloc(&fake, fb.size() * 4, &pf)) || (rc = dev_alloc(&fake, (size_t)F * 4 + 16, &pm))) {
-      for (void* p : fake.owned) hipFree(p);
-      delete a;
-      return rc;
-    }
-    hipMemcpy(pw, win.data(), win.size() * 4, hipMemcpyHostToDevice);
-    hipMemcpy(pt, tw.data(), tw.size() * 4, hipMemcpyHostToDevice);
-    hipMemcpy(pf, fb.data(), fb.size() * 4, hipMemcpyHostToDevice);
-    launch_logmel(d_samples, n_samples, (float*)pw, (float*)pt, (float*)pf, d_out, (float*)pm, F, st);
-    hipError_t e = hipGetLastError();
-    hipStreamSynchronize(st);
+  void *pw = nullptr, *pt = nullptr, *pf = nullptr, *pm = nullptr, *pc = nullptr;
+  if ((rc = dev_alloc(&fake, win.size() * 4, &pw)) || (rc = dev_alloc(&fake, tw.size() * 4, &pt)) ||
+      (rc = dev_alloc(&fake, fb.size() * 4, &pf)) || (rc = dev_alloc(&fake, (size_t)Ftot * 4 + 16, &pm)) ||
+      (rc = dev_alloc(&fake, tab.size() * 8, &pc))) {
     for (void* p : fake.owned) hipFree(p);
-    delete a;
-    if (e != hipSuccess) {
-      set_error(std::string("logmel launch failed: ") + hipGetErrorString(e));
-      return AHA_ERR_HIP;
-    }
+    return rc;
+  }
+  hipMemcpy(pw, win.data(), win.size() * 4, hipMemcpyHostToDevice);
+  hipMemcpy(pt, tw.data(), tw.size() * 4, hipMemcpyHostToDevice);
+  hipMemcpy(pf, fb.data(), fb.size() * 4, hipMemcpyHostToDevice);
+  hipMemcpy(pc, tab.data(), tab.size() * 8, hipMemcpyHostToDevice);
+  launch_logmel(d_samples, (const int64_t*)pc, (int)n_clips, groups, Ftot, (float*)pw, (float*)pt, (float*)pf, d_out, (float*)pm, st);
+  hipError_t e = hipGetLastError();
+  hipStreamSynchronize(st);
+  for (void* p : fake.owned) hipFree(p);
+  if (e != hipSuccess) {
+    set_error(std::string("logmel launch failed: ") + hipGetErrorString(e));
+    return AHA_ERR_HIP;
   }
   return AHA_OK;
 }

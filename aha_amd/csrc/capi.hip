@@ -1067,7 +1067,29 @@ int aha_hip_logmel(const float* samples, int64_t n_samples, float* out, void* st
     set_error("logmel: need more than 400 samples");
     return AHA_ERR_INVALID;
   }
-  return logmel_standalone(samples, n_samples, out, (hipStream_t)stream);
+  return logmel_standalone(samples, &n_samples, 1, out, (hipStream_t)stream);
+  API_GUARD_END
+}
+
+int aha_hip_logmel_batch(const float* samples, const int64_t* n_samples, size_t n_clips, float* out, void* stream) {
+  API_GUARD_BEGIN
+  if (!samples || !n_samples || !out || n_clips == 0 || n_clips > ((size_t)1 << 20)) {
+    set_error("logmel_batch: null argument or no clips");
+    return AHA_ERR_INVALID;
+  }
+  int64_t frames = 0;
+  for (size_t j = 0; j < n_clips; ++j) {
+    if (n_samples[j] < 401 || n_samples[j] > ((int64_t)1 << 34)) {
+      set_error("logmel_batch: clip " + std::to_string(j) + ": need more than 400 samples");
+      return AHA_ERR_INVALID;
+    }
+    frames += n_samples[j] / 160;
+  }
+  if (frames > ((int64_t)1 << 31) / 128) {
+    set_error("logmel_batch: too many frames for one call");
+    return AHA_ERR_INVALID;
+  }
+  return logmel_standalone(samples, n_samples, n_clips, out, (hipStream_t)stream);
   API_GUARD_END
 }
 

@@ -174,8 +174,9 @@ struct AttnPrefillArgs {
   // segment j is q / o rows row0 .. row0 + len - 1 and its cache positions 0 .. len - 1 live on pages page0, page0 + 1, ... of
   // kv.page_ptrs; seg_items = (n_items, 2) int32 {segment, 64-row q block}, most expensive first.  One block per (item, head); S = the
   // packed rows, kv_offset / kv_total / S2 unused.  Causal (model_embed_batch, generate_batch: head_dim 128, raw q heads with q_norm_w), or
-  // non-causal (the ViT's block-diagonal attention, vision_tower.hip: head_dim 72, q rows in the (N, nh, 96) layout, v_ones_row); a row's
-  // bits are those of its segment's own launch on the 16-row kernel.
+  // non-causal (the ViT's block-diagonal attention, vision_tower.hip: head_dim 72, q rows in the (N, nh, 96) layout, v_ones_row; the audio
+  // encoder's, audio_tower.hip: head_dim 64, q rows of the fused qkv activation with q_ld = 3 * D); a row's bits are those of its segment's
+  // own launch on the 16-row kernel.
   const int32_t* seg_tab = nullptr;
   const int32_t* seg_items = nullptr;
   int n_items = 0;
@@ -369,11 +370,17 @@ void launch_image_to_patches(const uint8_t* img, void* out, int H, int W, int pa
 
 // ---- Qwen3-ASR audio path (kernels_audio.hip) ----------------------------------------------------------------------
 namespace aha {
-void launch_logmel(const float* x, int64_t L, const float* window, const float* twid, const float* melfb, float* out,
-                   float* frame_max, int F, hipStream_t st);
-void launch_audio_im2col1(const float* feat, void* out, int F, int C, int Hin, int Win, hipStream_t st);
+// Log-mel of n_clips clips in one launch pair.  d_clips: (n_clips, LOGMEL_CLIP_WORDS) int64 {sample offset in x, L_j, first output column,
+// F_j = L_j / 160, first block} with the blocks ascending, n_groups = sum of ceil(F_j / 4); out: (128, ld) f32, clip j's frames in its
+// columns; frame_max: ld floats of scratch.  Each clip's bits are those of the clip alone.
+constexpr int LOGMEL_CLIP_WORDS = 5;
+void launch_logmel(const float* x, const int64_t* d_clips, int n_clips, int64_t n_groups, int64_t ld, const float* window, const float* twid,
+                   const float* melfb, float* out, float* frame_max, hipStream_t st);
+// d_chunks: (C, 3) int32 {first feature column of the clip, its F, window index within the clip}
+void launch_audio_im2col1(const float* feat, const int32_t* d_chunks, void* out, int64_t ld, int C, int Hin, int Win, hipStream_t st);
 void launch_im2col_nhwc(const void* in, void* out, int B, int Hin, int Win, int Cin, hipStream_t st);
 void launch_audio_tokens_gather(const void* in, void* out, int B, int Fq, int T, int Cc, hipStream_t st);
 void launch_sinus_pe_add(void* x, int64_t rows, int d, int T, hipStream_t st);
-void launch_kv_pack_generic(const void* src, int64_t ld, int k_off, int v_off, KvLayer kv, int N, int nh, int hd, hipStream_t st);
+void launch_kv_pack_generic(const void* src, int64_t ld, int k_off, int v_off, KvLayer kv, int N, int nh, int hd, hipStream_t st,
+                            const int32_t* slot_of = nullptr);
 }  // namespace aha

@@ -58,7 +58,8 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu((NWV =
   // Two causal segments in one launch (a.S2 > 0: a context-parallel rank's early and late chunk, csrc/model.hip): q / o rows
   // [0, S) see the cache through kv_offset, rows [S, S + S2) through kv_offset2; a block belongs to ONE segment, the late segment's
   // (longer) blocks go first and the early segment's fill the tail of the late one's last round.
-  // Packed independent sequences (a.seg_tab: model_embed_batch, generate_batch, the ViT's segments): the block's (segment, q block) is item
+  // Packed independent sequences (a.seg_tab: model_embed_batch, generate_batch, the ViT's segments, the audio encoder's clips -- any DQK:
+  // the q row address takes a.q_ld, the pages start at the segment's page0): the block's (segment, q block) is item
   // `it` of the host-sorted list (most expensive first) in either order; the segment's rows see only its own pages (page0 on), causally from
   // its first token or (ViT) all of them.
   int head, qblk, seg_rows = a.S, seg_off = a.kv_offset, seg_tot = a.kv_total, seg_row0 = 0, page0 = 0;

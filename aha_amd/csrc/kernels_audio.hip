@@ -13,17 +13,34 @@ namespace aha {
 // Every (frame, bin) and (frame, mel) sum keeps its order (n = 0..399, k = 0..200): bit-identical to the one-frame kernel.
 // Frame f covers padded samples [160 f, 160 f + 400) of reflect-padded input (pad 200 each side); the right pad carries
 // the reference's indexing quirk (tensor_utils.rs:525-549): it mirrors original samples [L-400, L-200), not [L-201, L-1).
+// Clips in one launch (round 7): clip j's samples start at sample_off in x, its F_j frames land in columns frame_off .. frame_off + F_j - 1
+// of the (128, ld) output, and its 4-frame groups are blocks group_off .. group_off + ceil(F_j / 4) - 1; the reflect pad (quirk included)
+// is per clip, and a block's arithmetic is the single-clip kernel's, so each clip's features are those of its own launch bit for bit.
 constexpr int MEL_FPB = 4;   // frames per block
-__global__ __launch_bounds__(256) void logmel_power_kernel(const float* __restrict__ x, int64_t L, const float* __restrict__ window,
+__global__ __launch_bounds__(256) void logmel_power_kernel(const float* __restrict__ x, const int64_t* __restrict__ clips, int n_clips,
+                                                           const float* __restrict__ window,
                                                            const float* __restrict__ twid,  // (400,2): cos, sin of 2 pi j / 400
                                                            const float* __restrict__ melfb, // (201,128)
-                                                           float* __restrict__ out,         // (128, F) log10 mel
-                                                           float* __restrict__ frame_max, int F) {
+                                                           float* __restrict__ out,         // (128, ld) log10 mel
+                                                           float* __restrict__ frame_max, int64_t ld) {
   __shared__ float4 fr[400];     // [tap][frame of the block]
   __shared__ float2 tw[400];
   __shared__ float4 pw[208];     // [bin][frame of the block]
   __shared__ float red[MEL_FPB][4];
-  const int f0 = blockIdx.x * MEL_FPB, tid = threadIdx.x;
+  // the block's clip: the last one whose first group is <= blockIdx.x (binary search over the clip table, groups ascending)
+  int lo = 0, hi = n_clips - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (clips[LOGMEL_CLIP_WORDS * mid + 4] <= (int64_t)blockIdx.x) lo = mid;
+    else hi = mid - 1;
+  }
+  const int64_t* cl = clips + LOGMEL_CLIP_WORDS * lo;
+  x += cl[0];
+  const int64_t L = cl[1];
+  out += cl[2];
+  frame_max += cl[2];
+  const int F = (int)cl[3];
+  const int f0 = (int)((int64_t)blockIdx.x - cl[4]) * MEL_FPB, tid = threadIdx.x;
   for (int n = tid; n < 400; n += 256) {
     float v[MEL_FPB];
 #pragma unroll
@@ -79,7 +96,7 @@ __global__ __launch_bounds__(256) void logmel_power_kernel(const float* __restri
       if (f0 + q >= F) continue;
       const float mm = fmaxf(m[q], 1e-10f);
       lg[q] = logf(mm) * (float)(1.0 / 2.302585092994046);  // log10 = ln * (1/ln 10) (modules.rs:1256-1258)
-      out[(int64_t)tid * F + f0 + q] = lg[q];
+      out[(int64_t)tid * ld + f0 + q] = lg[q];
     }
   }
 #pragma unroll
@@ -90,33 +107,44 @@ __global__ __launch_bounds__(256) void logmel_power_kernel(const float* __restri
   __syncthreads();
   if (tid < MEL_FPB && f0 + tid < F) frame_max[f0 + tid] = fmaxf(fmaxf(red[tid][0], red[tid][1]), fmaxf(red[tid][2], red[tid][3]));
 }
-// max over frames, then x = (max(x, gmax - 8) + 4) * 0.25 (feature_extraction_whisper.rs:110-113)
-__global__ __launch_bounds__(256) void logmel_finalize_kernel(float* __restrict__ out, const float* __restrict__ frame_max, int F) {
+// max over the clip's frames, then x = (max(x, gmax - 8) + 4) * 0.25 (feature_extraction_whisper.rs:110-113); one row of blocks per clip
+// (blockIdx.y), each clip with its own maximum
+__global__ __launch_bounds__(256) void logmel_finalize_kernel(float* __restrict__ out, const float* __restrict__ frame_max,
+                                                              const int64_t* __restrict__ clips, int64_t ld) {
   __shared__ float red[4];
+  const int64_t* cl = clips + LOGMEL_CLIP_WORDS * blockIdx.y;
+  const int64_t f_off = cl[2];
+  const int F = (int)cl[3];
   float g = -INFINITY;
-  for (int i = threadIdx.x; i < F; i += 256) g = fmaxf(g, frame_max[i]);
+  for (int i = threadIdx.x; i < F; i += 256) g = fmaxf(g, frame_max[f_off + i]);
   g = wave_max(g);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = g;
   __syncthreads();
   g = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) - 8.0f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (int64_t)128 * F; i += (int64_t)gridDim.x * 256)
-    out[i] = (fmaxf(out[i], g) * 1.0f + 4.0f) * 0.25f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (int64_t)128 * F; i += (int64_t)gridDim.x * 256) {
+    float* p = out + (i / F) * ld + f_off + i % F;
+    *p = (fmaxf(*p, g) * 1.0f + 4.0f) * 0.25f;
+  }
 }
-void launch_logmel(const float* x, int64_t L, const float* window, const float* twid, const float* melfb, float* out,
-                   float* frame_max, int F, hipStream_t st) {
-  if (F <= 0) return;
-  hipLaunchKernelGGL(logmel_power_kernel, dim3((F + MEL_FPB - 1) / MEL_FPB), dim3(256), 0, st, x, L, window, twid, melfb, out, frame_max, F);
-  hipLaunchKernelGGL(logmel_finalize_kernel, dim3(64), dim3(256), 0, st, out, frame_max, F);
+void launch_logmel(const float* x, const int64_t* d_clips, int n_clips, int64_t n_groups, int64_t ld, const float* window, const float* twid,
+                   const float* melfb, float* out, float* frame_max, hipStream_t st) {
+  if (n_clips <= 0 || n_groups <= 0) return;
+  hipLaunchKernelGGL(logmel_power_kernel, dim3((unsigned)n_groups), dim3(256), 0, st, x, d_clips, n_clips, window, twid, melfb, out, frame_max, ld);
+  hipLaunchKernelGGL(logmel_finalize_kernel, dim3(64, (unsigned)n_clips), dim3(256), 0, st, out, frame_max, d_clips, ld);
 }
 
 // ---- A1: conv2d 3x3, stride 2, pad 1 as im2col + GEMM (qwen3_asr/model.rs:196-204) ----------------------------------------
-// conv1 (1 input channel): mel features (128, F) f32 -> bf16 (input_features.to_dtype(model dtype)), chunked along time
+// conv1 (1 input channel): mel features (128, ld) f32 -> bf16 (input_features.to_dtype(model dtype)), chunked along time
 // into C windows of 100 frames (zero padded), rows = (chunk, ho, wo) over the (64, 50) output grid, 16 columns (9 used).
-__global__ __launch_bounds__(256) void audio_im2col1_kernel(const float* __restrict__ feat, bf16_t* __restrict__ out, int F,
-                                                            int64_t rows, int Hin, int Win, int Ho, int Wo) {
+// Chunks of several clips (round 7): chunk ch = window chunks[3 ch + 2] of the clip whose F = chunks[3 ch + 1] frames start at column
+// chunks[3 ch], so each clip's last window is zero-padded on its own.
+__global__ __launch_bounds__(256) void audio_im2col1_kernel(const float* __restrict__ feat, const int32_t* __restrict__ chunks,
+                                                            bf16_t* __restrict__ out, int64_t ld, int64_t rows, int Hin, int Win, int Ho, int Wo) {
   const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (r >= rows) return;
   const int wo = (int)(r % Wo), ho = (int)((r / Wo) % Ho), ch = (int)(r / ((int64_t)Wo * Ho));
+  const int64_t base = chunks[3 * ch];
+  const int F = chunks[3 * ch + 1], ci = chunks[3 * ch + 2];
   uint32_t v[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) v[i] = 0u;
@@ -125,8 +153,8 @@ __global__ __launch_bounds__(256) void audio_im2col1_kernel(const float* __restr
     const int h = 2 * ho - 1 + t / 3, w = 2 * wo - 1 + t % 3;
     float x = 0.f;
     if (h >= 0 && h < Hin && w >= 0 && w < Win) {
-      const int64_t fw = (int64_t)ch * Win + w;
-      if (fw < F) x = bf2f(f2bf(feat[(int64_t)h * F + fw]));
+      const int64_t fw = (int64_t)ci * Win + w;
+      if (fw < F) x = bf2f(f2bf(feat[(int64_t)h * ld + base + fw]));
     }
     const uint32_t b = f2bf(x);
     v[t >> 1] |= (t & 1) ? (b << 16) : b;
@@ -135,10 +163,11 @@ __global__ __launch_bounds__(256) void audio_im2col1_kernel(const float* __restr
   o[0] = u32x4_t{v[0], v[1], v[2], v[3]};
   o[1] = u32x4_t{v[4], v[5], v[6], v[7]};
 }
-void launch_audio_im2col1(const float* feat, void* out, int F, int C, int Hin, int Win, hipStream_t st) {
+void launch_audio_im2col1(const float* feat, const int32_t* d_chunks, void* out, int64_t ld, int C, int Hin, int Win, hipStream_t st) {
   const int Ho = (Hin + 1) / 2, Wo = (Win + 1) / 2;
   const int64_t rows = (int64_t)C * Ho * Wo;
-  hipLaunchKernelGGL(audio_im2col1_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, feat, (bf16_t*)out, F, rows,
+  if (rows <= 0) return;
+  hipLaunchKernelGGL(audio_im2col1_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, feat, d_chunks, (bf16_t*)out, ld, rows,
                      Hin, Win, Ho, Wo);
 }
 // NHWC (B, Hin, Win, Cin) bf16 -> rows (b, ho, wo) x columns (kh, kw, cin); one wave per (row, tap), 16-byte copies.
@@ -200,13 +229,16 @@ void launch_sinus_pe_add(void* x, int64_t rows, int d, int T, hipStream_t st) {
 
 // ---- A2 staging: K / V of a fused qkv activation -> attention pages (head_dim hd, multiple of 32) ----------------------
 // Fragment-major page blocks (common.h kpage_elem / vpage_elem): K block [nh][64 * hd], V block [nh][hd * 64].
+// slot_of (optional): row n goes to cache slot slot_of[n] (page slot / 64, slot % 64) -- the audio tower starts every clip on a page of
+// its own; null = slot n.
 __global__ __launch_bounds__(256) void kv_pack_generic_kernel(const bf16_t* __restrict__ src, int64_t ld, int k_off, int v_off,
-                                                              KvLayer kv, int N, int nh, int hd) {
+                                                              KvLayer kv, int N, int nh, int hd, const int32_t* __restrict__ slot_of) {
   const int lane = threadIdx.x & 63;
   const int64_t wid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (wid >= (int64_t)N * nh) return;
   const int n = (int)(wid / nh), h = (int)(wid % nh);
-  const int page = n / KV_PAGE_TOKENS, slot = n % KV_PAGE_TOKENS;
+  const int sn = slot_of ? slot_of[n] : n;
+  const int page = sn / KV_PAGE_TOKENS, slot = sn % KV_PAGE_TOKENS;
   bf16_t* base = reinterpret_cast<bf16_t*>(kv.page_ptrs[page] + kv.layer_off);
   bf16_t* kd = base + (int64_t)h * KV_PAGE_TOKENS * hd;
   bf16_t* vd = base + (int64_t)nh * KV_PAGE_TOKENS * hd + (int64_t)h * hd * KV_PAGE_TOKENS;
@@ -217,11 +249,12 @@ __global__ __launch_bounds__(256) void kv_pack_generic_kernel(const bf16_t* __re
     vd[vpage_elem(slot, e)] = vs[e];
   }
 }
-void launch_kv_pack_generic(const void* src, int64_t ld, int k_off, int v_off, KvLayer kv, int N, int nh, int hd, hipStream_t st) {
+void launch_kv_pack_generic(const void* src, int64_t ld, int k_off, int v_off, KvLayer kv, int N, int nh, int hd, hipStream_t st,
+                            const int32_t* slot_of) {
   const int64_t waves = (int64_t)N * nh;
   if (waves <= 0) return;
   hipLaunchKernelGGL(kv_pack_generic_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, (const bf16_t*)src, ld, k_off,
-                     v_off, kv, N, nh, hd);
+                     v_off, kv, N, nh, hd, slot_of);
 }
 
 }  // namespace aha

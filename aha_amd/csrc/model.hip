@@ -1726,7 +1726,8 @@ static int forward_initial_impl(aha_model* m, const uint32_t* ids, size_t n, siz
   }
   if (has_audio) {
     // audio tower -> masked_scatter into the <|audio_pad|> rows (qwen3_asr/model.rs:343-358)
-    if ((rc = audio_forward_and_scatter(m, ids, n, mm, m->p_x))) return rc;
+    const AudRequest r{mm, ids, n, 0, -1};
+    if ((rc = audio_forward_requests(m, &r, 1, m->p_x))) return rc;
   }
   if (d == 128) launch_rope_table(m->p_pos, Mloc, m->d_inv_freq, m->d_axis_map, Mloc, m->p_rope, st);   // cos / sin once for all layers
   // sequence-parallel tensor parallelism: rank r owns rows [r * spr, (r+1) * spr) of the residual stream between the GEMMs
@@ -2254,6 +2255,12 @@ static int generate_prefill_pass(aha_model* m, GenCall& gc, const uint32_t* ids,
     const aha_mm_input* q = mm[j0 + j];
     if (q && (q->n_images > 0 || q->n_videos > 0)) vreqs.push_back(VisRequest{q, ids + seg[3 * j], lens[j], seg[3 * j], j0 + j});
   }
+  std::vector<AudRequest> areqs;   // the pass's requests with an audio clip (generate_batch_impl checked them)
+  for (int j = 0; j < n_seg && mm && m->audio; ++j) {
+    const aha_mm_input* q = mm[j0 + j];
+    if (q && q->n_images <= 0 && q->n_videos <= 0)
+      areqs.push_back(AudRequest{q, ids + seg[3 * j], lens[j], seg[3 * j], j0 + j});
+  }
   int rc;
   if ((rc = ensure_prefill_scratch(m, (size_t)S))) return rc;
   if (m->p_seg_cap < n_tab) {
@@ -2293,6 +2300,8 @@ static int generate_prefill_pass(aha_model* m, GenCall& gc, const uint32_t* ids,
   }
   // ViT -> masked_scatter of every request's visual rows into its placeholder rows of the pass (qwen3vl/model.rs:1166-1190)
   if (!vreqs.empty() && (rc = vision_forward_requests(m, vreqs.data(), vreqs.size(), m->p_x))) return rc;
+  // the audio tower over every clip of the pass -> masked_scatter into each request's <|audio_pad|> rows (qwen3_asr/model.rs:343-358)
+  if (!areqs.empty() && (rc = audio_forward_requests(m, areqs.data(), areqs.size(), m->p_x))) return rc;
   launch_rope_table(m->p_pos, S, m->d_inv_freq, m->d_axis_map, S, m->p_rope, st);
   double attn_flops = 0;
   for (int j = 0; j < n_seg; ++j) attn_flops += 4.0 * seg[3 * j + 1] * (0.5 * seg[3 * j + 1]) * nq;
@@ -2329,8 +2338,8 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
     set_error("generate_batch: max_new must be at least 1");
     return AHA_ERR_INVALID;
   }
-  if (c.arch != AHA_ARCH_QWEN3 && c.arch != AHA_ARCH_QWEN3VL) {
-    set_error("generate_batch: Qwen3 and text-only Qwen3-VL only");
+  if (c.arch != AHA_ARCH_QWEN3 && c.arch != AHA_ARCH_QWEN3VL && c.arch != AHA_ARCH_QWEN3ASR) {
+    set_error("generate_batch: Qwen3, Qwen3-VL and Qwen3-ASR only");
     return AHA_ERR_UNSUPPORTED;
   }
   if (m->tp_size > 1 || m->cp_size > 1 || c.head_dim != 128) {
@@ -2362,21 +2371,29 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
   // of each request with images / videos (a text request: arange, delta 0)
   std::vector<std::vector<int32_t>> pos3(n_seqs);
   std::vector<int64_t> rope_delta(n_seqs, 0);
+  int rc = AHA_OK;
   if (mm) {
     size_t off = 0;
     for (size_t j = 0; j < n_seqs; off += seq_lens[j], ++j) {
       const aha_mm_input* q = mm[j];
       if (!q) continue;
       const std::string who = "generate_batch_mm: sequence " + std::to_string(j) + ": ";
-      if ((q->audio_features && q->n_frames > 0) || (q->audio_samples && q->n_samples > 0)) {
-        set_error(who + "audio input is not supported in batches");
-        return AHA_ERR_UNSUPPORTED;
-      }
       if (q->image_embeds) {
         set_error(who + "precomputed image_embeds are not supported in batches (pixel values only)");
         return AHA_ERR_UNSUPPORTED;
       }
       const bool has_img = q->n_images > 0, has_vid = q->n_videos > 0;
+      if (((q->audio_features && q->n_frames > 0) || (q->audio_samples && q->n_samples > 0)) && (c.arch != AHA_ARCH_QWEN3ASR || !m->audio)) {
+        set_error(who + "audio input given but this model has no audio tower");
+        return AHA_ERR_UNSUPPORTED;
+      }
+      // on a Qwen3-ASR model every entry without images / videos is an audio request: the tower's own checks (samples or features, the
+      // placeholder count)
+      if (!has_img && !has_vid && c.arch == AHA_ARCH_QWEN3ASR && m->audio) {
+        const AudRequest r{q, ids + off, seq_lens[j], 0, (int)j};
+        if ((rc = audio_check_requests(m, &r, 1))) return rc;
+        continue;
+      }
       if (!has_img && !has_vid) continue;
       if (c.arch != AHA_ARCH_QWEN3VL || !m->vision) {
         set_error(who + "image input given but this model has no vision tower (arch / model.visual.* weights)");
@@ -2426,8 +2443,7 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
     }
   }
   AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
-  int rc = model_clear_cache(m);
-  if (rc) return rc;
+  if ((rc = model_clear_cache(m))) return rc;
   struct ClearGuard {
     aha_model* m;
     ~ClearGuard() { model_clear_cache(m); }

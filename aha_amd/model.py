@@ -388,8 +388,9 @@ class HipInferenceModel:
 
     def generate_batch_mm(self, prompts: Sequence[Sequence[int]], data, max_new: int, params=None, max_tokens_per_pass: int = 0,
                           want_step_logits: bool = False):
-        """Generation of every request at once, with its images / videos (aha_hip_generate_batch_mm): data[j] is request j's
-        MultiModalData (pixel values and grids; no image_embeds, no audio) or None for a text request; data itself may be None.
+        """Generation of every request at once, with its images / videos or its audio clip (aha_hip_generate_batch_mm): data[j] is
+        request j's MultiModalData -- pixel values and grids (no image_embeds) on a Qwen3-VL model, audio_samples or audio_features on a
+        Qwen3-ASR model (samples win if both are set) -- or None for a text request; data itself may be None.
         params: None = every request greedy, else a sampling.SamplingParams per request (or one for all).  Per request, the tokens
         generate_generic yields for it alone with its data.  Returns a list of token lists, and with want_step_logits also the
         (len(prompts), max_new, vocab) float32 logits that chose each token (rows past a sequence's length are zero)."""

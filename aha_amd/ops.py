@@ -201,6 +201,20 @@ def logmel(samples: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def logmel_batch(clips) -> torch.Tensor:
+    """A0 over many clips in one launch pair (aha_hip_logmel_batch): a list of 1-D f32 sample tensors on one GPU -> (128, sum F_j) f32,
+    F_j = len(clip j) // 160, clip j's frames in its own columns (bit-identical to logmel(clip j))."""
+    assert len(clips) > 0
+    for c in clips:
+        _chk(c)
+        assert c.dtype == torch.float32 and c.dim() == 1
+    flat = torch.cat([c.reshape(-1) for c in clips]).contiguous()
+    n = np.ascontiguousarray([c.numel() for c in clips], dtype=np.int64)
+    out = torch.empty(128, int((n // 160).sum()), dtype=torch.float32, device=flat.device)
+    check(lib().aha_hip_logmel_batch(_ptr(flat), n.ctypes.data, len(clips), _ptr(out), _stream()))
+    return out
+
+
 # ---- batched decode (aha_hip_generate_batch's kernels) ----------------------------------------------------------------------
 GEMV_ROWS_STORE, GEMV_ROWS_RESIDUAL, GEMV_ROWS_SILU_MUL, GEMV_ROWS_LOGITS = 0, 1, 2, 3
 

@@ -290,6 +290,53 @@ def generate_asr(model, audio_datas, temperature: float, top_p: Optional[float] 
     return generated, prompt_tokens
 
 
+def generate_asr_batch(model, requests, temperature: float, top_p: Optional[float] = None, seed: int = 34562,
+                       max_tokens: int = 1024) -> List[Tuple[List[int], int]]:
+    """generate_asr for many requests at once: requests[r] is one request's list of (input_ids, MultiModalData) chunks, as
+    generate_asr takes it; returns, per request, what generate_asr returns for it alone (generated ids, prompt token count).
+    Every chunk of every request runs through ONE model.generate_batch_mm call (max_new = max_tokens), then the ASR loop's own rules
+    are applied on the host (qwen3_asr/generate.rs:130-186):
+      * a chunk ends AFTER its first token that is one of stop_token_ids()[:2] -- the first token included, which generate_batch_mm
+        never treats as a stop;
+      * a chunk the batch ended on another stop id (the model's third and later ones, which the ASR loop does not stop on) is run
+        again on its own with generate_asr's loop;
+      * the chunks of a request are joined in order.
+    Sampling (temperature >= 1e-7): every chunk samples with SamplingParams(temperature, top_p, top_k None, penalty 1, seed) -- its own
+    RNG stream, so a single-chunk request is exact.  A multi-chunk sampled request runs serially through generate_asr instead: its
+    chunks share ONE stream there, which a batch of independent streams cannot reproduce."""
+    sampled = not (np.float32(temperature) < np.float32(1e-7))
+    eos = set(model.stop_token_ids()[:2])
+    out: List[Optional[Tuple[List[int], int]]] = [None] * len(requests)
+    prompts, datas, where = [], [], []
+    for r, chunks in enumerate(requests):
+        if sampled and len(chunks) > 1:
+            out[r] = generate_asr(model, chunks, temperature, top_p, seed, max_tokens)
+            continue
+        for c, (ids, data) in enumerate(chunks):
+            prompts.append(list(ids))
+            datas.append(data)
+            where.append((r, c))
+    rows: List[List[int]] = []
+    if prompts:
+        params = SamplingParams(temperature=float(temperature), top_p=top_p, seed=seed) if sampled else None
+        rows = model.generate_batch_mm(prompts, datas, max_tokens, params=params)
+    per_chunk = {}
+    for (r, c), ids, data, toks in zip(where, prompts, datas, rows):
+        cut = next((i for i, t in enumerate(toks) if t in eos), None)
+        if cut is not None:
+            toks = toks[:cut + 1]
+        elif len(toks) < max_tokens:   # stopped on a stop id the ASR loop does not stop on: the chunk's own loop
+            toks = generate_asr(model, [(ids, data)], temperature, top_p, seed, max_tokens)[0]
+        per_chunk[(r, c)] = toks
+    for r, chunks in enumerate(requests):
+        if out[r] is None:
+            gen: List[int] = []
+            for c in range(len(chunks)):
+                gen += per_chunk[(r, c)]
+            out[r] = (gen, sum(len(ids) for ids, _ in chunks))
+    return out
+
+
 def generate_stream_generic_text(model, decode, input_ids: Sequence[int], ctx: GenerationContext, data=None, device_chunk: int = 8):
     """generate_stream_generic_text (src/models/common/generate.rs:161-229) as a Python generator of decoded text pieces.
 

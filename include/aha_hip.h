@@ -181,7 +181,8 @@ int aha_hip_embed_batch(aha_model* m, const uint32_t* input_ids, const size_t* s
  * Prefill runs as packed passes of at most max_tokens_per_pass rows (0: the embed_batch default); decode advances every unfinished sequence
  * in one step per token, the weights streamed once per group of <= 32 rows.  Sequence j owns ceil((len_j + max_new) / 64) pages of the
  * cache, reserved before any work (AHA_ERR_OOM if they cannot be had); the cache is cleared before and after, on success and on error.
- * AHA_ARCH_QWEN3 and text-only AHA_ARCH_QWEN3VL on one GPU with head_dim 128, else AHA_ERR_UNSUPPORTED.  AHA_ERR_INVALID: a null
+ * AHA_ARCH_QWEN3, text-only AHA_ARCH_QWEN3VL and text-only AHA_ARCH_QWEN3ASR (the thinker) on one GPU with head_dim 128, else
+ * AHA_ERR_UNSUPPORTED.  AHA_ERR_INVALID: a null
  * pointer, n_seqs == 0, an empty prompt, max_new == 0, or an id >= vocab_size (naming the sequence and position). */
 int aha_hip_generate_batch(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
                            size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* logits_out);
@@ -220,24 +221,30 @@ int aha_hip_generate_batch_sampled(aha_model* m, const uint32_t* input_ids, cons
                                    const aha_sampling_params* params, size_t max_new, size_t max_tokens_per_pass,
                                    uint32_t* tokens_out, size_t* n_out, float* step_logits_out);
 
-/* ---- batched generation with images ------------------------------------------------------------------------------------
- * aha_hip_generate_batch / _sampled for Qwen3-VL requests with images and videos.  mm: n_seqs entries, each NULL (a text request) or
- * that request's images and / or videos with forward_initial's rules (pixel values in host or device memory, bf16 or f32, grids on
- * the host); mm == NULL: every request is text.  params: NULL = every sequence greedy, else n_seqs samplers with exactly the semantics
- * of aha_hip_generate_batch_sampled (one RNG stream per sequence).  step_logits_out: the layout of _sampled (n_seqs x max_new x vocab
- * f32, may be NULL), for greedy sequences too: entry [j, n_out[j] - 1] of a greedy sequence is aha_hip_generate_batch's logits_out.
+/* ---- batched generation with images and audio ---------------------------------------------------------------------------
+ * aha_hip_generate_batch / _sampled for Qwen3-VL requests with images and videos and for Qwen3-ASR requests with audio.  mm: n_seqs
+ * entries, each NULL (a text request) or that request's images and / or videos, or its audio clip, with forward_initial's rules (pixel
+ * values in host or device memory, bf16 or f32, grids on the host; audio samples or (128, n_frames) features in host or device memory,
+ * samples winning when both are set); mm == NULL: every request is text.  params: NULL = every sequence greedy, else n_seqs samplers
+ * with exactly the semantics of aha_hip_generate_batch_sampled (one RNG stream per sequence).  step_logits_out: the layout of _sampled
+ * (n_seqs x max_new x vocab f32, may be NULL), for greedy sequences too: entry [j, n_out[j] - 1] of a greedy sequence is
+ * aha_hip_generate_batch's logits_out.
  * Row j of tokens_out holds what generate_generic (generate.rs:115-159) yields for request j alone, on a cleared model, with its
- * MultiModalData (sampled rows: given the logits this call computes).  Per request, as Qwen3VLModel::forward does it for one:
- *   positions      get_rope_index of its own ids and grids at offset 0 (qwen3vl/model.rs:901-1133), a text request arange;
+ * MultiModalData (sampled rows: given the logits this call computes).  Per request, as Qwen3VLModel::forward / Qwen3ASRThinker::forward
+ * do it for one:
+ *   positions      get_rope_index of its own ids and grids at offset 0 (qwen3vl/model.rs:901-1133), a text or audio request arange;
  *   visual rows    the merged tower rows masked_scatter'ed into its <|image_pad|> then <|video_pad|> rows (model.rs:1166-1190);
  *   DeepStack      feature k added to its visual rows after decoder layer k (model.rs:806-822);
- *   decode         position seqlen_offset + its own rope_delta on all three rows (model.rs:1235-1264).
+ *   audio rows     its clip's audio tower rows masked_scatter'ed into its <|audio_pad|> rows (qwen3_asr/model.rs:336-361);
+ *   decode         position seqlen_offset + its own rope_delta on all three rows (model.rs:1235-1264; 0 for text and audio).
  * The prefill passes follow aha_hip_generate_batch's rule (text rows, placeholders included, up to max_tokens_per_pass; a request is
- * never split); one tower pass encodes every image and video of a prefill pass.  The model's own rope_delta is neither read nor left
- * behind.  Errors, all before any device work (the cache stays cleared): AHA_ERR_UNSUPPORTED for an mm entry on a model that is not
- * Qwen3-VL or has no vision weights, image_embeds, or audio input; AHA_ERR_SHAPE for a placeholder-count, grid or n_patches mismatch
- * (the message names the sequence); everything else as aha_hip_generate_batch / _sampled.  Text requests give tokens and logits
- * bit-identical to aha_hip_generate_batch / _sampled. */
+ * never split); one tower pass encodes every image and video of a prefill pass, and one audio tower pass (split in sub-passes of at
+ * most 240 s of audio, a clip never split) every clip of it.  The model's own rope_delta is neither read nor left behind.
+ * Errors, all before any device work (the cache stays cleared), the message naming the sequence: AHA_ERR_UNSUPPORTED for images or
+ * videos on a model that is not Qwen3-VL or has no vision weights, image_embeds, or audio on a model without an audio tower;
+ * AHA_ERR_SHAPE for a placeholder-count, grid or n_patches mismatch; AHA_ERR_INVALID for audio of at most 400 samples or an entry
+ * without samples or features on a Qwen3-ASR model; everything else as aha_hip_generate_batch / _sampled.  Text requests give tokens
+ * and logits bit-identical to aha_hip_generate_batch / _sampled. */
 int aha_hip_generate_batch_mm(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs,
                               const aha_mm_input* const* mm, const aha_sampling_params* params, size_t max_new,
                               size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* step_logits_out);
@@ -578,6 +585,10 @@ int aha_hip_video_to_patches(const uint8_t* frames_thwc, void* out, int32_t T, i
  * device samples -> out (128, n_samples/160) f32 device (n_fft 400, hop 160, symmetric Hann, Slaney mel, log10, max-8 clamp,
  * (x+4)/4).  n_samples must be >= 401. */
 int aha_hip_logmel(const float* samples, int64_t n_samples, float* out, void* stream);
+/* aha_hip_logmel over n_clips clips in one launch pair: `samples` holds the clips back to back (device), clip j n_samples[j] (> 400,
+ * host array) of them; out (128, sum F_j) f32 device, F_j = n_samples[j] / 160, clip j's frames in columns F_0 + .. + F_{j-1} on.  Each
+ * clip's columns are bit-identical to aha_hip_logmel on that clip alone (its own max - 8 clamp). */
+int aha_hip_logmel_batch(const float* samples, const int64_t* n_samples, size_t n_clips, float* out, void* stream);
 /* A0-pre: resample_audio_from_vec_f32 (src/utils/audio_utils.rs:590-616), the step between the audio decoder and the
  * feature extractor on the Qwen3-ASR request path (qwen3_asr/processor.rs:76,85: 16 kHz, 1 channel): interleaved PCM f32
  * (n_frames x channels, host) -> mean over channels -> resample_simple (audio_utils.rs:247-255: sinc interpolation, Hann

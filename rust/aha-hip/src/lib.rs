@@ -305,6 +305,13 @@ pub mod sys {
         ) -> i32;
         pub fn aha_hip_sampler_rng_words(s: *const AhaSampler) -> u64;
         pub fn aha_hip_cache_len(m: *const AhaModel) -> usize;
+        pub fn aha_hip_logmel_batch(
+            samples: *const f32,
+            n_samples: *const i64,
+            n_clips: usize,
+            out: *mut f32,
+            stream: *mut std::ffi::c_void,
+        ) -> i32;
         pub fn aha_hip_audio_resample(
             ctx: *mut AhaCtx,
             pcm: *const f32,
@@ -366,6 +373,16 @@ pub enum MmInput<'a> {
 }
 
 /// One model on one GPU.  Not thread-safe by contract (the reference takes `&mut self` everywhere and a write lock per request).
+/// The Whisper log-mel of many clips in one launch pair (aha_hip_logmel_batch): `samples` = the clips back to back in device memory,
+/// `n_samples[j]` (> 400) of clip j; `out` = a device (128, sum F_j) f32 buffer, F_j = n_samples[j] / 160, clip j's frames in its own
+/// columns, each clip bit-identical to its own aha_hip_logmel.
+///
+/// # Safety
+/// `samples` and `out` must be device buffers of at least the sizes above, `stream` a HIP stream of their device or null.
+pub unsafe fn logmel_batch(samples: *const f32, n_samples: &[i64], out: *mut f32, stream: *mut std::ffi::c_void) -> Result<(), Error> {
+    check(sys::aha_hip_logmel_batch(samples, n_samples.as_ptr(), n_samples.len(), out, stream))
+}
+
 pub struct Model {
     ctx: *mut sys::AhaCtx,
     model: *mut sys::AhaModel,
@@ -580,9 +597,10 @@ impl Model {
         Ok(n_out.iter().enumerate().map(|(j, &n)| toks[j * max_new..j * max_new + n].to_vec()).collect())
     }
 
-    /// `generate_generic` for many Qwen3-VL requests with their images / videos, every request at once (aha_hip_generate_batch_mm):
-    /// `mm[j]` is request j's payload (`MmInput::None` for a text request; `Image` / `Vision` otherwise), `params` `None` = every
-    /// request greedy, else one sampler per request.  Per request, the tokens `generate_generic` yields for it alone with its data.
+    /// `generate_generic` for many Qwen3-VL requests with their images / videos, or Qwen3-ASR requests with their audio clips, every
+    /// request at once (aha_hip_generate_batch_mm): `mm[j]` is request j's payload (`MmInput::None` for a text request; `Image` /
+    /// `Vision` / `AudioFeatures` / `AudioSamples` otherwise), `params` `None` = every request greedy, else one sampler per request.
+    /// Per request, the tokens `generate_generic` yields for it alone with its data.
     pub fn generate_batch_mm(
         &mut self,
         prompts: &[&[u32]],

@@ -17,7 +17,13 @@ text tokens each, no stop tokens, through generate_batch_mm.  Per B: prefill ms 
 the B images in one call, timed apart: the tower's share of that prefill), decode step ms by the rule above, aggregate tok/s, and the
 speed-up over a serial leg of forward_initial(mm) + decode_greedy on --serial requests (aggregate tok/s over whole requests).
     python scripts/bench_generate_batch.py --vl [--batches 1,4,8,16] [--image 448] [--prompt 512] [--max-new 64]
-    python scripts/bench_generate_batch.py --vl --once vl8b:16   # one generate_batch_mm call (rocprofv3 --kernel-trace --stats)"""
+    python scripts/bench_generate_batch.py --vl --once vl8b:16   # one generate_batch_mm call (rocprofv3 --kernel-trace --stats)
+With --asr: Qwen3-ASR-0.6B with its audio tower (configs.qwen3_asr_0_6b, seeded weights), B requests of one --clip-s second seeded clip
+(raw samples) each, no stop tokens, through generate_batch_mm.  Per B: prefill ms (one call with max_new 1), tower ms (that prefill
+minus the prefill of the same ids as text: the audio tower's share), the tower per clip, decode step ms by the rule above, aggregate
+tok/s, audio seconds per wall second, and the speed-up over serial generate_asr (the ASR loop, greedy) on --serial requests.
+    python scripts/bench_generate_batch.py --asr [--batches 1,4,16] [--clip-s 30] [--max-new 64]
+    python scripts/bench_generate_batch.py --asr --once asr:16   # one generate_batch_mm call (rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
 import os
@@ -169,6 +175,78 @@ def bench_vl(a):
     m.close()
 
 
+def asr_requests(cfg, B, seconds, seed=0):
+    """B (ids, MultiModalData) requests: a few text tokens, <|audio_start|>, one <|audio_pad|> per audio token, <|audio_end|>, text."""
+    from aha_amd.model import MultiModalData
+    from oracle.qwen3_asr import get_feat_extract_output_lengths
+    g = np.random.default_rng(seed)
+    out = []
+    for _ in range(B):
+        wave = np.clip(g.normal(0, 0.1, int(16000 * seconds)), -1, 1).astype(np.float32)
+        n_tok = get_feat_extract_output_lengths(wave.size // 160)
+        ids = [int(x) for x in g.integers(0, 150000, size=5)] + [cfg.audio_start_token_id] + [cfg.audio_token_id] * n_tok + \
+              [cfg.audio_end_token_id] + [int(x) for x in g.integers(0, 150000, size=7)]
+        out.append((ids, MultiModalData(audio_samples=wave)))
+    return out
+
+
+def bench_asr(a):
+    """generate_batch_mm on Qwen3-ASR-0.6B with one clip per request against serial generate_asr."""
+    import torch
+    from aha_amd import sampling as hs
+    from aha_amd.configs import qwen3_asr_0_6b
+    from aha_amd.model import HipInferenceModel
+    from aha_amd.weights import qwen3_asr_weights
+    cfg = qwen3_asr_0_6b()
+    cfg.text.eos_token_ids = []
+    w = qwen3_asr_weights(cfg, seed=0, device="cuda")
+    m = HipInferenceModel(cfg, w)
+    del w
+    torch.cuda.empty_cache()
+    batches = [int(b) for b in a.batches.split(",")]
+    if a.once:
+        B = int(a.once.split(":")[1])
+        reqs = asr_requests(cfg, B, a.clip_s)
+        m.generate_batch_mm([r[0] for r in reqs], [r[1] for r in reqs], a.max_new)
+        torch.cuda.synchronize()
+        m.close()
+        return
+    reqs_all = asr_requests(cfg, max(batches + [a.serial]), a.clip_s)
+    hs.generate_asr(m, [reqs_all[0]], 0.0, max_tokens=2)   # warm-up
+    t_ser, t_pre = 0.0, 0.0
+    for ids, data in reqs_all[:a.serial]:   # the whole ASR loop of one request: prefill + decode
+        t, (out, _) = timed(lambda: hs.generate_asr(m, [(ids, data)], 0.0, max_tokens=a.max_new))
+        assert len(out) == a.max_new
+        t_ser += t
+        tp, _ = timed(lambda: (m.forward_initial(ids, 0, data, want_logits=False), m.clear_cache()))
+        t_pre += tp
+    serial_tps = a.serial * a.max_new / t_ser
+    print(json.dumps({"model": "asr0.6b", "clip_s": a.clip_s, "serial_prefill_ms": round(t_pre / a.serial * 1e3, 2),
+                      "serial_request_s": round(t_ser / a.serial, 3), "serial_aggregate_tok_s": round(serial_tps, 1),
+                      "serial_audio_s_per_s": round(a.serial * a.clip_s / t_ser, 1)}), flush=True)
+    m.generate_batch_mm([reqs_all[0][0]], [reqs_all[0][1]], 2)   # warm-up
+    tower1 = None
+    for B in batches:
+        reqs = reqs_all[:B]
+        ps, ds = [r[0] for r in reqs], [r[1] for r in reqs]
+        m.generate_batch_mm(ps, ds, 1)   # scratch at this size
+        t1, _ = timed(lambda: m.generate_batch_mm(ps, ds, 1))
+        tt, _ = timed(lambda: m.generate_batch_mm(ps, None, 1))
+        tn, out = timed(lambda: m.generate_batch_mm(ps, ds, a.max_new))
+        assert all(len(o) == a.max_new for o in out)
+        step = (tn - t1) / (a.max_new - 1)
+        tower = t1 - tt
+        tower1 = tower if tower1 is None and B == 1 else tower1
+        rec = {"model": "asr0.6b", "B": B, "clip_s": a.clip_s, "max_new": a.max_new, "prefill_ms": round(t1 * 1e3, 2),
+               "tower_ms": round(tower * 1e3, 2), "tower_ms_per_clip": round(tower / B * 1e3, 3), "step_ms": round(step * 1e3, 3),
+               "total_s": round(tn, 3), "aggregate_tok_s": round(B * a.max_new / tn, 1), "audio_s_per_s": round(B * a.clip_s / tn, 1),
+               "vs_serial": round(B * a.max_new / tn / serial_tps, 2)}
+        if tower1:
+            rec["tower_per_clip_vs_alone"] = round(tower / B / tower1, 3)
+        print(json.dumps(rec), flush=True)
+    m.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="0.6b,8b")
@@ -181,12 +259,17 @@ def main():
     ap.add_argument("--sampler", action="store_true", help="also the batched sampled path; the serial leg samples too")
     ap.add_argument("--vl", action="store_true", help="Qwen3-VL-8B requests with one image each through generate_batch_mm")
     ap.add_argument("--image", type=int, default=448)
+    ap.add_argument("--asr", action="store_true", help="Qwen3-ASR-0.6B requests with one audio clip each through generate_batch_mm")
+    ap.add_argument("--clip-s", type=float, default=30.0)
     a = ap.parse_args()
     import torch
     from aha_amd import build
     build.build()
     if a.vl:
         bench_vl(a)
+        return
+    if a.asr:
+        bench_asr(a)
         return
     if a.once:
         name, B = a.once.split(":")
