@@ -431,12 +431,9 @@ static int audio_tower_pass(aha_model* m, const AudClip* k, int n, void* x_text)
     Ntok += k[j].n_tok;
     pages += (k[j].n_tok + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
   }
-  // attention items: (clip, 64-row q block); non-causal, so a block's cost is its clip's length: longest first
-  std::vector<std::pair<int, int>> items;
-  for (int j = 0; j < n; ++j)
-    for (int b = 0; b * 64 < k[j].n_tok; ++b) items.emplace_back(j, b);
-  std::stable_sort(items.begin(), items.end(), [&](const auto& p, const auto& q) { return k[p.first].n_tok > k[q.first].n_tok; });
-  for (const auto& it : items) seg.push_back(it.first), seg.push_back(it.second);
+  // attention items: (clip, 64-row q block), non-causal: longest clip first
+  const std::vector<int32_t> items = seg_items_of(seg, false);
+  seg.insert(seg.end(), items.begin(), items.end());
   const bool packed = n > 1;   // one clip: its rows are already packed, its KV slots the identity
   int rc;
   if ((rc = audio_ensure_scratch(m, (size_t)Ftot, (size_t)Ltot, (size_t)Ctot, (size_t)pages, (size_t)n))) return rc;
@@ -528,7 +525,7 @@ static int audio_tower_pass(aha_model* m, const AudClip* k, int n, void* x_text)
       AttnPrefillArgs q{};
       q.q = a->qkv; q.q_ld = 3 * D; q.kv = kv; q.o = a->attn; q.S = n_tok; q.nh = a->nh; q.kvh = a->nh; q.d = a->hd;
       q.kv_offset = 0; q.kv_total = n_tok; q.causal = 0; q.scale = a->scale;
-      q.seg_tab = a->d_seg; q.seg_items = a->d_seg + 3 * (size_t)n; q.n_items = (int)items.size();
+      q.seg_tab = a->d_seg; q.seg_items = a->d_seg + 3 * (size_t)n; q.n_items = (int)items.size() / 2;
       ProfScope ps(m, "attn_audio", (double)n_tok * D * 8, attn_flops);
       launch_attn_prefill(q, st);
     }

@@ -4,6 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <utility>
+#include <vector>
+
 namespace aha {
 
 // Paged KV cache view of ONE layer.  Page p of this layer lives at page_ptrs[p] + layer_off (bytes):
@@ -181,6 +185,23 @@ struct AttnPrefillArgs {
   const int32_t* seg_items = nullptr;
   int n_items = 0;
 };
+// The seg_items of a host seg_tab ({row0, len, page0} per segment): {segment, 64-row q block} pairs in segment order, then stable-sorted
+// most expensive first.  Causal: a block costs the keys its last row sees, min(len, (b + 1) * 64); non-causal: its segment's length.
+inline std::vector<int32_t> seg_items_of(const std::vector<int32_t>& seg_tab, bool causal) {
+  constexpr int QB = 64;   // q rows per block (launch_attn_prefill: 4 waves with seg_tab)
+  std::vector<std::pair<int32_t, int32_t>> items;
+  for (size_t j = 0; 3 * j < seg_tab.size(); ++j)
+    for (int32_t b = 0; b * QB < seg_tab[3 * j + 1]; ++b) items.emplace_back((int32_t)j, b);
+  auto cost = [&](const std::pair<int32_t, int32_t>& it) {
+    const int32_t len = seg_tab[3 * (size_t)it.first + 1];
+    return causal ? std::min(len, (it.second + 1) * QB) : len;
+  };
+  std::stable_sort(items.begin(), items.end(), [&](const auto& x, const auto& y) { return cost(x) > cost(y); });
+  std::vector<int32_t> out;
+  out.reserve(2 * items.size());
+  for (const auto& it : items) out.push_back(it.first), out.push_back(it.second);
+  return out;
+}
 void launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t st);
 bool attn_prefill_takes_qfuse(const AttnPrefillArgs& a);
 int attn_prefill_form_of(const AttnPrefillArgs& a);       // the kernel form launch_attn_prefill takes: 0 = the 16-rows-per-wave kernel, 64 / 65   // would launch_attn_prefill run a kernel that norms + rotates Q itself for these arguments?

@@ -174,13 +174,14 @@ struct aha_model {
   size_t gemm_ws_bytes = 0;
   void* d_sk_ctrs = nullptr;    // SK_MAX_COUNTERS zeroed u32: per-tile arrival counters of the persistent GEMM kernel (kernels_gemm_sk.hip)
   std::vector<void*> pf_owned;
-  // packed-batch embedding (model_embed_batch): the per-pass int32 tables and the (sequences, hidden) f32 output, grown on demand
-  int32_t* p_seg = nullptr;
-  size_t p_seg_cap = 0;
-  float* p_pool = nullptr;
+  // packed prefill passes (model_embed_batch, the generate_batch entries; model.hip PackedPass), grown on demand: the pass's int32 table
+  // (segments | items | row slots | page rows | last rows), and the pinned staging buffer its ids | positions | table go up through
+  int32_t* p_pass_tab = nullptr;
+  size_t p_pass_tab_cap = 0;
+  int32_t* h_pass_stage = nullptr;
+  size_t h_pass_stage_cap = 0;
+  float* p_pool = nullptr;   // model_embed_batch: a pass's (sequences, hidden) f32 embeddings
   size_t p_pool_cap = 0;
-  int32_t* h_embed_stage = nullptr;   // pinned: a pass's ids | positions | tables on their way up
-  size_t h_embed_stage_cap = 0;
   // vision tower (Qwen3-VL)
   aha::VisionModel* vision = nullptr;
   // audio tower (Qwen3-ASR)

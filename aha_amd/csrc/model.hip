@@ -767,9 +767,9 @@ void model_destroy(aha_model* m) {
   tp_destroy(m);
   for (void* p : m->owned) hipFree(p);
   for (void* p : m->pf_owned) hipFree(p);
-  if (m->p_seg) hipFree(m->p_seg);
+  if (m->p_pass_tab) hipFree(m->p_pass_tab);
   if (m->p_pool) hipFree(m->p_pool);
-  if (m->h_embed_stage) hipHostFree(m->h_embed_stage);
+  if (m->h_pass_stage) hipHostFree(m->h_pass_stage);
   for (void* p : m->slabs) hipFree(p);
   if (m->d_page_ptrs) hipFree(m->d_page_ptrs);
   if (m->h_state) hipHostFree(m->h_state);
@@ -1875,12 +1875,60 @@ static int forward_initial_impl(aha_model* m, const uint32_t* ids, size_t n, siz
 // sequence -- positions 0 .. len-1, a cache window of its own from a fresh 64-token page, causal attention inside it -- but the texts of
 // a pass run as ONE packed prefill.  Every GEMM, norm and activation is row-wise and needs no change; the q/k-norm + RoPE kernel puts row r's
 // K / V at cache slot row_slot[r], the 16-row attention kernel runs one block per (sequence, q block, head) over the sequence's own pages
-// (AttnPrefillArgs::seg_tab), and embed_pool_kernel normalises every sequence's last row straight into the f32 output.
-// Passes: sequences in order while the pass stays within max_tokens_per_pass rows (0: EMBED_PASS_ROWS) and twice that many cache slots
-// (short texts waste up to a page each); a pass always holds at least one whole sequence.
-constexpr size_t EMBED_PASS_ROWS = 16384;
+// (AttnPrefillArgs::seg_tab), and embed_pool_kernel normalises every sequence's last row straight into the f32 output.  The generate_batch
+// entries run their prompts' prefill as the same passes.
+constexpr size_t PACKED_PASS_ROWS = 16384;
 
-// The single-GPU layer stack of a packed prefill pass of independent sequences (embed_pass, generate_prefill_pass): the rows' embeddings in
+// The passes of a batch: sequences in order while the pass stays within max_tokens_per_pass rows (0: PACKED_PASS_ROWS) and twice that
+// many cache slots (short texts waste up to a page each); a pass always holds at least one whole sequence.
+struct PassRange {
+  size_t j, k, off;   // sequences j .. k - 1, their ids from ids[off] on
+};
+static std::vector<PassRange> split_passes(const size_t* lens, size_t n, size_t max_tokens_per_pass) {
+  const size_t budget = std::min(max_tokens_per_pass ? max_tokens_per_pass : PACKED_PASS_ROWS, (size_t)1 << 24);
+  std::vector<PassRange> passes;
+  for (size_t j = 0, off = 0; j < n;) {
+    size_t rows = 0, slots = 0, k = j;
+    while (k < n) {
+      const size_t len = lens[k], sl = (len + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS * KV_PAGE_TOKENS;
+      if (k > j && (rows + len > budget || slots + sl > 2 * budget)) break;
+      rows += len, slots += sl, ++k;
+    }
+    passes.push_back({j, k, off});
+    off += rows;
+    j = k;
+  }
+  return passes;
+}
+
+// The token ids of a batch: every sequence non-empty, within 2^24 tokens after growing by `grow` new ones, every id in the vocabulary
+static int check_batch_ids(const aha_model_desc& c, const char* who, const uint32_t* ids, const size_t* lens, size_t n, size_t grow) {
+  size_t total = 0;
+  for (size_t j = 0; j < n; ++j) {
+    if (lens[j] == 0) {
+      set_error(std::string(who) + ": empty input_ids of sequence " + std::to_string(j));
+      return AHA_ERR_INVALID;
+    }
+    if (lens[j] + grow > (size_t)1 << 24) {
+      set_error(std::string(who) + ": sequence " + std::to_string(j) + (grow ? " would grow past" : " is longer than") + " 2^24 tokens");
+      return AHA_ERR_INVALID;
+    }
+    for (size_t i = 0; i < lens[j]; ++i)
+      if (ids[total + i] >= (uint32_t)c.vocab_size) {
+        set_error("token id out of range in sequence " + std::to_string(j) + " at position " + std::to_string(i));
+        return AHA_ERR_INVALID;
+      }
+    total += lens[j];
+  }
+  return AHA_OK;
+}
+
+struct ClearCacheGuard {   // the cache is empty afterwards, on success and on error alike (qwen3_embedding/mod.rs:58)
+  aha_model* m;
+  ~ClearCacheGuard() { model_clear_cache(m); }
+};
+
+// The single-GPU layer stack of a packed prefill pass of independent sequences (run_packed_pass): the rows' embeddings in
 // p_x, their positions' rope table in p_rope; K / V of row r go to cache slot d_slot[r] of the pages page_ptrs names, page p of 0 .. npages-1
 // holding the rows d_prow[2p] .. + d_prow[2p + 1]; the attention runs one block per (d_items entry, head) over d_seg's segments.  Leaves the
 // last layer's output rows in p_x.  vis: the pass has visual rows (the tower's last pass scattered them): DeepStack adds after layer k <
@@ -1954,98 +2002,133 @@ static int packed_layers(aha_model* m, int S, const uint64_t* page_ptrs, const i
   return AHA_OK;
 }
 
-static int embed_pass(aha_model* m, const uint32_t* ids, const size_t* lens, int n_seg, float* out) {
-  const aha_model_desc& c = m->desc;
-  const int H = c.hidden_size, nq = c.num_attention_heads * c.head_dim;
-  hipStream_t st = m->stream;
-  // host plan: segment table {row0, len, page0}, (segment, q block) items most expensive first, per-row cache slots, per-page rows
+// The host plan of one packed pass over n_seg sequences.  tab is the int32 table the pass's kernels read from p_pass_tab: segments
+// {row0, len, page0} (AttnPrefillArgs::seg_tab) | items {segment, 64-row q block} (seg_items_of, causal) | per-row cache slots | per pass
+// page {first row, rows} | every segment's last row.  Segment j's rows row0 .. row0 + len - 1 are its cache positions 0 .. len - 1, on
+// pass pages page0, page0 + 1, ...; pass page p is logical page pages[p].
+struct PackedPass {
+  int n_seg = 0, S = 0, npages = 0, n_items = 0;
+  size_t o_items = 0, o_slot = 0, o_prow = 0, o_last = 0;
+  std::vector<int32_t> tab;
+  std::vector<int32_t> pos;     // (3, S) positions
+  std::vector<int64_t> pages;
+};
+
+// lens: the sequences' lengths; page0: each one's first logical page (its pages follow it); pos3: null, or per sequence its (3, len)
+// positions, an empty one meaning arange
+static PackedPass plan_packed_pass(const size_t* lens, int n_seg, const int64_t* page0, const std::vector<int32_t>* pos3) {
+  PackedPass pp;
+  pp.n_seg = n_seg;
   std::vector<int32_t> seg(3 * (size_t)n_seg);
-  int S = 0, npages = 0;
   for (int j = 0; j < n_seg; ++j) {
     const int len = (int)lens[j];
-    seg[3 * j] = S, seg[3 * j + 1] = len, seg[3 * j + 2] = npages;
-    S += len;
-    npages += (len + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
+    seg[3 * j] = pp.S, seg[3 * j + 1] = len, seg[3 * j + 2] = (int32_t)pp.pages.size();
+    for (int p = 0; p * KV_PAGE_TOKENS < len; ++p) pp.pages.push_back(page0[j] + p);
+    pp.S += len;
   }
-  constexpr int QB = 64;   // q rows per attention block (launch_attn_prefill: 4 waves with seg_tab)
-  std::vector<std::pair<int, int>> items;
-  for (int j = 0; j < n_seg; ++j)
-    for (int b = 0; b * QB < seg[3 * j + 1]; ++b) items.emplace_back(j, b);
-  // cost of a block ~ the keys its last row sees
-  auto cost = [&](const std::pair<int, int>& it) { return std::min(seg[3 * it.first + 1], (it.second + 1) * QB); };
-  std::stable_sort(items.begin(), items.end(), [&](const auto& x, const auto& y) { return cost(x) > cost(y); });
-  const int n_items = (int)items.size();
-  const size_t o_seg = 0, o_items = o_seg + seg.size(), o_slot = o_items + 2 * (size_t)n_items, o_prow = o_slot + S,
-               n_tab = o_prow + 2 * (size_t)npages;
-  std::vector<int32_t> tab(n_tab);
+  const int S = pp.S;
+  pp.npages = (int)pp.pages.size();
+  const std::vector<int32_t> items = seg_items_of(seg, true);
+  pp.n_items = (int)items.size() / 2;
+  pp.o_items = seg.size(), pp.o_slot = pp.o_items + items.size(), pp.o_prow = pp.o_slot + S, pp.o_last = pp.o_prow + 2 * (size_t)pp.npages;
+  std::vector<int32_t>& tab = pp.tab;
+  tab.resize(pp.o_last + n_seg);
   std::copy(seg.begin(), seg.end(), tab.begin());
-  for (int i = 0; i < n_items; ++i) tab[o_items + 2 * i] = items[i].first, tab[o_items + 2 * i + 1] = items[i].second;
-  std::vector<int32_t> pos(3 * (size_t)S);
+  std::copy(items.begin(), items.end(), tab.begin() + pp.o_items);
+  pp.pos.resize(3 * (size_t)S);
   for (int j = 0; j < n_seg; ++j) {
     const int r0 = seg[3 * j], len = seg[3 * j + 1], p0 = seg[3 * j + 2];
+    const int32_t* pj = pos3 && !pos3[j].empty() ? pos3[j].data() : nullptr;
     for (int i = 0; i < len; ++i) {
-      tab[o_slot + r0 + i] = p0 * KV_PAGE_TOKENS + i;
-      for (int a = 0; a < 3; ++a) pos[(size_t)a * S + r0 + i] = i;
+      tab[pp.o_slot + r0 + i] = p0 * KV_PAGE_TOKENS + i;
+      for (int a = 0; a < 3; ++a) pp.pos[(size_t)a * S + r0 + i] = pj ? pj[(size_t)a * len + i] : i;
     }
     for (int p = 0; p * KV_PAGE_TOKENS < len; ++p) {
-      tab[o_prow + 2 * (size_t)(p0 + p)] = r0 + p * KV_PAGE_TOKENS;
-      tab[o_prow + 2 * (size_t)(p0 + p) + 1] = std::min(KV_PAGE_TOKENS, len - p * KV_PAGE_TOKENS);
+      tab[pp.o_prow + 2 * (size_t)(p0 + p)] = r0 + p * KV_PAGE_TOKENS;
+      tab[pp.o_prow + 2 * (size_t)(p0 + p) + 1] = std::min(KV_PAGE_TOKENS, len - p * KV_PAGE_TOKENS);
     }
+    tab[pp.o_last + j] = r0 + len - 1;
   }
+  return pp;
+}
+
+// Grows a buffer kept from pass to pass to at least n elements, its contents dropped: device memory (4096 elements at least) or pinned host
+// memory.  The stream drains first, as work in flight may still read the old buffer.
+template <class T>
+static int grow_pass_buffer(aha_model* m, T** buf, size_t* cap, size_t n, bool pinned) {
+  if (n <= *cap) return AHA_OK;
+  AHA_HIP_CHECK(hipStreamSynchronize(m->stream));
+  if (*buf) AHA_HIP_CHECK(pinned ? hipHostFree(*buf) : hipFree(*buf));
+  *buf = nullptr;
+  *cap = 0;
+  const size_t want = pinned ? n : std::max(n, (size_t)4096);
+  const hipError_t e = pinned ? hipHostMalloc((void**)buf, want * sizeof(T)) : hipMalloc((void**)buf, want * sizeof(T));
+  if (e != hipSuccess) {
+    set_error(std::string(pinned ? "hipHostMalloc" : "hipMalloc") + " of a packed pass's buffer failed: " + hipGetErrorString(e));
+    return !pinned && e == hipErrorOutOfMemory ? AHA_ERR_OOM : AHA_ERR_HIP;
+  }
+  *cap = want;
+  return AHA_OK;
+}
+
+// A planned pass up to its last layer: the rows' embeddings gathered from ids (the pass's, packed), the images / videos of vreqs and the
+// audio clips of areqs encoded and scattered to their placeholder rows, the positions' rope table, then packed_layers over the pass pages
+// page_ptrs names.  Leaves the last layer's rows in p_x and the plan's table in p_pass_tab.  The staging buffer is rewritten without a
+// wait: every pass ends in a synchronise (its caller's tail, which needs one for its output anyway), so the previous pass's copies out
+// of it have landed.
+static int run_packed_pass(aha_model* m, const PackedPass& pp, const uint32_t* ids, const uint64_t* page_ptrs,
+                           const std::vector<VisRequest>& vreqs = {}, const std::vector<AudRequest>& areqs = {}) {
+  const aha_model_desc& c = m->desc;
+  const int S = pp.S, H = c.hidden_size, nq = c.num_attention_heads * c.head_dim;
+  hipStream_t st = m->stream;
   int rc;
   if ((rc = ensure_prefill_scratch(m, (size_t)S))) return rc;
   if ((size_t)S > m->pf_cap) {
-    set_error("embed_batch: prefill scratch of " + std::to_string(m->pf_cap) + " rows for a pass of " + std::to_string(S));
+    set_error("packed pass: prefill scratch of " + std::to_string(m->pf_cap) + " rows for a pass of " + std::to_string(S));
     return AHA_ERR_STATE;
   }
-  if ((rc = model_ensure_pages(m, (size_t)npages * KV_PAGE_TOKENS))) return rc;
-  auto grow = [&](auto** buf, size_t* cap, size_t n) -> int {
-    if (n <= *cap) return AHA_OK;
-    AHA_HIP_CHECK(hipStreamSynchronize(st));
-    if (*buf) AHA_HIP_CHECK(hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    const size_t want = std::max(n, (size_t)4096);
-    hipError_t e = hipMalloc((void**)buf, want * sizeof(**buf));
-    if (e != hipSuccess) {
-      set_error(std::string("embed_batch: hipMalloc failed: ") + hipGetErrorString(e));
-      return e == hipErrorOutOfMemory ? AHA_ERR_OOM : AHA_ERR_HIP;
-    }
-    *cap = want;
-    return AHA_OK;
-  };
-  if ((rc = grow(&m->p_seg, &m->p_seg_cap, n_tab))) return rc;
-  if ((rc = grow(&m->p_pool, &m->p_pool_cap, (size_t)n_seg * H))) return rc;
-  // ids | positions | tables through one pinned staging buffer (the previous pass's copies have landed: it ended in a synchronise)
-  const size_t n_stage = 4 * (size_t)S + n_tab;
-  if (n_stage > m->h_embed_stage_cap) {
-    if (m->h_embed_stage) AHA_HIP_CHECK(hipHostFree(m->h_embed_stage));
-    m->h_embed_stage = nullptr;
-    m->h_embed_stage_cap = 0;
-    AHA_HIP_CHECK(hipHostMalloc((void**)&m->h_embed_stage, n_stage * 4));
-    m->h_embed_stage_cap = n_stage;
-  }
-  int32_t* hs = m->h_embed_stage;
+  const size_t n_tab = pp.tab.size(), n_stage = 4 * (size_t)S + n_tab;
+  if ((rc = grow_pass_buffer(m, &m->p_pass_tab, &m->p_pass_tab_cap, n_tab, false)) ||
+      (rc = grow_pass_buffer(m, &m->h_pass_stage, &m->h_pass_stage_cap, n_stage, true)))
+    return rc;
+  int32_t* hs = m->h_pass_stage;   // ids | positions | table
   memcpy(hs, ids, (size_t)S * 4);
-  memcpy(hs + S, pos.data(), pos.size() * 4);
-  memcpy(hs + 4 * (size_t)S, tab.data(), n_tab * 4);
+  memcpy(hs + S, pp.pos.data(), pp.pos.size() * 4);
+  memcpy(hs + 4 * (size_t)S, pp.tab.data(), n_tab * 4);
   GemmWorkspaceScope ws_scope(m->p_gemm_ws, m->gemm_ws_bytes, m->d_sk_ctrs);
   AHA_HIP_CHECK(hipMemcpyAsync(m->p_ids, hs, (size_t)S * 4, hipMemcpyHostToDevice, st));
-  AHA_HIP_CHECK(hipMemcpyAsync(m->p_pos, hs + S, pos.size() * 4, hipMemcpyHostToDevice, st));
-  AHA_HIP_CHECK(hipMemcpyAsync(m->p_seg, hs + 4 * (size_t)S, n_tab * 4, hipMemcpyHostToDevice, st));
-  const int32_t* d_seg = m->p_seg + o_seg;
+  AHA_HIP_CHECK(hipMemcpyAsync(m->p_pos, hs + S, pp.pos.size() * 4, hipMemcpyHostToDevice, st));
+  AHA_HIP_CHECK(hipMemcpyAsync(m->p_pass_tab, hs + 4 * (size_t)S, n_tab * 4, hipMemcpyHostToDevice, st));
   {
     ProfScope ps(m, "elem", (double)S * H * 4, 0);
     launch_embed_gather(m->embed, m->p_ids, m->p_x, S, H, st);
   }
+  // ViT -> masked_scatter of every request's visual rows into its placeholder rows of the pass (qwen3vl/model.rs:1166-1190)
+  if (!vreqs.empty() && (rc = vision_forward_requests(m, vreqs.data(), vreqs.size(), m->p_x))) return rc;
+  // the audio tower over every clip of the pass -> masked_scatter into each request's <|audio_pad|> rows (qwen3_asr/model.rs:343-358)
+  if (!areqs.empty() && (rc = audio_forward_requests(m, areqs.data(), areqs.size(), m->p_x))) return rc;
   launch_rope_table(m->p_pos, S, m->d_inv_freq, m->d_axis_map, S, m->p_rope, st);   // the packed rows' cos / sin, once for all layers
   double attn_flops = 0;
-  for (int j = 0; j < n_seg; ++j) attn_flops += 4.0 * seg[3 * j + 1] * (0.5 * seg[3 * j + 1]) * nq;
-  if ((rc = packed_layers(m, S, m->d_page_ptrs, d_seg, m->p_seg + o_items, n_items, m->p_seg + o_slot, m->p_seg + o_prow, npages, attn_flops)))
+  for (int j = 0; j < pp.n_seg; ++j) attn_flops += 4.0 * pp.tab[3 * j + 1] * (0.5 * pp.tab[3 * j + 1]) * nq;
+  const int32_t* t = m->p_pass_tab;
+  return packed_layers(m, S, page_ptrs, t, t + pp.o_items, pp.n_items, t + pp.o_slot, t + pp.o_prow, pp.npages, attn_flops, !vreqs.empty());
+}
+
+static int embed_pass(aha_model* m, const uint32_t* ids, const size_t* lens, int n_seg, float* out) {
+  const aha_model_desc& c = m->desc;
+  const int H = c.hidden_size;
+  hipStream_t st = m->stream;
+  // the pass's pages are logical pages 0 .. npages - 1 (a pass reuses the previous one's): m->d_page_ptrs is its page table
+  std::vector<int64_t> page0(n_seg);
+  for (int j = 0, p = 0; j < n_seg; p += (int)((lens[j] + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS), ++j) page0[j] = p;
+  const PackedPass pp = plan_packed_pass(lens, n_seg, page0.data(), nullptr);
+  int rc;
+  if ((rc = model_ensure_pages(m, (size_t)pp.npages * KV_PAGE_TOKENS)) ||
+      (rc = grow_pass_buffer(m, &m->p_pool, &m->p_pool_cap, (size_t)n_seg * H, false)) || (rc = run_packed_pass(m, pp, ids, m->d_page_ptrs)))
     return rc;
   {
     ProfScope ps(m, "elem", (double)n_seg * H * 2 + (double)n_seg * H * 4, 0);
-    launch_embed_pool(m->p_x, d_seg, n_seg, m->final_norm, m->p_pool, H, c.rms_norm_eps, st);
+    launch_embed_pool(m->p_x, m->p_pass_tab, n_seg, m->final_norm, m->p_pool, H, c.rms_norm_eps, st);
   }
   AHA_HIP_CHECK(hipGetLastError());
   AHA_HIP_CHECK(hipMemcpyAsync(out, m->p_pool, (size_t)n_seg * H * 4, hipMemcpyDeviceToHost, st));
@@ -2071,44 +2154,13 @@ int model_embed_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens,
     set_error("embed_batch: a single-GPU model with head_dim 128 only (no tensor / context parallelism)");
     return AHA_ERR_UNSUPPORTED;
   }
-  size_t total = 0;
-  for (size_t j = 0; j < n_seqs; ++j) {
-    if (seq_lens[j] == 0) {
-      set_error("embed_batch: empty input_ids of sequence " + std::to_string(j));
-      return AHA_ERR_INVALID;
-    }
-    if (seq_lens[j] > (size_t)1 << 24) {
-      set_error("embed_batch: sequence " + std::to_string(j) + " is longer than 2^24 tokens");
-      return AHA_ERR_INVALID;
-    }
-    for (size_t i = 0; i < seq_lens[j]; ++i)
-      if (ids[total + i] >= (uint32_t)c.vocab_size) {
-        set_error("token id out of range in sequence " + std::to_string(j) + " at position " + std::to_string(i));
-        return AHA_ERR_INVALID;
-      }
-    total += seq_lens[j];
-  }
-  AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
-  int rc = model_clear_cache(m);
+  int rc = check_batch_ids(c, "embed_batch", ids, seq_lens, n_seqs, 0);
   if (rc) return rc;
-  struct ClearGuard {   // the cache is empty afterwards, on success and on error alike (qwen3_embedding/mod.rs:58)
-    aha_model* m;
-    ~ClearGuard() { model_clear_cache(m); }
-  } guard{m};
-  const size_t budget = std::min(max_tokens_per_pass ? max_tokens_per_pass : EMBED_PASS_ROWS, (size_t)1 << 24);
-  const size_t H = (size_t)c.hidden_size;
-  size_t j = 0, off = 0;
-  while (j < n_seqs) {
-    size_t rows = 0, slots = 0, k = j;
-    while (k < n_seqs) {
-      const size_t len = seq_lens[k], sl = (len + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS * KV_PAGE_TOKENS;
-      if (k > j && (rows + len > budget || slots + sl > 2 * budget)) break;
-      rows += len, slots += sl, ++k;
-    }
-    if ((rc = embed_pass(m, ids + off, seq_lens + j, (int)(k - j), out + j * H))) return rc;
-    off += rows;
-    j = k;
-  }
+  AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
+  if ((rc = model_clear_cache(m))) return rc;
+  ClearCacheGuard guard{m};
+  for (const PassRange& p : split_passes(seq_lens, n_seqs, max_tokens_per_pass))
+    if ((rc = embed_pass(m, ids + p.off, seq_lens + p.j, (int)(p.k - p.j), out + p.j * c.hidden_size))) return rc;
   return AHA_OK;
 }
 
@@ -2183,6 +2235,13 @@ struct GenCall {
   int32_t* rowtab = nullptr;
   unsigned* ctr = nullptr;
   uint64_t* pass_pages = nullptr;
+  int32_t* h_rowtab = nullptr;   // pinned
+  uint32_t* h_tok = nullptr;     // pinned: a step's tokens
+  // the caller's outputs: per sequence max_new entries of tokens_out (n_out of them written) and of step_logits_out (V floats each)
+  size_t max_new = 0;
+  uint32_t* tokens_out = nullptr;
+  size_t* n_out = nullptr;
+  float* step_logits_out = nullptr;
 };
 
 // final RMSNorm + lm_head + argmax of `rows` rows of gc.x (bf16, pitch H) -> logits rows / token vector entries from `row0` on
@@ -2205,115 +2264,297 @@ static void gen_head(aha_model* m, GenCall& gc, int row0, int rows, uint32_t* to
 
 // One packed prefill pass over sequences j0 .. j0+n_seg-1 (ids: theirs, packed); sequence j's cache starts on logical page page0[j].
 // Positions: sequence j's three M-RoPE rows pos3[j] (3 x len, get_rope_index at offset 0) when it has them, else arange; mm[j] (may be
-// null, or all null): its images / videos, encoded for the whole pass in one tower pass and scattered to its placeholder rows.
+// null, or all null): its images / videos or its audio clip, encoded for the whole pass in one tower pass and scattered to its placeholder
+// rows.  Then every sequence's last row through the head -> its first token in token vector 0.
 static int generate_prefill_pass(aha_model* m, GenCall& gc, const uint32_t* ids, const size_t* lens, int j0, int n_seg,
                                  const std::vector<int64_t>& page0, const std::vector<std::vector<int32_t>>& pos3,
                                  const aha_mm_input* const* mm) {
-  const aha_model_desc& c = m->desc;
-  const int H = c.hidden_size, nq = c.num_attention_heads * c.head_dim;
+  const int H = m->desc.hidden_size;
   hipStream_t st = m->stream;
-  // plan as in embed_pass, but the pass's pages are a table of their own: pass page p = the sequence's logical page, so its decode pages
-  // (not written here) never appear in the rope kernel's page list
-  std::vector<int32_t> seg(3 * (size_t)n_seg);
-  std::vector<uint64_t> pages;
-  int S = 0;
-  for (int j = 0; j < n_seg; ++j) {
-    const int len = (int)lens[j];
-    seg[3 * j] = S, seg[3 * j + 1] = len, seg[3 * j + 2] = (int32_t)pages.size();
-    for (int p = 0; p * KV_PAGE_TOKENS < len; ++p) pages.push_back(m->h_page_ptrs[(size_t)page0[j0 + j] + p]);
-    S += len;
-  }
-  const int npages = (int)pages.size();
-  constexpr int QB = 64;
-  std::vector<std::pair<int, int>> items;
-  for (int j = 0; j < n_seg; ++j)
-    for (int b = 0; b * QB < seg[3 * j + 1]; ++b) items.emplace_back(j, b);
-  auto cost = [&](const std::pair<int, int>& it) { return std::min(seg[3 * it.first + 1], (it.second + 1) * QB); };
-  std::stable_sort(items.begin(), items.end(), [&](const auto& x, const auto& y) { return cost(x) > cost(y); });
-  const int n_items = (int)items.size();
-  const size_t o_seg = 0, o_items = o_seg + seg.size(), o_slot = o_items + 2 * (size_t)n_items, o_prow = o_slot + S,
-               o_last = o_prow + 2 * (size_t)npages, n_tab = o_last + n_seg;
-  std::vector<int32_t> tab(n_tab);
-  std::copy(seg.begin(), seg.end(), tab.begin());
-  for (int i = 0; i < n_items; ++i) tab[o_items + 2 * i] = items[i].first, tab[o_items + 2 * i + 1] = items[i].second;
-  std::vector<int32_t> pos(3 * (size_t)S);
-  for (int j = 0; j < n_seg; ++j) {
-    const int r0 = seg[3 * j], len = seg[3 * j + 1], p0 = seg[3 * j + 2];
-    const std::vector<int32_t>& pj = pos3[(size_t)(j0 + j)];
-    for (int i = 0; i < len; ++i) {
-      tab[o_slot + r0 + i] = p0 * KV_PAGE_TOKENS + i;
-      for (int a = 0; a < 3; ++a) pos[(size_t)a * S + r0 + i] = pj.empty() ? i : pj[(size_t)a * len + i];
-    }
-    for (int p = 0; p * KV_PAGE_TOKENS < len; ++p) {
-      tab[o_prow + 2 * (size_t)(p0 + p)] = r0 + p * KV_PAGE_TOKENS;
-      tab[o_prow + 2 * (size_t)(p0 + p) + 1] = std::min(KV_PAGE_TOKENS, len - p * KV_PAGE_TOKENS);
-    }
-    tab[o_last + j] = r0 + len - 1;
-  }
+  const PackedPass pp = plan_packed_pass(lens, n_seg, page0.data() + j0, pos3.data() + j0);
   std::vector<VisRequest> vreqs;   // the pass's requests with images / videos, at their first packed row
+  std::vector<AudRequest> areqs;   // the pass's requests with an audio clip (check_mm_requests checked both kinds)
   for (int j = 0; j < n_seg && mm; ++j) {
     const aha_mm_input* q = mm[j0 + j];
-    if (q && (q->n_images > 0 || q->n_videos > 0)) vreqs.push_back(VisRequest{q, ids + seg[3 * j], lens[j], seg[3 * j], j0 + j});
+    const int r0 = pp.tab[3 * j];
+    if (q && (q->n_images > 0 || q->n_videos > 0)) vreqs.push_back(VisRequest{q, ids + r0, lens[j], r0, j0 + j});
+    else if (q && m->audio) areqs.push_back(AudRequest{q, ids + r0, lens[j], r0, j0 + j});
   }
-  std::vector<AudRequest> areqs;   // the pass's requests with an audio clip (generate_batch_impl checked them)
-  for (int j = 0; j < n_seg && mm && m->audio; ++j) {
-    const aha_mm_input* q = mm[j0 + j];
-    if (q && q->n_images <= 0 && q->n_videos <= 0)
-      areqs.push_back(AudRequest{q, ids + seg[3 * j], lens[j], seg[3 * j], j0 + j});
-  }
-  int rc;
-  if ((rc = ensure_prefill_scratch(m, (size_t)S))) return rc;
-  if (m->p_seg_cap < n_tab) {
-    AHA_HIP_CHECK(hipStreamSynchronize(st));
-    if (m->p_seg) AHA_HIP_CHECK(hipFree(m->p_seg));
-    m->p_seg = nullptr;
-    m->p_seg_cap = 0;
-    const size_t want = std::max(n_tab, (size_t)4096);
-    hipError_t e = hipMalloc((void**)&m->p_seg, want * 4);
-    if (e != hipSuccess) {
-      set_error(std::string("generate_batch: hipMalloc failed: ") + hipGetErrorString(e));
-      return e == hipErrorOutOfMemory ? AHA_ERR_OOM : AHA_ERR_HIP;
-    }
-    m->p_seg_cap = want;
-  }
-  AHA_HIP_CHECK(hipStreamSynchronize(st));   // the previous pass's copies out of the staging buffer have landed
-  const size_t n_stage = 4 * (size_t)S + n_tab;
-  if (n_stage > m->h_embed_stage_cap) {
-    if (m->h_embed_stage) AHA_HIP_CHECK(hipHostFree(m->h_embed_stage));
-    m->h_embed_stage = nullptr;
-    m->h_embed_stage_cap = 0;
-    AHA_HIP_CHECK(hipHostMalloc((void**)&m->h_embed_stage, n_stage * 4));
-    m->h_embed_stage_cap = n_stage;
-  }
-  int32_t* hs = m->h_embed_stage;
-  memcpy(hs, ids, (size_t)S * 4);
-  memcpy(hs + S, pos.data(), pos.size() * 4);
-  memcpy(hs + 4 * (size_t)S, tab.data(), n_tab * 4);
-  GemmWorkspaceScope ws_scope(m->p_gemm_ws, m->gemm_ws_bytes, m->d_sk_ctrs);
-  AHA_HIP_CHECK(hipMemcpyAsync(m->p_ids, hs, (size_t)S * 4, hipMemcpyHostToDevice, st));
-  AHA_HIP_CHECK(hipMemcpyAsync(m->p_pos, hs + S, pos.size() * 4, hipMemcpyHostToDevice, st));
-  AHA_HIP_CHECK(hipMemcpyAsync(m->p_seg, hs + 4 * (size_t)S, n_tab * 4, hipMemcpyHostToDevice, st));
+  // the pass's pages are a table of their own: pass page p = the sequence's logical page, so its decode pages (not written here) never
+  // appear in the rope kernel's page list.  The previous pass ended in a synchronise: the table is free.
+  std::vector<uint64_t> pages(pp.pages.size());
+  for (size_t p = 0; p < pages.size(); ++p) pages[p] = m->h_page_ptrs[(size_t)pp.pages[p]];
   AHA_HIP_CHECK(hipMemcpy(gc.pass_pages, pages.data(), pages.size() * 8, hipMemcpyHostToDevice));
-  {
-    ProfScope ps(m, "elem", (double)S * H * 4, 0);
-    launch_embed_gather(m->embed, m->p_ids, m->p_x, S, H, st);
-  }
-  // ViT -> masked_scatter of every request's visual rows into its placeholder rows of the pass (qwen3vl/model.rs:1166-1190)
-  if (!vreqs.empty() && (rc = vision_forward_requests(m, vreqs.data(), vreqs.size(), m->p_x))) return rc;
-  // the audio tower over every clip of the pass -> masked_scatter into each request's <|audio_pad|> rows (qwen3_asr/model.rs:343-358)
-  if (!areqs.empty() && (rc = audio_forward_requests(m, areqs.data(), areqs.size(), m->p_x))) return rc;
-  launch_rope_table(m->p_pos, S, m->d_inv_freq, m->d_axis_map, S, m->p_rope, st);
-  double attn_flops = 0;
-  for (int j = 0; j < n_seg; ++j) attn_flops += 4.0 * seg[3 * j + 1] * (0.5 * seg[3 * j + 1]) * nq;
-  if ((rc = packed_layers(m, S, gc.pass_pages, m->p_seg + o_seg, m->p_seg + o_items, n_items, m->p_seg + o_slot, m->p_seg + o_prow, npages,
-                          attn_flops, !vreqs.empty())))
-    return rc;
+  int rc;
+  if ((rc = run_packed_pass(m, pp, ids, gc.pass_pages, vreqs, areqs))) return rc;
   // every sequence's last row -> gc.x row j0 + j, then the head -> first tokens into token vector 0
-  launch_embed_gather(m->p_x, reinterpret_cast<const uint32_t*>(m->p_seg + o_last), (bf16_t*)gc.x + (int64_t)j0 * H, n_seg, H, st);
+  launch_embed_gather(m->p_x, reinterpret_cast<const uint32_t*>(m->p_pass_tab + pp.o_last), (bf16_t*)gc.x + (int64_t)j0 * H, n_seg, H, st);
   gen_head(m, gc, j0, n_seg, gc.tok[0]);
   AHA_HIP_CHECK(hipGetLastError());
   AHA_HIP_CHECK(hipStreamSynchronize(st));   // the pass page table and the staging buffer are reused by the next pass
   return AHA_OK;
+}
+
+// generate_batch_mm's requests, every check of the towers and of get_rope_index before any device work; positions (3, len) and
+// rope_delta of each request with images / videos (a text request: arange, delta 0)
+static int check_mm_requests(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
+                             std::vector<std::vector<int32_t>>& pos3, std::vector<int64_t>& rope_delta) {
+  const aha_model_desc& c = m->desc;
+  int rc;
+  size_t off = 0;
+  for (size_t j = 0; j < n_seqs; off += seq_lens[j], ++j) {
+    const aha_mm_input* q = mm[j];
+    if (!q) continue;
+    const std::string who = "generate_batch_mm: sequence " + std::to_string(j) + ": ";
+    if (q->image_embeds) {
+      set_error(who + "precomputed image_embeds are not supported in batches (pixel values only)");
+      return AHA_ERR_UNSUPPORTED;
+    }
+    const bool has_img = q->n_images > 0, has_vid = q->n_videos > 0;
+    if (((q->audio_features && q->n_frames > 0) || (q->audio_samples && q->n_samples > 0)) && (c.arch != AHA_ARCH_QWEN3ASR || !m->audio)) {
+      set_error(who + "audio input given but this model has no audio tower");
+      return AHA_ERR_UNSUPPORTED;
+    }
+    // on a Qwen3-ASR model every entry without images / videos is an audio request: the tower's own checks (samples or features, the
+    // placeholder count)
+    if (!has_img && !has_vid && c.arch == AHA_ARCH_QWEN3ASR && m->audio) {
+      const AudRequest r{q, ids + off, seq_lens[j], 0, (int)j};
+      if ((rc = audio_check_requests(m, &r, 1))) return rc;
+      continue;
+    }
+    if (!has_img && !has_vid) continue;
+    if (c.arch != AHA_ARCH_QWEN3VL || !m->vision) {
+      set_error(who + "image input given but this model has no vision tower (arch / model.visual.* weights)");
+      return AHA_ERR_UNSUPPORTED;
+    }
+    int64_t n_img, n_vid;
+    if ((rc = vision_check_request(c, VisRequest{q, ids + off, seq_lens[j], 0, (int)j}, &n_img, &n_vid))) return rc;
+    pos3[j].resize(3 * seq_lens[j]);
+    if ((rc = rope_index_core(c, ids + off, seq_lens[j], q->image_grid_thw, has_img ? q->n_images : 0, q->video_grid_thw,
+                              has_vid ? q->n_videos : 0, pos3[j].data(), &rope_delta[j]))) {
+      set_error(who + last_error_cstr());
+      return rc;
+    }
+  }
+  return AHA_OK;
+}
+
+// The call's device buffers (decode rows, logits, token vectors, attention partials, the pass page table) and pinned row table / tokens
+static int gen_call_alloc(aha_model* m, DevBufs& bufs, GenCall& gc, const size_t* seq_lens) {
+  const aha_model_desc& c = m->desc;
+  const int n = gc.n, H = gc.H, V = gc.V, I = c.intermediate_size, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
+  const int nq = nh * 128, nkv = kvh * 128;
+  for (int j = 0; j < n; ++j)
+    gc.max_nsplit = std::max(gc.max_nsplit, attn_decode_nsplit((int)(seq_lens[j] + gc.max_new), nh / kvh, m->max_nsplit));
+  size_t ws = 0;
+  const int shapes[5][2] = {{nq + 2 * nkv, H}, {H, nq}, {2 * I, H}, {H, I}, {V, H}};
+  for (auto& sh : shapes) ws = std::max(ws, gemv_rows_ws_floats(std::min(n, GEN_ROW_GROUP), sh[0], sh[1]));
+  const int tiles = gemv_rows_num_tiles(V);
+  size_t max_pass_pages = 0;
+  for (int j = 0; j < n; ++j) max_pass_pages += (seq_lens[j] + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
+  int rc;
+  if ((rc = bufs.alloc(&gc.ws, ws)) || (rc = bufs.alloc((bf16_t**)&gc.x, (size_t)n * H)) || (rc = bufs.alloc((bf16_t**)&gc.h, (size_t)n * H)) ||
+      (rc = bufs.alloc((bf16_t**)&gc.qkv, (size_t)n * (nq + 2 * nkv))) || (rc = bufs.alloc((bf16_t**)&gc.attn, (size_t)n * nq)) ||
+      (rc = bufs.alloc((bf16_t**)&gc.act, (size_t)n * I)) || (rc = bufs.alloc(&gc.rope, (size_t)n * 128)) ||
+      (rc = bufs.alloc(&gc.logits, (size_t)n * V)) || (rc = bufs.alloc(&gc.blk_max, (size_t)n * tiles)) ||
+      (rc = bufs.alloc(&gc.blk_idx, (size_t)n * tiles)) || (rc = bufs.alloc(&gc.tok[0], (size_t)n)) || (rc = bufs.alloc(&gc.tok[1], (size_t)n)) ||
+      (rc = bufs.alloc(&gc.rowtab, (size_t)n * GEN_ROW_WORDS)) || (rc = bufs.alloc(&gc.ctr, (size_t)n * kvh * 32, true)) ||
+      (rc = bufs.alloc(&gc.part_o, (size_t)n * gc.max_nsplit * nq)) || (rc = bufs.alloc(&gc.part_ml, (size_t)n * gc.max_nsplit * nh * 2)) ||
+      (rc = bufs.alloc(&gc.pass_pages, max_pass_pages)) || (rc = bufs.alloc_host(&gc.h_rowtab, (size_t)n * GEN_ROW_WORDS)) ||
+      (rc = bufs.alloc_host(&gc.h_tok, (size_t)n)))
+    return rc;
+  return AHA_OK;
+}
+
+// Sampled generation: one sampler per sequence and the candidate step's buffers (no samplers: greedy)
+struct GenChoice {
+  std::vector<HostSampler> samplers;
+  int nw = 0;   // sample_stage1_waves(V)
+  int32_t *d_stab = nullptr, *h_stab = nullptr;
+  uint32_t *d_sctx = nullptr, *h_sctx = nullptr, *d_cidx = nullptr;
+  float *d_cval = nullptr, *d_part = nullptr, *d_sout = nullptr, *h_sout = nullptr, *h_fb = nullptr;
+  std::vector<int> mode, slot, fb_rows;   // finish_step's per-row scratch
+};
+
+static int gen_choice_init(DevBufs& bufs, const GenCall& gc, const aha_sampling_params* params, GenChoice& ch) {
+  const int n = gc.n, V = gc.V;
+  if (!sample_shape_ok(V, 64)) {
+    set_error("generate_batch_sampled: vocabulary too large for the candidate step");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  ch.samplers.resize(n);
+  ch.nw = sample_stage1_waves(V);
+  size_t ctx_cap = 0, n_fb = 0;
+  int rc;
+  for (int j = 0; j < n; ++j) {
+    if ((rc = host_sampler_init(ch.samplers[j], params[j]))) return rc;
+    const HostSampler& S = ch.samplers[j];
+    if (S.repeat_penalty != 1.0f) ctx_cap += std::min<size_t>(gc.max_new, (size_t)S.repeat_last_n);
+    // a sequence that may need its full logits row: Sampling::All, oversized k, any TopP (nucleus wider than the candidates)
+    if (S.kind != SAMPLE_ARGMAX && (S.kind == SAMPLE_TOPP || sampler_candidates_needed(S, (size_t)V) == 0)) ++n_fb;
+  }
+  const size_t cand = (size_t)n * (ch.nw + 16) * 64;
+  if ((rc = bufs.alloc(&ch.d_stab, (size_t)n * SAMPLE_ROW_WORDS)) || (rc = bufs.alloc(&ch.d_sctx, ctx_cap)) || (rc = bufs.alloc(&ch.d_cval, cand)) ||
+      (rc = bufs.alloc(&ch.d_cidx, cand)) || (rc = bufs.alloc(&ch.d_part, 2 * (size_t)n * ch.nw)) ||
+      (rc = bufs.alloc(&ch.d_sout, (size_t)n * SAMPLE_OUT_WORDS)) || (rc = bufs.alloc_host(&ch.h_stab, (size_t)n * SAMPLE_ROW_WORDS)) ||
+      (rc = bufs.alloc_host(&ch.h_sctx, ctx_cap)) || (rc = bufs.alloc_host(&ch.h_sout, (size_t)n * SAMPLE_OUT_WORDS)) ||
+      (rc = bufs.alloc_host(&ch.h_fb, n_fb * (size_t)V)))
+    return rc;
+  return AHA_OK;
+}
+
+// The end of every step (the prefill's first tokens, then each decode step): the tokens of rows r = 0 .. R-1 (row r = sequence seqs[r])
+// into gc.h_tok, from the device argmax vector `tok_dev` the head wrote.  Greedy: one copy and one sync.  Sampled: before that sync, one
+// candidate step over every row that samples (its penalty context uploaded with it) and the candidates' copy; after it the host picks,
+// a second sync only for rows whose candidates cannot decide (their logits rows come down), and the picked tokens go back up into
+// tok_dev for the next step's embedding gather.  gc.step_logits_out (greedy or sampled): every step's logits.
+static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::vector<int>& seqs, uint32_t* tok_dev) {
+  hipStream_t st = m->stream;
+  const int R = (int)seqs.size(), V = gc.V;
+  const bool sampled = !ch.samplers.empty();
+  const size_t max_new = gc.max_new;
+  uint32_t* h_tok = gc.h_tok;
+  enum { GREEDY, CAND, FULL };
+  int ns = 0;
+  if (sampled) {
+    ch.mode.assign(R, GREEDY);
+    ch.slot.assign(R, -1);
+    size_t nc = 0;
+    for (int r = 0; r < R; ++r) {
+      const int j = seqs[r];
+      const HostSampler& S = ch.samplers[j];
+      float pen;
+      size_t n_ctx;
+      sampler_penalty_context(S, gc.n_out[j], &pen, &n_ctx);
+      if (S.kind == SAMPLE_ARGMAX && pen == 1.0f) continue;   // the device argmax is the token
+      const int k = S.kind == SAMPLE_ARGMAX ? 1 : sampler_candidates_needed(S, (size_t)V);
+      if (!k) {
+        ch.mode[r] = FULL;
+        continue;
+      }
+      ch.mode[r] = CAND;
+      ch.slot[r] = ns;
+      int32_t* t = ch.h_stab + (size_t)ns * SAMPLE_ROW_WORDS;
+      // `&logits / temperature`: 1/T computed in f64, applied in f32 (as model_sample_candidates; ArgMax: T treated as 1)
+      const float inv_t = S.kind == SAMPLE_ARGMAX ? 1.0f : (float)(1.0 / (double)(float)S.temperature);
+      const size_t c0 = nc;
+      if (pen != 1.0f) {   // the distinct in-vocabulary ids of the last n_ctx generated (apply_repeat_penalty's HashSet)
+        const uint32_t* g = gc.tokens_out + (size_t)j * max_new + gc.n_out[j] - n_ctx;
+        for (size_t i = 0; i < n_ctx; ++i)
+          if (g[i] < (uint32_t)V) ch.h_sctx[nc++] = g[i];
+        std::sort(ch.h_sctx + c0, ch.h_sctx + nc);
+        nc = (size_t)(std::unique(ch.h_sctx + c0, ch.h_sctx + nc) - ch.h_sctx);
+      }
+      t[SAMPLE_ROW_LROW] = r;
+      t[SAMPLE_ROW_K] = k;
+      memcpy(&t[SAMPLE_ROW_INVT], &inv_t, 4);
+      memcpy(&t[SAMPLE_ROW_PEN], &pen, 4);
+      t[SAMPLE_ROW_CTX0] = (int32_t)c0;
+      t[SAMPLE_ROW_NCTX] = (int32_t)(nc - c0);
+      t[6] = t[7] = 0;
+      ++ns;
+    }
+    if (ns) {
+      AHA_HIP_CHECK(hipMemcpyAsync(ch.d_stab, ch.h_stab, (size_t)ns * SAMPLE_ROW_WORDS * 4, hipMemcpyHostToDevice, st));
+      if (nc) AHA_HIP_CHECK(hipMemcpyAsync(ch.d_sctx, ch.h_sctx, nc * 4, hipMemcpyHostToDevice, st));
+      const char* names[3] = {"sample_rows_stage1", "sample_rows_stage2a", "sample_rows_stage2b"};
+      for (int stage = 0; stage < 3; ++stage) {
+        ProfScope ps(m, names[stage], stage == 0 ? (double)ns * V * 4 : 0, 0);
+        launch_topk_rows(gc.logits, V, V, ns, ch.d_stab, ch.d_sctx, ch.d_cval, ch.d_cidx, ch.d_part, ch.d_part + (size_t)gc.n * ch.nw, ch.d_sout,
+                         stage, st);
+      }
+      AHA_HIP_CHECK(hipGetLastError());
+      AHA_HIP_CHECK(hipMemcpyAsync(ch.h_sout, ch.d_sout, (size_t)ns * SAMPLE_OUT_WORDS * 4, hipMemcpyDeviceToHost, st));
+    }
+  }
+  if (gc.step_logits_out)
+    for (int r = 0; r < R; ++r)
+      AHA_HIP_CHECK(hipMemcpyAsync(gc.step_logits_out + ((size_t)seqs[r] * max_new + gc.n_out[seqs[r]]) * V, gc.logits + (size_t)r * V,
+                                   (size_t)V * 4, hipMemcpyDeviceToHost, st));
+  AHA_HIP_CHECK(hipMemcpyAsync(h_tok, tok_dev, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+  AHA_HIP_CHECK(hipStreamSynchronize(st));
+  if (!sampled) return AHA_OK;
+  ch.fb_rows.clear();
+  for (int r = 0; r < R; ++r) {
+    if (ch.mode[r] == GREEDY) continue;
+    const int j = seqs[r];
+    if (ch.mode[r] == CAND) {
+      const float* o = ch.h_sout + (size_t)ch.slot[r] * SAMPLE_OUT_WORDS;
+      const int k = ch.h_stab[(size_t)ch.slot[r] * SAMPLE_ROW_WORDS + SAMPLE_ROW_K];
+      const int prc = sampler_pick(ch.samplers[j], o, reinterpret_cast<const uint32_t*>(o + 66), k, o[64], o[65], nullptr, (size_t)V,
+                                   gc.tokens_out + (size_t)j * max_new, gc.n_out[j], &h_tok[r]);
+      if (prc < 0) return prc;
+      if (prc == AHA_OK) continue;
+    }
+    ch.fb_rows.push_back(r);
+  }
+  if (!ch.fb_rows.empty()) {   // rows whose candidates cannot decide: their full logits rows, one more sync
+    for (size_t f = 0; f < ch.fb_rows.size(); ++f)
+      AHA_HIP_CHECK(hipMemcpyAsync(ch.h_fb + f * V, gc.logits + (size_t)ch.fb_rows[f] * V, (size_t)V * 4, hipMemcpyDeviceToHost, st));
+    AHA_HIP_CHECK(hipStreamSynchronize(st));
+    for (size_t f = 0; f < ch.fb_rows.size(); ++f) {
+      const int r = ch.fb_rows[f], j = seqs[r];
+      const int prc = sampler_pick(ch.samplers[j], nullptr, nullptr, 0, 0.f, 0.f, ch.h_fb + f * V, (size_t)V, gc.tokens_out + (size_t)j * max_new,
+                                   gc.n_out[j], &h_tok[r]);
+      if (prc != AHA_OK) return prc < 0 ? prc : AHA_ERR_STATE;
+    }
+  }
+  AHA_HIP_CHECK(hipMemcpyAsync(tok_dev, h_tok, (size_t)R * 4, hipMemcpyHostToDevice, st));
+  return AHA_OK;
+}
+
+// One decode step's device work over the R rows of the uploaded row table gc.rowtab: the tokens tok_in embedded (with their rope rows),
+// every layer, then the head -> tok_out.  kv_tokens: the rows' cache lengths summed (the profile's bytes); max_split: their largest split.
+static void gen_decode_step(aha_model* m, GenCall& gc, int R, int max_split, double kv_tokens, const uint32_t* tok_in, uint32_t* tok_out) {
+  const aha_model_desc& c = m->desc;
+  hipStream_t st = m->stream;
+  const int H = c.hidden_size, I = c.intermediate_size, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
+  const int nq = nh * 128, nkv = kvh * 128;
+  {
+    ProfScope ps(m, "elem", (double)R * H * 4, 0);
+    launch_gen_embed(m->embed, tok_in, gc.rowtab, R, gc.x, H, m->d_inv_freq, m->d_axis_map, gc.rope, st);
+  }
+  for (int li = 0; li < c.num_hidden_layers; ++li) {
+    const LayerWeights& Lw = m->layers[li];
+    {   // h = RMSNorm(x); qkv = h Wqkv^T                      (qwen3/model.rs:79, modules.rs:538-552)
+      {
+        ProfScope ps(m, "elem", (double)R * H * 4, 0);
+        launch_rmsnorm_rows(gc.x, Lw.in_norm, gc.h, R, H, H, H, c.rms_norm_eps, st);
+      }
+      GemvRowsArgs a{};
+      a.W = Lw.wqkv; a.x = gc.h; a.ldx = H; a.y = gc.qkv; a.ldy = nq + 2 * nkv; a.N = nq + 2 * nkv; a.K = H;
+      gemv_rows_groups(m, a, GEMV_STORE, R, gc.ws);
+    }
+    {   // q/k norm + rope + KV append + attention of every row over its own pages (modules.rs:544-574, 757-813)
+      AttnDecodeBatchArgs b{};
+      b.qkv = gc.qkv; b.q_norm_w = Lw.q_norm; b.k_norm_w = Lw.k_norm; b.rope = gc.rope; b.page_ptrs = m->d_page_ptrs;
+      b.layer_off = (uint64_t)li * m->layer_stride; b.row_tab = gc.rowtab; b.part_o = gc.part_o; b.part_ml = gc.part_ml; b.o = gc.attn;
+      b.head_ctr = gc.ctr; b.ctr_step = li + 1; b.nh = nh; b.kvh = kvh; b.max_nsplit = gc.max_nsplit; b.eps = c.rms_norm_eps;
+      b.scale = m->attn_scale;
+      ProfScope ps(m, "attn_decode_batch", kv_tokens * 2 * nkv * 2 + (double)R * (nq + 2 * nkv) * 2, 4.0 * kv_tokens * nq);
+      launch_attn_decode_batch(b, R, max_split, st);
+    }
+    {   // x = x + attn Wo^T                                    (modules.rs:577, qwen3/model.rs:81)
+      GemvRowsArgs a{};
+      a.W = Lw.wo; a.x = gc.attn; a.ldx = nq; a.residual = gc.x; a.y = gc.x; a.ldy = H; a.N = H; a.K = nq;
+      gemv_rows_groups(m, a, GEMV_RESIDUAL, R, gc.ws);
+    }
+    {   // act = silu(h Wg^T) * (h Wu^T), h = RMSNorm(x)        (qwen3/model.rs:83, modules.rs:81-84)
+      {
+        ProfScope ps(m, "elem", (double)R * H * 4, 0);
+        launch_rmsnorm_rows(gc.x, Lw.post_norm, gc.h, R, H, H, H, c.rms_norm_eps, st);
+      }
+      GemvRowsArgs a{};
+      a.W = Lw.wgu; a.x = gc.h; a.ldx = H; a.y = gc.act; a.ldy = I; a.N = 2 * I; a.K = H;
+      gemv_rows_groups(m, a, GEMV_SILU_MUL, R, gc.ws);
+    }
+    {   // x = x + act Wd^T                                     (modules.rs:85, qwen3/model.rs:86)
+      GemvRowsArgs a{};
+      a.W = Lw.wdown; a.x = gc.act; a.ldx = I; a.residual = gc.x; a.y = gc.x; a.ldy = H; a.N = H; a.K = I;
+      gemv_rows_groups(m, a, GEMV_RESIDUAL, R, gc.ws);
+    }
+  }
+  gen_head(m, gc, 0, R, tok_out);
 }
 
 // params == nullptr: greedy (aha_hip_generate_batch: logits_out = each sequence's last logits).  Otherwise one sampler per sequence
@@ -2350,108 +2591,16 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
     set_error("generate_batch: at most 2^20 sequences and 2^20 new tokens");
     return AHA_ERR_INVALID;
   }
-  size_t total = 0;
-  for (size_t j = 0; j < n_seqs; ++j) {
-    if (seq_lens[j] == 0) {
-      set_error("generate_batch: empty input_ids of sequence " + std::to_string(j));
-      return AHA_ERR_INVALID;
-    }
-    if (seq_lens[j] + max_new > (size_t)1 << 24) {
-      set_error("generate_batch: sequence " + std::to_string(j) + " would grow past 2^24 tokens");
-      return AHA_ERR_INVALID;
-    }
-    for (size_t i = 0; i < seq_lens[j]; ++i)
-      if (ids[total + i] >= (uint32_t)c.vocab_size) {
-        set_error("token id out of range in sequence " + std::to_string(j) + " at position " + std::to_string(i));
-        return AHA_ERR_INVALID;
-      }
-    total += seq_lens[j];
-  }
-  // Qwen3-VL requests: every check of the tower and of get_rope_index here, before any device work; positions (3, len) and rope_delta
-  // of each request with images / videos (a text request: arange, delta 0)
+  int rc = check_batch_ids(c, "generate_batch", ids, seq_lens, n_seqs, max_new);
+  if (rc) return rc;
   std::vector<std::vector<int32_t>> pos3(n_seqs);
   std::vector<int64_t> rope_delta(n_seqs, 0);
-  int rc = AHA_OK;
-  if (mm) {
-    size_t off = 0;
-    for (size_t j = 0; j < n_seqs; off += seq_lens[j], ++j) {
-      const aha_mm_input* q = mm[j];
-      if (!q) continue;
-      const std::string who = "generate_batch_mm: sequence " + std::to_string(j) + ": ";
-      if (q->image_embeds) {
-        set_error(who + "precomputed image_embeds are not supported in batches (pixel values only)");
-        return AHA_ERR_UNSUPPORTED;
-      }
-      const bool has_img = q->n_images > 0, has_vid = q->n_videos > 0;
-      if (((q->audio_features && q->n_frames > 0) || (q->audio_samples && q->n_samples > 0)) && (c.arch != AHA_ARCH_QWEN3ASR || !m->audio)) {
-        set_error(who + "audio input given but this model has no audio tower");
-        return AHA_ERR_UNSUPPORTED;
-      }
-      // on a Qwen3-ASR model every entry without images / videos is an audio request: the tower's own checks (samples or features, the
-      // placeholder count)
-      if (!has_img && !has_vid && c.arch == AHA_ARCH_QWEN3ASR && m->audio) {
-        const AudRequest r{q, ids + off, seq_lens[j], 0, (int)j};
-        if ((rc = audio_check_requests(m, &r, 1))) return rc;
-        continue;
-      }
-      if (!has_img && !has_vid) continue;
-      if (c.arch != AHA_ARCH_QWEN3VL || !m->vision) {
-        set_error(who + "image input given but this model has no vision tower (arch / model.visual.* weights)");
-        return AHA_ERR_UNSUPPORTED;
-      }
-      if ((has_img && (!q->pixel_values || !q->image_grid_thw)) || (has_vid && (!q->pixel_values_video || !q->video_grid_thw))) {
-        set_error(who + "image / video input without pixel values / grid_thw");
-        return AHA_ERR_INVALID;
-      }
-      if (q->pixel_dtype != AHA_BF16 && q->pixel_dtype != AHA_F32) {
-        set_error(who + "pixel_values must be bf16 or f32");
-        return AHA_ERR_UNSUPPORTED;
-      }
-      const int ms = c.vis_spatial_merge_size;
-      int64_t n_img = 0, n_vid = 0;
-      for (int i = 0; i < (has_img ? q->n_images : 0) + (has_vid ? q->n_videos : 0); ++i) {
-        const bool img = has_img && i < q->n_images;
-        const uint32_t* g = img ? q->image_grid_thw + 3 * i : q->video_grid_thw + 3 * (i - (has_img ? q->n_images : 0));
-        if (ms <= 0 || g[1] % ms || g[2] % ms || g[0] == 0) {
-          set_error(who + "grid_thw: h and w must be multiples of spatial_merge_size");
-          return AHA_ERR_SHAPE;
-        }
-        (img ? n_img : n_vid) += (int64_t)g[0] * g[1] * g[2];
-      }
-      if (n_img != (has_img ? q->n_patches : 0) || n_vid != (has_vid ? q->n_patches_video : 0)) {
-        set_error(who + "pixel_values has " + std::to_string(has_img ? q->n_patches : 0) + " / " + std::to_string(has_vid ? q->n_patches_video : 0) +
-                  " image / video rows, the grids describe " + std::to_string(n_img) + " / " + std::to_string(n_vid));
-        return AHA_ERR_SHAPE;
-      }
-      int64_t n_ipad = 0, n_vpad = 0;
-      for (size_t i = 0; i < seq_lens[j]; ++i) {
-        n_ipad += ids[off + i] == (uint32_t)c.image_token_id;
-        n_vpad += ids[off + i] == (uint32_t)c.video_token_id;
-      }
-      if (n_ipad != n_img / (ms * ms) || n_vpad != n_vid / (ms * ms)) {   // model.rs:1158-1164, 1176-1183
-        set_error(who + "n_image_token num: " + std::to_string(n_ipad) + " / " + std::to_string(n_vpad) + " image / video placeholders, image_embed len: " +
-                  std::to_string(n_img / (ms * ms)) + " / " + std::to_string(n_vid / (ms * ms)));
-        return AHA_ERR_SHAPE;
-      }
-      pos3[j].resize(3 * seq_lens[j]);
-      const int prc = rope_index_core(c, ids + off, seq_lens[j], q->image_grid_thw, has_img ? q->n_images : 0, q->video_grid_thw,
-                                      has_vid ? q->n_videos : 0, pos3[j].data(), &rope_delta[j]);
-      if (prc) {
-        set_error(who + last_error_cstr());
-        return prc;
-      }
-    }
-  }
+  if (mm && (rc = check_mm_requests(m, ids, seq_lens, n_seqs, mm, pos3, rope_delta))) return rc;
   AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
   if ((rc = model_clear_cache(m))) return rc;
-  struct ClearGuard {
-    aha_model* m;
-    ~ClearGuard() { model_clear_cache(m); }
-  } guard{m};
+  ClearCacheGuard guard{m};
   hipStream_t st = m->stream;
-  const int n = (int)n_seqs, L = c.num_hidden_layers;
-  const int H = c.hidden_size, I = c.intermediate_size, nh = c.num_attention_heads, kvh = c.num_key_value_heads, g = nh / kvh;
-  const int nq = nh * 128, nkv = kvh * 128, V = c.vocab_size;
+  const int n = (int)n_seqs, L = c.num_hidden_layers, g = c.num_attention_heads / c.num_key_value_heads, V = c.vocab_size;
   // every sequence's pages, reserved up front: ceil((len + max_new) / 64) consecutive logical pages
   std::vector<int64_t> page0(n);
   size_t npages = 0;
@@ -2462,170 +2611,18 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
   if ((rc = model_ensure_pages(m, npages * KV_PAGE_TOKENS))) return rc;
   DevBufs bufs{st, {}, {}};
   GenCall gc;
-  gc.n = n, gc.V = V, gc.H = H;
-  for (int j = 0; j < n; ++j) gc.max_nsplit = std::max(gc.max_nsplit, attn_decode_nsplit((int)(seq_lens[j] + max_new), g, m->max_nsplit));
-  size_t ws = 0;
-  const int shapes[5][2] = {{nq + 2 * nkv, H}, {H, nq}, {2 * I, H}, {H, I}, {V, H}};
-  for (auto& sh : shapes) ws = std::max(ws, gemv_rows_ws_floats(std::min(n, GEN_ROW_GROUP), sh[0], sh[1]));
-  const int tiles = gemv_rows_num_tiles(V);
-  size_t max_pass_pages = 0;
-  for (int j = 0; j < n; ++j) max_pass_pages += (seq_lens[j] + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
-  int32_t* h_rowtab = nullptr;
-  uint32_t* h_tok = nullptr;
-  if ((rc = bufs.alloc(&gc.ws, ws)) || (rc = bufs.alloc((bf16_t**)&gc.x, (size_t)n * H)) || (rc = bufs.alloc((bf16_t**)&gc.h, (size_t)n * H)) ||
-      (rc = bufs.alloc((bf16_t**)&gc.qkv, (size_t)n * (nq + 2 * nkv))) || (rc = bufs.alloc((bf16_t**)&gc.attn, (size_t)n * nq)) ||
-      (rc = bufs.alloc((bf16_t**)&gc.act, (size_t)n * I)) || (rc = bufs.alloc(&gc.rope, (size_t)n * 128)) ||
-      (rc = bufs.alloc(&gc.logits, (size_t)n * V)) || (rc = bufs.alloc(&gc.blk_max, (size_t)n * tiles)) ||
-      (rc = bufs.alloc(&gc.blk_idx, (size_t)n * tiles)) || (rc = bufs.alloc(&gc.tok[0], (size_t)n)) || (rc = bufs.alloc(&gc.tok[1], (size_t)n)) ||
-      (rc = bufs.alloc(&gc.rowtab, (size_t)n * GEN_ROW_WORDS)) || (rc = bufs.alloc(&gc.ctr, (size_t)n * kvh * 32, true)) ||
-      (rc = bufs.alloc(&gc.part_o, (size_t)n * gc.max_nsplit * nq)) || (rc = bufs.alloc(&gc.part_ml, (size_t)n * gc.max_nsplit * nh * 2)) ||
-      (rc = bufs.alloc(&gc.pass_pages, max_pass_pages)) || (rc = bufs.alloc_host(&h_rowtab, (size_t)n * GEN_ROW_WORDS)) ||
-      (rc = bufs.alloc_host(&h_tok, (size_t)n)))
-    return rc;
+  gc.n = n, gc.V = V, gc.H = c.hidden_size, gc.max_new = max_new;
+  gc.tokens_out = tokens_out, gc.n_out = n_out, gc.step_logits_out = step_logits_out;
+  GenChoice ch;
+  if ((rc = gen_call_alloc(m, bufs, gc, seq_lens)) || (params && (rc = gen_choice_init(bufs, gc, params, ch)))) return rc;
 
-  // ---- sampled generation: per-sequence samplers and the candidate step's buffers ----
-  std::vector<HostSampler> samplers(params ? n : 0);
-  const int nw = sample_stage1_waves(V);
-  int32_t *d_stab = nullptr, *h_stab = nullptr;
-  uint32_t *d_sctx = nullptr, *h_sctx = nullptr, *d_cidx = nullptr;
-  float *d_cval = nullptr, *d_part = nullptr, *d_sout = nullptr, *h_sout = nullptr, *h_fb = nullptr;
-  if (params) {
-    if (!sample_shape_ok(V, 64)) {
-      set_error("generate_batch_sampled: vocabulary too large for the candidate step");
-      return AHA_ERR_UNSUPPORTED;
-    }
-    size_t ctx_cap = 0, n_fb = 0;
-    for (int j = 0; j < n; ++j) {
-      if ((rc = host_sampler_init(samplers[j], params[j]))) return rc;
-      const HostSampler& S = samplers[j];
-      if (S.repeat_penalty != 1.0f) ctx_cap += std::min<size_t>(max_new, (size_t)S.repeat_last_n);
-      // a sequence that may need its full logits row: Sampling::All, oversized k, any TopP (nucleus wider than the candidates)
-      if (S.kind != SAMPLE_ARGMAX && (S.kind == SAMPLE_TOPP || sampler_candidates_needed(S, (size_t)V) == 0)) ++n_fb;
-    }
-    const size_t cand = (size_t)n * (nw + 16) * 64;
-    if ((rc = bufs.alloc(&d_stab, (size_t)n * SAMPLE_ROW_WORDS)) || (rc = bufs.alloc(&d_sctx, ctx_cap)) || (rc = bufs.alloc(&d_cval, cand)) ||
-        (rc = bufs.alloc(&d_cidx, cand)) || (rc = bufs.alloc(&d_part, 2 * (size_t)n * nw)) ||
-        (rc = bufs.alloc(&d_sout, (size_t)n * SAMPLE_OUT_WORDS)) || (rc = bufs.alloc_host(&h_stab, (size_t)n * SAMPLE_ROW_WORDS)) ||
-        (rc = bufs.alloc_host(&h_sctx, ctx_cap)) || (rc = bufs.alloc_host(&h_sout, (size_t)n * SAMPLE_OUT_WORDS)) ||
-        (rc = bufs.alloc_host(&h_fb, n_fb * (size_t)V)))
-      return rc;
-  }
-  // The end of every step (the prefill's first tokens, then each decode step): the tokens of rows r = 0 .. R-1 (row r = sequence seqs[r])
-  // into h_tok, from the device argmax vector `tok_dev` the head wrote.  Greedy: one copy and one sync.  Sampled: before that sync, one
-  // candidate step over every row that samples (its penalty context uploaded with it) and the candidates' copy; after it the host picks,
-  // a second sync only for rows whose candidates cannot decide (their logits rows come down), and the picked tokens go back up into
-  // tok_dev for the next step's embedding gather.
-  std::vector<int> mode, slot, fb_rows;
-  auto finish_step = [&](const std::vector<int>& seqs, uint32_t* tok_dev) -> int {
-    const int R = (int)seqs.size();
-    enum { GREEDY, CAND, FULL };
-    int ns = 0;
-    if (params) {
-      mode.assign(R, GREEDY);
-      slot.assign(R, -1);
-      size_t nc = 0;
-      for (int r = 0; r < R; ++r) {
-        const int j = seqs[r];
-        const HostSampler& S = samplers[j];
-        float pen;
-        size_t n_ctx;
-        sampler_penalty_context(S, n_out[j], &pen, &n_ctx);
-        if (S.kind == SAMPLE_ARGMAX && pen == 1.0f) continue;   // the device argmax is the token
-        const int k = S.kind == SAMPLE_ARGMAX ? 1 : sampler_candidates_needed(S, (size_t)V);
-        if (!k) {
-          mode[r] = FULL;
-          continue;
-        }
-        mode[r] = CAND;
-        slot[r] = ns;
-        int32_t* t = h_stab + (size_t)ns * SAMPLE_ROW_WORDS;
-        // `&logits / temperature`: 1/T computed in f64, applied in f32 (as model_sample_candidates; ArgMax: T treated as 1)
-        const float inv_t = S.kind == SAMPLE_ARGMAX ? 1.0f : (float)(1.0 / (double)(float)S.temperature);
-        const size_t c0 = nc;
-        if (pen != 1.0f) {   // the distinct in-vocabulary ids of the last n_ctx generated (apply_repeat_penalty's HashSet)
-          const uint32_t* g = tokens_out + (size_t)j * max_new + n_out[j] - n_ctx;
-          for (size_t i = 0; i < n_ctx; ++i)
-            if (g[i] < (uint32_t)V) h_sctx[nc++] = g[i];
-          std::sort(h_sctx + c0, h_sctx + nc);
-          nc = (size_t)(std::unique(h_sctx + c0, h_sctx + nc) - h_sctx);
-        }
-        t[SAMPLE_ROW_LROW] = r;
-        t[SAMPLE_ROW_K] = k;
-        memcpy(&t[SAMPLE_ROW_INVT], &inv_t, 4);
-        memcpy(&t[SAMPLE_ROW_PEN], &pen, 4);
-        t[SAMPLE_ROW_CTX0] = (int32_t)c0;
-        t[SAMPLE_ROW_NCTX] = (int32_t)(nc - c0);
-        t[6] = t[7] = 0;
-        ++ns;
-      }
-      if (ns) {
-        AHA_HIP_CHECK(hipMemcpyAsync(d_stab, h_stab, (size_t)ns * SAMPLE_ROW_WORDS * 4, hipMemcpyHostToDevice, st));
-        if (nc) AHA_HIP_CHECK(hipMemcpyAsync(d_sctx, h_sctx, nc * 4, hipMemcpyHostToDevice, st));
-        const char* names[3] = {"sample_rows_stage1", "sample_rows_stage2a", "sample_rows_stage2b"};
-        for (int stage = 0; stage < 3; ++stage) {
-          ProfScope ps(m, names[stage], stage == 0 ? (double)ns * V * 4 : 0, 0);
-          launch_topk_rows(gc.logits, V, V, ns, d_stab, d_sctx, d_cval, d_cidx, d_part, d_part + (size_t)n * nw, d_sout, stage, st);
-        }
-        AHA_HIP_CHECK(hipGetLastError());
-        AHA_HIP_CHECK(hipMemcpyAsync(h_sout, d_sout, (size_t)ns * SAMPLE_OUT_WORDS * 4, hipMemcpyDeviceToHost, st));
-      }
-    }
-    if (step_logits_out)
-      for (int r = 0; r < R; ++r)
-        AHA_HIP_CHECK(hipMemcpyAsync(step_logits_out + ((size_t)seqs[r] * max_new + n_out[seqs[r]]) * V, gc.logits + (size_t)r * V,
-                                     (size_t)V * 4, hipMemcpyDeviceToHost, st));
-    AHA_HIP_CHECK(hipMemcpyAsync(h_tok, tok_dev, (size_t)R * 4, hipMemcpyDeviceToHost, st));
-    AHA_HIP_CHECK(hipStreamSynchronize(st));
-    if (!params) return AHA_OK;
-    fb_rows.clear();
-    for (int r = 0; r < R; ++r) {
-      if (mode[r] == GREEDY) continue;
-      const int j = seqs[r];
-      if (mode[r] == CAND) {
-        const float* o = h_sout + (size_t)slot[r] * SAMPLE_OUT_WORDS;
-        const int k = h_stab[(size_t)slot[r] * SAMPLE_ROW_WORDS + SAMPLE_ROW_K];
-        const int prc = sampler_pick(samplers[j], o, reinterpret_cast<const uint32_t*>(o + 66), k, o[64], o[65], nullptr, (size_t)V,
-                                     tokens_out + (size_t)j * max_new, n_out[j], &h_tok[r]);
-        if (prc < 0) return prc;
-        if (prc == AHA_OK) continue;
-      }
-      fb_rows.push_back(r);
-    }
-    if (!fb_rows.empty()) {   // rows whose candidates cannot decide: their full logits rows, one more sync
-      for (size_t f = 0; f < fb_rows.size(); ++f)
-        AHA_HIP_CHECK(hipMemcpyAsync(h_fb + f * V, gc.logits + (size_t)fb_rows[f] * V, (size_t)V * 4, hipMemcpyDeviceToHost, st));
-      AHA_HIP_CHECK(hipStreamSynchronize(st));
-      for (size_t f = 0; f < fb_rows.size(); ++f) {
-        const int r = fb_rows[f], j = seqs[r];
-        const int prc = sampler_pick(samplers[j], nullptr, nullptr, 0, 0.f, 0.f, h_fb + f * V, (size_t)V, tokens_out + (size_t)j * max_new,
-                                     n_out[j], &h_tok[r]);
-        if (prc != AHA_OK) return prc < 0 ? prc : AHA_ERR_STATE;
-      }
-    }
-    AHA_HIP_CHECK(hipMemcpyAsync(tok_dev, h_tok, (size_t)R * 4, hipMemcpyHostToDevice, st));
-    return AHA_OK;
-  };
-
-  // ---- prefill: packed passes (embed_batch's pass rule) ----
-  const size_t budget = std::min(max_tokens_per_pass ? max_tokens_per_pass : EMBED_PASS_ROWS, (size_t)1 << 24);
-  {
-    size_t j = 0, off = 0;
-    while (j < n_seqs) {
-      size_t rows = 0, slots = 0, k = j;
-      while (k < n_seqs) {
-        const size_t len = seq_lens[k], sl = (len + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS * KV_PAGE_TOKENS;
-        if (k > j && (rows + len > budget || slots + sl > 2 * budget)) break;
-        rows += len, slots += sl, ++k;
-      }
-      if ((rc = generate_prefill_pass(m, gc, ids + off, seq_lens + j, (int)j, (int)(k - j), page0, pos3, mm))) return rc;
-      off += rows;
-      j = k;
-    }
-  }
+  // ---- prefill: packed passes ----
+  for (const PassRange& p : split_passes(seq_lens, n_seqs, max_tokens_per_pass))
+    if ((rc = generate_prefill_pass(m, gc, ids + p.off, seq_lens + p.j, (int)p.j, (int)(p.k - p.j), page0, pos3, mm))) return rc;
   {
     std::vector<int> all(n);
     for (int j = 0; j < n; ++j) all[j] = j, n_out[j] = 0;
-    if ((rc = finish_step(all, gc.tok[0]))) return rc;
+    if ((rc = gen_finish_step(m, gc, ch, all, gc.tok[0]))) return rc;
   }
   auto is_stop = [&](uint32_t t) {
     for (int e = 0; e < c.n_stop_tokens; ++e)
@@ -2638,7 +2635,7 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
   };
   std::vector<int> active, src_row(n);
   for (int j = 0; j < n; ++j) {
-    tokens_out[(size_t)j * max_new] = h_tok[j];   // the first token never ends a sequence (generate.rs:131-134)
+    tokens_out[(size_t)j * max_new] = gc.h_tok[j];   // the first token never ends a sequence (generate.rs:131-134)
     n_out[j] = 1;
     src_row[j] = j;
     if (max_new == 1) {
@@ -2654,11 +2651,12 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
   while (!active.empty()) {
     const int R = (int)active.size();
     int max_split = 1;
+    double kv_tokens = 0;
     for (int r = 0; r < R; ++r) {
       const int j = active[r];
       const int kv_len = (int)(seq_lens[j] + n_out[j]);   // the cache after this step's append
       const int ns = attn_decode_nsplit(kv_len, g, m->max_nsplit);
-      int32_t* t = h_rowtab + (size_t)r * GEN_ROW_WORDS;
+      int32_t* t = gc.h_rowtab + (size_t)r * GEN_ROW_WORDS;
       t[GEN_ROW_PAGE0] = (int32_t)page0[j];
       t[GEN_ROW_KVLEN] = kv_len;
       t[GEN_ROW_NSPLIT] = ns;
@@ -2668,61 +2666,16 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
       t[6] = t[7] = 0;
       if (ns > 1) ctr_acc[r] += (unsigned)L * (unsigned)ns;   // a single split never touches its counter
       max_split = std::max(max_split, ns);
+      kv_tokens += kv_len;
     }
-    AHA_HIP_CHECK(hipMemcpyAsync(gc.rowtab, h_rowtab, (size_t)R * GEN_ROW_WORDS * 4, hipMemcpyHostToDevice, st));
-    {
-      ProfScope ps(m, "elem", (double)R * H * 4, 0);
-      launch_gen_embed(m->embed, gc.tok[cur], gc.rowtab, R, gc.x, H, m->d_inv_freq, m->d_axis_map, gc.rope, st);
-    }
-    double kv_tokens = 0;
-    for (int r = 0; r < R; ++r) kv_tokens += h_rowtab[(size_t)r * GEN_ROW_WORDS + GEN_ROW_KVLEN];
-    for (int li = 0; li < L; ++li) {
-      const LayerWeights& Lw = m->layers[li];
-      {   // h = RMSNorm(x); qkv = h Wqkv^T                      (qwen3/model.rs:79, modules.rs:538-552)
-        {
-          ProfScope ps(m, "elem", (double)R * H * 4, 0);
-          launch_rmsnorm_rows(gc.x, Lw.in_norm, gc.h, R, H, H, H, c.rms_norm_eps, st);
-        }
-        GemvRowsArgs a{};
-        a.W = Lw.wqkv; a.x = gc.h; a.ldx = H; a.y = gc.qkv; a.ldy = nq + 2 * nkv; a.N = nq + 2 * nkv; a.K = H;
-        gemv_rows_groups(m, a, GEMV_STORE, R, gc.ws);
-      }
-      {   // q/k norm + rope + KV append + attention of every row over its own pages (modules.rs:544-574, 757-813)
-        AttnDecodeBatchArgs b{};
-        b.qkv = gc.qkv; b.q_norm_w = Lw.q_norm; b.k_norm_w = Lw.k_norm; b.rope = gc.rope; b.page_ptrs = m->d_page_ptrs;
-        b.layer_off = (uint64_t)li * m->layer_stride; b.row_tab = gc.rowtab; b.part_o = gc.part_o; b.part_ml = gc.part_ml; b.o = gc.attn;
-        b.head_ctr = gc.ctr; b.ctr_step = li + 1; b.nh = nh; b.kvh = kvh; b.max_nsplit = gc.max_nsplit; b.eps = c.rms_norm_eps;
-        b.scale = m->attn_scale;
-        ProfScope ps(m, "attn_decode_batch", kv_tokens * 2 * nkv * 2 + (double)R * (nq + 2 * nkv) * 2, 4.0 * kv_tokens * nq);
-        launch_attn_decode_batch(b, R, max_split, st);
-      }
-      {   // x = x + attn Wo^T                                    (modules.rs:577, qwen3/model.rs:81)
-        GemvRowsArgs a{};
-        a.W = Lw.wo; a.x = gc.attn; a.ldx = nq; a.residual = gc.x; a.y = gc.x; a.ldy = H; a.N = H; a.K = nq;
-        gemv_rows_groups(m, a, GEMV_RESIDUAL, R, gc.ws);
-      }
-      {   // act = silu(h Wg^T) * (h Wu^T), h = RMSNorm(x)        (qwen3/model.rs:83, modules.rs:81-84)
-        {
-          ProfScope ps(m, "elem", (double)R * H * 4, 0);
-          launch_rmsnorm_rows(gc.x, Lw.post_norm, gc.h, R, H, H, H, c.rms_norm_eps, st);
-        }
-        GemvRowsArgs a{};
-        a.W = Lw.wgu; a.x = gc.h; a.ldx = H; a.y = gc.act; a.ldy = I; a.N = 2 * I; a.K = H;
-        gemv_rows_groups(m, a, GEMV_SILU_MUL, R, gc.ws);
-      }
-      {   // x = x + act Wd^T                                     (modules.rs:85, qwen3/model.rs:86)
-        GemvRowsArgs a{};
-        a.W = Lw.wdown; a.x = gc.act; a.ldx = I; a.residual = gc.x; a.y = gc.x; a.ldy = H; a.N = H; a.K = I;
-        gemv_rows_groups(m, a, GEMV_RESIDUAL, R, gc.ws);
-      }
-    }
-    gen_head(m, gc, 0, R, gc.tok[cur ^ 1]);
+    AHA_HIP_CHECK(hipMemcpyAsync(gc.rowtab, gc.h_rowtab, (size_t)R * GEN_ROW_WORDS * 4, hipMemcpyHostToDevice, st));
+    gen_decode_step(m, gc, R, max_split, kv_tokens, gc.tok[cur], gc.tok[cur ^ 1]);
     AHA_HIP_CHECK(hipGetLastError());
-    if ((rc = finish_step(active, gc.tok[cur ^ 1]))) return rc;
+    if ((rc = gen_finish_step(m, gc, ch, active, gc.tok[cur ^ 1]))) return rc;
     std::vector<int> next;
     for (int r = 0; r < R; ++r) {
       const int j = active[r];
-      const uint32_t t = h_tok[r];
+      const uint32_t t = gc.h_tok[r];
       tokens_out[(size_t)j * max_new + n_out[j]++] = t;
       src_row[j] = r;
       if (is_stop(t) || n_out[j] == max_new) {

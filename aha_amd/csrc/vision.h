@@ -21,6 +21,9 @@ struct VisRequest {
   int64_t row0;
   int seq;
 };
+// Every check of a request's images / videos, no device work: pixel values and grids given, the pixel dtype, h and w multiples of the merge
+// size, the patch rows the grids describe, and (ids given) its placeholder counts.  n_img / n_vid: its image / video patch rows.
+int vision_check_request(const aha_model_desc& c, const VisRequest& r, int64_t* n_img, int64_t* n_vid);
 // The tower over every request's images and videos in ONE pass (no image_embeds), the merged rows scattered to each request's
 // placeholder rows of x; vision_deepstack_add then adds to those rows.  vision_forward_and_scatter = one request at row 0.
 int vision_forward_requests(aha_model* m, const VisRequest* reqs, size_t n_reqs, void* x);

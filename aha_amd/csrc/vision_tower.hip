@@ -296,6 +296,49 @@ int vision_forward_and_scatter(aha_model* m, const uint32_t* ids, size_t n, cons
   return vision_forward_requests(m, &r, 1, x_text);
 }
 
+int vision_check_request(const aha_model_desc& c, const VisRequest& r, int64_t* n_img, int64_t* n_vid) {
+  const std::string who = r.seq >= 0 ? "sequence " + std::to_string(r.seq) + ": " : "";
+  const aha_mm_input* mm = r.mm;
+  const bool has_img = mm->n_images > 0, has_vid = mm->n_videos > 0;
+  if ((!has_img && !has_vid) || (has_img && (!mm->pixel_values || !mm->image_grid_thw)) ||
+      (has_vid && (!mm->pixel_values_video || !mm->video_grid_thw))) {
+    set_error(who + "image / video input without pixel values / grid_thw");
+    return AHA_ERR_INVALID;
+  }
+  if (mm->pixel_dtype != AHA_BF16 && mm->pixel_dtype != AHA_F32) {
+    set_error(who + "pixel_values must be bf16 or f32");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  const int ms = c.vis_spatial_merge_size;
+  *n_img = *n_vid = 0;
+  for (int i = 0; i < (has_img ? mm->n_images : 0) + (has_vid ? mm->n_videos : 0); ++i) {
+    const bool img = has_img && i < mm->n_images;
+    const uint32_t* g = img ? mm->image_grid_thw + 3 * i : mm->video_grid_thw + 3 * (i - (has_img ? mm->n_images : 0));
+    if (ms <= 0 || g[1] % ms || g[2] % ms || g[0] == 0) {
+      set_error(who + "grid_thw: h and w must be multiples of spatial_merge_size");
+      return AHA_ERR_SHAPE;
+    }
+    *(img ? n_img : n_vid) += (int64_t)g[0] * g[1] * g[2];
+  }
+  if (*n_img != (has_img ? mm->n_patches : 0) || *n_vid != (has_vid ? mm->n_patches_video : 0)) {
+    set_error(who + "pixel_values has " + std::to_string(has_img ? mm->n_patches : 0) + " / " + std::to_string(has_vid ? mm->n_patches_video : 0) +
+              " image / video rows, the grids describe " + std::to_string(*n_img) + " / " + std::to_string(*n_vid));
+    return AHA_ERR_SHAPE;
+  }
+  if (!r.ids) return AHA_OK;
+  int64_t n_ipad = 0, n_vpad = 0;
+  for (size_t i = 0; i < r.n; ++i) {
+    n_ipad += r.ids[i] == (uint32_t)c.image_token_id;
+    n_vpad += r.ids[i] == (uint32_t)c.video_token_id;
+  }
+  if (n_ipad != *n_img / (ms * ms) || n_vpad != *n_vid / (ms * ms)) {   // model.rs:1158-1164, 1176-1183
+    set_error(who + "n_image_token num: " + std::to_string(n_ipad) + " / " + std::to_string(n_vpad) + " image / video placeholders, image_embed len: " +
+              std::to_string(*n_img / (ms * ms)) + " / " + std::to_string(*n_vid / (ms * ms)));
+    return AHA_ERR_SHAPE;
+  }
+  return AHA_OK;
+}
+
 // Every (image | video frame) of a list of requests through ONE tower pass.  Rows: request order, within a request image patches then
 // video patches; merged rows likewise, scattered to each request's placeholder rows (request row0 + its <|image_pad|> positions, then
 // its <|video_pad|> positions) of x_text.  forward_initial: one request at row 0; generate_batch_mm: the requests of a prefill pass.
@@ -318,54 +361,17 @@ int vision_forward_requests(aha_model* m, const VisRequest* reqs, size_t n_reqs,
   int64_t N = 0;
   for (size_t q = 0; q < n_reqs; ++q) {
     const aha_mm_input* mm = reqs[q].mm;
-    const std::string who = reqs[q].seq >= 0 ? "sequence " + std::to_string(reqs[q].seq) + ": " : "";
-    const bool has_img = mm->n_images > 0, has_vid = mm->n_videos > 0;
-    if ((!has_img && !has_vid) || (has_img && (!mm->pixel_values || !mm->image_grid_thw)) ||
-        (has_vid && (!mm->pixel_values_video || !mm->video_grid_thw))) {
-      set_error(who + "forward_initial: image / video input without pixel values / grid_thw");
-      return AHA_ERR_INVALID;
-    }
     int64_t n_img = 0, n_vid = 0;
-    for (int i = 0; i < (has_img ? mm->n_images : 0) + (has_vid ? mm->n_videos : 0); ++i) {
-      const bool img = has_img && i < mm->n_images;
-      const uint32_t* g = img ? mm->image_grid_thw + 3 * i : mm->video_grid_thw + 3 * (i - (has_img ? mm->n_images : 0));
-      if (g[1] % ms || g[2] % ms || g[0] == 0) {
-        set_error(who + "grid_thw: h and w must be multiples of spatial_merge_size");
-        return AHA_ERR_SHAPE;
-      }
-      grids.push_back(g);
-      (img ? n_img : n_vid) += (int64_t)g[0] * g[1] * g[2];
-    }
-    if (n_img != (has_img ? mm->n_patches : 0)) {
-      set_error(who + "pixel_values has " + std::to_string(mm->n_patches) + " rows, image_grid_thw describes " + std::to_string(n_img));
-      return AHA_ERR_SHAPE;
-    }
-    if (n_vid != (has_vid ? mm->n_patches_video : 0)) {
-      set_error(who + "pixel_values_video has " + std::to_string(mm->n_patches_video) + " rows, video_grid_thw describes " + std::to_string(n_vid));
-      return AHA_ERR_SHAPE;
-    }
-    if (mm->pixel_dtype != AHA_BF16 && mm->pixel_dtype != AHA_F32) {
-      set_error(who + "pixel_values must be bf16 or f32");
-      return AHA_ERR_UNSUPPORTED;
-    }
+    const int rc = vision_check_request(c, reqs[q], &n_img, &n_vid);
+    if (rc) return rc;
+    for (int i = 0; i < mm->n_images; ++i) grids.push_back(mm->image_grid_thw + 3 * i);
+    for (int i = 0; i < mm->n_videos; ++i) grids.push_back(mm->video_grid_thw + 3 * i);
     req_img[q] = n_img, req_vid[q] = n_vid;
     N += n_img + n_vid;
-    if (!encode_only) {
-      const uint32_t* ids = reqs[q].ids;
-      const size_t v0 = vis_rows.size();
-      for (size_t i = 0; i < reqs[q].n; ++i)
-        if (ids[i] == (uint32_t)c.image_token_id) vis_rows.push_back((int32_t)(reqs[q].row0 + (int64_t)i));
-      if ((int64_t)(vis_rows.size() - v0) != n_img / (ms * ms)) {  // model.rs:1158-1164
-        set_error(who + "n_image_token num: " + std::to_string(vis_rows.size() - v0) + " not equal to image_embed len: " + std::to_string(n_img / (ms * ms)));
-        return AHA_ERR_SHAPE;
-      }
-      for (size_t i = 0; i < reqs[q].n; ++i)
-        if (ids[i] == (uint32_t)c.video_token_id) vis_rows.push_back((int32_t)(reqs[q].row0 + (int64_t)i));
-      if ((int64_t)(vis_rows.size() - v0) != (n_img + n_vid) / (ms * ms)) {  // model.rs:1176-1183 (the reference reuses the image wording)
-        set_error(who + "n_image_token num: " + std::to_string(vis_rows.size() - v0 - n_img / (ms * ms)) + " not equal to image_embed len: " +
-                  std::to_string(n_vid / (ms * ms)));
-        return AHA_ERR_SHAPE;
-      }
+    if (!encode_only) {   // the placeholder rows: its <|image_pad|> positions, then its <|video_pad|> positions
+      for (uint32_t tok : {(uint32_t)c.image_token_id, (uint32_t)c.video_token_id})
+        for (size_t i = 0; i < reqs[q].n; ++i)
+          if (reqs[q].ids[i] == tok) vis_rows.push_back((int32_t)(reqs[q].row0 + (int64_t)i));
     }
   }
   const int64_t n4 = N / (ms * ms);
@@ -487,22 +493,19 @@ int vision_forward_requests(aha_model* m, const VisRequest* reqs, size_t n_reqs,
   double small_flops = 0;
   std::vector<int32_t> stab;   // (lives until the synchronise below: pageable)
   if (seg_attn) {
-    std::vector<std::pair<int, int>> items;   // (segment, 64-row q block)
     for (Seg& s : segs) {
       AttnPrefillArgs a = seg_args(s.start, s.page0);
       a.S = (int)s.len; a.kv_total = (int)s.len;
       if (attn_prefill_form_of(a) != 0) continue;
       s.small = true;
-      for (int b = 0; (int64_t)b * 64 < s.len; ++b) items.emplace_back(n_small, b);
       stab.push_back((int32_t)s.start), stab.push_back((int32_t)s.len), stab.push_back((int32_t)s.page0);
       ++n_small;
       small_rows += s.len;
       small_flops += 4.0 * s.len * s.len * v->D;
     }
-    // non-causal: a block's cost is its segment's length
-    std::stable_sort(items.begin(), items.end(), [&](const auto& x, const auto& y) { return stab[3 * x.first + 1] > stab[3 * y.first + 1]; });
-    n_seg_items = (int)items.size();
-    for (const auto& it : items) stab.push_back(it.first), stab.push_back(it.second);
+    const std::vector<int32_t> items = seg_items_of(stab, false);
+    n_seg_items = (int)items.size() / 2;
+    stab.insert(stab.end(), items.begin(), items.end());
     if (n_small > 0) AHA_HIP_CHECK(hipMemcpyAsync(v->d_seg, stab.data(), stab.size() * 4, hipMemcpyHostToDevice, st));
   }
   if (!m->cp_row_map.empty())

@@ -107,6 +107,23 @@ def _mm_input(data: MultiModalData):
     return mm, keep
 
 
+def _pack_batch(seqs):
+    """A batch's token ids, packed: (ids uint32, lengths uint64)."""
+    seqs = [np.asarray(x, dtype=np.uint32).reshape(-1) for x in seqs]
+    ids = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0, np.uint32))
+    return ids, np.ascontiguousarray([s.size for s in seqs], dtype=np.uint64)
+
+
+def _sampling_array(params, n: int):
+    """params (one sampling.SamplingParams, or one per sequence) as the C array of n entries."""
+    from .sampling import SamplingParams
+    if isinstance(params, SamplingParams):
+        params = [params] * n
+    if len(params) != n:
+        raise ValueError(f"{len(params)} sampling params for {n} prompts")
+    return (_lib.SamplingParams * max(n, 1))(*[p.to_c() for p in params])
+
+
 def make_desc(cfg, kv_reserve_tokens: int = 0) -> ModelDesc:
     d = ModelDesc()
     if isinstance(cfg, Qwen3VLConfig):
@@ -339,28 +356,30 @@ class HipInferenceModel:
     def embed_batch(self, inputs: Sequence[Sequence[int]], max_tokens_per_pass: int = 0) -> np.ndarray:
         """embed_one of every sequence, run as packed prefills (aha_hip_embed_batch): (len(inputs), hidden) float32.
         max_tokens_per_pass = 0 takes the library default; a longer sequence still runs whole, alone in its pass."""
-        seqs = [np.asarray(x, dtype=np.uint32).reshape(-1) for x in inputs]
-        ids = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0, np.uint32))
-        lens = np.ascontiguousarray([s.size for s in seqs], dtype=np.uint64)
-        out = np.empty((len(seqs), self.text_cfg.hidden_size), dtype=np.float32)
-        check(lib().aha_hip_embed_batch(self.handle, ids.ctypes.data, lens.ctypes.data, len(seqs), int(max_tokens_per_pass),
+        ids, lens = _pack_batch(inputs)
+        out = np.empty((lens.size, self.text_cfg.hidden_size), dtype=np.float32)
+        check(lib().aha_hip_embed_batch(self.handle, ids.ctypes.data, lens.ctypes.data, lens.size, int(max_tokens_per_pass),
                                         out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def _generate_batch(self, entry, prompts, extra, max_new: int, max_tokens_per_pass: int, logits: Optional[str]):
+        """The packing and unpacking of the generate_batch* wrappers: entry(handle, ids, lens, n, *extra, max_new, max_tokens_per_pass,
+        tokens, n_out, logits).  logits: None, "last" = (n, vocab) or "step" = (n, max_new, vocab) float32, returned after the token lists."""
+        ids, lens = _pack_batch(prompts)
+        n, width, V = lens.size, max(int(max_new), 1), self.text_cfg.vocab_size
+        toks = np.zeros((n, width), dtype=np.uint32)
+        n_out = np.zeros(n, dtype=np.uint64)
+        lg = None if logits is None else np.empty((n, V), np.float32) if logits == "last" else np.zeros((n, width, V), np.float32)
+        check(entry(self.handle, ids.ctypes.data, lens.ctypes.data, n, *extra, int(max_new), int(max_tokens_per_pass), toks.ctypes.data,
+                    n_out.ctypes.data, None if lg is None else lg.ctypes.data))
+        out = [[int(t) for t in toks[j, :int(n_out[j])]] for j in range(n)]
+        return out if lg is None else (out, lg)
 
     def generate_batch(self, prompts: Sequence[Sequence[int]], max_new: int, max_tokens_per_pass: int = 0, want_logits: bool = False):
         """Greedy generation of every prompt at once (aha_hip_generate_batch): per prompt, the tokens generate_generic(device_loop=True)
         yields for it alone at temperature 0.  Returns a list of token lists, and with want_logits also the (len(prompts), vocab) float32
         logits that chose each prompt's last token."""
-        seqs = [np.asarray(x, dtype=np.uint32).reshape(-1) for x in prompts]
-        ids = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0, np.uint32))
-        lens = np.ascontiguousarray([s.size for s in seqs], dtype=np.uint64)
-        toks = np.zeros((len(seqs), max(int(max_new), 1)), dtype=np.uint32)
-        n_out = np.zeros(len(seqs), dtype=np.uint64)
-        logits = np.empty((len(seqs), self.text_cfg.vocab_size), dtype=np.float32) if want_logits else None
-        check(lib().aha_hip_generate_batch(self.handle, ids.ctypes.data, lens.ctypes.data, len(seqs), int(max_new), int(max_tokens_per_pass),
-                                           toks.ctypes.data, n_out.ctypes.data, None if logits is None else logits.ctypes.data))
-        out = [[int(t) for t in toks[j, :int(n_out[j])]] for j in range(len(seqs))]
-        return (out, logits) if want_logits else out
+        return self._generate_batch(lib().aha_hip_generate_batch, prompts, (), max_new, max_tokens_per_pass, "last" if want_logits else None)
 
     def generate_batch_sampled(self, prompts: Sequence[Sequence[int]], params, max_new: int, max_tokens_per_pass: int = 0,
                                want_step_logits: bool = False):
@@ -368,23 +387,8 @@ class HipInferenceModel:
         yields for it alone with params[j] (a sampling.SamplingParams each, or one for all prompts).  Returns a list of token lists, and
         with want_step_logits also the (len(prompts), max_new, vocab) float32 logits before the penalty that chose each token (rows past
         a sequence's length are zero)."""
-        from .sampling import SamplingParams
-        seqs = [np.asarray(x, dtype=np.uint32).reshape(-1) for x in prompts]
-        if isinstance(params, SamplingParams):
-            params = [params] * len(seqs)
-        if len(params) != len(seqs):
-            raise ValueError(f"{len(params)} sampling params for {len(seqs)} prompts")
-        cp = (_lib.SamplingParams * max(len(seqs), 1))(*[p.to_c() for p in params])
-        ids = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0, np.uint32))
-        lens = np.ascontiguousarray([s.size for s in seqs], dtype=np.uint64)
-        toks = np.zeros((len(seqs), max(int(max_new), 1)), dtype=np.uint32)
-        n_out = np.zeros(len(seqs), dtype=np.uint64)
-        step = np.zeros((len(seqs), max(int(max_new), 1), self.text_cfg.vocab_size), dtype=np.float32) if want_step_logits else None
-        check(lib().aha_hip_generate_batch_sampled(self.handle, ids.ctypes.data, lens.ctypes.data, len(seqs), cp, int(max_new),
-                                                   int(max_tokens_per_pass), toks.ctypes.data, n_out.ctypes.data,
-                                                   None if step is None else step.ctypes.data))
-        out = [[int(t) for t in toks[j, :int(n_out[j])]] for j in range(len(seqs))]
-        return (out, step) if want_step_logits else out
+        return self._generate_batch(lib().aha_hip_generate_batch_sampled, prompts, (_sampling_array(params, len(prompts)),), max_new,
+                                    max_tokens_per_pass, "step" if want_step_logits else None)
 
     def generate_batch_mm(self, prompts: Sequence[Sequence[int]], data, max_new: int, params=None, max_tokens_per_pass: int = 0,
                           want_step_logits: bool = False):
@@ -394,35 +398,20 @@ class HipInferenceModel:
         params: None = every request greedy, else a sampling.SamplingParams per request (or one for all).  Per request, the tokens
         generate_generic yields for it alone with its data.  Returns a list of token lists, and with want_step_logits also the
         (len(prompts), max_new, vocab) float32 logits that chose each token (rows past a sequence's length are zero)."""
-        from .sampling import SamplingParams
-        seqs = [np.asarray(x, dtype=np.uint32).reshape(-1) for x in prompts]
-        if data is not None and len(data) != len(seqs):
-            raise ValueError(f"{len(data)} MultiModalData entries for {len(seqs)} prompts")
-        cp = None
-        if params is not None:
-            if isinstance(params, SamplingParams):
-                params = [params] * len(seqs)
-            if len(params) != len(seqs):
-                raise ValueError(f"{len(params)} sampling params for {len(seqs)} prompts")
-            cp = (_lib.SamplingParams * max(len(seqs), 1))(*[p.to_c() for p in params])
+        n = len(prompts)
+        if data is not None and len(data) != n:
+            raise ValueError(f"{len(data)} MultiModalData entries for {n} prompts")
+        cp = None if params is None else _sampling_array(params, n)
         keep, mm_arr = [], None
         if data is not None:
-            mm_arr = (C.c_void_p * max(len(seqs), 1))()
+            mm_arr = (C.c_void_p * max(n, 1))()
             for j, d in enumerate(data):
                 if d is not None:
                     mm, k = _mm_input(d)
                     keep += [mm, k]
                     mm_arr[j] = C.addressof(mm)
-        ids = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0, np.uint32))
-        lens = np.ascontiguousarray([s.size for s in seqs], dtype=np.uint64)
-        toks = np.zeros((len(seqs), max(int(max_new), 1)), dtype=np.uint32)
-        n_out = np.zeros(len(seqs), dtype=np.uint64)
-        step = np.zeros((len(seqs), max(int(max_new), 1), self.text_cfg.vocab_size), dtype=np.float32) if want_step_logits else None
-        check(lib().aha_hip_generate_batch_mm(self.handle, ids.ctypes.data, lens.ctypes.data, len(seqs), mm_arr, cp, int(max_new),
-                                              int(max_tokens_per_pass), toks.ctypes.data, n_out.ctypes.data,
-                                              None if step is None else step.ctypes.data))
-        out = [[int(t) for t in toks[j, :int(n_out[j])]] for j in range(len(seqs))]
-        return (out, step) if want_step_logits else out
+        return self._generate_batch(lib().aha_hip_generate_batch_mm, prompts, (mm_arr, cp), max_new, max_tokens_per_pass,
+                                    "step" if want_step_logits else None)
 
     def embed_multi(self, inputs: Sequence[Sequence[int]]) -> np.ndarray:
         if len(inputs) == 0:
