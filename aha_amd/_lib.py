@@ -27,6 +27,26 @@ class SamplingParams(C.Structure):
     ]
 
 
+AHA_ENGINE_EV_FIRST, AHA_ENGINE_EV_STOP, AHA_ENGINE_EV_LENGTH, AHA_ENGINE_EV_CANCELLED = 1, 2, 4, 8
+AHA_ENGINE_NO_TOKEN = 0xFFFFFFFF
+AHA_ENGINE_MAX_RUNNING = 64
+
+
+class EngineConfig(C.Structure):
+    """aha_engine_config (include/aha_hip.h)."""
+    _fields_ = [("max_running", C.c_size_t), ("kv_pages", C.c_size_t), ("max_tokens_per_step", C.c_size_t), ("prefill_chunk", C.c_size_t)]
+
+
+class EngineEvent(C.Structure):
+    """aha_engine_event (include/aha_hip.h)."""
+    _fields_ = [("req_id", C.c_uint64), ("token", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class EngineStats(C.Structure):
+    """aha_engine_stats (include/aha_hip.h)."""
+    _fields_ = [("waiting", C.c_size_t), ("running", C.c_size_t), ("free_pages", C.c_size_t), ("total_pages", C.c_size_t)]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [
         ("arch", C.c_int32),
@@ -131,6 +151,7 @@ SIGNATURES = {
     "aha_hip_attn_decode": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
     "aha_hip_attn_prefill": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_float, _P]),
+    "aha_hip_debug_attn_prefill_segs": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_float, _P]),
     "aha_hip_argmax": (C.c_int, [_P, C.c_int64, _P, _P]),
     "aha_hip_logmel": (C.c_int, [_P, C.c_int64, _P, _P]),
     "aha_hip_logmel_batch": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
@@ -149,6 +170,13 @@ SIGNATURES = {
     "aha_hip_generate_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P]),
     "aha_hip_generate_batch_sampled": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(SamplingParams), C.c_size_t, C.c_size_t, _P, _P, _P]),
     "aha_hip_generate_batch_mm": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.POINTER(SamplingParams), C.c_size_t, C.c_size_t, _P, _P, _P]),
+    "aha_hip_engine_create": (C.c_int, [_P, C.POINTER(EngineConfig), _P]),
+    "aha_hip_engine_destroy": (None, [_P]),
+    "aha_hip_engine_submit": (C.c_int, [_P, _P, C.c_size_t, _P, C.POINTER(SamplingParams), C.c_size_t, C.POINTER(C.c_uint64)]),
+    "aha_hip_engine_cancel": (C.c_int, [_P, C.c_uint64]),
+    "aha_hip_engine_step": (C.c_int, [_P, C.POINTER(EngineEvent), C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    "aha_hip_engine_stats": (C.c_int, [_P, C.POINTER(EngineStats)]),
+    "aha_hip_engine_debug_ctr_base": (C.c_int, [_P, C.c_uint32]),
     "aha_hip_sample_rows": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "aha_hip_sampler_create": (C.c_int, [C.POINTER(SamplingParams), _P]),
     "aha_hip_sampler_destroy": (None, [_P]),

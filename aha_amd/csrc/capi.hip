@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -29,6 +30,13 @@ using namespace aha;
     set_error("unknown exception");                     \
     return AHA_ERR_INVALID;                             \
   }
+
+// While an engine exists on a model it owns the cache: the other entries that use it are refused
+static int engine_owns_cache(const aha_model* m, const char* who) {
+  if (!m->engine) return AHA_OK;
+  set_error(std::string(who) + ": the model's cache belongs to its engine (aha_hip_engine_destroy first)");
+  return AHA_ERR_STATE;
+}
 
 extern "C" {
 
@@ -112,6 +120,7 @@ int aha_hip_forward_initial(aha_model* m, const uint32_t* input_ids, size_t n_id
     set_error("null model");
     return AHA_ERR_INVALID;
   }
+  if (int rc = engine_owns_cache(m, "forward_initial")) return rc;
   return model_forward_initial(m, input_ids, n_ids, seqlen_offset, mm, logits_out, argmax_out);
   API_GUARD_END
 }
@@ -121,6 +130,7 @@ int aha_hip_forward_step(aha_model* m, uint32_t token, size_t seqlen_offset, flo
     set_error("null model");
     return AHA_ERR_INVALID;
   }
+  if (int rc = engine_owns_cache(m, "forward_step")) return rc;
   return model_forward_step(m, token, seqlen_offset, logits_out, argmax_out);
   API_GUARD_END
 }
@@ -129,6 +139,7 @@ int aha_hip_clear_cache(aha_model* m) {
     set_error("null model");
     return AHA_ERR_INVALID;
   }
+  if (int rc = engine_owns_cache(m, "clear_cache")) return rc;
   return model_clear_cache(m);
 }
 int aha_hip_stop_token_ids(const aha_model* m, uint32_t* out, size_t cap) {
@@ -146,6 +157,7 @@ int aha_hip_decode_greedy(aha_model* m, uint32_t first_token, size_t seqlen_offs
     set_error("null argument");
     return AHA_ERR_INVALID;
   }
+  if (int rc = engine_owns_cache(m, "decode_greedy")) return rc;
   return model_decode_greedy(m, first_token, seqlen_offset, max_new, tokens_out);
   API_GUARD_END
 }
@@ -176,12 +188,14 @@ int64_t aha_hip_debug_steps_executed(const aha_model* m) { return m ? m->steps_e
 int aha_hip_debug_graph_step(aha_model* m, int32_t replays, double* us_launches, double* us_graph) {
   if (!m) return AHA_ERR_INVALID;
   API_GUARD_BEGIN
+  if (int rc = engine_owns_cache(m, "debug_graph_step")) return rc;
   return model_debug_graph_step(m, replays, us_launches, us_graph);
   API_GUARD_END
 }
 int aha_hip_kv_export(aha_model* m, void* out_dev, size_t out_bytes, size_t* bytes_needed, size_t* n_tokens, int64_t* rope_delta) {
   if (!m) return AHA_ERR_INVALID;
   API_GUARD_BEGIN
+  if (int rc = engine_owns_cache(m, "kv_export")) return rc;
   return model_kv_export(m, out_dev, out_bytes, bytes_needed, n_tokens, rope_delta);
   API_GUARD_END
 }
@@ -189,6 +203,7 @@ int aha_hip_kv_import(aha_model* m, const void* in_dev, size_t in_bytes, int32_t
                       size_t n_tokens, int64_t rope_delta) {
   if (!m) return AHA_ERR_INVALID;
   API_GUARD_BEGIN
+  if (int rc = engine_owns_cache(m, "kv_import")) return rc;
   return model_kv_import(m, in_dev, in_bytes, src_heads, src_head0, dst_head0, n_heads, n_tokens, rope_delta);
   API_GUARD_END
 }
@@ -458,6 +473,68 @@ int build_tmp_pages(TmpPages& t, const void* k, const void* v, int L, int kvh, i
 }
 }  // namespace
 
+int aha_hip_debug_attn_prefill_segs(const void* q, const void* k, const void* v, void* o, int32_t nh, int32_t kvh, const int32_t* segs,
+                                    int32_t n_seg, int32_t with_kv0, float scale, void* stream) {
+  API_GUARD_BEGIN
+  if (!q || !k || !v || !o || !segs || n_seg < 1 || kvh < 1 || nh % kvh || nh / kvh > 16) {
+    set_error("debug_attn_prefill_segs: bad arguments");
+    return AHA_ERR_INVALID;
+  }
+  const int d = 128;
+  std::vector<int32_t> seg(3 * (size_t)n_seg), kv0(n_seg);
+  int S = 0;
+  for (int j = 0; j < n_seg; ++j) {
+    const int len = segs[2 * j], k0 = segs[2 * j + 1];
+    if (len < 1 || k0 < 0 || k0 % KV_PAGE_TOKENS || (!with_kv0 && k0)) {
+      set_error("debug_attn_prefill_segs: segment " + std::to_string(j) + " needs len >= 1 and kv0 a multiple of 64 (0 without with_kv0)");
+      return AHA_ERR_INVALID;
+    }
+    kv0[j] = k0;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // every segment's cache on pages of its own (handed out back to front), the page tables back to back
+  std::vector<std::unique_ptr<TmpPages>> tp;
+  std::vector<uint64_t> ptrs;
+  int64_t c0 = 0;
+  const size_t row_bytes = (size_t)kvh * d * 2, page_bytes = (size_t)2 * kvh * KV_PAGE_TOKENS * d * 2;
+  for (int j = 0; j < n_seg; ++j) {
+    const int len = segs[2 * j], L = kv0[j] + len, np = (L + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
+    tp.emplace_back(new TmpPages());
+    if (int rc = build_tmp_pages(*tp.back(), (const char*)k + c0 * row_bytes, (const char*)v + c0 * row_bytes, L, kvh, d, st)) return rc;
+    seg[3 * j] = S, seg[3 * j + 1] = len, seg[3 * j + 2] = (int32_t)ptrs.size();
+    for (int i = 0; i < np; ++i) ptrs.push_back((uint64_t)(uintptr_t)tp.back()->store + (size_t)(np - 1 - i) * page_bytes);
+    S += len;
+    c0 += L;
+  }
+  const std::vector<int32_t> items = seg_items_of(seg, true, with_kv0 ? &kv0 : nullptr);
+  std::vector<int32_t> tab(seg);
+  tab.insert(tab.end(), items.begin(), items.end());
+  tab.insert(tab.end(), kv0.begin(), kv0.end());
+  uint64_t* d_ptrs = nullptr;
+  int32_t* d_tab = nullptr;
+  AHA_HIP_CHECK(hipMalloc((void**)&d_ptrs, ptrs.size() * 8));
+  if (hipMalloc((void**)&d_tab, tab.size() * 4) != hipSuccess) {
+    hipFree(d_ptrs);
+    set_error("debug_attn_prefill_segs: hipMalloc failed");
+    return AHA_ERR_HIP;
+  }
+  hipMemcpy(d_ptrs, ptrs.data(), ptrs.size() * 8, hipMemcpyHostToDevice);
+  hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
+  AttnPrefillArgs a{};
+  a.q = q; a.q_ld = (int64_t)nh * d; a.kv.page_ptrs = d_ptrs; a.kv.layer_off = 0; a.kv.kvh = kvh; a.kv.d = d; a.o = o;
+  a.S = S; a.nh = nh; a.kvh = kvh; a.d = d; a.kv_offset = 0; a.kv_total = S; a.causal = 1; a.scale = scale;
+  a.seg_tab = d_tab; a.seg_items = d_tab + seg.size(); a.n_items = (int)items.size() / 2;
+  a.seg_kv0 = with_kv0 ? d_tab + seg.size() + items.size() : nullptr;
+  launch_attn_prefill(a, st);
+  hipError_t e = hipGetLastError();
+  hipStreamSynchronize(st);
+  hipFree(d_ptrs);
+  hipFree(d_tab);
+  AHA_HIP_CHECK(e);
+  return AHA_OK;
+  API_GUARD_END
+}
+
 int aha_hip_attn_decode(const void* q, const void* k, const void* v, void* o, int32_t nh, int32_t kvh, int32_t d,
                         int32_t L, float scale, void* stream) {
   API_GUARD_BEGIN
@@ -612,6 +689,7 @@ int aha_hip_attn_decode_batch(const void* qkv, const void* q_norm_w, const void*
     t[GEN_ROW_KVLEN] = kv_len[r];
     t[GEN_ROW_NSPLIT] = attn_decode_nsplit(kv_len[r], g, 64);
     t[GEN_ROW_POS] = kv_len[r] - 1;
+    t[GEN_ROW_CTRROW] = r;
     max_split = std::max(max_split, t[GEN_ROW_NSPLIT]);
   }
   int32_t* d_tab = nullptr;
@@ -838,6 +916,7 @@ int aha_hip_embed(aha_model* m, const uint32_t* input_ids, size_t n_ids, float* 
     set_error("null model");
     return AHA_ERR_INVALID;
   }
+  if (int rc = engine_owns_cache(m, "embed")) return rc;
   return model_embed(m, input_ids, n_ids, out);
   API_GUARD_END
 }
@@ -848,6 +927,7 @@ int aha_hip_embed_batch(aha_model* m, const uint32_t* input_ids, const size_t* s
     set_error("null model");
     return AHA_ERR_INVALID;
   }
+  if (int rc = engine_owns_cache(m, "embed_batch")) return rc;
   return model_embed_batch(m, input_ids, seq_lens, n_seqs, max_tokens_per_pass, out);
   API_GUARD_END
 }
@@ -858,6 +938,7 @@ int aha_hip_generate_batch(aha_model* m, const uint32_t* input_ids, const size_t
     set_error("null model");
     return AHA_ERR_INVALID;
   }
+  if (int rc = engine_owns_cache(m, "generate_batch")) return rc;
   return model_generate_batch(m, input_ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, logits_out);
   API_GUARD_END
 }
@@ -880,6 +961,7 @@ int aha_hip_generate_batch_sampled(aha_model* m, const uint32_t* input_ids, cons
     set_error("null model");
     return AHA_ERR_INVALID;
   }
+  if (int rc = engine_owns_cache(m, "generate_batch_sampled")) return rc;
   return model_generate_batch_sampled(m, input_ids, seq_lens, n_seqs, params, max_new, max_tokens_per_pass, tokens_out, n_out, step_logits_out);
   API_GUARD_END
 }
@@ -898,8 +980,76 @@ int aha_hip_generate_batch_mm(aha_model* m, const uint32_t* input_ids, const siz
     set_error("null model");
     return AHA_ERR_INVALID;
   }
+  if (int rc = engine_owns_cache(m, "generate_batch_mm")) return rc;
   return model_generate_batch_mm(m, input_ids, seq_lens, n_seqs, mm, params, max_new, max_tokens_per_pass, tokens_out, n_out, step_logits_out);
   API_GUARD_END
+}
+int aha_hip_engine_create(aha_model* m, const aha_engine_config* cfg, aha_engine** out) {
+  API_GUARD_BEGIN
+  if (int rc = engine_config_check(cfg, nullptr, nullptr)) return rc;   // the config first: checked before the model is touched
+  if (!m || !out) {
+    set_error("engine_create: null model / out");
+    return AHA_ERR_INVALID;
+  }
+  return engine_create(m, cfg, out);
+  API_GUARD_END
+}
+void aha_hip_engine_destroy(aha_engine* e) {
+  try {
+    engine_destroy(e);
+  } catch (...) {
+  }
+}
+int aha_hip_engine_submit(aha_engine* e, const uint32_t* input_ids, size_t n_ids, const aha_mm_input* mm, const aha_sampling_params* params,
+                          size_t max_new, uint64_t* req_id) {
+  API_GUARD_BEGIN
+  if (params) {   // the parameters first, as generate_batch_sampled checks them
+    std::string why;
+    if (sampling_params_check(*params, &why)) {
+      set_error("engine_submit: params: " + why);
+      return AHA_ERR_INVALID;
+    }
+  }
+  if (!e) {
+    set_error("engine_submit: null engine");
+    return AHA_ERR_INVALID;
+  }
+  return engine_submit(e, input_ids, n_ids, mm, params, max_new, req_id);
+  API_GUARD_END
+}
+int aha_hip_engine_cancel(aha_engine* e, uint64_t req_id) {
+  API_GUARD_BEGIN
+  if (!e) {
+    set_error("engine_cancel: null engine");
+    return AHA_ERR_INVALID;
+  }
+  return engine_cancel(e, req_id);
+  API_GUARD_END
+}
+int aha_hip_engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, float* logits_out) {
+  API_GUARD_BEGIN
+  if (!e) {
+    set_error("engine_step: null engine");
+    return AHA_ERR_INVALID;
+  }
+  return engine_step(e, ev, cap, n_ev, logits_out);
+  API_GUARD_END
+}
+int aha_hip_engine_stats(const aha_engine* e, aha_engine_stats* out) {
+  API_GUARD_BEGIN
+  if (!e || !out) {
+    set_error("engine_stats: null engine / out");
+    return AHA_ERR_INVALID;
+  }
+  return engine_stats(e, out);
+  API_GUARD_END
+}
+int aha_hip_engine_debug_ctr_base(aha_engine* e, uint32_t base) {
+  if (!e) {
+    set_error("engine_debug_ctr_base: null engine");
+    return AHA_ERR_INVALID;
+  }
+  return engine_debug_ctr_base(e, base);
 }
 int aha_hip_config_parse(const char* model_dir, aha_model_desc* out) {
   API_GUARD_BEGIN

@@ -184,17 +184,22 @@ struct AttnPrefillArgs {
   const int32_t* seg_tab = nullptr;
   const int32_t* seg_items = nullptr;
   int n_items = 0;
+  // Optional cache prefix per segment (causal seg_tab launches; the engine's chunked prefill): seg_kv0 = (segments) int32 on the device.
+  // Segment j's q rows are then its cache positions kv0 .. kv0 + len - 1, row i seeing keys 0 .. kv0 + i on pages page0, page0 + 1, ...
+  // (the prefix's pages first).  nullptr = every kv0 0: the launch is the one without the field, bit for bit.
+  const int32_t* seg_kv0 = nullptr;
 };
 // The seg_items of a host seg_tab ({row0, len, page0} per segment): {segment, 64-row q block} pairs in segment order, then stable-sorted
-// most expensive first.  Causal: a block costs the keys its last row sees, min(len, (b + 1) * 64); non-causal: its segment's length.
-inline std::vector<int32_t> seg_items_of(const std::vector<int32_t>& seg_tab, bool causal) {
+// most expensive first.  Causal: a block costs the keys its last row sees, kv0 + min(len, (b + 1) * 64) (kv0: the segment's cache prefix,
+// AttnPrefillArgs::seg_kv0; none = 0); non-causal: its segment's length.
+inline std::vector<int32_t> seg_items_of(const std::vector<int32_t>& seg_tab, bool causal, const std::vector<int32_t>* kv0 = nullptr) {
   constexpr int QB = 64;   // q rows per block (launch_attn_prefill: 4 waves with seg_tab)
   std::vector<std::pair<int32_t, int32_t>> items;
   for (size_t j = 0; 3 * j < seg_tab.size(); ++j)
     for (int32_t b = 0; b * QB < seg_tab[3 * j + 1]; ++b) items.emplace_back((int32_t)j, b);
   auto cost = [&](const std::pair<int32_t, int32_t>& it) {
     const int32_t len = seg_tab[3 * (size_t)it.first + 1];
-    return causal ? std::min(len, (it.second + 1) * QB) : len;
+    return causal ? (kv0 ? (*kv0)[(size_t)it.first] : 0) + std::min(len, (it.second + 1) * QB) : len;
   };
   std::stable_sort(items.begin(), items.end(), [&](const auto& x, const auto& y) { return cost(x) > cost(y); });
   std::vector<int32_t> out;
@@ -316,6 +321,7 @@ constexpr int GEN_ROW_NSPLIT = 2;  // KV splits (attn_decode_nsplit of the row's
 constexpr int GEN_ROW_CTR = 3;     // the row's split-arrival counters before this step (the layer's target: + ctr_step * nsplit)
 constexpr int GEN_ROW_POS = 4;     // rope position of the step's token
 constexpr int GEN_ROW_SRC = 5;     // row of the previous step's token vector that holds this row's input token
+constexpr int GEN_ROW_CTRROW = 6;  // which (kvh, 32) block of head_ctr holds the row's counters (generate_batch: the row; the engine: its slot)
 void launch_gen_embed(const void* table, const uint32_t* tok_in, const int32_t* row_tab, int rows, void* x, int H, const float* inv_freq,
                       const int32_t* axis_map, float* rope, hipStream_t st);
 
@@ -332,7 +338,7 @@ struct AttnDecodeBatchArgs {
   float* part_o;              // (rows, max_nsplit, nh, 128)
   float* part_ml;             // (rows, max_nsplit, nh, 2)
   void* o;                    // (rows, nh * 128) bf16
-  unsigned* head_ctr;         // (rows, kvh, 32) monotonic split-arrival counters
+  unsigned* head_ctr;         // (counter rows, kvh, 32) monotonic split-arrival counters; row r uses block row_tab[r].ctrrow
   int ctr_step;               // target of row r = row_tab[r].ctr + ctr_step * nsplit
   int nh, kvh, max_nsplit;
   float eps, scale;

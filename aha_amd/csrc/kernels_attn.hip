@@ -61,7 +61,8 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu((NWV =
   // Packed independent sequences (a.seg_tab: model_embed_batch, generate_batch, the ViT's segments, the audio encoder's clips -- any DQK:
   // the q row address takes a.q_ld, the pages start at the segment's page0): the block's (segment, q block) is item
   // `it` of the host-sorted list (most expensive first) in either order; the segment's rows see only its own pages (page0 on), causally from
-  // its first token or (ViT) all of them.
+  // its first token or (ViT) all of them.  With a.seg_kv0 (causal) the segment's rows are cache positions kv0 .. kv0 + len - 1 and see the
+  // kv0 prefix tokens too: the kv_offset masking of the single-sequence path, per segment.
   int head, qblk, seg_rows = a.S, seg_off = a.kv_offset, seg_tot = a.kv_total, seg_row0 = 0, page0 = 0;
   if (a.seg_tab != nullptr) {
     int it;
@@ -78,7 +79,8 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu((NWV =
     const int sg = a.seg_items[2 * it];
     qblk = a.seg_items[2 * it + 1];
     seg_row0 = a.seg_tab[3 * sg], seg_rows = a.seg_tab[3 * sg + 1], page0 = a.seg_tab[3 * sg + 2];
-    seg_off = 0, seg_tot = seg_rows;
+    seg_off = a.seg_kv0 != nullptr ? a.seg_kv0[sg] : 0;
+    seg_tot = seg_off + seg_rows;
   } else if (a.nqb > 0) {
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int g = a.nh / a.kvh, hpx = a.nh >> 3;  // q heads per kv head / q heads per XCD

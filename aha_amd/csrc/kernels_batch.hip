@@ -240,7 +240,7 @@ __global__ __launch_bounds__(256, 2) void attn_decode_batch_kernel(AttnDecodeBat
   a.part_o = b.part_o + (int64_t)r * b.max_nsplit * b.nh * 128;
   a.part_ml = b.part_ml + (int64_t)r * b.max_nsplit * b.nh * 2;
   a.o = (bf16_t*)b.o + (int64_t)r * b.nh * 128;
-  a.head_ctr = b.head_ctr + (int64_t)r * b.kvh * 32;
+  a.head_ctr = b.head_ctr + (int64_t)__builtin_amdgcn_readfirstlane(t[GEN_ROW_CTRROW]) * b.kvh * 32;
   a.ctr_target = ctr0 + (unsigned)b.ctr_step * (unsigned)nsplit;
   a.trace = nullptr;
   a.nh = b.nh;

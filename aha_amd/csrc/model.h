@@ -182,6 +182,9 @@ struct aha_model {
   size_t h_pass_stage_cap = 0;
   float* p_pool = nullptr;   // model_embed_batch: a pass's (sequences, hidden) f32 embeddings
   size_t p_pool_cap = 0;
+  // the continuous batching engine that owns the cache while it exists (model.hip engine_*): every other entry that touches the cache
+  // returns AHA_ERR_STATE meanwhile (capi.hip)
+  aha_engine* engine = nullptr;
   // vision tower (Qwen3-VL)
   aha::VisionModel* vision = nullptr;
   // audio tower (Qwen3-ASR)
@@ -209,6 +212,15 @@ int model_generate_batch_sampled(aha_model* m, const uint32_t* ids, const size_t
 int model_generate_batch_mm(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
                             const aha_sampling_params* params, size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out,
                             float* step_logits_out);
+int engine_config_check(const aha_engine_config* cfg, size_t* budget_out, size_t* chunk_out);
+int engine_create(aha_model* m, const aha_engine_config* cfg, aha_engine** out);
+void engine_destroy(aha_engine* e);
+int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const aha_mm_input* mm, const aha_sampling_params* params, size_t max_new,
+                  uint64_t* req_id);
+int engine_cancel(aha_engine* e, uint64_t req_id);
+int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, float* logits_out);
+int engine_stats(const aha_engine* e, aha_engine_stats* out);
+int engine_debug_ctr_base(aha_engine* e, uint32_t base);
 int model_forward_initial(aha_model* m, const uint32_t* ids, size_t n, size_t offset, const aha_mm_input* mm,
                           float* logits_out, uint32_t* argmax_out);
 int model_forward_step(aha_model* m, uint32_t token, size_t offset, float* logits_out, uint32_t* argmax_out);

@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <deque>
 
 #include "common.h"
 #include "audio.h"
@@ -760,6 +761,7 @@ int model_create(aha_ctx* ctx, const aha_model_desc* desc, const aha_tensor_view
 
 void model_destroy(aha_model* m) {
   if (!m) return;
+  if (m->engine) engine_destroy(m->engine);   // an engine left open goes with its model (its handle is dead afterwards)
   hipStreamSynchronize(m->stream);
   for (auto& r : m->prof) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
   vision_destroy(m);
@@ -1934,7 +1936,8 @@ struct ClearCacheGuard {   // the cache is empty afterwards, on success and on e
 // last layer's output rows in p_x.  vis: the pass has visual rows (the tower's last pass scattered them): DeepStack adds after layer k <
 // n_deepstack (qwen3vl/model.rs:806-822), and on those layers the next in_norm does not ride on down_proj (as in forward_initial_impl).
 static int packed_layers(aha_model* m, int S, const uint64_t* page_ptrs, const int32_t* d_seg, const int32_t* d_items, int n_items,
-                         const int32_t* d_slot, const int32_t* d_prow, int npages, double attn_flops, bool vis = false) {
+                         const int32_t* d_slot, const int32_t* d_prow, int npages, double attn_flops, bool vis = false,
+                         const uint64_t* attn_page_ptrs = nullptr, const int32_t* d_kv0 = nullptr) {
   const aha_model_desc& c = m->desc;
   const int H = c.hidden_size, I = c.intermediate_size, d = c.head_dim, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
   const int nq = nh * d, nkv = kvh * d;
@@ -1971,6 +1974,8 @@ static int packed_layers(aha_model* m, int S, const uint64_t* page_ptrs, const i
       a.kv_offset = 0; a.kv_total = S; a.causal = 1; a.scale = m->attn_scale;
       a.q_norm_w = L.q_norm; a.q_rope_tab = m->p_rope; a.q_eps = c.rms_norm_eps;
       a.seg_tab = d_seg; a.seg_items = d_items; a.n_items = n_items;
+      if (attn_page_ptrs) a.kv.page_ptrs = attn_page_ptrs;   // chunked segments: their prefix pages, then the pages this pass writes
+      a.seg_kv0 = d_kv0;
       ProfScope ps(m, "attn_prefill", (double)S * nq * 4 + (double)S * nkv * 4, attn_flops);
       launch_attn_prefill(a, st);
     }
@@ -2006,42 +2011,55 @@ static int packed_layers(aha_model* m, int S, const uint64_t* page_ptrs, const i
 // {row0, len, page0} (AttnPrefillArgs::seg_tab) | items {segment, 64-row q block} (seg_items_of, causal) | per-row cache slots | per pass
 // page {first row, rows} | every segment's last row.  Segment j's rows row0 .. row0 + len - 1 are its cache positions 0 .. len - 1, on
 // pass pages page0, page0 + 1, ...; pass page p is logical page pages[p].
+// With cache prefixes (kv0: the engine's chunked prefill) the table ends in every segment's kv0 (AttnPrefillArgs::seg_kv0), segment j's rows
+// are its cache positions kv0 .. kv0 + len - 1, and the attention reads a page table of its own, attn_pages: per segment its prefix pages,
+// then the ones this pass writes.  `pages` (the rope kernel's table: the slots and page rows index it) lists only the written ones, so no
+// page of the rope kernel's list is without rows.
 struct PackedPass {
   int n_seg = 0, S = 0, npages = 0, n_items = 0;
-  size_t o_items = 0, o_slot = 0, o_prow = 0, o_last = 0;
+  size_t o_items = 0, o_slot = 0, o_prow = 0, o_last = 0, o_kv0 = 0;
   std::vector<int32_t> tab;
   std::vector<int32_t> pos;     // (3, S) positions
   std::vector<int64_t> pages;
+  std::vector<int64_t> attn_pages;   // kv0 only
 };
 
 // lens: the sequences' lengths; page0: each one's first logical page (its pages follow it); pos3: null, or per sequence its (3, len)
-// positions, an empty one meaning arange
-static PackedPass plan_packed_pass(const size_t* lens, int n_seg, const int64_t* page0, const std::vector<int32_t>* pos3) {
+// positions, an empty one meaning arange; kv0: null, or per sequence its cache prefix (a multiple of 64 tokens: the rows start a page),
+// positions then kv0 + i
+static PackedPass plan_packed_pass(const size_t* lens, int n_seg, const int64_t* page0, const std::vector<int32_t>* pos3,
+                                   const int32_t* kv0 = nullptr) {
   PackedPass pp;
   pp.n_seg = n_seg;
-  std::vector<int32_t> seg(3 * (size_t)n_seg);
+  std::vector<int32_t> seg(3 * (size_t)n_seg), rope_p0(n_seg), k0s(n_seg, 0);
   for (int j = 0; j < n_seg; ++j) {
-    const int len = (int)lens[j];
-    seg[3 * j] = pp.S, seg[3 * j + 1] = len, seg[3 * j + 2] = (int32_t)pp.pages.size();
-    for (int p = 0; p * KV_PAGE_TOKENS < len; ++p) pp.pages.push_back(page0[j] + p);
+    const int len = (int)lens[j], k0 = kv0 ? kv0[j] : 0;
+    k0s[j] = k0;
+    seg[3 * j] = pp.S, seg[3 * j + 1] = len, seg[3 * j + 2] = (int32_t)(kv0 ? pp.attn_pages.size() : pp.pages.size());
+    if (kv0)
+      for (int p = 0; p * KV_PAGE_TOKENS < k0 + len; ++p) pp.attn_pages.push_back(page0[j] + p);
+    rope_p0[j] = (int32_t)pp.pages.size();
+    for (int p = 0; p * KV_PAGE_TOKENS < len; ++p) pp.pages.push_back(page0[j] + k0 / KV_PAGE_TOKENS + p);
     pp.S += len;
   }
   const int S = pp.S;
   pp.npages = (int)pp.pages.size();
-  const std::vector<int32_t> items = seg_items_of(seg, true);
+  const std::vector<int32_t> items = seg_items_of(seg, true, kv0 ? &k0s : nullptr);
   pp.n_items = (int)items.size() / 2;
   pp.o_items = seg.size(), pp.o_slot = pp.o_items + items.size(), pp.o_prow = pp.o_slot + S, pp.o_last = pp.o_prow + 2 * (size_t)pp.npages;
+  pp.o_kv0 = pp.o_last + n_seg;
   std::vector<int32_t>& tab = pp.tab;
-  tab.resize(pp.o_last + n_seg);
+  tab.resize(pp.o_last + n_seg + (kv0 ? n_seg : 0));
   std::copy(seg.begin(), seg.end(), tab.begin());
   std::copy(items.begin(), items.end(), tab.begin() + pp.o_items);
+  if (kv0) std::copy(k0s.begin(), k0s.end(), tab.begin() + pp.o_kv0);
   pp.pos.resize(3 * (size_t)S);
   for (int j = 0; j < n_seg; ++j) {
-    const int r0 = seg[3 * j], len = seg[3 * j + 1], p0 = seg[3 * j + 2];
+    const int r0 = seg[3 * j], len = seg[3 * j + 1], p0 = rope_p0[j], k0 = k0s[j];
     const int32_t* pj = pos3 && !pos3[j].empty() ? pos3[j].data() : nullptr;
     for (int i = 0; i < len; ++i) {
       tab[pp.o_slot + r0 + i] = p0 * KV_PAGE_TOKENS + i;
-      for (int a = 0; a < 3; ++a) pp.pos[(size_t)a * S + r0 + i] = pj ? pj[(size_t)a * len + i] : i;
+      for (int a = 0; a < 3; ++a) pp.pos[(size_t)a * S + r0 + i] = pj ? pj[(size_t)a * len + i] : k0 + i;
     }
     for (int p = 0; p * KV_PAGE_TOKENS < len; ++p) {
       tab[pp.o_prow + 2 * (size_t)(p0 + p)] = r0 + p * KV_PAGE_TOKENS;
@@ -2077,7 +2095,8 @@ static int grow_pass_buffer(aha_model* m, T** buf, size_t* cap, size_t n, bool p
 // wait: every pass ends in a synchronise (its caller's tail, which needs one for its output anyway), so the previous pass's copies out
 // of it have landed.
 static int run_packed_pass(aha_model* m, const PackedPass& pp, const uint32_t* ids, const uint64_t* page_ptrs,
-                           const std::vector<VisRequest>& vreqs = {}, const std::vector<AudRequest>& areqs = {}) {
+                           const std::vector<VisRequest>& vreqs = {}, const std::vector<AudRequest>& areqs = {},
+                           const uint64_t* attn_page_ptrs = nullptr) {
   const aha_model_desc& c = m->desc;
   const int S = pp.S, H = c.hidden_size, nq = c.num_attention_heads * c.head_dim;
   hipStream_t st = m->stream;
@@ -2109,9 +2128,12 @@ static int run_packed_pass(aha_model* m, const PackedPass& pp, const uint32_t* i
   if (!areqs.empty() && (rc = audio_forward_requests(m, areqs.data(), areqs.size(), m->p_x))) return rc;
   launch_rope_table(m->p_pos, S, m->d_inv_freq, m->d_axis_map, S, m->p_rope, st);   // the packed rows' cos / sin, once for all layers
   double attn_flops = 0;
-  for (int j = 0; j < pp.n_seg; ++j) attn_flops += 4.0 * pp.tab[3 * j + 1] * (0.5 * pp.tab[3 * j + 1]) * nq;
+  const bool has_kv0 = !pp.attn_pages.empty();
+  for (int j = 0; j < pp.n_seg; ++j)
+    attn_flops += 4.0 * pp.tab[3 * j + 1] * ((has_kv0 ? pp.tab[pp.o_kv0 + j] : 0) + 0.5 * pp.tab[3 * j + 1]) * nq;
   const int32_t* t = m->p_pass_tab;
-  return packed_layers(m, S, page_ptrs, t, t + pp.o_items, pp.n_items, t + pp.o_slot, t + pp.o_prow, pp.npages, attn_flops, !vreqs.empty());
+  return packed_layers(m, S, page_ptrs, t, t + pp.o_items, pp.n_items, t + pp.o_slot, t + pp.o_prow, pp.npages, attn_flops, !vreqs.empty(),
+                       has_kv0 ? attn_page_ptrs : nullptr, has_kv0 ? t + pp.o_kv0 : nullptr);
 }
 
 static int embed_pass(aha_model* m, const uint32_t* ids, const size_t* lens, int n_seg, float* out) {
@@ -2242,7 +2264,16 @@ struct GenCall {
   uint32_t* tokens_out = nullptr;
   size_t* n_out = nullptr;
   float* step_logits_out = nullptr;
+  // the engine (aha_engine): sequence j's generated tokens at seq_tokens[j] instead of tokens_out + j * max_new; row r's logits to
+  // row_logits[r] (null: not copied) instead of step_logits_out; the decode steps' page table (null: the model's)
+  uint32_t* const* seq_tokens = nullptr;
+  float* const* row_logits = nullptr;
+  const uint64_t* dec_pages = nullptr;
 };
+
+static inline uint32_t* gen_seq_tokens(const GenCall& gc, int j) {
+  return gc.seq_tokens ? gc.seq_tokens[j] : gc.tokens_out + (size_t)j * gc.max_new;
+}
 
 // final RMSNorm + lm_head + argmax of `rows` rows of gc.x (bf16, pitch H) -> logits rows / token vector entries from `row0` on
 static void gen_head(aha_model* m, GenCall& gc, int row0, int rows, uint32_t* tok_out) {
@@ -2339,19 +2370,16 @@ static int check_mm_requests(aha_model* m, const uint32_t* ids, const size_t* se
   return AHA_OK;
 }
 
-// The call's device buffers (decode rows, logits, token vectors, attention partials, the pass page table) and pinned row table / tokens
-static int gen_call_alloc(aha_model* m, DevBufs& bufs, GenCall& gc, const size_t* seq_lens) {
+// The call's device buffers (decode rows, logits, token vectors, attention partials, the pass page table) and pinned row table / tokens;
+// gc.max_nsplit set by the caller
+static int gen_call_alloc(aha_model* m, DevBufs& bufs, GenCall& gc, size_t max_pass_pages) {
   const aha_model_desc& c = m->desc;
   const int n = gc.n, H = gc.H, V = gc.V, I = c.intermediate_size, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
   const int nq = nh * 128, nkv = kvh * 128;
-  for (int j = 0; j < n; ++j)
-    gc.max_nsplit = std::max(gc.max_nsplit, attn_decode_nsplit((int)(seq_lens[j] + gc.max_new), nh / kvh, m->max_nsplit));
   size_t ws = 0;
   const int shapes[5][2] = {{nq + 2 * nkv, H}, {H, nq}, {2 * I, H}, {H, I}, {V, H}};
   for (auto& sh : shapes) ws = std::max(ws, gemv_rows_ws_floats(std::min(n, GEN_ROW_GROUP), sh[0], sh[1]));
   const int tiles = gemv_rows_num_tiles(V);
-  size_t max_pass_pages = 0;
-  for (int j = 0; j < n; ++j) max_pass_pages += (seq_lens[j] + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
   int rc;
   if ((rc = bufs.alloc(&gc.ws, ws)) || (rc = bufs.alloc((bf16_t**)&gc.x, (size_t)n * H)) || (rc = bufs.alloc((bf16_t**)&gc.h, (size_t)n * H)) ||
       (rc = bufs.alloc((bf16_t**)&gc.qkv, (size_t)n * (nq + 2 * nkv))) || (rc = bufs.alloc((bf16_t**)&gc.attn, (size_t)n * nq)) ||
@@ -2376,6 +2404,22 @@ struct GenChoice {
   std::vector<int> mode, slot, fb_rows;   // finish_step's per-row scratch
 };
 
+// The candidate step's buffers for gc.n rows: ctx_cap penalty-context ids, n_fb full logits rows on the host
+static int gen_choice_alloc(DevBufs& bufs, const GenCall& gc, size_t ctx_cap, size_t n_fb, GenChoice& ch) {
+  const int n = gc.n;
+  const size_t V = (size_t)gc.V;
+  ch.nw = sample_stage1_waves(gc.V);
+  int rc;
+  const size_t cand = (size_t)n * (ch.nw + 16) * 64;
+  if ((rc = bufs.alloc(&ch.d_stab, (size_t)n * SAMPLE_ROW_WORDS)) || (rc = bufs.alloc(&ch.d_sctx, ctx_cap)) || (rc = bufs.alloc(&ch.d_cval, cand)) ||
+      (rc = bufs.alloc(&ch.d_cidx, cand)) || (rc = bufs.alloc(&ch.d_part, 2 * (size_t)n * ch.nw)) ||
+      (rc = bufs.alloc(&ch.d_sout, (size_t)n * SAMPLE_OUT_WORDS)) || (rc = bufs.alloc_host(&ch.h_stab, (size_t)n * SAMPLE_ROW_WORDS)) ||
+      (rc = bufs.alloc_host(&ch.h_sctx, ctx_cap)) || (rc = bufs.alloc_host(&ch.h_sout, (size_t)n * SAMPLE_OUT_WORDS)) ||
+      (rc = bufs.alloc_host(&ch.h_fb, n_fb * V)))
+    return rc;
+  return AHA_OK;
+}
+
 static int gen_choice_init(DevBufs& bufs, const GenCall& gc, const aha_sampling_params* params, GenChoice& ch) {
   const int n = gc.n, V = gc.V;
   if (!sample_shape_ok(V, 64)) {
@@ -2383,7 +2427,6 @@ static int gen_choice_init(DevBufs& bufs, const GenCall& gc, const aha_sampling_
     return AHA_ERR_UNSUPPORTED;
   }
   ch.samplers.resize(n);
-  ch.nw = sample_stage1_waves(V);
   size_t ctx_cap = 0, n_fb = 0;
   int rc;
   for (int j = 0; j < n; ++j) {
@@ -2393,14 +2436,7 @@ static int gen_choice_init(DevBufs& bufs, const GenCall& gc, const aha_sampling_
     // a sequence that may need its full logits row: Sampling::All, oversized k, any TopP (nucleus wider than the candidates)
     if (S.kind != SAMPLE_ARGMAX && (S.kind == SAMPLE_TOPP || sampler_candidates_needed(S, (size_t)V) == 0)) ++n_fb;
   }
-  const size_t cand = (size_t)n * (ch.nw + 16) * 64;
-  if ((rc = bufs.alloc(&ch.d_stab, (size_t)n * SAMPLE_ROW_WORDS)) || (rc = bufs.alloc(&ch.d_sctx, ctx_cap)) || (rc = bufs.alloc(&ch.d_cval, cand)) ||
-      (rc = bufs.alloc(&ch.d_cidx, cand)) || (rc = bufs.alloc(&ch.d_part, 2 * (size_t)n * ch.nw)) ||
-      (rc = bufs.alloc(&ch.d_sout, (size_t)n * SAMPLE_OUT_WORDS)) || (rc = bufs.alloc_host(&ch.h_stab, (size_t)n * SAMPLE_ROW_WORDS)) ||
-      (rc = bufs.alloc_host(&ch.h_sctx, ctx_cap)) || (rc = bufs.alloc_host(&ch.h_sout, (size_t)n * SAMPLE_OUT_WORDS)) ||
-      (rc = bufs.alloc_host(&ch.h_fb, n_fb * (size_t)V)))
-    return rc;
-  return AHA_OK;
+  return gen_choice_alloc(bufs, gc, ctx_cap, n_fb, ch);
 }
 
 // The end of every step (the prefill's first tokens, then each decode step): the tokens of rows r = 0 .. R-1 (row r = sequence seqs[r])
@@ -2439,7 +2475,7 @@ static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::
       const float inv_t = S.kind == SAMPLE_ARGMAX ? 1.0f : (float)(1.0 / (double)(float)S.temperature);
       const size_t c0 = nc;
       if (pen != 1.0f) {   // the distinct in-vocabulary ids of the last n_ctx generated (apply_repeat_penalty's HashSet)
-        const uint32_t* g = gc.tokens_out + (size_t)j * max_new + gc.n_out[j] - n_ctx;
+        const uint32_t* g = gen_seq_tokens(gc, j) + gc.n_out[j] - n_ctx;
         for (size_t i = 0; i < n_ctx; ++i)
           if (g[i] < (uint32_t)V) ch.h_sctx[nc++] = g[i];
         std::sort(ch.h_sctx + c0, ch.h_sctx + nc);
@@ -2467,10 +2503,14 @@ static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::
       AHA_HIP_CHECK(hipMemcpyAsync(ch.h_sout, ch.d_sout, (size_t)ns * SAMPLE_OUT_WORDS * 4, hipMemcpyDeviceToHost, st));
     }
   }
-  if (gc.step_logits_out)
+  if (gc.row_logits) {
+    for (int r = 0; r < R; ++r)
+      if (gc.row_logits[r]) AHA_HIP_CHECK(hipMemcpyAsync(gc.row_logits[r], gc.logits + (size_t)r * V, (size_t)V * 4, hipMemcpyDeviceToHost, st));
+  } else if (gc.step_logits_out) {
     for (int r = 0; r < R; ++r)
       AHA_HIP_CHECK(hipMemcpyAsync(gc.step_logits_out + ((size_t)seqs[r] * max_new + gc.n_out[seqs[r]]) * V, gc.logits + (size_t)r * V,
                                    (size_t)V * 4, hipMemcpyDeviceToHost, st));
+  }
   AHA_HIP_CHECK(hipMemcpyAsync(h_tok, tok_dev, (size_t)R * 4, hipMemcpyDeviceToHost, st));
   AHA_HIP_CHECK(hipStreamSynchronize(st));
   if (!sampled) return AHA_OK;
@@ -2482,7 +2522,7 @@ static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::
       const float* o = ch.h_sout + (size_t)ch.slot[r] * SAMPLE_OUT_WORDS;
       const int k = ch.h_stab[(size_t)ch.slot[r] * SAMPLE_ROW_WORDS + SAMPLE_ROW_K];
       const int prc = sampler_pick(ch.samplers[j], o, reinterpret_cast<const uint32_t*>(o + 66), k, o[64], o[65], nullptr, (size_t)V,
-                                   gc.tokens_out + (size_t)j * max_new, gc.n_out[j], &h_tok[r]);
+                                   gen_seq_tokens(gc, j), gc.n_out[j], &h_tok[r]);
       if (prc < 0) return prc;
       if (prc == AHA_OK) continue;
     }
@@ -2494,7 +2534,7 @@ static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::
     AHA_HIP_CHECK(hipStreamSynchronize(st));
     for (size_t f = 0; f < ch.fb_rows.size(); ++f) {
       const int r = ch.fb_rows[f], j = seqs[r];
-      const int prc = sampler_pick(ch.samplers[j], nullptr, nullptr, 0, 0.f, 0.f, ch.h_fb + f * V, (size_t)V, gc.tokens_out + (size_t)j * max_new,
+      const int prc = sampler_pick(ch.samplers[j], nullptr, nullptr, 0, 0.f, 0.f, ch.h_fb + f * V, (size_t)V, gen_seq_tokens(gc, j),
                                    gc.n_out[j], &h_tok[r]);
       if (prc != AHA_OK) return prc < 0 ? prc : AHA_ERR_STATE;
     }
@@ -2527,7 +2567,7 @@ static void gen_decode_step(aha_model* m, GenCall& gc, int R, int max_split, dou
     }
     {   // q/k norm + rope + KV append + attention of every row over its own pages (modules.rs:544-574, 757-813)
       AttnDecodeBatchArgs b{};
-      b.qkv = gc.qkv; b.q_norm_w = Lw.q_norm; b.k_norm_w = Lw.k_norm; b.rope = gc.rope; b.page_ptrs = m->d_page_ptrs;
+      b.qkv = gc.qkv; b.q_norm_w = Lw.q_norm; b.k_norm_w = Lw.k_norm; b.rope = gc.rope; b.page_ptrs = gc.dec_pages ? gc.dec_pages : m->d_page_ptrs;
       b.layer_off = (uint64_t)li * m->layer_stride; b.row_tab = gc.rowtab; b.part_o = gc.part_o; b.part_ml = gc.part_ml; b.o = gc.attn;
       b.head_ctr = gc.ctr; b.ctr_step = li + 1; b.nh = nh; b.kvh = kvh; b.max_nsplit = gc.max_nsplit; b.eps = c.rms_norm_eps;
       b.scale = m->attn_scale;
@@ -2614,7 +2654,12 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
   gc.n = n, gc.V = V, gc.H = c.hidden_size, gc.max_new = max_new;
   gc.tokens_out = tokens_out, gc.n_out = n_out, gc.step_logits_out = step_logits_out;
   GenChoice ch;
-  if ((rc = gen_call_alloc(m, bufs, gc, seq_lens)) || (params && (rc = gen_choice_init(bufs, gc, params, ch)))) return rc;
+  size_t max_pass_pages = 0;
+  for (int j = 0; j < n; ++j) {
+    gc.max_nsplit = std::max(gc.max_nsplit, attn_decode_nsplit((int)(seq_lens[j] + max_new), g, m->max_nsplit));
+    max_pass_pages += (seq_lens[j] + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
+  }
+  if ((rc = gen_call_alloc(m, bufs, gc, max_pass_pages)) || (params && (rc = gen_choice_init(bufs, gc, params, ch)))) return rc;
 
   // ---- prefill: packed passes ----
   for (const PassRange& p : split_passes(seq_lens, n_seqs, max_tokens_per_pass))
@@ -2663,7 +2708,8 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
       t[GEN_ROW_CTR] = (int32_t)ctr_acc[r];
       t[GEN_ROW_POS] = (int32_t)(kv_len - 1 + rope_delta[j]);   // seqlen_offset + rope_delta (qwen3vl/model.rs:1235-1264)
       t[GEN_ROW_SRC] = src_row[j];
-      t[6] = t[7] = 0;
+      t[GEN_ROW_CTRROW] = r;
+      t[7] = 0;
       if (ns > 1) ctr_acc[r] += (unsigned)L * (unsigned)ns;   // a single split never touches its counter
       max_split = std::max(max_split, ns);
       kv_tokens += kv_len;
@@ -2704,6 +2750,475 @@ int model_generate_batch_mm(aha_model* m, const uint32_t* ids, const size_t* seq
                             const aha_sampling_params* params, size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out,
                             float* step_logits_out) {
   return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, nullptr, params, step_logits_out, mm);
+}
+
+// ---- continuous batching engine (aha_hip_engine_*) ------------------------------------------------------------------------------
+// generate_generic's stream (common/generate.rs:231-368) for requests that come and go: the engine owns the model's cache (kv_pages pages
+// reserved up front, a free list) and max_running slots.  A slot owns the window [slot * kv_pages, + kv_pages) of the engine's device page
+// table; a request takes ceil((len + max_new) / 64) pages from the free list when it is admitted, writes them into its slot's window, and
+// gives them back when it ends or is cancelled.  A step = the prefill work (one packed pass: whole prompts of requests admitted this step in
+// submission order under max_tokens_per_step, then at most one 64-aligned chunk of a long TEXT prompt, with its cache prefix in the
+// attention: AttnPrefillArgs::seg_kv0) -> the first tokens of the prompts it completes, then one gen_decode_step over every request that
+// had a first token before the step, then its gen_finish_step.  The pieces are generate_batch_impl's: a request's bits are those of its
+// prompt's packed pass (the same composition through generate_batch* gives the same bits: the decode rows are row-isolated) -- requests
+// with images, video or audio are prefilled whole, never chunked.
+// Split counters: slot s owns head_ctr block s (GEN_ROW_CTRROW) and ctr_acc[s], both reset to ctr_base when a slot is taken.  The kernel's
+// "last split" test is prev + 1 == ctr0 + layer * nsplit in 32-bit unsigned arithmetic, so a counter that wraps past 2^32 still meets its
+// target exactly once: a false match would need 2^32 arrivals inside one launch (aha_hip_engine_debug_ctr_base moves the base near the wrap
+// point for the test).
+namespace {
+struct EngReq {
+  uint64_t id = 0;
+  std::vector<uint32_t> ids;
+  const aha_mm_input* mm = nullptr;   // the caller's, valid until the request's first token
+  bool whole = false;                 // images / video / audio: prefilled whole
+  std::vector<int32_t> pos3;          // (3, len) of an image / video request, else empty
+  int64_t rope_delta = 0;
+  aha_sampling_params params{};
+  size_t max_new = 0, npages = 0, done = 0;   // done: prompt tokens prefilled
+  int slot = -1;
+  bool started = false, cancel = false;
+  std::vector<uint32_t> toks;         // capacity max_new: gen_finish_step reads the penalty context through a pointer to it
+};
+struct EngSeg {
+  EngReq* q;
+  int kv0, len;
+};
+}  // namespace
+}  // namespace aha
+
+struct aha_engine {
+  aha_model* m = nullptr;
+  size_t max_running = 0, kv_pages = 0, budget = 0, chunk = 0;
+  uint64_t next_id = 1;
+  std::deque<aha::EngReq*> waiting;
+  std::vector<aha::EngReq*> slots;
+  std::vector<std::vector<uint64_t>> slot_pages;
+  std::vector<uint64_t> free_pages;   // page addresses; taken from the back
+  std::vector<aha_engine_event> pending;   // cancellations of requests that never ran
+  std::vector<unsigned> ctr_acc;
+  unsigned ctr_base = 0;
+  std::vector<size_t> n_out;          // per slot: tokens so far
+  std::vector<uint32_t*> seq_tok;     // per slot: EngReq::toks
+  std::vector<float*> row_logits;
+  aha::DevBufs bufs{nullptr, {}, {}};
+  aha::GenCall gc;
+  aha::GenChoice ch;
+  uint64_t* d_win = nullptr;          // (max_running, kv_pages) page table of the slots
+  uint32_t* d_tok_in = nullptr;       // a decode step's input tokens
+  uint32_t* h_tok_in = nullptr;       // pinned
+  size_t ctx_cap = 0;
+  ~aha_engine() {
+    for (aha::EngReq* q : waiting) delete q;
+    for (aha::EngReq* q : slots) delete q;
+  }
+};
+
+namespace aha {
+
+static bool engine_is_stop(const aha_model_desc& c, uint32_t t) {
+  for (int e = 0; e < c.n_stop_tokens; ++e)
+    if (t == c.stop_tokens[e]) return true;
+  return false;
+}
+
+// The config's own rules (no model needed): the effective step budget and chunk
+int engine_config_check(const aha_engine_config* cfg, size_t* budget_out, size_t* chunk_out) {
+  if (!cfg) {
+    set_error("engine_create: null config");
+    return AHA_ERR_INVALID;
+  }
+  const size_t budget = cfg->max_tokens_per_step ? cfg->max_tokens_per_step : PACKED_PASS_ROWS;
+  const size_t chunk = cfg->prefill_chunk ? cfg->prefill_chunk : budget / KV_PAGE_TOKENS * KV_PAGE_TOKENS;
+  if (cfg->max_running < 1 || cfg->max_running > AHA_ENGINE_MAX_RUNNING || cfg->kv_pages < 1 || cfg->kv_pages > ((size_t)1 << 18) ||
+      budget < (size_t)KV_PAGE_TOKENS || budget > ((size_t)1 << 24) || chunk < (size_t)KV_PAGE_TOKENS || chunk % KV_PAGE_TOKENS || chunk > budget) {
+    set_error("engine_create: bad config (max_running 1 .. " + std::to_string(AHA_ENGINE_MAX_RUNNING) +
+              ", kv_pages 1 .. 2^18, max_tokens_per_step 0 or >= 64, prefill_chunk 0 or a multiple of 64 within max_tokens_per_step)");
+    return AHA_ERR_INVALID;
+  }
+  if (budget_out) *budget_out = budget;
+  if (chunk_out) *chunk_out = chunk;
+  return AHA_OK;
+}
+
+int engine_create(aha_model* m, const aha_engine_config* cfg, aha_engine** out) {
+  const aha_model_desc& c = m->desc;
+  size_t budget = 0, chunk = 0;
+  if (int rc = engine_config_check(cfg, &budget, &chunk)) return rc;
+  if (!out) {
+    set_error("engine_create: null out");
+    return AHA_ERR_INVALID;
+  }
+  if (m->engine) {
+    set_error("engine_create: the model already has an engine");
+    return AHA_ERR_STATE;
+  }
+  if (c.arch != AHA_ARCH_QWEN3 && c.arch != AHA_ARCH_QWEN3VL && c.arch != AHA_ARCH_QWEN3ASR) {
+    set_error("engine_create: Qwen3, Qwen3-VL and Qwen3-ASR only");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  if (m->tp_size > 1 || m->cp_size > 1 || c.head_dim != 128) {
+    set_error("engine_create: a single-GPU model with head_dim 128 only (no tensor / context parallelism)");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  if (!sample_shape_ok(c.vocab_size, 64)) {
+    set_error("engine_create: vocabulary too large for the candidate step");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
+  int rc;
+  if ((rc = model_clear_cache(m)) || (rc = model_ensure_pages(m, cfg->kv_pages * KV_PAGE_TOKENS))) return rc;
+  aha_engine* e = new aha_engine();
+  e->m = m;
+  e->max_running = cfg->max_running, e->kv_pages = cfg->kv_pages, e->budget = budget, e->chunk = chunk;
+  e->bufs.st = m->stream;
+  const int n = (int)e->max_running, kvh = c.num_key_value_heads;
+  e->slots.assign(n, nullptr);
+  e->slot_pages.resize(n);
+  e->ctr_acc.assign(n, 0u);
+  e->n_out.assign(n, 0);
+  e->seq_tok.assign(n, nullptr);
+  e->row_logits.assign(n, nullptr);
+  for (size_t p = e->kv_pages; p > 0; --p) e->free_pages.push_back(m->h_page_ptrs[p - 1]);   // page 0 is taken first
+  GenCall& gc = e->gc;
+  gc.n = n, gc.V = c.vocab_size, gc.H = c.hidden_size, gc.max_new = 0;
+  gc.max_nsplit = attn_decode_nsplit((int)std::min<size_t>(e->kv_pages * KV_PAGE_TOKENS, (size_t)1 << 24), c.num_attention_heads / kvh, m->max_nsplit);
+  gc.n_out = e->n_out.data(), gc.seq_tokens = e->seq_tok.data(), gc.row_logits = e->row_logits.data();
+  e->ctx_cap = (size_t)n * 64;
+  if ((rc = gen_call_alloc(m, e->bufs, gc, 2 * e->kv_pages)) || (rc = gen_choice_alloc(e->bufs, gc, e->ctx_cap, (size_t)n, e->ch)) ||
+      (rc = e->bufs.alloc(&e->d_win, (size_t)n * e->kv_pages, true)) || (rc = e->bufs.alloc(&e->d_tok_in, (size_t)n)) ||
+      (rc = e->bufs.alloc_host(&e->h_tok_in, (size_t)n))) {
+    delete e;
+    model_clear_cache(m);
+    return rc;
+  }
+  gc.dec_pages = e->d_win;
+  e->ch.samplers.resize(n);
+  (void)kvh;
+  m->engine = e;
+  *out = e;
+  return AHA_OK;
+}
+
+void engine_destroy(aha_engine* e) {
+  if (!e) return;
+  aha_model* m = e->m;
+  hipSetDevice(m->ctx->device);
+  delete e;   // DevBufs drains the stream before it frees
+  m->engine = nullptr;
+  model_clear_cache(m);
+}
+
+int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const aha_mm_input* mm, const aha_sampling_params* params, size_t max_new,
+                  uint64_t* req_id) {
+  aha_model* m = e->m;
+  const aha_model_desc& c = m->desc;
+  if (!ids || !req_id) {
+    set_error("engine_submit: null input_ids / req_id");
+    return AHA_ERR_INVALID;
+  }
+  if (max_new == 0) {
+    set_error("engine_submit: max_new must be at least 1");
+    return AHA_ERR_INVALID;
+  }
+  if (max_new > ((size_t)1 << 20)) {
+    set_error("engine_submit: at most 2^20 new tokens");
+    return AHA_ERR_INVALID;
+  }
+  int rc = check_batch_ids(c, "engine_submit", ids, &n_ids, 1, max_new);
+  if (rc) return rc;
+  std::vector<std::vector<int32_t>> pos3(1);
+  std::vector<int64_t> rope_delta(1, 0);
+  if (mm && (rc = check_mm_requests(m, ids, &n_ids, 1, &mm, pos3, rope_delta))) return rc;
+  const size_t npages = (n_ids + max_new + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
+  if (npages > e->kv_pages) {
+    set_error("engine_submit: the request needs " + std::to_string(npages) + " pages, the engine has " + std::to_string(e->kv_pages));
+    return AHA_ERR_OOM;
+  }
+  EngReq* q = new EngReq();
+  q->id = e->next_id++;
+  q->ids.assign(ids, ids + n_ids);
+  const bool vis = mm && (mm->n_images > 0 || mm->n_videos > 0);
+  q->mm = mm && (vis || m->audio) ? mm : nullptr;
+  q->whole = q->mm != nullptr;
+  q->pos3 = std::move(pos3[0]);
+  q->rope_delta = rope_delta[0];
+  if (params) q->params = *params;
+  else q->params = aha_sampling_params{0.f, 1.f, 0, 1.f, 64, 0u, 299792458ull};   // ArgMax, no penalty: the device argmax
+  q->max_new = max_new;
+  q->npages = npages;
+  q->toks.reserve(max_new);
+  e->waiting.push_back(q);
+  *req_id = q->id;
+  return AHA_OK;
+}
+
+int engine_cancel(aha_engine* e, uint64_t req_id) {
+  for (auto it = e->waiting.begin(); it != e->waiting.end(); ++it)
+    if ((*it)->id == req_id) {
+      e->pending.push_back(aha_engine_event{req_id, AHA_ENGINE_NO_TOKEN, AHA_ENGINE_EV_CANCELLED});
+      delete *it;
+      e->waiting.erase(it);
+      return AHA_OK;
+    }
+  for (EngReq* q : e->slots)
+    if (q && q->id == req_id) {
+      q->cancel = true;
+      return AHA_OK;
+    }
+  set_error("engine_cancel: no waiting or running request " + std::to_string(req_id));
+  return AHA_ERR_INVALID;
+}
+
+int engine_stats(const aha_engine* e, aha_engine_stats* out) {
+  out->waiting = e->waiting.size();
+  out->running = 0;
+  for (const EngReq* q : e->slots) out->running += q != nullptr;
+  out->free_pages = e->free_pages.size();
+  out->total_pages = e->kv_pages;
+  return AHA_OK;
+}
+
+int engine_debug_ctr_base(aha_engine* e, uint32_t base) {
+  e->ctr_base = base;
+  return AHA_OK;
+}
+
+static void engine_release(aha_engine* e, int s) {
+  EngReq* q = e->slots[s];
+  std::vector<uint64_t>& pg = e->slot_pages[s];
+  for (size_t i = pg.size(); i > 0; --i) e->free_pages.push_back(pg[i - 1]);
+  pg.clear();
+  e->slots[s] = nullptr;
+  delete q;
+}
+
+// a waiting request into a free slot: its pages from the free list into the slot's window, its sampler, its counters reset
+static int engine_admit(aha_engine* e, EngReq* q, int s) {
+  aha_model* m = e->m;
+  hipStream_t st = m->stream;
+  std::vector<uint64_t>& pg = e->slot_pages[s];
+  for (size_t i = 0; i < q->npages; ++i) {
+    pg.push_back(e->free_pages.back());
+    e->free_pages.pop_back();
+  }
+  q->slot = s;
+  e->slots[s] = q;   // from here on a failure releases the slot and its pages with the request
+  const int kvh = m->desc.num_key_value_heads;
+  const std::vector<unsigned> base((size_t)kvh * 32, e->ctr_base);
+  int rc = AHA_OK;
+  if (hipMemcpyAsync(e->d_win + (size_t)s * e->kv_pages, pg.data(), pg.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(e->gc.ctr + (size_t)s * kvh * 32, base.data(), base.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess) {   // (pageable sources)
+    set_error("engine_step: uploading a slot's page window / counters failed");
+    rc = AHA_ERR_HIP;
+  }
+  e->ctr_acc[s] = e->ctr_base;
+  if (rc || (rc = host_sampler_init(e->ch.samplers[s], q->params))) {
+    engine_release(e, s);
+    return rc;
+  }
+  const HostSampler& S = e->ch.samplers[s];
+  size_t need = 0;   // the penalty contexts of every slot's sampler
+  for (int k = 0; k < (int)e->max_running; ++k) {
+    const EngReq* o = k == s ? q : e->slots[k];
+    if (o && e->ch.samplers[k].repeat_penalty != 1.0f) need += std::min<size_t>(o->max_new, (size_t)e->ch.samplers[k].repeat_last_n);
+  }
+  (void)S;
+  if (need > e->ctx_cap) {   // grow the penalty-context buffers (the stream has drained)
+    const size_t cap = std::max(need, 2 * e->ctx_cap);
+    uint32_t *d = nullptr, *h = nullptr;
+    if ((rc = e->bufs.alloc(&d, cap)) || (rc = e->bufs.alloc_host(&h, cap))) {
+      engine_release(e, s);
+      return rc;
+    }
+    e->ch.d_sctx = d, e->ch.h_sctx = h;
+    e->ctx_cap = cap;
+  }
+  e->n_out[s] = 0;
+  e->seq_tok[s] = q->toks.data();
+  return AHA_OK;
+}
+
+int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, float* logits_out) {
+  aha_model* m = e->m;
+  const aha_model_desc& c = m->desc;
+  hipStream_t st = m->stream;
+  GenCall& gc = e->gc;
+  const int V = c.vocab_size, g = c.num_attention_heads / c.num_key_value_heads, L = c.num_hidden_layers;
+  if (!ev || !n_ev) {
+    set_error("engine_step: null events / n_ev");
+    return AHA_ERR_INVALID;
+  }
+  *n_ev = 0;
+  size_t n_cancel = e->pending.size();
+  for (const EngReq* q : e->slots) n_cancel += q && q->cancel;
+  if (cap < n_cancel + e->max_running) {
+    set_error("engine_step: room for " + std::to_string(cap) + " events, a step may emit " + std::to_string(n_cancel + e->max_running));
+    return AHA_ERR_INVALID;
+  }
+  AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
+  size_t ne = 0;
+  auto emit = [&](uint64_t id, uint32_t tok, uint32_t flags) { ev[ne++] = aha_engine_event{id, tok, flags}; };
+  // 1. cancellations
+  for (const aha_engine_event& p : e->pending) ev[ne++] = p;
+  e->pending.clear();
+  for (int s = 0; s < (int)e->max_running; ++s)
+    if (e->slots[s] && e->slots[s]->cancel) {
+      emit(e->slots[s]->id, AHA_ENGINE_NO_TOKEN, AHA_ENGINE_EV_CANCELLED);
+      engine_release(e, s);
+    }
+  // 2. the decode rows: every request with a first token, in submission order
+  std::vector<int> dec;
+  for (int s = 0; s < (int)e->max_running; ++s)
+    if (e->slots[s] && e->slots[s]->started) dec.push_back(s);
+  std::sort(dec.begin(), dec.end(), [&](int a, int b) { return e->slots[a]->id < e->slots[b]->id; });
+  // 3. the prefill pass: at most one chunk of the running long prompt, then admissions in FIFO order
+  std::vector<EngSeg> whole;
+  EngSeg chunk{nullptr, 0, 0};
+  long long left = (long long)e->budget;
+  for (EngReq* q : e->slots)
+    if (q && !q->started) {   // a long prompt part-way through its prefill (at most one)
+      const int len = (int)std::min(e->chunk, q->ids.size() - q->done);
+      chunk = EngSeg{q, (int)q->done, len};
+      left -= len;
+    }
+  int rc;
+  while (!e->waiting.empty()) {
+    EngReq* q = e->waiting.front();
+    int s = 0;
+    while (s < (int)e->max_running && e->slots[s]) ++s;
+    if (s == (int)e->max_running || e->free_pages.size() < q->npages) break;
+    const long long len = (long long)q->ids.size();
+    EngSeg sg{q, 0, (int)len};
+    if (len <= left || (q->whole && whole.empty() && !chunk.q)) {
+      whole.push_back(sg);   // (a request with images / video / audio over the budget runs alone)
+    } else if (!q->whole && len > (long long)e->budget && !chunk.q && left >= KV_PAGE_TOKENS) {   // only prompts over the whole budget
+      sg.len = (int)std::min<long long>((long long)e->chunk, left / KV_PAGE_TOKENS * KV_PAGE_TOKENS);
+      chunk = sg;
+    } else {
+      break;
+    }
+    left -= sg.len;
+    e->waiting.pop_front();
+    if ((rc = engine_admit(e, q, s))) return rc;   // (the request is gone, its pages back in the pool)
+  }
+  std::vector<EngSeg> segs = whole;
+  if (chunk.q) segs.push_back(chunk);
+  if (!segs.empty()) {
+    const int n_seg = (int)segs.size();
+    std::vector<size_t> lens(n_seg);
+    std::vector<int64_t> page0(n_seg);
+    std::vector<int32_t> kv0(n_seg);
+    std::vector<std::vector<int32_t>> pos3(n_seg);
+    std::vector<uint64_t> phys;   // the pass's "logical" pages: every segment's slot pages, back to back
+    std::vector<uint32_t> ids;
+    bool any_kv0 = false;
+    for (int j = 0; j < n_seg; ++j) {
+      const EngSeg& sg = segs[j];
+      lens[j] = (size_t)sg.len;
+      kv0[j] = sg.kv0;
+      any_kv0 |= sg.kv0 > 0;
+      page0[j] = (int64_t)phys.size();
+      const std::vector<uint64_t>& pg = e->slot_pages[sg.q->slot];
+      phys.insert(phys.end(), pg.begin(), pg.end());
+      pos3[j] = sg.q->pos3;
+      ids.insert(ids.end(), sg.q->ids.begin() + sg.kv0, sg.q->ids.begin() + sg.kv0 + sg.len);
+    }
+    const PackedPass pp = plan_packed_pass(lens.data(), n_seg, page0.data(), pos3.data(), any_kv0 ? kv0.data() : nullptr);
+    std::vector<VisRequest> vreqs;
+    std::vector<AudRequest> areqs;
+    for (int j = 0; j < n_seg; ++j) {
+      const aha_mm_input* q = segs[j].q->mm;
+      const int r0 = pp.tab[3 * j];
+      if (q && (q->n_images > 0 || q->n_videos > 0)) vreqs.push_back(VisRequest{q, ids.data() + r0, lens[j], r0, j});
+      else if (q && m->audio) areqs.push_back(AudRequest{q, ids.data() + r0, lens[j], r0, j});
+    }
+    // pass page table: the rope kernel's pages, then (chunks) the attention's
+    std::vector<uint64_t> tab(pp.pages.size() + pp.attn_pages.size());
+    for (size_t p = 0; p < pp.pages.size(); ++p) tab[p] = phys[(size_t)pp.pages[p]];
+    for (size_t p = 0; p < pp.attn_pages.size(); ++p) tab[pp.pages.size() + p] = phys[(size_t)pp.attn_pages[p]];
+    AHA_HIP_CHECK(hipMemcpy(gc.pass_pages, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    if ((rc = run_packed_pass(m, pp, ids.data(), gc.pass_pages, vreqs, areqs, gc.pass_pages + pp.pages.size()))) return rc;
+    // the prompts this pass completes: their last rows -> gc rows 0 .. k-1 (the chunk, if it does not end its prompt, is the last segment)
+    int k = n_seg;
+    if (chunk.q && (size_t)(chunk.kv0 + chunk.len) < chunk.q->ids.size()) --k;
+    for (int j = 0; j < n_seg; ++j) segs[j].q->done += (size_t)segs[j].len;
+    if (k > 0) {
+      launch_embed_gather(m->p_x, reinterpret_cast<const uint32_t*>(m->p_pass_tab + pp.o_last), gc.x, k, gc.H, st);
+      gen_head(m, gc, 0, k, gc.tok[0]);
+      AHA_HIP_CHECK(hipGetLastError());
+      std::vector<int> seqs(k);
+      for (int j = 0; j < k; ++j) {
+        seqs[j] = segs[j].q->slot;
+        e->n_out[seqs[j]] = 0;
+        e->row_logits[j] = logits_out ? logits_out + (ne + j) * (size_t)V : nullptr;
+      }
+      if ((rc = gen_finish_step(m, gc, e->ch, seqs, gc.tok[0]))) return rc;
+      for (int j = 0; j < k; ++j) {
+        EngReq* q = segs[j].q;
+        const uint32_t t = gc.h_tok[j];   // the first token never ends a sequence (generate.rs:131-134)
+        q->toks.push_back(t);
+        q->started = true;
+        q->mm = nullptr;
+        e->n_out[q->slot] = 1;
+        emit(q->id, t, AHA_ENGINE_EV_FIRST | (q->max_new == 1 ? AHA_ENGINE_EV_LENGTH : 0u));
+      }
+    } else {
+      AHA_HIP_CHECK(hipStreamSynchronize(st));
+    }
+  }
+  // 4. one decode step over the rows that had a first token before this step
+  std::vector<int> rows;
+  for (int s : dec)
+    if (e->slots[s]->toks.size() < e->slots[s]->max_new) rows.push_back(s);
+  if (!rows.empty()) {
+    const int R = (int)rows.size();
+    int max_split = 1;
+    double kv_tokens = 0;
+    for (int r = 0; r < R; ++r) {
+      const int s = rows[r];
+      const EngReq* q = e->slots[s];
+      const int kv_len = (int)(q->ids.size() + e->n_out[s]);   // the cache after this step's append
+      const int ns = attn_decode_nsplit(kv_len, g, m->max_nsplit);
+      int32_t* t = gc.h_rowtab + (size_t)r * GEN_ROW_WORDS;
+      t[GEN_ROW_PAGE0] = (int32_t)((size_t)s * e->kv_pages);
+      t[GEN_ROW_KVLEN] = kv_len;
+      t[GEN_ROW_NSPLIT] = ns;
+      t[GEN_ROW_CTR] = (int32_t)e->ctr_acc[s];
+      t[GEN_ROW_POS] = (int32_t)(kv_len - 1 + q->rope_delta);
+      t[GEN_ROW_SRC] = r;
+      t[GEN_ROW_CTRROW] = s;
+      t[7] = 0;
+      if (ns > 1) e->ctr_acc[s] += (unsigned)L * (unsigned)ns;   // a single split never touches its counter
+      max_split = std::max(max_split, ns);
+      kv_tokens += kv_len;
+      e->h_tok_in[r] = q->toks.back();
+      e->row_logits[r] = logits_out ? logits_out + (ne + r) * (size_t)V : nullptr;
+    }
+    AHA_HIP_CHECK(hipMemcpyAsync(gc.rowtab, gc.h_rowtab, (size_t)R * GEN_ROW_WORDS * 4, hipMemcpyHostToDevice, st));
+    AHA_HIP_CHECK(hipMemcpyAsync(e->d_tok_in, e->h_tok_in, (size_t)R * 4, hipMemcpyHostToDevice, st));
+    gen_decode_step(m, gc, R, max_split, kv_tokens, e->d_tok_in, gc.tok[1]);
+    AHA_HIP_CHECK(hipGetLastError());
+    if ((rc = gen_finish_step(m, gc, e->ch, rows, gc.tok[1]))) return rc;
+    for (int r = 0; r < R; ++r) {
+      EngReq* q = e->slots[rows[r]];
+      const uint32_t t = gc.h_tok[r];
+      q->toks.push_back(t);
+      e->n_out[rows[r]] = q->toks.size();
+      const uint32_t f = (engine_is_stop(c, t) ? AHA_ENGINE_EV_STOP : 0u) | (q->toks.size() == q->max_new ? AHA_ENGINE_EV_LENGTH : 0u);
+      emit(q->id, t, f);
+    }
+  }
+  // 5. retire what ended
+  for (int s = 0; s < (int)e->max_running; ++s) {
+    EngReq* q = e->slots[s];
+    if (!q || !q->started) continue;
+    const uint32_t last = q->toks.back();
+    if (q->toks.size() >= q->max_new || (q->toks.size() > 1 && engine_is_stop(c, last))) engine_release(e, s);
+  }
+  *n_ev = ne;
+  return AHA_OK;
 }
 
 }  // namespace aha

@@ -514,6 +514,9 @@ class HipInferenceModel:
 
     def close(self):
         if self.handle:
+            eng = getattr(self, "_engine", None)
+            if eng is not None:   # an engine left open goes first: it owns this model's cache
+                eng.close()
             lib().aha_hip_model_destroy(self.handle)
             self.handle = C.c_void_p()
         if self._own_ctx:
@@ -524,6 +527,133 @@ class HipInferenceModel:
             self.close()
         except Exception:
             pass
+
+
+@dataclass
+class EngineEvent:
+    """One emitted token of a step (aha_engine_event): flags are AHA_ENGINE_EV_* bits; a cancellation has token None."""
+    req_id: int
+    token: Optional[int]
+    first: bool
+    stop: bool
+    length: bool
+    cancelled: bool
+
+    @property
+    def finished(self) -> bool:
+        return self.stop or self.length or self.cancelled
+
+
+class HipEngine:
+    """Continuous batching over one model (aha_hip_engine_*): submit requests at any time, step() returns every token emitted in the
+    step, cancel() ends a request at the next step.  The engine owns the model's cache while it lives: the model's other generation
+    entries raise AHA_ERR_STATE until close().  generate_stream_generic (common/generate.rs:231-368) for many requests at once."""
+
+    def __init__(self, model: HipInferenceModel, max_running: int = 8, kv_pages: int = 256, max_tokens_per_step: int = 0,
+                 prefill_chunk: int = 0):
+        self.model = model
+        cfg = _lib.EngineConfig(max_running, kv_pages, max_tokens_per_step, prefill_chunk)
+        self.handle = C.c_void_p()
+        check(lib().aha_hip_engine_create(model.handle, C.byref(cfg), C.byref(self.handle)))
+        model._engine = self
+        self.max_running = int(max_running)
+        self._keep: Dict[int, list] = {}      # per request: the arrays its aha_mm_input points into, until its first token
+        self._streams: Dict[int, List[int]] = {}
+        self._done: Dict[int, bool] = {}
+        self._n_cancel = 0
+
+    def submit(self, input_ids: Sequence[int], max_new: int, params=None, data: Optional[MultiModalData] = None) -> int:
+        """Queue one request; returns its id.  params: None = greedy, else a sampling.SamplingParams; data: its MultiModalData."""
+        ids = np.ascontiguousarray(np.asarray(input_ids, dtype=np.uint32).reshape(-1))
+        keep = [ids]
+        mm_p = None
+        if data is not None:
+            mm, k = _mm_input(data)
+            keep += [mm, k]
+            mm_p = C.byref(mm)
+        cp = None if params is None else C.byref(params.to_c())
+        rid = C.c_uint64()
+        check(lib().aha_hip_engine_submit(self.handle, ids.ctypes.data, ids.size, mm_p, cp, int(max_new), C.byref(rid)))
+        self._keep[rid.value] = keep
+        self._streams[rid.value] = []
+        self._done[rid.value] = False
+        return rid.value
+
+    def cancel(self, req_id: int) -> None:
+        check(lib().aha_hip_engine_cancel(self.handle, int(req_id)))
+        self._n_cancel += 1
+
+    def step(self, want_logits: bool = False):
+        """One engine step: a list of EngineEvent (and with want_logits the (len(events), vocab) float32 logits that chose each token)."""
+        cap = self.max_running + self._n_cancel
+        evs = (_lib.EngineEvent * cap)()
+        n = C.c_size_t()
+        lg = np.zeros((cap, self.model.text_cfg.vocab_size), np.float32) if want_logits else None
+        check(lib().aha_hip_engine_step(self.handle, evs, cap, C.byref(n), None if lg is None else lg.ctypes.data))
+        self._n_cancel = 0
+        out = []
+        for i in range(n.value):
+            e = evs[i]
+            f = int(e.flags)
+            ev = EngineEvent(int(e.req_id), None if f & _lib.AHA_ENGINE_EV_CANCELLED else int(e.token), bool(f & _lib.AHA_ENGINE_EV_FIRST),
+                             bool(f & _lib.AHA_ENGINE_EV_STOP), bool(f & _lib.AHA_ENGINE_EV_LENGTH), bool(f & _lib.AHA_ENGINE_EV_CANCELLED))
+            if ev.first or ev.cancelled:
+                self._keep.pop(ev.req_id, None)
+            if ev.token is not None and ev.req_id in self._streams:
+                self._streams[ev.req_id].append(ev.token)
+            if ev.finished and ev.req_id in self._done:
+                self._done[ev.req_id] = True
+            out.append(ev)
+        return out if lg is None else (out, lg[:n.value])
+
+    def stats(self) -> Dict[str, int]:
+        st = _lib.EngineStats()
+        check(lib().aha_hip_engine_stats(self.handle, C.byref(st)))
+        return {"waiting": st.waiting, "running": st.running, "free_pages": st.free_pages, "total_pages": st.total_pages}
+
+    def tokens(self, req_id: int) -> List[int]:
+        """The tokens request req_id has streamed so far."""
+        return list(self._streams[req_id])
+
+    def forget(self, req_id: int) -> None:
+        """Drop a finished request's record (its tokens, its state): a long-lived engine keeps none of them otherwise."""
+        if not self._done.get(req_id, True):
+            raise ValueError(f"request {req_id} has not finished")
+        self._streams.pop(req_id, None)
+        self._done.pop(req_id, None)
+
+    def finished(self, req_id: int) -> bool:
+        return self._done[req_id]
+
+    def stream(self, req_id: int):
+        """Per-request token iterator: yields req_id's tokens as steps emit them, stepping the engine (every request advances).  The
+        request's record is dropped once the iterator is exhausted (forget)."""
+        sent = 0
+        while True:
+            toks = self._streams[req_id]
+            while sent < len(toks):
+                yield toks[sent]
+                sent += 1
+            if self._done[req_id]:
+                self.forget(req_id)
+                return
+            self.step()
+
+    def debug_ctr_base(self, base: int) -> None:
+        check(lib().aha_hip_engine_debug_ctr_base(self.handle, int(base) & 0xFFFFFFFF))
+
+    def close(self):
+        if self.handle:
+            lib().aha_hip_engine_destroy(self.handle)
+            self.handle = C.c_void_p()
+            if getattr(self.model, "_engine", None) is self:
+                self.model._engine = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 @dataclass

@@ -5,6 +5,7 @@ seeded inputs.  All tensors must live on the GPU and be contiguous bf16 unless s
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from typing import Optional
 
@@ -137,6 +138,19 @@ def attn_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, nh: int, kvh
     o = torch.empty(S, nh * d, dtype=torch.bfloat16, device=q.device)
     check(lib().aha_hip_attn_prefill(_ptr(q), _ptr(k), _ptr(v), _ptr(o), S, L, nh, kvh, d, kv_offset, int(causal),
                                      scale, _stream()))
+    return o
+
+
+def attn_prefill_segs(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, nh: int, kvh: int, segs, with_kv0: bool = True,
+                      scale: Optional[float] = None) -> torch.Tensor:
+    """Test entry (aha_hip_debug_attn_prefill_segs): segs = [(len, kv0), ...]; q (sum len, nh*128) packed in segment order; k, v
+    (sum (kv0 + len), kvh*128) every segment's cache back to back.  Causal, row i of a segment at cache position kv0 + i."""
+    _chk(q, k, v)
+    scale = bf16_scale(128) if scale is None else scale
+    o = torch.empty(q.shape[0], nh * 128, dtype=torch.bfloat16, device=q.device)
+    flat = (C.c_int32 * (2 * len(segs)))(*[int(x) for sg in segs for x in sg])
+    check(lib().aha_hip_debug_attn_prefill_segs(_ptr(q), _ptr(k), _ptr(v), _ptr(o), nh, kvh, flat, len(segs), int(with_kv0), scale,
+                                                _stream()))
     return o
 
 

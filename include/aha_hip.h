@@ -249,6 +249,74 @@ int aha_hip_generate_batch_mm(aha_model* m, const uint32_t* input_ids, const siz
                               const aha_mm_input* const* mm, const aha_sampling_params* params, size_t max_new,
                               size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* step_logits_out);
 
+/* ---- continuous batching engine --------------------------------------------------------------------------------------------
+ * A stateful server loop over the generate_batch machinery, for generate_stream_generic (/root/reference/src/models/common/generate.rs:
+ * 231-368, `stream: true`): requests are submitted at any time, every step returns one event per emitted token, requests can be cancelled,
+ * each has its own max_new.  While an engine exists on a model, the engine owns the KV cache: the model's single-sequence entries
+ * (forward_initial, forward_step, decode_greedy, clear_cache, kv_export / kv_import, debug_graph_step), embed / embed_batch and every
+ * generate_batch* entry return AHA_ERR_STATE; aha_hip_engine_destroy clears the cache.  Destroy the engine before its model:
+ * aha_hip_model_destroy destroys an engine left open, and that engine's handle must not be used afterwards.  One GPU, the models and head_dim of
+ * aha_hip_generate_batch (else AHA_ERR_UNSUPPORTED); no environment variable changes what it does.
+ *   max_running          requests admitted at once (1 .. AHA_ENGINE_MAX_RUNNING); rows past 32 take one more weight pass per step
+ *   kv_pages             64-token cache pages reserved at creation; a request holds ceil((len + max_new) / 64) of them from admission to its end
+ *   max_tokens_per_step  prompt rows one step prefills (0: 16384, else >= 64)
+ *   prefill_chunk        rows of one chunk of a long text prompt, a multiple of 64 within max_tokens_per_step (0: max_tokens_per_step
+ *                        rounded down to 64) */
+#define AHA_ENGINE_MAX_RUNNING 64
+typedef struct aha_engine aha_engine;
+typedef struct aha_engine_config {
+  size_t max_running;
+  size_t kv_pages;
+  size_t max_tokens_per_step;
+  size_t prefill_chunk;
+} aha_engine_config;
+#define AHA_ENGINE_EV_FIRST 1u      /* the request's first token (from its prefill) */
+#define AHA_ENGINE_EV_STOP 2u       /* a stop token: kept, the request ended */
+#define AHA_ENGINE_EV_LENGTH 4u     /* the request's max_new-th token: it ended */
+#define AHA_ENGINE_EV_CANCELLED 8u  /* aha_hip_engine_cancel took effect: token is AHA_ENGINE_NO_TOKEN, the request ended */
+#define AHA_ENGINE_NO_TOKEN 0xffffffffu
+typedef struct aha_engine_event {
+  uint64_t req_id;
+  uint32_t token;
+  uint32_t flags;
+} aha_engine_event;
+typedef struct aha_engine_stats {
+  size_t waiting;      /* submitted, not admitted */
+  size_t running;      /* admitted: prefilling or decoding */
+  size_t free_pages;
+  size_t total_pages;  /* kv_pages */
+} aha_engine_stats;
+/* Clears the model's cache and reserves the pages.  AHA_ERR_INVALID: a null argument or a bad config (checked first, before the model is
+ * looked at); AHA_ERR_STATE: the model already has an engine; AHA_ERR_OOM: the pages or buffers cannot be had. */
+int aha_hip_engine_create(aha_model* m, const aha_engine_config* cfg, aha_engine** out);
+void aha_hip_engine_destroy(aha_engine* e);
+/* Queues one request (generate_generic's input for one prompt: ids, its MultiModalData, GenerationContext's options, max_tokens).
+ * mm: NULL or the request's images / videos or audio clip, with aha_hip_generate_batch_mm's rules; the struct and what it points to stay the
+ * caller's and must stay valid until the request's first-token (or cancelled) event.  params: NULL = greedy, else the sampler with the
+ * semantics of aha_hip_generate_batch_sampled (its own RNG stream).  Every check happens here, before any device work, with
+ * aha_hip_generate_batch_mm's codes and messages; a request that needs more than kv_pages pages is AHA_ERR_OOM.  *req_id: 1, 2, ... */
+int aha_hip_engine_submit(aha_engine* e, const uint32_t* input_ids, size_t n_ids, const aha_mm_input* mm, const aha_sampling_params* params,
+                          size_t max_new, uint64_t* req_id);
+/* A waiting or running request ends at the next step with a CANCELLED event and gives its pages back; AHA_ERR_INVALID for an id that is
+ * neither (unknown or already ended). */
+int aha_hip_engine_cancel(aha_engine* e, uint64_t req_id);
+/* One step.  Cancellations first; then the prefill pass: at most one prefill_chunk-row chunk of the long text prompt part-way through its
+ * prefill, and waiting requests admitted in submission order while a slot and their pages are free and their prompt fits in what is left of
+ * max_tokens_per_step.  Only a text prompt longer than max_tokens_per_step is chunked (when no other chunked prefill runs); a shorter
+ * one that does not fit waits for the next step, so it is always prefilled whole; a request with images, video or audio is prefilled
+ * whole, never chunked, alone if it is over the budget.  The prompts it completes give their first token (FIRST).  Then one
+ * decode step over every request that had its first token before this step (generate_generic's loop: greedy argmax or the request's sampler,
+ * stop tokens kept, STOP / LENGTH end it).  ev (cap >= max_running + pending cancellations, else AHA_ERR_INVALID): cancellations, first
+ * tokens in pass order, decode tokens in submission order; *n_ev of them.  logits_out (NULL or cap x vocab f32, as the count is known only
+ * afterwards): row i = the logits that chose event i's token (a cancellation's row is not written).  A request prefilled whole has the
+ * tokens and logits of aha_hip_generate_batch_mm (or _sampled) for the same prefill pass composition, bit for bit; a chunked prompt's
+ * equal its whole prefill within the parity bounds only.  A step that fails (a HIP or allocation error) loses its events: destroy the
+ * engine then. */
+int aha_hip_engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, float* logits_out);
+int aha_hip_engine_stats(const aha_engine* e, aha_engine_stats* out);
+/* Test hook: the value a slot's split-arrival counters are reset to when a request takes it (default 0; near 2^32 they wrap mid-request). */
+int aha_hip_engine_debug_ctr_base(aha_engine* e, uint32_t base);
+
 /* Host-only sampler: candle's LogitsProcessor built by get_logit_processor (sample.rs:7-38) plus use_repeat_penalty's slicing, over
  * the rand 0.9.2 StdRng of aha_hip_rng_*.  The deterministic half restates aha_amd/sampling.py (weights over the device candidates, the
  * top-p tie rule, the full-vector path); each sampled token consumes one next_u32, an ArgMax pick none.
@@ -542,6 +610,13 @@ int aha_hip_sample_rows(const float* logits, int64_t ld, int32_t R, int32_t V, c
  * nh == kvh (the Qwen3-ASR audio encoder's geometry). */
 int aha_hip_attn_prefill(const void* q, const void* k, const void* v, void* o, int32_t S, int32_t L, int32_t nh,
                          int32_t kvh, int32_t d, int32_t kv_offset, int32_t causal, float scale, void* stream);
+/* Test entry: the packed prefill attention over independent segments (AttnPrefillArgs::seg_tab, the engine's and generate_batch's launch),
+ * causal, head_dim 128, q rows as given (already normed and rotated).  segs: n_seg host pairs {len, kv0}; segment j's q / o rows follow
+ * segment j - 1's, and its cache -- kv0 + len token-major rows of k / v ((rows, kvh * 128) bf16 on the device), after segment j - 1's --
+ * goes to pages of its own.  Row i of segment j sees cache positions 0 .. kv0 + i.  with_kv0: pass kv0 as AttnPrefillArgs::seg_kv0
+ * (multiples of 64); 0: launch without it (every kv0 must be 0).  Synchronises the stream. */
+int aha_hip_debug_attn_prefill_segs(const void* q, const void* k, const void* v, void* o, int32_t nh, int32_t kvh, const int32_t* segs,
+                                    int32_t n_seg, int32_t with_kv0, float scale, void* stream);
 /* V0-pre, host arithmetic: img_smart_resize (src/utils/img_utils.rs:294-331) -- the size Qwen3VLProcessor::process_img
  * (qwen3vl/processor.rs:159-165) resizes an image to: multiples of `factor` (patch * merge = 32), area within
  * [min_pixels, max_pixels] (shortest_edge / longest_edge of the preprocessor config).  AHA_ERR_INVALID when the aspect ratio

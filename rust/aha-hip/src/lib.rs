@@ -29,6 +29,40 @@ pub mod sys {
     pub struct AhaSampler {
         _p: [u8; 0],
     }
+    #[repr(C)]
+    pub struct AhaEngine {
+        _p: [u8; 0],
+    }
+    /// ctypes mirror `aha_amd._lib.EngineConfig`.
+    #[repr(C)]
+    #[derive(Debug, Clone, Copy)]
+    pub struct AhaEngineConfig {
+        pub max_running: usize,
+        pub kv_pages: usize,
+        pub max_tokens_per_step: usize,
+        pub prefill_chunk: usize,
+    }
+    /// ctypes mirror `aha_amd._lib.EngineEvent`.
+    #[repr(C)]
+    #[derive(Debug, Clone, Copy, Default)]
+    pub struct AhaEngineEvent {
+        pub req_id: u64,
+        pub token: u32,
+        pub flags: u32,
+    }
+    /// ctypes mirror `aha_amd._lib.EngineStats`.
+    #[repr(C)]
+    #[derive(Debug, Clone, Copy, Default)]
+    pub struct AhaEngineStats {
+        pub waiting: usize,
+        pub running: usize,
+        pub free_pages: usize,
+        pub total_pages: usize,
+    }
+    pub const AHA_ENGINE_EV_FIRST: u32 = 1;
+    pub const AHA_ENGINE_EV_STOP: u32 = 2;
+    pub const AHA_ENGINE_EV_LENGTH: u32 = 4;
+    pub const AHA_ENGINE_EV_CANCELLED: u32 = 8;
 
     pub const AHA_SAMPLE_HAS_TOP_P: u32 = 1;
     pub const AHA_SAMPLE_HAS_TOP_K: u32 = 2;
@@ -264,6 +298,21 @@ pub mod sys {
             n_out: *mut usize,
             step_logits_out: *mut f32,
         ) -> i32;
+        pub fn aha_hip_engine_create(m: *mut AhaModel, cfg: *const AhaEngineConfig, out: *mut *mut AhaEngine) -> i32;
+        pub fn aha_hip_engine_destroy(e: *mut AhaEngine);
+        pub fn aha_hip_engine_submit(
+            e: *mut AhaEngine,
+            ids: *const u32,
+            n_ids: usize,
+            mm: *const AhaMmInput,
+            params: *const AhaSamplingParams,
+            max_new: usize,
+            req_id: *mut u64,
+        ) -> i32;
+        pub fn aha_hip_engine_cancel(e: *mut AhaEngine, req_id: u64) -> i32;
+        pub fn aha_hip_engine_step(e: *mut AhaEngine, ev: *mut AhaEngineEvent, cap: usize, n_ev: *mut usize, logits_out: *mut f32) -> i32;
+        pub fn aha_hip_engine_stats(e: *const AhaEngine, out: *mut AhaEngineStats) -> i32;
+        pub fn aha_hip_engine_debug_ctr_base(e: *mut AhaEngine, base: u32) -> i32;
         pub fn aha_hip_sample_rows(
             logits: *const f32,
             ld: i64,
@@ -760,6 +809,58 @@ impl Drop for Model {
             sys::aha_hip_model_destroy(self.model);
             sys::aha_hip_shutdown(self.ctx);
         }
+    }
+}
+
+/// Continuous batching over one model (`aha_hip_engine_*`): what `generate_stream` drives for `stream: true`
+/// (`generate_stream_generic`, reference `src/models/common/generate.rs:231-368`).  `submit` queues a request, every `step` returns
+/// the tokens emitted in it (one per running request), `cancel` ends one at the next step.  While it lives the engine owns the model's
+/// cache: borrow the model mutably for its lifetime.
+pub struct Engine<'a> {
+    e: *mut sys::AhaEngine,
+    max_running: usize,
+    n_cancel: usize,
+    _m: std::marker::PhantomData<&'a mut Model>,
+}
+impl<'a> Engine<'a> {
+    pub fn new(model: &'a mut Model, cfg: sys::AhaEngineConfig) -> Result<Self, Error> {
+        let mut e = std::ptr::null_mut();
+        check(unsafe { sys::aha_hip_engine_create(model.model, &cfg, &mut e) })?;
+        Ok(Self { e, max_running: cfg.max_running, n_cancel: 0, _m: std::marker::PhantomData })
+    }
+    /// One request: `params` None = greedy.  Text only here (`mm` must outlive the request's first token in the C ABI).
+    pub fn submit(&mut self, ids: &[u32], params: Option<&sys::AhaSamplingParams>, max_new: usize) -> Result<u64, Error> {
+        let mut id = 0u64;
+        let p = params.map_or(std::ptr::null(), |p| p as *const _);
+        check(unsafe { sys::aha_hip_engine_submit(self.e, ids.as_ptr(), ids.len(), std::ptr::null(), p, max_new, &mut id) })?;
+        Ok(id)
+    }
+    pub fn cancel(&mut self, req_id: u64) -> Result<(), Error> {
+        check(unsafe { sys::aha_hip_engine_cancel(self.e, req_id) })?;
+        self.n_cancel += 1;
+        Ok(())
+    }
+    /// The step's events: (request, token or None for a cancellation, flags `AHA_ENGINE_EV_*`).
+    pub fn step(&mut self) -> Result<Vec<(u64, Option<u32>, u32)>, Error> {
+        let cap = self.max_running + self.n_cancel;
+        let mut ev = vec![sys::AhaEngineEvent::default(); cap];
+        let mut n = 0usize;
+        check(unsafe { sys::aha_hip_engine_step(self.e, ev.as_mut_ptr(), cap, &mut n, std::ptr::null_mut()) })?;
+        self.n_cancel = 0;
+        Ok(ev[..n]
+            .iter()
+            .map(|x| (x.req_id, if x.flags & sys::AHA_ENGINE_EV_CANCELLED != 0 { None } else { Some(x.token) }, x.flags))
+            .collect())
+    }
+    pub fn stats(&self) -> Result<sys::AhaEngineStats, Error> {
+        let mut s = sys::AhaEngineStats::default();
+        check(unsafe { sys::aha_hip_engine_stats(self.e, &mut s) })?;
+        Ok(s)
+    }
+}
+impl Drop for Engine<'_> {
+    fn drop(&mut self) {
+        unsafe { sys::aha_hip_engine_destroy(self.e) }
     }
 }
 
