@@ -47,6 +47,16 @@ class EngineStats(C.Structure):
     _fields_ = [("waiting", C.c_size_t), ("running", C.c_size_t), ("free_pages", C.c_size_t), ("total_pages", C.c_size_t)]
 
 
+class SpecConfig(C.Structure):
+    """aha_spec_config (include/aha_hip.h); the Rust shim's AhaSpecConfig has the same fields in the same order."""
+    _fields_ = [("max_draft", C.c_int32), ("ngram_min", C.c_int32), ("ngram_max", C.c_int32)]
+
+
+class SpecStats(C.Structure):
+    """aha_spec_stats (include/aha_hip.h)."""
+    _fields_ = [("decode_steps", C.c_size_t), ("rows", C.c_size_t), ("proposed", C.c_size_t), ("accepted", C.c_size_t)]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [
         ("arch", C.c_int32),
@@ -170,6 +180,9 @@ SIGNATURES = {
     "aha_hip_generate_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P]),
     "aha_hip_generate_batch_sampled": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(SamplingParams), C.c_size_t, C.c_size_t, _P, _P, _P]),
     "aha_hip_generate_batch_mm": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.POINTER(SamplingParams), C.c_size_t, C.c_size_t, _P, _P, _P]),
+    "aha_hip_generate_batch_spec": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(SpecConfig), _P, _P, _P, _P, _P, _P, _P,
+                                              C.POINTER(SpecStats)]),
+    "aha_hip_spec_propose": (C.c_int, [C.POINTER(SpecConfig), _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P, C.POINTER(C.c_size_t)]),
     "aha_hip_engine_create": (C.c_int, [_P, C.POINTER(EngineConfig), _P]),
     "aha_hip_engine_destroy": (None, [_P]),
     "aha_hip_engine_submit": (C.c_int, [_P, _P, C.c_size_t, _P, C.POINTER(SamplingParams), C.c_size_t, C.POINTER(C.c_uint64)]),

@@ -24,6 +24,10 @@ constexpr int ATTN_DECODE_FUSED_LDS = 16 * 128 * 2 + 128 * 2 + 128 * 2 + ATTN_DE
 //   * in the page loop K and V of a page are separate register buffers re-requested as soon as their MFMAs have
 //     consumed them (K(next) right after QK^T, V(next) right after P.V), so a wave always has 16-32 KB in flight.
 // smem: ATTN_DECODE_FUSED_LDS bytes, 16-byte aligned.  Returns true in the one block per kv head that wrote the output.
+// APPEND = false (draft-and-verify steps, kernels_batch.hip): the new K/V is already in its slot (kv_append_rows_kernel wrote the same
+// bits before this launch) and the append below is compiled out; everything else -- the new token taken from LDS, the old ones from the
+// pages, the split rule -- is the same code, so a row's output bits are those of the default instantiation.
+template <bool APPEND = true>
 __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs& a, char* smem, const int kvhd, const int split,
                                                        const int nsplit) {
   constexpr int NW = ATTN_DECODE_NW, NT = NW * 64;
@@ -132,7 +136,7 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
   }
   __syncthreads();
   stamp(1);
-  if (split == 0) {  // append (k roped, v raw) for the following steps
+  if (APPEND && split == 0) {  // append (k roped, v raw) for the following steps
     // global address space spelled out: a flat store here would make every later wait in the kernel a vmcnt(0)
     typedef __attribute__((address_space(1))) bf16_t* gbf_t;
     const int pg = slot_new / KV_PAGE_TOKENS, t = slot_new % KV_PAGE_TOKENS;

@@ -984,6 +984,37 @@ int aha_hip_generate_batch_mm(aha_model* m, const uint32_t* input_ids, const siz
   return model_generate_batch_mm(m, input_ids, seq_lens, n_seqs, mm, params, max_new, max_tokens_per_pass, tokens_out, n_out, step_logits_out);
   API_GUARD_END
 }
+int aha_hip_generate_batch_spec(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
+                                size_t max_tokens_per_pass, const aha_spec_config* spec, const uint32_t* predictions,
+                                const size_t* prediction_lens, uint32_t* tokens_out, size_t* n_out, float* logits_out, size_t* n_proposed,
+                                size_t* n_accepted, aha_spec_stats* stats) {
+  API_GUARD_BEGIN
+  if (int rc = spec_config_check(spec, "generate_batch_spec")) return rc;   // the config first, before anything touches the model
+  if ((predictions == nullptr) != (prediction_lens == nullptr)) {
+    set_error("generate_batch_spec: predictions and prediction_lens must both be set or both be null");
+    return AHA_ERR_INVALID;
+  }
+  if (!m) {
+    set_error("null model");
+    return AHA_ERR_INVALID;
+  }
+  if (int rc = engine_owns_cache(m, "generate_batch_spec")) return rc;
+  return model_generate_batch_spec(m, input_ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, spec, predictions, prediction_lens, tokens_out,
+                                   n_out, logits_out, n_proposed, n_accepted, stats);
+  API_GUARD_END
+}
+int aha_hip_spec_propose(const aha_spec_config* spec, const uint32_t* context, size_t n_context, size_t n_prompt, const uint32_t* prediction,
+                         size_t n_prediction, uint32_t* draft_out, size_t* n_draft) {
+  API_GUARD_BEGIN
+  if (int rc = spec_config_check(spec, "spec_propose")) return rc;
+  if (!context || !draft_out || !n_draft || n_context == 0 || n_prompt > n_context) {
+    set_error("spec_propose: null context / draft_out / n_draft, an empty context or n_prompt > n_context");
+    return AHA_ERR_INVALID;
+  }
+  spec_propose(*spec, context, n_context, n_prompt, prediction, prediction ? n_prediction : 0, draft_out, n_draft);
+  return AHA_OK;
+  API_GUARD_END
+}
 int aha_hip_engine_create(aha_model* m, const aha_engine_config* cfg, aha_engine** out) {
   API_GUARD_BEGIN
   if (int rc = engine_config_check(cfg, nullptr, nullptr)) return rc;   // the config first: checked before the model is touched

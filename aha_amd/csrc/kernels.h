@@ -322,6 +322,8 @@ constexpr int GEN_ROW_CTR = 3;     // the row's split-arrival counters before th
 constexpr int GEN_ROW_POS = 4;     // rope position of the step's token
 constexpr int GEN_ROW_SRC = 5;     // row of the previous step's token vector that holds this row's input token
 constexpr int GEN_ROW_CTRROW = 6;  // which (kvh, 32) block of head_ctr holds the row's counters (generate_batch: the row; the engine: its slot)
+constexpr int GEN_ROW_TOK = 7;     // draft-and-verify steps: the row's input token, uploaded with the table (then SRC = r * GEN_ROW_WORDS + GEN_ROW_TOK
+                                   // with the table itself as the token vector); 0 elsewhere
 void launch_gen_embed(const void* table, const uint32_t* tok_in, const int32_t* row_tab, int rows, void* x, int H, const float* inv_freq,
                       const int32_t* axis_map, float* rope, hipStream_t st);
 
@@ -343,7 +345,17 @@ struct AttnDecodeBatchArgs {
   int nh, kvh, max_nsplit;
   float eps, scale;
 };
-void launch_attn_decode_batch(const AttnDecodeBatchArgs& a, int rows, int max_nsplit_rows, hipStream_t st);
+// append = false: the rows' K/V are in their slots already (launch_kv_append_rows before it); the body's append is compiled out
+void launch_attn_decode_batch(const AttnDecodeBatchArgs& a, int rows, int max_nsplit_rows, hipStream_t st, bool append = true);
+// Draft-and-verify steps: (k roped, v raw) of every row into slot kv_len - 1 of its sequence, the bits of the fused kernel's own append
+// (reads qkv, k_norm_w, rope, page_ptrs, layer_off, row_tab, nh, kvh, eps of the batch arguments)
+void launch_kv_append_rows(const AttnDecodeBatchArgs& a, int rows, hipStream_t st);
+// Per sequence s of a draft-and-verify step: seq_tab[s] = {first row, draft rows after it}; out[s] = {emitted count, row whose logits chose
+// the last emitted token, the emitted tokens}: the longest draft prefix the argmax vector confirms, plus the token that follows it
+constexpr int SPEC_MAX_DRAFT = 15;
+constexpr int SPEC_SEQ_WORDS = 2, SPEC_SEQ_ROW0 = 0, SPEC_SEQ_NDRAFT = 1;
+constexpr int SPEC_OUT_WORDS = 2 + SPEC_MAX_DRAFT + 1, SPEC_OUT_COUNT = 0, SPEC_OUT_LAST_ROW = 1, SPEC_OUT_TOKENS = 2;
+void launch_spec_accept_rows(const uint32_t* argmax, const int32_t* row_tab, const int32_t* seq_tab, int n_seqs, uint32_t* out, hipStream_t st);
 int attn_decode_nsplit(int kv_len_after, int g, int max_nsplit);   // enqueue_decode_step's split rule
 
 struct StepState;  // model.h

@@ -10,6 +10,10 @@
 //                            rope cos / sin table.
 //   attn_decode_batch_kernel q/k-norm + RoPE + KV append + split-KV attention + split merge of ALL rows in one launch: one block per
 //                            (kv head, split, row), each running attn_decode_fused_body on its row's qkv, rope row and pages.
+//   kv_append_rows_kernel    draft-and-verify steps (model_generate_batch_spec): the k-norm + RoPE + KV append of every row in a launch of
+//                            its own, so that row i + 1 of a sequence finds row i's K/V in the pages; the attention launch that follows is
+//                            attn_decode_rows_kernel, the batch attention with the body's append compiled out.
+//   spec_accept_rows_kernel  per sequence, the longest draft prefix the step's argmax vector confirms -> its emitted tokens.
 //
 // Row isolation (tests/test_generate_batch_gpu.py): every output element of gemv_rows is summed in an order that depends only on
 // (N, K) -- within a wave the MFMA chain over its chunks, across the 4 waves of a block ((w0 + w1) + w2) + w3 through LDS, across the
@@ -217,6 +221,41 @@ __global__ __launch_bounds__(256) void gen_embed_kernel(const bf16_t* __restrict
 }
 
 // Block (kv head, split, row).  Splits past the row's own count return at once.
+template <bool APPEND>
+__device__ __forceinline__ void attn_decode_batch_block(const AttnDecodeBatchArgs& b, char* smem) {
+  const int kvhd = blockIdx.x, split = blockIdx.y, r = blockIdx.z;
+  const int32_t* t = b.row_tab + (int64_t)r * GEN_ROW_WORDS;
+  const int nsplit = __builtin_amdgcn_readfirstlane(t[GEN_ROW_NSPLIT]);
+  if (split >= nsplit) return;
+  const int page0 = __builtin_amdgcn_readfirstlane(t[GEN_ROW_PAGE0]);
+  const int kv_len = __builtin_amdgcn_readfirstlane(t[GEN_ROW_KVLEN]);
+  const unsigned ctr0 = (unsigned)__builtin_amdgcn_readfirstlane(t[GEN_ROW_CTR]);
+  AttnDecodeFusedArgs a{};
+  a.qkv = (const bf16_t*)b.qkv + (int64_t)r * (b.nh + 2 * b.kvh) * 128;
+  a.q_norm_w = b.q_norm_w;
+  a.k_norm_w = b.k_norm_w;
+  a.rope = b.rope + (int64_t)r * 128;
+  a.kv.page_ptrs = b.page_ptrs + page0;
+  a.kv.layer_off = b.layer_off;
+  a.kv.kvh = b.kvh;
+  a.kv.d = 128;
+  a.kv_start_v = kv_len - 1;
+  a.kv_len_v = kv_len;
+  a.part_o = b.part_o + (int64_t)r * b.max_nsplit * b.nh * 128;
+  a.part_ml = b.part_ml + (int64_t)r * b.max_nsplit * b.nh * 2;
+  a.o = (bf16_t*)b.o + (int64_t)r * b.nh * 128;
+  a.head_ctr = b.head_ctr + (int64_t)__builtin_amdgcn_readfirstlane(t[GEN_ROW_CTRROW]) * b.kvh * 32;
+  a.ctr_target = ctr0 + (unsigned)b.ctr_step * (unsigned)nsplit;
+  a.trace = nullptr;
+  a.nh = b.nh;
+  a.kvh = b.kvh;
+  a.nsplit = nsplit;
+  a.eps = b.eps;
+  a.scale = b.scale;
+  attn_decode_fused_body<APPEND>(a, smem, kvhd, split, nsplit);
+}
+
+// (spelled out rather than attn_decode_batch_block<true>: the instruction stream of this kernel is the one its measurements were taken on)
 __global__ __launch_bounds__(256, 2) void attn_decode_batch_kernel(AttnDecodeBatchArgs b) {
   __shared__ __attribute__((aligned(16))) char smem[ATTN_DECODE_FUSED_LDS];
   const int kvhd = blockIdx.x, split = blockIdx.y, r = blockIdx.z;
@@ -249,6 +288,75 @@ __global__ __launch_bounds__(256, 2) void attn_decode_batch_kernel(AttnDecodeBat
   a.eps = b.eps;
   a.scale = b.scale;
   attn_decode_fused_body(a, smem, kvhd, split, nsplit);
+}
+
+// The same without the append: every row's K/V was written by kv_append_rows_kernel in the launch before, so rows of one sequence at
+// consecutive positions see each other's tokens in the pages (tokens < kv_len - 1), and their own from LDS, as a row decoding alone does.
+__global__ __launch_bounds__(256, 2) void attn_decode_rows_kernel(AttnDecodeBatchArgs b) {
+  __shared__ __attribute__((aligned(16))) char smem[ATTN_DECODE_FUSED_LDS];
+  attn_decode_batch_block<false>(b, smem);
+}
+
+// One wave per (kv head, row): k-norm + RoPE of the row's k head, (k roped, v raw) -> slot kv_len - 1 of the row's sequence.  The
+// arithmetic and its rounding points are attn_decode_fused_body's norm_rope lambda and append (attn_decode_body.h), expression by
+// expression: the page bits are those the fused kernel's own append writes (tests/test_generate_spec_gpu.py compares whole generations).
+__global__ __launch_bounds__(64) void kv_append_rows_kernel(AttnDecodeBatchArgs b) {
+  typedef const __attribute__((address_space(1))) int32_t* gci32_t;
+  typedef const __attribute__((address_space(1))) uint64_t* gcu64_t;
+  const int kvhd = blockIdx.x, r = blockIdx.y, lane = (int)threadIdx.x;
+  const gci32_t t = gp<gci32_t>(b.row_tab) + (int64_t)r * GEN_ROW_WORDS;
+  const int page0 = __builtin_amdgcn_readfirstlane(t[GEN_ROW_PAGE0]);
+  const int kv_len = __builtin_amdgcn_readfirstlane(t[GEN_ROW_KVLEN]);
+  const gcbf_t qkv = gp<gcbf_t>(b.qkv) + (int64_t)r * (b.nh + 2 * b.kvh) * 128;
+  const gcbf_t ksrc = qkv + (int64_t)(b.nh + kvhd) * 128, vsrc = qkv + (int64_t)(b.nh + b.kvh + kvhd) * 128;
+  const gcbf_t nw = gp<gcbf_t>(b.k_norm_w);
+  const gcf_t rope = gp<gcf_t>(b.rope) + (int64_t)r * 128;
+  const bf16_t bx0 = ksrc[lane], bx1 = ksrc[lane + 64];
+  const bf16_t bw0 = nw[lane], bw1 = nw[lane + 64];
+  const float cs = rope[lane], sn = rope[64 + lane];
+  const bf16_t v0 = vsrc[lane], v1 = vsrc[lane + 64];
+  const int slot = kv_len - 1, pg = slot / KV_PAGE_TOKENS, tk = slot % KV_PAGE_TOKENS;
+  const uint64_t base = gp<gcu64_t>(b.page_ptrs)[page0 + pg] + b.layer_off;
+  float x0 = bf2f(bx0), x1 = bf2f(bx1);
+  const float ss = wave_sum(fmaf(x0, x0, x1 * x1));
+  const float rinv = 1.0f / sqrtf(ss / 128.0f + b.eps);
+  x0 = rbf(x0 * rinv * bf2f(bw0));
+  x1 = rbf(x1 * rinv * bf2f(bw1));
+  const bf16_t y0 = f2bf(rbf(x0 * cs) + rbf(-x1 * sn));
+  const bf16_t y1 = f2bf(rbf(x1 * cs) + rbf(x0 * sn));
+  const gbf_t kd = reinterpret_cast<gbf_t>(base) + (int64_t)kvhd * KV_PAGE_TOKENS * 128;
+  const gbf_t vd = reinterpret_cast<gbf_t>(base) + (int64_t)b.kvh * KV_PAGE_TOKENS * 128 + (int64_t)kvhd * 128 * KV_PAGE_TOKENS;
+  kd[kpage_elem(tk, lane, 4)] = y0;
+  kd[kpage_elem(tk, lane + 64, 4)] = y1;
+  vd[vpage_elem(tk, lane)] = v0;
+  vd[vpage_elem(tk, lane + 64)] = v1;
+}
+
+// Thread s: sequence s of the step, rows row0 .. row0 + k (its last token, then its k draft tokens; a row's input token is word
+// GEN_ROW_TOK of its table entry).  a = the longest prefix with argmax(row0 + i) == draft i + 1; the emitted tokens are
+// argmax(row0 .. row0 + a): the a confirmed drafts and the token the last confirmed row chose.
+__global__ __launch_bounds__(64) void spec_accept_rows_kernel(const uint32_t* argmax, const int32_t* row_tab, const int32_t* seq_tab, int n_seqs,
+                                                              uint32_t* out) {
+  typedef const __attribute__((address_space(1))) int32_t* gci32_t;
+  typedef const __attribute__((address_space(1))) uint32_t* gcu32_t;
+  typedef __attribute__((address_space(1))) uint32_t* gu32_t;
+  const int s = blockIdx.x * 64 + (int)threadIdx.x;
+  if (s >= n_seqs) return;
+  const gci32_t st = gp<gci32_t>(seq_tab) + (int64_t)s * SPEC_SEQ_WORDS;
+  const gci32_t rt = gp<gci32_t>(row_tab);
+  const gcu32_t am = gp<gcu32_t>(argmax);
+  const gu32_t o = gp<gu32_t>(out) + (int64_t)s * SPEC_OUT_WORDS;
+  const int row0 = st[SPEC_SEQ_ROW0], k = min(st[SPEC_SEQ_NDRAFT], SPEC_MAX_DRAFT);
+  int a = 0;
+  uint32_t tok = am[row0];
+  o[SPEC_OUT_TOKENS] = tok;
+  while (a < k && tok == (uint32_t)rt[(int64_t)(row0 + a + 1) * GEN_ROW_WORDS + GEN_ROW_TOK]) {
+    ++a;
+    tok = am[row0 + a];
+    o[SPEC_OUT_TOKENS + a] = tok;
+  }
+  o[SPEC_OUT_COUNT] = (uint32_t)(a + 1);
+  o[SPEC_OUT_LAST_ROW] = (uint32_t)(row0 + a);
 }
 
 }  // namespace
@@ -322,9 +430,21 @@ int attn_decode_nsplit(int kv_len_after, int g, int max_nsplit) {
   return std::max(1, std::min(std::min(nsplit, max_nsplit), 1024 / g));
 }
 
-void launch_attn_decode_batch(const AttnDecodeBatchArgs& b, int rows, int max_nsplit_rows, hipStream_t st) {
+void launch_attn_decode_batch(const AttnDecodeBatchArgs& b, int rows, int max_nsplit_rows, hipStream_t st, bool append) {
   if (rows <= 0) return;
-  hipLaunchKernelGGL(attn_decode_batch_kernel, dim3((unsigned)b.kvh, (unsigned)max_nsplit_rows, (unsigned)rows), dim3(256), 0, st, b);
+  const dim3 grid((unsigned)b.kvh, (unsigned)max_nsplit_rows, (unsigned)rows);
+  if (append) hipLaunchKernelGGL(attn_decode_batch_kernel, grid, dim3(256), 0, st, b);
+  else hipLaunchKernelGGL(attn_decode_rows_kernel, grid, dim3(256), 0, st, b);
+}
+
+void launch_kv_append_rows(const AttnDecodeBatchArgs& b, int rows, hipStream_t st) {
+  if (rows <= 0) return;
+  hipLaunchKernelGGL(kv_append_rows_kernel, dim3((unsigned)b.kvh, (unsigned)rows), dim3(64), 0, st, b);
+}
+
+void launch_spec_accept_rows(const uint32_t* argmax, const int32_t* row_tab, const int32_t* seq_tab, int n_seqs, uint32_t* out, hipStream_t st) {
+  if (n_seqs <= 0) return;
+  hipLaunchKernelGGL(spec_accept_rows_kernel, dim3((unsigned)((n_seqs + 63) / 64)), dim3(64), 0, st, argmax, row_tab, seq_tab, n_seqs, out);
 }
 
 }  // namespace aha

@@ -212,6 +212,13 @@ int model_generate_batch_sampled(aha_model* m, const uint32_t* ids, const size_t
 int model_generate_batch_mm(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
                             const aha_sampling_params* params, size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out,
                             float* step_logits_out);
+int model_generate_batch_spec(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new, size_t max_tokens_per_pass,
+                              const aha_spec_config* spec, const uint32_t* predictions, const size_t* prediction_lens, uint32_t* tokens_out,
+                              size_t* n_out, float* logits_out, size_t* n_proposed, size_t* n_accepted, aha_spec_stats* stats);
+// spec_host.hip: the draft proposer (host only).  spec_config_check: AHA_OK or AHA_ERR_INVALID with the message set (who: the entry's name)
+int spec_config_check(const aha_spec_config* spec, const char* who);
+void spec_propose(const aha_spec_config& spec, const uint32_t* ctx, size_t n_ctx, size_t n_prompt, const uint32_t* pred, size_t n_pred,
+                  uint32_t* draft_out, size_t* n_draft);
 int engine_config_check(const aha_engine_config* cfg, size_t* budget_out, size_t* chunk_out);
 int engine_create(aha_model* m, const aha_engine_config* cfg, aha_engine** out);
 void engine_destroy(aha_engine* e);

@@ -2250,6 +2250,7 @@ static void gemv_rows_groups(aha_model* m, GemvRowsArgs g, GemvEpi epi, int rows
 
 struct GenCall {
   int n = 0, V = 0, H = 0, max_nsplit = 1;
+  int rows = 0;   // the largest row count of a step when it exceeds n (draft-and-verify: a sequence's drafts are rows of their own)
   float* ws = nullptr;
   void *x = nullptr, *h = nullptr, *qkv = nullptr, *attn = nullptr, *act = nullptr;
   float *rope = nullptr, *logits = nullptr, *blk_max = nullptr, *part_o = nullptr, *part_ml = nullptr;
@@ -2259,6 +2260,7 @@ struct GenCall {
   uint64_t* pass_pages = nullptr;
   int32_t* h_rowtab = nullptr;   // pinned
   uint32_t* h_tok = nullptr;     // pinned: a step's tokens
+  uint32_t *spec_out = nullptr, *h_spec_out = nullptr;   // draft-and-verify: (n, SPEC_OUT_WORDS) emitted tokens per sequence, device / pinned
   // the caller's outputs: per sequence max_new entries of tokens_out (n_out of them written) and of step_logits_out (V floats each)
   size_t max_new = 0;
   uint32_t* tokens_out = nullptr;
@@ -2374,8 +2376,10 @@ static int check_mm_requests(aha_model* m, const uint32_t* ids, const size_t* se
 // gc.max_nsplit set by the caller
 static int gen_call_alloc(aha_model* m, DevBufs& bufs, GenCall& gc, size_t max_pass_pages) {
   const aha_model_desc& c = m->desc;
-  const int n = gc.n, H = gc.H, V = gc.V, I = c.intermediate_size, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
+  // n: the rows a step can have (the row table also holds one SPEC_SEQ_WORDS entry per sequence behind the rows)
+  const int n = std::max(gc.n, gc.rows), H = gc.H, V = gc.V, I = c.intermediate_size, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
   const int nq = nh * 128, nkv = kvh * 128;
+  const size_t tab_words = (size_t)n * GEN_ROW_WORDS + (size_t)gc.n * SPEC_SEQ_WORDS;
   size_t ws = 0;
   const int shapes[5][2] = {{nq + 2 * nkv, H}, {H, nq}, {2 * I, H}, {H, I}, {V, H}};
   for (auto& sh : shapes) ws = std::max(ws, gemv_rows_ws_floats(std::min(n, GEN_ROW_GROUP), sh[0], sh[1]));
@@ -2386,9 +2390,9 @@ static int gen_call_alloc(aha_model* m, DevBufs& bufs, GenCall& gc, size_t max_p
       (rc = bufs.alloc((bf16_t**)&gc.act, (size_t)n * I)) || (rc = bufs.alloc(&gc.rope, (size_t)n * 128)) ||
       (rc = bufs.alloc(&gc.logits, (size_t)n * V)) || (rc = bufs.alloc(&gc.blk_max, (size_t)n * tiles)) ||
       (rc = bufs.alloc(&gc.blk_idx, (size_t)n * tiles)) || (rc = bufs.alloc(&gc.tok[0], (size_t)n)) || (rc = bufs.alloc(&gc.tok[1], (size_t)n)) ||
-      (rc = bufs.alloc(&gc.rowtab, (size_t)n * GEN_ROW_WORDS)) || (rc = bufs.alloc(&gc.ctr, (size_t)n * kvh * 32, true)) ||
+      (rc = bufs.alloc(&gc.rowtab, tab_words)) || (rc = bufs.alloc(&gc.ctr, (size_t)n * kvh * 32, true)) ||
       (rc = bufs.alloc(&gc.part_o, (size_t)n * gc.max_nsplit * nq)) || (rc = bufs.alloc(&gc.part_ml, (size_t)n * gc.max_nsplit * nh * 2)) ||
-      (rc = bufs.alloc(&gc.pass_pages, max_pass_pages)) || (rc = bufs.alloc_host(&gc.h_rowtab, (size_t)n * GEN_ROW_WORDS)) ||
+      (rc = bufs.alloc(&gc.pass_pages, max_pass_pages)) || (rc = bufs.alloc_host(&gc.h_rowtab, tab_words)) ||
       (rc = bufs.alloc_host(&gc.h_tok, (size_t)n)))
     return rc;
   return AHA_OK;
@@ -2545,7 +2549,10 @@ static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::
 
 // One decode step's device work over the R rows of the uploaded row table gc.rowtab: the tokens tok_in embedded (with their rope rows),
 // every layer, then the head -> tok_out.  kv_tokens: the rows' cache lengths summed (the profile's bytes); max_split: their largest split.
-static void gen_decode_step(aha_model* m, GenCall& gc, int R, int max_split, double kv_tokens, const uint32_t* tok_in, uint32_t* tok_out) {
+// split_append (draft-and-verify steps): rows of one sequence at consecutive positions -- every row's K/V is appended by a launch of its
+// own in front of the attention, whose own append is compiled out, so row i + 1 reads row i's token from the pages.
+static void gen_decode_step(aha_model* m, GenCall& gc, int R, int max_split, double kv_tokens, const uint32_t* tok_in, uint32_t* tok_out,
+                            bool split_append = false) {
   const aha_model_desc& c = m->desc;
   hipStream_t st = m->stream;
   const int H = c.hidden_size, I = c.intermediate_size, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
@@ -2571,8 +2578,12 @@ static void gen_decode_step(aha_model* m, GenCall& gc, int R, int max_split, dou
       b.layer_off = (uint64_t)li * m->layer_stride; b.row_tab = gc.rowtab; b.part_o = gc.part_o; b.part_ml = gc.part_ml; b.o = gc.attn;
       b.head_ctr = gc.ctr; b.ctr_step = li + 1; b.nh = nh; b.kvh = kvh; b.max_nsplit = gc.max_nsplit; b.eps = c.rms_norm_eps;
       b.scale = m->attn_scale;
+      if (split_append) {
+        ProfScope ps(m, "kv_append_rows", (double)R * nkv * 2 * 4, 0);
+        launch_kv_append_rows(b, R, st);
+      }
       ProfScope ps(m, "attn_decode_batch", kv_tokens * 2 * nkv * 2 + (double)R * (nq + 2 * nkv) * 2, 4.0 * kv_tokens * nq);
-      launch_attn_decode_batch(b, R, max_split, st);
+      launch_attn_decode_batch(b, R, max_split, st, !split_append);
     }
     {   // x = x + attn Wo^T                                    (modules.rs:577, qwen3/model.rs:81)
       GemvRowsArgs a{};
@@ -2597,6 +2608,134 @@ static void gen_decode_step(aha_model* m, GenCall& gc, int R, int max_split, dou
   gen_head(m, gc, 0, R, tok_out);
 }
 
+// ---- draft-and-verify greedy decoding (aha_hip_generate_batch_spec) ------------------------------------------------------------------
+struct SpecRun {
+  aha_spec_config cfg;
+  const uint32_t* predictions;    // packed like input_ids, or null
+  const size_t* prediction_lens;
+  size_t *n_proposed, *n_accepted;   // per sequence, may be null
+  aha_spec_stats* stats;             // may be null
+};
+
+// The decode loop of generate_batch_impl with up to max_draft draft tokens per sequence riding along as rows of the same step: a sequence
+// whose cache holds p tokens and whose last token is g contributes rows (g, d1 .. dk) at cache lengths p + 1 .. p + 1 + k on the same pages.
+// Row i's logits are those of plain greedy decoding at its position as long as d1 .. di are the tokens greedy decoding chose there (row
+// isolation of gemv_rows, the unchanged attention body), which is exactly what spec_accept_rows_kernel checks: it keeps the longest
+// confirmed prefix and the token that follows it.  K/V of rejected rows stay in slots >= the new cache length: every reader masks by its
+// kv_len, and the slots are overwritten by the appends of the next steps before any kv_len reaches them.
+// Rows of a step: every active sequence's mandatory row, then drafts in submission order until the total reaches the next multiple of
+// GEN_ROW_GROUP at or above the number of active sequences -- no gemv_rows group is added by speculation.
+// The input tokens of the rows are known on the host (the last emitted token, the drafts): they travel in word GEN_ROW_TOK of the row
+// table, which doubles as the step's token vector; the sequences' (first row, drafts) pairs sit behind the rows, one upload per step.
+static int spec_decode_loop(aha_model* m, GenCall& gc, const SpecRun& sp, const uint32_t* ids, const size_t* seq_lens,
+                            const std::vector<size_t>& pred_off, const std::vector<int64_t>& page0, const std::vector<int64_t>& rope_delta,
+                            std::vector<int>& active, float* logits_out) {
+  const aha_model_desc& c = m->desc;
+  hipStream_t st = m->stream;
+  const int n = gc.n, L = c.num_hidden_layers, g = c.num_attention_heads / c.num_key_value_heads, V = gc.V;
+  const size_t max_new = gc.max_new;
+  // context of the proposer: prompt || generated
+  std::vector<std::vector<uint32_t>> ctx(n);
+  {
+    size_t off = 0;
+    for (int j = 0; j < n; off += seq_lens[j], ++j) {
+      ctx[j].reserve(seq_lens[j] + max_new);
+      ctx[j].assign(ids + off, ids + off + seq_lens[j]);
+      ctx[j].push_back(gc.tokens_out[(size_t)j * max_new]);
+    }
+  }
+  auto is_stop = [&](uint32_t t) {
+    for (int e = 0; e < c.n_stop_tokens; ++e)
+      if (t == c.stop_tokens[e]) return true;
+    return false;
+  };
+  std::vector<unsigned> ctr_acc((size_t)gc.rows, 0u);   // per row slot: the rows of a step change from step to step
+  std::vector<int> row0(n), ndraft(n);
+  uint32_t draft[SPEC_MAX_DRAFT];
+  while (!active.empty()) {
+    const int nact = (int)active.size();
+    int extra = (nact + GEN_ROW_GROUP - 1) / GEN_ROW_GROUP * GEN_ROW_GROUP - nact;
+    int R = 0, max_split = 1, n_drafts = 0;
+    double kv_tokens = 0;
+    for (int a = 0; a < nact; ++a) {
+      const int j = active[a];
+      const size_t t_gen = gc.n_out[j];
+      size_t k = 0;
+      const size_t room = std::min<size_t>((size_t)extra, max_new - t_gen - 1);   // t + 1 + |draft| <= max_new: the cache stays in its pages
+      if (room > 0) {
+        const uint32_t* pred = sp.predictions ? sp.predictions + pred_off[j] : nullptr;
+        spec_propose(sp.cfg, ctx[j].data(), ctx[j].size(), seq_lens[j], pred, pred ? sp.prediction_lens[j] : 0, draft, &k);
+        k = std::min(k, room);
+      }
+      extra -= (int)k;
+      n_drafts += (int)k;
+      row0[a] = R;
+      ndraft[a] = (int)k;
+      for (int i = 0; i <= (int)k; ++i, ++R) {
+        const int kv_len = (int)(seq_lens[j] + t_gen) + i;   // the cache after this row's append
+        const int ns = attn_decode_nsplit(kv_len, g, m->max_nsplit);
+        int32_t* t = gc.h_rowtab + (size_t)R * GEN_ROW_WORDS;
+        t[GEN_ROW_PAGE0] = (int32_t)page0[j];
+        t[GEN_ROW_KVLEN] = kv_len;
+        t[GEN_ROW_NSPLIT] = ns;
+        t[GEN_ROW_CTR] = (int32_t)ctr_acc[R];
+        t[GEN_ROW_POS] = (int32_t)(kv_len - 1 + rope_delta[j]);
+        t[GEN_ROW_SRC] = R * GEN_ROW_WORDS + GEN_ROW_TOK;
+        t[GEN_ROW_CTRROW] = R;
+        t[GEN_ROW_TOK] = (int32_t)(i == 0 ? ctx[j].back() : draft[i - 1]);
+        if (ns > 1) ctr_acc[R] += (unsigned)L * (unsigned)ns;   // a single split never touches its counter
+        max_split = std::max(max_split, ns);
+        kv_tokens += kv_len;
+      }
+    }
+    int32_t* h_seq = gc.h_rowtab + (size_t)R * GEN_ROW_WORDS;
+    for (int a = 0; a < nact; ++a) h_seq[a * SPEC_SEQ_WORDS + SPEC_SEQ_ROW0] = row0[a], h_seq[a * SPEC_SEQ_WORDS + SPEC_SEQ_NDRAFT] = ndraft[a];
+    const size_t words = (size_t)R * GEN_ROW_WORDS + (size_t)nact * SPEC_SEQ_WORDS;
+    AHA_HIP_CHECK(hipMemcpyAsync(gc.rowtab, gc.h_rowtab, words * 4, hipMemcpyHostToDevice, st));
+    // a step without drafts is generate_batch's step: one attention launch per layer, the fused append
+    gen_decode_step(m, gc, R, max_split, kv_tokens, reinterpret_cast<const uint32_t*>(gc.rowtab), gc.tok[0], n_drafts > 0);
+    {
+      ProfScope ps(m, "spec_accept_rows", (double)R * 8, 0);
+      launch_spec_accept_rows(gc.tok[0], gc.rowtab, gc.rowtab + (size_t)R * GEN_ROW_WORDS, nact, gc.spec_out, st);
+    }
+    AHA_HIP_CHECK(hipGetLastError());
+    AHA_HIP_CHECK(hipMemcpyAsync(gc.h_spec_out, gc.spec_out, (size_t)nact * SPEC_OUT_WORDS * 4, hipMemcpyDeviceToHost, st));
+    AHA_HIP_CHECK(hipStreamSynchronize(st));
+    if (sp.stats) sp.stats->decode_steps += 1, sp.stats->rows += (size_t)R, sp.stats->proposed += (size_t)n_drafts;
+    std::vector<int> next;
+    for (int a = 0; a < nact; ++a) {
+      const int j = active[a];
+      const uint32_t* o = gc.h_spec_out + (size_t)a * SPEC_OUT_WORDS;
+      const int emitted = (int)o[SPEC_OUT_COUNT];
+      if (emitted < 1 || emitted > ndraft[a] + 1 || (int)o[SPEC_OUT_LAST_ROW] != row0[a] + emitted - 1) {
+        set_error("generate_batch_spec: the accept step returned an impossible run");
+        return AHA_ERR_STATE;
+      }
+      // stop tokens and max_new in order: the run is cut at, and keeps, the first stop token
+      int kept = 0;
+      bool done = false;
+      while (kept < emitted && !done) {
+        const uint32_t t = o[SPEC_OUT_TOKENS + kept++];
+        gc.tokens_out[(size_t)j * max_new + gc.n_out[j]++] = t;
+        ctx[j].push_back(t);
+        done = is_stop(t) || gc.n_out[j] == max_new;
+      }
+      const size_t acc = (size_t)std::min(kept, emitted - 1);   // drafts among the kept tokens (the run's last token is the row's own choice)
+      if (sp.n_proposed) sp.n_proposed[j] += (size_t)ndraft[a];
+      if (sp.n_accepted) sp.n_accepted[j] += acc;
+      if (sp.stats) sp.stats->accepted += acc;
+      if (done) {   // the logits that chose the last kept token
+        if (logits_out)
+          AHA_HIP_CHECK(hipMemcpy(logits_out + (size_t)j * V, gc.logits + (size_t)(row0[a] + kept - 1) * V, (size_t)V * 4, hipMemcpyDeviceToHost));
+      } else {
+        next.push_back(j);
+      }
+    }
+    active.swap(next);
+  }
+  return AHA_OK;
+}
+
 // params == nullptr: greedy (aha_hip_generate_batch: logits_out = each sequence's last logits).  Otherwise one sampler per sequence
 // (aha_hip_generate_batch_sampled: step_logits_out = every step's logits); the step's tokens are then picked on the host after the batched
 // candidate step, and written back into the token vector the next step's embedding gather reads.  step_logits_out (greedy or sampled):
@@ -2605,7 +2744,8 @@ static void gen_decode_step(aha_model* m, GenCall& gc, int R, int max_split, dou
 // the sequence's rope_delta (qwen3vl/model.rs:1235-1264); m->rope_delta is neither read nor written.
 static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
                                size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* logits_out,
-                               const aha_sampling_params* params, float* step_logits_out, const aha_mm_input* const* mm = nullptr) {
+                               const aha_sampling_params* params, float* step_logits_out, const aha_mm_input* const* mm = nullptr,
+                               const SpecRun* sp = nullptr) {
   const aha_model_desc& c = m->desc;
   if (!ids || !seq_lens || !tokens_out || !n_out) {
     set_error("generate_batch: null input_ids / seq_lens / tokens_out / n_out");
@@ -2633,6 +2773,26 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
   }
   int rc = check_batch_ids(c, "generate_batch", ids, seq_lens, n_seqs, max_new);
   if (rc) return rc;
+  std::vector<size_t> pred_off(n_seqs, 0);
+  if (sp && sp->predictions) {
+    size_t off = 0;
+    for (size_t j = 0; j < n_seqs; off += sp->prediction_lens[j], ++j) {
+      pred_off[j] = off;
+      for (size_t i = 0; i < sp->prediction_lens[j]; ++i)
+        if (sp->predictions[off + i] >= (uint32_t)c.vocab_size) {
+          set_error("generate_batch_spec: prediction id out of range in sequence " + std::to_string(j) + " at position " + std::to_string(i));
+          return AHA_ERR_INVALID;
+        }
+    }
+  }
+  const bool spec_on = sp && sp->cfg.max_draft > 0;
+  if (sp) {
+    if (sp->stats) *sp->stats = aha_spec_stats{0, 0, 0, 0};
+    for (size_t j = 0; j < n_seqs; ++j) {
+      if (sp->n_proposed) sp->n_proposed[j] = 0;
+      if (sp->n_accepted) sp->n_accepted[j] = 0;
+    }
+  }
   std::vector<std::vector<int32_t>> pos3(n_seqs);
   std::vector<int64_t> rope_delta(n_seqs, 0);
   if (mm && (rc = check_mm_requests(m, ids, seq_lens, n_seqs, mm, pos3, rope_delta))) return rc;
@@ -2652,6 +2812,8 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
   DevBufs bufs{st, {}, {}};
   GenCall gc;
   gc.n = n, gc.V = V, gc.H = c.hidden_size, gc.max_new = max_new;
+  // draft-and-verify: a step's rows never pass the next multiple of GEN_ROW_GROUP at or above its sequences (the row budget)
+  if (spec_on) gc.rows = (int)std::min<size_t>((size_t)(n + GEN_ROW_GROUP - 1) / GEN_ROW_GROUP * GEN_ROW_GROUP, (size_t)n * (1 + sp->cfg.max_draft));
   gc.tokens_out = tokens_out, gc.n_out = n_out, gc.step_logits_out = step_logits_out;
   GenChoice ch;
   size_t max_pass_pages = 0;
@@ -2660,6 +2822,8 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
     max_pass_pages += (seq_lens[j] + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
   }
   if ((rc = gen_call_alloc(m, bufs, gc, max_pass_pages)) || (params && (rc = gen_choice_init(bufs, gc, params, ch)))) return rc;
+  if (spec_on && ((rc = bufs.alloc(&gc.spec_out, (size_t)n * SPEC_OUT_WORDS)) || (rc = bufs.alloc_host(&gc.h_spec_out, (size_t)n * SPEC_OUT_WORDS))))
+    return rc;
 
   // ---- prefill: packed passes ----
   for (const PassRange& p : split_passes(seq_lens, n_seqs, max_tokens_per_pass))
@@ -2691,10 +2855,12 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
   }
 
   // ---- decode ----
+  if (spec_on) return spec_decode_loop(m, gc, *sp, ids, seq_lens, pred_off, page0, rope_delta, active, logits_out);
   std::vector<unsigned> ctr_acc(n, 0u);
   int cur = 0;
   while (!active.empty()) {
     const int R = (int)active.size();
+    if (sp && sp->stats) sp->stats->decode_steps += 1, sp->stats->rows += (size_t)R;
     int max_split = 1;
     double kv_tokens = 0;
     for (int r = 0; r < R; ++r) {
@@ -2750,6 +2916,13 @@ int model_generate_batch_mm(aha_model* m, const uint32_t* ids, const size_t* seq
                             const aha_sampling_params* params, size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out,
                             float* step_logits_out) {
   return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, nullptr, params, step_logits_out, mm);
+}
+
+int model_generate_batch_spec(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new, size_t max_tokens_per_pass,
+                              const aha_spec_config* spec, const uint32_t* predictions, const size_t* prediction_lens, uint32_t* tokens_out,
+                              size_t* n_out, float* logits_out, size_t* n_proposed, size_t* n_accepted, aha_spec_stats* stats) {
+  const SpecRun sp{*spec, predictions, prediction_lens, n_proposed, n_accepted, stats};
+  return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, logits_out, nullptr, nullptr, nullptr, &sp);
 }
 
 // ---- continuous batching engine (aha_hip_engine_*) ------------------------------------------------------------------------------

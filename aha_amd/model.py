@@ -413,6 +413,39 @@ class HipInferenceModel:
         return self._generate_batch(lib().aha_hip_generate_batch_mm, prompts, (mm_arr, cp), max_new, max_tokens_per_pass,
                                     "step" if want_step_logits else None)
 
+    def generate_batch_spec(self, prompts: Sequence[Sequence[int]], max_new: int, spec=None, predictions=None, want_logits: bool = False,
+                            want_stats: bool = False, max_tokens_per_pass: int = 0):
+        """generate_batch with draft-and-verify decoding (aha_hip_generate_batch_spec): the same tokens and logits, bit for bit, in fewer
+        decode steps when the drafts are right.  spec: a speculative.SpecConfig (None: its defaults); predictions: None, or per prompt
+        its predicted output (a token list; None or empty = no prediction for that prompt) -- drafts come from the prediction first, then
+        from n-gram lookup in the prompt and the generated text (speculative.propose).  Returns the token lists; with want_logits also the
+        (len(prompts), vocab) float32 logits that chose each prompt's last token; with want_stats also a dict: "proposed" / "accepted"
+        (per prompt draft tokens run / kept) and "stats" (a speculative.SpecStats over the call)."""
+        from .speculative import SpecConfig, SpecStats
+        from ._lib import SpecConfig as CSpecConfig, SpecStats as CSpecStats
+        spec = spec or SpecConfig()
+        cspec = CSpecConfig(int(spec.max_draft), int(spec.ngram_min), int(spec.ngram_max))
+        n = len(prompts)
+        pp = pl = None
+        if predictions is not None:
+            if len(predictions) != n:
+                raise ValueError(f"{len(predictions)} predictions for {n} prompts")
+            pl = np.asarray([0 if p is None else len(p) for p in predictions], dtype=np.uint64)
+            flat = [int(t) for p in predictions if p is not None for t in p]
+            pp = np.ascontiguousarray(np.asarray(flat + [0], dtype=np.uint32))   # never a null pointer, even when every prediction is empty
+        prop, acc, st = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64), CSpecStats()
+        extra = (C.byref(cspec), None if pp is None else pp.ctypes.data, None if pl is None else pl.ctypes.data)
+
+        def entry(handle, ids, lens, n_, ex0, ex1, ex2, mx, pas, toks, n_out, lg):
+            return lib().aha_hip_generate_batch_spec(handle, ids, lens, n_, mx, pas, ex0, ex1, ex2, toks, n_out, lg, prop.ctypes.data,
+                                                     acc.ctypes.data, C.byref(st))
+        res = self._generate_batch(entry, prompts, extra, max_new, max_tokens_per_pass, "last" if want_logits else None)
+        if not want_stats:
+            return res
+        info = {"proposed": [int(v) for v in prop[:n]], "accepted": [int(v) for v in acc[:n]],
+                "stats": SpecStats(int(st.decode_steps), int(st.rows), int(st.proposed), int(st.accepted))}
+        return (*res, info) if want_logits else (res, info)
+
     def embed_multi(self, inputs: Sequence[Sequence[int]]) -> np.ndarray:
         if len(inputs) == 0:
             raise ValueError("embedding input cannot be empty")  # qwen3_embedding/mod.rs:39-41
@@ -663,6 +696,9 @@ class Usage:
     prompt_secs: float
     completion_tokens: int
     completion_secs: float
+    # params/shared.rs:58-63 (CompletionTokensDetails): filled only by generate_generic_batch_spec
+    accepted_prediction_tokens: Optional[int] = None
+    rejected_prediction_tokens: Optional[int] = None
 
     @property
     def completion_tps(self) -> float:
@@ -730,3 +766,14 @@ def generate_generic_batch_mm(model: HipInferenceModel, prompts: Sequence[Sequen
     out = model.generate_batch_mm(prompts, data, max_tokens, params, max_tokens_per_pass)
     secs = time.perf_counter() - t0
     return out, Usage(sum(len(p) for p in prompts), 0.0, sum(len(o) for o in out), secs)
+
+
+def generate_generic_batch_spec(model: HipInferenceModel, prompts: Sequence[Sequence[int]], max_tokens: int, spec=None, predictions=None,
+                                max_tokens_per_pass: int = 0):
+    """generate_generic_batch with draft-and-verify decoding (HipInferenceModel.generate_batch_spec): the same tokens; the Usage also
+    carries accepted_prediction_tokens / rejected_prediction_tokens (draft tokens kept / run and dropped, over all prompts)."""
+    t0 = time.perf_counter()
+    out, info = model.generate_batch_spec(prompts, max_tokens, spec, predictions, want_stats=True, max_tokens_per_pass=max_tokens_per_pass)
+    secs = time.perf_counter() - t0
+    acc, prop = sum(info["accepted"]), sum(info["proposed"])
+    return out, Usage(sum(len(p) for p in prompts), 0.0, sum(len(o) for o in out), secs, acc, prop - acc)

@@ -249,6 +249,55 @@ int aha_hip_generate_batch_mm(aha_model* m, const uint32_t* input_ids, const siz
                               const aha_mm_input* const* mm, const aha_sampling_params* params, size_t max_new,
                               size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* step_logits_out);
 
+/* ---- draft-and-verify greedy generation -----------------------------------------------------------------------------------
+ * aha_hip_generate_batch with up to max_draft draft tokens per sequence verified in every decode step: Predicted Outputs (the request's
+ * `prediction`, /root/reference/src/params/chat.rs:105, whose usage counters accepted_prediction_tokens / rejected_prediction_tokens are
+ * params/shared.rs:58-63; the reference declares them and never fills them in) plus prompt-lookup drafting.  A sequence whose cache holds
+ * p tokens runs its last token and its k draft tokens as k + 1 rows of the same step, at positions p .. p + k on its own pages; the longest
+ * draft prefix that equals what greedy decoding chooses is kept, with the token that follows it.  tokens_out, n_out and logits_out are
+ * EXACTLY those of aha_hip_generate_batch on the same arguments -- equal, not close -- for any spec and any predictions, wrong or
+ * adversarial ones included: a wrong draft costs rows of a step, never a token.  Greedy only.
+ *   spec         max_draft 1..15 draft tokens per sequence per step (0: speculation off, aha_hip_generate_batch's own steps);
+ *                ngram_min .. ngram_max (1 <= min <= max <= 8): the suffix lengths the n-gram rules try, longest first.
+ *   predictions  NULL with prediction_lens NULL, or the sequences' predicted outputs packed like input_ids, prediction_lens[j] ids each
+ *                (a length may be 0: no prediction for that sequence).
+ *   drafts       per sequence and step, the first non-empty of (c = prompt || generated, n = |c|, t generated tokens, D = max_draft):
+ *                1. generated[0:t] == p[0:t]: p[t : t+D];  2. for k = ngram_max .. ngram_min, s = c[n-k:n], the earliest i with
+ *                p[i:i+k] == s and i + k < |p|: p[i+k : i+k+D];  3. the same k loop over c, the latest i < n - k with c[i:i+k] == s:
+ *                c[i+k : min(i+k+D, n)] (aha_hip_spec_propose).  A draft is cut so that t + 1 + |draft| <= max_new.
+ *   row budget   every unfinished sequence has its one row; drafts are then granted in submission order until the step's rows reach the
+ *                next multiple of 32 at or above the number of unfinished sequences: speculation never adds a pass over the weights.
+ *   n_proposed / n_accepted (n_seqs each, may be NULL): draft tokens run / kept per sequence (a request's accepted_prediction_tokens,
+ *                and rejected = proposed - accepted);  stats (may be NULL): decode steps, rows over all steps, proposed, accepted.
+ * Supported models, errors, the page reservation ceil((len + max_new) / 64) and the cache clearing are aha_hip_generate_batch's.
+ * AHA_ERR_INVALID before any device work, additionally: "null spec"; "max_draft must be in 0..15"; "n-gram bounds must satisfy
+ * 1 <= ngram_min <= ngram_max <= 8"; "predictions and prediction_lens must both be set or both be null"; "prediction id out of
+ * range" (an id >= vocab_size, naming the sequence and position). */
+typedef struct aha_spec_config {
+  int32_t max_draft;  /* 1..15 draft tokens per sequence per step; 0 = speculation off */
+  int32_t ngram_min;  /* >= 1 */
+  int32_t ngram_max;  /* >= ngram_min, <= 8 */
+} aha_spec_config;
+
+typedef struct aha_spec_stats {
+  size_t decode_steps;
+  size_t rows;       /* rows run over all steps */
+  size_t proposed;
+  size_t accepted;
+} aha_spec_stats;
+
+int aha_hip_generate_batch_spec(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
+                                size_t max_tokens_per_pass, const aha_spec_config* spec, const uint32_t* predictions,
+                                const size_t* prediction_lens, uint32_t* tokens_out, size_t* n_out, float* logits_out, size_t* n_proposed,
+                                size_t* n_accepted, aha_spec_stats* stats);
+
+/* Host only: the draft the rules above yield for one sequence -- context = prompt || generated (n_context ids, the first n_prompt of them
+ * the prompt), its prediction (NULL or n_prediction == 0: none).  draft_out: room for max_draft ids; *n_draft: how many were written
+ * (0: no draft, the sequence runs one row).  AHA_ERR_INVALID: a bad spec (as above), a null context / draft_out / n_draft, an empty
+ * context or n_prompt > n_context. */
+int aha_hip_spec_propose(const aha_spec_config* spec, const uint32_t* context, size_t n_context, size_t n_prompt,
+                         const uint32_t* prediction, size_t n_prediction, uint32_t* draft_out, size_t* n_draft);
+
 /* ---- continuous batching engine --------------------------------------------------------------------------------------------
  * A stateful server loop over the generate_batch machinery, for generate_stream_generic (/root/reference/src/models/common/generate.rs:
  * 231-368, `stream: true`): requests are submitted at any time, every step returns one event per emitted token, requests can be cancelled,

@@ -139,6 +139,26 @@ pub mod sys {
         pub compute_dtype: i32,
     }
 
+    /// `aha_spec_config`: draft-and-verify decoding (aha_hip_generate_batch_spec)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug)]
+    pub struct AhaSpecConfig {
+        /// 1..15 draft tokens per sequence per step; 0 = speculation off
+        pub max_draft: i32,
+        pub ngram_min: i32,
+        pub ngram_max: i32,
+    }
+
+    /// `aha_spec_stats`
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct AhaSpecStats {
+        pub decode_steps: usize,
+        pub rows: usize,
+        pub proposed: usize,
+        pub accepted: usize,
+    }
+
     /// `aha_tensor_view`
     #[repr(C)]
     pub struct AhaTensorView {
@@ -297,6 +317,33 @@ pub mod sys {
             tokens_out: *mut u32,
             n_out: *mut usize,
             step_logits_out: *mut f32,
+        ) -> i32;
+        pub fn aha_hip_generate_batch_spec(
+            m: *mut AhaModel,
+            ids: *const u32,
+            seq_lens: *const usize,
+            n_seqs: usize,
+            max_new: usize,
+            max_tokens_per_pass: usize,
+            spec: *const AhaSpecConfig,
+            predictions: *const u32,
+            prediction_lens: *const usize,
+            tokens_out: *mut u32,
+            n_out: *mut usize,
+            logits_out: *mut f32,
+            n_proposed: *mut usize,
+            n_accepted: *mut usize,
+            stats: *mut AhaSpecStats,
+        ) -> i32;
+        pub fn aha_hip_spec_propose(
+            spec: *const AhaSpecConfig,
+            context: *const u32,
+            n_context: usize,
+            n_prompt: usize,
+            prediction: *const u32,
+            n_prediction: usize,
+            draft_out: *mut u32,
+            n_draft: *mut usize,
         ) -> i32;
         pub fn aha_hip_engine_create(m: *mut AhaModel, cfg: *const AhaEngineConfig, out: *mut *mut AhaEngine) -> i32;
         pub fn aha_hip_engine_destroy(e: *mut AhaEngine);
@@ -611,6 +658,57 @@ impl Model {
             )
         })?;
         Ok(n_out.iter().enumerate().map(|(j, &n)| toks[j * max_new..j * max_new + n].to_vec()).collect())
+    }
+
+    /// `generate_batch` with draft-and-verify decoding (aha_hip_generate_batch_spec): the same tokens, bit for bit, in fewer decode
+    /// steps when the drafts are right.  `predictions`: `None`, or per prompt its predicted output (the request's `prediction`,
+    /// params/chat.rs:105; an empty slice = none for that prompt).  Returns the token lists, per prompt (proposed, accepted) draft
+    /// tokens -- `accepted_prediction_tokens` = accepted, `rejected_prediction_tokens` = proposed - accepted (params/shared.rs:58-63)
+    /// -- and the call's statistics.
+    pub fn generate_batch_spec(
+        &mut self,
+        prompts: &[&[u32]],
+        max_new: usize,
+        max_tokens_per_pass: usize,
+        spec: sys::AhaSpecConfig,
+        predictions: Option<&[&[u32]]>,
+    ) -> Result<(Vec<Vec<u32>>, Vec<(usize, usize)>, sys::AhaSpecStats), Error> {
+        if let Some(p) = predictions {
+            if p.len() != prompts.len() {
+                return Err(Error { code: -1, message: format!("{} predictions for {} prompts", p.len(), prompts.len()) });
+            }
+        }
+        let ids: Vec<u32> = prompts.iter().flat_map(|s| s.iter().copied()).collect();
+        let lens: Vec<usize> = prompts.iter().map(|s| s.len()).collect();
+        // one spare id keeps the pointer non-null when every prediction is empty
+        let pred_ids: Vec<u32> = predictions.map(|p| p.iter().flat_map(|s| s.iter().copied()).chain(std::iter::once(0)).collect()).unwrap_or_default();
+        let pred_lens: Vec<usize> = predictions.map(|p| p.iter().map(|s| s.len()).collect()).unwrap_or_default();
+        let mut toks = vec![0u32; prompts.len() * max_new.max(1)];
+        let mut n_out = vec![0usize; prompts.len()];
+        let mut proposed = vec![0usize; prompts.len()];
+        let mut accepted = vec![0usize; prompts.len()];
+        let mut stats = sys::AhaSpecStats::default();
+        check(unsafe {
+            sys::aha_hip_generate_batch_spec(
+                self.model,
+                ids.as_ptr(),
+                lens.as_ptr(),
+                lens.len(),
+                max_new,
+                max_tokens_per_pass,
+                &spec,
+                if predictions.is_some() { pred_ids.as_ptr() } else { std::ptr::null() },
+                if predictions.is_some() { pred_lens.as_ptr() } else { std::ptr::null() },
+                toks.as_mut_ptr(),
+                n_out.as_mut_ptr(),
+                std::ptr::null_mut(),
+                proposed.as_mut_ptr(),
+                accepted.as_mut_ptr(),
+                &mut stats,
+            )
+        })?;
+        let out = n_out.iter().enumerate().map(|(j, &n)| toks[j * max_new..j * max_new + n].to_vec()).collect();
+        Ok((out, proposed.into_iter().zip(accepted).collect(), stats))
     }
 
     /// `generate_generic` with each prompt's own sampler, every prompt at once (aha_hip_generate_batch_sampled): per prompt, the
