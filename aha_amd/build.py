@@ -17,6 +17,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # Debug builds (measurement scripts only; never the shipped library): AHA_BUILD_DEFINES="-DAHA_DEBUG_KERNELS" compiles the ablation / trace
 # instantiations and their environment dispatch in (README "Debug kernels"); the flags are part of the build digest.
 FLAGS += [f for f in os.environ.get("AHA_BUILD_DEFINES", "").split() if f.startswith("-D")]
+# Per-source extra flags.  Kernarg preload: the decode step's kernels (matvec, fused decode attention, the step's state kernels) take
+# what they need in front of their first memory request as plain leading parameters, and gfx950 delivers up to 14 such dwords in user
+# SGPRs at wave launch instead of through a scalar load from the kernarg segment.  The compiler keeps a prologue that loads the same
+# values itself for firmware that does not preload.  Only these translation units: every other one compiles exactly as with FLAGS.
+_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+EXTRA_FLAGS = {"kernels_gemv.hip": _PRELOAD, "kernels_attn.hip": _PRELOAD, "model.hip": _PRELOAD}
 
 
 def _hipcc() -> str:
@@ -33,6 +39,7 @@ def _digest(paths) -> str:
             h.update(os.path.basename(p).encode())  # not the absolute path: the tree is copied to other roots (gpurun)
             h.update(f.read())
     h.update(" ".join(FLAGS).encode())
+    h.update(repr(sorted(EXTRA_FLAGS.items())).encode())
     return h.hexdigest()
 
 
@@ -67,7 +74,7 @@ def _build_locked(srcs, stamp: str, dig: str, verbose: bool) -> str:
 
     def compile_one(src):
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
-        cmd = [hipcc, *FLAGS, "-c", src, "-o", obj]
+        cmd = [hipcc, *FLAGS, *EXTRA_FLAGS.get(os.path.basename(src), []), "-c", src, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed for {src}:\n{r.stderr}")

@@ -561,15 +561,66 @@ __global__ __launch_bounds__(128) void attn_decode_combine_kernel(AttnDecodeArgs
   ((bf16_t*)a.o)[head * 128 + d] = f2bf(acc / lsum);
 }
 
-__global__ __launch_bounds__(256, 2) void attn_decode_fused_kernel(AttnDecodeFusedArgs a) {
+// Kernel arguments of the fused decode attention.  What the prologue needs in front of its first requests -- the qkv row, the page
+// table, the rope table, the norm weights, the cache length, and the head counts with the split count (nh | kvh << 10 | nsplit << 20: gridDim itself is
+// an implicit kernel argument, i.e. another kernarg load) -- are plain leading parameters: 14 dwords, delivered in user SGPRs at wave launch on gfx950 (kernarg preload, build.py), so the launch's chain of dependent round trips
+// no longer starts with a scalar load from the kernarg segment the host has just written.  The rest is first used behind those requests
+// and travels in the trailing struct.  The trace pointer is tested in front of the first request (stamp(0)): the shipped kernel holds it
+// null at compile time, AHA_ATTN_TRACE launches the traced twin.
+struct AttnDecodeFusedTail {
+  float* part_o;
+  float* part_ml;
+  void* o;
+  unsigned* head_ctr;
+  unsigned long long* trace;
+  unsigned ctr_target;
+  int kv_start_v, kv_kvh, kv_d;
+  float eps, scale;
+};
+
+template <bool TRACE>
+__device__ __forceinline__ void attn_decode_fused_flat(const void* qkv, const uint64_t* page_ptrs, uint64_t layer_off, const float* rope,
+                                                       const void* q_norm_w, const void* k_norm_w, int kv_len_v, int dims,
+                                                       const AttnDecodeFusedTail& t, char* smem) {
+  AttnDecodeFusedArgs a;
+  a.qkv = qkv; a.q_norm_w = q_norm_w; a.k_norm_w = k_norm_w; a.rope = rope;
+  a.kv.page_ptrs = page_ptrs; a.kv.layer_off = layer_off; a.kv.kvh = t.kv_kvh; a.kv.d = t.kv_d;
+  a.kv_start_v = t.kv_start_v; a.kv_len_v = kv_len_v;
+  a.part_o = t.part_o; a.part_ml = t.part_ml; a.o = t.o; a.head_ctr = t.head_ctr; a.ctr_target = t.ctr_target;
+  a.trace = TRACE ? t.trace : nullptr;
+  a.nh = dims & 1023; a.kvh = (dims >> 10) & 1023; a.nsplit = dims >> 20; a.eps = t.eps; a.scale = t.scale;
+  attn_decode_fused_body(a, smem, (int)blockIdx.x, (int)blockIdx.y, a.nsplit);
+}
+
+__global__ __launch_bounds__(256, 2) void attn_decode_fused_kernel(const void* qkv, const uint64_t* page_ptrs, uint64_t layer_off,
+                                                                   const float* rope, const void* q_norm_w, const void* k_norm_w,
+                                                                   int kv_len_v, int dims, AttnDecodeFusedTail t) {
   __shared__ __attribute__((aligned(16))) char smem[ATTN_DECODE_FUSED_LDS];
-  attn_decode_fused_body(a, smem, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y);
+  attn_decode_fused_flat<false>(qkv, page_ptrs, layer_off, rope, q_norm_w, k_norm_w, kv_len_v, dims, t, smem);
+}
+__global__ __launch_bounds__(256, 2) void attn_decode_fused_traced_kernel(const void* qkv, const uint64_t* page_ptrs, uint64_t layer_off,
+                                                                          const float* rope, const void* q_norm_w, const void* k_norm_w,
+                                                                          int kv_len_v, int dims, AttnDecodeFusedTail t) {
+  __shared__ __attribute__((aligned(16))) char smem[ATTN_DECODE_FUSED_LDS];
+  attn_decode_fused_flat<true>(qkv, page_ptrs, layer_off, rope, q_norm_w, k_norm_w, kv_len_v, dims, t, smem);
 }
 
 }  // namespace
 
 void launch_attn_decode_fused(const AttnDecodeFusedArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(attn_decode_fused_kernel, dim3(a.kvh, a.nsplit), dim3(256), 0, st, a);
+  const AttnDecodeFusedTail t{a.part_o, a.part_ml, a.o, a.head_ctr, a.trace, a.ctr_target, a.kv_start_v, a.kv.kvh, a.kv.d, a.eps, a.scale};
+  // 10 bits each for the head counts, 11 for the split count (g * nsplit <= 1024: the LDS tables of the split merge)
+  if (a.nh > 1023 || a.kvh > 1023 || a.nsplit > 1024 || a.nsplit < 1) {
+    fprintf(stderr, "launch_attn_decode_fused: head / split counts out of range\n");
+    abort();
+  }
+  const int dims = a.nh | (a.kvh << 10) | (a.nsplit << 20);
+  if (a.trace == nullptr)
+    hipLaunchKernelGGL(attn_decode_fused_kernel, dim3(a.kvh, a.nsplit), dim3(256), 0, st, a.qkv, a.kv.page_ptrs, a.kv.layer_off, a.rope,
+                       a.q_norm_w, a.k_norm_w, a.kv_len_v, dims, t);
+  else
+    hipLaunchKernelGGL(attn_decode_fused_traced_kernel, dim3(a.kvh, a.nsplit), dim3(256), 0, st, a.qkv, a.kv.page_ptrs, a.kv.layer_off, a.rope,
+                       a.q_norm_w, a.k_norm_w, a.kv_len_v, dims, t);
 }
 
 static int g_attn_smx_override = -1;

@@ -18,10 +18,32 @@ namespace aha {
 
 namespace {
 
-template <int R, int U, int EPI, bool FAST>
-__global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel(GemvArgs a) {
+// Kernel arguments.  The values every wave needs before it can request anything (the matrix, the activation vector, the norm weights,
+// the output, the shape, the grid size -- gridDim itself is an implicit kernel argument, i.e. another kernarg load) are plain leading
+// parameters: 14 dwords, which gfx950 delivers in user SGPRs at wave launch (kernarg preload,
+// build.py) -- a struct by value is passed by reference and its first use is a scalar load from the kernarg segment the host has just
+// written, one cold round trip in front of the first request of every launch.  `aux` is the one further pointer an epilogue's first
+// request needs: the residual vector, or (GEMV_SILU_MUL, which has no residual) the separate up matrix W2.  What is first used behind
+// the first weight tile travels in the trailing struct and is loaded from the kernarg segment as before.  The trace pointer is tested in
+// front of the first request (stamp(0)): it is null at compile time unless TRACE (AHA_GEMV_TRACE).
+struct GemvTailArgs {
+  float* y_f32;
+  float* blk_max;
+  uint32_t* blk_idx;
+  void* h_out;
+  unsigned long long* trace;
+  int cached;
+};
+
+template <int R, int U, int EPI, bool FAST, bool TRACE>
+__global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel(const void* W, const void* x, const void* norm_w, void* y, const void* aux, int N,
+                                                            int K, float eps, int nblk, GemvTailArgs t) {
   extern __shared__ __attribute__((aligned(16))) float xs[];  // K f32 + 8 floats reduction scratch
-  gemv_body<R, U, EPI, false, FAST>(a, xs, (int)blockIdx.x, (int)gridDim.x, [] {});
+  GemvArgs a;
+  a.W = W; a.W2 = EPI == GEMV_SILU_MUL ? aux : nullptr; a.x = x; a.norm_w = norm_w; a.residual = EPI == GEMV_SILU_MUL ? nullptr : aux; a.y = y;
+  a.y_f32 = t.y_f32; a.blk_max = t.blk_max; a.blk_idx = t.blk_idx; a.h_out = t.h_out; a.N = N; a.K = K; a.eps = eps; a.cached = t.cached;
+  a.trace = TRACE ? t.trace : nullptr;
+  gemv_body<R, U, EPI, false, FAST>(a, xs, (int)blockIdx.x, nblk, [] {});
 }
 
 struct GemvPlan { int R, U, grid; };
@@ -88,10 +110,17 @@ static void launch_gemv_epi(const GemvArgs& a, const GemvPlan& p, hipStream_t st
   // FAST form (gemv_body.h): every chunk group full and in range, weights non-temporal
   static const bool fast_ok = [] { const char* e = getenv("AHA_GEMV_FAST"); return e ? atoi(e) != 0 : true; }();
   const bool fast = fast_ok && a.K % (512 * p.U) == 0 && !a.cached && a.N >= 1;
-#define GV(RR, UU)                                                                            \
-  do {                                                                                        \
-    if (fast) hipLaunchKernelGGL((gemv_kernel<RR, UU, EPI, true>), grid, block, lds, st, a);  \
-    else hipLaunchKernelGGL((gemv_kernel<RR, UU, EPI, false>), grid, block, lds, st, a);      \
+  const GemvTailArgs t{a.y_f32, a.blk_max, a.blk_idx, a.h_out, a.trace, a.cached};
+  const void* aux = EPI == GEMV_SILU_MUL ? a.W2 : a.residual;
+#define GV_(RR, UU, FF, TT) \
+  hipLaunchKernelGGL((gemv_kernel<RR, UU, EPI, FF, TT>), grid, block, lds, st, a.W, a.x, a.norm_w, a.y, aux, a.N, a.K, a.eps, p.grid, t)
+#define GV(RR, UU)                                                      \
+  do {                                                                  \
+    if (a.trace == nullptr) {                                           \
+      if (fast) GV_(RR, UU, true, false); else GV_(RR, UU, false, false); \
+    } else {                                                            \
+      if (fast) GV_(RR, UU, true, true); else GV_(RR, UU, false, true);   \
+    }                                                                   \
   } while (0)
   if (p.R == 4) {
     if (p.U >= 4) GV(4, 4); else if (p.U == 2) GV(4, 2); else GV(4, 1);
@@ -101,6 +130,7 @@ static void launch_gemv_epi(const GemvArgs& a, const GemvPlan& p, hipStream_t st
     if (p.U >= 8) GV(1, 8); else if (p.U == 4) GV(1, 4); else if (p.U == 2) GV(1, 2); else GV(1, 1);
   }
 #undef GV
+#undef GV_
 }
 
 void launch_gemv(const GemvArgs& a_in, GemvEpi epi, hipStream_t st) {

@@ -840,7 +840,7 @@ static int push_state(aha_model* m, uint32_t token, const int64_t pos[3], size_t
 
 // final RMSNorm (qwen3/model.rs:186) fused into the lm_head matvec of the LAST position only (model.rs:187,142),
 // f32 logits + argmax partials -> d_state->next_token
-static void enqueue_lm_head(aha_model* m, const void* x_last) {
+static void enqueue_lm_head(aha_model* m, const void* x_last, bool argmax = true) {
   const aha_model_desc& c = m->desc;
   GemvArgs g{};
   g.W = m->lm_head;
@@ -857,6 +857,7 @@ static void enqueue_lm_head(aha_model* m, const void* x_last) {
     ProfScope ps(m, "gemv", (double)m->lm_rows * c.hidden_size * 2 + c.hidden_size * 2 + m->lm_rows * 4.0, 2.0 * m->lm_rows * c.hidden_size);
     launch_gemv(g, GEMV_LOGITS, m->stream);
   }
+  if (!argmax) return;   // the caller reduces the partials itself (step_tail_kernel)
   ProfScope ps(m, "argmax", 0, 0);
   const int ntiles = gemv_num_tiles(m->lm_rows, c.hidden_size);
   if (m->lm_rows == c.vocab_size) {
@@ -1299,6 +1300,68 @@ __global__ void advance_state_kernel(StepState* st, uint32_t* token_log, uint32_
   __hip_atomic_store(host_done, (uint32_t)step + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// Tail of a step of the device-resident greedy loop (model_decode_greedy): argmax_partials_kernel + advance_state_kernel + the NEXT step's
+// embed_state_kernel in one launch -- three single-block launches, each waiting on one or two dependent round trips, were 12.6 us of the
+// 8B step.  Same values: the argmax rule (larger value, then smaller index) is a total order, so the order of the reduction is free;
+// thread 0 then does advance_state_kernel's updates and stores verbatim; the embedding row and the rope table of the advanced position
+// are embed_state_kernel's expressions on the values thread 0 has just written (handed over through LDS).  d_x and d_rope were last
+// read by the lm_head matvec and the step's last attention launch, both earlier in the stream.
+__global__ __launch_bounds__(256) void step_tail_kernel(const float* __restrict__ pv, const uint32_t* __restrict__ pi, int n, StepState* st,
+                                                        const bf16_t* __restrict__ table, bf16_t* __restrict__ out, int H,
+                                                        const float* __restrict__ inv_freq, const int32_t* __restrict__ axis_map,
+                                                        float* __restrict__ rope, uint32_t* token_log, uint32_t* host_ring,
+                                                        uint32_t* host_done) {
+  __shared__ float sv[4];
+  __shared__ uint32_t si[4];
+  __shared__ uint32_t s_token;
+  __shared__ int32_t s_pos[3];
+  auto combine = [](float& bv, uint32_t& bi, float v, uint32_t i) {
+    if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+  };
+  float bv = -INFINITY;
+  uint32_t bi = 0xffffffffu;
+  for (int i = threadIdx.x; i < n; i += 256) combine(bv, bi, pv[i], pi[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const uint32_t oi = __shfl_xor(bi, o, 64);
+    combine(bv, bi, ov, oi);
+  }
+  if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) combine(bv, bi, sv[w], si[w]);
+    const uint32_t t = bi;
+    const int32_t step = st->step;
+    const int32_t p0 = st->pos[0] + 1, p1 = st->pos[1] + 1, p2 = st->pos[2] + 1;
+    st->next_token = t;
+    token_log[step & 0xffff] = t;
+    st->step = step + 1;
+    st->token = t;
+    st->pos[0] = p0;
+    st->pos[1] = p1;
+    st->pos[2] = p2;
+    st->kv_start += 1;
+    st->kv_len += 1;
+    // publish to the host: token first, then the count (release at system scope: the host reads the count, then the slot)
+    __hip_atomic_store(host_ring + ((uint32_t)step % RING_CAP), t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(host_done, (uint32_t)step + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    s_token = t;
+    s_pos[0] = p0; s_pos[1] = p1; s_pos[2] = p2;
+  }
+  __syncthreads();
+  // the next step's embed_state_kernel
+  const u32x4_t* src = reinterpret_cast<const u32x4_t*>(table + (size_t)s_token * H);
+  u32x4_t* dst = reinterpret_cast<u32x4_t*>(out);
+  for (int i = threadIdx.x; i < H / 8; i += 256) dst[i] = src[i];
+  if (threadIdx.x < 64) {
+    const int i = threadIdx.x;
+    const float ang = (float)s_pos[axis_map[i]] * inv_freq[i];
+    rope[i] = rbf(cosf(ang));
+    rope[64 + i] = rbf(sinf(ang));
+  }
+}
+
 // AHA_GEMV_TRACE=1: in-kernel timeline of the decode matvecs (launch-per-op path), dumped by fetch_outputs
 static unsigned long long* gemv_trace_slot(aha_model* m, int launch_idx) {
   static const char* e = getenv("AHA_GEMV_TRACE");
@@ -1341,12 +1404,15 @@ static void gemv_trace_dump(aha_model* m) {
   }
 }
 
-static void enqueue_decode_step(aha_model* m, size_t kv_len_after) {
+// embed = false: d_x and the rope table of this step were written by the previous step's tail.  tail = true (device-resident loop, whole
+// vocabulary on this rank): the step ends with step_tail_kernel instead of the argmax launch (and the caller's advance_state_kernel).
+static bool decode_tail_fused(const aha_model* m) { return m->lm_rows == m->desc.vocab_size; }
+static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = true, bool tail = false) {
   const aha_model_desc& c = m->desc;
   const int H = c.hidden_size, I = c.intermediate_size, d = c.head_dim, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
   const int nq = nh * d, nkv = kvh * d;
   hipStream_t st = m->stream;
-  {
+  if (embed) {
     ProfScope ps(m, "elem", H * 4.0, 0);
     hipLaunchKernelGGL(embed_state_kernel, dim3(1), dim3(256), 0, st, (const bf16_t*)m->embed, m->d_state, (bf16_t*)m->d_x, H,
                        m->d_inv_freq, m->d_axis_map, m->d_rope);
@@ -1434,7 +1500,15 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after) {
       gemv_row_parallel(m, g);
     }
   }
-  enqueue_lm_head(m, m->d_x);
+  if (!tail) {
+    enqueue_lm_head(m, m->d_x);
+    return;
+  }
+  enqueue_lm_head(m, m->d_x, false);
+  ProfScope ps(m, "argmax", H * 4.0, 0);
+  hipLaunchKernelGGL(step_tail_kernel, dim3(1), dim3(256), 0, st, m->d_blk_max, m->d_blk_idx, gemv_num_tiles(m->lm_rows, H), m->d_state,
+                     (const bf16_t*)m->embed, (bf16_t*)m->d_x, H, m->d_inv_freq, m->d_axis_map, m->d_rope, m->d_token_log, m->h_ring_dev,
+                     m->h_done_dev);
 }
 
 int model_forward_step(aha_model* m, uint32_t token, size_t offset, float* logits_out, uint32_t* argmax_out) {
@@ -1547,13 +1621,17 @@ int model_decode_greedy(aha_model* m, uint32_t first_token, size_t offset, size_
   // queues `ahead` more steps and then waits for ever in their all-reduces).  Under TP the schedule is therefore a function of the
   // token sequence alone: whole groups of `ahead` steps, the next group only after every token of the last one has been read.
   const bool lockstep = m->tp_size > 1;
+  const bool fused_tail = decode_tail_fused(m);
   while (seen < max_new && !stop) {
     size_t want = 0;
     if (!lockstep) want = enq < max_new && enq - seen < ahead ? std::min(max_new - enq, ahead - (enq - seen)) : 0;
     else if (seen == enq) want = std::min(max_new - enq, ahead);
     for (size_t i = 0; i < want; ++i) {
-      enqueue_decode_step(m, base_len + enq + 1);
-      hipLaunchKernelGGL(advance_state_kernel, dim3(1), dim3(1), 0, m->stream, m->d_state, m->d_token_log, m->h_ring_dev, m->h_done_dev);
+      // one tail launch per step: it also writes the next step's d_x and rope table (the one after the last queued step is never used);
+      // only the first step of the call embeds its own token (push_state above)
+      enqueue_decode_step(m, base_len + enq + 1, !fused_tail || enq == 0, fused_tail);
+      if (!fused_tail)
+        hipLaunchKernelGGL(advance_state_kernel, dim3(1), dim3(1), 0, m->stream, m->d_state, m->d_token_log, m->h_ring_dev, m->h_done_dev);
       ++enq;
     }
     AHA_HIP_CHECK(hipGetLastError());
