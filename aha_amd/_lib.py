@@ -149,6 +149,7 @@ SIGNATURES = {
     "aha_hip_get_profile": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "aha_hip_debug_scramble_pages": (C.c_int, [_P, C.c_int]),
+    "aha_hip_debug_attn_decode_form": (C.c_int, [_P]),
     "aha_hip_debug_last_hidden": (C.c_int, [_P, C.POINTER(C.c_float), C.c_size_t]),
     "aha_hip_debug_image_embeds": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.c_size_t]),
     "aha_hip_rmsnorm": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P]),

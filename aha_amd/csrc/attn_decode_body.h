@@ -6,7 +6,12 @@
 namespace aha {
 
 constexpr int ATTN_DECODE_NW = 4;  // waves (= KV units) per workgroup
-constexpr int ATTN_DECODE_FUSED_LDS = 16 * 128 * 2 + 128 * 2 + 128 * 2 + ATTN_DECODE_NW * 128 * 16 * 4 + 2 * ATTN_DECODE_NW * 16 * 4;  // bytes
+// Row of the per-wave staging image of the in-block merge, in floats: O of a wave is kept [q 16][d 128 (+4)].  The MFMA fragment of a
+// lane is 4 consecutive d of one q: one ds_write_b128 at q * ROW + d; ROW = 132 = 4 (mod 32) spreads the 8 lanes (8 consecutive q) of a
+// store's lane group over the 32 banks.  A merge thread reads 4 consecutive d of one q, 32 threads a row: ds_read_b128, 512 contiguous
+// bytes per half wave.  Both conflict-free.  (The [d][q 16] image this replaces was read with all 32 lanes of a group on ONE bank.)
+constexpr int ATTN_DECODE_MO_ROW = 132;
+constexpr int ATTN_DECODE_FUSED_LDS = 16 * 128 * 2 + 128 * 2 + 128 * 2 + ATTN_DECODE_NW * 16 * ATTN_DECODE_MO_ROW * 4 + 2 * ATTN_DECODE_NW * 16 * 4;  // bytes
 
 // ---- decode, fused: q/k RMSNorm + (M-)RoPE + KV append + split-KV attention + in-block merge --------------------
 // One launch replaces qknorm_rope_kernel + attn_decode_kernel + the combine: every block redoes the (tiny) norm/rope of
@@ -27,15 +32,21 @@ constexpr int ATTN_DECODE_FUSED_LDS = 16 * 128 * 2 + 128 * 2 + 128 * 2 + ATTN_DE
 // APPEND = false (draft-and-verify steps, kernels_batch.hip): the new K/V is already in its slot (kv_append_rows_kernel wrote the same
 // bits before this launch) and the append below is compiled out; everything else -- the new token taken from LDS, the old ones from the
 // pages, the split rule -- is the same code, so a row's output bits are those of the default instantiation.
-template <bool APPEND = true>
+// LINEAR = true (attn_decode_fused_kernel, the single-request decode step): the pages the launch touches are an arithmetic progression,
+// page i of this layer at a.lin_page0 + i * a.lin_step (both kernel arguments, in scalar registers at wave launch): every page address,
+// the append's included, is scalar arithmetic and the first K/V request has no load and no wait in front of it.  LINEAR = false: the
+// addresses come from the page table (a.kv.page_ptrs), one vector load whose return the first K/V request has to wait for -- and,
+// returns being in order, for every prologue input requested before it.
+template <bool APPEND = true, bool LINEAR = false>
 __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs& a, char* smem, const int kvhd, const int split,
                                                        const int nsplit) {
   constexpr int NW = ATTN_DECODE_NW, NT = NW * 64;
   bf16_t* qs = reinterpret_cast<bf16_t*>(smem);                 // [16][128]
   bf16_t* ksn = qs + 16 * 128;                                  // [128]
   bf16_t* vsn = ksn + 128;                                      // [128]
-  float* mo = reinterpret_cast<float*>(vsn + 128);              // per wave O^T [NW][d 128][q 16]
-  float* mm = mo + NW * 128 * 16;                               // [NW][16]
+  constexpr int MO_ROW = ATTN_DECODE_MO_ROW, MO_WAVE = 16 * MO_ROW;
+  float* mo = reinterpret_cast<float*>(vsn + 128);              // per wave O [NW][q 16][MO_ROW]
+  float* mm = mo + NW * MO_WAVE;                                // [NW][16]
   float* mlz = mm + NW * 16;                                    // [NW][16]
   const int tid = (int)threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -94,10 +105,12 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
   // stores, so the compiler will not use the scalar cache -- and its wait drains the K/V requests queued behind it.)
   uint64_t my_pages = 0;
   auto fetch_page_ptrs = [&](int first_it) {
+    if (LINEAR) return;
     const int pg = unit + (first_it + lane) * nunits;
     my_pages = pg < npages ? (uint64_t)(a.kv.page_ptrs[pg] + a.kv.layer_off) : 0;
   };
   auto page_base = [&](int i) {
+    if (LINEAR) return a.lin_page0 + (uint64_t)((int64_t)(unit + i * nunits) * a.lin_step);
     const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)my_pages, i & 63), hi = __builtin_amdgcn_readlane((uint32_t)(my_pages >> 32), i & 63);
     return ((uint64_t)hi << 32) | lo;
   };
@@ -140,7 +153,7 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
     // global address space spelled out: a flat store here would make every later wait in the kernel a vmcnt(0)
     typedef __attribute__((address_space(1))) bf16_t* gbf_t;
     const int pg = slot_new / KV_PAGE_TOKENS, t = slot_new % KV_PAGE_TOKENS;
-    const uint64_t base = (uint64_t)(a.kv.page_ptrs[pg] + a.kv.layer_off);
+    const uint64_t base = LINEAR ? a.lin_page0 + (uint64_t)((int64_t)pg * a.lin_step) : (uint64_t)(a.kv.page_ptrs[pg] + a.kv.layer_off);
     gbf_t kd = reinterpret_cast<gbf_t>(base) + (int64_t)kvhd * KV_PAGE_TOKENS * 128;
     gbf_t vd = reinterpret_cast<gbf_t>(base) + (int64_t)a.kvh * KV_PAGE_TOKENS * 128 + (int64_t)kvhd * 128 * KV_PAGE_TOKENS;
     for (int i = tid; i < 128; i += NT) {
@@ -203,11 +216,23 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
   }
   stamp(2);
   if (unit == 0) {  // the new token: score from LDS, one more online-softmax step
+    // the lane's 32 q and 32 k elements (64 bytes each) as four 16-byte LDS reads, the v elements below as 8-byte ones; the products
+    // are summed in element order, as before
     float dot = 0.f;
-    const bf16_t* qr = qs + min(c, g - 1) * 128 + G * 32;
-    const bf16_t* kr = ksn + G * 32;
+    const u32x4_t* qr = reinterpret_cast<const u32x4_t*>(qs + min(c, g - 1) * 128 + G * 32);
+    const u32x4_t* kr = reinterpret_cast<const u32x4_t*>(ksn + G * 32);
+    u32x4_t qv[4], kv4[4];
 #pragma unroll
-    for (int j = 0; j < 32; ++j) dot = fmaf(bf2f(qr[j]), bf2f(kr[j]), dot);
+    for (int j = 0; j < 4; ++j) {
+      qv[j] = qr[j];
+      kv4[j] = kr[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const uint32_t qw = qv[j >> 2][j & 3], kw = kv4[j >> 2][j & 3];
+      dot = fmaf(__uint_as_float(qw << 16), __uint_as_float(kw << 16), dot);
+      dot = fmaf(__uint_as_float(qw & 0xffff0000u), __uint_as_float(kw & 0xffff0000u), dot);
+    }
     dot = group_sum(dot);
     const float s = rbf(rbf(dot) * a.scale);
     const float m_new = fmaxf(m, s);
@@ -216,19 +241,21 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
     l = l * alpha + (G == 0 ? __expf(s - m_new) : 0.f);
     m = m_new;
 #pragma unroll
-    for (int ds = 0; ds < 8; ++ds)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o[ds][r] = fmaf(p, bf2f(vsn[ds * 16 + G * 4 + r]), o[ds][r] * alpha);
+    for (int ds = 0; ds < 8; ++ds) {
+      const uint2 vv = *reinterpret_cast<const uint2*>(vsn + ds * 16 + G * 4);
+      o[ds][0] = fmaf(p, __uint_as_float(vv.x << 16), o[ds][0] * alpha);
+      o[ds][1] = fmaf(p, __uint_as_float(vv.x & 0xffff0000u), o[ds][1] * alpha);
+      o[ds][2] = fmaf(p, __uint_as_float(vv.y << 16), o[ds][2] * alpha);
+      o[ds][3] = fmaf(p, __uint_as_float(vv.y & 0xffff0000u), o[ds][3] * alpha);
+    }
   }
   l = group_sum(l);
 
   // ---- merge the 4 waves through LDS, leave one partial per (split, head) ---------------------------------------------
   {
-    float* wo = mo + wave * (128 * 16);
+    float* wo = mo + wave * MO_WAVE + c * MO_ROW + G * 4;
 #pragma unroll
-    for (int ds = 0; ds < 8; ++ds)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) wo[(ds * 16 + G * 4 + r) * 16 + c] = o[ds][r];
+    for (int ds = 0; ds < 8; ++ds) *reinterpret_cast<f32x4_t*>(wo + ds * 16) = o[ds];
     if (G == 0) {
       mm[wave * 16 + c] = m;
       mlz[wave * 16 + c] = l;
@@ -249,8 +276,9 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
     for (int w = 0; w < NW; ++w) {
       const float mw = mm[w * 16 + q];
       const float wt = (mw == -INFINITY) ? 0.f : __expf(mw - M);
+      const f32x4_t ov = *reinterpret_cast<const f32x4_t*>(mo + w * MO_WAVE + q * MO_ROW + d0);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] = fmaf(wt, mo[w * (128 * 16) + (d0 + e) * 16 + q], acc[e]);
+      for (int e = 0; e < 4; ++e) acc[e] = fmaf(wt, ov[e], acc[e]);
       ls = fmaf(wt, mlz[w * 16 + q], ls);
     }
     const int head = kvhd * g + q;

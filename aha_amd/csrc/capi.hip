@@ -185,6 +185,7 @@ int aha_hip_last_logits(aha_model* m, float* logits_out) {
 
 size_t aha_hip_cache_len(const aha_model* m) { return m ? m->cache_len : 0; }
 int64_t aha_hip_debug_steps_executed(const aha_model* m) { return m ? m->steps_executed : 0; }
+int aha_hip_debug_attn_decode_form(const aha_model* m) { return m ? m->last_attn_form : -1; }
 int aha_hip_debug_graph_step(aha_model* m, int32_t replays, double* us_launches, double* us_graph) {
   if (!m) return AHA_ERR_INVALID;
   API_GUARD_BEGIN

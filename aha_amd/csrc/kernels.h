@@ -130,6 +130,11 @@ struct AttnDecodeFusedArgs {
   const float* rope;        // (128) f32: cos[64], sin[64] of the step's rope angles, already rounded to bf16 values
                             // (rope_step_kernel: once per step instead of once per layer and block)
   KvLayer kv;
+  // Linear form (lin_step != 0): every page the launch touches -- pages 0 .. kv_start_v / KV_PAGE_TOKENS -- is at lin_page0 + i * lin_step
+  // (lin_page0 includes the layer offset) and the kernel forms the addresses by arithmetic instead of reading kv.page_ptrs.  Set by
+  // the single-request decode step when the model's page map is such a progression (model.h lin_pages); 0: the table form.
+  uint64_t lin_page0 = 0;
+  int64_t lin_step = 0;
   int kv_start_v;           // cache slot of the token (host value: the step is enqueued with its lengths known)
   int kv_len_v;             // cache length after the append (= kv_start_v + 1)
   float* part_o;            // (nsplit, nh, 128) f32

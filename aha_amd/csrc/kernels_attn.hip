@@ -561,8 +561,8 @@ __global__ __launch_bounds__(128) void attn_decode_combine_kernel(AttnDecodeArgs
   ((bf16_t*)a.o)[head * 128 + d] = f2bf(acc / lsum);
 }
 
-// Kernel arguments of the fused decode attention.  What the prologue needs in front of its first requests -- the qkv row, the page
-// table, the rope table, the norm weights, the cache length, and the head counts with the split count (nh | kvh << 10 | nsplit << 20: gridDim itself is
+// Kernel arguments of the fused decode attention.  What the prologue needs in front of its first requests -- the qkv row, the pages
+// (linear form: address of page 0 of the layer and the byte step to the next page; table form: page table and layer offset), the rope table, the norm weights, the cache length, and the head counts with the split count (nh | kvh << 10 | nsplit << 20: gridDim itself is
 // an implicit kernel argument, i.e. another kernarg load) -- are plain leading parameters: 14 dwords, delivered in user SGPRs at wave launch on gfx950 (kernarg preload, build.py), so the launch's chain of dependent round trips
 // no longer starts with a scalar load from the kernarg segment the host has just written.  The rest is first used behind those requests
 // and travels in the trailing struct.  The trace pointer is tested in front of the first request (stamp(0)): the shipped kernel holds it
@@ -578,32 +578,37 @@ struct AttnDecodeFusedTail {
   float eps, scale;
 };
 
-template <bool TRACE>
-__device__ __forceinline__ void attn_decode_fused_flat(const void* qkv, const uint64_t* page_ptrs, uint64_t layer_off, const float* rope,
+// LINEAR: the two page arguments are (address of page 0 of this layer, byte step from a page to the next) instead of (page table, layer
+// offset): the same four leading dwords, so the 14 stay 14.
+template <bool TRACE, bool LINEAR>
+__device__ __forceinline__ void attn_decode_fused_flat(const void* qkv, uint64_t pages, uint64_t pages2, const float* rope,
                                                        const void* q_norm_w, const void* k_norm_w, int kv_len_v, int dims,
                                                        const AttnDecodeFusedTail& t, char* smem) {
   AttnDecodeFusedArgs a;
   a.qkv = qkv; a.q_norm_w = q_norm_w; a.k_norm_w = k_norm_w; a.rope = rope;
-  a.kv.page_ptrs = page_ptrs; a.kv.layer_off = layer_off; a.kv.kvh = t.kv_kvh; a.kv.d = t.kv_d;
+  a.kv.page_ptrs = LINEAR ? nullptr : reinterpret_cast<const uint64_t*>(pages); a.kv.layer_off = LINEAR ? 0 : pages2;
+  a.lin_page0 = LINEAR ? pages : 0; a.lin_step = LINEAR ? (int64_t)pages2 : 0;
+  a.kv.kvh = t.kv_kvh; a.kv.d = t.kv_d;
   a.kv_start_v = t.kv_start_v; a.kv_len_v = kv_len_v;
   a.part_o = t.part_o; a.part_ml = t.part_ml; a.o = t.o; a.head_ctr = t.head_ctr; a.ctr_target = t.ctr_target;
   a.trace = TRACE ? t.trace : nullptr;
   a.nh = dims & 1023; a.kvh = (dims >> 10) & 1023; a.nsplit = dims >> 20; a.eps = t.eps; a.scale = t.scale;
-  attn_decode_fused_body(a, smem, (int)blockIdx.x, (int)blockIdx.y, a.nsplit);
+  attn_decode_fused_body<true, LINEAR>(a, smem, (int)blockIdx.x, (int)blockIdx.y, a.nsplit);
 }
 
-__global__ __launch_bounds__(256, 2) void attn_decode_fused_kernel(const void* qkv, const uint64_t* page_ptrs, uint64_t layer_off,
-                                                                   const float* rope, const void* q_norm_w, const void* k_norm_w,
-                                                                   int kv_len_v, int dims, AttnDecodeFusedTail t) {
-  __shared__ __attribute__((aligned(16))) char smem[ATTN_DECODE_FUSED_LDS];
-  attn_decode_fused_flat<false>(qkv, page_ptrs, layer_off, rope, q_norm_w, k_norm_w, kv_len_v, dims, t, smem);
-}
-__global__ __launch_bounds__(256, 2) void attn_decode_fused_traced_kernel(const void* qkv, const uint64_t* page_ptrs, uint64_t layer_off,
-                                                                          const float* rope, const void* q_norm_w, const void* k_norm_w,
-                                                                          int kv_len_v, int dims, AttnDecodeFusedTail t) {
-  __shared__ __attribute__((aligned(16))) char smem[ATTN_DECODE_FUSED_LDS];
-  attn_decode_fused_flat<true>(qkv, page_ptrs, layer_off, rope, q_norm_w, k_norm_w, kv_len_v, dims, t, smem);
-}
+// attn_decode_fused_kernel is the linear form (the decode step of a single request whose pages are an arithmetic progression: what
+// bench.py and every plain generation run); the table form and the traced twins of both have family names of their own.
+#define AHA_ATTN_DECODE_FUSED_KERNEL(NAME, TRACE, LINEAR)                                                                                    \
+  __global__ __launch_bounds__(256, 2) void NAME(const void* qkv, uint64_t pages, uint64_t pages2, const float* rope, const void* q_norm_w, \
+                                                 const void* k_norm_w, int kv_len_v, int dims, AttnDecodeFusedTail t) {                      \
+    __shared__ __attribute__((aligned(16))) char smem[ATTN_DECODE_FUSED_LDS];                                                                \
+    attn_decode_fused_flat<TRACE, LINEAR>(qkv, pages, pages2, rope, q_norm_w, k_norm_w, kv_len_v, dims, t, smem);                            \
+  }
+AHA_ATTN_DECODE_FUSED_KERNEL(attn_decode_fused_kernel, false, true)
+AHA_ATTN_DECODE_FUSED_KERNEL(attn_decode_fused_table_kernel, false, false)
+AHA_ATTN_DECODE_FUSED_KERNEL(attn_decode_fused_traced_kernel, true, true)
+AHA_ATTN_DECODE_FUSED_KERNEL(attn_decode_fused_table_traced_kernel, true, false)
+#undef AHA_ATTN_DECODE_FUSED_KERNEL
 
 }  // namespace
 
@@ -615,12 +620,13 @@ void launch_attn_decode_fused(const AttnDecodeFusedArgs& a, hipStream_t st) {
     abort();
   }
   const int dims = a.nh | (a.kvh << 10) | (a.nsplit << 20);
-  if (a.trace == nullptr)
-    hipLaunchKernelGGL(attn_decode_fused_kernel, dim3(a.kvh, a.nsplit), dim3(256), 0, st, a.qkv, a.kv.page_ptrs, a.kv.layer_off, a.rope,
-                       a.q_norm_w, a.k_norm_w, a.kv_len_v, dims, t);
-  else
-    hipLaunchKernelGGL(attn_decode_fused_traced_kernel, dim3(a.kvh, a.nsplit), dim3(256), 0, st, a.qkv, a.kv.page_ptrs, a.kv.layer_off, a.rope,
-                       a.q_norm_w, a.k_norm_w, a.kv_len_v, dims, t);
+  const bool linear = a.lin_step != 0;
+  const uint64_t pages = linear ? a.lin_page0 : (uint64_t)(uintptr_t)a.kv.page_ptrs;
+  const uint64_t pages2 = linear ? (uint64_t)a.lin_step : a.kv.layer_off;
+  auto kernel = a.trace == nullptr ? (linear ? attn_decode_fused_kernel : attn_decode_fused_table_kernel)
+                                   : (linear ? attn_decode_fused_traced_kernel : attn_decode_fused_table_traced_kernel);
+  hipLaunchKernelGGL(kernel, dim3(a.kvh, a.nsplit), dim3(256), 0, st, a.qkv, pages, pages2, a.rope, a.q_norm_w, a.k_norm_w, a.kv_len_v,
+                     dims, t);
 }
 
 static int g_attn_smx_override = -1;

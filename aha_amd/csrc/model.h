@@ -91,6 +91,13 @@ struct aha_model {
   uint64_t page_bytes = 0;      // bytes of one page of one layer (K block + V block)
   uint64_t layer_stride = 0;    // bytes between layers inside a slab
   size_t n_pages = 0;           // pages currently mapped
+  // Pages [0, lin_pages) are the arithmetic progression lin_p0 + i * lin_step (model_ensure_pages keeps this up to date, O(1) per page):
+  // one slab handed out in order, which is every cache up to a slab's tokens.  The decode step's attention then takes (lin_p0 + layer
+  // offset, lin_step) as kernel arguments and never reads the page table (kernels.h AttnDecodeFusedArgs::lin_step).
+  size_t lin_pages = 0;
+  uint64_t lin_p0 = 0;
+  int64_t lin_step = 0;
+  int last_attn_form = -1;      // the last decode step's attention launches: 1 linear form, 0 table form, -1 none yet (debug getter)
   size_t cache_len = 0;         // tokens in the cache (== reference kv_cache.dim(2))
   bool scramble_pages = false;
   std::vector<uint64_t> free_pages;

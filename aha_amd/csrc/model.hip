@@ -338,6 +338,14 @@ int model_ensure_pages(aha_model* m, size_t tokens) {
     const uint64_t p = m->free_pages.back();
     m->free_pages.pop_back();
     if (m->h_page_ptrs.size() <= m->n_pages) m->h_page_ptrs.resize(m->n_pages + 1);
+    if (m->n_pages == 0) {  // a lone page is a progression of any step
+      m->lin_p0 = p;
+      m->lin_step = (int64_t)m->page_bytes;
+      m->lin_pages = 1;
+    } else if (m->lin_pages == m->n_pages) {  // unbroken so far: the second page sets the step, every later one has to keep it
+      if (m->n_pages == 1) m->lin_step = (int64_t)(p - m->lin_p0);
+      if (m->lin_step != 0 && p == m->lin_p0 + (uint64_t)((int64_t)m->n_pages * m->lin_step)) m->lin_pages = m->n_pages + 1;
+    }
     m->h_page_ptrs[m->n_pages++] = p;
   }
   AHA_HIP_CHECK(hipMemcpyAsync(m->d_page_ptrs + first_new, m->h_page_ptrs.data() + first_new,
@@ -530,6 +538,7 @@ int model_clear_cache(aha_model* m) {
   // QKNormAttention::clear_kv_cache (modules.rs:581-583): the cache becomes empty; pages go back to the pool
   for (size_t i = m->n_pages; i > 0; --i) m->free_pages.push_back(m->h_page_ptrs[i - 1]);
   m->n_pages = 0;
+  m->lin_pages = 0;
   m->cache_len = 0;
   m->rope_delta = 0;
   m->rope_delta_valid = false;
@@ -1438,6 +1447,13 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = 
       AttnDecodeFusedArgs a{};
       a.qkv = m->d_qkv; a.q_norm_w = L.q_norm; a.k_norm_w = L.k_norm; a.rope = m->d_rope;
       a.kv = model_kv_layer(m, li); a.kv_start_v = (int)kv_len_after - 1; a.kv_len_v = (int)kv_len_after;
+      // pages 0 .. npages - 1, the append slot's included, are lin_p0 + i * lin_step (the scramble knob is there to exercise the page
+      // table: it keeps the table form even where one or two shuffled pages still are a progression)
+      if ((size_t)npages <= m->lin_pages && !m->scramble_pages) {
+        a.lin_page0 = m->lin_p0 + a.kv.layer_off;
+        a.lin_step = m->lin_step;
+      }
+      m->last_attn_form = a.lin_step != 0 ? 1 : 0;
       a.part_o = m->d_part_o; a.part_ml = m->d_part_ml; a.nh = nh; a.kvh = kvh; a.nsplit = nsplit; a.eps = c.rms_norm_eps;
       a.scale = m->attn_scale; a.o = m->d_attn; a.head_ctr = m->d_bar + DECODE_HEAD_CTR_WORD;
       if (nsplit > 1) m->head_ctr_base += (unsigned)nsplit;  // a single split never touches the counter

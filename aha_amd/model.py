@@ -495,6 +495,10 @@ class HipInferenceModel:
         check(lib().aha_hip_get_profile(self.handle, kernel_class.encode(), C.byref(ms), C.byref(n), C.byref(b), C.byref(f)))
         return {"ms": ms.value, "launches": n.value, "bytes": b.value, "flops": f.value}
 
+    def debug_attn_decode_form(self) -> int:
+        """Form of the fused decode attention in the last decode step: 1 linear (arithmetic page addresses), 0 page table, -1 none yet."""
+        return int(lib().aha_hip_debug_attn_decode_form(self.handle))
+
     def debug_scramble_pages(self, on: bool = True):
         check(lib().aha_hip_debug_scramble_pages(self.handle, int(on)))
 

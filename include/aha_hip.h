@@ -556,6 +556,9 @@ int aha_hip_get_profile(aha_model* m, const char* kernel_class, double* total_ms
                         double* flops);
 /* Debug knob for the paged-KV property tests: 1 => hand out physical pages in a scrambled order. */
 int aha_hip_debug_scramble_pages(aha_model* m, int enable);
+/* Which form of the fused decode attention the last single-request decode step launched: 1 = linear (page addresses formed by
+ * arithmetic from two kernel arguments: the cache's pages are an arithmetic progression), 0 = page table, -1 = no step yet. */
+int aha_hip_debug_attn_decode_form(const aha_model* m);
 /* Copies the last hidden state before lm_head (hidden_size floats) / the image embeddings of the last
  * forward_initial (rows x out_hidden floats) to the host, for parity tests of intermediate tensors. */
 int aha_hip_debug_last_hidden(aha_model* m, float* out, size_t n);
