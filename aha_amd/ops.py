@@ -120,7 +120,9 @@ def qknorm_rope(qkv: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: torch.Tenso
 
 def attn_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, nh: int, kvh: int, d: int,
                 scale: Optional[float] = None) -> torch.Tensor:
-    """q (nh*d); k, v (L, kvh*d) token-major -> o (nh*d)."""
+    """q (nh*d); k, v (L, kvh*d) token-major -> o (nh*d).  The three-launch fallback (attn_decode_kernel + combine), which the model runs
+    only with AHA_DECODE_FUSED=0; the default decode kernel is the fused one behind attn_decode_batch / debug_attn_decode_fused
+    (tests/test_attn_decode_fused_gpu.py)."""
     _chk(q, k, v)
     L = k.shape[0]
     scale = bf16_scale(d) if scale is None else scale

@@ -2,6 +2,10 @@
 
 Tolerances (bf16 model dtype): a HIP op may differ from the oracle's op-granular bf16 result by at most a few bf16
 ulps of the output (f32 accumulation order, f32 vs bf16-rounded softmax probabilities); each test states its bound.
+
+ops.attn_decode (test_attn_decode, test_attn_decode_peaky) is the three-launch fallback, token-major K/V, which the model runs only with
+AHA_DECODE_FUSED=0.  The default decode kernel, the fused one over fragment-major pages, is held to an f64 reference in
+tests/test_attn_decode_fused_gpu.py.
 """
 import math
 
