@@ -47,6 +47,15 @@ class EngineStats(C.Structure):
     _fields_ = [("waiting", C.c_size_t), ("running", C.c_size_t), ("free_pages", C.c_size_t), ("total_pages", C.c_size_t)]
 
 
+AHA_MAX_TOP_LOGPROBS = 20
+
+
+class TokenLogprobs(C.Structure):
+    """aha_token_logprobs (include/aha_hip.h); the Rust shim's AhaTokenLogprobs has the same fields in the same order."""
+    _fields_ = [("logprob", C.c_float), ("n_top", C.c_int32), ("top_ids", C.c_uint32 * AHA_MAX_TOP_LOGPROBS),
+                ("top_logprobs", C.c_float * AHA_MAX_TOP_LOGPROBS)]
+
+
 class SpecConfig(C.Structure):
     """aha_spec_config (include/aha_hip.h); the Rust shim's AhaSpecConfig has the same fields in the same order."""
     _fields_ = [("max_draft", C.c_int32), ("ngram_min", C.c_int32), ("ngram_max", C.c_int32)]
@@ -191,6 +200,12 @@ SIGNATURES = {
     "aha_hip_engine_step": (C.c_int, [_P, C.POINTER(EngineEvent), C.c_size_t, C.POINTER(C.c_size_t), _P]),
     "aha_hip_engine_stats": (C.c_int, [_P, C.POINTER(EngineStats)]),
     "aha_hip_engine_debug_ctr_base": (C.c_int, [_P, C.c_uint32]),
+    "aha_hip_generate_batch_logprobs": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.POINTER(SamplingParams), _P, C.c_size_t, C.c_size_t, _P, _P, _P,
+                                                  C.POINTER(TokenLogprobs)]),
+    "aha_hip_engine_submit_logprobs": (C.c_int, [_P, _P, C.c_size_t, _P, C.POINTER(SamplingParams), C.c_size_t, C.c_int32,
+                                                 C.POINTER(C.c_uint64)]),
+    "aha_hip_engine_step_logprobs": (C.c_int, [_P, C.POINTER(EngineEvent), C.c_size_t, C.POINTER(C.c_size_t), _P, C.POINTER(TokenLogprobs)]),
+    "aha_hip_logprob_rows": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "aha_hip_sample_rows": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "aha_hip_sampler_create": (C.c_int, [C.POINTER(SamplingParams), _P]),
     "aha_hip_sampler_destroy": (None, [_P]),

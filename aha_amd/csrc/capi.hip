@@ -665,6 +665,59 @@ int aha_hip_sample_rows(const float* logits, int64_t ld, int32_t R, int32_t V, c
   API_GUARD_END
 }
 
+int aha_hip_logprob_rows(const float* logits, int64_t ld, int32_t R, int32_t V, const uint32_t* tokens, const int32_t* n_top,
+                         aha_token_logprobs* out, void* stream) {
+  API_GUARD_BEGIN
+  if (!logits || R < 1 || V < 1 || ld < V || !tokens || !n_top || !out) {
+    set_error("logprob_rows: bad arguments (R >= 1, ld >= V >= 1, logits / tokens / n_top / out)");
+    return AHA_ERR_INVALID;
+  }
+  for (int r = 0; r < R; ++r)
+    if (n_top[r] < 0 || n_top[r] > AHA_MAX_TOP_LOGPROBS) {
+      set_error("logprob_rows: row " + std::to_string(r) + " needs 0 <= n_top <= " + std::to_string(AHA_MAX_TOP_LOGPROBS));
+      return AHA_ERR_INVALID;
+    }
+  if (!logprob_shape_ok(V)) {
+    set_error("logprob_rows: vocabulary too large for the logprob pass");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<int32_t> tab((size_t)R * LOGPROB_ROW_WORDS, 0);
+  for (int r = 0; r < R; ++r) {
+    int32_t* t = tab.data() + (size_t)r * LOGPROB_ROW_WORDS;
+    t[LOGPROB_ROW_LROW] = r;
+    t[LOGPROB_ROW_NTOP] = n_top[r];
+    t[LOGPROB_ROW_TOK] = r;
+    t[LOGPROB_ROW_CSLOT] = -1;
+  }
+  const int nw = logprob_stage1_waves(V);
+  const size_t cand = (size_t)R * nw * LOGPROB_MAX_TOP;
+  int32_t* d_tab = nullptr;
+  uint32_t* d_cidx = nullptr;
+  float *d_cval = nullptr, *d_part = nullptr, *d_out = nullptr;
+  AHA_HIP_CHECK(hipMalloc((void**)&d_tab, tab.size() * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&d_cval, cand * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&d_cidx, cand * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&d_part, 2 * (size_t)R * nw * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&d_out, (size_t)R * LOGPROB_OUT_WORDS * 4));
+  AHA_HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+  for (int stage = 0; stage < 2; ++stage)
+    launch_logprob_rows(logits, ld, V, R, d_tab, tokens, d_cval, d_cidx, d_part, d_part + (size_t)R * nw, nullptr, d_out, stage, st);
+  hipError_t err = hipGetLastError();
+  // the aha_token_logprobs at the head of every output row
+  if (err == hipSuccess)
+    err = hipMemcpy2DAsync(out, sizeof(aha_token_logprobs), d_out, LOGPROB_OUT_WORDS * 4, sizeof(aha_token_logprobs), R, hipMemcpyDeviceToDevice, st);
+  hipStreamSynchronize(st);
+  hipFree(d_tab);
+  hipFree(d_cval);
+  hipFree(d_cidx);
+  hipFree(d_part);
+  hipFree(d_out);
+  AHA_HIP_CHECK(err);
+  return AHA_OK;
+  API_GUARD_END
+}
+
 static bool attn_batch_geometry_ok(int32_t nh, int32_t kvh) { return nh > 0 && kvh > 0 && nh % kvh == 0 && nh / kvh <= 16 && kvh <= 64; }
 
 int aha_hip_attn_decode_batch(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
@@ -985,6 +1038,37 @@ int aha_hip_generate_batch_mm(aha_model* m, const uint32_t* input_ids, const siz
   return model_generate_batch_mm(m, input_ids, seq_lens, n_seqs, mm, params, max_new, max_tokens_per_pass, tokens_out, n_out, step_logits_out);
   API_GUARD_END
 }
+int aha_hip_generate_batch_logprobs(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs,
+                                    const aha_mm_input* const* mm, const aha_sampling_params* params, const int32_t* top_logprobs,
+                                    size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out,
+                                    float* step_logits_out, aha_token_logprobs* logprobs_out) {
+  API_GUARD_BEGIN
+  for (size_t j = 0; params && j < n_seqs && j < ((size_t)1 << 20); ++j) {   // params == NULL: every sequence greedy
+    std::string why;
+    if (sampling_params_check(params[j], &why)) {
+      set_error("generate_batch_logprobs: params of sequence " + std::to_string(j) + ": " + why);
+      return AHA_ERR_INVALID;
+    }
+  }
+  if (!top_logprobs || !logprobs_out) {
+    set_error("generate_batch_logprobs: null top_logprobs / logprobs_out");
+    return AHA_ERR_INVALID;
+  }
+  for (size_t j = 0; j < n_seqs && j < ((size_t)1 << 20); ++j)
+    if (top_logprobs[j] < -1 || top_logprobs[j] > AHA_MAX_TOP_LOGPROBS) {
+      set_error("generate_batch_logprobs: top_logprobs of sequence " + std::to_string(j) + " must be -1 (none) or 0 .. " +
+                std::to_string(AHA_MAX_TOP_LOGPROBS) + ", got " + std::to_string(top_logprobs[j]));
+      return AHA_ERR_INVALID;
+    }
+  if (!m) {
+    set_error("null model");
+    return AHA_ERR_INVALID;
+  }
+  if (int rc = engine_owns_cache(m, "generate_batch_logprobs")) return rc;
+  return model_generate_batch_logprobs(m, input_ids, seq_lens, n_seqs, mm, params, top_logprobs, max_new, max_tokens_per_pass, tokens_out, n_out,
+                                       step_logits_out, logprobs_out);
+  API_GUARD_END
+}
 int aha_hip_generate_batch_spec(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
                                 size_t max_tokens_per_pass, const aha_spec_config* spec, const uint32_t* predictions,
                                 const size_t* prediction_lens, uint32_t* tokens_out, size_t* n_out, float* logits_out, size_t* n_proposed,
@@ -1049,6 +1133,27 @@ int aha_hip_engine_submit(aha_engine* e, const uint32_t* input_ids, size_t n_ids
   return engine_submit(e, input_ids, n_ids, mm, params, max_new, req_id);
   API_GUARD_END
 }
+int aha_hip_engine_submit_logprobs(aha_engine* e, const uint32_t* input_ids, size_t n_ids, const aha_mm_input* mm,
+                                   const aha_sampling_params* params, size_t max_new, int32_t top_logprobs, uint64_t* req_id) {
+  API_GUARD_BEGIN
+  if (params) {
+    std::string why;
+    if (sampling_params_check(*params, &why)) {
+      set_error("engine_submit_logprobs: params: " + why);
+      return AHA_ERR_INVALID;
+    }
+  }
+  if (top_logprobs < 0 || top_logprobs > AHA_MAX_TOP_LOGPROBS) {
+    set_error("engine_submit_logprobs: top_logprobs must be 0 .. " + std::to_string(AHA_MAX_TOP_LOGPROBS) + ", got " + std::to_string(top_logprobs));
+    return AHA_ERR_INVALID;
+  }
+  if (!e) {
+    set_error("engine_submit_logprobs: null engine");
+    return AHA_ERR_INVALID;
+  }
+  return engine_submit(e, input_ids, n_ids, mm, params, max_new, req_id, top_logprobs);
+  API_GUARD_END
+}
 int aha_hip_engine_cancel(aha_engine* e, uint64_t req_id) {
   API_GUARD_BEGIN
   if (!e) {
@@ -1065,6 +1170,16 @@ int aha_hip_engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t*
     return AHA_ERR_INVALID;
   }
   return engine_step(e, ev, cap, n_ev, logits_out);
+  API_GUARD_END
+}
+int aha_hip_engine_step_logprobs(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, float* logits_out,
+                                 aha_token_logprobs* logprobs_out) {
+  API_GUARD_BEGIN
+  if (!e) {
+    set_error("engine_step: null engine");
+    return AHA_ERR_INVALID;
+  }
+  return engine_step(e, ev, cap, n_ev, logits_out, logprobs_out);
   API_GUARD_END
 }
 int aha_hip_engine_stats(const aha_engine* e, aha_engine_stats* out) {

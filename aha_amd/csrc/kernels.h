@@ -67,6 +67,23 @@ constexpr int SAMPLE_OUT_WORDS = 64 + 2 + 64;
 void launch_topk_rows(const float* logits, int64_t ld, int V, int rows, const int32_t* tab, const uint32_t* ctx, float* cand_val,
                       unsigned* cand_idx, float* part_m, float* part_s, float* out, int stage, hipStream_t st);
 
+// Per-token log-probabilities (kernels_logprob.hip) for `rows` rows of f32 logits (pitch ld), one launch per stage (stage 0: stage 1,
+// 1: stage 2; the caller scopes each for the profile).  Row s of `tab` (device, LOGPROB_ROW_WORDS int32 per row): its logits row, its n_top
+// (0 .. LOGPROB_MAX_TOP), the entry of `tokens` (device) that holds its token, and the row of `sample_out` (launch_topk_rows' out; -1:
+// none) whose 64 candidate ids it gathers raw logits for.  Row s: cand_* [s * nw * LOGPROB_MAX_TOP, ...) with nw = logprob_stage1_waves(V),
+// part_* [s * nw, ...), out [s * LOGPROB_OUT_WORDS, ...) = {an aha_token_logprobs (lp(token), n_top, ids[20], lps[20]), M, log S,
+// raw[64]}.  Temperature 1, no penalty; a row's output depends on its own row only; the logits are only read.
+constexpr int LOGPROB_MAX_TOP = 20;
+constexpr int LOGPROB_ROW_WORDS = 4;
+constexpr int LOGPROB_ROW_LROW = 0, LOGPROB_ROW_NTOP = 1, LOGPROB_ROW_TOK = 2, LOGPROB_ROW_CSLOT = 3;
+constexpr int LOGPROB_OUT_LP = 0, LOGPROB_OUT_NTOP = 1, LOGPROB_OUT_IDS = 2, LOGPROB_OUT_LPS = 2 + LOGPROB_MAX_TOP;
+constexpr int LOGPROB_OUT_M = 2 + 2 * LOGPROB_MAX_TOP, LOGPROB_OUT_LOGS = LOGPROB_OUT_M + 1, LOGPROB_OUT_RAW = LOGPROB_OUT_M + 2;
+constexpr int LOGPROB_OUT_WORDS = LOGPROB_OUT_RAW + 64;
+int logprob_stage1_waves(int V);
+bool logprob_shape_ok(int V);
+void launch_logprob_rows(const float* logits, int64_t ld, int V, int rows, const int32_t* tab, const uint32_t* tokens, float* cand_val,
+                         unsigned* cand_idx, float* part_m, float* part_s, const float* sample_out, float* out, int stage, hipStream_t st);
+
 void launch_embed_gather(const void* table, const uint32_t* ids, void* out, int S, int H, hipStream_t st);
 void launch_rmsnorm_rows(const void* x, const void* w, void* y, int64_t rows, int dim, int64_t ldx, int64_t ldy,
                          float eps, hipStream_t st);

@@ -2365,7 +2365,19 @@ struct GenCall {
   uint32_t* const* seq_tokens = nullptr;
   float* const* row_logits = nullptr;
   const uint64_t* dec_pages = nullptr;
+  // per-token logprobs (aha_hip_generate_batch_logprobs, aha_hip_engine_step_logprobs): lp_top[j] = sequence j's top_logprobs (-1: none);
+  // row r's entry goes to row_logprobs[r] (the engine; null: not reported) or to logprobs_out[j * max_new + n_out[j]].  The pass's
+  // buffers (gen_logprob_alloc; lp_tab null: none) and finish_step's per-row scratch.
+  const int32_t* lp_top = nullptr;
+  aha_token_logprobs* logprobs_out = nullptr;
+  aha_token_logprobs* const* row_logprobs = nullptr;
+  int32_t *lp_tab = nullptr, *h_lp_tab = nullptr;
+  float *lp_cval = nullptr, *lp_part = nullptr, *lp_out = nullptr, *h_lp_out = nullptr;
+  unsigned* lp_cidx = nullptr;
+  std::vector<int> lp_slot, lp_fb;
 };
+static_assert(sizeof(aha_token_logprobs) == 168 && sizeof(aha_token_logprobs) == (size_t)LOGPROB_OUT_M * 4 && AHA_MAX_TOP_LOGPROBS == LOGPROB_MAX_TOP,
+              "aha_token_logprobs is the head of a logprob pass output row");
 
 static inline uint32_t* gen_seq_tokens(const GenCall& gc, int j) {
   return gc.seq_tokens ? gc.seq_tokens[j] : gc.tokens_out + (size_t)j * gc.max_new;
@@ -2492,6 +2504,22 @@ static int gen_call_alloc(aha_model* m, DevBufs& bufs, GenCall& gc, size_t max_p
   return AHA_OK;
 }
 
+// The logprob pass's buffers for gc.n rows
+static int gen_logprob_alloc(DevBufs& bufs, GenCall& gc) {
+  if (!logprob_shape_ok(gc.V)) {
+    set_error("generate_batch_logprobs: vocabulary too large for the logprob pass");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  const size_t n = (size_t)gc.n, nw = (size_t)logprob_stage1_waves(gc.V);
+  int rc;
+  if ((rc = bufs.alloc(&gc.lp_tab, n * LOGPROB_ROW_WORDS)) || (rc = bufs.alloc_host(&gc.h_lp_tab, n * LOGPROB_ROW_WORDS)) ||
+      (rc = bufs.alloc(&gc.lp_cval, n * nw * LOGPROB_MAX_TOP)) || (rc = bufs.alloc(&gc.lp_cidx, n * nw * LOGPROB_MAX_TOP)) ||
+      (rc = bufs.alloc(&gc.lp_part, 2 * n * nw)) || (rc = bufs.alloc(&gc.lp_out, n * LOGPROB_OUT_WORDS)) ||
+      (rc = bufs.alloc_host(&gc.h_lp_out, n * LOGPROB_OUT_WORDS)))
+    return rc;
+  return AHA_OK;
+}
+
 // Sampled generation: one sampler per sequence and the candidate step's buffers (no samplers: greedy)
 struct GenChoice {
   std::vector<HostSampler> samplers;
@@ -2542,6 +2570,9 @@ static int gen_choice_init(DevBufs& bufs, const GenCall& gc, const aha_sampling_
 // candidate step over every row that samples (its penalty context uploaded with it) and the candidates' copy; after it the host picks,
 // a second sync only for rows whose candidates cannot decide (their logits rows come down), and the picked tokens go back up into
 // tok_dev for the next step's embedding gather.  gc.step_logits_out (greedy or sampled): every step's logits.
+// Logprobs (gc.lp_top): one two-launch pass over the rows that ask for them, behind the candidate step and in front of the same sync; a
+// greedy row's entry is complete on the device (its token is in tok_dev), a sampled row's lp is finished here from the raw logit of the
+// token the host picked -- among its candidates' raw logits, which came down with the entry, or in its full row when it fell back.
 static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::vector<int>& seqs, uint32_t* tok_dev) {
   hipStream_t st = m->stream;
   const int R = (int)seqs.size(), V = gc.V;
@@ -2601,6 +2632,70 @@ static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::
       AHA_HIP_CHECK(hipMemcpyAsync(ch.h_sout, ch.d_sout, (size_t)ns * SAMPLE_OUT_WORDS * 4, hipMemcpyDeviceToHost, st));
     }
   }
+  auto lp_dst = [&](int r) -> aha_token_logprobs* {
+    if (gc.row_logprobs) return gc.row_logprobs[r];
+    return gc.logprobs_out ? gc.logprobs_out + (size_t)seqs[r] * max_new + gc.n_out[seqs[r]] : nullptr;
+  };
+  int nl = 0;
+  if (gc.lp_top && gc.lp_tab) {
+    gc.lp_slot.assign(R, -1);
+    gc.lp_fb.assign(R, -1);
+    for (int r = 0; r < R; ++r) {
+      if (!lp_dst(r) || gc.lp_top[seqs[r]] < 0) continue;
+      int32_t* t = gc.h_lp_tab + (size_t)nl * LOGPROB_ROW_WORDS;
+      t[LOGPROB_ROW_LROW] = r;
+      t[LOGPROB_ROW_NTOP] = gc.lp_top[seqs[r]];
+      t[LOGPROB_ROW_TOK] = r;
+      t[LOGPROB_ROW_CSLOT] = sampled ? ch.slot[r] : -1;
+      gc.lp_slot[r] = nl++;
+    }
+    if (nl) {
+      const int nw = logprob_stage1_waves(V);
+      AHA_HIP_CHECK(hipMemcpyAsync(gc.lp_tab, gc.h_lp_tab, (size_t)nl * LOGPROB_ROW_WORDS * 4, hipMemcpyHostToDevice, st));
+      const char* names[2] = {"logprob_rows_stage1", "logprob_rows_stage2"};
+      for (int stage = 0; stage < 2; ++stage) {
+        ProfScope ps(m, names[stage], stage == 0 ? (double)nl * V * 4 : 0, 0);
+        launch_logprob_rows(gc.logits, V, V, nl, gc.lp_tab, tok_dev, gc.lp_cval, gc.lp_cidx, gc.lp_part, gc.lp_part + (size_t)gc.n * nw,
+                            sampled ? ch.d_sout : nullptr, gc.lp_out, stage, st);
+      }
+      AHA_HIP_CHECK(hipGetLastError());
+      AHA_HIP_CHECK(hipMemcpyAsync(gc.h_lp_out, gc.lp_out, (size_t)nl * LOGPROB_OUT_WORDS * 4, hipMemcpyDeviceToHost, st));
+    }
+  }
+  // after the step's sync(s) and picks: every row's entry to the caller
+  auto lp_finish = [&]() -> int {
+    if (!gc.lp_top) return AHA_OK;
+    for (int r = 0; r < R; ++r) {
+      aha_token_logprobs* d = lp_dst(r);
+      if (!d) continue;
+      if (!nl || gc.lp_slot[r] < 0) {
+        d->n_top = -1;
+        continue;
+      }
+      const float* o = gc.h_lp_out + (size_t)gc.lp_slot[r] * LOGPROB_OUT_WORDS;
+      memcpy(d, o, sizeof(aha_token_logprobs));
+      if (!sampled || ch.mode[r] == GREEDY) continue;
+      const uint32_t tok = h_tok[r];
+      float x = 0.f;
+      bool found = false;
+      if (gc.lp_fb[r] >= 0) {
+        x = ch.h_fb[(size_t)gc.lp_fb[r] * V + tok];
+        found = true;
+      } else {
+        const float* so = ch.h_sout + (size_t)ch.slot[r] * SAMPLE_OUT_WORDS;
+        const uint32_t* ids = reinterpret_cast<const uint32_t*>(so + 66);
+        const int k = ch.h_stab[(size_t)ch.slot[r] * SAMPLE_ROW_WORDS + SAMPLE_ROW_K];
+        for (int i = 0; i < k && !found; ++i)
+          if (ids[i] == tok) x = o[LOGPROB_OUT_RAW + i], found = true;
+      }
+      if (!found) {
+        set_error("generate_batch_logprobs: the sampled token is not among the row's candidates");
+        return AHA_ERR_STATE;
+      }
+      d->logprob = (x - o[LOGPROB_OUT_M]) - o[LOGPROB_OUT_LOGS];
+    }
+    return AHA_OK;
+  };
   if (gc.row_logits) {
     for (int r = 0; r < R; ++r)
       if (gc.row_logits[r]) AHA_HIP_CHECK(hipMemcpyAsync(gc.row_logits[r], gc.logits + (size_t)r * V, (size_t)V * 4, hipMemcpyDeviceToHost, st));
@@ -2611,7 +2706,7 @@ static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::
   }
   AHA_HIP_CHECK(hipMemcpyAsync(h_tok, tok_dev, (size_t)R * 4, hipMemcpyDeviceToHost, st));
   AHA_HIP_CHECK(hipStreamSynchronize(st));
-  if (!sampled) return AHA_OK;
+  if (!sampled) return lp_finish();
   ch.fb_rows.clear();
   for (int r = 0; r < R; ++r) {
     if (ch.mode[r] == GREEDY) continue;
@@ -2632,13 +2727,14 @@ static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::
     AHA_HIP_CHECK(hipStreamSynchronize(st));
     for (size_t f = 0; f < ch.fb_rows.size(); ++f) {
       const int r = ch.fb_rows[f], j = seqs[r];
+      if (nl) gc.lp_fb[r] = (int)f;
       const int prc = sampler_pick(ch.samplers[j], nullptr, nullptr, 0, 0.f, 0.f, ch.h_fb + f * V, (size_t)V, gen_seq_tokens(gc, j),
                                    gc.n_out[j], &h_tok[r]);
       if (prc != AHA_OK) return prc < 0 ? prc : AHA_ERR_STATE;
     }
   }
   AHA_HIP_CHECK(hipMemcpyAsync(tok_dev, h_tok, (size_t)R * 4, hipMemcpyHostToDevice, st));
-  return AHA_OK;
+  return lp_finish();
 }
 
 // One decode step's device work over the R rows of the uploaded row table gc.rowtab: the tokens tok_in embedded (with their rope rows),
@@ -2839,7 +2935,7 @@ static int spec_decode_loop(aha_model* m, GenCall& gc, const SpecRun& sp, const 
 static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
                                size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* logits_out,
                                const aha_sampling_params* params, float* step_logits_out, const aha_mm_input* const* mm = nullptr,
-                               const SpecRun* sp = nullptr) {
+                               const SpecRun* sp = nullptr, const int32_t* top_logprobs = nullptr, aha_token_logprobs* logprobs_out = nullptr) {
   const aha_model_desc& c = m->desc;
   if (!ids || !seq_lens || !tokens_out || !n_out) {
     set_error("generate_batch: null input_ids / seq_lens / tokens_out / n_out");
@@ -2916,6 +3012,10 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
     max_pass_pages += (seq_lens[j] + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
   }
   if ((rc = gen_call_alloc(m, bufs, gc, max_pass_pages)) || (params && (rc = gen_choice_init(bufs, gc, params, ch)))) return rc;
+  if (top_logprobs) {
+    gc.lp_top = top_logprobs, gc.logprobs_out = logprobs_out;
+    if (std::any_of(top_logprobs, top_logprobs + n, [](int32_t t) { return t >= 0; }) && (rc = gen_logprob_alloc(bufs, gc))) return rc;
+  }
   if (spec_on && ((rc = bufs.alloc(&gc.spec_out, (size_t)n * SPEC_OUT_WORDS)) || (rc = bufs.alloc_host(&gc.h_spec_out, (size_t)n * SPEC_OUT_WORDS))))
     return rc;
 
@@ -3012,6 +3112,13 @@ int model_generate_batch_mm(aha_model* m, const uint32_t* ids, const size_t* seq
   return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, nullptr, params, step_logits_out, mm);
 }
 
+int model_generate_batch_logprobs(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
+                                  const aha_sampling_params* params, const int32_t* top_logprobs, size_t max_new, size_t max_tokens_per_pass,
+                                  uint32_t* tokens_out, size_t* n_out, float* step_logits_out, aha_token_logprobs* logprobs_out) {
+  return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, nullptr, params, step_logits_out, mm,
+                             nullptr, top_logprobs, logprobs_out);
+}
+
 int model_generate_batch_spec(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new, size_t max_tokens_per_pass,
                               const aha_spec_config* spec, const uint32_t* predictions, const size_t* prediction_lens, uint32_t* tokens_out,
                               size_t* n_out, float* logits_out, size_t* n_proposed, size_t* n_accepted, aha_spec_stats* stats) {
@@ -3043,6 +3150,7 @@ struct EngReq {
   int64_t rope_delta = 0;
   aha_sampling_params params{};
   size_t max_new = 0, npages = 0, done = 0;   // done: prompt tokens prefilled
+  int32_t top_logprobs = -1;          // aha_hip_engine_submit_logprobs (-1: no logprobs)
   int slot = -1;
   bool started = false, cancel = false;
   std::vector<uint32_t> toks;         // capacity max_new: gen_finish_step reads the penalty context through a pointer to it
@@ -3068,6 +3176,8 @@ struct aha_engine {
   std::vector<size_t> n_out;          // per slot: tokens so far
   std::vector<uint32_t*> seq_tok;     // per slot: EngReq::toks
   std::vector<float*> row_logits;
+  std::vector<int32_t> lp_top;        // per slot: its request's top_logprobs (-1: none)
+  std::vector<aha_token_logprobs*> row_lp;
   aha::DevBufs bufs{nullptr, {}, {}};
   aha::GenCall gc;
   aha::GenChoice ch;
@@ -3146,15 +3256,18 @@ int engine_create(aha_model* m, const aha_engine_config* cfg, aha_engine** out) 
   e->n_out.assign(n, 0);
   e->seq_tok.assign(n, nullptr);
   e->row_logits.assign(n, nullptr);
+  e->lp_top.assign(n, -1);
+  e->row_lp.assign(n, nullptr);
   for (size_t p = e->kv_pages; p > 0; --p) e->free_pages.push_back(m->h_page_ptrs[p - 1]);   // page 0 is taken first
   GenCall& gc = e->gc;
   gc.n = n, gc.V = c.vocab_size, gc.H = c.hidden_size, gc.max_new = 0;
   gc.max_nsplit = attn_decode_nsplit((int)std::min<size_t>(e->kv_pages * KV_PAGE_TOKENS, (size_t)1 << 24), c.num_attention_heads / kvh, m->max_nsplit);
   gc.n_out = e->n_out.data(), gc.seq_tokens = e->seq_tok.data(), gc.row_logits = e->row_logits.data();
+  gc.lp_top = e->lp_top.data(), gc.row_logprobs = e->row_lp.data();
   e->ctx_cap = (size_t)n * 64;
   if ((rc = gen_call_alloc(m, e->bufs, gc, 2 * e->kv_pages)) || (rc = gen_choice_alloc(e->bufs, gc, e->ctx_cap, (size_t)n, e->ch)) ||
       (rc = e->bufs.alloc(&e->d_win, (size_t)n * e->kv_pages, true)) || (rc = e->bufs.alloc(&e->d_tok_in, (size_t)n)) ||
-      (rc = e->bufs.alloc_host(&e->h_tok_in, (size_t)n))) {
+      (rc = e->bufs.alloc_host(&e->h_tok_in, (size_t)n)) || (logprob_shape_ok(gc.V) && (rc = gen_logprob_alloc(e->bufs, gc)))) {
     delete e;
     model_clear_cache(m);
     return rc;
@@ -3177,9 +3290,13 @@ void engine_destroy(aha_engine* e) {
 }
 
 int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const aha_mm_input* mm, const aha_sampling_params* params, size_t max_new,
-                  uint64_t* req_id) {
+                  uint64_t* req_id, int32_t top_logprobs) {
   aha_model* m = e->m;
   const aha_model_desc& c = m->desc;
+  if (top_logprobs >= 0 && !e->gc.lp_tab) {
+    set_error("engine_submit_logprobs: vocabulary too large for the logprob pass");
+    return AHA_ERR_UNSUPPORTED;
+  }
   if (!ids || !req_id) {
     set_error("engine_submit: null input_ids / req_id");
     return AHA_ERR_INVALID;
@@ -3213,6 +3330,7 @@ int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const aha_mm
   if (params) q->params = *params;
   else q->params = aha_sampling_params{0.f, 1.f, 0, 1.f, 64, 0u, 299792458ull};   // ArgMax, no penalty: the device argmax
   q->max_new = max_new;
+  q->top_logprobs = top_logprobs;
   q->npages = npages;
   q->toks.reserve(max_new);
   e->waiting.push_back(q);
@@ -3304,10 +3422,11 @@ static int engine_admit(aha_engine* e, EngReq* q, int s) {
   }
   e->n_out[s] = 0;
   e->seq_tok[s] = q->toks.data();
+  e->lp_top[s] = q->top_logprobs;
   return AHA_OK;
 }
 
-int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, float* logits_out) {
+int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, float* logits_out, aha_token_logprobs* logprobs_out) {
   aha_model* m = e->m;
   const aha_model_desc& c = m->desc;
   hipStream_t st = m->stream;
@@ -3326,9 +3445,12 @@ int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, f
   }
   AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
   size_t ne = 0;
-  auto emit = [&](uint64_t id, uint32_t tok, uint32_t flags) { ev[ne++] = aha_engine_event{id, tok, flags}; };
+  auto emit = [&](uint64_t id, uint32_t tok, uint32_t flags) {
+    if (logprobs_out && (flags & AHA_ENGINE_EV_CANCELLED)) logprobs_out[ne].n_top = -1;   // (a token's entry: gen_finish_step wrote it)
+    ev[ne++] = aha_engine_event{id, tok, flags};
+  };
   // 1. cancellations
-  for (const aha_engine_event& p : e->pending) ev[ne++] = p;
+  for (const aha_engine_event& p : e->pending) emit(p.req_id, p.token, p.flags);
   e->pending.clear();
   for (int s = 0; s < (int)e->max_running; ++s)
     if (e->slots[s] && e->slots[s]->cancel) {
@@ -3420,6 +3542,7 @@ int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, f
         seqs[j] = segs[j].q->slot;
         e->n_out[seqs[j]] = 0;
         e->row_logits[j] = logits_out ? logits_out + (ne + j) * (size_t)V : nullptr;
+        e->row_lp[j] = logprobs_out ? logprobs_out + (ne + j) : nullptr;
       }
       if ((rc = gen_finish_step(m, gc, e->ch, seqs, gc.tok[0]))) return rc;
       for (int j = 0; j < k; ++j) {
@@ -3462,6 +3585,7 @@ int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, f
       kv_tokens += kv_len;
       e->h_tok_in[r] = q->toks.back();
       e->row_logits[r] = logits_out ? logits_out + (ne + r) * (size_t)V : nullptr;
+      e->row_lp[r] = logprobs_out ? logprobs_out + (ne + r) : nullptr;
     }
     AHA_HIP_CHECK(hipMemcpyAsync(gc.rowtab, gc.h_rowtab, (size_t)R * GEN_ROW_WORDS * 4, hipMemcpyHostToDevice, st));
     AHA_HIP_CHECK(hipMemcpyAsync(e->d_tok_in, e->h_tok_in, (size_t)R * 4, hipMemcpyHostToDevice, st));

@@ -413,6 +413,38 @@ class HipInferenceModel:
         return self._generate_batch(lib().aha_hip_generate_batch_mm, prompts, (mm_arr, cp), max_new, max_tokens_per_pass,
                                     "step" if want_step_logits else None)
 
+    def generate_batch_logprobs(self, prompts: Sequence[Sequence[int]], max_new: int, top_logprobs, data=None, params=None,
+                                max_tokens_per_pass: int = 0, want_step_logits: bool = False):
+        """generate_batch_mm plus per-token log-probabilities (aha_hip_generate_batch_logprobs): the same tokens and step logits, bit for
+        bit.  top_logprobs: an int (0..20) for every prompt, or one entry per prompt with None = no logprobs for that prompt.  The
+        log-probabilities are those of the model's own distribution over the step's logits (temperature 1, before the repeat penalty),
+        whatever the sampler.  Returns (token lists, logprobs[, step logits]): logprobs[j] is None for a prompt that asked for none, else
+        per generated token (logprob, [(id, logprob), ...]) with the top_logprobs most likely tokens, most likely first."""
+        n = len(prompts)
+        if data is not None and len(data) != n:
+            raise ValueError(f"{len(data)} MultiModalData entries for {n} prompts")
+        tops = [top_logprobs] * n if top_logprobs is None or isinstance(top_logprobs, (int, np.integer)) else list(top_logprobs)
+        if len(tops) != n:
+            raise ValueError(f"{len(tops)} top_logprobs entries for {n} prompts")
+        top = np.ascontiguousarray(np.asarray([-1 if t is None else int(t) for t in tops] + [0], dtype=np.int32))
+        cp = None if params is None else _sampling_array(params, n)
+        keep, mm_arr = [], None
+        if data is not None:
+            mm_arr = (C.c_void_p * max(n, 1))()
+            for j, d in enumerate(data):
+                if d is not None:
+                    mm, k = _mm_input(d)
+                    keep += [mm, k]
+                    mm_arr[j] = C.addressof(mm)
+        lp = (_lib.TokenLogprobs * max(n * max(int(max_new), 1), 1))()
+
+        def entry(handle, ids, lens, n_, mm_, cp_, mx, pas, toks, n_out, lg):
+            return lib().aha_hip_generate_batch_logprobs(handle, ids, lens, n_, mm_, cp_, top.ctypes.data, mx, pas, toks, n_out, lg, lp)
+        res = self._generate_batch(entry, prompts, (mm_arr, cp), max_new, max_tokens_per_pass, "step" if want_step_logits else None)
+        toks = res[0] if want_step_logits else res
+        out = [None if top[j] < 0 else [_token_logprobs(lp[j * int(max_new) + t]) for t in range(len(toks[j]))] for j in range(n)]
+        return (toks, out, res[1]) if want_step_logits else (toks, out)
+
     def generate_batch_spec(self, prompts: Sequence[Sequence[int]], max_new: int, spec=None, predictions=None, want_logits: bool = False,
                             want_stats: bool = False, max_tokens_per_pass: int = 0):
         """generate_batch with draft-and-verify decoding (aha_hip_generate_batch_spec): the same tokens and logits, bit for bit, in fewer
@@ -581,6 +613,13 @@ class EngineEvent:
         return self.stop or self.length or self.cancelled
 
 
+def _token_logprobs(e):
+    """One aha_token_logprobs -> (logprob, [(id, logprob), ...]); None for an entry whose request asked for none (n_top = -1)."""
+    if e.n_top < 0:
+        return None
+    return float(e.logprob), [(int(e.top_ids[i]), float(e.top_logprobs[i])) for i in range(e.n_top)]
+
+
 class HipEngine:
     """Continuous batching over one model (aha_hip_engine_*): submit requests at any time, step() returns every token emitted in the
     step, cancel() ends a request at the next step.  The engine owns the model's cache while it lives: the model's other generation
@@ -599,8 +638,10 @@ class HipEngine:
         self._done: Dict[int, bool] = {}
         self._n_cancel = 0
 
-    def submit(self, input_ids: Sequence[int], max_new: int, params=None, data: Optional[MultiModalData] = None) -> int:
-        """Queue one request; returns its id.  params: None = greedy, else a sampling.SamplingParams; data: its MultiModalData."""
+    def submit(self, input_ids: Sequence[int], max_new: int, params=None, data: Optional[MultiModalData] = None,
+               top_logprobs: Optional[int] = None) -> int:
+        """Queue one request; returns its id.  params: None = greedy, else a sampling.SamplingParams; data: its MultiModalData;
+        top_logprobs: None, or 0..20 = report every token's log-probability and that many alternatives (step(want_logprobs=True))."""
         ids = np.ascontiguousarray(np.asarray(input_ids, dtype=np.uint32).reshape(-1))
         keep = [ids]
         mm_p = None
@@ -610,7 +651,11 @@ class HipEngine:
             mm_p = C.byref(mm)
         cp = None if params is None else C.byref(params.to_c())
         rid = C.c_uint64()
-        check(lib().aha_hip_engine_submit(self.handle, ids.ctypes.data, ids.size, mm_p, cp, int(max_new), C.byref(rid)))
+        if top_logprobs is None:
+            check(lib().aha_hip_engine_submit(self.handle, ids.ctypes.data, ids.size, mm_p, cp, int(max_new), C.byref(rid)))
+        else:
+            check(lib().aha_hip_engine_submit_logprobs(self.handle, ids.ctypes.data, ids.size, mm_p, cp, int(max_new), int(top_logprobs),
+                                                       C.byref(rid)))
         self._keep[rid.value] = keep
         self._streams[rid.value] = []
         self._done[rid.value] = False
@@ -620,13 +665,19 @@ class HipEngine:
         check(lib().aha_hip_engine_cancel(self.handle, int(req_id)))
         self._n_cancel += 1
 
-    def step(self, want_logits: bool = False):
-        """One engine step: a list of EngineEvent (and with want_logits the (len(events), vocab) float32 logits that chose each token)."""
+    def step(self, want_logits: bool = False, want_logprobs: bool = False):
+        """One engine step: a list of EngineEvent (and with want_logits the (len(events), vocab) float32 logits that chose each token;
+        with want_logprobs, after them, one entry per event: (logprob, [(id, logprob), ...]), or None for a cancellation or a request
+        submitted without top_logprobs)."""
         cap = self.max_running + self._n_cancel
         evs = (_lib.EngineEvent * cap)()
         n = C.c_size_t()
         lg = np.zeros((cap, self.model.text_cfg.vocab_size), np.float32) if want_logits else None
-        check(lib().aha_hip_engine_step(self.handle, evs, cap, C.byref(n), None if lg is None else lg.ctypes.data))
+        lp = (_lib.TokenLogprobs * cap)() if want_logprobs else None
+        if lp is None:
+            check(lib().aha_hip_engine_step(self.handle, evs, cap, C.byref(n), None if lg is None else lg.ctypes.data))
+        else:
+            check(lib().aha_hip_engine_step_logprobs(self.handle, evs, cap, C.byref(n), None if lg is None else lg.ctypes.data, lp))
         self._n_cancel = 0
         out = []
         for i in range(n.value):
@@ -641,7 +692,10 @@ class HipEngine:
             if ev.finished and ev.req_id in self._done:
                 self._done[ev.req_id] = True
             out.append(ev)
-        return out if lg is None else (out, lg[:n.value])
+        if lp is None:
+            return out if lg is None else (out, lg[:n.value])
+        lps = [_token_logprobs(lp[i]) for i in range(n.value)]
+        return (out, lps) if lg is None else (out, lg[:n.value], lps)
 
     def stats(self) -> Dict[str, int]:
         st = _lib.EngineStats()

@@ -293,3 +293,19 @@ def sample_rows(logits: torch.Tensor, k, temperature, repeat_penalty, contexts):
     check(lib().aha_hip_sample_rows(_ptr(logits), logits.stride(0), R, V, kk.ctypes.data, tt.ctypes.data, pp.ctypes.data, ctx.ctypes.data,
                                     off.ctypes.data, _ptr(vals), _ptr(idx), _ptr(ms), _stream()))
     return vals, idx, ms
+
+
+def logprob_rows(logits: torch.Tensor, tokens, n_top):
+    """aha_hip_logprob_rows: the per-token log-probability pass over every row of logits (R, V) f32 (row pitch logits.stride(0)): row r's
+    emitted token tokens[r] and its n_top[r] (0..20; an int: the same for every row) most likely tokens.  The logits are only read.
+    -> numpy (logprob (R,) f32, n_top (R,) int32, top_ids (R, 20) uint32, top_logprobs (R, 20) f32): one aha_token_logprobs per row."""
+    if not logits.is_cuda:
+        raise ValueError("op inputs must be GPU tensors")
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.stride(0) >= logits.shape[1]   # (a row pitch)
+    R, V = logits.shape
+    nn = np.ascontiguousarray(np.broadcast_to(np.asarray(n_top, dtype=np.int32), (R,)))
+    tok = torch.as_tensor(np.asarray(tokens, dtype=np.int64).reshape(R), dtype=torch.int64).to(torch.int32).to(logits.device)
+    out = torch.empty(R, 42, dtype=torch.int32, device=logits.device)
+    check(lib().aha_hip_logprob_rows(_ptr(logits), logits.stride(0), R, V, _ptr(tok), nn.ctypes.data, _ptr(out), _stream()))
+    o = out.cpu().numpy()
+    return (o[:, 0].copy().view(np.float32), o[:, 1].copy(), o[:, 2:22].copy().view(np.uint32), o[:, 22:42].copy().view(np.float32))

@@ -366,6 +366,50 @@ int aha_hip_engine_stats(const aha_engine* e, aha_engine_stats* out);
 /* Test hook: the value a slot's split-arrival counters are reset to when a request takes it (default 0; near 2^32 they wrap mid-request). */
 int aha_hip_engine_debug_ctr_base(aha_engine* e, uint32_t base);
 
+/* ---- per-token log-probabilities -----------------------------------------------------------------------------------------
+ * The chat request's `logprobs` / `top_logprobs` (src/params/chat.rs:85-89 of the reference, whose responses always carry
+ * `logprobs: None`): for every generated token its log-probability and the top_logprobs most likely tokens with theirs.
+ * Definition.  For a step's row of V f32 logits x -- the logits the lm_head produced, the ones step_logits_out reports -- let
+ * M = max_i x_i and S = sum_i exp(x_i - M).  lp(t) = (x_t - M) - log S, in f32.  The distribution is the model's own: temperature 1,
+ * before the repeat penalty, independent of the request's sampler (a sampled token's logprob is that of the token the sampler picked,
+ * under this distribution, computed from its raw logit).  top_logprobs = N (0 .. AHA_MAX_TOP_LOGPROBS) asks for the N tokens with the
+ * largest logits, ordered by (value descending, index ascending) -- the order of aha_hip_sample_candidates, exact among equal values
+ * too; if N > V the surplus entries are id 0xFFFFFFFF / logprob -inf.  A row that contains NaN, or whose every entry is -inf, is
+ * unspecified.
+ * Cost: two small launches per step that has a logprob row (profile classes logprob_rows_stage1 / logprob_rows_stage2) and 168 bytes
+ * per token in the copy that ends the step anyway; a step without such a row takes the path it took before.
+ * Out of scope: logprobs of prompt tokens (`echo`), logprobs in aha_hip_generate_batch_spec, tensor-parallel models, `logit_bias` and
+ * the presence / frequency penalties. */
+#define AHA_MAX_TOP_LOGPROBS 20
+typedef struct aha_token_logprobs {
+  float    logprob;                              /* lp(emitted token) */
+  int32_t  n_top;                                /* the request's top_logprobs; -1: it did not ask for logprobs, nothing else is written */
+  uint32_t top_ids[AHA_MAX_TOP_LOGPROBS];        /* first n_top valid */
+  float    top_logprobs[AHA_MAX_TOP_LOGPROBS];
+} aha_token_logprobs;                            /* 168 bytes */
+
+/* aha_hip_generate_batch_mm plus logprobs.  top_logprobs: HOST, n_seqs entries, -1 = none for that sequence, else 0 .. 20.
+ * logprobs_out: n_seqs x max_new entries; entry [j, t] belongs to token t of sequence j (the first token included); entries past
+ * n_out[j] are untouched; a sequence with -1 gets n_top = -1 in its entries and nothing else.  tokens_out, n_out and step_logits_out are
+ * EXACTLY those of aha_hip_generate_batch_mm on the same arguments, for any top_logprobs; every sampler's RNG stream is consumed
+ * identically.  Supported models, page reservation, cache clearing, error codes and messages are aha_hip_generate_batch_mm's;
+ * additionally AHA_ERR_INVALID before any device work, naming the sequence: a null top_logprobs or logprobs_out, or an entry outside
+ * -1 .. 20. */
+int aha_hip_generate_batch_logprobs(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs,
+                                    const aha_mm_input* const* mm, const aha_sampling_params* params, const int32_t* top_logprobs,
+                                    size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out,
+                                    float* step_logits_out, aha_token_logprobs* logprobs_out);
+/* aha_hip_engine_submit plus the request's top_logprobs (0 .. 20, else AHA_ERR_INVALID).  Requests of either submit function share an
+ * engine and a step. */
+int aha_hip_engine_submit_logprobs(aha_engine* e, const uint32_t* input_ids, size_t n_ids, const aha_mm_input* mm,
+                                   const aha_sampling_params* params, size_t max_new, int32_t top_logprobs, uint64_t* req_id);
+/* aha_hip_engine_step plus one entry per event: logprobs_out (NULL: exactly aha_hip_engine_step) has cap entries, entry i belongs to
+ * event i.  The event of a request that did not ask for logprobs has n_top = -1, and so has a CANCELLED event.  Events, tokens and
+ * logits_out are those of aha_hip_engine_step on the same submission history, bit for bit; aha_hip_engine_step itself keeps working on
+ * an engine with logprob requests (it reports none and does not compute them). */
+int aha_hip_engine_step_logprobs(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, float* logits_out,
+                                 aha_token_logprobs* logprobs_out);
+
 /* Host-only sampler: candle's LogitsProcessor built by get_logit_processor (sample.rs:7-38) plus use_repeat_penalty's slicing, over
  * the rand 0.9.2 StdRng of aha_hip_rng_*.  The deterministic half restates aha_amd/sampling.py (weights over the device candidates, the
  * top-p tie rule, the full-vector path); each sampled token consumes one next_u32, an ArgMax pick none.
@@ -657,6 +701,11 @@ int aha_hip_debug_attn_decode_fused(const void* qkv, const void* q_norm_w, const
 int aha_hip_sample_rows(const float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* k, const float* temperature,
                         const float* repeat_penalty, const uint32_t* context, const size_t* context_offsets, float* vals_out,
                         uint32_t* idx_out, float* ms_out, void* stream);
+/* aha_hip_logprob_rows: the log-probability pass of aha_hip_generate_batch_logprobs for R rows of f32 logits (device, row r at
+ * logits + r * ld, V floats, only read).  tokens (device, R): row r's emitted token; n_top (HOST, R, each 0 .. 20); out (device, R).
+ * AHA_ERR_INVALID for R < 1, V < 1, ld < V, a null pointer or an n_top outside 0 .. 20, checked before anything touches the device. */
+int aha_hip_logprob_rows(const float* logits, int64_t ld, int32_t R, int32_t V, const uint32_t* tokens, const int32_t* n_top,
+                         aha_token_logprobs* out, void* stream);
 /* D7 prefill attention, causal with q position i attending to k positions <= kv_offset + i; q (S, nh*d),
  * k/v (L, kvh*d) token-major, L = kv_offset + S.  causal = 0 gives full (ViT / audio encoder) attention.  d = 128, or 64 with
  * nh == kvh (the Qwen3-ASR audio encoder's geometry). */

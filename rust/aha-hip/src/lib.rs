@@ -149,6 +149,24 @@ pub mod sys {
         pub ngram_max: i32,
     }
 
+    pub const AHA_MAX_TOP_LOGPROBS: usize = 20;
+
+    /// `aha_token_logprobs`: one generated token's log-probability and its `n_top` most likely alternatives (`n_top` -1: the request
+    /// asked for none and nothing else is written).  Temperature 1, before the repeat penalty, whatever the sampler.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug)]
+    pub struct AhaTokenLogprobs {
+        pub logprob: f32,
+        pub n_top: i32,
+        pub top_ids: [u32; AHA_MAX_TOP_LOGPROBS],
+        pub top_logprobs: [f32; AHA_MAX_TOP_LOGPROBS],
+    }
+    impl Default for AhaTokenLogprobs {
+        fn default() -> Self {
+            Self { logprob: 0.0, n_top: -1, top_ids: [u32::MAX; AHA_MAX_TOP_LOGPROBS], top_logprobs: [f32::NEG_INFINITY; AHA_MAX_TOP_LOGPROBS] }
+        }
+    }
+
     /// `aha_spec_stats`
     #[repr(C)]
     #[derive(Clone, Copy, Debug, Default)]
@@ -318,6 +336,21 @@ pub mod sys {
             n_out: *mut usize,
             step_logits_out: *mut f32,
         ) -> i32;
+        pub fn aha_hip_generate_batch_logprobs(
+            m: *mut AhaModel,
+            ids: *const u32,
+            seq_lens: *const usize,
+            n_seqs: usize,
+            mm: *const *const AhaMmInput,
+            params: *const AhaSamplingParams,
+            top_logprobs: *const i32,
+            max_new: usize,
+            max_tokens_per_pass: usize,
+            tokens_out: *mut u32,
+            n_out: *mut usize,
+            step_logits_out: *mut f32,
+            logprobs_out: *mut AhaTokenLogprobs,
+        ) -> i32;
         pub fn aha_hip_generate_batch_spec(
             m: *mut AhaModel,
             ids: *const u32,
@@ -356,10 +389,38 @@ pub mod sys {
             max_new: usize,
             req_id: *mut u64,
         ) -> i32;
+        pub fn aha_hip_engine_submit_logprobs(
+            e: *mut AhaEngine,
+            ids: *const u32,
+            n_ids: usize,
+            mm: *const AhaMmInput,
+            params: *const AhaSamplingParams,
+            max_new: usize,
+            top_logprobs: i32,
+            req_id: *mut u64,
+        ) -> i32;
         pub fn aha_hip_engine_cancel(e: *mut AhaEngine, req_id: u64) -> i32;
         pub fn aha_hip_engine_step(e: *mut AhaEngine, ev: *mut AhaEngineEvent, cap: usize, n_ev: *mut usize, logits_out: *mut f32) -> i32;
+        pub fn aha_hip_engine_step_logprobs(
+            e: *mut AhaEngine,
+            ev: *mut AhaEngineEvent,
+            cap: usize,
+            n_ev: *mut usize,
+            logits_out: *mut f32,
+            logprobs_out: *mut AhaTokenLogprobs,
+        ) -> i32;
         pub fn aha_hip_engine_stats(e: *const AhaEngine, out: *mut AhaEngineStats) -> i32;
         pub fn aha_hip_engine_debug_ctr_base(e: *mut AhaEngine, base: u32) -> i32;
+        pub fn aha_hip_logprob_rows(
+            logits: *const f32,
+            ld: i64,
+            rows: i32,
+            vocab: i32,
+            tokens: *const u32,
+            n_top: *const i32,
+            out: *mut AhaTokenLogprobs,
+            stream: *mut std::ffi::c_void,
+        ) -> i32;
         pub fn aha_hip_sample_rows(
             logits: *const f32,
             ld: i64,
@@ -833,6 +894,56 @@ impl Model {
         Ok(n_out.iter().enumerate().map(|(j, &n)| toks[j * max_new..j * max_new + n].to_vec()).collect())
     }
 
+    /// `generate_batch_mm` for text requests plus per-token log-probabilities (aha_hip_generate_batch_logprobs): `top_logprobs[j]` is
+    /// `None` (no logprobs for request j) or `Some(0..=20)` alternatives per token.  The tokens are exactly `generate_batch_mm`'s;
+    /// entry `[j][t]` of the second result belongs to token `t` of request j (empty for a request that asked for none).  The
+    /// log-probabilities are the model's own (temperature 1, before the repeat penalty), whatever the sampler.
+    pub fn generate_batch_logprobs(
+        &mut self,
+        prompts: &[&[u32]],
+        params: Option<&[sys::AhaSamplingParams]>,
+        top_logprobs: &[Option<u32>],
+        max_new: usize,
+        max_tokens_per_pass: usize,
+    ) -> Result<(Vec<Vec<u32>>, Vec<Vec<sys::AhaTokenLogprobs>>), Error> {
+        if top_logprobs.len() != prompts.len() {
+            return Err(Error { code: -1, message: format!("{} top_logprobs for {} prompts", top_logprobs.len(), prompts.len()) });
+        }
+        if let Some(p) = params {
+            if p.len() != prompts.len() {
+                return Err(Error { code: -1, message: format!("{} sampling params for {} prompts", p.len(), prompts.len()) });
+            }
+        }
+        let top: Vec<i32> = top_logprobs.iter().map(|t| t.map_or(-1, |n| n as i32)).collect();
+        let ids: Vec<u32> = prompts.iter().flat_map(|s| s.iter().copied()).collect();
+        let lens: Vec<usize> = prompts.iter().map(|s| s.len()).collect();
+        let width = max_new.max(1);
+        let mut toks = vec![0u32; prompts.len() * width];
+        let mut n_out = vec![0usize; prompts.len()];
+        let mut lps = vec![sys::AhaTokenLogprobs::default(); prompts.len() * width];
+        check(unsafe {
+            sys::aha_hip_generate_batch_logprobs(
+                self.model,
+                ids.as_ptr(),
+                lens.as_ptr(),
+                lens.len(),
+                std::ptr::null(),
+                params.map_or(std::ptr::null(), |p| p.as_ptr()),
+                top.as_ptr(),
+                max_new,
+                max_tokens_per_pass,
+                toks.as_mut_ptr(),
+                n_out.as_mut_ptr(),
+                std::ptr::null_mut(),
+                lps.as_mut_ptr(),
+            )
+        })?;
+        let tokens = n_out.iter().enumerate().map(|(j, &n)| toks[j * max_new..j * max_new + n].to_vec()).collect();
+        let logprobs =
+            n_out.iter().enumerate().map(|(j, &n)| if top[j] < 0 { Vec::new() } else { lps[j * max_new..j * max_new + n].to_vec() }).collect();
+        Ok((tokens, logprobs))
+    }
+
     /// The greedy loop of `generate_generic` / `generate_stream_generic` (common/generate.rs:115-159, 161-368) kept on the
     /// device in chunks of `chunk` tokens: `on_token` sees every token in order (what a streaming response forwards) and
     /// returns `false` to stop; an eos id stops after it has been delivered, as in the reference.
@@ -933,6 +1044,15 @@ impl<'a> Engine<'a> {
         check(unsafe { sys::aha_hip_engine_submit(self.e, ids.as_ptr(), ids.len(), std::ptr::null(), p, max_new, &mut id) })?;
         Ok(id)
     }
+    /// `submit` plus the request's `top_logprobs` (0..=20): `step_logprobs` then reports every token's log-probability.
+    pub fn submit_logprobs(&mut self, ids: &[u32], params: Option<&sys::AhaSamplingParams>, max_new: usize, top_logprobs: u32) -> Result<u64, Error> {
+        let mut id = 0u64;
+        let p = params.map_or(std::ptr::null(), |p| p as *const _);
+        check(unsafe {
+            sys::aha_hip_engine_submit_logprobs(self.e, ids.as_ptr(), ids.len(), std::ptr::null(), p, max_new, top_logprobs as i32, &mut id)
+        })?;
+        Ok(id)
+    }
     pub fn cancel(&mut self, req_id: u64) -> Result<(), Error> {
         check(unsafe { sys::aha_hip_engine_cancel(self.e, req_id) })?;
         self.n_cancel += 1;
@@ -948,6 +1068,23 @@ impl<'a> Engine<'a> {
         Ok(ev[..n]
             .iter()
             .map(|x| (x.req_id, if x.flags & sys::AHA_ENGINE_EV_CANCELLED != 0 { None } else { Some(x.token) }, x.flags))
+            .collect())
+    }
+    /// `step` plus each event's log-probabilities: `None` for a cancellation and for a request submitted without `top_logprobs`.
+    pub fn step_logprobs(&mut self) -> Result<Vec<(u64, Option<u32>, u32, Option<sys::AhaTokenLogprobs>)>, Error> {
+        let cap = self.max_running + self.n_cancel;
+        let mut ev = vec![sys::AhaEngineEvent::default(); cap];
+        let mut lp = vec![sys::AhaTokenLogprobs::default(); cap];
+        let mut n = 0usize;
+        check(unsafe { sys::aha_hip_engine_step_logprobs(self.e, ev.as_mut_ptr(), cap, &mut n, std::ptr::null_mut(), lp.as_mut_ptr()) })?;
+        self.n_cancel = 0;
+        Ok(ev[..n]
+            .iter()
+            .zip(lp[..n].iter())
+            .map(|(x, l)| {
+                let tok = if x.flags & sys::AHA_ENGINE_EV_CANCELLED != 0 { None } else { Some(x.token) };
+                (x.req_id, tok, x.flags, if l.n_top < 0 { None } else { Some(*l) })
+            })
             .collect())
     }
     pub fn stats(&self) -> Result<sys::AhaEngineStats, Error> {
