@@ -536,6 +536,154 @@ int aha_hip_debug_attn_prefill_segs(const void* q, const void* k, const void* v,
   API_GUARD_END
 }
 
+namespace {
+struct DevBuf {   // a small device allocation freed on every return path
+  void* p = nullptr;
+  ~DevBuf() { if (p) hipFree(p); }
+  int upload(const void* host, size_t bytes) {
+    AHA_HIP_CHECK(hipMalloc(&p, bytes));
+    AHA_HIP_CHECK(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+    return AHA_OK;
+  }
+};
+}  // namespace
+
+int aha_hip_debug_prefill_rope(const void* qkv, const void* q_norm_w, const void* k_norm_w, const int32_t* pos, const int32_t* axis_map,
+                               const float* inv_freq, const uint64_t* page_ptrs, int32_t n_page_ptrs, int32_t S, int32_t nh, int32_t kvh,
+                               int32_t d, float eps, int32_t form, int32_t kv_start, int32_t skip_q, const int32_t* row_slot,
+                               const int32_t* page_rows, int32_t n_pages, void* rope_tab, void* q_out, void* stream) {
+  API_GUARD_BEGIN
+  const char* who = "debug_prefill_rope: ";
+  auto bad = [&](const std::string& why) {
+    set_error(who + why);
+    return AHA_ERR_INVALID;
+  };
+  // (q_out even with skip_q: with AHA_ROPE_ROWS=0 the per-element kernel runs instead, and it writes the q heads whatever skip_q says)
+  if (!qkv || !q_norm_w || !k_norm_w || !pos || !axis_map || !inv_freq || !page_ptrs || !rope_tab || !q_out) return bad("null pointer");
+  if (d != 128) return bad("head_dim must be 128");
+  if (S < 1 || S > (1 << 24) || nh < 1 || kvh < 1 || nh > 1024 || kvh > 1024 || n_page_ptrs < 1) return bad("S outside 1 .. 2^24, nh or kvh outside 1 .. 1024, or n_page_ptrs < 1");
+  if (form < AHA_ROPE_FORM_TABLE || form > AHA_ROPE_FORM_PACKED) return bad("form must be 0 .. 3");
+  if (skip_q != 0 && skip_q != 1) return bad("skip_q must be 0 or 1");
+  if (form == AHA_ROPE_FORM_PACKED && !skip_q) return bad("the packed form writes K and V only (skip_q = 1)");
+  if (form == AHA_ROPE_FORM_DEVICE_START && skip_q) return bad("the per-element kernel always writes the q heads (skip_q = 0)");
+  if (skip_q && form != AHA_ROPE_FORM_PACKED && S < 16) return bad("skip_q needs the row-vectorised kernel (S >= 16)");
+  const int64_t slots = (int64_t)n_page_ptrs * KV_PAGE_TOKENS;
+  if (form == AHA_ROPE_FORM_PACKED) {
+    if (!row_slot || !page_rows) return bad("the packed form needs row_slot and page_rows");
+    if (n_pages < 1 || n_pages > n_page_ptrs) return bad("n_pages outside 1 .. n_page_ptrs");
+    for (int r = 0; r < S; ++r)
+      if (row_slot[r] < 0 || row_slot[r] >= (int64_t)n_pages * KV_PAGE_TOKENS) return bad("row_slot[" + std::to_string(r) + "] outside the pages of the call");
+    for (int p = 0; p < n_pages; ++p) {
+      const int r0 = page_rows[2 * p], n = page_rows[2 * p + 1];
+      if (r0 < 0 || n < 1 || n > KV_PAGE_TOKENS || (int64_t)r0 + n > S) return bad("page_rows of page " + std::to_string(p) + " outside the rows of the call");
+    }
+  } else {
+    if (kv_start < 0 || (int64_t)kv_start + S > slots) return bad("the cache range [kv_start, kv_start + S) runs past the page table");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  DevBuf d_start, d_slot, d_prow;
+  int rc;
+  if (form == AHA_ROPE_FORM_DEVICE_START && (rc = d_start.upload(&kv_start, 4))) return rc;
+  if (form == AHA_ROPE_FORM_PACKED &&
+      ((rc = d_slot.upload(row_slot, (size_t)S * 4)) || (rc = d_prow.upload(page_rows, (size_t)n_pages * 2 * 4))))
+    return rc;
+  launch_rope_table(pos, S, inv_freq, axis_map, S, rope_tab, st);   // stage 1: cos / sin once, as the prefill has them for all layers
+  RopeArgs r{};
+  r.qkv = qkv; r.ld = (int64_t)(nh + 2 * kvh) * d; r.q_norm_w = q_norm_w; r.k_norm_w = k_norm_w; r.pos = pos; r.pos_ld = S;
+  r.inv_freq = inv_freq; r.axis_map = axis_map; r.q_out = q_out;
+  r.kv.page_ptrs = page_ptrs; r.kv.layer_off = 0; r.kv.kvh = kvh; r.kv.d = d;
+  r.S = S; r.nh = nh; r.kvh = kvh; r.d = d; r.eps = eps; r.skip_q = skip_q;
+  switch (form) {
+    case AHA_ROPE_FORM_TABLE: r.kv_start_host = kv_start; r.rope_tab = rope_tab; break;           // forward_initial_impl's call
+    case AHA_ROPE_FORM_NO_TABLE: r.kv_start_host = kv_start; break;                               // the angles computed in place
+    case AHA_ROPE_FORM_DEVICE_START: r.kv_start_host = -1; r.kv_start = (const int32_t*)d_start.p; break;
+    default:                                                                                      // packed_layers' call
+      r.kv_start_host = 0; r.rope_tab = rope_tab;
+      r.row_slot = (const int32_t*)d_slot.p; r.page_rows = (const int32_t*)d_prow.p; r.n_pages = n_pages;
+  }
+  launch_qknorm_rope(r, st);
+  hipError_t e = hipGetLastError();
+  hipStreamSynchronize(st);   // (the tables above are freed on return)
+  AHA_HIP_CHECK(e);
+  return AHA_OK;
+  API_GUARD_END
+}
+
+int aha_hip_debug_prefill_attn_qfuse(const void* qkv, const void* q_norm_w, const void* rope_tab, const uint64_t* page_ptrs,
+                                     int32_t n_page_ptrs, int32_t S, int32_t nh, int32_t kvh, int32_t d, float eps, float scale,
+                                     int32_t kv_offset, int32_t kv_total, int32_t S2, int32_t kv_offset2, int32_t kv_total2,
+                                     const int32_t* segs, int32_t n_seg, int32_t with_kv0, void* o, void* stream) {
+  API_GUARD_BEGIN
+  const char* who = "debug_prefill_attn_qfuse: ";
+  auto bad = [&](const std::string& why) {
+    set_error(who + why);
+    return AHA_ERR_INVALID;
+  };
+  if (!qkv || !q_norm_w || !rope_tab || !page_ptrs || !o) return bad("null pointer");
+  if (d != 128) return bad("head_dim must be 128");
+  if (S < 1 || S > (1 << 24) || nh < 1 || kvh < 1 || nh % kvh || nh / kvh > 16 || n_page_ptrs < 1)
+    return bad("S outside 1 .. 2^24, n_page_ptrs < 1, nh not a multiple of kvh, or a group size above 16");
+  const int64_t slots = (int64_t)n_page_ptrs * KV_PAGE_TOKENS;
+  std::vector<int32_t> tab;
+  size_t o_items = 0, o_kv0 = 0;
+  int n_items = 0;
+  if (n_seg > 0) {
+    if (!segs || S2 != 0) return bad("a packed launch needs segs and takes no second segment");
+    std::vector<int32_t> seg(3 * (size_t)n_seg), kv0(n_seg);
+    int64_t rows = 0;
+    for (int j = 0; j < n_seg; ++j) {
+      const int len = segs[3 * j], p0 = segs[3 * j + 1], k0 = segs[3 * j + 2];
+      if (len < 1 || p0 < 0 || k0 < 0 || k0 % KV_PAGE_TOKENS || (!with_kv0 && k0) || (int64_t)k0 + len > (1 << 24) ||
+          (int64_t)p0 * KV_PAGE_TOKENS + k0 + len > slots)
+        return bad("segment " + std::to_string(j) + ": len >= 1, kv0 a multiple of 64 (0 without with_kv0), its cache within the page table");
+      seg[3 * j] = (int32_t)rows, seg[3 * j + 1] = len, seg[3 * j + 2] = p0, kv0[j] = k0;
+      rows += len;
+    }
+    if (rows != S) return bad("the segments' lengths must add up to S");
+    const std::vector<int32_t> items = seg_items_of(seg, true, with_kv0 ? &kv0 : nullptr);
+    n_items = (int)items.size() / 2;
+    tab = seg;
+    o_items = tab.size();
+    tab.insert(tab.end(), items.begin(), items.end());
+    o_kv0 = tab.size();
+    tab.insert(tab.end(), kv0.begin(), kv0.end());
+  } else {
+    if (n_seg < 0 || S2 < 0 || S2 > (1 << 24)) return bad("n_seg and S2 must be >= 0");
+    if (kv_offset < 0 || kv_total < 1 || kv_total > slots || (int64_t)kv_offset + S > kv_total)
+      return bad("rows [kv_offset, kv_offset + S) must lie within kv_total cache tokens within the page table");
+    if (S2 > 0 && (kv_offset2 < 0 || kv_total2 < 1 || kv_total2 > slots || (int64_t)kv_offset2 + S2 > kv_total2))
+      return bad("second segment: rows [kv_offset2, kv_offset2 + S2) must lie within kv_total2 cache tokens within the page table");
+  }
+  AttnPrefillArgs a{};
+  a.q = qkv; a.q_ld = (int64_t)(nh + 2 * kvh) * d; a.kv.page_ptrs = page_ptrs; a.kv.layer_off = 0; a.kv.kvh = kvh; a.kv.d = d; a.o = o;
+  a.S = S; a.nh = nh; a.kvh = kvh; a.d = d; a.causal = 1; a.scale = scale;
+  a.q_norm_w = q_norm_w; a.q_rope_tab = rope_tab; a.q_eps = eps;
+  if (n_seg > 0) {
+    a.kv_offset = 0; a.kv_total = S;
+    a.seg_tab = tab.data();   // (host address: only its presence matters to the form; the device copy replaces it below)
+  } else {
+    a.kv_offset = kv_offset; a.kv_total = kv_total; a.S2 = S2; a.kv_offset2 = kv_offset2; a.kv_total2 = kv_total2;
+  }
+  if (!attn_prefill_takes_qfuse(a)) {
+    set_error(std::string(who) + "the attention form these arguments select does not norm and rotate Q itself");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  DevBuf d_tab;
+  if (n_seg > 0) {
+    if (int rc = d_tab.upload(tab.data(), tab.size() * 4)) return rc;
+    const int32_t* t = (const int32_t*)d_tab.p;
+    a.seg_tab = t; a.seg_items = t + o_items; a.n_items = n_items;
+    a.seg_kv0 = with_kv0 ? t + o_kv0 : nullptr;
+  }
+  launch_attn_prefill(a, st);
+  hipError_t e = hipGetLastError();
+  hipStreamSynchronize(st);
+  AHA_HIP_CHECK(e);
+  return AHA_OK;
+  API_GUARD_END
+}
+
 int aha_hip_attn_decode(const void* q, const void* k, const void* v, void* o, int32_t nh, int32_t kvh, int32_t d,
                         int32_t L, float scale, void* stream) {
   API_GUARD_BEGIN

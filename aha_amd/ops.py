@@ -156,6 +156,56 @@ def attn_prefill_segs(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, nh: int
     return o
 
 
+ROPE_FORM_TABLE, ROPE_FORM_NO_TABLE, ROPE_FORM_DEVICE_START, ROPE_FORM_PACKED = 0, 1, 2, 3
+
+
+def debug_prefill_rope(qkv: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: torch.Tensor, pos: torch.Tensor, axis_map: torch.Tensor,
+                       inv_freq: torch.Tensor, page_ptrs: torch.Tensor, nh: int, kvh: int, eps: float, form: int = ROPE_FORM_TABLE,
+                       kv_start: int = 0, skip_q: bool = False, row_slot=None, page_rows=None):
+    """Test entry (aha_hip_debug_prefill_rope): the prefill's rope table, then its q/k-norm + RoPE + paged KV write, in the form the model
+    (ROPE_FORM_TABLE), the in-place-angle A/B (NO_TABLE), the device-scalar path (DEVICE_START) or a packed pass (PACKED: row_slot (S),
+    page_rows (n_pages, 2) host ints) launches it.  qkv (S, (nh+2kvh)*128) bf16, pos (3, S) int32, axis_map (64) int32, inv_freq (64) f32,
+    page_ptrs (P,) int64 device page addresses into a pool of the caller's.  -> (rope_tab (S, 128) bf16, q (S, nh*128) bf16; with skip_q
+    the kernel leaves q as allocated: zeros)."""
+    _chk(qkv, q_norm_w, k_norm_w, pos, axis_map, inv_freq, page_ptrs)
+    assert pos.dtype == torch.int32 and axis_map.dtype == torch.int32 and inv_freq.dtype == torch.float32 and page_ptrs.dtype == torch.int64
+    S = qkv.shape[0]
+    assert tuple(pos.shape) == (3, S) and axis_map.numel() == 64 and inv_freq.numel() == 64 and qkv.shape[1] == (nh + 2 * kvh) * 128
+    tab = torch.empty(S, 128, dtype=torch.bfloat16, device=qkv.device)
+    q = torch.zeros(S, nh * 128, dtype=torch.bfloat16, device=qkv.device)
+    slot = prow = None
+    n_pages = 0
+    if form == ROPE_FORM_PACKED:
+        slot = np.ascontiguousarray(np.asarray(row_slot, dtype=np.int32).reshape(S))
+        prow = np.ascontiguousarray(np.asarray(page_rows, dtype=np.int32).reshape(-1, 2))
+        n_pages = prow.shape[0]
+    check(lib().aha_hip_debug_prefill_rope(_ptr(qkv), _ptr(q_norm_w), _ptr(k_norm_w), _ptr(pos), _ptr(axis_map), _ptr(inv_freq), _ptr(page_ptrs),
+                                           page_ptrs.numel(), S, nh, kvh, 128, eps, int(form), int(kv_start), int(bool(skip_q)),
+                                           None if slot is None else slot.ctypes.data, None if prow is None else prow.ctypes.data, n_pages,
+                                           _ptr(tab), _ptr(q), _stream()))
+    return tab, q
+
+
+def debug_prefill_attn_qfuse(qkv: torch.Tensor, q_norm_w: torch.Tensor, rope_tab: torch.Tensor, page_ptrs: torch.Tensor, nh: int, kvh: int,
+                             eps: float, kv_offset: int = 0, kv_total: int = 0, seg2=None, segs=None, with_kv0: bool = False,
+                             scale: Optional[float] = None) -> torch.Tensor:
+    """Test entry (aha_hip_debug_prefill_attn_qfuse): the prefill attention norming + rotating the RAW q heads of qkv in its Q load, over the
+    pages debug_prefill_rope wrote.  One sequence: rows at cache positions kv_offset .. of kv_total tokens; seg2 = (S2, kv_offset2,
+    kv_total2): the last S2 rows of qkv are a second causal segment of the same launch.  Packed: segs = [(len, page0, kv0), ...].
+    -> o (rows, nh*128) bf16.  Raises AhaHipError (AHA_ERR_UNSUPPORTED) where the selected attention form takes no fused Q."""
+    _chk(qkv, q_norm_w, rope_tab, page_ptrs)
+    assert page_ptrs.dtype == torch.int64 and rope_tab.shape == (qkv.shape[0], 128) and qkv.shape[1] == (nh + 2 * kvh) * 128
+    rows = qkv.shape[0]
+    scale = bf16_scale(128) if scale is None else scale
+    o = torch.empty(rows, nh * 128, dtype=torch.bfloat16, device=qkv.device)
+    S2, off2, tot2 = (int(x) for x in seg2) if seg2 else (0, 0, 0)
+    flat = (C.c_int32 * (3 * len(segs)))(*[int(x) for sg in segs for x in sg]) if segs else None
+    check(lib().aha_hip_debug_prefill_attn_qfuse(_ptr(qkv), _ptr(q_norm_w), _ptr(rope_tab), _ptr(page_ptrs), page_ptrs.numel(), rows - S2, nh, kvh,
+                                                 128, eps, scale, int(kv_offset), int(kv_total), S2, off2, tot2, flat, len(segs) if segs else 0,
+                                                 int(with_kv0), _ptr(o), _stream()))
+    return o
+
+
 def argmax(x: torch.Tensor) -> int:
     _chk(x)
     assert x.dtype == torch.float32

@@ -718,6 +718,39 @@ int aha_hip_attn_prefill(const void* q, const void* k, const void* v, void* o, i
  * (multiples of 64); 0: launch without it (every kv0 must be 0).  Synchronises the stream. */
 int aha_hip_debug_attn_prefill_segs(const void* q, const void* k, const void* v, void* o, int32_t nh, int32_t kvh, const int32_t* segs,
                                     int32_t n_seg, int32_t with_kv0, float scale, void* stream);
+/* Test entry: the rope stage of a prefill as the model runs it, on pages of the caller.  Stage 1: launch_rope_table into rope_tab
+ * ((S, 128) bf16, cos[64] | sin[64] per row; always written).  Stage 2: launch_qknorm_rope with the paged destination, in one of the forms
+ * below.  Device inputs: qkv (S, (nh + 2 kvh) * 128) bf16, q_norm_w / k_norm_w (128) bf16, pos (3, S) int32, axis_map (64) int32, inv_freq
+ * (64) f32 -- used as given, not derived from a theta -- and page_ptrs, n_page_ptrs byte addresses of pages (kvh K blocks then kvh V
+ * blocks) in memory the caller owns.  q_out (S, nh * 128) bf16 receives the q heads unless skip_q (never null: with AHA_ROPE_ROWS=0 the
+ * per-element kernel writes it regardless).  kv_start: the cache position of row 0 (forms 0 - 2).  The packed form takes HOST arrays:
+ * row_slot (S): the cache slot of every row, counted over the call's pages page_ptrs[0 .. n_pages), and page_rows (2 * n_pages): per page
+ * its first row and row count (1 .. 64), as plan_packed_pass lays them out.  The two must agree (row page_rows[2p] + t in slot 64 p + t): each
+ * is checked against the pages and rows of the call, not against the other, so a mismatch stays inside the caller's pages but puts K and
+ * V of a row in different slots.  AHA_ERR_INVALID, before any device work, for a null pointer,
+ * S < 1, d != 128, an unknown form, skip_q outside what the form's kernel takes, or slots / rows outside the page table or the call.
+ * Synchronises the stream. */
+#define AHA_ROPE_FORM_TABLE 0         /* kv_start_host = kv_start, rope_tab set: forward_initial_impl's call (S < 16: the per-element kernel) */
+#define AHA_ROPE_FORM_NO_TABLE 1      /* the same without rope_tab: cos / sin computed in place */
+#define AHA_ROPE_FORM_DEVICE_START 2  /* kv_start_host = -1, kv_start read from a device int: the per-element kernel whatever S is */
+#define AHA_ROPE_FORM_PACKED 3        /* row_slot / page_rows / n_pages, rope_tab set, skip_q = 1: packed_layers' call */
+int aha_hip_debug_prefill_rope(const void* qkv, const void* q_norm_w, const void* k_norm_w, const int32_t* pos, const int32_t* axis_map,
+                               const float* inv_freq, const uint64_t* page_ptrs, int32_t n_page_ptrs, int32_t S, int32_t nh, int32_t kvh,
+                               int32_t d, float eps, int32_t form, int32_t kv_start, int32_t skip_q, const int32_t* row_slot,
+                               const int32_t* page_rows, int32_t n_pages, void* rope_tab, void* q_out, void* stream);
+/* Test entry: launch_attn_prefill with q-norm + RoPE of Q inside the kernel's Q load (AttnPrefillArgs::q_norm_w / q_rope_tab / q_eps), over
+ * pages of the caller: qkv as above (the RAW q heads are read, row pitch (nh + 2 kvh) * 128), rope_tab as aha_hip_debug_prefill_rope left
+ * it, o (rows, nh * 128) bf16.  Causal.  n_seg == 0: one sequence, rows [0, S) at cache positions kv_offset .. of kv_total tokens on
+ * page_ptrs[0 ..], and with S2 > 0 a second segment of rows [S, S + S2) at kv_offset2 / kv_total2 in the same launch
+ * (AttnPrefillArgs::S2).  n_seg > 0: packed, segs = n_seg HOST triples {len, page0, kv0}, segment j's rows after segment j - 1's, its cache
+ * positions 0 .. kv0 + len - 1 on page_ptrs[page0 ..]; with_kv0 passes the kv0 column as AttnPrefillArgs::seg_kv0 (multiples of 64), 0
+ * launches without it (every kv0 0).  AHA_ERR_UNSUPPORTED, nothing launched, when attn_prefill_takes_qfuse says no for these arguments
+ * (the 64-row form); AHA_ERR_INVALID, before any device work, for a null pointer, S < 1, d != 128, nh / kvh > 16 or a cache range past
+ * the page table.  Synchronises the stream. */
+int aha_hip_debug_prefill_attn_qfuse(const void* qkv, const void* q_norm_w, const void* rope_tab, const uint64_t* page_ptrs,
+                                     int32_t n_page_ptrs, int32_t S, int32_t nh, int32_t kvh, int32_t d, float eps, float scale,
+                                     int32_t kv_offset, int32_t kv_total, int32_t S2, int32_t kv_offset2, int32_t kv_total2,
+                                     const int32_t* segs, int32_t n_seg, int32_t with_kv0, void* o, void* stream);
 /* V0-pre, host arithmetic: img_smart_resize (src/utils/img_utils.rs:294-331) -- the size Qwen3VLProcessor::process_img
  * (qwen3vl/processor.rs:159-165) resizes an image to: multiples of `factor` (patch * merge = 32), area within
  * [min_pixels, max_pixels] (shortest_edge / longest_edge of the preprocessor config).  AHA_ERR_INVALID when the aspect ratio

@@ -54,17 +54,16 @@ import functools
 import os
 import sys
 
-import numpy as np
 import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kv_pages  # noqa: E402
+from rope_ref import D, SPARE_PAGES, Pool, _r, norm_rope_ref, norm_weights, prologue_ref, prologue_rows_ref, rnd  # noqa: E402,F401
 from test_ops_gpu import assert_close_ulps, ulp_bf16  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-D = 128
 EPS = 1e-6
 ULPS = 3                       # test_ops_gpu.py::test_attn_decode
 K_ULPS, K_EXACT = 2, 0.97      # test_ops_gpu.py::test_qknorm_rope
@@ -73,16 +72,10 @@ LENS = [1, 2, 64, 65, 66, 129, 193, 257, 300, 1025, 4097, 4500]
 LONG_SHAPES = [(8, 2), (8, 1), (16, 1)]
 LONG_LENS = [16449, 40000]
 SINGLE_LENS = [1, 65, 257, 4097]   # also through the single-sequence entry
-SPARE_PAGES = 3
 
 
 def lens_of(nh, kvh):
     return LENS + (LONG_LENS if (nh, kvh) in LONG_SHAPES else [])
-
-
-def rnd(shape, seed, std=1.0, mean=0.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(shape, generator=g) * std + mean).to(torch.bfloat16)
 
 
 def bf16_scale():
@@ -90,26 +83,6 @@ def bf16_scale():
 
 
 # ---- the reference ---------------------------------------------------------------------------------------------------------------
-def _r(x):
-    """One materialisation in the model dtype: f64 -> bf16 -> f64."""
-    return x.to(torch.bfloat16).double()
-
-
-def prologue_ref(qkv_row, q_norm_w, k_norm_w, rope_row, nh, kvh, eps):
-    """-> (q (nh, 128) bf16, k_new (kvh, 128) bf16, v_new (kvh, 128) bf16 = the row's v heads as they are)."""
-    x = qkv_row.double()
-    cos, sin = rope_row[:64].double().repeat(2), rope_row[64:].double().repeat(2)
-
-    def norm_rope(h, w):
-        h = _r(h / torch.sqrt(h.pow(2).mean(-1, keepdim=True) + eps) * w.double())
-        rot = torch.cat([-h[:, 64:], h[:, :64]], 1)     # element i pairs with i + 64
-        return _r(_r(h * cos) + _r(rot * sin)).to(torch.bfloat16)
-
-    q = norm_rope(x[: nh * D].view(nh, D), q_norm_w)
-    k = norm_rope(x[nh * D: (nh + kvh) * D].view(kvh, D), k_norm_w)
-    return q, k, qkv_row[(nh + kvh) * D:].view(kvh, D)
-
-
 def fused_ref(qkv_row, q_norm_w, k_norm_w, rope_row, k_cache, v_cache, nh, kvh, eps, scale):
     """The fused decode attention of one sequence in f64.  k_cache, v_cache: (kv_len - 1, kvh * 128) bf16, the tokens already cached.
     -> (o (nh * 128) f64, k_new (kvh * 128) bf16, v_new (kvh * 128) bf16)."""
@@ -124,50 +97,6 @@ def fused_ref(qkv_row, q_norm_w, k_norm_w, rope_row, k_cache, v_cache, nh, kvh, 
 
 
 # ---- inputs ----------------------------------------------------------------------------------------------------------------------
-class Pool:
-    """Pages of several sequences in one garbage-filled pool, addressed through a seeded permutation."""
-
-    def __init__(self, kvh, lens, seed):
-        self.kvh, self.lens = kvh, list(lens)
-        self.npg = [(L + 63) // 64 for L in self.lens]              # pages of a sequence AFTER the append
-        self.page0 = [int(x) for x in np.cumsum([0] + self.npg[:-1])]
-        P = sum(self.npg) + SPARE_PAGES
-        self.host = rnd((P, kv_pages.page_elems(kvh)), seed, 100.0)   # finite garbage everywhere
-        self.perm = torch.randperm(P, generator=torch.Generator().manual_seed(seed + 1))
-
-    def phys(self, r, i):
-        return int(self.perm[self.page0[r] + i])
-
-    def write(self, r, k_cache, v_cache):
-        n = (k_cache.shape[0] + 63) // 64
-        if n == 0:
-            return
-        pg = self.perm[self.page0[r]: self.page0[r] + n]
-        self.host[pg] = kv_pages.pack_pages(k_cache, v_cache, self.kvh, out=self.host[pg])
-
-    def upload(self):
-        self.dev = self.host.to("cuda")
-        self.before = self.dev.clone()
-        self.ptrs = (self.dev.data_ptr() + self.perm.to(torch.int64) * self.host.shape[1] * 2).to("cuda")
-
-    def restore(self):
-        self.dev.copy_(self.before)
-
-    def changed(self):
-        """Flat indices (page * page_elems + element) of the pool elements whose bits differ from before the launch."""
-        return torch.nonzero((self.dev.view(torch.int16) != self.before.view(torch.int16)).flatten()).flatten().cpu()
-
-    def slot_elems(self, r):
-        """(flat indices of the elements of the slot that row r appends to, the page, the slot)."""
-        L = self.lens[r]
-        pg, t = self.phys(r, (L - 1) // 64), (L - 1) % 64
-        return pg * self.host.shape[1] + kv_pages.slot_index(self.kvh)[t], pg, t
-
-
-def norm_weights():
-    return rnd((D,), 8, 0.1, 1.0), rnd((D,), 9, 0.1, 1.0)
-
-
 def rope_rows(R, seed=10):
     ang = torch.rand(R, 64, generator=torch.Generator().manual_seed(seed)) * 6.0
     return torch.cat([torch.cos(ang), torch.sin(ang)], 1).to(torch.bfloat16).float().contiguous()
