@@ -56,6 +56,15 @@ class TokenLogprobs(C.Structure):
                 ("top_logprobs", C.c_float * AHA_MAX_TOP_LOGPROBS)]
 
 
+AHA_MAX_LOGIT_BIAS = 1024
+
+
+class LogitAdjust(C.Structure):
+    """aha_logit_adjust (include/aha_hip.h); the Rust shim's AhaLogitAdjust has the same fields in the same order."""
+    _fields_ = [("presence_penalty", C.c_float), ("frequency_penalty", C.c_float), ("bias_ids", C.POINTER(C.c_uint32)),
+                ("bias_vals", C.POINTER(C.c_float)), ("n_bias", C.c_size_t)]
+
+
 class SpecConfig(C.Structure):
     """aha_spec_config (include/aha_hip.h); the Rust shim's AhaSpecConfig has the same fields in the same order."""
     _fields_ = [("max_draft", C.c_int32), ("ngram_min", C.c_int32), ("ngram_max", C.c_int32)]
@@ -209,6 +218,13 @@ SIGNATURES = {
     "aha_hip_engine_submit_logprobs": (C.c_int, [_P, _P, C.c_size_t, _P, C.POINTER(SamplingParams), C.c_size_t, C.c_int32,
                                                  C.POINTER(C.c_uint64)]),
     "aha_hip_engine_step_logprobs": (C.c_int, [_P, C.POINTER(EngineEvent), C.c_size_t, C.POINTER(C.c_size_t), _P, C.POINTER(TokenLogprobs)]),
+    "aha_hip_generate_batch_adjusted": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.POINTER(SamplingParams), C.POINTER(LogitAdjust), _P, C.c_size_t,
+                                                  C.c_size_t, _P, _P, _P, C.POINTER(TokenLogprobs)]),
+    "aha_hip_engine_submit_adjusted": (C.c_int, [_P, _P, C.c_size_t, _P, C.POINTER(SamplingParams), C.POINTER(LogitAdjust), C.c_size_t, C.c_int32,
+                                                 C.POINTER(C.c_uint64)]),
+    "aha_hip_sample_rows_adjusted": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "aha_hip_sampler_set_adjust": (C.c_int, [_P, C.POINTER(LogitAdjust)]),
+    "aha_hip_sampler_adjust_list": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "aha_hip_logprob_rows": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "aha_hip_sample_rows": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "aha_hip_sampler_create": (C.c_int, [C.POINTER(SamplingParams), _P]),

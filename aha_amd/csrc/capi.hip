@@ -6,6 +6,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <vector>
 
 #include "common.h"
@@ -746,10 +747,20 @@ int aha_hip_gemv_rows(const void* W, const void* x, void* y, int32_t R, int32_t 
   API_GUARD_END
 }
 
-int aha_hip_sample_rows(const float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* k, const float* temperature,
-                        const float* repeat_penalty, const uint32_t* context, const size_t* context_offsets, float* vals_out,
-                        uint32_t* idx_out, float* ms_out, void* stream) {
-  API_GUARD_BEGIN
+namespace {
+struct DevFree {   // device buffers released when the call returns, on the error paths too
+  void* p[2] = {nullptr, nullptr};
+  ~DevFree() {
+    for (void* q : p)
+      if (q) hipFree(q);
+  }
+};
+}  // namespace
+
+// aha_hip_sample_rows / aha_hip_sample_rows_adjusted (adj_offsets == nullptr: no addends)
+static int sample_rows_impl(const float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* k, const float* temperature,
+                            const float* repeat_penalty, const uint32_t* context, const size_t* context_offsets, const uint32_t* adj_ids,
+                            const float* adj_vals, const size_t* adj_offsets, float* vals_out, uint32_t* idx_out, float* ms_out, void* stream) {
   if (!logits || R < 1 || V < 1 || ld < V || !k || !temperature || !repeat_penalty || !context_offsets || !vals_out || !idx_out || !ms_out) {
     set_error("sample_rows: bad arguments (R >= 1, ld >= V >= 1, per-row k / temperature / repeat_penalty / context_offsets, outputs)");
     return AHA_ERR_INVALID;
@@ -781,8 +792,49 @@ int aha_hip_sample_rows(const float* logits, int64_t ld, int32_t R, int32_t V, c
     t[SAMPLE_ROW_CTX0] = (int32_t)c0;
     t[SAMPLE_ROW_NCTX] = (int32_t)(ctx.size() - c0);
   }
+  // every row's addends sorted by id; an id >= V or a duplicate is refused before anything touches the device
+  std::vector<uint32_t> aid;
+  std::vector<float> aval;
+  for (int r = 0; adj_offsets && r < R; ++r) {
+    const size_t a0 = adj_offsets[r], a1 = adj_offsets[r + 1];
+    if (a1 < a0 || (a1 > a0 && (!adj_ids || !adj_vals)) || a1 - a0 > (size_t)V) {
+      set_error("sample_rows_adjusted: row " + std::to_string(r) + " needs ordered adj_offsets, adj_ids / adj_vals and at most V entries");
+      return AHA_ERR_INVALID;
+    }
+    std::vector<size_t> o(a1 - a0);
+    std::iota(o.begin(), o.end(), a0);
+    std::sort(o.begin(), o.end(), [&](size_t x, size_t y) { return adj_ids[x] < adj_ids[y]; });
+    int32_t* t = tab.data() + (size_t)r * SAMPLE_ROW_WORDS;
+    t[SAMPLE_ROW_ADJ0] = (int32_t)aid.size();
+    t[SAMPLE_ROW_NADJ] = (int32_t)o.size();
+    for (size_t i = 0; i < o.size(); ++i) {
+      const uint32_t id = adj_ids[o[i]];
+      const float a = adj_vals[o[i]];
+      if (id >= (uint32_t)V || (i && id == aid.back()) || isnan(a) || a == INFINITY) {
+        set_error("sample_rows_adjusted: row " + std::to_string(r) + " needs distinct ids < V and addends that are finite or -inf");
+        return AHA_ERR_INVALID;
+      }
+      aid.push_back(id);
+      aval.push_back(a);
+    }
+  }
+  if (aid.size() > (size_t)INT32_MAX) {
+    set_error("sample_rows_adjusted: too many addends");
+    return AHA_ERR_INVALID;
+  }
   const int nw = sample_stage1_waves(V);
   const size_t cand = (size_t)R * (nw + 16) * 64;
+  DevFree adj_free;
+  uint32_t* d_aid = nullptr;
+  float* d_aval = nullptr;
+  if (!aid.empty()) {
+    AHA_HIP_CHECK(hipMalloc((void**)&d_aid, aid.size() * 4));
+    adj_free.p[0] = d_aid;
+    AHA_HIP_CHECK(hipMalloc((void**)&d_aval, aid.size() * 4));
+    adj_free.p[1] = d_aval;
+    AHA_HIP_CHECK(hipMemcpyAsync(d_aid, aid.data(), aid.size() * 4, hipMemcpyHostToDevice, st));
+    AHA_HIP_CHECK(hipMemcpyAsync(d_aval, aval.data(), aid.size() * 4, hipMemcpyHostToDevice, st));
+  }
   int32_t* d_tab = nullptr;
   uint32_t *d_ctx = nullptr, *d_cidx = nullptr;
   float *d_cval = nullptr, *d_part = nullptr, *d_out = nullptr;
@@ -795,7 +847,7 @@ int aha_hip_sample_rows(const float* logits, int64_t ld, int32_t R, int32_t V, c
   AHA_HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
   if (!ctx.empty()) AHA_HIP_CHECK(hipMemcpyAsync(d_ctx, ctx.data(), ctx.size() * 4, hipMemcpyHostToDevice, st));
   for (int stage = 0; stage < 3; ++stage)
-    launch_topk_rows(logits, ld, V, R, d_tab, d_ctx, d_cval, d_cidx, d_part, d_part + (size_t)R * nw, d_out, stage, st);
+    launch_topk_rows(logits, ld, V, R, d_tab, d_ctx, d_cval, d_cidx, d_part, d_part + (size_t)R * nw, d_out, stage, st, d_aid, d_aval);
   hipError_t err = hipGetLastError();
   // {vals[64], max, sumexp, idx[64]} per row -> the three outputs
   if (err == hipSuccess) err = hipMemcpy2DAsync(vals_out, 64 * 4, d_out, SAMPLE_OUT_WORDS * 4, 64 * 4, R, hipMemcpyDeviceToDevice, st);
@@ -810,6 +862,28 @@ int aha_hip_sample_rows(const float* logits, int64_t ld, int32_t R, int32_t V, c
   hipFree(d_out);
   AHA_HIP_CHECK(err);
   return AHA_OK;
+}
+
+int aha_hip_sample_rows(const float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* k, const float* temperature,
+                        const float* repeat_penalty, const uint32_t* context, const size_t* context_offsets, float* vals_out,
+                        uint32_t* idx_out, float* ms_out, void* stream) {
+  API_GUARD_BEGIN
+  return sample_rows_impl(logits, ld, R, V, k, temperature, repeat_penalty, context, context_offsets, nullptr, nullptr, nullptr, vals_out, idx_out,
+                          ms_out, stream);
+  API_GUARD_END
+}
+
+int aha_hip_sample_rows_adjusted(const float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* k, const float* temperature,
+                                 const float* repeat_penalty, const uint32_t* context, const size_t* context_offsets,
+                                 const uint32_t* adj_ids, const float* adj_vals, const size_t* adj_offsets, float* vals_out,
+                                 uint32_t* idx_out, float* ms_out, void* stream) {
+  API_GUARD_BEGIN
+  if (!adj_offsets) {
+    set_error("sample_rows_adjusted: null adj_offsets");
+    return AHA_ERR_INVALID;
+  }
+  return sample_rows_impl(logits, ld, R, V, k, temperature, repeat_penalty, context, context_offsets, adj_ids, adj_vals, adj_offsets, vals_out,
+                          idx_out, ms_out, stream);
   API_GUARD_END
 }
 
@@ -1217,6 +1291,37 @@ int aha_hip_generate_batch_logprobs(aha_model* m, const uint32_t* input_ids, con
                                        step_logits_out, logprobs_out);
   API_GUARD_END
 }
+int aha_hip_generate_batch_adjusted(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs,
+                                    const aha_mm_input* const* mm, const aha_sampling_params* params, const aha_logit_adjust* adjust,
+                                    const int32_t* top_logprobs, size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out,
+                                    size_t* n_out, float* step_logits_out, aha_token_logprobs* logprobs_out) {
+  API_GUARD_BEGIN
+  for (size_t j = 0; params && j < n_seqs && j < ((size_t)1 << 20); ++j) {   // params == NULL: every sequence greedy
+    std::string why;
+    if (sampling_params_check(params[j], &why)) {
+      set_error("generate_batch_adjusted: params of sequence " + std::to_string(j) + ": " + why);
+      return AHA_ERR_INVALID;
+    }
+  }
+  if ((top_logprobs == nullptr) != (logprobs_out == nullptr)) {
+    set_error("generate_batch_adjusted: top_logprobs and logprobs_out go together (both NULL: no logprobs)");
+    return AHA_ERR_INVALID;
+  }
+  for (size_t j = 0; top_logprobs && j < n_seqs && j < ((size_t)1 << 20); ++j)
+    if (top_logprobs[j] < -1 || top_logprobs[j] > AHA_MAX_TOP_LOGPROBS) {
+      set_error("generate_batch_adjusted: top_logprobs of sequence " + std::to_string(j) + " must be -1 (none) or 0 .. " +
+                std::to_string(AHA_MAX_TOP_LOGPROBS) + ", got " + std::to_string(top_logprobs[j]));
+      return AHA_ERR_INVALID;
+    }
+  if (!m) {
+    set_error("null model");
+    return AHA_ERR_INVALID;
+  }
+  if (int rc = engine_owns_cache(m, "generate_batch_adjusted")) return rc;
+  return model_generate_batch_adjusted(m, input_ids, seq_lens, n_seqs, mm, params, adjust, top_logprobs, max_new, max_tokens_per_pass, tokens_out,
+                                       n_out, step_logits_out, logprobs_out);
+  API_GUARD_END
+}
 int aha_hip_generate_batch_spec(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
                                 size_t max_tokens_per_pass, const aha_spec_config* spec, const uint32_t* predictions,
                                 const size_t* prediction_lens, uint32_t* tokens_out, size_t* n_out, float* logits_out, size_t* n_proposed,
@@ -1300,6 +1405,29 @@ int aha_hip_engine_submit_logprobs(aha_engine* e, const uint32_t* input_ids, siz
     return AHA_ERR_INVALID;
   }
   return engine_submit(e, input_ids, n_ids, mm, params, max_new, req_id, top_logprobs);
+  API_GUARD_END
+}
+int aha_hip_engine_submit_adjusted(aha_engine* e, const uint32_t* input_ids, size_t n_ids, const aha_mm_input* mm,
+                                   const aha_sampling_params* params, const aha_logit_adjust* adjust, size_t max_new, int32_t top_logprobs,
+                                   uint64_t* req_id) {
+  API_GUARD_BEGIN
+  if (params) {
+    std::string why;
+    if (sampling_params_check(*params, &why)) {
+      set_error("engine_submit_adjusted: params: " + why);
+      return AHA_ERR_INVALID;
+    }
+  }
+  if (top_logprobs < -1 || top_logprobs > AHA_MAX_TOP_LOGPROBS) {
+    set_error("engine_submit_adjusted: top_logprobs must be -1 (none) or 0 .. " + std::to_string(AHA_MAX_TOP_LOGPROBS) + ", got " +
+              std::to_string(top_logprobs));
+    return AHA_ERR_INVALID;
+  }
+  if (!e) {
+    set_error("engine_submit_adjusted: null engine");
+    return AHA_ERR_INVALID;
+  }
+  return engine_submit(e, input_ids, n_ids, mm, params, max_new, req_id, top_logprobs, adjust);
   API_GUARD_END
 }
 int aha_hip_engine_cancel(aha_engine* e, uint64_t req_id) {

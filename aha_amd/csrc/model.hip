@@ -2527,8 +2527,24 @@ struct GenChoice {
   int32_t *d_stab = nullptr, *h_stab = nullptr;
   uint32_t *d_sctx = nullptr, *h_sctx = nullptr, *d_cidx = nullptr;
   float *d_cval = nullptr, *d_part = nullptr, *d_sout = nullptr, *h_sout = nullptr, *h_fb = nullptr;
+  // the rows' addend lists (logit_bias, presence / frequency penalties), pinned staging and device: null until a sequence has an adjust
+  uint32_t *d_adj_id = nullptr, *h_adj_id = nullptr;
+  float *d_adj_val = nullptr, *h_adj_val = nullptr;
   std::vector<int> mode, slot, fb_rows;   // finish_step's per-row scratch
 };
+
+// room for `cap` addend entries (cap > 0)
+static int gen_choice_adj_alloc(DevBufs& bufs, size_t cap, GenChoice& ch) {
+  int rc;
+  if ((rc = bufs.alloc(&ch.d_adj_id, cap)) || (rc = bufs.alloc(&ch.d_adj_val, cap)) || (rc = bufs.alloc_host(&ch.h_adj_id, cap)) ||
+      (rc = bufs.alloc_host(&ch.h_adj_val, cap)))
+    return rc;
+  return AHA_OK;
+}
+// the most entries a sequence's list can reach: its non-zero biases and one per generated token, never more than the vocabulary
+static size_t adjust_list_cap(const HostSampler& S, size_t max_new, size_t V) {
+  return S.adj.active ? std::min(V, S.adj.bias_ids.size() + max_new) : 0;
+}
 
 // The candidate step's buffers for gc.n rows: ctx_cap penalty-context ids, n_fb full logits rows on the host
 static int gen_choice_alloc(DevBufs& bufs, const GenCall& gc, size_t ctx_cap, size_t n_fb, GenChoice& ch) {
@@ -2546,22 +2562,26 @@ static int gen_choice_alloc(DevBufs& bufs, const GenCall& gc, size_t ctx_cap, si
   return AHA_OK;
 }
 
-static int gen_choice_init(DevBufs& bufs, const GenCall& gc, const aha_sampling_params* params, GenChoice& ch) {
+static int gen_choice_init(DevBufs& bufs, const GenCall& gc, const aha_sampling_params* params, GenChoice& ch,
+                           const aha_logit_adjust* adjust = nullptr) {
   const int n = gc.n, V = gc.V;
   if (!sample_shape_ok(V, 64)) {
     set_error("generate_batch_sampled: vocabulary too large for the candidate step");
     return AHA_ERR_UNSUPPORTED;
   }
   ch.samplers.resize(n);
-  size_t ctx_cap = 0, n_fb = 0;
+  size_t ctx_cap = 0, n_fb = 0, adj_cap = 0;
   int rc;
   for (int j = 0; j < n; ++j) {
     if ((rc = host_sampler_init(ch.samplers[j], params[j]))) return rc;
+    if (adjust) sampler_set_adjust(ch.samplers[j], &adjust[j]);
     const HostSampler& S = ch.samplers[j];
+    adj_cap += adjust_list_cap(S, gc.max_new, (size_t)V);
     if (S.repeat_penalty != 1.0f) ctx_cap += std::min<size_t>(gc.max_new, (size_t)S.repeat_last_n);
     // a sequence that may need its full logits row: Sampling::All, oversized k, any TopP (nucleus wider than the candidates)
     if (S.kind != SAMPLE_ARGMAX && (S.kind == SAMPLE_TOPP || sampler_candidates_needed(S, (size_t)V) == 0)) ++n_fb;
   }
+  if (adj_cap && (rc = gen_choice_adj_alloc(bufs, adj_cap, ch))) return rc;
   return gen_choice_alloc(bufs, gc, ctx_cap, n_fb, ch);
 }
 
@@ -2570,6 +2590,9 @@ static int gen_choice_init(DevBufs& bufs, const GenCall& gc, const aha_sampling_
 // candidate step over every row that samples (its penalty context uploaded with it) and the candidates' copy; after it the host picks,
 // a second sync only for rows whose candidates cannot decide (their logits rows come down), and the picked tokens go back up into
 // tok_dev for the next step's embedding gather.  gc.step_logits_out (greedy or sampled): every step's logits.
+// Addends (a sampler with an active aha_logit_adjust): the sampler's counts are brought up to the sequence's tokens, and a row with a live
+// addend is a candidate row (k = 1 for ArgMax) whose sorted (id, addend) list goes up with the table; a row that needs its full vector gets
+// the addends in sampler_pick.  A step without a live addend launches and copies what it did before they existed.
 // Logprobs (gc.lp_top): one two-launch pass over the rows that ask for them, behind the candidate step and in front of the same sync; a
 // greedy row's entry is complete on the device (its token is in tok_dev), a sampled row's lp is finished here from the raw logit of the
 // token the host picked -- among its candidates' raw logits, which came down with the entry, or in its full row when it fell back.
@@ -2584,14 +2607,16 @@ static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::
   if (sampled) {
     ch.mode.assign(R, GREEDY);
     ch.slot.assign(R, -1);
-    size_t nc = 0;
+    size_t nc = 0, na = 0;
     for (int r = 0; r < R; ++r) {
       const int j = seqs[r];
-      const HostSampler& S = ch.samplers[j];
+      HostSampler& S = ch.samplers[j];
       float pen;
       size_t n_ctx;
       sampler_penalty_context(S, gc.n_out[j], &pen, &n_ctx);
-      if (S.kind == SAMPLE_ARGMAX && pen == 1.0f) continue;   // the device argmax is the token
+      sampler_adjust_sync(S, gen_seq_tokens(gc, j), gc.n_out[j], (size_t)V);
+      const bool live = sampler_adjust_bound(S) > 0;
+      if (S.kind == SAMPLE_ARGMAX && pen == 1.0f && !live) continue;   // the device argmax is the token
       const int k = S.kind == SAMPLE_ARGMAX ? 1 : sampler_candidates_needed(S, (size_t)V);
       if (!k) {
         ch.mode[r] = FULL;
@@ -2616,17 +2641,23 @@ static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::
       memcpy(&t[SAMPLE_ROW_PEN], &pen, 4);
       t[SAMPLE_ROW_CTX0] = (int32_t)c0;
       t[SAMPLE_ROW_NCTX] = (int32_t)(nc - c0);
-      t[6] = t[7] = 0;
+      t[SAMPLE_ROW_ADJ0] = (int32_t)na;
+      t[SAMPLE_ROW_NADJ] = live ? (int32_t)sampler_adjust_list(S, ch.h_adj_id + na, ch.h_adj_val + na) : 0;
+      na += (size_t)t[SAMPLE_ROW_NADJ];
       ++ns;
     }
     if (ns) {
       AHA_HIP_CHECK(hipMemcpyAsync(ch.d_stab, ch.h_stab, (size_t)ns * SAMPLE_ROW_WORDS * 4, hipMemcpyHostToDevice, st));
       if (nc) AHA_HIP_CHECK(hipMemcpyAsync(ch.d_sctx, ch.h_sctx, nc * 4, hipMemcpyHostToDevice, st));
+      if (na) {
+        AHA_HIP_CHECK(hipMemcpyAsync(ch.d_adj_id, ch.h_adj_id, na * 4, hipMemcpyHostToDevice, st));
+        AHA_HIP_CHECK(hipMemcpyAsync(ch.d_adj_val, ch.h_adj_val, na * 4, hipMemcpyHostToDevice, st));
+      }
       const char* names[3] = {"sample_rows_stage1", "sample_rows_stage2a", "sample_rows_stage2b"};
       for (int stage = 0; stage < 3; ++stage) {
-        ProfScope ps(m, names[stage], stage == 0 ? (double)ns * V * 4 : 0, 0);
+        ProfScope ps(m, names[stage], stage == 0 ? (double)ns * V * 4 + (double)na * 8 : 0, 0);   // (the logits, the uploaded lists)
         launch_topk_rows(gc.logits, V, V, ns, ch.d_stab, ch.d_sctx, ch.d_cval, ch.d_cidx, ch.d_part, ch.d_part + (size_t)gc.n * ch.nw, ch.d_sout,
-                         stage, st);
+                         stage, st, ch.d_adj_id, ch.d_adj_val);
       }
       AHA_HIP_CHECK(hipGetLastError());
       AHA_HIP_CHECK(hipMemcpyAsync(ch.h_sout, ch.d_sout, (size_t)ns * SAMPLE_OUT_WORDS * 4, hipMemcpyDeviceToHost, st));
@@ -2935,7 +2966,8 @@ static int spec_decode_loop(aha_model* m, GenCall& gc, const SpecRun& sp, const 
 static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
                                size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* logits_out,
                                const aha_sampling_params* params, float* step_logits_out, const aha_mm_input* const* mm = nullptr,
-                               const SpecRun* sp = nullptr, const int32_t* top_logprobs = nullptr, aha_token_logprobs* logprobs_out = nullptr) {
+                               const SpecRun* sp = nullptr, const int32_t* top_logprobs = nullptr, aha_token_logprobs* logprobs_out = nullptr,
+                               const aha_logit_adjust* adjust = nullptr) {
   const aha_model_desc& c = m->desc;
   if (!ids || !seq_lens || !tokens_out || !n_out) {
     set_error("generate_batch: null input_ids / seq_lens / tokens_out / n_out");
@@ -2963,6 +2995,25 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
   }
   int rc = check_batch_ids(c, "generate_batch", ids, seq_lens, n_seqs, max_new);
   if (rc) return rc;
+  // aha_logit_adjust: checked against the vocabulary; all inactive = no adjust at all; a greedy call (params == nullptr) with an active
+  // one gets ArgMax samplers, whose rows without a live addend stay the device argmax
+  std::vector<aha_sampling_params> greedy_params;
+  if (adjust) {
+    bool any = false;
+    for (size_t j = 0; j < n_seqs; ++j) {
+      std::string why;
+      if (logit_adjust_check(&adjust[j], (size_t)c.vocab_size, &why)) {
+        set_error("generate_batch_adjusted: adjust of sequence " + std::to_string(j) + ": " + why);
+        return AHA_ERR_INVALID;
+      }
+      any |= logit_adjust_active(&adjust[j]);
+    }
+    if (!any) adjust = nullptr;
+    else if (!params) {
+      greedy_params.assign(n_seqs, aha_sampling_params{0.f, 1.f, 0, 1.f, 64, 0u, 299792458ull});
+      params = greedy_params.data();
+    }
+  }
   std::vector<size_t> pred_off(n_seqs, 0);
   if (sp && sp->predictions) {
     size_t off = 0;
@@ -3011,7 +3062,7 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
     gc.max_nsplit = std::max(gc.max_nsplit, attn_decode_nsplit((int)(seq_lens[j] + max_new), g, m->max_nsplit));
     max_pass_pages += (seq_lens[j] + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
   }
-  if ((rc = gen_call_alloc(m, bufs, gc, max_pass_pages)) || (params && (rc = gen_choice_init(bufs, gc, params, ch)))) return rc;
+  if ((rc = gen_call_alloc(m, bufs, gc, max_pass_pages)) || (params && (rc = gen_choice_init(bufs, gc, params, ch, adjust)))) return rc;
   if (top_logprobs) {
     gc.lp_top = top_logprobs, gc.logprobs_out = logprobs_out;
     if (std::any_of(top_logprobs, top_logprobs + n, [](int32_t t) { return t >= 0; }) && (rc = gen_logprob_alloc(bufs, gc))) return rc;
@@ -3119,6 +3170,14 @@ int model_generate_batch_logprobs(aha_model* m, const uint32_t* ids, const size_
                              nullptr, top_logprobs, logprobs_out);
 }
 
+int model_generate_batch_adjusted(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
+                                  const aha_sampling_params* params, const aha_logit_adjust* adjust, const int32_t* top_logprobs, size_t max_new,
+                                  size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* step_logits_out,
+                                  aha_token_logprobs* logprobs_out) {
+  return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, nullptr, params, step_logits_out, mm,
+                             nullptr, top_logprobs, logprobs_out, adjust);
+}
+
 int model_generate_batch_spec(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new, size_t max_tokens_per_pass,
                               const aha_spec_config* spec, const uint32_t* predictions, const size_t* prediction_lens, uint32_t* tokens_out,
                               size_t* n_out, float* logits_out, size_t* n_proposed, size_t* n_accepted, aha_spec_stats* stats) {
@@ -3151,6 +3210,9 @@ struct EngReq {
   aha_sampling_params params{};
   size_t max_new = 0, npages = 0, done = 0;   // done: prompt tokens prefilled
   int32_t top_logprobs = -1;          // aha_hip_engine_submit_logprobs (-1: no logprobs)
+  aha_logit_adjust adjust{};          // aha_hip_engine_submit_adjusted: its arrays point into the two vectors below
+  std::vector<uint32_t> bias_ids;
+  std::vector<float> bias_vals;
   int slot = -1;
   bool started = false, cancel = false;
   std::vector<uint32_t> toks;         // capacity max_new: gen_finish_step reads the penalty context through a pointer to it
@@ -3184,7 +3246,7 @@ struct aha_engine {
   uint64_t* d_win = nullptr;          // (max_running, kv_pages) page table of the slots
   uint32_t* d_tok_in = nullptr;       // a decode step's input tokens
   uint32_t* h_tok_in = nullptr;       // pinned
-  size_t ctx_cap = 0;
+  size_t ctx_cap = 0, adj_cap = 0;
   ~aha_engine() {
     for (aha::EngReq* q : waiting) delete q;
     for (aha::EngReq* q : slots) delete q;
@@ -3290,9 +3352,16 @@ void engine_destroy(aha_engine* e) {
 }
 
 int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const aha_mm_input* mm, const aha_sampling_params* params, size_t max_new,
-                  uint64_t* req_id, int32_t top_logprobs) {
+                  uint64_t* req_id, int32_t top_logprobs, const aha_logit_adjust* adjust) {
   aha_model* m = e->m;
   const aha_model_desc& c = m->desc;
+  {
+    std::string why;
+    if (logit_adjust_check(adjust, (size_t)c.vocab_size, &why)) {
+      set_error("engine_submit_adjusted: adjust: " + why);
+      return AHA_ERR_INVALID;
+    }
+  }
   if (top_logprobs >= 0 && !e->gc.lp_tab) {
     set_error("engine_submit_logprobs: vocabulary too large for the logprob pass");
     return AHA_ERR_UNSUPPORTED;
@@ -3331,6 +3400,11 @@ int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const aha_mm
   else q->params = aha_sampling_params{0.f, 1.f, 0, 1.f, 64, 0u, 299792458ull};   // ArgMax, no penalty: the device argmax
   q->max_new = max_new;
   q->top_logprobs = top_logprobs;
+  if (logit_adjust_active(adjust)) {   // copied: the caller's arrays need not outlive the call
+    q->bias_ids.assign(adjust->bias_ids, adjust->bias_ids + adjust->n_bias);
+    q->bias_vals.assign(adjust->bias_vals, adjust->bias_vals + adjust->n_bias);
+    q->adjust = aha_logit_adjust{adjust->presence_penalty, adjust->frequency_penalty, q->bias_ids.data(), q->bias_vals.data(), adjust->n_bias};
+  }
   q->npages = npages;
   q->toks.reserve(max_new);
   e->waiting.push_back(q);
@@ -3375,6 +3449,7 @@ static void engine_release(aha_engine* e, int s) {
   for (size_t i = pg.size(); i > 0; --i) e->free_pages.push_back(pg[i - 1]);
   pg.clear();
   e->slots[s] = nullptr;
+  e->ch.samplers[s].adj = LogitAdjust{};   // the slot's bias copy and count table go with the request
   delete q;
 }
 
@@ -3403,13 +3478,23 @@ static int engine_admit(aha_engine* e, EngReq* q, int s) {
     engine_release(e, s);
     return rc;
   }
-  const HostSampler& S = e->ch.samplers[s];
-  size_t need = 0;   // the penalty contexts of every slot's sampler
+  sampler_set_adjust(e->ch.samplers[s], &q->adjust);
+  size_t need = 0, need_adj = 0;   // the penalty contexts and the addend lists of every slot's sampler
   for (int k = 0; k < (int)e->max_running; ++k) {
     const EngReq* o = k == s ? q : e->slots[k];
     if (o && e->ch.samplers[k].repeat_penalty != 1.0f) need += std::min<size_t>(o->max_new, (size_t)e->ch.samplers[k].repeat_last_n);
+    if (o) need_adj += adjust_list_cap(e->ch.samplers[k], o->max_new, (size_t)m->desc.vocab_size);
   }
-  (void)S;
+  if (need_adj > e->adj_cap) {   // grow the addend buffers the same way (the stream has drained)
+    const size_t cap = std::max(need_adj, 2 * e->adj_cap);
+    GenChoice grown;
+    if ((rc = gen_choice_adj_alloc(e->bufs, cap, grown))) {
+      engine_release(e, s);
+      return rc;
+    }
+    e->ch.d_adj_id = grown.d_adj_id, e->ch.d_adj_val = grown.d_adj_val, e->ch.h_adj_id = grown.h_adj_id, e->ch.h_adj_val = grown.h_adj_val;
+    e->adj_cap = cap;
+  }
   if (need > e->ctx_cap) {   // grow the penalty-context buffers (the stream has drained)
     const size_t cap = std::max(need, 2 * e->ctx_cap);
     uint32_t *d = nullptr, *h = nullptr;

@@ -6,6 +6,8 @@
 
 #include <memory>
 #include <string>
+#include <utility>
+#include <vector>
 
 #include "../../include/aha_hip.h"
 
@@ -17,6 +19,17 @@ struct RngDeleter {
   void operator()(aha_rng* r) const { aha_hip_rng_destroy(r); }
 };
 
+// A request's aha_logit_adjust and its running state: the non-zero biases sorted by id, and the sorted (id, count) table of every
+// in-vocabulary token generated so far -- one entry inserted or bumped per emitted token, never rebuilt.
+struct LogitAdjust {
+  bool active = false;
+  float presence = 0.f, frequency = 0.f;
+  std::vector<uint32_t> bias_ids;
+  std::vector<float> bias_vals;
+  std::vector<std::pair<uint32_t, uint32_t>> counts;
+  size_t n_counted = 0;       // generated tokens already in `counts`
+};
+
 struct HostSampler {
   SampleKind kind = SAMPLE_ARGMAX;
   double temperature = 1.0;   // `temp as f64` of the request's f32
@@ -26,6 +39,7 @@ struct HostSampler {
   int64_t repeat_last_n = 64;
   std::unique_ptr<aha_rng, RngDeleter> rng;
   uint64_t words = 0;         // u32 handed out by rng
+  LogitAdjust adj;            // host_sampler_init leaves it inactive
 };
 
 // AHA_OK, or AHA_ERR_INVALID with *why set: NaN temperature / top_p, top_k < 1 with its flag, repeat_last_n < 0, repeat_penalty <= 0.
@@ -38,5 +52,21 @@ int sampler_candidates_needed(const HostSampler& s, size_t vocab_size);
 // aha_hip_sampler_pick
 int sampler_pick(HostSampler& s, const float* vals, const uint32_t* idx, int k, float max, float sumexp, const float* logits,
                  size_t vocab_size, const uint32_t* generated, size_t n_generated, uint32_t* token_out);
+
+
+// aha_logit_adjust: AHA_OK, or AHA_ERR_INVALID with *why set (a NaN / infinite penalty, n_bias > AHA_MAX_LOGIT_BIAS, null arrays, a
+// duplicate id, a NaN / +inf bias; with vocab_size > 0 also an id >= vocab_size and -inf on every id).  a == nullptr: inactive, fine.
+int logit_adjust_check(const aha_logit_adjust* a, size_t vocab_size, std::string* why);
+inline bool logit_adjust_active(const aha_logit_adjust* a) {
+  return a && (a->presence_penalty != 0.f || a->frequency_penalty != 0.f || a->n_bias > 0);
+}
+// a checked adjust (or nullptr) into the sampler: biases copied, counts emptied
+void sampler_set_adjust(HostSampler& s, const aha_logit_adjust* a);
+// counts brought up to generated[0 .. n_generated) (ids >= vocab_size ignored); no-op for an inactive adjust
+void sampler_adjust_sync(HostSampler& s, const uint32_t* generated, size_t n_generated, size_t vocab_size);
+// entries the step's addend list can have at most / the list itself, sorted by id, after sampler_adjust_sync: every id with a
+// non-zero bias or a count, a_i = (float)((double)b_i - (double)frequency * c_i - (double)presence * [c_i > 0]).  Returns its length.
+inline size_t sampler_adjust_bound(const HostSampler& s) { return s.adj.active ? s.adj.bias_ids.size() + s.adj.counts.size() : 0; }
+size_t sampler_adjust_list(const HostSampler& s, uint32_t* ids_out, float* vals_out);
 
 }  // namespace aha

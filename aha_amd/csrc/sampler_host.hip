@@ -152,6 +152,69 @@ int sampling_params_check(const aha_sampling_params& p, std::string* why) {
   return AHA_OK;
 }
 
+int logit_adjust_check(const aha_logit_adjust* a, size_t vocab_size, std::string* why) {
+  if (!a) return AHA_OK;
+  if (!isfinite(a->presence_penalty) || !isfinite(a->frequency_penalty)) return *why = "presence / frequency penalty must be finite", AHA_ERR_INVALID;
+  if (a->n_bias > AHA_MAX_LOGIT_BIAS) return *why = "n_bias above AHA_MAX_LOGIT_BIAS", AHA_ERR_INVALID;
+  if (a->n_bias && (!a->bias_ids || !a->bias_vals)) return *why = "null bias_ids / bias_vals with n_bias > 0", AHA_ERR_INVALID;
+  std::vector<uint32_t> ids(a->bias_ids, a->bias_ids + a->n_bias);
+  std::sort(ids.begin(), ids.end());
+  if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return *why = "duplicate bias id", AHA_ERR_INVALID;
+  size_t n_ninf = 0;
+  for (size_t i = 0; i < a->n_bias; ++i) {
+    const float b = a->bias_vals[i];
+    if (isnan(b) || b == INFINITY) return *why = "bias must be finite or -inf", AHA_ERR_INVALID;
+    if (vocab_size && a->bias_ids[i] >= vocab_size) return *why = "bias id " + std::to_string(a->bias_ids[i]) + " >= vocab_size", AHA_ERR_INVALID;
+    n_ninf += b == -INFINITY;
+  }
+  if (vocab_size && n_ninf >= vocab_size) return *why = "-inf bias on every id of the vocabulary", AHA_ERR_INVALID;
+  return AHA_OK;
+}
+
+void sampler_set_adjust(HostSampler& s, const aha_logit_adjust* a) {
+  LogitAdjust& A = s.adj;
+  A = LogitAdjust{};
+  if (!logit_adjust_active(a)) return;
+  A.active = true;
+  A.presence = a->presence_penalty;
+  A.frequency = a->frequency_penalty;
+  std::vector<uint32_t> o(a->n_bias);
+  std::iota(o.begin(), o.end(), 0u);
+  std::sort(o.begin(), o.end(), [&](uint32_t x, uint32_t y) { return a->bias_ids[x] < a->bias_ids[y]; });
+  for (uint32_t i : o)
+    if (a->bias_vals[i] != 0.f) A.bias_ids.push_back(a->bias_ids[i]), A.bias_vals.push_back(a->bias_vals[i]);
+}
+
+void sampler_adjust_sync(HostSampler& s, const uint32_t* generated, size_t n_generated, size_t vocab_size) {
+  LogitAdjust& A = s.adj;
+  if (!A.active) return;
+  if (n_generated < A.n_counted) A.counts.clear(), A.n_counted = 0;   // an external driver started over
+  for (; A.n_counted < n_generated; ++A.n_counted) {
+    const uint32_t t = generated[A.n_counted];
+    if (t >= vocab_size) continue;
+    auto it = std::lower_bound(A.counts.begin(), A.counts.end(), std::make_pair(t, 0u));
+    if (it != A.counts.end() && it->first == t) ++it->second;
+    else A.counts.insert(it, std::make_pair(t, 1u));
+  }
+}
+
+size_t sampler_adjust_list(const HostSampler& s, uint32_t* ids_out, float* vals_out) {
+  const LogitAdjust& A = s.adj;
+  if (!A.active) return 0;
+  size_t n = 0, b = 0, c = 0;
+  const size_t nb = A.bias_ids.size(), nc = A.counts.size();
+  while (b < nb || c < nc) {
+    const uint32_t ib = b < nb ? A.bias_ids[b] : 0xffffffffu, ic = c < nc ? A.counts[c].first : 0xffffffffu;
+    const uint32_t id = std::min(ib, ic);
+    double a = 0.0;
+    if (b < nb && ib == id) a = (double)A.bias_vals[b++];
+    if (c < nc && ic == id) a = a - (double)A.frequency * (double)A.counts[c++].second - (double)A.presence;
+    ids_out[n] = id;
+    vals_out[n++] = (float)a;
+  }
+  return n;
+}
+
 int host_sampler_init(HostSampler& s, const aha_sampling_params& p) {
   std::string why;
   if (sampling_params_check(p, &why)) {
@@ -162,6 +225,7 @@ int host_sampler_init(HostSampler& s, const aha_sampling_params& p) {
   if (int rc = aha_hip_rng_create(p.seed, &r)) return rc;
   s.rng.reset(r);
   s.words = 0;
+  s.adj = LogitAdjust{};
   // get_logit_processor (sample.rs:7-38): a temperature below 1e-7 means ArgMax whatever top_k / top_p say
   const bool has_t = !(p.temperature < 1e-7f), has_p = p.flags & AHA_SAMPLE_HAS_TOP_P, has_k = p.flags & AHA_SAMPLE_HAS_TOP_K;
   s.temperature = (double)p.temperature;
@@ -215,6 +279,14 @@ int sampler_pick(HostSampler& s, const float* vals, const uint32_t* idx, int k, 
     for (uint32_t t : ids)
       if (t < vocab_size) x[t] = x[t] >= 0.f ? x[t] / pen : x[t] * pen;
   }
+  if (s.adj.active) {   // the addends, after the penalty: one f32 add per listed id
+    sampler_adjust_sync(s, generated, n_generated, vocab_size);
+    std::vector<uint32_t> ids(sampler_adjust_bound(s));
+    std::vector<float> a(ids.size());
+    const size_t n = sampler_adjust_list(s, ids.data(), a.data());
+    for (size_t i = 0; i < n; ++i)
+      if (ids[i] < vocab_size) x[ids[i]] = x[ids[i]] + a[i];
+  }
   return pick_from_logits(s, x, token_out);
 }
 
@@ -251,7 +323,9 @@ int aha_hip_sampler_plan(const aha_sampler* s, size_t vocab_size, size_t n_gener
   size_t n_ctx;
   sampler_penalty_context(s->s, n_generated, &pen, &n_ctx);
   const bool argmax = s->s.kind == SAMPLE_ARGMAX;
-  *k_out = argmax ? (pen != 1.0f ? 1 : 0) : sampler_candidates_needed(s->s, vocab_size);
+  // an addend is live once the adjust has a non-zero bias or a token has been generated
+  const bool live = s->s.adj.active && (!s->s.adj.bias_ids.empty() || n_generated > 0);
+  *k_out = argmax ? (pen != 1.0f || live ? 1 : 0) : sampler_candidates_needed(s->s, vocab_size);
   if (temperature_out) *temperature_out = argmax ? 0.f : (float)s->s.temperature;
   if (repeat_penalty_out) *repeat_penalty_out = pen;
   if (n_context_out) *n_context_out = n_ctx;
@@ -268,6 +342,52 @@ int aha_hip_sampler_pick(aha_sampler* s, const float* vals, const uint32_t* idx,
     return sampler_pick(s->s, vals, idx, k, max, sumexp, logits, vocab_size, generated, n_generated, token_out);
   } catch (const std::bad_alloc&) {
     set_error("sampler_pick: out of host memory");
+    return AHA_ERR_OOM;
+  }
+}
+
+int aha_hip_sampler_set_adjust(aha_sampler* s, const aha_logit_adjust* adjust) {
+  if (!s) {
+    set_error("sampler_set_adjust: null sampler");
+    return AHA_ERR_INVALID;
+  }
+  try {
+    std::string why;
+    if (logit_adjust_check(adjust, 0, &why)) {
+      set_error("sampler_set_adjust: " + why);
+      return AHA_ERR_INVALID;
+    }
+    sampler_set_adjust(s->s, adjust);
+    return AHA_OK;
+  } catch (const std::bad_alloc&) {
+    set_error("sampler_set_adjust: out of host memory");
+    return AHA_ERR_OOM;
+  }
+}
+
+int aha_hip_sampler_adjust_list(aha_sampler* s, size_t vocab_size, const uint32_t* generated, size_t n_generated, uint32_t* ids_out,
+                                float* vals_out, size_t cap, size_t* n_out) {
+  if (!s || !n_out || vocab_size == 0 || (n_generated && !generated)) {
+    set_error("sampler_adjust_list: bad argument");
+    return AHA_ERR_INVALID;
+  }
+  try {
+    sampler_adjust_sync(s->s, generated, n_generated, vocab_size);
+    const size_t bound = sampler_adjust_bound(s->s);
+    std::vector<uint32_t> ids(bound);
+    std::vector<float> a(bound);
+    size_t n = sampler_adjust_list(s->s, ids.data(), a.data()), k = 0;
+    for (size_t i = 0; i < n; ++i)   // a bias id the vocabulary does not have (set_adjust cannot know it) is dropped
+      if (ids[i] < vocab_size) ids[k] = ids[i], a[k++] = a[i];
+    *n_out = k;
+    if (k > cap || (k && (!ids_out || !vals_out))) {
+      set_error("sampler_adjust_list: room for " + std::to_string(cap) + " entries, the list has " + std::to_string(k));
+      return AHA_ERR_INVALID;
+    }
+    if (k) memcpy(ids_out, ids.data(), k * 4), memcpy(vals_out, a.data(), k * 4);
+    return AHA_OK;
+  } catch (const std::bad_alloc&) {
+    set_error("sampler_adjust_list: out of host memory");
     return AHA_ERR_OOM;
   }
 }

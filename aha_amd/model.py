@@ -445,6 +445,50 @@ class HipInferenceModel:
         out = [None if top[j] < 0 else [_token_logprobs(lp[j * int(max_new) + t]) for t in range(len(toks[j]))] for j in range(n)]
         return (toks, out, res[1]) if want_step_logits else (toks, out)
 
+    def generate_batch_adjusted(self, prompts: Sequence[Sequence[int]], max_new: int, params=None, top_logprobs=None, data=None,
+                                max_tokens_per_pass: int = 0, want_step_logits: bool = False):
+        """generate_batch_logprobs whose sampling.SamplingParams also carry logit_bias / presence_penalty / frequency_penalty
+        (aha_hip_generate_batch_adjusted; include/aha_hip.h states the definition).  params: None = greedy without any adjust, one
+        SamplingParams for all, or one per prompt.  top_logprobs: None = no logprobs at all, else as generate_batch_logprobs.  Returns
+        (token lists, logprobs or None[, step logits])."""
+        n = len(prompts)
+        if data is not None and len(data) != n:
+            raise ValueError(f"{len(data)} MultiModalData entries for {n} prompts")
+        from .sampling import SamplingParams
+        plist = None if params is None else [params] * n if isinstance(params, SamplingParams) else list(params)
+        cp = None if plist is None else _sampling_array(plist, n)
+        keep, adj = [], None
+        if plist is not None:
+            adj = (_lib.LogitAdjust * max(n, 1))()
+            for j, p in enumerate(plist):
+                adj[j], k = p.adjust_to_c()
+                keep.append(k)
+        top = None
+        if top_logprobs is not None:
+            tops = [top_logprobs] * n if isinstance(top_logprobs, (int, np.integer)) else list(top_logprobs)
+            if len(tops) != n:
+                raise ValueError(f"{len(tops)} top_logprobs entries for {n} prompts")
+            top = np.ascontiguousarray(np.asarray([-1 if t is None else int(t) for t in tops] + [0], dtype=np.int32))
+        mm_arr = None
+        if data is not None:
+            mm_arr = (C.c_void_p * max(n, 1))()
+            for j, d in enumerate(data):
+                if d is not None:
+                    mm, k = _mm_input(d)
+                    keep += [mm, k]
+                    mm_arr[j] = C.addressof(mm)
+        lp = None if top is None else (_lib.TokenLogprobs * max(n * max(int(max_new), 1), 1))()
+
+        def entry(handle, ids, lens, n_, mm_, cp_, mx, pas, toks, n_out, lg):
+            return lib().aha_hip_generate_batch_adjusted(handle, ids, lens, n_, mm_, cp_, adj, None if top is None else top.ctypes.data, mx, pas,
+                                                         toks, n_out, lg, lp)
+        res = self._generate_batch(entry, prompts, (mm_arr, cp), max_new, max_tokens_per_pass, "step" if want_step_logits else None)
+        toks = res[0] if want_step_logits else res
+        out = None
+        if top is not None:
+            out = [None if top[j] < 0 else [_token_logprobs(lp[j * int(max_new) + t]) for t in range(len(toks[j]))] for j in range(n)]
+        return (toks, out, res[1]) if want_step_logits else (toks, out)
+
     def generate_batch_spec(self, prompts: Sequence[Sequence[int]], max_new: int, spec=None, predictions=None, want_logits: bool = False,
                             want_stats: bool = False, max_tokens_per_pass: int = 0):
         """generate_batch with draft-and-verify decoding (aha_hip_generate_batch_spec): the same tokens and logits, bit for bit, in fewer
@@ -651,7 +695,12 @@ class HipEngine:
             mm_p = C.byref(mm)
         cp = None if params is None else C.byref(params.to_c())
         rid = C.c_uint64()
-        if top_logprobs is None:
+        if params is not None and getattr(params, "adjust_active", False):   # logit_bias / presence / frequency: the arrays are copied
+            adj, k = params.adjust_to_c()
+            check(lib().aha_hip_engine_submit_adjusted(self.handle, ids.ctypes.data, ids.size, mm_p, cp, C.byref(adj), int(max_new),
+                                                       -1 if top_logprobs is None else int(top_logprobs), C.byref(rid)))
+            del k
+        elif top_logprobs is None:
             check(lib().aha_hip_engine_submit(self.handle, ids.ctypes.data, ids.size, mm_p, cp, int(max_new), C.byref(rid)))
         else:
             check(lib().aha_hip_engine_submit_logprobs(self.handle, ids.ctypes.data, ids.size, mm_p, cp, int(max_new), int(top_logprobs),

@@ -345,6 +345,32 @@ def sample_rows(logits: torch.Tensor, k, temperature, repeat_penalty, contexts):
     return vals, idx, ms
 
 
+def sample_rows_adjusted(logits: torch.Tensor, k, temperature, repeat_penalty, contexts, adjusts):
+    """sample_rows with addends (aha_hip_sample_rows_adjusted): adjusts[r] = (ids, vals) -- vals[i] (finite or -inf) is added, in f32, to the
+    penalised logit of the distinct ids[i] < V of row r, in any order; an empty pair gives the row sample_rows gives it.  The rows may
+    have a pitch above V."""
+    if not logits.is_cuda:
+        raise ValueError("op inputs must be GPU tensors")
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.stride(0) >= logits.shape[1]   # (a row pitch)
+    R, V = logits.shape
+    assert len(adjusts) == R
+    kk = np.ascontiguousarray(np.asarray(k, dtype=np.int32).reshape(R))
+    tt = np.ascontiguousarray(np.asarray(temperature, dtype=np.float32).reshape(R))
+    pp = np.ascontiguousarray(np.asarray(repeat_penalty, dtype=np.float32).reshape(R))
+    off = np.ascontiguousarray(np.cumsum([0] + [len(c) for c in contexts]), dtype=np.uint64)
+    ctx = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.uint32).reshape(-1) for c in contexts] + [np.zeros(1, np.uint32)]))
+    aoff = np.ascontiguousarray(np.cumsum([0] + [len(a[0]) for a in adjusts]), dtype=np.uint64)
+    aid = np.ascontiguousarray(np.concatenate([np.asarray(a[0], dtype=np.uint32).reshape(-1) for a in adjusts] + [np.zeros(1, np.uint32)]))
+    aval = np.ascontiguousarray(np.concatenate([np.asarray(a[1], dtype=np.float32).reshape(-1) for a in adjusts] + [np.zeros(1, np.float32)]))
+    vals = torch.empty(R, 64, dtype=torch.float32, device=logits.device)
+    idx = torch.empty(R, 64, dtype=torch.int32, device=logits.device)
+    ms = torch.empty(R, 2, dtype=torch.float32, device=logits.device)
+    check(lib().aha_hip_sample_rows_adjusted(_ptr(logits), logits.stride(0), R, V, kk.ctypes.data, tt.ctypes.data, pp.ctypes.data,
+                                             ctx.ctypes.data, off.ctypes.data, aid.ctypes.data, aval.ctypes.data, aoff.ctypes.data, _ptr(vals),
+                                             _ptr(idx), _ptr(ms), _stream()))
+    return vals, idx, ms
+
+
 def logprob_rows(logits: torch.Tensor, tokens, n_top):
     """aha_hip_logprob_rows: the per-token log-probability pass over every row of logits (R, V) f32 (row pitch logits.stride(0)): row r's
     emitted token tokens[r] and its n_top[r] (0..20; an int: the same for every row) most likely tokens.  The logits are only read.

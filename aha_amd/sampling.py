@@ -15,7 +15,7 @@ here (forward_* already returns the arg-max token).
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import ctypes as C
 
@@ -178,6 +178,10 @@ class GenerationContext:
         self.seqlen_offset = 0
         self.seq_len = initial_seq_len
         self.sample_len = max_tokens
+        # logit_bias / presence / frequency (SamplingParams.context sets them; the reference declares the fields and never reads them)
+        self.presence_penalty = 0.0
+        self.frequency_penalty = 0.0
+        self.logit_bias: Dict[int, float] = {}
 
 
 def penalty_context(repeat_penalty: float, repeat_last_n: Optional[int], generated: Sequence[int]) -> Tuple[float, Sequence[int]]:
@@ -187,6 +191,28 @@ def penalty_context(repeat_penalty: float, repeat_last_n: Optional[int], generat
     start_at = 0 if repeat_last_n is None else max(len(generated) - repeat_last_n, 0)
     ids = generated[start_at:]
     return (float(repeat_penalty), ids) if len(ids) else (1.0, [])
+
+
+def logit_addends(presence_penalty: float, frequency_penalty: float, logit_bias: Optional[Dict[int, float]], generated: Sequence[int],
+                  vocab_size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The step's sorted (ids, f32 addends) of include/aha_hip.h's aha_logit_adjust definition: every id with a non-zero bias or a
+    count c_i > 0 over ALL generated tokens (ids >= vocab_size ignored), a_i = f32(f64(b_i) - f64(frequency) * c_i - f64(presence));
+    the penalties and biases are the f32 values the C struct carries."""
+    bias = {int(i): np.float32(b) for i, b in (logit_bias or {}).items() if np.float32(b) != 0 and 0 <= int(i) < vocab_size}
+    counts: Dict[int, int] = {}
+    for t in generated:
+        if 0 <= int(t) < vocab_size:
+            counts[int(t)] = counts.get(int(t), 0) + 1
+    ids = sorted(set(bias) | set(counts))
+    fp, pp = np.float64(np.float32(frequency_penalty)), np.float64(np.float32(presence_penalty))
+    vals = []
+    with np.errstate(invalid="ignore", over="ignore"):
+        for i in ids:
+            a = np.float64(bias.get(i, np.float32(0.0)))
+            if i in counts:
+                a = a - fp * np.float64(counts[i]) - pp
+            vals.append(np.float32(a))
+    return np.asarray(ids, dtype=np.uint32), np.asarray(vals, dtype=np.float32)
 
 
 def draw_from_candidates(lp: "LogitsProcessor", w: np.ndarray, idx: np.ndarray) -> int:
@@ -207,10 +233,12 @@ def sample_and_push(ctx: GenerationContext, model, argmax_token: int, generated:
     lp = ctx.logit_processor
     pen, pctx = penalty_context(ctx.repeat_penalty, ctx.repeat_last_n, generated)
     V = model.text_cfg.vocab_size
-    if lp.sampling.kind == "ArgMax" and pen == 1.0:
+    adjusted = bool(getattr(ctx, "presence_penalty", 0.0) or getattr(ctx, "frequency_penalty", 0.0) or getattr(ctx, "logit_bias", None))
+    if lp.sampling.kind == "ArgMax" and pen == 1.0 and not adjusted:
         token = int(argmax_token)
     else:
-        k = 1 if lp.sampling.kind == "ArgMax" else lp.candidates_needed(V)
+        # the single-sequence candidate step knows no addends: an adjusted request takes the full vector
+        k = 0 if adjusted else 1 if lp.sampling.kind == "ArgMax" else lp.candidates_needed(V)
         token = None
         if k:
             vals, idx, mx, se = model.sample_candidates(pctx, pen, lp.sampling.temperature if lp.sampling.kind != "ArgMax" else 0.0, k)
@@ -228,6 +256,10 @@ def sample_and_push(ctx: GenerationContext, model, argmax_token: int, generated:
                     if t not in seen and 0 <= t < V:
                         logits[t] = logits[t] / np.float32(pen) if logits[t] >= 0 else logits[t] * np.float32(pen)
                     seen.add(t)
+            if adjusted:   # after the penalty: one f32 add per listed id
+                a_ids, a_vals = logit_addends(ctx.presence_penalty, ctx.frequency_penalty, ctx.logit_bias, generated, V)
+                logits = np.asarray(logits, dtype=np.float32)
+                logits[a_ids] = logits[a_ids] + a_vals
             w, ids = lp.weights_from_logits(logits)
             pos = lp.draw(w)
             token = pos if ids is None else int(ids[pos])
@@ -397,6 +429,23 @@ class SamplingParams:
     repeat_penalty: Optional[float] = None
     repeat_last_n: int = 64
     seed: int = 299792458
+    # the chat request's presence_penalty / frequency_penalty / logit_bias (aha_logit_adjust); inactive by default
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: Optional[Dict[int, float]] = None
+
+    @property
+    def adjust_active(self) -> bool:
+        return bool(self.presence_penalty != 0 or self.frequency_penalty != 0 or self.logit_bias)
+
+    def adjust_to_c(self):
+        """(aha_logit_adjust, the arrays it points into -- keep them alive for as long as the struct is used)."""
+        from ._lib import LogitAdjust
+        ids = np.asarray(list((self.logit_bias or {}).keys()), dtype=np.uint32)
+        vals = np.asarray(list((self.logit_bias or {}).values()), dtype=np.float32)
+        adj = LogitAdjust(float(self.presence_penalty), float(self.frequency_penalty), ids.ctypes.data_as(C.POINTER(C.c_uint32)),
+                          vals.ctypes.data_as(C.POINTER(C.c_float)), ids.size)
+        return adj, (ids, vals)
 
     def to_c(self):
         from ._lib import AHA_SAMPLE_HAS_TOP_K, AHA_SAMPLE_HAS_TOP_P, SamplingParams as CParams
@@ -407,5 +456,8 @@ class SamplingParams:
 
     def context(self, initial_seq_len: int, max_tokens: int) -> GenerationContext:
         """The single-sequence GenerationContext of the same request (generate_generic_sampled)."""
-        return GenerationContext(self.temperature, self.top_p, self.top_k, self.repeat_penalty, self.repeat_last_n, self.seed,
-                                 initial_seq_len, max_tokens)
+        ctx = GenerationContext(self.temperature, self.top_p, self.top_k, self.repeat_penalty, self.repeat_last_n, self.seed,
+                                initial_seq_len, max_tokens)
+        ctx.presence_penalty, ctx.frequency_penalty = float(self.presence_penalty), float(self.frequency_penalty)
+        ctx.logit_bias = dict(self.logit_bias or {})
+        return ctx

@@ -378,8 +378,8 @@ int aha_hip_engine_debug_ctr_base(aha_engine* e, uint32_t base);
  * unspecified.
  * Cost: two small launches per step that has a logprob row (profile classes logprob_rows_stage1 / logprob_rows_stage2) and 168 bytes
  * per token in the copy that ends the step anyway; a step without such a row takes the path it took before.
- * Out of scope: logprobs of prompt tokens (`echo`), logprobs in aha_hip_generate_batch_spec, tensor-parallel models, `logit_bias` and
- * the presence / frequency penalties. */
+ * Out of scope: logprobs of prompt tokens (`echo`), logprobs in aha_hip_generate_batch_spec, tensor-parallel models.  `logit_bias` and
+ * the presence / frequency penalties (aha_logit_adjust below) change the token choice, never these log-probabilities. */
 #define AHA_MAX_TOP_LOGPROBS 20
 typedef struct aha_token_logprobs {
   float    logprob;                              /* lp(emitted token) */
@@ -431,6 +431,56 @@ int aha_hip_sampler_plan(const aha_sampler* s, size_t vocab_size, size_t n_gener
 int aha_hip_sampler_pick(aha_sampler* s, const float* vals, const uint32_t* idx, int32_t k, float max, float sumexp, const float* logits,
                          size_t vocab_size, const uint32_t* generated, size_t n_generated, uint32_t* token_out);
 uint64_t aha_hip_sampler_rng_words(const aha_sampler* s);
+
+/* ---- logit_bias, presence_penalty, frequency_penalty ------------------------------------------------------------------------
+ * The chat request's three remaining sampling fields (src/params/chat.rs:75-81,109-112 of the reference, which declares and never
+ * reads them).  Definition, for one request with generated tokens g[0..t) and the step's V f32 logits x (what step_logits_out reports):
+ *   1. y = x after the repeat penalty (unchanged: distinct ids of the last repeat_last_n generated tokens, / if >= 0 else *).
+ *   2. c_i = occurrences of id i in ALL of g[0..t) (not windowed; ids >= V ignored; prompt tokens are not counted).  The addend of id i is
+ *      a_i = (float)((double)b_i - (double)frequency_penalty * c_i - (double)presence_penalty * [c_i > 0]), computed on the host in f64
+ *      and rounded once; b_i is the request's bias for i (0 if none).  Ids with b_i == 0 and c_i == 0 have no addend.
+ *   3. z_i = y_i + a_i, one f32 add (ids without an addend: z_i = y_i).  A b_i of -inf gives z_i = -inf: the token is never chosen.
+ *   4. The request's sampler runs on z wherever it ran on y: argmax (first maximal index), the candidates, their max and sumexp over
+ *      the whole vocabulary, the top-p cut, the draw.  RNG consumption per token is unchanged.
+ *   5. Logprobs keep their definition: the model's own distribution, from the raw x.
+ * The first token has every c_i = 0: only the bias applies.  A sparse token ban is a bias of -inf.
+ * An adjust is INACTIVE when both penalties are 0 and n_bias == 0; a NULL adjust pointer means inactive.  A row / step without a live
+ * addend launches and copies exactly what it did before; one with addends takes the candidate step (k = 1 for ArgMax), whose stage 1
+ * finds each wave's slice of the row's sorted (id, addend) list by binary search -- the list (8 bytes per entry) is uploaded with the
+ * step's row table.
+ * Errors, AHA_ERR_INVALID before any device work, naming the sequence: a NaN or infinite penalty, n_bias > AHA_MAX_LOGIT_BIAS, a null
+ * array with n_bias > 0, a bias id >= vocab_size, a duplicate id, a NaN or +inf bias, -inf biases on every id of the vocabulary.
+ * Out of scope: the single-sequence aha_hip_sample_candidates path; aha_hip_generate_batch_spec; dense allowed-token masks and
+ * grammars; the repeat penalty's own context walk in stage 1, which is unchanged. */
+#define AHA_MAX_LOGIT_BIAS 1024
+typedef struct aha_logit_adjust {
+  float presence_penalty;    /* 0 = off; finite */
+  float frequency_penalty;   /* 0 = off; finite */
+  const uint32_t* bias_ids;  /* n_bias distinct ids < vocab_size, any order */
+  const float* bias_vals;    /* finite or -inf */
+  size_t n_bias;             /* <= AHA_MAX_LOGIT_BIAS */
+} aha_logit_adjust;          /* 32 bytes */
+/* aha_hip_generate_batch_logprobs plus `adjust`: HOST, n_seqs entries (NULL: all inactive).  top_logprobs and logprobs_out may both be
+ * NULL (no logprobs); params NULL still means greedy.  With every adjust inactive: tokens, step logits, logprobs and launches are those
+ * of aha_hip_generate_batch_logprobs.  Everything else (models, pages, cache clearing, errors) is aha_hip_generate_batch_logprobs's. */
+int aha_hip_generate_batch_adjusted(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs,
+                                    const aha_mm_input* const* mm, const aha_sampling_params* params, const aha_logit_adjust* adjust,
+                                    const int32_t* top_logprobs, size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out,
+                                    size_t* n_out, float* step_logits_out, aha_token_logprobs* logprobs_out);
+/* aha_hip_engine_submit_logprobs plus the request's adjust (NULL: inactive; its arrays are copied).  top_logprobs -1: none.  Requests of
+ * all three submit functions share an engine and a step; aha_hip_engine_step and aha_hip_engine_step_logprobs are unchanged. */
+int aha_hip_engine_submit_adjusted(aha_engine* e, const uint32_t* input_ids, size_t n_ids, const aha_mm_input* mm,
+                                   const aha_sampling_params* params, const aha_logit_adjust* adjust, size_t max_new, int32_t top_logprobs,
+                                   uint64_t* req_id);
+/* The host sampler with an adjust (NULL or inactive: none): it keeps a copy and the running counts, which follow the `generated`
+ * arrays later calls pass.  Errors as above, except those that need a vocabulary.  aha_hip_sampler_plan then returns k_out = 1 for an
+ * ArgMax sampler while an addend is live (a non-zero bias, or any generated token); aha_hip_sampler_pick adds the addends in its
+ * full-vector path, after its own penalty -- candidates passed to it must come from aha_hip_sample_rows_adjusted with the step's list.
+ * aha_hip_sampler_adjust_list: that list after `generated[0 .. n_generated)`, sorted by id: *n_out entries into ids_out / vals_out
+ * (AHA_ERR_INVALID, with *n_out set, if cap is too small; at most n_bias + the distinct generated ids). */
+int aha_hip_sampler_set_adjust(aha_sampler* s, const aha_logit_adjust* adjust);
+int aha_hip_sampler_adjust_list(aha_sampler* s, size_t vocab_size, const uint32_t* generated, size_t n_generated, uint32_t* ids_out,
+                                float* vals_out, size_t cap, size_t* n_out);
 
 /* ---- checkpoint directory -> model (XxxGenerateModel::init minus tokenizer / chat template) --------------------------
  * aha_hip_config_parse: <dir>/config.json -> aha_model_desc, the same field mapping serde does into Qwen3Config
@@ -706,6 +756,13 @@ int aha_hip_sample_rows(const float* logits, int64_t ld, int32_t R, int32_t V, c
  * AHA_ERR_INVALID for R < 1, V < 1, ld < V, a null pointer or an n_top outside 0 .. 20, checked before anything touches the device. */
 int aha_hip_logprob_rows(const float* logits, int64_t ld, int32_t R, int32_t V, const uint32_t* tokens, const int32_t* n_top,
                          aha_token_logprobs* out, void* stream);
+/* aha_hip_sample_rows plus addends: adj_ids / adj_vals / adj_offsets are HOST; row r adds adj_vals[i] (finite or -inf) to the penalised
+ * logit of adj_ids[i] for i in [adj_offsets[r], adj_offsets[r + 1]) -- ids distinct and < V, in any order (AHA_ERR_INVALID otherwise).
+ * A row with no entries gives bit-identical outputs to aha_hip_sample_rows; a row whose every logit ends at -inf is unspecified. */
+int aha_hip_sample_rows_adjusted(const float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* k, const float* temperature,
+                                 const float* repeat_penalty, const uint32_t* context, const size_t* context_offsets,
+                                 const uint32_t* adj_ids, const float* adj_vals, const size_t* adj_offsets, float* vals_out,
+                                 uint32_t* idx_out, float* ms_out, void* stream);
 /* D7 prefill attention, causal with q position i attending to k positions <= kv_offset + i; q (S, nh*d),
  * k/v (L, kvh*d) token-major, L = kv_offset + S.  causal = 0 gives full (ViT / audio encoder) attention.  d = 128, or 64 with
  * nh == kvh (the Qwen3-ASR audio encoder's geometry). */

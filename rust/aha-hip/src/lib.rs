@@ -167,6 +167,25 @@ pub mod sys {
         }
     }
 
+    pub const AHA_MAX_LOGIT_BIAS: usize = 1024;
+
+    /// `aha_logit_adjust`: a request's `presence_penalty`, `frequency_penalty` and `logit_bias` (ids / values, `n_bias` of them; a value
+    /// of -inf bans the token).  Both penalties 0 and `n_bias` 0: inactive.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug)]
+    pub struct AhaLogitAdjust {
+        pub presence_penalty: f32,
+        pub frequency_penalty: f32,
+        pub bias_ids: *const u32,
+        pub bias_vals: *const f32,
+        pub n_bias: usize,
+    }
+    impl Default for AhaLogitAdjust {
+        fn default() -> Self {
+            Self { presence_penalty: 0.0, frequency_penalty: 0.0, bias_ids: std::ptr::null(), bias_vals: std::ptr::null(), n_bias: 0 }
+        }
+    }
+
     /// `aha_spec_stats`
     #[repr(C)]
     #[derive(Clone, Copy, Debug, Default)]
@@ -351,6 +370,22 @@ pub mod sys {
             step_logits_out: *mut f32,
             logprobs_out: *mut AhaTokenLogprobs,
         ) -> i32;
+        pub fn aha_hip_generate_batch_adjusted(
+            m: *mut AhaModel,
+            ids: *const u32,
+            seq_lens: *const usize,
+            n_seqs: usize,
+            mm: *const *const AhaMmInput,
+            params: *const AhaSamplingParams,
+            adjust: *const AhaLogitAdjust,
+            top_logprobs: *const i32,
+            max_new: usize,
+            max_tokens_per_pass: usize,
+            tokens_out: *mut u32,
+            n_out: *mut usize,
+            step_logits_out: *mut f32,
+            logprobs_out: *mut AhaTokenLogprobs,
+        ) -> i32;
         pub fn aha_hip_generate_batch_spec(
             m: *mut AhaModel,
             ids: *const u32,
@@ -399,6 +434,17 @@ pub mod sys {
             top_logprobs: i32,
             req_id: *mut u64,
         ) -> i32;
+        pub fn aha_hip_engine_submit_adjusted(
+            e: *mut AhaEngine,
+            ids: *const u32,
+            n_ids: usize,
+            mm: *const AhaMmInput,
+            params: *const AhaSamplingParams,
+            adjust: *const AhaLogitAdjust,
+            max_new: usize,
+            top_logprobs: i32,
+            req_id: *mut u64,
+        ) -> i32;
         pub fn aha_hip_engine_cancel(e: *mut AhaEngine, req_id: u64) -> i32;
         pub fn aha_hip_engine_step(e: *mut AhaEngine, ev: *mut AhaEngineEvent, cap: usize, n_ev: *mut usize, logits_out: *mut f32) -> i32;
         pub fn aha_hip_engine_step_logprobs(
@@ -435,6 +481,35 @@ pub mod sys {
             idx_out: *mut u32,
             ms_out: *mut f32,
             stream: *mut c_void,
+        ) -> i32;
+        pub fn aha_hip_sample_rows_adjusted(
+            logits: *const f32,
+            ld: i64,
+            rows: i32,
+            vocab: i32,
+            k: *const i32,
+            temperature: *const f32,
+            repeat_penalty: *const f32,
+            context: *const u32,
+            context_offsets: *const usize,
+            adj_ids: *const u32,
+            adj_vals: *const f32,
+            adj_offsets: *const usize,
+            vals_out: *mut f32,
+            idx_out: *mut u32,
+            ms_out: *mut f32,
+            stream: *mut c_void,
+        ) -> i32;
+        pub fn aha_hip_sampler_set_adjust(s: *mut AhaSampler, adjust: *const AhaLogitAdjust) -> i32;
+        pub fn aha_hip_sampler_adjust_list(
+            s: *mut AhaSampler,
+            vocab_size: usize,
+            generated: *const u32,
+            n_generated: usize,
+            ids_out: *mut u32,
+            vals_out: *mut f32,
+            cap: usize,
+            n_out: *mut usize,
         ) -> i32;
         pub fn aha_hip_sampler_create(params: *const AhaSamplingParams, out: *mut *mut AhaSampler) -> i32;
         pub fn aha_hip_sampler_destroy(s: *mut AhaSampler);
@@ -538,6 +613,29 @@ pub enum MmInput<'a> {
 /// `samples` and `out` must be device buffers of at least the sizes above, `stream` a HIP stream of their device or null.
 pub unsafe fn logmel_batch(samples: *const f32, n_samples: &[i64], out: *mut f32, stream: *mut std::ffi::c_void) -> Result<(), Error> {
     check(sys::aha_hip_logmel_batch(samples, n_samples.as_ptr(), n_samples.len(), out, stream))
+}
+
+/// A request's `logit_bias` (`bias_ids[i]` -> `bias_vals[i]`; -inf bans the token), `presence_penalty` and `frequency_penalty`
+/// (aha_logit_adjust).  `Default` is the inactive adjust.  A server maps the chat request's `logit_bias: {"id": bias}` object by
+/// parsing each key as a token id.
+#[derive(Clone, Debug, Default)]
+pub struct LogitAdjust {
+    pub presence_penalty: f32,
+    pub frequency_penalty: f32,
+    pub bias_ids: Vec<u32>,
+    pub bias_vals: Vec<f32>,
+}
+impl LogitAdjust {
+    /// The C view; it borrows the two vectors (an entry without its value is left out).
+    pub fn as_c(&self) -> sys::AhaLogitAdjust {
+        sys::AhaLogitAdjust {
+            presence_penalty: self.presence_penalty,
+            frequency_penalty: self.frequency_penalty,
+            bias_ids: self.bias_ids.as_ptr(),
+            bias_vals: self.bias_vals.as_ptr(),
+            n_bias: self.bias_ids.len().min(self.bias_vals.len()),
+        }
+    }
 }
 
 pub struct Model {
@@ -944,6 +1042,63 @@ impl Model {
         Ok((tokens, logprobs))
     }
 
+    /// `generate_batch_logprobs` plus one `LogitAdjust` per request (aha_hip_generate_batch_adjusted): `logit_bias`, `presence_penalty`
+    /// and `frequency_penalty` as include/aha_hip.h defines them.  `top_logprobs` None: no logprobs at all (the second result is empty).
+    pub fn generate_batch_adjusted(
+        &mut self,
+        prompts: &[&[u32]],
+        params: Option<&[sys::AhaSamplingParams]>,
+        adjust: &[LogitAdjust],
+        top_logprobs: Option<&[Option<u32>]>,
+        max_new: usize,
+        max_tokens_per_pass: usize,
+    ) -> Result<(Vec<Vec<u32>>, Vec<Vec<sys::AhaTokenLogprobs>>), Error> {
+        if adjust.len() != prompts.len() || top_logprobs.map_or(false, |t| t.len() != prompts.len()) {
+            return Err(Error { code: -1, message: format!("adjust / top_logprobs entries do not match {} prompts", prompts.len()) });
+        }
+        if let Some(p) = params {
+            if p.len() != prompts.len() {
+                return Err(Error { code: -1, message: format!("{} sampling params for {} prompts", p.len(), prompts.len()) });
+            }
+        }
+        let adj: Vec<sys::AhaLogitAdjust> = adjust.iter().map(|a| a.as_c()).collect();
+        let top: Option<Vec<i32>> = top_logprobs.map(|t| t.iter().map(|t| t.map_or(-1, |n| n as i32)).collect());
+        let ids: Vec<u32> = prompts.iter().flat_map(|s| s.iter().copied()).collect();
+        let lens: Vec<usize> = prompts.iter().map(|s| s.len()).collect();
+        let width = max_new.max(1);
+        let mut toks = vec![0u32; prompts.len() * width];
+        let mut n_out = vec![0usize; prompts.len()];
+        let mut lps = vec![sys::AhaTokenLogprobs::default(); if top.is_some() { prompts.len() * width } else { 0 }];
+        check(unsafe {
+            sys::aha_hip_generate_batch_adjusted(
+                self.model,
+                ids.as_ptr(),
+                lens.as_ptr(),
+                lens.len(),
+                std::ptr::null(),
+                params.map_or(std::ptr::null(), |p| p.as_ptr()),
+                adj.as_ptr(),
+                top.as_ref().map_or(std::ptr::null(), |t| t.as_ptr()),
+                max_new,
+                max_tokens_per_pass,
+                toks.as_mut_ptr(),
+                n_out.as_mut_ptr(),
+                std::ptr::null_mut(),
+                if top.is_some() { lps.as_mut_ptr() } else { std::ptr::null_mut() },
+            )
+        })?;
+        let tokens = n_out.iter().enumerate().map(|(j, &n)| toks[j * max_new..j * max_new + n].to_vec()).collect();
+        let logprobs = n_out
+            .iter()
+            .enumerate()
+            .map(|(j, &n)| match &top {
+                Some(t) if t[j] >= 0 => lps[j * max_new..j * max_new + n].to_vec(),
+                _ => Vec::new(),
+            })
+            .collect();
+        Ok((tokens, logprobs))
+    }
+
     /// The greedy loop of `generate_generic` / `generate_stream_generic` (common/generate.rs:115-159, 161-368) kept on the
     /// device in chunks of `chunk` tokens: `on_token` sees every token in order (what a streaming response forwards) and
     /// returns `false` to stop; an eos id stops after it has been delivered, as in the reference.
@@ -1050,6 +1205,33 @@ impl<'a> Engine<'a> {
         let p = params.map_or(std::ptr::null(), |p| p as *const _);
         check(unsafe {
             sys::aha_hip_engine_submit_logprobs(self.e, ids.as_ptr(), ids.len(), std::ptr::null(), p, max_new, top_logprobs as i32, &mut id)
+        })?;
+        Ok(id)
+    }
+    /// `submit_logprobs` plus the request's `LogitAdjust` (copied by the library); `top_logprobs` None: no logprobs.
+    pub fn submit_adjusted(
+        &mut self,
+        ids: &[u32],
+        params: Option<&sys::AhaSamplingParams>,
+        adjust: &LogitAdjust,
+        max_new: usize,
+        top_logprobs: Option<u32>,
+    ) -> Result<u64, Error> {
+        let mut id = 0u64;
+        let p = params.map_or(std::ptr::null(), |p| p as *const _);
+        let a = adjust.as_c();
+        check(unsafe {
+            sys::aha_hip_engine_submit_adjusted(
+                self.e,
+                ids.as_ptr(),
+                ids.len(),
+                std::ptr::null(),
+                p,
+                &a,
+                max_new,
+                top_logprobs.map_or(-1, |n| n as i32),
+                &mut id,
+            )
         })?;
         Ok(id)
     }
