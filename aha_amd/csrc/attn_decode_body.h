@@ -13,6 +13,21 @@ constexpr int ATTN_DECODE_NW = 4;  // waves (= KV units) per workgroup
 constexpr int ATTN_DECODE_MO_ROW = 132;
 constexpr int ATTN_DECODE_FUSED_LDS = 16 * 128 * 2 + 128 * 2 + 128 * 2 + ATTN_DECODE_NW * 16 * ATTN_DECODE_MO_ROW * 4 + 2 * ATTN_DECODE_NW * 16 * 4;  // bytes
 
+// Sum of v[0 .. 15] in the association in which wave_sum (common.h) combines lanes 0 .. 15 of a wave whose other lanes hold zero: its two
+// cross-row steps add those zeros (exact), then partners 8, 4, 2, 1 apart inside the row.  The final merge of up to 16 splits derives a
+// head's sum with this in every merge thread, to the bits that wave_sum over one split per lane gives.  Contraction off: no add of
+// the tree may be fused with the multiply that formed its operand.
+__device__ __forceinline__ float split_sum16(const float (&v)[16]) {
+#pragma clang fp contract(off)
+  float t[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) t[j] = v[j] + v[j + 8];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) t[j] = t[j] + t[j + 4];
+  const float c0 = t[0] + t[2], c1 = t[1] + t[3];
+  return c0 + c1;
+}
+
 // ---- decode, fused: q/k RMSNorm + (M-)RoPE + KV append + split-KV attention + in-block merge --------------------
 // One launch replaces qknorm_rope_kernel + attn_decode_kernel + the combine: every block redoes the (tiny) norm/rope of
 // its kv head's g query heads and of the new key in LDS (QKNormAttention::forward, modules.rs:538-557), block (kvhd, 0)
@@ -321,9 +336,52 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
   // The merging block is ONE workgroup, so this phase is bound by how many load instructions it issues and by dependent round
   // trips to memory (the partials were published write-through: they are in memory, not in any L2).  Hence: 16-byte
   // write-through-coherent (sc1) buffer loads, one thread per (head, 4 dims) -- nsplit wave-loads per wave instead of
-  // 4 * nsplit -- and ONE round for up to 16 splits: the (max, sum) pairs of all splits of the g heads (shared through LDS)
-  // and the thread's first 16 partial vectors are requested together; the global max, the split weights and 1/sum are
-  // derived from LDS while the vectors are in flight.
+  // 4 * nsplit -- and ONE round per 16 splits: the (max, sum) pairs and the thread's first 16 partial vectors are requested together.
+  if (nsplit <= 16) {
+    // Up to 16 splits (at 4 pages per block: contexts up to 4 k tokens): no LDS pass.  Every merge thread (head q, 4 dims) requests its
+    // head's (max, sum) pairs itself -- the 32 threads of a head ask for the same 8 bytes -- right in front of its 16 partial vectors: one round trip, as
+    // on the other path, but behind it no barrier, no LDS image of the pairs and no per-head wave pass: the weights are derived in
+    // registers, with the values and in the association of the other path (split_sum16), while the vectors arrive.  Both paths clamp
+    // the split index of the loads beyond nsplit and give those a weight of zero.
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(a.part_o, 0, (int)((size_t)nsplit * a.nh * 128 * 4), 0x00020000);
+    const uint32_t split_stride = (uint32_t)a.nh * 128 * 4;
+    for (int item = tid; item < g * 32; item += NT) {
+      const int head = kvhd * g + (item >> 5);
+      float2 ml[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) ml[j] = act_ldf2<true>(a.part_ml + ((size_t)min(j, nsplit - 1) * a.nh + head) * 2);
+      const uint32_t off = (uint32_t)(head * 128 + (item & 31) * 4) * 4;
+      f32x4_t pv[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + (uint32_t)min(j, nsplit - 1) * split_stride, 0, 16 /* sc1 */);
+        pv[j] = f32x4_t{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
+      }
+      float M = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) M = fmaxf(M, ml[j].x);  // the clamped repeats change no maximum
+      float wgt[16], wl[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        wgt[j] = (j < nsplit && ml[j].x != -INFINITY) ? __expf(ml[j].x - M) : 0.f;
+        wl[j] = fmaf(wgt[j], ml[j].y, 0.f);
+      }
+      const float inv = 1.0f / split_sum16(wl);
+      f32x4_t f = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) f[e] = fmaf(wgt[j], pv[j][e], f[e]);
+      uint2 w;
+      w.x = pack_bf(f[0] * inv, f[1] * inv);
+      w.y = pack_bf(f[2] * inv, f[3] * inv);
+      *reinterpret_cast<uint2*>((bf16_t*)a.o + (kvhd * g) * 128 + item * 4) = w;   // attention output tensor (bf16)
+    }
+    stamp(5);
+    return true;
+  }
+  // More than 16 splits: the pairs of all splits of the g heads are shared through LDS; the global max, the split weights and 1/sum are
+  // derived there, one wave per head, while the first 16 vectors are in flight.
   float* w_lds = mo;               // [g][nsplit] weights  (the per-wave O^T staging area is free again)
   float* inv_lds = mo + 16 * 256;  // [g] 1 / sum
   float2* ml_lds = reinterpret_cast<float2*>(mo + 8 * 256);  // [g][nsplit] (max, sum)

@@ -923,6 +923,19 @@ static int fetch_outputs(aha_model* m, float* logits_out, uint32_t* argmax_out) 
         }
         if (n) fprintf(stderr, "[attn trace] block %d: prologue %.2f | pages %.2f | merge+publish %.2f | arrive %.2f | final merge %.2f us\n", b, v[0] / n, v[1] / n, v[2] / n, v[3] / n, v[4] / n);
       }
+      // the stamps are absolute: who started first, and when each block's arrival was known, counted from the earlier start
+      double dstart = 0.0, arr[2] = {};
+      int n = 0;
+      for (int li = 1; li < L; ++li) {
+        const unsigned long long* p = t.data() + (size_t)li * 12;
+        if (p[0] == 0 || p[4] == 0 || p[6] == 0 || p[10] == 0) continue;
+        const unsigned long long t0 = std::min(p[0], p[6]);
+        dstart += ((double)p[6] - (double)p[0]) * 0.01;
+        arr[0] += (double)(p[4] - t0) * 0.01;
+        arr[1] += (double)(p[10] - t0) * 0.01;
+        ++n;
+      }
+      if (n) fprintf(stderr, "[attn trace] start of block 1 - start of block 0 %+.2f | arrival after the earlier start: block 0 %.2f | block 1 %.2f us\n", dstart / n, arr[0] / n, arr[1] / n);
     }
   }
   if (logits_out) memcpy(logits_out, m->h_logits, (size_t)c.vocab_size * 4);
