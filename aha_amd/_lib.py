@@ -225,6 +225,13 @@ SIGNATURES = {
     "aha_hip_sample_rows_adjusted": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "aha_hip_sampler_set_adjust": (C.c_int, [_P, C.POINTER(LogitAdjust)]),
     "aha_hip_sampler_adjust_list": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "aha_hip_generate_batch_masked": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.POINTER(SamplingParams), C.POINTER(LogitAdjust), _P, C.c_size_t,
+                                                C.c_size_t, _P, _P, _P, _P, _P, C.POINTER(TokenLogprobs)]),
+    "aha_hip_engine_submit_masked": (C.c_int, [_P, _P, C.c_size_t, _P, C.POINTER(SamplingParams), C.POINTER(LogitAdjust), _P, C.c_size_t,
+                                               C.c_size_t, C.c_int32, C.POINTER(C.c_uint64)]),
+    "aha_hip_engine_set_mask": (C.c_int, [_P, C.c_uint64, _P, C.c_size_t]),
+    "aha_hip_sample_rows_masked": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "aha_hip_sampler_set_mask": (C.c_int, [_P, _P, C.c_size_t]),
     "aha_hip_logprob_rows": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "aha_hip_sample_rows": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "aha_hip_sampler_create": (C.c_int, [C.POINTER(SamplingParams), _P]),
@@ -261,6 +268,9 @@ SIGNATURES = {
     "aha_hip_video_to_patches": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
                                            C.POINTER(C.c_float), _P]),
 }
+
+# aha_token_mask_fn (include/aha_hip.h): (user, seq, generated, n_generated, mask_words, n_words) -> 1 use / 0 unmasked / < 0 fail
+TOKEN_MASK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t)
 
 _lib = None
 

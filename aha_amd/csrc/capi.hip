@@ -757,10 +757,12 @@ struct DevFree {   // device buffers released when the call returns, on the erro
 };
 }  // namespace
 
-// aha_hip_sample_rows / aha_hip_sample_rows_adjusted (adj_offsets == nullptr: no addends)
+// aha_hip_sample_rows / aha_hip_sample_rows_adjusted / aha_hip_sample_rows_masked (adj_offsets == nullptr: no addends; mask_rows ==
+// nullptr: no masks)
 static int sample_rows_impl(const float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* k, const float* temperature,
                             const float* repeat_penalty, const uint32_t* context, const size_t* context_offsets, const uint32_t* adj_ids,
-                            const float* adj_vals, const size_t* adj_offsets, float* vals_out, uint32_t* idx_out, float* ms_out, void* stream) {
+                            const float* adj_vals, const size_t* adj_offsets, float* vals_out, uint32_t* idx_out, float* ms_out, void* stream,
+                            const uint32_t* masks = nullptr, const int32_t* mask_rows = nullptr) {
   if (!logits || R < 1 || V < 1 || ld < V || !k || !temperature || !repeat_penalty || !context_offsets || !vals_out || !idx_out || !ms_out) {
     set_error("sample_rows: bad arguments (R >= 1, ld >= V >= 1, per-row k / temperature / repeat_penalty / context_offsets, outputs)");
     return AHA_ERR_INVALID;
@@ -791,6 +793,11 @@ static int sample_rows_impl(const float* logits, int64_t ld, int32_t R, int32_t 
     memcpy(&t[SAMPLE_ROW_PEN], &repeat_penalty[r], 4);
     t[SAMPLE_ROW_CTX0] = (int32_t)c0;
     t[SAMPLE_ROW_NCTX] = (int32_t)(ctx.size() - c0);
+    t[SAMPLE_ROW_MASK] = mask_rows && mask_rows[r] >= 0 ? mask_rows[r] : -1;
+    if (t[SAMPLE_ROW_MASK] >= 0 && (!masks || (int64_t)t[SAMPLE_ROW_MASK] * ((V + 31) / 32) > (int64_t)INT32_MAX)) {
+      set_error("sample_rows_masked: row " + std::to_string(r) + " names a mask but masks is null, or the mask index is out of range");
+      return AHA_ERR_INVALID;
+    }
   }
   // every row's addends sorted by id; an id >= V or a duplicate is refused before anything touches the device
   std::vector<uint32_t> aid;
@@ -847,7 +854,7 @@ static int sample_rows_impl(const float* logits, int64_t ld, int32_t R, int32_t 
   AHA_HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
   if (!ctx.empty()) AHA_HIP_CHECK(hipMemcpyAsync(d_ctx, ctx.data(), ctx.size() * 4, hipMemcpyHostToDevice, st));
   for (int stage = 0; stage < 3; ++stage)
-    launch_topk_rows(logits, ld, V, R, d_tab, d_ctx, d_cval, d_cidx, d_part, d_part + (size_t)R * nw, d_out, stage, st, d_aid, d_aval);
+    launch_topk_rows(logits, ld, V, R, d_tab, d_ctx, d_cval, d_cidx, d_part, d_part + (size_t)R * nw, d_out, stage, st, d_aid, d_aval, masks);
   hipError_t err = hipGetLastError();
   // {vals[64], max, sumexp, idx[64]} per row -> the three outputs
   if (err == hipSuccess) err = hipMemcpy2DAsync(vals_out, 64 * 4, d_out, SAMPLE_OUT_WORDS * 4, 64 * 4, R, hipMemcpyDeviceToDevice, st);
@@ -884,6 +891,20 @@ int aha_hip_sample_rows_adjusted(const float* logits, int64_t ld, int32_t R, int
   }
   return sample_rows_impl(logits, ld, R, V, k, temperature, repeat_penalty, context, context_offsets, adj_ids, adj_vals, adj_offsets, vals_out,
                           idx_out, ms_out, stream);
+  API_GUARD_END
+}
+
+int aha_hip_sample_rows_masked(const float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* k, const float* temperature,
+                               const float* repeat_penalty, const uint32_t* context, const size_t* context_offsets, const uint32_t* adj_ids,
+                               const float* adj_vals, const size_t* adj_offsets, const uint32_t* masks, const int32_t* mask_rows,
+                               float* vals_out, uint32_t* idx_out, float* ms_out, void* stream) {
+  API_GUARD_BEGIN
+  if (!mask_rows) {
+    set_error("sample_rows_masked: null mask_rows");
+    return AHA_ERR_INVALID;
+  }
+  return sample_rows_impl(logits, ld, R, V, k, temperature, repeat_penalty, context, context_offsets, adj_ids, adj_vals, adj_offsets, vals_out,
+                          idx_out, ms_out, stream, masks, mask_rows);
   API_GUARD_END
 }
 
@@ -1322,6 +1343,41 @@ int aha_hip_generate_batch_adjusted(aha_model* m, const uint32_t* input_ids, con
                                        n_out, step_logits_out, logprobs_out);
   API_GUARD_END
 }
+int aha_hip_generate_batch_masked(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs,
+                                  const aha_mm_input* const* mm, const aha_sampling_params* params, const aha_logit_adjust* adjust,
+                                  const int32_t* top_logprobs, size_t max_new, size_t max_tokens_per_pass, aha_token_mask_fn mask_fn,
+                                  void* mask_user, uint32_t* tokens_out, size_t* n_out, float* step_logits_out,
+                                  aha_token_logprobs* logprobs_out) {
+  if (!mask_fn)   // exactly aha_hip_generate_batch_adjusted
+    return aha_hip_generate_batch_adjusted(m, input_ids, seq_lens, n_seqs, mm, params, adjust, top_logprobs, max_new, max_tokens_per_pass,
+                                           tokens_out, n_out, step_logits_out, logprobs_out);
+  API_GUARD_BEGIN
+  for (size_t j = 0; params && j < n_seqs && j < ((size_t)1 << 20); ++j) {   // params == NULL: every sequence greedy
+    std::string why;
+    if (sampling_params_check(params[j], &why)) {
+      set_error("generate_batch_masked: params of sequence " + std::to_string(j) + ": " + why);
+      return AHA_ERR_INVALID;
+    }
+  }
+  if ((top_logprobs == nullptr) != (logprobs_out == nullptr)) {
+    set_error("generate_batch_masked: top_logprobs and logprobs_out go together (both NULL: no logprobs)");
+    return AHA_ERR_INVALID;
+  }
+  for (size_t j = 0; top_logprobs && j < n_seqs && j < ((size_t)1 << 20); ++j)
+    if (top_logprobs[j] < -1 || top_logprobs[j] > AHA_MAX_TOP_LOGPROBS) {
+      set_error("generate_batch_masked: top_logprobs of sequence " + std::to_string(j) + " must be -1 (none) or 0 .. " +
+                std::to_string(AHA_MAX_TOP_LOGPROBS) + ", got " + std::to_string(top_logprobs[j]));
+      return AHA_ERR_INVALID;
+    }
+  if (!m) {
+    set_error("null model");
+    return AHA_ERR_INVALID;
+  }
+  if (int rc = engine_owns_cache(m, "generate_batch_masked")) return rc;
+  return model_generate_batch_masked(m, input_ids, seq_lens, n_seqs, mm, params, adjust, top_logprobs, max_new, max_tokens_per_pass, mask_fn,
+                                     mask_user, tokens_out, n_out, step_logits_out, logprobs_out);
+  API_GUARD_END
+}
 int aha_hip_generate_batch_spec(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
                                 size_t max_tokens_per_pass, const aha_spec_config* spec, const uint32_t* predictions,
                                 const size_t* prediction_lens, uint32_t* tokens_out, size_t* n_out, float* logits_out, size_t* n_proposed,
@@ -1428,6 +1484,38 @@ int aha_hip_engine_submit_adjusted(aha_engine* e, const uint32_t* input_ids, siz
     return AHA_ERR_INVALID;
   }
   return engine_submit(e, input_ids, n_ids, mm, params, max_new, req_id, top_logprobs, adjust);
+  API_GUARD_END
+}
+int aha_hip_engine_submit_masked(aha_engine* e, const uint32_t* input_ids, size_t n_ids, const aha_mm_input* mm,
+                                 const aha_sampling_params* params, const aha_logit_adjust* adjust, const uint32_t* mask_words,
+                                 size_t n_mask_words, size_t max_new, int32_t top_logprobs, uint64_t* req_id) {
+  API_GUARD_BEGIN
+  if (params) {
+    std::string why;
+    if (sampling_params_check(*params, &why)) {
+      set_error("engine_submit_masked: params: " + why);
+      return AHA_ERR_INVALID;
+    }
+  }
+  if (top_logprobs < -1 || top_logprobs > AHA_MAX_TOP_LOGPROBS) {
+    set_error("engine_submit_masked: top_logprobs must be -1 (none) or 0 .. " + std::to_string(AHA_MAX_TOP_LOGPROBS) + ", got " +
+              std::to_string(top_logprobs));
+    return AHA_ERR_INVALID;
+  }
+  if (!e) {
+    set_error("engine_submit_masked: null engine");
+    return AHA_ERR_INVALID;
+  }
+  return engine_submit(e, input_ids, n_ids, mm, params, max_new, req_id, top_logprobs, adjust, mask_words, n_mask_words);
+  API_GUARD_END
+}
+int aha_hip_engine_set_mask(aha_engine* e, uint64_t req_id, const uint32_t* words, size_t n_words) {
+  API_GUARD_BEGIN
+  if (!e) {
+    set_error("engine_set_mask: null engine");
+    return AHA_ERR_INVALID;
+  }
+  return engine_set_mask(e, req_id, words, n_words);
   API_GUARD_END
 }
 int aha_hip_engine_cancel(aha_engine* e, uint64_t req_id) {

@@ -64,13 +64,15 @@ void launch_topk_candidates(const float* x, int V, int k, float inv_temp, float*
 // Addends (logit_bias, presence / frequency penalties): row s adds adj_val[i] to the penalised logit of adj_id[i] for i in
 // [ADJ0, ADJ0 + NADJ) -- ids sorted ascending, distinct and < V; NADJ == 0 (adj_* may then be null): the row's work is what it was
 // before addends existed.
-constexpr int SAMPLE_ROW_WORDS = 8;
+// Allowed-token masks: row s with MASK = i >= 0 reads the ceil(V / 32) words masks[i * ceil(V / 32) ..) -- id t is allowed iff bit t & 31 of
+// word t >> 5 is set, and every other penalised, adjusted logit becomes -inf before the max; MASK < 0 (masks may then be null): no mask.
+constexpr int SAMPLE_ROW_WORDS = 9;
 constexpr int SAMPLE_ROW_LROW = 0, SAMPLE_ROW_K = 1, SAMPLE_ROW_INVT = 2, SAMPLE_ROW_PEN = 3, SAMPLE_ROW_CTX0 = 4, SAMPLE_ROW_NCTX = 5;
-constexpr int SAMPLE_ROW_ADJ0 = 6, SAMPLE_ROW_NADJ = 7;
+constexpr int SAMPLE_ROW_ADJ0 = 6, SAMPLE_ROW_NADJ = 7, SAMPLE_ROW_MASK = 8;
 constexpr int SAMPLE_OUT_WORDS = 64 + 2 + 64;
 void launch_topk_rows(const float* logits, int64_t ld, int V, int rows, const int32_t* tab, const uint32_t* ctx, float* cand_val,
                       unsigned* cand_idx, float* part_m, float* part_s, float* out, int stage, hipStream_t st,
-                      const uint32_t* adj_id = nullptr, const float* adj_val = nullptr);
+                      const uint32_t* adj_id = nullptr, const float* adj_val = nullptr, const uint32_t* masks = nullptr);
 
 // Per-token log-probabilities (kernels_logprob.hip) for `rows` rows of f32 logits (pitch ld), one launch per stage (stage 0: stage 1,
 // 1: stage 2; the caller scopes each for the profile).  Row s of `tab` (device, LOGPROB_ROW_WORDS int32 per row): its logits row, its n_top

@@ -38,12 +38,16 @@ __host__ __device__ constexpr int sample_stage1_waves_dev(int V) { return (V + S
 // The wave finds the first entry inside its 512 logits by a wave-uniform binary search and walks on from there until an id leaves them:
 // it reads at most ceil(log2 n_adj) + hits + 1 ids (the search's last upper probe is kept, so the walk's first id is not read again)
 // and `hits` values.  A wave left with nothing but -inf contributes (max -inf, sum 0): exp(-inf - -inf) would be NaN.
-template <bool PEN, bool ADJ = false>
+// MASK: after the addends, every logit whose bit in the row's allowed-token mask is clear becomes -inf.  The wave's 512 logits are the 16
+// consecutive words mask[16 w ..), of which lanes 0 .. 15 load one each (words at or past ceil(V / 32) are not read); element j of lane l
+// takes bit l & 31 of word 2 j + (l >> 5) through two wave-uniform lane reads.  Bits at positions >= V belong to elements that are -inf anyway.
+template <bool PEN, bool ADJ = false, bool MASK = false>
 __device__ __forceinline__ void topk_stage1_body(const float* x, int V, int k, float inv_temp, const uint32_t* ctx, int n_ctx,
                                                  float penalty, int w, float* cand_val, unsigned* cand_idx, float* part_m, float* part_s,
-                                                 const uint32_t* adj_id = nullptr, const float* adj_val = nullptr, int n_adj = 0) {
+                                                 const uint32_t* adj_id = nullptr, const float* adj_val = nullptr, int n_adj = 0,
+                                                 const uint32_t* mask = nullptr) {
   const int lane = threadIdx.x & 63;
-  if (ADJ) w = __builtin_amdgcn_readfirstlane(w);   // the search and the walk below run on scalars
+  if (ADJ || MASK) w = __builtin_amdgcn_readfirstlane(w);   // the search and the walk below run on scalars
   const int base = w * S1_WAVE_ELEMS;
   if (base >= V) return;
   float v[S1_C];
@@ -82,12 +86,22 @@ __device__ __forceinline__ void topk_stage1_body(const float* x, int V, int k, f
         if (id[j] == t) v[j] = v[j] + a;
     }
   }
+  if (MASK) {
+    const int n_words = (V + 31) >> 5, wi = w * (S1_WAVE_ELEMS / 32) + lane;
+    const bool ok = lane < S1_WAVE_ELEMS / 32 && wi < n_words;
+    const unsigned word = ok ? mask[ok ? wi : 0] : 0u;
+#pragma unroll
+    for (int j = 0; j < S1_C; ++j) {
+      const unsigned lo = __builtin_amdgcn_readlane(word, 2 * j), hi = __builtin_amdgcn_readlane(word, 2 * j + 1);
+      if (!(((lane < 32 ? lo : hi) >> (lane & 31)) & 1u)) v[j] = -INFINITY;
+    }
+  }
   float lm = -INFINITY;
 #pragma unroll
   for (int j = 0; j < S1_C; ++j) lm = fmaxf(lm, v[j]);
   const float wm = wave_max(lm);
   float s = 0.f;
-  if (!ADJ || wm != -INFINITY) {
+  if (!(ADJ || MASK) || wm != -INFINITY) {
 #pragma unroll
     for (int j = 0; j < S1_C; ++j)
       if (id[j] != NO_IDX) s += __expf((v[j] - wm) * inv_temp);
@@ -187,7 +201,9 @@ __global__ __launch_bounds__(64) void topk_stage2b_kernel(const float* mid_val, 
 
 // ---- the same three stages for R rows at once (batched sampled generation): blockIdx.y is the row of the sample table ----------
 // Row s of the table (SAMPLE_ROW_WORDS int32): logits row, k, 1/T and penalty (f32 bits), its distinct context ids ctx[c0 .. c0 + n),
-// its addends adj_id / adj_val [a0 .. a0 + n_adj) (sorted by id, distinct; a row without any takes the instantiation it always took).
+// its addends adj_id / adj_val [a0 .. a0 + n_adj) (sorted by id, distinct; a row without any takes the instantiation it always took),
+// its allowed-token mask masks[SAMPLE_ROW_MASK * ceil(V / 32) ..) (SAMPLE_ROW_MASK < 0: none, and the instantiation it took without masks;
+// a masked row takes one more, which also walks its possibly empty context and addend list).
 // Row s owns cand_* [s * (nw + 16) * 64, +(nw + 16) * 64) (stage-1 candidates, then the 16 x k intermediates), part_* [s * nw, +nw) and
 // out [s * SAMPLE_OUT_WORDS, +SAMPLE_OUT_WORDS) = {vals[64], max, sumexp, idx[64]}.  Every stage runs the single-row body on the row's
 // own slices, so a row's outputs are those of the single-row pipeline (the penalty copy there, the load-time penalty here, give the
@@ -195,15 +211,20 @@ __global__ __launch_bounds__(64) void topk_stage2b_kernel(const float* mid_val, 
 __global__ __launch_bounds__(64 * S1_WAVES_PER_BLOCK) void topk_rows_stage1_kernel(const float* logits, int64_t ld, int V,
                                                                                    const int32_t* tab, const uint32_t* ctx,
                                                                                    const uint32_t* adj_id, const float* adj_val,
-                                                                                   float* cand_val, unsigned* cand_idx,
+                                                                                   const uint32_t* masks, float* cand_val, unsigned* cand_idx,
                                                                                    float* part_m, float* part_s) {
   const int32_t* t = tab + (size_t)blockIdx.y * SAMPLE_ROW_WORDS;
   const int nw = sample_stage1_waves_dev(V);
   const size_t cb = (size_t)blockIdx.y * (nw + S2_WAVES) * 64, pb = (size_t)blockIdx.y * nw;
   const float* x = logits + (int64_t)t[SAMPLE_ROW_LROW] * ld;
   const int w = blockIdx.x * S1_WAVES_PER_BLOCK + (threadIdx.x >> 6);
-  const int n_ctx = t[SAMPLE_ROW_NCTX], n_adj = t[SAMPLE_ROW_NADJ];
-  if (n_adj > 0)
+  const int n_ctx = t[SAMPLE_ROW_NCTX], n_adj = t[SAMPLE_ROW_NADJ], mrow = t[SAMPLE_ROW_MASK];
+  if (mrow >= 0)
+    topk_stage1_body<true, true, true>(x, V, t[SAMPLE_ROW_K], __int_as_float(t[SAMPLE_ROW_INVT]), ctx + t[SAMPLE_ROW_CTX0], n_ctx,
+                                       __int_as_float(t[SAMPLE_ROW_PEN]), w, cand_val + cb, cand_idx + cb, part_m + pb, part_s + pb,
+                                       adj_id + t[SAMPLE_ROW_ADJ0], adj_val + t[SAMPLE_ROW_ADJ0], n_adj,
+                                       masks + (size_t)mrow * ((V + 31) >> 5));
+  else if (n_adj > 0)
     topk_stage1_body<true, true>(x, V, t[SAMPLE_ROW_K], __int_as_float(t[SAMPLE_ROW_INVT]), ctx + t[SAMPLE_ROW_CTX0], n_ctx,
                                  __int_as_float(t[SAMPLE_ROW_PEN]), w, cand_val + cb, cand_idx + cb, part_m + pb, part_s + pb,
                                  adj_id + t[SAMPLE_ROW_ADJ0], adj_val + t[SAMPLE_ROW_ADJ0], n_adj);
@@ -260,12 +281,12 @@ void launch_topk_candidates(const float* x, int V, int k, float inv_temp, float*
 
 void launch_topk_rows(const float* logits, int64_t ld, int V, int rows, const int32_t* tab, const uint32_t* ctx, float* cand_val,
                       unsigned* cand_idx, float* part_m, float* part_s, float* out, int stage, hipStream_t st, const uint32_t* adj_id,
-                      const float* adj_val) {
+                      const float* adj_val, const uint32_t* masks) {
   if (rows <= 0) return;
   const int nw = sample_stage1_waves(V);
   if (stage == 0)
     hipLaunchKernelGGL(topk_rows_stage1_kernel, dim3((nw + S1_WAVES_PER_BLOCK - 1) / S1_WAVES_PER_BLOCK, rows), dim3(64 * S1_WAVES_PER_BLOCK),
-                       0, st, logits, ld, V, tab, ctx, adj_id, adj_val, cand_val, cand_idx, part_m, part_s);
+                       0, st, logits, ld, V, tab, ctx, adj_id, adj_val, masks, cand_val, cand_idx, part_m, part_s);
   else if (stage == 1)
     hipLaunchKernelGGL(topk_rows_stage2a_kernel, dim3(S2_WAVES, rows), dim3(64), 0, st, V, tab, cand_val, cand_idx);
   else

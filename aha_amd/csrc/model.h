@@ -226,6 +226,10 @@ int model_generate_batch_adjusted(aha_model* m, const uint32_t* ids, const size_
                                   const aha_sampling_params* params, const aha_logit_adjust* adjust, const int32_t* top_logprobs, size_t max_new,
                                   size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* step_logits_out,
                                   aha_token_logprobs* logprobs_out);
+int model_generate_batch_masked(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
+                                const aha_sampling_params* params, const aha_logit_adjust* adjust, const int32_t* top_logprobs, size_t max_new,
+                                size_t max_tokens_per_pass, aha_token_mask_fn mask_fn, void* mask_user, uint32_t* tokens_out, size_t* n_out,
+                                float* step_logits_out, aha_token_logprobs* logprobs_out);
 int model_generate_batch_spec(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new, size_t max_tokens_per_pass,
                               const aha_spec_config* spec, const uint32_t* predictions, const size_t* prediction_lens, uint32_t* tokens_out,
                               size_t* n_out, float* logits_out, size_t* n_proposed, size_t* n_accepted, aha_spec_stats* stats);
@@ -237,7 +241,9 @@ int engine_config_check(const aha_engine_config* cfg, size_t* budget_out, size_t
 int engine_create(aha_model* m, const aha_engine_config* cfg, aha_engine** out);
 void engine_destroy(aha_engine* e);
 int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const aha_mm_input* mm, const aha_sampling_params* params, size_t max_new,
-                  uint64_t* req_id, int32_t top_logprobs = -1, const aha_logit_adjust* adjust = nullptr);
+                  uint64_t* req_id, int32_t top_logprobs = -1, const aha_logit_adjust* adjust = nullptr,
+                  const uint32_t* mask = nullptr, size_t n_mask_words = 0);
+int engine_set_mask(aha_engine* e, uint64_t req_id, const uint32_t* words, size_t n_words);
 int engine_cancel(aha_engine* e, uint64_t req_id);
 int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, float* logits_out, aha_token_logprobs* logprobs_out = nullptr);
 int engine_stats(const aha_engine* e, aha_engine_stats* out);

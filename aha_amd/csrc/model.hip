@@ -2543,8 +2543,25 @@ struct GenChoice {
   // the rows' addend lists (logit_bias, presence / frequency penalties), pinned staging and device: null until a sequence has an adjust
   uint32_t *d_adj_id = nullptr, *h_adj_id = nullptr;
   float *d_adj_val = nullptr, *h_adj_val = nullptr;
+  // allowed-token masks: row j of h_masks (pinned) / d_masks is sequence / slot j's ceil(V / 32) words; null until the call or engine can
+  // have masks.  mask_state[j]: 0 = its next token is unmasked, 1 = masked by the words already on the device, 2 = masked, words to upload.
+  uint32_t *d_masks = nullptr, *h_masks = nullptr;
+  size_t mask_w = 0;
+  std::vector<uint8_t> mask_state;
+  aha_token_mask_fn mask_fn = nullptr;   // aha_hip_generate_batch_masked's callback: asked once per live sequence per step
+  void* mask_user = nullptr;
   std::vector<int> mode, slot, fb_rows;   // finish_step's per-row scratch
 };
+
+// the mask buffers for n sequences / slots, every word all ones, every sequence unmasked
+static int gen_choice_mask_alloc(DevBufs& bufs, int n, int V, GenChoice& ch) {
+  ch.mask_w = token_mask_words((size_t)V);
+  int rc;
+  if ((rc = bufs.alloc(&ch.d_masks, (size_t)n * ch.mask_w)) || (rc = bufs.alloc_host(&ch.h_masks, (size_t)n * ch.mask_w))) return rc;
+  memset(ch.h_masks, 0xff, (size_t)n * ch.mask_w * 4);
+  ch.mask_state.assign(n, 0);
+  return AHA_OK;
+}
 
 // room for `cap` addend entries (cap > 0)
 static int gen_choice_adj_alloc(DevBufs& bufs, size_t cap, GenChoice& ch) {
@@ -2606,6 +2623,10 @@ static int gen_choice_init(DevBufs& bufs, const GenCall& gc, const aha_sampling_
 // Addends (a sampler with an active aha_logit_adjust): the sampler's counts are brought up to the sequence's tokens, and a row with a live
 // addend is a candidate row (k = 1 for ArgMax) whose sorted (id, addend) list goes up with the table; a row that needs its full vector gets
 // the addends in sampler_pick.  A step without a live addend launches and copies what it did before they existed.
+// Masks: the callback (batch generation) is asked here, after the step's device work has been queued and before the candidate step is, with
+// the sequence's previous words in place; a masked row is a candidate row (k = 1 for ArgMax) that names its words in d_masks, uploaded when
+// they changed; a row that needs its full vector gets the mask in sampler_pick.  A step without a masked row launches and copies what it
+// did before masks existed.
 // Logprobs (gc.lp_top): one two-launch pass over the rows that ask for them, behind the candidate step and in front of the same sync; a
 // greedy row's entry is complete on the device (its token is in tok_dev), a sampled row's lp is finished here from the raw logit of the
 // token the host picked -- among its candidates' raw logits, which came down with the entry, or in its full row when it fell back.
@@ -2620,7 +2641,7 @@ static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::
   if (sampled) {
     ch.mode.assign(R, GREEDY);
     ch.slot.assign(R, -1);
-    size_t nc = 0, na = 0;
+    size_t nc = 0, na = 0, nm = 0;
     for (int r = 0; r < R; ++r) {
       const int j = seqs[r];
       HostSampler& S = ch.samplers[j];
@@ -2629,7 +2650,25 @@ static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::
       sampler_penalty_context(S, gc.n_out[j], &pen, &n_ctx);
       sampler_adjust_sync(S, gen_seq_tokens(gc, j), gc.n_out[j], (size_t)V);
       const bool live = sampler_adjust_bound(S) > 0;
-      if (S.kind == SAMPLE_ARGMAX && pen == 1.0f && !live) continue;   // the device argmax is the token
+      if (ch.mask_fn) {
+        uint32_t* words = ch.h_masks + (size_t)j * ch.mask_w;
+        const int mrc = ch.mask_fn(ch.mask_user, (size_t)j, gen_seq_tokens(gc, j), gc.n_out[j], words, ch.mask_w);
+        if (mrc < 0) {
+          set_error("generate_batch_masked: the mask callback returned " + std::to_string(mrc) + " for sequence " + std::to_string(j) +
+                    " at step " + std::to_string(gc.n_out[j]));
+          return AHA_ERR_STATE;
+        }
+        if (mrc > 0 && !token_mask_any(words, (size_t)V)) {
+          set_error("generate_batch_masked: the mask of sequence " + std::to_string(j) + " at step " + std::to_string(gc.n_out[j]) +
+                    " allows no id below vocab_size");
+          return AHA_ERR_INVALID;
+        }
+        ch.mask_state[j] = mrc > 0 ? 2 : 0;
+      }
+      const bool masked = !ch.mask_state.empty() && ch.mask_state[j] != 0;
+      S.mask = masked ? ch.h_masks + (size_t)j * ch.mask_w : nullptr;   // for a pick from the full vector
+      S.mask_words = masked ? ch.mask_w : 0;
+      if (S.kind == SAMPLE_ARGMAX && pen == 1.0f && !live && !masked) continue;   // the device argmax is the token
       const int k = S.kind == SAMPLE_ARGMAX ? 1 : sampler_candidates_needed(S, (size_t)V);
       if (!k) {
         ch.mode[r] = FULL;
@@ -2657,7 +2696,16 @@ static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::
       t[SAMPLE_ROW_ADJ0] = (int32_t)na;
       t[SAMPLE_ROW_NADJ] = live ? (int32_t)sampler_adjust_list(S, ch.h_adj_id + na, ch.h_adj_val + na) : 0;
       na += (size_t)t[SAMPLE_ROW_NADJ];
+      t[SAMPLE_ROW_MASK] = masked ? j : -1;
+      nm += masked;
       ++ns;
+    }
+    // changed masks go up whether their row is a candidate row or not: state 1 means "on the device"
+    for (int r = 0; r < R && !ch.mask_state.empty(); ++r) {
+      const int j = seqs[r];
+      if (ch.mask_state[j] != 2) continue;
+      AHA_HIP_CHECK(hipMemcpyAsync(ch.d_masks + (size_t)j * ch.mask_w, ch.h_masks + (size_t)j * ch.mask_w, ch.mask_w * 4, hipMemcpyHostToDevice, st));
+      ch.mask_state[j] = 1;
     }
     if (ns) {
       AHA_HIP_CHECK(hipMemcpyAsync(ch.d_stab, ch.h_stab, (size_t)ns * SAMPLE_ROW_WORDS * 4, hipMemcpyHostToDevice, st));
@@ -2668,9 +2716,10 @@ static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::
       }
       const char* names[3] = {"sample_rows_stage1", "sample_rows_stage2a", "sample_rows_stage2b"};
       for (int stage = 0; stage < 3; ++stage) {
-        ProfScope ps(m, names[stage], stage == 0 ? (double)ns * V * 4 + (double)na * 8 : 0, 0);   // (the logits, the uploaded lists)
+        // (the logits, the uploaded lists, the masks)
+        ProfScope ps(m, names[stage], stage == 0 ? (double)ns * V * 4 + (double)na * 8 + (double)nm * ch.mask_w * 4 : 0, 0);
         launch_topk_rows(gc.logits, V, V, ns, ch.d_stab, ch.d_sctx, ch.d_cval, ch.d_cidx, ch.d_part, ch.d_part + (size_t)gc.n * ch.nw, ch.d_sout,
-                         stage, st, ch.d_adj_id, ch.d_adj_val);
+                         stage, st, ch.d_adj_id, ch.d_adj_val, ch.d_masks);
       }
       AHA_HIP_CHECK(hipGetLastError());
       AHA_HIP_CHECK(hipMemcpyAsync(ch.h_sout, ch.d_sout, (size_t)ns * SAMPLE_OUT_WORDS * 4, hipMemcpyDeviceToHost, st));
@@ -2980,7 +3029,7 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
                                size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* logits_out,
                                const aha_sampling_params* params, float* step_logits_out, const aha_mm_input* const* mm = nullptr,
                                const SpecRun* sp = nullptr, const int32_t* top_logprobs = nullptr, aha_token_logprobs* logprobs_out = nullptr,
-                               const aha_logit_adjust* adjust = nullptr) {
+                               const aha_logit_adjust* adjust = nullptr, aha_token_mask_fn mask_fn = nullptr, void* mask_user = nullptr) {
   const aha_model_desc& c = m->desc;
   if (!ids || !seq_lens || !tokens_out || !n_out) {
     set_error("generate_batch: null input_ids / seq_lens / tokens_out / n_out");
@@ -3022,10 +3071,10 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
       any |= logit_adjust_active(&adjust[j]);
     }
     if (!any) adjust = nullptr;
-    else if (!params) {
-      greedy_params.assign(n_seqs, aha_sampling_params{0.f, 1.f, 0, 1.f, 64, 0u, 299792458ull});
-      params = greedy_params.data();
-    }
+  }
+  if ((adjust || mask_fn) && !params) {   // (a mask callback likewise: a row it leaves unmasked stays the device argmax)
+    greedy_params.assign(n_seqs, aha_sampling_params{0.f, 1.f, 0, 1.f, 64, 0u, 299792458ull});
+    params = greedy_params.data();
   }
   std::vector<size_t> pred_off(n_seqs, 0);
   if (sp && sp->predictions) {
@@ -3076,6 +3125,10 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
     max_pass_pages += (seq_lens[j] + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
   }
   if ((rc = gen_call_alloc(m, bufs, gc, max_pass_pages)) || (params && (rc = gen_choice_init(bufs, gc, params, ch, adjust)))) return rc;
+  if (mask_fn) {
+    if ((rc = gen_choice_mask_alloc(bufs, n, V, ch))) return rc;
+    ch.mask_fn = mask_fn, ch.mask_user = mask_user;
+  }
   if (top_logprobs) {
     gc.lp_top = top_logprobs, gc.logprobs_out = logprobs_out;
     if (std::any_of(top_logprobs, top_logprobs + n, [](int32_t t) { return t >= 0; }) && (rc = gen_logprob_alloc(bufs, gc))) return rc;
@@ -3191,6 +3244,14 @@ int model_generate_batch_adjusted(aha_model* m, const uint32_t* ids, const size_
                              nullptr, top_logprobs, logprobs_out, adjust);
 }
 
+int model_generate_batch_masked(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
+                                const aha_sampling_params* params, const aha_logit_adjust* adjust, const int32_t* top_logprobs, size_t max_new,
+                                size_t max_tokens_per_pass, aha_token_mask_fn mask_fn, void* mask_user, uint32_t* tokens_out, size_t* n_out,
+                                float* step_logits_out, aha_token_logprobs* logprobs_out) {
+  return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, nullptr, params, step_logits_out, mm,
+                             nullptr, top_logprobs, logprobs_out, adjust, mask_fn, mask_user);
+}
+
 int model_generate_batch_spec(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new, size_t max_tokens_per_pass,
                               const aha_spec_config* spec, const uint32_t* predictions, const size_t* prediction_lens, uint32_t* tokens_out,
                               size_t* n_out, float* logits_out, size_t* n_proposed, size_t* n_accepted, aha_spec_stats* stats) {
@@ -3226,6 +3287,8 @@ struct EngReq {
   aha_logit_adjust adjust{};          // aha_hip_engine_submit_adjusted: its arrays point into the two vectors below
   std::vector<uint32_t> bias_ids;
   std::vector<float> bias_vals;
+  std::vector<uint32_t> mask;         // aha_hip_engine_submit_masked / set_mask while the request waits (empty: none); a running
+                                      // request's words live in its slot's row of GenChoice::h_masks
   int slot = -1;
   bool started = false, cancel = false;
   std::vector<uint32_t> toks;         // capacity max_new: gen_finish_step reads the penalty context through a pointer to it
@@ -3267,6 +3330,19 @@ struct aha_engine {
 };
 
 namespace aha {
+
+// a caller's mask: n_words == ceil(V / 32) and an allowed id below V, or the error `who` reports (non-zero)
+static int rc_mask_check(const uint32_t* words, size_t n_words, size_t V, const char* who) {
+  if (n_words != token_mask_words(V)) {
+    set_error(std::string(who) + ": the mask has " + std::to_string(n_words) + " words, the vocabulary needs " + std::to_string(token_mask_words(V)));
+    return AHA_ERR_INVALID;
+  }
+  if (!token_mask_any(words, V)) {
+    set_error(std::string(who) + ": the mask allows no id below vocab_size");
+    return AHA_ERR_INVALID;
+  }
+  return AHA_OK;
+}
 
 static bool engine_is_stop(const aha_model_desc& c, uint32_t t) {
   for (int e = 0; e < c.n_stop_tokens; ++e)
@@ -3342,7 +3418,8 @@ int engine_create(aha_model* m, const aha_engine_config* cfg, aha_engine** out) 
   e->ctx_cap = (size_t)n * 64;
   if ((rc = gen_call_alloc(m, e->bufs, gc, 2 * e->kv_pages)) || (rc = gen_choice_alloc(e->bufs, gc, e->ctx_cap, (size_t)n, e->ch)) ||
       (rc = e->bufs.alloc(&e->d_win, (size_t)n * e->kv_pages, true)) || (rc = e->bufs.alloc(&e->d_tok_in, (size_t)n)) ||
-      (rc = e->bufs.alloc_host(&e->h_tok_in, (size_t)n)) || (logprob_shape_ok(gc.V) && (rc = gen_logprob_alloc(e->bufs, gc)))) {
+      (rc = e->bufs.alloc_host(&e->h_tok_in, (size_t)n)) || (logprob_shape_ok(gc.V) && (rc = gen_logprob_alloc(e->bufs, gc))) ||
+      (rc = gen_choice_mask_alloc(e->bufs, n, gc.V, e->ch))) {
     delete e;
     model_clear_cache(m);
     return rc;
@@ -3365,9 +3442,10 @@ void engine_destroy(aha_engine* e) {
 }
 
 int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const aha_mm_input* mm, const aha_sampling_params* params, size_t max_new,
-                  uint64_t* req_id, int32_t top_logprobs, const aha_logit_adjust* adjust) {
+                  uint64_t* req_id, int32_t top_logprobs, const aha_logit_adjust* adjust, const uint32_t* mask, size_t n_mask_words) {
   aha_model* m = e->m;
   const aha_model_desc& c = m->desc;
+  if (mask && (rc_mask_check(mask, n_mask_words, (size_t)c.vocab_size, "engine_submit_masked"))) return AHA_ERR_INVALID;
   {
     std::string why;
     if (logit_adjust_check(adjust, (size_t)c.vocab_size, &why)) {
@@ -3418,11 +3496,32 @@ int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const aha_mm
     q->bias_vals.assign(adjust->bias_vals, adjust->bias_vals + adjust->n_bias);
     q->adjust = aha_logit_adjust{adjust->presence_penalty, adjust->frequency_penalty, q->bias_ids.data(), q->bias_vals.data(), adjust->n_bias};
   }
+  if (mask) q->mask.assign(mask, mask + n_mask_words);
   q->npages = npages;
   q->toks.reserve(max_new);
   e->waiting.push_back(q);
   *req_id = q->id;
   return AHA_OK;
+}
+
+int engine_set_mask(aha_engine* e, uint64_t req_id, const uint32_t* words, size_t n_words) {
+  const size_t V = (size_t)e->m->desc.vocab_size;
+  if (words && rc_mask_check(words, n_words, V, "engine_set_mask")) return AHA_ERR_INVALID;
+  for (EngReq* q : e->waiting)
+    if (q->id == req_id) {
+      if (words) q->mask.assign(words, words + n_words);
+      else q->mask.clear();
+      return AHA_OK;
+    }
+  for (EngReq* q : e->slots)
+    if (q && q->id == req_id && !q->cancel) {
+      // between steps the stream has drained: the slot's pinned words are free to change, and go up with the next candidate step
+      if (words) memcpy(e->ch.h_masks + (size_t)q->slot * e->ch.mask_w, words, n_words * 4);
+      e->ch.mask_state[q->slot] = words ? 2 : 0;
+      return AHA_OK;
+    }
+  set_error("engine_set_mask: no waiting or running request " + std::to_string(req_id));
+  return AHA_ERR_INVALID;
 }
 
 int engine_cancel(aha_engine* e, uint64_t req_id) {
@@ -3463,6 +3562,8 @@ static void engine_release(aha_engine* e, int s) {
   pg.clear();
   e->slots[s] = nullptr;
   e->ch.samplers[s].adj = LogitAdjust{};   // the slot's bias copy and count table go with the request
+  e->ch.samplers[s].mask = nullptr, e->ch.samplers[s].mask_words = 0;
+  e->ch.mask_state[s] = 0;                 // and its mask: the slot's next request starts unmasked
   delete q;
 }
 
@@ -3492,6 +3593,10 @@ static int engine_admit(aha_engine* e, EngReq* q, int s) {
     return rc;
   }
   sampler_set_adjust(e->ch.samplers[s], &q->adjust);
+  if (!q->mask.empty()) {   // the mask it was submitted with, or was given while it waited
+    memcpy(e->ch.h_masks + (size_t)s * e->ch.mask_w, q->mask.data(), e->ch.mask_w * 4);
+    e->ch.mask_state[s] = 2;
+  }
   size_t need = 0, need_adj = 0;   // the penalty contexts and the addend lists of every slot's sampler
   for (int k = 0; k < (int)e->max_running; ++k) {
     const EngReq* o = k == s ? q : e->slots[k];

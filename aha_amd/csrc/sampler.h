@@ -40,6 +40,11 @@ struct HostSampler {
   std::unique_ptr<aha_rng, RngDeleter> rng;
   uint64_t words = 0;         // u32 handed out by rng
   LogitAdjust adj;            // host_sampler_init leaves it inactive
+  // the allowed-token mask of the next pick (mask_words = ceil(V / 32) words, not owned; nullptr: none).  aha_hip_sampler_set_mask points it
+  // at mask_own, batch generation and the engine at the sequence's words of the step.
+  const uint32_t* mask = nullptr;
+  size_t mask_words = 0;
+  std::vector<uint32_t> mask_own;
 };
 
 // AHA_OK, or AHA_ERR_INVALID with *why set: NaN temperature / top_p, top_k < 1 with its flag, repeat_last_n < 0, repeat_penalty <= 0.
@@ -68,5 +73,10 @@ void sampler_adjust_sync(HostSampler& s, const uint32_t* generated, size_t n_gen
 // non-zero bias or a count, a_i = (float)((double)b_i - (double)frequency * c_i - (double)presence * [c_i > 0]).  Returns its length.
 inline size_t sampler_adjust_bound(const HostSampler& s) { return s.adj.active ? s.adj.bias_ids.size() + s.adj.counts.size() : 0; }
 size_t sampler_adjust_list(const HostSampler& s, uint32_t* ids_out, float* vals_out);
+
+
+// allowed-token masks: true iff a set bit names an id < vocab_size among words[0 .. ceil(vocab_size / 32))
+bool token_mask_any(const uint32_t* words, size_t vocab_size);
+inline size_t token_mask_words(size_t vocab_size) { return (vocab_size + 31) / 32; }
 
 }  // namespace aha

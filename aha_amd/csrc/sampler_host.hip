@@ -215,6 +215,13 @@ size_t sampler_adjust_list(const HostSampler& s, uint32_t* ids_out, float* vals_
   return n;
 }
 
+bool token_mask_any(const uint32_t* words, size_t vocab_size) {
+  const size_t full = vocab_size / 32, rest = vocab_size % 32;
+  for (size_t i = 0; i < full; ++i)
+    if (words[i]) return true;
+  return rest && (words[full] & ((1u << rest) - 1u));
+}
+
 int host_sampler_init(HostSampler& s, const aha_sampling_params& p) {
   std::string why;
   if (sampling_params_check(p, &why)) {
@@ -226,6 +233,7 @@ int host_sampler_init(HostSampler& s, const aha_sampling_params& p) {
   s.rng.reset(r);
   s.words = 0;
   s.adj = LogitAdjust{};
+  s.mask = nullptr, s.mask_words = 0, s.mask_own.clear();
   // get_logit_processor (sample.rs:7-38): a temperature below 1e-7 means ArgMax whatever top_k / top_p say
   const bool has_t = !(p.temperature < 1e-7f), has_p = p.flags & AHA_SAMPLE_HAS_TOP_P, has_k = p.flags & AHA_SAMPLE_HAS_TOP_K;
   s.temperature = (double)p.temperature;
@@ -287,6 +295,19 @@ int sampler_pick(HostSampler& s, const float* vals, const uint32_t* idx, int k, 
     for (size_t i = 0; i < n; ++i)
       if (ids[i] < vocab_size) x[ids[i]] = x[ids[i]] + a[i];
   }
+  if (s.mask) {   // the allowed-token mask, after the addends: -inf on every id whose bit is clear
+    if (s.mask_words != token_mask_words(vocab_size)) {
+      set_error("sampler_pick: the mask has " + std::to_string(s.mask_words) + " words, a vocabulary of " + std::to_string(vocab_size) +
+                " needs " + std::to_string(token_mask_words(vocab_size)));
+      return AHA_ERR_INVALID;
+    }
+    if (!token_mask_any(s.mask, vocab_size)) {
+      set_error("sampler_pick: the mask allows no id below vocab_size");
+      return AHA_ERR_INVALID;
+    }
+    for (size_t i = 0; i < vocab_size; ++i)
+      if (!((s.mask[i >> 5] >> (i & 31)) & 1u)) x[i] = -INFINITY;
+  }
   return pick_from_logits(s, x, token_out);
 }
 
@@ -325,7 +346,7 @@ int aha_hip_sampler_plan(const aha_sampler* s, size_t vocab_size, size_t n_gener
   const bool argmax = s->s.kind == SAMPLE_ARGMAX;
   // an addend is live once the adjust has a non-zero bias or a token has been generated
   const bool live = s->s.adj.active && (!s->s.adj.bias_ids.empty() || n_generated > 0);
-  *k_out = argmax ? (pen != 1.0f || live ? 1 : 0) : sampler_candidates_needed(s->s, vocab_size);
+  *k_out = argmax ? (pen != 1.0f || live || s->s.mask ? 1 : 0) : sampler_candidates_needed(s->s, vocab_size);
   if (temperature_out) *temperature_out = argmax ? 0.f : (float)s->s.temperature;
   if (repeat_penalty_out) *repeat_penalty_out = pen;
   if (n_context_out) *n_context_out = n_ctx;
@@ -388,6 +409,29 @@ int aha_hip_sampler_adjust_list(aha_sampler* s, size_t vocab_size, const uint32_
     return AHA_OK;
   } catch (const std::bad_alloc&) {
     set_error("sampler_adjust_list: out of host memory");
+    return AHA_ERR_OOM;
+  }
+}
+
+int aha_hip_sampler_set_mask(aha_sampler* s, const uint32_t* words, size_t n_words) {
+  if (!s || (words && n_words == 0)) {
+    set_error("sampler_set_mask: null sampler, or a mask of 0 words");
+    return AHA_ERR_INVALID;
+  }
+  try {
+    if (!words) {
+      s->s.mask = nullptr, s->s.mask_words = 0, s->s.mask_own.clear();
+      return AHA_OK;
+    }
+    if (std::all_of(words, words + n_words, [](uint32_t w) { return w == 0; })) {
+      set_error("sampler_set_mask: the mask allows no id");
+      return AHA_ERR_INVALID;
+    }
+    s->s.mask_own.assign(words, words + n_words);
+    s->s.mask = s->s.mask_own.data(), s->s.mask_words = n_words;
+    return AHA_OK;
+  } catch (const std::bad_alloc&) {
+    set_error("sampler_set_mask: out of host memory");
     return AHA_ERR_OOM;
   }
 }

@@ -451,6 +451,18 @@ class HipInferenceModel:
         (aha_hip_generate_batch_adjusted; include/aha_hip.h states the definition).  params: None = greedy without any adjust, one
         SamplingParams for all, or one per prompt.  top_logprobs: None = no logprobs at all, else as generate_batch_logprobs.  Returns
         (token lists, logprobs or None[, step logits])."""
+        return self._generate_batch_adjusted(prompts, max_new, params, top_logprobs, data, max_tokens_per_pass, want_step_logits, None)
+
+    def generate_batch_masked(self, prompts: Sequence[Sequence[int]], max_new: int, constraint=None, params=None, top_logprobs=None,
+                              data=None, max_tokens_per_pass: int = 0, want_step_logits: bool = False):
+        """generate_batch_adjusted under a per-step allowed-token mask (aha_hip_generate_batch_masked; include/aha_hip.h states the
+        definition).  constraint: a callable (seq, generated) -> packed words (guided.pack_mask) or None, asked once per live prompt per
+        step -- generated is the prompt's token list so far, empty for the first token -- while the step's device work runs; None means
+        the step is unmasked, a negative int fails the call (AHA_ERR_STATE).  guided.ChoiceConstraint is one; constraint None is generate_batch_adjusted.  An exception the
+        constraint raises ends the call (the cache is cleared) and is raised again here."""
+        return self._generate_batch_adjusted(prompts, max_new, params, top_logprobs, data, max_tokens_per_pass, want_step_logits, constraint)
+
+    def _generate_batch_adjusted(self, prompts, max_new, params, top_logprobs, data, max_tokens_per_pass, want_step_logits, constraint):
         n = len(prompts)
         if data is not None and len(data) != n:
             raise ValueError(f"{len(data)} MultiModalData entries for {n} prompts")
@@ -479,10 +491,37 @@ class HipInferenceModel:
                     mm_arr[j] = C.addressof(mm)
         lp = None if top is None else (_lib.TokenLogprobs * max(n * max(int(max_new), 1), 1))()
 
+        raised = []
+
+        def on_mask(user, seq, generated, n_generated, words, n_words):   # aha_token_mask_fn
+            try:
+                got = constraint(int(seq), np.ctypeslib.as_array(generated, shape=(n_generated,)).tolist() if n_generated else [])
+                if got is None:
+                    return 0
+                if isinstance(got, (int, np.integer)) and got < 0:   # the C callback's own failure code: AHA_ERR_STATE names the prompt
+                    return int(got)
+                w = np.ascontiguousarray(got, dtype=np.uint32).reshape(-1)
+                if w.size != n_words:
+                    raise ValueError(f"the constraint returned {w.size} words for prompt {seq}, the vocabulary needs {n_words}")
+                C.memmove(words, w.ctypes.data, 4 * n_words)
+                return 1
+            except BaseException as e:   # (nothing may propagate through the C frames)
+                raised.append(e)
+                return -1
+        cb = None if constraint is None else _lib.TOKEN_MASK_FN(on_mask)
+
         def entry(handle, ids, lens, n_, mm_, cp_, mx, pas, toks, n_out, lg):
-            return lib().aha_hip_generate_batch_adjusted(handle, ids, lens, n_, mm_, cp_, adj, None if top is None else top.ctypes.data, mx, pas,
-                                                         toks, n_out, lg, lp)
-        res = self._generate_batch(entry, prompts, (mm_arr, cp), max_new, max_tokens_per_pass, "step" if want_step_logits else None)
+            if cb is None:
+                return lib().aha_hip_generate_batch_adjusted(handle, ids, lens, n_, mm_, cp_, adj, None if top is None else top.ctypes.data, mx,
+                                                             pas, toks, n_out, lg, lp)
+            return lib().aha_hip_generate_batch_masked(handle, ids, lens, n_, mm_, cp_, adj, None if top is None else top.ctypes.data, mx, pas,
+                                                       C.cast(cb, C.c_void_p), None, toks, n_out, lg, lp)
+        try:
+            res = self._generate_batch(entry, prompts, (mm_arr, cp), max_new, max_tokens_per_pass, "step" if want_step_logits else None)
+        except Exception:
+            if raised:
+                raise raised[0]
+            raise
         toks = res[0] if want_step_logits else res
         out = None
         if top is not None:
@@ -683,9 +722,10 @@ class HipEngine:
         self._n_cancel = 0
 
     def submit(self, input_ids: Sequence[int], max_new: int, params=None, data: Optional[MultiModalData] = None,
-               top_logprobs: Optional[int] = None) -> int:
+               top_logprobs: Optional[int] = None, mask=None) -> int:
         """Queue one request; returns its id.  params: None = greedy, else a sampling.SamplingParams; data: its MultiModalData;
-        top_logprobs: None, or 0..20 = report every token's log-probability and that many alternatives (step(want_logprobs=True))."""
+        top_logprobs: None, or 0..20 = report every token's log-probability and that many alternatives (step(want_logprobs=True));
+        mask: None, or the packed allowed-token words (guided.pack_mask) that govern its tokens from the first one until set_mask."""
         ids = np.ascontiguousarray(np.asarray(input_ids, dtype=np.uint32).reshape(-1))
         keep = [ids]
         mm_p = None
@@ -695,7 +735,15 @@ class HipEngine:
             mm_p = C.byref(mm)
         cp = None if params is None else C.byref(params.to_c())
         rid = C.c_uint64()
-        if params is not None and getattr(params, "adjust_active", False):   # logit_bias / presence / frequency: the arrays are copied
+        if mask is not None:
+            words = np.ascontiguousarray(mask, dtype=np.uint32).reshape(-1)
+            adj_p = None
+            if params is not None and getattr(params, "adjust_active", False):
+                adj, k = params.adjust_to_c()
+                adj_p = C.byref(adj)
+            check(lib().aha_hip_engine_submit_masked(self.handle, ids.ctypes.data, ids.size, mm_p, cp, adj_p, words.ctypes.data, words.size,
+                                                     int(max_new), -1 if top_logprobs is None else int(top_logprobs), C.byref(rid)))
+        elif params is not None and getattr(params, "adjust_active", False):   # logit_bias / presence / frequency: the arrays are copied
             adj, k = params.adjust_to_c()
             check(lib().aha_hip_engine_submit_adjusted(self.handle, ids.ctypes.data, ids.size, mm_p, cp, C.byref(adj), int(max_new),
                                                        -1 if top_logprobs is None else int(top_logprobs), C.byref(rid)))
@@ -709,6 +757,15 @@ class HipEngine:
         self._streams[rid.value] = []
         self._done[rid.value] = False
         return rid.value
+
+    def set_mask(self, req_id: int, mask) -> None:
+        """Replace the allowed-token mask of a waiting or running request (aha_hip_engine_set_mask): packed words (guided.pack_mask), or
+        None to clear it.  It stays until it is replaced and acts from the next token the request samples."""
+        if mask is None:
+            check(lib().aha_hip_engine_set_mask(self.handle, int(req_id), None, 0))
+            return
+        words = np.ascontiguousarray(mask, dtype=np.uint32).reshape(-1)
+        check(lib().aha_hip_engine_set_mask(self.handle, int(req_id), words.ctypes.data, words.size))
 
     def cancel(self, req_id: int) -> None:
         check(lib().aha_hip_engine_cancel(self.handle, int(req_id)))

@@ -385,3 +385,34 @@ def logprob_rows(logits: torch.Tensor, tokens, n_top):
     check(lib().aha_hip_logprob_rows(_ptr(logits), logits.stride(0), R, V, _ptr(tok), nn.ctypes.data, _ptr(out), _stream()))
     o = out.cpu().numpy()
     return (o[:, 0].copy().view(np.float32), o[:, 1].copy(), o[:, 2:22].copy().view(np.uint32), o[:, 22:42].copy().view(np.float32))
+
+
+def sample_rows_masked(logits: torch.Tensor, k, temperature, repeat_penalty, contexts, adjusts, masks: torch.Tensor, mask_rows):
+    """sample_rows_adjusted with allowed-token masks (aha_hip_sample_rows_masked): masks (n_masks, ceil(V / 32)) int32 / uint32 words on the
+    device -- id i of a mask is allowed iff bit i & 31 of word i >> 5 is set, bits at positions >= V are ignored -- and mask_rows[r] the
+    mask of row r, or -1 for none.  Every logit that is not allowed becomes -inf after the penalty and the addends.  adjusts None: no addends."""
+    if not logits.is_cuda or not masks.is_cuda:
+        raise ValueError("op inputs must be GPU tensors")
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.stride(0) >= logits.shape[1]   # (a row pitch)
+    R, V = logits.shape
+    W = (V + 31) // 32
+    assert masks.dim() == 2 and masks.shape[1] == W and masks.is_contiguous() and masks.element_size() == 4
+    mr = np.ascontiguousarray(np.asarray(mask_rows, dtype=np.int32).reshape(R))
+    assert ((mr >= -1) & (mr < masks.shape[0])).all(), "mask_rows name masks that do not exist"
+    adjusts = [([], [])] * R if adjusts is None else adjusts
+    assert len(adjusts) == R
+    kk = np.ascontiguousarray(np.asarray(k, dtype=np.int32).reshape(R))
+    tt = np.ascontiguousarray(np.asarray(temperature, dtype=np.float32).reshape(R))
+    pp = np.ascontiguousarray(np.asarray(repeat_penalty, dtype=np.float32).reshape(R))
+    off = np.ascontiguousarray(np.cumsum([0] + [len(c) for c in contexts]), dtype=np.uint64)
+    ctx = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.uint32).reshape(-1) for c in contexts] + [np.zeros(1, np.uint32)]))
+    aoff = np.ascontiguousarray(np.cumsum([0] + [len(a[0]) for a in adjusts]), dtype=np.uint64)
+    aid = np.ascontiguousarray(np.concatenate([np.asarray(a[0], dtype=np.uint32).reshape(-1) for a in adjusts] + [np.zeros(1, np.uint32)]))
+    aval = np.ascontiguousarray(np.concatenate([np.asarray(a[1], dtype=np.float32).reshape(-1) for a in adjusts] + [np.zeros(1, np.float32)]))
+    vals = torch.empty(R, 64, dtype=torch.float32, device=logits.device)
+    idx = torch.empty(R, 64, dtype=torch.int32, device=logits.device)
+    ms = torch.empty(R, 2, dtype=torch.float32, device=logits.device)
+    check(lib().aha_hip_sample_rows_masked(_ptr(logits), logits.stride(0), R, V, kk.ctypes.data, tt.ctypes.data, pp.ctypes.data, ctx.ctypes.data,
+                                           off.ctypes.data, aid.ctypes.data, aval.ctypes.data, aoff.ctypes.data, _ptr(masks), mr.ctypes.data,
+                                           _ptr(vals), _ptr(idx), _ptr(ms), _stream()))
+    return vals, idx, ms

@@ -182,6 +182,9 @@ class GenerationContext:
         self.presence_penalty = 0.0
         self.frequency_penalty = 0.0
         self.logit_bias: Dict[int, float] = {}
+        # the allowed-token mask of the next token (packed words as aha_amd.guided.pack_mask gives them), or None; the caller replaces it
+        # between tokens
+        self.token_mask: Optional[np.ndarray] = None
 
 
 def penalty_context(repeat_penalty: float, repeat_last_n: Optional[int], generated: Sequence[int]) -> Tuple[float, Sequence[int]]:
@@ -215,6 +218,23 @@ def logit_addends(presence_penalty: float, frequency_penalty: float, logit_bias:
     return np.asarray(ids, dtype=np.uint32), np.asarray(vals, dtype=np.float32)
 
 
+def apply_token_mask(logits: np.ndarray, words: np.ndarray) -> np.ndarray:
+    """Step 3b of include/aha_hip.h's guided-decoding definition on a full f32 vector (after the penalty and the addends): -inf on every
+    id whose bit is clear.  words: ceil(V / 32) uint32, id i at bit i & 31 of word i >> 5; bits at positions >= V are ignored.  A mask
+    of another length, or one without an allowed id below V, is an error."""
+    x = np.asarray(logits, dtype=np.float32).copy()
+    V = x.shape[0]
+    w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+    if w.size != (V + 31) // 32:
+        raise ValueError(f"the mask has {w.size} words, a vocabulary of {V} needs {(V + 31) // 32}")
+    ids = np.arange(V)
+    allowed = ((w[ids >> 5] >> (ids & 31).astype(np.uint32)) & np.uint32(1)).astype(bool)
+    if not allowed.any():
+        raise ValueError("the mask allows no id below vocab_size")
+    x[~allowed] = -np.inf
+    return x
+
+
 def draw_from_candidates(lp: "LogitsProcessor", w: np.ndarray, idx: np.ndarray) -> int:
     """The weighted draw over a candidate list, in the order candle draws in.  sample_topk / sample_topk_topp draw over the k
     selected probabilities in selection order and map the position back through `indices` -- the candidate order.  sample_topp
@@ -234,11 +254,12 @@ def sample_and_push(ctx: GenerationContext, model, argmax_token: int, generated:
     pen, pctx = penalty_context(ctx.repeat_penalty, ctx.repeat_last_n, generated)
     V = model.text_cfg.vocab_size
     adjusted = bool(getattr(ctx, "presence_penalty", 0.0) or getattr(ctx, "frequency_penalty", 0.0) or getattr(ctx, "logit_bias", None))
-    if lp.sampling.kind == "ArgMax" and pen == 1.0 and not adjusted:
+    mask = getattr(ctx, "token_mask", None)
+    if lp.sampling.kind == "ArgMax" and pen == 1.0 and not adjusted and mask is None:
         token = int(argmax_token)
     else:
-        # the single-sequence candidate step knows no addends: an adjusted request takes the full vector
-        k = 0 if adjusted else 1 if lp.sampling.kind == "ArgMax" else lp.candidates_needed(V)
+        # the single-sequence candidate step knows no addends and no masks: such a request takes the full vector
+        k = 0 if adjusted or mask is not None else 1 if lp.sampling.kind == "ArgMax" else lp.candidates_needed(V)
         token = None
         if k:
             vals, idx, mx, se = model.sample_candidates(pctx, pen, lp.sampling.temperature if lp.sampling.kind != "ArgMax" else 0.0, k)
@@ -260,6 +281,8 @@ def sample_and_push(ctx: GenerationContext, model, argmax_token: int, generated:
                 a_ids, a_vals = logit_addends(ctx.presence_penalty, ctx.frequency_penalty, ctx.logit_bias, generated, V)
                 logits = np.asarray(logits, dtype=np.float32)
                 logits[a_ids] = logits[a_ids] + a_vals
+            if mask is not None:   # after the addends: -inf on every id that is not allowed
+                logits = apply_token_mask(logits, mask)
             w, ids = lp.weights_from_logits(logits)
             pos = lp.draw(w)
             token = pos if ids is None else int(ids[pos])

@@ -482,6 +482,56 @@ int aha_hip_sampler_set_adjust(aha_sampler* s, const aha_logit_adjust* adjust);
 int aha_hip_sampler_adjust_list(aha_sampler* s, size_t vocab_size, const uint32_t* generated, size_t n_generated, uint32_t* ids_out,
                                 float* vals_out, size_t cap, size_t* n_out);
 
+/* ---- guided decoding: per-step allowed-token masks ----------------------------------------------------------------------------------
+ * What `response_format` / Structured Outputs (src/params/chat.rs:115-118,226 of the reference, declared and never acted on), guided
+ * choice, tool-call grammars and regex constraints need from the backend: the caller owns the grammar and hands over one bit per
+ * vocabulary id each step; the bits are applied inside the kernel that already reads the logits row.
+ * A token mask is W = ceil(V / 32) uint32_t words.  Id i is allowed iff bit i & 31 of word i >> 5 is set.  Bits at positions >= V in the
+ * last word are ignored, whatever they hold.  For one request and one step:
+ *   1-3. z = the row after the repeat penalty and the addends, steps 1-3 of the logit_bias definition above, unchanged.
+ *   3b.  z_i = -inf for every id i that is not allowed.
+ *   4.   The request's sampler runs on that z wherever it ran on z before: argmax (first maximal index), the candidates, max and sumexp
+ *        over the whole vocabulary, the top-p cut, the draw.  RNG consumption per token is unchanged.
+ *   5.   Logprobs keep their definition: the model's own distribution, from the raw logits.
+ * The first token is masked too.  Stop tokens are ordinary ids: the caller sets their bits when the constraint may end.
+ * A request with no mask, or a step for which the callback says "no mask", takes exactly the path it takes without this section.  A
+ * masked row is a candidate row (k = 1 for ArgMax), as a row with a live addend is; stage 1 of the candidate step takes one more
+ * instantiation for it, in which each wave loads its 16 mask words once.  A row that falls back to its full vector gets the mask on the
+ * host.  A mask with no allowed id < V is an error (AHA_ERR_INVALID); one that, together with -inf biases, leaves no finite logit is
+ * unspecified, like the all--inf row of the logprob section.
+ * Out of scope: grammars, regex and JSON-schema compilation (the caller's job: they feed the callback / set_mask);
+ * aha_hip_generate_batch_spec; the single-sequence aha_hip_sample_candidates; tensor-parallel models.
+ *
+ * aha_token_mask_fn: called on the host once per live sequence per step, the first token included (n_generated == 0), after the step's
+ * device work has been queued and before its candidate step is, so a grammar's work overlaps the forward pass.  `generated` are the
+ * sequence's tokens so far; mask_words (n_words == W) arrives holding that sequence's previous mask, the first time all ones.  Return 1:
+ * use mask_words; 0: this step is unmasked; negative: the call fails with AHA_ERR_STATE, naming the sequence and step.  A mask without an
+ * allowed id: AHA_ERR_INVALID, the same way.  The cache is cleared as on every error. */
+typedef int (*aha_token_mask_fn)(void* user, size_t seq, const uint32_t* generated, size_t n_generated, uint32_t* mask_words,
+                                 size_t n_words);
+/* aha_hip_generate_batch_adjusted plus the callback and its user pointer.  One device buffer of n_seqs x W words; a sequence's words
+ * (W * 4 bytes) are uploaded only when the callback returned 1.  mask_fn NULL: exactly aha_hip_generate_batch_adjusted. */
+int aha_hip_generate_batch_masked(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs,
+                                  const aha_mm_input* const* mm, const aha_sampling_params* params, const aha_logit_adjust* adjust,
+                                  const int32_t* top_logprobs, size_t max_new, size_t max_tokens_per_pass, aha_token_mask_fn mask_fn,
+                                  void* mask_user, uint32_t* tokens_out, size_t* n_out, float* step_logits_out,
+                                  aha_token_logprobs* logprobs_out);
+/* aha_hip_engine_submit_adjusted plus an initial mask (mask_words NULL: none; copied), which governs the first token.
+ * aha_hip_engine_set_mask: callable between steps for a waiting or running request; the mask (copied) stays until it is replaced, words
+ * NULL clears it, and it acts from the next token the request samples.  AHA_ERR_INVALID before any device work: an unknown, cancelled or
+ * ended id, n_words != W, no allowed id.  A request's mask lives and dies with the request: a slot taken by the next request starts
+ * unmasked, a cancelled request leaves nothing behind.  aha_hip_engine_step / _step_logprobs are unchanged and, on an engine without
+ * masks, so are their launches. */
+int aha_hip_engine_submit_masked(aha_engine* e, const uint32_t* input_ids, size_t n_ids, const aha_mm_input* mm,
+                                 const aha_sampling_params* params, const aha_logit_adjust* adjust, const uint32_t* mask_words,
+                                 size_t n_mask_words, size_t max_new, int32_t top_logprobs, uint64_t* req_id);
+int aha_hip_engine_set_mask(aha_engine* e, uint64_t req_id, const uint32_t* words, size_t n_words);
+/* The host sampler with a mask (copied; words NULL clears it; AHA_ERR_INVALID for n_words == 0 or all-zero words).  aha_hip_sampler_plan
+ * then returns k_out = 1 for an ArgMax sampler; aha_hip_sampler_pick applies the mask in its full-vector path, after the addends
+ * (AHA_ERR_INVALID if n_words != ceil(vocab_size / 32) or no id < vocab_size is allowed) -- candidates passed to it must come from
+ * aha_hip_sample_rows_masked with the same words. */
+int aha_hip_sampler_set_mask(aha_sampler* s, const uint32_t* words, size_t n_words);
+
 /* ---- checkpoint directory -> model (XxxGenerateModel::init minus tokenizer / chat template) --------------------------
  * aha_hip_config_parse: <dir>/config.json -> aha_model_desc, the same field mapping serde does into Qwen3Config
  *   (/root/reference/src/models/qwen3/config.rs:4-27), Qwen3VLConfig (qwen3vl/config.rs:51-133, text_config / vision_config,
@@ -763,6 +813,14 @@ int aha_hip_sample_rows_adjusted(const float* logits, int64_t ld, int32_t R, int
                                  const float* repeat_penalty, const uint32_t* context, const size_t* context_offsets,
                                  const uint32_t* adj_ids, const float* adj_vals, const size_t* adj_offsets, float* vals_out,
                                  uint32_t* idx_out, float* ms_out, void* stream);
+/* aha_hip_sample_rows_adjusted plus allowed-token masks (the definition is in the guided-decoding section): masks is DEVICE memory,
+ * n_masks x ceil(V / 32) words, only read; mask_rows is HOST, R entries: the mask index of row r, or -1 for none.  adj_offsets may be
+ * NULL (no addends).  A row without a mask gives bit-identical outputs to aha_hip_sample_rows_adjusted, and so does an all-ones mask;
+ * entries past the number of allowed ids have value -inf; a row left without a finite logit is unspecified. */
+int aha_hip_sample_rows_masked(const float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* k, const float* temperature,
+                               const float* repeat_penalty, const uint32_t* context, const size_t* context_offsets, const uint32_t* adj_ids,
+                               const float* adj_vals, const size_t* adj_offsets, const uint32_t* masks, const int32_t* mask_rows,
+                               float* vals_out, uint32_t* idx_out, float* ms_out, void* stream);
 /* D7 prefill attention, causal with q position i attending to k positions <= kv_offset + i; q (S, nh*d),
  * k/v (L, kvh*d) token-major, L = kv_offset + S.  causal = 0 gives full (ViT / audio encoder) attention.  d = 128, or 64 with
  * nh == kvh (the Qwen3-ASR audio encoder's geometry). */

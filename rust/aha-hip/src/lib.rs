@@ -169,6 +169,11 @@ pub mod sys {
 
     pub const AHA_MAX_LOGIT_BIAS: usize = 1024;
 
+    /// `aha_token_mask_fn`: asked once per live sequence per step for the sequence's allowed-token mask (`n_words` = ceil(V / 32) packed
+    /// words in `mask_words`, holding its previous mask).  1: use them; 0: this step is unmasked; negative: the call fails.  Like the
+    /// rest of this crate it has never been compiled here (no Rust toolchain): it is written against include/aha_hip.h by hand.
+    pub type AhaTokenMaskFn =
+        unsafe extern "C" fn(user: *mut c_void, seq: usize, generated: *const u32, n_generated: usize, mask_words: *mut u32, n_words: usize) -> i32;
     /// `aha_logit_adjust`: a request's `presence_penalty`, `frequency_penalty` and `logit_bias` (ids / values, `n_bias` of them; a value
     /// of -inf bans the token).  Both penalties 0 and `n_bias` 0: inactive.
     #[repr(C)]
@@ -386,6 +391,24 @@ pub mod sys {
             step_logits_out: *mut f32,
             logprobs_out: *mut AhaTokenLogprobs,
         ) -> i32;
+        pub fn aha_hip_generate_batch_masked(
+            m: *mut AhaModel,
+            ids: *const u32,
+            seq_lens: *const usize,
+            n_seqs: usize,
+            mm: *const *const AhaMmInput,
+            params: *const AhaSamplingParams,
+            adjust: *const AhaLogitAdjust,
+            top_logprobs: *const i32,
+            max_new: usize,
+            max_tokens_per_pass: usize,
+            mask_fn: Option<AhaTokenMaskFn>,
+            mask_user: *mut c_void,
+            tokens_out: *mut u32,
+            n_out: *mut usize,
+            step_logits_out: *mut f32,
+            logprobs_out: *mut AhaTokenLogprobs,
+        ) -> i32;
         pub fn aha_hip_generate_batch_spec(
             m: *mut AhaModel,
             ids: *const u32,
@@ -445,6 +468,20 @@ pub mod sys {
             top_logprobs: i32,
             req_id: *mut u64,
         ) -> i32;
+        pub fn aha_hip_engine_submit_masked(
+            e: *mut AhaEngine,
+            ids: *const u32,
+            n_ids: usize,
+            mm: *const AhaMmInput,
+            params: *const AhaSamplingParams,
+            adjust: *const AhaLogitAdjust,
+            mask_words: *const u32,
+            n_mask_words: usize,
+            max_new: usize,
+            top_logprobs: i32,
+            req_id: *mut u64,
+        ) -> i32;
+        pub fn aha_hip_engine_set_mask(e: *mut AhaEngine, req_id: u64, words: *const u32, n_words: usize) -> i32;
         pub fn aha_hip_engine_cancel(e: *mut AhaEngine, req_id: u64) -> i32;
         pub fn aha_hip_engine_step(e: *mut AhaEngine, ev: *mut AhaEngineEvent, cap: usize, n_ev: *mut usize, logits_out: *mut f32) -> i32;
         pub fn aha_hip_engine_step_logprobs(
@@ -500,6 +537,27 @@ pub mod sys {
             ms_out: *mut f32,
             stream: *mut c_void,
         ) -> i32;
+        pub fn aha_hip_sample_rows_masked(
+            logits: *const f32,
+            ld: i64,
+            rows: i32,
+            vocab: i32,
+            k: *const i32,
+            temperature: *const f32,
+            repeat_penalty: *const f32,
+            context: *const u32,
+            context_offsets: *const usize,
+            adj_ids: *const u32,
+            adj_vals: *const f32,
+            adj_offsets: *const usize,
+            masks: *const u32,
+            mask_rows: *const i32,
+            vals_out: *mut f32,
+            idx_out: *mut u32,
+            ms_out: *mut f32,
+            stream: *mut c_void,
+        ) -> i32;
+        pub fn aha_hip_sampler_set_mask(s: *mut AhaSampler, words: *const u32, n_words: usize) -> i32;
         pub fn aha_hip_sampler_set_adjust(s: *mut AhaSampler, adjust: *const AhaLogitAdjust) -> i32;
         pub fn aha_hip_sampler_adjust_list(
             s: *mut AhaSampler,
@@ -557,7 +615,7 @@ pub mod sys {
     }
 }
 
-use std::ffi::{c_char, CStr, CString};
+use std::ffi::{c_char, c_void, CStr, CString};
 use std::fmt;
 
 /// Non-zero status of the library + its thread-local message (`aha_hip_last_error`)
@@ -1099,6 +1157,70 @@ impl Model {
         Ok((tokens, logprobs))
     }
 
+    /// `generate_batch_adjusted` under a per-step allowed-token mask (aha_hip_generate_batch_masked; include/aha_hip.h states the
+    /// definition).  `constraint(seq, generated, words)` is called once per live prompt per step, the first token included, while the
+    /// step's device work runs: `words` (ceil(V / 32) of them; id i is bit `i & 31` of word `i >> 5`) holds that prompt's previous mask,
+    /// all ones the first time.  It returns `Ok(true)` to use `words`, `Ok(false)` for an unmasked step, `Err(())` to fail the call.
+    /// A grammar / JSON-schema / regex automaton lives in the closure; this crate compiles none.
+    pub fn generate_batch_masked<F: FnMut(usize, &[u32], &mut [u32]) -> Result<bool, ()>>(
+        &mut self,
+        prompts: &[&[u32]],
+        params: Option<&[sys::AhaSamplingParams]>,
+        adjust: Option<&[LogitAdjust]>,
+        max_new: usize,
+        max_tokens_per_pass: usize,
+        mut constraint: F,
+    ) -> Result<Vec<Vec<u32>>, Error> {
+        if adjust.map_or(false, |a| a.len() != prompts.len()) || params.map_or(false, |p| p.len() != prompts.len()) {
+            return Err(Error { code: -1, message: format!("adjust / params entries do not match {} prompts", prompts.len()) });
+        }
+        unsafe extern "C" fn trampoline<F: FnMut(usize, &[u32], &mut [u32]) -> Result<bool, ()>>(
+            user: *mut c_void,
+            seq: usize,
+            generated: *const u32,
+            n_generated: usize,
+            mask_words: *mut u32,
+            n_words: usize,
+        ) -> i32 {
+            let f = &mut *(user as *mut F);
+            let gen: &[u32] = if n_generated == 0 { &[] } else { std::slice::from_raw_parts(generated, n_generated) };
+            let words = std::slice::from_raw_parts_mut(mask_words, n_words);
+            // a panic must not unwind through the C frames
+            match std::panic::catch_unwind(std::panic::AssertUnwindSafe(|| f(seq, gen, words))) {
+                Ok(Ok(true)) => 1,
+                Ok(Ok(false)) => 0,
+                _ => -1,
+            }
+        }
+        let adj: Option<Vec<sys::AhaLogitAdjust>> = adjust.map(|a| a.iter().map(|a| a.as_c()).collect());
+        let ids: Vec<u32> = prompts.iter().flat_map(|s| s.iter().copied()).collect();
+        let lens: Vec<usize> = prompts.iter().map(|s| s.len()).collect();
+        let width = max_new.max(1);
+        let mut toks = vec![0u32; prompts.len() * width];
+        let mut n_out = vec![0usize; prompts.len()];
+        check(unsafe {
+            sys::aha_hip_generate_batch_masked(
+                self.model,
+                ids.as_ptr(),
+                lens.as_ptr(),
+                lens.len(),
+                std::ptr::null(),
+                params.map_or(std::ptr::null(), |p| p.as_ptr()),
+                adj.as_ref().map_or(std::ptr::null(), |a| a.as_ptr()),
+                std::ptr::null(),
+                max_new,
+                max_tokens_per_pass,
+                Some(trampoline::<F>),
+                &mut constraint as *mut F as *mut c_void,
+                toks.as_mut_ptr(),
+                n_out.as_mut_ptr(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+            )
+        })?;
+        Ok(n_out.iter().enumerate().map(|(j, &n)| toks[j * max_new..j * max_new + n].to_vec()).collect())
+    }
+
     /// The greedy loop of `generate_generic` / `generate_stream_generic` (common/generate.rs:115-159, 161-368) kept on the
     /// device in chunks of `chunk` tokens: `on_token` sees every token in order (what a streaming response forwards) and
     /// returns `false` to stop; an eos id stops after it has been delivered, as in the reference.
@@ -1234,6 +1356,42 @@ impl<'a> Engine<'a> {
             )
         })?;
         Ok(id)
+    }
+    /// `submit_adjusted` plus an initial allowed-token mask (ceil(V / 32) packed words, copied), which governs the request's tokens from
+    /// the first one until `set_mask` replaces or clears it.
+    pub fn submit_masked(
+        &mut self,
+        ids: &[u32],
+        params: Option<&sys::AhaSamplingParams>,
+        adjust: Option<&LogitAdjust>,
+        mask: Option<&[u32]>,
+        max_new: usize,
+        top_logprobs: Option<u32>,
+    ) -> Result<u64, Error> {
+        let mut id = 0u64;
+        let p = params.map_or(std::ptr::null(), |p| p as *const _);
+        let a = adjust.map(|a| a.as_c());
+        check(unsafe {
+            sys::aha_hip_engine_submit_masked(
+                self.e,
+                ids.as_ptr(),
+                ids.len(),
+                std::ptr::null(),
+                p,
+                a.as_ref().map_or(std::ptr::null(), |a| a as *const _),
+                mask.map_or(std::ptr::null(), |m| m.as_ptr()),
+                mask.map_or(0, |m| m.len()),
+                max_new,
+                top_logprobs.map_or(-1, |n| n as i32),
+                &mut id,
+            )
+        })?;
+        Ok(id)
+    }
+    /// Replace (`Some(words)`) or clear (`None`) the mask of a waiting or running request, between steps: it acts from the next token the
+    /// request samples and stays until it is replaced.  A server drives its grammar from the streamed tokens and calls this each step.
+    pub fn set_mask(&mut self, req_id: u64, mask: Option<&[u32]>) -> Result<(), Error> {
+        check(unsafe { sys::aha_hip_engine_set_mask(self.e, req_id, mask.map_or(std::ptr::null(), |m| m.as_ptr()), mask.map_or(0, |m| m.len())) })
     }
     pub fn cancel(&mut self, req_id: u64) -> Result<(), Error> {
         check(unsafe { sys::aha_hip_engine_cancel(self.e, req_id) })?;
