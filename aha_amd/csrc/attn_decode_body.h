@@ -40,7 +40,12 @@ __device__ __forceinline__ float split_sum16(const float (&v)[16]) {
 //   * every length-dependent scalar (cache length, slot, rope table of the step) arrives as a kernel ARGUMENT or from a
 //     table the step's first kernel wrote -- no dependent scalar loads, no sincos, in front of the first page request;
 //   * the prologue's own inputs (qkv, norm weights, rope table: L2 hits) are requested first, the unit's first page
-//     right behind them (returns are in order within a wave), and the norm/rope arithmetic runs under the page fetch;
+//     right behind them (returns are in order within a wave), and the norm/rope arithmetic runs under the page fetch.
+//     That needs counted waits (vmcnt >= the page's 32 loads) up to the barrier that ends the prologue, and the compiler
+//     only counts what is outstanding on EVERY path: so no global load sits under a run-time condition there.  Every
+//     wave requests the inputs of its first AND second prologue item (clamped to the k head), every thread a v element,
+//     and every wave a page: a unit without one requests an existing page (clamped index) and skips only the compute.
+//     Conditions guard LDS writes only.  (Heads beyond two rounds, g >= 8, are done behind the barrier.)
 //   * in the page loop K and V of a page are separate register buffers re-requested as soon as their MFMAs have
 //     consumed them (K(next) right after QK^T, V(next) right after P.V), so a wave always has 16-32 KB in flight.
 // smem: ATTN_DECODE_FUSED_LDS bytes, 16-byte aligned.  Returns true in the one block per kv head that wrote the output.
@@ -90,8 +95,14 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
   const bf16_t px0 = p_src[lane], px1 = p_src[lane + 64];
   const bf16_t pw0 = p_nw[lane], pw1 = p_nw[lane + 64];
   const float cs = a.rope[lane], sn = a.rope[64 + lane];   // bf16-representable values (rope_step_kernel)
-  bf16_t vnew = 0;
-  if (tid < 128) vnew = qkv[(int64_t)(a.nh + a.kvh + kvhd) * 128 + tid];
+  // second item (g >= 4: a further q head, or the k head for wave g - 4): requested by every wave, the k head where there is none
+  const int hs2 = wave + NW;
+  const bool p2_is_k = hs2 >= g;
+  const bf16_t* p2_src = p2_is_k ? qkv + (int64_t)(a.nh + kvhd) * 128 : qkv + (int64_t)(kvhd * g + min(hs2, g - 1)) * 128;
+  const bf16_t* p2_nw = (const bf16_t*)(p2_is_k ? a.k_norm_w : a.q_norm_w);
+  const bf16_t p2x0 = p2_src[lane], p2x1 = p2_src[lane + 64];
+  const bf16_t p2w0 = p2_nw[lane], p2w1 = p2_nw[lane + 64];
+  const bf16_t vnew = qkv[(int64_t)(a.nh + a.kvh + kvhd) * 128 + (tid & 127)];   // waves 2, 3: a second copy, not stored
 
   u32x4_t kf[4][4], vf[8][2];
   // Addresses: wave-uniform 64-bit base (scalar registers) + ONE 32-bit per-lane offset (lane * 16), the rest immediates:
@@ -104,8 +115,12 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
 #pragma unroll
     for (int sub = 0; sub < 4; ++sub)
 #pragma unroll
-      for (int k4 = 0; k4 < 4; ++k4)
+      for (int k4 = 0; k4 < 4; ++k4) {
         kf[sub][k4] = __builtin_nontemporal_load(reinterpret_cast<gptr16_t>(kb + (sub * 4 + k4) * 1024 + l_off));
+        // issue order = the order QK^T consumes them (left alone, the compiler requests fragment 0 fifteenth and the first MFMA waits for
+        // nearly the whole of K)
+        __builtin_amdgcn_sched_barrier(0);
+      }
   };
   auto load_v = [&](uint64_t base) {
     gchar_t vb = reinterpret_cast<gchar_t>(base + (uint64_t)a.kvh * KV_PAGE_TOKENS * 256 + (uint64_t)kvhd * 128 * (KV_PAGE_TOKENS * 2));
@@ -119,10 +134,13 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
   // broadcast per iteration with v_readlane.  (A load of page_ptrs[page] inside the loop is a VECTOR load -- the kernel also
   // stores, so the compiler will not use the scalar cache -- and its wait drains the K/V requests queued behind it.)
   uint64_t my_pages = 0;
+  // Lanes beyond the unit's last page hold the pointer of an existing page (clamped index; with no old token at all, L_old = 0, that
+  // is page 0, the append slot's): no load under a condition, and a unit without a page has an address it may request from.
+  const int page_clamp = max(npages - 1, 0);
   auto fetch_page_ptrs = [&](int first_it) {
     if (LINEAR) return;
     const int pg = unit + (first_it + lane) * nunits;
-    my_pages = pg < npages ? (uint64_t)(a.kv.page_ptrs[pg] + a.kv.layer_off) : 0;
+    my_pages = (uint64_t)(a.kv.page_ptrs[min(pg, page_clamp)] + a.kv.layer_off);
   };
   auto page_base = [&](int i) {
     if (LINEAR) return a.lin_page0 + (uint64_t)((int64_t)(unit + i * nunits) * a.lin_step);
@@ -131,8 +149,9 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
   };
   fetch_page_ptrs(0);
   int page = unit, it = 0;
-  if (page < npages) {
-    const uint64_t b0 = page_base(0);
+  {
+    // unconditional: a unit without a page (page >= npages) requests the clamped page and never looks at what arrives
+    const uint64_t b0 = LINEAR ? a.lin_page0 + (uint64_t)((int64_t)min(unit, page_clamp) * a.lin_step) : page_base(0);
     __builtin_amdgcn_sched_barrier(0);  // K strictly ahead of V (as in the loop): the loop's counted waits assume that order
     load_k(b0);
     __builtin_amdgcn_sched_barrier(0);
@@ -154,15 +173,19 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
       dst[lane + 64] = y1;
     };
     if (p_have) norm_rope(px0, px1, pw0, pw1, p_is_k ? ksn : qs + wave * 128);
-    for (int hs = wave + NW; hs <= g; hs += NW) {  // more heads than waves (g >= 4): a second round for some waves
-      const bool is_k = hs == g;
-      const bf16_t* src = is_k ? qkv + (int64_t)(a.nh + kvhd) * 128 : qkv + (int64_t)(kvhd * g + hs) * 128;
-      const bf16_t* nw = (const bf16_t*)(is_k ? a.k_norm_w : a.q_norm_w);
-      norm_rope(src[lane], src[lane + 64], nw[lane], nw[lane + 64], is_k ? ksn : qs + hs * 128);
-    }
+    if (hs2 <= g) norm_rope(p2x0, p2x1, p2w0, p2w1, p2_is_k ? ksn : qs + hs2 * 128);  // more heads than waves (g >= 4): a second round
     if (tid < 128) vsn[tid] = vnew;
+    __syncthreads();
+    if (g >= 2 * NW) {  // further rounds (block-uniform): loads under a condition, so behind the barrier that ends the straight-line part
+      for (int hs = wave + 2 * NW; hs <= g; hs += NW) {
+        const bool is_k = hs == g;
+        const bf16_t* src = is_k ? qkv + (int64_t)(a.nh + kvhd) * 128 : qkv + (int64_t)(kvhd * g + hs) * 128;
+        const bf16_t* nw = (const bf16_t*)(is_k ? a.k_norm_w : a.q_norm_w);
+        norm_rope(src[lane], src[lane + 64], nw[lane], nw[lane + 64], is_k ? ksn : qs + hs * 128);
+      }
+      __syncthreads();
+    }
   }
-  __syncthreads();
   stamp(1);
   if (APPEND && split == 0) {  // append (k roped, v raw) for the following steps
     // global address space spelled out: a flat store here would make every later wait in the kernel a vmcnt(0)

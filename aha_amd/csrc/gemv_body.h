@@ -21,7 +21,9 @@ __device__ __forceinline__ int xs_index(int k) {
 // xs: LDS, (ceil(K/512)*512 + 16) floats.  bid/nblk: this block's index in, and the size of, the persistent grid.
 // after_issue() runs once the block's first weight tile has been requested and before anything that depends on the
 // activation vector -- the stand-alone kernel passes a no-op, the persistent kernel waits on its grid barrier there.
-template <int R, int U, int EPI, bool COH, bool FAST, class AfterIssue>
+// PRO (stand-alone FAST kernels only; the host picks it): 1 = no norm weights, K <= 8 * 2048; 2 = with norm weights, K <= 4 * 2048: the
+// prologue's inputs and the first weight tile are requested in straight-line code (see below).  0 = the general form.
+template <int R, int U, int EPI, bool COH, bool FAST, int PRO = 0, class AfterIssue>
 __device__ __forceinline__ void gemv_body(const GemvArgs& a, float* xs, const int bid, const int nblk, AfterIssue&& after_issue) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K, N = a.N;
@@ -94,24 +96,52 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, float* xs, const in
   // Memory returns are IN ORDER within a wave: a load issued behind the first weight tile only returns after that
   // tile has arrived (several microseconds under a chip-wide burst).  The activation vector and the norm weights the
   // prologue needs are therefore requested FIRST (stand-alone kernels, K <= 8 * 2048), the weight tile right behind them.
+  // PRO != 0: and the prologue runs UNDER that tile.  For that every wait between here and the barrier that ends the prologue
+  // has to be a counted one that leaves the tile's R * U * NW loads in flight, and the compiler only counts what it can see on
+  // every path: a global load under a run-time branch (`if (v * 8 < K)`, `if (norm_w)`, `if (ngroups > 0)`, a run-time `pre`)
+  // gives the join two arms with different numbers of outstanding loads, and every staging step then waits vmcnt(0) -- for
+  // the whole tile.  So in this form nothing is loaded under a condition: x and the norm weights come from clamped indices
+  // (K is a multiple of 512 in the FAST form: a vector is either whole or absent, and an absent one is never staged), "has
+  // norm weights" is a template parameter, the first tile is requested unconditionally (the grid never exceeds the tile
+  // count; rows are clamped anyway), and sched_barriers pin the order: prologue inputs, tile, staging.  Conditions only
+  // guard LDS writes (tests/test_decode_prologue_waits_cpu.py reads the waits off the code object).
   constexpr int XPRE = 8;
-  const bool pre = !COH && (nchunks << 6) <= XPRE * GEMV_THREADS;
+  constexpr bool SL = PRO != 0, SL_NORM = PRO == 2;
+  // vectors per thread of the straight-line form: ALL of them are requested (clamped: at K = 4096 two per thread are real), in front
+  // of the weight tile, so with norm weights (two requests per vector) half as many: 8 requests either way.  A norm in front of a
+  // matvec is over the hidden size: 8192 covers every model this project loads, and a wider one takes the general form.
+  constexpr int XSL = SL_NORM ? 4 : XPRE;
+  static_assert(!SL || (FAST && !COH), "the straight-line prologue is a form of the stand-alone FAST kernel");
+  const bool pre = SL || (!COH && (nchunks << 6) <= XPRE * GEMV_THREADS);
   u32x4_t xpre[XPRE], npre[XPRE];
-  if (pre) {
-#pragma unroll
-    for (int j = 0; j < XPRE; ++j) {
-      const int v = tid + j * GEMV_THREADS;
-      xpre[j] = u32x4_t{0u, 0u, 0u, 0u};
-      npre[j] = u32x4_t{0u, 0u, 0u, 0u};
-      if (v * 8 < K) {
-        xpre[j] = ld16((const bf16_t*)a.x + v * 8);
-        if (a.norm_w != nullptr) npre[j] = ld16((const bf16_t*)a.norm_w + v * 8);
-      }
-    }
-  }
   u32x4_t bufA[U][NW][R], bufB[U][NW][R];
   bf16_t resA[R], resB[R];   // FAST + GEMV_RESIDUAL: the residual values of the buffer's tile, requested with it
-  if (ngroups > 0) issue(0, bufA, resA);
+  if (SL) {
+    const int vlast = (K >> 3) - 1;
+#pragma unroll
+    for (int j = 0; j < XSL; ++j) {
+      const int v = min(tid + j * GEMV_THREADS, vlast);
+      xpre[j] = ld16((const bf16_t*)a.x + v * 8);
+      if (SL_NORM) npre[j] = ld16((const bf16_t*)a.norm_w + v * 8);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    issue(0, bufA, resA);
+    __builtin_amdgcn_sched_barrier(0);
+  } else {
+    if (pre) {
+#pragma unroll
+      for (int j = 0; j < XPRE; ++j) {
+        const int v = tid + j * GEMV_THREADS;
+        xpre[j] = u32x4_t{0u, 0u, 0u, 0u};
+        npre[j] = u32x4_t{0u, 0u, 0u, 0u};
+        if (v * 8 < K) {
+          xpre[j] = ld16((const bf16_t*)a.x + v * 8);
+          if (a.norm_w != nullptr) npre[j] = ld16((const bf16_t*)a.norm_w + v * 8);
+        }
+      }
+    }
+    if (ngroups > 0) issue(0, bufA, resA);
+  }
   stamp(1);
   after_issue();  // grid barrier of the persistent decode kernel: the first weight tile is already in flight
 
@@ -132,7 +162,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, float* xs, const in
     };
     if (pre) {
 #pragma unroll
-      for (int it = 0; it < XPRE; ++it) {
+      for (int it = 0; it < (SL ? XSL : XPRE); ++it) {
         const int v = tid + it * GEMV_THREADS;
         if (v < (nchunks << 6)) stage(v, xpre[it]);
       }
@@ -143,7 +173,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, float* xs, const in
         stage(v, xv);
       }
     }
-    if (nw != nullptr) {
+    if (SL ? SL_NORM : nw != nullptr) {
       ss = wave_sum(ss);
       if (lane == 0) red[wave] = ss;
       __syncthreads();
@@ -166,7 +196,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, float* xs, const in
       };
       if (pre) {
 #pragma unroll
-        for (int it = 0; it < XPRE; ++it) {
+        for (int it = 0; it < (SL ? XSL : XPRE); ++it) {
           const int v = tid + it * GEMV_THREADS;
           if (v < (K >> 3)) norm(v, npre[it]);
         }

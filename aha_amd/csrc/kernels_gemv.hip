@@ -35,7 +35,8 @@ struct GemvTailArgs {
   int cached;
 };
 
-template <int R, int U, int EPI, bool FAST, bool TRACE>
+// PRO (gemv_body.h): 0 = the general prologue; 1 / 2 = the straight-line one, without / with norm weights (FAST only, K <= 8 / 4 * 2048).
+template <int R, int U, int EPI, bool FAST, bool TRACE, int PRO>
 __global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel(const void* W, const void* x, const void* norm_w, void* y, const void* aux, int N,
                                                             int K, float eps, int nblk, GemvTailArgs t) {
   extern __shared__ __attribute__((aligned(16))) float xs[];  // K f32 + 8 floats reduction scratch
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel(const void* W, const
   a.W = W; a.W2 = EPI == GEMV_SILU_MUL ? aux : nullptr; a.x = x; a.norm_w = norm_w; a.residual = EPI == GEMV_SILU_MUL ? nullptr : aux; a.y = y;
   a.y_f32 = t.y_f32; a.blk_max = t.blk_max; a.blk_idx = t.blk_idx; a.h_out = t.h_out; a.N = N; a.K = K; a.eps = eps; a.cached = t.cached;
   a.trace = TRACE ? t.trace : nullptr;
-  gemv_body<R, U, EPI, false, FAST>(a, xs, (int)blockIdx.x, nblk, [] {});
+  gemv_body<R, U, EPI, false, FAST, PRO>(a, xs, (int)blockIdx.x, nblk, [] {});
 }
 
 struct GemvPlan { int R, U, grid; };
@@ -112,14 +113,18 @@ static void launch_gemv_epi(const GemvArgs& a, const GemvPlan& p, hipStream_t st
   const bool fast = fast_ok && a.K % (512 * p.U) == 0 && !a.cached && a.N >= 1;
   const GemvTailArgs t{a.y_f32, a.blk_max, a.blk_idx, a.h_out, a.trace, a.cached};
   const void* aux = EPI == GEMV_SILU_MUL ? a.W2 : a.residual;
-#define GV_(RR, UU, FF, TT) \
-  hipLaunchKernelGGL((gemv_kernel<RR, UU, EPI, FF, TT>), grid, block, lds, st, a.W, a.x, a.norm_w, a.y, aux, a.N, a.K, a.eps, p.grid, t)
+  // straight-line prologue (gemv_body.h): the FAST form whose activation vector fits the preloaded vectors, 8 per thread, 4 with norm weights
+  const int pro = fast && a.K <= (a.norm_w != nullptr ? 4 : 8) * 8 * GEMV_THREADS ? (a.norm_w != nullptr ? 2 : 1) : 0;
+#define GV_(RR, UU, FF, TT, PP) \
+  hipLaunchKernelGGL((gemv_kernel<RR, UU, EPI, FF, TT, PP>), grid, block, lds, st, a.W, a.x, a.norm_w, a.y, aux, a.N, a.K, a.eps, p.grid, t)
 #define GV(RR, UU)                                                      \
   do {                                                                  \
     if (a.trace == nullptr) {                                           \
-      if (fast) GV_(RR, UU, true, false); else GV_(RR, UU, false, false); \
+      if (pro == 2) GV_(RR, UU, true, false, 2); else if (pro == 1) GV_(RR, UU, true, false, 1);      \
+      else if (fast) GV_(RR, UU, true, false, 0); else GV_(RR, UU, false, false, 0);                  \
     } else {                                                            \
-      if (fast) GV_(RR, UU, true, true); else GV_(RR, UU, false, true);   \
+      if (pro == 2) GV_(RR, UU, true, true, 2); else if (pro == 1) GV_(RR, UU, true, true, 1);        \
+      else if (fast) GV_(RR, UU, true, true, 0); else GV_(RR, UU, false, true, 0);                    \
     }                                                                   \
   } while (0)
   if (p.R == 4) {
