@@ -762,7 +762,7 @@ struct DevFree {   // device buffers released when the call returns, on the erro
 static int sample_rows_impl(const float* logits, int64_t ld, int32_t R, int32_t V, const int32_t* k, const float* temperature,
                             const float* repeat_penalty, const uint32_t* context, const size_t* context_offsets, const uint32_t* adj_ids,
                             const float* adj_vals, const size_t* adj_offsets, float* vals_out, uint32_t* idx_out, float* ms_out, void* stream,
-                            const uint32_t* masks = nullptr, const int32_t* mask_rows = nullptr) {
+                            const uint32_t* masks, const int32_t* mask_rows) {
   if (!logits || R < 1 || V < 1 || ld < V || !k || !temperature || !repeat_penalty || !context_offsets || !vals_out || !idx_out || !ms_out) {
     set_error("sample_rows: bad arguments (R >= 1, ld >= V >= 1, per-row k / temperature / repeat_penalty / context_offsets, outputs)");
     return AHA_ERR_INVALID;
@@ -876,7 +876,7 @@ int aha_hip_sample_rows(const float* logits, int64_t ld, int32_t R, int32_t V, c
                         uint32_t* idx_out, float* ms_out, void* stream) {
   API_GUARD_BEGIN
   return sample_rows_impl(logits, ld, R, V, k, temperature, repeat_penalty, context, context_offsets, nullptr, nullptr, nullptr, vals_out, idx_out,
-                          ms_out, stream);
+                          ms_out, stream, nullptr, nullptr);
   API_GUARD_END
 }
 
@@ -890,7 +890,7 @@ int aha_hip_sample_rows_adjusted(const float* logits, int64_t ld, int32_t R, int
     return AHA_ERR_INVALID;
   }
   return sample_rows_impl(logits, ld, R, V, k, temperature, repeat_penalty, context, context_offsets, adj_ids, adj_vals, adj_offsets, vals_out,
-                          idx_out, ms_out, stream);
+                          idx_out, ms_out, stream, nullptr, nullptr);
   API_GUARD_END
 }
 
@@ -1228,57 +1228,63 @@ int aha_hip_embed_batch(aha_model* m, const uint32_t* input_ids, const size_t* s
   return model_embed_batch(m, input_ids, seq_lens, n_seqs, max_tokens_per_pass, out);
   API_GUARD_END
 }
-int aha_hip_generate_batch(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
-                           size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* logits_out) {
-  API_GUARD_BEGIN
+// The device-free checks of the aha_hip_generate_batch* entries, in their fixed order: the sampling parameters, the top_logprobs /
+// logprobs_out pairing and range, then the model handle and the engine's claim on the cache.  who: the entry's name, which prefixes its
+// messages.  A new per-request option's argument check goes here.
+enum LogprobRule { LP_ABSENT, LP_BOTH, LP_BOTH_OR_NEITHER };
+static int gen_options_check(const char* who, const aha_model* m, size_t n_seqs, const GenOptions& o, bool params_required, LogprobRule lp) {
+  auto refuse = [who](const std::string& why) {   // (nothing is built for a call that passes)
+    set_error(std::string(who) + ": " + why);
+    return AHA_ERR_INVALID;
+  };
+  const size_t n = std::min(n_seqs, (size_t)1 << 20);
+  // the parameters first: they are checked before anything touches the model or the device
+  if (params_required && n_seqs && !o.params) return refuse("null params");
+  for (size_t j = 0; o.params && j < n; ++j) {   // params == NULL: every sequence greedy
+    std::string why;
+    if (sampling_params_check(o.params[j], &why)) return refuse("params of sequence " + std::to_string(j) + ": " + why);
+  }
+  if (lp == LP_BOTH && (!o.top_logprobs || !o.logprobs_out)) return refuse("null top_logprobs / logprobs_out");
+  if (lp == LP_BOTH_OR_NEITHER && (o.top_logprobs == nullptr) != (o.logprobs_out == nullptr))
+    return refuse("top_logprobs and logprobs_out go together (both NULL: no logprobs)");
+  for (size_t j = 0; o.top_logprobs && j < n; ++j)
+    if (o.top_logprobs[j] < -1 || o.top_logprobs[j] > AHA_MAX_TOP_LOGPROBS)
+      return refuse("top_logprobs of sequence " + std::to_string(j) + " must be -1 (none) or 0 .. " + std::to_string(AHA_MAX_TOP_LOGPROBS) +
+                    ", got " + std::to_string(o.top_logprobs[j]));
   if (!m) {
     set_error("null model");
     return AHA_ERR_INVALID;
   }
-  if (int rc = engine_owns_cache(m, "generate_batch")) return rc;
-  return model_generate_batch(m, input_ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, logits_out);
+  return engine_owns_cache(m, who);
+}
+
+int aha_hip_generate_batch(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
+                           size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* logits_out) {
+  API_GUARD_BEGIN
+  GenOptions o;
+  o.logits_out = logits_out;
+  if (int rc = gen_options_check("generate_batch", m, n_seqs, o, false, LP_ABSENT)) return rc;
+  return model_generate_batch(m, input_ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, o, tokens_out, n_out);
   API_GUARD_END
 }
 int aha_hip_generate_batch_sampled(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs,
                                    const aha_sampling_params* params, size_t max_new, size_t max_tokens_per_pass,
                                    uint32_t* tokens_out, size_t* n_out, float* step_logits_out) {
   API_GUARD_BEGIN
-  if (n_seqs && !params) {   // the parameters first: they are checked before anything touches the model or the device
-    set_error("generate_batch_sampled: null params");
-    return AHA_ERR_INVALID;
-  }
-  for (size_t j = 0; j < n_seqs && j < ((size_t)1 << 20); ++j) {
-    std::string why;
-    if (sampling_params_check(params[j], &why)) {
-      set_error("generate_batch_sampled: params of sequence " + std::to_string(j) + ": " + why);
-      return AHA_ERR_INVALID;
-    }
-  }
-  if (!m) {
-    set_error("null model");
-    return AHA_ERR_INVALID;
-  }
-  if (int rc = engine_owns_cache(m, "generate_batch_sampled")) return rc;
-  return model_generate_batch_sampled(m, input_ids, seq_lens, n_seqs, params, max_new, max_tokens_per_pass, tokens_out, n_out, step_logits_out);
+  GenOptions o;
+  o.params = params, o.step_logits_out = step_logits_out;
+  if (int rc = gen_options_check("generate_batch_sampled", m, n_seqs, o, true, LP_ABSENT)) return rc;
+  return model_generate_batch(m, input_ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, o, tokens_out, n_out);
   API_GUARD_END
 }
 int aha_hip_generate_batch_mm(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
                               const aha_sampling_params* params, size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out,
                               size_t* n_out, float* step_logits_out) {
   API_GUARD_BEGIN
-  for (size_t j = 0; params && j < n_seqs && j < ((size_t)1 << 20); ++j) {   // params == NULL: every sequence greedy
-    std::string why;
-    if (sampling_params_check(params[j], &why)) {
-      set_error("generate_batch_mm: params of sequence " + std::to_string(j) + ": " + why);
-      return AHA_ERR_INVALID;
-    }
-  }
-  if (!m) {
-    set_error("null model");
-    return AHA_ERR_INVALID;
-  }
-  if (int rc = engine_owns_cache(m, "generate_batch_mm")) return rc;
-  return model_generate_batch_mm(m, input_ids, seq_lens, n_seqs, mm, params, max_new, max_tokens_per_pass, tokens_out, n_out, step_logits_out);
+  GenOptions o;
+  o.mm = mm, o.params = params, o.step_logits_out = step_logits_out;
+  if (int rc = gen_options_check("generate_batch_mm", m, n_seqs, o, false, LP_ABSENT)) return rc;
+  return model_generate_batch(m, input_ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, o, tokens_out, n_out);
   API_GUARD_END
 }
 int aha_hip_generate_batch_logprobs(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs,
@@ -1286,97 +1292,42 @@ int aha_hip_generate_batch_logprobs(aha_model* m, const uint32_t* input_ids, con
                                     size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out,
                                     float* step_logits_out, aha_token_logprobs* logprobs_out) {
   API_GUARD_BEGIN
-  for (size_t j = 0; params && j < n_seqs && j < ((size_t)1 << 20); ++j) {   // params == NULL: every sequence greedy
-    std::string why;
-    if (sampling_params_check(params[j], &why)) {
-      set_error("generate_batch_logprobs: params of sequence " + std::to_string(j) + ": " + why);
-      return AHA_ERR_INVALID;
-    }
-  }
-  if (!top_logprobs || !logprobs_out) {
-    set_error("generate_batch_logprobs: null top_logprobs / logprobs_out");
-    return AHA_ERR_INVALID;
-  }
-  for (size_t j = 0; j < n_seqs && j < ((size_t)1 << 20); ++j)
-    if (top_logprobs[j] < -1 || top_logprobs[j] > AHA_MAX_TOP_LOGPROBS) {
-      set_error("generate_batch_logprobs: top_logprobs of sequence " + std::to_string(j) + " must be -1 (none) or 0 .. " +
-                std::to_string(AHA_MAX_TOP_LOGPROBS) + ", got " + std::to_string(top_logprobs[j]));
-      return AHA_ERR_INVALID;
-    }
-  if (!m) {
-    set_error("null model");
-    return AHA_ERR_INVALID;
-  }
-  if (int rc = engine_owns_cache(m, "generate_batch_logprobs")) return rc;
-  return model_generate_batch_logprobs(m, input_ids, seq_lens, n_seqs, mm, params, top_logprobs, max_new, max_tokens_per_pass, tokens_out, n_out,
-                                       step_logits_out, logprobs_out);
+  GenOptions o;
+  o.mm = mm, o.params = params, o.step_logits_out = step_logits_out;
+  o.top_logprobs = top_logprobs, o.logprobs_out = logprobs_out;
+  if (int rc = gen_options_check("generate_batch_logprobs", m, n_seqs, o, false, LP_BOTH)) return rc;
+  return model_generate_batch(m, input_ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, o, tokens_out, n_out);
+  API_GUARD_END
+}
+// aha_hip_generate_batch_adjusted, and aha_hip_generate_batch_masked (mask_fn set; without one it is exactly _adjusted, name included)
+static int generate_batch_adjusted(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs,
+                                   const aha_mm_input* const* mm, const aha_sampling_params* params, const aha_logit_adjust* adjust,
+                                   const int32_t* top_logprobs, size_t max_new, size_t max_tokens_per_pass, aha_token_mask_fn mask_fn,
+                                   void* mask_user, uint32_t* tokens_out, size_t* n_out, float* step_logits_out,
+                                   aha_token_logprobs* logprobs_out) {
+  API_GUARD_BEGIN
+  GenOptions o;
+  o.mm = mm, o.params = params, o.adjust = adjust, o.step_logits_out = step_logits_out;
+  o.top_logprobs = top_logprobs, o.logprobs_out = logprobs_out;
+  o.mask_fn = mask_fn, o.mask_user = mask_fn ? mask_user : nullptr;
+  if (int rc = gen_options_check(mask_fn ? "generate_batch_masked" : "generate_batch_adjusted", m, n_seqs, o, false, LP_BOTH_OR_NEITHER)) return rc;
+  return model_generate_batch(m, input_ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, o, tokens_out, n_out);
   API_GUARD_END
 }
 int aha_hip_generate_batch_adjusted(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs,
                                     const aha_mm_input* const* mm, const aha_sampling_params* params, const aha_logit_adjust* adjust,
                                     const int32_t* top_logprobs, size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out,
                                     size_t* n_out, float* step_logits_out, aha_token_logprobs* logprobs_out) {
-  API_GUARD_BEGIN
-  for (size_t j = 0; params && j < n_seqs && j < ((size_t)1 << 20); ++j) {   // params == NULL: every sequence greedy
-    std::string why;
-    if (sampling_params_check(params[j], &why)) {
-      set_error("generate_batch_adjusted: params of sequence " + std::to_string(j) + ": " + why);
-      return AHA_ERR_INVALID;
-    }
-  }
-  if ((top_logprobs == nullptr) != (logprobs_out == nullptr)) {
-    set_error("generate_batch_adjusted: top_logprobs and logprobs_out go together (both NULL: no logprobs)");
-    return AHA_ERR_INVALID;
-  }
-  for (size_t j = 0; top_logprobs && j < n_seqs && j < ((size_t)1 << 20); ++j)
-    if (top_logprobs[j] < -1 || top_logprobs[j] > AHA_MAX_TOP_LOGPROBS) {
-      set_error("generate_batch_adjusted: top_logprobs of sequence " + std::to_string(j) + " must be -1 (none) or 0 .. " +
-                std::to_string(AHA_MAX_TOP_LOGPROBS) + ", got " + std::to_string(top_logprobs[j]));
-      return AHA_ERR_INVALID;
-    }
-  if (!m) {
-    set_error("null model");
-    return AHA_ERR_INVALID;
-  }
-  if (int rc = engine_owns_cache(m, "generate_batch_adjusted")) return rc;
-  return model_generate_batch_adjusted(m, input_ids, seq_lens, n_seqs, mm, params, adjust, top_logprobs, max_new, max_tokens_per_pass, tokens_out,
-                                       n_out, step_logits_out, logprobs_out);
-  API_GUARD_END
+  return generate_batch_adjusted(m, input_ids, seq_lens, n_seqs, mm, params, adjust, top_logprobs, max_new, max_tokens_per_pass, nullptr, nullptr,
+                                 tokens_out, n_out, step_logits_out, logprobs_out);
 }
 int aha_hip_generate_batch_masked(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs,
                                   const aha_mm_input* const* mm, const aha_sampling_params* params, const aha_logit_adjust* adjust,
                                   const int32_t* top_logprobs, size_t max_new, size_t max_tokens_per_pass, aha_token_mask_fn mask_fn,
                                   void* mask_user, uint32_t* tokens_out, size_t* n_out, float* step_logits_out,
                                   aha_token_logprobs* logprobs_out) {
-  if (!mask_fn)   // exactly aha_hip_generate_batch_adjusted
-    return aha_hip_generate_batch_adjusted(m, input_ids, seq_lens, n_seqs, mm, params, adjust, top_logprobs, max_new, max_tokens_per_pass,
-                                           tokens_out, n_out, step_logits_out, logprobs_out);
-  API_GUARD_BEGIN
-  for (size_t j = 0; params && j < n_seqs && j < ((size_t)1 << 20); ++j) {   // params == NULL: every sequence greedy
-    std::string why;
-    if (sampling_params_check(params[j], &why)) {
-      set_error("generate_batch_masked: params of sequence " + std::to_string(j) + ": " + why);
-      return AHA_ERR_INVALID;
-    }
-  }
-  if ((top_logprobs == nullptr) != (logprobs_out == nullptr)) {
-    set_error("generate_batch_masked: top_logprobs and logprobs_out go together (both NULL: no logprobs)");
-    return AHA_ERR_INVALID;
-  }
-  for (size_t j = 0; top_logprobs && j < n_seqs && j < ((size_t)1 << 20); ++j)
-    if (top_logprobs[j] < -1 || top_logprobs[j] > AHA_MAX_TOP_LOGPROBS) {
-      set_error("generate_batch_masked: top_logprobs of sequence " + std::to_string(j) + " must be -1 (none) or 0 .. " +
-                std::to_string(AHA_MAX_TOP_LOGPROBS) + ", got " + std::to_string(top_logprobs[j]));
-      return AHA_ERR_INVALID;
-    }
-  if (!m) {
-    set_error("null model");
-    return AHA_ERR_INVALID;
-  }
-  if (int rc = engine_owns_cache(m, "generate_batch_masked")) return rc;
-  return model_generate_batch_masked(m, input_ids, seq_lens, n_seqs, mm, params, adjust, top_logprobs, max_new, max_tokens_per_pass, mask_fn,
-                                     mask_user, tokens_out, n_out, step_logits_out, logprobs_out);
-  API_GUARD_END
+  return generate_batch_adjusted(m, input_ids, seq_lens, n_seqs, mm, params, adjust, top_logprobs, max_new, max_tokens_per_pass, mask_fn, mask_user,
+                                 tokens_out, n_out, step_logits_out, logprobs_out);
 }
 int aha_hip_generate_batch_spec(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
                                 size_t max_tokens_per_pass, const aha_spec_config* spec, const uint32_t* predictions,
@@ -1388,13 +1339,12 @@ int aha_hip_generate_batch_spec(aha_model* m, const uint32_t* input_ids, const s
     set_error("generate_batch_spec: predictions and prediction_lens must both be set or both be null");
     return AHA_ERR_INVALID;
   }
-  if (!m) {
-    set_error("null model");
-    return AHA_ERR_INVALID;
-  }
-  if (int rc = engine_owns_cache(m, "generate_batch_spec")) return rc;
-  return model_generate_batch_spec(m, input_ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, spec, predictions, prediction_lens, tokens_out,
-                                   n_out, logits_out, n_proposed, n_accepted, stats);
+  GenOptions o;
+  o.logits_out = logits_out;
+  o.spec = spec, o.predictions = predictions, o.prediction_lens = prediction_lens;
+  o.n_proposed = n_proposed, o.n_accepted = n_accepted, o.stats = stats;
+  if (int rc = gen_options_check("generate_batch_spec", m, n_seqs, o, false, LP_ABSENT)) return rc;
+  return model_generate_batch(m, input_ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, o, tokens_out, n_out);
   API_GUARD_END
 }
 int aha_hip_spec_propose(const aha_spec_config* spec, const uint32_t* context, size_t n_context, size_t n_prompt, const uint32_t* prediction,
@@ -1425,88 +1375,61 @@ void aha_hip_engine_destroy(aha_engine* e) {
   } catch (...) {
   }
 }
+// The device-free checks of the aha_hip_engine_submit* entries: the parameters, top_logprobs (min_top: -1 where "no logprobs" is a
+// legal value, 0 for _logprobs), then the handle.  who: the entry's name.
+static int submit_options_check(const char* who, const aha_engine* e, const SubmitOptions& o, int32_t min_top) {
+  auto refuse = [who](const std::string& why) {
+    set_error(std::string(who) + ": " + why);
+    return AHA_ERR_INVALID;
+  };
+  if (o.params) {   // the parameters first, as generate_batch_sampled checks them
+    std::string why;
+    if (sampling_params_check(*o.params, &why)) return refuse("params: " + why);
+  }
+  if (o.top_logprobs < min_top || o.top_logprobs > AHA_MAX_TOP_LOGPROBS)
+    return refuse(std::string("top_logprobs must be ") + (min_top < 0 ? "-1 (none) or " : "") + "0 .. " + std::to_string(AHA_MAX_TOP_LOGPROBS) +
+                  ", got " + std::to_string(o.top_logprobs));
+  if (!e) return refuse("null engine");
+  return AHA_OK;
+}
+
 int aha_hip_engine_submit(aha_engine* e, const uint32_t* input_ids, size_t n_ids, const aha_mm_input* mm, const aha_sampling_params* params,
                           size_t max_new, uint64_t* req_id) {
   API_GUARD_BEGIN
-  if (params) {   // the parameters first, as generate_batch_sampled checks them
-    std::string why;
-    if (sampling_params_check(*params, &why)) {
-      set_error("engine_submit: params: " + why);
-      return AHA_ERR_INVALID;
-    }
-  }
-  if (!e) {
-    set_error("engine_submit: null engine");
-    return AHA_ERR_INVALID;
-  }
-  return engine_submit(e, input_ids, n_ids, mm, params, max_new, req_id);
+  SubmitOptions o;
+  o.mm = mm, o.params = params;
+  if (int rc = submit_options_check("engine_submit", e, o, -1)) return rc;
+  return engine_submit(e, input_ids, n_ids, o, max_new, req_id);
   API_GUARD_END
 }
 int aha_hip_engine_submit_logprobs(aha_engine* e, const uint32_t* input_ids, size_t n_ids, const aha_mm_input* mm,
                                    const aha_sampling_params* params, size_t max_new, int32_t top_logprobs, uint64_t* req_id) {
   API_GUARD_BEGIN
-  if (params) {
-    std::string why;
-    if (sampling_params_check(*params, &why)) {
-      set_error("engine_submit_logprobs: params: " + why);
-      return AHA_ERR_INVALID;
-    }
-  }
-  if (top_logprobs < 0 || top_logprobs > AHA_MAX_TOP_LOGPROBS) {
-    set_error("engine_submit_logprobs: top_logprobs must be 0 .. " + std::to_string(AHA_MAX_TOP_LOGPROBS) + ", got " + std::to_string(top_logprobs));
-    return AHA_ERR_INVALID;
-  }
-  if (!e) {
-    set_error("engine_submit_logprobs: null engine");
-    return AHA_ERR_INVALID;
-  }
-  return engine_submit(e, input_ids, n_ids, mm, params, max_new, req_id, top_logprobs);
+  SubmitOptions o;
+  o.mm = mm, o.params = params, o.top_logprobs = top_logprobs;
+  if (int rc = submit_options_check("engine_submit_logprobs", e, o, 0)) return rc;
+  return engine_submit(e, input_ids, n_ids, o, max_new, req_id);
   API_GUARD_END
 }
 int aha_hip_engine_submit_adjusted(aha_engine* e, const uint32_t* input_ids, size_t n_ids, const aha_mm_input* mm,
                                    const aha_sampling_params* params, const aha_logit_adjust* adjust, size_t max_new, int32_t top_logprobs,
                                    uint64_t* req_id) {
   API_GUARD_BEGIN
-  if (params) {
-    std::string why;
-    if (sampling_params_check(*params, &why)) {
-      set_error("engine_submit_adjusted: params: " + why);
-      return AHA_ERR_INVALID;
-    }
-  }
-  if (top_logprobs < -1 || top_logprobs > AHA_MAX_TOP_LOGPROBS) {
-    set_error("engine_submit_adjusted: top_logprobs must be -1 (none) or 0 .. " + std::to_string(AHA_MAX_TOP_LOGPROBS) + ", got " +
-              std::to_string(top_logprobs));
-    return AHA_ERR_INVALID;
-  }
-  if (!e) {
-    set_error("engine_submit_adjusted: null engine");
-    return AHA_ERR_INVALID;
-  }
-  return engine_submit(e, input_ids, n_ids, mm, params, max_new, req_id, top_logprobs, adjust);
+  SubmitOptions o;
+  o.mm = mm, o.params = params, o.adjust = adjust, o.top_logprobs = top_logprobs;
+  if (int rc = submit_options_check("engine_submit_adjusted", e, o, -1)) return rc;
+  return engine_submit(e, input_ids, n_ids, o, max_new, req_id);
   API_GUARD_END
 }
 int aha_hip_engine_submit_masked(aha_engine* e, const uint32_t* input_ids, size_t n_ids, const aha_mm_input* mm,
                                  const aha_sampling_params* params, const aha_logit_adjust* adjust, const uint32_t* mask_words,
                                  size_t n_mask_words, size_t max_new, int32_t top_logprobs, uint64_t* req_id) {
   API_GUARD_BEGIN
-  if (params) {
-    std::string why;
-    if (sampling_params_check(*params, &why)) {
-      set_error("engine_submit_masked: params: " + why);
-      return AHA_ERR_INVALID;
-    }
-  }
-  if (top_logprobs < -1 || top_logprobs > AHA_MAX_TOP_LOGPROBS) {
-    set_error("engine_submit_masked: top_logprobs must be -1 (none) or 0 .. " + std::to_string(AHA_MAX_TOP_LOGPROBS) + ", got " +
-              std::to_string(top_logprobs));
-    return AHA_ERR_INVALID;
-  }
-  if (!e) {
-    set_error("engine_submit_masked: null engine");
-    return AHA_ERR_INVALID;
-  }
-  return engine_submit(e, input_ids, n_ids, mm, params, max_new, req_id, top_logprobs, adjust, mask_words, n_mask_words);
+  SubmitOptions o;
+  o.mm = mm, o.params = params, o.adjust = adjust, o.top_logprobs = top_logprobs;
+  o.mask = mask_words, o.n_mask_words = n_mask_words;
+  if (int rc = submit_options_check("engine_submit_masked", e, o, -1)) return rc;
+  return engine_submit(e, input_ids, n_ids, o, max_new, req_id);
   API_GUARD_END
 }
 int aha_hip_engine_set_mask(aha_engine* e, uint64_t req_id, const uint32_t* words, size_t n_words) {

@@ -10,7 +10,7 @@
 //                            rope cos / sin table.
 //   attn_decode_batch_kernel q/k-norm + RoPE + KV append + split-KV attention + split merge of ALL rows in one launch: one block per
 //                            (kv head, split, row), each running attn_decode_fused_body on its row's qkv, rope row and pages.
-//   kv_append_rows_kernel    draft-and-verify steps (model_generate_batch_spec): the k-norm + RoPE + KV append of every row in a launch of
+//   kv_append_rows_kernel    draft-and-verify steps (aha_hip_generate_batch_spec): the k-norm + RoPE + KV append of every row in a launch of
 //                            its own, so that row i + 1 of a sequence finds row i's K/V in the pages; the attention launch that follows is
 //                            attn_decode_rows_kernel, the batch attention with the body's append compiled out.
 //   spec_accept_rows_kernel  per sequence, the longest draft prefix the step's argmax vector confirms -> its emitted tokens.

@@ -212,27 +212,27 @@ int model_create(aha_ctx* ctx, const aha_model_desc* desc, const aha_tensor_view
 void model_destroy(aha_model* m);
 int model_embed(aha_model* m, const uint32_t* ids, size_t n, float* out);
 int model_embed_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_tokens_per_pass, float* out);
+// What a batch generation call may carry beyond ids, lens, max_new, the pass budget, tokens_out and n_out: every field absent by default.
+// A new per-request option is a field here, a check in capi.hip's gen_options_check and its use in model_generate_batch.
+struct GenOptions {
+  const aha_mm_input* const* mm = nullptr;         // per sequence null or its images / videos / audio
+  const aha_sampling_params* params = nullptr;     // per sequence; null: every sequence greedy
+  const aha_logit_adjust* adjust = nullptr;        // per sequence
+  const int32_t* top_logprobs = nullptr;           // per sequence (-1: none), with logprobs_out
+  aha_token_logprobs* logprobs_out = nullptr;
+  aha_token_mask_fn mask_fn = nullptr;
+  void* mask_user = nullptr;
+  float* logits_out = nullptr;                     // (n_seqs, vocab): the logits that chose each sequence's last token
+  float* step_logits_out = nullptr;                // (n_seqs, max_new, vocab): every step's logits
+  // aha_hip_generate_batch_spec (spec set: a draft-and-verify run, checked by spec_config_check)
+  const aha_spec_config* spec = nullptr;
+  const uint32_t* predictions = nullptr;           // packed like input_ids, or null
+  const size_t* prediction_lens = nullptr;
+  size_t *n_proposed = nullptr, *n_accepted = nullptr;   // per sequence, may be null
+  aha_spec_stats* stats = nullptr;                 // may be null
+};
 int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new, size_t max_tokens_per_pass,
-                         uint32_t* tokens_out, size_t* n_out, float* logits_out);
-int model_generate_batch_sampled(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_sampling_params* params,
-                                 size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* step_logits_out);
-int model_generate_batch_mm(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
-                            const aha_sampling_params* params, size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out,
-                            float* step_logits_out);
-int model_generate_batch_logprobs(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
-                                  const aha_sampling_params* params, const int32_t* top_logprobs, size_t max_new, size_t max_tokens_per_pass,
-                                  uint32_t* tokens_out, size_t* n_out, float* step_logits_out, aha_token_logprobs* logprobs_out);
-int model_generate_batch_adjusted(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
-                                  const aha_sampling_params* params, const aha_logit_adjust* adjust, const int32_t* top_logprobs, size_t max_new,
-                                  size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* step_logits_out,
-                                  aha_token_logprobs* logprobs_out);
-int model_generate_batch_masked(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
-                                const aha_sampling_params* params, const aha_logit_adjust* adjust, const int32_t* top_logprobs, size_t max_new,
-                                size_t max_tokens_per_pass, aha_token_mask_fn mask_fn, void* mask_user, uint32_t* tokens_out, size_t* n_out,
-                                float* step_logits_out, aha_token_logprobs* logprobs_out);
-int model_generate_batch_spec(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new, size_t max_tokens_per_pass,
-                              const aha_spec_config* spec, const uint32_t* predictions, const size_t* prediction_lens, uint32_t* tokens_out,
-                              size_t* n_out, float* logits_out, size_t* n_proposed, size_t* n_accepted, aha_spec_stats* stats);
+                         const GenOptions& o, uint32_t* tokens_out, size_t* n_out);
 // spec_host.hip: the draft proposer (host only).  spec_config_check: AHA_OK or AHA_ERR_INVALID with the message set (who: the entry's name)
 int spec_config_check(const aha_spec_config* spec, const char* who);
 void spec_propose(const aha_spec_config& spec, const uint32_t* ctx, size_t n_ctx, size_t n_prompt, const uint32_t* pred, size_t n_pred,
@@ -240,9 +240,15 @@ void spec_propose(const aha_spec_config& spec, const uint32_t* ctx, size_t n_ctx
 int engine_config_check(const aha_engine_config* cfg, size_t* budget_out, size_t* chunk_out);
 int engine_create(aha_model* m, const aha_engine_config* cfg, aha_engine** out);
 void engine_destroy(aha_engine* e);
-int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const aha_mm_input* mm, const aha_sampling_params* params, size_t max_new,
-                  uint64_t* req_id, int32_t top_logprobs = -1, const aha_logit_adjust* adjust = nullptr,
-                  const uint32_t* mask = nullptr, size_t n_mask_words = 0);
+struct SubmitOptions {   // what an engine request may carry beyond its ids, max_new and req_id: every field absent by default
+  const aha_mm_input* mm = nullptr;
+  const aha_sampling_params* params = nullptr;   // null: greedy
+  const aha_logit_adjust* adjust = nullptr;
+  int32_t top_logprobs = -1;                     // -1: no logprobs
+  const uint32_t* mask = nullptr;                // n_mask_words packed allowed-token words, or null
+  size_t n_mask_words = 0;
+};
+int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const SubmitOptions& o, size_t max_new, uint64_t* req_id);
 int engine_set_mask(aha_engine* e, uint64_t req_id, const uint32_t* words, size_t n_words);
 int engine_cancel(aha_engine* e, uint64_t req_id);
 int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, float* logits_out, aha_token_logprobs* logprobs_out = nullptr);

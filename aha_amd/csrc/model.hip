@@ -2891,16 +2891,14 @@ static void gen_decode_step(aha_model* m, GenCall& gc, int R, int max_split, dou
   gen_head(m, gc, 0, R, tok_out);
 }
 
-// ---- draft-and-verify greedy decoding (aha_hip_generate_batch_spec) ------------------------------------------------------------------
-struct SpecRun {
-  aha_spec_config cfg;
-  const uint32_t* predictions;    // packed like input_ids, or null
-  const size_t* prediction_lens;
-  size_t *n_proposed, *n_accepted;   // per sequence, may be null
-  aha_spec_stats* stats;             // may be null
-};
+static bool is_stop(const aha_model_desc& c, uint32_t t) {
+  for (int e = 0; e < c.n_stop_tokens; ++e)
+    if (t == c.stop_tokens[e]) return true;
+  return false;
+}
 
-// The decode loop of generate_batch_impl with up to max_draft draft tokens per sequence riding along as rows of the same step: a sequence
+// ---- draft-and-verify greedy decoding (aha_hip_generate_batch_spec) ------------------------------------------------------------------
+// The decode loop of model_generate_batch with up to max_draft draft tokens per sequence riding along as rows of the same step: a sequence
 // whose cache holds p tokens and whose last token is g contributes rows (g, d1 .. dk) at cache lengths p + 1 .. p + 1 + k on the same pages.
 // Row i's logits are those of plain greedy decoding at its position as long as d1 .. di are the tokens greedy decoding chose there (row
 // isolation of gemv_rows, the unchanged attention body), which is exactly what spec_accept_rows_kernel checks: it keeps the longest
@@ -2910,7 +2908,8 @@ struct SpecRun {
 // GEN_ROW_GROUP at or above the number of active sequences -- no gemv_rows group is added by speculation.
 // The input tokens of the rows are known on the host (the last emitted token, the drafts): they travel in word GEN_ROW_TOK of the row
 // table, which doubles as the step's token vector; the sequences' (first row, drafts) pairs sit behind the rows, one upload per step.
-static int spec_decode_loop(aha_model* m, GenCall& gc, const SpecRun& sp, const uint32_t* ids, const size_t* seq_lens,
+// sp: the call's options, of which the spec fields are read.
+static int spec_decode_loop(aha_model* m, GenCall& gc, const GenOptions& sp, const uint32_t* ids, const size_t* seq_lens,
                             const std::vector<size_t>& pred_off, const std::vector<int64_t>& page0, const std::vector<int64_t>& rope_delta,
                             std::vector<int>& active, float* logits_out) {
   const aha_model_desc& c = m->desc;
@@ -2927,11 +2926,6 @@ static int spec_decode_loop(aha_model* m, GenCall& gc, const SpecRun& sp, const 
       ctx[j].push_back(gc.tokens_out[(size_t)j * max_new]);
     }
   }
-  auto is_stop = [&](uint32_t t) {
-    for (int e = 0; e < c.n_stop_tokens; ++e)
-      if (t == c.stop_tokens[e]) return true;
-    return false;
-  };
   std::vector<unsigned> ctr_acc((size_t)gc.rows, 0u);   // per row slot: the rows of a step change from step to step
   std::vector<int> row0(n), ndraft(n);
   uint32_t draft[SPEC_MAX_DRAFT];
@@ -2947,7 +2941,7 @@ static int spec_decode_loop(aha_model* m, GenCall& gc, const SpecRun& sp, const 
       const size_t room = std::min<size_t>((size_t)extra, max_new - t_gen - 1);   // t + 1 + |draft| <= max_new: the cache stays in its pages
       if (room > 0) {
         const uint32_t* pred = sp.predictions ? sp.predictions + pred_off[j] : nullptr;
-        spec_propose(sp.cfg, ctx[j].data(), ctx[j].size(), seq_lens[j], pred, pred ? sp.prediction_lens[j] : 0, draft, &k);
+        spec_propose(*sp.spec, ctx[j].data(), ctx[j].size(), seq_lens[j], pred, pred ? sp.prediction_lens[j] : 0, draft, &k);
         k = std::min(k, room);
       }
       extra -= (int)k;
@@ -3001,7 +2995,7 @@ static int spec_decode_loop(aha_model* m, GenCall& gc, const SpecRun& sp, const 
         const uint32_t t = o[SPEC_OUT_TOKENS + kept++];
         gc.tokens_out[(size_t)j * max_new + gc.n_out[j]++] = t;
         ctx[j].push_back(t);
-        done = is_stop(t) || gc.n_out[j] == max_new;
+        done = is_stop(c, t) || gc.n_out[j] == max_new;
       }
       const size_t acc = (size_t)std::min(kept, emitted - 1);   // drafts among the kept tokens (the run's last token is the row's own choice)
       if (sp.n_proposed) sp.n_proposed[j] += (size_t)ndraft[a];
@@ -3019,17 +3013,20 @@ static int spec_decode_loop(aha_model* m, GenCall& gc, const SpecRun& sp, const 
   return AHA_OK;
 }
 
-// params == nullptr: greedy (aha_hip_generate_batch: logits_out = each sequence's last logits).  Otherwise one sampler per sequence
-// (aha_hip_generate_batch_sampled: step_logits_out = every step's logits); the step's tokens are then picked on the host after the batched
-// candidate step, and written back into the token vector the next step's embedding gather reads.  step_logits_out (greedy or sampled):
-// every step's logits.  mm (aha_hip_generate_batch_mm; may be null): per sequence null or its images / videos -- Qwen3-VL positions
-// (get_rope_index of the sequence alone), the tower per prefill pass, DeepStack in the packed layers, and decode positions kv_len - 1 +
-// the sequence's rope_delta (qwen3vl/model.rs:1235-1264); m->rope_delta is neither read nor written.
-static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new,
-                               size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* logits_out,
-                               const aha_sampling_params* params, float* step_logits_out, const aha_mm_input* const* mm = nullptr,
-                               const SpecRun* sp = nullptr, const int32_t* top_logprobs = nullptr, aha_token_logprobs* logprobs_out = nullptr,
-                               const aha_logit_adjust* adjust = nullptr, aha_token_mask_fn mask_fn = nullptr, void* mask_user = nullptr) {
+constexpr aha_sampling_params GREEDY_PARAMS{0.f, 1.f, 0, 1.f, 64, 0u, 299792458ull};   // ArgMax, no penalty: the device argmax
+
+// The one implementation behind every aha_hip_generate_batch* entry; GenOptions (model.h) names what a call carries.  A new per-request
+// option is added in three places: a GenOptions field, its device-free check in capi.hip's gen_options_check, and its use here.
+// o.params == nullptr: greedy, the device argmax.  Otherwise one sampler per sequence; the step's tokens are then picked on the host after
+// the batched candidate step, and written back into the token vector the next step's embedding gather reads.  o.logits_out: each sequence's
+// last logits; o.step_logits_out (greedy or sampled): every step's logits.  o.mm (may be null): per sequence null or its images / videos
+// -- Qwen3-VL positions (get_rope_index of the sequence alone), the tower per prefill pass, DeepStack in the packed layers, and decode
+// positions kv_len - 1 + the sequence's rope_delta (qwen3vl/model.rs:1235-1264); m->rope_delta is neither read nor written.
+int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new, size_t max_tokens_per_pass,
+                         const GenOptions& o, uint32_t* tokens_out, size_t* n_out) {
+  const aha_sampling_params* params = o.params;
+  const aha_logit_adjust* adjust = o.adjust;
+  float* const logits_out = o.logits_out;
   const aha_model_desc& c = m->desc;
   if (!ids || !seq_lens || !tokens_out || !n_out) {
     set_error("generate_batch: null input_ids / seq_lens / tokens_out / n_out");
@@ -3072,33 +3069,33 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
     }
     if (!any) adjust = nullptr;
   }
-  if ((adjust || mask_fn) && !params) {   // (a mask callback likewise: a row it leaves unmasked stays the device argmax)
-    greedy_params.assign(n_seqs, aha_sampling_params{0.f, 1.f, 0, 1.f, 64, 0u, 299792458ull});
+  if ((adjust || o.mask_fn) && !params) {   // (a mask callback likewise: a row it leaves unmasked stays the device argmax)
+    greedy_params.assign(n_seqs, GREEDY_PARAMS);
     params = greedy_params.data();
   }
   std::vector<size_t> pred_off(n_seqs, 0);
-  if (sp && sp->predictions) {
+  if (o.spec && o.predictions) {
     size_t off = 0;
-    for (size_t j = 0; j < n_seqs; off += sp->prediction_lens[j], ++j) {
+    for (size_t j = 0; j < n_seqs; off += o.prediction_lens[j], ++j) {
       pred_off[j] = off;
-      for (size_t i = 0; i < sp->prediction_lens[j]; ++i)
-        if (sp->predictions[off + i] >= (uint32_t)c.vocab_size) {
+      for (size_t i = 0; i < o.prediction_lens[j]; ++i)
+        if (o.predictions[off + i] >= (uint32_t)c.vocab_size) {
           set_error("generate_batch_spec: prediction id out of range in sequence " + std::to_string(j) + " at position " + std::to_string(i));
           return AHA_ERR_INVALID;
         }
     }
   }
-  const bool spec_on = sp && sp->cfg.max_draft > 0;
-  if (sp) {
-    if (sp->stats) *sp->stats = aha_spec_stats{0, 0, 0, 0};
+  const bool spec_on = o.spec && o.spec->max_draft > 0;
+  if (o.spec) {
+    if (o.stats) *o.stats = aha_spec_stats{0, 0, 0, 0};
     for (size_t j = 0; j < n_seqs; ++j) {
-      if (sp->n_proposed) sp->n_proposed[j] = 0;
-      if (sp->n_accepted) sp->n_accepted[j] = 0;
+      if (o.n_proposed) o.n_proposed[j] = 0;
+      if (o.n_accepted) o.n_accepted[j] = 0;
     }
   }
   std::vector<std::vector<int32_t>> pos3(n_seqs);
   std::vector<int64_t> rope_delta(n_seqs, 0);
-  if (mm && (rc = check_mm_requests(m, ids, seq_lens, n_seqs, mm, pos3, rope_delta))) return rc;
+  if (o.mm && (rc = check_mm_requests(m, ids, seq_lens, n_seqs, o.mm, pos3, rope_delta))) return rc;
   AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
   if ((rc = model_clear_cache(m))) return rc;
   ClearCacheGuard guard{m};
@@ -3116,8 +3113,8 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
   GenCall gc;
   gc.n = n, gc.V = V, gc.H = c.hidden_size, gc.max_new = max_new;
   // draft-and-verify: a step's rows never pass the next multiple of GEN_ROW_GROUP at or above its sequences (the row budget)
-  if (spec_on) gc.rows = (int)std::min<size_t>((size_t)(n + GEN_ROW_GROUP - 1) / GEN_ROW_GROUP * GEN_ROW_GROUP, (size_t)n * (1 + sp->cfg.max_draft));
-  gc.tokens_out = tokens_out, gc.n_out = n_out, gc.step_logits_out = step_logits_out;
+  if (spec_on) gc.rows = (int)std::min<size_t>((size_t)(n + GEN_ROW_GROUP - 1) / GEN_ROW_GROUP * GEN_ROW_GROUP, (size_t)n * (1 + o.spec->max_draft));
+  gc.tokens_out = tokens_out, gc.n_out = n_out, gc.step_logits_out = o.step_logits_out;
   GenChoice ch;
   size_t max_pass_pages = 0;
   for (int j = 0; j < n; ++j) {
@@ -3125,30 +3122,25 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
     max_pass_pages += (seq_lens[j] + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
   }
   if ((rc = gen_call_alloc(m, bufs, gc, max_pass_pages)) || (params && (rc = gen_choice_init(bufs, gc, params, ch, adjust)))) return rc;
-  if (mask_fn) {
+  if (o.mask_fn) {
     if ((rc = gen_choice_mask_alloc(bufs, n, V, ch))) return rc;
-    ch.mask_fn = mask_fn, ch.mask_user = mask_user;
+    ch.mask_fn = o.mask_fn, ch.mask_user = o.mask_user;
   }
-  if (top_logprobs) {
-    gc.lp_top = top_logprobs, gc.logprobs_out = logprobs_out;
-    if (std::any_of(top_logprobs, top_logprobs + n, [](int32_t t) { return t >= 0; }) && (rc = gen_logprob_alloc(bufs, gc))) return rc;
+  if (o.top_logprobs) {
+    gc.lp_top = o.top_logprobs, gc.logprobs_out = o.logprobs_out;
+    if (std::any_of(o.top_logprobs, o.top_logprobs + n, [](int32_t t) { return t >= 0; }) && (rc = gen_logprob_alloc(bufs, gc))) return rc;
   }
   if (spec_on && ((rc = bufs.alloc(&gc.spec_out, (size_t)n * SPEC_OUT_WORDS)) || (rc = bufs.alloc_host(&gc.h_spec_out, (size_t)n * SPEC_OUT_WORDS))))
     return rc;
 
   // ---- prefill: packed passes ----
   for (const PassRange& p : split_passes(seq_lens, n_seqs, max_tokens_per_pass))
-    if ((rc = generate_prefill_pass(m, gc, ids + p.off, seq_lens + p.j, (int)p.j, (int)(p.k - p.j), page0, pos3, mm))) return rc;
+    if ((rc = generate_prefill_pass(m, gc, ids + p.off, seq_lens + p.j, (int)p.j, (int)(p.k - p.j), page0, pos3, o.mm))) return rc;
   {
     std::vector<int> all(n);
     for (int j = 0; j < n; ++j) all[j] = j, n_out[j] = 0;
     if ((rc = gen_finish_step(m, gc, ch, all, gc.tok[0]))) return rc;
   }
-  auto is_stop = [&](uint32_t t) {
-    for (int e = 0; e < c.n_stop_tokens; ++e)
-      if (t == c.stop_tokens[e]) return true;
-    return false;
-  };
   auto copy_logits = [&](int row, int j) -> int {
     if (logits_out) AHA_HIP_CHECK(hipMemcpy(logits_out + (size_t)j * V, gc.logits + (size_t)row * V, (size_t)V * 4, hipMemcpyDeviceToHost));
     return AHA_OK;
@@ -3166,12 +3158,12 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
   }
 
   // ---- decode ----
-  if (spec_on) return spec_decode_loop(m, gc, *sp, ids, seq_lens, pred_off, page0, rope_delta, active, logits_out);
+  if (spec_on) return spec_decode_loop(m, gc, o, ids, seq_lens, pred_off, page0, rope_delta, active, logits_out);
   std::vector<unsigned> ctr_acc(n, 0u);
   int cur = 0;
   while (!active.empty()) {
     const int R = (int)active.size();
-    if (sp && sp->stats) sp->stats->decode_steps += 1, sp->stats->rows += (size_t)R;
+    if (o.spec && o.stats) o.stats->decode_steps += 1, o.stats->rows += (size_t)R;
     int max_split = 1;
     double kv_tokens = 0;
     for (int r = 0; r < R; ++r) {
@@ -3201,7 +3193,7 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
       const uint32_t t = gc.h_tok[r];
       tokens_out[(size_t)j * max_new + n_out[j]++] = t;
       src_row[j] = r;
-      if (is_stop(t) || n_out[j] == max_new) {
+      if (is_stop(c, t) || n_out[j] == max_new) {
         if ((rc = copy_logits(r, j))) return rc;
       } else {
         next.push_back(j);
@@ -3213,52 +3205,6 @@ static int generate_batch_impl(aha_model* m, const uint32_t* ids, const size_t* 
   return AHA_OK;
 }
 
-int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new, size_t max_tokens_per_pass,
-                         uint32_t* tokens_out, size_t* n_out, float* logits_out) {
-  return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, logits_out, nullptr, nullptr);
-}
-
-int model_generate_batch_sampled(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_sampling_params* params,
-                                 size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* step_logits_out) {
-  return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, nullptr, params, step_logits_out);
-}
-
-int model_generate_batch_mm(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
-                            const aha_sampling_params* params, size_t max_new, size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out,
-                            float* step_logits_out) {
-  return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, nullptr, params, step_logits_out, mm);
-}
-
-int model_generate_batch_logprobs(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
-                                  const aha_sampling_params* params, const int32_t* top_logprobs, size_t max_new, size_t max_tokens_per_pass,
-                                  uint32_t* tokens_out, size_t* n_out, float* step_logits_out, aha_token_logprobs* logprobs_out) {
-  return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, nullptr, params, step_logits_out, mm,
-                             nullptr, top_logprobs, logprobs_out);
-}
-
-int model_generate_batch_adjusted(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
-                                  const aha_sampling_params* params, const aha_logit_adjust* adjust, const int32_t* top_logprobs, size_t max_new,
-                                  size_t max_tokens_per_pass, uint32_t* tokens_out, size_t* n_out, float* step_logits_out,
-                                  aha_token_logprobs* logprobs_out) {
-  return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, nullptr, params, step_logits_out, mm,
-                             nullptr, top_logprobs, logprobs_out, adjust);
-}
-
-int model_generate_batch_masked(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, const aha_mm_input* const* mm,
-                                const aha_sampling_params* params, const aha_logit_adjust* adjust, const int32_t* top_logprobs, size_t max_new,
-                                size_t max_tokens_per_pass, aha_token_mask_fn mask_fn, void* mask_user, uint32_t* tokens_out, size_t* n_out,
-                                float* step_logits_out, aha_token_logprobs* logprobs_out) {
-  return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, nullptr, params, step_logits_out, mm,
-                             nullptr, top_logprobs, logprobs_out, adjust, mask_fn, mask_user);
-}
-
-int model_generate_batch_spec(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_new, size_t max_tokens_per_pass,
-                              const aha_spec_config* spec, const uint32_t* predictions, const size_t* prediction_lens, uint32_t* tokens_out,
-                              size_t* n_out, float* logits_out, size_t* n_proposed, size_t* n_accepted, aha_spec_stats* stats) {
-  const SpecRun sp{*spec, predictions, prediction_lens, n_proposed, n_accepted, stats};
-  return generate_batch_impl(m, ids, seq_lens, n_seqs, max_new, max_tokens_per_pass, tokens_out, n_out, logits_out, nullptr, nullptr, nullptr, &sp);
-}
-
 // ---- continuous batching engine (aha_hip_engine_*) ------------------------------------------------------------------------------
 // generate_generic's stream (common/generate.rs:231-368) for requests that come and go: the engine owns the model's cache (kv_pages pages
 // reserved up front, a free list) and max_running slots.  A slot owns the window [slot * kv_pages, + kv_pages) of the engine's device page
@@ -3266,7 +3212,7 @@ int model_generate_batch_spec(aha_model* m, const uint32_t* ids, const size_t* s
 // gives them back when it ends or is cancelled.  A step = the prefill work (one packed pass: whole prompts of requests admitted this step in
 // submission order under max_tokens_per_step, then at most one 64-aligned chunk of a long TEXT prompt, with its cache prefix in the
 // attention: AttnPrefillArgs::seg_kv0) -> the first tokens of the prompts it completes, then one gen_decode_step over every request that
-// had a first token before the step, then its gen_finish_step.  The pieces are generate_batch_impl's: a request's bits are those of its
+// had a first token before the step, then its gen_finish_step.  The pieces are model_generate_batch's: a request's bits are those of its
 // prompt's packed pass (the same composition through generate_batch* gives the same bits: the decode rows are row-isolated) -- requests
 // with images, video or audio are prefilled whole, never chunked.
 // Split counters: slot s owns head_ctr block s (GEN_ROW_CTRROW) and ctr_acc[s], both reset to ctr_base when a slot is taken.  The kernel's
@@ -3342,12 +3288,6 @@ static int rc_mask_check(const uint32_t* words, size_t n_words, size_t V, const 
     return AHA_ERR_INVALID;
   }
   return AHA_OK;
-}
-
-static bool engine_is_stop(const aha_model_desc& c, uint32_t t) {
-  for (int e = 0; e < c.n_stop_tokens; ++e)
-    if (t == c.stop_tokens[e]) return true;
-  return false;
 }
 
 // The config's own rules (no model needed): the effective step budget and chunk
@@ -3426,7 +3366,6 @@ int engine_create(aha_model* m, const aha_engine_config* cfg, aha_engine** out) 
   }
   gc.dec_pages = e->d_win;
   e->ch.samplers.resize(n);
-  (void)kvh;
   m->engine = e;
   *out = e;
   return AHA_OK;
@@ -3441,11 +3380,12 @@ void engine_destroy(aha_engine* e) {
   model_clear_cache(m);
 }
 
-int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const aha_mm_input* mm, const aha_sampling_params* params, size_t max_new,
-                  uint64_t* req_id, int32_t top_logprobs, const aha_logit_adjust* adjust, const uint32_t* mask, size_t n_mask_words) {
+int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const SubmitOptions& o, size_t max_new, uint64_t* req_id) {
   aha_model* m = e->m;
   const aha_model_desc& c = m->desc;
-  if (mask && (rc_mask_check(mask, n_mask_words, (size_t)c.vocab_size, "engine_submit_masked"))) return AHA_ERR_INVALID;
+  const aha_mm_input* mm = o.mm;
+  const aha_logit_adjust* adjust = o.adjust;
+  if (o.mask && (rc_mask_check(o.mask, o.n_mask_words, (size_t)c.vocab_size, "engine_submit_masked"))) return AHA_ERR_INVALID;
   {
     std::string why;
     if (logit_adjust_check(adjust, (size_t)c.vocab_size, &why)) {
@@ -3453,7 +3393,7 @@ int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const aha_mm
       return AHA_ERR_INVALID;
     }
   }
-  if (top_logprobs >= 0 && !e->gc.lp_tab) {
+  if (o.top_logprobs >= 0 && !e->gc.lp_tab) {
     set_error("engine_submit_logprobs: vocabulary too large for the logprob pass");
     return AHA_ERR_UNSUPPORTED;
   }
@@ -3487,16 +3427,15 @@ int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const aha_mm
   q->whole = q->mm != nullptr;
   q->pos3 = std::move(pos3[0]);
   q->rope_delta = rope_delta[0];
-  if (params) q->params = *params;
-  else q->params = aha_sampling_params{0.f, 1.f, 0, 1.f, 64, 0u, 299792458ull};   // ArgMax, no penalty: the device argmax
+  q->params = o.params ? *o.params : GREEDY_PARAMS;
   q->max_new = max_new;
-  q->top_logprobs = top_logprobs;
+  q->top_logprobs = o.top_logprobs;
   if (logit_adjust_active(adjust)) {   // copied: the caller's arrays need not outlive the call
     q->bias_ids.assign(adjust->bias_ids, adjust->bias_ids + adjust->n_bias);
     q->bias_vals.assign(adjust->bias_vals, adjust->bias_vals + adjust->n_bias);
     q->adjust = aha_logit_adjust{adjust->presence_penalty, adjust->frequency_penalty, q->bias_ids.data(), q->bias_vals.data(), adjust->n_bias};
   }
-  if (mask) q->mask.assign(mask, mask + n_mask_words);
+  if (o.mask) q->mask.assign(o.mask, o.mask + o.n_mask_words);
   q->npages = npages;
   q->toks.reserve(max_new);
   e->waiting.push_back(q);
@@ -3800,7 +3739,7 @@ int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, f
       const uint32_t t = gc.h_tok[r];
       q->toks.push_back(t);
       e->n_out[rows[r]] = q->toks.size();
-      const uint32_t f = (engine_is_stop(c, t) ? AHA_ENGINE_EV_STOP : 0u) | (q->toks.size() == q->max_new ? AHA_ENGINE_EV_LENGTH : 0u);
+      const uint32_t f = (is_stop(c, t) ? AHA_ENGINE_EV_STOP : 0u) | (q->toks.size() == q->max_new ? AHA_ENGINE_EV_LENGTH : 0u);
       emit(q->id, t, f);
     }
   }
@@ -3809,7 +3748,7 @@ int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, f
     EngReq* q = e->slots[s];
     if (!q || !q->started) continue;
     const uint32_t last = q->toks.back();
-    if (q->toks.size() >= q->max_new || (q->toks.size() > 1 && engine_is_stop(c, last))) engine_release(e, s);
+    if (q->toks.size() >= q->max_new || (q->toks.size() > 1 && is_stop(c, last))) engine_release(e, s);
   }
   *n_ev = ne;
   return AHA_OK;

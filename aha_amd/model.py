@@ -124,6 +124,36 @@ def _sampling_array(params, n: int):
     return (_lib.SamplingParams * max(n, 1))(*[p.to_c() for p in params])
 
 
+def _mm_array(data, n: int):
+    """data (None, or per prompt a MultiModalData or None) as the C array of n aha_mm_input pointers (None for data None).  Returns
+    (array, what its entries point into: keep it alive for the call)."""
+    if data is None:
+        return None, []
+    if len(data) != n:
+        raise ValueError(f"{len(data)} MultiModalData entries for {n} prompts")
+    keep, mm_arr = [], (C.c_void_p * max(n, 1))()
+    for j, d in enumerate(data):
+        if d is not None:
+            mm, k = _mm_input(d)
+            keep += [mm, k]
+            mm_arr[j] = C.addressof(mm)
+    return mm_arr, keep
+
+
+def _top_logprobs_array(top_logprobs, n: int):
+    """top_logprobs (an int or None for every prompt, or one entry per prompt; None = no logprobs for that prompt) as int32[n + 1]: -1 for
+    None, and one trailing pad element so the array is never empty."""
+    tops = [top_logprobs] * n if top_logprobs is None or isinstance(top_logprobs, (int, np.integer)) else list(top_logprobs)
+    if len(tops) != n:
+        raise ValueError(f"{len(tops)} top_logprobs entries for {n} prompts")
+    return np.ascontiguousarray(np.asarray([-1 if t is None else int(t) for t in tops] + [0], dtype=np.int32))
+
+
+def _unpack_logprobs(lp, top, toks, max_new: int):
+    """The aha_token_logprobs block of a batch call -> per prompt None (it asked for none) or one _token_logprobs per generated token."""
+    return [None if top[j] < 0 else [_token_logprobs(lp[j * int(max_new) + t]) for t in range(len(toks[j]))] for j in range(len(toks))]
+
+
 def make_desc(cfg, kv_reserve_tokens: int = 0) -> ModelDesc:
     d = ModelDesc()
     if isinstance(cfg, Qwen3VLConfig):
@@ -399,17 +429,8 @@ class HipInferenceModel:
         generate_generic yields for it alone with its data.  Returns a list of token lists, and with want_step_logits also the
         (len(prompts), max_new, vocab) float32 logits that chose each token (rows past a sequence's length are zero)."""
         n = len(prompts)
-        if data is not None and len(data) != n:
-            raise ValueError(f"{len(data)} MultiModalData entries for {n} prompts")
+        mm_arr, keep = _mm_array(data, n)
         cp = None if params is None else _sampling_array(params, n)
-        keep, mm_arr = [], None
-        if data is not None:
-            mm_arr = (C.c_void_p * max(n, 1))()
-            for j, d in enumerate(data):
-                if d is not None:
-                    mm, k = _mm_input(d)
-                    keep += [mm, k]
-                    mm_arr[j] = C.addressof(mm)
         return self._generate_batch(lib().aha_hip_generate_batch_mm, prompts, (mm_arr, cp), max_new, max_tokens_per_pass,
                                     "step" if want_step_logits else None)
 
@@ -421,28 +442,16 @@ class HipInferenceModel:
         whatever the sampler.  Returns (token lists, logprobs[, step logits]): logprobs[j] is None for a prompt that asked for none, else
         per generated token (logprob, [(id, logprob), ...]) with the top_logprobs most likely tokens, most likely first."""
         n = len(prompts)
-        if data is not None and len(data) != n:
-            raise ValueError(f"{len(data)} MultiModalData entries for {n} prompts")
-        tops = [top_logprobs] * n if top_logprobs is None or isinstance(top_logprobs, (int, np.integer)) else list(top_logprobs)
-        if len(tops) != n:
-            raise ValueError(f"{len(tops)} top_logprobs entries for {n} prompts")
-        top = np.ascontiguousarray(np.asarray([-1 if t is None else int(t) for t in tops] + [0], dtype=np.int32))
+        mm_arr, keep = _mm_array(data, n)
+        top = _top_logprobs_array(top_logprobs, n)
         cp = None if params is None else _sampling_array(params, n)
-        keep, mm_arr = [], None
-        if data is not None:
-            mm_arr = (C.c_void_p * max(n, 1))()
-            for j, d in enumerate(data):
-                if d is not None:
-                    mm, k = _mm_input(d)
-                    keep += [mm, k]
-                    mm_arr[j] = C.addressof(mm)
         lp = (_lib.TokenLogprobs * max(n * max(int(max_new), 1), 1))()
 
         def entry(handle, ids, lens, n_, mm_, cp_, mx, pas, toks, n_out, lg):
             return lib().aha_hip_generate_batch_logprobs(handle, ids, lens, n_, mm_, cp_, top.ctypes.data, mx, pas, toks, n_out, lg, lp)
         res = self._generate_batch(entry, prompts, (mm_arr, cp), max_new, max_tokens_per_pass, "step" if want_step_logits else None)
         toks = res[0] if want_step_logits else res
-        out = [None if top[j] < 0 else [_token_logprobs(lp[j * int(max_new) + t]) for t in range(len(toks[j]))] for j in range(n)]
+        out = _unpack_logprobs(lp, top, toks, max_new)
         return (toks, out, res[1]) if want_step_logits else (toks, out)
 
     def generate_batch_adjusted(self, prompts: Sequence[Sequence[int]], max_new: int, params=None, top_logprobs=None, data=None,
@@ -464,31 +473,17 @@ class HipInferenceModel:
 
     def _generate_batch_adjusted(self, prompts, max_new, params, top_logprobs, data, max_tokens_per_pass, want_step_logits, constraint):
         n = len(prompts)
-        if data is not None and len(data) != n:
-            raise ValueError(f"{len(data)} MultiModalData entries for {n} prompts")
+        mm_arr, keep = _mm_array(data, n)
         from .sampling import SamplingParams
         plist = None if params is None else [params] * n if isinstance(params, SamplingParams) else list(params)
         cp = None if plist is None else _sampling_array(plist, n)
-        keep, adj = [], None
+        adj = None
         if plist is not None:
             adj = (_lib.LogitAdjust * max(n, 1))()
             for j, p in enumerate(plist):
                 adj[j], k = p.adjust_to_c()
                 keep.append(k)
-        top = None
-        if top_logprobs is not None:
-            tops = [top_logprobs] * n if isinstance(top_logprobs, (int, np.integer)) else list(top_logprobs)
-            if len(tops) != n:
-                raise ValueError(f"{len(tops)} top_logprobs entries for {n} prompts")
-            top = np.ascontiguousarray(np.asarray([-1 if t is None else int(t) for t in tops] + [0], dtype=np.int32))
-        mm_arr = None
-        if data is not None:
-            mm_arr = (C.c_void_p * max(n, 1))()
-            for j, d in enumerate(data):
-                if d is not None:
-                    mm, k = _mm_input(d)
-                    keep += [mm, k]
-                    mm_arr[j] = C.addressof(mm)
+        top = None if top_logprobs is None else _top_logprobs_array(top_logprobs, n)
         lp = None if top is None else (_lib.TokenLogprobs * max(n * max(int(max_new), 1), 1))()
 
         raised = []
@@ -523,9 +518,7 @@ class HipInferenceModel:
                 raise raised[0]
             raise
         toks = res[0] if want_step_logits else res
-        out = None
-        if top is not None:
-            out = [None if top[j] < 0 else [_token_logprobs(lp[j * int(max_new) + t]) for t in range(len(toks[j]))] for j in range(n)]
+        out = None if top is None else _unpack_logprobs(lp, top, toks, max_new)
         return (toks, out, res[1]) if want_step_logits else (toks, out)
 
     def generate_batch_spec(self, prompts: Sequence[Sequence[int]], max_new: int, spec=None, predictions=None, want_logits: bool = False,
@@ -735,24 +728,22 @@ class HipEngine:
             mm_p = C.byref(mm)
         cp = None if params is None else C.byref(params.to_c())
         rid = C.c_uint64()
+        head, top = (self.handle, ids.ctypes.data, ids.size, mm_p, cp), -1 if top_logprobs is None else int(top_logprobs)
+        adj_p = None
+        if params is not None and getattr(params, "adjust_active", False):   # logit_bias / presence / frequency: the arrays are copied
+            adj, k = params.adjust_to_c()
+            adj_p = C.byref(adj)
+        # the entry: mask -> _masked, an active adjust -> _adjusted, top_logprobs -> _logprobs, otherwise the plain one
         if mask is not None:
             words = np.ascontiguousarray(mask, dtype=np.uint32).reshape(-1)
-            adj_p = None
-            if params is not None and getattr(params, "adjust_active", False):
-                adj, k = params.adjust_to_c()
-                adj_p = C.byref(adj)
-            check(lib().aha_hip_engine_submit_masked(self.handle, ids.ctypes.data, ids.size, mm_p, cp, adj_p, words.ctypes.data, words.size,
-                                                     int(max_new), -1 if top_logprobs is None else int(top_logprobs), C.byref(rid)))
-        elif params is not None and getattr(params, "adjust_active", False):   # logit_bias / presence / frequency: the arrays are copied
-            adj, k = params.adjust_to_c()
-            check(lib().aha_hip_engine_submit_adjusted(self.handle, ids.ctypes.data, ids.size, mm_p, cp, C.byref(adj), int(max_new),
-                                                       -1 if top_logprobs is None else int(top_logprobs), C.byref(rid)))
-            del k
-        elif top_logprobs is None:
-            check(lib().aha_hip_engine_submit(self.handle, ids.ctypes.data, ids.size, mm_p, cp, int(max_new), C.byref(rid)))
+            rc = lib().aha_hip_engine_submit_masked(*head, adj_p, words.ctypes.data, words.size, int(max_new), top, C.byref(rid))
+        elif adj_p is not None:
+            rc = lib().aha_hip_engine_submit_adjusted(*head, adj_p, int(max_new), top, C.byref(rid))
+        elif top_logprobs is not None:
+            rc = lib().aha_hip_engine_submit_logprobs(*head, int(max_new), top, C.byref(rid))
         else:
-            check(lib().aha_hip_engine_submit_logprobs(self.handle, ids.ctypes.data, ids.size, mm_p, cp, int(max_new), int(top_logprobs),
-                                                       C.byref(rid)))
+            rc = lib().aha_hip_engine_submit(*head, int(max_new), C.byref(rid))
+        check(rc)
         self._keep[rid.value] = keep
         self._streams[rid.value] = []
         self._done[rid.value] = False
