@@ -1691,42 +1691,84 @@ int model_decode_greedy(aha_model* m, uint32_t first_token, size_t offset, size_
 }
 
 // ---- prefill ---------------------------------------------------------------------------------------------------
-static int forward_initial_impl(aha_model* m, const uint32_t* ids, size_t n, size_t offset, const aha_mm_input* mm,
-                                float* logits_out, uint32_t* argmax_out, bool hidden_only);
+// The decoder layers of every prefill: forward_initial_impl's (one prompt; context-, tensor- or sequence-parallel) and a packed pass's
+// (packed_layers: independent sequences, single GPU).  What differs between the callers is this struct and the callable that runs between
+// the qkv GEMM and o_proj -- q/k-norm + RoPE + KV append and the attention, which need the rows' cache positions.
+struct PrefillRows {
+  int M;               // rows in the activation buffers (a context-parallel rank: its own rows)
+  int S;               // rows of the whole prompt: the sequence-parallel row slices are cut from it
+  int spr;             // sequence-parallel tensor parallelism: rank r owns rows [r * spr, (r+1) * spr) between the GEMMs; 0 = off
+  bool norm_in_gemm;   // the RMSNorm that follows o_proj / down_proj + residual rides on the GEMM call (GemmArgs::norm_w: inside the
+                       // split-K reduce pass where the plan has one, a separate launch otherwise -- the same values); single GPU only
+  bool vis;            // visual rows: DeepStack adds feature k after layer k < n_deepstack (qwen3vl/model.rs:806-822), which changes the
+                       // rows between down_proj and the next layer's norm -- on those layers the norm does not ride on down_proj
+};
 
-int model_forward_initial(aha_model* m, const uint32_t* ids, size_t n, size_t offset, const aha_mm_input* mm,
-                          float* logits_out, uint32_t* argmax_out) {
-  return forward_initial_impl(m, ids, n, offset, mm, logits_out, argmax_out, false);
-}
+// A prefill GEMM's profile entry: A, W and C once, C twice with a residual (read + write), half of N's columns out of a gate+up pair
+struct GemmProf : ProfScope {
+  static double out_elems(const GemmArgs& g) {
+    return g.residual ? 2.0 * g.M * g.N : g.act == ACT_SILU_MUL_PAIRS ? (double)g.M * (g.N / 2) : (double)g.M * g.N;
+  }
+  GemmProf(aha_model* m, const GemmArgs& g)
+      : ProfScope(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + out_elems(g)) * 2, 2.0 * g.M * g.N * g.K) {}
+};
 
-// Qwen3Embedding::embed_one (qwen3_embedding/mod.rs:50-64): forward_hidden(ids, offset 0) -> last position after the final
-// RMSNorm, bf16 -> f32, l2_normalize over the last dim (modules.rs:1287-1294: x / sqrt(sum(x^2) + 1e-6)), cache cleared.
-// The stack runs on the GPU without the lm_head; the H-element normalisation is f32 host arithmetic like the reference's.
-int model_embed(aha_model* m, const uint32_t* ids, size_t n, float* out) {
-  if (!out) {
-    set_error("embed: out is null");
-    return AHA_ERR_INVALID;
+// rope_attn(li, L): layer li's q/k-norm + RoPE + KV append out of p_qkv and its attention into p_attn; returns an error code
+template <class RopeAttn>
+static int prefill_layers(aha_model* m, const PrefillRows& pr, RopeAttn&& rope_attn) {
+  const aha_model_desc& c = m->desc;
+  const int H = c.hidden_size, I = c.intermediate_size, nq = c.num_attention_heads * c.head_dim, nkv = c.num_key_value_heads * c.head_dim;
+  const int M = pr.M;
+  hipStream_t st = m->stream;
+  int rc;
+  bool in_norm_done = false;
+  for (int li = 0; li < c.num_hidden_layers; ++li) {
+    const LayerWeights& L = m->layers[li];
+    {
+      GemmArgs g{};
+      g.A = m->p_h; g.W = L.wqkv; g.C = m->p_qkv; g.M = M; g.N = nq + 2 * nkv; g.K = H; g.lda = H; g.ldw = H; g.ldc = g.N; g.act = ACT_NONE;
+      if (pr.spr > 0) {   // sequence-parallel: norm of this rank's rows, all-gather in chunks, GEMM per chunk (norm_gather_gemm)
+        if ((rc = norm_gather_gemm(m, L.in_norm, g, pr.S, pr.spr))) return rc;
+      } else {
+        if (!in_norm_done && (rc = prefill_norm(m, L.in_norm, M, 0))) return rc;
+        GemmProf ps(m, g);
+        launch_gemm(g, st);
+      }
+    }
+    in_norm_done = false;
+    if ((rc = rope_attn(li, L))) return rc;
+    {
+      GemmArgs g{};
+      g.A = m->p_attn; g.W = L.wo; g.C = m->p_x; g.residual = m->p_x; g.M = M; g.N = H; g.K = nq; g.lda = nq; g.ldw = nq; g.ldc = H; g.act = ACT_NONE;
+      if (pr.norm_in_gemm) { g.norm_w = L.post_norm; g.norm_out = m->p_h; g.norm_eps = c.rms_norm_eps; }
+      GemmProf ps(m, g);
+      if ((rc = gemm_row_parallel(m, g, pr.spr))) return rc;
+    }
+    {
+      GemmArgs g{};
+      g.A = m->p_h; g.W = L.wgu; g.C = m->p_act; g.M = M; g.N = 2 * I; g.K = H; g.lda = H; g.ldw = H; g.ldc = I; g.act = ACT_SILU_MUL_PAIRS;
+      if (pr.spr > 0) {
+        if ((rc = norm_gather_gemm(m, L.post_norm, g, pr.S, pr.spr))) return rc;
+      } else {
+        if (!pr.norm_in_gemm && (rc = prefill_norm(m, L.post_norm, M, 0))) return rc;
+        GemmProf ps(m, g);
+        launch_gemm(g, st);
+      }
+    }
+    {
+      GemmArgs g{};
+      g.A = m->p_act; g.W = L.wdown; g.C = m->p_x; g.residual = m->p_x; g.M = M; g.N = H; g.K = I; g.lda = I; g.ldw = I; g.ldc = H; g.act = ACT_NONE;
+      if (pr.norm_in_gemm && li + 1 < c.num_hidden_layers && !(pr.vis && vision_has_deepstack(m, li))) {
+        g.norm_w = m->layers[li + 1].in_norm; g.norm_out = m->p_h; g.norm_eps = c.rms_norm_eps;
+        in_norm_done = true;
+      }
+      GemmProf ps(m, g);
+      if ((rc = gemm_row_parallel(m, g, pr.spr))) return rc;
+    }
+    // (context-parallel: the visual rows of other ranks all land on the scratch row behind this rank's rows)
+    if (pr.vis && (rc = vision_deepstack_add(m, li, m->p_x))) return rc;
   }
-  if (m->desc.arch != AHA_ARCH_QWEN3) {
-    set_error("embed: only the Qwen3 text stack has an embedding head in the reference (qwen3_embedding/mod.rs)");
-    return AHA_ERR_UNSUPPORTED;
-  }
-  int rc = model_clear_cache(m);
-  if (rc) return rc;
-  if ((rc = forward_initial_impl(m, ids, n, 0, nullptr, nullptr, nullptr, true))) return rc;
-  const int H = m->desc.hidden_size;
-  std::vector<uint16_t> h((size_t)H);
-  AHA_HIP_CHECK(hipMemcpyAsync(h.data(), m->d_hlast, (size_t)H * 2, hipMemcpyDeviceToHost, m->stream));
-  AHA_HIP_CHECK(hipStreamSynchronize(m->stream));
-  float ss = 0.f;
-  for (int i = 0; i < H; ++i) {
-    uint32_t u = (uint32_t)h[i] << 16;
-    memcpy(&out[i], &u, 4);
-    ss += out[i] * out[i];
-  }
-  const float nrm = sqrtf(ss + 1e-6f);
-  for (int i = 0; i < H; ++i) out[i] /= nrm;
-  return model_clear_cache(m);
+  return AHA_OK;
 }
 
 static int forward_initial_impl(aha_model* m, const uint32_t* ids, size_t n, size_t offset, const aha_mm_input* mm,
@@ -1756,7 +1798,7 @@ static int forward_initial_impl(aha_model* m, const uint32_t* ids, size_t n, siz
     if (ptrace) fprintf(stderr, "[prefill trace] %-28s %8.1f us\n", what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - pt0).count());
   };
   const int S = (int)n;
-  const int H = c.hidden_size, I = c.intermediate_size, d = c.head_dim, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
+  const int H = c.hidden_size, d = c.head_dim, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
   const int nq = nh * d, nkv = kvh * d;
   hipStream_t st = m->stream;
   int rc;
@@ -1839,41 +1881,22 @@ static int forward_initial_impl(aha_model* m, const uint32_t* ids, size_t n, siz
     if ((rc = audio_forward_requests(m, &r, 1, m->p_x))) return rc;
   }
   if (d == 128) launch_rope_table(m->p_pos, Mloc, m->d_inv_freq, m->d_axis_map, Mloc, m->p_rope, st);   // cos / sin once for all layers
-  // sequence-parallel tensor parallelism: rank r owns rows [r * spr, (r+1) * spr) of the residual stream between the GEMMs
-  const int spr = seq_parallel_on(m) ? (S + m->tp_size - 1) / m->tp_size : 0;
   auto rows = [](const void* base, int64_t r0, int64_t row_elems) { return (void*)((char*)base + r0 * row_elems * 2); };   // bf16 rows
-  // Single GPU: the RMSNorm that follows o_proj / down_proj + residual rides on the GEMM call (GemmArgs::norm_w: inside the
-  // split-K reduce pass where the plan has one, a separate launch otherwise -- the same values).  Not across a DeepStack add,
-  // which changes the rows between down_proj and the next layer's norm.
-  const bool norm_in_gemm = m->tp_size <= 1;
-  bool in_norm_done = false;
-  for (int li = 0; li < c.num_hidden_layers; ++li) {
-    const LayerWeights& L = m->layers[li];
-    {
-      GemmArgs g{};
-      g.A = m->p_h; g.W = L.wqkv; g.C = m->p_qkv; g.M = Mloc; g.N = nq + 2 * nkv; g.K = H; g.lda = H; g.ldw = H; g.ldc = g.N; g.act = ACT_NONE;
-      if (spr > 0) {   // sequence-parallel: norm of this rank's rows, all-gather in chunks, GEMM per chunk (norm_gather_gemm)
-        if ((rc = norm_gather_gemm(m, L.in_norm, g, S, spr))) return rc;
-      } else {
-        if (!in_norm_done && (rc = prefill_norm(m, L.in_norm, Mloc, 0))) return rc;
-        ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
-        launch_gemm(g, st);
-      }
-    }
-    in_norm_done = false;
-    // q-norm + RoPE of the q heads inside the attention kernel's Q load where that kernel takes it (round 6: head_dim 128 on the 16-row
-    // form, i.e. every prompt below ~3 k tokens): the rope kernel then handles K and V only and the attention reads the raw q heads of p_qkv
-    bool q_fused = d == 128 && m->p_rope != nullptr;
-    {
-      const bool one = segs.size() == 2 && segs[1].l0 == segs[0].l0 + segs[0].len && segs[1].r0 > segs[0].r0;
-      for (size_t si = 0; si < segs.size() && q_fused; ++si) {
-        AttnPrefillArgs pa{};
-        pa.S = segs[si].len; pa.nh = nh; pa.kvh = kvh; pa.d = d; pa.causal = 1; pa.scale = m->attn_scale; pa.rows_hint = (int)S;
-        if (one) pa.S2 = segs[1].len;
-        q_fused = attn_prefill_takes_qfuse(pa);
-        if (one) break;
-      }
-    }
+  // A context-parallel rank's two chunks (early + late, adjacent local rows) go out as ONE attention launch: each alone is a few hundred
+  // blocks -- block rounds and ramp, not tile work, set its time (profiles/r05_shard_rank_time.txt) -- together the early chunk's
+  // short blocks fill the late chunk's last round (kernels_attn.hip, AttnPrefillArgs::S2).
+  const bool one_launch = segs.size() == 2 && segs[1].l0 == segs[0].l0 + segs[0].len && segs[1].r0 > segs[0].r0;
+  const size_t n_attn = one_launch ? 1 : segs.size();   // attention launches per layer
+  // q-norm + RoPE of the q heads inside the attention kernel's Q load where that kernel takes it (round 6: head_dim 128 on the 16-row
+  // form, i.e. every prompt below ~3 k tokens): the rope kernel then handles K and V only and the attention reads the raw q heads of p_qkv
+  bool q_fused = d == 128 && m->p_rope != nullptr;
+  for (size_t si = 0; si < n_attn && q_fused; ++si) {
+    AttnPrefillArgs pa{};
+    pa.S = segs[si].len; pa.nh = nh; pa.kvh = kvh; pa.d = d; pa.causal = 1; pa.scale = m->attn_scale; pa.rows_hint = (int)S;
+    if (one_launch) pa.S2 = segs[1].len;
+    q_fused = attn_prefill_takes_qfuse(pa);
+  }
+  auto rope_attn = [&](int li, const LayerWeights& L) -> int {
     for (const RowSeg& sg : segs) {
       RopeArgs r{};
       r.qkv = rows(m->p_qkv, sg.l0, nq + 2 * nkv); r.ld = nq + 2 * nkv; r.q_norm_w = L.q_norm; r.k_norm_w = L.k_norm;
@@ -1887,11 +1910,7 @@ static int forward_initial_impl(aha_model* m, const uint32_t* ids, size_t n, siz
       launch_qknorm_rope(r, st);
     }
     if (cp && (rc = cp_gather_kv(m, li, cpp))) return rc;
-    // A context-parallel rank's two chunks (early + late, adjacent local rows) go out as ONE launch: each alone is a few hundred
-    // blocks -- block rounds and ramp, not tile work, set its time (profiles/r05_shard_rank_time.txt) -- together the early chunk's
-    // short blocks fill the late chunk's last round (kernels_attn.hip, AttnPrefillArgs::S2).
-    const bool one_launch = segs.size() == 2 && segs[1].l0 == segs[0].l0 + segs[0].len && segs[1].r0 > segs[0].r0;
-    for (size_t si = 0; si < segs.size(); ++si) {
+    for (size_t si = 0; si < n_attn; ++si) {
       const RowSeg& sg = segs[si];
       AttnPrefillArgs a{};
       a.q = rows(m->p_q, sg.l0, nq); a.kv = model_kv_layer(m, li); a.o = rows(m->p_attn, sg.l0, nq); a.S = sg.len; a.nh = nh; a.kvh = kvh; a.d = d;
@@ -1909,42 +1928,12 @@ static int forward_initial_impl(aha_model* m, const uint32_t* ids, size_t n, siz
       }
       ProfScope ps(m, "attn_prefill", rows_io * nq * 4 + Lk * nkv * 4, flops);
       launch_attn_prefill(a, st);
-      if (one_launch) break;
     }
-    {
-      GemmArgs g{};
-      g.A = m->p_attn; g.W = L.wo; g.C = m->p_x; g.residual = m->p_x; g.M = Mloc; g.N = H; g.K = nq; g.lda = nq; g.ldw = nq; g.ldc = H; g.act = ACT_NONE;
-      if (norm_in_gemm) { g.norm_w = L.post_norm; g.norm_out = m->p_h; g.norm_eps = c.rms_norm_eps; }
-      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + 2.0 * g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
-      if ((rc = gemm_row_parallel(m, g, spr))) return rc;
-    }
-    {
-      GemmArgs g{};
-      g.A = m->p_h; g.W = L.wgu; g.C = m->p_act; g.M = Mloc; g.N = 2 * I; g.K = H; g.lda = H; g.ldw = H; g.ldc = I; g.act = ACT_SILU_MUL_PAIRS;
-      if (spr > 0) {
-        if ((rc = norm_gather_gemm(m, L.post_norm, g, S, spr))) return rc;
-      } else {
-        if (!norm_in_gemm && (rc = prefill_norm(m, L.post_norm, Mloc, 0))) return rc;
-        ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * I) * 2, 2.0 * g.M * g.N * g.K);
-        launch_gemm(g, st);
-      }
-    }
-    {
-      GemmArgs g{};
-      g.A = m->p_act; g.W = L.wdown; g.C = m->p_x; g.residual = m->p_x; g.M = Mloc; g.N = H; g.K = I; g.lda = I; g.ldw = I; g.ldc = H; g.act = ACT_NONE;
-      if (norm_in_gemm && li + 1 < c.num_hidden_layers && !(has_image && vision_has_deepstack(m, li))) {
-        g.norm_w = m->layers[li + 1].in_norm; g.norm_out = m->p_h; g.norm_eps = c.rms_norm_eps;
-        in_norm_done = true;
-      }
-      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + 2.0 * g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
-      if ((rc = gemm_row_parallel(m, g, spr))) return rc;
-    }
-    if (has_image) {
-      // DeepStack: add visual feature k to the visual rows after decoder layer k (qwen3vl/model.rs:806-822)
-      // (context-parallel: the rows of other ranks all land on the scratch row behind this rank's rows)
-      if ((rc = vision_deepstack_add(m, li, m->p_x))) return rc;
-    }
-  }
+    return AHA_OK;
+  };
+  // sequence-parallel tensor parallelism: rank r owns rows [r * spr, (r+1) * spr) of the residual stream between the GEMMs
+  const int spr = seq_parallel_on(m) ? (S + m->tp_size - 1) / m->tp_size : 0;
+  if ((rc = prefill_layers(m, PrefillRows{Mloc, S, spr, m->tp_size <= 1, has_image}, rope_attn))) return rc;
   const void* x_last = (const char*)m->p_x + (size_t)(Mloc - 1) * H * 2;   // the prompt's last row (context-parallel: on rank 0, which owns the last chunk)
   if (cp) {
     // rank 0 owns the last chunk, hence the last row: every rank contributes its (stale, except rank 0's) copy of that row to one small
@@ -1977,6 +1966,41 @@ static int forward_initial_impl(aha_model* m, const uint32_t* ids, size_t n, siz
   rc = fetch_outputs(m, logits_out, argmax_out);
   pstamp("outputs fetched (GPU done)");
   return rc;
+}
+
+int model_forward_initial(aha_model* m, const uint32_t* ids, size_t n, size_t offset, const aha_mm_input* mm,
+                          float* logits_out, uint32_t* argmax_out) {
+  return forward_initial_impl(m, ids, n, offset, mm, logits_out, argmax_out, false);
+}
+
+// Qwen3Embedding::embed_one (qwen3_embedding/mod.rs:50-64): forward_hidden(ids, offset 0) -> last position after the final
+// RMSNorm, bf16 -> f32, l2_normalize over the last dim (modules.rs:1287-1294: x / sqrt(sum(x^2) + 1e-6)), cache cleared.
+// The stack runs on the GPU without the lm_head; the H-element normalisation is f32 host arithmetic like the reference's.
+int model_embed(aha_model* m, const uint32_t* ids, size_t n, float* out) {
+  if (!out) {
+    set_error("embed: out is null");
+    return AHA_ERR_INVALID;
+  }
+  if (m->desc.arch != AHA_ARCH_QWEN3) {
+    set_error("embed: only the Qwen3 text stack has an embedding head in the reference (qwen3_embedding/mod.rs)");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  int rc = model_clear_cache(m);
+  if (rc) return rc;
+  if ((rc = forward_initial_impl(m, ids, n, 0, nullptr, nullptr, nullptr, true))) return rc;
+  const int H = m->desc.hidden_size;
+  std::vector<uint16_t> h((size_t)H);
+  AHA_HIP_CHECK(hipMemcpyAsync(h.data(), m->d_hlast, (size_t)H * 2, hipMemcpyDeviceToHost, m->stream));
+  AHA_HIP_CHECK(hipStreamSynchronize(m->stream));
+  float ss = 0.f;
+  for (int i = 0; i < H; ++i) {
+    uint32_t u = (uint32_t)h[i] << 16;
+    memcpy(&out[i], &u, 4);
+    ss += out[i] * out[i];
+  }
+  const float nrm = sqrtf(ss + 1e-6f);
+  for (int i = 0; i < H; ++i) out[i] /= nrm;
+  return model_clear_cache(m);
 }
 
 // ---- packed-batch embedding -----------------------------------------------------------------------------------------------
@@ -2037,33 +2061,21 @@ struct ClearCacheGuard {   // the cache is empty afterwards, on success and on e
   ~ClearCacheGuard() { model_clear_cache(m); }
 };
 
-// The single-GPU layer stack of a packed prefill pass of independent sequences (run_packed_pass): the rows' embeddings in
-// p_x, their positions' rope table in p_rope; K / V of row r go to cache slot d_slot[r] of the pages page_ptrs names, page p of 0 .. npages-1
-// holding the rows d_prow[2p] .. + d_prow[2p + 1]; the attention runs one block per (d_items entry, head) over d_seg's segments.  Leaves the
-// last layer's output rows in p_x.  vis: the pass has visual rows (the tower's last pass scattered them): DeepStack adds after layer k <
-// n_deepstack (qwen3vl/model.rs:806-822), and on those layers the next in_norm does not ride on down_proj (as in forward_initial_impl).
+// The layer stack of a packed prefill pass of independent sequences (run_packed_pass): prefill_layers on a single GPU, with the packed rows'
+// cache slots in the rope kernel and segments in the attention.  The rows' embeddings in p_x, their positions' rope table in p_rope; K / V of
+// row r go to cache slot d_slot[r] of the pages page_ptrs names, page p of 0 .. npages-1 holding the rows d_prow[2p] .. + d_prow[2p + 1]; the
+// attention runs one block per (d_items entry, head) over d_seg's segments, reading attn_page_ptrs (chunked segments, d_kv0 their cache
+// prefixes: the prefix pages, then the pages this pass writes) or else page_ptrs.  Leaves the last layer's output rows in p_x.  vis: the pass
+// has visual rows (the tower's last pass scattered them).
 static int packed_layers(aha_model* m, int S, const uint64_t* page_ptrs, const int32_t* d_seg, const int32_t* d_items, int n_items,
                          const int32_t* d_slot, const int32_t* d_prow, int npages, double attn_flops, bool vis = false,
                          const uint64_t* attn_page_ptrs = nullptr, const int32_t* d_kv0 = nullptr) {
   const aha_model_desc& c = m->desc;
-  const int H = c.hidden_size, I = c.intermediate_size, d = c.head_dim, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
-  const int nq = nh * d, nkv = kvh * d;
+  const int d = c.head_dim, nh = c.num_attention_heads, kvh = c.num_key_value_heads, nq = nh * d, nkv = kvh * d;
   hipStream_t st = m->stream;
-  int rc;
-  // the single-GPU layer of forward_initial_impl, with the packed rows' cache slots in the rope kernel and segments in the attention
-  bool in_norm_done = false;
-  for (int li = 0; li < c.num_hidden_layers; ++li) {
-    const LayerWeights& L = m->layers[li];
+  return prefill_layers(m, PrefillRows{S, S, 0, true, vis}, [&](int li, const LayerWeights& L) -> int {
     KvLayer kv = model_kv_layer(m, li);
     kv.page_ptrs = page_ptrs;
-    {
-      GemmArgs g{};
-      g.A = m->p_h; g.W = L.wqkv; g.C = m->p_qkv; g.M = S; g.N = nq + 2 * nkv; g.K = H; g.lda = H; g.ldw = H; g.ldc = g.N; g.act = ACT_NONE;
-      if (!in_norm_done && (rc = prefill_norm(m, L.in_norm, S, 0))) return rc;
-      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
-      launch_gemm(g, st);
-    }
-    in_norm_done = false;
     {   // K and V of every row to its slot; the q heads are normed and rotated in the attention kernel's Q load
       RopeArgs r{};
       r.qkv = m->p_qkv; r.ld = nq + 2 * nkv; r.q_norm_w = L.q_norm; r.k_norm_w = L.k_norm;
@@ -2075,43 +2087,17 @@ static int packed_layers(aha_model* m, int S, const uint64_t* page_ptrs, const i
       ProfScope ps(m, "elem", (double)S * 2 * nkv * 4, 0);
       launch_qknorm_rope(r, st);
     }
-    {
-      AttnPrefillArgs a{};
-      a.q = m->p_qkv; a.q_ld = nq + 2 * nkv; a.kv = kv; a.o = m->p_attn; a.S = S; a.nh = nh; a.kvh = kvh; a.d = d;
-      a.kv_offset = 0; a.kv_total = S; a.causal = 1; a.scale = m->attn_scale;
-      a.q_norm_w = L.q_norm; a.q_rope_tab = m->p_rope; a.q_eps = c.rms_norm_eps;
-      a.seg_tab = d_seg; a.seg_items = d_items; a.n_items = n_items;
-      if (attn_page_ptrs) a.kv.page_ptrs = attn_page_ptrs;   // chunked segments: their prefix pages, then the pages this pass writes
-      a.seg_kv0 = d_kv0;
-      ProfScope ps(m, "attn_prefill", (double)S * nq * 4 + (double)S * nkv * 4, attn_flops);
-      launch_attn_prefill(a, st);
-    }
-    {
-      GemmArgs g{};
-      g.A = m->p_attn; g.W = L.wo; g.C = m->p_x; g.residual = m->p_x; g.M = S; g.N = H; g.K = nq; g.lda = nq; g.ldw = nq; g.ldc = H; g.act = ACT_NONE;
-      g.norm_w = L.post_norm; g.norm_out = m->p_h; g.norm_eps = c.rms_norm_eps;
-      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + 2.0 * g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
-      if ((rc = gemm_row_parallel(m, g, 0))) return rc;
-    }
-    {
-      GemmArgs g{};
-      g.A = m->p_h; g.W = L.wgu; g.C = m->p_act; g.M = S; g.N = 2 * I; g.K = H; g.lda = H; g.ldw = H; g.ldc = I; g.act = ACT_SILU_MUL_PAIRS;
-      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * I) * 2, 2.0 * g.M * g.N * g.K);
-      launch_gemm(g, st);
-    }
-    {
-      GemmArgs g{};
-      g.A = m->p_act; g.W = L.wdown; g.C = m->p_x; g.residual = m->p_x; g.M = S; g.N = H; g.K = I; g.lda = I; g.ldw = I; g.ldc = H; g.act = ACT_NONE;
-      if (li + 1 < c.num_hidden_layers && !(vis && vision_has_deepstack(m, li))) {
-        g.norm_w = m->layers[li + 1].in_norm; g.norm_out = m->p_h; g.norm_eps = c.rms_norm_eps;
-        in_norm_done = true;
-      }
-      ProfScope ps(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + 2.0 * g.M * g.N) * 2, 2.0 * g.M * g.N * g.K);
-      if ((rc = gemm_row_parallel(m, g, 0))) return rc;
-    }
-    if (vis && (rc = vision_deepstack_add(m, li, m->p_x))) return rc;
-  }
-  return AHA_OK;
+    AttnPrefillArgs a{};
+    a.q = m->p_qkv; a.q_ld = nq + 2 * nkv; a.kv = kv; a.o = m->p_attn; a.S = S; a.nh = nh; a.kvh = kvh; a.d = d;
+    a.kv_offset = 0; a.kv_total = S; a.causal = 1; a.scale = m->attn_scale;
+    a.q_norm_w = L.q_norm; a.q_rope_tab = m->p_rope; a.q_eps = c.rms_norm_eps;
+    a.seg_tab = d_seg; a.seg_items = d_items; a.n_items = n_items;
+    if (attn_page_ptrs) a.kv.page_ptrs = attn_page_ptrs;
+    a.seg_kv0 = d_kv0;
+    ProfScope ps(m, "attn_prefill", (double)S * nq * 4 + (double)S * nkv * 4, attn_flops);
+    launch_attn_prefill(a, st);
+    return AHA_OK;
+  });
 }
 
 // The host plan of one packed pass over n_seg sequences.  tab is the int32 table the pass's kernels read from p_pass_tab: segments
@@ -2294,11 +2280,13 @@ int model_embed_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens,
 }
 
 // ---- batched greedy generation ---------------------------------------------------------------------------------------------------
-// generate_generic (common/generate.rs:115-159) at temperature 0 for many prompts at once.  Prefill: the packed passes of embed_batch
-// (packed_layers), each prompt on its own run of pages, then every prompt's last row through the final RMSNorm and the batched lm_head ->
-// the first token.  Decode: all unfinished sequences advance together, one step = the R rows through every layer with the weights streamed
-// once per group of <= 32 rows (gemv_rows) and ONE attention launch per layer (attn_decode_batch); the next tokens stay on the device (the
-// step's argmax writes the token vector the next step's embedding gather reads), the host reads them once per step to drop finished rows.
+// generate_generic (common/generate.rs:115-159) at temperature 0 for many prompts at once.  Prefill (gen_packed_pass): the packed passes
+// of embed_batch, each prompt on its own run of pages, then every prompt's last row through the final RMSNorm and the batched lm_head ->
+// the first token.  Decode (gen_write_row per row, gen_decode_step, gen_finish_step): all unfinished sequences advance together, one step =
+// the R rows through every layer with the weights streamed once per group of <= 32 rows (gemv_rows) and ONE attention launch per layer
+// (attn_decode_batch); the next tokens stay on the device (the step's argmax writes the token vector the next step's embedding gather
+// reads), the host reads them once per step to drop finished rows.  The blocking entries (model_generate_batch, its draft-and-verify loop)
+// and the engine's step are these same pieces under different bookkeeping.
 namespace {
 struct DevBufs {   // per-call device / pinned scratch, freed after the stream has drained
   hipStream_t st;
@@ -2414,36 +2402,63 @@ static void gen_head(aha_model* m, GenCall& gc, int row0, int rows, uint32_t* to
   launch_argmax_rows(gc.blk_max + (int64_t)row0 * tiles, gc.blk_idx + (int64_t)row0 * tiles, tiles, rows, tok_out + row0, m->stream);
 }
 
-// One packed prefill pass over sequences j0 .. j0+n_seg-1 (ids: theirs, packed); sequence j's cache starts on logical page page0[j].
-// Positions: sequence j's three M-RoPE rows pos3[j] (3 x len, get_rope_index at offset 0) when it has them, else arange; mm[j] (may be
-// null, or all null): its images / videos or its audio clip, encoded for the whole pass in one tower pass and scattered to its placeholder
-// rows.  Then every sequence's last row through the head -> its first token in token vector 0.
-static int generate_prefill_pass(aha_model* m, GenCall& gc, const uint32_t* ids, const size_t* lens, int j0, int n_seg,
-                                 const std::vector<int64_t>& page0, const std::vector<std::vector<int32_t>>& pos3,
-                                 const aha_mm_input* const* mm) {
-  const int H = m->desc.hidden_size;
-  hipStream_t st = m->stream;
-  const PackedPass pp = plan_packed_pass(lens, n_seg, page0.data() + j0, pos3.data() + j0);
+// A batched decode step's running totals over its rows
+struct GenStepRows {
+  int max_split = 1;      // the rows' largest KV split
+  double kv_tokens = 0;   // their cache lengths summed (the profile's bytes)
+};
+
+// Row r of a batched decode step's table (kernels.h GEN_ROW_*): a sequence whose cache holds kv_len tokens after the row's append, on the
+// pages from page0 of the step's page table.  ctr_acc: where the counters of the row's head_ctr block ctr_row stand, advanced by the step's
+// arrivals; src / tok: the entry of the step's token vector that holds the row's input token, or the token itself (GEN_ROW_TOK).
+static void gen_write_row(const aha_model* m, GenCall& gc, GenStepRows& sr, int r, int64_t page0, int kv_len, int64_t rope_delta,
+                          unsigned& ctr_acc, int src, int ctr_row, int32_t tok = 0) {
+  const aha_model_desc& c = m->desc;
+  const int ns = attn_decode_nsplit(kv_len, c.num_attention_heads / c.num_key_value_heads, m->max_nsplit);
+  int32_t* t = gc.h_rowtab + (size_t)r * GEN_ROW_WORDS;
+  t[GEN_ROW_PAGE0] = (int32_t)page0;
+  t[GEN_ROW_KVLEN] = kv_len;
+  t[GEN_ROW_NSPLIT] = ns;
+  t[GEN_ROW_CTR] = (int32_t)ctr_acc;
+  t[GEN_ROW_POS] = (int32_t)(kv_len - 1 + rope_delta);   // seqlen_offset + rope_delta (qwen3vl/model.rs:1235-1264)
+  t[GEN_ROW_SRC] = src;
+  t[GEN_ROW_CTRROW] = ctr_row;
+  t[GEN_ROW_TOK] = tok;
+  if (ns > 1) ctr_acc += (unsigned)c.num_hidden_layers * (unsigned)ns;   // a single split never touches its counter
+  sr.max_split = std::max(sr.max_split, ns);
+  sr.kv_tokens += kv_len;
+}
+
+// The packed prefill pass of a generate_batch* call or of an engine step, planned by the caller: pp over ids (the pass's, packed), its pages
+// indices into phys, the physical page addresses.  mm (may be null, as may any entry): segment j's images / videos or its audio clip
+// (check_mm_requests checked both kinds), reported as sequence seq0 + j, encoded for the whole pass in one tower pass and scattered to its
+// placeholder rows.  The pass's pages go up as a table of their own, gc.pass_pages -- the rope kernel's, then the attention's when the plan
+// has cache prefixes -- so pages a segment does not write in this pass never appear in the rope kernel's page list; the table is free: the
+// previous pass ended in a synchronise.  Then the last rows of the first k segments -> gc.x rows row0 .., and the head -> their first tokens
+// in token vector 0.  Nothing here waits for the stream: the caller does, before the table and the staging buffer are reused.
+static int gen_packed_pass(aha_model* m, GenCall& gc, const PackedPass& pp, const uint32_t* ids, const aha_mm_input* const* mm, int seq0,
+                           const uint64_t* phys, int k, int row0) {
   std::vector<VisRequest> vreqs;   // the pass's requests with images / videos, at their first packed row
-  std::vector<AudRequest> areqs;   // the pass's requests with an audio clip (check_mm_requests checked both kinds)
-  for (int j = 0; j < n_seg && mm; ++j) {
-    const aha_mm_input* q = mm[j0 + j];
+  std::vector<AudRequest> areqs;   // the pass's requests with an audio clip
+  for (int j = 0; j < pp.n_seg && mm; ++j) {
+    const aha_mm_input* q = mm[j];
     const int r0 = pp.tab[3 * j];
-    if (q && (q->n_images > 0 || q->n_videos > 0)) vreqs.push_back(VisRequest{q, ids + r0, lens[j], r0, j0 + j});
-    else if (q && m->audio) areqs.push_back(AudRequest{q, ids + r0, lens[j], r0, j0 + j});
+    const size_t len = (size_t)pp.tab[3 * j + 1];
+    if (q && (q->n_images > 0 || q->n_videos > 0)) vreqs.push_back(VisRequest{q, ids + r0, len, r0, seq0 + j});
+    else if (q && m->audio) areqs.push_back(AudRequest{q, ids + r0, len, r0, seq0 + j});
   }
-  // the pass's pages are a table of their own: pass page p = the sequence's logical page, so its decode pages (not written here) never
-  // appear in the rope kernel's page list.  The previous pass ended in a synchronise: the table is free.
-  std::vector<uint64_t> pages(pp.pages.size());
-  for (size_t p = 0; p < pages.size(); ++p) pages[p] = m->h_page_ptrs[(size_t)pp.pages[p]];
-  AHA_HIP_CHECK(hipMemcpy(gc.pass_pages, pages.data(), pages.size() * 8, hipMemcpyHostToDevice));
-  int rc;
-  if ((rc = run_packed_pass(m, pp, ids, gc.pass_pages, vreqs, areqs))) return rc;
-  // every sequence's last row -> gc.x row j0 + j, then the head -> first tokens into token vector 0
-  launch_embed_gather(m->p_x, reinterpret_cast<const uint32_t*>(m->p_pass_tab + pp.o_last), (bf16_t*)gc.x + (int64_t)j0 * H, n_seg, H, st);
-  gen_head(m, gc, j0, n_seg, gc.tok[0]);
-  AHA_HIP_CHECK(hipGetLastError());
-  AHA_HIP_CHECK(hipStreamSynchronize(st));   // the pass page table and the staging buffer are reused by the next pass
+  const size_t n_rope = pp.pages.size();
+  std::vector<uint64_t> tab(n_rope + pp.attn_pages.size());
+  for (size_t p = 0; p < n_rope; ++p) tab[p] = phys[(size_t)pp.pages[p]];
+  for (size_t p = 0; p < pp.attn_pages.size(); ++p) tab[n_rope + p] = phys[(size_t)pp.attn_pages[p]];
+  AHA_HIP_CHECK(hipMemcpy(gc.pass_pages, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+  if (int rc = run_packed_pass(m, pp, ids, gc.pass_pages, vreqs, areqs, gc.pass_pages + n_rope)) return rc;
+  if (k > 0) {
+    launch_embed_gather(m->p_x, reinterpret_cast<const uint32_t*>(m->p_pass_tab + pp.o_last), (bf16_t*)gc.x + (int64_t)row0 * gc.H, k, gc.H,
+                        m->stream);
+    gen_head(m, gc, row0, k, gc.tok[0]);
+    AHA_HIP_CHECK(hipGetLastError());
+  }
   return AHA_OK;
 }
 
@@ -2914,7 +2929,7 @@ static int spec_decode_loop(aha_model* m, GenCall& gc, const GenOptions& sp, con
                             std::vector<int>& active, float* logits_out) {
   const aha_model_desc& c = m->desc;
   hipStream_t st = m->stream;
-  const int n = gc.n, L = c.num_hidden_layers, g = c.num_attention_heads / c.num_key_value_heads, V = gc.V;
+  const int n = gc.n, V = gc.V;
   const size_t max_new = gc.max_new;
   // context of the proposer: prompt || generated
   std::vector<std::vector<uint32_t>> ctx(n);
@@ -2932,8 +2947,8 @@ static int spec_decode_loop(aha_model* m, GenCall& gc, const GenOptions& sp, con
   while (!active.empty()) {
     const int nact = (int)active.size();
     int extra = (nact + GEN_ROW_GROUP - 1) / GEN_ROW_GROUP * GEN_ROW_GROUP - nact;
-    int R = 0, max_split = 1, n_drafts = 0;
-    double kv_tokens = 0;
+    int R = 0, n_drafts = 0;
+    GenStepRows sr;
     for (int a = 0; a < nact; ++a) {
       const int j = active[a];
       const size_t t_gen = gc.n_out[j];
@@ -2948,29 +2963,16 @@ static int spec_decode_loop(aha_model* m, GenCall& gc, const GenOptions& sp, con
       n_drafts += (int)k;
       row0[a] = R;
       ndraft[a] = (int)k;
-      for (int i = 0; i <= (int)k; ++i, ++R) {
-        const int kv_len = (int)(seq_lens[j] + t_gen) + i;   // the cache after this row's append
-        const int ns = attn_decode_nsplit(kv_len, g, m->max_nsplit);
-        int32_t* t = gc.h_rowtab + (size_t)R * GEN_ROW_WORDS;
-        t[GEN_ROW_PAGE0] = (int32_t)page0[j];
-        t[GEN_ROW_KVLEN] = kv_len;
-        t[GEN_ROW_NSPLIT] = ns;
-        t[GEN_ROW_CTR] = (int32_t)ctr_acc[R];
-        t[GEN_ROW_POS] = (int32_t)(kv_len - 1 + rope_delta[j]);
-        t[GEN_ROW_SRC] = R * GEN_ROW_WORDS + GEN_ROW_TOK;
-        t[GEN_ROW_CTRROW] = R;
-        t[GEN_ROW_TOK] = (int32_t)(i == 0 ? ctx[j].back() : draft[i - 1]);
-        if (ns > 1) ctr_acc[R] += (unsigned)L * (unsigned)ns;   // a single split never touches its counter
-        max_split = std::max(max_split, ns);
-        kv_tokens += kv_len;
-      }
+      for (int i = 0; i <= (int)k; ++i, ++R)   // the cache after row i's append: the prompt, the tokens so far and the drafts before it
+        gen_write_row(m, gc, sr, R, page0[j], (int)(seq_lens[j] + t_gen) + i, rope_delta[j], ctr_acc[R], R * GEN_ROW_WORDS + GEN_ROW_TOK, R,
+                      (int32_t)(i == 0 ? ctx[j].back() : draft[i - 1]));
     }
     int32_t* h_seq = gc.h_rowtab + (size_t)R * GEN_ROW_WORDS;
     for (int a = 0; a < nact; ++a) h_seq[a * SPEC_SEQ_WORDS + SPEC_SEQ_ROW0] = row0[a], h_seq[a * SPEC_SEQ_WORDS + SPEC_SEQ_NDRAFT] = ndraft[a];
     const size_t words = (size_t)R * GEN_ROW_WORDS + (size_t)nact * SPEC_SEQ_WORDS;
     AHA_HIP_CHECK(hipMemcpyAsync(gc.rowtab, gc.h_rowtab, words * 4, hipMemcpyHostToDevice, st));
     // a step without drafts is generate_batch's step: one attention launch per layer, the fused append
-    gen_decode_step(m, gc, R, max_split, kv_tokens, reinterpret_cast<const uint32_t*>(gc.rowtab), gc.tok[0], n_drafts > 0);
+    gen_decode_step(m, gc, R, sr.max_split, sr.kv_tokens, reinterpret_cast<const uint32_t*>(gc.rowtab), gc.tok[0], n_drafts > 0);
     {
       ProfScope ps(m, "spec_accept_rows", (double)R * 8, 0);
       launch_spec_accept_rows(gc.tok[0], gc.rowtab, gc.rowtab + (size_t)R * GEN_ROW_WORDS, nact, gc.spec_out, st);
@@ -3100,7 +3102,7 @@ int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_le
   if ((rc = model_clear_cache(m))) return rc;
   ClearCacheGuard guard{m};
   hipStream_t st = m->stream;
-  const int n = (int)n_seqs, L = c.num_hidden_layers, g = c.num_attention_heads / c.num_key_value_heads, V = c.vocab_size;
+  const int n = (int)n_seqs, g = c.num_attention_heads / c.num_key_value_heads, V = c.vocab_size;
   // every sequence's pages, reserved up front: ceil((len + max_new) / 64) consecutive logical pages
   std::vector<int64_t> page0(n);
   size_t npages = 0;
@@ -3134,8 +3136,14 @@ int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_le
     return rc;
 
   // ---- prefill: packed passes ----
-  for (const PassRange& p : split_passes(seq_lens, n_seqs, max_tokens_per_pass))
-    if ((rc = generate_prefill_pass(m, gc, ids + p.off, seq_lens + p.j, (int)p.j, (int)(p.k - p.j), page0, pos3, o.mm))) return rc;
+  // sequence j's cache starts on logical page page0[j]; its positions are its three M-RoPE rows pos3[j] (get_rope_index at offset 0) when
+  // it has them, else arange; every sequence's last row -> gc.x row j -> its first token
+  for (const PassRange& p : split_passes(seq_lens, n_seqs, max_tokens_per_pass)) {
+    const int j0 = (int)p.j, n_seg = (int)(p.k - p.j);
+    const PackedPass pp = plan_packed_pass(seq_lens + j0, n_seg, page0.data() + j0, pos3.data() + j0);
+    if ((rc = gen_packed_pass(m, gc, pp, ids + p.off, o.mm ? o.mm + j0 : nullptr, j0, m->h_page_ptrs.data(), n_seg, j0))) return rc;
+    AHA_HIP_CHECK(hipStreamSynchronize(st));   // the pass page table and the staging buffer are reused by the next pass
+  }
   {
     std::vector<int> all(n);
     for (int j = 0; j < n; ++j) all[j] = j, n_out[j] = 0;
@@ -3164,27 +3172,13 @@ int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_le
   while (!active.empty()) {
     const int R = (int)active.size();
     if (o.spec && o.stats) o.stats->decode_steps += 1, o.stats->rows += (size_t)R;
-    int max_split = 1;
-    double kv_tokens = 0;
+    GenStepRows sr;
     for (int r = 0; r < R; ++r) {
-      const int j = active[r];
-      const int kv_len = (int)(seq_lens[j] + n_out[j]);   // the cache after this step's append
-      const int ns = attn_decode_nsplit(kv_len, g, m->max_nsplit);
-      int32_t* t = gc.h_rowtab + (size_t)r * GEN_ROW_WORDS;
-      t[GEN_ROW_PAGE0] = (int32_t)page0[j];
-      t[GEN_ROW_KVLEN] = kv_len;
-      t[GEN_ROW_NSPLIT] = ns;
-      t[GEN_ROW_CTR] = (int32_t)ctr_acc[r];
-      t[GEN_ROW_POS] = (int32_t)(kv_len - 1 + rope_delta[j]);   // seqlen_offset + rope_delta (qwen3vl/model.rs:1235-1264)
-      t[GEN_ROW_SRC] = src_row[j];
-      t[GEN_ROW_CTRROW] = r;
-      t[7] = 0;
-      if (ns > 1) ctr_acc[r] += (unsigned)L * (unsigned)ns;   // a single split never touches its counter
-      max_split = std::max(max_split, ns);
-      kv_tokens += kv_len;
+      const int j = active[r];   // its cache after this step's append: the prompt and the tokens so far
+      gen_write_row(m, gc, sr, r, page0[j], (int)(seq_lens[j] + n_out[j]), rope_delta[j], ctr_acc[r], src_row[j], r);
     }
     AHA_HIP_CHECK(hipMemcpyAsync(gc.rowtab, gc.h_rowtab, (size_t)R * GEN_ROW_WORDS * 4, hipMemcpyHostToDevice, st));
-    gen_decode_step(m, gc, R, max_split, kv_tokens, gc.tok[cur], gc.tok[cur ^ 1]);
+    gen_decode_step(m, gc, R, sr.max_split, sr.kv_tokens, gc.tok[cur], gc.tok[cur ^ 1]);
     AHA_HIP_CHECK(hipGetLastError());
     if ((rc = gen_finish_step(m, gc, ch, active, gc.tok[cur ^ 1]))) return rc;
     std::vector<int> next;
@@ -3209,12 +3203,12 @@ int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_le
 // generate_generic's stream (common/generate.rs:231-368) for requests that come and go: the engine owns the model's cache (kv_pages pages
 // reserved up front, a free list) and max_running slots.  A slot owns the window [slot * kv_pages, + kv_pages) of the engine's device page
 // table; a request takes ceil((len + max_new) / 64) pages from the free list when it is admitted, writes them into its slot's window, and
-// gives them back when it ends or is cancelled.  A step = the prefill work (one packed pass: whole prompts of requests admitted this step in
-// submission order under max_tokens_per_step, then at most one 64-aligned chunk of a long TEXT prompt, with its cache prefix in the
+// gives them back when it ends or is cancelled.  A step = the prefill work (one gen_packed_pass: whole prompts of requests admitted this
+// step in submission order under max_tokens_per_step, then at most one 64-aligned chunk of a long TEXT prompt, with its cache prefix in the
 // attention: AttnPrefillArgs::seg_kv0) -> the first tokens of the prompts it completes, then one gen_decode_step over every request that
-// had a first token before the step, then its gen_finish_step.  The pieces are model_generate_batch's: a request's bits are those of its
-// prompt's packed pass (the same composition through generate_batch* gives the same bits: the decode rows are row-isolated) -- requests
-// with images, video or audio are prefilled whole, never chunked.
+// had a first token before the step, then its gen_finish_step.  A request's bits are those of its prompt's packed pass (the same
+// composition through generate_batch* gives the same bits: the decode rows are row-isolated) -- requests with images, video or audio are
+// prefilled whole, never chunked.
 // Split counters: slot s owns head_ctr block s (GEN_ROW_CTRROW) and ctr_acc[s], both reset to ctr_base when a slot is taken.  The kernel's
 // "last split" test is prev + 1 == ctr0 + layer * nsplit in 32-bit unsigned arithmetic, so a counter that wraps past 2^32 still meets its
 // target exactly once: a false match would need 2^32 arrivals inside one launch (aha_hip_engine_debug_ctr_base moves the base near the wrap
@@ -3573,7 +3567,7 @@ int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, f
   const aha_model_desc& c = m->desc;
   hipStream_t st = m->stream;
   GenCall& gc = e->gc;
-  const int V = c.vocab_size, g = c.num_attention_heads / c.num_key_value_heads, L = c.num_hidden_layers;
+  const int V = c.vocab_size;
   if (!ev || !n_ev) {
     set_error("engine_step: null events / n_ev");
     return AHA_ERR_INVALID;
@@ -3644,6 +3638,7 @@ int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, f
     std::vector<std::vector<int32_t>> pos3(n_seg);
     std::vector<uint64_t> phys;   // the pass's "logical" pages: every segment's slot pages, back to back
     std::vector<uint32_t> ids;
+    std::vector<const aha_mm_input*> mm(n_seg);
     bool any_kv0 = false;
     for (int j = 0; j < n_seg; ++j) {
       const EngSeg& sg = segs[j];
@@ -3654,31 +3649,16 @@ int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, f
       const std::vector<uint64_t>& pg = e->slot_pages[sg.q->slot];
       phys.insert(phys.end(), pg.begin(), pg.end());
       pos3[j] = sg.q->pos3;
+      mm[j] = sg.q->mm;
       ids.insert(ids.end(), sg.q->ids.begin() + sg.kv0, sg.q->ids.begin() + sg.kv0 + sg.len);
     }
     const PackedPass pp = plan_packed_pass(lens.data(), n_seg, page0.data(), pos3.data(), any_kv0 ? kv0.data() : nullptr);
-    std::vector<VisRequest> vreqs;
-    std::vector<AudRequest> areqs;
-    for (int j = 0; j < n_seg; ++j) {
-      const aha_mm_input* q = segs[j].q->mm;
-      const int r0 = pp.tab[3 * j];
-      if (q && (q->n_images > 0 || q->n_videos > 0)) vreqs.push_back(VisRequest{q, ids.data() + r0, lens[j], r0, j});
-      else if (q && m->audio) areqs.push_back(AudRequest{q, ids.data() + r0, lens[j], r0, j});
-    }
-    // pass page table: the rope kernel's pages, then (chunks) the attention's
-    std::vector<uint64_t> tab(pp.pages.size() + pp.attn_pages.size());
-    for (size_t p = 0; p < pp.pages.size(); ++p) tab[p] = phys[(size_t)pp.pages[p]];
-    for (size_t p = 0; p < pp.attn_pages.size(); ++p) tab[pp.pages.size() + p] = phys[(size_t)pp.attn_pages[p]];
-    AHA_HIP_CHECK(hipMemcpy(gc.pass_pages, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
-    if ((rc = run_packed_pass(m, pp, ids.data(), gc.pass_pages, vreqs, areqs, gc.pass_pages + pp.pages.size()))) return rc;
     // the prompts this pass completes: their last rows -> gc rows 0 .. k-1 (the chunk, if it does not end its prompt, is the last segment)
     int k = n_seg;
     if (chunk.q && (size_t)(chunk.kv0 + chunk.len) < chunk.q->ids.size()) --k;
+    if ((rc = gen_packed_pass(m, gc, pp, ids.data(), mm.data(), 0, phys.data(), k, 0))) return rc;
     for (int j = 0; j < n_seg; ++j) segs[j].q->done += (size_t)segs[j].len;
     if (k > 0) {
-      launch_embed_gather(m->p_x, reinterpret_cast<const uint32_t*>(m->p_pass_tab + pp.o_last), gc.x, k, gc.H, st);
-      gen_head(m, gc, 0, k, gc.tok[0]);
-      AHA_HIP_CHECK(hipGetLastError());
       std::vector<int> seqs(k);
       for (int j = 0; j < k; ++j) {
         seqs[j] = segs[j].q->slot;
@@ -3706,32 +3686,18 @@ int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, f
     if (e->slots[s]->toks.size() < e->slots[s]->max_new) rows.push_back(s);
   if (!rows.empty()) {
     const int R = (int)rows.size();
-    int max_split = 1;
-    double kv_tokens = 0;
+    GenStepRows sr;
     for (int r = 0; r < R; ++r) {
       const int s = rows[r];
-      const EngReq* q = e->slots[s];
-      const int kv_len = (int)(q->ids.size() + e->n_out[s]);   // the cache after this step's append
-      const int ns = attn_decode_nsplit(kv_len, g, m->max_nsplit);
-      int32_t* t = gc.h_rowtab + (size_t)r * GEN_ROW_WORDS;
-      t[GEN_ROW_PAGE0] = (int32_t)((size_t)s * e->kv_pages);
-      t[GEN_ROW_KVLEN] = kv_len;
-      t[GEN_ROW_NSPLIT] = ns;
-      t[GEN_ROW_CTR] = (int32_t)e->ctr_acc[s];
-      t[GEN_ROW_POS] = (int32_t)(kv_len - 1 + q->rope_delta);
-      t[GEN_ROW_SRC] = r;
-      t[GEN_ROW_CTRROW] = s;
-      t[7] = 0;
-      if (ns > 1) e->ctr_acc[s] += (unsigned)L * (unsigned)ns;   // a single split never touches its counter
-      max_split = std::max(max_split, ns);
-      kv_tokens += kv_len;
+      const EngReq* q = e->slots[s];   // its cache after this step's append: the prompt and the tokens so far, in the slot's page window
+      gen_write_row(m, gc, sr, r, (int64_t)((size_t)s * e->kv_pages), (int)(q->ids.size() + e->n_out[s]), q->rope_delta, e->ctr_acc[s], r, s);
       e->h_tok_in[r] = q->toks.back();
       e->row_logits[r] = logits_out ? logits_out + (ne + r) * (size_t)V : nullptr;
       e->row_lp[r] = logprobs_out ? logprobs_out + (ne + r) : nullptr;
     }
     AHA_HIP_CHECK(hipMemcpyAsync(gc.rowtab, gc.h_rowtab, (size_t)R * GEN_ROW_WORDS * 4, hipMemcpyHostToDevice, st));
     AHA_HIP_CHECK(hipMemcpyAsync(e->d_tok_in, e->h_tok_in, (size_t)R * 4, hipMemcpyHostToDevice, st));
-    gen_decode_step(m, gc, R, max_split, kv_tokens, e->d_tok_in, gc.tok[1]);
+    gen_decode_step(m, gc, R, sr.max_split, sr.kv_tokens, e->d_tok_in, gc.tok[1]);
     AHA_HIP_CHECK(hipGetLastError());
     if ((rc = gen_finish_step(m, gc, e->ch, rows, gc.tok[1]))) return rc;
     for (int r = 0; r < R; ++r) {
