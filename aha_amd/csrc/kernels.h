@@ -337,6 +337,22 @@ struct GemvRowsArgs {
   int64_t ldws = 0;    // set by the launcher
 };
 void launch_gemv_rows(const GemvRowsArgs& a, GemvEpi epi, hipStream_t st);
+void launch_gemv_rows_merge(const GemvRowsArgs& a, GemvEpi epi, int nks, hipStream_t st);   // the call's second launch alone (a.ldws set)
+// MXFP8 weight copies (kernels_gemv_rows_fp8.hip, mxfp8.h): a bf16 matrix W (N, K), K % 32 == 0, as
+//   q       (N, K) bytes, row-major: OCP E4M3 (e4m3fn) codes of w / 2^e, e the exponent of the element's block of 32 consecutive k
+//   scales  (N, ceil(K / 128)) u32: word (n, c) holds the E8M0 bytes e + 127 of row n's blocks 4c .. 4c + 3, block 4c + g in bits
+//           8g .. 8g + 7 -- the four lane groups of a column in chunk c of gemv_rows share one dword load; bytes of blocks past K are 127
+// launch_gemv_rows_mxfp8 is launch_gemv_rows with (q, scales) in place of a.W (ignored): bit-identical to launch_gemv_rows on
+// W' = q * 2^e.  launch_mxfp8_quantize writes q, scales and (optional, may be w itself) W'; launch_mxfp8_check ORs 1 into *flag when a
+// weight is non-finite or would round past bf16's range (|w| >= 1.9375 * 2^127).
+struct WQuant {
+  void* q = nullptr;
+  uint32_t* scales = nullptr;
+};
+size_t mxfp8_scale_words(int N, int K);
+void launch_gemv_rows_mxfp8(const GemvRowsArgs& a, const void* q, const uint32_t* scales, GemvEpi epi, hipStream_t st);
+void launch_mxfp8_quantize(const void* w, int N, int K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, hipStream_t st);
+void launch_mxfp8_check(const void* w, int64_t n_elems, int* flag, hipStream_t st);
 void gemv_rows_plan(int N, int K, int* chunks_per_wave, int* k_splits);
 int gemv_rows_num_tiles(int N);
 size_t gemv_rows_ws_floats(int R, int N, int K);

@@ -398,6 +398,11 @@ void launch_gemv_rows(const GemvRowsArgs& a0, GemvEpi epi, hipStream_t st) {
     if (two) hipLaunchKernelGGL((gemv_rows_kernel<1, 2>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((gemv_rows_kernel<1, 1>), grid, dim3(256), 0, st, a);
   }
+  launch_gemv_rows_merge(a, epi, nks, st);
+}
+
+// the second launch of a gemv_rows call: a.ws holds the nks slabs (a.ldws set)
+void launch_gemv_rows_merge(const GemvRowsArgs& a, GemvEpi epi, int nks, hipStream_t st) {
   const int nout = epi == GEMV_SILU_MUL ? a.N / 2 : a.N;
   const dim3 mgrid((unsigned)((nout + 255) / 256), (unsigned)a.R);
   switch (epi) {

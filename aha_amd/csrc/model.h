@@ -37,6 +37,8 @@ struct LayerWeights {
   void* post_norm = nullptr;
   void* q_norm = nullptr;   // (d)
   void* k_norm = nullptr;
+  // MXFP8 copies of the four matrices (aha_hip_model_quantize_weights; null: none): the batched decode matvec streams these
+  WQuant q_wqkv, q_wo, q_wgu, q_wdown;
 };
 
 // device-resident scalars every decode kernel reads (so a step can be enqueued / replayed without host values)
@@ -77,6 +79,11 @@ struct aha_model {
   void* final_norm = nullptr;
   std::vector<aha::LayerWeights> layers;
   std::vector<void*> owned;  // every hipMalloc'd block (weights, scratch), freed on destroy
+  // aha_hip_model_quantize_weights: AHA_WQ_NONE or the format the matrices were quantised with, its flags, lm_head's copy (AHA_WQ_LM_HEAD)
+  int32_t wq_format = 0;
+  uint32_t wq_flags = 0;
+  aha::WQuant q_lm_head;
+  bool fp8_rows = true;      // aha_hip_debug_fp8_rows: false = the bf16 matvec on W' although a copy exists
   // rope constants
   float* d_inv_freq = nullptr;
   int32_t* d_axis_map = nullptr;
@@ -259,6 +266,7 @@ int model_forward_initial(aha_model* m, const uint32_t* ids, size_t n, size_t of
 int model_forward_step(aha_model* m, uint32_t token, size_t offset, float* logits_out, uint32_t* argmax_out);
 int model_decode_greedy(aha_model* m, uint32_t first_token, size_t offset, size_t max_new, uint32_t* out);
 int model_clear_cache(aha_model* m);
+int model_quantize_weights(aha_model* m, int32_t format, uint32_t flags);
 int model_last_logits(aha_model* m, float* logits_out);
 int model_sample_candidates(aha_model* m, const uint32_t* ctx, size_t n_ctx, float repeat_penalty, float temperature, int k,
                             float* vals_out, uint32_t* idx_out, float* max_out, float* sumexp_out);

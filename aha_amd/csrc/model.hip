@@ -5,6 +5,7 @@
 // The KV cache is paged (64-token pages, K / V blocks fragment-major, see common.h) and must be indistinguishable from
 // the reference's Tensor::cat growth (modules.rs:558-566).
 #include "model.h"
+#include "mxfp8.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -542,6 +543,108 @@ int model_clear_cache(aha_model* m) {
   m->cache_len = 0;
   m->rope_delta = 0;
   m->rope_delta_valid = false;
+  return AHA_OK;
+}
+
+// aha_hip_model_quantize_weights (include/aha_hip.h): every check first, then every allocation, then the matrices one by one -- W becomes
+// W' in place (the quantiser reads an element before it writes it), its (q, scales) copy lands in the matrix's slot.
+int model_quantize_weights(aha_model* m, int32_t format, uint32_t flags) {
+  const aha_model_desc& c = m->desc;
+  if (format != AHA_WQ_MXFP8_E4M3) {
+    set_error("quantize_weights: unknown format " + std::to_string(format) + " (AHA_WQ_MXFP8_E4M3 = 1)");
+    return AHA_ERR_INVALID;
+  }
+  if (flags & ~(uint32_t)AHA_WQ_LM_HEAD) {
+    set_error("quantize_weights: unknown flag bits " + std::to_string(flags & ~(uint32_t)AHA_WQ_LM_HEAD) + " (AHA_WQ_LM_HEAD = 1)");
+    return AHA_ERR_INVALID;
+  }
+  if (m->engine) {
+    set_error("quantize_weights: the model has an engine (aha_hip_engine_destroy first)");
+    return AHA_ERR_STATE;
+  }
+  if (m->wq_format != AHA_WQ_NONE) {
+    if (m->wq_format == format && m->wq_flags == flags) return AHA_OK;
+    set_error("quantize_weights: the model is already quantised with format " + std::to_string(m->wq_format) + ", flags " +
+              std::to_string(m->wq_flags));
+    return AHA_ERR_STATE;
+  }
+  if (m->cache_len != 0) {
+    set_error("quantize_weights: the cache holds " + std::to_string(m->cache_len) + " tokens (aha_hip_clear_cache first)");
+    return AHA_ERR_STATE;
+  }
+  if (m->tp_size > 1 || m->cp_size > 1) {
+    set_error("quantize_weights: tensor- and context-parallel models are not supported");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  if ((c.arch != AHA_ARCH_QWEN3 && c.arch != AHA_ARCH_QWEN3VL && c.arch != AHA_ARCH_QWEN3ASR) || c.head_dim != 128) {
+    set_error("quantize_weights: Qwen3, Qwen3-VL and Qwen3-ASR with head_dim 128 only (the models of generate_batch)");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  struct Mat { std::string name; void* w; int N, K; WQuant* slot; };
+  std::vector<Mat> mats;
+  const int H = c.hidden_size, I = c.intermediate_size, nq = c.num_attention_heads * 128, nkv = c.num_key_value_heads * 128;
+  for (int li = 0; li < c.num_hidden_layers; ++li) {
+    LayerWeights& L = m->layers[li];
+    const std::string p = "layers." + std::to_string(li) + ".";
+    mats.push_back({p + "self_attn.q_proj/k_proj/v_proj.weight", L.wqkv, nq + 2 * nkv, H, &L.q_wqkv});
+    mats.push_back({p + "self_attn.o_proj.weight", L.wo, H, nq, &L.q_wo});
+    mats.push_back({p + "mlp.gate_proj/up_proj.weight", L.wgu, 2 * I, H, &L.q_wgu});
+    mats.push_back({p + "mlp.down_proj.weight", L.wdown, H, I, &L.q_wdown});
+  }
+  if (flags & AHA_WQ_LM_HEAD)
+    mats.push_back({c.tie_word_embeddings ? "embed_tokens.weight (tied lm_head)" : "lm_head.weight", m->lm_head, c.vocab_size, H, &m->q_lm_head});
+  for (const Mat& t : mats)
+    if (t.K % MX_BLOCK) {
+      set_error("quantize_weights: " + t.name + " has K = " + std::to_string(t.K) + ", not a multiple of 32 (the MXFP8 block)");
+      return AHA_ERR_UNSUPPORTED;
+    }
+  AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
+  hipStream_t st = m->stream;
+  {   // every matrix finite (and inside the format's range) before any is touched
+    int* d_flag = nullptr;
+    std::vector<int> h_flag(mats.size(), 0);
+    AHA_HIP_CHECK(hipMalloc((void**)&d_flag, mats.size() * sizeof(int)));
+    hipError_t e = hipMemsetAsync(d_flag, 0, mats.size() * sizeof(int), st);
+    for (size_t i = 0; i < mats.size() && e == hipSuccess; ++i) launch_mxfp8_check(mats[i].w, (int64_t)mats[i].N * mats[i].K, d_flag + i, st);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h_flag.data(), d_flag, mats.size() * sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    hipFree(d_flag);
+    AHA_HIP_CHECK(e);
+    for (size_t i = 0; i < mats.size(); ++i)
+      if (h_flag[i]) {
+        set_error("quantize_weights: " + mats[i].name + " holds a weight that is not finite (or is 1.9375 * 2^127 or more in magnitude); no matrix was modified");
+        return AHA_ERR_INVALID;
+      }
+  }
+  std::vector<void*> got;
+  std::vector<WQuant> wq(mats.size());
+  for (size_t i = 0; i < mats.size(); ++i) {
+    const size_t bytes[2] = {(size_t)mats[i].N * mats[i].K, mxfp8_scale_words(mats[i].N, mats[i].K) * 4};
+    for (int k = 0; k < 2; ++k) {
+      void* p = nullptr;
+      const hipError_t e = hipMalloc(&p, bytes[k]);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (void* q : got) hipFree(q);
+        set_error("quantize_weights: hipMalloc of " + std::to_string(bytes[k]) + " bytes for the copy of " + mats[i].name + " failed: " +
+                  hipGetErrorString(e) + "; the model is unchanged");
+        return e == hipErrorOutOfMemory ? AHA_ERR_OOM : AHA_ERR_HIP;
+      }
+      got.push_back(p);
+      if (k == 0) wq[i].q = p;
+      else wq[i].scales = (uint32_t*)p;
+    }
+  }
+  for (size_t i = 0; i < mats.size(); ++i) launch_mxfp8_quantize(mats[i].w, mats[i].N, mats[i].K, wq[i].q, wq[i].scales, mats[i].w, st);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  for (void* p : got) m->owned.push_back(p);   // freed with the model whatever happened
+  AHA_HIP_CHECK(e);
+  for (size_t i = 0; i < mats.size(); ++i) *mats[i].slot = wq[i];
+  m->wq_format = format;
+  m->wq_flags = flags;
+  m->have_logits = false;
   return AHA_OK;
 }
 
@@ -2326,9 +2429,11 @@ struct DevBufs {   // per-call device / pinned scratch, freed after the stream h
 constexpr int GEN_ROW_GROUP = 32;   // rows of one gemv_rows launch: larger batches stream the weights once per group
 
 // y[rows] = epi(x[rows] . W^T) in groups of GEN_ROW_GROUP rows.  For GEMV_LOGITS, y_f32 / blk partials are (rows, ldf) / (rows, tiles).
-static void gemv_rows_groups(aha_model* m, GemvRowsArgs g, GemvEpi epi, int rows, float* ws) {
+// wq: the MXFP8 copy of g.W (model_quantize_weights), streamed in its place when it exists -- the same bits at 1 + 1/32 bytes per weight.
+static void gemv_rows_groups(aha_model* m, GemvRowsArgs g, GemvEpi epi, int rows, float* ws, const WQuant* wq = nullptr) {
   const int tiles = gemv_rows_num_tiles(g.N);
-  const double wbytes = (double)g.N * g.K * 2;
+  const bool fp8 = wq && wq->q && m->fp8_rows;
+  const double wbytes = (double)g.N * g.K * (fp8 ? 1.0 + 1.0 / 32 : 2.0);
   for (int r0 = 0; r0 < rows; r0 += GEN_ROW_GROUP) {
     GemvRowsArgs a = g;
     a.R = std::min(GEN_ROW_GROUP, rows - r0);
@@ -2338,8 +2443,9 @@ static void gemv_rows_groups(aha_model* m, GemvRowsArgs g, GemvEpi epi, int rows
     if (g.y_f32) a.y_f32 = g.y_f32 + (int64_t)r0 * g.ldf;
     if (g.blk_max) a.blk_max = g.blk_max + (int64_t)r0 * tiles, a.blk_idx = g.blk_idx + (int64_t)r0 * tiles;
     a.ws = ws;
-    ProfScope ps(m, "gemv_rows", wbytes + (double)a.R * (g.K + g.N) * 2, 2.0 * a.R * g.N * g.K);
-    launch_gemv_rows(a, epi, m->stream);
+    ProfScope ps(m, fp8 ? "gemv_rows_fp8" : "gemv_rows", wbytes + (double)a.R * (g.K + g.N) * 2, 2.0 * a.R * g.N * g.K);
+    if (fp8) launch_gemv_rows_mxfp8(a, wq->q, wq->scales, epi, m->stream);
+    else launch_gemv_rows(a, epi, m->stream);
   }
 }
 
@@ -2397,7 +2503,7 @@ static void gen_head(aha_model* m, GenCall& gc, int row0, int rows, uint32_t* to
   g.W = m->lm_head; g.x = (const bf16_t*)gc.h + (int64_t)row0 * H; g.ldx = H; g.N = gc.V; g.K = H;
   g.y_f32 = gc.logits + (int64_t)row0 * gc.V; g.ldf = gc.V;
   g.blk_max = gc.blk_max + (int64_t)row0 * tiles; g.blk_idx = gc.blk_idx + (int64_t)row0 * tiles;
-  gemv_rows_groups(m, g, GEMV_LOGITS, rows, gc.ws);
+  gemv_rows_groups(m, g, GEMV_LOGITS, rows, gc.ws, &m->q_lm_head);
   ProfScope ps(m, "argmax", 0, 0);
   launch_argmax_rows(gc.blk_max + (int64_t)row0 * tiles, gc.blk_idx + (int64_t)row0 * tiles, tiles, rows, tok_out + row0, m->stream);
 }
@@ -2868,7 +2974,7 @@ static void gen_decode_step(aha_model* m, GenCall& gc, int R, int max_split, dou
       }
       GemvRowsArgs a{};
       a.W = Lw.wqkv; a.x = gc.h; a.ldx = H; a.y = gc.qkv; a.ldy = nq + 2 * nkv; a.N = nq + 2 * nkv; a.K = H;
-      gemv_rows_groups(m, a, GEMV_STORE, R, gc.ws);
+      gemv_rows_groups(m, a, GEMV_STORE, R, gc.ws, &Lw.q_wqkv);
     }
     {   // q/k norm + rope + KV append + attention of every row over its own pages (modules.rs:544-574, 757-813)
       AttnDecodeBatchArgs b{};
@@ -2886,7 +2992,7 @@ static void gen_decode_step(aha_model* m, GenCall& gc, int R, int max_split, dou
     {   // x = x + attn Wo^T                                    (modules.rs:577, qwen3/model.rs:81)
       GemvRowsArgs a{};
       a.W = Lw.wo; a.x = gc.attn; a.ldx = nq; a.residual = gc.x; a.y = gc.x; a.ldy = H; a.N = H; a.K = nq;
-      gemv_rows_groups(m, a, GEMV_RESIDUAL, R, gc.ws);
+      gemv_rows_groups(m, a, GEMV_RESIDUAL, R, gc.ws, &Lw.q_wo);
     }
     {   // act = silu(h Wg^T) * (h Wu^T), h = RMSNorm(x)        (qwen3/model.rs:83, modules.rs:81-84)
       {
@@ -2895,12 +3001,12 @@ static void gen_decode_step(aha_model* m, GenCall& gc, int R, int max_split, dou
       }
       GemvRowsArgs a{};
       a.W = Lw.wgu; a.x = gc.h; a.ldx = H; a.y = gc.act; a.ldy = I; a.N = 2 * I; a.K = H;
-      gemv_rows_groups(m, a, GEMV_SILU_MUL, R, gc.ws);
+      gemv_rows_groups(m, a, GEMV_SILU_MUL, R, gc.ws, &Lw.q_wgu);
     }
     {   // x = x + act Wd^T                                     (modules.rs:85, qwen3/model.rs:86)
       GemvRowsArgs a{};
       a.W = Lw.wdown; a.x = gc.act; a.ldx = I; a.residual = gc.x; a.y = gc.x; a.ldy = H; a.N = H; a.K = I;
-      gemv_rows_groups(m, a, GEMV_RESIDUAL, R, gc.ws);
+      gemv_rows_groups(m, a, GEMV_RESIDUAL, R, gc.ws, &Lw.q_wdown);
     }
   }
   gen_head(m, gc, 0, R, tok_out);

@@ -595,6 +595,24 @@ class HipInferenceModel:
     def debug_steps_executed(self) -> int:
         return int(lib().aha_hip_debug_steps_executed(self.handle))
 
+    def quantize_weights(self, fmt: str = "mxfp8", lm_head: bool = False) -> None:
+        """Quantise the layer matrices (and lm_head with lm_head=True) to MXFP8 in place (aha_hip_model_quantize_weights): the batched decode
+        then streams the FP8 copies; every other path reads the dequantised bf16 matrices.  aha_amd/quant.py is the reference quantiser."""
+        if fmt != "mxfp8":
+            raise ValueError(f"unknown weight format {fmt!r} (\"mxfp8\")")
+        check(lib().aha_hip_model_quantize_weights(self.handle, _lib.AHA_WQ_MXFP8_E4M3, _lib.AHA_WQ_LM_HEAD if lm_head else 0))
+
+    @property
+    def weight_format(self):
+        """None, or ("mxfp8", lm_head) as quantize_weights was called."""
+        f, fl = C.c_int32(), C.c_uint32()
+        check(lib().aha_hip_model_weight_format(self.handle, C.byref(f), C.byref(fl)))
+        return None if f.value == _lib.AHA_WQ_NONE else ("mxfp8", bool(fl.value & _lib.AHA_WQ_LM_HEAD))
+
+    def debug_fp8_rows(self, on: bool = True) -> None:
+        """Test hook: False makes a quantised model's batched decode run the bf16 matvec on the dequantised matrices (the same bits)."""
+        check(lib().aha_hip_debug_fp8_rows(self.handle, int(on)))
+
     def set_profiling(self, on: bool):
         check(lib().aha_hip_set_profiling(self.handle, int(on)))
 

@@ -301,6 +301,37 @@ def gemv_rows(W: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, resi
     return (logits, am.long()) if epi == GEMV_ROWS_LOGITS else y
 
 
+def quantize_mxfp8(W: torch.Tensor):
+    """The library's MXFP8 quantiser (aha_hip_quantize_mxfp8) on a GPU bf16 matrix (N, K), K % 32 == 0 -> (q (N, K) uint8, scales
+    (N, K / 32) uint8, W' (N, K) bf16) on the GPU, scales in the reference's order (aha_amd/quant.py quantize_mxfp8: the same bytes)."""
+    from . import quant
+    _chk(W)
+    N, K = W.shape
+    q = torch.empty(N, K, dtype=torch.uint8, device=W.device)
+    words = torch.empty(N, (K + 127) // 128, dtype=torch.int32, device=W.device)
+    wr = torch.empty_like(W)
+    check(lib().aha_hip_quantize_mxfp8(_ptr(W), N, K, _ptr(q), _ptr(words), _ptr(wr), _stream()))
+    return q, quant.scales_from_kernel(words, K).to(W.device), wr
+
+
+def gemv_rows_mxfp8(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, residual: Optional[torch.Tensor] = None):
+    """gemv_rows from the MXFP8 copy of W: q (N, K) uint8, scales (N, K / 32) uint8 in the reference's order (converted to the kernel's
+    words here).  Every output bit equals gemv_rows(W', x, epi, residual) for W' = dequantize_mxfp8(q, scales)."""
+    from . import quant
+    _chk(q, x, residual)
+    N, K = q.shape
+    R = x.shape[0]
+    words = quant.scales_to_kernel(scales).to(x.device)
+    y = logits = am = None
+    if epi == GEMV_ROWS_LOGITS:
+        logits = torch.empty(R, N, dtype=torch.float32, device=x.device)
+        am = torch.empty(R, dtype=torch.int32, device=x.device)
+    else:
+        y = torch.empty(R, N // 2 if epi == GEMV_ROWS_SILU_MUL else N, dtype=torch.bfloat16, device=x.device)
+    check(lib().aha_hip_gemv_rows_mxfp8(_ptr(q), _ptr(words), _ptr(x), _ptr(y), R, N, K, epi, _ptr(residual), _ptr(logits), _ptr(am), _stream()))
+    return (logits, am.long()) if epi == GEMV_ROWS_LOGITS else y
+
+
 def attn_decode_batch(qkv: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: torch.Tensor, rope: torch.Tensor, page_ptrs: torch.Tensor,
                       page0, kv_len, nh: int, kvh: int, eps: float, scale: float) -> torch.Tensor:
     """Fused decode attention of R sequences in one launch: qkv (R, (nh+2kvh)*128) bf16, rope (R, 128) f32, page_ptrs (P,) int64 device

@@ -685,6 +685,27 @@ int aha_hip_kv_import(aha_model* m, const void* in_dev, size_t in_bytes, int32_t
  * wait for it.  Lets a 1-GPU box exercise the RCCL wiring with a communicator of size 1. */
 int aha_hip_debug_allreduce(aha_model* m, void* buf_f32_dev, size_t count);
 
+/* ---- quantised weight copies for the batched decode ------------------------------------------------------------- */
+/* aha_hip_model_quantize_weights: quantise the layer matrices (wqkv, wo, wgu, wdown) of a created model to MXFP8 (see
+ * aha_hip_quantize_mxfp8), in place: each bf16 matrix W is overwritten with W' = dequantised W and its (q, scales) copy is kept beside it.
+ * The batched decode matvec (every aha_hip_generate_batch* entry and the engine) then streams q and the scales, 1.03125 bytes per weight
+ * instead of 2, with the bits it would compute from W'; prefill and every other path go on reading the bf16 W'.  flags: 0, or
+ * AHA_WQ_LM_HEAD to quantise lm_head too (with tied embeddings: the embedding table).  Costs 0.516 x the quantised matrices in memory.
+ * AHA_ERR_INVALID: a null model, an unknown format or flag, or a weight that is not finite (or >= 1.9375 * 2^127 in magnitude), naming
+ * the tensor -- every matrix is checked before any is modified.  AHA_ERR_STATE: the cache is not empty, the model has an engine, or it
+ * was quantised with other arguments (the same arguments again: AHA_OK, nothing done).  AHA_ERR_UNSUPPORTED, naming the cause: a tensor-
+ * or context-parallel model, a matrix whose K is not a multiple of 32, a model outside aha_hip_generate_batch's set.  AHA_ERR_OOM: the
+ * copies cannot be had; the model is as it was.  Reads no environment variable. */
+#define AHA_WQ_NONE 0
+#define AHA_WQ_MXFP8_E4M3 1
+#define AHA_WQ_LM_HEAD 1u
+int aha_hip_model_quantize_weights(aha_model* m, int32_t format, uint32_t flags);
+/* *format = AHA_WQ_NONE or the format the model was quantised with, *flags its flags (either pointer may be NULL). */
+int aha_hip_model_weight_format(const aha_model* m, int32_t* format, uint32_t* flags);
+/* Test hook: on = 0 makes a quantised model's batched decode run the bf16 matvec on W' instead of the FP8 one (the same bits); on = 1
+ * (the default) restores it. */
+int aha_hip_debug_fp8_rows(aha_model* m, int on);
+
 /* ---- introspection used by bench.py / tests ------------------------------------------------------------------ */
 size_t aha_hip_cache_len(const aha_model* m);
 /* Decode steps the device ran in the last aha_hip_decode_greedy call, including the ones queued past a stop token (at most
@@ -783,6 +804,17 @@ int aha_hip_attn_decode(const void* q, const void* k, const void* v, void* o, in
  * (R, N) f32 and argmax_out (R) u32 (device), the first maximal index.  Each output row depends only on its own input row. */
 int aha_hip_gemv_rows(const void* W, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi, const void* residual,
                       float* logits, uint32_t* argmax_out, void* stream);
+/* MXFP8 weight copies, op level.  A bf16 matrix W (N, K), K % 32 == 0, as OCP microscaling FP8: every row in blocks of 32 consecutive k;
+ * per block e = the smallest integer in [-117, 120] with max |w| <= 448 * 2^e (an all-zero block: -117), the scale byte e + 127 (E8M0)
+ * and q = e4m3fn(w / 2^e), round to nearest even, one byte per element; W' = q * 2^e is exact in bf16.
+ * aha_hip_quantize_mxfp8: q_out (N, K) bytes; scales_out (N, ceil(K / 128)) u32, word (n, c) = the scale bytes of row n's blocks
+ * 4c .. 4c + 3, block 4c + g in bits 8g .. 8g + 7 (bytes of blocks past K: 127); w_roundtrip_out (N, K) bf16 = W', may be NULL or W
+ * itself.  The weights must be finite and below 1.9375 * 2^127 in magnitude (not checked here).
+ * aha_hip_gemv_rows_mxfp8: aha_hip_gemv_rows with (q, scales) in place of W, K % 32 == 0: every output bit equals
+ * aha_hip_gemv_rows on W'. */
+int aha_hip_quantize_mxfp8(const void* W, int32_t N, int32_t K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, void* stream);
+int aha_hip_gemv_rows_mxfp8(const void* q, const uint32_t* scales, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi,
+                            const void* residual, float* logits, uint32_t* argmax_out, void* stream);
 /* aha_hip_attn_decode_batch: the fused decode attention block (QKNormAttention::forward, modules.rs:538-577, without o_proj) of `rows`
  * sequences in one launch.  qkv (rows, (nh + 2kvh) * 128) bf16; q_norm_w / k_norm_w (128) bf16; rope (rows, 128) f32 cos | sin, bf16
  * values; page_ptrs: device table of page addresses (pages of kvh K blocks then kvh V blocks, 16 KB each); row r's pages are
