@@ -353,6 +353,13 @@ size_t mxfp8_scale_words(int N, int K);
 void launch_gemv_rows_mxfp8(const GemvRowsArgs& a, const void* q, const uint32_t* scales, GemvEpi epi, hipStream_t st);
 void launch_mxfp8_quantize(const void* w, int N, int K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, hipStream_t st);
 void launch_mxfp8_check(const void* w, int64_t n_elems, int* flag, hipStream_t st);
+// Batch-1 matvec from the same copies (kernels_gemv_fp8.hip): launch_gemv with (q, scales) in place of g.W / g.W2 (ignored; GEMV_SILU_MUL
+// reads the fused 16-row gate / up block layout, g.N = I), g.cached and g.trace ignored, no GEMV_PARTIAL_F32.  Bit-identical to launch_gemv
+// on W' = q * 2^e.  GEMV_LOGITS writes gemv_mxfp8_num_tiles(N, K) (max, index) partials -- its own plan's grid, not gemv_num_tiles'.
+void launch_gemv_mxfp8(const GemvArgs& g, const void* q, const uint32_t* scales, GemvEpi epi, hipStream_t st);
+int gemv_mxfp8_num_tiles(int N, int K);
+bool gemv_mxfp8_by_plan(int N, int K, GemvEpi epi);   // does the model's single-sequence step read this matrix (N rows: 2I for gate+up) from its copy?
+void debug_plan_gemv_mxfp8(int N, int K, GemvEpi epi, bool has_norm, int* out5);   // host only: {R, U, grid, FAST, PRO}; N = output rows
 void gemv_rows_plan(int N, int K, int* chunks_per_wave, int* k_splits);
 int gemv_rows_num_tiles(int N);
 size_t gemv_rows_ws_floats(int R, int N, int K);

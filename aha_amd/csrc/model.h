@@ -84,6 +84,8 @@ struct aha_model {
   uint32_t wq_flags = 0;
   aha::WQuant q_lm_head;
   bool fp8_rows = true;      // aha_hip_debug_fp8_rows: false = the bf16 matvec on W' although a copy exists
+  int fp8_single = 1;        // aha_hip_debug_fp8_single, the single-sequence matvec (enqueue_decode_step, enqueue_lm_head): 0 = bf16 on W',
+                             // 1 = the FP8 kernel where the plan takes the shape (gemv_mxfp8_by_plan), 2 = wherever a copy exists
   // rope constants
   float* d_inv_freq = nullptr;
   int32_t* d_axis_map = nullptr;

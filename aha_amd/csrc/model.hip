@@ -838,7 +838,7 @@ int model_create(aha_ctx* ctx, const aha_model_desc* desc, const aha_tensor_view
   m->d_partial = (float*)p;
   if ((rc = dev_alloc(m, (size_t)c.vocab_size * 4, &p))) return fail(rc);
   m->d_logits = (float*)p;
-  const int nt = std::max(gemv_num_tiles(c.vocab_size, H), 512);
+  const int nt = std::max(std::max(gemv_num_tiles(c.vocab_size, H), gemv_mxfp8_num_tiles(c.vocab_size, H)), 512);
   if ((rc = dev_alloc(m, (size_t)nt * 4, &p))) return fail(rc);
   m->d_blk_max = (float*)p;
   if ((rc = dev_alloc(m, (size_t)nt * 4, &p))) return fail(rc);
@@ -950,6 +950,28 @@ static int push_state(aha_model* m, uint32_t token, const int64_t pos[3], size_t
   return AHA_OK;
 }
 
+static void gemv_row_parallel(aha_model* m, GemvArgs g);
+
+// One batch-1 matvec of the single-sequence path (g.N output rows: I for GEMV_SILU_MUL).  A matrix with an MXFP8 copy is read from it
+// where the plan takes the shape (gemv_mxfp8_by_plan: the matrices for which FP8 measured faster; the two kernels give the same bits, so
+// the choice is invisible in the output; aha_hip_debug_fp8_single overrides it either way) -- sharded models never have a copy.
+// Profile class gemv_fp8 at 1.03125 bytes per weight, gemv at 2; act_bytes: the activation traffic.
+static bool fp8_single(const aha_model* m, const WQuant& wq, int rows, int K, GemvEpi epi) {
+  return wq.q != nullptr && m->tp_size <= 1 && (m->fp8_single == 2 || (m->fp8_single == 1 && gemv_mxfp8_by_plan(rows, K, epi)));
+}
+static void decode_gemv(aha_model* m, const GemvArgs& g, GemvEpi epi, const WQuant& wq, double act_bytes) {
+  const double weights = (epi == GEMV_SILU_MUL ? 2.0 : 1.0) * g.N * g.K;
+  const bool fp8 = fp8_single(m, wq, (epi == GEMV_SILU_MUL ? 2 : 1) * g.N, g.K, epi);
+  ProfScope ps(m, fp8 ? "gemv_fp8" : "gemv", weights * (fp8 ? 1.03125 : 2.0) + act_bytes, 2.0 * weights);
+  if (fp8) launch_gemv_mxfp8(g, wq.q, wq.scales, epi, m->stream);
+  else if (epi == GEMV_RESIDUAL) gemv_row_parallel(m, g);
+  else launch_gemv(g, epi, m->stream);
+}
+// (max, index) partials the lm_head matvec of enqueue_lm_head writes: the grid of the kernel that runs
+static int lm_head_partials(const aha_model* m) {
+  return fp8_single(m, m->q_lm_head, m->lm_rows, m->desc.hidden_size, GEMV_LOGITS) ? gemv_mxfp8_num_tiles(m->lm_rows, m->desc.hidden_size) : gemv_num_tiles(m->lm_rows, m->desc.hidden_size);
+}
+
 // final RMSNorm (qwen3/model.rs:186) fused into the lm_head matvec of the LAST position only (model.rs:187,142),
 // f32 logits + argmax partials -> d_state->next_token
 static void enqueue_lm_head(aha_model* m, const void* x_last, bool argmax = true) {
@@ -965,13 +987,10 @@ static void enqueue_lm_head(aha_model* m, const void* x_last, bool argmax = true
   g.blk_max = m->d_blk_max;
   g.blk_idx = m->d_blk_idx;
   g.h_out = m->d_hlast;
-  {
-    ProfScope ps(m, "gemv", (double)m->lm_rows * c.hidden_size * 2 + c.hidden_size * 2 + m->lm_rows * 4.0, 2.0 * m->lm_rows * c.hidden_size);
-    launch_gemv(g, GEMV_LOGITS, m->stream);
-  }
+  decode_gemv(m, g, GEMV_LOGITS, m->q_lm_head, c.hidden_size * 2 + m->lm_rows * 4.0);
   if (!argmax) return;   // the caller reduces the partials itself (step_tail_kernel)
   ProfScope ps(m, "argmax", 0, 0);
-  const int ntiles = gemv_num_tiles(m->lm_rows, c.hidden_size);
+  const int ntiles = lm_head_partials(m);
   if (m->lm_rows == c.vocab_size) {
     launch_argmax_partials(m->d_blk_max, m->d_blk_idx, ntiles, &m->d_state->next_token, m->stream);
     return;
@@ -1487,7 +1506,8 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const float* __restrict_
   }
 }
 
-// AHA_GEMV_TRACE=1: in-kernel timeline of the decode matvecs (launch-per-op path), dumped by fetch_outputs
+// AHA_GEMV_TRACE=1: in-kernel timeline of the decode matvecs (launch-per-op path), dumped by fetch_outputs.  The bf16 kernel only:
+// gemv_mxfp8_kernel has no trace stamps, so a launch that decode_gemv sends to it leaves its slot as it was (gemv_trace_dump says so).
 static unsigned long long* gemv_trace_slot(aha_model* m, int launch_idx) {
   static const char* e = getenv("AHA_GEMV_TRACE");
   if (!e || !atoi(e)) return nullptr;
@@ -1505,6 +1525,9 @@ static void gemv_trace_dump(aha_model* m) {
   std::vector<unsigned long long> t((size_t)nl * 18);
   if (hipMemcpy(t.data(), m->d_gemv_trace, t.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
   static const char* names[4] = {"qkv", "o_proj", "gate_up", "down"};
+  if (m->fp8_single && L > 0 && m->layers[0].q_wqkv.q)
+    fprintf(stderr, "[gemv trace] the model has MXFP8 copies: launches of gemv_mxfp8_kernel are not traced, their slots are stale or empty "
+                    "(aha_hip_debug_fp8_single(m, 0) traces the bf16 kernel on the same weights)\n");
   for (int k = 0; k < 4; ++k) {
     double d[3][5] = {}, gap = 0, span = 0;
     int n = 0;
@@ -1554,8 +1577,7 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = 
       GemvArgs g{};
       g.W = L.wqkv; g.x = m->d_x; g.norm_w = L.in_norm; g.eps = c.rms_norm_eps; g.y = m->d_qkv; g.N = nq + 2 * nkv; g.K = H;
       g.trace = gemv_trace_slot(m, li * 4 + 0);
-      ProfScope ps(m, "gemv", (double)g.N * g.K * 2 + g.K * 4.0 + g.N * 2.0, 2.0 * g.N * g.K);
-      launch_gemv(g, GEMV_STORE, st);
+      decode_gemv(m, g, GEMV_STORE, L.q_wqkv, g.K * 4.0 + g.N * 2.0);
     }
     if (m->decode_fused) {
       // q/k norm + rope + KV append + attention over the paged cache (modules.rs:544-574, 757-813), then
@@ -1586,13 +1608,11 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = 
       g.W = L.wo; g.x = m->d_attn; g.residual = m->d_x; g.y = m->d_x; g.N = H; g.K = nq;
       g.trace = gemv_trace_slot(m, li * 4 + 1);
       const double attn_bytes = (double)kv_len_after * 2 * nkv * 2 + (nq + 2 * nkv) * 2.0 + nsplit * nq * 4.0;
-      const double gemv_bytes = (double)g.N * g.K * 2 + g.K * 2.0 + g.N * 4.0;
       {
         ProfScope ps(m, "attn_decode", attn_bytes, 4.0 * kv_len_after * nq);
         launch_attn_decode_fused(a, st);
       }
-      ProfScope ps(m, "gemv", gemv_bytes, 2.0 * g.N * g.K);
-      gemv_row_parallel(m, g);
+      decode_gemv(m, g, GEMV_RESIDUAL, L.q_wo, g.K * 2.0 + g.N * 4.0);
     } else {  // three-launch variant (A/B knob AHA_DECODE_FUSED=0)
       {  // q/k norm + rope + append                            (modules.rs:544-566)
         RopeArgs r{};
@@ -1613,23 +1633,20 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = 
       {  // x = x + attn Wo^T                                    (modules.rs:577, qwen3/model.rs:81)
         GemvArgs g{};
         g.W = L.wo; g.x = m->d_attn; g.residual = m->d_x; g.y = m->d_x; g.N = H; g.K = nq;
-        ProfScope ps(m, "gemv", (double)g.N * g.K * 2 + g.K * 2.0 + g.N * 4.0, 2.0 * g.N * g.K);
-        gemv_row_parallel(m, g);
+        decode_gemv(m, g, GEMV_RESIDUAL, L.q_wo, g.K * 2.0 + g.N * 4.0);
       }
     }
     {  // act = silu(h Wg^T) * (h Wu^T), h = RMSNorm(x)        (qwen3/model.rs:83, modules.rs:81-84)
       GemvArgs g{};
       g.W = L.wgu; g.W2 = nullptr; g.x = m->d_x; g.norm_w = L.post_norm; g.eps = c.rms_norm_eps; g.y = m->d_act; g.N = I; g.K = H;
       g.trace = gemv_trace_slot(m, li * 4 + 2);
-      ProfScope ps(m, "gemv", (double)2 * I * H * 2 + H * 4.0 + I * 2.0, 4.0 * I * H);
-      launch_gemv(g, GEMV_SILU_MUL, st);
+      decode_gemv(m, g, GEMV_SILU_MUL, L.q_wgu, H * 4.0 + I * 2.0);
     }
     {  // x = x + act Wd^T                                     (modules.rs:85, qwen3/model.rs:86)
       GemvArgs g{};
       g.W = L.wdown; g.x = m->d_act; g.residual = m->d_x; g.y = m->d_x; g.N = H; g.K = I;
       g.trace = gemv_trace_slot(m, li * 4 + 3);
-      ProfScope ps(m, "gemv", (double)g.N * g.K * 2 + g.K * 2.0 + g.N * 4.0, 2.0 * g.N * g.K);
-      gemv_row_parallel(m, g);
+      decode_gemv(m, g, GEMV_RESIDUAL, L.q_wdown, g.K * 2.0 + g.N * 4.0);
     }
   }
   if (!tail) {
@@ -1638,7 +1655,7 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = 
   }
   enqueue_lm_head(m, m->d_x, false);
   ProfScope ps(m, "argmax", H * 4.0, 0);
-  hipLaunchKernelGGL(step_tail_kernel, dim3(1), dim3(256), 0, st, m->d_blk_max, m->d_blk_idx, gemv_num_tiles(m->lm_rows, H), m->d_state,
+  hipLaunchKernelGGL(step_tail_kernel, dim3(1), dim3(256), 0, st, m->d_blk_max, m->d_blk_idx, lm_head_partials(m), m->d_state,
                      (const bf16_t*)m->embed, (bf16_t*)m->d_x, H, m->d_inv_freq, m->d_axis_map, m->d_rope, m->d_token_log, m->h_ring_dev,
                      m->h_done_dev);
 }

@@ -613,6 +613,13 @@ class HipInferenceModel:
         """Test hook: False makes a quantised model's batched decode run the bf16 matvec on the dequantised matrices (the same bits)."""
         check(lib().aha_hip_debug_fp8_rows(self.handle, int(on)))
 
+    def debug_fp8_single(self, on=True) -> None:
+        """Test hook: the switch of the single-sequence decode matvec (forward_step, decode_greedy, the generate_generic loops, the last-row
+        lm_head of forward_initial).  True / 1 (the default): the FP8 kernel on the matrices whose shape the plan takes (those it measured
+        faster on); 2: on every matrix with a copy; False / 0: the bf16 kernel on W'.  The same bits in all three.  Profile class of the FP8
+        launches: "gemv_fp8"."""
+        check(lib().aha_hip_debug_fp8_single(self.handle, int(on)))
+
     def set_profiling(self, on: bool):
         check(lib().aha_hip_set_profiling(self.handle, int(on)))
 

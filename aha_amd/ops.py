@@ -332,6 +332,57 @@ def gemv_rows_mxfp8(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, epi:
     return (logits, am.long()) if epi == GEMV_ROWS_LOGITS else y
 
 
+def _gemv_epi_outputs(N: int, epi: int, device, out: Optional[torch.Tensor]):
+    y = logits = am = None
+    if epi == GEMV_ROWS_LOGITS:
+        logits = torch.empty(N, dtype=torch.float32, device=device)
+        am = torch.empty(1, dtype=torch.int32, device=device)
+    else:
+        y = out if out is not None else torch.empty(N // 2 if epi == GEMV_ROWS_SILU_MUL else N, dtype=torch.bfloat16, device=device)
+    return y, logits, am
+
+
+def gemv_epi(W: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, norm_w: Optional[torch.Tensor] = None, eps: float = 1e-6,
+             residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """The single-sequence decode matvec with an epilogue (aha_hip_gemv_epi): W (N, K) bf16, x (K) bf16, epi as in gemv_rows -- STORE /
+    RESIDUAL -> (N) bf16 (`out` may be the residual itself); SILU_MUL (W in the 16-row gate / up block layout) -> (N / 2) bf16; LOGITS ->
+    ((N) f32 logits, int argmax).  norm_w fuses RMSNorm(x; norm_w, eps) in front."""
+    _chk(W, x, norm_w, residual, out)
+    N, K = W.shape
+    y, logits, am = _gemv_epi_outputs(N, epi, x.device, out)
+    check(lib().aha_hip_gemv_epi(_ptr(W), _ptr(x), _ptr(y), N, K, epi, _ptr(norm_w), eps, _ptr(residual), _ptr(logits), _ptr(am), _stream()))
+    return (logits, int(am.item())) if epi == GEMV_ROWS_LOGITS else y
+
+
+def gemv_mxfp8(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, norm_w: Optional[torch.Tensor] = None,
+               eps: float = 1e-6, residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """gemv_epi from the MXFP8 copy of W (aha_hip_gemv_mxfp8): q (N, K) uint8, scales (N, K / 32) uint8 in the reference's order (converted
+    to the kernel's words here).  Every output bit, and the argmax, equals gemv_epi(W', ...) for W' = dequantize_mxfp8(q, scales)."""
+    from . import quant
+    _chk(q, x, norm_w, residual, out)
+    N, K = q.shape
+    words = quant.scales_to_kernel(scales).to(x.device)
+    y, logits, am = _gemv_epi_outputs(N, epi, x.device, out)
+    check(lib().aha_hip_gemv_mxfp8(_ptr(q), _ptr(words), _ptr(x), _ptr(y), N, K, epi, _ptr(norm_w), eps, _ptr(residual), _ptr(logits), _ptr(am),
+                                   _stream()))
+    return (logits, int(am.item())) if epi == GEMV_ROWS_LOGITS else y
+
+
+def plan_gemv_mxfp8(N: int, K: int, epi: int = GEMV_ROWS_STORE, has_norm: bool = False):
+    """Host only: (R, U, grid, form) gemv_mxfp8 picks for a matrix of N rows (aha_hip_debug_plan_gemv_mxfp8): form 0 general, 1 FAST, 2 / 3
+    FAST with the straight-line prologue without / with norm weights."""
+    r, u, g, f = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib().aha_hip_debug_plan_gemv_mxfp8(N, K, epi, int(has_norm), C.byref(r), C.byref(u), C.byref(g), C.byref(f), None))
+    return r.value, u.value, g.value, f.value
+
+
+def gemv_mxfp8_by_plan(N: int, K: int, epi: int = GEMV_ROWS_STORE) -> bool:
+    """Host only: does a quantised model's single-sequence step read a matrix of N rows (gate+up: 2I) and K columns from its copy?"""
+    r, b = C.c_int32(), C.c_int32()
+    check(lib().aha_hip_debug_plan_gemv_mxfp8(N, K, epi, 0, C.byref(r), C.byref(r), C.byref(r), None, C.byref(b)))
+    return bool(b.value)
+
+
 def attn_decode_batch(qkv: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: torch.Tensor, rope: torch.Tensor, page_ptrs: torch.Tensor,
                       page0, kv_len, nh: int, kvh: int, eps: float, scale: float) -> torch.Tensor:
     """Fused decode attention of R sequences in one launch: qkv (R, (nh+2kvh)*128) bf16, rope (R, 128) f32, page_ptrs (P,) int64 device

@@ -685,11 +685,14 @@ int aha_hip_kv_import(aha_model* m, const void* in_dev, size_t in_bytes, int32_t
  * wait for it.  Lets a 1-GPU box exercise the RCCL wiring with a communicator of size 1. */
 int aha_hip_debug_allreduce(aha_model* m, void* buf_f32_dev, size_t count);
 
-/* ---- quantised weight copies for the batched decode ------------------------------------------------------------- */
+/* ---- quantised weight copies for decode ------------------------------------------------------------------------- */
 /* aha_hip_model_quantize_weights: quantise the layer matrices (wqkv, wo, wgu, wdown) of a created model to MXFP8 (see
  * aha_hip_quantize_mxfp8), in place: each bf16 matrix W is overwritten with W' = dequantised W and its (q, scales) copy is kept beside it.
  * The batched decode matvec (every aha_hip_generate_batch* entry and the engine) then streams q and the scales, 1.03125 bytes per weight
- * instead of 2, with the bits it would compute from W'; prefill and every other path go on reading the bf16 W'.  flags: 0, or
+ * instead of 2, with the bits it would compute from W', and so does the single-sequence decode matvec (aha_hip_forward_step,
+ * aha_hip_decode_greedy, the generate_generic loops, the last-row lm_head of aha_hip_forward_initial: gemv_mxfp8_kernel, bit-identical to
+ * the bf16 kernel on W') on the matrices it measured faster on, those of 2^24 elements or more whose launch takes the kernel's FAST form (aha_hip_debug_fp8_single); prefill and
+ * every other path go on reading the bf16 W'.  flags: 0, or
  * AHA_WQ_LM_HEAD to quantise lm_head too (with tied embeddings: the embedding table).  Costs 0.516 x the quantised matrices in memory.
  * AHA_ERR_INVALID: a null model, an unknown format or flag, or a weight that is not finite (or >= 1.9375 * 2^127 in magnitude), naming
  * the tensor -- every matrix is checked before any is modified.  AHA_ERR_STATE: the cache is not empty, the model has an engine, or it
@@ -705,6 +708,13 @@ int aha_hip_model_weight_format(const aha_model* m, int32_t* format, uint32_t* f
 /* Test hook: on = 0 makes a quantised model's batched decode run the bf16 matvec on W' instead of the FP8 one (the same bits); on = 1
  * (the default) restores it. */
 int aha_hip_debug_fp8_rows(aha_model* m, int on);
+/* The switch of the single-sequence decode matvec (the decode step's four projections and the lm_head); independent of
+ * aha_hip_debug_fp8_rows, and unlike it three-valued, because here the plan may keep a shape on bf16.  on = 1 (the default): a matrix with a copy is read from it where the plan takes its shape -- the matrices for
+ * which the FP8 kernel measured faster, at least 2^24 elements and K a multiple of 512 * U, the FAST form (aha_hip_debug_plan_gemv_mxfp8
+ * tells; profiles/weights_fp8_single.md) -- so small models, the test suite's among them, decode on bf16 unless the switch is 2;
+ * 2: every matrix with a copy; 0: none (the bf16 kernel on W').  The bits are the same in all three.  Profile class of the FP8 launches:
+ * gemv_fp8 (bf16: gemv).  AHA_ERR_INVALID: a null model or another value. */
+int aha_hip_debug_fp8_single(aha_model* m, int on);
 
 /* ---- introspection used by bench.py / tests ------------------------------------------------------------------ */
 size_t aha_hip_cache_len(const aha_model* m);
@@ -767,6 +777,13 @@ int aha_hip_debug_plan_gemm(int32_t M, int32_t N, int32_t K, int32_t act, int32_
  * that every (tile, K tile) is covered exactly once for the BASELINE shapes. */
 int aha_hip_debug_streamk_plan(int32_t M, int32_t N, int32_t K, int32_t tile_n, int32_t workers, size_t workspace_bytes, int32_t* out,
                                int32_t cap, int32_t* off_out, int32_t* info7);
+/* Host only (no GPU): the plan aha_hip_gemv_mxfp8 / the model's single-sequence FP8 matvec picks for a matrix of N rows (epi 2: N = 2I)
+ * and K columns: *R rows per wave, *U 512-k chunks per work item, *grid persistent blocks (= the (max, index) partials of epi 3), and
+ * (form may be NULL) *form = 0 the general kernel, 1 FAST (every chunk group full), 2 / 3 FAST with the straight-line prologue without /
+ * with norm weights (has_norm).  Names the instantiation gemv_mxfp8_kernel<R, U, epi, form != 0, max(form - 1, 0)>.  *by_plan (may be
+ * NULL) = 1 if a model's single-sequence step reads a matrix of this shape from its copy by default (aha_hip_debug_fp8_single). */
+int aha_hip_debug_plan_gemv_mxfp8(int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form,
+                                  int32_t* by_plan);
 /* CUs the persistent GEMM kernel leaves free (rounded so that its workgroup count stays a multiple of 8; 0 = use every CU; < 0 = take
  * AHA_GEMM_RESERVE_CUS from the environment).  Process-wide.  For tensor-parallel prefill: RCCL's kernels on the communication stream
  * need CUs next to a GEMM whose workgroups each fill one (csrc/model.hip gemm_row_parallel).  Must be the same on every rank only
@@ -813,6 +830,20 @@ int aha_hip_gemv_rows(const void* W, const void* x, void* y, int32_t R, int32_t 
  * aha_hip_gemv_rows_mxfp8: aha_hip_gemv_rows with (q, scales) in place of W, K % 32 == 0: every output bit equals
  * aha_hip_gemv_rows on W'. */
 int aha_hip_quantize_mxfp8(const void* W, int32_t N, int32_t K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, void* stream);
+/* Batch-1 matvec with an epilogue, op level (the single-sequence decode step's kernels).  N counts MATRIX rows; epi as in
+ * aha_hip_gemv_rows: 0 y (N) bf16; 1 y = residual + Linear (may alias); 2 SiLU(gate) * up with W in the 16-row gate / up block layout
+ * (N = 2I, N % 32 == 0), y (I) bf16; 3 logits (N) f32 and *argmax_out (device u32) the first maximal index.  norm_w != NULL fuses
+ * h = RMSNorm(x; norm_w, eps) in front.
+ * aha_hip_gemv_epi: W (N, K) bf16, K % 8 == 0, K <= 32768 -- the kernel of aha_hip_gemv.
+ * aha_hip_gemv_mxfp8: (q, scales) of aha_hip_quantize_mxfp8 in place of W, K % 32 == 0, K <= 32768.  The contract is bit identity: per
+ * 512-k chunk a lane reads the same 8 k as the bf16 kernel (8 E4M3 bytes and their block's scale byte), byte * 2^e is exact in f32 and
+ * equals the bf16 weight of W' = q * 2^e, and the fma order, wave reduction and rounding points are the bf16 kernel's, so every output
+ * bit -- and the argmax -- equals aha_hip_gemv_epi on W'.  AHA_ERR_INVALID with a message, before anything is launched: a null q,
+ * scales, x or output of the epilogue, K not a multiple of 32 or above 32768, N < 1, epi outside 0..3, epi 2 with N % 32 != 0. */
+int aha_hip_gemv_epi(const void* W, const void* x, void* y, int32_t N, int32_t K, int32_t epi, const void* norm_w, float eps,
+                     const void* residual, float* logits, uint32_t* argmax_out, void* stream);
+int aha_hip_gemv_mxfp8(const void* q, const uint32_t* scales, const void* x, void* y, int32_t N, int32_t K, int32_t epi, const void* norm_w,
+                       float eps, const void* residual, float* logits, uint32_t* argmax_out, void* stream);
 int aha_hip_gemv_rows_mxfp8(const void* q, const uint32_t* scales, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi,
                             const void* residual, float* logits, uint32_t* argmax_out, void* stream);
 /* aha_hip_attn_decode_batch: the fused decode attention block (QKNormAttention::forward, modules.rs:538-577, without o_proj) of `rows`

@@ -601,6 +601,47 @@ pub mod sys {
         pub fn aha_hip_model_quantize_weights(m: *mut AhaModel, format: i32, flags: u32) -> i32;
         pub fn aha_hip_model_weight_format(m: *const AhaModel, format: *mut i32, flags: *mut u32) -> i32;
         pub fn aha_hip_debug_fp8_rows(m: *mut AhaModel, on: i32) -> i32;
+        pub fn aha_hip_debug_fp8_single(m: *mut AhaModel, on: i32) -> i32;
+        pub fn aha_hip_debug_plan_gemv_mxfp8(
+            n: i32,
+            k: i32,
+            epi: i32,
+            has_norm: i32,
+            r: *mut i32,
+            u: *mut i32,
+            grid: *mut i32,
+            form: *mut i32,
+            by_plan: *mut i32,
+        ) -> i32;
+        pub fn aha_hip_gemv_epi(
+            w: *const std::ffi::c_void,
+            x: *const std::ffi::c_void,
+            y: *mut std::ffi::c_void,
+            n: i32,
+            k: i32,
+            epi: i32,
+            norm_w: *const std::ffi::c_void,
+            eps: f32,
+            residual: *const std::ffi::c_void,
+            logits: *mut f32,
+            argmax_out: *mut u32,
+            stream: *mut std::ffi::c_void,
+        ) -> i32;
+        pub fn aha_hip_gemv_mxfp8(
+            q: *const std::ffi::c_void,
+            scales: *const u32,
+            x: *const std::ffi::c_void,
+            y: *mut std::ffi::c_void,
+            n: i32,
+            k: i32,
+            epi: i32,
+            norm_w: *const std::ffi::c_void,
+            eps: f32,
+            residual: *const std::ffi::c_void,
+            logits: *mut f32,
+            argmax_out: *mut u32,
+            stream: *mut std::ffi::c_void,
+        ) -> i32;
         pub fn aha_hip_quantize_mxfp8(
             w: *const std::ffi::c_void,
             n: i32,
@@ -880,7 +921,9 @@ impl Model {
 
     /// Quantise the layer matrices (and `lm_head` with `lm_head = true`; the embedding table when tied) to block-scaled FP8 in place
     /// (`aha_hip_model_quantize_weights`): the batched decode then streams 1.03 bytes per weight instead of 2, with the bits it would
-    /// compute from the dequantised bf16 matrices, which every other path goes on reading.  Needs an empty cache and no engine.
+    /// compute from the dequantised bf16 matrices, which every other path goes on reading.  Single-sequence decode (`forward_step`,
+    /// `decode_greedy`, the generate loops) reads the copies too where that measured faster (matrices of 2^24 elements or more in the kernel's FAST form), bit-identical
+    /// to the bf16 matvec.  Needs an empty cache and no engine.
     pub fn quantize_weights(&mut self, format: WeightFormat, lm_head: bool) -> Result<(), Error> {
         let flags = if lm_head { sys::AHA_WQ_LM_HEAD } else { 0 };
         check(unsafe { sys::aha_hip_model_quantize_weights(self.model, format as i32, flags) })
