@@ -17,7 +17,7 @@ ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF, ACT_SILU, ACT_SILU_MUL_PAIRS = 0, 1, 2, 3
 
 AHA_SAMPLE_HAS_TOP_P, AHA_SAMPLE_HAS_TOP_K = 1, 2
 AHA_SAMPLE_NEED_LOGITS = 1
-AHA_WQ_NONE, AHA_WQ_MXFP8_E4M3 = 0, 1
+AHA_WQ_NONE, AHA_WQ_MXFP8_E4M3, AHA_WQ_MXFP4_E2M1 = 0, 1, 2
 AHA_WQ_LM_HEAD = 1
 
 
@@ -245,6 +245,8 @@ SIGNATURES = {
     "aha_hip_gemv_rows": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "aha_hip_quantize_mxfp8": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "aha_hip_gemv_rows_mxfp8": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "aha_hip_quantize_mxfp4": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "aha_hip_gemv_rows_mxfp4": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "aha_hip_model_quantize_weights": (C.c_int, [_P, C.c_int32, C.c_uint32]),
     "aha_hip_model_weight_format": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]),
     "aha_hip_debug_fp8_rows": (C.c_int, [_P, C.c_int]),

@@ -793,6 +793,52 @@ int aha_hip_quantize_mxfp8(const void* W, int32_t N, int32_t K, void* q_out, uin
   API_GUARD_END
 }
 
+int aha_hip_gemv_rows_mxfp4(const void* q, const uint32_t* scales, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi,
+                            const void* residual, float* logits, uint32_t* argmax_out, void* stream) {
+  API_GUARD_BEGIN
+  if (!q || !scales || !x || R < 1 || R > 32 || N < 1 || K < 32 || K % 32 || epi < 0 || epi > 3 || (epi == 1 && (!residual || !y)) ||
+      ((epi == 0 || epi == 2) && !y) || (epi == 2 && N % 32) || (epi == 3 && (!logits || !argmax_out))) {
+    set_error("gemv_rows_mxfp4: bad arguments (q, scales, 1 <= R <= 32, K % 32 == 0, epi 0..3 with its outputs; epi 2 needs N % 32 == 0)");
+    return AHA_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int tiles = gemv_rows_num_tiles(N);
+  float *ws = nullptr, *bm = nullptr;
+  uint32_t* bi = nullptr;
+  AHA_HIP_CHECK(hipMalloc((void**)&ws, gemv_rows_ws_floats(R, N, K) * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&bm, (size_t)R * tiles * 4));
+  AHA_HIP_CHECK(hipMalloc((void**)&bi, (size_t)R * tiles * 4));
+  GemvRowsArgs a{};
+  a.x = x; a.ldx = K; a.R = R; a.N = N; a.K = K; a.ws = ws;
+  a.y = y; a.residual = residual; a.ldy = epi == 2 ? N / 2 : N;
+  a.y_f32 = logits; a.ldf = N; a.blk_max = bm; a.blk_idx = bi;
+  const GemvEpi e = epi == 0 ? GEMV_STORE : epi == 1 ? GEMV_RESIDUAL : epi == 2 ? GEMV_SILU_MUL : GEMV_LOGITS;
+  launch_gemv_rows_mxfp4(a, q, scales, e, st);
+  if (epi == 3) launch_argmax_rows(bm, bi, tiles, R, argmax_out, st);
+  hipError_t err = hipGetLastError();
+  hipStreamSynchronize(st);
+  hipFree(ws);
+  hipFree(bm);
+  hipFree(bi);
+  AHA_HIP_CHECK(err);
+  return AHA_OK;
+  API_GUARD_END
+}
+
+int aha_hip_quantize_mxfp4(const void* W, int32_t N, int32_t K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, void* stream) {
+  API_GUARD_BEGIN
+  if (!W || !q_out || !scales_out || N < 1 || K < 32 || K % 32) {
+    set_error("quantize_mxfp4: bad arguments (W, q_out, scales_out, N >= 1, K a positive multiple of 32)");
+    return AHA_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  launch_mxfp4_quantize(W, N, K, q_out, scales_out, w_roundtrip_out, st);
+  AHA_HIP_CHECK(hipGetLastError());
+  AHA_HIP_CHECK(hipStreamSynchronize(st));
+  return AHA_OK;
+  API_GUARD_END
+}
+
 int aha_hip_model_quantize_weights(aha_model* m, int32_t format, uint32_t flags) {
   API_GUARD_BEGIN
   if (!m) {

@@ -37,7 +37,8 @@ struct LayerWeights {
   void* post_norm = nullptr;
   void* q_norm = nullptr;   // (d)
   void* k_norm = nullptr;
-  // MXFP8 copies of the four matrices (aha_hip_model_quantize_weights; null: none): the batched decode matvec streams these
+  // MXFP8 or MXFP4 copies of the four matrices (aha_hip_model_quantize_weights; null: none; the format is aha_model::wq_format): the batched
+  // decode matvec streams these
   WQuant q_wqkv, q_wo, q_wgu, q_wdown;
 };
 
@@ -83,9 +84,9 @@ struct aha_model {
   int32_t wq_format = 0;
   uint32_t wq_flags = 0;
   aha::WQuant q_lm_head;
-  bool fp8_rows = true;      // aha_hip_debug_fp8_rows: false = the bf16 matvec on W' although a copy exists
+  bool fp8_rows = true;      // aha_hip_debug_fp8_rows: false = the bf16 matvec on W' although a copy (of either format) exists
   int fp8_single = 1;        // aha_hip_debug_fp8_single, the single-sequence matvec (enqueue_decode_step, enqueue_lm_head): 0 = bf16 on W',
-                             // 1 = the FP8 kernel where the plan takes the shape (gemv_mxfp8_by_plan), 2 = wherever a copy exists
+                             // 1 = the FP8 kernel where the plan takes the shape (gemv_mxfp8_by_plan), 2 = wherever a copy exists; MXFP8 models only
   // rope constants
   float* d_inv_freq = nullptr;
   int32_t* d_axis_map = nullptr;

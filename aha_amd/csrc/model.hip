@@ -550,8 +550,8 @@ int model_clear_cache(aha_model* m) {
 // W' in place (the quantiser reads an element before it writes it), its (q, scales) copy lands in the matrix's slot.
 int model_quantize_weights(aha_model* m, int32_t format, uint32_t flags) {
   const aha_model_desc& c = m->desc;
-  if (format != AHA_WQ_MXFP8_E4M3) {
-    set_error("quantize_weights: unknown format " + std::to_string(format) + " (AHA_WQ_MXFP8_E4M3 = 1)");
+  if (format != AHA_WQ_MXFP8_E4M3 && format != AHA_WQ_MXFP4_E2M1) {
+    set_error("quantize_weights: unknown format " + std::to_string(format) + " (AHA_WQ_MXFP8_E4M3 = 1, AHA_WQ_MXFP4_E2M1 = 2)");
     return AHA_ERR_INVALID;
   }
   if (flags & ~(uint32_t)AHA_WQ_LM_HEAD) {
@@ -595,17 +595,21 @@ int model_quantize_weights(aha_model* m, int32_t format, uint32_t flags) {
     mats.push_back({c.tie_word_embeddings ? "embed_tokens.weight (tied lm_head)" : "lm_head.weight", m->lm_head, c.vocab_size, H, &m->q_lm_head});
   for (const Mat& t : mats)
     if (t.K % MX_BLOCK) {
-      set_error("quantize_weights: " + t.name + " has K = " + std::to_string(t.K) + ", not a multiple of 32 (the MXFP8 block)");
+      set_error("quantize_weights: " + t.name + " has K = " + std::to_string(t.K) + ", not a multiple of 32 (the MX block)");
       return AHA_ERR_UNSUPPORTED;
     }
   AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
   hipStream_t st = m->stream;
+  const bool fp4 = format == AHA_WQ_MXFP4_E2M1;
   {   // every matrix finite (and inside the format's range) before any is touched
     int* d_flag = nullptr;
     std::vector<int> h_flag(mats.size(), 0);
     AHA_HIP_CHECK(hipMalloc((void**)&d_flag, mats.size() * sizeof(int)));
     hipError_t e = hipMemsetAsync(d_flag, 0, mats.size() * sizeof(int), st);
-    for (size_t i = 0; i < mats.size() && e == hipSuccess; ++i) launch_mxfp8_check(mats[i].w, (int64_t)mats[i].N * mats[i].K, d_flag + i, st);
+    for (size_t i = 0; i < mats.size() && e == hipSuccess; ++i) {
+      if (fp4) launch_mxfp4_check(mats[i].w, (int64_t)mats[i].N * mats[i].K, d_flag + i, st);
+      else launch_mxfp8_check(mats[i].w, (int64_t)mats[i].N * mats[i].K, d_flag + i, st);
+    }
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h_flag.data(), d_flag, mats.size() * sizeof(int), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -613,14 +617,15 @@ int model_quantize_weights(aha_model* m, int32_t format, uint32_t flags) {
     AHA_HIP_CHECK(e);
     for (size_t i = 0; i < mats.size(); ++i)
       if (h_flag[i]) {
-        set_error("quantize_weights: " + mats[i].name + " holds a weight that is not finite (or is 1.9375 * 2^127 or more in magnitude); no matrix was modified");
+        set_error("quantize_weights: " + mats[i].name + " holds a weight that is not finite (or is " +
+                  (fp4 ? "above 1.5 * 2^127" : "1.9375 * 2^127 or more") + " in magnitude); no matrix was modified");
         return AHA_ERR_INVALID;
       }
   }
   std::vector<void*> got;
   std::vector<WQuant> wq(mats.size());
   for (size_t i = 0; i < mats.size(); ++i) {
-    const size_t bytes[2] = {(size_t)mats[i].N * mats[i].K, mxfp8_scale_words(mats[i].N, mats[i].K) * 4};
+    const size_t bytes[2] = {(size_t)mats[i].N * mats[i].K / (fp4 ? 2 : 1), mxfp8_scale_words(mats[i].N, mats[i].K) * 4};
     for (int k = 0; k < 2; ++k) {
       void* p = nullptr;
       const hipError_t e = hipMalloc(&p, bytes[k]);
@@ -636,7 +641,10 @@ int model_quantize_weights(aha_model* m, int32_t format, uint32_t flags) {
       else wq[i].scales = (uint32_t*)p;
     }
   }
-  for (size_t i = 0; i < mats.size(); ++i) launch_mxfp8_quantize(mats[i].w, mats[i].N, mats[i].K, wq[i].q, wq[i].scales, mats[i].w, st);
+  for (size_t i = 0; i < mats.size(); ++i) {
+    if (fp4) launch_mxfp4_quantize(mats[i].w, mats[i].N, mats[i].K, wq[i].q, wq[i].scales, mats[i].w, st);
+    else launch_mxfp8_quantize(mats[i].w, mats[i].N, mats[i].K, wq[i].q, wq[i].scales, mats[i].w, st);
+  }
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   for (void* p : got) m->owned.push_back(p);   // freed with the model whatever happened
@@ -955,9 +963,10 @@ static void gemv_row_parallel(aha_model* m, GemvArgs g);
 // One batch-1 matvec of the single-sequence path (g.N output rows: I for GEMV_SILU_MUL).  A matrix with an MXFP8 copy is read from it
 // where the plan takes the shape (gemv_mxfp8_by_plan: the matrices for which FP8 measured faster; the two kernels give the same bits, so
 // the choice is invisible in the output; aha_hip_debug_fp8_single overrides it either way) -- sharded models never have a copy.
-// Profile class gemv_fp8 at 1.03125 bytes per weight, gemv at 2; act_bytes: the activation traffic.
+// Profile class gemv_fp8 at 1.03125 bytes per weight, gemv at 2; act_bytes: the activation traffic.  An MXFP4 copy is never read here:
+// there is no batch-1 kernel for it, so an MXFP4 model's single-sequence path runs the bf16 matvec on W' whatever the switch says.
 static bool fp8_single(const aha_model* m, const WQuant& wq, int rows, int K, GemvEpi epi) {
-  return wq.q != nullptr && m->tp_size <= 1 && (m->fp8_single == 2 || (m->fp8_single == 1 && gemv_mxfp8_by_plan(rows, K, epi)));
+  return wq.q != nullptr && m->wq_format == AHA_WQ_MXFP8_E4M3 && m->tp_size <= 1 && (m->fp8_single == 2 || (m->fp8_single == 1 && gemv_mxfp8_by_plan(rows, K, epi)));
 }
 static void decode_gemv(aha_model* m, const GemvArgs& g, GemvEpi epi, const WQuant& wq, double act_bytes) {
   const double weights = (epi == GEMV_SILU_MUL ? 2.0 : 1.0) * g.N * g.K;
@@ -1525,7 +1534,7 @@ static void gemv_trace_dump(aha_model* m) {
   std::vector<unsigned long long> t((size_t)nl * 18);
   if (hipMemcpy(t.data(), m->d_gemv_trace, t.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
   static const char* names[4] = {"qkv", "o_proj", "gate_up", "down"};
-  if (m->fp8_single && L > 0 && m->layers[0].q_wqkv.q)
+  if (m->fp8_single && m->wq_format == AHA_WQ_MXFP8_E4M3 && L > 0 && m->layers[0].q_wqkv.q)
     fprintf(stderr, "[gemv trace] the model has MXFP8 copies: launches of gemv_mxfp8_kernel are not traced, their slots are stale or empty "
                     "(aha_hip_debug_fp8_single(m, 0) traces the bf16 kernel on the same weights)\n");
   for (int k = 0; k < 4; ++k) {
@@ -2446,11 +2455,13 @@ struct DevBufs {   // per-call device / pinned scratch, freed after the stream h
 constexpr int GEN_ROW_GROUP = 32;   // rows of one gemv_rows launch: larger batches stream the weights once per group
 
 // y[rows] = epi(x[rows] . W^T) in groups of GEN_ROW_GROUP rows.  For GEMV_LOGITS, y_f32 / blk partials are (rows, ldf) / (rows, tiles).
-// wq: the MXFP8 copy of g.W (model_quantize_weights), streamed in its place when it exists -- the same bits at 1 + 1/32 bytes per weight.
+// wq: the MXFP8 or MXFP4 copy of g.W (model_quantize_weights, m->wq_format), streamed in its place when it exists -- the same bits at
+// 1 + 1/32 or 1/2 + 1/32 bytes per weight (profile classes gemv_rows_fp8, gemv_rows_fp4).
 static void gemv_rows_groups(aha_model* m, GemvRowsArgs g, GemvEpi epi, int rows, float* ws, const WQuant* wq = nullptr) {
   const int tiles = gemv_rows_num_tiles(g.N);
-  const bool fp8 = wq && wq->q && m->fp8_rows;
-  const double wbytes = (double)g.N * g.K * (fp8 ? 1.0 + 1.0 / 32 : 2.0);
+  const bool copy = wq && wq->q && m->fp8_rows;
+  const bool fp8 = copy && m->wq_format == AHA_WQ_MXFP8_E4M3, fp4 = copy && m->wq_format == AHA_WQ_MXFP4_E2M1;
+  const double wbytes = (double)g.N * g.K * (fp8 ? 1.03125 : fp4 ? 0.53125 : 2.0);
   for (int r0 = 0; r0 < rows; r0 += GEN_ROW_GROUP) {
     GemvRowsArgs a = g;
     a.R = std::min(GEN_ROW_GROUP, rows - r0);
@@ -2460,8 +2471,9 @@ static void gemv_rows_groups(aha_model* m, GemvRowsArgs g, GemvEpi epi, int rows
     if (g.y_f32) a.y_f32 = g.y_f32 + (int64_t)r0 * g.ldf;
     if (g.blk_max) a.blk_max = g.blk_max + (int64_t)r0 * tiles, a.blk_idx = g.blk_idx + (int64_t)r0 * tiles;
     a.ws = ws;
-    ProfScope ps(m, fp8 ? "gemv_rows_fp8" : "gemv_rows", wbytes + (double)a.R * (g.K + g.N) * 2, 2.0 * a.R * g.N * g.K);
+    ProfScope ps(m, fp8 ? "gemv_rows_fp8" : fp4 ? "gemv_rows_fp4" : "gemv_rows", wbytes + (double)a.R * (g.K + g.N) * 2, 2.0 * a.R * g.N * g.K);
     if (fp8) launch_gemv_rows_mxfp8(a, wq->q, wq->scales, epi, m->stream);
+    else if (fp4) launch_gemv_rows_mxfp4(a, wq->q, wq->scales, epi, m->stream);
     else launch_gemv_rows(a, epi, m->stream);
   }
 }

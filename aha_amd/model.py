@@ -597,17 +597,22 @@ class HipInferenceModel:
 
     def quantize_weights(self, fmt: str = "mxfp8", lm_head: bool = False) -> None:
         """Quantise the layer matrices (and lm_head with lm_head=True) to MXFP8 in place (aha_hip_model_quantize_weights): the batched decode
-        then streams the FP8 copies; every other path reads the dequantised bf16 matrices.  aha_amd/quant.py is the reference quantiser."""
-        if fmt != "mxfp8":
-            raise ValueError(f"unknown weight format {fmt!r} (\"mxfp8\")")
-        check(lib().aha_hip_model_quantize_weights(self.handle, _lib.AHA_WQ_MXFP8_E4M3, _lib.AHA_WQ_LM_HEAD if lm_head else 0))
+        then streams the FP8 copies; every other path reads the dequantised bf16 matrices.  aha_amd/quant.py is the reference quantiser.
+        fmt "mxfp4": MXFP4 copies (E2M1 nibbles, 0.53 bytes per weight) for the batched decode; the single-sequence decode of such a
+        model runs the bf16 matvec on the dequantised matrices."""
+        formats = {"mxfp8": _lib.AHA_WQ_MXFP8_E4M3, "mxfp4": _lib.AHA_WQ_MXFP4_E2M1}
+        if fmt not in formats:
+            raise ValueError(f"unknown weight format {fmt!r} (\"mxfp8\", \"mxfp4\")")
+        check(lib().aha_hip_model_quantize_weights(self.handle, formats[fmt], _lib.AHA_WQ_LM_HEAD if lm_head else 0))
 
     @property
     def weight_format(self):
-        """None, or ("mxfp8", lm_head) as quantize_weights was called."""
+        """None, or ("mxfp8" | "mxfp4", lm_head) as quantize_weights was called."""
         f, fl = C.c_int32(), C.c_uint32()
         check(lib().aha_hip_model_weight_format(self.handle, C.byref(f), C.byref(fl)))
-        return None if f.value == _lib.AHA_WQ_NONE else ("mxfp8", bool(fl.value & _lib.AHA_WQ_LM_HEAD))
+        if f.value == _lib.AHA_WQ_NONE:
+            return None
+        return ("mxfp4" if f.value == _lib.AHA_WQ_MXFP4_E2M1 else "mxfp8", bool(fl.value & _lib.AHA_WQ_LM_HEAD))
 
     def debug_fp8_rows(self, on: bool = True) -> None:
         """Test hook: False makes a quantised model's batched decode run the bf16 matvec on the dequantised matrices (the same bits)."""

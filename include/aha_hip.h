@@ -698,22 +698,30 @@ int aha_hip_debug_allreduce(aha_model* m, void* buf_f32_dev, size_t count);
  * the tensor -- every matrix is checked before any is modified.  AHA_ERR_STATE: the cache is not empty, the model has an engine, or it
  * was quantised with other arguments (the same arguments again: AHA_OK, nothing done).  AHA_ERR_UNSUPPORTED, naming the cause: a tensor-
  * or context-parallel model, a matrix whose K is not a multiple of 32, a model outside aha_hip_generate_batch's set.  AHA_ERR_OOM: the
- * copies cannot be had; the model is as it was.  Reads no environment variable. */
+ * copies cannot be had; the model is as it was.  Reads no environment variable.
+ * format AHA_WQ_MXFP4_E2M1 does the same with MXFP4 copies (see aha_hip_quantize_mxfp4): W' = dequantised W in place, E2M1 nibbles and
+ * the same scale words beside it, 0.53125 bytes per weight for the batched decode matvec (gemv_rows_mxfp4_kernel, the bits of the bf16
+ * kernel on W'), +0.266 x the quantised matrices in memory, a weight refused when it is not finite or above 1.5 * 2^127 in magnitude.
+ * There is no batch-1 MXFP4 kernel: an MXFP4 model's single-sequence decode (aha_hip_forward_step, aha_hip_decode_greedy, the generate
+ * loops, the last-row lm_head) runs the bf16 matvec on W', at bf16 speed, whatever aha_hip_debug_fp8_single says.  A model holds copies
+ * of one format: quantising with the other afterwards is AHA_ERR_STATE. */
 #define AHA_WQ_NONE 0
 #define AHA_WQ_MXFP8_E4M3 1
+#define AHA_WQ_MXFP4_E2M1 2
 #define AHA_WQ_LM_HEAD 1u
 int aha_hip_model_quantize_weights(aha_model* m, int32_t format, uint32_t flags);
 /* *format = AHA_WQ_NONE or the format the model was quantised with, *flags its flags (either pointer may be NULL). */
 int aha_hip_model_weight_format(const aha_model* m, int32_t* format, uint32_t* flags);
 /* Test hook: on = 0 makes a quantised model's batched decode run the bf16 matvec on W' instead of the FP8 one (the same bits); on = 1
- * (the default) restores it. */
+ * (the default) restores it.  It holds for either format: on = 0 sends an MXFP4 model to the bf16 kernel on W' as well. */
 int aha_hip_debug_fp8_rows(aha_model* m, int on);
 /* The switch of the single-sequence decode matvec (the decode step's four projections and the lm_head); independent of
  * aha_hip_debug_fp8_rows, and unlike it three-valued, because here the plan may keep a shape on bf16.  on = 1 (the default): a matrix with a copy is read from it where the plan takes its shape -- the matrices for
  * which the FP8 kernel measured faster, at least 2^24 elements and K a multiple of 512 * U, the FAST form (aha_hip_debug_plan_gemv_mxfp8
  * tells; profiles/weights_fp8_single.md) -- so small models, the test suite's among them, decode on bf16 unless the switch is 2;
  * 2: every matrix with a copy; 0: none (the bf16 kernel on W').  The bits are the same in all three.  Profile class of the FP8 launches:
- * gemv_fp8 (bf16: gemv).  AHA_ERR_INVALID: a null model or another value. */
+ * gemv_fp8 (bf16: gemv).  AHA_ERR_INVALID: a null model or another value.  An MXFP4 model ignores the switch: its copies are never read
+ * by the single-sequence path (value 2 included). */
 int aha_hip_debug_fp8_single(aha_model* m, int on);
 
 /* ---- introspection used by bench.py / tests ------------------------------------------------------------------ */
@@ -845,6 +853,22 @@ int aha_hip_gemv_epi(const void* W, const void* x, void* y, int32_t N, int32_t K
 int aha_hip_gemv_mxfp8(const void* q, const uint32_t* scales, const void* x, void* y, int32_t N, int32_t K, int32_t epi, const void* norm_w,
                        float eps, const void* residual, float* logits, uint32_t* argmax_out, void* stream);
 int aha_hip_gemv_rows_mxfp8(const void* q, const uint32_t* scales, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi,
+                            const void* residual, float* logits, uint32_t* argmax_out, void* stream);
+/* MXFP4 weight copies, op level.  A bf16 matrix W (N, K), K % 32 == 0, as OCP microscaling FP4: every row in blocks of 32 consecutive k.
+ * Elements are OCP E2M1: the magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6}, code = sign << 3 | index.  Per block e = the smallest integer in
+ * [-125, 125] with max |w| <= 6 * 2^e (an all-zero block: -125) and the scale byte is e + 127 (E8M0) -- the no-saturation convention of
+ * the MXFP8 path, not the OCP text's floor(log2 max |w|) - 2.  q = the code nearest to v = w / 2^e (exact), a tie to the even code:
+ * 0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4.  The sign bit is kept, so the code 0x8 (-0) occurs; gfx950's
+ * conversion returns -0.0 for it, as W' holds.  W' = q * 2^e has two significant bits and is 0 or at least 2^-126 in magnitude: exact
+ * in bf16.  |w' - w| <= max(|w| / 4, 2^(e - 2)); quantising W' gives W' again.
+ * aha_hip_quantize_mxfp4: q_out (N, K / 2) bytes, byte (n, k / 2) holds even k in bits 0..3 and odd k in bits 4..7; scales_out as for
+ * aha_hip_quantize_mxfp8 -- (N, ceil(K / 128)) u32, block 4c + g in bits 8g .. 8g + 7 of word (n, c), bytes of blocks past K: 127;
+ * w_roundtrip_out (N, K) bf16 = W', may be NULL or W itself.  The weights must be finite and at most 1.5 * 2^127 in magnitude (beyond
+ * it a weight would round past 6 * 2^125; not checked here).
+ * aha_hip_gemv_rows_mxfp4: aha_hip_gemv_rows with (q, scales) in place of W, K % 32 == 0: every output bit equals aha_hip_gemv_rows on
+ * W'.  Argument checks as for aha_hip_gemv_rows_mxfp8. */
+int aha_hip_quantize_mxfp4(const void* W, int32_t N, int32_t K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, void* stream);
+int aha_hip_gemv_rows_mxfp4(const void* q, const uint32_t* scales, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi,
                             const void* residual, float* logits, uint32_t* argmax_out, void* stream);
 /* aha_hip_attn_decode_batch: the fused decode attention block (QKNormAttention::forward, modules.rs:538-577, without o_proj) of `rows`
  * sequences in one launch.  qkv (rows, (nh + 2kvh) * 128) bf16; q_norm_w / k_norm_w (128) bf16; rope (rows, 128) f32 cos | sin, bf16

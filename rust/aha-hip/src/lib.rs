@@ -69,6 +69,7 @@ pub mod sys {
     pub const AHA_SAMPLE_NEED_LOGITS: i32 = 1;
     pub const AHA_WQ_NONE: i32 = 0;
     pub const AHA_WQ_MXFP8_E4M3: i32 = 1;
+    pub const AHA_WQ_MXFP4_E2M1: i32 = 2;
     pub const AHA_WQ_LM_HEAD: u32 = 1;
 
     /// `aha_sampling_params`: the Options of `GenerationContext::new` (common/generate.rs:21-53); same fields, same order as the
@@ -665,6 +666,29 @@ pub mod sys {
             argmax_out: *mut u32,
             stream: *mut std::ffi::c_void,
         ) -> i32;
+        pub fn aha_hip_quantize_mxfp4(
+            w: *const std::ffi::c_void,
+            n: i32,
+            k: i32,
+            q_out: *mut std::ffi::c_void,
+            scales_out: *mut u32,
+            w_roundtrip_out: *mut std::ffi::c_void,
+            stream: *mut std::ffi::c_void,
+        ) -> i32;
+        pub fn aha_hip_gemv_rows_mxfp4(
+            q: *const std::ffi::c_void,
+            scales: *const u32,
+            x: *const std::ffi::c_void,
+            y: *mut std::ffi::c_void,
+            r: i32,
+            n: i32,
+            k: i32,
+            epi: i32,
+            residual: *const std::ffi::c_void,
+            logits: *mut f32,
+            argmax_out: *mut u32,
+            stream: *mut std::ffi::c_void,
+        ) -> i32;
         pub fn aha_hip_logmel_batch(
             samples: *const f32,
             n_samples: *const i64,
@@ -707,6 +731,9 @@ impl std::error::Error for Error {}
 pub enum WeightFormat {
     /// OCP microscaling FP8: E4M3 elements, one E8M0 scale per 32 consecutive k
     Mxfp8E4m3 = 1,
+    /// OCP microscaling FP4: E2M1 elements, two to a byte, one E8M0 scale per 32 consecutive k.  Batched decode only: single-sequence
+    /// decode of such a model runs the bf16 matvec on the dequantised matrices.
+    Mxfp4E2m1 = 2,
 }
 
 fn check(rc: i32) -> Result<(), Error> {
@@ -923,7 +950,8 @@ impl Model {
     /// (`aha_hip_model_quantize_weights`): the batched decode then streams 1.03 bytes per weight instead of 2, with the bits it would
     /// compute from the dequantised bf16 matrices, which every other path goes on reading.  Single-sequence decode (`forward_step`,
     /// `decode_greedy`, the generate loops) reads the copies too where that measured faster (matrices of 2^24 elements or more in the kernel's FAST form), bit-identical
-    /// to the bf16 matvec.  Needs an empty cache and no engine.
+    /// to the bf16 matvec.  `WeightFormat::Mxfp4E2m1` keeps E2M1 nibbles instead, 0.53 bytes per weight for the batched decode; its
+    /// single-sequence decode stays on the bf16 matvec.  Needs an empty cache and no engine.
     pub fn quantize_weights(&mut self, format: WeightFormat, lm_head: bool) -> Result<(), Error> {
         let flags = if lm_head { sys::AHA_WQ_LM_HEAD } else { 0 };
         check(unsafe { sys::aha_hip_model_quantize_weights(self.model, format as i32, flags) })
@@ -933,7 +961,12 @@ impl Model {
     pub fn weight_format(&self) -> Result<Option<(WeightFormat, bool)>, Error> {
         let (mut f, mut fl) = (0i32, 0u32);
         check(unsafe { sys::aha_hip_model_weight_format(self.model, &mut f, &mut fl) })?;
-        Ok(if f == WeightFormat::Mxfp8E4m3 as i32 { Some((WeightFormat::Mxfp8E4m3, fl & sys::AHA_WQ_LM_HEAD != 0)) } else { None })
+        let lm_head = fl & sys::AHA_WQ_LM_HEAD != 0;
+        Ok(match f {
+            sys::AHA_WQ_MXFP8_E4M3 => Some((WeightFormat::Mxfp8E4m3, lm_head)),
+            sys::AHA_WQ_MXFP4_E2M1 => Some((WeightFormat::Mxfp4E2m1, lm_head)),
+            _ => None,
+        })
     }
 
     /// `Qwen3Embedding::embed_one` (qwen3_embedding/mod.rs:50-64) of every sequence, computed as packed prefills
