@@ -187,6 +187,16 @@ SIGNATURES = {
                                              C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
     "aha_hip_debug_prefill_attn_qfuse": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
+    "aha_hip_debug_layernorm_rows": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P]),
+    "aha_hip_debug_gemm_layernorm": (C.c_int, [_P, _P, _P] + [C.c_int32] * 6 + [_P, _P, C.c_int32, _P, _P, _P, C.c_float, _P]),
+    "aha_hip_debug_vit_pos_embed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
+    "aha_hip_debug_vit_rope": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "aha_hip_debug_scatter_rows": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "aha_hip_debug_audio_im2col1": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "aha_hip_debug_im2col_nhwc": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "aha_hip_debug_audio_tokens_gather": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "aha_hip_debug_sinus_pe_add": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "aha_hip_debug_kv_pack_generic": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "aha_hip_argmax": (C.c_int, [_P, C.c_int64, _P, _P]),
     "aha_hip_logmel": (C.c_int, [_P, C.c_int64, _P, _P]),
     "aha_hip_logmel_batch": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),

@@ -324,6 +324,18 @@ int aha_hip_debug_last_hidden(aha_model* m, float* out, size_t n) {
 }
 
 // ---- op-level entry points --------------------------------------------------------------------------------------
+namespace {
+struct DevBuf {   // a small device allocation freed on every return path
+  void* p = nullptr;
+  ~DevBuf() { if (p) hipFree(p); }
+  int upload(const void* host, size_t bytes) {
+    AHA_HIP_CHECK(hipMalloc(&p, bytes));
+    AHA_HIP_CHECK(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+    return AHA_OK;
+  }
+};
+}  // namespace
+
 int aha_hip_rmsnorm(const void* x, const void* w, void* y, int64_t rows, int32_t dim, float eps, void* stream) {
   if (!x || !w || !y || dim % 8 || dim > 8192) {
     set_error("rmsnorm: dim must be a multiple of 8 and <= 8192");
@@ -360,19 +372,10 @@ int aha_hip_gemv_gate_up(const void* Wg, const void* Wu, const void* x, void* y,
   return AHA_OK;
 }
 
-int aha_hip_gemm(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw,
-                 int32_t ldc, const void* bias, const void* residual, int32_t act, void* stream) {
-  if (!A || !W || !C || K % 8 || N % 8 || lda % 8 || ldw % 8 || ldc % 4 || act < 0 || act > ACT_SILU_MUL_PAIRS) {
-    set_error("gemm: K, N, lda, ldw must be multiples of 8 (16-byte rows), ldc of 4");
-    return AHA_ERR_INVALID;
-  }
-  if (act == ACT_SILU_MUL_PAIRS && (N % 32 || bias || residual)) {
-    set_error("gemm: ACT_SILU_MUL_PAIRS needs N % 32 == 0 and no bias/residual");
-    return AHA_ERR_INVALID;
-  }
-  GemmArgs g{};
-  g.A = A; g.W = W; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.bias = bias; g.residual = residual; g.act = act;
-  // op-level entry (tests, scripts): one split-K scratch per DEVICE, grown on demand; not for concurrent callers
+// the op-level GEMM entries' split-K scratch (aha_hip_gemm, aha_hip_debug_gemm_layernorm): one per DEVICE, grown on demand; not for
+// concurrent callers
+static void op_gemm_scratch(GemmArgs& g) {
+  const int M = g.M, N = g.N;
   struct OpScratch { void* ws = nullptr; size_t ws_bytes = 0; void* ctrs = nullptr; };
   static std::map<int, OpScratch> scratch_by_dev;
   static std::mutex scratch_mu;   // the map is reachable from several devices / threads; a device's scratch itself is still one caller at a time
@@ -392,10 +395,255 @@ int aha_hip_gemm(const void* A, const void* W, void* C, int32_t M, int32_t N, in
   g.workspace = sc.ws;
   g.workspace_bytes = sc.ws_bytes;
   g.sk_counters = sc.ws ? sc.ctrs : nullptr;
-  scratch_lk.unlock();   // (std::map nodes are stable: `sc` stays valid)
+}
+
+int aha_hip_gemm(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw,
+                 int32_t ldc, const void* bias, const void* residual, int32_t act, void* stream) {
+  if (!A || !W || !C || K % 8 || N % 8 || lda % 8 || ldw % 8 || ldc % 4 || act < 0 || act > ACT_SILU_MUL_PAIRS) {
+    set_error("gemm: K, N, lda, ldw must be multiples of 8 (16-byte rows), ldc of 4");
+    return AHA_ERR_INVALID;
+  }
+  if (act == ACT_SILU_MUL_PAIRS && (N % 32 || bias || residual)) {
+    set_error("gemm: ACT_SILU_MUL_PAIRS needs N % 32 == 0 and no bias/residual");
+    return AHA_ERR_INVALID;
+  }
+  GemmArgs g{};
+  g.A = A; g.W = W; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.bias = bias; g.residual = residual; g.act = act;
+  op_gemm_scratch(g);
   launch_gemm(g, (hipStream_t)stream);
   AHA_HIP_CHECK(hipGetLastError());
   return AHA_OK;
+}
+
+// ---- op-level test entries of the towers' row kernels (tests/test_tower_rows_gpu.py) ------------------------------------------------------
+int aha_hip_debug_layernorm_rows(const void* x, const void* w, const void* b, void* y, int64_t rows, int32_t dim, float eps, void* stream) {
+  if (!x || !w || !b || !y || rows < 1 || dim < 8 || dim % 8 || dim > 8192) {
+    set_error("debug_layernorm_rows: null pointer, rows < 1, or dim not a multiple of 8 in 8 .. 8192");
+    return AHA_ERR_INVALID;
+  }
+  launch_layernorm_rows(x, w, b, y, rows, dim, eps, (hipStream_t)stream);
+  AHA_HIP_CHECK(hipGetLastError());
+  return AHA_OK;
+}
+
+int aha_hip_debug_gemm_layernorm(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t ldc,
+                                 const void* bias, const void* residual, int32_t act, const void* norm_w, const void* norm_b, void* norm_out,
+                                 float eps, void* stream) {
+  if (!A || !W || !C || !norm_w || !norm_b || !norm_out) {
+    set_error("debug_gemm_layernorm: null pointer");
+    return AHA_ERR_INVALID;
+  }
+  if (M < 1 || N < 8 || K < 8 || K % 8 || N % 8 || N > 8192 || lda % 8 || ldw % 8 || lda < K || ldw < K || ldc != N || act < 0 || act >= ACT_SILU_MUL_PAIRS) {
+    set_error("debug_gemm_layernorm: M >= 1, K, N, lda, ldw multiples of 8, N <= 8192 (the LayerNorm's row), ldc == N (the norm reads C's rows "
+              "back to back), act below the gate+up pairs");
+    return AHA_ERR_INVALID;
+  }
+  GemmArgs g{};
+  g.A = A; g.W = W; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.bias = bias; g.residual = residual; g.act = act;
+  g.norm_w = norm_w; g.norm_b = norm_b; g.norm_out = norm_out; g.norm_eps = eps;
+  op_gemm_scratch(g);
+  launch_gemm(g, (hipStream_t)stream);
+  AHA_HIP_CHECK(hipGetLastError());
+  return AHA_OK;
+}
+
+namespace {
+// the grids of a tower test entry: t >= 1, h and w positive multiples of merge; -> the patch rows they describe, or -1
+int64_t check_vit_grids(const uint32_t* grid_thw, int32_t n_grids, int32_t merge) {
+  if (!grid_thw || n_grids < 1 || merge < 1) return -1;
+  int64_t N = 0;
+  for (int i = 0; i < n_grids; ++i) {
+    const uint32_t* g = grid_thw + 3 * i;
+    if (g[0] < 1 || g[1] < 1 || g[2] < 1 || g[1] % merge || g[2] % merge || g[0] > 4096 || g[1] > 4096 || g[2] > 4096) return -1;
+    N += (int64_t)g[0] * g[1] * g[2];
+    if (N > (1 << 24)) return -1;
+  }
+  return N;
+}
+void vit_host_tables(const uint32_t* grid_thw, int32_t n_grids, int G, int merge, VisHostTables* ht) {
+  std::vector<const uint32_t*> grids(n_grids);
+  for (int i = 0; i < n_grids; ++i) grids[i] = grid_thw + 3 * i;
+  vision_host_tables(grids.data(), grids.size(), G, merge, ht);
+}
+}  // namespace
+
+int aha_hip_debug_vit_pos_embed(const uint32_t* grid_thw, int32_t n_grids, int32_t G, int32_t merge, const void* table, void* x, int64_t N,
+                                int32_t D, int32_t* idx_out, float* wt_out, void* stream) {
+  API_GUARD_BEGIN
+  const char* who = "debug_vit_pos_embed: ";
+  auto bad = [&](const std::string& why) {
+    set_error(who + why);
+    return AHA_ERR_INVALID;
+  };
+  if (!grid_thw || !table || !x || !idx_out || !wt_out) return bad("null pointer");
+  if (G < 1 || G > 4096 || D < 8 || D % 8) return bad("the table side must be 1 .. 4096 and D a positive multiple of 8");
+  const int64_t rows = check_vit_grids(grid_thw, n_grids, merge);
+  if (rows < 0) return bad("n_grids, merge >= 1 and every grid t >= 1, h and w positive multiples of merge (each at most 4096, 2^24 rows in all)");
+  if (rows != N) return bad("the grids describe " + std::to_string(rows) + " rows, N is " + std::to_string(N));
+  VisHostTables ht;
+  vit_host_tables(grid_thw, n_grids, G, merge, &ht);
+  hipStream_t st = (hipStream_t)stream;
+  DevBuf d_idx, d_wt;
+  int rc;
+  if ((rc = d_idx.upload(ht.idx.data(), ht.idx.size() * 4)) || (rc = d_wt.upload(ht.wt.data(), ht.wt.size() * 4))) return rc;
+  launch_pos_embed_add(x, table, (const int32_t*)d_idx.p, (const float*)d_wt.p, N, D, st);
+  hipError_t e = hipGetLastError();
+  hipStreamSynchronize(st);   // (the tables above are freed on return)
+  AHA_HIP_CHECK(e);
+  memcpy(idx_out, ht.idx.data(), ht.idx.size() * 4);
+  memcpy(wt_out, ht.wt.data(), ht.wt.size() * 4);
+  return AHA_OK;
+  API_GUARD_END
+}
+
+int aha_hip_debug_vit_rope(const void* qkv, const uint32_t* grid_thw, int32_t n_grids, int32_t merge, const float* inv_freq,
+                           const uint64_t* page_ptrs, int32_t n_page_ptrs, int64_t N, int32_t nh, int32_t hd, float* cs_tab, void* q_out,
+                           int32_t* rowcol_out, int32_t* page_of_out, int32_t* slot_of_out, void* stream) {
+  API_GUARD_BEGIN
+  const char* who = "debug_vit_rope: ";
+  auto bad = [&](const std::string& why) {
+    set_error(who + why);
+    return AHA_ERR_INVALID;
+  };
+  if (!qkv || !grid_thw || !inv_freq || !page_ptrs || !cs_tab || !q_out || !rowcol_out || !page_of_out || !slot_of_out) return bad("null pointer");
+  if (hd != 72) return bad("head_dim must be 72");
+  if (nh < 1 || nh > 1024) return bad("nh outside 1 .. 1024");
+  const int64_t rows = check_vit_grids(grid_thw, n_grids, merge);
+  if (rows < 0) return bad("n_grids, merge >= 1 and every grid t >= 1, h and w positive multiples of merge (each at most 4096, 2^24 rows in all)");
+  if (rows != N) return bad("the grids describe " + std::to_string(rows) + " rows, N is " + std::to_string(N));
+  VisHostTables ht;
+  vit_host_tables(grid_thw, n_grids, 0, merge, &ht);
+  if (n_page_ptrs < 1 || ht.pages > n_page_ptrs)
+    return bad("the call writes " + std::to_string(ht.pages) + " pages, page_ptrs holds " + std::to_string(n_page_ptrs));
+  hipStream_t st = (hipStream_t)stream;
+  DevBuf d_rowcol, d_page_of, d_slot_of, d_first, d_cnt;
+  int rc;
+  if ((rc = d_rowcol.upload(ht.rowcol.data(), ht.rowcol.size() * 4)) || (rc = d_page_of.upload(ht.page_of.data(), ht.page_of.size() * 4)) ||
+      (rc = d_slot_of.upload(ht.slot_of.data(), ht.slot_of.size() * 4)) || (rc = d_first.upload(ht.page_first.data(), ht.page_first.size() * 4)) ||
+      (rc = d_cnt.upload(ht.page_cnt.data(), ht.page_cnt.size() * 4)))
+    return rc;
+  launch_vit_rope_table((const int32_t*)d_rowcol.p, inv_freq, (int)N, hd, cs_tab, st);
+  VitRopeArgs r{};
+  r.qkv = qkv; r.rowcol = (const int32_t*)d_rowcol.p; r.inv_freq = inv_freq; r.page_of = (const int32_t*)d_page_of.p;
+  r.slot_of = (const int32_t*)d_slot_of.p; r.q_out = q_out;
+  r.kv.page_ptrs = page_ptrs; r.kv.layer_off = 0; r.kv.kvh = nh; r.kv.d = hd;
+  r.N = (int)N; r.nh = nh; r.hd = hd; r.cs_tab = cs_tab;
+  r.page_first = (const int32_t*)d_first.p; r.page_cnt = (const int32_t*)d_cnt.p; r.n_pages = (int)ht.pages;
+  launch_vit_rope_pack(r, st);
+  hipError_t e = hipGetLastError();
+  hipStreamSynchronize(st);   // (the tables above are freed on return)
+  AHA_HIP_CHECK(e);
+  memcpy(rowcol_out, ht.rowcol.data(), ht.rowcol.size() * 4);
+  memcpy(page_of_out, ht.page_of.data(), ht.page_of.size() * 4);
+  memcpy(slot_of_out, ht.slot_of.data(), ht.slot_of.size() * 4);
+  return AHA_OK;
+  API_GUARD_END
+}
+
+int aha_hip_debug_scatter_rows(void* dst, const void* src, const int32_t* rows, int64_t n, int64_t dst_rows, int32_t D, int32_t add, void* stream) {
+  API_GUARD_BEGIN
+  const char* who = "debug_scatter_rows: ";
+  auto bad = [&](const std::string& why) {
+    set_error(who + why);
+    return AHA_ERR_INVALID;
+  };
+  if (!dst || !src || !rows) return bad("null pointer");
+  if (n < 1 || n > (1 << 24) || dst_rows < 1 || D < 8 || D % 8 || (add != 0 && add != 1)) return bad("n, dst_rows >= 1, D a positive multiple of 8, add 0 or 1");
+  for (int64_t i = 0; i < n; ++i)
+    if (rows[i] < 0 || rows[i] >= dst_rows) return bad("rows[" + std::to_string(i) + "] outside the destination");
+  hipStream_t st = (hipStream_t)stream;
+  DevBuf d_rows;
+  if (int rc = d_rows.upload(rows, (size_t)n * 4)) return rc;
+  launch_scatter_rows(dst, src, (const int32_t*)d_rows.p, n, D, add, st);
+  hipError_t e = hipGetLastError();
+  hipStreamSynchronize(st);
+  AHA_HIP_CHECK(e);
+  return AHA_OK;
+  API_GUARD_END
+}
+
+int aha_hip_debug_audio_im2col1(const float* feat, int64_t ld, const int32_t* chunks, int32_t C, int32_t mels, int32_t win, void* out, void* stream) {
+  API_GUARD_BEGIN
+  const char* who = "debug_audio_im2col1: ";
+  auto bad = [&](const std::string& why) {
+    set_error(who + why);
+    return AHA_ERR_INVALID;
+  };
+  if (!feat || !chunks || !out) return bad("null pointer");
+  if (C < 1 || C > (1 << 20) || mels < 1 || mels > 4096 || win < 1 || win > 4096 || ld < 1) return bad("C, mels, win, ld must be positive");
+  for (int i = 0; i < C; ++i) {   // {first column of the clip, its frames, window index}: the window starts inside the clip, the clip inside a row
+    const int64_t base = chunks[3 * i], F = chunks[3 * i + 1], ci = chunks[3 * i + 2];
+    if (base < 0 || F < 1 || base + F > ld || ci < 0 || ci * win >= F) return bad("chunk " + std::to_string(i) + " outside its clip, or its clip outside the feature rows");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  DevBuf d_chunks;
+  if (int rc = d_chunks.upload(chunks, (size_t)C * 3 * 4)) return rc;
+  launch_audio_im2col1(feat, (const int32_t*)d_chunks.p, out, ld, C, mels, win, st);
+  hipError_t e = hipGetLastError();
+  hipStreamSynchronize(st);
+  AHA_HIP_CHECK(e);
+  return AHA_OK;
+  API_GUARD_END
+}
+
+int aha_hip_debug_im2col_nhwc(const void* in, void* out, int32_t B, int32_t Hin, int32_t Win, int32_t Cin, void* stream) {
+  if (!in || !out || B < 1 || Hin < 1 || Win < 1 || Cin < 8 || Cin % 8 || (int64_t)B * Hin * Win > (1 << 26)) {
+    set_error("debug_im2col_nhwc: null pointer, a non-positive size, or Cin not a positive multiple of 8");
+    return AHA_ERR_INVALID;
+  }
+  launch_im2col_nhwc(in, out, B, Hin, Win, Cin, (hipStream_t)stream);
+  AHA_HIP_CHECK(hipGetLastError());
+  return AHA_OK;
+}
+
+int aha_hip_debug_audio_tokens_gather(const void* in, void* out, int32_t B, int32_t Fq, int32_t T, int32_t Cc, void* stream) {
+  if (!in || !out || B < 1 || Fq < 1 || T < 1 || Cc < 1 || (int64_t)B * Fq * T * Cc > ((int64_t)1 << 32)) {
+    set_error("debug_audio_tokens_gather: null pointer or a non-positive size");
+    return AHA_ERR_INVALID;
+  }
+  launch_audio_tokens_gather(in, out, B, Fq, T, Cc, (hipStream_t)stream);
+  AHA_HIP_CHECK(hipGetLastError());
+  return AHA_OK;
+}
+
+int aha_hip_debug_sinus_pe_add(void* x, int64_t rows, int32_t d, int32_t T, void* stream) {
+  if (!x || rows < 1 || d < 2 || d % 2 || T < 1) {
+    set_error("debug_sinus_pe_add: null pointer, rows or T < 1, or d not a positive even number");
+    return AHA_ERR_INVALID;
+  }
+  launch_sinus_pe_add(x, rows, d, T, (hipStream_t)stream);
+  AHA_HIP_CHECK(hipGetLastError());
+  return AHA_OK;
+}
+
+int aha_hip_debug_kv_pack_generic(const void* src, int64_t ld, int32_t k_off, int32_t v_off, const uint64_t* page_ptrs, int32_t n_page_ptrs,
+                                  int32_t N, int32_t nh, int32_t hd, const int32_t* slot_of, void* stream) {
+  API_GUARD_BEGIN
+  const char* who = "debug_kv_pack_generic: ";
+  auto bad = [&](const std::string& why) {
+    set_error(who + why);
+    return AHA_ERR_INVALID;
+  };
+  if (!src || !page_ptrs) return bad("null pointer");
+  if (N < 1 || N > (1 << 24) || nh < 1 || nh > 1024 || hd < 32 || hd % 32 || hd > 256 || n_page_ptrs < 1) return bad("N, nh, n_page_ptrs >= 1 and head_dim a multiple of 32 in 32 .. 256");
+  const int64_t width = (int64_t)nh * hd;
+  if (k_off < 0 || v_off < 0 || k_off + width > ld || v_off + width > ld) return bad("the K or V heads run past the row pitch ld");
+  const int64_t slots = (int64_t)n_page_ptrs * KV_PAGE_TOKENS;
+  if (!slot_of && N > slots) return bad("N rows need more pages than page_ptrs holds");
+  for (int n = 0; slot_of && n < N; ++n)   // slot_of (HOST here): the cache slot of every row
+    if (slot_of[n] < 0 || slot_of[n] >= slots) return bad("slot_of[" + std::to_string(n) + "] outside the pages of the call");
+  hipStream_t st = (hipStream_t)stream;
+  DevBuf d_slot;
+  if (slot_of)
+    if (int rc = d_slot.upload(slot_of, (size_t)N * 4)) return rc;
+  KvLayer kv{};
+  kv.page_ptrs = page_ptrs; kv.layer_off = 0; kv.kvh = nh; kv.d = hd;
+  launch_kv_pack_generic(src, ld, k_off, v_off, kv, N, nh, hd, st, (const int32_t*)d_slot.p);
+  hipError_t e = hipGetLastError();
+  hipStreamSynchronize(st);
+  AHA_HIP_CHECK(e);
+  return AHA_OK;
+  API_GUARD_END
 }
 
 int aha_hip_debug_gemm_grouped(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, int32_t ldc, int32_t act,
@@ -536,18 +784,6 @@ int aha_hip_debug_attn_prefill_segs(const void* q, const void* k, const void* v,
   return AHA_OK;
   API_GUARD_END
 }
-
-namespace {
-struct DevBuf {   // a small device allocation freed on every return path
-  void* p = nullptr;
-  ~DevBuf() { if (p) hipFree(p); }
-  int upload(const void* host, size_t bytes) {
-    AHA_HIP_CHECK(hipMalloc(&p, bytes));
-    AHA_HIP_CHECK(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
-    return AHA_OK;
-  }
-};
-}  // namespace
 
 int aha_hip_debug_prefill_rope(const void* qkv, const void* q_norm_w, const void* k_norm_w, const int32_t* pos, const int32_t* axis_map,
                                const float* inv_freq, const uint64_t* page_ptrs, int32_t n_page_ptrs, int32_t S, int32_t nh, int32_t kvh,

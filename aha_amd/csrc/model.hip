@@ -681,6 +681,21 @@ int model_create(aha_ctx* ctx, const aha_model_desc* desc, const aha_tensor_view
     set_error("hidden_size must be a multiple of 8 and intermediate_size of 16");
     return AHA_ERR_UNSUPPORTED;
   }
+  // the towers' LayerNorm (launch_layernorm_rows) holds a row of at most 8192 elements in 16-byte pieces: a wider or ragged row would be
+  // normalised over a prefix only
+  auto ln_covers = [](int64_t dim) { return dim > 0 && dim % 8 == 0 && dim <= 8192; };
+  if (cd.arch == AHA_ARCH_QWEN3VL && find_tensor(w, nw, "model.visual.patch_embed.proj.weight")) {
+    const int64_t m4 = (int64_t)cd.vis_hidden_size * cd.vis_spatial_merge_size * cd.vis_spatial_merge_size;
+    if (!ln_covers(cd.vis_hidden_size) || !ln_covers(m4)) {
+      set_error("vision tower: hidden_size " + std::to_string(cd.vis_hidden_size) + " and hidden_size * spatial_merge_size^2 = " + std::to_string(m4) +
+                " must be multiples of 8 and at most 8192 (the LayerNorm kernel's row)");
+      return AHA_ERR_UNSUPPORTED;
+    }
+  }
+  if (cd.arch == AHA_ARCH_QWEN3ASR && !ln_covers(cd.aud_d_model)) {
+    set_error("audio tower: d_model " + std::to_string(cd.aud_d_model) + " must be a multiple of 8 and at most 8192 (the LayerNorm kernel's row)");
+    return AHA_ERR_UNSUPPORTED;
+  }
   AHA_HIP_CHECK(hipSetDevice(ctx->device));
   aha_model* m = new aha_model();
   m->ctx = ctx;

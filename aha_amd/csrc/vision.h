@@ -27,6 +27,16 @@ int vision_check_request(const aha_model_desc& c, const VisRequest& r, int64_t* 
 // The tower over every request's images and videos in ONE pass (no image_embeds), the merged rows scattered to each request's
 // placeholder rows of x; vision_deepstack_add then adds to those rows.  vision_forward_and_scatter = one request at row 0.
 int vision_forward_requests(aha_model* m, const VisRequest* reqs, size_t n_reqs, void* x);
+// The host tables of a tower pass (vision_tower.hip vision_host_tables): idx / wt (4, N) corner indices and f32 weights of the position
+// embedding, rowcol (N, 2), page_of / slot_of (N), page_first / page_cnt (pages), and one attention segment per (grid, frame).
+struct VisSeg { int64_t start, len, page0; bool small; };
+struct VisHostTables {
+  int64_t N = 0, pages = 0;
+  std::vector<int32_t> idx, rowcol, page_of, slot_of, page_first, page_cnt;
+  std::vector<float> wt;
+  std::vector<VisSeg> segs;
+};
+void vision_host_tables(const uint32_t* const* grids, size_t n_grids, int G, int ms, VisHostTables* out);
 int vision_deepstack_add(aha_model* m, int layer, void* x);
 bool vision_has_deepstack(aha_model* m, int layer);   // vision_deepstack_add(layer) would change rows
 int vision_debug_embeds(aha_model* m, int which, float* out, size_t n);

@@ -339,6 +339,84 @@ int vision_check_request(const aha_model_desc& c, const VisRequest& r, int64_t* 
   return AHA_OK;
 }
 
+// The host index construction of a tower pass over `grids` (n_grids pointers to {t, h, w}; h and w multiples of ms, checked by the caller),
+// rows in grid order and merge-window order (t, bh, bw, ih, iw) inside a grid: the bilinear corner indices / weights of the position
+// embedding into a G x G table (G <= 0: left empty), the patch (row, col) of the 2-D rotary, and the attention segments -- every (grid,
+// frame) one, on pages of its own -- with each row's page / slot and each page's first row / row count.  Shared by
+// vision_forward_requests and the op-level test entries (capi.hip), so that those test what the tower runs.
+void vision_host_tables(const uint32_t* const* grids, size_t n_grids, int G, int ms, VisHostTables* out) {
+  VisHostTables& o = *out;
+  int64_t N = 0;
+  for (size_t im = 0; im < n_grids; ++im) N += (int64_t)grids[im][0] * grids[im][1] * grids[im][2];
+  o.N = N;
+  o.idx.assign(G > 0 ? 4 * N : 0, 0);
+  o.wt.assign(G > 0 ? 4 * N : 0, 0.f);
+  o.rowcol.assign(2 * N, 0);
+  o.page_of.assign(N, 0);
+  o.slot_of.assign(N, 0);
+  o.segs.clear();
+  std::vector<int32_t>&idx = o.idx, &rowcol = o.rowcol, &page_of = o.page_of, &slot_of = o.slot_of;
+  std::vector<float>& wt = o.wt;
+  int64_t off = 0, pages = 0;
+  const float Gm1 = (float)(G - 1);
+  for (size_t im = 0; im < n_grids; ++im) {
+    const uint32_t* g = grids[im];
+    const int t = g[0], h = g[1], w = g[2];
+    // linspace(0, G-1, h) in f32 (tensor_utils.rs:354-365), floor by u32 truncation, ceil clamped (model.rs:520-548)
+    auto lin = [&](int steps, std::vector<float>& val, std::vector<int>& fl, std::vector<int>& ce) {
+      val.resize(steps); fl.resize(steps); ce.resize(steps);
+      const float step = steps > 1 ? (Gm1 - 0.0f) / (float)(steps - 1) : 0.f;
+      for (int i = 0; i < steps; ++i) {
+        val[i] = steps > 1 ? 0.0f + (float)i * step : 0.0f;
+        fl[i] = (int)(uint32_t)val[i];
+        ce[i] = std::min(fl[i] + 1, G - 1);
+      }
+    };
+    std::vector<float> hv, wv;
+    std::vector<int> hf, hc, wf, wc;
+    if (G > 0) {
+      lin(h, hv, hf, hc);
+      lin(w, wv, wf, wc);
+    }
+    for (int ti = 0; ti < t; ++ti) {
+      o.segs.push_back({off + (int64_t)ti * h * w, (int64_t)h * w, pages, false});
+      for (int bh = 0; bh < h / ms; ++bh)
+        for (int bw = 0; bw < w / ms; ++bw)
+          for (int ih = 0; ih < ms; ++ih)
+            for (int iw = 0; iw < ms; ++iw) {
+              const int y = bh * ms + ih, xq = bw * ms + iw;
+              const int64_t local = (((int64_t)bh * (w / ms) + bw) * ms + ih) * ms + iw;
+              const int64_t nn = off + (int64_t)ti * h * w + local;
+              if (G > 0) {
+                const float dh = hv[y] - (float)hf[y], dw = wv[xq] - (float)wf[xq];
+                idx[0 * N + nn] = hf[y] * G + wf[xq];
+                idx[1 * N + nn] = hf[y] * G + wc[xq];
+                idx[2 * N + nn] = hc[y] * G + wf[xq];
+                idx[3 * N + nn] = hc[y] * G + wc[xq];
+                wt[0 * N + nn] = (1.0f - dh) * (1.0f - dw);
+                wt[1 * N + nn] = (1.0f - dh) * dw;
+                wt[2 * N + nn] = dh * (1.0f - dw);
+                wt[3 * N + nn] = dh * dw;
+              }
+              rowcol[2 * nn] = y;
+              rowcol[2 * nn + 1] = xq;
+              page_of[nn] = (int32_t)(pages + local / KV_PAGE_TOKENS);
+              slot_of[nn] = (int32_t)(local % KV_PAGE_TOKENS);
+            }
+      pages += ((int64_t)h * w + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
+    }
+    off += (int64_t)t * h * w;
+  }
+  o.pages = pages;
+  o.page_first.assign((size_t)pages, 0);
+  o.page_cnt.assign((size_t)pages, 0);
+  for (const VisSeg& sg : o.segs)
+    for (int64_t p = 0; p * KV_PAGE_TOKENS < sg.len; ++p) {
+      o.page_first[(size_t)(sg.page0 + p)] = (int32_t)(sg.start + p * KV_PAGE_TOKENS);
+      o.page_cnt[(size_t)(sg.page0 + p)] = (int32_t)std::min<int64_t>(KV_PAGE_TOKENS, sg.len - p * KV_PAGE_TOKENS);
+    }
+}
+
 // Every (image | video frame) of a list of requests through ONE tower pass.  Rows: request order, within a request image patches then
 // video patches; merged rows likewise, scattered to each request's placeholder rows (request row0 + its <|image_pad|> positions, then
 // its <|video_pad|> positions) of x_text.  forward_initial: one request at row 0; generate_batch_mm: the requests of a prefill pass.
@@ -375,56 +453,13 @@ int vision_forward_requests(aha_model* m, const VisRequest* reqs, size_t n_reqs,
     }
   }
   const int64_t n4 = N / (ms * ms);
-  std::vector<int32_t> idx(4 * N), rowcol(2 * N), page_of(N), slot_of(N);
-  std::vector<float> wt(4 * N);
-  struct Seg { int64_t start, len, page0; bool small; };
-  std::vector<Seg> segs;
-  int64_t off = 0, pages = 0;
-  const float Gm1 = (float)(v->G - 1);
-  for (size_t im = 0; im < grids.size(); ++im) {
-    const uint32_t* g = grids[im];
-    const int t = g[0], h = g[1], w = g[2];
-    // linspace(0, G-1, h) in f32 (tensor_utils.rs:354-365), floor by u32 truncation, ceil clamped (model.rs:520-548)
-    auto lin = [&](int steps, std::vector<float>& val, std::vector<int>& fl, std::vector<int>& ce) {
-      val.resize(steps); fl.resize(steps); ce.resize(steps);
-      const float step = steps > 1 ? (Gm1 - 0.0f) / (float)(steps - 1) : 0.f;
-      for (int i = 0; i < steps; ++i) {
-        val[i] = steps > 1 ? 0.0f + (float)i * step : 0.0f;
-        fl[i] = (int)(uint32_t)val[i];
-        ce[i] = std::min(fl[i] + 1, v->G - 1);
-      }
-    };
-    std::vector<float> hv, wv;
-    std::vector<int> hf, hc, wf, wc;
-    lin(h, hv, hf, hc);
-    lin(w, wv, wf, wc);
-    for (int ti = 0; ti < t; ++ti) {
-      segs.push_back({off + (int64_t)ti * h * w, (int64_t)h * w, pages, false});
-      for (int bh = 0; bh < h / ms; ++bh)
-        for (int bw = 0; bw < w / ms; ++bw)
-          for (int ih = 0; ih < ms; ++ih)
-            for (int iw = 0; iw < ms; ++iw) {
-              const int y = bh * ms + ih, xq = bw * ms + iw;
-              const int64_t local = (((int64_t)bh * (w / ms) + bw) * ms + ih) * ms + iw;
-              const int64_t nn = off + (int64_t)ti * h * w + local;
-              const float dh = hv[y] - (float)hf[y], dw = wv[xq] - (float)wf[xq];
-              idx[0 * N + nn] = hf[y] * v->G + wf[xq];
-              idx[1 * N + nn] = hf[y] * v->G + wc[xq];
-              idx[2 * N + nn] = hc[y] * v->G + wf[xq];
-              idx[3 * N + nn] = hc[y] * v->G + wc[xq];
-              wt[0 * N + nn] = (1.0f - dh) * (1.0f - dw);
-              wt[1 * N + nn] = (1.0f - dh) * dw;
-              wt[2 * N + nn] = dh * (1.0f - dw);
-              wt[3 * N + nn] = dh * dw;
-              rowcol[2 * nn] = y;
-              rowcol[2 * nn + 1] = xq;
-              page_of[nn] = (int32_t)(pages + local / KV_PAGE_TOKENS);
-              slot_of[nn] = (int32_t)(local % KV_PAGE_TOKENS);
-            }
-      pages += ((int64_t)h * w + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
-    }
-    off += (int64_t)t * h * w;
-  }
+  VisHostTables ht;   // (lives until the synchronise below: pageable)
+  vision_host_tables(grids.data(), grids.size(), v->G, ms, &ht);
+  const std::vector<int32_t>&idx = ht.idx, &rowcol = ht.rowcol, &page_of = ht.page_of, &slot_of = ht.slot_of;
+  const std::vector<int32_t>&page_first = ht.page_first, &page_cnt = ht.page_cnt;
+  const std::vector<float>& wt = ht.wt;
+  std::vector<VisSeg>& segs = ht.segs;
+  const int64_t pages = ht.pages;
   int rc;
   if ((rc = vision_ensure_scratch(m, (size_t)N, (size_t)pages))) return rc;
   GemmWorkspaceScope ws_scope(v->gemm_ws, v->gemm_ws_bytes, m->d_sk_ctrs);
@@ -457,12 +492,6 @@ int vision_forward_requests(aha_model* m, const VisRequest* reqs, size_t n_reqs,
   AHA_HIP_CHECK(hipMemcpyAsync(v->d_rowcol, rowcol.data(), rowcol.size() * 4, hipMemcpyHostToDevice, st));
   AHA_HIP_CHECK(hipMemcpyAsync(v->d_page_of, page_of.data(), page_of.size() * 4, hipMemcpyHostToDevice, st));
   AHA_HIP_CHECK(hipMemcpyAsync(v->d_slot_of, slot_of.data(), slot_of.size() * 4, hipMemcpyHostToDevice, st));
-  std::vector<int32_t> page_first((size_t)pages), page_cnt((size_t)pages);
-  for (const Seg& sg : segs)
-    for (int64_t p = 0; p * KV_PAGE_TOKENS < sg.len; ++p) {
-      page_first[(size_t)(sg.page0 + p)] = (int32_t)(sg.start + p * KV_PAGE_TOKENS);
-      page_cnt[(size_t)(sg.page0 + p)] = (int32_t)std::min<int64_t>(KV_PAGE_TOKENS, sg.len - p * KV_PAGE_TOKENS);
-    }
   AHA_HIP_CHECK(hipMemcpyAsync(v->d_page_first, page_first.data(), page_first.size() * 4, hipMemcpyHostToDevice, st));
   AHA_HIP_CHECK(hipMemcpyAsync(v->d_page_cnt, page_cnt.data(), page_cnt.size() * 4, hipMemcpyHostToDevice, st));
   // One attention launch per (image, frame) segment cannot fill the chip for the small images of chat (448 x 448: 784 patches = 13 q
@@ -493,7 +522,7 @@ int vision_forward_requests(aha_model* m, const VisRequest* reqs, size_t n_reqs,
   double small_flops = 0;
   std::vector<int32_t> stab;   // (lives until the synchronise below: pageable)
   if (seg_attn) {
-    for (Seg& s : segs) {
+    for (VisSeg& s : segs) {
       AttnPrefillArgs a = seg_args(s.start, s.page0);
       a.S = (int)s.len; a.kv_total = (int)s.len;
       if (attn_prefill_form_of(a) != 0) continue;
@@ -548,7 +577,7 @@ int vision_forward_requests(aha_model* m, const VisRequest* reqs, size_t n_reqs,
       ProfScope ps(m, "attn_vit", (double)small_rows * v->D * 8, small_flops);
       launch_attn_prefill(a, st);
     }
-    for (const Seg& s : segs) {
+    for (const VisSeg& s : segs) {
       if (s.small) continue;
       AttnPrefillArgs a = seg_args(s.start, s.page0);
       a.S = (int)s.len; a.kv_total = (int)s.len;

@@ -206,6 +206,118 @@ def debug_prefill_attn_qfuse(qkv: torch.Tensor, q_norm_w: torch.Tensor, rope_tab
     return o
 
 
+# ---- the vision and audio towers' row kernels (test entries; tests/test_tower_rows_gpu.py) --------------------------------------------------
+def debug_layernorm_rows(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float, out: Optional[torch.Tensor] = None,
+                         rows: Optional[int] = None) -> torch.Tensor:
+    """Test entry (aha_hip_debug_layernorm_rows): launch_layernorm_rows over the first `rows` rows (default: all) of x (R, dim) bf16 into
+    `out` (default: a new tensor)."""
+    _chk(x, w, b, out)
+    out = torch.empty_like(x) if out is None else out
+    check(lib().aha_hip_debug_layernorm_rows(_ptr(x), _ptr(w), _ptr(b), _ptr(out), x.shape[0] if rows is None else int(rows), x.shape[-1], eps,
+                                             _stream()))
+    return out
+
+
+def debug_gemm_layernorm(A: torch.Tensor, W: torch.Tensor, norm_w: torch.Tensor, norm_b: torch.Tensor, eps: float,
+                         bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, act: int = _lib.ACT_NONE,
+                         out: Optional[torch.Tensor] = None, norm_out: Optional[torch.Tensor] = None):
+    """Test entry (aha_hip_debug_gemm_layernorm): gemm() with LayerNorm(C; norm_w, norm_b, eps) riding on the call -> (C, norm_out), both
+    (M, N) bf16 (`out` / `norm_out`: pre-filled tensors to write into)."""
+    _chk(A, W, norm_w, norm_b, bias, residual, out, norm_out)
+    M, K = A.shape
+    N = W.shape[0]
+    Cm = torch.empty(M, N, dtype=torch.bfloat16, device=A.device) if out is None else out
+    Y = torch.empty(M, N, dtype=torch.bfloat16, device=A.device) if norm_out is None else norm_out
+    check(lib().aha_hip_debug_gemm_layernorm(_ptr(A), _ptr(W), _ptr(Cm), M, N, K, K, W.shape[1], N, _ptr(bias), _ptr(residual), act, _ptr(norm_w),
+                                             _ptr(norm_b), _ptr(Y), eps, _stream()))
+    return Cm, Y
+
+
+def _grids(grid_thw):
+    g = np.ascontiguousarray(np.asarray(grid_thw, dtype=np.uint32).reshape(-1, 3))
+    return g, int((g[:, 0].astype(np.int64) * g[:, 1] * g[:, 2]).sum())
+
+
+def debug_vit_pos_embed(x: torch.Tensor, table: torch.Tensor, grid_thw, G: int, merge: int = 2):
+    """Test entry (aha_hip_debug_vit_pos_embed): the tower's host corner tables for grid_thw [(t, h, w), ...] and launch_pos_embed_add on x
+    (N, D) bf16 IN PLACE with table (G * G, D) bf16.  -> (idx (4, N) int32, wt (4, N) f32) numpy."""
+    _chk(x, table)
+    g, N = _grids(grid_thw)
+    idx, wt = np.empty((4, max(N, 1)), np.int32), np.empty((4, max(N, 1)), np.float32)
+    check(lib().aha_hip_debug_vit_pos_embed(g.ctypes.data, g.shape[0], int(G), int(merge), _ptr(table), _ptr(x), x.shape[0], x.shape[1],
+                                            idx.ctypes.data, wt.ctypes.data, _stream()))
+    return idx[:, :N], wt[:, :N]
+
+
+def debug_vit_rope(qkv: torch.Tensor, grid_thw, inv_freq: torch.Tensor, page_ptrs: torch.Tensor, nh: int, q_out: torch.Tensor,
+                   merge: int = 2, hd: int = 72):
+    """Test entry (aha_hip_debug_vit_rope): launch_vit_rope_table, then launch_vit_rope_pack onto pages of the caller, with the tower's host
+    tables for grid_thw.  qkv (N, 3 * nh * 72) bf16, inv_freq (18) f32, page_ptrs (P,) int64 device page addresses, q_out (N, nh, 96) bf16
+    (pre-filled by the caller).  -> (cs_tab (N, 36, 2) f32 device tensor, rowcol (N, 2), page_of (N), slot_of (N) numpy int32)."""
+    _chk(qkv, inv_freq, page_ptrs, q_out)
+    assert inv_freq.dtype == torch.float32 and page_ptrs.dtype == torch.int64
+    g, N = _grids(grid_thw)
+    tab = torch.empty(max(N, 1), 36, 2, dtype=torch.float32, device=qkv.device)
+    rowcol, page_of, slot_of = np.empty((max(N, 1), 2), np.int32), np.empty(max(N, 1), np.int32), np.empty(max(N, 1), np.int32)
+    check(lib().aha_hip_debug_vit_rope(_ptr(qkv), g.ctypes.data, g.shape[0], int(merge), _ptr(inv_freq), _ptr(page_ptrs), page_ptrs.numel(),
+                                       qkv.shape[0], nh, hd, _ptr(tab), _ptr(q_out), rowcol.ctypes.data, page_of.ctypes.data, slot_of.ctypes.data,
+                                       _stream()))
+    return tab[:N], rowcol[:N], page_of[:N], slot_of[:N]
+
+
+def debug_scatter_rows(dst: torch.Tensor, src: torch.Tensor, rows, add: bool) -> None:
+    """Test entry (aha_hip_debug_scatter_rows): dst[rows[i]] = src[i] (or bf16(dst + src) with add), in place."""
+    _chk(dst, src)
+    r = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+    assert r.size == src.shape[0] and dst.shape[1] == src.shape[1]
+    check(lib().aha_hip_debug_scatter_rows(_ptr(dst), _ptr(src), r.ctypes.data, r.size, dst.shape[0], dst.shape[1], int(bool(add)), _stream()))
+
+
+def debug_audio_im2col1(feat: torch.Tensor, chunks, out: torch.Tensor, win: int = 100) -> torch.Tensor:
+    """Test entry (aha_hip_debug_audio_im2col1): feat (mels, ld) f32, chunks [(first column, F, window), ...] -> out (C * ceil(mels / 2) *
+    ceil(win / 2), 16) bf16 (pre-filled by the caller)."""
+    _chk(feat, out)
+    assert feat.dtype == torch.float32
+    c = np.ascontiguousarray(np.asarray(chunks, dtype=np.int32).reshape(-1, 3))
+    check(lib().aha_hip_debug_audio_im2col1(_ptr(feat), feat.shape[1], c.ctypes.data, c.shape[0], feat.shape[0], int(win), _ptr(out), _stream()))
+    return out
+
+
+def debug_im2col_nhwc(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """Test entry (aha_hip_debug_im2col_nhwc): x (B, Hin, Win, Cin) bf16 -> out (B * ceil(Hin / 2) * ceil(Win / 2), 9 * Cin)."""
+    _chk(x, out)
+    B, Hin, Win, Cin = x.shape
+    check(lib().aha_hip_debug_im2col_nhwc(_ptr(x), _ptr(out), B, Hin, Win, Cin, _stream()))
+    return out
+
+
+def debug_audio_tokens_gather(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """Test entry (aha_hip_debug_audio_tokens_gather): x (B, Fq, T, Cc) bf16 -> out (B * T, Cc * Fq)."""
+    _chk(x, out)
+    B, Fq, T, Cc = x.shape
+    check(lib().aha_hip_debug_audio_tokens_gather(_ptr(x), _ptr(out), B, Fq, T, Cc, _stream()))
+    return out
+
+
+def debug_sinus_pe_add(x: torch.Tensor, T: int, rows: Optional[int] = None) -> torch.Tensor:
+    """Test entry (aha_hip_debug_sinus_pe_add): x (R, d) bf16 IN PLACE over the first `rows` rows, row r at position r % T."""
+    _chk(x)
+    check(lib().aha_hip_debug_sinus_pe_add(_ptr(x), x.shape[0] if rows is None else int(rows), x.shape[1], int(T), _stream()))
+    return x
+
+
+def debug_kv_pack_generic(src: torch.Tensor, k_off: int, v_off: int, page_ptrs: torch.Tensor, nh: int, hd: int, slot_of=None,
+                          rows: Optional[int] = None) -> None:
+    """Test entry (aha_hip_debug_kv_pack_generic): the K / V heads at columns k_off / v_off of src (N, ld) bf16 -> pages of the caller;
+    slot_of: host ints, the cache slot of every row (None: row n in slot n)."""
+    _chk(src, page_ptrs)
+    assert page_ptrs.dtype == torch.int64
+    N = src.shape[0] if rows is None else int(rows)
+    s = None if slot_of is None else np.ascontiguousarray(np.asarray(slot_of, dtype=np.int32).reshape(N))
+    check(lib().aha_hip_debug_kv_pack_generic(_ptr(src), src.shape[1], int(k_off), int(v_off), _ptr(page_ptrs), page_ptrs.numel(), N, nh, hd,
+                                              None if s is None else s.ctypes.data, _stream()))
+
+
 def argmax(x: torch.Tensor) -> int:
     _chk(x)
     assert x.dtype == torch.float32

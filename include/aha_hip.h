@@ -953,6 +953,49 @@ int aha_hip_debug_prefill_attn_qfuse(const void* qkv, const void* q_norm_w, cons
                                      int32_t n_page_ptrs, int32_t S, int32_t nh, int32_t kvh, int32_t d, float eps, float scale,
                                      int32_t kv_offset, int32_t kv_total, int32_t S2, int32_t kv_offset2, int32_t kv_total2,
                                      const int32_t* segs, int32_t n_seg, int32_t with_kv0, void* o, void* stream);
+/* Test entries of the vision and audio towers' row kernels (tests/test_tower_rows_gpu.py): each launches the production launcher unchanged
+ * on buffers and page pools of the caller, and returns AHA_ERR_INVALID before any device work for a null pointer, a non-positive size, a
+ * width the kernel cannot cover, or a page-pointer array shorter than the pages the call writes.  Unless stated, pointers are device memory.
+ *
+ * LayerNorm rows (launch_layernorm_rows): y = LayerNorm(x; w, b, eps) over rows x dim bf16; dim a multiple of 8, at most 8192. */
+int aha_hip_debug_layernorm_rows(const void* x, const void* w, const void* b, void* y, int64_t rows, int32_t dim, float eps, void* stream);
+/* aha_hip_gemm with a LayerNorm of the finished rows riding on the call (GemmArgs::norm_w / norm_b / norm_out / norm_eps): norm_out (M, N)
+ * bf16.  The norm runs inside the split-K reduce pass where the plan has one and takes the width, else as a launch of its own.  ldc == N,
+ * N <= 8192, no gate+up epilogue.  Shares aha_hip_gemm's per-device scratch; aha_hip_debug_gemm_plan selects the plan. */
+int aha_hip_debug_gemm_layernorm(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t ldc,
+                                 const void* bias, const void* residual, int32_t act, const void* norm_w, const void* norm_b, void* norm_out,
+                                 float eps, void* stream);
+/* The ViT's learned position embedding: the tower's host construction of the bilinear corner indices and f32 weights for the HOST grids
+ * grid_thw (n_grids x {t, h, w}; h, w multiples of merge) into a G x G table, then launch_pos_embed_add on x (N, D) bf16 in place with
+ * table (G * G, D) bf16.  idx_out (4, N) int32 and wt_out (4, N) f32 are HOST arrays that receive the tables.  N must be the rows the grids
+ * describe, D a multiple of 8.  Synchronises the stream. */
+int aha_hip_debug_vit_pos_embed(const uint32_t* grid_thw, int32_t n_grids, int32_t G, int32_t merge, const void* table, void* x, int64_t N,
+                                int32_t D, int32_t* idx_out, float* wt_out, void* stream);
+/* The ViT's rope stage: launch_vit_rope_table into cs_tab ((N, 36, 2) f32: bf16-rounded cos, sin), then launch_vit_rope_pack, with the
+ * tower's host tables for the HOST grids.  qkv (N, 3 * nh * 72) bf16, inv_freq (18) f32, page_ptrs: n_page_ptrs byte addresses of pages
+ * (nh K blocks of 64 x 96, then nh V blocks of 80 x 64) in memory the caller owns, at least one page per 64 rows of every (grid, frame).
+ * q_out (N, nh, 96) bf16.  rowcol_out (N, 2), page_of_out (N), slot_of_out (N) are HOST int32 arrays that receive the tables.  hd must be
+ * 72.  Synchronises the stream. */
+int aha_hip_debug_vit_rope(const void* qkv, const uint32_t* grid_thw, int32_t n_grids, int32_t merge, const float* inv_freq,
+                           const uint64_t* page_ptrs, int32_t n_page_ptrs, int64_t N, int32_t nh, int32_t hd, float* cs_tab, void* q_out,
+                           int32_t* rowcol_out, int32_t* page_of_out, int32_t* slot_of_out, void* stream);
+/* launch_scatter_rows: dst[rows[i], :] = src[i, :] (add 0) or bf16(dst + src) (add 1) for i < n; rows is a HOST array of indices below
+ * dst_rows, D a multiple of 8.  Synchronises the stream. */
+int aha_hip_debug_scatter_rows(void* dst, const void* src, const int32_t* rows, int64_t n, int64_t dst_rows, int32_t D, int32_t add, void* stream);
+/* The audio tower's staging kernels, one entry each.
+ * im2col1: feat (mels, ld) f32, chunks: C HOST triples {first column of the clip, its frames F, window index}; out (C * ceil(mels / 2) *
+ * ceil(win / 2), 16) bf16.  Synchronises the stream.
+ * im2col_nhwc: in (B, Hin, Win, Cin) bf16 -> out (B * ceil(Hin / 2) * ceil(Win / 2), 9 * Cin), Cin a multiple of 8.
+ * tokens_gather: in (B, Fq, T, Cc) bf16 -> out (B * T, Cc * Fq).
+ * sinus_pe_add: x (rows, d) bf16 in place, row r at position r % T.
+ * kv_pack_generic: K / V heads at columns k_off / v_off of src (N, ld) bf16 -> pages of the caller (nh K blocks of 64 x hd, then nh V
+ * blocks of hd x 64); slot_of: optional HOST array, the cache slot of every row (NULL: row n in slot n).  Synchronises the stream. */
+int aha_hip_debug_audio_im2col1(const float* feat, int64_t ld, const int32_t* chunks, int32_t C, int32_t mels, int32_t win, void* out, void* stream);
+int aha_hip_debug_im2col_nhwc(const void* in, void* out, int32_t B, int32_t Hin, int32_t Win, int32_t Cin, void* stream);
+int aha_hip_debug_audio_tokens_gather(const void* in, void* out, int32_t B, int32_t Fq, int32_t T, int32_t Cc, void* stream);
+int aha_hip_debug_sinus_pe_add(void* x, int64_t rows, int32_t d, int32_t T, void* stream);
+int aha_hip_debug_kv_pack_generic(const void* src, int64_t ld, int32_t k_off, int32_t v_off, const uint64_t* page_ptrs, int32_t n_page_ptrs,
+                                  int32_t N, int32_t nh, int32_t hd, const int32_t* slot_of, void* stream);
 /* V0-pre, host arithmetic: img_smart_resize (src/utils/img_utils.rs:294-331) -- the size Qwen3VLProcessor::process_img
  * (qwen3vl/processor.rs:159-165) resizes an image to: multiples of `factor` (patch * merge = 32), area within
  * [min_pixels, max_pixels] (shortest_edge / longest_edge of the preprocessor config).  AHA_ERR_INVALID when the aspect ratio

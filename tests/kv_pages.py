@@ -58,6 +58,28 @@ def slot_index(kvh):
     return _TABLES[kvh]
 
 
+def page_elems_of(nh, dqk, dv):
+    """Elements of a page whose K rows hold dqk dims (a multiple of 32: dqk / 32 fragments per 16 tokens) and whose V block holds dv dims (a
+    multiple of 16): the K block [nh][64 * dqk], then the V block [nh][dv * 64].  The ViT's pages are 96 / 80, the audio tower's 64 / 64."""
+    return nh * PAGE_TOKENS * (dqk + dv)
+
+
+_TABLES_OF = {}
+
+
+def slot_index_of(nh, dqk, dv):
+    """(64, nh * (dqk + dv)) int64: page element of [k (nh * dqk) | v (nh * dv)] of every token slot of a (dqk, dv) page;
+    slot_index_of(kvh, 128, 128) is slot_index(kvh)."""
+    key = (nh, dqk, dv)
+    if key not in _TABLES_OF:
+        assert dqk % 32 == 0 and dv % 16 == 0
+        ke = torch.tensor([[kpage_elem(t, e, dqk // 32) for e in range(dqk)] for t in range(PAGE_TOKENS)])
+        ve = torch.tensor([[vpage_elem(t, e) for e in range(dv)] for t in range(PAGE_TOKENS)])
+        heads = [ke + h * PAGE_TOKENS * dqk for h in range(nh)] + [ve + nh * PAGE_TOKENS * dqk + h * dv * PAGE_TOKENS for h in range(nh)]
+        _TABLES_OF[key] = torch.cat(heads, 1)
+    return _TABLES_OF[key]
+
+
 def pack_pages(k, v, kvh, out=None):
     """Token-major k, v (L, kvh * 128) -> page images (ceil(L / 64), 2 * kvh * 64 * 128), token i in slot i % 64 of page i // 64.  `out`:
     the pre-filled images to write into (default: zeros); the slots of tokens >= L keep what it holds."""

@@ -1,4 +1,7 @@
-"""-m gpu: every HIP kernel family against the oracle restatement on the same seeded inputs (through the C ABI).
+"""-m gpu: the text path's HIP kernel families (norms, matvecs, GEMMs, rope, attention, sampling stages) and the image / audio front ends against
+the oracle restatement on the same seeded inputs (through the C ABI).  The row-wise kernels of the vision and audio towers
+(aha_amd/csrc/kernels_vit.hip, kernels_audio.hip, the LayerNorm riding on a GEMM in kernels_gemm.hip) are held to references of their own in
+tests/test_tower_rows_gpu.py (CPU tier: tests/test_tower_rows_cpu.py).
 
 Tolerances (bf16 model dtype): a HIP op may differ from the oracle's op-granular bf16 result by at most a few bf16
 ulps of the output (f32 accumulation order, f32 vs bf16-rounded softmax probabilities); each test states its bound.
