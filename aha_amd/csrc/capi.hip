@@ -951,12 +951,16 @@ int aha_hip_attn_decode(const void* q, const void* k, const void* v, void* o, in
 }
 
 // ---- batched decode, op level (scratch allocated per call: test / measurement entries) ----
-int aha_hip_gemv_rows(const void* W, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi, const void* residual,
-                      float* logits, uint32_t* argmax_out, void* stream) {
-  API_GUARD_BEGIN
-  if (!W || !x || R < 1 || R > 32 || N < 1 || K < 8 || K % 8 || epi < 0 || epi > 3 || (epi == 1 && (!residual || !y)) ||
+// One body for the three weight forms: W and scales == nullptr for bf16 weights (K % 8 == 0), (q, scales) for an MXFP8 (mx == 8) or
+// MXFP4 (mx == 4) copy (K % 32 == 0).
+static int gemv_rows_op(int mx, const void* W, const uint32_t* scales, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi,
+                        const void* residual, float* logits, uint32_t* argmax_out, void* stream) {
+  const int kmul = mx ? 32 : 8;
+  if (!W || (mx && !scales) || !x || R < 1 || R > 32 || N < 1 || K < kmul || K % kmul || epi < 0 || epi > 3 || (epi == 1 && (!residual || !y)) ||
       ((epi == 0 || epi == 2) && !y) || (epi == 2 && N % 32) || (epi == 3 && (!logits || !argmax_out))) {
-    set_error("gemv_rows: bad arguments (1 <= R <= 32, K % 8 == 0, epi 0..3 with its outputs; epi 2 needs N % 32 == 0)");
+    if (!mx) set_error("gemv_rows: bad arguments (1 <= R <= 32, K % 8 == 0, epi 0..3 with its outputs; epi 2 needs N % 32 == 0)");
+    else set_error(std::string("gemv_rows_mxfp") + (mx == 8 ? "8" : "4") +
+                   ": bad arguments (q, scales, 1 <= R <= 32, K % 32 == 0, epi 0..3 with its outputs; epi 2 needs N % 32 == 0)");
     return AHA_ERR_INVALID;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -967,11 +971,13 @@ int aha_hip_gemv_rows(const void* W, const void* x, void* y, int32_t R, int32_t 
   AHA_HIP_CHECK(hipMalloc((void**)&bm, (size_t)R * tiles * 4));
   AHA_HIP_CHECK(hipMalloc((void**)&bi, (size_t)R * tiles * 4));
   GemvRowsArgs a{};
-  a.W = W; a.x = x; a.ldx = K; a.R = R; a.N = N; a.K = K; a.ws = ws;
+  a.W = mx ? nullptr : W; a.x = x; a.ldx = K; a.R = R; a.N = N; a.K = K; a.ws = ws;
   a.y = y; a.residual = residual; a.ldy = epi == 2 ? N / 2 : N;
   a.y_f32 = logits; a.ldf = N; a.blk_max = bm; a.blk_idx = bi;
   const GemvEpi e = epi == 0 ? GEMV_STORE : epi == 1 ? GEMV_RESIDUAL : epi == 2 ? GEMV_SILU_MUL : GEMV_LOGITS;
-  launch_gemv_rows(a, e, st);
+  if (mx == 8) launch_gemv_rows_mxfp8(a, W, scales, e, st);
+  else if (mx == 4) launch_gemv_rows_mxfp4(a, W, scales, e, st);
+  else launch_gemv_rows(a, e, st);
   if (epi == 3) launch_argmax_rows(bm, bi, tiles, R, argmax_out, st);
   hipError_t err = hipGetLastError();
   hipStreamSynchronize(st);
@@ -980,98 +986,52 @@ int aha_hip_gemv_rows(const void* W, const void* x, void* y, int32_t R, int32_t 
   hipFree(bi);
   AHA_HIP_CHECK(err);
   return AHA_OK;
+}
+
+int aha_hip_gemv_rows(const void* W, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi, const void* residual,
+                      float* logits, uint32_t* argmax_out, void* stream) {
+  API_GUARD_BEGIN
+  return gemv_rows_op(0, W, nullptr, x, y, R, N, K, epi, residual, logits, argmax_out, stream);
   API_GUARD_END
 }
 
 int aha_hip_gemv_rows_mxfp8(const void* q, const uint32_t* scales, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi,
                             const void* residual, float* logits, uint32_t* argmax_out, void* stream) {
   API_GUARD_BEGIN
-  if (!q || !scales || !x || R < 1 || R > 32 || N < 1 || K < 32 || K % 32 || epi < 0 || epi > 3 || (epi == 1 && (!residual || !y)) ||
-      ((epi == 0 || epi == 2) && !y) || (epi == 2 && N % 32) || (epi == 3 && (!logits || !argmax_out))) {
-    set_error("gemv_rows_mxfp8: bad arguments (q, scales, 1 <= R <= 32, K % 32 == 0, epi 0..3 with its outputs; epi 2 needs N % 32 == 0)");
-    return AHA_ERR_INVALID;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int tiles = gemv_rows_num_tiles(N);
-  float *ws = nullptr, *bm = nullptr;
-  uint32_t* bi = nullptr;
-  AHA_HIP_CHECK(hipMalloc((void**)&ws, gemv_rows_ws_floats(R, N, K) * 4));
-  AHA_HIP_CHECK(hipMalloc((void**)&bm, (size_t)R * tiles * 4));
-  AHA_HIP_CHECK(hipMalloc((void**)&bi, (size_t)R * tiles * 4));
-  GemvRowsArgs a{};
-  a.x = x; a.ldx = K; a.R = R; a.N = N; a.K = K; a.ws = ws;
-  a.y = y; a.residual = residual; a.ldy = epi == 2 ? N / 2 : N;
-  a.y_f32 = logits; a.ldf = N; a.blk_max = bm; a.blk_idx = bi;
-  const GemvEpi e = epi == 0 ? GEMV_STORE : epi == 1 ? GEMV_RESIDUAL : epi == 2 ? GEMV_SILU_MUL : GEMV_LOGITS;
-  launch_gemv_rows_mxfp8(a, q, scales, e, st);
-  if (epi == 3) launch_argmax_rows(bm, bi, tiles, R, argmax_out, st);
-  hipError_t err = hipGetLastError();
-  hipStreamSynchronize(st);
-  hipFree(ws);
-  hipFree(bm);
-  hipFree(bi);
-  AHA_HIP_CHECK(err);
-  return AHA_OK;
-  API_GUARD_END
-}
-
-int aha_hip_quantize_mxfp8(const void* W, int32_t N, int32_t K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, void* stream) {
-  API_GUARD_BEGIN
-  if (!W || !q_out || !scales_out || N < 1 || K < 32 || K % 32) {
-    set_error("quantize_mxfp8: bad arguments (W, q_out, scales_out, N >= 1, K a positive multiple of 32)");
-    return AHA_ERR_INVALID;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  launch_mxfp8_quantize(W, N, K, q_out, scales_out, w_roundtrip_out, st);
-  AHA_HIP_CHECK(hipGetLastError());
-  AHA_HIP_CHECK(hipStreamSynchronize(st));
-  return AHA_OK;
+  return gemv_rows_op(8, q, scales, x, y, R, N, K, epi, residual, logits, argmax_out, stream);
   API_GUARD_END
 }
 
 int aha_hip_gemv_rows_mxfp4(const void* q, const uint32_t* scales, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi,
                             const void* residual, float* logits, uint32_t* argmax_out, void* stream) {
   API_GUARD_BEGIN
-  if (!q || !scales || !x || R < 1 || R > 32 || N < 1 || K < 32 || K % 32 || epi < 0 || epi > 3 || (epi == 1 && (!residual || !y)) ||
-      ((epi == 0 || epi == 2) && !y) || (epi == 2 && N % 32) || (epi == 3 && (!logits || !argmax_out))) {
-    set_error("gemv_rows_mxfp4: bad arguments (q, scales, 1 <= R <= 32, K % 32 == 0, epi 0..3 with its outputs; epi 2 needs N % 32 == 0)");
+  return gemv_rows_op(4, q, scales, x, y, R, N, K, epi, residual, logits, argmax_out, stream);
+  API_GUARD_END
+}
+
+static int quantize_mx_op(int mx, const void* W, int32_t N, int32_t K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, void* stream) {
+  if (!W || !q_out || !scales_out || N < 1 || K < 32 || K % 32) {
+    set_error(std::string("quantize_mxfp") + (mx == 8 ? "8" : "4") +
+              ": bad arguments (W, q_out, scales_out, N >= 1, K a positive multiple of 32)");
     return AHA_ERR_INVALID;
   }
   hipStream_t st = (hipStream_t)stream;
-  const int tiles = gemv_rows_num_tiles(N);
-  float *ws = nullptr, *bm = nullptr;
-  uint32_t* bi = nullptr;
-  AHA_HIP_CHECK(hipMalloc((void**)&ws, gemv_rows_ws_floats(R, N, K) * 4));
-  AHA_HIP_CHECK(hipMalloc((void**)&bm, (size_t)R * tiles * 4));
-  AHA_HIP_CHECK(hipMalloc((void**)&bi, (size_t)R * tiles * 4));
-  GemvRowsArgs a{};
-  a.x = x; a.ldx = K; a.R = R; a.N = N; a.K = K; a.ws = ws;
-  a.y = y; a.residual = residual; a.ldy = epi == 2 ? N / 2 : N;
-  a.y_f32 = logits; a.ldf = N; a.blk_max = bm; a.blk_idx = bi;
-  const GemvEpi e = epi == 0 ? GEMV_STORE : epi == 1 ? GEMV_RESIDUAL : epi == 2 ? GEMV_SILU_MUL : GEMV_LOGITS;
-  launch_gemv_rows_mxfp4(a, q, scales, e, st);
-  if (epi == 3) launch_argmax_rows(bm, bi, tiles, R, argmax_out, st);
-  hipError_t err = hipGetLastError();
-  hipStreamSynchronize(st);
-  hipFree(ws);
-  hipFree(bm);
-  hipFree(bi);
-  AHA_HIP_CHECK(err);
+  if (mx == 8) launch_mxfp8_quantize(W, N, K, q_out, scales_out, w_roundtrip_out, st);
+  else launch_mxfp4_quantize(W, N, K, q_out, scales_out, w_roundtrip_out, st);
+  AHA_HIP_CHECK(hipGetLastError());
+  AHA_HIP_CHECK(hipStreamSynchronize(st));
   return AHA_OK;
+}
+
+int aha_hip_quantize_mxfp8(const void* W, int32_t N, int32_t K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, void* stream) {
+  API_GUARD_BEGIN
+  return quantize_mx_op(8, W, N, K, q_out, scales_out, w_roundtrip_out, stream);
   API_GUARD_END
 }
 
 int aha_hip_quantize_mxfp4(const void* W, int32_t N, int32_t K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, void* stream) {
   API_GUARD_BEGIN
-  if (!W || !q_out || !scales_out || N < 1 || K < 32 || K % 32) {
-    set_error("quantize_mxfp4: bad arguments (W, q_out, scales_out, N >= 1, K a positive multiple of 32)");
-    return AHA_ERR_INVALID;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  launch_mxfp4_quantize(W, N, K, q_out, scales_out, w_roundtrip_out, st);
-  AHA_HIP_CHECK(hipGetLastError());
-  AHA_HIP_CHECK(hipStreamSynchronize(st));
-  return AHA_OK;
+  return quantize_mx_op(4, W, N, K, q_out, scales_out, w_roundtrip_out, stream);
   API_GUARD_END
 }
 

@@ -342,8 +342,8 @@ void launch_gemv_rows_merge(const GemvRowsArgs& a, GemvEpi epi, int nks, hipStre
 //   q       (N, K) bytes, row-major: OCP E4M3 (e4m3fn) codes of w / 2^e, e the exponent of the element's block of 32 consecutive k
 //   scales  (N, ceil(K / 128)) u32: word (n, c) holds the E8M0 bytes e + 127 of row n's blocks 4c .. 4c + 3, block 4c + g in bits
 //           8g .. 8g + 7 -- the four lane groups of a column in chunk c of gemv_rows share one dword load; bytes of blocks past K are 127
-// launch_gemv_rows_mxfp8 is launch_gemv_rows with (q, scales) in place of a.W (ignored): bit-identical to launch_gemv_rows on
-// W' = q * 2^e.  launch_mxfp8_quantize writes q, scales and (optional, may be w itself) W'; launch_mxfp8_check ORs 1 into *flag when a
+// launch_gemv_rows_mxfp8 is launch_gemv_rows with (q, scales) in place of a.W (ignored) -- the same kernel body with another weight
+// form (gemv_rows_body.h) -- and bit-identical to launch_gemv_rows on W' = q * 2^e.  launch_mxfp8_quantize writes q, scales and (optional, may be w itself) W'; launch_mxfp8_check ORs 1 into *flag when a
 // weight is non-finite or would round past bf16's range (|w| >= 1.9375 * 2^127).
 struct WQuant {
   void* q = nullptr;
@@ -363,8 +363,8 @@ void debug_plan_gemv_mxfp8(int N, int K, GemvEpi epi, bool has_norm, int* out5);
 // MXFP4 weight copies (kernels_gemv_rows_fp4.hip, mxfp4.h): the same blocks and the same scale words as MXFP8, with
 //   q       (N, K / 2) bytes, row-major: OCP E2M1 codes (sign << 3 | index into {0, 0.5, 1, 1.5, 2, 3, 4, 6}) of w / 2^e, byte (n, k / 2)
 //           holds even k in bits 0..3 and odd k in bits 4..7 -- a lane's MX block of gemv_rows is one 16-byte load
-// launch_gemv_rows_mxfp4 is launch_gemv_rows with (q, scales) in place of a.W (ignored): bit-identical to launch_gemv_rows on
-// W' = q * 2^e.  launch_mxfp4_quantize writes q, scales and (optional, may be w itself) W'; launch_mxfp4_check ORs 1 into *flag when a
+// launch_gemv_rows_mxfp4 is launch_gemv_rows with (q, scales) in place of a.W (ignored) -- the third weight form of the one kernel body
+// (gemv_rows_body.h) -- and bit-identical to launch_gemv_rows on W' = q * 2^e.  launch_mxfp4_quantize writes q, scales and (optional, may be w itself) W'; launch_mxfp4_check ORs 1 into *flag when a
 // weight is non-finite or above 1.5 * 2^127 in magnitude (it would round past 6 * 2^125).  Batched decode only: there is no batch-1 kernel.
 void launch_gemv_rows_mxfp4(const GemvRowsArgs& a, const void* q, const uint32_t* scales, GemvEpi epi, hipStream_t st);
 void launch_mxfp4_quantize(const void* w, int N, int K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, hipStream_t st);

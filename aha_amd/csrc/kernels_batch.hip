@@ -4,6 +4,8 @@
 //   gemv_rows_kernel         out[R, N] = x[R, K] . W[N, K]^T for R <= 32: every weight element is read from HBM ONCE per launch
 //                            (non-temporal, straight to VGPRs) and multiplied with all R rows by v_mfma_f32_16x16x32_bf16 -- the rows
 //                            are the A operand, padded to 16 (one or two row tiles), 32 weight rows the B operand of two MFMAs.
+//                            gemv_rows_body (gemv_rows_body.h) with the GemvRowsBf16 weight form; the MXFP8 / MXFP4 kernels are the
+//                            same body with theirs.
 //   gemv_rows_merge_kernel   the fixed-order sum of the K-split partials + the epilogue (store / residual / SiLU.mul pairs / logits).
 //   argmax_rows_kernel       per-row pick of the logits epilogue's (max, index) partials -> the device token vector.
 //   gen_embed_kernel         the R token embeddings (tokens read from the device vector the previous step's pick wrote) + every row's
@@ -25,98 +27,21 @@
 #include "attn_decode_body.h"
 #include "common.h"
 #include "gemv_body.h"   // silu_f: the matvec's activation, for the same bits
+#include "gemv_rows_body.h"
 #include "kernels.h"
 
 namespace aha {
 
 namespace {
 
-typedef const __attribute__((address_space(1))) char* gcchar_t;
 typedef const __attribute__((address_space(1))) bf16_t* gcbf_t;
 typedef __attribute__((address_space(1))) bf16_t* gbf_t;
 typedef const __attribute__((address_space(1))) float* gcf_t;
-typedef __attribute__((address_space(1))) float* gf_t;
-// generic pointer -> explicitly global one (global loads / stores, never flat: see common.h gptr16_t)
-template <class T>
-__device__ __forceinline__ T gp(const void* p) { return reinterpret_cast<T>((uint64_t)(uintptr_t)p); }
 
-constexpr int GR_CHUNK = 128;   // k per chunk: 4 MFMA k-steps of 32; lane group q = lane / 16 holds k q*32 .. q*32+31 of the chunk
-constexpr int GR_NB = 32;       // weight rows (output columns) per block: two 16-wide MFMA column tiles
-
-// One wave: columns n0 .. n0+31 (two tiles) x chunks c0 .. c0+CW-1 of K, for NRT row tiles of x.  Lane l: column / row c = l & 15 of a
-// tile, k group q = l >> 4.  MFMA step j of chunk c covers k = c*128 + q*32 + j*8 .. +7 in lane group q: a fixed permutation of the k
-// order, the same for W and x.  Requests are issued x(c), W(c) in chunk order, all up front; the MFMAs of chunk c then wait only for
-// what was requested before chunk c+1.
 template <int CW, int NRT>
 __global__ __launch_bounds__(256, 2) void gemv_rows_kernel(GemvRowsArgs a) {
   __shared__ __attribute__((aligned(16))) float red[4 * 2 * NRT * 256];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 15, q = lane >> 4;
-  const int n0 = blockIdx.x * GR_NB, ks = blockIdx.y;
-  const int K = a.K, N = a.N, R = a.R;
-  const int nchunks = (K + GR_CHUNK - 1) / GR_CHUNK;
-  const int cbase = (ks * 4 + wave) * CW;
-  const gcchar_t W = gp<gcchar_t>(a.W);
-  const gcchar_t X = gp<gcchar_t>(a.x);
-  // weight rows of this lane in the two column tiles (rows past N re-read row N-1: finite values whose outputs are never stored)
-  const int64_t wr0 = (int64_t)min(n0 + c, N - 1) * K, wr1 = (int64_t)min(n0 + 16 + c, N - 1) * K;
-  u32x4_t wf[CW][2][4], xf[CW][NRT][4];
-#pragma unroll
-  for (int i = 0; i < CW; ++i) {
-    const int ch = cbase + i;
-    const int chc = min(ch, nchunks - 1);   // waves past the end of K re-read the last chunk; their x is zero
-#pragma unroll
-    for (int rt = 0; rt < NRT; ++rt) {
-      const int row = rt * 16 + c;
-      const int64_t xr = (int64_t)min(row, R - 1) * a.ldx;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int k = ch * GR_CHUNK + q * 32 + j * 8;
-        const int kc = min(chc * GR_CHUNK + q * 32 + j * 8, K - 8);
-        u32x4_t v = *reinterpret_cast<gptr16_t>(X + (xr + kc) * 2);
-        if (row >= R || k >= K) v = u32x4_t{0u, 0u, 0u, 0u};
-        xf[i][rt][j] = v;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int kc = min(chc * GR_CHUNK + q * 32 + j * 8, K - 8);
-      wf[i][0][j] = __builtin_nontemporal_load(reinterpret_cast<gptr16_t>(W + (wr0 + kc) * 2));
-      wf[i][1][j] = __builtin_nontemporal_load(reinterpret_cast<gptr16_t>(W + (wr1 + kc) * 2));
-    }
-  }
-  f32x4_t acc[2][NRT];
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-    for (int rt = 0; rt < NRT; ++rt) acc[nt][rt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < CW; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int rt = 0; rt < NRT; ++rt) acc[nt][rt] = mfma16(as_frag(xf[i][rt][j]), as_frag(wf[i][nt][j]), acc[nt][rt]);
-  // lane l holds out[row (l>>4)*4 + e][col l & 15] of each (column tile, row tile)
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-    for (int rt = 0; rt < NRT; ++rt)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) red[((wave * 2 + nt) * NRT + rt) * 256 + (q * 4 + e) * 16 + c] = acc[nt][rt][e];
-  __syncthreads();
-  // ((w0 + w1) + w2) + w3, then the f32 partial of this K split: ws[ks][row][n]
-  gf_t ws = gp<gf_t>(a.ws) + (int64_t)ks * a.R * a.ldws;
-  for (int e = tid; e < 2 * NRT * 256; e += 256) {
-    const int nt = e / (NRT * 256), rt = (e / 256) % NRT, m = (e >> 4) & 15, n = e & 15;
-    float s = red[e];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) s += red[w * 2 * NRT * 256 + e];
-    const int row = rt * 16 + m, col = n0 + nt * 16 + n;
-    if (row < R && col < N) ws[(int64_t)row * a.ldws + col] = s;
-  }
+  gemv_rows_body<GemvRowsBf16, CW, NRT>(a, a.W, nullptr, red);
 }
 
 // Sum of the K splits in slab order + the epilogue.  Block (bx, row): 256 output columns of one row.  The Linear output is rounded to
@@ -383,22 +308,10 @@ size_t gemv_rows_ws_floats(int R, int N, int K) {
   return (size_t)nks * R * N;
 }
 
-void launch_gemv_rows(const GemvRowsArgs& a0, GemvEpi epi, hipStream_t st) {
-  if (a0.R <= 0 || a0.N <= 0 || a0.K <= 0) return;
-  GemvRowsArgs a = a0;
-  a.ldws = a.N;
-  int cw, nks;
-  gemv_rows_plan(a.N, a.K, &cw, &nks);
-  const dim3 grid((unsigned)((a.N + GR_NB - 1) / GR_NB), (unsigned)nks);
-  const bool two = a.R > 16;
-  if (cw == 2) {
-    if (two) hipLaunchKernelGGL((gemv_rows_kernel<2, 2>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gemv_rows_kernel<2, 1>), grid, dim3(256), 0, st, a);
-  } else {
-    if (two) hipLaunchKernelGGL((gemv_rows_kernel<1, 2>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gemv_rows_kernel<1, 1>), grid, dim3(256), 0, st, a);
-  }
-  launch_gemv_rows_merge(a, epi, nks, st);
+void launch_gemv_rows(const GemvRowsArgs& a, GemvEpi epi, hipStream_t st) {
+  static constexpr void (*kern[2][2])(GemvRowsArgs) = {{gemv_rows_kernel<1, 1>, gemv_rows_kernel<1, 2>},
+                                                       {gemv_rows_kernel<2, 1>, gemv_rows_kernel<2, 2>}};
+  launch_gemv_rows_form(kern, a, epi, st);
 }
 
 // the second launch of a gemv_rows call: a.ws holds the nks slabs (a.ldws set)

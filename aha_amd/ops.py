@@ -413,26 +413,23 @@ def gemv_rows(W: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, resi
     return (logits, am.long()) if epi == GEMV_ROWS_LOGITS else y
 
 
-def quantize_mxfp8(W: torch.Tensor):
-    """The library's MXFP8 quantiser (aha_hip_quantize_mxfp8) on a GPU bf16 matrix (N, K), K % 32 == 0 -> (q (N, K) uint8, scales
-    (N, K / 32) uint8, W' (N, K) bf16) on the GPU, scales in the reference's order (aha_amd/quant.py quantize_mxfp8: the same bytes)."""
+def _quantize_mx(entry, W: torch.Tensor, k_per_byte: int):
+    """One of the library's MX quantisers on a GPU bf16 matrix (N, K): q holds k_per_byte elements per byte."""
     from . import quant
     _chk(W)
     N, K = W.shape
-    q = torch.empty(N, K, dtype=torch.uint8, device=W.device)
+    q = torch.empty(N, K // k_per_byte, dtype=torch.uint8, device=W.device)
     words = torch.empty(N, (K + 127) // 128, dtype=torch.int32, device=W.device)
     wr = torch.empty_like(W)
-    check(lib().aha_hip_quantize_mxfp8(_ptr(W), N, K, _ptr(q), _ptr(words), _ptr(wr), _stream()))
+    check(entry(_ptr(W), N, K, _ptr(q), _ptr(words), _ptr(wr), _stream()))
     return q, quant.scales_from_kernel(words, K).to(W.device), wr
 
 
-def gemv_rows_mxfp8(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, residual: Optional[torch.Tensor] = None):
-    """gemv_rows from the MXFP8 copy of W: q (N, K) uint8, scales (N, K / 32) uint8 in the reference's order (converted to the kernel's
-    words here).  Every output bit equals gemv_rows(W', x, epi, residual) for W' = dequantize_mxfp8(q, scales)."""
+def _gemv_rows_mx(entry, q: torch.Tensor, K: int, scales: torch.Tensor, x: torch.Tensor, epi: int, residual: Optional[torch.Tensor]):
+    """gemv_rows from an MX copy (q, scales) of a matrix with K columns, through the C entry of its format."""
     from . import quant
     _chk(q, x, residual)
-    N, K = q.shape
-    R = x.shape[0]
+    N, R = q.shape[0], x.shape[0]
     words = quant.scales_to_kernel(scales).to(x.device)
     y = logits = am = None
     if epi == GEMV_ROWS_LOGITS:
@@ -440,42 +437,37 @@ def gemv_rows_mxfp8(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, epi:
         am = torch.empty(R, dtype=torch.int32, device=x.device)
     else:
         y = torch.empty(R, N // 2 if epi == GEMV_ROWS_SILU_MUL else N, dtype=torch.bfloat16, device=x.device)
-    check(lib().aha_hip_gemv_rows_mxfp8(_ptr(q), _ptr(words), _ptr(x), _ptr(y), R, N, K, epi, _ptr(residual), _ptr(logits), _ptr(am), _stream()))
+    check(entry(_ptr(q), _ptr(words), _ptr(x), _ptr(y), R, N, K, epi, _ptr(residual), _ptr(logits), _ptr(am), _stream()))
     return (logits, am.long()) if epi == GEMV_ROWS_LOGITS else y
+
+
+def quantize_mxfp8(W: torch.Tensor):
+    """The library's MXFP8 quantiser (aha_hip_quantize_mxfp8) on a GPU bf16 matrix (N, K), K % 32 == 0 -> (q (N, K) uint8, scales
+    (N, K / 32) uint8, W' (N, K) bf16) on the GPU, scales in the reference's order (aha_amd/quant.py quantize_mxfp8: the same bytes)."""
+    return _quantize_mx(lib().aha_hip_quantize_mxfp8, W, 1)
+
+
+def gemv_rows_mxfp8(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, residual: Optional[torch.Tensor] = None):
+    """gemv_rows from the MXFP8 copy of W: q (N, K) uint8, scales (N, K / 32) uint8 in the reference's order (converted to the kernel's
+    words here).  Every output bit equals gemv_rows(W', x, epi, residual) for W' = dequantize_mxfp8(q, scales)."""
+    return _gemv_rows_mx(lib().aha_hip_gemv_rows_mxfp8, q, q.shape[1], scales, x, epi, residual)
 
 
 def quantize_mxfp4(W: torch.Tensor):
     """The library's MXFP4 quantiser (aha_hip_quantize_mxfp4) on a GPU bf16 matrix (N, K), K % 32 == 0 -> (q (N, K / 2) uint8 packed E2M1
     codes, scales (N, K / 32) uint8, W' (N, K) bf16) on the GPU, scales in the reference's order (aha_amd/quant.py quantize_mxfp4: the same
     bytes)."""
-    from . import quant
-    _chk(W)
-    N, K = W.shape
-    q = torch.empty(N, K // 2, dtype=torch.uint8, device=W.device)
-    words = torch.empty(N, (K + 127) // 128, dtype=torch.int32, device=W.device)
-    wr = torch.empty_like(W)
-    check(lib().aha_hip_quantize_mxfp4(_ptr(W), N, K, _ptr(q), _ptr(words), _ptr(wr), _stream()))
-    return q, quant.scales_from_kernel(words, K).to(W.device), wr
+    return _quantize_mx(lib().aha_hip_quantize_mxfp4, W, 2)
 
 
 def gemv_rows_mxfp4(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, residual: Optional[torch.Tensor] = None):
     """gemv_rows from the MXFP4 copy of W: q (N, K / 2) uint8 packed E2M1 codes, scales (N, K / 32) uint8 in the reference's order
     (converted to the kernel's words here).  Every output bit equals gemv_rows(W', x, epi, residual) for W' = dequantize_mxfp4(q, scales)."""
-    from . import quant
     _chk(q, x, residual)
     N, K = q.shape[0], q.shape[1] * 2
-    R = x.shape[0]
     if scales.shape != (N, K // 32) or x.shape[1] != K:
         raise ValueError(f"gemv_rows_mxfp4: q {tuple(q.shape)} wants scales ({N}, {K // 32}) and x (R, {K})")
-    words = quant.scales_to_kernel(scales).to(x.device)
-    y = logits = am = None
-    if epi == GEMV_ROWS_LOGITS:
-        logits = torch.empty(R, N, dtype=torch.float32, device=x.device)
-        am = torch.empty(R, dtype=torch.int32, device=x.device)
-    else:
-        y = torch.empty(R, N // 2 if epi == GEMV_ROWS_SILU_MUL else N, dtype=torch.bfloat16, device=x.device)
-    check(lib().aha_hip_gemv_rows_mxfp4(_ptr(q), _ptr(words), _ptr(x), _ptr(y), R, N, K, epi, _ptr(residual), _ptr(logits), _ptr(am), _stream()))
-    return (logits, am.long()) if epi == GEMV_ROWS_LOGITS else y
+    return _gemv_rows_mx(lib().aha_hip_gemv_rows_mxfp4, q, K, scales, x, epi, residual)
 
 
 def _gemv_epi_outputs(N: int, epi: int, device, out: Optional[torch.Tensor]):

@@ -289,7 +289,7 @@ def test_fp4_matvec_kernels_in_the_code_object(kernels, tmp_path):  # noqa: F811
     # global loads only, nothing through scratch, the same MFMA count as the bf16 kernel's instantiation, and the FP4 conversion
     shutil.copy(os.path.join(ROOT, "aha_amd", "csrc", "libaha_hip.so"), tmp_path / "lib.so")
     subprocess.run([f"{isa.LLVM}/llvm-objdump", "--offloading", "lib.so"], cwd=tmp_path, capture_output=True, check=True)
-    mfma, cvt, bad = {}, {}, {}
+    mfma, cvt, bad, count = {}, {}, {}, {}
     for o in sorted(glob.glob(str(tmp_path / "lib.so.*gfx950"))):
         dis = subprocess.run([f"{isa.LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", o], capture_output=True, text=True, check=True).stdout
         cur = None
@@ -298,10 +298,12 @@ def test_fp4_matvec_kernels_in_the_code_object(kernels, tmp_path):  # noqa: F811
             if m:
                 cur = m.group(1)
                 continue
-            if not cur or isa.family(cur) not in ("gemv_rows_mxfp4_kernel", "gemv_rows_kernel"):
+            if not cur or isa.family(cur) not in ("gemv_rows_mxfp4_kernel", "gemv_rows_mxfp8_kernel", "gemv_rows_kernel"):
                 continue
             op = line.split()[0] if line.split() else ""
             key = (isa.family(cur), tuple(int(x) for x in re.findall(r"Li(\d+)E", cur)[:2]))
+            if op in ("global_load_dwordx4", "global_load_dword", "s_barrier"):
+                count[key + (op,)] = count.get(key + (op,), 0) + 1
             if op.startswith("v_mfma"):
                 mfma[key] = mfma.get(key, 0) + 1
             if op == "v_cvt_scalef32_pk_bf16_fp4":
@@ -313,3 +315,11 @@ def test_fp4_matvec_kernels_in_the_code_object(kernels, tmp_path):  # noqa: F811
         for nrt in (1, 2):
             assert mfma[("gemv_rows_mxfp4_kernel", (cw, nrt))] == mfma[("gemv_rows_kernel", (cw, nrt))] == 8 * cw * nrt
             assert cvt[("gemv_rows_mxfp4_kernel", (cw, nrt))] == 32 * cw                # 4 per fragment, 4 fragments, 2 column tiles
+    # the three weight forms are one body (csrc/gemv_rows_body.h): per chunk 4 x loads per row tile and L 16-byte weight loads for each of
+    # the two column tiles, one scale dword per column tile for the MX forms, and the one barrier of the LDS reduction
+    for family, L in (("gemv_rows_kernel", 4), ("gemv_rows_mxfp8_kernel", 2), ("gemv_rows_mxfp4_kernel", 1)):
+        for cw in (1, 2):
+            for nrt in (1, 2):
+                assert count.get((family, (cw, nrt), "global_load_dwordx4"), 0) == cw * (4 * nrt + 2 * L), (family, cw, nrt)
+                assert count.get((family, (cw, nrt), "global_load_dword"), 0) == (0 if family == "gemv_rows_kernel" else 2 * cw), (family, cw, nrt)
+                assert count.get((family, (cw, nrt), "s_barrier"), 0) == 1, (family, cw, nrt)
