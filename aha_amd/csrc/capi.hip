@@ -1077,18 +1077,43 @@ int aha_hip_debug_fp8_single(aha_model* m, int on) {
   return AHA_OK;
 }
 
-int aha_hip_debug_plan_gemv_mxfp8(int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form,
-                                  int32_t* by_plan) {
+int aha_hip_debug_fp4_single(aha_model* m, int on) {
+  if (!m) {
+    set_error("debug_fp4_single: null model");
+    return AHA_ERR_INVALID;
+  }
+  if (on < 0 || on > 2) {
+    set_error("debug_fp4_single: on must be 0 (bf16), 1 (by plan) or 2 (every matrix with a copy)");
+    return AHA_ERR_INVALID;
+  }
+  m->fp4_single = on;
+  return AHA_OK;
+}
+
+// aha_hip_debug_plan_gemv_mxfp8 / _mxfp4 (mx: 8 / 4)
+static int debug_plan_gemv_mx(int mx, int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form,
+                              int32_t* by_plan) {
   if (!R || !U || !grid || N < 1 || K < 32 || K % 32 || epi < 0 || epi > 3 || (epi == 2 && N % 32)) {
-    set_error("debug_plan_gemv_mxfp8: bad argument (N >= 1, K a positive multiple of 32, epi 0..3, epi 2 needs N % 32 == 0)");
+    set_error(std::string("debug_plan_gemv_mxfp") + (mx == 8 ? "8" : "4") +
+              ": bad argument (N >= 1, K a positive multiple of 32, epi 0..3, epi 2 needs N % 32 == 0)");
     return AHA_ERR_INVALID;
   }
   int o[5];
-  debug_plan_gemv_mxfp8(epi == 2 ? N / 2 : N, K, (GemvEpi)epi, has_norm != 0, o);
+  (mx == 8 ? debug_plan_gemv_mxfp8 : debug_plan_gemv_mxfp4)(epi == 2 ? N / 2 : N, K, (GemvEpi)epi, has_norm != 0, o);
   *R = o[0]; *U = o[1]; *grid = o[2];
   if (form) *form = o[3] ? 1 + o[4] : 0;
-  if (by_plan) *by_plan = gemv_mxfp8_by_plan(N, K, (GemvEpi)epi) ? 1 : 0;
+  if (by_plan) *by_plan = (mx == 8 ? gemv_mxfp8_by_plan : gemv_mxfp4_by_plan)(N, K, (GemvEpi)epi) ? 1 : 0;
   return AHA_OK;
+}
+
+int aha_hip_debug_plan_gemv_mxfp8(int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form,
+                                  int32_t* by_plan) {
+  return debug_plan_gemv_mx(8, N, K, epi, has_norm, R, U, grid, form, by_plan);
+}
+
+int aha_hip_debug_plan_gemv_mxfp4(int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form,
+                                  int32_t* by_plan) {
+  return debug_plan_gemv_mx(4, N, K, epi, has_norm, R, U, grid, form, by_plan);
 }
 
 // ---- batch-1 matvec with an epilogue, op level (the partials of epi 3 are allocated per call: test / measurement entries) ----
@@ -1104,7 +1129,7 @@ const char* gemv_epi_args_bad(const void* w, const void* x, const void* y, int N
                               const float* logits, const uint32_t* argmax_out) {
   if (!w || !x) return "null matrix or x";
   if (N < 1) return "N must be at least 1";
-  if (K < kmul || K % kmul) return kmul == 32 ? "K must be a positive multiple of 32 (the MXFP8 block)" : "K must be a positive multiple of 8";
+  if (K < kmul || K % kmul) return kmul == 32 ? "K must be a positive multiple of 32 (the MX block)" : "K must be a positive multiple of 8";
   if (K > 32768) return "K must be at most 32768";
   if (epi < 0 || epi > 3) return "epi must be 0..3";
   if (epi != 3 && !y) return "null y";
@@ -1115,7 +1140,8 @@ const char* gemv_epi_args_bad(const void* w, const void* x, const void* y, int N
 }
 }  // namespace
 
-static int gemv_epi_run(const void* W, const void* q, const uint32_t* scales, const void* x, void* y, int32_t N, int32_t K,
+// q: the MXFP8 (mx == 8) or MXFP4 (mx == 4) copy in place of W
+static int gemv_epi_run(const void* W, int mx, const void* q, const uint32_t* scales, const void* x, void* y, int32_t N, int32_t K,
                         int32_t epi, const void* norm_w, float eps, const void* residual, float* logits, uint32_t* argmax_out, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   GemvArgs g{};
@@ -1125,14 +1151,15 @@ static int gemv_epi_run(const void* W, const void* q, const uint32_t* scales, co
   GemvPartials part;
   int tiles = 0;
   if (epi == 3) {
-    tiles = q ? gemv_mxfp8_num_tiles(N, K) : gemv_num_tiles(N, K);
+    tiles = !q ? gemv_num_tiles(N, K) : mx == 8 ? gemv_mxfp8_num_tiles(N, K) : gemv_mxfp4_num_tiles(N, K);
     AHA_HIP_CHECK(hipMalloc(&part.p[0], (size_t)tiles * 4));
     AHA_HIP_CHECK(hipMalloc(&part.p[1], (size_t)tiles * 4));
     g.blk_max = (float*)part.p[0];
     g.blk_idx = (uint32_t*)part.p[1];
   }
-  if (q) launch_gemv_mxfp8(g, q, scales, e, st);
-  else launch_gemv(g, e, st);
+  if (!q) launch_gemv(g, e, st);
+  else if (mx == 8) launch_gemv_mxfp8(g, q, scales, e, st);
+  else launch_gemv_mxfp4(g, q, scales, e, st);
   if (epi == 3) launch_argmax_partials(g.blk_max, g.blk_idx, tiles, argmax_out, st);
   hipError_t err = hipGetLastError();
   if (epi == 3) {   // the partials are freed on return
@@ -1150,7 +1177,7 @@ int aha_hip_gemv_epi(const void* W, const void* x, void* y, int32_t N, int32_t K
     set_error(std::string("gemv_epi: ") + bad);
     return AHA_ERR_INVALID;
   }
-  return gemv_epi_run(W, nullptr, nullptr, x, y, N, K, epi, norm_w, eps, residual, logits, argmax_out, stream);
+  return gemv_epi_run(W, 0, nullptr, nullptr, x, y, N, K, epi, norm_w, eps, residual, logits, argmax_out, stream);
   API_GUARD_END
 }
 
@@ -1165,7 +1192,22 @@ int aha_hip_gemv_mxfp8(const void* q, const uint32_t* scales, const void* x, voi
     set_error(std::string("gemv_mxfp8: ") + bad);
     return AHA_ERR_INVALID;
   }
-  return gemv_epi_run(nullptr, q, scales, x, y, N, K, epi, norm_w, eps, residual, logits, argmax_out, stream);
+  return gemv_epi_run(nullptr, 8, q, scales, x, y, N, K, epi, norm_w, eps, residual, logits, argmax_out, stream);
+  API_GUARD_END
+}
+
+int aha_hip_gemv_mxfp4(const void* q, const uint32_t* scales, const void* x, void* y, int32_t N, int32_t K, int32_t epi, const void* norm_w,
+                       float eps, const void* residual, float* logits, uint32_t* argmax_out, void* stream) {
+  API_GUARD_BEGIN
+  if (!scales) {
+    set_error("gemv_mxfp4: null scales");
+    return AHA_ERR_INVALID;
+  }
+  if (const char* bad = gemv_epi_args_bad(q, x, y, N, K, 32, epi, residual, logits, argmax_out)) {
+    set_error(std::string("gemv_mxfp4: ") + bad);
+    return AHA_ERR_INVALID;
+  }
+  return gemv_epi_run(nullptr, 4, q, scales, x, y, N, K, epi, norm_w, eps, residual, logits, argmax_out, stream);
   API_GUARD_END
 }
 

@@ -1,7 +1,8 @@
-// Body of the batch-1 matvec from MXFP8 weights (kernels_gemv_fp8.hip has the design notes): gemv_body (gemv_body.h) with the weight
-// operand read as one E4M3 byte per element plus one E8M0 scale byte per 32 k.  Lane roles, the LDS image of the activation vector, the
-// prologue, the tile walk, the two register buffers, the fma order and the epilogues' rounding points are gemv_body's, so that every
-// output bit equals gemv_kernel on W' = q * 2^e.
+// Body of the batch-1 matvec from MXFP8 and MXFP4 weights (kernels_gemv_fp8.hip has the design notes, kernels_gemv_fp4.hip the FP4 form's):
+// gemv_body (gemv_body.h) with the weight operand read as one E4M3 byte or one E2M1 nibble per element plus one E8M0 scale byte per 32 k.
+// Lane roles, the LDS image of the activation vector, the prologue, the tile walk, the two register buffers, the fma order and the
+// epilogues' rounding points are gemv_body's, so that every output bit equals gemv_kernel on W' = q * 2^e.  One text for both formats: the
+// weight form WF (below) names what differs, a lane's load and its conversion.
 #pragma once
 #include "gemv_body.h"   // xs_index, silu_f, GEMV_THREADS, GEMV_WAVES
 
@@ -14,8 +15,39 @@ __device__ __forceinline__ u32x2_t ld_nt8(const void* p) { return __builtin_nont
 // (returned as the byte it is: widening it where it is loaded puts a wait for it -- an `and 0xff` -- in front of the prologue)
 __device__ __forceinline__ uint8_t ld_nt1(const void* p) { return __builtin_nontemporal_load(reinterpret_cast<const uint8_t*>(p)); }
 
+// ld_nt8's 4-byte twin: a lane's 8 E2M1 codes of a chunk
+__device__ __forceinline__ uint32_t ld_nt4(const void* p) { return __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p)); }
+
+// Weight forms.  Per 512-k chunk a lane owns k = chunk * 512 + lane * 8 .. + 7 in either: load_t is what load() fetches for them from
+// the row at row(); convert() gives the 8 f32 operands, pairs in ascending k, with the block's scale 2^e folded in
+// by the hardware -- exact in f32 and bit for bit what lo_bf / hi_bf give on W' (a zero code keeps its sign; 2^e is never 0 or inf).
+struct GemvWFp8 {   // 8 E4M3 bytes
+  typedef u32x2_t load_t;
+  static __device__ __forceinline__ const uint8_t* row(const uint8_t* Q, size_t r, int K) { return Q + r * K; }
+  static __device__ __forceinline__ load_t load(const uint8_t* qp, int k) { return ld_nt8(qp + k); }
+  static __device__ __forceinline__ load_t zero() { return u32x2_t{0u, 0u}; }
+  static __device__ __forceinline__ void convert(const load_t w, const float sf, f32x2_t (&o)[4]) {
+    o[0] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[0], sf, false);
+    o[1] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[0], sf, true);
+    o[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[1], sf, false);
+    o[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[1], sf, true);
+  }
+};
+struct GemvWFp4 {   // 8 E2M1 codes in 4 bytes, the even k of a byte in bits 0..3 (kernels.h "MXFP4 weight copies")
+  typedef uint32_t load_t;
+  static __device__ __forceinline__ const uint8_t* row(const uint8_t* Q, size_t r, int K) { return Q + r * (K >> 1); }
+  static __device__ __forceinline__ load_t load(const uint8_t* qp, int k) { return ld_nt4(qp + (k >> 1)); }
+  static __device__ __forceinline__ load_t zero() { return 0u; }
+  static __device__ __forceinline__ void convert(const load_t w, const float sf, f32x2_t (&o)[4]) {
+    o[0] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sf, 0);
+    o[1] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sf, 1);
+    o[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sf, 2);
+    o[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sf, 3);
+  }
+};
+
 struct GemvFp8Args {
-  const void* q;          // (N, K) E4M3 bytes, row-major; GEMV_SILU_MUL: the fused matrix, 16-row blocks alternating gate / up (2N rows)
+  const void* q;          // (N, K) E4M3 bytes or (N, K / 2) E2M1 pairs, row-major; GEMV_SILU_MUL: the fused matrix, 16-row blocks alternating gate / up (2N rows)
   const uint8_t* scales;  // the scale words of kernels.h "MXFP8 weight copies" as bytes: byte k / 32 of a row of 4 * ceil(K / 128)
   const void* x;          // (K) bf16
   const void* norm_w;     // optional (K) bf16
@@ -30,7 +62,7 @@ struct GemvFp8Args {
 };
 
 // xs: LDS, (ceil(K/512)*512 + 16) floats.  PRO as in gemv_body: 1 / 2 = the straight-line prologue without / with norm weights (FAST only).
-template <int R, int U, int EPI, bool FAST, int PRO>
+template <class WF, int R, int U, int EPI, bool FAST, int PRO>
 __device__ __forceinline__ void gemv_fp8_body(const GemvFp8Args& a, float* xs, const int bid, const int nblk) {
   const int tid = threadIdx.x, lane = tid & 63;
   // wave-uniform on purpose: a wave's row pointers then live in SGPRs and every weight / scale load is the scalar-base form with the lane's
@@ -50,10 +82,11 @@ __device__ __forceinline__ void gemv_fp8_body(const GemvFp8Args& a, float* xs, c
   const uint8_t* Q = (const uint8_t*)a.q;
   const uint8_t* S = a.scales;
   const size_t srow = (size_t)((K + 127) >> 7) << 2;   // scale bytes per row
+  typedef typename WF::load_t load_t;
 
-  // Per 512-k chunk a lane owns k = chunk * 512 + lane * 8 .. + 7: 8 consecutive bytes of the row, one 8-byte load; four lanes share an
+  // Per 512-k chunk a lane owns k = chunk * 512 + lane * 8 .. + 7: 8 (FP4: 4) consecutive bytes of the row, one load; four lanes share an
   // MX block, whose scale is byte chunk * 16 + (lane >> 2) of the row's scales.  R*U*NW weight loads + as many scale-byte loads per item.
-  auto issue = [&](int gi, u32x2_t (&buf)[U][NW][R], uint8_t (&sc)[U][NW][R], bf16_t (&resv)[R]) {
+  auto issue = [&](int gi, load_t (&buf)[U][NW][R], uint8_t (&sc)[U][NW][R], bf16_t (&resv)[R]) {
     const int tile = bid + (gi / gpt) * nblk;
     const int c0 = (gi % gpt) * U;
     const int row0 = tile * ROWS_PER_TILE + wave * R;
@@ -68,19 +101,19 @@ __device__ __forceinline__ void gemv_fp8_body(const GemvFp8Args& a, float* xs, c
       const size_t fr = NW == 2 ? (size_t)(row >> 4) * 32 + (row & 15) : (size_t)row;
 #pragma unroll
       for (int m = 0; m < NW; ++m) {
-        const uint8_t* qp = Q + (fr + 16 * m) * K;
+        const uint8_t* qp = WF::row(Q, fr + 16 * m, K);
         const uint8_t* sp = S + (fr + 16 * m) * srow;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int k = ((c0 + u) << 9) + lane * 8;
           const int sb = ((c0 + u) << 4) + (lane >> 2);
           if (FAST) {
-            buf[u][m][r] = ld_nt8(qp + k);
+            buf[u][m][r] = WF::load(qp, k);
             sc[u][m][r] = ld_nt1(sp + sb);
             continue;
           }
           const bool ok = k < K;   // K % 32 == 0: the lane's 8 k are inside K or past it as a whole (a chunk past the last one: past it)
-          buf[u][m][r] = ok ? ld_nt8(qp + k) : u32x2_t{0u, 0u};
+          buf[u][m][r] = ok ? WF::load(qp, k) : WF::zero();
           sc[u][m][r] = ok ? ld_nt1(sp + sb) : (uint8_t)127;
         }
       }
@@ -96,7 +129,7 @@ __device__ __forceinline__ void gemv_fp8_body(const GemvFp8Args& a, float* xs, c
   static_assert(!SL || FAST, "the straight-line prologue is a form of the FAST kernel");
   const bool pre = SL || (nchunks << 6) <= XPRE * GEMV_THREADS;
   u32x4_t xpre[XPRE], npre[XPRE];
-  u32x2_t bufA[U][NW][R], bufB[U][NW][R];
+  load_t bufA[U][NW][R], bufB[U][NW][R];
   uint8_t scA[U][NW][R], scB[U][NW][R];
   bf16_t resA[R], resB[R];
   if (SL) {
@@ -200,7 +233,7 @@ __device__ __forceinline__ void gemv_fp8_body(const GemvFp8Args& a, float* xs, c
 #pragma unroll
     for (int r = 0; r < R; ++r) acc[m][r] = 0.f;
 
-  auto consume = [&](int gi, u32x2_t (&buf)[U][NW][R], uint8_t (&sc)[U][NW][R], bf16_t (&resv)[R]) {
+  auto consume = [&](int gi, load_t (&buf)[U][NW][R], uint8_t (&sc)[U][NW][R], bf16_t (&resv)[R]) {
     const int c0 = (gi % gpt) * U;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -211,19 +244,16 @@ __device__ __forceinline__ void gemv_fp8_body(const GemvFp8Args& a, float* xs, c
         for (int m = 0; m < NW; ++m)
 #pragma unroll
           for (int r = 0; r < R; ++r) {
-            const u32x2_t w = buf[u][m][r];
-            // byte * 2^e, exact in f32: bit for bit what lo_bf / hi_bf give on W' (a zero code keeps its sign; 2^e is never 0 or inf)
+            // code * 2^e
             const float sf = __uint_as_float((uint32_t)sc[u][m][r] << 23);
-            const f32x2_t w01 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[0], sf, false);
-            const f32x2_t w23 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[0], sf, true);
-            const f32x2_t w45 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[1], sf, false);
-            const f32x2_t w67 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w[1], sf, true);
+            f32x2_t w[4];
+            WF::convert(buf[u][m][r], sf, w);
             float s = acc[m][r];
             // gemv_body's order: elements 0..7 ascending, the activation as the first operand
-            s = fmaf(xlo.x, w01[0], s); s = fmaf(xlo.y, w01[1], s);
-            s = fmaf(xlo.z, w23[0], s); s = fmaf(xlo.w, w23[1], s);
-            s = fmaf(xhi.x, w45[0], s); s = fmaf(xhi.y, w45[1], s);
-            s = fmaf(xhi.z, w67[0], s); s = fmaf(xhi.w, w67[1], s);
+            s = fmaf(xlo.x, w[0][0], s); s = fmaf(xlo.y, w[0][1], s);
+            s = fmaf(xlo.z, w[1][0], s); s = fmaf(xlo.w, w[1][1], s);
+            s = fmaf(xhi.x, w[2][0], s); s = fmaf(xhi.y, w[2][1], s);
+            s = fmaf(xhi.z, w[3][0], s); s = fmaf(xhi.w, w[3][1], s);
             acc[m][r] = s;
           }
       }

@@ -365,10 +365,16 @@ void debug_plan_gemv_mxfp8(int N, int K, GemvEpi epi, bool has_norm, int* out5);
 //           holds even k in bits 0..3 and odd k in bits 4..7 -- a lane's MX block of gemv_rows is one 16-byte load
 // launch_gemv_rows_mxfp4 is launch_gemv_rows with (q, scales) in place of a.W (ignored) -- the third weight form of the one kernel body
 // (gemv_rows_body.h) -- and bit-identical to launch_gemv_rows on W' = q * 2^e.  launch_mxfp4_quantize writes q, scales and (optional, may be w itself) W'; launch_mxfp4_check ORs 1 into *flag when a
-// weight is non-finite or above 1.5 * 2^127 in magnitude (it would round past 6 * 2^125).  Batched decode only: there is no batch-1 kernel.
+// weight is non-finite or above 1.5 * 2^127 in magnitude (it would round past 6 * 2^125).
 void launch_gemv_rows_mxfp4(const GemvRowsArgs& a, const void* q, const uint32_t* scales, GemvEpi epi, hipStream_t st);
 void launch_mxfp4_quantize(const void* w, int N, int K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, hipStream_t st);
 void launch_mxfp4_check(const void* w, int64_t n_elems, int* flag, hipStream_t st);
+// Batch-1 matvec from the MXFP4 copies (kernels_gemv_fp4.hip): launch_gemv_mxfp8's twin, the same body with the other weight form, and
+// bit-identical to launch_gemv on W' = q * 2^e.  GEMV_LOGITS writes gemv_mxfp4_num_tiles(N, K) (max, index) partials, its own plan's grid.
+void launch_gemv_mxfp4(const GemvArgs& g, const void* q, const uint32_t* scales, GemvEpi epi, hipStream_t st);
+int gemv_mxfp4_num_tiles(int N, int K);
+bool gemv_mxfp4_by_plan(int N, int K, GemvEpi epi);   // as gemv_mxfp8_by_plan, for a model with MXFP4 copies
+void debug_plan_gemv_mxfp4(int N, int K, GemvEpi epi, bool has_norm, int* out5);   // host only: {R, U, grid, FAST, PRO}; N = output rows
 void gemv_rows_plan(int N, int K, int* chunks_per_wave, int* k_splits);
 int gemv_rows_num_tiles(int N);
 size_t gemv_rows_ws_floats(int R, int N, int K);

@@ -87,6 +87,7 @@ struct aha_model {
   bool fp8_rows = true;      // aha_hip_debug_fp8_rows: false = the bf16 matvec on W' although a copy (of either format) exists
   int fp8_single = 1;        // aha_hip_debug_fp8_single, the single-sequence matvec (enqueue_decode_step, enqueue_lm_head): 0 = bf16 on W',
                              // 1 = the FP8 kernel where the plan takes the shape (gemv_mxfp8_by_plan), 2 = wherever a copy exists; MXFP8 models only
+  int fp4_single = 1;        // aha_hip_debug_fp4_single: the same three values for an MXFP4 model and gemv_mxfp4_kernel (gemv_mxfp4_by_plan)
   // rope constants
   float* d_inv_freq = nullptr;
   int32_t* d_axis_map = nullptr;

@@ -861,7 +861,7 @@ int model_create(aha_ctx* ctx, const aha_model_desc* desc, const aha_tensor_view
   m->d_partial = (float*)p;
   if ((rc = dev_alloc(m, (size_t)c.vocab_size * 4, &p))) return fail(rc);
   m->d_logits = (float*)p;
-  const int nt = std::max(std::max(gemv_num_tiles(c.vocab_size, H), gemv_mxfp8_num_tiles(c.vocab_size, H)), 512);
+  const int nt = std::max(std::max(std::max(gemv_num_tiles(c.vocab_size, H), gemv_mxfp8_num_tiles(c.vocab_size, H)), gemv_mxfp4_num_tiles(c.vocab_size, H)), 512);
   if ((rc = dev_alloc(m, (size_t)nt * 4, &p))) return fail(rc);
   m->d_blk_max = (float*)p;
   if ((rc = dev_alloc(m, (size_t)nt * 4, &p))) return fail(rc);
@@ -978,22 +978,30 @@ static void gemv_row_parallel(aha_model* m, GemvArgs g);
 // One batch-1 matvec of the single-sequence path (g.N output rows: I for GEMV_SILU_MUL).  A matrix with an MXFP8 copy is read from it
 // where the plan takes the shape (gemv_mxfp8_by_plan: the matrices for which FP8 measured faster; the two kernels give the same bits, so
 // the choice is invisible in the output; aha_hip_debug_fp8_single overrides it either way) -- sharded models never have a copy.
-// Profile class gemv_fp8 at 1.03125 bytes per weight, gemv at 2; act_bytes: the activation traffic.  An MXFP4 copy is never read here:
-// there is no batch-1 kernel for it, so an MXFP4 model's single-sequence path runs the bf16 matvec on W' whatever the switch says.
+// Profile class gemv_fp8 at 1.03125 bytes per weight, gemv at 2; act_bytes: the activation traffic.  An MXFP4 copy goes the same way
+// through a switch, a plan and a class of its own: aha_hip_debug_fp4_single, gemv_mxfp4_by_plan, gemv_fp4 at 0.53125 bytes per weight.
 static bool fp8_single(const aha_model* m, const WQuant& wq, int rows, int K, GemvEpi epi) {
   return wq.q != nullptr && m->wq_format == AHA_WQ_MXFP8_E4M3 && m->tp_size <= 1 && (m->fp8_single == 2 || (m->fp8_single == 1 && gemv_mxfp8_by_plan(rows, K, epi)));
 }
+static bool fp4_single(const aha_model* m, const WQuant& wq, int rows, int K, GemvEpi epi) {
+  return wq.q != nullptr && m->wq_format == AHA_WQ_MXFP4_E2M1 && m->tp_size <= 1 && (m->fp4_single == 2 || (m->fp4_single == 1 && gemv_mxfp4_by_plan(rows, K, epi)));
+}
 static void decode_gemv(aha_model* m, const GemvArgs& g, GemvEpi epi, const WQuant& wq, double act_bytes) {
   const double weights = (epi == GEMV_SILU_MUL ? 2.0 : 1.0) * g.N * g.K;
-  const bool fp8 = fp8_single(m, wq, (epi == GEMV_SILU_MUL ? 2 : 1) * g.N, g.K, epi);
-  ProfScope ps(m, fp8 ? "gemv_fp8" : "gemv", weights * (fp8 ? 1.03125 : 2.0) + act_bytes, 2.0 * weights);
+  const int rows = (epi == GEMV_SILU_MUL ? 2 : 1) * g.N;
+  const bool fp8 = fp8_single(m, wq, rows, g.K, epi), fp4 = fp4_single(m, wq, rows, g.K, epi);
+  ProfScope ps(m, fp8 ? "gemv_fp8" : fp4 ? "gemv_fp4" : "gemv", weights * (fp8 ? 1.03125 : fp4 ? 0.53125 : 2.0) + act_bytes, 2.0 * weights);
   if (fp8) launch_gemv_mxfp8(g, wq.q, wq.scales, epi, m->stream);
+  else if (fp4) launch_gemv_mxfp4(g, wq.q, wq.scales, epi, m->stream);
   else if (epi == GEMV_RESIDUAL) gemv_row_parallel(m, g);
   else launch_gemv(g, epi, m->stream);
 }
 // (max, index) partials the lm_head matvec of enqueue_lm_head writes: the grid of the kernel that runs
 static int lm_head_partials(const aha_model* m) {
-  return fp8_single(m, m->q_lm_head, m->lm_rows, m->desc.hidden_size, GEMV_LOGITS) ? gemv_mxfp8_num_tiles(m->lm_rows, m->desc.hidden_size) : gemv_num_tiles(m->lm_rows, m->desc.hidden_size);
+  const int N = m->lm_rows, K = m->desc.hidden_size;
+  if (fp8_single(m, m->q_lm_head, N, K, GEMV_LOGITS)) return gemv_mxfp8_num_tiles(N, K);
+  if (fp4_single(m, m->q_lm_head, N, K, GEMV_LOGITS)) return gemv_mxfp4_num_tiles(N, K);
+  return gemv_num_tiles(N, K);
 }
 
 // final RMSNorm (qwen3/model.rs:186) fused into the lm_head matvec of the LAST position only (model.rs:187,142),
@@ -1531,7 +1539,8 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const float* __restrict_
 }
 
 // AHA_GEMV_TRACE=1: in-kernel timeline of the decode matvecs (launch-per-op path), dumped by fetch_outputs.  The bf16 kernel only:
-// gemv_mxfp8_kernel has no trace stamps, so a launch that decode_gemv sends to it leaves its slot as it was (gemv_trace_dump says so).
+// gemv_mxfp8_kernel and gemv_mxfp4_kernel have no trace stamps, so a launch that decode_gemv sends to either leaves its slot as it was
+// (gemv_trace_dump says so).
 static unsigned long long* gemv_trace_slot(aha_model* m, int launch_idx) {
   static const char* e = getenv("AHA_GEMV_TRACE");
   if (!e || !atoi(e)) return nullptr;
@@ -1552,6 +1561,9 @@ static void gemv_trace_dump(aha_model* m) {
   if (m->fp8_single && m->wq_format == AHA_WQ_MXFP8_E4M3 && L > 0 && m->layers[0].q_wqkv.q)
     fprintf(stderr, "[gemv trace] the model has MXFP8 copies: launches of gemv_mxfp8_kernel are not traced, their slots are stale or empty "
                     "(aha_hip_debug_fp8_single(m, 0) traces the bf16 kernel on the same weights)\n");
+  if (m->fp4_single && m->wq_format == AHA_WQ_MXFP4_E2M1 && L > 0 && m->layers[0].q_wqkv.q)
+    fprintf(stderr, "[gemv trace] the model has MXFP4 copies: launches of gemv_mxfp4_kernel are not traced, their slots are stale or empty "
+                    "(aha_hip_debug_fp4_single(m, 0) traces the bf16 kernel on the same weights)\n");
   for (int k = 0; k < 4; ++k) {
     double d[3][5] = {}, gap = 0, span = 0;
     int n = 0;

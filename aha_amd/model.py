@@ -598,8 +598,8 @@ class HipInferenceModel:
     def quantize_weights(self, fmt: str = "mxfp8", lm_head: bool = False) -> None:
         """Quantise the layer matrices (and lm_head with lm_head=True) to MXFP8 in place (aha_hip_model_quantize_weights): the batched decode
         then streams the FP8 copies; every other path reads the dequantised bf16 matrices.  aha_amd/quant.py is the reference quantiser.
-        fmt "mxfp4": MXFP4 copies (E2M1 nibbles, 0.53 bytes per weight) for the batched decode; the single-sequence decode of such a
-        model runs the bf16 matvec on the dequantised matrices."""
+        fmt "mxfp4": MXFP4 copies (E2M1 nibbles, 0.53 bytes per weight) for the batched decode and, on the matrices its plan takes
+        (debug_fp4_single), the single-sequence decode."""
         formats = {"mxfp8": _lib.AHA_WQ_MXFP8_E4M3, "mxfp4": _lib.AHA_WQ_MXFP4_E2M1}
         if fmt not in formats:
             raise ValueError(f"unknown weight format {fmt!r} (\"mxfp8\", \"mxfp4\")")
@@ -624,6 +624,12 @@ class HipInferenceModel:
         faster on); 2: on every matrix with a copy; False / 0: the bf16 kernel on W'.  The same bits in all three.  Profile class of the FP8
         launches: "gemv_fp8"."""
         check(lib().aha_hip_debug_fp8_single(self.handle, int(on)))
+
+    def debug_fp4_single(self, on=True) -> None:
+        """Test hook: debug_fp8_single's twin for a model with MXFP4 copies (the FP8 switch reads FP8 copies only).  True / 1 (the default):
+        the FP4 kernel on the matrices whose shape its plan takes; 2: on every matrix with a copy; False / 0: the bf16 kernel on W'.  The
+        same bits in all three.  Profile class of the FP4 launches: "gemv_fp4"."""
+        check(lib().aha_hip_debug_fp4_single(self.handle, int(on)))
 
     def set_profiling(self, on: bool):
         check(lib().aha_hip_set_profiling(self.handle, int(on)))

@@ -521,6 +521,37 @@ def gemv_mxfp8_by_plan(N: int, K: int, epi: int = GEMV_ROWS_STORE) -> bool:
     return bool(b.value)
 
 
+def gemv_mxfp4(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, norm_w: Optional[torch.Tensor] = None,
+               eps: float = 1e-6, residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """gemv_epi from the MXFP4 copy of W (aha_hip_gemv_mxfp4): q (N, K / 2) uint8 packed E2M1 codes, scales (N, K / 32) uint8 in the
+    reference's order (converted to the kernel's words here).  Every output bit, and the argmax, equals gemv_epi(W', ...) for W' =
+    dequantize_mxfp4(q, scales)."""
+    from . import quant
+    _chk(q, x, norm_w, residual, out)
+    N, K = q.shape[0], q.shape[1] * 2
+    if scales.shape != (N, K // 32) or x.shape[0] != K:
+        raise ValueError(f"gemv_mxfp4: q {tuple(q.shape)} wants scales ({N}, {K // 32}) and x ({K})")
+    words = quant.scales_to_kernel(scales).to(x.device)
+    y, logits, am = _gemv_epi_outputs(N, epi, x.device, out)
+    check(lib().aha_hip_gemv_mxfp4(_ptr(q), _ptr(words), _ptr(x), _ptr(y), N, K, epi, _ptr(norm_w), eps, _ptr(residual), _ptr(logits), _ptr(am),
+                                   _stream()))
+    return (logits, int(am.item())) if epi == GEMV_ROWS_LOGITS else y
+
+
+def plan_gemv_mxfp4(N: int, K: int, epi: int = GEMV_ROWS_STORE, has_norm: bool = False):
+    """Host only: (R, U, grid, form) gemv_mxfp4 picks for a matrix of N rows (aha_hip_debug_plan_gemv_mxfp4), form as plan_gemv_mxfp8's."""
+    r, u, g, f = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib().aha_hip_debug_plan_gemv_mxfp4(N, K, epi, int(has_norm), C.byref(r), C.byref(u), C.byref(g), C.byref(f), None))
+    return r.value, u.value, g.value, f.value
+
+
+def gemv_mxfp4_by_plan(N: int, K: int, epi: int = GEMV_ROWS_STORE) -> bool:
+    """Host only: does an MXFP4 model's single-sequence step read a matrix of N rows (gate+up: 2I) and K columns from its copy?"""
+    r, b = C.c_int32(), C.c_int32()
+    check(lib().aha_hip_debug_plan_gemv_mxfp4(N, K, epi, 0, C.byref(r), C.byref(r), C.byref(r), None, C.byref(b)))
+    return bool(b.value)
+
+
 def attn_decode_batch(qkv: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: torch.Tensor, rope: torch.Tensor, page_ptrs: torch.Tensor,
                       page0, kv_len, nh: int, kvh: int, eps: float, scale: float) -> torch.Tensor:
     """Fused decode attention of R sequences in one launch: qkv (R, (nh+2kvh)*128) bf16, rope (R, 128) f32, page_ptrs (P,) int64 device

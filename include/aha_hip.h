@@ -702,9 +702,10 @@ int aha_hip_debug_allreduce(aha_model* m, void* buf_f32_dev, size_t count);
  * format AHA_WQ_MXFP4_E2M1 does the same with MXFP4 copies (see aha_hip_quantize_mxfp4): W' = dequantised W in place, E2M1 nibbles and
  * the same scale words beside it, 0.53125 bytes per weight for the batched decode matvec (gemv_rows_mxfp4_kernel, the bits of the bf16
  * kernel on W'), +0.266 x the quantised matrices in memory, a weight refused when it is not finite or above 1.5 * 2^127 in magnitude.
- * There is no batch-1 MXFP4 kernel: an MXFP4 model's single-sequence decode (aha_hip_forward_step, aha_hip_decode_greedy, the generate
- * loops, the last-row lm_head) runs the bf16 matvec on W', at bf16 speed, whatever aha_hip_debug_fp8_single says.  A model holds copies
- * of one format: quantising with the other afterwards is AHA_ERR_STATE. */
+ * An MXFP4 model's single-sequence decode (aha_hip_forward_step, aha_hip_decode_greedy, the generate loops, the last-row lm_head) reads
+ * the same copies through a batch-1 kernel of its own (gemv_mxfp4_kernel, bit-identical to the bf16 kernel on W') on the matrices its
+ * plan takes (aha_hip_debug_fp4_single; profiles/weights_fp4_single.md has what was measured) and runs the bf16 matvec on W' on the
+ * others.  A model holds copies of one format: quantising with the other afterwards is AHA_ERR_STATE. */
 #define AHA_WQ_NONE 0
 #define AHA_WQ_MXFP8_E4M3 1
 #define AHA_WQ_MXFP4_E2M1 2
@@ -720,9 +721,16 @@ int aha_hip_debug_fp8_rows(aha_model* m, int on);
  * which the FP8 kernel measured faster, at least 2^24 elements and K a multiple of 512 * U, the FAST form (aha_hip_debug_plan_gemv_mxfp8
  * tells; profiles/weights_fp8_single.md) -- so small models, the test suite's among them, decode on bf16 unless the switch is 2;
  * 2: every matrix with a copy; 0: none (the bf16 kernel on W').  The bits are the same in all three.  Profile class of the FP8 launches:
- * gemv_fp8 (bf16: gemv).  AHA_ERR_INVALID: a null model or another value.  An MXFP4 model ignores the switch: its copies are never read
- * by the single-sequence path (value 2 included). */
+ * gemv_fp8 (bf16: gemv).  AHA_ERR_INVALID: a null model or another value.  FP8 copies only: an MXFP4 model ignores this switch (value 2
+ * included) and has aha_hip_debug_fp4_single. */
 int aha_hip_debug_fp8_single(aha_model* m, int on);
+/* aha_hip_debug_fp8_single's twin for a model with MXFP4 copies; it replaces "an MXFP4 model's single-sequence path always runs the bf16
+ * matvec".  on = 1 (the default): a matrix with a copy is read from it by gemv_mxfp4_kernel where that kernel's plan takes the shape
+ * (aha_hip_debug_plan_gemv_mxfp4 tells; the rule and the measurements: profiles/weights_fp4_single.md); 2: every matrix with a copy;
+ * 0: none (the bf16 kernel on W', what the path ran before the kernel existed).  The bits are the same in all three.  Profile class of
+ * the FP4 launches: gemv_fp4, at 0.53125 bytes per weight.  Sharded models have no copies.  AHA_ERR_INVALID: a null model or another
+ * value.  An MXFP8 model ignores it. */
+int aha_hip_debug_fp4_single(aha_model* m, int on);
 
 /* ---- introspection used by bench.py / tests ------------------------------------------------------------------ */
 size_t aha_hip_cache_len(const aha_model* m);
@@ -791,6 +799,10 @@ int aha_hip_debug_streamk_plan(int32_t M, int32_t N, int32_t K, int32_t tile_n, 
  * with norm weights (has_norm).  Names the instantiation gemv_mxfp8_kernel<R, U, epi, form != 0, max(form - 1, 0)>.  *by_plan (may be
  * NULL) = 1 if a model's single-sequence step reads a matrix of this shape from its copy by default (aha_hip_debug_fp8_single). */
 int aha_hip_debug_plan_gemv_mxfp8(int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form,
+                                  int32_t* by_plan);
+/* The same query for aha_hip_gemv_mxfp4 / the single-sequence matvec of an MXFP4 model (there was no such plan: the path had no FP4
+ * kernel): names gemv_mxfp4_kernel<R, U, epi, form != 0, max(form - 1, 0)>, *by_plan as aha_hip_debug_fp4_single reads it. */
+int aha_hip_debug_plan_gemv_mxfp4(int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form,
                                   int32_t* by_plan);
 /* CUs the persistent GEMM kernel leaves free (rounded so that its workgroup count stays a multiple of 8; 0 = use every CU; < 0 = take
  * AHA_GEMM_RESERVE_CUS from the environment).  Process-wide.  For tensor-parallel prefill: RCCL's kernels on the communication stream
@@ -866,7 +878,13 @@ int aha_hip_gemv_rows_mxfp8(const void* q, const uint32_t* scales, const void* x
  * w_roundtrip_out (N, K) bf16 = W', may be NULL or W itself.  The weights must be finite and at most 1.5 * 2^127 in magnitude (beyond
  * it a weight would round past 6 * 2^125; not checked here).
  * aha_hip_gemv_rows_mxfp4: aha_hip_gemv_rows with (q, scales) in place of W, K % 32 == 0: every output bit equals aha_hip_gemv_rows on
- * W'.  Argument checks as for aha_hip_gemv_rows_mxfp8. */
+ * W'.  Argument checks as for aha_hip_gemv_rows_mxfp8.
+ * aha_hip_gemv_mxfp4: aha_hip_gemv_mxfp8 with (q, scales) of aha_hip_quantize_mxfp4, q rows of K / 2 bytes; it replaces running
+ * aha_hip_gemv_epi on W' for a matrix kept as MXFP4.  The same contract: a lane reads the same 8 k of a 512-k chunk (one dword of 8 codes
+ * and their block's scale byte), code * 2^e is exact in f32 and equals the bf16 weight of W', everything else is the bf16 kernel's, so
+ * every output bit -- and the argmax -- equals aha_hip_gemv_epi on W'.  The same argument checks, messages prefixed "gemv_mxfp4:". */
+int aha_hip_gemv_mxfp4(const void* q, const uint32_t* scales, const void* x, void* y, int32_t N, int32_t K, int32_t epi, const void* norm_w,
+                       float eps, const void* residual, float* logits, uint32_t* argmax_out, void* stream);
 int aha_hip_quantize_mxfp4(const void* W, int32_t N, int32_t K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, void* stream);
 int aha_hip_gemv_rows_mxfp4(const void* q, const uint32_t* scales, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi,
                             const void* residual, float* logits, uint32_t* argmax_out, void* stream);

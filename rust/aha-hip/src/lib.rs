@@ -643,6 +643,33 @@ pub mod sys {
             argmax_out: *mut u32,
             stream: *mut std::ffi::c_void,
         ) -> i32;
+        pub fn aha_hip_debug_fp4_single(m: *mut AhaModel, on: i32) -> i32;
+        pub fn aha_hip_debug_plan_gemv_mxfp4(
+            n: i32,
+            k: i32,
+            epi: i32,
+            has_norm: i32,
+            r: *mut i32,
+            u: *mut i32,
+            grid: *mut i32,
+            form: *mut i32,
+            by_plan: *mut i32,
+        ) -> i32;
+        pub fn aha_hip_gemv_mxfp4(
+            q: *const std::ffi::c_void,
+            scales: *const u32,
+            x: *const std::ffi::c_void,
+            y: *mut std::ffi::c_void,
+            n: i32,
+            k: i32,
+            epi: i32,
+            norm_w: *const std::ffi::c_void,
+            eps: f32,
+            residual: *const std::ffi::c_void,
+            logits: *mut f32,
+            argmax_out: *mut u32,
+            stream: *mut std::ffi::c_void,
+        ) -> i32;
         pub fn aha_hip_quantize_mxfp8(
             w: *const std::ffi::c_void,
             n: i32,
@@ -950,11 +977,18 @@ impl Model {
     /// (`aha_hip_model_quantize_weights`): the batched decode then streams 1.03 bytes per weight instead of 2, with the bits it would
     /// compute from the dequantised bf16 matrices, which every other path goes on reading.  Single-sequence decode (`forward_step`,
     /// `decode_greedy`, the generate loops) reads the copies too where that measured faster (matrices of 2^24 elements or more in the kernel's FAST form), bit-identical
-    /// to the bf16 matvec.  `WeightFormat::Mxfp4E2m1` keeps E2M1 nibbles instead, 0.53 bytes per weight for the batched decode; its
-    /// single-sequence decode stays on the bf16 matvec.  Needs an empty cache and no engine.
+    /// to the bf16 matvec.  `WeightFormat::Mxfp4E2m1` keeps E2M1 nibbles instead, 0.53 bytes per weight; its single-sequence decode
+    /// has a kernel of its own (`gemv_mxfp4_kernel`, bit-identical again) under the switch `debug_fp4_single`.  Needs an empty cache
+    /// and no engine.
     pub fn quantize_weights(&mut self, format: WeightFormat, lm_head: bool) -> Result<(), Error> {
         let flags = if lm_head { sys::AHA_WQ_LM_HEAD } else { 0 };
         check(unsafe { sys::aha_hip_model_quantize_weights(self.model, format as i32, flags) })
+    }
+
+    /// The single-sequence matvec of a model with MXFP4 copies (`aha_hip_debug_fp4_single`): 0 the bf16 kernel on the dequantised
+    /// matrices, 1 (the default) the FP4 kernel on the matrices its plan takes, 2 on every matrix with a copy.  The same bits in all three.
+    pub fn debug_fp4_single(&mut self, on: i32) -> Result<(), Error> {
+        check(unsafe { sys::aha_hip_debug_fp4_single(self.model, on) })
     }
 
     /// `None`, or the format and the `lm_head` flag `quantize_weights` was called with.
