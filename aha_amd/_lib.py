@@ -225,6 +225,10 @@ SIGNATURES = {
     "aha_hip_engine_step": (C.c_int, [_P, C.POINTER(EngineEvent), C.c_size_t, C.POINTER(C.c_size_t), _P]),
     "aha_hip_engine_stats": (C.c_int, [_P, C.POINTER(EngineStats)]),
     "aha_hip_engine_debug_ctr_base": (C.c_int, [_P, C.c_uint32]),
+    "aha_hip_engine_submit_spec": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(SpecConfig), _P, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "aha_hip_engine_max_events": (C.c_size_t, [_P]),
+    "aha_hip_engine_spec_stats": (C.c_int, [_P, C.POINTER(SpecStats)]),
+    "aha_hip_engine_request_spec": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "aha_hip_generate_batch_logprobs": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.POINTER(SamplingParams), _P, C.c_size_t, C.c_size_t, _P, _P, _P,
                                                   C.POINTER(TokenLogprobs)]),
     "aha_hip_engine_submit_logprobs": (C.c_int, [_P, _P, C.c_size_t, _P, C.POINTER(SamplingParams), C.c_size_t, C.c_int32,

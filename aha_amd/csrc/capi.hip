@@ -1896,6 +1896,17 @@ int aha_hip_engine_submit_masked(aha_engine* e, const uint32_t* input_ids, size_
   return engine_submit(e, input_ids, n_ids, o, max_new, req_id);
   API_GUARD_END
 }
+int aha_hip_engine_submit_spec(aha_engine* e, const uint32_t* input_ids, size_t n_ids, const aha_mm_input* mm, size_t max_new,
+                               const aha_spec_config* spec, const uint32_t* prediction, size_t n_prediction, uint64_t* req_id) {
+  API_GUARD_BEGIN
+  if (int rc = spec_config_check(spec, "engine_submit_spec")) return rc;   // the config first, as aha_hip_generate_batch_spec checks it
+  SubmitOptions o;
+  o.mm = mm, o.spec = spec;
+  o.prediction = n_prediction ? prediction : nullptr, o.n_prediction = prediction ? n_prediction : 0;
+  if (int rc = submit_options_check("engine_submit_spec", e, o, -1)) return rc;
+  return engine_submit(e, input_ids, n_ids, o, max_new, req_id);
+  API_GUARD_END
+}
 int aha_hip_engine_set_mask(aha_engine* e, uint64_t req_id, const uint32_t* words, size_t n_words) {
   API_GUARD_BEGIN
   if (!e) {
@@ -1940,6 +1951,27 @@ int aha_hip_engine_stats(const aha_engine* e, aha_engine_stats* out) {
     return AHA_ERR_INVALID;
   }
   return engine_stats(e, out);
+  API_GUARD_END
+}
+size_t aha_hip_engine_max_events(const aha_engine* e) {
+  return e ? engine_max_events(e) : 0;
+}
+int aha_hip_engine_spec_stats(const aha_engine* e, aha_spec_stats* out) {
+  API_GUARD_BEGIN
+  if (!e || !out) {
+    set_error("engine_spec_stats: null engine / out");
+    return AHA_ERR_INVALID;
+  }
+  return engine_spec_stats(e, out);
+  API_GUARD_END
+}
+int aha_hip_engine_request_spec(const aha_engine* e, uint64_t req_id, size_t* n_proposed, size_t* n_accepted) {
+  API_GUARD_BEGIN
+  if (!e || !n_proposed || !n_accepted) {
+    set_error("engine_request_spec: null engine / n_proposed / n_accepted");
+    return AHA_ERR_INVALID;
+  }
+  return engine_request_spec(e, req_id, n_proposed, n_accepted);
   API_GUARD_END
 }
 int aha_hip_engine_debug_ctr_base(aha_engine* e, uint32_t base) {

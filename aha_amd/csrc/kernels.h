@@ -423,6 +423,10 @@ constexpr int SPEC_MAX_DRAFT = 15;
 constexpr int SPEC_SEQ_WORDS = 2, SPEC_SEQ_ROW0 = 0, SPEC_SEQ_NDRAFT = 1;
 constexpr int SPEC_OUT_WORDS = 2 + SPEC_MAX_DRAFT + 1, SPEC_OUT_COUNT = 0, SPEC_OUT_LAST_ROW = 1, SPEC_OUT_TOKENS = 2;
 void launch_spec_accept_rows(const uint32_t* argmax, const int32_t* row_tab, const int32_t* seq_tab, int n_seqs, uint32_t* out, hipStream_t st);
+// The same for the engine's row layout (every request's own row first, the draft rows behind them): seq_tab[s] = {own row, first draft
+// row, draft rows}; out[s] is the same record, the last row being the own row when no draft is confirmed
+constexpr int ENG_SEQ_WORDS = 3, ENG_SEQ_ROW = 0, ENG_SEQ_DRAFT0 = 1, ENG_SEQ_NDRAFT = 2;
+void launch_spec_accept_split(const uint32_t* argmax, const int32_t* row_tab, const int32_t* seq_tab, int n_seqs, uint32_t* out, hipStream_t st);
 int attn_decode_nsplit(int kv_len_after, int g, int max_nsplit);   // enqueue_decode_step's split rule
 
 struct StepState;  // model.h

@@ -16,6 +16,8 @@
 //                            its own, so that row i + 1 of a sequence finds row i's K/V in the pages; the attention launch that follows is
 //                            attn_decode_rows_kernel, the batch attention with the body's append compiled out.
 //   spec_accept_rows_kernel  per sequence, the longest draft prefix the step's argmax vector confirms -> its emitted tokens.
+//   spec_accept_split_kernel the same for the engine's row layout (aha_hip_engine_submit_spec): a request's own row among the step's mandatory
+//                            rows, its draft rows behind them.
 //
 // Row isolation (tests/test_generate_batch_gpu.py): every output element of gemv_rows is summed in an order that depends only on
 // (N, K) -- within a wave the MFMA chain over its chunks, across the 4 waves of a block ((w0 + w1) + w2) + w3 through LDS, across the
@@ -284,6 +286,35 @@ __global__ __launch_bounds__(64) void spec_accept_rows_kernel(const uint32_t* ar
   o[SPEC_OUT_LAST_ROW] = (uint32_t)(row0 + a);
 }
 
+// The engine's layout (model.hip engine_step): a request's own row sits among the step's mandatory rows, its k draft rows are rows
+// d0 .. d0 + k - 1 behind them.  Thread s: position 0 is the own row, position i >= 1 is row d0 + i - 1, whose input token (GEN_ROW_TOK) is
+// draft i.  The same rule and the same record as spec_accept_rows_kernel: a = the longest prefix with argmax(position i) == draft i + 1,
+// the emitted tokens are argmax(position 0 .. a), the last row is position a's.
+__global__ __launch_bounds__(64) void spec_accept_split_kernel(const uint32_t* argmax, const int32_t* row_tab, const int32_t* seq_tab, int n_seqs,
+                                                               uint32_t* out) {
+  typedef const __attribute__((address_space(1))) int32_t* gci32_t;
+  typedef const __attribute__((address_space(1))) uint32_t* gcu32_t;
+  typedef __attribute__((address_space(1))) uint32_t* gu32_t;
+  const int s = blockIdx.x * 64 + (int)threadIdx.x;
+  if (s >= n_seqs) return;
+  const gci32_t st = gp<gci32_t>(seq_tab) + (int64_t)s * ENG_SEQ_WORDS;
+  const gci32_t rt = gp<gci32_t>(row_tab);
+  const gcu32_t am = gp<gcu32_t>(argmax);
+  const gu32_t o = gp<gu32_t>(out) + (int64_t)s * SPEC_OUT_WORDS;
+  const int own = st[ENG_SEQ_ROW], d0 = st[ENG_SEQ_DRAFT0], k = min(st[ENG_SEQ_NDRAFT], SPEC_MAX_DRAFT);
+  int a = 0, row = own;
+  uint32_t tok = am[own];
+  o[SPEC_OUT_TOKENS] = tok;
+  while (a < k && tok == (uint32_t)rt[(int64_t)(d0 + a) * GEN_ROW_WORDS + GEN_ROW_TOK]) {
+    row = d0 + a;
+    ++a;
+    tok = am[row];
+    o[SPEC_OUT_TOKENS + a] = tok;
+  }
+  o[SPEC_OUT_COUNT] = (uint32_t)(a + 1);
+  o[SPEC_OUT_LAST_ROW] = (uint32_t)row;
+}
+
 }  // namespace
 
 // K-split plan of gemv_rows: a function of (N, K) only (row isolation).  Chunks per wave cw in {1, 2}; splits nks = ceil(chunks / 4cw);
@@ -363,6 +394,11 @@ void launch_kv_append_rows(const AttnDecodeBatchArgs& b, int rows, hipStream_t s
 void launch_spec_accept_rows(const uint32_t* argmax, const int32_t* row_tab, const int32_t* seq_tab, int n_seqs, uint32_t* out, hipStream_t st) {
   if (n_seqs <= 0) return;
   hipLaunchKernelGGL(spec_accept_rows_kernel, dim3((unsigned)((n_seqs + 63) / 64)), dim3(64), 0, st, argmax, row_tab, seq_tab, n_seqs, out);
+}
+
+void launch_spec_accept_split(const uint32_t* argmax, const int32_t* row_tab, const int32_t* seq_tab, int n_seqs, uint32_t* out, hipStream_t st) {
+  if (n_seqs <= 0) return;
+  hipLaunchKernelGGL(spec_accept_split_kernel, dim3((unsigned)((n_seqs + 63) / 64)), dim3(64), 0, st, argmax, row_tab, seq_tab, n_seqs, out);
 }
 
 }  // namespace aha

@@ -258,6 +258,10 @@ struct SubmitOptions {   // what an engine request may carry beyond its ids, max
   int32_t top_logprobs = -1;                     // -1: no logprobs
   const uint32_t* mask = nullptr;                // n_mask_words packed allowed-token words, or null
   size_t n_mask_words = 0;
+  // aha_hip_engine_submit_spec (spec set: checked by spec_config_check; max_draft 0: an ordinary greedy request)
+  const aha_spec_config* spec = nullptr;
+  const uint32_t* prediction = nullptr;          // n_prediction ids, or null: prompt lookup only
+  size_t n_prediction = 0;
 };
 int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const SubmitOptions& o, size_t max_new, uint64_t* req_id);
 int engine_set_mask(aha_engine* e, uint64_t req_id, const uint32_t* words, size_t n_words);
@@ -265,6 +269,9 @@ int engine_cancel(aha_engine* e, uint64_t req_id);
 int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, float* logits_out, aha_token_logprobs* logprobs_out = nullptr);
 int engine_stats(const aha_engine* e, aha_engine_stats* out);
 int engine_debug_ctr_base(aha_engine* e, uint32_t base);
+size_t engine_max_events(const aha_engine* e);
+int engine_spec_stats(const aha_engine* e, aha_spec_stats* out);
+int engine_request_spec(const aha_engine* e, uint64_t req_id, size_t* n_proposed, size_t* n_accepted);
 int model_forward_initial(aha_model* m, const uint32_t* ids, size_t n, size_t offset, const aha_mm_input* mm,
                           float* logits_out, uint32_t* argmax_out);
 int model_forward_step(aha_model* m, uint32_t token, size_t offset, float* logits_out, uint32_t* argmax_out);

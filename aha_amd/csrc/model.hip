@@ -2508,6 +2508,8 @@ static void gemv_rows_groups(aha_model* m, GemvRowsArgs g, GemvEpi epi, int rows
 struct GenCall {
   int n = 0, V = 0, H = 0, max_nsplit = 1;
   int rows = 0;   // the largest row count of a step when it exceeds n (draft-and-verify: a sequence's drafts are rows of their own)
+  int seq_words = SPEC_SEQ_WORDS;   // words of a sequence's entry behind the row table's rows (the engine: ENG_SEQ_WORDS)
+  int ctr_rows = 0;                 // head_ctr blocks when they are not one per row (the engine: its slots, then its draft rows)
   float* ws = nullptr;
   void *x = nullptr, *h = nullptr, *qkv = nullptr, *attn = nullptr, *act = nullptr;
   float *rope = nullptr, *logits = nullptr, *blk_max = nullptr, *part_o = nullptr, *part_ml = nullptr;
@@ -2675,7 +2677,7 @@ static int gen_call_alloc(aha_model* m, DevBufs& bufs, GenCall& gc, size_t max_p
   // n: the rows a step can have (the row table also holds one SPEC_SEQ_WORDS entry per sequence behind the rows)
   const int n = std::max(gc.n, gc.rows), H = gc.H, V = gc.V, I = c.intermediate_size, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
   const int nq = nh * 128, nkv = kvh * 128;
-  const size_t tab_words = (size_t)n * GEN_ROW_WORDS + (size_t)gc.n * SPEC_SEQ_WORDS;
+  const size_t tab_words = (size_t)n * GEN_ROW_WORDS + (size_t)gc.n * gc.seq_words;
   size_t ws = 0;
   const int shapes[5][2] = {{nq + 2 * nkv, H}, {H, nq}, {2 * I, H}, {H, I}, {V, H}};
   for (auto& sh : shapes) ws = std::max(ws, gemv_rows_ws_floats(std::min(n, GEN_ROW_GROUP), sh[0], sh[1]));
@@ -2686,7 +2688,7 @@ static int gen_call_alloc(aha_model* m, DevBufs& bufs, GenCall& gc, size_t max_p
       (rc = bufs.alloc((bf16_t**)&gc.act, (size_t)n * I)) || (rc = bufs.alloc(&gc.rope, (size_t)n * 128)) ||
       (rc = bufs.alloc(&gc.logits, (size_t)n * V)) || (rc = bufs.alloc(&gc.blk_max, (size_t)n * tiles)) ||
       (rc = bufs.alloc(&gc.blk_idx, (size_t)n * tiles)) || (rc = bufs.alloc(&gc.tok[0], (size_t)n)) || (rc = bufs.alloc(&gc.tok[1], (size_t)n)) ||
-      (rc = bufs.alloc(&gc.rowtab, tab_words)) || (rc = bufs.alloc(&gc.ctr, (size_t)n * kvh * 32, true)) ||
+      (rc = bufs.alloc(&gc.rowtab, tab_words)) || (rc = bufs.alloc(&gc.ctr, (size_t)(gc.ctr_rows ? gc.ctr_rows : n) * kvh * 32, true)) ||
       (rc = bufs.alloc(&gc.part_o, (size_t)n * gc.max_nsplit * nq)) || (rc = bufs.alloc(&gc.part_ml, (size_t)n * gc.max_nsplit * nh * 2)) ||
       (rc = bufs.alloc(&gc.pass_pages, max_pass_pages)) || (rc = bufs.alloc_host(&gc.h_rowtab, tab_words)) ||
       (rc = bufs.alloc_host(&gc.h_tok, (size_t)n)))
@@ -3375,6 +3377,10 @@ int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_le
 // "last split" test is prev + 1 == ctr0 + layer * nsplit in 32-bit unsigned arithmetic, so a counter that wraps past 2^32 still meets its
 // target exactly once: a false match would need 2^32 arrivals inside one launch (aha_hip_engine_debug_ctr_base moves the base near the wrap
 // point for the test).
+// Requests that may draft (aha_hip_engine_submit_spec): a decode step's mandatory rows keep rows 0 .. R-1, the draft rows follow request by
+// request (include/aha_hip.h has the scheduler).  Draft row d of a step owns head_ctr block max_running + d and ctr_acc[max_running + d],
+// kept per row slot as in spec_decode_loop.  The accept step (spec_accept_split_kernel), its download and the draft rows' logits are queued
+// in front of gen_finish_step's synchronisation; a step in which no row drafts is the step it was before such requests existed.
 namespace {
 struct EngReq {
   uint64_t id = 0;
@@ -3394,6 +3400,16 @@ struct EngReq {
   int slot = -1;
   bool started = false, cancel = false;
   std::vector<uint32_t> toks;         // capacity max_new: gen_finish_step reads the penalty context through a pointer to it
+  // aha_hip_engine_submit_spec with max_draft > 0 (drafts: true): the proposer's config, the prediction (copied) and context
+  // (prompt || generated, kept beside ids / toks because spec_propose wants it in one piece), the draft counts so far
+  bool drafts = false;
+  aha_spec_config spec{};
+  std::vector<uint32_t> prediction, ctx;
+  size_t n_proposed = 0, n_accepted = 0;
+};
+struct EngSpecCount {   // a request a step retired: what aha_hip_engine_request_spec answers until the next step begins
+  uint64_t id;
+  size_t n_proposed, n_accepted;
 };
 struct EngSeg {
   EngReq* q;
@@ -3425,6 +3441,16 @@ struct aha_engine {
   uint32_t* d_tok_in = nullptr;       // a decode step's input tokens
   uint32_t* h_tok_in = nullptr;       // pinned
   size_t ctx_cap = 0, adj_cap = 0;
+  // draft-and-verify requests (aha_hip_engine_submit_spec): a step's rows may reach row_cap = the row budget of max_running.  Draft row d
+  // of a step (the d-th row behind the mandatory ones) owns head_ctr block max_running + d and ctr_acc[max_running + d]; the blocks are
+  // set to ctr_base at creation and again by the first drafting step after aha_hip_engine_debug_ctr_base (draft_ctr_stale).
+  size_t row_cap = 0;
+  bool draft_ctr_stale = false;
+  float* h_stage = nullptr;           // pinned (row_cap, vocab), from the first drafting step that reports logits: a drafting step's
+                                      // rows come down here, as the events they belong to are known only after the accept step
+  std::vector<aha_token_logprobs> lp_stage;   // the same for the rows' logprob entries
+  aha_spec_stats spec_stats{};
+  std::vector<aha::EngSpecCount> retired;
   ~aha_engine() {
     for (aha::EngReq* q : waiting) delete q;
     for (aha::EngReq* q : slots) delete q;
@@ -3499,7 +3525,8 @@ int engine_create(aha_model* m, const aha_engine_config* cfg, aha_engine** out) 
   const int n = (int)e->max_running, kvh = c.num_key_value_heads;
   e->slots.assign(n, nullptr);
   e->slot_pages.resize(n);
-  e->ctr_acc.assign(n, 0u);
+  e->row_cap = (size_t)((n + GEN_ROW_GROUP - 1) / GEN_ROW_GROUP * GEN_ROW_GROUP);
+  e->ctr_acc.assign((size_t)n + GEN_ROW_GROUP, 0u);   // the slots, then the draft rows of a step (fewer than GEN_ROW_GROUP)
   e->n_out.assign(n, 0);
   e->seq_tok.assign(n, nullptr);
   e->row_logits.assign(n, nullptr);
@@ -3508,13 +3535,15 @@ int engine_create(aha_model* m, const aha_engine_config* cfg, aha_engine** out) 
   for (size_t p = e->kv_pages; p > 0; --p) e->free_pages.push_back(m->h_page_ptrs[p - 1]);   // page 0 is taken first
   GenCall& gc = e->gc;
   gc.n = n, gc.V = c.vocab_size, gc.H = c.hidden_size, gc.max_new = 0;
+  gc.rows = (int)e->row_cap, gc.seq_words = ENG_SEQ_WORDS, gc.ctr_rows = n + GEN_ROW_GROUP;
   gc.max_nsplit = attn_decode_nsplit((int)std::min<size_t>(e->kv_pages * KV_PAGE_TOKENS, (size_t)1 << 24), c.num_attention_heads / kvh, m->max_nsplit);
   gc.n_out = e->n_out.data(), gc.seq_tokens = e->seq_tok.data(), gc.row_logits = e->row_logits.data();
   gc.lp_top = e->lp_top.data(), gc.row_logprobs = e->row_lp.data();
   e->ctx_cap = (size_t)n * 64;
   if ((rc = gen_call_alloc(m, e->bufs, gc, 2 * e->kv_pages)) || (rc = gen_choice_alloc(e->bufs, gc, e->ctx_cap, (size_t)n, e->ch)) ||
-      (rc = e->bufs.alloc(&e->d_win, (size_t)n * e->kv_pages, true)) || (rc = e->bufs.alloc(&e->d_tok_in, (size_t)n)) ||
-      (rc = e->bufs.alloc_host(&e->h_tok_in, (size_t)n)) || (logprob_shape_ok(gc.V) && (rc = gen_logprob_alloc(e->bufs, gc))) ||
+      (rc = e->bufs.alloc(&e->d_win, (size_t)n * e->kv_pages, true)) || (rc = e->bufs.alloc(&e->d_tok_in, e->row_cap)) ||
+      (rc = e->bufs.alloc_host(&e->h_tok_in, e->row_cap)) || (rc = e->bufs.alloc(&gc.spec_out, (size_t)n * SPEC_OUT_WORDS)) ||
+      (rc = e->bufs.alloc_host(&gc.h_spec_out, (size_t)n * SPEC_OUT_WORDS)) || (logprob_shape_ok(gc.V) && (rc = gen_logprob_alloc(e->bufs, gc))) ||
       (rc = gen_choice_mask_alloc(e->bufs, n, gc.V, e->ch))) {
     delete e;
     model_clear_cache(m);
@@ -3570,6 +3599,11 @@ int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const Submit
   std::vector<std::vector<int32_t>> pos3(1);
   std::vector<int64_t> rope_delta(1, 0);
   if (mm && (rc = check_mm_requests(m, ids, &n_ids, 1, &mm, pos3, rope_delta))) return rc;
+  for (size_t i = 0; o.spec && o.prediction && i < o.n_prediction; ++i)
+    if (o.prediction[i] >= (uint32_t)c.vocab_size) {
+      set_error("engine_submit_spec: prediction id out of range at position " + std::to_string(i));
+      return AHA_ERR_INVALID;
+    }
   const size_t npages = (n_ids + max_new + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;
   if (npages > e->kv_pages) {
     set_error("engine_submit: the request needs " + std::to_string(npages) + " pages, the engine has " + std::to_string(e->kv_pages));
@@ -3592,6 +3626,13 @@ int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const Submit
     q->adjust = aha_logit_adjust{adjust->presence_penalty, adjust->frequency_penalty, q->bias_ids.data(), q->bias_vals.data(), adjust->n_bias};
   }
   if (o.mask) q->mask.assign(o.mask, o.mask + o.n_mask_words);
+  if (o.spec && o.spec->max_draft > 0) {   // max_draft 0: an ordinary greedy request
+    q->drafts = true;
+    q->spec = *o.spec;
+    if (o.prediction) q->prediction.assign(o.prediction, o.prediction + o.n_prediction);
+    q->ctx.reserve(n_ids + max_new);
+    q->ctx = q->ids;
+  }
   q->npages = npages;
   q->toks.reserve(max_new);
   e->waiting.push_back(q);
@@ -3602,14 +3643,20 @@ int engine_submit(aha_engine* e, const uint32_t* ids, size_t n_ids, const Submit
 int engine_set_mask(aha_engine* e, uint64_t req_id, const uint32_t* words, size_t n_words) {
   const size_t V = (size_t)e->m->desc.vocab_size;
   if (words && rc_mask_check(words, n_words, V, "engine_set_mask")) return AHA_ERR_INVALID;
+  auto drafts = [&](const EngReq* q) {   // a drafting step takes its tokens from the unmasked argmax: such a request has no mask
+    if (q->drafts) set_error("engine_set_mask: request " + std::to_string(req_id) + " was submitted through engine_submit_spec, which takes no mask");
+    return q->drafts;
+  };
   for (EngReq* q : e->waiting)
     if (q->id == req_id) {
+      if (drafts(q)) return AHA_ERR_INVALID;
       if (words) q->mask.assign(words, words + n_words);
       else q->mask.clear();
       return AHA_OK;
     }
   for (EngReq* q : e->slots)
     if (q && q->id == req_id && !q->cancel) {
+      if (drafts(q)) return AHA_ERR_INVALID;
       // between steps the stream has drained: the slot's pinned words are free to change, and go up with the next candidate step
       if (words) memcpy(e->ch.h_masks + (size_t)q->slot * e->ch.mask_w, words, n_words * 4);
       e->ch.mask_state[q->slot] = words ? 2 : 0;
@@ -3647,11 +3694,49 @@ int engine_stats(const aha_engine* e, aha_engine_stats* out) {
 
 int engine_debug_ctr_base(aha_engine* e, uint32_t base) {
   e->ctr_base = base;
+  e->draft_ctr_stale = true;   // the draft rows' blocks follow at the next step that drafts
   return AHA_OK;
+}
+
+// Whether a request that may draft is waiting or running: its steps may emit more than one event per request
+static bool engine_may_draft(const aha_engine* e) {
+  for (const EngReq* q : e->waiting)
+    if (q->drafts) return true;
+  for (const EngReq* q : e->slots)
+    if (q && q->drafts) return true;
+  return false;
+}
+
+// The events the next step may emit, cancellations included: the cap it asks for
+size_t engine_max_events(const aha_engine* e) {
+  size_t n = e->pending.size();
+  for (const EngReq* q : e->slots) n += q && q->cancel;
+  return n + (engine_may_draft(e) ? e->row_cap : e->max_running);
+}
+
+int engine_spec_stats(const aha_engine* e, aha_spec_stats* out) {
+  *out = e->spec_stats;
+  return AHA_OK;
+}
+
+int engine_request_spec(const aha_engine* e, uint64_t req_id, size_t* n_proposed, size_t* n_accepted) {
+  for (const EngReq* q : e->slots)
+    if (q && q->id == req_id) {
+      *n_proposed = q->n_proposed, *n_accepted = q->n_accepted;
+      return AHA_OK;
+    }
+  for (const EngSpecCount& r : e->retired)
+    if (r.id == req_id) {
+      *n_proposed = r.n_proposed, *n_accepted = r.n_accepted;
+      return AHA_OK;
+    }
+  set_error("engine_request_spec: no running request " + std::to_string(req_id) + ", and none the last step ended");
+  return AHA_ERR_INVALID;
 }
 
 static void engine_release(aha_engine* e, int s) {
   EngReq* q = e->slots[s];
+  e->retired.push_back(EngSpecCount{q->id, q->n_proposed, q->n_accepted});
   std::vector<uint64_t>& pg = e->slot_pages[s];
   for (size_t i = pg.size(); i > 0; --i) e->free_pages.push_back(pg[i - 1]);
   pg.clear();
@@ -3735,20 +3820,24 @@ int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, f
     return AHA_ERR_INVALID;
   }
   *n_ev = 0;
-  size_t n_cancel = e->pending.size();
-  for (const EngReq* q : e->slots) n_cancel += q && q->cancel;
-  if (cap < n_cancel + e->max_running) {
-    set_error("engine_step: room for " + std::to_string(cap) + " events, a step may emit " + std::to_string(n_cancel + e->max_running));
+  const size_t max_ev = engine_max_events(e);
+  if (cap < max_ev) {
+    set_error("engine_step: room for " + std::to_string(cap) + " events, a step may emit " + std::to_string(max_ev));
     return AHA_ERR_INVALID;
   }
   AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
+  e->retired.clear();   // the counts of what the previous step retired were kept until here
   size_t ne = 0;
+  int n_first = 0;      // first-token events of this step
   auto emit = [&](uint64_t id, uint32_t tok, uint32_t flags) {
     if (logprobs_out && (flags & AHA_ENGINE_EV_CANCELLED)) logprobs_out[ne].n_top = -1;   // (a token's entry: gen_finish_step wrote it)
     ev[ne++] = aha_engine_event{id, tok, flags};
   };
   // 1. cancellations
-  for (const aha_engine_event& p : e->pending) emit(p.req_id, p.token, p.flags);
+  for (const aha_engine_event& p : e->pending) {
+    emit(p.req_id, p.token, p.flags);
+    e->retired.push_back(EngSpecCount{p.req_id, 0, 0});   // it ended in this step, without ever running
+  }
   e->pending.clear();
   for (int s = 0; s < (int)e->max_running; ++s)
     if (e->slots[s] && e->slots[s]->cancel) {
@@ -3820,6 +3909,7 @@ int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, f
     if (chunk.q && (size_t)(chunk.kv0 + chunk.len) < chunk.q->ids.size()) --k;
     if ((rc = gen_packed_pass(m, gc, pp, ids.data(), mm.data(), 0, phys.data(), k, 0))) return rc;
     for (int j = 0; j < n_seg; ++j) segs[j].q->done += (size_t)segs[j].len;
+    n_first = k;
     if (k > 0) {
       std::vector<int> seqs(k);
       for (int j = 0; j < k; ++j) {
@@ -3833,6 +3923,7 @@ int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, f
         EngReq* q = segs[j].q;
         const uint32_t t = gc.h_tok[j];   // the first token never ends a sequence (generate.rs:131-134)
         q->toks.push_back(t);
+        if (q->drafts) q->ctx.push_back(t);
         q->started = true;
         q->mm = nullptr;
         e->n_out[q->slot] = 1;
@@ -3847,28 +3938,121 @@ int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, f
   for (int s : dec)
     if (e->slots[s]->toks.size() < e->slots[s]->max_new) rows.push_back(s);
   if (!rows.empty()) {
-    const int R = (int)rows.size();
+    const int R = (int)rows.size(), nslots = (int)e->max_running;
+    // the draft rows (aha_hip_engine_step's scheduler): behind the R mandatory rows, granted in submission order while the step stays
+    // inside its last gemv_rows group and inside the event cap its first tokens have already drawn on
+    int extra = std::max(0, std::min((R + GEN_ROW_GROUP - 1) / GEN_ROW_GROUP * GEN_ROW_GROUP - R, (int)e->row_cap - n_first - R));
+    std::vector<int> nd(R, 0), d0(R, 0);
+    int D = 0, n_seq = 0;
+    for (int r = 0; r < R && extra > 0; ++r) {
+      const EngReq* q = e->slots[rows[r]];
+      if (!q->drafts) continue;
+      const size_t room = std::min<size_t>((size_t)extra, q->max_new - q->toks.size() - 1);   // t + 1 + |draft| <= max_new: the cache stays in its pages
+      if (room == 0) continue;
+      uint32_t draft[SPEC_MAX_DRAFT];
+      size_t k = 0;
+      spec_propose(q->spec, q->ctx.data(), q->ctx.size(), q->ids.size(), q->prediction.empty() ? nullptr : q->prediction.data(),
+                   q->prediction.size(), draft, &k);
+      k = std::min(k, room);
+      if (k == 0) continue;
+      nd[r] = (int)k, d0[r] = R + D;
+      for (size_t i = 0; i < k; ++i) e->h_tok_in[R + D + (int)i] = draft[i];
+      D += (int)k, extra -= (int)k, ++n_seq;
+    }
+    const bool staged = D > 0;   // the rows' events are known only after the accept step: logits and logprob entries come down to staging
+    if (staged && e->draft_ctr_stale) {   // (after aha_hip_engine_debug_ctr_base only; the stream has drained)
+      const std::vector<unsigned> base((size_t)GEN_ROW_GROUP * c.num_key_value_heads * 32, e->ctr_base);
+      AHA_HIP_CHECK(hipMemcpy(gc.ctr + (size_t)nslots * c.num_key_value_heads * 32, base.data(), base.size() * 4, hipMemcpyHostToDevice));
+      std::fill(e->ctr_acc.begin() + nslots, e->ctr_acc.end(), e->ctr_base);
+      e->draft_ctr_stale = false;
+    }
+    if (staged && logits_out && !e->h_stage && (rc = e->bufs.alloc_host(&e->h_stage, e->row_cap * (size_t)V))) return rc;
+    if (staged && logprobs_out) e->lp_stage.resize((size_t)R);
     GenStepRows sr;
     for (int r = 0; r < R; ++r) {
       const int s = rows[r];
       const EngReq* q = e->slots[s];   // its cache after this step's append: the prompt and the tokens so far, in the slot's page window
       gen_write_row(m, gc, sr, r, (int64_t)((size_t)s * e->kv_pages), (int)(q->ids.size() + e->n_out[s]), q->rope_delta, e->ctr_acc[s], r, s);
       e->h_tok_in[r] = q->toks.back();
-      e->row_logits[r] = logits_out ? logits_out + (ne + r) * (size_t)V : nullptr;
-      e->row_lp[r] = logprobs_out ? logprobs_out + (ne + r) : nullptr;
+      if (staged) {
+        e->row_logits[r] = logits_out ? e->h_stage + (size_t)r * V : nullptr;
+        e->row_lp[r] = logprobs_out ? &e->lp_stage[r] : nullptr;
+      } else {
+        e->row_logits[r] = logits_out ? logits_out + (ne + r) * (size_t)V : nullptr;
+        e->row_lp[r] = logprobs_out ? logprobs_out + (ne + r) : nullptr;
+      }
     }
-    AHA_HIP_CHECK(hipMemcpyAsync(gc.rowtab, gc.h_rowtab, (size_t)R * GEN_ROW_WORDS * 4, hipMemcpyHostToDevice, st));
-    AHA_HIP_CHECK(hipMemcpyAsync(e->d_tok_in, e->h_tok_in, (size_t)R * 4, hipMemcpyHostToDevice, st));
-    gen_decode_step(m, gc, R, sr.max_split, sr.kv_tokens, e->d_tok_in, gc.tok[1]);
+    if (staged) {   // draft row i of a request: its cache one token longer per row, counters of its own, the draft in GEN_ROW_TOK
+      int32_t* h_seq = gc.h_rowtab + (size_t)(R + D) * GEN_ROW_WORDS;
+      for (int r = 0, a = 0; r < R; ++r) {
+        if (!nd[r]) continue;
+        const int s = rows[r];
+        const EngReq* q = e->slots[s];
+        for (int i = 0; i < nd[r]; ++i) {
+          const int row = d0[r] + i, blk = nslots + row - R;
+          gen_write_row(m, gc, sr, row, (int64_t)((size_t)s * e->kv_pages), (int)(q->ids.size() + e->n_out[s]) + 1 + i, q->rope_delta,
+                        e->ctr_acc[blk], row, blk, (int32_t)e->h_tok_in[row]);
+        }
+        h_seq[a * ENG_SEQ_WORDS + ENG_SEQ_ROW] = r, h_seq[a * ENG_SEQ_WORDS + ENG_SEQ_DRAFT0] = d0[r], h_seq[a * ENG_SEQ_WORDS + ENG_SEQ_NDRAFT] = nd[r];
+        ++a;
+      }
+    }
+    const int RT = R + D;
+    AHA_HIP_CHECK(hipMemcpyAsync(gc.rowtab, gc.h_rowtab, ((size_t)RT * GEN_ROW_WORDS + (size_t)n_seq * ENG_SEQ_WORDS) * 4, hipMemcpyHostToDevice, st));
+    AHA_HIP_CHECK(hipMemcpyAsync(e->d_tok_in, e->h_tok_in, (size_t)RT * 4, hipMemcpyHostToDevice, st));
+    // a step without drafts is the step it was before: one attention launch per layer, the fused append
+    gen_decode_step(m, gc, RT, sr.max_split, sr.kv_tokens, e->d_tok_in, gc.tok[1], staged);
+    if (staged) {   // the accept step, its download and the draft rows' logits in front of gen_finish_step's synchronisation
+      {
+        ProfScope ps(m, "spec_accept_split", (double)RT * 8, 0);
+        launch_spec_accept_split(gc.tok[1], gc.rowtab, gc.rowtab + (size_t)RT * GEN_ROW_WORDS, n_seq, gc.spec_out, st);
+      }
+      AHA_HIP_CHECK(hipMemcpyAsync(gc.h_spec_out, gc.spec_out, (size_t)n_seq * SPEC_OUT_WORDS * 4, hipMemcpyDeviceToHost, st));
+      if (logits_out)
+        AHA_HIP_CHECK(hipMemcpyAsync(e->h_stage + (size_t)R * V, gc.logits + (size_t)R * V, (size_t)D * V * 4, hipMemcpyDeviceToHost, st));
+    }
     AHA_HIP_CHECK(hipGetLastError());
     if ((rc = gen_finish_step(m, gc, e->ch, rows, gc.tok[1]))) return rc;
-    for (int r = 0; r < R; ++r) {
+    e->spec_stats.decode_steps += 1, e->spec_stats.rows += (size_t)RT, e->spec_stats.proposed += (size_t)D;
+    for (int r = 0, a = 0; r < R; ++r) {
       EngReq* q = e->slots[rows[r]];
-      const uint32_t t = gc.h_tok[r];
-      q->toks.push_back(t);
+      if (!nd[r]) {
+        const uint32_t t = gc.h_tok[r];
+        q->toks.push_back(t);
+        if (q->drafts) q->ctx.push_back(t);
+        e->n_out[rows[r]] = q->toks.size();
+        const uint32_t f = (is_stop(c, t) ? AHA_ENGINE_EV_STOP : 0u) | (q->toks.size() == q->max_new ? AHA_ENGINE_EV_LENGTH : 0u);
+        if (staged && logits_out) memcpy(logits_out + ne * (size_t)V, e->h_stage + (size_t)r * V, (size_t)V * 4);
+        if (staged && logprobs_out) logprobs_out[ne] = e->lp_stage[r];
+        emit(q->id, t, f);
+        continue;
+      }
+      const uint32_t* o = gc.h_spec_out + (size_t)a++ * SPEC_OUT_WORDS;
+      const int emitted = (int)o[SPEC_OUT_COUNT];
+      if (emitted < 1 || emitted > nd[r] + 1 || (int)o[SPEC_OUT_LAST_ROW] != (emitted == 1 ? r : d0[r] + emitted - 2)) {
+        set_error("engine_step: the accept step returned an impossible run");
+        return AHA_ERR_STATE;
+      }
+      // stop tokens and max_new in order: the run is cut at, and keeps, the first stop token; event i's logits are those of the row that
+      // chose its token -- the request's own row, then the verify row of draft i
+      int kept = 0;
+      bool done = false;
+      while (kept < emitted && !done) {
+        const uint32_t t = o[SPEC_OUT_TOKENS + kept];
+        const int row = kept == 0 ? r : d0[r] + kept - 1;
+        ++kept;
+        q->toks.push_back(t);
+        q->ctx.push_back(t);
+        const bool stop = is_stop(c, t), length = q->toks.size() == q->max_new;
+        done = stop || length;
+        if (logits_out) memcpy(logits_out + ne * (size_t)V, e->h_stage + (size_t)row * V, (size_t)V * 4);
+        if (logprobs_out) logprobs_out[ne].n_top = -1;   // a request that drafts has no logprobs
+        emit(q->id, t, (stop ? AHA_ENGINE_EV_STOP : 0u) | (length ? AHA_ENGINE_EV_LENGTH : 0u));
+      }
       e->n_out[rows[r]] = q->toks.size();
-      const uint32_t f = (is_stop(c, t) ? AHA_ENGINE_EV_STOP : 0u) | (q->toks.size() == q->max_new ? AHA_ENGINE_EV_LENGTH : 0u);
-      emit(q->id, t, f);
+      const size_t acc = (size_t)std::min(kept, emitted - 1);   // drafts among the kept tokens (the run's last token is its row's own choice)
+      q->n_proposed += (size_t)nd[r], q->n_accepted += acc;
+      e->spec_stats.accepted += acc;
     }
   }
   // 5. retire what ended

@@ -748,13 +748,14 @@ class HipEngine:
         self._keep: Dict[int, list] = {}      # per request: the arrays its aha_mm_input points into, until its first token
         self._streams: Dict[int, List[int]] = {}
         self._done: Dict[int, bool] = {}
-        self._n_cancel = 0
 
     def submit(self, input_ids: Sequence[int], max_new: int, params=None, data: Optional[MultiModalData] = None,
-               top_logprobs: Optional[int] = None, mask=None) -> int:
+               top_logprobs: Optional[int] = None, mask=None, spec=None, prediction: Optional[Sequence[int]] = None) -> int:
         """Queue one request; returns its id.  params: None = greedy, else a sampling.SamplingParams; data: its MultiModalData;
         top_logprobs: None, or 0..20 = report every token's log-probability and that many alternatives (step(want_logprobs=True));
-        mask: None, or the packed allowed-token words (guided.pack_mask) that govern its tokens from the first one until set_mask."""
+        mask: None, or the packed allowed-token words (guided.pack_mask) that govern its tokens from the first one until set_mask.
+        spec: None, or a speculative.SpecConfig = a greedy draft-and-verify request (aha_hip_engine_submit_spec) with its predicted
+        output `prediction` (None: prompt lookup only); it takes no params, top_logprobs or mask."""
         ids = np.ascontiguousarray(np.asarray(input_ids, dtype=np.uint32).reshape(-1))
         keep = [ids]
         mm_p = None
@@ -762,6 +763,10 @@ class HipEngine:
             mm, k = _mm_input(data)
             keep += [mm, k]
             mm_p = C.byref(mm)
+        if spec is not None and (params is not None or top_logprobs is not None or mask is not None):
+            raise ValueError("a draft-and-verify request is greedy: no params, top_logprobs or mask")
+        if spec is None and prediction is not None:
+            raise ValueError("a prediction needs a spec")
         cp = None if params is None else C.byref(params.to_c())
         rid = C.c_uint64()
         head, top = (self.handle, ids.ctypes.data, ids.size, mm_p, cp), -1 if top_logprobs is None else int(top_logprobs)
@@ -769,8 +774,13 @@ class HipEngine:
         if params is not None and getattr(params, "adjust_active", False):   # logit_bias / presence / frequency: the arrays are copied
             adj, k = params.adjust_to_c()
             adj_p = C.byref(adj)
-        # the entry: mask -> _masked, an active adjust -> _adjusted, top_logprobs -> _logprobs, otherwise the plain one
-        if mask is not None:
+        # the entry: spec -> _spec, mask -> _masked, an active adjust -> _adjusted, top_logprobs -> _logprobs, otherwise the plain one
+        if spec is not None:
+            cs = _lib.SpecConfig(spec.max_draft, spec.ngram_min, spec.ngram_max)
+            pred = np.ascontiguousarray(np.asarray([] if prediction is None else prediction, dtype=np.uint32).reshape(-1))
+            rc = lib().aha_hip_engine_submit_spec(*head[:4], int(max_new), C.byref(cs), pred.ctypes.data if pred.size else None, pred.size,
+                                                  C.byref(rid))
+        elif mask is not None:
             words = np.ascontiguousarray(mask, dtype=np.uint32).reshape(-1)
             rc = lib().aha_hip_engine_submit_masked(*head, adj_p, words.ctypes.data, words.size, int(max_new), top, C.byref(rid))
         elif adj_p is not None:
@@ -796,13 +806,12 @@ class HipEngine:
 
     def cancel(self, req_id: int) -> None:
         check(lib().aha_hip_engine_cancel(self.handle, int(req_id)))
-        self._n_cancel += 1
 
     def step(self, want_logits: bool = False, want_logprobs: bool = False):
         """One engine step: a list of EngineEvent (and with want_logits the (len(events), vocab) float32 logits that chose each token;
         with want_logprobs, after them, one entry per event: (logprob, [(id, logprob), ...]), or None for a cancellation or a request
         submitted without top_logprobs)."""
-        cap = self.max_running + self._n_cancel
+        cap = int(lib().aha_hip_engine_max_events(self.handle))
         evs = (_lib.EngineEvent * cap)()
         n = C.c_size_t()
         lg = np.zeros((cap, self.model.text_cfg.vocab_size), np.float32) if want_logits else None
@@ -811,7 +820,6 @@ class HipEngine:
             check(lib().aha_hip_engine_step(self.handle, evs, cap, C.byref(n), None if lg is None else lg.ctypes.data))
         else:
             check(lib().aha_hip_engine_step_logprobs(self.handle, evs, cap, C.byref(n), None if lg is None else lg.ctypes.data, lp))
-        self._n_cancel = 0
         out = []
         for i in range(n.value):
             e = evs[i]
@@ -834,6 +842,24 @@ class HipEngine:
         st = _lib.EngineStats()
         check(lib().aha_hip_engine_stats(self.handle, C.byref(st)))
         return {"waiting": st.waiting, "running": st.running, "free_pages": st.free_pages, "total_pages": st.total_pages}
+
+    def max_events(self) -> int:
+        """The cap the next step needs (aha_hip_engine_max_events): max_running, or the row budget of max_running while a request that
+        may draft is waiting or running, plus pending cancellations."""
+        return int(lib().aha_hip_engine_max_events(self.handle))
+
+    def spec_stats(self):
+        """speculative.SpecStats over the engine's life (aha_hip_engine_spec_stats)."""
+        from .speculative import SpecStats
+        st = _lib.SpecStats()
+        check(lib().aha_hip_engine_spec_stats(self.handle, C.byref(st)))
+        return SpecStats(int(st.decode_steps), int(st.rows), int(st.proposed), int(st.accepted))
+
+    def request_spec(self, req_id: int):
+        """(proposed, accepted) draft tokens of a running request, or of one the most recent step ended (aha_hip_engine_request_spec)."""
+        p, a = C.c_size_t(), C.c_size_t()
+        check(lib().aha_hip_engine_request_spec(self.handle, int(req_id), C.byref(p), C.byref(a)))
+        return int(p.value), int(a.value)
 
     def tokens(self, req_id: int) -> List[int]:
         """The tokens request req_id has streamed so far."""

@@ -75,3 +75,38 @@ def row_budget(n_active: int, group: int = 32) -> int:
     """Rows a step may have: the next multiple of the gemv_rows group at or above its unfinished sequences (speculation never adds a
     pass over the weights)."""
     return (n_active + group - 1) // group * group
+
+
+@dataclass
+class EngineRow:
+    """One decoding request of an engine step, as the scheduler of aha_hip_engine_step sees it: context = prompt + generated (the first
+    n_prompt ids are the prompt), its max_new, and for a request of aha_hip_engine_submit_spec its SpecConfig and prediction (spec None:
+    a request that never drafts)."""
+    context: Sequence[int]
+    n_prompt: int
+    max_new: int
+    spec: Optional[SpecConfig] = None
+    prediction: Optional[Sequence[int]] = None
+
+
+def engine_step_drafts(rows: Sequence[EngineRow], max_running: int = 0, n_first: int = 0) -> List[List[int]]:
+    """The draft rows of one engine decode step (include/aha_hip.h, "scheduler"), a pure function of the step's state: rows are the R
+    requests that decode, in submission order.  extra = row_budget(R) - R; drafts are granted in that order among the requests with a
+    spec: k = min(len(propose(...)), extra, max_new - t - 1) for a request with t tokens so far, extra -= k.  A step whose prefill gave
+    n_first first tokens grants at most row_budget(max_running) - n_first - R rows (max_running 0: no such cut; none when n_first = 0).
+    Returns one draft (possibly empty) per request; the step runs R + sum(len) rows."""
+    R = len(rows)
+    extra = row_budget(R) - R
+    if max_running:
+        extra = max(0, min(extra, row_budget(max_running) - n_first - R))
+    out: List[List[int]] = []
+    for q in rows:
+        t = len(q.context) - q.n_prompt
+        room = min(extra, q.max_new - t - 1)
+        if q.spec is None or q.spec.max_draft == 0 or room <= 0:
+            out.append([])
+            continue
+        d = propose(q.spec, q.context, q.n_prompt, q.prediction)[:room]
+        extra -= len(d)
+        out.append(d)
+    return out

@@ -360,11 +360,53 @@ int aha_hip_engine_cancel(aha_engine* e, uint64_t req_id);
  * afterwards): row i = the logits that chose event i's token (a cancellation's row is not written).  A request prefilled whole has the
  * tokens and logits of aha_hip_generate_batch_mm (or _sampled) for the same prefill pass composition, bit for bit; a chunked prompt's
  * equal its whole prefill within the parity bounds only.  A step that fails (a HIP or allocation error) loses its events: destroy the
- * engine then. */
+ * engine then.
+ * With requests of aha_hip_engine_submit_spec (below) waiting or running, cap >= aha_hip_engine_max_events(e), and: a request may emit up
+ * to 1 + max_draft token events in one step; its events of one step are consecutive and in generation order, at the place its single event
+ * has otherwise, among the decode tokens in submission order; STOP / LENGTH can only be on the last of them, and tokens behind a stop token
+ * inside an accepted run are dropped; logits_out row i is still the logits that chose event i's token -- for a drafted token the verify
+ * row that confirmed it.  Everything above stays true for an engine without such requests. */
 int aha_hip_engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, float* logits_out);
 int aha_hip_engine_stats(const aha_engine* e, aha_engine_stats* out);
-/* Test hook: the value a slot's split-arrival counters are reset to when a request takes it (default 0; near 2^32 they wrap mid-request). */
+/* Test hook: the value a slot's split-arrival counters are reset to when a request takes it (default 0; near 2^32 they wrap mid-request).
+ * The counter blocks of a step's draft rows (aha_hip_engine_submit_spec) are set to it at the next step that drafts. */
 int aha_hip_engine_debug_ctr_base(aha_engine* e, uint32_t base);
+
+/* ---- draft-and-verify requests in the engine ---------------------------------------------------------------------------------
+ * aha_hip_generate_batch_spec's decoding for streamed requests: where the request's `prediction` (src/params/chat.rs:105 of the reference)
+ * arrives when `stream: true` (generate_stream_generic, models/common/generate.rs:231-368).  A request submitted here is greedy and may
+ * run up to max_draft draft tokens as rows of its own in every decode step; its tokens, flags and logits are EXACTLY those of the same
+ * request through aha_hip_engine_submit on the same submission history, for any prediction, and every other request of the engine keeps
+ * its bits.  An engine without such a request launches and computes what it did before they existed.
+ *   spec, prediction   aha_hip_generate_batch_spec's rules for one sequence: the drafts are aha_hip_spec_propose's over prompt || generated;
+ *                      the prediction is copied at submit; NULL / 0: prompt lookup only; max_draft 0: an ordinary greedy request.
+ *   scheduler          in the decode step of aha_hip_engine_step the R requests that decode have their one row each, in submission order;
+ *                      extra = row_budget(R) - R, row_budget(n) the next multiple of 32 at or above n; drafts are then granted in
+ *                      submission order among the requests of this entry: k = min(|propose(...)|, extra, max_new - t - 1) for a request
+ *                      with t tokens so far, extra -= k -- aha_hip_generate_batch_spec's rule, with the same cut that keeps the cache
+ *                      inside the request's reserved pages.  Speculation never adds a pass over the weights.  A step whose prefill gave F
+ *                      first tokens grants at most row_budget(max_running) - F - R draft rows, so that the step's events fit the cap (no
+ *                      cut when F = 0).  A step in which no row drafts is the step it was before: one attention launch per layer with the
+ *                      fused append.  Draft rows sit behind the R mandatory rows, request by request.
+ *   counters           a draft token is accepted when the verify step's greedy choice equals it; proposed = draft rows run.
+ * Out of scope: samplers, logprobs (an event of such a request has n_top = -1 in aha_hip_engine_step_logprobs), logit adjustments and masks
+ * on these requests (aha_hip_engine_set_mask refuses their ids with AHA_ERR_INVALID); tensor-parallel and context-parallel models (as the engine).
+ * Errors, all before any device work: aha_hip_engine_submit's codes and messages, plus AHA_ERR_INVALID "null spec"; "max_draft must be in
+ * 0..15"; "n-gram bounds must satisfy 1 <= ngram_min <= ngram_max <= 8"; "prediction id out of range" (an id >= vocab_size, naming its
+ * position).  A request with mm is allowed, as in aha_hip_generate_batch_spec. */
+int aha_hip_engine_submit_spec(aha_engine* e, const uint32_t* input_ids, size_t n_ids, const aha_mm_input* mm, size_t max_new,
+                               const aha_spec_config* spec, const uint32_t* prediction, size_t n_prediction, uint64_t* req_id);
+/* The cap the next aha_hip_engine_step* call needs, pending cancellations included: max_running + pending cancellations while no request
+ * submitted with max_draft > 0 is waiting or running (what aha_hip_engine_step has always demanded), else row_budget(max_running) + pending
+ * cancellations.  0 for a null engine. */
+size_t aha_hip_engine_max_events(const aha_engine* e);
+/* aha_spec_stats over the engine's life: its decode steps (those of requests that never draft included), their rows, the draft tokens
+ * proposed and accepted. */
+int aha_hip_engine_spec_stats(const aha_engine* e, aha_spec_stats* out);
+/* The draft tokens run / kept for one request (a response's accepted_prediction_tokens, params/shared.rs:58-63; rejected = proposed -
+ * accepted): for a running request, and for one that ended in the most recent step -- the engine keeps the counts of the requests a step
+ * retired until the next step begins.  Any other id: AHA_ERR_INVALID. */
+int aha_hip_engine_request_spec(const aha_engine* e, uint64_t req_id, size_t* n_proposed, size_t* n_accepted);
 
 /* ---- per-token log-probabilities -----------------------------------------------------------------------------------------
  * The chat request's `logprobs` / `top_logprobs` (src/params/chat.rs:85-89 of the reference, whose responses always carry

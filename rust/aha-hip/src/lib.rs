@@ -498,6 +498,20 @@ pub mod sys {
         ) -> i32;
         pub fn aha_hip_engine_stats(e: *const AhaEngine, out: *mut AhaEngineStats) -> i32;
         pub fn aha_hip_engine_debug_ctr_base(e: *mut AhaEngine, base: u32) -> i32;
+        pub fn aha_hip_engine_submit_spec(
+            e: *mut AhaEngine,
+            input_ids: *const u32,
+            n_ids: usize,
+            mm: *const AhaMmInput,
+            max_new: usize,
+            spec: *const AhaSpecConfig,
+            prediction: *const u32,
+            n_prediction: usize,
+            req_id: *mut u64,
+        ) -> i32;
+        pub fn aha_hip_engine_max_events(e: *const AhaEngine) -> usize;
+        pub fn aha_hip_engine_spec_stats(e: *const AhaEngine, out: *mut AhaSpecStats) -> i32;
+        pub fn aha_hip_engine_request_spec(e: *const AhaEngine, req_id: u64, n_proposed: *mut usize, n_accepted: *mut usize) -> i32;
         pub fn aha_hip_logprob_rows(
             logits: *const f32,
             ld: i64,
@@ -1466,15 +1480,13 @@ impl Drop for Model {
 /// cache: borrow the model mutably for its lifetime.
 pub struct Engine<'a> {
     e: *mut sys::AhaEngine,
-    max_running: usize,
-    n_cancel: usize,
     _m: std::marker::PhantomData<&'a mut Model>,
 }
 impl<'a> Engine<'a> {
     pub fn new(model: &'a mut Model, cfg: sys::AhaEngineConfig) -> Result<Self, Error> {
         let mut e = std::ptr::null_mut();
         check(unsafe { sys::aha_hip_engine_create(model.model, &cfg, &mut e) })?;
-        Ok(Self { e, max_running: cfg.max_running, n_cancel: 0, _m: std::marker::PhantomData })
+        Ok(Self { e, _m: std::marker::PhantomData })
     }
     /// One request: `params` None = greedy.  Text only here (`mm` must outlive the request's first token in the C ABI).
     pub fn submit(&mut self, ids: &[u32], params: Option<&sys::AhaSamplingParams>, max_new: usize) -> Result<u64, Error> {
@@ -1555,18 +1567,52 @@ impl<'a> Engine<'a> {
     pub fn set_mask(&mut self, req_id: u64, mask: Option<&[u32]>) -> Result<(), Error> {
         check(unsafe { sys::aha_hip_engine_set_mask(self.e, req_id, mask.map_or(std::ptr::null(), |m| m.as_ptr()), mask.map_or(0, |m| m.len())) })
     }
+    /// A greedy draft-and-verify request (`aha_hip_engine_submit_spec`): the chat request's `prediction` (reference
+    /// `src/params/chat.rs:105`) for `stream: true`; `None`: prompt lookup only.  Its tokens are those of `submit` with `params` None; a
+    /// step may return up to `1 + spec.max_draft` events for it, consecutive and in generation order.
+    pub fn submit_spec(&mut self, ids: &[u32], max_new: usize, spec: &sys::AhaSpecConfig, prediction: Option<&[u32]>) -> Result<u64, Error> {
+        let mut id = 0u64;
+        check(unsafe {
+            sys::aha_hip_engine_submit_spec(
+                self.e,
+                ids.as_ptr(),
+                ids.len(),
+                std::ptr::null(),
+                max_new,
+                spec,
+                prediction.map_or(std::ptr::null(), |p| p.as_ptr()),
+                prediction.map_or(0, |p| p.len()),
+                &mut id,
+            )
+        })?;
+        Ok(id)
+    }
+    /// The event capacity the next `step` needs (`aha_hip_engine_max_events`), pending cancellations included.
+    pub fn max_events(&self) -> usize {
+        unsafe { sys::aha_hip_engine_max_events(self.e) }
+    }
+    /// Decode steps, rows, proposed and accepted draft tokens over the engine's life (`aha_hip_engine_spec_stats`).
+    pub fn spec_stats(&self) -> Result<sys::AhaSpecStats, Error> {
+        let mut s = sys::AhaSpecStats::default();
+        check(unsafe { sys::aha_hip_engine_spec_stats(self.e, &mut s) })?;
+        Ok(s)
+    }
+    /// (proposed, accepted) draft tokens of a running request or of one the most recent step ended (`aha_hip_engine_request_spec`): a
+    /// response's `accepted_prediction_tokens` / `rejected_prediction_tokens` (reference `src/params/shared.rs:58-63`).
+    pub fn request_spec(&self, req_id: u64) -> Result<(usize, usize), Error> {
+        let (mut p, mut a) = (0usize, 0usize);
+        check(unsafe { sys::aha_hip_engine_request_spec(self.e, req_id, &mut p, &mut a) })?;
+        Ok((p, a))
+    }
     pub fn cancel(&mut self, req_id: u64) -> Result<(), Error> {
-        check(unsafe { sys::aha_hip_engine_cancel(self.e, req_id) })?;
-        self.n_cancel += 1;
-        Ok(())
+        check(unsafe { sys::aha_hip_engine_cancel(self.e, req_id) })
     }
     /// The step's events: (request, token or None for a cancellation, flags `AHA_ENGINE_EV_*`).
     pub fn step(&mut self) -> Result<Vec<(u64, Option<u32>, u32)>, Error> {
-        let cap = self.max_running + self.n_cancel;
+        let cap = self.max_events();
         let mut ev = vec![sys::AhaEngineEvent::default(); cap];
         let mut n = 0usize;
         check(unsafe { sys::aha_hip_engine_step(self.e, ev.as_mut_ptr(), cap, &mut n, std::ptr::null_mut()) })?;
-        self.n_cancel = 0;
         Ok(ev[..n]
             .iter()
             .map(|x| (x.req_id, if x.flags & sys::AHA_ENGINE_EV_CANCELLED != 0 { None } else { Some(x.token) }, x.flags))
@@ -1574,12 +1620,11 @@ impl<'a> Engine<'a> {
     }
     /// `step` plus each event's log-probabilities: `None` for a cancellation and for a request submitted without `top_logprobs`.
     pub fn step_logprobs(&mut self) -> Result<Vec<(u64, Option<u32>, u32, Option<sys::AhaTokenLogprobs>)>, Error> {
-        let cap = self.max_running + self.n_cancel;
+        let cap = self.max_events();
         let mut ev = vec![sys::AhaEngineEvent::default(); cap];
         let mut lp = vec![sys::AhaTokenLogprobs::default(); cap];
         let mut n = 0usize;
         check(unsafe { sys::aha_hip_engine_step_logprobs(self.e, ev.as_mut_ptr(), cap, &mut n, std::ptr::null_mut(), lp.as_mut_ptr()) })?;
-        self.n_cancel = 0;
         Ok(ev[..n]
             .iter()
             .zip(lp[..n].iter())

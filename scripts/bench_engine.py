@@ -12,6 +12,14 @@ process of --rate requests per engine step (seeded), every request --max-new tok
            once every request has its first token, against generate_batch's per-step time at the same rows ((t(1 + N new) - t(1 new)) / N);
   long     the --long prompt's whole prefill alone (generate_batch with max_new 1), the figure a chunked admission is to stay below.
 Writes the lines to --out (default: stdout only).
+
+--spec: draft-and-verify requests instead (HipEngine.submit(spec=...), aha_hip_engine_submit_spec).  Per model, for 1 / 4 / 16 concurrent
+requests of --steady-len tokens (all admitted in the first step), predictions = the greedy output with 0 / 50 / 100 % of its tokens
+corrupted (seeded) and max_draft 7 / 15: engines with predictions and engines without, alternated, --spec-repeats runs each, and
+generate_batch_spec against generate_batch on the same prompts.  Reported per case (one JSON line): the decode phase's aggregate tok/s
+(tokens after the first ones over the time from the end of the prefill step to the last event; min / median / max over the runs), the
+mean inter-token gap of a request (that time over its tokens), the engine's decode steps and accepted / proposed draft tokens.
+--repeat N runs the Poisson workload N times and reports every run (for a comparison of two trees, alternated from outside).
 """
 import argparse
 import json
@@ -142,6 +150,60 @@ def run_long(m, a, vocab):
     return {"mode": "long", "whole_prefill_ms": t * 1e3, "tokens": a.long}
 
 
+def run_spec_engine(m, prompts, a, spec, preds):
+    """One engine run over prompts all submitted up front; spec None: plain requests.  -> (tokens per request, decode seconds, stats)"""
+    from aha_amd.model import HipEngine
+    R = len(prompts)
+    eng = HipEngine(m, max_running=R, kv_pages=R * ((a.steady_len + a.max_new + 63) // 64 + 1), max_tokens_per_step=max(a.budget, R * a.steady_len))
+    try:
+        ids = [eng.submit(p, a.max_new) if spec is None else eng.submit(p, a.max_new, spec=spec, prediction=preds[j])
+               for j, p in enumerate(prompts)]
+        eng.step()   # every prefill, the first tokens
+        t0 = time.perf_counter()
+        while eng.stats()["running"]:
+            eng.step()
+        secs = time.perf_counter() - t0
+        st = eng.spec_stats()
+        return [eng.tokens(r) for r in ids], secs, st
+    finally:
+        eng.close()
+
+
+def run_spec(m, a, vocab, name):
+    from aha_amd.speculative import SpecConfig
+    g = np.random.default_rng(a.seed + 3)
+    out = []
+    for R in (1, 4, 16):
+        prompts = [[int(x) for x in g.integers(0, min(vocab, 150000), size=a.steady_len)] for _ in range(R)]
+        truth, _, _ = run_spec_engine(m, prompts, a, None, None)
+        n_dec = sum(len(t) - 1 for t in truth)
+        t1 = min(timed_call(lambda: m.generate_batch(prompts, 1, a.budget)) for _ in range(3))
+        for corrupt in (0.0, 0.5, 1.0):
+            preds = [[(t + 1) % vocab if g.random() < corrupt else t for t in o] for o in truth]
+            for D in (7, 15):
+                spec = SpecConfig(D, 1, 3)
+                plain, drafted, st = [], [], None
+                for _ in range(a.spec_repeats):   # alternated: the two see the same clocks and the same neighbours on the machine
+                    plain.append(run_spec_engine(m, prompts, a, None, None)[1])
+                    toks, secs, st = run_spec_engine(m, prompts, a, spec, preds)
+                    assert toks == truth, "draft-and-verify changed the tokens"
+                    drafted.append(secs)
+                gb = min(timed_call(lambda: m.generate_batch(prompts, a.max_new, a.budget)) for _ in range(a.spec_repeats)) - t1
+                gbs = min(timed_call(lambda: m.generate_batch_spec(prompts, a.max_new, spec, preds, max_tokens_per_pass=a.budget))
+                          for _ in range(a.spec_repeats)) - t1
+
+                def rate(ts):
+                    return {"min": n_dec / max(ts), "median": n_dec / float(np.median(ts)), "max": n_dec / min(ts)}
+                r = {"mode": "spec", "model": name, "requests": R, "kv_len": a.steady_len, "max_new": a.max_new, "corrupt": corrupt, "max_draft": D,
+                     "engine_plain_tok_s": rate(plain), "engine_spec_tok_s": rate(drafted),
+                     "engine_plain_gap_ms": float(np.median(plain)) * R / n_dec * 1e3, "engine_spec_gap_ms": float(np.median(drafted)) * R / n_dec * 1e3,
+                     "generate_batch_tok_s": n_dec / gb, "generate_batch_spec_tok_s": n_dec / gbs,
+                     "decode_steps": st.decode_steps, "proposed": st.proposed, "accepted": st.accepted, "runs": a.spec_repeats}
+                print(json.dumps(r), flush=True)
+                out.append(r)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="0.6b,8b")
@@ -158,13 +220,20 @@ def main():
     ap.add_argument("--steady-len", type=int, default=512)
     ap.add_argument("--steady-steps", type=int, default=32)
     ap.add_argument("--out", default="")
+    ap.add_argument("--spec", action="store_true", help="measure draft-and-verify requests instead of the Poisson workload")
+    ap.add_argument("--spec-repeats", type=int, default=3)
+    ap.add_argument("--repeat", type=int, default=1, help="runs of the Poisson workload")
     a = ap.parse_args()
     lines = []
     for name in a.models.split(","):
         cfg, m = model_for(name)
         prompts, arrive = workload(a, cfg.vocab_size)
         m.generate_batch([prompts[0][:64]], 4)   # warm-up: code objects, scratch
-        res = [run_engine(m, prompts, arrive, a)]
+        if a.spec:
+            lines += run_spec(m, a, cfg.vocab_size, name)
+            m.close()
+            continue
+        res = [run_engine(m, prompts, arrive, a) for _ in range(a.repeat)]
         if not a.skip_baselines:
             res += [run_serial(m, prompts, a), run_waves(m, prompts, a), run_steady(m, a, cfg.vocab_size), run_long(m, a, cfg.vocab_size)]
         for r in res:
