@@ -10,7 +10,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libaha_hip.so")
-SOURCES = ["kernels_elem.hip", "kernels_gemv.hip", "kernels_attn.hip", "kernels_attn64.hip", "kernels_gemm.hip", "kernels_gemm_sk.hip", "kernels_vit.hip", "kernels_audio.hip", "kernels_sample.hip", "kernels_logprob.hip", "kernels_batch.hip", "kernels_gemv_rows_fp8.hip", "kernels_gemv_fp8.hip", "kernels_gemv_rows_fp4.hip", "kernels_gemv_fp4.hip", "sampler_rng.hip", "sampler_host.hip", "spec_host.hip", "audio_tower.hip", "audio_pre.hip", "image_pre.hip", "tp_rccl.hip", "loader.hip", "model.hip",
+SOURCES = ["kernels_elem.hip", "kernels_gemv.hip", "kernels_attn.hip", "kernels_attn64.hip", "kernels_gemm.hip", "kernels_gemm_sk.hip", "kernels_vit.hip", "kernels_audio.hip", "kernels_sample.hip", "kernels_logprob.hip", "kernels_batch.hip", "kernels_gemv_rows_fp8.hip", "kernels_gemv_fp8.hip", "kernels_gemv_rows_fp4.hip", "kernels_gemv_fp4.hip", "kernels_gemv_pk13.hip", "sampler_rng.hip", "sampler_host.hip", "spec_host.hip", "audio_tower.hip", "audio_pre.hip", "image_pre.hip", "tp_rccl.hip", "loader.hip", "model.hip",
            "vision.hip", "vision_tower.hip", "capi.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value",
          "-Wno-unused-result"]
@@ -23,9 +23,9 @@ FLAGS += [f for f in os.environ.get("AHA_BUILD_DEFINES", "").split() if f.starts
 # values itself for firmware that does not preload.  Only these translation units: every other one compiles exactly as with FLAGS.
 _PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 EXTRA_FLAGS = {"kernels_gemv.hip": _PRELOAD, "kernels_attn.hip": _PRELOAD, "model.hip": _PRELOAD}
-# Sources compiled with the extra flags of another one: the FP8 and FP4 matvecs are the bf16 matvec with another weight load and take their
+# Sources compiled with the extra flags of another one: the FP8, FP4 and 13-bit matvecs are the bf16 matvec with another weight load and take their
 # 14 leading dwords the same way.  (Kept apart from EXTRA_FLAGS, whose keys tests/test_decode_preload_cpu.py pins as the sources that change alone.)
-FLAGS_LIKE = {"kernels_gemv_fp8.hip": "kernels_gemv.hip", "kernels_gemv_fp4.hip": "kernels_gemv.hip"}
+FLAGS_LIKE = {"kernels_gemv_fp8.hip": "kernels_gemv.hip", "kernels_gemv_fp4.hip": "kernels_gemv.hip", "kernels_gemv_pk13.hip": "kernels_gemv.hip"}
 
 
 def _extra_flags(src: str):

@@ -1077,6 +1077,38 @@ int aha_hip_debug_fp8_single(aha_model* m, int on) {
   return AHA_OK;
 }
 
+int aha_hip_debug_pk13_single(aha_model* m, int on) {
+  if (!m) {
+    set_error("debug_pk13_single: null model");
+    return AHA_ERR_INVALID;
+  }
+  if (on < 0 || on > 2) {
+    set_error("debug_pk13_single: on must be 0 (bf16), 1 (by plan) or 2 (every matrix with a copy)");
+    return AHA_ERR_INVALID;
+  }
+  m->pk13_single = on;
+  return AHA_OK;
+}
+
+int aha_hip_pk13_status(const aha_model* m, char* buf, size_t cap) {
+  if (!m || (!buf && cap)) {
+    set_error("pk13_status: null model or buffer");
+    return AHA_ERR_INVALID;
+  }
+  std::string s;
+  int n = 0;
+  for (const Pk13Entry& e : m->pk13) {
+    s += e.name + "\t" + e.status + "\n";
+    n += e.slot->p != nullptr;
+  }
+  if (cap) {
+    const size_t k = std::min(s.size(), cap - 1);
+    memcpy(buf, s.data(), k);
+    buf[k] = 0;
+  }
+  return n;
+}
+
 int aha_hip_debug_fp4_single(aha_model* m, int on) {
   if (!m) {
     set_error("debug_fp4_single: null model");
@@ -1111,6 +1143,20 @@ int aha_hip_debug_plan_gemv_mxfp8(int32_t N, int32_t K, int32_t epi, int32_t has
   return debug_plan_gemv_mx(8, N, K, epi, has_norm, R, U, grid, form, by_plan);
 }
 
+int aha_hip_debug_plan_gemv_pk13(int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form,
+                                 int32_t* by_plan) {
+  if (!R || !U || !grid || epi < 0 || epi > 3 || (epi == 2 && N % 32) || !gemv_pk13_shape_ok(N, K)) {
+    set_error("debug_plan_gemv_pk13: bad argument (N >= 1, K a multiple of 4096 and at most 32768, epi 0..3, epi 2 needs N % 32 == 0)");
+    return AHA_ERR_INVALID;
+  }
+  int o[5];
+  debug_plan_gemv_pk13(epi == 2 ? N / 2 : N, K, (GemvEpi)epi, has_norm != 0, o);
+  *R = o[0]; *U = o[1]; *grid = o[2];
+  if (form) *form = 1 + o[4];
+  if (by_plan) *by_plan = gemv_pk13_by_plan(N, K, (GemvEpi)epi) ? 1 : 0;
+  return AHA_OK;
+}
+
 int aha_hip_debug_plan_gemv_mxfp4(int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form,
                                   int32_t* by_plan) {
   return debug_plan_gemv_mx(4, N, K, epi, has_norm, R, U, grid, form, by_plan);
@@ -1140,9 +1186,10 @@ const char* gemv_epi_args_bad(const void* w, const void* x, const void* y, int N
 }
 }  // namespace
 
-// q: the MXFP8 (mx == 8) or MXFP4 (mx == 4) copy in place of W
+// q: the MXFP8 (mx == 8) or MXFP4 (mx == 4) copy in place of W, or the exact 13-bit copy (mx == 13, its base in pk13_bh)
 static int gemv_epi_run(const void* W, int mx, const void* q, const uint32_t* scales, const void* x, void* y, int32_t N, int32_t K,
-                        int32_t epi, const void* norm_w, float eps, const void* residual, float* logits, uint32_t* argmax_out, void* stream) {
+                        int32_t epi, const void* norm_w, float eps, const void* residual, float* logits, uint32_t* argmax_out, void* stream,
+                        int pk13_bh = 0) {
   hipStream_t st = (hipStream_t)stream;
   GemvArgs g{};
   g.W = W; g.x = x; g.y = y; g.N = epi == 2 ? N / 2 : N; g.K = K; g.norm_w = norm_w; g.eps = eps; g.residual = epi == 1 ? residual : nullptr;
@@ -1151,7 +1198,7 @@ static int gemv_epi_run(const void* W, int mx, const void* q, const uint32_t* sc
   GemvPartials part;
   int tiles = 0;
   if (epi == 3) {
-    tiles = !q ? gemv_num_tiles(N, K) : mx == 8 ? gemv_mxfp8_num_tiles(N, K) : gemv_mxfp4_num_tiles(N, K);
+    tiles = !q ? gemv_num_tiles(N, K) : mx == 8 ? gemv_mxfp8_num_tiles(N, K) : mx == 13 ? gemv_pk13_num_tiles(N, K) : gemv_mxfp4_num_tiles(N, K);
     AHA_HIP_CHECK(hipMalloc(&part.p[0], (size_t)tiles * 4));
     AHA_HIP_CHECK(hipMalloc(&part.p[1], (size_t)tiles * 4));
     g.blk_max = (float*)part.p[0];
@@ -1159,6 +1206,7 @@ static int gemv_epi_run(const void* W, int mx, const void* q, const uint32_t* sc
   }
   if (!q) launch_gemv(g, e, st);
   else if (mx == 8) launch_gemv_mxfp8(g, q, scales, e, st);
+  else if (mx == 13) launch_gemv_pk13(g, q, pk13_bh, e, st);
   else launch_gemv_mxfp4(g, q, scales, e, st);
   if (epi == 3) launch_argmax_partials(g.blk_max, g.blk_idx, tiles, argmax_out, st);
   hipError_t err = hipGetLastError();
@@ -1193,6 +1241,51 @@ int aha_hip_gemv_mxfp8(const void* q, const uint32_t* scales, const void* x, voi
     return AHA_ERR_INVALID;
   }
   return gemv_epi_run(nullptr, 8, q, scales, x, y, N, K, epi, norm_w, eps, residual, logits, argmax_out, stream);
+  API_GUARD_END
+}
+
+int aha_hip_gemv_pk13(const void* packed, int32_t bh, const void* x, void* y, int32_t N, int32_t K, int32_t epi, const void* norm_w,
+                      float eps, const void* residual, float* logits, uint32_t* argmax_out, void* stream) {
+  API_GUARD_BEGIN
+  if (const char* bad = gemv_epi_args_bad(packed, x, y, N, K, 8, epi, residual, logits, argmax_out)) {
+    set_error(std::string("gemv_pk13: ") + bad);
+    return AHA_ERR_INVALID;
+  }
+  if (K % 4096) {
+    set_error("gemv_pk13: K must be a multiple of 4096 (the unit)");
+    return AHA_ERR_INVALID;
+  }
+  if (bh < 0 || bh > 112) {
+    set_error("gemv_pk13: bh must be 0..112");
+    return AHA_ERR_INVALID;
+  }
+  return gemv_epi_run(nullptr, 13, packed, nullptr, x, y, N, K, epi, norm_w, eps, residual, logits, argmax_out, stream, bh);
+  API_GUARD_END
+}
+
+int aha_hip_pack_pk13(const void* W, int32_t N, int32_t K, void* out, int32_t* bh_out, int64_t* bad_out, void* stream) {
+  API_GUARD_BEGIN
+  if (!W || !bh_out || !bad_out || N < 1 || K < 4096 || K % 4096) {
+    set_error("pack_pk13: bad argument (W, bh_out, bad_out not null, N >= 1, K a positive multiple of 4096)");
+    return AHA_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  GemvPartials d;
+  AHA_HIP_CHECK(hipMalloc(&d.p[0], sizeof(Pk13Stats)));
+  AHA_HIP_CHECK(hipMemsetAsync(d.p[0], 0, sizeof(Pk13Stats), st));
+  launch_pk13_stats(W, (int64_t)N * K, (Pk13Stats*)d.p[0], st);
+  AHA_HIP_CHECK(hipGetLastError());
+  Pk13Stats h{};
+  AHA_HIP_CHECK(hipMemcpyAsync(&h, d.p[0], sizeof(h), hipMemcpyDeviceToHost, st));
+  AHA_HIP_CHECK(hipStreamSynchronize(st));
+  *bh_out = pk13_base(h.max_e2);
+  *bad_out = (int64_t)h.bad;
+  if (out && !h.bad) {
+    launch_pk13_pack(W, N, K, *bh_out, out, st);
+    AHA_HIP_CHECK(hipGetLastError());
+    AHA_HIP_CHECK(hipStreamSynchronize(st));
+  }
+  return AHA_OK;
   API_GUARD_END
 }
 

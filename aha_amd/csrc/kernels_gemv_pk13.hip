@@ -1,0 +1,209 @@
+// Batch-1 matvec from an exact 13-bit copy of a bf16 matrix: the single-sequence decode step reads 0.8125 of the weight bytes and
+// computes the same bits.
+//
+// The format, per matrix.  A bf16 weight is s | E(8) | m(7): high byte s | E >> 1, low byte (E & 1) | m.  The low byte is kept verbatim.
+// Of the high byte the sign is kept and E >> 1 is recoded to 4 bits with one base bh per matrix: h = 0 means E >> 1 == 0 (+-0, the bf16
+// subnormals and E = 1), h = 1 .. 15 means E >> 1 == bh + h.  bh = max(E >> 1 over the finite weights) - 15 (at least 0), so the window
+// runs 30 binades down from the matrix maximum; a matrix with a weight outside it (Inf / NaN, or a non-zero E >> 1 at or below bh) is not
+// packed.  The recoding is invertible, so the kernel rebuilds exactly the f32 operands lo_bf / hi_bf give on W.
+//
+// Layout.  Rows in the order of W; a row is K / 4096 units; a unit (one row x 4096 columns = eight 512-column chunks, a lane owning
+// k = chunk * 512 + lane * 8 .. + 7 of each as in gemv_body.h) is 6656 bytes in seven lane-linear pieces:
+//   low bytes   4 x 1 KiB   piece p, lane l: 16 bytes = chunk 2p elements 0..7, chunk 2p + 1 elements 0..7
+//   codes       2 x 1 KiB   piece q, lane l: 4 dwords = chunks 4q .. 4q + 3; byte i of a dword = h[element i] | h[element i + 4] << 4
+//   signs       512 B       lane l: 2 dwords; dword w covers chunks 4w .. 4w + 3: bit ((c & 3) * 2 + (e >> 2)) + 8 * (e & 3) = sign of element e
+// so a lane's 64 weights of a unit arrive as six full-wave 16-byte non-temporal loads and one 8-byte load, and four weights' high bytes are
+// rebuilt in one dword: the codes' low or high nibbles masked to bytes, a non-zero mask, one packed multiply-add by bh, the signs shifted to
+// bits 7 / 15 / 23 / 31 and ORed in; one v_perm_b32 per weight then places high and low byte on top of an f32.
+//
+// Plan: a work item is one unit of each row of the wave (R rows, x 2 for gate / up): 7 * R * NW loads per buffer -- R = 1 for the layer
+// matrices (7, gate+up 14), R = 2 for the lm_head (14).  At most 768 persistent blocks with plan_gemv's whole-rounds rule.
+#include <algorithm>
+
+#include "gemv_pk13_body.h"
+#include "kernels.h"
+
+namespace aha {
+
+namespace {
+
+// as GemvFp8TailArgs: what is first used behind the first weight request
+struct GemvPk13TailArgs {
+  float* y_f32;
+  float* blk_max;
+  uint32_t* blk_idx;
+  void* h_out;
+  float eps;
+  int nblk;
+};
+
+template <int R, int EPI, int PRO>
+__global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel_pk13(const void* p, const void* x, const void* norm_w, void* y, const void* residual,
+                                                                 int N, int K, int bh, GemvPk13TailArgs t) {
+  extern __shared__ __attribute__((aligned(16))) float xs[];  // K f32 + 8 floats reduction scratch
+  GemvPk13Args a;
+  a.p = p; a.x = x; a.norm_w = norm_w; a.residual = residual; a.y = y;
+  a.y_f32 = t.y_f32; a.blk_max = t.blk_max; a.blk_idx = t.blk_idx; a.h_out = t.h_out; a.N = N; a.K = K; a.bh = bh; a.eps = t.eps;
+  gemv_pk13_body<R, EPI, PRO>(a, xs, (int)blockIdx.x, t.nblk);
+}
+
+struct GemvPk13Plan { int R, grid; };
+
+GemvPk13Plan plan_gemv_pk13(int N, GemvEpi epi) {
+  const int R = epi == GEMV_LOGITS ? 2 : 1;
+  const int gmax = 768;
+  const int ntiles = (N + 4 * R - 1) / (4 * R);
+  int grid = std::min(ntiles, gmax);
+  // whole rounds, as plan_gemv: the largest grid in [gmax / 2, gmax] that divides the tile count, multiples of 8 only
+  if (ntiles > gmax) {
+    for (int g = gmax; g >= gmax / 2; g -= 8)
+      if (ntiles % g == 0) {
+        grid = g;
+        break;
+      }
+  }
+  return {R, std::max(grid, 1)};
+}
+
+int pro_of(int K, bool has_norm) { return K <= (has_norm ? 4 : 8) * 8 * GEMV_THREADS ? (has_norm ? 2 : 1) : 0; }
+
+template <int R, int EPI>
+void launch_pk13_epi(const GemvPk13Args& a, const GemvPk13Plan& p, hipStream_t st) {
+  const size_t lds = (size_t)a.K * 4 + 64;
+  dim3 grid(p.grid), block(GEMV_THREADS);
+  const GemvPk13TailArgs t{a.y_f32, a.blk_max, a.blk_idx, a.h_out, a.eps, p.grid};
+  const int pro = pro_of(a.K, a.norm_w != nullptr);
+#define GV_(PP) hipLaunchKernelGGL((gemv_kernel_pk13<R, EPI, PP>), grid, block, lds, st, a.p, a.x, a.norm_w, a.y, a.residual, a.N, a.K, a.bh, t)
+  if (pro == 2) GV_(2); else if (pro == 1) GV_(1); else GV_(0);
+#undef GV_
+}
+
+// ---- the check and the pack (once per matrix, when a model is created) ------------------------------------------------------------------
+__device__ __forceinline__ int pk13_e2(uint32_t bits16) { return (bits16 >> 8) & 0x7f; }
+
+// pass 1: max of E >> 1 over the finite weights, count of Inf / NaN
+__global__ __launch_bounds__(256) void pk13_max_kernel(const u32x4_t* w, int64_t nvec, Pk13Stats* out) {
+  int mx = 0;
+  unsigned long long bad = 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+    const u32x4_t v = ld_nt16(w + i);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t b = (v[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+      if ((b & 0x7f80u) == 0x7f80u) ++bad;
+      else mx = max(mx, pk13_e2(b));
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    mx = max(mx, __shfl_xor(mx, o));
+    bad += __shfl_xor(bad, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicMax(&out->max_e2, mx);
+    if (bad) atomicAdd(&out->bad, bad);
+  }
+}
+
+// pass 2: count of finite weights below the window of pass 1's maximum
+__global__ __launch_bounds__(256) void pk13_window_kernel(const u32x4_t* w, int64_t nvec, Pk13Stats* out) {
+  const int bh = pk13_base(out->max_e2);
+  unsigned long long bad = 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+    const u32x4_t v = ld_nt16(w + i);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t b = (v[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+      const int e2 = pk13_e2(b);
+      if ((b & 0x7f80u) != 0x7f80u && e2 != 0 && e2 <= bh) ++bad;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
+  if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&out->bad, bad);
+}
+
+// thread = (unit, lane): reads the lane's 8 k of the unit's eight chunks, writes its seven pieces
+__global__ __launch_bounds__(256) void pk13_pack_kernel(const bf16_t* w, int64_t nunits, int bh, uint8_t* out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t unit = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (unit >= nunits) return;
+  const bf16_t* src = w + unit * PK13_UNIT_K + lane * 8;   // units of a row are consecutive: unit u starts at element u * 4096
+  uint8_t* dst = out + unit * PK13_UNIT_BYTES;
+  u32x4_t a[4], h[2];
+  uint32_t s[2] = {0u, 0u};
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const u32x4_t v = ld16(src + c * 512);
+    uint32_t lo[2] = {0u, 0u}, hd = 0u;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const uint32_t b = (v[e >> 1] >> ((e & 1) * 16)) & 0xffffu;
+      const int e2 = pk13_e2(b);
+      const uint32_t code = e2 == 0 ? 0u : (uint32_t)(e2 - bh) & 15u;
+      lo[e >> 2] |= (b & 0xffu) << (8 * (e & 3));
+      hd |= code << (8 * (e & 3) + 4 * (e >> 2));
+      s[c >> 2] |= (b >> 15) << ((c & 3) * 2 + (e >> 2) + 8 * (e & 3));
+    }
+    a[c >> 1][(c & 1) * 2] = lo[0];
+    a[c >> 1][(c & 1) * 2 + 1] = lo[1];
+    h[c >> 2][c & 3] = hd;
+  }
+#pragma unroll
+  for (int p = 0; p < 4; ++p) *reinterpret_cast<u32x4_t*>(dst + p * 1024 + lane * 16) = a[p];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) *reinterpret_cast<u32x4_t*>(dst + PK13_OFF_H + q * 1024 + lane * 16) = h[q];
+  *reinterpret_cast<pk13_u32x2_t*>(dst + PK13_OFF_S + lane * 8) = pk13_u32x2_t{s[0], s[1]};
+}
+
+}  // namespace
+
+size_t pk13_bytes(int N, int K) { return (size_t)N * (K / PK13_UNIT_K) * PK13_UNIT_BYTES; }
+
+void launch_pk13_stats(const void* w, int64_t n_elems, Pk13Stats* stats, hipStream_t st) {
+  const int64_t nvec = n_elems / 8;
+  const int grid = (int)std::min<int64_t>((nvec + 255) / 256, 4096);
+  hipLaunchKernelGGL(pk13_max_kernel, dim3(grid), dim3(256), 0, st, (const u32x4_t*)w, nvec, stats);
+  hipLaunchKernelGGL(pk13_window_kernel, dim3(grid), dim3(256), 0, st, (const u32x4_t*)w, nvec, stats);
+}
+
+void launch_pk13_pack(const void* w, int N, int K, int bh, void* out, hipStream_t st) {
+  const int64_t nunits = (int64_t)N * (K / PK13_UNIT_K);
+  hipLaunchKernelGGL(pk13_pack_kernel, dim3((unsigned)((nunits + 3) / 4)), dim3(256), 0, st, (const bf16_t*)w, nunits, bh, (uint8_t*)out);
+}
+
+// The shapes the kernel takes: whole units, an activation vector that fits the LDS image
+bool gemv_pk13_shape_ok(int N, int K) { return N >= 1 && K >= PK13_UNIT_K && K % PK13_UNIT_K == 0 && K <= 32768; }
+
+// Which matrices the model hands to this kernel by default: those of at least 2^25 elements in whole units.  Measured per matrix on an
+// MI355X, 20 alternating launches per form (scripts/bench_gemv.py FORMS=pk13; the rule: packed p90 below bf16 p10; profiles/weights_pk13.md):
+// of Qwen3-8B's decode matrices gate+up (100.7 M elements: 39.0 -> 33.9 us), down_proj (50.3 M: 22.7 -> 21.2) and lm_head (622 M: 227 -> 197)
+// win; qkv (25.2 M: 16.0 -> 15.9, the ranges overlap) and o_proj (16.8 M: 12.9 -> 13.7) do not -- two rounds of tiles per block, where the
+// decoding of the last round is not hidden behind loads -- and stay on bf16.  Nothing between 25.2 M and 50.3 M elements was measured except
+// that 2^25 itself is where the two-layer test model's gate+up sits; the line is drawn there.  N: matrix rows (gate+up: 2I).
+bool gemv_pk13_by_plan(int N, int K, GemvEpi epi) {
+  (void)epi;
+  return gemv_pk13_shape_ok(N, K) && (int64_t)N * K >= ((int64_t)1 << 25);
+}
+
+int gemv_pk13_num_tiles(int N, int K) { (void)K; return plan_gemv_pk13(N, GEMV_LOGITS).grid; }
+
+void debug_plan_gemv_pk13(int N, int K, GemvEpi epi, bool has_norm, int* out5) {
+  const GemvPk13Plan p = plan_gemv_pk13(N, epi);
+  out5[0] = p.R; out5[1] = 8; out5[2] = p.grid; out5[3] = 1; out5[4] = pro_of(K, has_norm);
+}
+
+void launch_gemv_pk13(const GemvArgs& g, const void* packed, int bh, GemvEpi epi, hipStream_t st) {
+  if (!gemv_pk13_shape_ok(g.N, g.K)) abort();   // the callers check the shape
+  GemvPk13Args a{};
+  a.p = packed; a.x = g.x; a.norm_w = g.norm_w; a.residual = g.residual; a.y = g.y; a.y_f32 = g.y_f32;
+  a.blk_max = g.blk_max; a.blk_idx = g.blk_idx; a.h_out = g.h_out; a.N = g.N; a.K = g.K; a.bh = bh; a.eps = g.eps;
+  const GemvPk13Plan p = plan_gemv_pk13(g.N, epi);
+  switch (epi) {
+    case GEMV_STORE: launch_pk13_epi<1, GEMV_STORE>(a, p, st); break;
+    case GEMV_RESIDUAL: launch_pk13_epi<1, GEMV_RESIDUAL>(a, p, st); break;
+    case GEMV_SILU_MUL: launch_pk13_epi<1, GEMV_SILU_MUL>(a, p, st); break;
+    case GEMV_LOGITS: launch_pk13_epi<2, GEMV_LOGITS>(a, p, st); break;
+    default: abort();   // GEMV_PARTIAL_F32: sharded models have no copies
+  }
+}
+
+}  // namespace aha

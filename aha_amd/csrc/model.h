@@ -28,6 +28,12 @@ void set_error(const std::string& msg);
     }                                                                                                \
   } while (0)
 
+struct Pk13Copy {
+  void* p = nullptr;   // pk13_bytes(N, K), a hipMalloc of its own (freed by model_free_packed)
+  int bh = 0;          // the matrix's exponent base
+};
+struct Pk13Entry { std::string name; Pk13Copy* slot; std::string status; };   // aha_hip_pk13_status: "packed" or the reason it is not
+
 struct LayerWeights {
   void* wqkv = nullptr;     // ((nh+2kvh)*d, H): q rows, then k rows, then v rows
   void* wo = nullptr;       // (H, nh*d)
@@ -40,6 +46,8 @@ struct LayerWeights {
   // MXFP8 or MXFP4 copies of the four matrices (aha_hip_model_quantize_weights; null: none; the format is aha_model::wq_format): the batched
   // decode matvec streams these
   WQuant q_wqkv, q_wo, q_wgu, q_wdown;
+  // exact 13-bit copies (kernels_gemv_pk13.hip; model_pack_weights; null: none): the single-sequence matvec streams these
+  Pk13Copy p_wqkv, p_wo, p_wgu, p_wdown;
 };
 
 // device-resident scalars every decode kernel reads (so a step can be enqueued / replayed without host values)
@@ -87,6 +95,12 @@ struct aha_model {
   bool fp8_rows = true;      // aha_hip_debug_fp8_rows: false = the bf16 matvec on W' although a copy (of either format) exists
   int fp8_single = 1;        // aha_hip_debug_fp8_single, the single-sequence matvec (enqueue_decode_step, enqueue_lm_head): 0 = bf16 on W',
                              // 1 = the FP8 kernel where the plan takes the shape (gemv_mxfp8_by_plan), 2 = wherever a copy exists; MXFP8 models only
+  // Exact 13-bit copies of the four layer matrices and lm_head, made when the model is created (model_pack_weights; a bf16 model only:
+  // aha_hip_model_quantize_weights frees them).  pk13_single (aha_hip_debug_pk13_single): 0 = the bf16 kernel, 1 = the packed kernel where
+  // the plan takes the shape (gemv_pk13_by_plan), 2 = wherever a copy exists
+  aha::Pk13Copy p_lm_head;
+  std::vector<aha::Pk13Entry> pk13;
+  int pk13_single = 1;
   int fp4_single = 1;        // aha_hip_debug_fp4_single: the same three values for an MXFP4 model and gemv_mxfp4_kernel (gemv_mxfp4_by_plan)
   // rope constants
   float* d_inv_freq = nullptr;

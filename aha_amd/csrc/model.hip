@@ -546,6 +546,104 @@ int model_clear_cache(aha_model* m) {
   return AHA_OK;
 }
 
+// Exact 13-bit copies (kernels_gemv_pk13.hip).  model_free_packed drops them all: the matrices are about to change, or the model goes.
+static void model_free_packed(aha_model* m, const char* why) {
+  for (Pk13Entry& e : m->pk13) {
+    if (e.slot->p) {
+      hipFree(e.slot->p);
+      e.status = why;
+    }
+    *e.slot = Pk13Copy{};
+  }
+}
+
+// Called once, at the end of model_create: the four layer matrices and lm_head of an unsharded model get a copy each if the matrix is
+// large enough, in whole units, inside the format's window, and the device has the copies' bytes plus a tenth more free -- else the model
+// keeps reading bf16, and aha_hip_pk13_status says why.  AHA_WPACK=0 makes no copies.
+static int model_pack_weights(aha_model* m) {
+  const aha_model_desc& c = m->desc;
+  struct Mat { const void* w; int N, K; };
+  std::vector<Mat> mats;
+  const int H = c.hidden_size, I = c.intermediate_size, nq = c.num_attention_heads * c.head_dim, nkv = c.num_key_value_heads * c.head_dim;
+  for (int li = 0; li < c.num_hidden_layers; ++li) {
+    LayerWeights& L = m->layers[li];
+    const std::string p = "layers." + std::to_string(li) + ".";
+    m->pk13.push_back({p + "self_attn.q_proj/k_proj/v_proj.weight", &L.p_wqkv, ""});
+    mats.push_back({L.wqkv, nq + 2 * nkv, H});
+    m->pk13.push_back({p + "self_attn.o_proj.weight", &L.p_wo, ""});
+    mats.push_back({L.wo, H, nq});
+    m->pk13.push_back({p + "mlp.gate_proj/up_proj.weight", &L.p_wgu, ""});
+    mats.push_back({L.wgu, 2 * I, H});
+    m->pk13.push_back({p + "mlp.down_proj.weight", &L.p_wdown, ""});
+    mats.push_back({L.wdown, H, I});
+  }
+  m->pk13.push_back({c.tie_word_embeddings ? "embed_tokens.weight (tied lm_head)" : "lm_head.weight", &m->p_lm_head, ""});
+  mats.push_back({m->lm_head, m->lm_rows, H});
+  auto all = [&](const char* why) {
+    for (Pk13Entry& e : m->pk13)
+      if (e.status.empty()) e.status = why;
+    return AHA_OK;
+  };
+  const char* env = getenv("AHA_WPACK");
+  if (env && atoi(env) == 0) return all("off (AHA_WPACK=0)");
+  if (m->tp_size > 1 || m->cp_size > 1) return all("sharded model");
+  std::vector<size_t> cand;
+  for (size_t i = 0; i < mats.size(); ++i) {
+    if (!gemv_pk13_shape_ok(mats[i].N, mats[i].K)) m->pk13[i].status = "K is not a multiple of 4096 (or above 32768)";
+    else if ((int64_t)mats[i].N * mats[i].K < ((int64_t)1 << 24)) m->pk13[i].status = "fewer than 2^24 elements";
+    else cand.push_back(i);
+  }
+  if (cand.empty()) return AHA_OK;
+  hipStream_t st = m->stream;
+  std::vector<Pk13Stats> h(cand.size());
+  {
+    Pk13Stats* d = nullptr;
+    if (hipMalloc((void**)&d, cand.size() * sizeof(Pk13Stats)) != hipSuccess) {
+      (void)hipGetLastError();
+      return all("not enough device memory");
+    }
+    hipError_t e = hipMemsetAsync(d, 0, cand.size() * sizeof(Pk13Stats), st);
+    for (size_t k = 0; k < cand.size() && e == hipSuccess; ++k) launch_pk13_stats(mats[cand[k]].w, (int64_t)mats[cand[k]].N * mats[cand[k]].K, d + k, st);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d, cand.size() * sizeof(Pk13Stats), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    hipFree(d);
+    AHA_HIP_CHECK(e);
+  }
+  std::vector<size_t> take;
+  size_t bytes = 0;
+  for (size_t k = 0; k < cand.size(); ++k) {
+    if (h[k].bad) {
+      m->pk13[cand[k]].status = std::to_string(h[k].bad) + " weights outside the window (Inf, NaN, or more than 30 binades below the matrix maximum)";
+      continue;
+    }
+    m->pk13[cand[k]].slot->bh = pk13_base(h[k].max_e2);
+    take.push_back(cand[k]);
+    bytes += pk13_bytes(mats[cand[k]].N, mats[cand[k]].K);
+  }
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+    (void)hipGetLastError();
+    free_b = 0;
+  }
+  if (take.empty()) return AHA_OK;
+  if ((double)free_b < 1.1 * (double)bytes) return all("not enough device memory");
+  for (size_t i : take) {
+    if (hipMalloc(&m->pk13[i].slot->p, pk13_bytes(mats[i].N, mats[i].K)) != hipSuccess) {
+      (void)hipGetLastError();
+      m->pk13[i].slot->p = nullptr;
+      model_free_packed(m, "not enough device memory");
+      return all("not enough device memory");
+    }
+    launch_pk13_pack(mats[i].w, mats[i].N, mats[i].K, m->pk13[i].slot->bh, m->pk13[i].slot->p, st);
+    m->pk13[i].status = "packed";
+  }
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  AHA_HIP_CHECK(e);
+  return AHA_OK;
+}
+
 // aha_hip_model_quantize_weights (include/aha_hip.h): every check first, then every allocation, then the matrices one by one -- W becomes
 // W' in place (the quantiser reads an element before it writes it), its (q, scales) copy lands in the matrix's slot.
 int model_quantize_weights(aha_model* m, int32_t format, uint32_t flags) {
@@ -641,6 +739,12 @@ int model_quantize_weights(aha_model* m, int32_t format, uint32_t flags) {
       else wq[i].scales = (uint32_t*)p;
     }
   }
+  // the matrices change from here on: a quantised model never reads the exact copies of what they were
+  if (const hipError_t es = hipStreamSynchronize(st); es != hipSuccess) {
+    for (void* q : got) hipFree(q);
+    AHA_HIP_CHECK(es);
+  }
+  model_free_packed(m, "freed by quantize_weights");
   for (size_t i = 0; i < mats.size(); ++i) {
     if (fp4) launch_mxfp4_quantize(mats[i].w, mats[i].N, mats[i].K, wq[i].q, wq[i].scales, mats[i].w, st);
     else launch_mxfp8_quantize(mats[i].w, mats[i].N, mats[i].K, wq[i].q, wq[i].scales, mats[i].w, st);
@@ -861,7 +965,7 @@ int model_create(aha_ctx* ctx, const aha_model_desc* desc, const aha_tensor_view
   m->d_partial = (float*)p;
   if ((rc = dev_alloc(m, (size_t)c.vocab_size * 4, &p))) return fail(rc);
   m->d_logits = (float*)p;
-  const int nt = std::max(std::max(std::max(gemv_num_tiles(c.vocab_size, H), gemv_mxfp8_num_tiles(c.vocab_size, H)), gemv_mxfp4_num_tiles(c.vocab_size, H)), 512);
+  const int nt = std::max(std::max(std::max(gemv_num_tiles(c.vocab_size, H), gemv_mxfp8_num_tiles(c.vocab_size, H)), gemv_mxfp4_num_tiles(c.vocab_size, H)), std::max(gemv_pk13_num_tiles(c.vocab_size, H), 512));
   if ((rc = dev_alloc(m, (size_t)nt * 4, &p))) return fail(rc);
   m->d_blk_max = (float*)p;
   if ((rc = dev_alloc(m, (size_t)nt * 4, &p))) return fail(rc);
@@ -886,6 +990,7 @@ int model_create(aha_ctx* ctx, const aha_model_desc* desc, const aha_tensor_view
   if (c.arch == AHA_ARCH_QWEN3ASR) {
     if ((rc = audio_create(m, w, nw))) return fail(rc);
   }
+  if ((rc = model_pack_weights(m))) return fail(rc);
   if (hipStreamSynchronize(m->stream) != hipSuccess) {
     set_error(std::string("model_create: ") + hipGetErrorString(hipGetLastError()));
     return fail(AHA_ERR_HIP);
@@ -902,6 +1007,7 @@ void model_destroy(aha_model* m) {
   vision_destroy(m);
   audio_destroy(m);
   tp_destroy(m);
+  model_free_packed(m, "freed");
   for (void* p : m->owned) hipFree(p);
   for (void* p : m->pf_owned) hipFree(p);
   if (m->p_pass_tab) hipFree(m->p_pass_tab);
@@ -986,13 +1092,20 @@ static bool fp8_single(const aha_model* m, const WQuant& wq, int rows, int K, Ge
 static bool fp4_single(const aha_model* m, const WQuant& wq, int rows, int K, GemvEpi epi) {
   return wq.q != nullptr && m->wq_format == AHA_WQ_MXFP4_E2M1 && m->tp_size <= 1 && (m->fp4_single == 2 || (m->fp4_single == 1 && gemv_mxfp4_by_plan(rows, K, epi)));
 }
-static void decode_gemv(aha_model* m, const GemvArgs& g, GemvEpi epi, const WQuant& wq, double act_bytes) {
+// An exact 13-bit copy (a bf16 model only: quantising frees them) goes the same way through aha_hip_debug_pk13_single and gemv_pk13_by_plan,
+// and stays in class gemv with the 1.625 bytes per weight it reads: the same matrix, the same bits.
+static bool pk13_single(const aha_model* m, const Pk13Copy& pk, int rows, int K, GemvEpi epi) {
+  return pk.p != nullptr && m->wq_format == AHA_WQ_NONE && m->tp_size <= 1 && gemv_pk13_shape_ok(rows, K) &&
+         (m->pk13_single == 2 || (m->pk13_single == 1 && gemv_pk13_by_plan(rows, K, epi)));
+}
+static void decode_gemv(aha_model* m, const GemvArgs& g, GemvEpi epi, const WQuant& wq, const Pk13Copy& pk, double act_bytes) {
   const double weights = (epi == GEMV_SILU_MUL ? 2.0 : 1.0) * g.N * g.K;
   const int rows = (epi == GEMV_SILU_MUL ? 2 : 1) * g.N;
-  const bool fp8 = fp8_single(m, wq, rows, g.K, epi), fp4 = fp4_single(m, wq, rows, g.K, epi);
-  ProfScope ps(m, fp8 ? "gemv_fp8" : fp4 ? "gemv_fp4" : "gemv", weights * (fp8 ? 1.03125 : fp4 ? 0.53125 : 2.0) + act_bytes, 2.0 * weights);
+  const bool fp8 = fp8_single(m, wq, rows, g.K, epi), fp4 = fp4_single(m, wq, rows, g.K, epi), p13 = pk13_single(m, pk, rows, g.K, epi);
+  ProfScope ps(m, fp8 ? "gemv_fp8" : fp4 ? "gemv_fp4" : "gemv", weights * (fp8 ? 1.03125 : fp4 ? 0.53125 : p13 ? 1.625 : 2.0) + act_bytes, 2.0 * weights);
   if (fp8) launch_gemv_mxfp8(g, wq.q, wq.scales, epi, m->stream);
   else if (fp4) launch_gemv_mxfp4(g, wq.q, wq.scales, epi, m->stream);
+  else if (p13) launch_gemv_pk13(g, pk.p, pk.bh, epi, m->stream);
   else if (epi == GEMV_RESIDUAL) gemv_row_parallel(m, g);
   else launch_gemv(g, epi, m->stream);
 }
@@ -1001,6 +1114,7 @@ static int lm_head_partials(const aha_model* m) {
   const int N = m->lm_rows, K = m->desc.hidden_size;
   if (fp8_single(m, m->q_lm_head, N, K, GEMV_LOGITS)) return gemv_mxfp8_num_tiles(N, K);
   if (fp4_single(m, m->q_lm_head, N, K, GEMV_LOGITS)) return gemv_mxfp4_num_tiles(N, K);
+  if (pk13_single(m, m->p_lm_head, N, K, GEMV_LOGITS)) return gemv_pk13_num_tiles(N, K);
   return gemv_num_tiles(N, K);
 }
 
@@ -1019,7 +1133,7 @@ static void enqueue_lm_head(aha_model* m, const void* x_last, bool argmax = true
   g.blk_max = m->d_blk_max;
   g.blk_idx = m->d_blk_idx;
   g.h_out = m->d_hlast;
-  decode_gemv(m, g, GEMV_LOGITS, m->q_lm_head, c.hidden_size * 2 + m->lm_rows * 4.0);
+  decode_gemv(m, g, GEMV_LOGITS, m->q_lm_head, m->p_lm_head, c.hidden_size * 2 + m->lm_rows * 4.0);
   if (!argmax) return;   // the caller reduces the partials itself (step_tail_kernel)
   ProfScope ps(m, "argmax", 0, 0);
   const int ntiles = lm_head_partials(m);
@@ -1540,7 +1654,7 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const float* __restrict_
 
 // AHA_GEMV_TRACE=1: in-kernel timeline of the decode matvecs (launch-per-op path), dumped by fetch_outputs.  The bf16 kernel only:
 // gemv_mxfp8_kernel and gemv_mxfp4_kernel have no trace stamps, so a launch that decode_gemv sends to either leaves its slot as it was
-// (gemv_trace_dump says so).
+// (gemv_trace_dump says so).  Nor has gemv_kernel_pk13: AHA_WPACK=0 or aha_hip_debug_pk13_single(m, 0) traces the bf16 kernel on the same weights.
 static unsigned long long* gemv_trace_slot(aha_model* m, int launch_idx) {
   static const char* e = getenv("AHA_GEMV_TRACE");
   if (!e || !atoi(e)) return nullptr;
@@ -1613,7 +1727,7 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = 
       GemvArgs g{};
       g.W = L.wqkv; g.x = m->d_x; g.norm_w = L.in_norm; g.eps = c.rms_norm_eps; g.y = m->d_qkv; g.N = nq + 2 * nkv; g.K = H;
       g.trace = gemv_trace_slot(m, li * 4 + 0);
-      decode_gemv(m, g, GEMV_STORE, L.q_wqkv, g.K * 4.0 + g.N * 2.0);
+      decode_gemv(m, g, GEMV_STORE, L.q_wqkv, L.p_wqkv, g.K * 4.0 + g.N * 2.0);
     }
     if (m->decode_fused) {
       // q/k norm + rope + KV append + attention over the paged cache (modules.rs:544-574, 757-813), then
@@ -1648,7 +1762,7 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = 
         ProfScope ps(m, "attn_decode", attn_bytes, 4.0 * kv_len_after * nq);
         launch_attn_decode_fused(a, st);
       }
-      decode_gemv(m, g, GEMV_RESIDUAL, L.q_wo, g.K * 2.0 + g.N * 4.0);
+      decode_gemv(m, g, GEMV_RESIDUAL, L.q_wo, L.p_wo, g.K * 2.0 + g.N * 4.0);
     } else {  // three-launch variant (A/B knob AHA_DECODE_FUSED=0)
       {  // q/k norm + rope + append                            (modules.rs:544-566)
         RopeArgs r{};
@@ -1669,20 +1783,20 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = 
       {  // x = x + attn Wo^T                                    (modules.rs:577, qwen3/model.rs:81)
         GemvArgs g{};
         g.W = L.wo; g.x = m->d_attn; g.residual = m->d_x; g.y = m->d_x; g.N = H; g.K = nq;
-        decode_gemv(m, g, GEMV_RESIDUAL, L.q_wo, g.K * 2.0 + g.N * 4.0);
+        decode_gemv(m, g, GEMV_RESIDUAL, L.q_wo, L.p_wo, g.K * 2.0 + g.N * 4.0);
       }
     }
     {  // act = silu(h Wg^T) * (h Wu^T), h = RMSNorm(x)        (qwen3/model.rs:83, modules.rs:81-84)
       GemvArgs g{};
       g.W = L.wgu; g.W2 = nullptr; g.x = m->d_x; g.norm_w = L.post_norm; g.eps = c.rms_norm_eps; g.y = m->d_act; g.N = I; g.K = H;
       g.trace = gemv_trace_slot(m, li * 4 + 2);
-      decode_gemv(m, g, GEMV_SILU_MUL, L.q_wgu, H * 4.0 + I * 2.0);
+      decode_gemv(m, g, GEMV_SILU_MUL, L.q_wgu, L.p_wgu, H * 4.0 + I * 2.0);
     }
     {  // x = x + act Wd^T                                     (modules.rs:85, qwen3/model.rs:86)
       GemvArgs g{};
       g.W = L.wdown; g.x = m->d_act; g.residual = m->d_x; g.y = m->d_x; g.N = H; g.K = I;
       g.trace = gemv_trace_slot(m, li * 4 + 3);
-      decode_gemv(m, g, GEMV_RESIDUAL, L.q_wdown, g.K * 2.0 + g.N * 4.0);
+      decode_gemv(m, g, GEMV_RESIDUAL, L.q_wdown, L.p_wdown, g.K * 2.0 + g.N * 4.0);
     }
   }
   if (!tail) {

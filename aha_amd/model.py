@@ -625,6 +625,20 @@ class HipInferenceModel:
         launches: "gemv_fp8"."""
         check(lib().aha_hip_debug_fp8_single(self.handle, int(on)))
 
+    def debug_pk13_single(self, on=True) -> None:
+        """The switch of the single-sequence decode matvec for the exact 13-bit weight copies made when the model was created.  True / 1 (the
+        default): the packed kernel on the matrices whose shape its plan takes; 2: on every matrix with a copy; False / 0: the bf16 kernel.
+        The same bits in all three; the launches stay in profile class "gemv"."""
+        check(lib().aha_hip_debug_pk13_single(self.handle, int(on)))
+
+    def pk13_status(self):
+        """{tensor name: "packed" or the reason the matrix has no exact 13-bit copy} (aha_hip_pk13_status)."""
+        buf = C.create_string_buffer(1 << 16)
+        n = lib().aha_hip_pk13_status(self.handle, buf, len(buf))
+        if n < 0:
+            check(n)
+        return dict(line.split("\t", 1) for line in buf.value.decode().splitlines())
+
     def debug_fp4_single(self, on=True) -> None:
         """Test hook: debug_fp8_single's twin for a model with MXFP4 copies (the FP8 switch reads FP8 copies only).  True / 1 (the default):
         the FP4 kernel on the matrices whose shape its plan takes; 2: on every matrix with a copy; False / 0: the bf16 kernel on W'.  The

@@ -521,6 +521,46 @@ def gemv_mxfp8_by_plan(N: int, K: int, epi: int = GEMV_ROWS_STORE) -> bool:
     return bool(b.value)
 
 
+def pack_pk13(W: torch.Tensor, check_only: bool = False):
+    """The exact 13-bit copy of a bf16 matrix W (N, K) on the GPU, K % 4096 == 0 (aha_hip_pack_pk13; quant.pack_pk13 is its restatement):
+    (packed (N, K / 4096, 6656) uint8 or None, bh, bad).  bad != 0: W holds that many weights the format cannot keep, and nothing is packed."""
+    _chk(W)
+    N, K = W.shape
+    bh, bad = C.c_int32(), C.c_int64()
+    out = None if check_only else torch.zeros(N, K // 4096, 6656, dtype=torch.uint8, device=W.device)
+    check(lib().aha_hip_pack_pk13(_ptr(W), N, K, _ptr(out), C.byref(bh), C.byref(bad), _stream()))
+    return (out if bad.value == 0 else None), bh.value, bad.value
+
+
+def gemv_pk13(packed: torch.Tensor, bh: int, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, norm_w: Optional[torch.Tensor] = None,
+              eps: float = 1e-6, residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """gemv_epi from the exact 13-bit copy of W (aha_hip_gemv_pk13): packed (N, K / 4096, 6656) uint8 and its base bh.  Every output bit,
+    and the argmax, equals gemv_epi(W, ...)."""
+    _chk(packed, x, norm_w, residual, out)
+    N, K = packed.shape[0], packed.shape[1] * 4096
+    y, logits, am = _gemv_epi_outputs(N, epi, x.device, out)
+    check(lib().aha_hip_gemv_pk13(_ptr(packed), bh, _ptr(x), _ptr(y), N, K, epi, _ptr(norm_w), eps, _ptr(residual), _ptr(logits), _ptr(am),
+                                  _stream()))
+    return (logits, int(am.item())) if epi == GEMV_ROWS_LOGITS else y
+
+
+def plan_gemv_pk13(N: int, K: int, epi: int = GEMV_ROWS_STORE, has_norm: bool = False):
+    """Host only: (R, U, grid, form) gemv_pk13 picks for a matrix of N rows (aha_hip_debug_plan_gemv_pk13): U is 8, form 1 FAST, 2 / 3 FAST
+    with the straight-line prologue without / with norm weights."""
+    r, u, g, f = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib().aha_hip_debug_plan_gemv_pk13(N, K, epi, int(has_norm), C.byref(r), C.byref(u), C.byref(g), C.byref(f), None))
+    return r.value, u.value, g.value, f.value
+
+
+def gemv_pk13_by_plan(N: int, K: int, epi: int = GEMV_ROWS_STORE) -> bool:
+    """Host only: does a model's single-sequence step read a matrix of N rows (gate+up: 2I) and K columns from its exact 13-bit copy?"""
+    if N < 1 or K < 4096 or K % 4096 or K > 32768:      # not a shape of the kernel at all
+        return False
+    r, b = C.c_int32(), C.c_int32()
+    check(lib().aha_hip_debug_plan_gemv_pk13(N, K, epi, 0, C.byref(r), C.byref(r), C.byref(r), None, C.byref(b)))
+    return bool(b.value)
+
+
 def gemv_mxfp4(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, norm_w: Optional[torch.Tensor] = None,
                eps: float = 1e-6, residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
     """gemv_epi from the MXFP4 copy of W (aha_hip_gemv_mxfp4): q (N, K / 2) uint8 packed E2M1 codes, scales (N, K / 32) uint8 in the

@@ -153,3 +153,72 @@ def scales_from_kernel(words: torch.Tensor, K: int) -> torch.Tensor:
     """The inverse of scales_to_kernel for a matrix with K columns."""
     N = words.shape[0]
     return words.cpu().contiguous().view(torch.uint8).reshape(N, -1)[:, :K // BLOCK].contiguous()
+
+
+# ---- exact 13-bit copies (aha_amd/csrc/kernels_gemv_pk13.hip) ----------------------------------------------------------------------------
+# A bf16 weight is s | E(8) | m(7).  The copy keeps the low byte (E & 1) | m and the sign, and recodes E >> 1 to a 4-bit code h with one
+# base bh per matrix: h = 0 means E >> 1 == 0 (+-0, subnormals, E = 1), h = 1 .. 15 means E >> 1 == bh + h.  Nothing is rounded: unpack_pk13
+# gives W back bit for bit.  The device kernels (aha_hip_pack_pk13) equal check_pk13 / pack_pk13 byte for byte.
+PK13_UNIT_K = 4096        # columns of a unit: eight 512-column chunks of one row; a lane owns k = chunk * 512 + lane * 8 .. + 7 of each
+PK13_UNIT_BYTES = 6656    # 4 x 1 KiB low bytes, 2 x 1 KiB codes, 512 B signs
+PK13_OFF_H, PK13_OFF_S = 4096, 6144
+
+
+def _bf16_bits(W: torch.Tensor) -> torch.Tensor:
+    assert W.dtype == torch.bfloat16 and W.dim() == 2
+    return W.contiguous().view(torch.int16).to(torch.int32) & 0xffff
+
+
+def check_pk13(W: torch.Tensor) -> Tuple[int, int]:
+    """(bh, bad): the base the matrix maximum gives -- max(0, max of E >> 1 over the finite weights - 15) -- and the number of weights the
+    format cannot hold: Inf / NaN, and non-zero E >> 1 at or below bh (more than 30 binades below the maximum).  Pack only if bad == 0."""
+    bits = _bf16_bits(W)
+    e2 = (bits >> 8) & 0x7f
+    nonfinite = (bits & 0x7f80) == 0x7f80
+    finite_e2 = e2[~nonfinite]
+    bh = max(int(finite_e2.max()) - 15, 0) if finite_e2.numel() else 0
+    bad = int(nonfinite.sum()) + int((~nonfinite & (e2 != 0) & (e2 <= bh)).sum())
+    return bh, bad
+
+
+def pack_pk13(W: torch.Tensor, bh: int) -> torch.Tensor:
+    """(N, K / 4096, 6656) uint8: per unit, lane-linear pieces --
+       bytes    0 .. 4095  low bytes: piece p (1 KiB), lane l, 16 bytes = chunk 2p elements 0..7, then chunk 2p + 1 elements 0..7
+       bytes 4096 .. 6143  codes: piece q (1 KiB), lane l, 4 dwords = chunks 4q .. 4q + 3; byte i of a dword = h[e = i] | h[e = i + 4] << 4
+       bytes 6144 .. 6655  signs: lane l, 2 dwords; in dword w (chunks 4w .. 4w + 3) byte e & 3 holds the sign of element e of chunk c at
+                           bit (c & 3) * 2 + (e >> 2)"""
+    N, K = W.shape
+    assert K % PK13_UNIT_K == 0 and 0 <= bh <= 112
+    J = K // PK13_UNIT_K
+    bits = _bf16_bits(W).reshape(N, J, 8, 64, 8)            # [row, unit, chunk, lane, element]
+    lo, e2, sg = bits & 0xff, (bits >> 8) & 0x7f, bits >> 15
+    h = torch.where(e2 == 0, torch.zeros_like(e2), (e2 - bh) & 15)
+    a = lo.reshape(N, J, 4, 2, 64, 8).permute(0, 1, 2, 4, 3, 5).reshape(N, J, 4 * 64 * 16)
+    nib = h[..., 0:4] | (h[..., 4:8] << 4)                  # [row, unit, chunk, lane, byte]
+    hp = nib.reshape(N, J, 2, 4, 64, 4).permute(0, 1, 2, 4, 3, 5).reshape(N, J, 2 * 64 * 16)
+    s5 = sg.reshape(N, J, 2, 4, 64, 2, 4)                   # [row, unit, dword, chunk & 3, lane, e >> 2, e & 3]
+    sb = torch.zeros(N, J, 2, 64, 4, dtype=torch.int32)
+    for cc in range(4):
+        for half in range(2):
+            sb |= s5[:, :, :, cc, :, half, :] << (cc * 2 + half)
+    sp = sb.permute(0, 1, 3, 2, 4).reshape(N, J, 64 * 8)
+    return torch.cat([a, hp, sp], dim=2).to(torch.uint8)
+
+
+def unpack_pk13(P: torch.Tensor, bh: int) -> torch.Tensor:
+    """The bf16 matrix (N, K) a copy holds: pack_pk13's inverse, bit for bit."""
+    N, J, B = P.shape
+    assert B == PK13_UNIT_BYTES
+    P = P.to(torch.int32)
+    lo = P[:, :, :PK13_OFF_H].reshape(N, J, 4, 64, 2, 8).permute(0, 1, 2, 4, 3, 5).reshape(N, J, 8, 64, 8)
+    nib = P[:, :, PK13_OFF_H:PK13_OFF_S].reshape(N, J, 2, 64, 4, 4).permute(0, 1, 2, 4, 3, 5).reshape(N, J, 8, 64, 4)
+    h = torch.cat([nib & 15, nib >> 4], dim=-1)
+    sb = P[:, :, PK13_OFF_S:].reshape(N, J, 64, 2, 4).permute(0, 1, 3, 2, 4)       # [row, unit, dword, lane, e & 3]
+    sg = torch.zeros(N, J, 2, 4, 64, 2, 4, dtype=torch.int32)
+    for cc in range(4):
+        for half in range(2):
+            sg[:, :, :, cc, :, half, :] = (sb >> (cc * 2 + half)) & 1
+    sg = sg.reshape(N, J, 8, 64, 8)
+    e2 = torch.where(h == 0, torch.zeros_like(h), h + bh)
+    bits = (sg << 15) | (e2 << 8) | lo
+    return bits.reshape(N, J * PK13_UNIT_K).to(torch.int16).view(torch.bfloat16)

@@ -773,6 +773,19 @@ int aha_hip_debug_fp8_single(aha_model* m, int on);
  * the FP4 launches: gemv_fp4, at 0.53125 bytes per weight.  Sharded models have no copies.  AHA_ERR_INVALID: a null model or another
  * value.  An MXFP8 model ignores it. */
 int aha_hip_debug_fp4_single(aha_model* m, int on);
+/* Exact 13-bit weight copies.  When a model is created unsharded, each of the four layer matrices and lm_head gets a copy that holds
+ * every bf16 weight exactly in 13 bits (aha_hip_pack_pk13 has the format) if the matrix has at least 2^24 elements, K is a multiple of
+ * 4096, every weight lies in the format's window, and the device has the copies' bytes plus a tenth more free; otherwise that matrix,
+ * or every matrix, stays without one, silently.  The single-sequence decode matvec then streams 0.8125 of the bytes and computes the same
+ * bits (gemv_kernel_pk13; profiles/weights_pk13.md).  AHA_WPACK=0 in the environment, read when a model is created, makes no copies.
+ * aha_hip_model_quantize_weights frees the copies: a quantised model never reads them.
+ * aha_hip_debug_pk13_single: on = 1 (the default): a matrix with a copy is read from it where the plan takes its shape
+ * (aha_hip_debug_plan_gemv_pk13 tells); 2: wherever a copy exists; 0: nowhere (the bf16 kernel).  The bits are the same in all three, and
+ * the launches stay in profile class gemv, at 1.625 bytes per weight.  AHA_ERR_INVALID: a null model or another value.
+ * aha_hip_pk13_status: one line per matrix into buf (NUL-terminated, truncated to cap), "<tensor name>\t<status>\n", status "packed" or
+ * the reason the matrix has no copy; returns the number of matrices with a copy, or a negative error. */
+int aha_hip_debug_pk13_single(aha_model* m, int on);
+int aha_hip_pk13_status(const aha_model* m, char* buf, size_t cap);
 
 /* ---- introspection used by bench.py / tests ------------------------------------------------------------------ */
 size_t aha_hip_cache_len(const aha_model* m);
@@ -842,6 +855,11 @@ int aha_hip_debug_streamk_plan(int32_t M, int32_t N, int32_t K, int32_t tile_n, 
  * NULL) = 1 if a model's single-sequence step reads a matrix of this shape from its copy by default (aha_hip_debug_fp8_single). */
 int aha_hip_debug_plan_gemv_mxfp8(int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form,
                                   int32_t* by_plan);
+/* The same query for aha_hip_gemv_pk13 / the single-sequence matvec from an exact 13-bit copy; K a multiple of 4096, at most 32768.
+ * *U is always 8 (a work item is one 4096-column unit per row) and *form 2 / 3, or 1 past the straight-line prologue's K; names
+ * gemv_kernel_pk13<R, epi, max(form - 1, 0)>.  *by_plan as aha_hip_debug_pk13_single reads it. */
+int aha_hip_debug_plan_gemv_pk13(int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form,
+                                 int32_t* by_plan);
 /* The same query for aha_hip_gemv_mxfp4 / the single-sequence matvec of an MXFP4 model (there was no such plan: the path had no FP4
  * kernel): names gemv_mxfp4_kernel<R, U, epi, form != 0, max(form - 1, 0)>, *by_plan as aha_hip_debug_fp4_single reads it. */
 int aha_hip_debug_plan_gemv_mxfp4(int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form,
@@ -927,6 +945,19 @@ int aha_hip_gemv_rows_mxfp8(const void* q, const uint32_t* scales, const void* x
  * every output bit -- and the argmax -- equals aha_hip_gemv_epi on W'.  The same argument checks, messages prefixed "gemv_mxfp4:". */
 int aha_hip_gemv_mxfp4(const void* q, const uint32_t* scales, const void* x, void* y, int32_t N, int32_t K, int32_t epi, const void* norm_w,
                        float eps, const void* residual, float* logits, uint32_t* argmax_out, void* stream);
+/* Exact 13-bit copy of a bf16 matrix W (N, K), K a multiple of 4096 (device pointers).  A bf16 weight is s | E(8) | m(7); the copy keeps
+ * its low byte (E & 1) | m and its sign verbatim and recodes E >> 1 to 4 bits with one base bh per matrix: code 0 means E >> 1 == 0
+ * (+-0, subnormals, E = 1), code h = 1..15 means E >> 1 == bh + h, bh = max(0, max of E >> 1 over the finite weights - 15).  Rows in the
+ * order of W, K / 4096 units of 6656 bytes per row; a unit holds one row x 4096 columns as four 1-KiB pieces of low bytes, two 1-KiB
+ * pieces of codes and 512 bytes of signs, each lane-linear for the matvec (kernels_gemv_pk13.hip and aha_amd/quant.py pack_pk13 spell the
+ * bit positions out).  aha_hip_pack_pk13 checks W first: *bad_out = the number of weights the format cannot hold (Inf, NaN, non-zero
+ * values with E >> 1 <= bh); *bh_out = bh.  out (may be NULL: check only) receives N * (K / 4096) * 6656 bytes if *bad_out == 0 and
+ * is left untouched otherwise.  Synchronises the stream.
+ * aha_hip_gemv_pk13: aha_hip_gemv_epi with (packed, bh) in place of W; K a multiple of 4096, at most 32768.  The contract is bit
+ * identity with aha_hip_gemv_epi on W, whatever either plan picks. */
+int aha_hip_pack_pk13(const void* W, int32_t N, int32_t K, void* out, int32_t* bh_out, int64_t* bad_out, void* stream);
+int aha_hip_gemv_pk13(const void* packed, int32_t bh, const void* x, void* y, int32_t N, int32_t K, int32_t epi, const void* norm_w,
+                      float eps, const void* residual, float* logits, uint32_t* argmax_out, void* stream);
 int aha_hip_quantize_mxfp4(const void* W, int32_t N, int32_t K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, void* stream);
 int aha_hip_gemv_rows_mxfp4(const void* q, const uint32_t* scales, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi,
                             const void* residual, float* logits, uint32_t* argmax_out, void* stream);

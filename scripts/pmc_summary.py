@@ -43,7 +43,7 @@ def main():
         "correction": "FETCH_SIZE (KB) x 1024 x 2: gfx950 reports half of the bytes of wide coalesced reads (MI355X_MICROARCH.md, HBM); WRITE_SIZE x 1024 uncalibrated",
         "launches": n, "fetch_bytes_per_launch": fb / n, "write_bytes_per_launch": wb / n,
         "traffic_bytes_per_launch": (fb + wb) / n,
-        "per_kernel_fetch_MB_x2": {(re.search(r"gemv_kernel<[^>]*>", k) or re.search(r".{0,32}$", k)).group(0): round(sum(fetch[k].values()) * 1024 * 2 / len(fetch[k]) / 1e6, 2) for k in cls},
+        "per_kernel_fetch_MB_x2": {(re.search(r"gemv_kernel(?:_pk13)?<[^>]*>", k) or re.search(r".{0,32}$", k)).group(0): round(sum(fetch[k].values()) * 1024 * 2 / len(fetch[k]) / 1e6, 2) for k in cls},
     }
     other = {k[:80]: round(sum(v.values()) * 1024 * 2 / len(v) / 1e6, 3) for k, v in fetch.items()
              if ("attn_decode" in k or "gemm256" in k or "attn_prefill" in k) and len(v)}
