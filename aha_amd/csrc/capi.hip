@@ -1162,6 +1162,33 @@ int aha_hip_debug_plan_gemv_mxfp4(int32_t N, int32_t K, int32_t epi, int32_t has
   return debug_plan_gemv_mx(4, N, K, epi, has_norm, R, U, grid, form, by_plan);
 }
 
+int aha_hip_debug_plan_gemv(int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form) {
+  if (!R || !U || !grid || N < 1 || K < 8 || K % 8 || K > 32768 || epi < 0 || epi > 4 || (epi == 2 && N % 2)) {
+    set_error("debug_plan_gemv: bad argument (N >= 1, K a positive multiple of 8 and at most 32768, epi 0..4, epi 2 needs an even N)");
+    return AHA_ERR_INVALID;
+  }
+  int o[5];
+  debug_plan_gemv(epi == 2 ? N / 2 : N, K, (GemvEpi)epi, has_norm != 0, o);
+  *R = o[0]; *U = o[1]; *grid = o[2];
+  if (form) *form = o[3] ? 1 + o[4] : 0;
+  return AHA_OK;
+}
+
+int aha_hip_debug_gemv_partial_f32(const void* W, const void* x, float* y_f32, int32_t N, int32_t K, const void* norm_w, float eps,
+                                   void* stream) {
+  API_GUARD_BEGIN
+  if (!W || !x || !y_f32 || N < 1 || K < 8 || K % 8 || K > 32768) {
+    set_error("debug_gemv_partial_f32: bad argument (W, x, y_f32 not null, N >= 1, K a positive multiple of 8 and at most 32768)");
+    return AHA_ERR_INVALID;
+  }
+  GemvArgs g{};
+  g.W = W; g.x = x; g.y_f32 = y_f32; g.N = N; g.K = K; g.norm_w = norm_w; g.eps = eps;
+  launch_gemv(g, GEMV_PARTIAL_F32, (hipStream_t)stream);
+  AHA_HIP_CHECK(hipGetLastError());
+  return AHA_OK;
+  API_GUARD_END
+}
+
 // ---- batch-1 matvec with an epilogue, op level (the partials of epi 3 are allocated per call: test / measurement entries) ----
 namespace {
 struct GemvPartials {   // released when the call returns, on the error paths too

@@ -41,6 +41,7 @@ struct GemvArgs {
 };
 void launch_gemv(const GemvArgs& a, GemvEpi epi, hipStream_t st);
 int gemv_num_tiles(int N, int K);  // number of (max,idx) partials GEMV_LOGITS writes
+void debug_plan_gemv(int N, int K, GemvEpi epi, bool has_norm, int* out5);   // host only: {R, U, grid, FAST, PRO} of launch_gemv; N = output rows
 
 void launch_argmax_partials(const float* blk_max, const uint32_t* blk_idx, int n, uint32_t* out, hipStream_t st);
 // vocab-parallel lm_head (tensor parallelism): per-rank (max, global index) pair into a zeroed 2T vector / pick after the all-reduce

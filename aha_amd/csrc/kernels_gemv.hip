@@ -100,21 +100,43 @@ GemvPlan plan_gemv(int N, int K, GemvEpi epi) {
   return {R, Up, grid};
 }
 
+// AHA_GEMV_CACHED overrides GemvArgs::cached (temporal weight loads: the general form only)
+int cached_or_env(int cached) {
+  static const char* e_cached = getenv("AHA_GEMV_CACHED");
+  return e_cached ? atoi(e_cached) : cached;
+}
+
+// The forms a launch takes for a shape, for launch_gemv_epi and debug_plan_gemv alike.
+// FAST (gemv_body.h): every chunk group full and in range, weights non-temporal.
+// PRO, the straight-line prologue (gemv_body.h): the FAST form whose activation vector fits the preloaded vectors, 8 per thread, 4 with
+// norm weights.
+void form_of(const GemvPlan& p, int N, int K, bool has_norm, int cached, bool* fast, int* pro) {
+  static const bool fast_ok = [] { const char* e = getenv("AHA_GEMV_FAST"); return e ? atoi(e) != 0 : true; }();
+  *fast = fast_ok && K % (512 * p.U) == 0 && !cached && N >= 1;
+  *pro = *fast && K <= (has_norm ? 4 : 8) * 8 * GEMV_THREADS ? (has_norm ? 2 : 1) : 0;
+}
+
 }  // namespace
 
 int gemv_num_tiles(int N, int K) { return plan_gemv(N, K, GEMV_LOGITS).grid; }
+
+void debug_plan_gemv(int N, int K, GemvEpi epi, bool has_norm, int* out5) {
+  const GemvPlan p = plan_gemv(N, K, epi);
+  bool fast;
+  int pro;
+  form_of(p, N, K, has_norm, cached_or_env(0), &fast, &pro);
+  out5[0] = p.R; out5[1] = p.U; out5[2] = p.grid; out5[3] = fast ? 1 : 0; out5[4] = pro;
+}
 
 template <int EPI>
 static void launch_gemv_epi(const GemvArgs& a, const GemvPlan& p, hipStream_t st) {
   const size_t lds = (size_t)((a.K + 511) / 512) * 512 * 4 + 64;
   dim3 grid(p.grid), block(GEMV_THREADS);
-  // FAST form (gemv_body.h): every chunk group full and in range, weights non-temporal
-  static const bool fast_ok = [] { const char* e = getenv("AHA_GEMV_FAST"); return e ? atoi(e) != 0 : true; }();
-  const bool fast = fast_ok && a.K % (512 * p.U) == 0 && !a.cached && a.N >= 1;
+  bool fast;
+  int pro;
+  form_of(p, a.N, a.K, a.norm_w != nullptr, a.cached, &fast, &pro);
   const GemvTailArgs t{a.y_f32, a.blk_max, a.blk_idx, a.h_out, a.trace, a.cached};
   const void* aux = EPI == GEMV_SILU_MUL ? a.W2 : a.residual;
-  // straight-line prologue (gemv_body.h): the FAST form whose activation vector fits the preloaded vectors, 8 per thread, 4 with norm weights
-  const int pro = fast && a.K <= (a.norm_w != nullptr ? 4 : 8) * 8 * GEMV_THREADS ? (a.norm_w != nullptr ? 2 : 1) : 0;
 #define GV_(RR, UU, FF, TT, PP) \
   hipLaunchKernelGGL((gemv_kernel<RR, UU, EPI, FF, TT, PP>), grid, block, lds, st, a.W, a.x, a.norm_w, a.y, aux, a.N, a.K, a.eps, p.grid, t)
 #define GV(RR, UU)                                                      \
@@ -140,8 +162,7 @@ static void launch_gemv_epi(const GemvArgs& a, const GemvPlan& p, hipStream_t st
 
 void launch_gemv(const GemvArgs& a_in, GemvEpi epi, hipStream_t st) {
   GemvArgs a = a_in;
-  static const char* e_cached = getenv("AHA_GEMV_CACHED");
-  if (e_cached) a.cached = atoi(e_cached);
+  a.cached = cached_or_env(a.cached);
   const GemvPlan p = plan_gemv(a.N, a.K, epi);
   switch (epi) {
     case GEMV_STORE: launch_gemv_epi<GEMV_STORE>(a, p, st); break;

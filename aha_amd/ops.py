@@ -492,6 +492,24 @@ def gemv_epi(W: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, norm_
     return (logits, int(am.item())) if epi == GEMV_ROWS_LOGITS else y
 
 
+def plan_gemv(N: int, K: int, epi: int = GEMV_ROWS_STORE, has_norm: bool = False):
+    """Host only: (R, U, grid, form) the bf16 matvec picks for a matrix of N rows (epi 2: N = 2I, either weight layout; epi 4: the f32
+    partial sums) (aha_hip_debug_plan_gemv): form 0 general, 1 FAST, 2 / 3 FAST with the straight-line prologue without / with norm weights."""
+    r, u, g, f = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib().aha_hip_debug_plan_gemv(N, K, epi, int(has_norm), C.byref(r), C.byref(u), C.byref(g), C.byref(f)))
+    return r.value, u.value, g.value, f.value
+
+
+def gemv_partial_f32(W: torch.Tensor, x: torch.Tensor, norm_w: Optional[torch.Tensor] = None, eps: float = 1e-6) -> torch.Tensor:
+    """Test entry (aha_hip_debug_gemv_partial_f32): the bf16 matvec's un-rounded f32 sums, the epilogue of a sharded model's row-parallel
+    projections.  W (N, K) bf16, x (K) bf16 -> (N) f32."""
+    _chk(W, x, norm_w)
+    N, K = W.shape
+    y = torch.empty(N, dtype=torch.float32, device=x.device)
+    check(lib().aha_hip_debug_gemv_partial_f32(_ptr(W), _ptr(x), _ptr(y), N, K, _ptr(norm_w), eps, _stream()))
+    return y
+
+
 def gemv_mxfp8(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, norm_w: Optional[torch.Tensor] = None,
                eps: float = 1e-6, residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
     """gemv_epi from the MXFP8 copy of W (aha_hip_gemv_mxfp8): q (N, K) uint8, scales (N, K / 32) uint8 in the reference's order (converted

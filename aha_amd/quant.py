@@ -197,7 +197,7 @@ def pack_pk13(W: torch.Tensor, bh: int) -> torch.Tensor:
     nib = h[..., 0:4] | (h[..., 4:8] << 4)                  # [row, unit, chunk, lane, byte]
     hp = nib.reshape(N, J, 2, 4, 64, 4).permute(0, 1, 2, 4, 3, 5).reshape(N, J, 2 * 64 * 16)
     s5 = sg.reshape(N, J, 2, 4, 64, 2, 4)                   # [row, unit, dword, chunk & 3, lane, e >> 2, e & 3]
-    sb = torch.zeros(N, J, 2, 64, 4, dtype=torch.int32)
+    sb = torch.zeros(N, J, 2, 64, 4, dtype=torch.int32, device=W.device)
     for cc in range(4):
         for half in range(2):
             sb |= s5[:, :, :, cc, :, half, :] << (cc * 2 + half)

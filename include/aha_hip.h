@@ -864,6 +864,15 @@ int aha_hip_debug_plan_gemv_pk13(int32_t N, int32_t K, int32_t epi, int32_t has_
  * kernel): names gemv_mxfp4_kernel<R, U, epi, form != 0, max(form - 1, 0)>, *by_plan as aha_hip_debug_fp4_single reads it. */
 int aha_hip_debug_plan_gemv_mxfp4(int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form,
                                   int32_t* by_plan);
+/* The same query for the bf16 matvec itself (aha_hip_gemv, aha_hip_gemv_gate_up, aha_hip_gemv_epi and the model's decode step): names
+ * gemv_kernel<R, U, epi, form != 0, false, max(form - 1, 0)>, by the function the launch itself calls.  epi 0..4 (4: the un-rounded f32
+ * partial sums of the tensor-parallel row split); epi 2 takes N = 2I for either weight layout, and any even N (aha_hip_gemv_gate_up has
+ * no 32-row blocks).  K a multiple of 8, at most 32768. */
+int aha_hip_debug_plan_gemv(int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form);
+/* Test entry of that epilogue, which only a sharded model's row-parallel projections launch: y_f32[n] = sum_k h[k] * W[n, k], f32, not
+ * rounded; h = x, or RMSNorm(x; norm_w, eps) rounded to bf16 when norm_w is not NULL.  W (N, K) bf16, x (K) bf16, device pointers. */
+int aha_hip_debug_gemv_partial_f32(const void* W, const void* x, float* y_f32, int32_t N, int32_t K, const void* norm_w, float eps,
+                                   void* stream);
 /* CUs the persistent GEMM kernel leaves free (rounded so that its workgroup count stays a multiple of 8; 0 = use every CU; < 0 = take
  * AHA_GEMM_RESERVE_CUS from the environment).  Process-wide.  For tensor-parallel prefill: RCCL's kernels on the communication stream
  * need CUs next to a GEMM whose workgroups each fill one (csrc/model.hip gemm_row_parallel).  Must be the same on every rank only

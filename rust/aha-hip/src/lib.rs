@@ -628,6 +628,26 @@ pub mod sys {
             form: *mut i32,
             by_plan: *mut i32,
         ) -> i32;
+        pub fn aha_hip_debug_plan_gemv(
+            n: i32,
+            k: i32,
+            epi: i32,
+            has_norm: i32,
+            r: *mut i32,
+            u: *mut i32,
+            grid: *mut i32,
+            form: *mut i32,
+        ) -> i32;
+        pub fn aha_hip_debug_gemv_partial_f32(
+            w: *const std::ffi::c_void,
+            x: *const std::ffi::c_void,
+            y_f32: *mut f32,
+            n: i32,
+            k: i32,
+            norm_w: *const std::ffi::c_void,
+            eps: f32,
+            stream: *mut std::ffi::c_void,
+        ) -> i32;
         pub fn aha_hip_gemv_epi(
             w: *const std::ffi::c_void,
             x: *const std::ffi::c_void,
