@@ -269,6 +269,10 @@ SIGNATURES = {
     "aha_hip_pk13_status": (C.c_int, [_P, C.c_char_p, C.c_size_t]),
     "aha_hip_pack_pk13": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _P]),
     "aha_hip_gemv_pk13": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, _P, _P, _P, _P]),
+    "aha_hip_pack_pk13_rows": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+    "aha_hip_gemv_pk13_rows": (C.c_int, [_P, C.c_int32, _P, C.POINTER(C.c_int32), C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float,
+                                         _P, _P, _P, _P]),
     "aha_hip_debug_plan_gemv_pk13": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "aha_hip_gemv_epi": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, _P, _P, _P, _P]),

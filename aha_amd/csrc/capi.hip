@@ -1216,7 +1216,7 @@ const char* gemv_epi_args_bad(const void* w, const void* x, const void* y, int N
 // q: the MXFP8 (mx == 8) or MXFP4 (mx == 4) copy in place of W, or the exact 13-bit copy (mx == 13, its base in pk13_bh)
 static int gemv_epi_run(const void* W, int mx, const void* q, const uint32_t* scales, const void* x, void* y, int32_t N, int32_t K,
                         int32_t epi, const void* norm_w, float eps, const void* residual, float* logits, uint32_t* argmax_out, void* stream,
-                        int pk13_bh = 0) {
+                        int pk13_bh = 0, const int32_t* pk13_rows = nullptr, int pk13_nrows = 0) {
   hipStream_t st = (hipStream_t)stream;
   GemvArgs g{};
   g.W = W; g.x = x; g.y = y; g.N = epi == 2 ? N / 2 : N; g.K = K; g.norm_w = norm_w; g.eps = eps; g.residual = epi == 1 ? residual : nullptr;
@@ -1233,7 +1233,7 @@ static int gemv_epi_run(const void* W, int mx, const void* q, const uint32_t* sc
   }
   if (!q) launch_gemv(g, e, st);
   else if (mx == 8) launch_gemv_mxfp8(g, q, scales, e, st);
-  else if (mx == 13) launch_gemv_pk13(g, q, pk13_bh, e, st);
+  else if (mx == 13) launch_gemv_pk13(g, q, pk13_bh, pk13_rows, pk13_nrows, e, st);   // g.W: the bf16 matrix, read for the exception rows
   else launch_gemv_mxfp4(g, q, scales, e, st);
   if (epi == 3) launch_argmax_partials(g.blk_max, g.blk_idx, tiles, argmax_out, st);
   hipError_t err = hipGetLastError();
@@ -1300,7 +1300,7 @@ int aha_hip_pack_pk13(const void* W, int32_t N, int32_t K, void* out, int32_t* b
   GemvPartials d;
   AHA_HIP_CHECK(hipMalloc(&d.p[0], sizeof(Pk13Stats)));
   AHA_HIP_CHECK(hipMemsetAsync(d.p[0], 0, sizeof(Pk13Stats), st));
-  launch_pk13_stats(W, (int64_t)N * K, (Pk13Stats*)d.p[0], st);
+  launch_pk13_stats(W, N, K, (Pk13Stats*)d.p[0], st);
   AHA_HIP_CHECK(hipGetLastError());
   Pk13Stats h{};
   AHA_HIP_CHECK(hipMemcpyAsync(&h, d.p[0], sizeof(h), hipMemcpyDeviceToHost, st));
@@ -1313,6 +1313,67 @@ int aha_hip_pack_pk13(const void* W, int32_t N, int32_t K, void* out, int32_t* b
     AHA_HIP_CHECK(hipStreamSynchronize(st));
   }
   return AHA_OK;
+  API_GUARD_END
+}
+
+int aha_hip_pack_pk13_rows(const void* W, int32_t N, int32_t K, void* out, int32_t* bh_out, int32_t* rows_out, int32_t cap, int32_t* nrows_out,
+                           int64_t* below_out, int64_t* nonfinite_out, void* stream) {
+  API_GUARD_BEGIN
+  if (!W || !bh_out || !rows_out || !nrows_out || !below_out || !nonfinite_out || cap < 0 || cap > PK13_MAX_EXC || N < 1 || K < 4096 || K % 4096) {
+    set_error("pack_pk13_rows: bad argument (W and the outputs not null, cap 0..16, N >= 1, K a positive multiple of 4096)");
+    return AHA_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  GemvPartials d;
+  AHA_HIP_CHECK(hipMalloc(&d.p[0], sizeof(Pk13Stats)));
+  AHA_HIP_CHECK(hipMemsetAsync(d.p[0], 0, sizeof(Pk13Stats), st));
+  launch_pk13_stats(W, N, K, (Pk13Stats*)d.p[0], st);
+  AHA_HIP_CHECK(hipGetLastError());
+  Pk13Stats h{};
+  AHA_HIP_CHECK(hipMemcpyAsync(&h, d.p[0], sizeof(h), hipMemcpyDeviceToHost, st));
+  AHA_HIP_CHECK(hipStreamSynchronize(st));
+  int rows[PK13_MAX_EXC];
+  const int n = pk13_exception_rows(h, rows);
+  *bh_out = pk13_base(h.max_e2);
+  *nonfinite_out = (int64_t)h.nonfinite;
+  *below_out = (int64_t)(h.bad - h.nonfinite);
+  *nrows_out = n;
+  for (int i = 0; i < cap && i < n && n <= PK13_MAX_EXC; ++i) rows_out[i] = rows[i];
+  if (out && !h.nonfinite && n <= cap) {
+    launch_pk13_pack(W, N, K, *bh_out, out, st);
+    AHA_HIP_CHECK(hipGetLastError());
+    AHA_HIP_CHECK(hipStreamSynchronize(st));
+  }
+  return AHA_OK;
+  API_GUARD_END
+}
+
+int aha_hip_gemv_pk13_rows(const void* packed, int32_t bh, const void* W, const int32_t* rows, int32_t nrows, const void* x, void* y, int32_t N,
+                           int32_t K, int32_t epi, const void* norm_w, float eps, const void* residual, float* logits, uint32_t* argmax_out,
+                           void* stream) {
+  API_GUARD_BEGIN
+  if (const char* bad = gemv_epi_args_bad(packed, x, y, N, K, 8, epi, residual, logits, argmax_out)) {
+    set_error(std::string("gemv_pk13_rows: ") + bad);
+    return AHA_ERR_INVALID;
+  }
+  if (K % 4096) {
+    set_error("gemv_pk13_rows: K must be a multiple of 4096 (the unit)");
+    return AHA_ERR_INVALID;
+  }
+  if (bh < 0 || bh > 112) {
+    set_error("gemv_pk13_rows: bh must be 0..112");
+    return AHA_ERR_INVALID;
+  }
+  if (nrows < 0 || nrows > PK13_MAX_EXC || (nrows > 0 && (!W || !rows))) {
+    set_error("gemv_pk13_rows: nrows must be 0..16, and rows need W and the list");
+    return AHA_ERR_INVALID;
+  }
+  for (int i = 0; i < nrows; ++i)
+    if (rows[i] < 0 || rows[i] >= N) {
+      set_error("gemv_pk13_rows: row " + std::to_string(rows[i]) + " is not a row of the matrix");
+      return AHA_ERR_INVALID;
+    }
+  return gemv_epi_run(W, 13, packed, nullptr, x, y, N, K, epi, norm_w, eps, residual, logits, argmax_out, stream, bh, rows, nrows);
   API_GUARD_END
 }
 

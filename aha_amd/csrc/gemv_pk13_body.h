@@ -53,10 +53,19 @@ struct GemvPk13Args {
   float eps;
 };
 
-// xs: LDS, (K + 16) floats.  PRO as in gemv_body: 1 / 2 = the straight-line prologue without / with norm weights, 0 = the general one.  Always
-// the FAST form: a work item is one unit of each of the wave's R (x 2 for gate / up) rows, nothing is predicated.
-template <int R, int EPI, int PRO>
-__device__ __forceinline__ void gemv_pk13_body(const GemvPk13Args& a, float* xs, const int bid, const int nblk) {
+// Exception rows (the twin kernel, EXC): rows of W that hold a finite weight below the matrix's window.  The copy has an arbitrary code at
+// such a weight, so the wave that owns such a row runs the bf16 kernel's chain over the row of W itself, in front of its main loop, and at
+// the end of the row its epilogue takes that sum in place of the one the copy gave.
+struct Pk13ExcRows {
+  const void* W;             // the bf16 matrix the copy was made of
+  int n;                     // rows in use
+  int row[PK13_MAX_EXC];     // rows of W, in W's own order (GEMV_SILU_MUL: of the fused matrix); unused entries -1
+};
+
+// xs: LDS, (K + 16) floats (EXC: K + 32).  PRO as in gemv_body: 1 / 2 = the straight-line prologue without / with norm weights, 0 = the
+// general one.  Always the FAST form: a work item is one unit of each of the wave's R (x 2 for gate / up) rows, nothing is predicated.
+template <int R, int EPI, int PRO, bool EXC = false>
+__device__ __forceinline__ void gemv_pk13_body(const GemvPk13Args& a, float* xs, const int bid, const int nblk, const Pk13ExcRows& ex = Pk13ExcRows{}) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: the row pointers live in SGPRs
   const int K = a.K, N = a.N;
@@ -210,6 +219,47 @@ __device__ __forceinline__ void gemv_pk13_body(const GemvPk13Args& a, float* xs,
 #pragma unroll
     for (int r = 0; r < R; ++r) acc[m][r] = 0.f;
 
+  // EXC: the sums of the exception rows this wave owns, from W itself and in front of the main loop: a lane's chain over the row, chunks
+  // 0 .. nchunks - 1, with gemv_body's loads, operands and fma order, then the wave sum every row ends with -- the bits the bf16 kernel
+  // hands to its epilogue.  They wait in LDS (exc[i] for list entry i, read back by the wave that wrote it) until the row's epilogue
+  // takes them in place of what the copy gave.  Here and not at the row end: the first buffer is in flight and nothing else is live, while
+  // a chain inside consume() splits the blocks the scheduler sees and cost the gate / up and logits forms their third wave per SIMD
+  // (195 VGPRs).  The sched_barriers keep the eight loads of a unit together and the LDS vectors to one chunk at a time.
+  float* exc = red + 16;
+  if (EXC) {
+    for (int i = 0; i < ex.n; ++i) {
+      int wr = -1;
+#pragma unroll
+      for (int j = 0; j < PK13_MAX_EXC; ++j) wr = j == i ? ex.row[j] : wr;
+      const int orow = NW == 2 ? (wr >> 5) * 16 + (wr & 15) : wr;          // the output row it belongs to
+      const int otile = orow / ROWS_PER_TILE;
+      if (otile % nblk != bid || (orow % ROWS_PER_TILE) / R != wave) continue;
+      const bf16_t* wp = (const bf16_t*)ex.W + (size_t)wr * K + lane * 8;
+      float s = 0.f;
+#pragma unroll 1
+      for (int u = 0; u < gpt; ++u) {
+        u32x4_t w[8];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) w[c] = ld16(wp + ((u * 8 + c) << 9));
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          __builtin_amdgcn_sched_barrier(0);
+          const float4 xlo = *reinterpret_cast<const float4*>(xs + ((u * 8 + c) << 9) + (lane << 2));
+          const float4 xhi = *reinterpret_cast<const float4*>(xs + ((u * 8 + c) << 9) + 256 + (lane << 2));
+          s = fmaf(xlo.x, lo_bf(w[c][0]), s); s = fmaf(xlo.y, hi_bf(w[c][0]), s);
+          s = fmaf(xlo.z, lo_bf(w[c][1]), s); s = fmaf(xlo.w, hi_bf(w[c][1]), s);
+          s = fmaf(xhi.x, lo_bf(w[c][2]), s); s = fmaf(xhi.y, hi_bf(w[c][2]), s);
+          s = fmaf(xhi.z, lo_bf(w[c][3]), s); s = fmaf(xhi.w, hi_bf(w[c][3]), s);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      s = wave_sum(s);
+      if (lane == 0) exc[i] = s;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+
   auto consume = [&](int gi, Pk13Unit (&buf)[NW][R], bf16_t (&resv)[R]) {
     const int c0 = (gi % gpt) * 8;
 #pragma unroll
@@ -241,6 +291,22 @@ __device__ __forceinline__ void gemv_pk13_body(const GemvPk13Args& a, float* xs,
     for (int m = 0; m < NW; ++m)
 #pragma unroll
       for (int r = 0; r < R; ++r) acc[m][r] = wave_sum(acc[m][r]);
+    if (EXC) {
+      // the row of W behind each sum is wave-uniform and the list sits in SGPRs: scalar compares, and one LDS word under a branch that is
+      // taken for at most PK13_MAX_EXC rows of the matrix (a clamped row may read a word nobody wrote: it is never stored)
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int row = min(row0 + r, n_out - 1);
+        const int fr = NW == 2 ? (row >> 4) * 32 + (row & 15) : row;
+#pragma unroll
+        for (int m = 0; m < NW; ++m) {
+          int hit = -1;
+#pragma unroll
+          for (int i = 0; i < PK13_MAX_EXC; ++i) hit = ex.row[i] == fr + 16 * m ? i : hit;
+          if (__builtin_expect(hit >= 0, 0)) acc[m][r] = exc[hit];
+        }
+      }
+    }
     if (lane == 0) {
 #pragma unroll
       for (int r = 0; r < R; ++r) {

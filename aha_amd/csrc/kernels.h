@@ -378,21 +378,32 @@ bool gemv_mxfp4_by_plan(int N, int K, GemvEpi epi);   // as gemv_mxfp8_by_plan, 
 void debug_plan_gemv_mxfp4(int N, int K, GemvEpi epi, bool has_norm, int* out5);   // host only: {R, U, grid, FAST, PRO}; N = output rows
 // Exact 13-bit copies (kernels_gemv_pk13.hip has the format): a bf16 matrix W (N, K), K % 4096 == 0, as pk13_bytes(N, K) = 0.8125 of its
 // bytes plus one exponent base bh.  launch_pk13_stats (stats zeroed by the caller) leaves the maximum of E >> 1 over the finite weights and
-// the count of weights the format cannot hold (Inf / NaN, non-zero values more than 30 binades below the maximum): only a matrix with
-// bad == 0 is packed, with bh = pk13_base(max_e2).  launch_gemv_pk13 is launch_gemv with (packed, bh) in place of g.W / g.W2 (ignored;
+// the count of weights the format cannot hold (Inf / NaN, non-zero values more than 30 binades below the maximum): a matrix with
+// bad == 0 is packed as it is, with bh = pk13_base(max_e2) (exception rows: below).  launch_gemv_pk13 is launch_gemv with (packed, bh) in place of g.W / g.W2 (ignored;
 // GEMV_SILU_MUL reads the fused 16-row gate / up block layout, g.N = I), g.cached and g.trace ignored, no GEMV_PARTIAL_F32, and
 // gemv_pk13_shape_ok(g.N, g.K) required.  Bit-identical to launch_gemv on W.  GEMV_LOGITS writes gemv_pk13_num_tiles(N, K) partials.
+// Exception rows: a finite weight below the window does not keep its matrix from being packed as long as at most PK13_MAX_EXC rows hold
+// one (a condition of the format, not a tuned figure: the kernel keeps the list in SGPRs).  The copy has an arbitrary code at such a weight;
+// launch_gemv_pk13 with (rows, nrows) -- rows of W in W's own order, GEMV_SILU_MUL: of the fused matrix, g.W the bf16 matrix -- launches the
+// twin kernel gemv_kernel_rows_pk13, which computes those rows from W itself with the bf16 kernel's chain: still bit-identical to
+// launch_gemv on W.  nrows == 0 is the plain kernel.  Inf / NaN (Pk13Stats::nonfinite) keep a matrix unpacked.
+constexpr int PK13_MAX_EXC = 16;
 struct Pk13Stats {
   int max_e2;
-  int pad;
-  unsigned long long bad;
+  int over;                       // more than PK13_MAX_EXC rows hold a finite weight below the window
+  unsigned long long bad;         // all weights the format cannot hold: nonfinite + finite below the window
+  unsigned long long nonfinite;   // Inf / NaN
+  int row1[PK13_MAX_EXC];         // the rows with a finite weight below the window, + 1, in the order found; 0: free
 };
 __host__ __device__ inline int pk13_base(int max_e2) { return max_e2 > 15 ? max_e2 - 15 : 0; }
 size_t pk13_bytes(int N, int K);
-void launch_pk13_stats(const void* w, int64_t n_elems, Pk13Stats* stats, hipStream_t st);
+void launch_pk13_stats(const void* w, int N, int K, Pk13Stats* stats, hipStream_t st);
+// host: the rows of s ascending into rows[PK13_MAX_EXC] (unused entries -1); returns their number, PK13_MAX_EXC + 1 if there are more
+int pk13_exception_rows(const Pk13Stats& s, int* rows);
 void launch_pk13_pack(const void* w, int N, int K, int bh, void* out, hipStream_t st);
 bool gemv_pk13_shape_ok(int N, int K);
 void launch_gemv_pk13(const GemvArgs& g, const void* packed, int bh, GemvEpi epi, hipStream_t st);
+void launch_gemv_pk13(const GemvArgs& g, const void* packed, int bh, const int* rows, int nrows, GemvEpi epi, hipStream_t st);
 int gemv_pk13_num_tiles(int N, int K);
 bool gemv_pk13_by_plan(int N, int K, GemvEpi epi);   // does the model's single-sequence step read this matrix (N rows: 2I for gate+up) from its copy?
 void debug_plan_gemv_pk13(int N, int K, GemvEpi epi, bool has_norm, int* out5);   // host only: {R, U = 8, grid, FAST = 1, PRO}; N = output rows

@@ -4,8 +4,10 @@
 // The format, per matrix.  A bf16 weight is s | E(8) | m(7): high byte s | E >> 1, low byte (E & 1) | m.  The low byte is kept verbatim.
 // Of the high byte the sign is kept and E >> 1 is recoded to 4 bits with one base bh per matrix: h = 0 means E >> 1 == 0 (+-0, the bf16
 // subnormals and E = 1), h = 1 .. 15 means E >> 1 == bh + h.  bh = max(E >> 1 over the finite weights) - 15 (at least 0), so the window
-// runs 30 binades down from the matrix maximum; a matrix with a weight outside it (Inf / NaN, or a non-zero E >> 1 at or below bh) is not
-// packed.  The recoding is invertible, so the kernel rebuilds exactly the f32 operands lo_bf / hi_bf give on W.
+// runs 30 binades down from the matrix maximum.  A matrix with Inf / NaN is not packed.  A finite weight below the window (a non-zero
+// E >> 1 at or below bh) gets an arbitrary code and makes its row an exception row, which the twin kernel gemv_kernel_rows_pk13 computes
+// from W itself; more than PK13_MAX_EXC such rows and the matrix is not packed.  Everywhere else the recoding is invertible, so the kernel
+// rebuilds exactly the f32 operands lo_bf / hi_bf give on W.
 //
 // Layout.  Rows in the order of W; a row is K / 4096 units; a unit (one row x 4096 columns = eight 512-column chunks, a lane owning
 // k = chunk * 512 + lane * 8 .. + 7 of each as in gemv_body.h) is 6656 bytes in seven lane-linear pieces:
@@ -47,6 +49,19 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel_pk13(const void* p, 
   gemv_pk13_body<R, EPI, PRO>(a, xs, (int)blockIdx.x, t.nblk);
 }
 
+// The twin for a matrix with exception rows: the same body with their sums from W and the row-end check compiled in (EXC).  The list is
+// part of the kernel arguments, so it arrives through scalar loads of the kernarg segment with everything else the prologue reads and
+// stays in SGPRs.  Its LDS has 16 more floats: the sums of the exception rows, one per list entry.
+template <int R, int EPI, int PRO>
+__global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel_rows_pk13(const void* p, const void* x, const void* norm_w, void* y, const void* residual,
+                                                                      int N, int K, int bh, GemvPk13TailArgs t, Pk13ExcRows ex) {
+  extern __shared__ __attribute__((aligned(16))) float xs[];  // K f32 + 8 floats reduction scratch, PK13_MAX_EXC floats at + 16
+  GemvPk13Args a;
+  a.p = p; a.x = x; a.norm_w = norm_w; a.residual = residual; a.y = y;
+  a.y_f32 = t.y_f32; a.blk_max = t.blk_max; a.blk_idx = t.blk_idx; a.h_out = t.h_out; a.N = N; a.K = K; a.bh = bh; a.eps = t.eps;
+  gemv_pk13_body<R, EPI, PRO, true>(a, xs, (int)blockIdx.x, t.nblk, ex);
+}
+
 struct GemvPk13Plan { int R, grid; };
 
 GemvPk13Plan plan_gemv_pk13(int N, GemvEpi epi) {
@@ -68,11 +83,17 @@ GemvPk13Plan plan_gemv_pk13(int N, GemvEpi epi) {
 int pro_of(int K, bool has_norm) { return K <= (has_norm ? 4 : 8) * 8 * GEMV_THREADS ? (has_norm ? 2 : 1) : 0; }
 
 template <int R, int EPI>
-void launch_pk13_epi(const GemvPk13Args& a, const GemvPk13Plan& p, hipStream_t st) {
+void launch_pk13_epi(const GemvPk13Args& a, const GemvPk13Plan& p, const Pk13ExcRows& ex, hipStream_t st) {
   const size_t lds = (size_t)a.K * 4 + 64;
   dim3 grid(p.grid), block(GEMV_THREADS);
   const GemvPk13TailArgs t{a.y_f32, a.blk_max, a.blk_idx, a.h_out, a.eps, p.grid};
   const int pro = pro_of(a.K, a.norm_w != nullptr);
+  if (ex.n > 0) {   // the plan is the plain kernel's
+#define GV_(PP) hipLaunchKernelGGL((gemv_kernel_rows_pk13<R, EPI, PP>), grid, block, lds + PK13_MAX_EXC * 4, st, a.p, a.x, a.norm_w, a.y, a.residual, a.N, a.K, a.bh, t, ex)
+    if (pro == 2) GV_(2); else if (pro == 1) GV_(1); else GV_(0);
+#undef GV_
+    return;
+  }
 #define GV_(PP) hipLaunchKernelGGL((gemv_kernel_pk13<R, EPI, PP>), grid, block, lds, st, a.p, a.x, a.norm_w, a.y, a.residual, a.N, a.K, a.bh, t)
   if (pro == 2) GV_(2); else if (pro == 1) GV_(1); else GV_(0);
 #undef GV_
@@ -100,21 +121,40 @@ __global__ __launch_bounds__(256) void pk13_max_kernel(const u32x4_t* w, int64_t
   }
   if ((threadIdx.x & 63) == 0) {
     atomicMax(&out->max_e2, mx);
-    if (bad) atomicAdd(&out->bad, bad);
+    if (bad) {
+      atomicAdd(&out->bad, bad);
+      atomicAdd(&out->nonfinite, bad);
+    }
   }
 }
 
-// pass 2: count of finite weights below the window of pass 1's maximum
-__global__ __launch_bounds__(256) void pk13_window_kernel(const u32x4_t* w, int64_t nvec, Pk13Stats* out) {
+// pass 2: count of finite weights below the window of pass 1's maximum, and the rows that hold one: a set of at most PK13_MAX_EXC rows
+// (stored + 1, 0 = free slot), filled by compare-and-swap in the order the rows are met; a row that finds no slot sets `over`.  Such weights
+// are a handful per matrix where the copy is of any use, and once the set is full a plain read of `over` ends the matter.
+__global__ __launch_bounds__(256) void pk13_window_kernel(const u32x4_t* w, int64_t nvec, int K, Pk13Stats* out) {
   const int bh = pk13_base(out->max_e2);
   unsigned long long bad = 0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
     const u32x4_t v = ld_nt16(w + i);
+    bool below = false;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const uint32_t b = (v[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
       const int e2 = pk13_e2(b);
-      if ((b & 0x7f80u) != 0x7f80u && e2 != 0 && e2 <= bh) ++bad;
+      if ((b & 0x7f80u) != 0x7f80u && e2 != 0 && e2 <= bh) {
+        ++bad;
+        below = true;
+      }
+    }
+    if (below && *(volatile int*)&out->over == 0) {
+      const int key = (int)(i * 8 / K) + 1;      // K % 8 == 0: a vector lies in one row
+      int s = 0;
+      for (; s < PK13_MAX_EXC; ++s) {
+        int cur = *(volatile int*)&out->row1[s];
+        if (cur == 0) cur = atomicCAS(&out->row1[s], 0, key);
+        if (cur == 0 || cur == key) break;
+      }
+      if (s == PK13_MAX_EXC) atomicExch(&out->over, 1);
     }
   }
   for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
@@ -158,11 +198,21 @@ __global__ __launch_bounds__(256) void pk13_pack_kernel(const bf16_t* w, int64_t
 
 size_t pk13_bytes(int N, int K) { return (size_t)N * (K / PK13_UNIT_K) * PK13_UNIT_BYTES; }
 
-void launch_pk13_stats(const void* w, int64_t n_elems, Pk13Stats* stats, hipStream_t st) {
-  const int64_t nvec = n_elems / 8;
+void launch_pk13_stats(const void* w, int N, int K, Pk13Stats* stats, hipStream_t st) {
+  const int64_t nvec = (int64_t)N * K / 8;
   const int grid = (int)std::min<int64_t>((nvec + 255) / 256, 4096);
   hipLaunchKernelGGL(pk13_max_kernel, dim3(grid), dim3(256), 0, st, (const u32x4_t*)w, nvec, stats);
-  hipLaunchKernelGGL(pk13_window_kernel, dim3(grid), dim3(256), 0, st, (const u32x4_t*)w, nvec, stats);
+  hipLaunchKernelGGL(pk13_window_kernel, dim3(grid), dim3(256), 0, st, (const u32x4_t*)w, nvec, K, stats);
+}
+
+int pk13_exception_rows(const Pk13Stats& s, int* rows) {
+  if (s.over) return PK13_MAX_EXC + 1;
+  int n = 0;
+  for (int i = 0; i < PK13_MAX_EXC; ++i)
+    if (s.row1[i] > 0) rows[n++] = s.row1[i] - 1;
+  std::sort(rows, rows + n);
+  for (int i = n; i < PK13_MAX_EXC; ++i) rows[i] = -1;
+  return n;
 }
 
 void launch_pk13_pack(const void* w, int N, int K, int bh, void* out, hipStream_t st) {
@@ -191,19 +241,32 @@ void debug_plan_gemv_pk13(int N, int K, GemvEpi epi, bool has_norm, int* out5) {
   out5[0] = p.R; out5[1] = 8; out5[2] = p.grid; out5[3] = 1; out5[4] = pro_of(K, has_norm);
 }
 
-void launch_gemv_pk13(const GemvArgs& g, const void* packed, int bh, GemvEpi epi, hipStream_t st) {
+void launch_gemv_pk13(const GemvArgs& g, const void* packed, int bh, const int* rows, int nrows, GemvEpi epi, hipStream_t st) {
   if (!gemv_pk13_shape_ok(g.N, g.K)) abort();   // the callers check the shape
+  const int mat_rows = (epi == GEMV_SILU_MUL ? 2 : 1) * g.N;
+  if (nrows < 0 || nrows > PK13_MAX_EXC || (nrows > 0 && (g.W == nullptr || rows == nullptr))) abort();
+  Pk13ExcRows ex{};
+  ex.W = g.W;
+  ex.n = nrows;
+  for (int i = 0; i < PK13_MAX_EXC; ++i) {
+    ex.row[i] = i < nrows ? rows[i] : -1;
+    if (i < nrows && (rows[i] < 0 || rows[i] >= mat_rows)) abort();   // the kernel reads row rows[i] of W
+  }
   GemvPk13Args a{};
   a.p = packed; a.x = g.x; a.norm_w = g.norm_w; a.residual = g.residual; a.y = g.y; a.y_f32 = g.y_f32;
   a.blk_max = g.blk_max; a.blk_idx = g.blk_idx; a.h_out = g.h_out; a.N = g.N; a.K = g.K; a.bh = bh; a.eps = g.eps;
   const GemvPk13Plan p = plan_gemv_pk13(g.N, epi);
   switch (epi) {
-    case GEMV_STORE: launch_pk13_epi<1, GEMV_STORE>(a, p, st); break;
-    case GEMV_RESIDUAL: launch_pk13_epi<1, GEMV_RESIDUAL>(a, p, st); break;
-    case GEMV_SILU_MUL: launch_pk13_epi<1, GEMV_SILU_MUL>(a, p, st); break;
-    case GEMV_LOGITS: launch_pk13_epi<2, GEMV_LOGITS>(a, p, st); break;
+    case GEMV_STORE: launch_pk13_epi<1, GEMV_STORE>(a, p, ex, st); break;
+    case GEMV_RESIDUAL: launch_pk13_epi<1, GEMV_RESIDUAL>(a, p, ex, st); break;
+    case GEMV_SILU_MUL: launch_pk13_epi<1, GEMV_SILU_MUL>(a, p, ex, st); break;
+    case GEMV_LOGITS: launch_pk13_epi<2, GEMV_LOGITS>(a, p, ex, st); break;
     default: abort();   // GEMV_PARTIAL_F32: sharded models have no copies
   }
+}
+
+void launch_gemv_pk13(const GemvArgs& g, const void* packed, int bh, GemvEpi epi, hipStream_t st) {
+  launch_gemv_pk13(g, packed, bh, nullptr, 0, epi, st);
 }
 
 }  // namespace aha

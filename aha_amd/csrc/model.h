@@ -31,8 +31,13 @@ void set_error(const std::string& msg);
 struct Pk13Copy {
   void* p = nullptr;   // pk13_bytes(N, K), a hipMalloc of its own (freed by model_free_packed)
   int bh = 0;          // the matrix's exponent base
+  // exception rows: rows of w (ascending, in its own order) with a finite weight below the window, which the kernel computes from w itself
+  const void* w = nullptr;   // the bf16 matrix the copy was made of (the model keeps it)
+  int nrows = 0;
+  int rows[PK13_MAX_EXC] = {};
 };
-struct Pk13Entry { std::string name; Pk13Copy* slot; std::string status; };   // aha_hip_pk13_status: "packed" or the reason it is not
+// aha_hip_pk13_status: "packed", "<n> weights outside the window: packed, rows ... read from bf16", or the reason there is no copy
+struct Pk13Entry { std::string name; Pk13Copy* slot; std::string status; };
 
 struct LayerWeights {
   void* wqkv = nullptr;     // ((nh+2kvh)*d, H): q rows, then k rows, then v rows

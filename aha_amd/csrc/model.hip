@@ -558,8 +558,9 @@ static void model_free_packed(aha_model* m, const char* why) {
 }
 
 // Called once, at the end of model_create: the four layer matrices and lm_head of an unsharded model get a copy each if the matrix is
-// large enough, in whole units, inside the format's window, and the device has the copies' bytes plus a tenth more free -- else the model
-// keeps reading bf16, and aha_hip_pk13_status says why.  AHA_WPACK=0 makes no copies.
+// large enough, in whole units, finite, with weights below the format's window in at most PK13_MAX_EXC rows (the exception rows, which the
+// matvec then computes from the bf16 matrix), and the device has the copies' bytes plus a tenth more free -- else the model keeps reading
+// bf16, and aha_hip_pk13_status says why.  AHA_WPACK=0 makes no copies.
 static int model_pack_weights(aha_model* m) {
   const aha_model_desc& c = m->desc;
   struct Mat { const void* w; int N, K; };
@@ -580,8 +581,10 @@ static int model_pack_weights(aha_model* m) {
   m->pk13.push_back({c.tie_word_embeddings ? "embed_tokens.weight (tied lm_head)" : "lm_head.weight", &m->p_lm_head, ""});
   mats.push_back({m->lm_head, m->lm_rows, H});
   auto all = [&](const char* why) {
-    for (Pk13Entry& e : m->pk13)
+    for (Pk13Entry& e : m->pk13) {
       if (e.status.empty()) e.status = why;
+      if (!e.slot->p) *e.slot = Pk13Copy{};
+    }
     return AHA_OK;
   };
   const char* env = getenv("AHA_WPACK");
@@ -603,7 +606,7 @@ static int model_pack_weights(aha_model* m) {
       return all("not enough device memory");
     }
     hipError_t e = hipMemsetAsync(d, 0, cand.size() * sizeof(Pk13Stats), st);
-    for (size_t k = 0; k < cand.size() && e == hipSuccess; ++k) launch_pk13_stats(mats[cand[k]].w, (int64_t)mats[cand[k]].N * mats[cand[k]].K, d + k, st);
+    for (size_t k = 0; k < cand.size() && e == hipSuccess; ++k) launch_pk13_stats(mats[cand[k]].w, mats[cand[k]].N, mats[cand[k]].K, d + k, st);
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d, cand.size() * sizeof(Pk13Stats), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -611,13 +614,25 @@ static int model_pack_weights(aha_model* m) {
     AHA_HIP_CHECK(e);
   }
   std::vector<size_t> take;
+  std::vector<std::string> row_note(mats.size());   // the status of a matrix that is packed with exception rows
   size_t bytes = 0;
   for (size_t k = 0; k < cand.size(); ++k) {
-    if (h[k].bad) {
+    Pk13Copy& pk = *m->pk13[cand[k]].slot;
+    // finite weights below the window in at most PK13_MAX_EXC rows: packed all the same, and the matvec reads those rows from bf16
+    pk.nrows = h[k].bad ? pk13_exception_rows(h[k], pk.rows) : 0;
+    if (h[k].nonfinite || pk.nrows > PK13_MAX_EXC) {
       m->pk13[cand[k]].status = std::to_string(h[k].bad) + " weights outside the window (Inf, NaN, or more than 30 binades below the matrix maximum)";
+      pk = Pk13Copy{};
       continue;
     }
-    m->pk13[cand[k]].slot->bh = pk13_base(h[k].max_e2);
+    if (h[k].bad) {
+      std::string& why = row_note[cand[k]];
+      why = std::to_string(h[k].bad) + " weights outside the window: packed, rows";
+      for (int i = 0; i < pk.nrows; ++i) why += (i ? ", " : " ") + std::to_string(pk.rows[i]);
+      why += " read from bf16";
+    }
+    pk.w = mats[cand[k]].w;
+    pk.bh = pk13_base(h[k].max_e2);
     take.push_back(cand[k]);
     bytes += pk13_bytes(mats[cand[k]].N, mats[cand[k]].K);
   }
@@ -636,7 +651,7 @@ static int model_pack_weights(aha_model* m) {
       return all("not enough device memory");
     }
     launch_pk13_pack(mats[i].w, mats[i].N, mats[i].K, m->pk13[i].slot->bh, m->pk13[i].slot->p, st);
-    m->pk13[i].status = "packed";
+    m->pk13[i].status = row_note[i].empty() ? "packed" : row_note[i];
   }
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1105,7 +1120,11 @@ static void decode_gemv(aha_model* m, const GemvArgs& g, GemvEpi epi, const WQua
   ProfScope ps(m, fp8 ? "gemv_fp8" : fp4 ? "gemv_fp4" : "gemv", weights * (fp8 ? 1.03125 : fp4 ? 0.53125 : p13 ? 1.625 : 2.0) + act_bytes, 2.0 * weights);
   if (fp8) launch_gemv_mxfp8(g, wq.q, wq.scales, epi, m->stream);
   else if (fp4) launch_gemv_mxfp4(g, wq.q, wq.scales, epi, m->stream);
-  else if (p13) launch_gemv_pk13(g, pk.p, pk.bh, epi, m->stream);
+  else if (p13) {
+    GemvArgs gw = g;
+    gw.W = pk.w;   // read only for the exception rows
+    launch_gemv_pk13(gw, pk.p, pk.bh, pk.rows, pk.nrows, epi, m->stream);
+  }
   else if (epi == GEMV_RESIDUAL) gemv_row_parallel(m, g);
   else launch_gemv(g, epi, m->stream);
 }

@@ -632,7 +632,8 @@ class HipInferenceModel:
         check(lib().aha_hip_debug_pk13_single(self.handle, int(on)))
 
     def pk13_status(self):
-        """{tensor name: "packed" or the reason the matrix has no exact 13-bit copy} (aha_hip_pk13_status)."""
+        """{tensor name: "packed", "<n> weights outside the window: packed, rows <list> read from bf16" (a copy whose exception rows the matvec
+        computes from the bf16 matrix), or the reason the matrix has no exact 13-bit copy} (aha_hip_pk13_status)."""
         buf = C.create_string_buffer(1 << 16)
         n = lib().aha_hip_pk13_status(self.handle, buf, len(buf))
         if n < 0:

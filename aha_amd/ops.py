@@ -562,6 +562,38 @@ def gemv_pk13(packed: torch.Tensor, bh: int, x: torch.Tensor, epi: int = GEMV_RO
     return (logits, int(am.item())) if epi == GEMV_ROWS_LOGITS else y
 
 
+def pack_pk13_rows(W: torch.Tensor, cap: int = 16, check_only: bool = False):
+    """pack_pk13 for a matrix that may hold finite weights below the window (aha_hip_pack_pk13_rows; quant.check_pk13_rows / pack_pk13_rows
+    are its restatement): (packed or None, bh, rows, below, nonfinite).  rows: the rows of W (ascending, at most 16) that hold such a weight
+    and that gemv_pk13_rows reads from W itself, or None if there are more than 16.  Packed if nonfinite == 0 and len(rows) <= cap."""
+    _chk(W)
+    N, K = W.shape
+    bh, n, below, nonfinite = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+    rows = (C.c_int32 * 16)()
+    out = None if check_only else torch.zeros(N, K // 4096, 6656, dtype=torch.uint8, device=W.device)
+    check(lib().aha_hip_pack_pk13_rows(_ptr(W), N, K, _ptr(out), C.byref(bh), rows, cap, C.byref(n), C.byref(below), C.byref(nonfinite), _stream()))
+    got = None if n.value > 16 else [int(rows[i]) for i in range(min(n.value, cap))]
+    ok = nonfinite.value == 0 and n.value <= cap
+    return (out if ok else None), bh.value, got, below.value, nonfinite.value
+
+
+def gemv_pk13_rows(packed: torch.Tensor, bh: int, W: Optional[torch.Tensor], rows, x: torch.Tensor, epi: int = GEMV_ROWS_STORE,
+                   norm_w: Optional[torch.Tensor] = None, eps: float = 1e-6, residual: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None):
+    """gemv_pk13 with exception rows (aha_hip_gemv_pk13_rows): the rows of W listed in `rows` (at most 16) are computed from the bf16 matrix
+    W, every other row from the copy.  Every output bit, and the argmax, equals gemv_epi(W, ...).  An empty list is gemv_pk13."""
+    _chk(packed, x, norm_w, residual, out)
+    if W is not None:
+        _chk(W)
+    N, K = packed.shape[0], packed.shape[1] * 4096
+    rows = [int(r) for r in rows]
+    arr = (C.c_int32 * max(len(rows), 1))(*rows)
+    y, logits, am = _gemv_epi_outputs(N, epi, x.device, out)
+    check(lib().aha_hip_gemv_pk13_rows(_ptr(packed), bh, _ptr(W), arr, len(rows), _ptr(x), _ptr(y), N, K, epi, _ptr(norm_w), eps, _ptr(residual),
+                                       _ptr(logits), _ptr(am), _stream()))
+    return (logits, int(am.item())) if epi == GEMV_ROWS_LOGITS else y
+
+
 def plan_gemv_pk13(N: int, K: int, epi: int = GEMV_ROWS_STORE, has_norm: bool = False):
     """Host only: (R, U, grid, form) gemv_pk13 picks for a matrix of N rows (aha_hip_debug_plan_gemv_pk13): U is 8, form 1 FAST, 2 / 3 FAST
     with the straight-line prologue without / with norm weights."""

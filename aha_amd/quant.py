@@ -20,7 +20,7 @@ on e keep every non-zero w' = q * 2^e at 2^-126 or above and finite, and q has t
 takes e - 1 with doubled q).  Weights must be finite and at most 1.5 * 2^127 in magnitude: beyond it w / 2^125 rounds past 6.  The
 library's kernel is csrc/kernels_gemv_rows_fp4.hip; tests/test_weights_fp4_gpu.py compares the two.  Nothing here needs a torch float4 dtype.
 """
-from typing import Tuple
+from typing import List, Tuple
 
 import torch
 
@@ -203,6 +203,45 @@ def pack_pk13(W: torch.Tensor, bh: int) -> torch.Tensor:
             sb |= s5[:, :, :, cc, :, half, :] << (cc * 2 + half)
     sp = sb.permute(0, 1, 3, 2, 4).reshape(N, J, 64 * 8)
     return torch.cat([a, hp, sp], dim=2).to(torch.uint8)
+
+
+PK13_MAX_ROWS = 16        # rows of a matrix the matvec may read from bf16 (aha_hip_pack_pk13_rows)
+
+
+def _below_window(W: torch.Tensor, bh: int) -> torch.Tensor:
+    bits = _bf16_bits(W)
+    e2 = (bits >> 8) & 0x7f
+    return ((bits & 0x7f80) != 0x7f80) & (e2 != 0) & (e2 <= bh)
+
+
+def check_pk13_rows(W: torch.Tensor) -> Tuple[int, int, List[int]]:
+    """(bh, nonfinite, rows): check_pk13's base, the number of Inf / NaN, and the rows of W (ascending) that hold a finite weight below the
+    window -- the exception rows the matvec reads from W itself.  Pack if nonfinite == 0 and len(rows) <= PK13_MAX_ROWS."""
+    bh, _ = check_pk13(W)
+    bits = _bf16_bits(W)
+    nonfinite = int(((bits & 0x7f80) == 0x7f80).sum())
+    rows = torch.nonzero(_below_window(W, bh).any(dim=1)).flatten().tolist()
+    return bh, nonfinite, rows
+
+
+def packable_pk13_rows(nonfinite: int, rows) -> bool:
+    """The rule of model_pack_weights and aha_hip_pack_pk13_rows: no Inf / NaN, at most PK13_MAX_ROWS exception rows."""
+    return nonfinite == 0 and len(rows) <= PK13_MAX_ROWS
+
+
+def pack_pk13_rows(W: torch.Tensor, bh: int) -> torch.Tensor:
+    """pack_pk13 of W with every finite weight below the window taken as +0: what the copy holds there is never used."""
+    Wz = W.clone()
+    Wz[_below_window(W, bh)] = 0.0
+    return pack_pk13(Wz, bh)
+
+
+def unpack_pk13_rows(P: torch.Tensor, bh: int, W: torch.Tensor, rows) -> torch.Tensor:
+    """The matrix the matvec computes with: unpack_pk13 of the copy, the exception rows taken from W.  Equals W bit for bit."""
+    out = unpack_pk13(P, bh).clone()
+    for r in rows:
+        out[r] = W[r]
+    return out
 
 
 def unpack_pk13(P: torch.Tensor, bh: int) -> torch.Tensor:

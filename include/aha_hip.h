@@ -775,15 +775,16 @@ int aha_hip_debug_fp8_single(aha_model* m, int on);
 int aha_hip_debug_fp4_single(aha_model* m, int on);
 /* Exact 13-bit weight copies.  When a model is created unsharded, each of the four layer matrices and lm_head gets a copy that holds
  * every bf16 weight exactly in 13 bits (aha_hip_pack_pk13 has the format) if the matrix has at least 2^24 elements, K is a multiple of
- * 4096, every weight lies in the format's window, and the device has the copies' bytes plus a tenth more free; otherwise that matrix,
- * or every matrix, stays without one, silently.  The single-sequence decode matvec then streams 0.8125 of the bytes and computes the same
+ * 4096, every weight is finite, at most 16 rows hold a weight below the format's window (those rows are then read from the bf16 matrix,
+ * aha_hip_pack_pk13_rows), and the device has the copies' bytes plus a tenth more free; otherwise that matrix, or every matrix, stays
+ * without one, silently.  The single-sequence decode matvec then streams 0.8125 of the bytes and computes the same
  * bits (gemv_kernel_pk13; profiles/weights_pk13.md).  AHA_WPACK=0 in the environment, read when a model is created, makes no copies.
  * aha_hip_model_quantize_weights frees the copies: a quantised model never reads them.
  * aha_hip_debug_pk13_single: on = 1 (the default): a matrix with a copy is read from it where the plan takes its shape
  * (aha_hip_debug_plan_gemv_pk13 tells); 2: wherever a copy exists; 0: nowhere (the bf16 kernel).  The bits are the same in all three, and
  * the launches stay in profile class gemv, at 1.625 bytes per weight.  AHA_ERR_INVALID: a null model or another value.
- * aha_hip_pk13_status: one line per matrix into buf (NUL-terminated, truncated to cap), "<tensor name>\t<status>\n", status "packed" or
- * the reason the matrix has no copy; returns the number of matrices with a copy, or a negative error. */
+ * aha_hip_pk13_status: one line per matrix into buf (NUL-terminated, truncated to cap), "<tensor name>\t<status>\n", status "packed",
+ * "<n> weights outside the window: packed, rows <list> read from bf16", or the reason the matrix has no copy; returns the number of matrices with a copy, or a negative error. */
 int aha_hip_debug_pk13_single(aha_model* m, int on);
 int aha_hip_pk13_status(const aha_model* m, char* buf, size_t cap);
 
@@ -967,6 +968,20 @@ int aha_hip_gemv_mxfp4(const void* q, const uint32_t* scales, const void* x, voi
 int aha_hip_pack_pk13(const void* W, int32_t N, int32_t K, void* out, int32_t* bh_out, int64_t* bad_out, void* stream);
 int aha_hip_gemv_pk13(const void* packed, int32_t bh, const void* x, void* y, int32_t N, int32_t K, int32_t epi, const void* norm_w,
                       float eps, const void* residual, float* logits, uint32_t* argmax_out, void* stream);
+/* Exception rows.  Finite weights below the window do not keep a matrix from being packed as long as at most 16 rows of W hold one: the
+ * copy has an arbitrary code at such a weight, and the matvec computes those rows from W itself (gemv_kernel_rows_pk13), still bit for bit
+ * what aha_hip_gemv_epi gives on W.  Inf / NaN keep a matrix unpacked.
+ * aha_hip_pack_pk13_rows: *nonfinite_out = the number of Inf / NaN, *below_out = the number of finite weights below the window,
+ * *nrows_out = the number of rows that hold one (17 stands for "more than 16"), rows_out (host, cap entries, cap 0..16) = those rows
+ * ascending, as many as fit, in W's own order (for a gate / up matrix: rows of the fused 16-row-alternating matrix).  out (may be NULL)
+ * receives the copy if *nonfinite_out == 0 and *nrows_out <= cap and is left untouched otherwise.  Synchronises the stream.
+ * aha_hip_gemv_pk13_rows: aha_hip_gemv_pk13 with the bf16 matrix W (device) and the row list (host, nrows 0..16, each a row of W);
+ * nrows == 0 is aha_hip_gemv_pk13 and needs neither.  Messages prefixed "gemv_pk13_rows:". */
+int aha_hip_pack_pk13_rows(const void* W, int32_t N, int32_t K, void* out, int32_t* bh_out, int32_t* rows_out, int32_t cap, int32_t* nrows_out,
+                           int64_t* below_out, int64_t* nonfinite_out, void* stream);
+int aha_hip_gemv_pk13_rows(const void* packed, int32_t bh, const void* W, const int32_t* rows, int32_t nrows, const void* x, void* y, int32_t N,
+                           int32_t K, int32_t epi, const void* norm_w, float eps, const void* residual, float* logits, uint32_t* argmax_out,
+                           void* stream);
 int aha_hip_quantize_mxfp4(const void* W, int32_t N, int32_t K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, void* stream);
 int aha_hip_gemv_rows_mxfp4(const void* q, const uint32_t* scales, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi,
                             const void* residual, float* logits, uint32_t* argmax_out, void* stream);
