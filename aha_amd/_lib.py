@@ -288,6 +288,9 @@ SIGNATURES = {
     "aha_hip_debug_gemv_partial_f32": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_float, _P]),
     "aha_hip_attn_decode_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "aha_hip_debug_attn_decode_fused": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
+    "aha_hip_debug_attn_decode_rows": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, C.c_int32,
+                                                 _P]),
+    "aha_hip_debug_spec_accept": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
     "aha_hip_config_parse": (C.c_int, [C.c_char_p, _P]),
     "aha_hip_config_torch_dtype": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
     "aha_hip_weights_open": (C.c_int, [C.c_char_p, _P]),

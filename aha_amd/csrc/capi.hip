@@ -1608,6 +1608,23 @@ int aha_hip_logprob_rows(const float* logits, int64_t ld, int32_t R, int32_t V, 
 
 static bool attn_batch_geometry_ok(int32_t nh, int32_t kvh) { return nh > 0 && kvh > 0 && nh % kvh == 0 && nh / kvh <= 16 && kvh <= 64; }
 
+// The row table of an op-level decode attention call: splits from the row's own length, counters from zero, one counter block per row.
+// -> the largest split count of a row.
+static int attn_batch_row_table(const int32_t* page0, const int32_t* kv_len, int rows, int g, std::vector<int32_t>& tab) {
+  int max_split = 1;
+  tab.assign((size_t)rows * GEN_ROW_WORDS, 0);
+  for (int r = 0; r < rows; ++r) {
+    int32_t* t = tab.data() + (size_t)r * GEN_ROW_WORDS;
+    t[GEN_ROW_PAGE0] = page0[r];
+    t[GEN_ROW_KVLEN] = kv_len[r];
+    t[GEN_ROW_NSPLIT] = attn_decode_nsplit(kv_len[r], g, 64);
+    t[GEN_ROW_POS] = kv_len[r] - 1;
+    t[GEN_ROW_CTRROW] = r;
+    max_split = std::max(max_split, t[GEN_ROW_NSPLIT]);
+  }
+  return max_split;
+}
+
 int aha_hip_attn_decode_batch(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
                               const int32_t* page0, const int32_t* kv_len, int32_t rows, int32_t nh, int32_t kvh, float eps, float scale,
                               void* o, void* stream) {
@@ -1622,18 +1639,8 @@ int aha_hip_attn_decode_batch(const void* qkv, const void* q_norm_w, const void*
       return AHA_ERR_INVALID;
     }
   hipStream_t st = (hipStream_t)stream;
-  const int g = nh / kvh;
-  int max_split = 1;
-  std::vector<int32_t> tab((size_t)rows * GEN_ROW_WORDS, 0);
-  for (int r = 0; r < rows; ++r) {
-    int32_t* t = tab.data() + (size_t)r * GEN_ROW_WORDS;
-    t[GEN_ROW_PAGE0] = page0[r];
-    t[GEN_ROW_KVLEN] = kv_len[r];
-    t[GEN_ROW_NSPLIT] = attn_decode_nsplit(kv_len[r], g, 64);
-    t[GEN_ROW_POS] = kv_len[r] - 1;
-    t[GEN_ROW_CTRROW] = r;
-    max_split = std::max(max_split, t[GEN_ROW_NSPLIT]);
-  }
+  std::vector<int32_t> tab;
+  const int max_split = attn_batch_row_table(page0, kv_len, rows, nh / kvh, tab);
   int32_t* d_tab = nullptr;
   float *po = nullptr, *pml = nullptr;
   unsigned* ctr = nullptr;
@@ -1654,6 +1661,81 @@ int aha_hip_attn_decode_batch(const void* qkv, const void* q_norm_w, const void*
   hipFree(po);
   hipFree(pml);
   hipFree(ctr);
+  AHA_HIP_CHECK(err);
+  return AHA_OK;
+  API_GUARD_END
+}
+
+int aha_hip_debug_attn_decode_rows(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
+                                   const int32_t* page0, const int32_t* kv_len, int32_t rows, int32_t nh, int32_t kvh, float eps, float scale,
+                                   void* o, int32_t form, void* stream) {
+  API_GUARD_BEGIN
+  const char* who = "debug_attn_decode_rows: ";
+  auto bad = [&](const std::string& why) {
+    set_error(who + why);
+    return AHA_ERR_INVALID;
+  };
+  if (form < 0 || form > 2) return bad("form must be 0 .. 2");
+  if (!qkv || !q_norm_w || !k_norm_w || !rope || !page_ptrs || !page0 || !kv_len || (!o && form != 2)) return bad("null pointer");
+  if (rows < 1 || rows > 65535 || !attn_batch_geometry_ok(nh, kvh)) return bad("bad arguments (rows 1 .. 65535, nh % kvh == 0, group size <= 16)");
+  for (int r = 0; r < rows; ++r)
+    if (kv_len[r] < 1 || page0[r] < 0) return bad("row " + std::to_string(r) + " needs kv_len >= 1 and page0 >= 0");
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<int32_t> tab;
+  const int max_split = attn_batch_row_table(page0, kv_len, rows, nh / kvh, tab);
+  DevBuf d_tab, po, pml, ctr;
+  if (int rc = d_tab.upload(tab.data(), tab.size() * 4)) return rc;
+  AttnDecodeBatchArgs b{};
+  b.qkv = qkv; b.q_norm_w = q_norm_w; b.k_norm_w = k_norm_w; b.rope = rope; b.page_ptrs = page_ptrs; b.layer_off = 0;
+  b.row_tab = (const int32_t*)d_tab.p; b.o = o; b.ctr_step = 1; b.nh = nh; b.kvh = kvh; b.max_nsplit = max_split; b.eps = eps; b.scale = scale;
+  if (form != 2) {
+    AHA_HIP_CHECK(hipMalloc(&po.p, (size_t)rows * max_split * nh * 128 * 4));
+    AHA_HIP_CHECK(hipMalloc(&pml.p, (size_t)rows * max_split * nh * 2 * 4));
+    AHA_HIP_CHECK(hipMalloc(&ctr.p, (size_t)rows * kvh * 32 * 4));
+    AHA_HIP_CHECK(hipMemsetAsync(ctr.p, 0, (size_t)rows * kvh * 32 * 4, st));
+    b.part_o = (float*)po.p; b.part_ml = (float*)pml.p; b.head_ctr = (unsigned*)ctr.p;
+  }
+  if (form != 0) launch_kv_append_rows(b, rows, st);
+  if (form != 2) launch_attn_decode_batch(b, rows, max_split, st, form == 0);
+  hipError_t err = hipGetLastError();
+  hipStreamSynchronize(st);
+  AHA_HIP_CHECK(err);
+  return AHA_OK;
+  API_GUARD_END
+}
+
+int aha_hip_debug_spec_accept(const uint32_t* argmax, const int32_t* row_tok, int32_t rows, const int32_t* seq_tab, int32_t n_seqs,
+                              int32_t layout, uint32_t* out, void* stream) {
+  API_GUARD_BEGIN
+  const char* who = "debug_spec_accept: ";
+  auto bad = [&](const std::string& why) {
+    set_error(who + why);
+    return AHA_ERR_INVALID;
+  };
+  if (layout < 0 || layout > 1) return bad("layout must be 0 (consecutive rows) or 1 (own row and draft rows apart)");
+  if (!argmax || !row_tok || !seq_tab || !out) return bad("null pointer");
+  if (rows < 1 || rows > (1 << 24) || n_seqs < 1 || n_seqs > (1 << 24)) return bad("rows and n_seqs must be 1 .. 2^24");
+  const int words = layout == 0 ? SPEC_SEQ_WORDS : ENG_SEQ_WORDS;
+  for (int s = 0; s < n_seqs; ++s) {   // every row the kernel would read for sequence s lies inside the call's rows
+    const int32_t* e = seq_tab + (size_t)s * words;
+    const int64_t first = e[0], nd = layout == 0 ? e[SPEC_SEQ_NDRAFT] : e[ENG_SEQ_NDRAFT], k = std::min<int64_t>(nd, SPEC_MAX_DRAFT);
+    const int64_t d0 = layout == 0 ? first + 1 : e[ENG_SEQ_DRAFT0];
+    if (nd < 0) return bad("sequence " + std::to_string(s) + " has a negative draft count");
+    if (first < 0 || first >= rows || (k > 0 && (d0 < 0 || d0 + k > rows)))
+      return bad("sequence " + std::to_string(s) + " reaches rows outside 0 .. " + std::to_string(rows - 1));
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // the step's upload: the row table (the input token in GEN_ROW_TOK) with the sequence entries behind it
+  std::vector<int32_t> tab((size_t)rows * GEN_ROW_WORDS + (size_t)n_seqs * words, 0);
+  for (int r = 0; r < rows; ++r) tab[(size_t)r * GEN_ROW_WORDS + GEN_ROW_TOK] = row_tok[r];
+  std::copy(seq_tab, seq_tab + (size_t)n_seqs * words, tab.begin() + (size_t)rows * GEN_ROW_WORDS);
+  DevBuf d_tab;
+  if (int rc = d_tab.upload(tab.data(), tab.size() * 4)) return rc;
+  const int32_t* rt = (const int32_t*)d_tab.p;
+  if (layout == 0) launch_spec_accept_rows(argmax, rt, rt + (size_t)rows * GEN_ROW_WORDS, n_seqs, out, st);
+  else launch_spec_accept_split(argmax, rt, rt + (size_t)rows * GEN_ROW_WORDS, n_seqs, out, st);
+  hipError_t err = hipGetLastError();
+  hipStreamSynchronize(st);
   AHA_HIP_CHECK(err);
   return AHA_OK;
   API_GUARD_END

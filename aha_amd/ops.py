@@ -666,6 +666,41 @@ def debug_attn_decode_fused(qkv_row: torch.Tensor, q_norm_w: torch.Tensor, k_nor
     return o
 
 
+ATTN_ROWS_FUSED, ATTN_ROWS_APPEND_THEN_ATTEND, ATTN_ROWS_APPEND_ONLY = 0, 1, 2
+SPEC_MAX_DRAFT, SPEC_OUT_WORDS = 15, 18   # kernels.h: the accept record is {count, last row, tokens[16]}
+
+
+def debug_attn_decode_rows(qkv: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: torch.Tensor, rope: torch.Tensor, page_ptrs: torch.Tensor,
+                           page0, kv_len, nh: int, kvh: int, eps: float, scale: float, form: int) -> Optional[torch.Tensor]:
+    """Test entry (aha_hip_debug_attn_decode_rows): attn_decode_batch's arguments, rows of one sequence allowed (the same page0, kv_len
+    ascending by one: a last token and its drafts).  form 0: the default launch (append inside the attention); 1: the KV append of every
+    row, then the attention without its append, as a draft-and-verify step queues them; 2: the append alone.  -> (R, nh*128) bf16, None
+    for form 2."""
+    _chk(qkv, q_norm_w, k_norm_w, rope, page_ptrs)
+    R = qkv.shape[0]
+    p0 = np.ascontiguousarray(np.asarray(page0, dtype=np.int32).reshape(R))
+    kl = np.ascontiguousarray(np.asarray(kv_len, dtype=np.int32).reshape(R))
+    o = None if form == ATTN_ROWS_APPEND_ONLY else torch.empty(R, nh * 128, dtype=torch.bfloat16, device=qkv.device)
+    check(lib().aha_hip_debug_attn_decode_rows(_ptr(qkv), _ptr(q_norm_w), _ptr(k_norm_w), _ptr(rope), _ptr(page_ptrs), p0.ctypes.data,
+                                               kl.ctypes.data, R, nh, kvh, eps, scale, _ptr(o), int(form), _stream()))
+    return o
+
+
+def debug_spec_accept(argmax: torch.Tensor, row_tok, seq_tab, layout: int) -> torch.Tensor:
+    """Test entry (aha_hip_debug_spec_accept): the accept kernel of a draft-and-verify step.  argmax (rows) int32 / uint32 on the device,
+    row_tok: the rows' input tokens (host ints), seq_tab: per sequence (row0, n_draft) for layout 0 (spec_accept_rows_kernel) or (own row,
+    first draft row, n_draft) for layout 1 (spec_accept_split_kernel).  -> (n_seqs, 18) int32 on the device: {count, last row, tokens[16]}
+    per sequence, words behind the count as allocated (0xffffffff)."""
+    _chk(argmax)
+    assert argmax.dim() == 1 and argmax.element_size() == 4
+    rows = argmax.numel()
+    tok = np.ascontiguousarray(np.asarray(row_tok, dtype=np.int64).reshape(rows).astype(np.int32))
+    seq = np.ascontiguousarray(np.asarray(seq_tab, dtype=np.int32).reshape(-1, 3 if layout else 2))
+    out = torch.full((seq.shape[0], SPEC_OUT_WORDS), -1, dtype=torch.int32, device=argmax.device)
+    check(lib().aha_hip_debug_spec_accept(_ptr(argmax), tok.ctypes.data, rows, seq.ctypes.data, seq.shape[0], int(layout), _ptr(out), _stream()))
+    return out
+
+
 def sample_rows(logits: torch.Tensor, k, temperature, repeat_penalty, contexts):
     """aha_hip_sample_candidates for every row of logits (R, V) f32 (row pitch logits.stride(0)) in one launch per stage: row r with
     k[r] (1..64), temperature[r], repeat_penalty[r] over the ids contexts[r].  The logits are only read.  -> (vals (R, 64) f32,

@@ -995,6 +995,24 @@ int aha_hip_attn_decode_batch(const void* qkv, const void* q_norm_w, const void*
 /* Debug: the single-sequence fused decode attention kernel (the decode step's) on one sequence whose pages are page_ptrs[0 ..]. */
 int aha_hip_debug_attn_decode_fused(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
                                     int32_t kv_len, int32_t nh, int32_t kvh, float eps, float scale, void* o, void* stream);
+/* Test entry: the attention launches of a draft-and-verify decode step on pages of the caller.  The arguments, the row table
+ * (splits from the row's own length, counters zeroed, one counter block per row, ctr_step 1) and the checks are
+ * aha_hip_attn_decode_batch's; several rows may name the same page0 (a sequence's last token and its drafts, kv_len ascending by one).
+ * form 0: the default launch, the append inside the attention (= aha_hip_attn_decode_batch).  form 1: the KV append of every row, then
+ * the attention without its append -- the pair a step with drafts queues.  form 2: the KV append alone (o may be NULL).
+ * AHA_ERR_INVALID, before any device work, for what aha_hip_attn_decode_batch refuses or a form outside 0 .. 2.  Synchronises the stream. */
+int aha_hip_debug_attn_decode_rows(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
+                                   const int32_t* page0, const int32_t* kv_len, int32_t rows, int32_t nh, int32_t kvh, float eps, float scale,
+                                   void* o, int32_t form, void* stream);
+/* Test entry: the accept step of draft-and-verify decoding.  argmax (device, rows uint32): the step's pick of every row; row_tok (HOST,
+ * rows): every row's input token (a draft row's is its draft); seq_tab (HOST): per sequence {first row, drafts} (layout 0: a sequence's
+ * rows are consecutive, generate_batch_spec's step) or {own row, first draft row, drafts} (layout 1: the engine's step).  out (device,
+ * n_seqs x 18 uint32): {emitted count, last confirmed row, tokens[16]} per sequence; words behind the count are unspecified.  At most 15
+ * drafts of a sequence are looked at.  AHA_ERR_INVALID, before any device work, for a null pointer, rows or n_seqs < 1, a layout outside
+ * 0 .. 1, a negative draft count, or a sequence whose rows (with its drafts clamped to 15) are not all inside 0 .. rows - 1.
+ * Synchronises the stream. */
+int aha_hip_debug_spec_accept(const uint32_t* argmax, const int32_t* row_tok, int32_t rows, const int32_t* seq_tab, int32_t n_seqs,
+                              int32_t layout, uint32_t* out, void* stream);
 /* aha_hip_sample_rows: aha_hip_sample_candidates for R rows of f32 logits at once (the candidate step of
  * aha_hip_generate_batch_sampled), bit-identical per row to it.  logits (device, row r at logits + r * ld, V floats) are only read;
  * k (1..64), temperature, repeat_penalty: HOST arrays of R; context / context_offsets: HOST, row r's penalty context is

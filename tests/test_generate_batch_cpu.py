@@ -19,7 +19,7 @@ def test_generate_batch_symbol_in_every_layer(hip_lib):
     assert re.search(r"int aha_hip_generate_batch\(aha_model\* m, const uint32_t\* input_ids, const size_t\* seq_lens, size_t n_seqs,"
                      r"\s+size_t max_new,\s+size_t max_tokens_per_pass, uint32_t\* tokens_out, size_t\* n_out, float\* logits_out\);", header)
     for name, nargs in (("aha_hip_generate_batch", 9), ("aha_hip_gemv_rows", 11), ("aha_hip_attn_decode_batch", 14),
-                        ("aha_hip_debug_attn_decode_fused", 12)):
+                        ("aha_hip_debug_attn_decode_fused", 12), ("aha_hip_debug_attn_decode_rows", 15), ("aha_hip_debug_spec_accept", 8)):
         assert f"int {name}(" in header, name
         assert hasattr(hip_lib, name), name
         assert len(_lib.SIGNATURES[name][1]) == nargs, name
