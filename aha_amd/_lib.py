@@ -285,6 +285,7 @@ SIGNATURES = {
                                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "aha_hip_debug_plan_gemv": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "aha_hip_debug_plan_gemv_rows": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "aha_hip_debug_gemv_partial_f32": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_float, _P]),
     "aha_hip_attn_decode_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "aha_hip_debug_attn_decode_fused": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),

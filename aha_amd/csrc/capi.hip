@@ -1174,6 +1174,17 @@ int aha_hip_debug_plan_gemv(int32_t N, int32_t K, int32_t epi, int32_t has_norm,
   return AHA_OK;
 }
 
+int aha_hip_debug_plan_gemv_rows(int32_t N, int32_t K, int32_t* cw, int32_t* nks) {
+  if (!cw || !nks || N < 1 || K < 8 || K % 8) {
+    set_error("debug_plan_gemv_rows: bad argument (cw, nks not null, N >= 1, K a positive multiple of 8)");
+    return AHA_ERR_INVALID;
+  }
+  int c, s;
+  gemv_rows_plan(N, K, &c, &s);
+  *cw = c; *nks = s;
+  return AHA_OK;
+}
+
 int aha_hip_debug_gemv_partial_f32(const void* W, const void* x, float* y_f32, int32_t N, int32_t K, const void* norm_w, float eps,
                                    void* stream) {
   API_GUARD_BEGIN

@@ -397,18 +397,31 @@ def logmel_batch(clips) -> torch.Tensor:
 GEMV_ROWS_STORE, GEMV_ROWS_RESIDUAL, GEMV_ROWS_SILU_MUL, GEMV_ROWS_LOGITS = 0, 1, 2, 3
 
 
-def gemv_rows(W: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, residual: Optional[torch.Tensor] = None):
-    """y[R, N] = x[R, K] . W[N, K]^T for 1 <= R <= 32, weights streamed once.  epi STORE / RESIDUAL -> (R, N) bf16; SILU_MUL (W in the
-    16-row gate / up block layout) -> (R, N/2) bf16; LOGITS -> ((R, N) f32 logits, (R,) int64 argmax)."""
-    _chk(W, x, residual)
-    N, K = W.shape
-    R = x.shape[0]
+def _gemv_rows_outputs(R: int, N: int, epi: int, device, out: Optional[torch.Tensor]):
+    """(y, logits, argmax) of a gemv_rows call.  `out`: the caller's (R, N_out) bf16 tensor for the bf16 epilogues -- rows of a larger
+    buffer, or the residual itself (the in-place form the model runs)."""
     y = logits = am = None
     if epi == GEMV_ROWS_LOGITS:
-        logits = torch.empty(R, N, dtype=torch.float32, device=x.device)
-        am = torch.empty(R, dtype=torch.int32, device=x.device)
+        if out is not None:
+            raise ValueError("gemv_rows: out= is for the bf16 epilogues")
+        logits = torch.empty(R, N, dtype=torch.float32, device=device)
+        am = torch.empty(R, dtype=torch.int32, device=device)
     else:
-        y = torch.empty(R, N // 2 if epi == GEMV_ROWS_SILU_MUL else N, dtype=torch.bfloat16, device=x.device)
+        shape = (R, N // 2 if epi == GEMV_ROWS_SILU_MUL else N)
+        if out is not None and (out.dtype != torch.bfloat16 or tuple(out.shape) != shape):
+            raise ValueError(f"gemv_rows: out must be {shape} bf16")
+        y = out if out is not None else torch.empty(shape, dtype=torch.bfloat16, device=device)
+    return y, logits, am
+
+
+def gemv_rows(W: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, residual: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None):
+    """y[R, N] = x[R, K] . W[N, K]^T for 1 <= R <= 32, weights streamed once.  epi STORE / RESIDUAL -> (R, N) bf16 (`out` may be the
+    residual itself); SILU_MUL (W in the 16-row gate / up block layout) -> (R, N/2) bf16; LOGITS -> ((R, N) f32 logits, (R,) int64 argmax)."""
+    _chk(W, x, residual, out)
+    N, K = W.shape
+    R = x.shape[0]
+    y, logits, am = _gemv_rows_outputs(R, N, epi, x.device, out)
     check(lib().aha_hip_gemv_rows(_ptr(W), _ptr(x), _ptr(y), R, N, K, epi, _ptr(residual), _ptr(logits), _ptr(am), _stream()))
     return (logits, am.long()) if epi == GEMV_ROWS_LOGITS else y
 
@@ -425,18 +438,14 @@ def _quantize_mx(entry, W: torch.Tensor, k_per_byte: int):
     return q, quant.scales_from_kernel(words, K).to(W.device), wr
 
 
-def _gemv_rows_mx(entry, q: torch.Tensor, K: int, scales: torch.Tensor, x: torch.Tensor, epi: int, residual: Optional[torch.Tensor]):
+def _gemv_rows_mx(entry, q: torch.Tensor, K: int, scales: torch.Tensor, x: torch.Tensor, epi: int, residual: Optional[torch.Tensor],
+                  out: Optional[torch.Tensor] = None):
     """gemv_rows from an MX copy (q, scales) of a matrix with K columns, through the C entry of its format."""
     from . import quant
-    _chk(q, x, residual)
+    _chk(q, x, residual, out)
     N, R = q.shape[0], x.shape[0]
     words = quant.scales_to_kernel(scales).to(x.device)
-    y = logits = am = None
-    if epi == GEMV_ROWS_LOGITS:
-        logits = torch.empty(R, N, dtype=torch.float32, device=x.device)
-        am = torch.empty(R, dtype=torch.int32, device=x.device)
-    else:
-        y = torch.empty(R, N // 2 if epi == GEMV_ROWS_SILU_MUL else N, dtype=torch.bfloat16, device=x.device)
+    y, logits, am = _gemv_rows_outputs(R, N, epi, x.device, out)
     check(entry(_ptr(q), _ptr(words), _ptr(x), _ptr(y), R, N, K, epi, _ptr(residual), _ptr(logits), _ptr(am), _stream()))
     return (logits, am.long()) if epi == GEMV_ROWS_LOGITS else y
 
@@ -447,10 +456,11 @@ def quantize_mxfp8(W: torch.Tensor):
     return _quantize_mx(lib().aha_hip_quantize_mxfp8, W, 1)
 
 
-def gemv_rows_mxfp8(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, residual: Optional[torch.Tensor] = None):
+def gemv_rows_mxfp8(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, residual: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None):
     """gemv_rows from the MXFP8 copy of W: q (N, K) uint8, scales (N, K / 32) uint8 in the reference's order (converted to the kernel's
     words here).  Every output bit equals gemv_rows(W', x, epi, residual) for W' = dequantize_mxfp8(q, scales)."""
-    return _gemv_rows_mx(lib().aha_hip_gemv_rows_mxfp8, q, q.shape[1], scales, x, epi, residual)
+    return _gemv_rows_mx(lib().aha_hip_gemv_rows_mxfp8, q, q.shape[1], scales, x, epi, residual, out)
 
 
 def quantize_mxfp4(W: torch.Tensor):
@@ -460,14 +470,15 @@ def quantize_mxfp4(W: torch.Tensor):
     return _quantize_mx(lib().aha_hip_quantize_mxfp4, W, 2)
 
 
-def gemv_rows_mxfp4(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, residual: Optional[torch.Tensor] = None):
+def gemv_rows_mxfp4(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, residual: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None):
     """gemv_rows from the MXFP4 copy of W: q (N, K / 2) uint8 packed E2M1 codes, scales (N, K / 32) uint8 in the reference's order
     (converted to the kernel's words here).  Every output bit equals gemv_rows(W', x, epi, residual) for W' = dequantize_mxfp4(q, scales)."""
-    _chk(q, x, residual)
+    _chk(q, x, residual, out)
     N, K = q.shape[0], q.shape[1] * 2
     if scales.shape != (N, K // 32) or x.shape[1] != K:
         raise ValueError(f"gemv_rows_mxfp4: q {tuple(q.shape)} wants scales ({N}, {K // 32}) and x (R, {K})")
-    return _gemv_rows_mx(lib().aha_hip_gemv_rows_mxfp4, q, K, scales, x, epi, residual)
+    return _gemv_rows_mx(lib().aha_hip_gemv_rows_mxfp4, q, K, scales, x, epi, residual, out)
 
 
 def _gemv_epi_outputs(N: int, epi: int, device, out: Optional[torch.Tensor]):
@@ -498,6 +509,14 @@ def plan_gemv(N: int, K: int, epi: int = GEMV_ROWS_STORE, has_norm: bool = False
     r, u, g, f = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
     check(lib().aha_hip_debug_plan_gemv(N, K, epi, int(has_norm), C.byref(r), C.byref(u), C.byref(g), C.byref(f)))
     return r.value, u.value, g.value, f.value
+
+
+def plan_gemv_rows(N: int, K: int):
+    """Host only: (cw, nks) of gemv_rows and its MX twins for a matrix of N rows and K columns (aha_hip_debug_plan_gemv_rows): chunks per
+    wave and K splits; with the row tiles (2 above 16 rows) the launch is gemv_rows_kernel<cw, 1 | 2>."""
+    cw, nks = C.c_int32(), C.c_int32()
+    check(lib().aha_hip_debug_plan_gemv_rows(N, K, C.byref(cw), C.byref(nks)))
+    return cw.value, nks.value
 
 
 def gemv_partial_f32(W: torch.Tensor, x: torch.Tensor, norm_w: Optional[torch.Tensor] = None, eps: float = 1e-6) -> torch.Tensor:

@@ -870,6 +870,10 @@ int aha_hip_debug_plan_gemv_mxfp4(int32_t N, int32_t K, int32_t epi, int32_t has
  * partial sums of the tensor-parallel row split); epi 2 takes N = 2I for either weight layout, and any even N (aha_hip_gemv_gate_up has
  * no 32-row blocks).  K a multiple of 8, at most 32768. */
 int aha_hip_debug_plan_gemv(int32_t N, int32_t K, int32_t epi, int32_t has_norm, int32_t* R, int32_t* U, int32_t* grid, int32_t* form);
+/* Host only (no GPU): the launch aha_hip_gemv_rows / _mxfp8 / _mxfp4 and the model's multi-sequence matvec pick for a matrix of N rows
+ * and K columns, by the function the launch itself calls: *cw chunks (128 k) per wave, 1 | 2, and *nks K splits (the f32 slabs the merge
+ * sums).  With the row tiles (2 above 16 rows of x) it names gemv_rows_kernel<cw, 1 | 2> and its MX twins.  K a multiple of 8. */
+int aha_hip_debug_plan_gemv_rows(int32_t N, int32_t K, int32_t* cw, int32_t* nks);
 /* Test entry of that epilogue, which only a sharded model's row-parallel projections launch: y_f32[n] = sum_k h[k] * W[n, k], f32, not
  * rounded; h = x, or RMSNorm(x; norm_w, eps) rounded to bf16 when norm_w is not NULL.  W (N, K) bf16, x (K) bf16, device pointers. */
 int aha_hip_debug_gemv_partial_f32(const void* W, const void* x, float* y_f32, int32_t N, int32_t K, const void* norm_w, float eps,

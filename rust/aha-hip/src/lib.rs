@@ -638,6 +638,7 @@ pub mod sys {
             grid: *mut i32,
             form: *mut i32,
         ) -> i32;
+        pub fn aha_hip_debug_plan_gemv_rows(n: i32, k: i32, cw: *mut i32, nks: *mut i32) -> i32;
         pub fn aha_hip_debug_gemv_partial_f32(
             w: *const std::ffi::c_void,
             x: *const std::ffi::c_void,
