@@ -1,4 +1,7 @@
-// Body of the batch-1 weight-streaming matvec (kernels_gemv.hip has the design notes).
+// Body of the batch-1 weight-streaming matvec (kernels_gemv.hip has the design notes), and what its forms share on the host side: the
+// grid and prologue rules and the tail arguments of the kernels that read a weight copy.  The device text of the MXFP8 / MXFP4 and 13-bit
+// forms (gemv_fp8_body.h, gemv_pk13_body.h) is still a copy of this body's, piece by piece: moved into shared function templates it did
+// not compile to the same programs (profiles/gemv_one_body.md).
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -8,6 +11,35 @@ namespace aha {
 
 constexpr int GEMV_THREADS = 256;
 constexpr int GEMV_WAVES = 4;
+
+// ---- host: the rules every form's plan and launch share ----------------------------------------------------------------------------------
+// Whole rounds: with 1024 tiles (N = 4096: o_proj, down_proj) 768 blocks leave a third of them a second tile and the rest idle
+// behind it; the largest grid in [gmax / 2, gmax] that divides the tile count (512 there: two tiles each) measured +1.9 % on the
+// 8B decode step (316.9 -> 323.0 tok/s, same box; 1024 and 1536 blocks: 313.9 / 304.6).  Multiples of 8 only (one share per XCD).
+inline int gemv_whole_rounds_grid(int ntiles, int gmax) {
+  if (ntiles <= gmax) return ntiles;
+  for (int g = gmax; g >= gmax / 2; g -= 8)
+    if (ntiles % g == 0) return g;
+  return gmax;
+}
+
+// PRO, the straight-line prologue (below): the FAST form whose activation vector fits the preloaded vectors, 8 per thread, 4 with norm
+// weights.  0 = the general prologue; 1 / 2 = the straight-line one without / with norm weights.
+inline int gemv_pro_of(int K, bool has_norm, bool fast) {
+  return fast && K <= (has_norm ? 4 : 8) * 8 * GEMV_THREADS ? (has_norm ? 2 : 1) : 0;
+}
+
+// Tail arguments of the kernels that read a weight copy (MXFP8, MXFP4, 13-bit): what is first used behind the first weight request
+// (kernels_gemv.hip has the reasoning).  Their leading dwords are taken by the copy's own pointers, so eps (first used in the prologue)
+// and the grid size (for a block's second tile) travel here; the bf16 kernel has both among its leading parameters and its own tail.
+struct GemvCopyTailArgs {
+  float* y_f32;
+  float* blk_max;
+  uint32_t* blk_idx;
+  void* h_out;
+  float eps;
+  int nblk;
+};
 
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }
 
@@ -19,12 +51,10 @@ __device__ __forceinline__ int xs_index(int k) {
 }
 
 // xs: LDS, (ceil(K/512)*512 + 16) floats.  bid/nblk: this block's index in, and the size of, the persistent grid.
-// after_issue() runs once the block's first weight tile has been requested and before anything that depends on the
-// activation vector -- the stand-alone kernel passes a no-op, the persistent kernel waits on its grid barrier there.
-// PRO (stand-alone FAST kernels only; the host picks it): 1 = no norm weights, K <= 8 * 2048; 2 = with norm weights, K <= 4 * 2048: the
+// PRO (FAST kernels only; the host picks it, gemv_pro_of): 1 = no norm weights, K <= 8 * 2048; 2 = with norm weights, K <= 4 * 2048: the
 // prologue's inputs and the first weight tile are requested in straight-line code (see below).  0 = the general form.
-template <int R, int U, int EPI, bool COH, bool FAST, int PRO = 0, class AfterIssue>
-__device__ __forceinline__ void gemv_body(const GemvArgs& a, float* xs, const int bid, const int nblk, AfterIssue&& after_issue) {
+template <int R, int U, int EPI, bool FAST, int PRO = 0>
+__device__ __forceinline__ void gemv_body(const GemvArgs& a, float* xs, const int bid, const int nblk) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K, N = a.N;
   const int nchunks = (K + 511) >> 9;  // K % 8 == 0; the tail of the last chunk is zero-filled
@@ -111,8 +141,8 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, float* xs, const in
   // of the weight tile, so with norm weights (two requests per vector) half as many: 8 requests either way.  A norm in front of a
   // matvec is over the hidden size: 8192 covers every model this project loads, and a wider one takes the general form.
   constexpr int XSL = SL_NORM ? 4 : XPRE;
-  static_assert(!SL || (FAST && !COH), "the straight-line prologue is a form of the stand-alone FAST kernel");
-  const bool pre = SL || (!COH && (nchunks << 6) <= XPRE * GEMV_THREADS);
+  static_assert(!SL || FAST, "the straight-line prologue is a form of the FAST kernel");
+  const bool pre = SL || (nchunks << 6) <= XPRE * GEMV_THREADS;
   u32x4_t xpre[XPRE], npre[XPRE];
   u32x4_t bufA[U][NW][R], bufB[U][NW][R];
   bf16_t resA[R], resB[R];   // FAST + GEMV_RESIDUAL: the residual values of the buffer's tile, requested with it
@@ -143,7 +173,6 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, float* xs, const in
     if (ngroups > 0) issue(0, bufA, resA);
   }
   stamp(1);
-  after_issue();  // grid barrier of the persistent decode kernel: the first weight tile is already in flight
 
   // ---- prologue: h = x, or h = bf16(RMSNorm(x) * norm_w) (qwen3/model.rs:79,83,186) ------------------------
   {
@@ -169,7 +198,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, float* xs, const in
     } else {
       for (int v = tid; v < (nchunks << 6); v += GEMV_THREADS) {
         u32x4_t xv = {0u, 0u, 0u, 0u};
-        if (v * 8 < K) xv = act_ld16<COH>(x + v * 8);
+        if (v * 8 < K) xv = ld16(x + v * 8);
         stage(v, xv);
       }
     }
@@ -256,16 +285,20 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, float* xs, const in
         const int row = row0 + r;
         if (row < n_out) {
           const float lin = rbf(acc[0][r]);  // candle_nn::Linear output tensor (bf16)
+          // (the stores below form their address first and compute the value second, the order the code objects were tuned with)
           if (EPI == GEMV_PARTIAL_F32) {
             a.y_f32[row] = acc[0][r];
           } else if (EPI == GEMV_STORE) {
-            act_st_bf<COH>((bf16_t*)a.y + row, f2bf(lin));
+            bf16_t* const yp = (bf16_t*)a.y + row;
+            *yp = f2bf(lin);
           } else if (EPI == GEMV_RESIDUAL) {
-            act_st_bf<COH>((bf16_t*)a.y + row, f2bf(bf2f(FAST ? resv[r] : act_ld_bf<COH>((const bf16_t*)a.residual + row)) + lin));
+            bf16_t* const yp = (bf16_t*)a.y + row;
+            *yp = f2bf(bf2f(FAST ? resv[r] : *((const bf16_t*)a.residual + row)) + lin);
           } else if (EPI == GEMV_SILU_MUL) {
             const float g = rbf(silu_f(lin));            // gate_proj -> act_fn   (modules.rs:82)
             const float up = rbf(acc[NW - 1][r]);        // up_proj               (modules.rs:83)
-            act_st_bf<COH>((bf16_t*)a.y + row, f2bf(g * up));  // lhs * rhs             (modules.rs:84)
+            bf16_t* const yp = (bf16_t*)a.y + row;
+            *yp = f2bf(g * up);                          // lhs * rhs             (modules.rs:84)
           } else {  // GEMV_LOGITS: logits tensor is bf16 in the reference, read back as f32 (generate.rs:75)
             a.y_f32[row] = lin;
             if (lin > tile_best || (lin == tile_best && (uint32_t)row < tile_best_i)) { tile_best = lin; tile_best_i = row; }

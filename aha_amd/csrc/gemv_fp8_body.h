@@ -4,7 +4,7 @@
 // epilogues' rounding points are gemv_body's, so that every output bit equals gemv_kernel on W' = q * 2^e.  One text for both formats: the
 // weight form WF (below) names what differs, a lane's load and its conversion.
 #pragma once
-#include "gemv_body.h"   // xs_index, silu_f, GEMV_THREADS, GEMV_WAVES
+#include "gemv_body.h"   // xs_index, silu_f, GEMV_THREADS, GEMV_WAVES; the host rules and GemvCopyTailArgs
 
 namespace aha {
 
@@ -46,24 +46,11 @@ struct GemvWFp4 {   // 8 E2M1 codes in 4 bytes, the even k of a byte in bits 0..
   }
 };
 
-struct GemvFp8Args {
-  const void* q;          // (N, K) E4M3 bytes or (N, K / 2) E2M1 pairs, row-major; GEMV_SILU_MUL: the fused matrix, 16-row blocks alternating gate / up (2N rows)
-  const uint8_t* scales;  // the scale words of kernels.h "MXFP8 weight copies" as bytes: byte k / 32 of a row of 4 * ceil(K / 128)
-  const void* x;          // (K) bf16
-  const void* norm_w;     // optional (K) bf16
-  const void* residual;   // GEMV_RESIDUAL: (N) bf16, may alias y
-  void* y;
-  float* y_f32;           // GEMV_LOGITS
-  float* blk_max;         // GEMV_LOGITS: one (max, index) partial per block of the grid
-  uint32_t* blk_idx;
-  void* h_out;
-  int N, K;               // N: output rows (GEMV_SILU_MUL: I)
-  float eps;
-};
-
+// a.W: (N, K) E4M3 bytes or (N, K / 2) E2M1 pairs, row-major; GEMV_SILU_MUL: the fused matrix, 16-row blocks alternating gate / up (2N rows);
+// a.scales: their scale bytes (GemvArgs, kernels.h).
 // xs: LDS, (ceil(K/512)*512 + 16) floats.  PRO as in gemv_body: 1 / 2 = the straight-line prologue without / with norm weights (FAST only).
 template <class WF, int R, int U, int EPI, bool FAST, int PRO>
-__device__ __forceinline__ void gemv_fp8_body(const GemvFp8Args& a, float* xs, const int bid, const int nblk) {
+__device__ __forceinline__ void gemv_fp8_body(const GemvArgs& a, float* xs, const int bid, const int nblk) {
   const int tid = threadIdx.x, lane = tid & 63;
   // wave-uniform on purpose: a wave's row pointers then live in SGPRs and every weight / scale load is the scalar-base form with the lane's
   // byte offset in one VGPR, instead of a 64-bit address pair per load
@@ -79,7 +66,7 @@ __device__ __forceinline__ void gemv_fp8_body(const GemvFp8Args& a, float* xs, c
   const int gpt = (nchunks + U - 1) / U;
   const int my_tiles = (ntiles - bid + nblk - 1) / nblk;
   const int ngroups = my_tiles * gpt;
-  const uint8_t* Q = (const uint8_t*)a.q;
+  const uint8_t* Q = (const uint8_t*)a.W;
   const uint8_t* S = a.scales;
   const size_t srow = (size_t)((K + 127) >> 7) << 2;   // scale bytes per row
   typedef typename WF::load_t load_t;

@@ -13,17 +13,8 @@ namespace aha {
 
 namespace {
 
-// What is first used behind the first weight request travels here (kernels_gemv.hip has the reasoning): the 14 leading dwords are q, scales,
-// x, norm_w, y, the residual vector, N and K; eps is first used in the prologue and the grid size for a block's second tile.
-struct GemvFp8TailArgs {
-  float* y_f32;
-  float* blk_max;
-  uint32_t* blk_idx;
-  void* h_out;
-  float eps;
-  int nblk;
-};
-
+// The kernels' parameters (kernels_gemv.hip has the reasoning): the 14 leading dwords are q, scales, x, norm_w, y, the residual vector, N and
+// K; what is first used behind the first weight request travels in GemvCopyTailArgs (gemv_body.h).
 struct GemvFp8Plan { int R, U, grid; };
 
 // N: output rows (GEMV_SILU_MUL: I).  Rows per wave so that there are at least 512 tiles (two per CU), then as many chunks per item as
@@ -41,22 +32,14 @@ GemvFp8Plan plan_gemv_mx(int N, int K, GemvEpi epi, int loads) {
   // with two buffers of 16 half-KiB requests each is the bytes in flight of the bf16 kernel's 8-load plans)
   const int gmax = 768;
   const int ntiles = (N + 4 * R - 1) / (4 * R);
-  int grid = std::min(ntiles, gmax);
-  // whole rounds, as plan_gemv: the largest grid in [gmax / 2, gmax] that divides the tile count, multiples of 8 only
-  if (ntiles > gmax) {
-    for (int g = gmax; g >= gmax / 2; g -= 8)
-      if (ntiles % g == 0) {
-        grid = g;
-        break;
-      }
-  }
+  const int grid = gemv_whole_rounds_grid(ntiles, gmax);   // whole rounds, as plan_gemv
   return {R, Up, std::max(grid, 1)};
 }
 
 // the forms a launch takes for a shape: FAST = every chunk group full; PRO = the straight-line prologue
 void form_of(const GemvFp8Plan& p, int K, bool has_norm, bool* fast, int* pro) {
   *fast = K % (512 * p.U) == 0;
-  *pro = *fast && K <= (has_norm ? 4 : 8) * 8 * GEMV_THREADS ? (has_norm ? 2 : 1) : 0;
+  *pro = gemv_pro_of(K, has_norm, *fast);
 }
 
 void debug_plan_out(const GemvFp8Plan& p, int K, bool has_norm, int* out5) {
@@ -67,15 +50,15 @@ void debug_plan_out(const GemvFp8Plan& p, int K, bool has_norm, int* out5) {
 }
 
 template <class KS, int EPI>
-void launch_mx_epi(const GemvFp8Args& a, const GemvFp8Plan& p, hipStream_t st) {
+void launch_mx_epi(const GemvArgs& a, const GemvFp8Plan& p, hipStream_t st) {
   const size_t lds = (size_t)((a.K + 511) / 512) * 512 * 4 + 64;
   dim3 grid(p.grid), block(GEMV_THREADS);
   bool fast;
   int pro;
   form_of(p, a.K, a.norm_w != nullptr, &fast, &pro);
-  const GemvFp8TailArgs t{a.y_f32, a.blk_max, a.blk_idx, a.h_out, a.eps, p.grid};
+  const GemvCopyTailArgs t{a.y_f32, a.blk_max, a.blk_idx, a.h_out, a.eps, p.grid};
 #define GV_(RR, UU, FF, PP) \
-  hipLaunchKernelGGL((KS::template get<RR, UU, EPI, FF, PP>()), grid, block, lds, st, a.q, a.scales, a.x, a.norm_w, a.y, a.residual, a.N, a.K, t)
+  hipLaunchKernelGGL((KS::template get<RR, UU, EPI, FF, PP>()), grid, block, lds, st, a.W, a.scales, a.x, a.norm_w, a.y, a.residual, a.N, a.K, t)
   // U at the plan's cap (the row has at least 2 * U chunks or exactly U): every form
 #define GV_FULL(RR, UU)                                                                 \
   do {                                                                                  \
@@ -110,9 +93,8 @@ void launch_mx_epi(const GemvFp8Args& a, const GemvFp8Plan& p, hipStream_t st) {
 // launch_gemv with (q, scales) in place of g.W, by plan p
 template <class KS>
 void launch_mx(const GemvArgs& g, const void* q, const uint32_t* scales, GemvEpi epi, const GemvFp8Plan& p, hipStream_t st) {
-  GemvFp8Args a{};
-  a.q = q; a.scales = (const uint8_t*)scales; a.x = g.x; a.norm_w = g.norm_w; a.residual = g.residual; a.y = g.y; a.y_f32 = g.y_f32;
-  a.blk_max = g.blk_max; a.blk_idx = g.blk_idx; a.h_out = g.h_out; a.N = g.N; a.K = g.K; a.eps = g.eps;
+  GemvArgs a = g;
+  a.W = q; a.scales = (const uint8_t*)scales;
   switch (epi) {
     case GEMV_STORE: launch_mx_epi<KS, GEMV_STORE>(a, p, st); break;
     case GEMV_RESIDUAL: launch_mx_epi<KS, GEMV_RESIDUAL>(a, p, st); break;

@@ -3,7 +3,7 @@
 // two register buffers, the fma order and the epilogues' rounding points are gemv_body's, and every f32 operand is rebuilt to the bits
 // lo_bf / hi_bf give on W, so that every output bit equals gemv_kernel on W.
 #pragma once
-#include "gemv_body.h"   // xs_index, silu_f, GEMV_THREADS, GEMV_WAVES
+#include "gemv_body.h"   // xs_index, silu_f, GEMV_THREADS, GEMV_WAVES; the host rules and GemvCopyTailArgs
 
 namespace aha {
 
@@ -38,20 +38,8 @@ __device__ __forceinline__ float pk13_f32(uint32_t hb, uint32_t lo) {
   return __uint_as_float(__builtin_amdgcn_perm(hb, lo, 0x04000c0cu + 0x01010000u * E));
 }
 
-struct GemvPk13Args {
-  const void* p;          // the copy: rows in the order of W, (K / 4096) units of PK13_UNIT_BYTES per row; GEMV_SILU_MUL: the fused matrix (2N rows)
-  const void* x;          // (K) bf16
-  const void* norm_w;     // optional (K) bf16
-  const void* residual;   // GEMV_RESIDUAL: (N) bf16, may alias y
-  void* y;
-  float* y_f32;           // GEMV_LOGITS
-  float* blk_max;         // GEMV_LOGITS: one (max, index) partial per block of the grid
-  uint32_t* blk_idx;
-  void* h_out;
-  int N, K;               // N: output rows (GEMV_SILU_MUL: I); K % 4096 == 0
-  int bh;                 // the matrix's exponent base: code h != 0 is E >> 1 == bh + h
-  float eps;
-};
+// a.W: the copy: rows in the order of W, (K / 4096) units of PK13_UNIT_BYTES per row; GEMV_SILU_MUL: the fused matrix (2N rows); a.bh: the
+// matrix's exponent base (GemvArgs, kernels.h); K % 4096 == 0.
 
 // Exception rows (the twin kernel, EXC): rows of W that hold a finite weight below the matrix's window.  The copy has an arbitrary code at
 // such a weight, so the wave that owns such a row runs the bf16 kernel's chain over the row of W itself, in front of its main loop, and at
@@ -65,7 +53,7 @@ struct Pk13ExcRows {
 // xs: LDS, (K + 16) floats (EXC: K + 32).  PRO as in gemv_body: 1 / 2 = the straight-line prologue without / with norm weights, 0 = the
 // general one.  Always the FAST form: a work item is one unit of each of the wave's R (x 2 for gate / up) rows, nothing is predicated.
 template <int R, int EPI, int PRO, bool EXC = false>
-__device__ __forceinline__ void gemv_pk13_body(const GemvPk13Args& a, float* xs, const int bid, const int nblk, const Pk13ExcRows& ex = Pk13ExcRows{}) {
+__device__ __forceinline__ void gemv_pk13_body(const GemvArgs& a, float* xs, const int bid, const int nblk, const Pk13ExcRows& ex = Pk13ExcRows{}) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: the row pointers live in SGPRs
   const int K = a.K, N = a.N;
@@ -79,7 +67,7 @@ __device__ __forceinline__ void gemv_pk13_body(const GemvPk13Args& a, float* xs,
   const int gpt = K >> 12;                                  // units per row = work items per tile
   const int my_tiles = (ntiles - bid + nblk - 1) / nblk;
   const int ngroups = my_tiles * gpt;
-  const uint8_t* P = (const uint8_t*)a.p;
+  const uint8_t* P = (const uint8_t*)a.W;
   const size_t prow = (size_t)gpt * PK13_UNIT_BYTES;        // bytes per row
   const pk13_u16x2_t bh2 = {(uint16_t)a.bh, (uint16_t)a.bh};
 

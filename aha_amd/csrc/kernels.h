@@ -38,6 +38,9 @@ struct GemvArgs {
   int cached;            // 0 (default): non-temporal weight loads (streamed once); 1: default cache policy
   unsigned long long* trace;  // optional (AHA_GEMV_TRACE): 100 MHz stamps of blocks 0 / 255 / last: start, issued, prologue done,
                               // first group consumed, last group consumed, end
+  // the weight copies' launches (launch_gemv_mxfp8 / _mxfp4 / _pk13) fill these in, with W = the copy; callers leave them alone
+  const uint8_t* scales;  // MXFP8 / MXFP4: the scale words of "MXFP8 weight copies" as bytes: byte k / 32 of a row of 4 * ceil(K / 128)
+  int bh;                 // 13-bit copy: the matrix's exponent base: code h != 0 is E >> 1 == bh + h
 };
 void launch_gemv(const GemvArgs& a, GemvEpi epi, hipStream_t st);
 int gemv_num_tiles(int N, int K);  // number of (max,idx) partials GEMV_LOGITS writes

@@ -40,11 +40,11 @@ template <int R, int U, int EPI, bool FAST, bool TRACE, int PRO>
 __global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel(const void* W, const void* x, const void* norm_w, void* y, const void* aux, int N,
                                                             int K, float eps, int nblk, GemvTailArgs t) {
   extern __shared__ __attribute__((aligned(16))) float xs[];  // K f32 + 8 floats reduction scratch
-  GemvArgs a;
+  GemvArgs a{};
   a.W = W; a.W2 = EPI == GEMV_SILU_MUL ? aux : nullptr; a.x = x; a.norm_w = norm_w; a.residual = EPI == GEMV_SILU_MUL ? nullptr : aux; a.y = y;
   a.y_f32 = t.y_f32; a.blk_max = t.blk_max; a.blk_idx = t.blk_idx; a.h_out = t.h_out; a.N = N; a.K = K; a.eps = eps; a.cached = t.cached;
   a.trace = TRACE ? t.trace : nullptr;
-  gemv_body<R, U, EPI, false, FAST, PRO>(a, xs, (int)blockIdx.x, nblk, [] {});
+  gemv_body<R, U, EPI, FAST, PRO>(a, xs, (int)blockIdx.x, nblk);
 }
 
 struct GemvPlan { int R, U, grid; };
@@ -85,18 +85,10 @@ GemvPlan plan_gemv(int N, int K, GemvEpi epi) {
     Up = q;
   }
   const int ntiles = (N + 4 * R - 1) / (4 * R);
-  int grid = ntiles < gmax ? ntiles : gmax;
-  // Whole rounds: with 1024 tiles (N = 4096: o_proj, down_proj) 768 blocks leave a third of them a second tile and the rest idle
-  // behind it; the largest grid in [gmax / 2, gmax] that divides the tile count (512 there: two tiles each) measured +1.9 % on the
-  // 8B decode step (316.9 -> 323.0 tok/s, same box; 1024 and 1536 blocks: 313.9 / 304.6).  Multiples of 8 only (one share per XCD).
+  // whole rounds (gemv_body.h) unless a knob says otherwise
   static const bool even_on = [] { const char* e = getenv("AHA_GEMV_EVEN_GRID"); return e ? atoi(e) != 0 : true; }();
-  if (even_on && !e_grid && !(e_grid1 && R == 1) && ntiles > gmax) {
-    for (int g = gmax; g >= gmax / 2; g -= 8)
-      if (ntiles % g == 0) {
-        grid = g;
-        break;
-      }
-  }
+  const bool even = even_on && !e_grid && !(e_grid1 && R == 1);
+  const int grid = even ? gemv_whole_rounds_grid(ntiles, gmax) : ntiles < gmax ? ntiles : gmax;
   return {R, Up, grid};
 }
 
@@ -107,13 +99,11 @@ int cached_or_env(int cached) {
 }
 
 // The forms a launch takes for a shape, for launch_gemv_epi and debug_plan_gemv alike.
-// FAST (gemv_body.h): every chunk group full and in range, weights non-temporal.
-// PRO, the straight-line prologue (gemv_body.h): the FAST form whose activation vector fits the preloaded vectors, 8 per thread, 4 with
-// norm weights.
+// FAST (gemv_body.h): every chunk group full and in range, weights non-temporal.  PRO: gemv_pro_of.
 void form_of(const GemvPlan& p, int N, int K, bool has_norm, int cached, bool* fast, int* pro) {
   static const bool fast_ok = [] { const char* e = getenv("AHA_GEMV_FAST"); return e ? atoi(e) != 0 : true; }();
   *fast = fast_ok && K % (512 * p.U) == 0 && !cached && N >= 1;
-  *pro = *fast && K <= (has_norm ? 4 : 8) * 8 * GEMV_THREADS ? (has_norm ? 2 : 1) : 0;
+  *pro = gemv_pro_of(K, has_norm, *fast);
 }
 
 }  // namespace

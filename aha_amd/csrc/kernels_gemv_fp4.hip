@@ -19,10 +19,10 @@ namespace {
 
 template <int R, int U, int EPI, bool FAST, int PRO>
 __global__ __launch_bounds__(GEMV_THREADS) void gemv_mxfp4_kernel(const void* q, const uint8_t* scales, const void* x, const void* norm_w, void* y,
-                                                                  const void* residual, int N, int K, GemvFp8TailArgs t) {
+                                                                  const void* residual, int N, int K, GemvCopyTailArgs t) {
   extern __shared__ __attribute__((aligned(16))) float xs[];  // K f32 + 8 floats reduction scratch
-  GemvFp8Args a;
-  a.q = q; a.scales = scales; a.x = x; a.norm_w = norm_w; a.residual = residual; a.y = y;
+  GemvArgs a{};
+  a.W = q; a.scales = scales; a.x = x; a.norm_w = norm_w; a.residual = residual; a.y = y;
   a.y_f32 = t.y_f32; a.blk_max = t.blk_max; a.blk_idx = t.blk_idx; a.h_out = t.h_out; a.N = N; a.K = K; a.eps = t.eps;
   gemv_fp8_body<GemvWFp4, R, U, EPI, FAST, PRO>(a, xs, (int)blockIdx.x, t.nblk);
 }

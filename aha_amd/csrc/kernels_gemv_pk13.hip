@@ -29,22 +29,12 @@ namespace aha {
 
 namespace {
 
-// as GemvFp8TailArgs: what is first used behind the first weight request
-struct GemvPk13TailArgs {
-  float* y_f32;
-  float* blk_max;
-  uint32_t* blk_idx;
-  void* h_out;
-  float eps;
-  int nblk;
-};
-
 template <int R, int EPI, int PRO>
 __global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel_pk13(const void* p, const void* x, const void* norm_w, void* y, const void* residual,
-                                                                 int N, int K, int bh, GemvPk13TailArgs t) {
+                                                                 int N, int K, int bh, GemvCopyTailArgs t) {
   extern __shared__ __attribute__((aligned(16))) float xs[];  // K f32 + 8 floats reduction scratch
-  GemvPk13Args a;
-  a.p = p; a.x = x; a.norm_w = norm_w; a.residual = residual; a.y = y;
+  GemvArgs a{};
+  a.W = p; a.x = x; a.norm_w = norm_w; a.residual = residual; a.y = y;
   a.y_f32 = t.y_f32; a.blk_max = t.blk_max; a.blk_idx = t.blk_idx; a.h_out = t.h_out; a.N = N; a.K = K; a.bh = bh; a.eps = t.eps;
   gemv_pk13_body<R, EPI, PRO>(a, xs, (int)blockIdx.x, t.nblk);
 }
@@ -54,10 +44,10 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel_pk13(const void* p, 
 // stays in SGPRs.  Its LDS has 16 more floats: the sums of the exception rows, one per list entry.
 template <int R, int EPI, int PRO>
 __global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel_rows_pk13(const void* p, const void* x, const void* norm_w, void* y, const void* residual,
-                                                                      int N, int K, int bh, GemvPk13TailArgs t, Pk13ExcRows ex) {
+                                                                      int N, int K, int bh, GemvCopyTailArgs t, Pk13ExcRows ex) {
   extern __shared__ __attribute__((aligned(16))) float xs[];  // K f32 + 8 floats reduction scratch, PK13_MAX_EXC floats at + 16
-  GemvPk13Args a;
-  a.p = p; a.x = x; a.norm_w = norm_w; a.residual = residual; a.y = y;
+  GemvArgs a{};
+  a.W = p; a.x = x; a.norm_w = norm_w; a.residual = residual; a.y = y;
   a.y_f32 = t.y_f32; a.blk_max = t.blk_max; a.blk_idx = t.blk_idx; a.h_out = t.h_out; a.N = N; a.K = K; a.bh = bh; a.eps = t.eps;
   gemv_pk13_body<R, EPI, PRO, true>(a, xs, (int)blockIdx.x, t.nblk, ex);
 }
@@ -68,33 +58,23 @@ GemvPk13Plan plan_gemv_pk13(int N, GemvEpi epi) {
   const int R = epi == GEMV_LOGITS ? 2 : 1;
   const int gmax = 768;
   const int ntiles = (N + 4 * R - 1) / (4 * R);
-  int grid = std::min(ntiles, gmax);
-  // whole rounds, as plan_gemv: the largest grid in [gmax / 2, gmax] that divides the tile count, multiples of 8 only
-  if (ntiles > gmax) {
-    for (int g = gmax; g >= gmax / 2; g -= 8)
-      if (ntiles % g == 0) {
-        grid = g;
-        break;
-      }
-  }
+  const int grid = gemv_whole_rounds_grid(ntiles, gmax);   // whole rounds, as plan_gemv
   return {R, std::max(grid, 1)};
 }
 
-int pro_of(int K, bool has_norm) { return K <= (has_norm ? 4 : 8) * 8 * GEMV_THREADS ? (has_norm ? 2 : 1) : 0; }
-
 template <int R, int EPI>
-void launch_pk13_epi(const GemvPk13Args& a, const GemvPk13Plan& p, const Pk13ExcRows& ex, hipStream_t st) {
+void launch_pk13_epi(const GemvArgs& a, const GemvPk13Plan& p, const Pk13ExcRows& ex, hipStream_t st) {
   const size_t lds = (size_t)a.K * 4 + 64;
   dim3 grid(p.grid), block(GEMV_THREADS);
-  const GemvPk13TailArgs t{a.y_f32, a.blk_max, a.blk_idx, a.h_out, a.eps, p.grid};
-  const int pro = pro_of(a.K, a.norm_w != nullptr);
+  const GemvCopyTailArgs t{a.y_f32, a.blk_max, a.blk_idx, a.h_out, a.eps, p.grid};
+  const int pro = gemv_pro_of(a.K, a.norm_w != nullptr, true);   // always the FAST form
   if (ex.n > 0) {   // the plan is the plain kernel's
-#define GV_(PP) hipLaunchKernelGGL((gemv_kernel_rows_pk13<R, EPI, PP>), grid, block, lds + PK13_MAX_EXC * 4, st, a.p, a.x, a.norm_w, a.y, a.residual, a.N, a.K, a.bh, t, ex)
+#define GV_(PP) hipLaunchKernelGGL((gemv_kernel_rows_pk13<R, EPI, PP>), grid, block, lds + PK13_MAX_EXC * 4, st, a.W, a.x, a.norm_w, a.y, a.residual, a.N, a.K, a.bh, t, ex)
     if (pro == 2) GV_(2); else if (pro == 1) GV_(1); else GV_(0);
 #undef GV_
     return;
   }
-#define GV_(PP) hipLaunchKernelGGL((gemv_kernel_pk13<R, EPI, PP>), grid, block, lds, st, a.p, a.x, a.norm_w, a.y, a.residual, a.N, a.K, a.bh, t)
+#define GV_(PP) hipLaunchKernelGGL((gemv_kernel_pk13<R, EPI, PP>), grid, block, lds, st, a.W, a.x, a.norm_w, a.y, a.residual, a.N, a.K, a.bh, t)
   if (pro == 2) GV_(2); else if (pro == 1) GV_(1); else GV_(0);
 #undef GV_
 }
@@ -238,7 +218,7 @@ int gemv_pk13_num_tiles(int N, int K) { (void)K; return plan_gemv_pk13(N, GEMV_L
 
 void debug_plan_gemv_pk13(int N, int K, GemvEpi epi, bool has_norm, int* out5) {
   const GemvPk13Plan p = plan_gemv_pk13(N, epi);
-  out5[0] = p.R; out5[1] = 8; out5[2] = p.grid; out5[3] = 1; out5[4] = pro_of(K, has_norm);
+  out5[0] = p.R; out5[1] = 8; out5[2] = p.grid; out5[3] = 1; out5[4] = gemv_pro_of(K, has_norm, true);
 }
 
 void launch_gemv_pk13(const GemvArgs& g, const void* packed, int bh, const int* rows, int nrows, GemvEpi epi, hipStream_t st) {
@@ -252,9 +232,8 @@ void launch_gemv_pk13(const GemvArgs& g, const void* packed, int bh, const int* 
     ex.row[i] = i < nrows ? rows[i] : -1;
     if (i < nrows && (rows[i] < 0 || rows[i] >= mat_rows)) abort();   // the kernel reads row rows[i] of W
   }
-  GemvPk13Args a{};
-  a.p = packed; a.x = g.x; a.norm_w = g.norm_w; a.residual = g.residual; a.y = g.y; a.y_f32 = g.y_f32;
-  a.blk_max = g.blk_max; a.blk_idx = g.blk_idx; a.h_out = g.h_out; a.N = g.N; a.K = g.K; a.bh = bh; a.eps = g.eps;
+  GemvArgs a = g;
+  a.W = packed; a.bh = bh;
   const GemvPk13Plan p = plan_gemv_pk13(g.N, epi);
   switch (epi) {
     case GEMV_STORE: launch_pk13_epi<1, GEMV_STORE>(a, p, ex, st); break;
