@@ -58,6 +58,11 @@ class TokenLogprobs(C.Structure):
                 ("top_logprobs", C.c_float * AHA_MAX_TOP_LOGPROBS)]
 
 
+class TokenScore(C.Structure):
+    """aha_token_score (include/aha_hip.h); the Rust shim's AhaTokenScore has the same fields in the same order."""
+    _fields_ = [("logprob", C.c_float), ("top_id", C.c_uint32), ("top_logprob", C.c_float)]
+
+
 AHA_MAX_LOGIT_BIAS = 1024
 
 
@@ -249,6 +254,8 @@ SIGNATURES = {
     "aha_hip_sample_rows_masked": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "aha_hip_sampler_set_mask": (C.c_int, [_P, _P, C.c_size_t]),
     "aha_hip_logprob_rows": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "aha_hip_score_rows": (C.c_int, [_P, C.c_int64, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P, _P, _P]),
+    "aha_hip_score_batch": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, C.POINTER(TokenScore)]),
     "aha_hip_sample_rows": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "aha_hip_sampler_create": (C.c_int, [C.POINTER(SamplingParams), _P]),
     "aha_hip_sampler_destroy": (None, [_P]),

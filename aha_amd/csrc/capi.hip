@@ -1617,6 +1617,30 @@ int aha_hip_logprob_rows(const float* logits, int64_t ld, int32_t R, int32_t V, 
   API_GUARD_END
 }
 
+int aha_hip_score_rows(const void* h, int64_t ldh, size_t rows, const void* W, size_t V, size_t K, const int32_t* targets,
+                       aha_token_score* out, void* stream) {
+  API_GUARD_BEGIN
+  if (!h || !W || !targets || !out || rows < 1 || V < 1 || K < 1 || ldh < (int64_t)K || rows >= (size_t)1 << 30 || V >= (size_t)1 << 30 ||
+      K >= (size_t)1 << 30) {
+    set_error("score_rows: bad arguments (rows >= 1, V >= 1, ldh >= K >= 1, h / W / targets / out)");
+    return AHA_ERR_INVALID;
+  }
+  if (!score_rows_shape_ok((int64_t)rows, (int)V, (int)K)) {
+    set_error("score_rows: K must be a multiple of 64");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  void* ws = nullptr;
+  AHA_HIP_CHECK(hipMalloc(&ws, score_rows_ws_bytes((int64_t)rows, (int)V, (int)K)));
+  launch_score_rows(h, ldh, (int64_t)rows, W, (int)V, (int)K, targets, ws, out, st);
+  hipError_t err = hipGetLastError();
+  hipStreamSynchronize(st);
+  hipFree(ws);
+  AHA_HIP_CHECK(err);
+  return AHA_OK;
+  API_GUARD_END
+}
+
 static bool attn_batch_geometry_ok(int32_t nh, int32_t kvh) { return nh > 0 && kvh > 0 && nh % kvh == 0 && nh / kvh <= 16 && kvh <= 64; }
 
 // The row table of an op-level decode attention call: splits from the row's own length, counters from zero, one counter block per row.
@@ -1964,6 +1988,17 @@ int aha_hip_embed_batch(aha_model* m, const uint32_t* input_ids, const size_t* s
   }
   if (int rc = engine_owns_cache(m, "embed_batch")) return rc;
   return model_embed_batch(m, input_ids, seq_lens, n_seqs, max_tokens_per_pass, out);
+  API_GUARD_END
+}
+int aha_hip_score_batch(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_tokens_per_pass,
+                        aha_token_score* scores_out) {
+  API_GUARD_BEGIN
+  if (!m) {
+    set_error("null model");
+    return AHA_ERR_INVALID;
+  }
+  if (int rc = engine_owns_cache(m, "score_batch")) return rc;
+  return model_score_batch(m, input_ids, seq_lens, n_seqs, max_tokens_per_pass, scores_out);
   API_GUARD_END
 }
 // The device-free checks of the aha_hip_generate_batch* entries, in their fixed order: the sampling parameters, the top_logprobs /

@@ -95,6 +95,21 @@ bool logprob_shape_ok(int V);
 void launch_logprob_rows(const float* logits, int64_t ld, int V, int rows, const int32_t* tab, const uint32_t* tokens, float* cand_val,
                          unsigned* cand_idx, float* part_m, float* part_s, const float* sample_out, float* out, int stage, hipStream_t st);
 
+// Log-probabilities of given tokens without the logits (kernels_score.hip): for each of R rows of h (bf16, row pitch ldh) against the (V, K)
+// bf16 matrix W, x = the bf16-rounded f32 dot products read as f32, M = max x, S = sum exp(x - M) -> out[r] = an aha_token_score
+// {(x[targets[r]] - M) - log S (0 for a target of -1), the first index with x = M, -log S}.  Two launches: score_rows_kernel over
+// plan.row_blocks x plan.slices workgroups (128 rows x a contiguous run of plan.tiles_per_slice 128-column tiles each: the slices fill the
+// CUs when there is one row block and fall to 1 as row blocks multiply) writes five f32 words per (row, slice) into ws
+// (score_rows_ws_bytes), score_rows_merge_kernel merges a row's partials in slice order.  The same inputs give the same bits.
+struct ScorePlan {
+  int row_blocks, slices, tiles_per_slice;
+};
+ScorePlan plan_score_rows(int64_t R, int V, int K);
+bool score_rows_shape_ok(int64_t R, int V, int K);   // K a multiple of 64, R >= 1, V >= 1
+size_t score_rows_ws_bytes(int64_t R, int V, int K);
+void launch_score_rows(const void* h, int64_t ldh, int64_t R, const void* W, int V, int K, const int32_t* targets, void* ws, void* out,
+                       hipStream_t st);
+
 void launch_embed_gather(const void* table, const uint32_t* ids, void* out, int S, int H, hipStream_t st);
 void launch_rmsnorm_rows(const void* x, const void* w, void* y, int64_t rows, int dim, int64_t ldx, int64_t ldy,
                          float eps, hipStream_t st);

@@ -219,6 +219,13 @@ struct aha_model {
   size_t h_pass_stage_cap = 0;
   float* p_pool = nullptr;   // model_embed_batch: a pass's (sequences, hidden) f32 embeddings
   size_t p_pool_cap = 0;
+  // model_score_batch: a pass's normed rows (S, hidden) bf16; its targets | scores | kernel partials as words; the pinned targets | scores
+  uint16_t* p_score_h = nullptr;
+  size_t p_score_h_cap = 0;
+  int32_t* p_score_ws = nullptr;
+  size_t p_score_ws_cap = 0;
+  int32_t* h_score = nullptr;
+  size_t h_score_cap = 0;
   // the continuous batching engine that owns the cache while it exists (model.hip engine_*): every other entry that touches the cache
   // returns AHA_ERR_STATE meanwhile (capi.hip)
   aha_engine* engine = nullptr;
@@ -242,6 +249,8 @@ int model_create(aha_ctx* ctx, const aha_model_desc* desc, const aha_tensor_view
 void model_destroy(aha_model* m);
 int model_embed(aha_model* m, const uint32_t* ids, size_t n, float* out);
 int model_embed_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_tokens_per_pass, float* out);
+int model_score_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_tokens_per_pass,
+                      aha_token_score* out);
 // What a batch generation call may carry beyond ids, lens, max_new, the pass budget, tokens_out and n_out: every field absent by default.
 // A new per-request option is a field here, a check in capi.hip's gen_options_check and its use in model_generate_batch.
 struct GenOptions {

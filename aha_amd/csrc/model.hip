@@ -1027,6 +1027,9 @@ void model_destroy(aha_model* m) {
   for (void* p : m->pf_owned) hipFree(p);
   if (m->p_pass_tab) hipFree(m->p_pass_tab);
   if (m->p_pool) hipFree(m->p_pool);
+  if (m->p_score_h) hipFree(m->p_score_h);
+  if (m->p_score_ws) hipFree(m->p_score_ws);
+  if (m->h_score) hipHostFree(m->h_score);
   if (m->h_pass_stage) hipHostFree(m->h_pass_stage);
   for (void* p : m->slabs) hipFree(p);
   if (m->d_page_ptrs) hipFree(m->d_page_ptrs);
@@ -2565,6 +2568,77 @@ int model_embed_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens,
   ClearCacheGuard guard{m};
   for (const PassRange& p : split_passes(seq_lens, n_seqs, max_tokens_per_pass))
     if ((rc = embed_pass(m, ids + p.off, seq_lens + p.j, (int)(p.k - p.j), out + p.j * c.hidden_size))) return rc;
+  return AHA_OK;
+}
+
+// ---- log-probabilities of given tokens (aha_hip_score_batch) ------------------------------------------------------------------------
+// A packed pass as embed_pass runs it, then ALL its rows through the final norm and the fused lm_head + log-softmax kernel
+// (kernels_score.hip): row r of a segment is scored against the segment's next id, the segment's last row against nothing.  The logits never
+// exist; the pass ends in one copy of 12 bytes per row and one synchronise, and the host moves each row's result to its target's position.
+static int score_pass(aha_model* m, const uint32_t* ids, const size_t* lens, int n_seg, aha_token_score* out) {
+  const aha_model_desc& c = m->desc;
+  const int H = c.hidden_size, V = c.vocab_size;
+  hipStream_t st = m->stream;
+  std::vector<int64_t> page0(n_seg);
+  for (int j = 0, p = 0; j < n_seg; p += (int)((lens[j] + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS), ++j) page0[j] = p;
+  const PackedPass pp = plan_packed_pass(lens, n_seg, page0.data(), nullptr);
+  const size_t S = (size_t)pp.S, ws_words = score_rows_ws_bytes(pp.S, V, H) / 4;
+  int rc;
+  // device words: targets (S) | scores (3 S) | the kernel's partials; pinned words: targets (S) | scores (3 S)
+  if ((rc = model_ensure_pages(m, (size_t)pp.npages * KV_PAGE_TOKENS)) ||
+      (rc = grow_pass_buffer(m, &m->p_score_h, &m->p_score_h_cap, S * H, false)) ||
+      (rc = grow_pass_buffer(m, &m->p_score_ws, &m->p_score_ws_cap, 4 * S + ws_words, false)) ||
+      (rc = grow_pass_buffer(m, &m->h_score, &m->h_score_cap, 4 * S, true)) || (rc = run_packed_pass(m, pp, ids, m->d_page_ptrs)))
+    return rc;
+  int32_t* tg = m->h_score;
+  for (size_t j = 0, r = 0; j < (size_t)n_seg; ++j)
+    for (size_t i = 0; i < lens[j]; ++i, ++r) tg[r] = i + 1 < lens[j] ? (int32_t)ids[r + 1] : -1;
+  int32_t* d_tg = m->p_score_ws;
+  int32_t* d_out = d_tg + S;
+  AHA_HIP_CHECK(hipMemcpyAsync(d_tg, tg, S * 4, hipMemcpyHostToDevice, st));
+  {
+    ProfScope ps(m, "elem", (double)S * H * 4, 0);
+    launch_rmsnorm_rows(m->p_x, m->final_norm, m->p_score_h, pp.S, H, H, H, c.rms_norm_eps, st);
+  }
+  {
+    ProfScope ps(m, "score_rows", (double)V * H * 2 + (double)S * H * 2, 2.0 * S * V * H);
+    launch_score_rows(m->p_score_h, H, pp.S, m->lm_head, V, H, d_tg, d_out + 3 * S, d_out, st);
+  }
+  AHA_HIP_CHECK(hipGetLastError());
+  AHA_HIP_CHECK(hipMemcpyAsync(m->h_score + S, d_out, 3 * S * 4, hipMemcpyDeviceToHost, st));
+  AHA_HIP_CHECK(hipStreamSynchronize(st));
+  const aha_token_score* got = reinterpret_cast<const aha_token_score*>(m->h_score + S);
+  for (size_t j = 0, r = 0; j < (size_t)n_seg; ++j)
+    for (size_t i = 0; i < lens[j]; ++i, ++r) out[r] = i == 0 ? aha_token_score{0.f, 0xFFFFFFFFu, 0.f} : got[r - 1];
+  return AHA_OK;
+}
+
+int model_score_batch(aha_model* m, const uint32_t* ids, const size_t* seq_lens, size_t n_seqs, size_t max_tokens_per_pass,
+                      aha_token_score* out) {
+  const aha_model_desc& c = m->desc;
+  int rc = model_clear_cache(m);   // (host state only) the cache is empty after every return, the refused calls' too
+  if (rc) return rc;
+  ClearCacheGuard guard{m};
+  if (n_seqs == 0) {
+    set_error("score_batch: empty batch (n_seqs == 0)");
+    return AHA_ERR_INVALID;
+  }
+  if (!ids || !seq_lens || !out) {
+    set_error("score_batch: null input_ids / seq_lens / scores_out");
+    return AHA_ERR_INVALID;
+  }
+  if (c.arch != AHA_ARCH_QWEN3) {
+    set_error("score_batch: the Qwen3 text stack only");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  if (m->tp_size > 1 || m->cp_size > 1 || c.head_dim != 128 || !score_rows_shape_ok(1, c.vocab_size, c.hidden_size)) {
+    set_error("score_batch: a single-GPU model with head_dim 128 and a hidden size that is a multiple of 64 only (no tensor / context parallelism)");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  if ((rc = check_batch_ids(c, "score_batch", ids, seq_lens, n_seqs, 0))) return rc;
+  AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
+  for (const PassRange& p : split_passes(seq_lens, n_seqs, max_tokens_per_pass))
+    if ((rc = score_pass(m, ids + p.off, seq_lens + p.j, (int)(p.k - p.j), out + p.off))) return rc;
   return AHA_OK;
 }
 

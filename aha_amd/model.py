@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MmInput, ModelDesc, TensorView, check, lib
+from ._lib import MmInput, ModelDesc, TensorView, TokenScore, check, lib
 from .configs import Qwen3ASRConfig, Qwen3Config, Qwen3VLConfig
 
 _DT = {torch.bfloat16: _lib.AHA_BF16, torch.float16: _lib.AHA_F16, torch.float32: _lib.AHA_F32}
@@ -391,6 +391,20 @@ class HipInferenceModel:
         check(lib().aha_hip_embed_batch(self.handle, ids.ctypes.data, lens.ctypes.data, lens.size, int(max_tokens_per_pass),
                                         out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def score_batch(self, prompts: Sequence[Sequence[int]], max_tokens_per_pass: int = 0):
+        """The log-probability of every token of every prompt given the tokens before it (aha_hip_score_batch: packed prefills, the lm_head
+        fused with the log-softmax, no logits).  Per prompt a list with one (logprob, top_id, top_logprob) per token: the token's own
+        log-probability (None for the first token, which has no context), the most likely token at that position and its log-probability."""
+        ids, lens = _pack_batch(prompts)
+        out = (TokenScore * int(ids.size))()
+        check(lib().aha_hip_score_batch(self.handle, ids.ctypes.data, lens.ctypes.data, lens.size, int(max_tokens_per_pass), out))
+        res, off = [], 0
+        for n in lens.tolist():
+            res.append([(None if p == 0 else float(out[off + p].logprob), int(out[off + p].top_id), float(out[off + p].top_logprob))
+                        for p in range(n)])
+            off += n
+        return res
 
     def _generate_batch(self, entry, prompts, extra, max_new: int, max_tokens_per_pass: int, logits: Optional[str]):
         """The packing and unpacking of the generate_batch* wrappers: entry(handle, ids, lens, n, *extra, max_new, max_tokens_per_pass,

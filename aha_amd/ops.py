@@ -782,6 +782,26 @@ def logprob_rows(logits: torch.Tensor, tokens, n_top):
     return (o[:, 0].copy().view(np.float32), o[:, 1].copy(), o[:, 2:22].copy().view(np.uint32), o[:, 22:42].copy().view(np.float32))
 
 
+def score_rows(h: torch.Tensor, W: torch.Tensor, targets):
+    """aha_hip_score_rows: for every row of h (R, K) bf16 (row pitch h.stride(0)) against W (V, K) bf16, the log-probability of the row's
+    target (targets[r] in [0, V), or -1: logprob 0) under the softmax of the bf16-rounded logits h . W^T, the row's most likely token and
+    its log-probability -- from the fused lm_head kernel, which never writes a logit.  K must be a multiple of 64.
+    -> numpy (logprob (R,) f32, top_id (R,) uint32, top_logprob (R,) f32): one aha_token_score per row."""
+    if not h.is_cuda or not W.is_cuda:
+        raise ValueError("op inputs must be GPU tensors")
+    assert h.dtype == torch.bfloat16 and h.dim() == 2 and h.stride(1) == 1 and h.stride(0) >= h.shape[1]   # (a row pitch)
+    assert W.dtype == torch.bfloat16 and W.dim() == 2 and W.is_contiguous() and W.shape[1] == h.shape[1]
+    R, K = h.shape
+    V = W.shape[0]
+    tg = np.asarray(targets, dtype=np.int64).reshape(R)
+    assert ((tg >= -1) & (tg < V)).all(), "targets must be in [0, V) or -1"
+    tgt = torch.as_tensor(tg).to(torch.int32).to(h.device)
+    out = torch.empty(R, 3, dtype=torch.int32, device=h.device)
+    check(lib().aha_hip_score_rows(_ptr(h), h.stride(0), R, _ptr(W), V, K, _ptr(tgt), _ptr(out), _stream()))
+    o = out.cpu().numpy()
+    return o[:, 0].copy().view(np.float32), o[:, 1].copy().view(np.uint32), o[:, 2].copy().view(np.float32)
+
+
 def sample_rows_masked(logits: torch.Tensor, k, temperature, repeat_penalty, contexts, adjusts, masks: torch.Tensor, mask_rows):
     """sample_rows_adjusted with allowed-token masks (aha_hip_sample_rows_masked): masks (n_masks, ceil(V / 32)) int32 / uint32 words on the
     device -- id i of a mask is allowed iff bit i & 31 of word i >> 5 is set, bits at positions >= V are ignored -- and mask_rows[r] the

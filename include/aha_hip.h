@@ -421,7 +421,8 @@ int aha_hip_engine_request_spec(const aha_engine* e, uint64_t req_id, size_t* n_
  * Cost: two small launches per step that has a logprob row (profile classes logprob_rows_stage1 / logprob_rows_stage2) and 168 bytes
  * per token in the copy that ends the step anyway; a step without such a row takes the path it took before.
  * Out of scope: logprobs of prompt tokens (`echo`), logprobs in aha_hip_generate_batch_spec, tensor-parallel models.  `logit_bias` and
- * the presence / frequency penalties (aha_logit_adjust below) change the token choice, never these log-probabilities. */
+ * the presence / frequency penalties (aha_logit_adjust below) change the token choice, never these log-probabilities.
+ * (The log-probabilities of tokens the caller already has: aha_hip_score_batch, "log-probabilities of given tokens" below.) */
 #define AHA_MAX_TOP_LOGPROBS 20
 typedef struct aha_token_logprobs {
   float    logprob;                              /* lp(emitted token) */
@@ -451,6 +452,33 @@ int aha_hip_engine_submit_logprobs(aha_engine* e, const uint32_t* input_ids, siz
  * an engine with logprob requests (it reports none and does not compute them). */
 int aha_hip_engine_step_logprobs(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, float* logits_out,
                                  aha_token_logprobs* logprobs_out);
+
+/* ---- log-probabilities of given tokens --------------------------------------------------------------------------------------
+ * Scoring: the log-probability of tokens the caller already has (OpenAI `echo` + `logprobs`, perplexity, loglikelihood ranking,
+ * multiple choice, yes / no reranking), in one packed prefill per pass instead of one forward per prefix, and without the logits:
+ * a 16 384-row pass at V = 151 936 would be 10 GB of f32.
+ * Definition.  For a hidden row h (after the final norm, bf16) and the (V, K) bf16 lm_head W let x_i = the bf16-rounded
+ * sum_k h_k W[i, k], accumulated in f32 and read back as f32 -- the "bf16 Linear output read as f32" the logits of every other
+ * entry are -- and M = max_i x_i, S = sum_i exp(x_i - M).  For the row's target token t:
+ *   logprob = (x_t - M) - log S,  top_id = the first index i with x_i = M,  top_logprob = -log S  (so logprob <= top_logprob <= 0).
+ * Temperature 1, no penalty, no addend.  The values are computed by a fused lm_head kernel (csrc/kernels_score.hip) whose accumulation
+ * order is its own: they lie within the parity bounds of, and are NOT bit-identical to, the logprobs a generate call reports for the
+ * same token.  The same inputs give the same bits on every call.
+ * Out of scope: top-N lists for prompt tokens, the engine, images and audio, tensor- or context-parallel models, the text-only
+ * Qwen3-VL / Qwen3-ASR stacks. */
+typedef struct aha_token_score {
+  float    logprob;      /* of the target; 0 where there is none */
+  uint32_t top_id;       /* the most likely token at that position; 0xFFFFFFFF where there is none */
+  float    top_logprob;
+} aha_token_score;       /* 12 bytes */
+/* input_ids / seq_lens: the packed batch of aha_hip_embed_batch (HOST).  scores_out (HOST): sum of seq_lens entries; with off_j the
+ * packed offset of sequence j, entry off_j + p (p >= 1) scores token p of sequence j given tokens 0 .. p - 1 of that sequence alone,
+ * and entry off_j + 0 is {0, 0xFFFFFFFF, 0}.  Runs as packed passes of at most max_tokens_per_pass rows (0: the embed_batch default),
+ * one copy and one synchronise per pass; clears the KV cache before and after.  AHA_ARCH_QWEN3 on one GPU with head_dim 128, anything
+ * else AHA_ERR_UNSUPPORTED.  Before any device work, with the cache left cleared: AHA_ERR_INVALID for a null pointer, n_seqs == 0, an
+ * empty sequence, or an id >= vocab_size (the message names the sequence and the position). */
+int aha_hip_score_batch(aha_model* m, const uint32_t* input_ids, const size_t* seq_lens, size_t n_seqs, size_t max_tokens_per_pass,
+                        aha_token_score* scores_out);
 
 /* Host-only sampler: candle's LogitsProcessor built by get_logit_processor (sample.rs:7-38) plus use_repeat_penalty's slicing, over
  * the rand 0.9.2 StdRng of aha_hip_rng_*.  The deterministic half restates aha_amd/sampling.py (weights over the device candidates, the
@@ -1030,6 +1058,11 @@ int aha_hip_sample_rows(const float* logits, int64_t ld, int32_t R, int32_t V, c
  * AHA_ERR_INVALID for R < 1, V < 1, ld < V, a null pointer or an n_top outside 0 .. 20, checked before anything touches the device. */
 int aha_hip_logprob_rows(const float* logits, int64_t ld, int32_t R, int32_t V, const uint32_t* tokens, const int32_t* n_top,
                          aha_token_logprobs* out, void* stream);
+/* aha_hip_score_rows: the kernel of aha_hip_score_batch for `rows` rows (all DEVICE pointers): h bf16, row r at h + r * ldh, K values;
+ * W (V, K) bf16 row-major; targets (rows) int32, each in [0, V) or -1 (logprob 0); out (rows).  K must be a multiple of 64, else
+ * AHA_ERR_UNSUPPORTED; any rows >= 1 and V >= 1.  Workspace inside the call: 20 bytes x rows x vocabulary slices (at most 256). */
+int aha_hip_score_rows(const void* h, int64_t ldh, size_t rows, const void* W, size_t V, size_t K, const int32_t* targets,
+                       aha_token_score* out, void* stream);
 /* aha_hip_sample_rows plus addends: adj_ids / adj_vals / adj_offsets are HOST; row r adds adj_vals[i] (finite or -inf) to the penalised
  * logit of adj_ids[i] for i in [adj_offsets[r], adj_offsets[r + 1]) -- ids distinct and < V, in any order (AHA_ERR_INVALID otherwise).
  * A row with no entries gives bit-identical outputs to aha_hip_sample_rows; a row whose every logit ends at -inf is unspecified. */

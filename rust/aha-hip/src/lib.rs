@@ -171,6 +171,16 @@ pub mod sys {
         }
     }
 
+    /// `aha_token_score`: the log-probability of a token the caller already has, the most likely token at its position and that
+    /// token's log-probability (`aha_hip_score_batch`).  The first token of a sequence has `{0, u32::MAX, 0}`.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug)]
+    pub struct AhaTokenScore {
+        pub logprob: f32,
+        pub top_id: u32,
+        pub top_logprob: f32,
+    }
+
     pub const AHA_MAX_LOGIT_BIAS: usize = 1024;
 
     /// `aha_token_mask_fn`: asked once per live sequence per step for the sequence's allowed-token mask (`n_words` = ceil(V / 32) packed
@@ -327,6 +337,25 @@ pub mod sys {
             n_seqs: usize,
             max_tokens_per_pass: usize,
             out: *mut f32,
+        ) -> i32;
+        pub fn aha_hip_score_batch(
+            m: *mut AhaModel,
+            ids: *const u32,
+            seq_lens: *const usize,
+            n_seqs: usize,
+            max_tokens_per_pass: usize,
+            scores_out: *mut AhaTokenScore,
+        ) -> i32;
+        pub fn aha_hip_score_rows(
+            h: *const std::ffi::c_void,
+            ldh: i64,
+            rows: usize,
+            w: *const std::ffi::c_void,
+            vocab: usize,
+            k: usize,
+            targets: *const i32,
+            out: *mut AhaTokenScore,
+            stream: *mut std::ffi::c_void,
         ) -> i32;
         pub fn aha_hip_generate_batch(
             m: *mut AhaModel,
@@ -1049,6 +1078,25 @@ impl Model {
             sys::aha_hip_embed_batch(self.model, ids.as_ptr(), lens.as_ptr(), lens.len(), max_tokens_per_pass, out.as_mut_ptr())
         })?;
         Ok(out)
+    }
+
+    /// The log-probability of every token of every sequence given the tokens before it (`aha_hip_score_batch`): per sequence one
+    /// `AhaTokenScore` per token, the first being `{0, u32::MAX, 0}`.  The cache is empty afterwards.
+    pub fn score_batch(&mut self, seqs: &[&[u32]], max_tokens_per_pass: usize) -> Result<Vec<Vec<sys::AhaTokenScore>>, Error> {
+        let ids: Vec<u32> = seqs.iter().flat_map(|s| s.iter().copied()).collect();
+        let lens: Vec<usize> = seqs.iter().map(|s| s.len()).collect();
+        let mut out = vec![sys::AhaTokenScore { logprob: 0.0, top_id: u32::MAX, top_logprob: 0.0 }; ids.len()];
+        check(unsafe {
+            sys::aha_hip_score_batch(self.model, ids.as_ptr(), lens.as_ptr(), lens.len(), max_tokens_per_pass, out.as_mut_ptr())
+        })?;
+        let mut off = 0usize;
+        Ok(lens
+            .iter()
+            .map(|&n| {
+                off += n;
+                out[off - n..off].to_vec()
+            })
+            .collect())
     }
 
     /// `generate_generic` at temperature 0 for every prompt at once (aha_hip_generate_batch): per prompt, the greedy tokens it
