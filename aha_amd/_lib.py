@@ -19,6 +19,7 @@ AHA_SAMPLE_HAS_TOP_P, AHA_SAMPLE_HAS_TOP_K = 1, 2
 AHA_SAMPLE_NEED_LOGITS = 1
 AHA_WQ_NONE, AHA_WQ_MXFP8_E4M3, AHA_WQ_MXFP4_E2M1 = 0, 1, 2
 AHA_WQ_LM_HEAD = 1
+AHA_WQ_PREFILL = 2
 
 
 class SamplingParams(C.Structure):
@@ -265,6 +266,9 @@ SIGNATURES = {
     "aha_hip_sampler_rng_words": (C.c_uint64, [_P]),
     "aha_hip_gemv_rows": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "aha_hip_quantize_mxfp8": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "aha_hip_quantize_mxfp8_rows": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
+    "aha_hip_gemm_mxfp8": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "aha_hip_debug_plan_gemm_mxfp8": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "aha_hip_gemv_rows_mxfp8": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "aha_hip_quantize_mxfp4": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "aha_hip_gemv_rows_mxfp4": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),

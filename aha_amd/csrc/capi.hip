@@ -1029,6 +1029,60 @@ int aha_hip_quantize_mxfp8(const void* W, int32_t N, int32_t K, void* q_out, uin
   API_GUARD_END
 }
 
+int aha_hip_quantize_mxfp8_rows(const void* A, int64_t lda, int32_t M, int32_t K, void* q_out, uint32_t* scales_out, void* stream) {
+  API_GUARD_BEGIN
+  if (!A || !q_out || !scales_out || M < 1 || K < 128 || K % 128 || lda < K || lda % 8) {
+    set_error("quantize_mxfp8_rows: bad arguments (A, q_out, scales_out, M >= 1, K a positive multiple of 128, lda >= K and a multiple of 8)");
+    return AHA_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  launch_mxfp8_quantize_rows(A, lda, M, K, q_out, scales_out, st);
+  AHA_HIP_CHECK(hipGetLastError());
+  AHA_HIP_CHECK(hipStreamSynchronize(st));
+  return AHA_OK;
+  API_GUARD_END
+}
+
+int aha_hip_gemm_mxfp8(const void* Aq, const uint32_t* a_scales, const void* Wq, const uint32_t* w_scales, void* C, int32_t M, int32_t N,
+                       int32_t K, int32_t ldc, int32_t act, const void* residual, void* stream) {
+  API_GUARD_BEGIN
+  if (!Aq || !a_scales || !Wq || !w_scales || !C) {
+    set_error("gemm_mxfp8: null pointer (Aq, a_scales, Wq, w_scales, C)");
+    return AHA_ERR_INVALID;
+  }
+  if (act != ACT_NONE && act != ACT_SILU_MUL_PAIRS) {
+    set_error("gemm_mxfp8: unknown act " + std::to_string(act) + " (0 = none, 4 = gate+up pairs)");
+    return AHA_ERR_INVALID;
+  }
+  if (M < 1 || K < 128 || K % 128 || N < 16 || N % 16 || (act == ACT_SILU_MUL_PAIRS && (N % 32 || residual))) {
+    set_error("gemm_mxfp8: M >= 1, K a positive multiple of 128, N a positive multiple of 16 (gate+up pairs: of 32, and no residual)");
+    return AHA_ERR_INVALID;
+  }
+  if (ldc % 4 || ldc < (act == ACT_SILU_MUL_PAIRS ? N / 2 : N)) {
+    set_error("gemm_mxfp8: ldc must be a multiple of 4 and hold an output row");
+    return AHA_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  GemmArgs g{};
+  g.A = Aq; g.W = Wq; g.C = C; g.residual = residual; g.M = M; g.N = N; g.K = K; g.ldc = ldc; g.act = act;
+  launch_gemm_mxfp8(g, a_scales, w_scales, st);
+  AHA_HIP_CHECK(hipGetLastError());
+  AHA_HIP_CHECK(hipStreamSynchronize(st));
+  return AHA_OK;
+  API_GUARD_END
+}
+
+int aha_hip_debug_plan_gemm_mxfp8(int32_t M, int32_t N, int32_t K, int32_t act, int32_t* out4) {
+  if (!out4 || !gemm_mxfp8_shape_ok(M, N, K, act)) {
+    set_error("debug_plan_gemm_mxfp8: bad argument (out4, M >= 1, N % 16 == 0, K % 128 == 0, act 0 or 4 with N % 32 == 0)");
+    return AHA_ERR_INVALID;
+  }
+  int o[4];
+  debug_plan_gemm_mxfp8(M, N, K, act, o);
+  for (int i = 0; i < 4; ++i) out4[i] = o[i];
+  return AHA_OK;
+}
+
 int aha_hip_quantize_mxfp4(const void* W, int32_t N, int32_t K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, void* stream) {
   API_GUARD_BEGIN
   return quantize_mx_op(4, W, N, K, q_out, scales_out, w_roundtrip_out, stream);

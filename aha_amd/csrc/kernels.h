@@ -379,6 +379,17 @@ void launch_gemv_mxfp8(const GemvArgs& g, const void* q, const uint32_t* scales,
 int gemv_mxfp8_num_tiles(int N, int K);
 bool gemv_mxfp8_by_plan(int N, int K, GemvEpi epi);   // does the model's single-sequence step read this matrix (N rows: 2I for gate+up) from its copy?
 void debug_plan_gemv_mxfp8(int N, int K, GemvEpi epi, bool has_norm, int* out5);   // host only: {R, U, grid, FAST, PRO}; N = output rows
+// MXFP8 prefill GEMM (kernels_gemm_fp8.hip): both operands as (q, scales) of the layout above, multiplied on the block-scaled MFMA.
+// launch_mxfp8_quantize_rows: bf16 rows A (M, K), row pitch lda (a multiple of 8), K % 128 == 0 -> q_out (M, K) bytes, scales_out (M, K / 128)
+// u32, byte for byte what launch_mxfp8_quantize writes for the same matrix; Inf and values of 1.9375 * 2^127 or more saturate to
+// +-448 * 2^120, NaN becomes the E4M3 NaN code.  launch_gemm_mxfp8: a.A = Aq, a.W = Wq (row pitch K bytes; lda / ldw / bias / groups / the
+// workspace are ignored), a.C bf16 (M, N) or (M, N / 2), a.act ACT_NONE (optional residual, may alias C) or ACT_SILU_MUL_PAIRS, a riding
+// RMSNorm (norm_w, norm_out) as the appended launch_rmsnorm_rows; gemm_mxfp8_shape_ok(M, N, K, act) required: N % 16 == 0 (pairs: 32),
+// K % 128 == 0.  One 256 x 128 tile kernel, no split-K.
+void launch_mxfp8_quantize_rows(const void* A, int64_t lda, int M, int K, void* q_out, uint32_t* scales_out, hipStream_t st);
+bool gemm_mxfp8_shape_ok(int M, int N, int K, int act);
+void launch_gemm_mxfp8(const GemmArgs& a, const uint32_t* a_scales, const uint32_t* w_scales, hipStream_t st);
+void debug_plan_gemm_mxfp8(int M, int N, int K, int act, int* out4);   // host only: {tile rows, tile columns, workgroups, ring stages}
 // MXFP4 weight copies (kernels_gemv_rows_fp4.hip, mxfp4.h): the same blocks and the same scale words as MXFP8, with
 //   q       (N, K / 2) bytes, row-major: OCP E2M1 codes (sign << 3 | index into {0, 0.5, 1, 1.5, 2, 3, 4, 6}) of w / 2^e, byte (n, k / 2)
 //           holds even k in bits 0..3 and odd k in bits 4..7 -- a lane's MX block of gemv_rows is one 16-byte load

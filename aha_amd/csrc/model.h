@@ -206,6 +206,9 @@ struct aha_model {
   uint32_t* p_ids = nullptr;
   int32_t* p_pos = nullptr;
   void *p_x = nullptr, *p_h = nullptr, *p_qkv = nullptr, *p_q = nullptr, *p_attn = nullptr, *p_act = nullptr;
+  // AHA_WQ_PREFILL: one layer GEMM's input rows as MXFP8 (bytes, scale words), sized with the buffers above
+  void* p_aq = nullptr;
+  uint32_t* p_ascales = nullptr;
   void* p_rope = nullptr;       // (S, 128) bf16 cos | sin table of the prefill's positions (kernels.h launch_rope_table)
   void* p_gemm_ws = nullptr;    // f32 split-K slabs (kernels_gemm.hip)
   size_t gemm_ws_bytes = 0;

@@ -667,9 +667,15 @@ int model_quantize_weights(aha_model* m, int32_t format, uint32_t flags) {
     set_error("quantize_weights: unknown format " + std::to_string(format) + " (AHA_WQ_MXFP8_E4M3 = 1, AHA_WQ_MXFP4_E2M1 = 2)");
     return AHA_ERR_INVALID;
   }
-  if (flags & ~(uint32_t)AHA_WQ_LM_HEAD) {
-    set_error("quantize_weights: unknown flag bits " + std::to_string(flags & ~(uint32_t)AHA_WQ_LM_HEAD) + " (AHA_WQ_LM_HEAD = 1)");
+  if (flags & ~(uint32_t)(AHA_WQ_LM_HEAD | AHA_WQ_PREFILL)) {
+    // (the whole word first, as before the second flag existed: flags 6 reads "unknown flag bits 6", of which bit 4 is the stranger)
+    set_error("quantize_weights: unknown flag bits " + std::to_string(flags) + ": " + std::to_string(flags & ~(uint32_t)(AHA_WQ_LM_HEAD | AHA_WQ_PREFILL)) +
+              " is not among AHA_WQ_LM_HEAD = 1, AHA_WQ_PREFILL = 2");
     return AHA_ERR_INVALID;
+  }
+  if ((flags & AHA_WQ_PREFILL) && format != AHA_WQ_MXFP8_E4M3) {
+    set_error("quantize_weights: AHA_WQ_PREFILL needs AHA_WQ_MXFP8_E4M3 (the prefill GEMM multiplies E4M3 operands; there is none for MXFP4 copies)");
+    return AHA_ERR_UNSUPPORTED;
   }
   if (m->engine) {
     set_error("quantize_weights: the model has an engine (aha_hip_engine_destroy first)");
@@ -1042,11 +1048,15 @@ void model_destroy(aha_model* m) {
 
 // ---------------------------------------------------------------------------------------------------------------
 static int ensure_prefill_scratch(aha_model* m, size_t S) {
-  if (S <= m->pf_cap) return AHA_OK;
+  const bool fp8_prefill = (m->wq_flags & AHA_WQ_PREFILL) != 0;
+  if (S <= m->pf_cap && (!fp8_prefill || m->p_aq)) return AHA_OK;   // (a model flagged after its first prefill has no quantiser scratch yet)
+  S = std::max(S, m->pf_cap);
   AHA_HIP_CHECK(hipStreamSynchronize(m->stream));
   for (void* p : m->pf_owned) hipFree(p);
   m->pf_owned.clear();
   m->pf_cap = 0;
+  m->p_aq = nullptr;
+  m->p_ascales = nullptr;
   const aha_model_desc& c = m->desc;
   const size_t cap = (S + 255) / 256 * 256;
   const size_t H = c.hidden_size, I = c.intermediate_size, nq = (size_t)c.num_attention_heads * c.head_dim,
@@ -1072,6 +1082,11 @@ static int ensure_prefill_scratch(aha_model* m, size_t S) {
   if ((rc = al(cap * nq * 2, &m->p_q))) return rc;
   if ((rc = al(cap * nq * 2, &m->p_attn))) return rc;
   if ((rc = al(cap * I * 2, &m->p_act))) return rc;
+  if (fp8_prefill) {   // one GEMM's input rows as MXFP8: the widest K of the four matrices
+    const size_t kmax = std::max(std::max(H, nq), I);
+    if ((rc = al(cap * kmax, &m->p_aq))) return rc;
+    if ((rc = al(cap * ((kmax + 127) / 128) * 4, (void**)&m->p_ascales))) return rc;
+  }
   if (m->tp_size > 1 && (rc = al((cap + 64) * H * 4, (void**)&m->p_partial))) return rc;
   if (m->tp_size > 1 && (rc = al((cap + 64) * H * 2, &m->p_hstage))) return rc;
   if (m->cp_size > 1) {   // one layer's K / V of every rank's pages: cp_size x (max pages of a rank) x kv heads x (K | V) 16-KB blocks
@@ -2005,6 +2020,28 @@ struct GemmProf : ProfScope {
       : ProfScope(m, "gemm", ((double)g.M * g.K + (double)g.N * g.K + out_elems(g)) * 2, 2.0 * g.M * g.N * g.K) {}
 };
 
+// One layer GEMM of a prefill pass.  A model quantised with AHA_WQ_PREFILL (MXFP8 copies, never sharded) quantises the GEMM's input rows into
+// its scratch and multiplies the copies on the block-scaled MFMA, for every M; a matrix the FP8 kernel has no shape for (K % 128) and every
+// other model run what they ran before the flag existed.
+static int prefill_gemm(aha_model* m, const GemmArgs& g, const WQuant& wq, bool row_parallel, int spr) {
+  if ((m->wq_flags & AHA_WQ_PREFILL) && wq.q && m->p_aq && g.lda == g.K && gemm_mxfp8_shape_ok(g.M, g.N, g.K, g.act)) {
+    {
+      ProfScope ps(m, "quant_rows", (double)g.M * g.K * 3.03125, 0);
+      launch_mxfp8_quantize_rows(g.A, g.lda, g.M, g.K, m->p_aq, m->p_ascales, m->stream);
+    }
+    GemmArgs f = g;
+    f.A = m->p_aq;
+    f.W = wq.q;
+    ProfScope ps(m, "gemm_fp8", ((double)g.M * g.K + (double)g.N * g.K + GemmProf::out_elems(g)) * 2, 2.0 * g.M * g.N * g.K);
+    launch_gemm_mxfp8(f, m->p_ascales, wq.scales, m->stream);
+    return AHA_OK;
+  }
+  GemmProf ps(m, g);
+  if (row_parallel) return gemm_row_parallel(m, g, spr);
+  launch_gemm(g, m->stream);
+  return AHA_OK;
+}
+
 // rope_attn(li, L): layer li's q/k-norm + RoPE + KV append out of p_qkv and its attention into p_attn; returns an error code
 template <class RopeAttn>
 static int prefill_layers(aha_model* m, const PrefillRows& pr, RopeAttn&& rope_attn) {
@@ -2023,8 +2060,7 @@ static int prefill_layers(aha_model* m, const PrefillRows& pr, RopeAttn&& rope_a
         if ((rc = norm_gather_gemm(m, L.in_norm, g, pr.S, pr.spr))) return rc;
       } else {
         if (!in_norm_done && (rc = prefill_norm(m, L.in_norm, M, 0))) return rc;
-        GemmProf ps(m, g);
-        launch_gemm(g, st);
+        if ((rc = prefill_gemm(m, g, L.q_wqkv, false, 0))) return rc;
       }
     }
     in_norm_done = false;
@@ -2033,8 +2069,7 @@ static int prefill_layers(aha_model* m, const PrefillRows& pr, RopeAttn&& rope_a
       GemmArgs g{};
       g.A = m->p_attn; g.W = L.wo; g.C = m->p_x; g.residual = m->p_x; g.M = M; g.N = H; g.K = nq; g.lda = nq; g.ldw = nq; g.ldc = H; g.act = ACT_NONE;
       if (pr.norm_in_gemm) { g.norm_w = L.post_norm; g.norm_out = m->p_h; g.norm_eps = c.rms_norm_eps; }
-      GemmProf ps(m, g);
-      if ((rc = gemm_row_parallel(m, g, pr.spr))) return rc;
+      if ((rc = prefill_gemm(m, g, L.q_wo, true, pr.spr))) return rc;
     }
     {
       GemmArgs g{};
@@ -2043,8 +2078,7 @@ static int prefill_layers(aha_model* m, const PrefillRows& pr, RopeAttn&& rope_a
         if ((rc = norm_gather_gemm(m, L.post_norm, g, pr.S, pr.spr))) return rc;
       } else {
         if (!pr.norm_in_gemm && (rc = prefill_norm(m, L.post_norm, M, 0))) return rc;
-        GemmProf ps(m, g);
-        launch_gemm(g, st);
+        if ((rc = prefill_gemm(m, g, L.q_wgu, false, 0))) return rc;
       }
     }
     {
@@ -2054,8 +2088,7 @@ static int prefill_layers(aha_model* m, const PrefillRows& pr, RopeAttn&& rope_a
         g.norm_w = m->layers[li + 1].in_norm; g.norm_out = m->p_h; g.norm_eps = c.rms_norm_eps;
         in_norm_done = true;
       }
-      GemmProf ps(m, g);
-      if ((rc = gemm_row_parallel(m, g, pr.spr))) return rc;
+      if ((rc = prefill_gemm(m, g, L.q_wdown, true, pr.spr))) return rc;
     }
     // (context-parallel: the visual rows of other ranks all land on the scratch row behind this rank's rows)
     if (pr.vis && (rc = vision_deepstack_add(m, li, m->p_x))) return rc;

@@ -613,20 +613,29 @@ class HipInferenceModel:
         """Quantise the layer matrices (and lm_head with lm_head=True) to MXFP8 in place (aha_hip_model_quantize_weights): the batched decode
         then streams the FP8 copies; every other path reads the dequantised bf16 matrices.  aha_amd/quant.py is the reference quantiser.
         fmt "mxfp4": MXFP4 copies (E2M1 nibbles, 0.53 bytes per weight) for the batched decode and, on the matrices its plan takes
-        (debug_fp4_single), the single-sequence decode."""
+        (debug_fp4_single), the single-sequence decode.  quantize_weights_with adds the opt-in prefill flag."""
+        HipInferenceModel.quantize_weights_with(self, fmt, lm_head)
+
+    def quantize_weights_with(self, fmt: str = "mxfp8", lm_head: bool = False, prefill: bool = False) -> None:
+        """quantize_weights with the opt-in flag prefill=True ("mxfp8" only: AHA_WQ_PREFILL): the four layer GEMMs of every prefill quantise
+        their input rows to MXFP8 and multiply the copies on the block-scaled MFMA (profile classes "quant_rows", "gemm_fp8").  Prefill
+        logits then differ from the unflagged model's by about what the weight quantisation itself changed (profiles/prefill_fp8.md);
+        decode is unchanged.  (A method of its own: quantize_weights keeps its two arguments.)"""
         formats = {"mxfp8": _lib.AHA_WQ_MXFP8_E4M3, "mxfp4": _lib.AHA_WQ_MXFP4_E2M1}
         if fmt not in formats:
             raise ValueError(f"unknown weight format {fmt!r} (\"mxfp8\", \"mxfp4\")")
-        check(lib().aha_hip_model_quantize_weights(self.handle, formats[fmt], _lib.AHA_WQ_LM_HEAD if lm_head else 0))
+        check(lib().aha_hip_model_quantize_weights(self.handle, formats[fmt],
+                                                 (_lib.AHA_WQ_LM_HEAD if lm_head else 0) | (_lib.AHA_WQ_PREFILL if prefill else 0)))
 
     @property
     def weight_format(self):
-        """None, or ("mxfp8" | "mxfp4", lm_head) as quantize_weights was called."""
+        """None, or ("mxfp8" | "mxfp4", lm_head) as quantize_weights was called; ("mxfp8", lm_head, "prefill") with prefill=True."""
         f, fl = C.c_int32(), C.c_uint32()
         check(lib().aha_hip_model_weight_format(self.handle, C.byref(f), C.byref(fl)))
         if f.value == _lib.AHA_WQ_NONE:
             return None
-        return ("mxfp4" if f.value == _lib.AHA_WQ_MXFP4_E2M1 else "mxfp8", bool(fl.value & _lib.AHA_WQ_LM_HEAD))
+        fmt = ("mxfp4" if f.value == _lib.AHA_WQ_MXFP4_E2M1 else "mxfp8", bool(fl.value & _lib.AHA_WQ_LM_HEAD))
+        return fmt + ("prefill",) if fl.value & _lib.AHA_WQ_PREFILL else fmt
 
     def debug_fp8_rows(self, on: bool = True) -> None:
         """Test hook: False makes a quantised model's batched decode run the bf16 matvec on the dequantised matrices (the same bits)."""

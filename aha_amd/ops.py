@@ -463,6 +463,41 @@ def gemv_rows_mxfp8(q: torch.Tensor, scales: torch.Tensor, x: torch.Tensor, epi:
     return _gemv_rows_mx(lib().aha_hip_gemv_rows_mxfp8, q, q.shape[1], scales, x, epi, residual, out)
 
 
+def quantize_mxfp8_rows(A: torch.Tensor):
+    """The row-streaming activation quantiser (aha_hip_quantize_mxfp8_rows) on GPU bf16 rows A (M, K), K % 128 == 0; A may be a column slice
+    of a wider contiguous matrix (row stride a multiple of 8) -> (q (M, K) uint8, scales (M, K / 32) uint8 in the reference's order) on the
+    GPU: the bytes of quantize_mxfp8 / aha_amd/quant.py quantize_mxfp8 on the same matrix."""
+    from . import quant
+    if not A.is_cuda or A.dim() != 2 or A.stride(1) != 1:
+        raise ValueError("quantize_mxfp8_rows: a GPU matrix with unit column stride")
+    M, K = A.shape
+    q = torch.empty(M, K, dtype=torch.uint8, device=A.device)
+    words = torch.empty(M, K // 128, dtype=torch.int32, device=A.device)
+    check(lib().aha_hip_quantize_mxfp8_rows(_ptr(A), A.stride(0), M, K, _ptr(q), _ptr(words), _stream()))
+    return q, quant.scales_from_kernel(words, K).to(A.device)
+
+
+def gemm_mxfp8(Aq: torch.Tensor, a_scales: torch.Tensor, Wq: torch.Tensor, w_scales: torch.Tensor, residual: Optional[torch.Tensor] = None,
+               act: int = _lib.ACT_NONE, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """C (M, N) bf16 = epilogue(A' . W'^T) on the block-scaled MFMA (aha_hip_gemm_mxfp8): Aq (M, K) / Wq (N, K) uint8 E4M3 codes with scales
+    (rows, K / 32) uint8 in the reference's order.  act ACT_NONE (+ residual, which may be `out` itself) or ACT_SILU_MUL_PAIRS -> (M, N / 2)."""
+    from . import quant
+    _chk(Aq, Wq, residual, out)
+    (M, K), N = Aq.shape, Wq.shape[0]
+    aw, ww = quant.scales_to_kernel(a_scales).to(Aq.device), quant.scales_to_kernel(w_scales).to(Aq.device)
+    n_out = N // 2 if act == _lib.ACT_SILU_MUL_PAIRS else N
+    Cm = out if out is not None else torch.empty(M, n_out, dtype=torch.bfloat16, device=Aq.device)
+    check(lib().aha_hip_gemm_mxfp8(_ptr(Aq), _ptr(aw), _ptr(Wq), _ptr(ww), _ptr(Cm), M, N, K, n_out, act, _ptr(residual), _stream()))
+    return Cm
+
+
+def plan_gemm_mxfp8(M: int, N: int, K: int, act: int = _lib.ACT_NONE):
+    """Host only: (tile rows, tile columns, workgroups, ring stages) of gemm_mxfp8's launch (aha_hip_debug_plan_gemm_mxfp8)."""
+    o = (C.c_int32 * 4)()
+    check(lib().aha_hip_debug_plan_gemm_mxfp8(M, N, K, act, o))
+    return tuple(o)
+
+
 def quantize_mxfp4(W: torch.Tensor):
     """The library's MXFP4 quantiser (aha_hip_quantize_mxfp4) on a GPU bf16 matrix (N, K), K % 32 == 0 -> (q (N, K / 2) uint8 packed E2M1
     codes, scales (N, K / 32) uint8, W' (N, K) bf16) on the GPU, scales in the reference's order (aha_amd/quant.py quantize_mxfp4: the same

@@ -762,7 +762,7 @@ int aha_hip_debug_allreduce(aha_model* m, void* buf_f32_dev, size_t count);
  * instead of 2, with the bits it would compute from W', and so does the single-sequence decode matvec (aha_hip_forward_step,
  * aha_hip_decode_greedy, the generate_generic loops, the last-row lm_head of aha_hip_forward_initial: gemv_mxfp8_kernel, bit-identical to
  * the bf16 kernel on W') on the matrices it measured faster on, those of 2^24 elements or more whose launch takes the kernel's FAST form (aha_hip_debug_fp8_single); prefill and
- * every other path go on reading the bf16 W'.  flags: 0, or
+ * every other path go on reading the bf16 W' (prefill: unless AHA_WQ_PREFILL is given, below).  flags: 0, or
  * AHA_WQ_LM_HEAD to quantise lm_head too (with tied embeddings: the embedding table).  Costs 0.516 x the quantised matrices in memory.
  * AHA_ERR_INVALID: a null model, an unknown format or flag, or a weight that is not finite (or >= 1.9375 * 2^127 in magnitude), naming
  * the tensor -- every matrix is checked before any is modified.  AHA_ERR_STATE: the cache is not empty, the model has an engine, or it
@@ -780,6 +780,16 @@ int aha_hip_debug_allreduce(aha_model* m, void* buf_f32_dev, size_t count);
 #define AHA_WQ_MXFP8_E4M3 1
 #define AHA_WQ_MXFP4_E2M1 2
 #define AHA_WQ_LM_HEAD 1u
+/* AHA_WQ_PREFILL (opt-in, AHA_WQ_MXFP8_E4M3 only; with AHA_WQ_MXFP4_E2M1: AHA_ERR_UNSUPPORTED, naming the cause): the prefill reads the copies
+ * too.  The four layer GEMMs of every prefill pass (qkv, o_proj, gate+up, down; every M, every entry point) then quantise their input rows to
+ * MXFP8 (aha_hip_quantize_mxfp8_rows, into scratch the model owns) and multiply E4M3 x E4M3 on the block-scaled matrix instruction
+ * (aha_hip_gemm_mxfp8; profile classes quant_rows and gemm_fp8) instead of running the bf16 GEMM on W'.  Quantising the activations changes
+ * the results: the prefill logits of a flagged model differ from those of the same model without the flag by about as much as the weight
+ * quantisation itself changed them (profiles/prefill_fp8.md has the measured deviation).  Decode, the lm_head, the towers, embedding pooling
+ * and the draft-and-verify rows are untouched: they run exactly what an unflagged MXFP8 model runs.  A matrix whose K is not a multiple of
+ * 128 stays on the bf16 GEMM.  The flag is part of the arguments the "same arguments again" rule compares: quantising a model again with
+ * the flag added or removed is AHA_ERR_STATE. */
+#define AHA_WQ_PREFILL 2u
 int aha_hip_model_quantize_weights(aha_model* m, int32_t format, uint32_t flags);
 /* *format = AHA_WQ_NONE or the format the model was quantised with, *flags its flags (either pointer may be NULL). */
 int aha_hip_model_weight_format(const aha_model* m, int32_t* format, uint32_t* flags);
@@ -952,6 +962,22 @@ int aha_hip_gemv_rows(const void* W, const void* x, void* y, int32_t R, int32_t 
  * aha_hip_gemv_rows_mxfp8: aha_hip_gemv_rows with (q, scales) in place of W, K % 32 == 0: every output bit equals
  * aha_hip_gemv_rows on W'. */
 int aha_hip_quantize_mxfp8(const void* W, int32_t N, int32_t K, void* q_out, uint32_t* scales_out, void* w_roundtrip_out, void* stream);
+/* MXFP8 prefill GEMM, op level (csrc/kernels_gemm_fp8.hip): both operands as (q, scales) of the layout above, multiplied by
+ * v_mfma_scale_f32_16x16x128_f8f6f4, which applies the E8M0 block scales inside the instruction; f32 accumulation.
+ * aha_hip_quantize_mxfp8_rows: the row-streaming quantiser for activations: A (M, K) bf16 with row pitch lda elements (a multiple of 8),
+ * K % 128 == 0 -> q_out (M, K) bytes and scales_out (M, K / 128) u32, byte for byte what aha_hip_quantize_mxfp8 writes for the same matrix.
+ * Device work cannot fail a call, so values the weight quantiser refuses are mapped: +-Inf and magnitudes of 1.9375 * 2^127 or more saturate
+ * to +-448 * 2^120, NaN becomes the E4M3 NaN code 0x7f (sign kept) and takes no part in its block's maximum.
+ * aha_hip_gemm_mxfp8: C (M, N) bf16 with row pitch ldc = epilogue(A' . W'^T), A' = Aq * 2^(a_scales) (M, K), W' = Wq * 2^(w_scales) (N, K).
+ * act 0: C = bf16(sum), + residual (M, N, pitch ldc; may be NULL, may alias C) -> bf16; act 4 (gate+up pairs, W in the 16-row gate / up block
+ * layout, N % 32 == 0): C (M, N / 2) = SiLU(gate) * up with the rounding points and the SiLU of aha_hip_gemm, no residual.  M >= 1,
+ * N % 16 == 0, K % 128 == 0, ldc a multiple of 4 that holds a row.  AHA_ERR_INVALID with a message, before anything is launched, for a null
+ * pointer or a size outside these.
+ * aha_hip_debug_plan_gemm_mxfp8 (host only, no GPU): out4 = {tile rows, tile columns, workgroups, LDS ring stages} of that launch. */
+int aha_hip_quantize_mxfp8_rows(const void* A, int64_t lda, int32_t M, int32_t K, void* q_out, uint32_t* scales_out, void* stream);
+int aha_hip_gemm_mxfp8(const void* Aq, const uint32_t* a_scales, const void* Wq, const uint32_t* w_scales, void* C, int32_t M, int32_t N,
+                       int32_t K, int32_t ldc, int32_t act, const void* residual, void* stream);
+int aha_hip_debug_plan_gemm_mxfp8(int32_t M, int32_t N, int32_t K, int32_t act, int32_t* out4);
 /* Batch-1 matvec with an epilogue, op level (the single-sequence decode step's kernels).  N counts MATRIX rows; epi as in
  * aha_hip_gemv_rows: 0 y (N) bf16; 1 y = residual + Linear (may alias); 2 SiLU(gate) * up with W in the 16-row gate / up block layout
  * (N = 2I, N % 32 == 0), y (I) bf16; 3 logits (N) f32 and *argmax_out (device u32) the first maximal index.  norm_w != NULL fuses

@@ -71,6 +71,7 @@ pub mod sys {
     pub const AHA_WQ_MXFP8_E4M3: i32 = 1;
     pub const AHA_WQ_MXFP4_E2M1: i32 = 2;
     pub const AHA_WQ_LM_HEAD: u32 = 1;
+    pub const AHA_WQ_PREFILL: u32 = 2;
 
     /// `aha_sampling_params`: the Options of `GenerationContext::new` (common/generate.rs:21-53); same fields, same order as the
     /// ctypes mirror `aha_amd._lib.SamplingParams`.
@@ -743,6 +744,30 @@ pub mod sys {
             w_roundtrip_out: *mut std::ffi::c_void,
             stream: *mut std::ffi::c_void,
         ) -> i32;
+        pub fn aha_hip_quantize_mxfp8_rows(
+            a: *const std::ffi::c_void,
+            lda: i64,
+            m: i32,
+            k: i32,
+            q_out: *mut std::ffi::c_void,
+            scales_out: *mut u32,
+            stream: *mut std::ffi::c_void,
+        ) -> i32;
+        pub fn aha_hip_gemm_mxfp8(
+            aq: *const std::ffi::c_void,
+            a_scales: *const u32,
+            wq: *const std::ffi::c_void,
+            w_scales: *const u32,
+            c: *mut std::ffi::c_void,
+            m: i32,
+            n: i32,
+            k: i32,
+            ldc: i32,
+            act: i32,
+            residual: *const std::ffi::c_void,
+            stream: *mut std::ffi::c_void,
+        ) -> i32;
+        pub fn aha_hip_debug_plan_gemm_mxfp8(m: i32, n: i32, k: i32, act: i32, out4: *mut i32) -> i32;
         pub fn aha_hip_gemv_rows_mxfp8(
             q: *const std::ffi::c_void,
             scales: *const u32,
@@ -1045,8 +1070,22 @@ impl Model {
     /// has a kernel of its own (`gemv_mxfp4_kernel`, bit-identical again) under the switch `debug_fp4_single`.  Needs an empty cache
     /// and no engine.
     pub fn quantize_weights(&mut self, format: WeightFormat, lm_head: bool) -> Result<(), Error> {
-        let flags = if lm_head { sys::AHA_WQ_LM_HEAD } else { 0 };
+        self.quantize_weights_with(format, lm_head, false)
+    }
+
+    /// `quantize_weights` with the opt-in `prefill` flag (`AHA_WQ_PREFILL`, `WeightFormat::Mxfp8E4m3` only): the four layer GEMMs of every
+    /// prefill then quantise their input rows to MXFP8 and multiply the copies on the block-scaled MFMA.  Prefill logits differ from the
+    /// unflagged model's by about what the weight quantisation itself changed; decode is unchanged.
+    pub fn quantize_weights_with(&mut self, format: WeightFormat, lm_head: bool, prefill: bool) -> Result<(), Error> {
+        let flags = if lm_head { sys::AHA_WQ_LM_HEAD } else { 0 } | if prefill { sys::AHA_WQ_PREFILL } else { 0 };
         check(unsafe { sys::aha_hip_model_quantize_weights(self.model, format as i32, flags) })
+    }
+
+    /// Was the model quantised with the `prefill` flag (`AHA_WQ_PREFILL`)?
+    pub fn prefill_from_copies(&self) -> Result<bool, Error> {
+        let (mut f, mut fl) = (0i32, 0u32);
+        check(unsafe { sys::aha_hip_model_weight_format(self.model, &mut f, &mut fl) })?;
+        Ok(fl & sys::AHA_WQ_PREFILL != 0)
     }
 
     /// The single-sequence matvec of a model with MXFP4 copies (`aha_hip_debug_fp4_single`): 0 the bf16 kernel on the dequantised
