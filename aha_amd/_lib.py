@@ -276,6 +276,7 @@ SIGNATURES = {
     "aha_hip_model_weight_format": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]),
     "aha_hip_debug_fp8_rows": (C.c_int, [_P, C.c_int]),
     "aha_hip_debug_fp8_single": (C.c_int, [_P, C.c_int]),
+    "aha_hip_debug_rows_wide": (C.c_int, [_P, C.c_int]),
     "aha_hip_debug_pk13_single": (C.c_int, [_P, C.c_int]),
     "aha_hip_pk13_status": (C.c_int, [_P, C.c_char_p, C.c_size_t]),
     "aha_hip_pack_pk13": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _P]),
@@ -297,6 +298,8 @@ SIGNATURES = {
     "aha_hip_debug_plan_gemv": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "aha_hip_debug_plan_gemv_rows": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "aha_hip_debug_plan_gemv_rows_wide": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                    C.POINTER(C.c_int32)]),
     "aha_hip_debug_gemv_partial_f32": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_float, _P]),
     "aha_hip_attn_decode_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "aha_hip_debug_attn_decode_fused": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),

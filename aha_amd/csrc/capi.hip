@@ -951,18 +951,35 @@ int aha_hip_attn_decode(const void* q, const void* k, const void* v, void* o, in
 }
 
 // ---- batched decode, op level (scratch allocated per call: test / measurement entries) ----
+// Is p memory a kernel can reach (device, pinned or managed)?  The op entries launch on the pointers they are given; with up to 128 rows
+// valid, a call with buffers of the wrong kind has no argument check left to stop it.
+static bool device_reachable(const void* p) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeHost || at.type == hipMemoryTypeManaged;
+}
+
 // One body for the three weight forms: W and scales == nullptr for bf16 weights (K % 8 == 0), (q, scales) for an MXFP8 (mx == 8) or
-// MXFP4 (mx == 4) copy (K % 32 == 0).
+// MXFP4 (mx == 4) copy (K % 32 == 0).  More than 32 rows: the wide kernel (kernels_gemv_rows_wide.hip), one pass over the weights.
 static int gemv_rows_op(int mx, const void* W, const uint32_t* scales, const void* x, void* y, int32_t R, int32_t N, int32_t K, int32_t epi,
                         const void* residual, float* logits, uint32_t* argmax_out, void* stream) {
   const int kmul = mx ? 32 : 8;
-  if (!W || (mx && !scales) || !x || R < 1 || R > 32 || N < 1 || K < kmul || K % kmul || epi < 0 || epi > 3 || (epi == 1 && (!residual || !y)) ||
+  if (!W || (mx && !scales) || !x || R < 1 || R > GEMV_ROWS_WIDE_MAX || N < 1 || K < kmul || K % kmul || epi < 0 || epi > 3 || (epi == 1 && (!residual || !y)) ||
       ((epi == 0 || epi == 2) && !y) || (epi == 2 && N % 32) || (epi == 3 && (!logits || !argmax_out))) {
-    if (!mx) set_error("gemv_rows: bad arguments (1 <= R <= 32, K % 8 == 0, epi 0..3 with its outputs; epi 2 needs N % 32 == 0)");
+    if (!mx) set_error("gemv_rows: bad arguments (1 <= R <= 128, K % 8 == 0, epi 0..3 with its outputs; epi 2 needs N % 32 == 0)");
     else set_error(std::string("gemv_rows_mxfp") + (mx == 8 ? "8" : "4") +
-                   ": bad arguments (q, scales, 1 <= R <= 32, K % 32 == 0, epi 0..3 with its outputs; epi 2 needs N % 32 == 0)");
+                   ": bad arguments (q, scales, 1 <= R <= 128, K % 32 == 0, epi 0..3 with its outputs; epi 2 needs N % 32 == 0)");
     return AHA_ERR_INVALID;
   }
+  for (const void* p : {W, (const void*)scales, x, (const void*)y, residual, (const void*)logits, (const void*)argmax_out})
+    if (p && !device_reachable(p)) {
+      set_error(std::string(mx ? (mx == 8 ? "gemv_rows_mxfp8" : "gemv_rows_mxfp4") : "gemv_rows") +
+                ": bad arguments (a pointer is not device, pinned or managed memory)");
+      return AHA_ERR_INVALID;
+    }
   hipStream_t st = (hipStream_t)stream;
   const int tiles = gemv_rows_num_tiles(N);
   float *ws = nullptr, *bm = nullptr;
@@ -975,7 +992,11 @@ static int gemv_rows_op(int mx, const void* W, const uint32_t* scales, const voi
   a.y = y; a.residual = residual; a.ldy = epi == 2 ? N / 2 : N;
   a.y_f32 = logits; a.ldf = N; a.blk_max = bm; a.blk_idx = bi;
   const GemvEpi e = epi == 0 ? GEMV_STORE : epi == 1 ? GEMV_RESIDUAL : epi == 2 ? GEMV_SILU_MUL : GEMV_LOGITS;
-  if (mx == 8) launch_gemv_rows_mxfp8(a, W, scales, e, st);
+  if (R > 32) {
+    if (mx == 8) launch_gemv_rows_wide_mxfp8(a, W, scales, e, st);
+    else if (mx == 4) launch_gemv_rows_wide_mxfp4(a, W, scales, e, st);
+    else launch_gemv_rows_wide(a, e, st);
+  } else if (mx == 8) launch_gemv_rows_mxfp8(a, W, scales, e, st);
   else if (mx == 4) launch_gemv_rows_mxfp4(a, W, scales, e, st);
   else launch_gemv_rows(a, e, st);
   if (epi == 3) launch_argmax_rows(bm, bi, tiles, R, argmax_out, st);
@@ -1131,6 +1152,19 @@ int aha_hip_debug_fp8_single(aha_model* m, int on) {
   return AHA_OK;
 }
 
+int aha_hip_debug_rows_wide(aha_model* m, int on) {
+  if (!m) {
+    set_error("debug_rows_wide: null model");
+    return AHA_ERR_INVALID;
+  }
+  if (on < 0 || on > 2) {
+    set_error("debug_rows_wide: on must be 0 (groups of 32), 1 (by plan) or 2 (wherever a step has more than 32 rows)");
+    return AHA_ERR_INVALID;
+  }
+  m->rows_wide = on;
+  return AHA_OK;
+}
+
 int aha_hip_debug_pk13_single(aha_model* m, int on) {
   if (!m) {
     set_error("debug_pk13_single: null model");
@@ -1236,6 +1270,20 @@ int aha_hip_debug_plan_gemv_rows(int32_t N, int32_t K, int32_t* cw, int32_t* nks
   int c, s;
   gemv_rows_plan(N, K, &c, &s);
   *cw = c; *nks = s;
+  return AHA_OK;
+}
+
+int aha_hip_debug_plan_gemv_rows_wide(int32_t N, int32_t K, int32_t R, int32_t form, int32_t* rows_per_pass, int32_t* cw, int32_t* nks) {
+  if (!rows_per_pass || N < 1 || K < 8 || K % 8 || R < 1 || R > GEMV_ROWS_WIDE_MAX || form < 0 || form > 2 || (form && K % 32)) {
+    set_error("debug_plan_gemv_rows_wide: bad argument (rows_per_pass not null, N >= 1, K a positive multiple of 8 (an MX form: of 32), "
+              "1 <= R <= 128, form 0 bf16 / 1 mxfp8 / 2 mxfp4)");
+    return AHA_ERR_INVALID;
+  }
+  int c, s;
+  gemv_rows_plan(N, K, &c, &s);
+  *rows_per_pass = gemv_rows_wide_plan(N, K, R, form);
+  if (cw) *cw = c;
+  if (nks) *nks = s;
   return AHA_OK;
 }
 

@@ -439,6 +439,15 @@ void debug_plan_gemv_pk13(int N, int K, GemvEpi epi, bool has_norm, int* out5); 
 void gemv_rows_plan(int N, int K, int* chunks_per_wave, int* k_splits);
 int gemv_rows_num_tiles(int N);
 size_t gemv_rows_ws_floats(int R, int N, int K);
+// 33 .. 128 rows in one pass over the weights (kernels_gemv_rows_wide.hip, gemv_rows_wide_body.h): launch_gemv_rows and its MX twins for
+// 1 <= a.R <= 128, every output bit what the same rows give in launches of at most 32 (the same gemv_rows_plan, k permutation, MFMA chain
+// and LDS reduction; the same merge launch).  a.ws: gemv_rows_ws_floats(a.R, N, K).  gemv_rows_wide_plan: the rows one pass of a step of R
+// rows takes over a matrix (N, K) in form 0 bf16 / 1 MXFP8 / 2 MXFP4 -- 32 (launch_gemv_rows*), 64 or 128 (the wide launches).
+constexpr int GEMV_ROWS_WIDE_MAX = 128;
+int gemv_rows_wide_plan(int N, int K, int R, int form);
+void launch_gemv_rows_wide(const GemvRowsArgs& a, GemvEpi epi, hipStream_t st);
+void launch_gemv_rows_wide_mxfp8(const GemvRowsArgs& a, const void* q, const uint32_t* scales, GemvEpi epi, hipStream_t st);
+void launch_gemv_rows_wide_mxfp4(const GemvRowsArgs& a, const void* q, const uint32_t* scales, GemvEpi epi, hipStream_t st);
 void launch_argmax_rows(const float* blk_max, const uint32_t* blk_idx, int ntiles, int rows, uint32_t* out, hipStream_t st);
 
 // Per-step row table of the batched decode, GEN_ROW_WORDS int32 per active row

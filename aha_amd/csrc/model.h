@@ -100,6 +100,8 @@ struct aha_model {
   bool fp8_rows = true;      // aha_hip_debug_fp8_rows: false = the bf16 matvec on W' although a copy (of either format) exists
   int fp8_single = 1;        // aha_hip_debug_fp8_single, the single-sequence matvec (enqueue_decode_step, enqueue_lm_head): 0 = bf16 on W',
                              // 1 = the FP8 kernel where the plan takes the shape (gemv_mxfp8_by_plan), 2 = wherever a copy exists; MXFP8 models only
+  int rows_wide = 1;         // aha_hip_debug_rows_wide, the batched matvec of a step of more than 32 rows (gemv_rows_groups): 0 = groups of 32,
+                             // 1 = passes of gemv_rows_wide_plan's width, 2 = the wide kernel wherever rows > 32; the bits are the same
   // Exact 13-bit copies of the four layer matrices and lm_head, made when the model is created (model_pack_weights; a bf16 model only:
   // aha_hip_model_quantize_weights frees them).  pk13_single (aha_hip_debug_pk13_single): 0 = the bf16 kernel, 1 = the packed kernel where
   // the plan takes the shape (gemv_pk13_by_plan), 2 = wherever a copy exists

@@ -2719,29 +2719,48 @@ struct DevBufs {   // per-call device / pinned scratch, freed after the stream h
 };
 }  // namespace
 
-constexpr int GEN_ROW_GROUP = 32;   // rows of one gemv_rows launch: larger batches stream the weights once per group
+constexpr int GEN_ROW_GROUP = 32;   // rows of one gemv_rows_kernel launch, and the unit of a draft-and-verify step's row budget
 
-// y[rows] = epi(x[rows] . W^T) in groups of GEN_ROW_GROUP rows.  For GEMV_LOGITS, y_f32 / blk partials are (rows, ldf) / (rows, tiles).
+// Rows of one pass over the weights of (N, K) in `form` (0 bf16, 1 MXFP8, 2 MXFP4) for a step of `rows` rows: GEN_ROW_GROUP (the 32-row
+// kernel, the weights streamed once per group) or 64 / 128 (gemv_rows_wide_kernel, once per pass), by aha_hip_debug_rows_wide.
+static int gen_rows_per_pass(const aha_model* m, int N, int K, int rows, int form) {
+  if (rows <= GEN_ROW_GROUP || m->rows_wide == 0) return GEN_ROW_GROUP;
+  if (m->rows_wide == 1) return gemv_rows_wide_plan(N, K, rows, form);
+  return rows <= 64 ? 64 : GEMV_ROWS_WIDE_MAX;
+}
+
+// y[rows] = epi(x[rows] . W^T) in passes of gen_rows_per_pass rows.  For GEMV_LOGITS, y_f32 / blk partials are (rows, ldf) / (rows, tiles).
 // wq: the MXFP8 or MXFP4 copy of g.W (model_quantize_weights, m->wq_format), streamed in its place when it exists -- the same bits at
-// 1 + 1/32 or 1/2 + 1/32 bytes per weight (profile classes gemv_rows_fp8, gemv_rows_fp4).
+// 1 + 1/32 or 1/2 + 1/32 bytes per weight (profile classes gemv_rows_fp8, gemv_rows_fp4).  A pass of more than 32 rows is the wide kernel
+// (classes gemv_rows_wide, gemv_rows_wide_fp8, gemv_rows_wide_fp4): the same bits again, row by row.
 static void gemv_rows_groups(aha_model* m, GemvRowsArgs g, GemvEpi epi, int rows, float* ws, const WQuant* wq = nullptr) {
   const int tiles = gemv_rows_num_tiles(g.N);
   const bool copy = wq && wq->q && m->fp8_rows;
   const bool fp8 = copy && m->wq_format == AHA_WQ_MXFP8_E4M3, fp4 = copy && m->wq_format == AHA_WQ_MXFP4_E2M1;
   const double wbytes = (double)g.N * g.K * (fp8 ? 1.03125 : fp4 ? 0.53125 : 2.0);
-  for (int r0 = 0; r0 < rows; r0 += GEN_ROW_GROUP) {
+  for (int r0 = 0; r0 < rows;) {
+    // planned for the rows that are left: a tail of at most 32 rows is a launch of the 32-row kernel
+    const int pass = gen_rows_per_pass(m, g.N, g.K, rows - r0, fp8 ? 1 : fp4 ? 2 : 0);
     GemvRowsArgs a = g;
-    a.R = std::min(GEN_ROW_GROUP, rows - r0);
+    a.R = std::min(pass, rows - r0);
     a.x = (const bf16_t*)g.x + (int64_t)r0 * g.ldx;
     if (g.y) a.y = (bf16_t*)g.y + (int64_t)r0 * g.ldy;
     if (g.residual) a.residual = (const bf16_t*)g.residual + (int64_t)r0 * g.ldy;
     if (g.y_f32) a.y_f32 = g.y_f32 + (int64_t)r0 * g.ldf;
     if (g.blk_max) a.blk_max = g.blk_max + (int64_t)r0 * tiles, a.blk_idx = g.blk_idx + (int64_t)r0 * tiles;
     a.ws = ws;
-    ProfScope ps(m, fp8 ? "gemv_rows_fp8" : fp4 ? "gemv_rows_fp4" : "gemv_rows", wbytes + (double)a.R * (g.K + g.N) * 2, 2.0 * a.R * g.N * g.K);
-    if (fp8) launch_gemv_rows_mxfp8(a, wq->q, wq->scales, epi, m->stream);
+    const bool wide = a.R > GEN_ROW_GROUP;
+    const char* cls = wide ? (fp8 ? "gemv_rows_wide_fp8" : fp4 ? "gemv_rows_wide_fp4" : "gemv_rows_wide")
+                           : (fp8 ? "gemv_rows_fp8" : fp4 ? "gemv_rows_fp4" : "gemv_rows");
+    ProfScope ps(m, cls, wbytes + (double)a.R * (g.K + g.N) * 2, 2.0 * a.R * g.N * g.K);
+    if (wide) {
+      if (fp8) launch_gemv_rows_wide_mxfp8(a, wq->q, wq->scales, epi, m->stream);
+      else if (fp4) launch_gemv_rows_wide_mxfp4(a, wq->q, wq->scales, epi, m->stream);
+      else launch_gemv_rows_wide(a, epi, m->stream);
+    } else if (fp8) launch_gemv_rows_mxfp8(a, wq->q, wq->scales, epi, m->stream);
     else if (fp4) launch_gemv_rows_mxfp4(a, wq->q, wq->scales, epi, m->stream);
     else launch_gemv_rows(a, epi, m->stream);
+    r0 += a.R;
   }
 }
 
@@ -2920,7 +2939,7 @@ static int gen_call_alloc(aha_model* m, DevBufs& bufs, GenCall& gc, size_t max_p
   const size_t tab_words = (size_t)n * GEN_ROW_WORDS + (size_t)gc.n * gc.seq_words;
   size_t ws = 0;
   const int shapes[5][2] = {{nq + 2 * nkv, H}, {H, nq}, {2 * I, H}, {H, I}, {V, H}};
-  for (auto& sh : shapes) ws = std::max(ws, gemv_rows_ws_floats(std::min(n, GEN_ROW_GROUP), sh[0], sh[1]));
+  for (auto& sh : shapes) ws = std::max(ws, gemv_rows_ws_floats(std::min(n, GEMV_ROWS_WIDE_MAX), sh[0], sh[1]));   // the largest pass
   const int tiles = gemv_rows_num_tiles(V);
   int rc;
   if ((rc = bufs.alloc(&gc.ws, ws)) || (rc = bufs.alloc((bf16_t**)&gc.x, (size_t)n * H)) || (rc = bufs.alloc((bf16_t**)&gc.h, (size_t)n * H)) ||

@@ -648,6 +648,12 @@ class HipInferenceModel:
         launches: "gemv_fp8"."""
         check(lib().aha_hip_debug_fp8_single(self.handle, int(on)))
 
+    def debug_rows_wide(self, on=True) -> None:
+        """Test hook: the batched decode matvec of a step of more than 32 rows.  True / 1 (the default): passes of the planned width
+        (ops.plan_gemv_rows_wide) on the wide kernel; 2: the wide kernel wherever more than 32 rows are left; False / 0: groups of 32.  The
+        same bits in all three.  Profile classes of the wide launches: "gemv_rows_wide", "gemv_rows_wide_fp8", "gemv_rows_wide_fp4"."""
+        check(lib().aha_hip_debug_rows_wide(self.handle, int(on)))
+
     def debug_pk13_single(self, on=True) -> None:
         """The switch of the single-sequence decode matvec for the exact 13-bit weight copies made when the model was created.  True / 1 (the
         default): the packed kernel on the matrices whose shape its plan takes; 2: on every matrix with a copy; False / 0: the bf16 kernel.

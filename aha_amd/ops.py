@@ -416,7 +416,8 @@ def _gemv_rows_outputs(R: int, N: int, epi: int, device, out: Optional[torch.Ten
 
 def gemv_rows(W: torch.Tensor, x: torch.Tensor, epi: int = GEMV_ROWS_STORE, residual: Optional[torch.Tensor] = None,
               out: Optional[torch.Tensor] = None):
-    """y[R, N] = x[R, K] . W[N, K]^T for 1 <= R <= 32, weights streamed once.  epi STORE / RESIDUAL -> (R, N) bf16 (`out` may be the
+    """y[R, N] = x[R, K] . W[N, K]^T for 1 <= R <= 128, weights streamed once (above 32 rows by the wide kernel, each row
+    with the bits a call of at most 32 rows gives it).  epi STORE / RESIDUAL -> (R, N) bf16 (`out` may be the
     residual itself); SILU_MUL (W in the 16-row gate / up block layout) -> (R, N/2) bf16; LOGITS -> ((R, N) f32 logits, (R,) int64 argmax)."""
     _chk(W, x, residual, out)
     N, K = W.shape
@@ -544,6 +545,18 @@ def plan_gemv(N: int, K: int, epi: int = GEMV_ROWS_STORE, has_norm: bool = False
     r, u, g, f = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
     check(lib().aha_hip_debug_plan_gemv(N, K, epi, int(has_norm), C.byref(r), C.byref(u), C.byref(g), C.byref(f)))
     return r.value, u.value, g.value, f.value
+
+
+GEMV_ROWS_FORMS = {"bf16": 0, "mxfp8": 1, "mxfp4": 2}
+
+
+def plan_gemv_rows_wide(N: int, K: int, R: int, form="bf16"):
+    """Host only: (rows_per_pass, cw, nks) of a batched decode step of R rows over a matrix (N, K) held as `form` ("bf16" / "mxfp8" /
+    "mxfp4" or 0 / 1 / 2): 32 = groups on gemv_rows_kernel, 64 / 128 = one gemv_rows_wide_kernel pass (aha_hip_debug_plan_gemv_rows_wide);
+    cw, nks are plan_gemv_rows(N, K)'s for every R."""
+    rpp, cw, nks = C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib().aha_hip_debug_plan_gemv_rows_wide(N, K, R, GEMV_ROWS_FORMS.get(form, form), C.byref(rpp), C.byref(cw), C.byref(nks)))
+    return rpp.value, cw.value, nks.value
 
 
 def plan_gemv_rows(N: int, K: int):

@@ -811,6 +811,13 @@ int aha_hip_debug_fp8_single(aha_model* m, int on);
  * the FP4 launches: gemv_fp4, at 0.53125 bytes per weight.  Sharded models have no copies.  AHA_ERR_INVALID: a null model or another
  * value.  An MXFP8 model ignores it. */
 int aha_hip_debug_fp4_single(aha_model* m, int on);
+/* The batched decode matvec of a step of more than 32 rows (aha_hip_generate_batch*, the engine, draft-and-verify steps).  on = 1 (the
+ * default): passes of the width aha_hip_debug_plan_gemv_rows_wide names -- gemv_rows_wide_kernel, every weight byte from HBM once per
+ * pass of up to 128 rows, where it measured faster than groups of 32; 2: the wide kernel wherever rows are left over 32; 0: groups of 32
+ * on gemv_rows_kernel, the weights streamed once per group.  The bits are the same in all three, for all three weight forms.  Profile
+ * classes of the wide launches: gemv_rows_wide, gemv_rows_wide_fp8, gemv_rows_wide_fp4.  Reads no environment variable.
+ * AHA_ERR_INVALID: a null model or another value. */
+int aha_hip_debug_rows_wide(aha_model* m, int on);
 /* Exact 13-bit weight copies.  When a model is created unsharded, each of the four layer matrices and lm_head gets a copy that holds
  * every bf16 weight exactly in 13 bits (aha_hip_pack_pk13 has the format) if the matrix has at least 2^24 elements, K is a multiple of
  * 4096, every weight is finite, at most 16 rows hold a weight below the format's window (those rows are then read from the bf16 matrix,
@@ -912,6 +919,12 @@ int aha_hip_debug_plan_gemv(int32_t N, int32_t K, int32_t epi, int32_t has_norm,
  * and K columns, by the function the launch itself calls: *cw chunks (128 k) per wave, 1 | 2, and *nks K splits (the f32 slabs the merge
  * sums).  With the row tiles (2 above 16 rows of x) it names gemv_rows_kernel<cw, 1 | 2> and its MX twins.  K a multiple of 8. */
 int aha_hip_debug_plan_gemv_rows(int32_t N, int32_t K, int32_t* cw, int32_t* nks);
+/* Host only: the rows one pass over the weights takes when a batched decode step of R rows (1 <= R <= 128) multiplies a matrix (N, K) held
+ * in form 0 bf16 / 1 MXFP8 / 2 MXFP4, by the function the model's step calls (aha_hip_debug_rows_wide at 1): *rows_per_pass = 32 (groups
+ * on gemv_rows_kernel<cw, 1 | 2>), 64 or 128 (one gemv_rows_wide_kernel<cw, 4 | 8> launch; profiles/gemv_rows_wide.md has the rule).
+ * *cw and *nks (may be NULL) are aha_hip_debug_plan_gemv_rows(N, K)'s for every R and form: how a row is summed never depends on the rows
+ * beside it.  K a multiple of 8, of 32 for an MX form.  AHA_ERR_INVALID otherwise. */
+int aha_hip_debug_plan_gemv_rows_wide(int32_t N, int32_t K, int32_t R, int32_t form, int32_t* rows_per_pass, int32_t* cw, int32_t* nks);
 /* Test entry of that epilogue, which only a sharded model's row-parallel projections launch: y_f32[n] = sum_k h[k] * W[n, k], f32, not
  * rounded; h = x, or RMSNorm(x; norm_w, eps) rounded to bf16 when norm_w is not NULL.  W (N, K) bf16, x (K) bf16, device pointers. */
 int aha_hip_debug_gemv_partial_f32(const void* W, const void* x, float* y_f32, int32_t N, int32_t K, const void* norm_w, float eps,
@@ -947,7 +960,9 @@ int aha_hip_qknorm_rope(const void* qkv, const void* q_norm_w, const void* k_nor
 int aha_hip_attn_decode(const void* q, const void* k, const void* v, void* o, int32_t nh, int32_t kvh, int32_t d,
                         int32_t L, float scale, void* stream);
 /* Batched decode (aha_hip_generate_batch's kernels), op level.
- * aha_hip_gemv_rows: y[R, N] = x[R, K] . W[N, K]^T for 1 <= R <= 32, the weights read once (the step's projections of
+ * aha_hip_gemv_rows: y[R, N] = x[R, K] . W[N, K]^T for 1 <= R <= 128, the weights read once -- up to 32 rows by gemv_rows_kernel, 33 .. 128
+ * by gemv_rows_wide_kernel, which gives every row the bits it has in a call of at most 32 rows; the same for the two MX entries below.
+ * The pointers must be device, pinned or managed memory (AHA_ERR_INVALID otherwise).  (The step's projections of
  * /root/reference/src/models/qwen3/model.rs:79-86 for R sequences).  x (R, K) bf16, K % 8 == 0.  epi 0: y (R, N) bf16; 1: y = residual +
  * Linear (both bf16 (R, N), may alias); 2: SiLU(gate) * up with W in the 16-row gate / up block layout (N = 2I), y (R, I) bf16; 3: logits
  * (R, N) f32 and argmax_out (R) u32 (device), the first maximal index.  Each output row depends only on its own input row. */

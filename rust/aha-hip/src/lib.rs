@@ -647,6 +647,7 @@ pub mod sys {
         pub fn aha_hip_model_weight_format(m: *const AhaModel, format: *mut i32, flags: *mut u32) -> i32;
         pub fn aha_hip_debug_fp8_rows(m: *mut AhaModel, on: i32) -> i32;
         pub fn aha_hip_debug_fp8_single(m: *mut AhaModel, on: i32) -> i32;
+        pub fn aha_hip_debug_rows_wide(m: *mut AhaModel, on: i32) -> i32;
         pub fn aha_hip_debug_plan_gemv_mxfp8(
             n: i32,
             k: i32,
@@ -669,6 +670,15 @@ pub mod sys {
             form: *mut i32,
         ) -> i32;
         pub fn aha_hip_debug_plan_gemv_rows(n: i32, k: i32, cw: *mut i32, nks: *mut i32) -> i32;
+        pub fn aha_hip_debug_plan_gemv_rows_wide(
+            n: i32,
+            k: i32,
+            r: i32,
+            form: i32,
+            rows_per_pass: *mut i32,
+            cw: *mut i32,
+            nks: *mut i32,
+        ) -> i32;
         pub fn aha_hip_debug_gemv_partial_f32(
             w: *const std::ffi::c_void,
             x: *const std::ffi::c_void,
