@@ -20,6 +20,7 @@ AHA_SAMPLE_NEED_LOGITS = 1
 AHA_WQ_NONE, AHA_WQ_MXFP8_E4M3, AHA_WQ_MXFP4_E2M1 = 0, 1, 2
 AHA_WQ_LM_HEAD = 1
 AHA_WQ_PREFILL = 2
+AHA_KV_BF16, AHA_KV_E4M3 = 0, 1
 
 
 class SamplingParams(C.Structure):
@@ -274,6 +275,8 @@ SIGNATURES = {
     "aha_hip_gemv_rows_mxfp4": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "aha_hip_model_quantize_weights": (C.c_int, [_P, C.c_int32, C.c_uint32]),
     "aha_hip_model_weight_format": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]),
+    "aha_hip_model_set_kv_format": (C.c_int, [_P, C.c_int32]),
+    "aha_hip_model_kv_format": (C.c_int, [_P]),
     "aha_hip_debug_fp8_rows": (C.c_int, [_P, C.c_int]),
     "aha_hip_debug_fp8_single": (C.c_int, [_P, C.c_int]),
     "aha_hip_debug_rows_wide": (C.c_int, [_P, C.c_int]),
@@ -305,6 +308,10 @@ SIGNATURES = {
     "aha_hip_debug_attn_decode_fused": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "aha_hip_debug_attn_decode_rows": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, C.c_int32,
                                                  _P]),
+    "aha_hip_kv8_page_bytes": (C.c_int64, [C.c_int32]),
+    "aha_hip_quantize_kv_pages": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
+    "aha_hip_attn_decode_batch_kv8": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, C.c_int32,
+                                                _P]),
     "aha_hip_debug_spec_accept": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
     "aha_hip_config_parse": (C.c_int, [C.c_char_p, _P]),
     "aha_hip_config_torch_dtype": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),

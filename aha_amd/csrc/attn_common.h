@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "kernels.h"
+#include "kv8.h"
 
 namespace aha {
 
@@ -183,6 +184,56 @@ __device__ __forceinline__ void softmax_tile(f32x4_t (&st)[4], float scale, Vali
   m = m_new;
 #endif
   softmax_probs(st, m2, alpha, l, pf);
+}
+
+// The same over a KV8 page (kv8.h), whose MFMA operands are the raw E4M3 code values.  ks / vs: the 16 K / V scale bytes of the lane
+// group's tokens, byte r of dword sub = token sub*16 + G*4 + r (common.h kv8_scale_byte).
+//   K: st * 2^ek is the f32 accumulator the dequantised k would have given (a power of two commutes with every rounding of the chain),
+//      one multiply per score where a scale on the operand would be one per converted pair;
+//   V: a lane's V fragment holds eight tokens, so the scale cannot ride the operand: p * 2^ev is formed in f32 and THEN rounded to the
+//      bf16 P^T operand -- the bits of bf16(p) * 2^ev -- and the MFMA's p' . qv is p . (qv * 2^ev).  The row sum keeps the plain p.
+// Plain f32 instructions, no packed forms (build.py NO_PK_F32).
+template <typename ValidFn>
+__device__ __forceinline__ void softmax_tile_kv8(f32x4_t (&st)[4], float scale, const u32x4_t ks, const u32x4_t vs, ValidFn valid, int G,
+                                                 float& m, float& l, float& alpha, bf16x8_t (&pf)[2]) {
+  constexpr float LOG2E = 1.4426950408889634f;
+  float tmax = -INFINITY;
+#pragma unroll
+  for (int sub = 0; sub < 4; ++sub)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float s = st[sub][r] * kv8_scale_f32((ks[sub] >> (8 * r)) & 0xffu) * scale;
+      if (!valid(sub * 16 + G * 4 + r)) s = -INFINITY;
+      st[sub][r] = s;
+      tmax = fmaxf(tmax, s);
+    }
+  tmax = group_max(tmax);
+  const float m_new = fmaxf(m, tmax);
+  const float m_use = (m_new == -INFINITY) ? 0.f : m_new;  // fully masked so far: keep everything at zero
+  alpha = __expf(m - m_use);                               // m = -inf -> 0
+  const float m2 = m_use * LOG2E;
+  m = m_new;
+  float psum = 0.f;
+  uint32_t pk[2][4];
+#pragma unroll
+  for (int sub = 0; sub < 4; ++sub) {
+    float p[4], pv[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      p[r] = __builtin_amdgcn_exp2f(fmaf(st[sub][r], LOG2E, -m2));
+      psum += p[r];
+      // (the byte clamped to 254: a page nobody wrote may hold 0xff = Inf, and a masked token's p = 0 times Inf would be a NaN operand)
+      pv[r] = p[r] * kv8_scale_f32(min((vs[sub] >> (8 * r)) & 0xffu, 254u));
+    }
+    pk[sub >> 1][(sub & 1) * 2 + 0] = pack_bf(pv[0], pv[1]);
+    pk[sub >> 1][(sub & 1) * 2 + 1] = pack_bf(pv[2], pv[3]);
+  }
+  l = l * alpha + psum;
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    u32x4_t u = {pk[kk][0], pk[kk][1], pk[kk][2], pk[kk][3]};
+    pf[kk] = as_frag(u);
+  }
 }
 
 }  // namespace aha

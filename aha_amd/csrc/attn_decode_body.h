@@ -57,9 +57,16 @@ __device__ __forceinline__ float split_sum16(const float (&v)[16]) {
 // the append's included, is scalar arithmetic and the first K/V request has no load and no wait in front of it.  LINEAR = false: the
 // addresses come from the page table (a.kv.page_ptrs), one vector load whose return the first K/V request has to wait for -- and,
 // returns being in order, for every prologue input requested before it.
-template <bool APPEND = true, bool LINEAR = false>
+// KV8 = true (kernels_attn_kv8.hip): the pages are KV8 pages (common.h "KV8 page layout", a.kv.page_ptrs / layer_off address them): half
+// the bytes per page plus one 16-byte piece of K and of V scale bytes per lane; the E4M3 bytes become the bf16 operands of the SAME MFMA
+// sequence in registers (kv8_frag) and the block scales ride the scores and the probabilities (softmax_tile_kv8).  The new token's roped
+// k and raw v are quantised behind the prologue's barrier, their codes and scale bytes are what the append stores, and ksn / vsn get the
+// DEQUANTISED values back: the token is scored and weighted in its own step from what every later step reads from the page.  The
+// request structure is the bf16 form's.  KV8 = false compiles to the instructions it compiled to before the parameter existed.
+template <bool APPEND = true, bool LINEAR = false, bool KV8 = false>
 __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs& a, char* smem, const int kvhd, const int split,
                                                        const int nsplit) {
+  static_assert(!(KV8 && LINEAR), "the single-sequence linear form has no KV8 instantiation");
   constexpr int NW = ATTN_DECODE_NW, NT = NW * 64;
   bf16_t* qs = reinterpret_cast<bf16_t*>(smem);                 // [16][128]
   bf16_t* ksn = qs + 16 * 128;                                  // [128]
@@ -105,12 +112,28 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
   const bf16_t vnew = qkv[(int64_t)(a.nh + a.kvh + kvhd) * 128 + (tid & 127)];   // waves 2, 3: a second copy, not stored
 
   u32x4_t kf[4][4], vf[8][2];
+  u32x4_t kf8[4][2], vf8[8], ksc, vsc;   // KV8: fragment pairs (sub, p) / ds and the lane group's 16 K / V scale bytes
   // Addresses: wave-uniform 64-bit base (scalar registers) + ONE 32-bit per-lane offset (lane * 16), the rest immediates:
   // pages are fragment-major (common.h), every load is `global_load_dwordx4 v, v_off, s[base] offset:frag*1024` = 1 KB
   // contiguous per wave instruction.
   typedef const __attribute__((address_space(1))) char* gchar_t;
   const uint32_t l_off = (uint32_t)lane * 16;
+  // KV8 scale bytes: the page's base + ONE more per-lane offset (the head's K scale piece of the lane group; V's is 64 bytes on), no
+  // further scalar address
+  const uint32_t s_off = (uint32_t)(a.kvh * (2 * KV8_HEAD_BYTES) + kvhd * KV8_SCALE_BYTES + G * 16);
   auto load_k = [&](uint64_t base) {
+    if constexpr (KV8) {
+      gchar_t kb = reinterpret_cast<gchar_t>(base + (uint64_t)kvhd * KV8_HEAD_BYTES);
+#pragma unroll
+      for (int sub = 0; sub < 4; ++sub)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          kf8[sub][p] = __builtin_nontemporal_load(reinterpret_cast<gptr16_t>(kb + (sub * 2 + p) * 1024 + l_off));
+          __builtin_amdgcn_sched_barrier(0);   // issue order = consumption order, as below
+        }
+      ksc = __builtin_nontemporal_load(reinterpret_cast<gptr16_t>(reinterpret_cast<gchar_t>(base) + s_off));   // wanted by the softmax, behind the last MFMA
+      return;
+    }
     gchar_t kb = reinterpret_cast<gchar_t>(base + (uint64_t)kvhd * KV_PAGE_TOKENS * 256);
 #pragma unroll
     for (int sub = 0; sub < 4; ++sub)
@@ -123,6 +146,13 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
       }
   };
   auto load_v = [&](uint64_t base) {
+    if constexpr (KV8) {
+      vsc = __builtin_nontemporal_load(reinterpret_cast<gptr16_t>(reinterpret_cast<gchar_t>(base) + KV_PAGE_TOKENS + s_off));   // wanted by the softmax, ahead of the fragments
+      gchar_t vb = reinterpret_cast<gchar_t>(base + (uint64_t)(a.kvh + kvhd) * KV8_HEAD_BYTES);
+#pragma unroll
+      for (int ds = 0; ds < 8; ++ds) vf8[ds] = __builtin_nontemporal_load(reinterpret_cast<gptr16_t>(vb + ds * 1024 + l_off));
+      return;
+    }
     gchar_t vb = reinterpret_cast<gchar_t>(base + (uint64_t)a.kvh * KV_PAGE_TOKENS * 256 + (uint64_t)kvhd * 128 * (KV_PAGE_TOKENS * 2));
 #pragma unroll
     for (int ds = 0; ds < 8; ++ds)
@@ -187,7 +217,31 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
     }
   }
   stamp(1);
-  if (APPEND && split == 0) {  // append (k roped, v raw) for the following steps
+  if constexpr (KV8) {
+    if (split == 0) {   // block-uniform: the block that appends, and whose unit 0 takes the new token from LDS
+      if (wave < 2) {   // wave 0: the roped k, wave 1: the raw v; a lane holds dims lane and lane + 64
+        typedef __attribute__((address_space(1))) uint8_t* gu8_t;
+        bf16_t* xs = wave == 0 ? ksn : vsn;
+        const uint32_t b0 = xs[lane], b1 = xs[lane + 64];
+        const int e = kv8_block_exp(kv8_wave_max(max(kv8_amax_term(b0), kv8_amax_term(b1))));
+        const float inv = mx_exp2(-e);
+        const uint32_t c0 = kv8_code(b0, inv), c1 = kv8_code(b1, inv);
+        xs[lane] = kv8_dequant(c0, e);
+        xs[lane + 64] = kv8_dequant(c1, e);
+        if (APPEND) {
+          const int pg = slot_new / KV_PAGE_TOKENS, t = slot_new % KV_PAGE_TOKENS;
+          const uint64_t base = (uint64_t)(a.kv.page_ptrs[pg] + a.kv.layer_off);
+          gu8_t cd = reinterpret_cast<gu8_t>(base + (uint64_t)(wave * a.kvh + kvhd) * KV8_HEAD_BYTES);
+          cd[wave == 0 ? kv8_kpage_byte(t, lane) : kv8_vpage_byte(t, lane)] = (uint8_t)c0;
+          cd[wave == 0 ? kv8_kpage_byte(t, lane + 64) : kv8_vpage_byte(t, lane + 64)] = (uint8_t)c1;
+          gu8_t sd = reinterpret_cast<gu8_t>(base + (uint64_t)a.kvh * (2 * KV8_HEAD_BYTES) + (uint64_t)kvhd * KV8_SCALE_BYTES + wave * KV_PAGE_TOKENS);
+          if (lane == 0) sd[kv8_scale_byte(t)] = (uint8_t)(e + 127);
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (!KV8 && APPEND && split == 0) {  // append (k roped, v raw) for the following steps
     // global address space spelled out: a flat store here would make every later wait in the kernel a vmcnt(0)
     typedef __attribute__((address_space(1))) bf16_t* gbf_t;
     const int pg = slot_new / KV_PAGE_TOKENS, t = slot_new % KV_PAGE_TOKENS;
@@ -228,20 +282,29 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
     for (int sub = 0; sub < 4; ++sub) {
       st[sub] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int k4 = 0; k4 < 4; ++k4) st[sub] = mfma16(as_frag(kf[sub][k4]), qf[k4], st[sub]);
+      for (int k4 = 0; k4 < 4; ++k4) {
+        if constexpr (KV8) st[sub] = mfma16(kv8_frag(kf8[sub][k4 >> 1][(k4 & 1) * 2], kf8[sub][k4 >> 1][(k4 & 1) * 2 + 1]), qf[k4], st[sub]);
+        else st[sub] = mfma16(as_frag(kf[sub][k4]), qf[k4], st[sub]);
+      }
     }
+    u32x4_t ks_cur = {0u, 0u, 0u, 0u};
+    if constexpr (KV8) ks_cur = ksc;   // this page's K scales: the request below replaces ksc with the next page's
     __builtin_amdgcn_sched_barrier(0);
     if (MORE) load_k(nb);   // K of the unit's next page: in flight during softmax + P.V of this one
     __builtin_amdgcn_sched_barrier(0);
     float alpha;
     bf16x8_t pf[2];
     const int t0 = page * KV_PAGE_TOKENS;
-    softmax_tile(st, a.scale, [&](int t) { return t0 + t < L_old; }, G, m, l, alpha, pf);
+    if constexpr (KV8) softmax_tile_kv8(st, a.scale, ks_cur, vsc, [&](int t) { return t0 + t < L_old; }, G, m, l, alpha, pf);
+    else softmax_tile(st, a.scale, [&](int t) { return t0 + t < L_old; }, G, m, l, alpha, pf);
 #pragma unroll
     for (int ds = 0; ds < 8; ++ds) {
       o[ds] *= alpha;
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) o[ds] = mfma16(as_frag(vf[ds][kk]), pf[kk], o[ds]);
+      for (int kk = 0; kk < 2; ++kk) {
+        if constexpr (KV8) o[ds] = mfma16(kv8_frag(vf8[ds][kk * 2], vf8[ds][kk * 2 + 1]), pf[kk], o[ds]);
+        else o[ds] = mfma16(as_frag(vf[ds][kk]), pf[kk], o[ds]);
+      }
     }
     __builtin_amdgcn_sched_barrier(0);
     if (MORE) load_v(nb);   // V of the next page: in flight during its QK^T and softmax
@@ -368,16 +431,20 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
     // the split index of the loads beyond nsplit and give those a weight of zero.
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(a.part_o, 0, (int)((size_t)nsplit * a.nh * 128 * 4), 0x00020000);
     const uint32_t split_stride = (uint32_t)a.nh * 128 * 4;
+    int ns1 = nsplit - 1;
+    // KV8: the 32 clamped split offsets below as vector values -- hoisted as scalars they do not fit next to what this form keeps in
+    // scalar registers, and the compiler parks them in VGPR lanes
+    if constexpr (KV8) asm volatile("" : "+v"(ns1));
     for (int item = tid; item < g * 32; item += NT) {
       const int head = kvhd * g + (item >> 5);
       float2 ml[16];
 #pragma unroll
-      for (int j = 0; j < 16; ++j) ml[j] = act_ldf2<true>(a.part_ml + ((size_t)min(j, nsplit - 1) * a.nh + head) * 2);
+      for (int j = 0; j < 16; ++j) ml[j] = act_ldf2<true>(a.part_ml + ((size_t)min(j, ns1) * a.nh + head) * 2);
       const uint32_t off = (uint32_t)(head * 128 + (item & 31) * 4) * 4;
       f32x4_t pv[16];
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
-        const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + (uint32_t)min(j, nsplit - 1) * split_stride, 0, 16 /* sc1 */);
+        const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + (uint32_t)min(j, ns1) * split_stride, 0, 16 /* sc1 */);
         pv[j] = f32x4_t{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
       }
       float M = -INFINITY;

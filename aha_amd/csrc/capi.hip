@@ -1120,6 +1120,18 @@ int aha_hip_model_quantize_weights(aha_model* m, int32_t format, uint32_t flags)
   API_GUARD_END
 }
 
+int aha_hip_model_set_kv_format(aha_model* m, int32_t format) {
+  API_GUARD_BEGIN
+  if (!m) {
+    set_error("set_kv_format: null model");
+    return AHA_ERR_INVALID;
+  }
+  return model_set_kv_format(m, format);
+  API_GUARD_END
+}
+
+int aha_hip_model_kv_format(const aha_model* m) { return m ? m->kv_format : -1; }
+
 int aha_hip_model_weight_format(const aha_model* m, int32_t* format, uint32_t* flags) {
   if (!m) {
     set_error("weight_format: null model");
@@ -1803,11 +1815,10 @@ int aha_hip_attn_decode_batch(const void* qkv, const void* q_norm_w, const void*
   API_GUARD_END
 }
 
-int aha_hip_debug_attn_decode_rows(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
-                                   const int32_t* page0, const int32_t* kv_len, int32_t rows, int32_t nh, int32_t kvh, float eps, float scale,
-                                   void* o, int32_t form, void* stream) {
-  API_GUARD_BEGIN
-  const char* who = "debug_attn_decode_rows: ";
+// aha_hip_debug_attn_decode_rows (kv8 = false) and aha_hip_attn_decode_batch_kv8 (true): the same checks, row table and launches
+static int attn_decode_rows_entry(const char* who, bool kv8, const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope,
+                                  const uint64_t* page_ptrs, const int32_t* page0, const int32_t* kv_len, int32_t rows, int32_t nh, int32_t kvh,
+                                  float eps, float scale, void* o, int32_t form, void* stream) {
   auto bad = [&](const std::string& why) {
     set_error(who + why);
     return AHA_ERR_INVALID;
@@ -1832,8 +1843,42 @@ int aha_hip_debug_attn_decode_rows(const void* qkv, const void* q_norm_w, const 
     AHA_HIP_CHECK(hipMemsetAsync(ctr.p, 0, (size_t)rows * kvh * 32 * 4, st));
     b.part_o = (float*)po.p; b.part_ml = (float*)pml.p; b.head_ctr = (unsigned*)ctr.p;
   }
-  if (form != 0) launch_kv_append_rows(b, rows, st);
-  if (form != 2) launch_attn_decode_batch(b, rows, max_split, st, form == 0);
+  if (form != 0) (kv8 ? launch_kv_append_rows_kv8 : launch_kv_append_rows)(b, rows, st);
+  if (form != 2) (kv8 ? launch_attn_decode_batch_kv8 : launch_attn_decode_batch)(b, rows, max_split, st, form == 0);
+  hipError_t err = hipGetLastError();
+  hipStreamSynchronize(st);
+  AHA_HIP_CHECK(err);
+  return AHA_OK;
+}
+
+int aha_hip_debug_attn_decode_rows(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
+                                   const int32_t* page0, const int32_t* kv_len, int32_t rows, int32_t nh, int32_t kvh, float eps, float scale,
+                                   void* o, int32_t form, void* stream) {
+  API_GUARD_BEGIN
+  return attn_decode_rows_entry("debug_attn_decode_rows: ", false, qkv, q_norm_w, k_norm_w, rope, page_ptrs, page0, kv_len, rows, nh, kvh, eps,
+                                scale, o, form, stream);
+  API_GUARD_END
+}
+
+int aha_hip_attn_decode_batch_kv8(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
+                                  const int32_t* page0, const int32_t* kv_len, int32_t rows, int32_t nh, int32_t kvh, float eps, float scale,
+                                  void* o, int32_t form, void* stream) {
+  API_GUARD_BEGIN
+  return attn_decode_rows_entry("attn_decode_batch_kv8: ", true, qkv, q_norm_w, k_norm_w, rope, page_ptrs, page0, kv_len, rows, nh, kvh, eps,
+                                scale, o, form, stream);
+  API_GUARD_END
+}
+
+int64_t aha_hip_kv8_page_bytes(int32_t kvh) { return kvh < 1 ? 0 : kv8_page_bytes(kvh); }
+
+int aha_hip_quantize_kv_pages(const uint64_t* src_page_ptrs, const uint64_t* dst_page_ptrs, int32_t n_pages, int32_t kvh, void* stream) {
+  API_GUARD_BEGIN
+  if (!src_page_ptrs || !dst_page_ptrs || n_pages < 1 || kvh < 1 || kvh > 64) {
+    set_error("quantize_kv_pages: bad arguments (page tables, n_pages >= 1, kvh 1 .. 64)");
+    return AHA_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  launch_kv_pages_quantize(src_page_ptrs, dst_page_ptrs, n_pages, kvh, 1, 0, 0, st);
   hipError_t err = hipGetLastError();
   hipStreamSynchronize(st);
   AHA_HIP_CHECK(err);

@@ -135,4 +135,26 @@ __host__ __device__ __forceinline__ int vpage_elem(int t, int e) {
   return ((((e >> 4) * 2 + (s >> 5)) * 64 + ((s >> 3) & 3) * 16 + (e & 15)) << 3) + (s & 7);
 }
 
+// ---- KV8 page layout: the same fragments in E4M3 bytes, one E8M0 scale byte per (token, kv head) block of 128 dims, K and V each -----
+// One layer's share of a KV8 page: [kvh] K blocks of 8 KB, [kvh] V blocks of 8 KB, [kvh] x (64 K scale bytes | 64 V scale bytes).
+// A fragment is 512 B and a lane's piece 8 bytes; two fragments lie side by side, piece l of the first in bytes 0..7 of the 16-byte
+// piece l of the pair, piece l of the second in bytes 8..15 -- so a wave load is still 16 bytes per lane and 1 KB contiguous:
+//   K pair (sub, p), stored at index sub * 2 + p: fragments (sub, k4 = 2p) | (sub, 2p + 1)
+//   V pair ds, stored at index ds:                fragments (ds, kk = 0) | (ds, 1)
+// Scale bytes of a head: token sub*16 + G*4 + r at byte G*16 + sub*4 + r -- the 16 tokens whose S^T accumulators lane group G holds
+// (attn_common.h softmax_tile) are one 16-byte load.
+constexpr int KV8_HEAD_BYTES = KV_PAGE_TOKENS * 128;                 // one kv head's K (or V) block
+constexpr int KV8_SCALE_BYTES = 2 * KV_PAGE_TOKENS;                  // one kv head's K | V scale bytes
+__host__ __device__ __forceinline__ int64_t kv8_page_bytes(int kvh) { return (int64_t)kvh * (2 * KV8_HEAD_BYTES + KV8_SCALE_BYTES); }
+// Byte index (from the head's block start) of dim e of token slot t:
+__host__ __device__ __forceinline__ int kv8_kpage_byte(int t, int e) {
+  return ((((t >> 4) * 2 + (e >> 6)) * 64 + ((e >> 3) & 3) * 16 + (t & 15)) << 4) + ((e >> 5) & 1) * 8 + (e & 7);
+}
+__host__ __device__ __forceinline__ int kv8_vpage_byte(int t, int e) {
+  const int s = v_slot(t);
+  return (((e >> 4) * 64 + ((s >> 3) & 3) * 16 + (e & 15)) << 4) + (s >> 5) * 8 + (s & 7);
+}
+// Byte index (from the head's K or V scale bytes) of token slot t's scale:
+__host__ __device__ __forceinline__ int kv8_scale_byte(int t) { return ((t >> 2) & 3) * 16 + (t >> 4) * 4 + (t & 3); }
+
 }  // namespace aha

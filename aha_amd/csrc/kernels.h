@@ -487,6 +487,20 @@ void launch_attn_decode_batch(const AttnDecodeBatchArgs& a, int rows, int max_ns
 // Draft-and-verify steps: (k roped, v raw) of every row into slot kv_len - 1 of its sequence, the bits of the fused kernel's own append
 // (reads qkv, k_norm_w, rope, page_ptrs, layer_off, row_tab, nh, kvh, eps of the batch arguments)
 void launch_kv_append_rows(const AttnDecodeBatchArgs& a, int rows, hipStream_t st);
+
+// ---- KV8: the decode attention over an E4M3 KV cache (kernels_attn_kv8.hip; page layout: common.h "KV8 page layout") -----------------
+// One (token, kv head) vector of 128 dims is one block: 128 OCP E4M3 bytes and one E8M0 scale byte, K and V each; exponent and rounding
+// are mxfp8.h's with the maximum taken over the 128 dims, +-Inf and magnitudes from MX_BF16_ABS_LIMIT on saturate to +-448 * 2^120 and
+// NaN becomes the code 0x7f outside the maximum (the activation row quantiser's rule, kernels_gemm_fp8.hip).
+// The same two launches over KV8 pages: a.page_ptrs / a.layer_off address KV8 pages (kv8_page_bytes(kvh) per layer), everything else is
+// as above.  The append stores the new token's codes and scale bytes, and the token is scored and weighted from the DEQUANTISED values in
+// its own step -- what every later step reads from the page.
+void launch_attn_decode_batch_kv8(const AttnDecodeBatchArgs& a, int rows, int max_nsplit_rows, hipStream_t st, bool append = true);
+void launch_kv_append_rows_kv8(const AttnDecodeBatchArgs& a, int rows, hipStream_t st);
+// bf16 pages -> KV8 pages: page p of 0 .. n_pages - 1, layer l of 0 .. n_layers - 1 from src_ptrs[p] + l * src_layer_stride to
+// dst_ptrs[p] + l * dst_layer_stride (all 64 slots, whatever they hold).
+void launch_kv_pages_quantize(const uint64_t* src_ptrs, const uint64_t* dst_ptrs, int n_pages, int kvh, int n_layers, uint64_t src_layer_stride,
+                              uint64_t dst_layer_stride, hipStream_t st);
 // Per sequence s of a draft-and-verify step: seq_tab[s] = {first row, draft rows after it}; out[s] = {emitted count, row whose logits chose
 // the last emitted token, the emitted tokens}: the longest draft prefix the argmax vector confirms, plus the token that follows it
 constexpr int SPEC_MAX_DRAFT = 15;

@@ -133,6 +133,15 @@ struct aha_model {
   size_t cache_len = 0;         // tokens in the cache (== reference kv_cache.dim(2))
   bool scramble_pages = false;
   std::vector<uint64_t> free_pages;
+  // KV8 (aha_hip_model_set_kv_format(AHA_KV_E4M3); kernels.h "KV8"): every slab gets a twin of KV8 pages on demand, page i of slab s at
+  // slabs8[s] + i * page_bytes8, layers layer_stride8 apart; d_page_ptrs8 is d_page_ptrs' logical numbering over the twins, rebuilt by
+  // model_ensure_pages8 for the pages mapped at that moment.  Prefill writes the bf16 pages; the batched decode reads and appends here.
+  int kv_format = 0;            // AHA_KV_BF16 / AHA_KV_E4M3
+  std::vector<void*> slabs8;
+  std::vector<uint64_t> h_page_ptrs8;
+  uint64_t* d_page_ptrs8 = nullptr;
+  size_t page_table_cap8 = 0;
+  uint64_t page_bytes8 = 0, layer_stride8 = 0;
   // step state
   aha::StepState* d_state = nullptr;
   aha::StepState* h_state = nullptr;  // pinned
@@ -315,6 +324,8 @@ int model_last_logits(aha_model* m, float* logits_out);
 int model_sample_candidates(aha_model* m, const uint32_t* ctx, size_t n_ctx, float repeat_penalty, float temperature, int k,
                             float* vals_out, uint32_t* idx_out, float* max_out, float* sumexp_out);
 int model_ensure_pages(aha_model* m, size_t tokens);
+int model_ensure_pages8(aha_model* m);
+int model_set_kv_format(aha_model* m, int format);
 KvLayer model_kv_layer(aha_model* m, int layer);
 int model_debug_graph_step(aha_model* m, int replays, double* us_launches, double* us_graph);
 int model_kv_export(aha_model* m, void* out_dev, size_t out_bytes, size_t* bytes_needed, size_t* n_tokens, int64_t* rope_delta);

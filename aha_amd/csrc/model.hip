@@ -355,6 +355,68 @@ int model_ensure_pages(aha_model* m, size_t tokens) {
   return AHA_OK;
 }
 
+// The KV8 twins of the slabs and the KV8 page table of the n_pages pages mapped now (model.h).  A twin is zeroed: a scale byte of 0 is a
+// scale of 0 and a code of 0 is 0, so a slot nobody wrote weighs nothing.
+int model_ensure_pages8(aha_model* m) {
+  const size_t slab_bytes8 = (size_t)m->layer_stride8 * m->desc.num_hidden_layers;
+  while (m->slabs8.size() < m->slabs.size()) {
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, slab_bytes8);
+    if (e != hipSuccess) {
+      set_error("KV8 slab hipMalloc of " + std::to_string(slab_bytes8) + " bytes failed: " + hipGetErrorString(e));
+      return e == hipErrorOutOfMemory ? AHA_ERR_OOM : AHA_ERR_HIP;
+    }
+    m->slabs8.push_back(p);
+    AHA_HIP_CHECK(hipMemsetAsync(p, 0, slab_bytes8, m->stream));
+  }
+  if (m->n_pages > m->page_table_cap8) {
+    AHA_HIP_CHECK(hipStreamSynchronize(m->stream));
+    if (m->d_page_ptrs8) AHA_HIP_CHECK(hipFree(m->d_page_ptrs8));
+    m->d_page_ptrs8 = nullptr;
+    AHA_HIP_CHECK(hipMalloc((void**)&m->d_page_ptrs8, m->page_table_cap * sizeof(uint64_t)));
+    m->page_table_cap8 = m->page_table_cap;
+  }
+  const uint64_t slab_span = (uint64_t)m->pages_per_slab * m->page_bytes;
+  m->h_page_ptrs8.resize(m->n_pages);
+  for (size_t i = 0; i < m->n_pages; ++i) {
+    const uint64_t p = m->h_page_ptrs[i];
+    size_t s = 0;
+    while (s < m->slabs.size() && !(p >= (uint64_t)(uintptr_t)m->slabs[s] && p < (uint64_t)(uintptr_t)m->slabs[s] + slab_span)) ++s;
+    if (s == m->slabs.size()) {
+      set_error("KV8 page table: a mapped page lies in no slab");
+      return AHA_ERR_STATE;
+    }
+    m->h_page_ptrs8[i] = (uint64_t)(uintptr_t)m->slabs8[s] + (p - (uint64_t)(uintptr_t)m->slabs[s]) / m->page_bytes * m->page_bytes8;
+  }
+  if (m->n_pages)
+    AHA_HIP_CHECK(hipMemcpyAsync(m->d_page_ptrs8, m->h_page_ptrs8.data(), m->n_pages * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
+  return AHA_OK;
+}
+
+int model_set_kv_format(aha_model* m, int format) {
+  if (format != AHA_KV_BF16 && format != AHA_KV_E4M3) {
+    set_error("set_kv_format: format must be AHA_KV_BF16 or AHA_KV_E4M3");
+    return AHA_ERR_INVALID;
+  }
+  if (m->tp_size > 1 || m->cp_size > 1 || (format == AHA_KV_E4M3 && m->desc.head_dim != 128)) {
+    set_error("set_kv_format: a single-GPU model with head_dim 128 only (sharded models keep the bf16 cache)");
+    return AHA_ERR_UNSUPPORTED;
+  }
+  if (m->cache_len != 0 || m->n_pages != 0 || m->engine) {
+    set_error("set_kv_format: the cache must be empty and no engine open");
+    return AHA_ERR_STATE;
+  }
+  m->kv_format = format;
+  return AHA_OK;
+}
+
+// The entries that read or write the cache as bf16 pages outside generate_batch refuse a KV8 model before any device work.
+static int refuse_kv8(const aha_model* m, const char* who) {
+  if (m->kv_format != AHA_KV_E4M3) return AHA_OK;
+  set_error(std::string(who) + ": not available on a model with an E4M3 KV cache (aha_hip_model_set_kv_format); generate_batch serves it");
+  return AHA_ERR_UNSUPPORTED;
+}
+
 KvLayer model_kv_layer(aha_model* m, int layer) {
   KvLayer kv;
   kv.page_ptrs = m->d_page_ptrs;
@@ -385,6 +447,7 @@ __global__ __launch_bounds__(256) void kv_pack_kernel(const uint64_t* __restrict
 }
 
 int model_kv_export(aha_model* m, void* out_dev, size_t out_bytes, size_t* bytes_needed, size_t* n_tokens, int64_t* rope_delta) {
+  if (int kv8rc = refuse_kv8(m, "kv_export")) return kv8rc;
   const aha_model_desc& c = m->desc;
   if (c.head_dim != 128) {
     set_error("kv_export: head_dim 128 only");
@@ -410,6 +473,7 @@ int model_kv_export(aha_model* m, void* out_dev, size_t out_bytes, size_t* bytes
 
 int model_kv_import(aha_model* m, const void* in_dev, size_t in_bytes, int src_heads, int src_head0, int dst_head0, int n_heads, size_t n_tokens,
                     int64_t rope_delta) {
+  if (int kv8rc = refuse_kv8(m, "kv_import")) return kv8rc;
   const aha_model_desc& c = m->desc;
   if (c.head_dim != 128) {
     set_error("kv_import: head_dim 128 only");
@@ -951,6 +1015,8 @@ int model_create(aha_ctx* ctx, const aha_model_desc* desc, const aha_tensor_view
   m->page_bytes = (uint64_t)2 * c.num_key_value_heads * KV_PAGE_TOKENS * d * 2;
   m->pages_per_slab = 64;
   m->layer_stride = m->pages_per_slab * m->page_bytes;
+  m->page_bytes8 = (uint64_t)kv8_page_bytes(c.num_key_value_heads);
+  m->layer_stride8 = m->pages_per_slab * m->page_bytes8;
   if (c.kv_reserve_tokens > 0) {
     if ((rc = model_ensure_pages(m, c.kv_reserve_tokens))) return fail(rc);
     model_clear_cache(m);
@@ -1039,6 +1105,8 @@ void model_destroy(aha_model* m) {
   if (m->h_pass_stage) hipHostFree(m->h_pass_stage);
   for (void* p : m->slabs) hipFree(p);
   if (m->d_page_ptrs) hipFree(m->d_page_ptrs);
+  for (void* p : m->slabs8) hipFree(p);
+  if (m->d_page_ptrs8) hipFree(m->d_page_ptrs8);
   if (m->h_state) hipHostFree(m->h_state);
   if (m->h_ring) hipHostFree(m->h_ring);
   if (m->h_logits) hipHostFree(m->h_logits);
@@ -1848,6 +1916,7 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = 
 }
 
 int model_forward_step(aha_model* m, uint32_t token, size_t offset, float* logits_out, uint32_t* argmax_out) {
+  if (int kv8rc = refuse_kv8(m, "forward_step")) return kv8rc;
   const aha_model_desc& c = m->desc;
   if (token >= (uint32_t)c.vocab_size) {
     set_error("token id out of range");
@@ -1929,6 +1998,7 @@ int model_debug_graph_step(aha_model* m, int replays, double* us_launches, doubl
 }
 
 int model_decode_greedy(aha_model* m, uint32_t first_token, size_t offset, size_t max_new, uint32_t* out) {
+  if (int kv8rc = refuse_kv8(m, "decode_greedy")) return kv8rc;
   const aha_model_desc& c = m->desc;
   if (max_new == 0) return 0;
   if (first_token >= (uint32_t)c.vocab_size) {
@@ -3296,15 +3366,20 @@ static void gen_decode_step(aha_model* m, GenCall& gc, int R, int max_split, dou
     {   // q/k norm + rope + KV append + attention of every row over its own pages (modules.rs:544-574, 757-813)
       AttnDecodeBatchArgs b{};
       b.qkv = gc.qkv; b.q_norm_w = Lw.q_norm; b.k_norm_w = Lw.k_norm; b.rope = gc.rope; b.page_ptrs = gc.dec_pages ? gc.dec_pages : m->d_page_ptrs;
-      b.layer_off = (uint64_t)li * m->layer_stride; b.row_tab = gc.rowtab; b.part_o = gc.part_o; b.part_ml = gc.part_ml; b.o = gc.attn;
+      b.layer_off = (uint64_t)li * m->layer_stride;
+      const bool kv8 = m->kv_format == AHA_KV_E4M3;   // (no engine on such a model: gc.dec_pages is null)
+      if (kv8) b.page_ptrs = m->d_page_ptrs8, b.layer_off = (uint64_t)li * m->layer_stride8;
+      b.row_tab = gc.rowtab; b.part_o = gc.part_o; b.part_ml = gc.part_ml; b.o = gc.attn;
       b.head_ctr = gc.ctr; b.ctr_step = li + 1; b.nh = nh; b.kvh = kvh; b.max_nsplit = gc.max_nsplit; b.eps = c.rms_norm_eps;
       b.scale = m->attn_scale;
       if (split_append) {
-        ProfScope ps(m, "kv_append_rows", (double)R * nkv * 2 * 4, 0);
-        launch_kv_append_rows(b, R, st);
+        ProfScope ps(m, kv8 ? "kv_append_rows_kv8" : "kv_append_rows", (double)R * nkv * 2 * (kv8 ? 3 : 4), 0);
+        (kv8 ? launch_kv_append_rows_kv8 : launch_kv_append_rows)(b, R, st);
       }
-      ProfScope ps(m, "attn_decode_batch", kv_tokens * 2 * nkv * 2 + (double)R * (nq + 2 * nkv) * 2, 4.0 * kv_tokens * nq);
-      launch_attn_decode_batch(b, R, max_split, st, !split_append);
+      // bytes per cached token: K and V of every kv head, 2 bytes an element, or 1 byte and a scale byte per 128
+      ProfScope ps(m, kv8 ? "attn_decode_batch_kv8" : "attn_decode_batch",
+                   kv_tokens * 2 * (kv8 ? nkv + kvh : nkv * 2) + (double)R * (nq + 2 * nkv) * 2, 4.0 * kv_tokens * nq);
+      (kv8 ? launch_attn_decode_batch_kv8 : launch_attn_decode_batch)(b, R, max_split, st, !split_append);
     }
     {   // x = x + attn Wo^T                                    (modules.rs:577, qwen3/model.rs:81)
       GemvRowsArgs a{};
@@ -3567,6 +3642,23 @@ int model_generate_batch(aha_model* m, const uint32_t* ids, const size_t* seq_le
     if ((rc = gen_packed_pass(m, gc, pp, ids + p.off, o.mm ? o.mm + j0 : nullptr, j0, m->h_page_ptrs.data(), n_seg, j0))) return rc;
     AHA_HIP_CHECK(hipStreamSynchronize(st));   // the pass page table and the staging buffer are reused by the next pass
   }
+  if (m->kv_format == AHA_KV_E4M3) {   // the prompts' pages -> their KV8 twins, all layers in one launch; decode reads and appends there
+    if ((rc = model_ensure_pages8(m))) return rc;
+    std::vector<uint64_t> pp;   // [sources | destinations]
+    for (int j = 0; j < n; ++j)
+      for (size_t i = 0; i < (seq_lens[j] + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS; ++i) pp.push_back(m->h_page_ptrs[page0[j] + i]);
+    const size_t np = pp.size();
+    for (int j = 0; j < n; ++j)
+      for (size_t i = 0; i < (seq_lens[j] + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS; ++i) pp.push_back(m->h_page_ptrs8[page0[j] + i]);
+    uint64_t* d_pp = nullptr;
+    if ((rc = bufs.alloc(&d_pp, 2 * np))) return rc;
+    AHA_HIP_CHECK(hipMemcpyAsync(d_pp, pp.data(), 2 * np * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    {
+      ProfScope ps(m, "kv_pages_quantize", (double)np * c.num_hidden_layers * (double)(m->page_bytes + m->page_bytes8), 0);
+      launch_kv_pages_quantize(d_pp, d_pp + np, (int)np, c.num_key_value_heads, c.num_hidden_layers, m->layer_stride, m->layer_stride8, st);
+    }
+    AHA_HIP_CHECK(hipStreamSynchronize(st));   // pp is pageable host memory
+  }
   {
     std::vector<int> all(n);
     for (int j = 0; j < n; ++j) all[j] = j, n_out[j] = 0;
@@ -3751,6 +3843,7 @@ int engine_config_check(const aha_engine_config* cfg, size_t* budget_out, size_t
 }
 
 int engine_create(aha_model* m, const aha_engine_config* cfg, aha_engine** out) {
+  if (int kv8rc = refuse_kv8(m, "engine_create")) return kv8rc;
   const aha_model_desc& c = m->desc;
   size_t budget = 0, chunk = 0;
   if (int rc = engine_config_check(cfg, &budget, &chunk)) return rc;

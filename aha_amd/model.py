@@ -637,6 +637,19 @@ class HipInferenceModel:
         fmt = ("mxfp4" if f.value == _lib.AHA_WQ_MXFP4_E2M1 else "mxfp8", bool(fl.value & _lib.AHA_WQ_LM_HEAD))
         return fmt + ("prefill",) if fl.value & _lib.AHA_WQ_PREFILL else fmt
 
+    def set_kv_format(self, fmt: str) -> None:
+        """"e4m3": the batched decode of generate_batch* reads and appends an E4M3 KV cache (aha_hip_model_set_kv_format; aha_amd/quant.py
+        quantize_kv is the reference); "bf16": the default.  Only while the cache is empty and no engine is open.  On an "e4m3" model
+        forward_step, decode_greedy, HipEngine, kv_export and kv_import raise (AHA_ERR_UNSUPPORTED)."""
+        formats = {"bf16": _lib.AHA_KV_BF16, "e4m3": _lib.AHA_KV_E4M3}
+        if fmt not in formats:
+            raise ValueError(f"unknown KV format {fmt!r} (\"bf16\", \"e4m3\")")
+        check(lib().aha_hip_model_set_kv_format(self.handle, formats[fmt]))
+
+    @property
+    def kv_format(self) -> str:
+        return "e4m3" if lib().aha_hip_model_kv_format(self.handle) == _lib.AHA_KV_E4M3 else "bf16"
+
     def debug_fp8_rows(self, on: bool = True) -> None:
         """Test hook: False makes a quantised model's batched decode run the bf16 matvec on the dequantised matrices (the same bits)."""
         check(lib().aha_hip_debug_fp8_rows(self.handle, int(on)))

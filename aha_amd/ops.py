@@ -753,6 +753,34 @@ def debug_attn_decode_rows(qkv: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: 
     return o
 
 
+def kv8_page_bytes(kvh: int) -> int:
+    """Host only: bytes of one layer's KV8 page (E4M3 KV cache; include/aha_hip.h "KV8") of kvh kv heads: 16512 * kvh."""
+    return int(lib().aha_hip_kv8_page_bytes(int(kvh)))
+
+
+def quantize_kv_pages(src_page_ptrs: torch.Tensor, dst_page_ptrs: torch.Tensor, kvh: int) -> None:
+    """bf16 pages -> KV8 pages (aha_hip_quantize_kv_pages): page i of the int64 device table src_page_ptrs (32768 * kvh bytes each) into the
+    page dst_page_ptrs[i] (kv8_page_bytes(kvh) bytes each), all 64 slots; quant.quantize_kv + quant.pack_kv8_pages give the same bytes."""
+    _chk(src_page_ptrs, dst_page_ptrs)
+    if src_page_ptrs.dtype != torch.int64 or dst_page_ptrs.dtype != torch.int64 or src_page_ptrs.shape != dst_page_ptrs.shape:
+        raise ValueError("quantize_kv_pages wants two int64 page tables of one length")
+    check(lib().aha_hip_quantize_kv_pages(_ptr(src_page_ptrs), _ptr(dst_page_ptrs), src_page_ptrs.numel(), int(kvh), _stream()))
+
+
+def attn_decode_batch_kv8(qkv: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: torch.Tensor, rope: torch.Tensor, page_ptrs: torch.Tensor,
+                          page0, kv_len, nh: int, kvh: int, eps: float, scale: float, form: int = ATTN_ROWS_FUSED) -> Optional[torch.Tensor]:
+    """debug_attn_decode_rows over KV8 pages (aha_hip_attn_decode_batch_kv8): page_ptrs addresses pages of kv8_page_bytes(kvh) bytes; the
+    append writes the new token's E4M3 codes and scale bytes, and its own step attends to its dequantised values.  Forms as there."""
+    _chk(qkv, q_norm_w, k_norm_w, rope, page_ptrs)
+    R = qkv.shape[0]
+    p0 = np.ascontiguousarray(np.asarray(page0, dtype=np.int32).reshape(R))
+    kl = np.ascontiguousarray(np.asarray(kv_len, dtype=np.int32).reshape(R))
+    o = None if form == ATTN_ROWS_APPEND_ONLY else torch.empty(R, nh * 128, dtype=torch.bfloat16, device=qkv.device)
+    check(lib().aha_hip_attn_decode_batch_kv8(_ptr(qkv), _ptr(q_norm_w), _ptr(k_norm_w), _ptr(rope), _ptr(page_ptrs), p0.ctypes.data,
+                                              kl.ctypes.data, R, nh, kvh, eps, scale, _ptr(o), int(form), _stream()))
+    return o
+
+
 def debug_spec_accept(argmax: torch.Tensor, row_tok, seq_tab, layout: int) -> torch.Tensor:
     """Test entry (aha_hip_debug_spec_accept): the accept kernel of a draft-and-verify step.  argmax (rows) int32 / uint32 on the device,
     row_tok: the rows' input tokens (host ints), seq_tab: per sequence (row0, n_draft) for layout 0 (spec_accept_rows_kernel) or (own row,

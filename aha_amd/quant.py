@@ -155,6 +155,80 @@ def scales_from_kernel(words: torch.Tensor, K: int) -> torch.Tensor:
     return words.cpu().contiguous().view(torch.uint8).reshape(N, -1)[:, :K // BLOCK].contiguous()
 
 
+# ---- KV8: the E4M3 KV cache of the batched decode attention (aha_amd/csrc/kernels_attn_kv8.hip) ----------------------------------------
+# One (token, kv head) vector of 128 dims is one block, for K and for V: block_exponents' rule with amax over the 128 dims, the codes of
+# quantize_mxfp8.  Non-finite input does not fail (a cache is written by kernels, not checked on load): +-Inf and magnitudes of
+# 1.9375 * 2^127 or more count as 1.9296875 * 2^127 in amax (so e = 120) and become +-448, NaN takes no part in amax and becomes 0x7f / 0xff.
+KV_DIM, KV_PAGE_TOKENS = 128, 64
+KV8_HEAD_BYTES, KV8_SCALE_BYTES = KV_PAGE_TOKENS * KV_DIM, 2 * KV_PAGE_TOKENS
+_KV_SAT, _KV_SAT_AMAX = 1.9375 * 2.0 ** 127, 1.9296875 * 2.0 ** 127
+
+
+def quantize_kv(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x (..., 128) bf16 -> (codes (..., 128) uint8 E4M3, scales (...) uint8 E8M0), on the CPU."""
+    if x.dtype != torch.bfloat16 or x.shape[-1] != KV_DIM:
+        raise ValueError(f"quantize_kv wants bf16 vectors of {KV_DIM} dims")
+    x = x.detach().cpu().contiguous()
+    f = x.float()
+    nan = torch.isnan(f)
+    sat = ~nan & (f.abs() >= _KV_SAT)
+    a = f.abs().masked_fill(nan, 0.0).masked_fill(sat, _KV_SAT_AMAX)
+    amax = a.amax(-1)
+    fr, ex = torch.frexp(amax)                          # as block_exponents: amax <= 448 * 2^e  <=>  e >= ex - 9 (+ 1 when fr > 0.875)
+    e = ex.to(torch.int32) - 9 + (fr > 0.875).to(torch.int32)
+    e = torch.where(amax == 0, torch.full_like(e, EXP_MIN), e).clamp(EXP_MIN, EXP_MAX)
+    v = f.masked_fill(nan | sat, 0.0) * torch.exp2(-e.float())[..., None]
+    q = v.to(torch.float8_e4m3fn).view(torch.uint8)
+    sign = ((x.view(torch.int16).to(torch.int32) >> 8) & 0x80).to(torch.uint8)
+    q = torch.where(sat, sign | 0x7e, q)
+    q = torch.where(nan, sign | 0x7f, q)
+    return q.contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_kv(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """(codes (..., 128) uint8, scales (...) uint8) -> (..., 128) bf16, exact."""
+    v = codes.cpu().contiguous().view(torch.float8_e4m3fn).float()
+    return (v * torch.exp2(scales.cpu().float() - 127.0)[..., None]).bfloat16()
+
+
+# KV8 page of one layer: [kvh] K blocks of 8 KB | [kvh] V blocks of 8 KB | [kvh] x (64 K scale bytes | 64 V scale bytes).  A block is the
+# bf16 page's MFMA operand fragments (tests/kv_pages.py states them) at one byte per element: a lane's piece is 8 bytes, and two fragments
+# lie side by side in one 1 KB unit whose 16-byte piece l = G * 16 + c is [piece l of the first | piece l of the second]:
+#   K unit sub * 2 + p: fragments (sub, k4 = 2p) | (sub, 2p + 1); piece l of (sub, k4) = dims k4*32 + G*8 .. +8 of token sub*16 + c
+#   V unit ds:          fragments (ds, kk = 0) | (ds, 1);         piece l of (ds, kk) = slots kk*32 + G*8 .. +8 of dim ds*16 + c,
+#                       token kk*32 + sub1*16 + G*4 + j in slot kk*32 + G*8 + sub1*4 + j
+#   scale bytes of a head: token sub*16 + G*4 + r at byte G*16 + sub*4 + r
+def _kv8_index(kvh: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    t, d = torch.arange(KV_PAGE_TOKENS)[:, None, None], torch.arange(KV_DIM)[None, None, :]
+    h = torch.arange(kvh)[None, :, None]
+    sub, c, k4, G, j = t // 16, t % 16, d // 32, (d % 32) // 8, d % 8
+    kb = h * KV8_HEAD_BYTES + ((sub * 2 + k4 // 2) * 64 + G * 16 + c) * 16 + (k4 % 2) * 8 + j
+    kk, sub1, Gt, jt, ds, cd = t // 32, (t // 16) % 2, (t // 4) % 4, t % 4, d // 16, d % 16
+    vb = (kvh + h) * KV8_HEAD_BYTES + (ds * 64 + Gt * 16 + cd) * 16 + kk * 8 + sub1 * 4 + jt
+    sb = 2 * kvh * KV8_HEAD_BYTES + h[..., 0] * KV8_SCALE_BYTES + (Gt * 16 + sub * 4 + jt)[..., 0]
+    return kb, vb, sb, sb + KV_PAGE_TOKENS
+
+
+def kv8_page_bytes(kvh: int) -> int:
+    return kvh * (2 * KV8_HEAD_BYTES + KV8_SCALE_BYTES)
+
+
+def pack_kv8_pages(kq: torch.Tensor, ks: torch.Tensor, vq: torch.Tensor, vs: torch.Tensor) -> torch.Tensor:
+    """Codes kq, vq (P, 64, kvh, 128) uint8 and scales ks, vs (P, 64, kvh) uint8 of the 64 slots of P pages -> page images (P, 16512 * kvh)."""
+    P, _, kvh, _ = kq.shape
+    kb, vb, ksb, vsb = _kv8_index(kvh)
+    out = torch.zeros(P, kv8_page_bytes(kvh), dtype=torch.uint8)
+    out[:, kb], out[:, vb], out[:, ksb], out[:, vsb] = kq, vq, ks, vs
+    return out
+
+
+def unpack_kv8_pages(pages: torch.Tensor, kvh: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The inverse of pack_kv8_pages: page images (P, 16512 * kvh) uint8 -> (kq, ks, vq, vs)."""
+    kb, vb, ksb, vsb = _kv8_index(kvh)
+    pages = pages.cpu()
+    return pages[:, kb], pages[:, ksb], pages[:, vb], pages[:, vsb]
+
+
 # ---- exact 13-bit copies (aha_amd/csrc/kernels_gemv_pk13.hip) ----------------------------------------------------------------------------
 # A bf16 weight is s | E(8) | m(7).  The copy keeps the low byte (E & 1) | m and the sign, and recodes E >> 1 to a 4-bit code h with one
 # base bh per matrix: h = 0 means E >> 1 == 0 (+-0, subnormals, E = 1), h = 1 .. 15 means E >> 1 == bh + h.  Nothing is rounded: unpack_pk13

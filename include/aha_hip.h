@@ -793,6 +793,17 @@ int aha_hip_debug_allreduce(aha_model* m, void* buf_f32_dev, size_t count);
 int aha_hip_model_quantize_weights(aha_model* m, int32_t format, uint32_t flags);
 /* *format = AHA_WQ_NONE or the format the model was quantised with, *flags its flags (either pointer may be NULL). */
 int aha_hip_model_weight_format(const aha_model* m, int32_t* format, uint32_t* flags);
+/* The format of the KV cache the batched decode reads (opt-in per model; the default is bf16).  AHA_KV_E4M3 ("KV8", the format stated at
+ * aha_hip_kv8_page_bytes below): every aha_hip_generate_batch* entry prefills into the bf16 pages as before, converts the prompts' pages
+ * once, behind the last prefill pass, and its decode steps (draft-and-verify ones included) read and append E4M3 pages: half the cache
+ * bytes per step.  The bf16 pages are kept (no capacity is gained).  Allowed only while the cache is empty and no engine is open
+ * (AHA_ERR_STATE otherwise); a sharded model or one whose head_dim is not 128 gets AHA_ERR_UNSUPPORTED.  On a KV8 model
+ * aha_hip_forward_step, aha_hip_decode_greedy, aha_hip_engine_create, aha_hip_kv_export and aha_hip_kv_import return
+ * AHA_ERR_UNSUPPORTED before any device work.  aha_hip_model_kv_format: the format set, AHA_KV_BF16 on a model never asked (-1: null). */
+#define AHA_KV_BF16 0
+#define AHA_KV_E4M3 1
+int aha_hip_model_set_kv_format(aha_model* m, int32_t format);
+int aha_hip_model_kv_format(const aha_model* m);
 /* Test hook: on = 0 makes a quantised model's batched decode run the bf16 matvec on W' instead of the FP8 one (the same bits); on = 1
  * (the default) restores it.  It holds for either format: on = 0 sends an MXFP4 model to the bf16 kernel on W' as well. */
 int aha_hip_debug_fp8_rows(aha_model* m, int on);
@@ -1077,6 +1088,24 @@ int aha_hip_debug_attn_decode_fused(const void* qkv, const void* q_norm_w, const
 int aha_hip_debug_attn_decode_rows(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
                                    const int32_t* page0, const int32_t* kv_len, int32_t rows, int32_t nh, int32_t kvh, float eps, float scale,
                                    void* o, int32_t form, void* stream);
+/* KV8: the decode attention over an E4M3 KV cache.  One (token, kv head) vector of 128 dims is one block: 128 OCP E4M3 bytes and one E8M0
+ * scale byte, for K and for V.  e = the smallest integer in [-117, 120] with amax <= 448 * 2^e over the 128 dims (all zero: -117), scale
+ * byte e + 127, code = e4m3fn(x / 2^e) round to nearest even; +-Inf and magnitudes of 1.9375 * 2^127 or more saturate to +-448 * 2^120,
+ * NaN becomes the code 0x7f / 0xff and takes no part in amax.  code * 2^e is exact in bf16.  A KV8 page of one layer:
+ * kvh K blocks of 8 KB, kvh V blocks of 8 KB, kvh x (64 K scale bytes | 64 V scale bytes) = aha_hip_kv8_page_bytes(kvh) = 16512 * kvh
+ * bytes (host only; 0 for kvh < 1); inside a block the bytes are ordered as the kernels' MFMA operand fragments (aha_amd/quant.py
+ * pack_kv8_pages states the order).
+ * aha_hip_quantize_kv_pages: the n_pages bf16 pages src_page_ptrs[i] (device table; a page is aha_hip_attn_decode_batch's, 32768 * kvh
+ * bytes) -> the KV8 pages dst_page_ptrs[i], all 64 slots of every page.  AHA_ERR_INVALID for a null table, n_pages < 1 or kvh outside
+ * 1 .. 64.  Synchronises the stream.
+ * aha_hip_attn_decode_batch_kv8: aha_hip_debug_attn_decode_rows -- arguments, forms 0 .. 2, checks -- with page_ptrs a table of KV8
+ * pages.  The append stores the new token's codes and scale bytes, and the token's own step scores and weights it from the dequantised
+ * values, the ones every later step reads.  The row table, split rule and split merge are the bf16 launch's. */
+int64_t aha_hip_kv8_page_bytes(int32_t kvh);
+int aha_hip_quantize_kv_pages(const uint64_t* src_page_ptrs, const uint64_t* dst_page_ptrs, int32_t n_pages, int32_t kvh, void* stream);
+int aha_hip_attn_decode_batch_kv8(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
+                                  const int32_t* page0, const int32_t* kv_len, int32_t rows, int32_t nh, int32_t kvh, float eps, float scale,
+                                  void* o, int32_t form, void* stream);
 /* Test entry: the accept step of draft-and-verify decoding.  argmax (device, rows uint32): the step's pick of every row; row_tok (HOST,
  * rows): every row's input token (a draft row's is its draft); seq_tab (HOST): per sequence {first row, drafts} (layout 0: a sequence's
  * rows are consecutive, generate_batch_spec's step) or {own row, first draft row, drafts} (layout 1: the engine's step).  out (device,

@@ -645,6 +645,8 @@ pub mod sys {
         pub fn aha_hip_cache_len(m: *const AhaModel) -> usize;
         pub fn aha_hip_model_quantize_weights(m: *mut AhaModel, format: i32, flags: u32) -> i32;
         pub fn aha_hip_model_weight_format(m: *const AhaModel, format: *mut i32, flags: *mut u32) -> i32;
+        pub fn aha_hip_model_set_kv_format(m: *mut AhaModel, format: i32) -> i32;
+        pub fn aha_hip_model_kv_format(m: *const AhaModel) -> i32;
         pub fn aha_hip_debug_fp8_rows(m: *mut AhaModel, on: i32) -> i32;
         pub fn aha_hip_debug_fp8_single(m: *mut AhaModel, on: i32) -> i32;
         pub fn aha_hip_debug_rows_wide(m: *mut AhaModel, on: i32) -> i32;
@@ -1102,6 +1104,18 @@ impl Model {
     /// matrices, 1 (the default) the FP4 kernel on the matrices its plan takes, 2 on every matrix with a copy.  The same bits in all three.
     pub fn debug_fp4_single(&mut self, on: i32) -> Result<(), Error> {
         check(unsafe { sys::aha_hip_debug_fp4_single(self.model, on) })
+    }
+
+    /// The KV cache the batched decode of `generate_batch*` reads (`aha_hip_model_set_kv_format`): `e4m3 = true` an E4M3 cache (the
+    /// prompts' pages are converted behind the prefill; `forward_step`, `decode_greedy`, the engine and the KV hand-back then fail as
+    /// unsupported), `false` the default bf16 one.  Only while the cache is empty and no engine is open.
+    pub fn set_kv_format(&mut self, e4m3: bool) -> Result<(), Error> {
+        check(unsafe { sys::aha_hip_model_set_kv_format(self.model, e4m3 as i32) })
+    }
+
+    /// Does the batched decode read an E4M3 KV cache (`aha_hip_model_kv_format`)?
+    pub fn kv_format_e4m3(&self) -> bool {
+        unsafe { sys::aha_hip_model_kv_format(self.model) == 1 }
     }
 
     /// `None`, or the format and the `lm_head` flag `quantize_weights` was called with.
