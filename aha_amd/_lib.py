@@ -21,6 +21,7 @@ AHA_WQ_NONE, AHA_WQ_MXFP8_E4M3, AHA_WQ_MXFP4_E2M1 = 0, 1, 2
 AHA_WQ_LM_HEAD = 1
 AHA_WQ_PREFILL = 2
 AHA_KV_BF16, AHA_KV_E4M3 = 0, 1
+AHA_KV_SINGLE = 1
 
 
 class SamplingParams(C.Structure):
@@ -277,6 +278,10 @@ SIGNATURES = {
     "aha_hip_model_weight_format": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]),
     "aha_hip_model_set_kv_format": (C.c_int, [_P, C.c_int32]),
     "aha_hip_model_kv_format": (C.c_int, [_P]),
+    "aha_hip_model_set_kv_format_with": (C.c_int, [_P, C.c_int32, C.c_uint32]),
+    "aha_hip_model_kv_flags": (C.c_uint32, [_P]),
+    "aha_hip_attn_decode_fused_kv8": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                                _P, _P]),
     "aha_hip_debug_fp8_rows": (C.c_int, [_P, C.c_int]),
     "aha_hip_debug_fp8_single": (C.c_int, [_P, C.c_int]),
     "aha_hip_debug_rows_wide": (C.c_int, [_P, C.c_int]),

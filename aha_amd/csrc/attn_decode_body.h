@@ -63,10 +63,12 @@ __device__ __forceinline__ float split_sum16(const float (&v)[16]) {
 // k and raw v are quantised behind the prologue's barrier, their codes and scale bytes are what the append stores, and ksn / vsn get the
 // DEQUANTISED values back: the token is scored and weighted in its own step from what every later step reads from the page.  The
 // request structure is the bf16 form's.  KV8 = false compiles to the instructions it compiled to before the parameter existed.
+// KV8 && LINEAR (kernels_attn_kv8_single.hip, the single-request decode step over the twins): a.lin_page0 / a.lin_step are the TWINS'
+// progression (model.h lin_p0_8 / lin_step8), so the unit's pages, the clamped first page and the append's slot -- codes and scale bytes
+// -- are all scalar arithmetic on the two arguments, as in the bf16 linear form.
 template <bool APPEND = true, bool LINEAR = false, bool KV8 = false>
 __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs& a, char* smem, const int kvhd, const int split,
                                                        const int nsplit) {
-  static_assert(!(KV8 && LINEAR), "the single-sequence linear form has no KV8 instantiation");
   constexpr int NW = ATTN_DECODE_NW, NT = NW * 64;
   bf16_t* qs = reinterpret_cast<bf16_t*>(smem);                 // [16][128]
   bf16_t* ksn = qs + 16 * 128;                                  // [128]
@@ -230,7 +232,7 @@ __device__ __forceinline__ bool attn_decode_fused_body(const AttnDecodeFusedArgs
         xs[lane + 64] = kv8_dequant(c1, e);
         if (APPEND) {
           const int pg = slot_new / KV_PAGE_TOKENS, t = slot_new % KV_PAGE_TOKENS;
-          const uint64_t base = (uint64_t)(a.kv.page_ptrs[pg] + a.kv.layer_off);
+          const uint64_t base = LINEAR ? a.lin_page0 + (uint64_t)((int64_t)pg * a.lin_step) : (uint64_t)(a.kv.page_ptrs[pg] + a.kv.layer_off);
           gu8_t cd = reinterpret_cast<gu8_t>(base + (uint64_t)(wave * a.kvh + kvhd) * KV8_HEAD_BYTES);
           cd[wave == 0 ? kv8_kpage_byte(t, lane) : kv8_vpage_byte(t, lane)] = (uint8_t)c0;
           cd[wave == 0 ? kv8_kpage_byte(t, lane + 64) : kv8_vpage_byte(t, lane + 64)] = (uint8_t)c1;

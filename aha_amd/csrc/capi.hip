@@ -1126,11 +1126,22 @@ int aha_hip_model_set_kv_format(aha_model* m, int32_t format) {
     set_error("set_kv_format: null model");
     return AHA_ERR_INVALID;
   }
-  return model_set_kv_format(m, format);
+  return model_set_kv_format(m, format, 0);
+  API_GUARD_END
+}
+
+int aha_hip_model_set_kv_format_with(aha_model* m, int32_t format, uint32_t flags) {
+  API_GUARD_BEGIN
+  if (!m) {
+    set_error("set_kv_format_with: null model");
+    return AHA_ERR_INVALID;
+  }
+  return model_set_kv_format(m, format, flags);
   API_GUARD_END
 }
 
 int aha_hip_model_kv_format(const aha_model* m) { return m ? m->kv_format : -1; }
+uint32_t aha_hip_model_kv_flags(const aha_model* m) { return m ? m->kv_flags : 0u; }
 
 int aha_hip_model_weight_format(const aha_model* m, int32_t* format, uint32_t* flags) {
   if (!m) {
@@ -1949,6 +1960,36 @@ int aha_hip_debug_attn_decode_fused(const void* qkv, const void* q_norm_w, const
   hipFree(po);
   hipFree(pml);
   hipFree(ctr);
+  AHA_HIP_CHECK(err);
+  return AHA_OK;
+  API_GUARD_END
+}
+
+int aha_hip_attn_decode_fused_kv8(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
+                                  uint64_t lin_page0, int64_t lin_step, int32_t kv_len, int32_t nh, int32_t kvh, float eps, float scale,
+                                  void* o, void* stream) {
+  API_GUARD_BEGIN
+  if (!qkv || !q_norm_w || !k_norm_w || !rope || !o || kv_len < 1 || !attn_batch_geometry_ok(nh, kvh) ||
+      (lin_step == 0 ? page_ptrs == nullptr : lin_page0 == 0)) {
+    set_error("attn_decode_fused_kv8: bad arguments (kv_len >= 1, nh % kvh == 0, group size <= 16, a page table or a progression)");
+    return AHA_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int nsplit = attn_decode_nsplit(kv_len, nh / kvh, 64);
+  DevBuf po, pml, ctr;
+  AHA_HIP_CHECK(hipMalloc(&po.p, (size_t)nsplit * nh * 128 * 4));
+  AHA_HIP_CHECK(hipMalloc(&pml.p, (size_t)nsplit * nh * 2 * 4));
+  AHA_HIP_CHECK(hipMalloc(&ctr.p, (size_t)kvh * 32 * 4));
+  AHA_HIP_CHECK(hipMemsetAsync(ctr.p, 0, (size_t)kvh * 32 * 4, st));
+  AttnDecodeFusedArgs a{};
+  a.qkv = qkv; a.q_norm_w = q_norm_w; a.k_norm_w = k_norm_w; a.rope = rope;
+  a.kv.page_ptrs = page_ptrs; a.kv.layer_off = 0; a.kv.kvh = kvh; a.kv.d = 128;
+  if (lin_step != 0) { a.lin_page0 = lin_page0; a.lin_step = lin_step; }
+  a.kv_start_v = kv_len - 1; a.kv_len_v = kv_len; a.part_o = (float*)po.p; a.part_ml = (float*)pml.p; a.o = o; a.head_ctr = (unsigned*)ctr.p;
+  a.ctr_target = nsplit > 1 ? (unsigned)nsplit : 0u; a.nh = nh; a.kvh = kvh; a.nsplit = nsplit; a.eps = eps; a.scale = scale;
+  launch_attn_decode_fused_kv8(a, st);
+  hipError_t err = hipGetLastError();
+  hipStreamSynchronize(st);
   AHA_HIP_CHECK(err);
   return AHA_OK;
   API_GUARD_END

@@ -497,6 +497,9 @@ void launch_kv_append_rows(const AttnDecodeBatchArgs& a, int rows, hipStream_t s
 // its own step -- what every later step reads from the page.
 void launch_attn_decode_batch_kv8(const AttnDecodeBatchArgs& a, int rows, int max_nsplit_rows, hipStream_t st, bool append = true);
 void launch_kv_append_rows_kv8(const AttnDecodeBatchArgs& a, int rows, hipStream_t st);
+// launch_attn_decode_fused over KV8 pages (kernels_attn_kv8_single.hip): a.kv.page_ptrs / a.kv.layer_off, or a.lin_page0 / a.lin_step with
+// the KV8 pages' own step, address KV8 pages; everything else is as there.  No traced form: a.trace is ignored.
+void launch_attn_decode_fused_kv8(const AttnDecodeFusedArgs& a, hipStream_t st);
 // bf16 pages -> KV8 pages: page p of 0 .. n_pages - 1, layer l of 0 .. n_layers - 1 from src_ptrs[p] + l * src_layer_stride to
 // dst_ptrs[p] + l * dst_layer_stride (all 64 slots, whatever they hold).
 void launch_kv_pages_quantize(const uint64_t* src_ptrs, const uint64_t* dst_ptrs, int n_pages, int kvh, int n_layers, uint64_t src_layer_stride,

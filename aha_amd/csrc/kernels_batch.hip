@@ -370,8 +370,8 @@ void launch_gen_embed(const void* table, const uint32_t* tok_in, const int32_t* 
 }
 
 int attn_decode_nsplit(int kv_len_after, int g, int max_nsplit) {
-  // enqueue_decode_step's rule (model.hip): one block (4 waves = 4 KV units) per AHA_ATTN_PAGES_PER_BLOCK pages, at most max_nsplit, and
-  // g * nsplit <= 1024 for the merge's LDS tables
+  // The split rule of every fused decode attention launch (enqueue_decode_step in model.hip, the batched rows, the op-level entries):
+  // one block (4 waves = 4 KV units) per AHA_ATTN_PAGES_PER_BLOCK pages, at most max_nsplit, and g * nsplit <= 1024 for the merge's LDS tables
   static const char* e_div = getenv("AHA_ATTN_PAGES_PER_BLOCK");
   const int div = e_div ? std::max(1, atoi(e_div)) : 4;
   const int npages = (kv_len_after + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;

@@ -137,6 +137,15 @@ struct aha_model {
   // slabs8[s] + i * page_bytes8, layers layer_stride8 apart; d_page_ptrs8 is d_page_ptrs' logical numbering over the twins, rebuilt by
   // model_ensure_pages8 for the pages mapped at that moment.  Prefill writes the bf16 pages; the batched decode reads and appends here.
   int kv_format = 0;            // AHA_KV_BF16 / AHA_KV_E4M3
+  // AHA_KV_SINGLE (aha_hip_model_set_kv_format_with): forward_step / decode_greedy read and append the twins too (attn_decode_fused_kv8_kernel),
+  // forward_initial converts the prompt's pages behind its last pass.  The twins of pages [0, lin_pages8) are the progression
+  // lin_p0_8 + i * lin_step8 -- lin_pages' rule on the twins' OWN addresses (a second slab's twin lies wherever hipMalloc put it, so one
+  // progression may break where the other holds); pages8_mapped: the pages the twin table held when it was last rebuilt.
+  unsigned kv_flags = 0;
+  size_t lin_pages8 = 0, pages8_mapped = 0;
+  uint64_t lin_p0_8 = 0;
+  int64_t lin_step8 = 0;
+  bool attn_trace_kv8_said = false;
   std::vector<void*> slabs8;
   std::vector<uint64_t> h_page_ptrs8;
   uint64_t* d_page_ptrs8 = nullptr;
@@ -325,7 +334,7 @@ int model_sample_candidates(aha_model* m, const uint32_t* ctx, size_t n_ctx, flo
                             float* vals_out, uint32_t* idx_out, float* max_out, float* sumexp_out);
 int model_ensure_pages(aha_model* m, size_t tokens);
 int model_ensure_pages8(aha_model* m);
-int model_set_kv_format(aha_model* m, int format);
+int model_set_kv_format(aha_model* m, int format, unsigned flags);
 KvLayer model_kv_layer(aha_model* m, int layer);
 int model_debug_graph_step(aha_model* m, int replays, double* us_launches, double* us_graph);
 int model_kv_export(aha_model* m, void* out_dev, size_t out_bytes, size_t* bytes_needed, size_t* n_tokens, int64_t* rope_delta);

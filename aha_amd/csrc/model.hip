@@ -386,16 +386,38 @@ int model_ensure_pages8(aha_model* m) {
       set_error("KV8 page table: a mapped page lies in no slab");
       return AHA_ERR_STATE;
     }
-    m->h_page_ptrs8[i] = (uint64_t)(uintptr_t)m->slabs8[s] + (p - (uint64_t)(uintptr_t)m->slabs[s]) / m->page_bytes * m->page_bytes8;
+    const uint64_t p8 = (uint64_t)(uintptr_t)m->slabs8[s] + (p - (uint64_t)(uintptr_t)m->slabs[s]) / m->page_bytes * m->page_bytes8;
+    m->h_page_ptrs8[i] = p8;
+    if (i == 0) {  // model_ensure_pages' rule on the twins' own addresses: a lone page is a progression of any step
+      m->lin_p0_8 = p8;
+      m->lin_step8 = (int64_t)m->page_bytes8;
+      m->lin_pages8 = 1;
+    } else if (m->lin_pages8 == i) {  // unbroken so far: the second twin sets the step, every later one has to keep it
+      if (i == 1) m->lin_step8 = (int64_t)(p8 - m->lin_p0_8);
+      if (m->lin_step8 != 0 && p8 == m->lin_p0_8 + (uint64_t)((int64_t)i * m->lin_step8)) m->lin_pages8 = i + 1;
+    }
   }
+  if (m->n_pages == 0) m->lin_pages8 = 0;
+  m->pages8_mapped = m->n_pages;
   if (m->n_pages)
     AHA_HIP_CHECK(hipMemcpyAsync(m->d_page_ptrs8, m->h_page_ptrs8.data(), m->n_pages * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
   return AHA_OK;
 }
 
-int model_set_kv_format(aha_model* m, int format) {
+// The single-sequence entries of a flagged model: the twin table (and the twins' progression) follows the page map.  Pages are only ever
+// mapped at the end (model_ensure_pages) or dropped altogether (model_clear_cache, which resets pages8_mapped), so the count tells.
+static int ensure_pages8_single(aha_model* m) {
+  if (m->pages8_mapped == m->n_pages && m->slabs8.size() == m->slabs.size()) return AHA_OK;
+  return model_ensure_pages8(m);
+}
+
+int model_set_kv_format(aha_model* m, int format, unsigned flags) {
   if (format != AHA_KV_BF16 && format != AHA_KV_E4M3) {
     set_error("set_kv_format: format must be AHA_KV_BF16 or AHA_KV_E4M3");
+    return AHA_ERR_INVALID;
+  }
+  if ((flags & ~AHA_KV_SINGLE) != 0 || (flags != 0 && format != AHA_KV_E4M3)) {
+    set_error("set_kv_format_with: flags must be 0 or AHA_KV_SINGLE, and AHA_KV_SINGLE goes with AHA_KV_E4M3 only");
     return AHA_ERR_INVALID;
   }
   if (m->tp_size > 1 || m->cp_size > 1 || (format == AHA_KV_E4M3 && m->desc.head_dim != 128)) {
@@ -407,12 +429,16 @@ int model_set_kv_format(aha_model* m, int format) {
     return AHA_ERR_STATE;
   }
   m->kv_format = format;
+  m->kv_flags = flags;
   return AHA_OK;
 }
 
+static bool kv8_single(const aha_model* m) { return m->kv_format == AHA_KV_E4M3 && (m->kv_flags & AHA_KV_SINGLE) != 0; }
+
 // The entries that read or write the cache as bf16 pages outside generate_batch refuse a KV8 model before any device work.
-static int refuse_kv8(const aha_model* m, const char* who) {
-  if (m->kv_format != AHA_KV_E4M3) return AHA_OK;
+// single_ok: forward_step and decode_greedy, which a model set with AHA_KV_SINGLE serves from the twins.
+static int refuse_kv8(const aha_model* m, const char* who, bool single_ok = false) {
+  if (m->kv_format != AHA_KV_E4M3 || (single_ok && kv8_single(m))) return AHA_OK;
   set_error(std::string(who) + ": not available on a model with an E4M3 KV cache (aha_hip_model_set_kv_format); generate_batch serves it");
   return AHA_ERR_UNSUPPORTED;
 }
@@ -604,6 +630,8 @@ int model_clear_cache(aha_model* m) {
   for (size_t i = m->n_pages; i > 0; --i) m->free_pages.push_back(m->h_page_ptrs[i - 1]);
   m->n_pages = 0;
   m->lin_pages = 0;
+  m->lin_pages8 = 0;
+  m->pages8_mapped = 0;
   m->cache_len = 0;
   m->rope_delta = 0;
   m->rope_delta_valid = false;
@@ -1821,11 +1849,10 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = 
                        m->d_inv_freq, m->d_axis_map, m->d_rope);
   }
   const int npages = (int)((kv_len_after + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS);
-  // KV splits of the fused decode attention: one block (4 waves = 4 KV units) per `div` pages
-  static const char* e_div = getenv("AHA_ATTN_PAGES_PER_BLOCK");
-  const int div = e_div ? std::max(1, atoi(e_div)) : 4;
-  int nsplit = (npages + div - 1) / div;
-  nsplit = std::max(1, std::min(std::min(nsplit, m->max_nsplit), 1024 / (nh / kvh)));  // g * nsplit <= 1024: LDS tables of the split merge
+  // KV splits of the fused decode attention: one block (4 waves = 4 KV units) per AHA_ATTN_PAGES_PER_BLOCK pages, then the caps
+  // (attn_decode_nsplit, kernels_batch.hip: the one statement of the rule, the op-level entries use it too)
+  const int nsplit = attn_decode_nsplit((int)kv_len_after, nh / kvh, m->max_nsplit);
+  const bool kv8 = kv8_single(m);   // the twins were brought up to the page map by the caller (ensure_pages8_single)
   for (int li = 0; li < c.num_hidden_layers; ++li) {
     const LayerWeights& L = m->layers[li];
     {  // h = RMSNorm(x); qkv = h Wqkv^T                      (qwen3/model.rs:79, modules.rs:538-552)
@@ -1834,7 +1861,7 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = 
       g.trace = gemv_trace_slot(m, li * 4 + 0);
       decode_gemv(m, g, GEMV_STORE, L.q_wqkv, L.p_wqkv, g.K * 4.0 + g.N * 2.0);
     }
-    if (m->decode_fused) {
+    if (m->decode_fused || kv8) {   // (the three-launch form has no KV8 kernel: a flagged model runs the fused form whatever the knob says)
       // q/k norm + rope + KV append + attention over the paged cache (modules.rs:544-574, 757-813), then
       // x = x + attn Wo^T with the KV-split partials merged in the matvec prologue (modules.rs:577, qwen3/model.rs:81)
       AttnDecodeFusedArgs a{};
@@ -1842,7 +1869,14 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = 
       a.kv = model_kv_layer(m, li); a.kv_start_v = (int)kv_len_after - 1; a.kv_len_v = (int)kv_len_after;
       // pages 0 .. npages - 1, the append slot's included, are lin_p0 + i * lin_step (the scramble knob is there to exercise the page
       // table: it keeps the table form even where one or two shuffled pages still are a progression)
-      if ((size_t)npages <= m->lin_pages && !m->scramble_pages) {
+      if (kv8) {   // the twin table / the twins' own progression
+        a.kv.page_ptrs = m->d_page_ptrs8;
+        a.kv.layer_off = (uint64_t)li * m->layer_stride8;
+        if ((size_t)npages <= m->lin_pages8 && !m->scramble_pages) {
+          a.lin_page0 = m->lin_p0_8 + a.kv.layer_off;
+          a.lin_step = m->lin_step8;
+        }
+      } else if ((size_t)npages <= m->lin_pages && !m->scramble_pages) {
         a.lin_page0 = m->lin_p0 + a.kv.layer_off;
         a.lin_step = m->lin_step;
       }
@@ -1852,7 +1886,11 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = 
       if (nsplit > 1) m->head_ctr_base += (unsigned)nsplit;  // a single split never touches the counter
       a.ctr_target = m->head_ctr_base;
       static const char* e_at = getenv("AHA_ATTN_TRACE");
-      if (e_at && atoi(e_at)) {
+      if (e_at && atoi(e_at) && kv8) {
+        if (!m->attn_trace_kv8_said)
+          fprintf(stderr, "[attn trace] the model decodes from an E4M3 KV cache: attn_decode_fused_kv8_kernel has no traced form, nothing is recorded\n");
+        m->attn_trace_kv8_said = true;
+      } else if (e_at && atoi(e_at)) {
         if (!m->d_attn_trace) {
           void* tp = nullptr;
           if (dev_alloc(m, (size_t)c.num_hidden_layers * 12 * 8, &tp, true) == AHA_OK) m->d_attn_trace = (unsigned long long*)tp;
@@ -1863,7 +1901,11 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = 
       g.W = L.wo; g.x = m->d_attn; g.residual = m->d_x; g.y = m->d_x; g.N = H; g.K = nq;
       g.trace = gemv_trace_slot(m, li * 4 + 1);
       const double attn_bytes = (double)kv_len_after * 2 * nkv * 2 + (nq + 2 * nkv) * 2.0 + nsplit * nq * 4.0;
-      {
+      if (kv8) {   // a byte per element and the pages' scale bytes instead of two bytes per element
+        const double kv8_bytes = (double)kv_len_after * 2 * nkv + (double)npages * kvh * KV8_SCALE_BYTES;
+        ProfScope ps(m, "attn_decode_kv8", attn_bytes - (double)kv_len_after * 2 * nkv * 2 + kv8_bytes, 4.0 * kv_len_after * nq);
+        launch_attn_decode_fused_kv8(a, st);
+      } else {
         ProfScope ps(m, "attn_decode", attn_bytes, 4.0 * kv_len_after * nq);
         launch_attn_decode_fused(a, st);
       }
@@ -1916,7 +1958,7 @@ static void enqueue_decode_step(aha_model* m, size_t kv_len_after, bool embed = 
 }
 
 int model_forward_step(aha_model* m, uint32_t token, size_t offset, float* logits_out, uint32_t* argmax_out) {
-  if (int kv8rc = refuse_kv8(m, "forward_step")) return kv8rc;
+  if (int kv8rc = refuse_kv8(m, "forward_step", true)) return kv8rc;
   const aha_model_desc& c = m->desc;
   if (token >= (uint32_t)c.vocab_size) {
     set_error("token id out of range");
@@ -1925,6 +1967,7 @@ int model_forward_step(aha_model* m, uint32_t token, size_t offset, float* logit
   AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
   int rc = model_ensure_pages(m, m->cache_len + 1);
   if (rc) return rc;
+  if (kv8_single(m) && (rc = ensure_pages8_single(m))) return rc;
   // rope position: seqlen_offset (+ rope_delta for Qwen3-VL, qwen3vl/model.rs:1235-1264); cache slot: current length
   int64_t p = (int64_t)offset + m->rope_delta;
   if (c.arch == AHA_ARCH_QWEN3VL && !m->rope_delta_valid) {
@@ -1955,6 +1998,7 @@ int model_debug_graph_step(aha_model* m, int replays, double* us_launches, doubl
   AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
   int rc = model_ensure_pages(m, m->cache_len + 1);
   if (rc) return rc;
+  if (kv8_single(m) && (rc = ensure_pages8_single(m))) return rc;
   const int64_t pos[3] = {(int64_t)m->cache_len, (int64_t)m->cache_len, (int64_t)m->cache_len};
   if ((rc = push_state(m, 0, pos, m->cache_len, m->cache_len + 1))) return rc;
   hipEvent_t e0, e1;
@@ -1998,7 +2042,7 @@ int model_debug_graph_step(aha_model* m, int replays, double* us_launches, doubl
 }
 
 int model_decode_greedy(aha_model* m, uint32_t first_token, size_t offset, size_t max_new, uint32_t* out) {
-  if (int kv8rc = refuse_kv8(m, "decode_greedy")) return kv8rc;
+  if (int kv8rc = refuse_kv8(m, "decode_greedy", true)) return kv8rc;
   const aha_model_desc& c = m->desc;
   if (max_new == 0) return 0;
   if (first_token >= (uint32_t)c.vocab_size) {
@@ -2008,6 +2052,7 @@ int model_decode_greedy(aha_model* m, uint32_t first_token, size_t offset, size_
   AHA_HIP_CHECK(hipSetDevice(m->ctx->device));
   int rc = model_ensure_pages(m, m->cache_len + max_new);
   if (rc) return rc;
+  if (kv8_single(m) && (rc = ensure_pages8_single(m))) return rc;
   const int64_t p = (int64_t)offset + m->rope_delta;
   const int64_t pos[3] = {p, p, p};
   if ((rc = push_state(m, first_token, pos, m->cache_len, m->cache_len + 1))) return rc;
@@ -2178,6 +2223,12 @@ static int forward_initial_impl(aha_model* m, const uint32_t* ids, size_t n, siz
       set_error("token id out of range at position " + std::to_string(i));
       return AHA_ERR_INVALID;
     }
+  if (kv8_single(m) && m->cache_len != 0) {
+    // the decode steps appended to the KV8 twins only: the bf16 pages a continuation prefill would attend over lack those tokens
+    set_error("forward_initial: a model set with AHA_KV_SINGLE prefills onto an empty cache only (its decode steps append to the E4M3 pages, "
+              "which no prefill reads); clear the cache first");
+    return AHA_ERR_UNSUPPORTED;
+  }
   const bool has_audio = mm && ((mm->audio_features && mm->n_frames > 0) || (mm->audio_samples && mm->n_samples > 0));
   if (has_audio && (c.arch != AHA_ARCH_QWEN3ASR || !m->audio)) {
     set_error("audio input given but this model has no audio tower");
@@ -2354,6 +2405,12 @@ static int forward_initial_impl(aha_model* m, const uint32_t* ids, size_t n, siz
     return AHA_OK;
   }
   enqueue_lm_head(m, x_last);
+  if (kv8_single(m)) {   // the prompt's pages -> their KV8 twins, all layers in one launch; forward_step / decode_greedy read and append there
+    if ((rc = ensure_pages8_single(m))) return rc;
+    const size_t np = (m->cache_len + n + KV_PAGE_TOKENS - 1) / KV_PAGE_TOKENS;   // <= n_pages: both tables hold them, in the same numbering
+    ProfScope ps(m, "kv_pages_quantize", (double)np * c.num_hidden_layers * (double)(m->page_bytes + m->page_bytes8), 0);
+    launch_kv_pages_quantize(m->d_page_ptrs, m->d_page_ptrs8, (int)np, kvh, c.num_hidden_layers, m->layer_stride, m->layer_stride8, st);
+  }
   m->cache_len += n;
   AHA_HIP_CHECK(hipGetLastError());
   if (m->async_rc) { const int e = m->async_rc; m->async_rc = 0; return e; }   // e.g. a failed vocab-parallel all-reduce

@@ -640,15 +640,28 @@ class HipInferenceModel:
     def set_kv_format(self, fmt: str) -> None:
         """"e4m3": the batched decode of generate_batch* reads and appends an E4M3 KV cache (aha_hip_model_set_kv_format; aha_amd/quant.py
         quantize_kv is the reference); "bf16": the default.  Only while the cache is empty and no engine is open.  On an "e4m3" model
-        forward_step, decode_greedy, HipEngine, kv_export and kv_import raise (AHA_ERR_UNSUPPORTED)."""
+        forward_step, decode_greedy, HipEngine, kv_export and kv_import raise (AHA_ERR_UNSUPPORTED); set_kv_format_with("e4m3", single=True)
+        is the opt-in that serves the first two from the E4M3 pages."""
         formats = {"bf16": _lib.AHA_KV_BF16, "e4m3": _lib.AHA_KV_E4M3}
         if fmt not in formats:
             raise ValueError(f"unknown KV format {fmt!r} (\"bf16\", \"e4m3\")")
         check(lib().aha_hip_model_set_kv_format(self.handle, formats[fmt]))
 
+    def set_kv_format_with(self, fmt: str, single: bool = False) -> None:
+        """set_kv_format with the opt-in flag single=True ("e4m3" only: AHA_KV_SINGLE): forward_step and decode_greedy -- and the generate
+        loops on top of them -- read and append the E4M3 pages too; forward_initial prefills into the bf16 pages and converts the prompt's
+        pages behind its last pass.  The engine, kv_export and kv_import still raise, and so does forward_initial onto a non-empty cache
+        (the decode steps append to the E4M3 pages only): clear_cache first.  (A method of its own: set_kv_format keeps its argument.)"""
+        formats = {"bf16": _lib.AHA_KV_BF16, "e4m3": _lib.AHA_KV_E4M3}
+        if fmt not in formats:
+            raise ValueError(f"unknown KV format {fmt!r} (\"bf16\", \"e4m3\")")
+        check(lib().aha_hip_model_set_kv_format_with(self.handle, formats[fmt], _lib.AHA_KV_SINGLE if single else 0))
+
     @property
-    def kv_format(self) -> str:
-        return "e4m3" if lib().aha_hip_model_kv_format(self.handle) == _lib.AHA_KV_E4M3 else "bf16"
+    def kv_format(self):
+        """"bf16" or "e4m3" as set_kv_format was called; ("e4m3", "single") with single=True."""
+        fmt = "e4m3" if lib().aha_hip_model_kv_format(self.handle) == _lib.AHA_KV_E4M3 else "bf16"
+        return (fmt, "single") if lib().aha_hip_model_kv_flags(self.handle) & _lib.AHA_KV_SINGLE else fmt
 
     def debug_fp8_rows(self, on: bool = True) -> None:
         """Test hook: False makes a quantised model's batched decode run the bf16 matvec on the dequantised matrices (the same bits)."""

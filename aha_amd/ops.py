@@ -781,6 +781,19 @@ def attn_decode_batch_kv8(qkv: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: t
     return o
 
 
+def attn_decode_fused_kv8(qkv_row: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: torch.Tensor, rope_row: torch.Tensor,
+                          page_ptrs: Optional[torch.Tensor], lin_page0: int, lin_step: int, kv_len: int, nh: int, kvh: int, eps: float,
+                          scale: float) -> torch.Tensor:
+    """debug_attn_decode_fused over KV8 pages (aha_hip_attn_decode_fused_kv8): the single-sequence decode attention of a model set with
+    set_kv_format_with("e4m3", single=True).  lin_step != 0: the linear kernel over the pages lin_page0 + i * lin_step (byte addresses;
+    page_ptrs may be None); lin_step == 0: the table kernel over page_ptrs[0 ..].  -> (nh*128) bf16."""
+    _chk(qkv_row, q_norm_w, k_norm_w, rope_row)
+    o = torch.empty(nh * 128, dtype=torch.bfloat16, device=qkv_row.device)
+    check(lib().aha_hip_attn_decode_fused_kv8(_ptr(qkv_row), _ptr(q_norm_w), _ptr(k_norm_w), _ptr(rope_row), _ptr(page_ptrs), int(lin_page0),
+                                              int(lin_step), int(kv_len), nh, kvh, eps, scale, _ptr(o), _stream()))
+    return o
+
+
 def debug_spec_accept(argmax: torch.Tensor, row_tok, seq_tab, layout: int) -> torch.Tensor:
     """Test entry (aha_hip_debug_spec_accept): the accept kernel of a draft-and-verify step.  argmax (rows) int32 / uint32 on the device,
     row_tok: the rows' input tokens (host ints), seq_tab: per sequence (row0, n_draft) for layout 0 (spec_accept_rows_kernel) or (own row,

@@ -799,11 +799,29 @@ int aha_hip_model_weight_format(const aha_model* m, int32_t* format, uint32_t* f
  * bytes per step.  The bf16 pages are kept (no capacity is gained).  Allowed only while the cache is empty and no engine is open
  * (AHA_ERR_STATE otherwise); a sharded model or one whose head_dim is not 128 gets AHA_ERR_UNSUPPORTED.  On a KV8 model
  * aha_hip_forward_step, aha_hip_decode_greedy, aha_hip_engine_create, aha_hip_kv_export and aha_hip_kv_import return
- * AHA_ERR_UNSUPPORTED before any device work.  aha_hip_model_kv_format: the format set, AHA_KV_BF16 on a model never asked (-1: null). */
+ * AHA_ERR_UNSUPPORTED before any device work (the first two unless the format was set with AHA_KV_SINGLE, below).
+ * aha_hip_model_kv_format: the format set, AHA_KV_BF16 on a model never asked (-1: null). */
 #define AHA_KV_BF16 0
 #define AHA_KV_E4M3 1
 int aha_hip_model_set_kv_format(aha_model* m, int32_t format);
 int aha_hip_model_kv_format(const aha_model* m);
+/* aha_hip_model_set_kv_format_with: the setter with flags; aha_hip_model_set_kv_format(m, f) is aha_hip_model_set_kv_format_with(m, f, 0),
+ * and the preconditions are that setter's (empty cache, no engine, one GPU, head_dim 128).  flags: 0 or AHA_KV_SINGLE; an unknown flag, or
+ * AHA_KV_SINGLE with AHA_KV_BF16, is AHA_ERR_INVALID.  aha_hip_model_kv_flags: the flags set (0 on a null model).
+ * AHA_KV_SINGLE (opt-in, AHA_KV_E4M3 only): the single-sequence decode reads and appends the E4M3 pages too.  aha_hip_forward_initial and
+ * aha_hip_forward_initial_mm prefill into the bf16 pages exactly as before and convert the request's pages of all layers in ONE launch
+ * behind the last pass; aha_hip_forward_step and aha_hip_decode_greedy (the device-resident loop and its fused tail included, and so every
+ * generate loop on top of them) then run attn_decode_fused_kv8_kernel over those pages and append there: 16 512 instead of 32 768 bytes
+ * per page and kv head and step.  It is a flag, not the format's meaning, because an unflagged KV8 model refuses those two entries and
+ * callers may rely on that.  Still AHA_ERR_UNSUPPORTED before any device work: aha_hip_engine_create, aha_hip_kv_export,
+ * aha_hip_kv_import.  New, also AHA_ERR_UNSUPPORTED before any device work and with the cache left as it was: aha_hip_forward_initial(_mm)
+ * onto a NON-EMPTY cache -- the decode steps append to the E4M3 pages only, so the bf16 pages a continuation prefill would attend over lack
+ * those tokens; clear the cache first.  The three-launch decode (AHA_DECODE_FUSED=0) has no KV8 kernel: a flagged model runs the fused form
+ * regardless.  AHA_ATTN_TRACE records nothing on such a model (one line on stderr says so).  aha_hip_generate_batch* behave as on an
+ * unflagged KV8 model. */
+#define AHA_KV_SINGLE 1u
+int aha_hip_model_set_kv_format_with(aha_model* m, int32_t format, uint32_t flags);
+uint32_t aha_hip_model_kv_flags(const aha_model* m);
 /* Test hook: on = 0 makes a quantised model's batched decode run the bf16 matvec on W' instead of the FP8 one (the same bits); on = 1
  * (the default) restores it.  It holds for either format: on = 0 sends an MXFP4 model to the bf16 kernel on W' as well. */
 int aha_hip_debug_fp8_rows(aha_model* m, int on);
@@ -1106,6 +1124,15 @@ int aha_hip_quantize_kv_pages(const uint64_t* src_page_ptrs, const uint64_t* dst
 int aha_hip_attn_decode_batch_kv8(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
                                   const int32_t* page0, const int32_t* kv_len, int32_t rows, int32_t nh, int32_t kvh, float eps, float scale,
                                   void* o, int32_t form, void* stream);
+/* aha_hip_attn_decode_fused_kv8: aha_hip_debug_attn_decode_fused over KV8 pages -- one single-sequence decode step of the attention block
+ * (q/k norm + RoPE, quantise and append the new token at slot kv_len - 1, attend over the kv_len tokens, merge the splits) with the split
+ * count of the model's decode step.  lin_step != 0: the linear kernel, page i at lin_page0 + i * lin_step (bytes; page_ptrs is ignored and
+ * may be NULL); lin_step == 0: the table kernel over page_ptrs (device table of ceil(kv_len / 64) KV8 page addresses).
+ * AHA_ERR_INVALID for a null pointer, kv_len < 1, nh % kvh != 0, a group size above 16, or neither a table nor a progression.
+ * Synchronises the stream. */
+int aha_hip_attn_decode_fused_kv8(const void* qkv_row, const void* q_norm_w, const void* k_norm_w, const float* rope_row, const uint64_t* page_ptrs,
+                                  uint64_t lin_page0, int64_t lin_step, int32_t kv_len, int32_t nh, int32_t kvh, float eps, float scale,
+                                  void* o, void* stream);
 /* Test entry: the accept step of draft-and-verify decoding.  argmax (device, rows uint32): the step's pick of every row; row_tok (HOST,
  * rows): every row's input token (a draft row's is its draft); seq_tab (HOST): per sequence {first row, drafts} (layout 0: a sequence's
  * rows are consecutive, generate_batch_spec's step) or {own row, first draft row, drafts} (layout 1: the engine's step).  out (device,

@@ -72,6 +72,7 @@ pub mod sys {
     pub const AHA_WQ_MXFP4_E2M1: i32 = 2;
     pub const AHA_WQ_LM_HEAD: u32 = 1;
     pub const AHA_WQ_PREFILL: u32 = 2;
+    pub const AHA_KV_SINGLE: u32 = 1;
 
     /// `aha_sampling_params`: the Options of `GenerationContext::new` (common/generate.rs:21-53); same fields, same order as the
     /// ctypes mirror `aha_amd._lib.SamplingParams`.
@@ -647,6 +648,8 @@ pub mod sys {
         pub fn aha_hip_model_weight_format(m: *const AhaModel, format: *mut i32, flags: *mut u32) -> i32;
         pub fn aha_hip_model_set_kv_format(m: *mut AhaModel, format: i32) -> i32;
         pub fn aha_hip_model_kv_format(m: *const AhaModel) -> i32;
+        pub fn aha_hip_model_set_kv_format_with(m: *mut AhaModel, format: i32, flags: u32) -> i32;
+        pub fn aha_hip_model_kv_flags(m: *const AhaModel) -> u32;
         pub fn aha_hip_debug_fp8_rows(m: *mut AhaModel, on: i32) -> i32;
         pub fn aha_hip_debug_fp8_single(m: *mut AhaModel, on: i32) -> i32;
         pub fn aha_hip_debug_rows_wide(m: *mut AhaModel, on: i32) -> i32;
@@ -1111,6 +1114,19 @@ impl Model {
     /// unsupported), `false` the default bf16 one.  Only while the cache is empty and no engine is open.
     pub fn set_kv_format(&mut self, e4m3: bool) -> Result<(), Error> {
         check(unsafe { sys::aha_hip_model_set_kv_format(self.model, e4m3 as i32) })
+    }
+
+    /// `set_kv_format` with the opt-in `single` flag (`AHA_KV_SINGLE`, E4M3 only): `forward_step` and `decode_greedy` read and append
+    /// the E4M3 pages too, `forward_initial` converts the prompt's pages behind its last pass.  The engine and the KV hand-back still
+    /// fail as unsupported, and so does `forward_initial` onto a non-empty cache: clear the cache first.
+    pub fn set_kv_format_with(&mut self, e4m3: bool, single: bool) -> Result<(), Error> {
+        let flags = if single { sys::AHA_KV_SINGLE } else { 0 };
+        check(unsafe { sys::aha_hip_model_set_kv_format_with(self.model, e4m3 as i32, flags) })
+    }
+
+    /// Was the KV format set with the `single` flag (`aha_hip_model_kv_flags`)?
+    pub fn kv_format_single(&self) -> bool {
+        unsafe { sys::aha_hip_model_kv_flags(self.model) & sys::AHA_KV_SINGLE != 0 }
     }
 
     /// Does the batched decode read an E4M3 KV cache (`aha_hip_model_kv_format`)?

@@ -9,6 +9,13 @@
       the op-level launches alone on random pages (32 q heads, 8 kv heads): ops.attn_decode_batch over bf16 pages, ops.attn_decode_batch_kv8
       over their conversion, ops.quantize_kv_pages -- each call once per repetition, for `rocprofv3 --kernel-trace --stats -- python ...`
       to time the kernels (the entries allocate and synchronise per call, so host-side timing of them says nothing about the kernels).
+  python scripts/bench_kv_fp8.py --single --size 8b --kv e4m3 --weights mxfp4 --ctxs 512,4096,32768
+      the SINGLE-sequence decode (results in profiles/kv_fp8_single.md): ONE (size, cache, weights) in THIS process
+      (run bf16 and e4m3 in fresh processes, alternated, at least three each), and per context one JSON line: forward_initial of `ctx`
+      random tokens, a warm-up decode_greedy, the wall time per step of decode_greedy over --new steps (the call ends in a stream
+      synchronise), then a few steps with the model's event profiler on for the attention launch.  --kv e4m3 sets the cache with
+      set_kv_format_with("e4m3", single=True).  AHA_ATTN_PAGES_PER_BLOCK in the environment changes the split rule under test.  Under
+      `rocprofv3 --kernel-trace --stats -- python ...` the kernels to compare are attn_decode_fused_kernel and attn_decode_fused_kv8_kernel.
 """
 import argparse
 import json
@@ -51,6 +58,37 @@ def run_model(a):
     m.close()
 
 
+def run_single(a):
+    import os
+    from aha_amd import configs
+    from aha_amd.model import HipInferenceModel
+    from aha_amd.weights import qwen3_text_weights
+    cfg = configs.qwen3_0_6b() if a.size == "0.6b" else configs.qwen3vl_8b_text()
+    m = HipInferenceModel(cfg, qwen3_text_weights(cfg, seed=0))
+    if a.weights != "bf16":
+        m.quantize_weights(a.weights)
+    if a.kv == "e4m3":
+        m.set_kv_format_with("e4m3", single=True)
+    cls = "attn_decode_kv8" if a.kv == "e4m3" else "attn_decode"
+    ids = [int(x) for x in np.random.default_rng(1).integers(0, cfg.vocab_size, size=max(a.ctxs))]
+    for ctx in a.ctxs:
+        m.clear_cache()
+        _, tok = m.forward_initial(ids[:ctx], 0, want_logits=False)
+        warm = m.decode_greedy(tok, ctx, 8)
+        t0 = time.perf_counter()
+        got = m.decode_greedy(warm[-1], ctx + len(warm), a.new)
+        t1 = time.perf_counter()
+        m.set_profiling(True)   # (clears the accumulators)
+        m.decode_greedy(got[-1], ctx + len(warm) + len(got), 8)
+        m.set_profiling(False)
+        attn = m.get_profile(cls)
+        print(json.dumps(dict(size=a.size, kv=a.kv, weights=a.weights, ctx=ctx, steps=len(got), pages_per_block=os.environ.get("AHA_ATTN_PAGES_PER_BLOCK", "4"),
+                              form=m.debug_attn_decode_form(), ms_per_step=(t1 - t0) * 1e3 / max(len(got), 1),
+                              attn_us_per_launch=attn["ms"] * 1e3 / max(attn["launches"], 1),
+                              attn_gb_per_s=attn["bytes"] / max(attn["ms"], 1e-9) / 1e6)), flush=True)
+    m.close()
+
+
 def run_launch(a):
     from aha_amd import ops
     nh, kvh, D, R = 32, 8, 128, a.seqs
@@ -88,5 +126,11 @@ if __name__ == "__main__":
     for p in (pm, pl):
         p.add_argument("--seqs", type=int, default=16)
         p.add_argument("--ctx", type=int, default=512)
-    args = ap.parse_args()
-    run_model(args) if args.mode == "model" else run_launch(args)
+    ps = sub.add_parser("single")
+    ps.add_argument("--size", choices=["0.6b", "8b"], default="0.6b")
+    ps.add_argument("--kv", choices=["bf16", "e4m3"], default="bf16")
+    ps.add_argument("--weights", choices=["bf16", "mxfp4"], default="bf16")
+    ps.add_argument("--ctxs", type=lambda v: [int(x) for x in v.split(",")], default=[512, 4096, 32768])
+    ps.add_argument("--new", type=int, default=64)
+    args = ap.parse_args(["single" if x == "--single" else x for x in sys.argv[1:]])
+    {"model": run_model, "launch": run_launch, "single": run_single}[args.mode](args)
