@@ -285,6 +285,8 @@ SIGNATURES = {
     "aha_hip_debug_fp8_rows": (C.c_int, [_P, C.c_int]),
     "aha_hip_debug_fp8_single": (C.c_int, [_P, C.c_int]),
     "aha_hip_debug_rows_wide": (C.c_int, [_P, C.c_int]),
+    "aha_hip_debug_rows_group": (C.c_int, [_P, C.c_int]),
+    "aha_hip_attn_decode_group": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "aha_hip_debug_pk13_single": (C.c_int, [_P, C.c_int]),
     "aha_hip_pk13_status": (C.c_int, [_P, C.c_char_p, C.c_size_t]),
     "aha_hip_pack_pk13": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _P]),

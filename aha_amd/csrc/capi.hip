@@ -1188,6 +1188,19 @@ int aha_hip_debug_rows_wide(aha_model* m, int on) {
   return AHA_OK;
 }
 
+int aha_hip_debug_rows_group(aha_model* m, int on) {
+  if (!m) {
+    set_error("debug_rows_group: null model");
+    return AHA_ERR_INVALID;
+  }
+  if (on < 0 || on > 2) {
+    set_error("debug_rows_group: on must be 0 (row by row), 1 (by plan) or 2 (wherever a step has drafts)");
+    return AHA_ERR_INVALID;
+  }
+  m->rows_group = on;
+  return AHA_OK;
+}
+
 int aha_hip_debug_pk13_single(aha_model* m, int on) {
   if (!m) {
     set_error("debug_pk13_single: null model");
@@ -1877,6 +1890,44 @@ int aha_hip_attn_decode_batch_kv8(const void* qkv, const void* q_norm_w, const v
   API_GUARD_BEGIN
   return attn_decode_rows_entry("attn_decode_batch_kv8: ", true, qkv, q_norm_w, k_norm_w, rope, page_ptrs, page0, kv_len, rows, nh, kvh, eps,
                                 scale, o, form, stream);
+  API_GUARD_END
+}
+
+int aha_hip_attn_decode_group(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
+                              const int32_t* page0, const int32_t* kv_len, int32_t rows, int32_t nh, int32_t kvh, float eps, float scale, void* o,
+                              void* stream) {
+  API_GUARD_BEGIN
+  auto bad = [&](const std::string& why) {
+    set_error("attn_decode_group: " + why);
+    return AHA_ERR_INVALID;
+  };
+  if (!qkv || !q_norm_w || !k_norm_w || !rope || !page_ptrs || !page0 || !kv_len || !o) return bad("null pointer");
+  if (rows < 1 || rows > 65535 || !attn_batch_geometry_ok(nh, kvh)) return bad("bad arguments (rows 1 .. 65535, nh % kvh == 0, group size <= 16)");
+  for (int r = 0; r < rows; ++r)
+    if (kv_len[r] < 1 || page0[r] < 0) return bad("row " + std::to_string(r) + " needs kv_len >= 1 and page0 >= 0");
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<int32_t> tab, groups;
+  int max_split = attn_batch_row_table(page0, kv_len, rows, nh / kvh, tab);
+  AttnDecodeBatchArgs b{};
+  b.nh = nh; b.kvh = kvh; b.max_nsplit = max_split;
+  if (!attn_group_shape_ok(b, rows)) return bad("rows * splits * nh * 512 bytes of partials and rows * (nh + 2 kvh) * 128 must stay below 2^31");
+  const int n_groups = attn_group_plan(tab.data(), rows, nh / kvh, 2, groups, &max_split, nullptr);
+  tab.insert(tab.end(), groups.begin(), groups.end());   // one upload: the rows, then the groups
+  DevBuf d_tab, po, pml, ctr;
+  if (int rc = d_tab.upload(tab.data(), tab.size() * 4)) return rc;
+  AHA_HIP_CHECK(hipMalloc(&po.p, (size_t)rows * max_split * nh * 128 * 4));
+  AHA_HIP_CHECK(hipMalloc(&pml.p, (size_t)rows * max_split * nh * 2 * 4));
+  AHA_HIP_CHECK(hipMalloc(&ctr.p, (size_t)rows * kvh * 32 * 4));
+  AHA_HIP_CHECK(hipMemsetAsync(ctr.p, 0, (size_t)rows * kvh * 32 * 4, st));
+  b.qkv = qkv; b.q_norm_w = q_norm_w; b.k_norm_w = k_norm_w; b.rope = rope; b.page_ptrs = page_ptrs; b.layer_off = 0;
+  b.row_tab = (const int32_t*)d_tab.p; b.o = o; b.ctr_step = 1; b.eps = eps; b.scale = scale;
+  b.part_o = (float*)po.p; b.part_ml = (float*)pml.p; b.head_ctr = (unsigned*)ctr.p;
+  launch_kv_append_rows(b, rows, st);
+  launch_attn_decode_group(b, b.row_tab + (size_t)rows * GEN_ROW_WORDS, n_groups, rows, max_split, st);
+  hipError_t err = hipGetLastError();
+  hipStreamSynchronize(st);
+  AHA_HIP_CHECK(err);
+  return AHA_OK;
   API_GUARD_END
 }
 

@@ -488,6 +488,27 @@ void launch_attn_decode_batch(const AttnDecodeBatchArgs& a, int rows, int max_ns
 // (reads qkv, k_norm_w, rope, page_ptrs, layer_off, row_tab, nh, kvh, eps of the batch arguments)
 void launch_kv_append_rows(const AttnDecodeBatchArgs& a, int rows, hipStream_t st);
 
+// ---- the rows of one sequence in one pass over its pages (kernels_attn_group.hip, attn_group_body.h) -------------------------------------
+// Group table of a draft-and-verify step, ATTN_GROUP_WORDS int32 per group: 1 .. attn_group_rows_cap(g) rows of one sequence (equal
+// GEN_ROW_PAGE0) at consecutive GEN_ROW_KVLEN, ascending, with the same GEN_ROW_NSPLIT.
+constexpr int ATTN_GROUP_WORDS = 40;
+constexpr int ATTN_GROUP_COUNT = 0;     // rows of the group
+constexpr int ATTN_GROUP_NSPLIT = 1;    // their common split count
+constexpr int ATTN_GROUP_PAGE0 = 2;     // their sequence's first logical page
+constexpr int ATTN_GROUP_KVLEN = 3;     // GEN_ROW_KVLEN of the first row; group row j has j more
+constexpr int ATTN_GROUP_CTR = 4;       // GEN_ROW_CTR of the first row: the group arrives on that row's counters
+constexpr int ATTN_GROUP_ROW0 = 8;      // [16] the rows' indices in the row table (= in qkv, rope, o, part_o, part_ml)
+constexpr int ATTN_GROUP_CTRROW0 = 24;  // [16] the rows' GEN_ROW_CTRROW; the last arriver brings rows 1 .. to where their own launches would
+constexpr int ATTN_GROUP_PLAN_MIN_KV = 8192;   // mode 1: the shortest "longest row of the step" at which the group launch measured faster
+int attn_group_rows_cap(int g);
+// row_tab: the step's table on the HOST.  mode 0: no groups, 1: by plan, 2: every row in a group (lone rows: groups of one).  -> groups
+int attn_group_plan(const int32_t* row_tab, int rows, int g, int mode, std::vector<int32_t>& out, int* max_split, double* kv_tokens);
+// the kernel addresses the rows' partials through one 32-bit buffer offset: rows * max_nsplit * nh * 512 bytes must stay below 2 GiB
+bool attn_group_shape_ok(const AttnDecodeBatchArgs& a, int rows);
+// a: launch_attn_decode_batch's arguments with append = false (a.row_tab is not read); group_tab: `groups` entries on the device; rows: the
+// rows part_o / part_ml hold.  Every row's output bits are those of launch_attn_decode_batch(append = false) on the same inputs.
+void launch_attn_decode_group(const AttnDecodeBatchArgs& a, const int32_t* group_tab, int groups, int rows, int max_nsplit_groups, hipStream_t st);
+
 // ---- KV8: the decode attention over an E4M3 KV cache (kernels_attn_kv8.hip; page layout: common.h "KV8 page layout") -----------------
 // One (token, kv head) vector of 128 dims is one block: 128 OCP E4M3 bytes and one E8M0 scale byte, K and V each; exponent and rounding
 // are mxfp8.h's with the maximum taken over the 128 dims, +-Inf and magnitudes from MX_BF16_ABS_LIMIT on saturate to +-448 * 2^120 and

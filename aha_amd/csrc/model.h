@@ -102,6 +102,9 @@ struct aha_model {
                              // 1 = the FP8 kernel where the plan takes the shape (gemv_mxfp8_by_plan), 2 = wherever a copy exists; MXFP8 models only
   int rows_wide = 1;         // aha_hip_debug_rows_wide, the batched matvec of a step of more than 32 rows (gemv_rows_groups): 0 = groups of 32,
                              // 1 = passes of gemv_rows_wide_plan's width, 2 = the wide kernel wherever rows > 32; the bits are the same
+  int rows_group = 0;        // aha_hip_debug_rows_group, the attention of a draft-and-verify step (gen_plan_groups): 0 = every row streams its
+                             // sequence's pages itself (attn_decode_rows_kernel), 1 = attn_decode_group_kernel by attn_group_plan's plan,
+                             // 2 = wherever the step has drafts; the bits are the same
   // Exact 13-bit copies of the four layer matrices and lm_head, made when the model is created (model_pack_weights; a bf16 model only:
   // aha_hip_model_quantize_weights frees them).  pk13_single (aha_hip_debug_pk13_single): 0 = the bf16 kernel, 1 = the packed kernel where
   // the plan takes the shape (gemv_pk13_by_plan), 2 = wherever a copy exists

@@ -2906,6 +2906,12 @@ struct GenCall {
   int32_t* h_rowtab = nullptr;   // pinned
   uint32_t* h_tok = nullptr;     // pinned: a step's tokens
   uint32_t *spec_out = nullptr, *h_spec_out = nullptr;   // draft-and-verify: (n, SPEC_OUT_WORDS) emitted tokens per sequence, device / pinned
+  // draft-and-verify with aha_hip_debug_rows_group on (gen_plan_groups): the step's group table sits group_off words into the row table's
+  // upload; n_groups == 0: the step attends row by row
+  int n_groups = 0, group_max_split = 1;
+  size_t group_off = 0;
+  double group_kv_tokens = 0;   // every group's longest row (the pages are read once per group)
+  std::vector<int32_t> groups;
   // the caller's outputs: per sequence max_new entries of tokens_out (n_out of them written) and of step_logits_out (V floats each)
   size_t max_new = 0;
   uint32_t* tokens_out = nullptr;
@@ -3063,7 +3069,7 @@ static int gen_call_alloc(aha_model* m, DevBufs& bufs, GenCall& gc, size_t max_p
   // n: the rows a step can have (the row table also holds one SPEC_SEQ_WORDS entry per sequence behind the rows)
   const int n = std::max(gc.n, gc.rows), H = gc.H, V = gc.V, I = c.intermediate_size, nh = c.num_attention_heads, kvh = c.num_key_value_heads;
   const int nq = nh * 128, nkv = kvh * 128;
-  const size_t tab_words = (size_t)n * GEN_ROW_WORDS + (size_t)gc.n * gc.seq_words;
+  const size_t tab_words = (size_t)n * GEN_ROW_WORDS + (size_t)gc.n * gc.seq_words + (size_t)n * ATTN_GROUP_WORDS;   // rows, sequences, groups
   size_t ws = 0;
   const int shapes[5][2] = {{nq + 2 * nkv, H}, {H, nq}, {2 * I, H}, {H, I}, {V, H}};
   for (auto& sh : shapes) ws = std::max(ws, gemv_rows_ws_floats(std::min(n, GEMV_ROWS_WIDE_MAX), sh[0], sh[1]));   // the largest pass
@@ -3395,6 +3401,23 @@ static int gen_finish_step(aha_model* m, GenCall& gc, GenChoice& ch, const std::
   return lp_finish();
 }
 
+// A draft-and-verify step's groups (kernels.h ATTN_GROUP_*, attn_group_plan) from the R rows of the pinned row table, written behind the
+// `words` words the step uploads anyway.  -> the words to upload.  No groups (the step then attends row by row) when the step has no
+// drafts, with aha_hip_debug_rows_group at 0, where its plan says so, and on a KV8 model.
+static size_t gen_plan_groups(const aha_model* m, GenCall& gc, int R, size_t words, bool drafts) {
+  const aha_model_desc& c = m->desc;
+  gc.n_groups = 0;
+  if (!drafts || m->rows_group == 0 || m->kv_format == AHA_KV_E4M3) return words;
+  AttnDecodeBatchArgs b{};
+  b.nh = c.num_attention_heads, b.kvh = c.num_key_value_heads, b.max_nsplit = gc.max_nsplit;
+  if (!attn_group_shape_ok(b, R)) return words;
+  gc.n_groups = attn_group_plan(gc.h_rowtab, R, b.nh / b.kvh, m->rows_group, gc.groups, &gc.group_max_split, &gc.group_kv_tokens);
+  if (gc.n_groups == 0) return words;
+  gc.group_off = words;
+  memcpy(gc.h_rowtab + words, gc.groups.data(), gc.groups.size() * 4);
+  return words + gc.groups.size();
+}
+
 // One decode step's device work over the R rows of the uploaded row table gc.rowtab: the tokens tok_in embedded (with their rope rows),
 // every layer, then the head -> tok_out.  kv_tokens: the rows' cache lengths summed (the profile's bytes); max_split: their largest split.
 // split_append (draft-and-verify steps): rows of one sequence at consecutive positions -- every row's K/V is appended by a launch of its
@@ -3433,10 +3456,15 @@ static void gen_decode_step(aha_model* m, GenCall& gc, int R, int max_split, dou
         ProfScope ps(m, kv8 ? "kv_append_rows_kv8" : "kv_append_rows", (double)R * nkv * 2 * (kv8 ? 3 : 4), 0);
         (kv8 ? launch_kv_append_rows_kv8 : launch_kv_append_rows)(b, R, st);
       }
-      // bytes per cached token: K and V of every kv head, 2 bytes an element, or 1 byte and a scale byte per 128
-      ProfScope ps(m, kv8 ? "attn_decode_batch_kv8" : "attn_decode_batch",
-                   kv_tokens * 2 * (kv8 ? nkv + kvh : nkv * 2) + (double)R * (nq + 2 * nkv) * 2, 4.0 * kv_tokens * nq);
-      (kv8 ? launch_attn_decode_batch_kv8 : launch_attn_decode_batch)(b, R, max_split, st, !split_append);
+      if (split_append && gc.n_groups > 0) {   // the rows of a sequence in one pass over its pages: every group's KV once
+        ProfScope ps(m, "attn_decode_group", gc.group_kv_tokens * 2 * nkv * 2 + (double)R * (nq + 2 * nkv) * 2, 4.0 * kv_tokens * nq);
+        launch_attn_decode_group(b, gc.rowtab + gc.group_off, gc.n_groups, R, gc.group_max_split, st);
+      } else {
+        // bytes per cached token: K and V of every kv head, 2 bytes an element, or 1 byte and a scale byte per 128
+        ProfScope ps(m, kv8 ? "attn_decode_batch_kv8" : "attn_decode_batch",
+                     kv_tokens * 2 * (kv8 ? nkv + kvh : nkv * 2) + (double)R * (nq + 2 * nkv) * 2, 4.0 * kv_tokens * nq);
+        (kv8 ? launch_attn_decode_batch_kv8 : launch_attn_decode_batch)(b, R, max_split, st, !split_append);
+      }
     }
     {   // x = x + attn Wo^T                                    (modules.rs:577, qwen3/model.rs:81)
       GemvRowsArgs a{};
@@ -3524,7 +3552,7 @@ static int spec_decode_loop(aha_model* m, GenCall& gc, const GenOptions& sp, con
     }
     int32_t* h_seq = gc.h_rowtab + (size_t)R * GEN_ROW_WORDS;
     for (int a = 0; a < nact; ++a) h_seq[a * SPEC_SEQ_WORDS + SPEC_SEQ_ROW0] = row0[a], h_seq[a * SPEC_SEQ_WORDS + SPEC_SEQ_NDRAFT] = ndraft[a];
-    const size_t words = (size_t)R * GEN_ROW_WORDS + (size_t)nact * SPEC_SEQ_WORDS;
+    const size_t words = gen_plan_groups(m, gc, R, (size_t)R * GEN_ROW_WORDS + (size_t)nact * SPEC_SEQ_WORDS, n_drafts > 0);
     AHA_HIP_CHECK(hipMemcpyAsync(gc.rowtab, gc.h_rowtab, words * 4, hipMemcpyHostToDevice, st));
     // a step without drafts is generate_batch's step: one attention launch per layer, the fused append
     gen_decode_step(m, gc, R, sr.max_split, sr.kv_tokens, reinterpret_cast<const uint32_t*>(gc.rowtab), gc.tok[0], n_drafts > 0);
@@ -4407,7 +4435,8 @@ int engine_step(aha_engine* e, aha_engine_event* ev, size_t cap, size_t* n_ev, f
       }
     }
     const int RT = R + D;
-    AHA_HIP_CHECK(hipMemcpyAsync(gc.rowtab, gc.h_rowtab, ((size_t)RT * GEN_ROW_WORDS + (size_t)n_seq * ENG_SEQ_WORDS) * 4, hipMemcpyHostToDevice, st));
+    const size_t tab_words = gen_plan_groups(m, gc, RT, (size_t)RT * GEN_ROW_WORDS + (size_t)n_seq * ENG_SEQ_WORDS, staged);
+    AHA_HIP_CHECK(hipMemcpyAsync(gc.rowtab, gc.h_rowtab, tab_words * 4, hipMemcpyHostToDevice, st));
     AHA_HIP_CHECK(hipMemcpyAsync(e->d_tok_in, e->h_tok_in, (size_t)RT * 4, hipMemcpyHostToDevice, st));
     // a step without drafts is the step it was before: one attention launch per layer, the fused append
     gen_decode_step(m, gc, RT, sr.max_split, sr.kv_tokens, e->d_tok_in, gc.tok[1], staged);

@@ -680,6 +680,14 @@ class HipInferenceModel:
         same bits in all three.  Profile classes of the wide launches: "gemv_rows_wide", "gemv_rows_wide_fp8", "gemv_rows_wide_fp4"."""
         check(lib().aha_hip_debug_rows_wide(self.handle, int(on)))
 
+    def debug_rows_group(self, on=True) -> None:
+        """The attention of a draft-and-verify step on a bf16 KV cache.  False / 0 (the default): every row streams its sequence's pages
+        itself; 2: the rows of a sequence share one pass over its pages (attn_decode_group_kernel, ops.attn_decode_group has the grouping
+        rule) in every step with drafts; True / 1: the same by plan (not at nh / kvh = 16, and only in steps whose longest row has 8192 cached
+        tokens or more: profiles/attn_group.md).  The same bits in all three.  Profile class of
+        the group launches: "attn_decode_group"."""
+        check(lib().aha_hip_debug_rows_group(self.handle, int(on)))
+
     def debug_pk13_single(self, on=True) -> None:
         """The switch of the single-sequence decode matvec for the exact 13-bit weight copies made when the model was created.  True / 1 (the
         default): the packed kernel on the matrices whose shape its plan takes; 2: on every matrix with a copy; False / 0: the bf16 kernel.

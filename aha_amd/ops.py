@@ -753,6 +753,22 @@ def debug_attn_decode_rows(qkv: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: 
     return o
 
 
+def attn_decode_group(qkv: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: torch.Tensor, rope: torch.Tensor, page_ptrs: torch.Tensor,
+                      page0, kv_len, nh: int, kvh: int, eps: float, scale: float) -> torch.Tensor:
+    """Several query rows of one sequence over one cache (aha_hip_attn_decode_group): debug_attn_decode_rows' arguments without form.  The
+    KV append of every row, then attn_decode_group_kernel: rows with the same page0, kv_len ascending by one and the same split count share
+    one pass over the sequence's pages (up to min(16, 4 * (16 // (nh // kvh))) rows a group; the rest are groups of one).  -> (R, nh*128)
+    bf16, every row the bits of debug_attn_decode_rows form 1."""
+    _chk(qkv, q_norm_w, k_norm_w, rope, page_ptrs)
+    R = qkv.shape[0]
+    p0 = np.ascontiguousarray(np.asarray(page0, dtype=np.int32).reshape(R))
+    kl = np.ascontiguousarray(np.asarray(kv_len, dtype=np.int32).reshape(R))
+    o = torch.empty(R, nh * 128, dtype=torch.bfloat16, device=qkv.device)
+    check(lib().aha_hip_attn_decode_group(_ptr(qkv), _ptr(q_norm_w), _ptr(k_norm_w), _ptr(rope), _ptr(page_ptrs), p0.ctypes.data,
+                                          kl.ctypes.data, R, nh, kvh, eps, scale, _ptr(o), _stream()))
+    return o
+
+
 def kv8_page_bytes(kvh: int) -> int:
     """Host only: bytes of one layer's KV8 page (E4M3 KV cache; include/aha_hip.h "KV8") of kvh kv heads: 16512 * kvh."""
     return int(lib().aha_hip_kv8_page_bytes(int(kvh)))

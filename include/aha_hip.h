@@ -847,6 +847,16 @@ int aha_hip_debug_fp4_single(aha_model* m, int on);
  * classes of the wide launches: gemv_rows_wide, gemv_rows_wide_fp8, gemv_rows_wide_fp4.  Reads no environment variable.
  * AHA_ERR_INVALID: a null model or another value. */
 int aha_hip_debug_rows_wide(aha_model* m, int on);
+/* The attention of a draft-and-verify decode step (aha_hip_generate_batch_spec, aha_hip_engine_submit_spec) on a bf16 KV cache.  on = 0
+ * (the default): every row streams its sequence's KV pages itself (attn_decode_rows_kernel, one block per (kv head, split, row)).
+ * 2: attn_decode_group_kernel -- the rows of a sequence, up to 16 at consecutive cache lengths and with the same split count, share one
+ * pass over the pages (aha_hip_attn_decode_group has the grouping rule; rows without a neighbour ride the same launch as groups of one)
+ * -- in every step that has drafts.  1: the same by plan (profiles/attn_group.md): not where nh / kvh = 16, where no MFMA column is
+ * shared, and only in steps whose longest row has 8192 cached tokens or more -- at 512 .. 640 tokens the group launch measured 4 .. 17 %
+ * slower end to end, at 8192 1.4 .. 1.7x faster; the lengths between were not measured.  The bits are the same in all three.  Profile class of the group launches: attn_decode_group, whose bytes
+ * count every group's KV once.  A step without drafts and a KV8 model launch what they launch at 0.  AHA_ERR_INVALID: a null model or
+ * another value. */
+int aha_hip_debug_rows_group(aha_model* m, int on);
 /* Exact 13-bit weight copies.  When a model is created unsharded, each of the four layer matrices and lm_head gets a copy that holds
  * every bf16 weight exactly in 13 bits (aha_hip_pack_pk13 has the format) if the matrix has at least 2^24 elements, K is a multiple of
  * 4096, every weight is finite, at most 16 rows hold a weight below the format's window (those rows are then read from the bf16 matrix,
@@ -1106,6 +1116,16 @@ int aha_hip_debug_attn_decode_fused(const void* qkv, const void* q_norm_w, const
 int aha_hip_debug_attn_decode_rows(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
                                    const int32_t* page0, const int32_t* kv_len, int32_t rows, int32_t nh, int32_t kvh, float eps, float scale,
                                    void* o, int32_t form, void* stream);
+/* aha_hip_attn_decode_group: several query rows of ONE sequence over one cache.  aha_hip_debug_attn_decode_rows' arguments without form:
+ * the KV append of every row (kv_append_rows_kernel), then attn_decode_group_kernel on the groups of the rows -- in call order, a row
+ * joins the group of the row with the same page0 and kv_len one less if that row has the same split count and its group has room
+ * (min(16, 4 * (16 / (nh / kvh))) rows); any other row starts a group.  A group's rows share one pass over the sequence's pages; every
+ * row's output is, bit for bit, that of aha_hip_debug_attn_decode_rows form 1.  AHA_ERR_INVALID ("attn_decode_group: ..."), before any
+ * device work: a null pointer, rows outside 1 .. 65535, nh % kvh != 0 or nh / kvh > 16, a row with kv_len < 1 or page0 < 0, or rows *
+ * splits * nh * 512 bytes of split partials (or rows * (nh + 2 kvh) * 128 qkv elements) from 2^31 on.  Synchronises the stream. */
+int aha_hip_attn_decode_group(const void* qkv, const void* q_norm_w, const void* k_norm_w, const float* rope, const uint64_t* page_ptrs,
+                              const int32_t* page0, const int32_t* kv_len, int32_t rows, int32_t nh, int32_t kvh, float eps, float scale,
+                              void* o, void* stream);
 /* KV8: the decode attention over an E4M3 KV cache.  One (token, kv head) vector of 128 dims is one block: 128 OCP E4M3 bytes and one E8M0
  * scale byte, for K and for V.  e = the smallest integer in [-117, 120] with amax <= 448 * 2^e over the 128 dims (all zero: -117), scale
  * byte e + 127, code = e4m3fn(x / 2^e) round to nearest even; +-Inf and magnitudes of 1.9375 * 2^127 or more saturate to +-448 * 2^120,

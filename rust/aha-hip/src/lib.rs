@@ -653,6 +653,7 @@ pub mod sys {
         pub fn aha_hip_debug_fp8_rows(m: *mut AhaModel, on: i32) -> i32;
         pub fn aha_hip_debug_fp8_single(m: *mut AhaModel, on: i32) -> i32;
         pub fn aha_hip_debug_rows_wide(m: *mut AhaModel, on: i32) -> i32;
+        pub fn aha_hip_debug_rows_group(m: *mut AhaModel, on: i32) -> i32;
         pub fn aha_hip_debug_plan_gemv_mxfp8(
             n: i32,
             k: i32,

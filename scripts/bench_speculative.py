@@ -15,8 +15,11 @@ accepted, 1 = every token wrong.  Per (B, fraction, max_draft), --reps timed cal
   vs_plain          decode_tok_s over generate_batch's on the same prompts in the same process.
 One JSON object per line.  --lib PATH loads another build of libaha_hip.so (e.g. the parent commit's, for the two figures that are
 compared against it); with --plain-only only generate_batch is timed, which is all an older build can do.
+--group 0|1|2: aha_hip_debug_rows_group for the whole process (0: every draft row streams its sequence's cache itself, the default; 2: the
+rows of a sequence share one pass, attn_decode_group_kernel; 1: by plan).  One value per process: profiles/attn_group.md compares fresh
+processes, alternated.  attn_GB then counts the group launches' bytes too (every group's cache once).
     python scripts/bench_speculative.py [--only 0.6b,8b] [--batches 1,4,16] [--drafts 1,3,7,15] [--fractions 0,0.25,0.5,1.0]
-                                        [--prompt 512] [--max-new 256] [--reps 5] [--lib PATH] [--plain-only]"""
+                                        [--prompt 512] [--max-new 256] [--reps 5] [--lib PATH] [--plain-only] [--group 0]"""
 import argparse
 import json
 import os
@@ -65,7 +68,7 @@ def attn_bytes(m, fn):
     m.set_profiling(False)
     m.set_profiling(True)
     fn()
-    b = m.get_profile("attn_decode_batch")["bytes"]
+    b = m.get_profile("attn_decode_batch")["bytes"] + m.get_profile("attn_decode_group")["bytes"]
     m.set_profiling(False)
     return b
 
@@ -81,6 +84,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--lib", default="", help="another build of libaha_hip.so to load instead of the tree's")
     ap.add_argument("--plain-only", action="store_true", help="time generate_batch only")
+    ap.add_argument("--group", type=int, default=0, choices=(0, 1, 2), help="aha_hip_debug_rows_group for the process")
     a = ap.parse_args()
     from aha_amd import _lib
     if a.lib:
@@ -97,6 +101,8 @@ def main():
     N = a.max_new
     for name in a.only.split(","):
         cfg, m = model_for(name)
+        if a.group:
+            m.debug_rows_group(a.group)
         kv_tok_bytes = 2 * cfg.num_key_value_heads * 128 * 2 * cfg.num_hidden_layers   # K + V, bf16, every layer
         ps_all = prompts(max(int(b) for b in a.batches.split(",")), a.prompt, cfg.vocab_size)
         for B in (int(b) for b in a.batches.split(",")):
@@ -127,7 +133,7 @@ def main():
                     mandatory = B * st.decode_steps   # no stop tokens: every sequence is active in every step
                     draft_rows = st.rows - mandatory
                     print(json.dumps({
-                        "model": name, "B": B, "prompt": a.prompt, "max_new": N, "path": "generate_batch_spec", "corrupt": frac, "max_draft": D,
+                        "model": name, "B": B, "prompt": a.prompt, "max_new": N, "path": "generate_batch_spec", "group": a.group, "corrupt": frac, "max_draft": D,
                         "decode_tok_s": spread(tok_s), "vs_plain": round(statistics.median(tok_s) / plain_med, 3),
                         "decode_steps": st.decode_steps, "step_ms": spread([(t - t1) / max(st.decode_steps, 1) * 1e3 for t in tss]),
                         "tok_per_step": round((N - 1) / max(st.decode_steps, 1), 2),
